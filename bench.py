@@ -9,9 +9,13 @@
 A step = pack weights + forward + fused loss + backward + gradient all-reduce (N>1) + fused Adam on one
 batch of synthetic inputs already resident in HBM (data: Bernoulli ink images + rasterised random
 atoms/bonds honouring the reference tensor contract; random-init weights of the reference architecture).
-Prints ONE JSON line on rank 0 with the contract fields plus
+Prints ONE JSON line on rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step).
+A plain run does only that: set up, warm up, time --steps steps, print.  --full adds what takes runs of its own:
   roofline     -- the dominant kernel's achieved TFLOP/s (algorithmic flops / HIP-event time, measured live)
-  cpu_baseline -- the oracle (CPU restatement of the reference path) timed on this host, rank 0, N=1 only.
+  other_configs -- BASELINE.json's configs 3 and 5 and the rasteriser loop (single-GPU headline only)
+  cpu_baseline -- the oracle (CPU restatement of the reference path) timed on this host, rank 0, N=1 only
+  exposed_exchange_ms -- (N > 1) the gradient exchange backward did not hide, from three extra steps.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy; see dump_outputs().
 """
 import argparse
 import json
@@ -22,6 +26,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -193,6 +198,57 @@ def other_configs(dev, steps=20, warmup=5):
     return recs
 
 
+DUMP_MB = 60          # all arrays of one --dump-outputs together (the .npy headers fit in the rest of 64 MB)
+DUMP_SEED = 20261016  # the sample positions of an array larger than its share: a function of this seed and the array's size
+
+
+def _dump_array(t, cap_bytes):
+    """t as a numpy array of float32 (float64 for f64 and integer tensors: exact), whole when it fits in cap_bytes, else a
+    fixed sample: the elements at sorted positions drawn without replacement from (DUMP_SEED, numel), flattened"""
+    dt = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+    item = 4 if dt == torch.float32 else 8
+    if t.numel() * item > cap_bytes:
+        k = cap_bytes // item
+        idx = np.sort(np.random.default_rng([DUMP_SEED, t.numel()]).choice(t.numel(), k, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.detach().to(dt).cpu().numpy()
+
+
+def dump_outputs(a, tr, model, out_dir):
+    """What the timed path handed its caller in the last timed step, as out_dir/<name>.npy (float32 / float64, DUMP_MB in all):
+    train  -- loss (total, 8 weighted and 8 raw terms, f64), logits_<head> (the eight output maps of the step's forward; not
+              with --no-logits), params / bn_buffers (the weights after the step's Adam update, the BatchNorm running
+              statistics), meters (--metrics), targets_<head> (--raster: the maps the rasteriser drew)
+    infer  -- logits_<head> (the maps the graph stores), atom_mask, bond_mask, rho_abs, omega_mask, btype_idx (--decode),
+              atoms / bonds / bond_rho (--extract: every image's candidate lists, concatenated)
+    The inputs are seeded, so two runs with the same arguments compare output for output; an array larger than its share of
+    the budget is a fixed sample of its elements (_dump_array)."""
+    from abcnet_amd.ops import HEAD_NAMES
+    arrs = []
+    if a.mode == "train":
+        arrs.append(("loss", tr.loss.out))
+        if not a.no_logits or a.metrics:
+            arrs += [("logits_" + n, t) for n, t in zip(HEAD_NAMES, tr.eng.logits)]
+        arrs += [("params", model._flat), ("bn_buffers", model._flat_buf)]
+        if tr.metrics is not None:
+            arrs.append(("meters", tr.metrics.totals))
+        if a.raster:
+            arrs += [("targets_" + n, t) for n, t in zip(HEAD_NAMES, tr.targets)]
+    else:
+        arrs += [("logits_" + n, t) for n, t in zip(HEAD_NAMES, tr.logits) if t is not None]
+        arrs += [("atom_mask", tr.atom_mask), ("bond_mask", tr.bond_mask), ("rho_abs", tr.rho_abs), ("omega_mask", tr.omega_mask)]
+        if tr.decode:
+            arrs.append(("btype_idx", tr.btype_idx))
+        if tr.extractor is not None:
+            lists = tr.candidates()
+            for k, name in (("atoms", "atoms"), ("bonds", "bonds"), ("rho", "bond_rho")):
+                arrs.append((name, torch.cat([c[k] for c in lists])))
+    os.makedirs(out_dir, exist_ok=True)
+    cap = (DUMP_MB << 20) // len(arrs)
+    for name, t in arrs:
+        np.save(os.path.join(out_dir, name + ".npy"), _dump_array(t, cap))
+
+
 def experiment_knobs():
     """ABC_* environment variables other than this script's own hooks: switches of the library / engine that change
     WHICH kernels run.  A benchmark line measured under one is not the product's: refused unless --allow-knobs, and
@@ -256,9 +312,14 @@ def main():
                     "raw rho map, the bond types as their six-way arg max per omega bin (uint8) instead of 360 f32 planes "
                     "(InferenceRunner(decode=True)); candidate lists unchanged")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="the default single-GPU headline run also times BASELINE.json's configs 3 (unet2.py "
+    ap.add_argument("--full", action="store_true", help="after the headline, also what takes runs of its own: the instrumented eager pass (roofline, "
+                    "kernel_breakdown_ms, whole_step), other_configs (single-GPU headline), cpu_baseline (N = 1) and exposed_exchange_ms (N > 1); "
+                    "a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB: a fixed, seeded sample of a larger output; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline")
+    ap.add_argument("--no-profile", action="store_true", help="(--full) skip the instrumented pass")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) the single-GPU headline run also times BASELINE.json's configs 3 (unet2.py "
                     "train) and 5 (inference heat-map path, bf16) after the headline and reports them as other_configs; this skips them")
     ap.add_argument("--allow-knobs", action="store_true", help="run although ABC_* experiment switches are set (they are echoed)")
     a = ap.parse_args()
@@ -369,11 +430,13 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a, tr, model, a.dump_outputs)
     loss = tr.loss_value()["total"] if a.mode == "train" else float(tr.atom_mask.sum().item())
     # N > 1: how much of the gradient exchange backward did NOT hide -- three extra steps AFTER the timed region with the launch
     # stream's wait for the communication stream (GradReducer.finish) bracketed by HIP events
     exposed = None
-    if a.mode == "train" and world > 1:
+    if a.full and a.mode == "train" and world > 1:
         tr.reducer.measure_exposed = True
         for _ in range(3):
             tr.step()
@@ -444,7 +507,7 @@ def main():
                                             "fractions (algorithmic bytes/img x img/s / 8 TB/s, algorithmic flops/img x img/s / 2.5 PF)"}
     # (the instrumented pass and the CPU leg are reported beside the measurement; a failure there must not lose the line)
     try:
-        if rank == 0 and not a.no_profile:
+        if a.full and rank == 0 and not a.no_profile:
             prof = tr.profile(iters=3)
             tot = sum(r["ms"] for r in prof.values())
             dom, r = dominant_family(prof)
@@ -474,14 +537,14 @@ def main():
                                  "mfma_frac": round(flops_step / (el / a.steps) / 1e12 / MFMA_PEAK["bf16" if a.dtype == "fp8" else a.dtype], 4),
                                  "hbm_frac": round(bytes_step / (el / a.steps) / 1e9 / HBM_PEAK, 4)}
         headline = (a.mode, a.variant, a.size, a.batch, a.dtype) == ("train", "unet", 384, 16, "bf16") and not (a.metrics or a.raster or a.no_graph)
-        if rank == 0 and world == 1 and headline and not a.no_other_configs:
+        if a.full and rank == 0 and world == 1 and headline and not a.no_other_configs:
             # (the headline's objects are released first: the other configs start from the state a fresh process would give them)
             del tr, model
             import gc
             gc.collect()
             torch.cuda.empty_cache()
             out["other_configs"] = other_configs(dev)
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = (cpu_baseline if a.mode == "train" else cpu_baseline_infer)(a.size, variant=a.variant)
 
     except Exception as e:  # noqa: BLE001

@@ -28,6 +28,6 @@ find $O -name "*kernel_stats.csv" | while read f; do cp $f $O/$(echo $f | sed "s
 # keep the merge small: drop the raw traces
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete; find $O -name "*agent_info.csv" -delete
 ls -la $O
-python3 bench.py --steps 20 --warmup 3 > $O/bench_unet.json 2> $O/bench_unet.err
-python3 bench.py --variant unet2 --steps 20 --warmup 3 > $O/bench_unet2.json 2> $O/bench_unet2.err
-python3 bench.py --mode infer --steps 10 --warmup 3 > $O/bench_infer.json 2> $O/bench_infer.err
+python3 bench.py --full --steps 20 --warmup 3 > $O/bench_unet.json 2> $O/bench_unet.err
+python3 bench.py --full --variant unet2 --steps 20 --warmup 3 > $O/bench_unet2.json 2> $O/bench_unet2.err
+python3 bench.py --full --mode infer --steps 10 --warmup 3 > $O/bench_infer.json 2> $O/bench_infer.err

@@ -4,7 +4,7 @@ pat=$1; shift
 for v in "$@"; do
 cp scratch/lib_$v.so abc-net_amd/libabcnet_hip.so
 echo "== $v"
-ABC_BENCH_TOP=60 timeout -k 10 300 python bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | python -c "
+ABC_BENCH_TOP=60 timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | python -c "
 import sys,json,re
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,5 +1,5 @@
 import ctypes as C, torch, sys
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, '.')
 import abcnet_amd
 from abcnet_amd import _lib as L
 lib = L.load()

@@ -337,6 +337,40 @@ def test_bench_refuses_more_gpus_than_visible_and_experiment_knobs():
     assert r.returncode != 0 and "experiment switches" in r.stderr
 
 
+def test_bench_dump_outputs_budget_dtypes_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs (host logic, CPU tensors standing in for the Trainer's): every array float32 / float64, the files
+    within 64 MB together, a small array whole, a large one sampled at the same positions in every run"""
+    import importlib.util
+    from types import SimpleNamespace
+    import numpy as np
+    from abcnet_amd.ops import HEAD_NAMES
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    B, h = 2, 96
+    logits = [torch.randn((B, c, h, h), generator=g) for c in HEADS]
+    eng = SimpleNamespace(logits=logits)
+    tr = SimpleNamespace(loss=SimpleNamespace(out=torch.randn(17, generator=g, dtype=torch.float64)), eng=eng, metrics=None, targets=None)
+    model = SimpleNamespace(_flat=torch.randn(10_698_575, generator=g), _flat_buf=torch.randn(9472, generator=g))
+    a = SimpleNamespace(mode="train", no_logits=False, metrics=False, raster=False)
+    runs = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        bench.dump_outputs(a, tr, model, str(d))
+        runs.append({f.name: np.load(d / f.name) for f in sorted(d.iterdir())})
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    r = runs[0]
+    assert set(r) == {"loss.npy", "params.npy", "bn_buffers.npy"} | {"logits_%s.npy" % n for n in HEAD_NAMES}
+    assert all(v.dtype in (np.float32, np.float64) for v in r.values())
+    assert r["loss.npy"].dtype == np.float64 and np.array_equal(r["loss.npy"], tr.loss.out.numpy())
+    assert np.array_equal(r["bn_buffers.npy"], model._flat_buf.numpy())                    # small: whole
+    assert np.array_equal(r["logits_atom_t.npy"], logits[0].numpy())
+    big = r["params.npy"]
+    assert 0 < big.size < model._flat.numel() and np.isin(big, model._flat.numpy()).all()  # large: a sample of its elements
+    assert all(np.array_equal(r[k], runs[1][k]) for k in r)                                # at the same positions every run
+
+
 def test_rank_dropout_seeds_differ_and_rank0_keeps_the_base():
     base = 0x1234ABCD
     seeds = [D.rank_dropout_seed(base, r) for r in range(8)]

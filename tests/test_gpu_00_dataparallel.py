@@ -83,7 +83,7 @@ def rank_runs(tmp_path_factory):
     env2 = dict(os.environ)
     if ndev < WORLD:
         env2.update(ABC_BENCH_DEVICE="0", ABC_BENCH_BACKEND="gloo")
-    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        env=env2, stdout=subprocess.PIPE, timeout=1200)
     assert p.returncode == 0, "bench.py --gpus 2: exit code %d" % p.returncode
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
