@@ -101,6 +101,26 @@ class AdamDesc(C.Structure):
                 ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("grad_scale", f32)]
 
 
+class LossScaleDesc(C.Structure):
+    _fields_ = [("dlogits", vp * 8), ("n", i64 * 8), ("head_scale", vp), ("ds", vp), ("grad_out", vp)]
+
+
+ADAM_MAX_CLASSES = 32
+
+
+class AdamSeg(C.Structure):
+    _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64), ("first_chunk", i64), ("cls", i32), ("pad_", i32)]
+
+
+class AdamClass(C.Structure):
+    _fields_ = [("step_size", f32), ("bc2_sqrt", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32),
+                ("pad_", f32 * 2)]
+
+
+class AdamMultiDesc(C.Structure):
+    _fields_ = [("segs", vp), ("nseg", i32), ("nclass", i32), ("chunk_total", i64), ("cls", AdamClass * ADAM_MAX_CLASSES)]
+
+
 class NmsDesc(C.Structure):
     _fields_ = [("atom", vp), ("bond", vp), ("rho", vp), ("omega", vp), ("B", i32), ("h", i32), ("w", i32),
                 ("n_omega", i32), ("atom_mask", vp), ("bond_mask", vp), ("rho_abs", vp), ("omega_mask", vp)]
@@ -162,7 +182,7 @@ class ConvTDesc(C.Structure):
 
 _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnApplyDesc, WgradDesc, WgradReduceDesc,
             LossDesc, LossFinDesc, AdamDesc, NmsDesc, CbamChannelDesc, CbamPixDesc, CbamConv7Desc, MetricsDesc, ExtractDesc, RasterDesc,
-            HeadsFusedDesc, HeadsEpi, ConvTDesc]
+            HeadsFusedDesc, HeadsEpi, ConvTDesc, LossScaleDesc, AdamSeg, AdamClass, AdamMultiDesc]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -219,6 +239,9 @@ SYMBOLS = {
     "abc_loss_fwd_bwd": (C.c_int, [P(LossDesc), vp]),
     "abc_loss_finalize": (C.c_int, [P(LossFinDesc), vp]),
     "abc_adam_step": (C.c_int, [P(AdamDesc), vp]),
+    "abc_loss_scale_grads": (C.c_int, [P(LossScaleDesc), vp]),
+    "abc_adam_multi_chunk": (C.c_int, []),
+    "abc_adam_multi": (C.c_int, [P(AdamMultiDesc), vp]),
     "abc_nms_peaks": (C.c_int, [P(NmsDesc), vp]),
     "abc_extract_work_ints": (i64, [P(ExtractDesc)]),
     "abc_extract_work_masks": (i64, [P(ExtractDesc)]),

@@ -187,6 +187,56 @@ __global__ __launch_bounds__(1024) void loss_finalize_kernel(const abc_loss_fin_
     }
 }
 
+
+// ---- true gradients of the standalone loss op (abcnet_amd.loss): dlogits[i] *= head_scale[i] * g, ds *= g, g = *grad_out.
+// The eight maps are one virtual array of 16-byte vectors (vector k of map i at k - vfirst[i]); each thread moves
+// SC_UNROLL vectors a grid-stride apart, all loads before the stores.  The maps' scalar tails (n % 4) and ds: workgroup 0.
+constexpr int SC_UNROLL = 4;
+struct ScaleArgs {
+    abc_loss_scale_desc d;
+    int64_t vfirst[9];   // running sum of n[i] / 4
+};
+
+__global__ __launch_bounds__(256) void loss_scale_kernel(const ScaleArgs a) {
+    const double g = *a.d.grad_out;
+    const int64_t nv = a.vfirst[8];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t k0 = (int64_t)blockIdx.x * 256 + threadIdx.x; k0 < nv; k0 += stride * SC_UNROLL) {
+        f32x4 v[SC_UNROLL];
+        f32x4* at[SC_UNROLL];
+        float f[SC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SC_UNROLL; ++u) {
+            const int64_t k = k0 + u * stride;
+            at[u] = nullptr;
+            if (k < nv) {
+                int i = 0;
+#pragma unroll
+                for (int j = 1; j < 8; ++j) i += (k >= a.vfirst[j]) ? 1 : 0;
+                at[u] = (f32x4*)a.d.dlogits[i] + (k - a.vfirst[i]);
+                f[u] = (float)((double)a.d.head_scale[i] * g);
+                v[u] = *at[u];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < SC_UNROLL; ++u)
+            if (at[u]) *at[u] = v[u] * f[u];
+    }
+    if (blockIdx.x == 0) {
+        const int t = threadIdx.x;
+        if (t < 32) {
+            const int i = t >> 2, r = t & 3;   // map i, tail element r
+            const int64_t n = a.d.n[i];
+            if (r < (int)(n & 3)) {
+                float* q = a.d.dlogits[i] + (n & ~(int64_t)3) + r;
+                *q *= (float)((double)a.d.head_scale[i] * g);
+            }
+        } else if (t < 42) {
+            a.d.ds[t - 32] = (float)((double)a.d.ds[t - 32] * g);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int abc_loss_blocks(const abc_loss_desc* d) { return abc_cdiv(d->B * d->h * d->w, LPX); }
@@ -200,4 +250,21 @@ extern "C" int abc_loss_fwd_bwd(const abc_loss_desc* d, abc_stream_t stream) {
 extern "C" int abc_loss_finalize(const abc_loss_fin_desc* d, abc_stream_t stream) {
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, *d);
     return abc_check_launch("loss_finalize");
+}
+
+extern "C" int abc_loss_scale_grads(const abc_loss_scale_desc* d, abc_stream_t stream) {
+    if (!d->head_scale || !d->ds || !d->grad_out) return abc_fail(ABC_EINVAL, "loss_scale_grads: null head_scale / ds / grad_out");
+    ScaleArgs a;
+    a.d = *d;
+    a.vfirst[0] = 0;
+    for (int i = 0; i < 8; ++i) {
+        if (d->n[i] < 0 || (d->n[i] > 0 && !d->dlogits[i])) return abc_fail(ABC_EINVAL, "loss_scale_grads: null / negative map");
+        if ((uintptr_t)d->dlogits[i] & 15) return abc_fail(ABC_EINVAL, "loss_scale_grads: maps must be 16-byte aligned");
+        a.vfirst[i + 1] = a.vfirst[i] + d->n[i] / 4;
+    }
+    int64_t nb = (a.vfirst[8] + 256 * SC_UNROLL - 1) / (256 * SC_UNROLL);
+    if (nb > 2048) nb = 2048;
+    if (nb < 1) nb = 1;
+    hipLaunchKernelGGL(loss_scale_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a);
+    return abc_check_launch("loss_scale_grads");
 }

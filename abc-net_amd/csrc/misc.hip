@@ -591,6 +591,10 @@ extern "C" int abc_sizeof(int which) {
         case 19: return (int)sizeof(abc_heads_fused_desc);
         case 20: return (int)sizeof(abc_heads_epi);
         case 21: return (int)sizeof(abc_convt_desc);
+        case 22: return (int)sizeof(abc_loss_scale_desc);
+        case 23: return (int)sizeof(abc_adam_seg);
+        case 24: return (int)sizeof(abc_adam_class);
+        case 25: return (int)sizeof(abc_adam_multi_desc);
         default: return -1;
     }
 }

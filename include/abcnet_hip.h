@@ -400,6 +400,17 @@ typedef struct abc_loss_fin_desc {
     float grad_scale;                  /* multiplies the scales (1/world for the DDP gradient mean) */
 } abc_loss_fin_desc;
 int abc_loss_finalize(const abc_loss_fin_desc* d, abc_stream_t stream);
+/* The true gradients of a standalone loss op (abcnet_amd.loss): abc_loss_finalize leaves the dlogits of abc_loss_fwd_bwd
+ * unscaled and writes head i's factor weight_i/denominator_i into chan_scale; this multiplies each of the 8 maps in place by
+ * head_scale[i] x (*grad_out) and ds[0..10) by (*grad_out).  grad_out is the incoming d(out)/d(loss), read on the device (no host
+ * sync; (0.5 * loss).backward() stays correct).  One launch over all maps, 16-byte accesses: every map must be 16-byte aligned. */
+typedef struct abc_loss_scale_desc {
+    float* dlogits[8]; int64_t n[8];   /* elements of map i (B * C_i * h * w) */
+    const float* head_scale;           /* [8]: the factor of head i (abc_loss_finalize's chan_scale with chan_off[i] = i, head_c[i] = 1) */
+    float* ds;                         /* [10] */
+    const double* grad_out;            /* device scalar */
+} abc_loss_scale_desc;
+int abc_loss_scale_grads(const abc_loss_scale_desc* d, abc_stream_t stream);
 
 /* per-channel sum over batch and pixels of a planar f32 tensor [B][C][HW], times chan_scale[c]:
  * bias gradient of the heads' 1x1 convs (unet.py:70) from the NCHW dlogits */
@@ -415,6 +426,35 @@ typedef struct abc_adam_desc {
     float lr, beta1, beta2, eps, weight_decay, grad_scale;
 } abc_adam_desc;
 int abc_adam_step(const abc_adam_desc* d, abc_stream_t stream);
+
+/* torch.optim.Adam over ANY list of f32 device tensors in one launch (abcnet_amd.optim.Adam): a device table of segments
+ * (runs of elements whose p, g, m, v are each contiguous -- a whole arena is one segment) and, by value, a table of
+ * hyper-parameter classes (one per distinct (param group, step count)) with the bias corrections computed on the host.
+ * Same per-element arithmetic as abc_adam_step.  Segments may come in any order; seg.first_chunk is the running sum of
+ * ceil(n / abc_adam_multi_chunk()) over the segments before it, chunk_total the sum over all. */
+#define ABC_ADAM_MAX_CLASSES 32
+typedef struct abc_adam_seg {
+    float* p; const float* g; float* m; float* v;
+    int64_t n;
+    int64_t first_chunk;
+    int32_t cls;                       /* index into abc_adam_multi_desc.cls */
+    int32_t pad_;
+} abc_adam_seg;
+typedef struct abc_adam_class {
+    float step_size;                   /* lr / (1 - beta1^step) */
+    float bc2_sqrt;                    /* sqrt(1 - beta2^step) */
+    float beta1, beta2, eps, weight_decay;
+    float pad_[2];
+} abc_adam_class;
+typedef struct abc_adam_multi_desc {
+    const abc_adam_seg* segs;          /* device table [nseg] */
+    int32_t nseg;
+    int32_t nclass;                    /* <= ABC_ADAM_MAX_CLASSES */
+    int64_t chunk_total;
+    abc_adam_class cls[ABC_ADAM_MAX_CLASSES];
+} abc_adam_multi_desc;
+int abc_adam_multi_chunk(void);        /* elements per workgroup */
+int abc_adam_multi(const abc_adam_multi_desc* d, abc_stream_t stream);
 
 /* The heads' 1x1 convolutions (unet.py:70, out_modules[i].conv2) of ALL heads in one launch: descs[0..n) are the same
  * descriptors abc_conv_fwd would take one by one (n <= 8, same batch and map size).  which = 0: forward into the NCHW
@@ -630,7 +670,7 @@ int abc_concat_f32(const float* const* srcs, const int32_t* counts, int32_t n, f
 /* *p += inc (one thread): the per-step dropout salt */
 int abc_counter_add_u32(uint32_t* p, uint32_t inc, abc_stream_t stream);
 
-/* sizeof(descriptor #which) in declaration order (abc_act_src = 0 ... abc_nms_desc = 12, abc_cbam_channel_desc = 13, abc_cbam_pix_desc = 14, abc_cbam_conv7_desc = 15, abc_metrics_desc = 16, abc_extract_desc = 17, abc_raster_desc = 18, abc_heads_fused_desc = 19, abc_heads_epi = 20, abc_convt_desc = 21):
+/* sizeof(descriptor #which) in declaration order (abc_act_src = 0 ... abc_nms_desc = 12, abc_cbam_channel_desc = 13, abc_cbam_pix_desc = 14, abc_cbam_conv7_desc = 15, abc_metrics_desc = 16, abc_extract_desc = 17, abc_raster_desc = 18, abc_heads_fused_desc = 19, abc_heads_epi = 20, abc_convt_desc = 21, abc_loss_scale_desc = 22, abc_adam_seg = 23, abc_adam_class = 24, abc_adam_multi_desc = 25):
  * lets a foreign-language binding check its mirror structs at load time */
 int abc_sizeof(int which);
 const char* abc_last_error(void);
