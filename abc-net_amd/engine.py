@@ -196,7 +196,8 @@ class Engine:
         # one pass.  Needs the loss in the plan (so: the Trainer asks for it; a module-style forward() cannot use it), bf16,
         # the reference's eight heads and whole 128-pixel chunks; settled in _build_heads
         self.batched_heads = bool(batched_heads)
-        self.want_fused_heads = bool(fused_heads) and train and dtype == "bf16" and self.batched_heads
+        # (the fused heads pass computes the loss of train.py:95-137: only for the head list of train.py:47)
+        self.want_fused_heads = bool(fused_heads) and train and dtype == "bf16" and self.batched_heads and self.heads == arch.TRAIN_HEADS
         self.hf = None
         self.dev = device
         self.params, self.grads, self.buffers, self.counters = params, grads, buffers, counters
@@ -989,7 +990,7 @@ class Engine:
         shared = None
         if batch_fin and self.dt == L.BF16 and trunk.C == 128:
             shared = self._heads_conv1_merged(trunk, h, w)
-        fused = self.want_fused_heads and shared is not None and self.heads == [1, 14, 3, 2, 1, 360, 60, 60] and (h * w) % 128 == 0 \
+        fused = self.want_fused_heads and shared is not None and (h * w) % 128 == 0 \
             and self.B * h * w * 128 * nh < (1 << 30)
         for i, hc in enumerate(self.heads):
             p = "out_modules.%d" % i
@@ -1357,7 +1358,9 @@ class Engine:
         dyh = self.new((B, h, w, 128 * nh))
         wd_all = self.packed(9, 128 * nh, 128)
         merged = None
-        if self.dt == L.BF16 and self.batched_heads and nh <= 8:
+        # (the one act_bwd pass over 128 x nh channels takes 16 nh bf16 vectors per pixel, which must divide its 256 threads: 1, 2, 4
+        #  or 8 heads; unet.py's default six heads and other counts take the per-head passes below)
+        if self.dt == L.BF16 and self.batched_heads and nh in (1, 2, 4, 8):
             merged = self._heads_act_bwd_merged(ops, dfeat)
         one_wgrad = merged is not None and self._heads_conv1_wgrad_merged(ops, merged, dyh, taps)
         for i, rec in enumerate(self.head_recs):

@@ -34,6 +34,10 @@ class InferenceRunner:
         (:73) and, for the 360 bond-type planes, their six-way arg max per omega bin as a uint8 map (:71,112; .btype_idx);
         .logits[5] and .logits[6] are then None, the candidate lists (extract=True) are unchanged bit for bit.  1.7 GB less written
         per batch of 64 at 512 x 512"""
+        from .ops import EXTRACT_HEADS, check_nms_heads
+        check_nms_heads(model.heads, "InferenceRunner")
+        if extract and list(model.heads) != EXTRACT_HEADS:
+            raise ValueError("InferenceRunner(extract=True): the peak extractor reads heads %s, got heads %s" % (EXTRACT_HEADS, list(model.heads)))
         if not torch.cuda.is_available():
             raise L.AbcNetHipError("InferenceRunner needs an MI355X; abcnet_amd has no CPU fallback")
         self.model = model

@@ -443,6 +443,7 @@ class UNetBase(nn.Module):
 
     def nms(self, x):
         """inference prologue of img2smiles2.py:56-79: forward + peak NMS, heat-map only"""
+        from .ops import check_nms_heads, nms_peaks
+        check_nms_heads(self.heads, "model.nms")
         lg, eng = self.forward_logits(x)
-        from .ops import nms_peaks
         return nms_peaks(lg[0], lg[4], lg[6], lg[7])

@@ -8,6 +8,7 @@ import torch
 
 from . import _lib as L
 
+EXTRACT_HEADS = [1, 14, 3, 2, 1, 360, 60, 60]   # the head widths extract.hip reads (train.py:47)
 HEAD_NAMES = ["atom_t", "atom_types", "atom_charges", "atom_hs", "bond_t", "bond_types", "bond_rhos", "bond_omega"]
 
 
@@ -46,7 +47,7 @@ class FusedLoss:
             if tuple(t.shape) != tuple(e) + (eng.h, eng.w) or t.dtype != dt or not t.is_contiguous():
                 raise ValueError("target %s %s does not match the contract %s %s" % (tuple(t.shape), t.dtype, e, dt))
         if eng.heads != [1, 14, 3, 2, 1, 360, 60, 60]:
-            raise ValueError("the fused loss is defined for heads [1,14,3,2,1,360,60,60] (train.py:47)")
+            raise ValueError("the fused loss is defined for heads [1,14,3,2,1,360,60,60] (train.py:47), got heads %s" % (eng.heads,))
 
     def run(self, stream):
         L.check(self.lib.abc_loss_fwd_bwd(C.byref(self.d), stream), "loss_fwd_bwd")
@@ -174,14 +175,30 @@ class FusedMetrics:
         return out
 
 
+def check_nms_heads(heads, what):
+    """img2smiles2.py:61-79 reads heads 0 and 4 as one-plane centre maps and heads 6 and 7 as rho / omega maps of the same
+    number of bins: refuse a head list that does not have that form (the NMS kernel would read and write past its maps)"""
+    heads = list(heads)
+    if not (len(heads) == 8 and heads[0] == heads[4] == 1 and heads[6] == heads[7] >= 1):
+        raise ValueError("%s needs 8 heads with heads[0] == heads[4] == 1 and heads[6] == heads[7] (the maps of img2smiles2.py:61-79), "
+                         "got heads %s" % (what, heads))
+
+
 def nms_peaks(atom, bond, rho, omega):
     """img2smiles2.py:61-79 on the NCHW f32 head maps: (atom_mask[B,1,h,w], bond_mask[B,1,h,w],
-    |rho|[B,60,h,w], omega_mask[B,60,h,w])"""
-    lib = L.load()
-    B, n, h, w = omega.shape
+    |rho|[B,n,h,w], omega_mask[B,n,h,w]).  The kernel reads atom / bond as one plane per image and rho / omega as n planes
+    each with n = omega.shape[1]: any other shape is refused before the device is touched."""
+    shapes = [tuple(t.shape) for t in (atom, bond, rho, omega)]
+    if any(len(s) != 4 for s in shapes):
+        raise ValueError("nms_peaks wants four NCHW maps, got shapes %s" % (shapes,))
+    B, n, h, w = shapes[3]
+    if shapes[0] != (B, 1, h, w) or shapes[1] != (B, 1, h, w) or shapes[2] != (B, n, h, w) or n < 1:
+        raise ValueError("nms_peaks: atom and bond must be [B,1,h,w] and rho and omega [B,n,h,w] with the same B, h, w and n; got "
+                         "atom %s, bond %s, rho %s, omega %s" % tuple(shapes))
     for t in (atom, bond, rho, omega):
         if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
             raise L.AbcNetHipError("nms_peaks wants contiguous f32 device tensors (no CPU fallback)")
+    lib = L.load()
     am, bm, r, om = torch.empty_like(atom), torch.empty_like(bond), torch.empty_like(rho), torch.empty_like(omega)
     d = L.NmsDesc()
     d.atom, d.bond, d.rho, d.omega = atom.data_ptr(), bond.data_ptr(), rho.data_ptr(), omega.data_ptr()
@@ -199,9 +216,24 @@ class PeakExtractor:
     def __init__(self, logits, atom_mask, bond_mask, cap_atoms=512, cap_bonds=16384, btype_idx=None, rho_abs=None):
         """btype_idx / rho_abs (decode mode, InferenceRunner(decode=True)): the uint8 arg-max map of the bond-type head and the |rho| map
         the heads kernel wrote instead of the raw maps logits[5] / logits[6] (which may then be None)"""
+        # (extract.hip reads the head widths of train.py:47 -- 14 atom types, 3 charges, 2 hs, 360 bond-type planes, 60 rho and 60
+        #  omega planes -- and one-plane masks: every shape is checked here, before the device is touched)
+        if len(logits) != 8 or logits[0] is None:
+            raise ValueError("PeakExtractor wants the 8 head maps of heads %s, got %d" % (EXTRACT_HEADS, len(logits)))
+        B, _, h, w = logits[0].shape
+        for i, (t, c) in enumerate(zip(logits, EXTRACT_HEADS)):
+            if t is None and ((i == 5 and btype_idx is not None) or (i == 6 and rho_abs is not None)):
+                continue
+            if t is None or tuple(t.shape) != (B, c, h, w):
+                raise ValueError("PeakExtractor: head %d must be [%d, %d, %d, %d] (heads %s), got %s"
+                                 % (i, B, c, h, w, EXTRACT_HEADS, None if t is None else tuple(t.shape)))
+        for name, t, c in (("atom_mask", atom_mask, 1), ("bond_mask", bond_mask, 1), ("rho_abs", rho_abs, 60)):
+            if t is not None and tuple(t.shape) != (B, c, h, w):
+                raise ValueError("PeakExtractor: %s must be [%d, %d, %d, %d], got %s" % (name, B, c, h, w, tuple(t.shape)))
+        if btype_idx is not None and tuple(btype_idx.shape) != (B, 60, h, w):
+            raise ValueError("PeakExtractor: btype_idx must be [%d, 60, %d, %d], got %s" % (B, h, w, tuple(btype_idx.shape)))
         lib = L.load()
         self.lib = lib
-        B, _, h, w = logits[0].shape
         need = [t for i, t in enumerate(logits) if not ((i == 5 and btype_idx is not None) or (i == 6 and rho_abs is not None))]
         for t in need + [atom_mask, bond_mask] + ([rho_abs] if rho_abs is not None else []):
             if t is None or not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):

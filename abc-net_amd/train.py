@@ -15,6 +15,7 @@ import torch
 
 from . import _lib as L
 from . import distributed as D
+from .arch import TRAIN_HEADS
 from .ops import FusedAdam, FusedHeadsLoss, FusedLoss, FusedMetrics
 
 
@@ -48,6 +49,11 @@ class Trainer:
         fused_convt=False: the ConvTranspose forward as four batched phase convolutions (Engine(fused_convt=...): the A/B of convt_fused.hip).
         force_exchange: segment the plan and run the bucket exchanges although the group has one rank (testing RCCL's launch
         mechanics between graph segments on a one-GPU box)."""
+        if list(model.heads) != TRAIN_HEADS:
+            # (the fused loss, the meters and the fused heads pass read the maps of train.py:47; other lists train through the
+            #  module's autograd, forward() + loss.backward())
+            raise ValueError("Trainer: the fused training step is defined for heads %s (train.py:47), got heads %s"
+                             % (TRAIN_HEADS, list(model.heads)))
         if not torch.cuda.is_available():
             raise L.AbcNetHipError("Trainer needs an MI355X; abcnet_amd has no CPU fallback")
         self.model = model

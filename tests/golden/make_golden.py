@@ -23,6 +23,10 @@ What is produced (all float32 unless noted):
   adam.npz                 one torch.optim.Adam step (train.py:55 settings)
   shapes_unet.npz          unet.py at an input size that is not a multiple of 32 (72x88, 104x40) and with 3 input channels:
                            head-map samples / statistics (eval, train) and gradient norms under a surrogate loss
+  heads_<variant>.npz      the other head lists of the reference (heads_goldens: unet.py's default [1,21,5,1,4,2] -- with its own
+                           480 x 480 three-channel self-check --, multi_gpu_train.py's [1,20,5,1,90,90,30,30], one head, three odd
+                           widths at 72 x 88, unet2.py's default): state_dict keys / shapes, head-map samples / statistics (eval,
+                           train; full maps at 64 x 64), gradient norms / leading samples under the surrogate loss
   calibrated_<variant>.npz BatchNorm running statistics after CALIB_STEPS train-mode forwards of the reference module (statistics that
                            match the activations: the eval maps then have their train-mode range), eval head maps with them at 64x64
                            (full) and for two images of the 512x512 benchmark batch (samples, statistics, NMS decisions)
@@ -198,6 +202,89 @@ def shape_goldens():
     np.savez(os.path.join(HERE, "shapes_unet.npz"), **{k: v for k, v in res.items() if not k.startswith("odd2")})
     np.savez(os.path.join(HERE, "shapes_unet2.npz"), **{k: v for k, v in res.items() if k.startswith("odd2")})
     print("wrote shapes")
+
+
+# (tag, variant, heads, batch, in_channels, H, W): the head lists the reference itself uses besides train.py's
+HEADS_CASES = (
+    ("selfcheck", "unet", [1, 21, 5, 1, 4, 2], 1, 3, 480, 480),              # unet.py:122-134, UNet(in_channels=3)
+    ("default", "unet", [1, 21, 5, 1, 4, 2], 2, 1, 128, 128),                # unet.py:78, test.py:30
+    ("mgpu", "unet", [1, 20, 5, 1, 90, 90, 30, 30], 2, 1, 256, 256),         # multi_gpu_train.py:47, multi_proc_img2smiles*.py:259
+    ("one", "unet", [3], 2, 1, 64, 64),
+    ("odd", "unet", [2, 7, 33], 1, 1, 72, 88),
+    ("default2", "unet2", [1, 21, 5, 1, 4, 2], 2, 1, 96, 96),
+)
+HEADS_TRUNK_GRADS = ("inc1.double_conv.0.weight", "down3.maxpool_conv.1.double_conv.3.weight", "up1.up.weight", "up2.up.weight",
+                     "up3.up.weight", "up2.up.bias", "up2.conv.double_conv.0.weight", "dconv2.double_conv.4.weight")
+HEADS_TRUNK_GRADS2 = ("down2.maxpool_conv.1.double_conv.5.channel_attention.shared_MLP.0.weight", "up1.conv.res_conv.weight",
+                      "inc2.double_conv.5.spatial_attention.conv2d.weight")
+
+
+def heads_case_input(B, cin, H, W):
+    return synthetic_images(B, max(H, W), seed=7, in_channels=cin)[:, :, :H, :W].contiguous()
+
+
+def savez_fixed(path, **arrays):
+    """np.savez with a fixed member timestamp and order: the same arrays give the same bytes"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for k in sorted(arrays):
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[k]), allow_pickle=False)
+
+
+def heads_goldens():
+    """the reference's UNet with the OTHER head lists it uses (HEADS_CASES: unet.py's default [1,21,5,1,4,2] and its own 480 x 480
+    three-channel self-check, multi_gpu_train.py's [1,20,5,1,90,90,30,30], one head, three odd widths at a size that is no multiple
+    of 32, unet2.py's default).  Per case: the state_dict keys and shapes; head-map shapes, strided samples and statistics in eval
+    and train mode (dropout p = 0), full maps where the input is 64 x 64 or smaller; under the surrogate loss sum_i mean(head_i ** 2)
+    in train mode the loss, the gradient norm of every parameter and the leading 64 gradient values of every out_modules.*
+    parameter and of a few trunk parameters."""
+    out = {"unet": {}, "unet2": {}}
+    for tag, variant, heads, B, cin, H, W in HEADS_CASES:
+        mod = ref_module(variant)
+        res = out[variant]
+        sd = uo.filled_state(variant, cin, heads, seed=0)
+        x = heads_case_input(B, cin, H, W)
+        res["%s_heads" % tag] = np.array(heads)
+        res["%s_input" % tag] = np.array([B, cin, H, W])
+        for mode in ("eval", "train"):
+            torch.manual_seed(0)
+            m = mod.UNet(cin, heads)
+            m.load_state_dict(sd, strict=True)
+            for om in m.out_modules:
+                if hasattr(om, "drop"):
+                    om.drop.p = 0.0
+            m.train(mode == "train")
+            if mode == "eval":
+                msd = m.state_dict()
+                res["%s_keys" % tag] = np.array(list(msd.keys()))
+                res["%s_shapes" % tag] = np.array([[v.dim()] + list(v.shape) + [0] * (4 - v.dim()) for v in msd.values()])
+            ys = m(x)
+            res["%s_%s_nmaps" % (tag, mode)] = np.array(len(ys))
+            for i, y in enumerate(ys):
+                k = "%s_%s_head%d" % (tag, mode, i)
+                res[k + "_shape"] = np.array(y.shape)
+                res[k + "_sample"] = sample(y)
+                res[k + "_stats"] = np.array([y.min().item(), y.max().item(), y.double().mean().item(), y.double().norm().item()])
+                if H * W <= 64 * 64:
+                    res[k] = y.detach().numpy()
+            if mode == "train":
+                loss = sum((y ** 2).mean() for y in ys)
+                loss.backward()
+                res["%s_loss" % tag] = np.array(loss.item())
+                heads_of = HEADS_TRUNK_GRADS + (HEADS_TRUNK_GRADS2 if variant == "unet2" else ())
+                for k, p in m.named_parameters():
+                    if p.grad is None:      # (s: not in the surrogate loss)
+                        continue
+                    res["%s_gnorm/%s" % (tag, k)] = np.array(p.grad.double().norm().item())
+                    if k.startswith("out_modules.") or k in heads_of:
+                        res["%s_ghead/%s" % (tag, k)] = p.grad.reshape(-1)[:64].double().numpy()
+        print("case", tag, "loss", res["%s_loss" % tag].item())
+    for variant in ("unet", "unet2"):
+        savez_fixed(os.path.join(HERE, "heads_%s.npz" % variant), **out[variant])
+    print("wrote heads")
 
 
 def loss_goldens():
@@ -457,11 +544,13 @@ if __name__ == "__main__":
         for v in ("unet", "unet2"):
             calibrated_goldens(v)
         sys.exit(0)
-    if len(sys.argv) > 1 and sys.argv[1] in ("metrics", "decode", "raster", "shapes"):   # (added after the other fixtures: regenerate one alone)
-        {"metrics": metrics_goldens, "decode": decode_goldens, "raster": raster_goldens, "shapes": shape_goldens}[sys.argv[1]]()
+    if len(sys.argv) > 1 and sys.argv[1] in ("metrics", "decode", "raster", "shapes", "heads"):   # (added after the other fixtures: regenerate one alone)
+        {"metrics": metrics_goldens, "decode": decode_goldens, "raster": raster_goldens, "shapes": shape_goldens,
+         "heads": heads_goldens}[sys.argv[1]]()
         sys.exit(0)
     meta()
     shape_goldens()
+    heads_goldens()
     metrics_goldens()
     decode_goldens()
     raster_goldens()

@@ -48,17 +48,18 @@ def pack(lib, w, mode, dt, Cout, Cin, k, rows_pad, red_real, py=0, px=0):
 
 def conv(lib, x, dt_in, dt, B, Hx, Wx, ldx, cin_off, Cin, wp, bias, Cout, taps, Hout, Wout, ldy=None, cout_off=0, coef=None,
          pool=False, stride=1, grid=None, om=1, oy0=0, ox0=0, out=None, out_dt=None, stats=False, drop_p=0.0, drop_seed=0,
-         planar_in=0, planar_out=False, out_slope=None, pool_out=None, stem=None, actbwd=None, defer=None):
+         planar_in=0, planar_out=False, out_slope=None, pool_out=None, stem=None, actbwd=None, defer=None, ctot_out=None):
     """actbwd: (y_raw, ld, coff, scale, shift, slope, mean, invstd) -> abc_conv_desc.actbwd_*; conv.last_actbwd_ok tells whether the
     library honoured it (else the plain convolution ran)"""
     out_dt = dt if out_dt is None else out_dt
     ldy = Cout if ldy is None else ldy
+    ctot_out = Cout if ctot_out is None else ctot_out      # (planar output: [B][ctot_out][Hout][Wout], channels cout_off ..)
     if out is None:
-        out = torch.zeros((B, Cout, Hout, Wout) if planar_out else (B, Hout, Wout, ldy), dtype=tdt(out_dt), device=DEV)
+        out = torch.zeros((B, ctot_out, Hout, Wout) if planar_out else (B, Hout, Wout, ldy), dtype=tdt(out_dt), device=DEV)
     d = L.ConvDesc()
     fill_src(d.src, x, Hx, Wx, ldx, coef, pool, drop_p, drop_seed)
     d.src.planar, d.src.ctot = (1, planar_in) if planar_in else (0, 0)
-    d.planar_out, d.ctot_out = (1, Cout) if planar_out else (0, 0)
+    d.planar_out, d.ctot_out = (1, ctot_out) if planar_out else (0, 0)
     d.w, d.bias, d.y = wp.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr()
     d.dtype_in, d.dtype_c, d.dtype_out = dt_in, dt, out_dt
     d.B, d.Hin, d.Win = B, (Hx // 2 if pool else Hx), (Wx // 2 if pool else Wx)
@@ -132,3 +133,28 @@ def tol(dt, f32=1e-4, bf16=3e-2):
 def relerr(a, b):
     a, b = a.double(), b.double()
     return ((a - b).abs().max() / (b.abs().max() + 1e-12)).item()
+
+
+def chan_relerr(got, ref, dim=1):
+    """per-channel relative L2 error ||got - ref|| / ||ref|| along axis `dim` (f64): a vector, one entry per channel"""
+    g, r = got.double().movedim(dim, 0).reshape(got.shape[dim], -1), ref.double().movedim(dim, 0).reshape(ref.shape[dim], -1)
+    return (g - r).norm(dim=1) / (r.norm(dim=1) + 1e-30)
+
+
+CHAN_BAR_BF16 = 2e-3      # bf16 operands, products exact, f32 sums: only the summation order and a rare bf16 rounding of the activation
+
+
+def check_channels(got, ref, bar, dim=1, what=""):
+    """every channel of `got` within `bar` (relative L2) of the f64 reference `ref`.  Host-side self-check first: on this very
+    reference, one channel scaled by 1.01 must fail the bar (a 1 % error in one channel is caught) -- where the old max-abs bar of
+    relerr() < 3e-2 passes it.  Returns the worst channel's error."""
+    ref = ref.double()
+    bad = ref.clone()
+    bad.select(dim, bad.shape[dim] - 1).mul_(1.01)
+    assert chan_relerr(bad, ref, dim).max().item() > bar, "the bar does not catch a 1 %% error in one channel (%s)" % what
+    assert relerr(bad, ref) < 3e-2
+    e = chan_relerr(got.cpu(), ref, dim)
+    worst = e.max().item()
+    assert worst <= bar, "%s: channel %d off by %.3g (relative L2; bar %.1g)" % (what, int(e.argmax()), worst, bar)
+    print("per-channel relative L2: %s %.3g" % (what, worst))
+    return worst

@@ -468,3 +468,123 @@ def test_reserved_cus_cannot_change_while_a_plan_is_alive():
     finally:
         E.Engine._live = saved
         L.check(lib.abc_set_reserved_cus(0), "set")
+
+
+# the reference's other head lists (tests/golden/heads_*.npz): (variant, in_channels, heads, B, H, W)
+OTHER_HEADS = [("unet", 3, [1, 21, 5, 1, 4, 2], 1, 480, 480), ("unet", 1, [1, 21, 5, 1, 4, 2], 2, 128, 128),
+               ("unet", 1, [1, 20, 5, 1, 90, 90, 30, 30], 2, 256, 256), ("unet", 1, [3], 2, 64, 64), ("unet", 1, [2, 7, 33], 1, 72, 88),
+               ("unet2", 1, [1, 21, 5, 1, 4, 2], 2, 96, 96)]
+
+
+@pytest.mark.parametrize("variant,cin,heads,B,H,W", OTHER_HEADS + [("unet", 1, HEADS, 2, 64, 64)])
+def test_plans_for_other_head_lists_build_without_gpu(variant, cin, heads, B, H, W):
+    """Engine plans (eval / train, bf16 / fp32) for every head list the reference uses: one logit map per head of its width; the
+    fused heads pass (the loss of train.py:95-137) only for train.py's list; bf16 runs the heads' conv1 as ONE merged 128 -> 128 n
+    convolution, fp32 one per head; every learnable tensor but s and the conv biases in front of a BatchNorm is written by the
+    backward plan"""
+    from abcnet_amd.engine import Engine
+    from abcnet_amd.unet import UNet
+    from abcnet_amd.unet2 import UNet as UNet2
+    for dtype in ("bf16", "fp32"):
+        m = (UNet if variant == "unet" else UNet2)(cin, heads, dtype=dtype)
+        m._flat_grad = torch.zeros_like(m._flat.data)
+        for train in (False, True):
+            e = Engine(variant, cin, heads, m._flat.data, m._flat_grad, m._flat_buf, m._counters, (m._lay_p, m._lay_b, m._lay_c), B, H, W,
+                       dtype, train, device="cpu", fused_heads=True)
+            assert len(e.logits) == len(heads) and [tuple(t.shape) for t in e.logits] == [(B, c, H // 4, W // 4) for c in heads]
+            assert e.want_fused_heads == (train and dtype == "bf16" and heads == HEADS)
+            assert (e.hf is not None) == e.want_fused_heads
+            conv1 = [op[2] for op in e.fwd_ops if "out_modules" in op[2] and "conv1" in op[2]]
+            assert len(conv1) == (1 if dtype == "bf16" else len(heads)), conv1
+            if not train:
+                assert len(e.bwd_ops) == 0
+                continue
+            if e.hf is None:
+                assert len(e.dlogits) == len(heads) and e.chan_scale.numel() == sum(heads)
+            # (the one BN -> LeakyReLU -> Dropout backward pass over 128 x nh channels: 16 nh bf16 vectors must divide 256 threads)
+            merged = sum(op[2] == "act_bwd out_modules.*.bn" for op in e.bwd_ops)
+            assert merged == (1 if dtype == "bf16" and len(heads) in (1, 2, 4, 8) and e.hf is None else 0), merged
+            written = set(w for op in e.bwd_ops for w in op[3])
+            missing = [n for n in m._lay_p if n not in written]
+            assert missing[0] == "s" and all(n.endswith(("double_conv.0.bias", "double_conv.3.bias", "conv1.bias")) for n in missing[1:]), missing
+            assert sum(n.endswith("conv1.bias") for n in missing) == len(heads)
+            assert all("out_modules.%d.conv2.%s" % (i, k) in written for i in range(len(heads)) for k in ("weight", "bias"))
+
+
+def test_nms_peaks_refuses_mismatched_shapes_before_the_device():
+    """img2smiles2.py:61-79 reads atom / bond as one plane and rho / omega as n planes each (n = omega.shape[1]): any other
+    combination -- a model with heads[6] < heads[7], a multi-channel centre map, another batch or map size -- is refused with
+    the shapes named, before the device is touched (so on CPU tensors too; no kernel ever sees such a shape)"""
+    from abcnet_amd.ops import nms_peaks
+
+    def z(*s):
+        return torch.zeros(s)
+
+    a, b = z(2, 1, 8, 8), z(2, 1, 8, 8)
+    for args in ((a, b, z(2, 30, 8, 8), z(2, 60, 8, 8)),      # rho narrower than omega: the kernel read / wrote past rho
+                 (a, b, z(2, 90, 8, 8), z(2, 30, 8, 8)),
+                 (z(2, 3, 8, 8), b, z(2, 60, 8, 8), z(2, 60, 8, 8)),
+                 (a, z(2, 4, 8, 8), z(2, 60, 8, 8), z(2, 60, 8, 8)),
+                 (z(1, 1, 8, 8), b, z(2, 60, 8, 8), z(2, 60, 8, 8)),
+                 (a, b, z(2, 60, 8, 9), z(2, 60, 8, 8)),
+                 (a, b, z(2, 60, 8, 8), z(2, 60, 8))):
+        with pytest.raises(ValueError, match=r"nms_peaks.*\(2, 1, 8, 8\)|nms_peaks wants four NCHW maps"):
+            nms_peaks(*args)
+    # consistent shapes pass the shape check and stop at the device check
+    with pytest.raises(L.AbcNetHipError, match="device"):
+        nms_peaks(a, b, z(2, 30, 8, 8), z(2, 30, 8, 8))
+
+
+def test_peak_extractor_refuses_other_head_widths_before_the_device():
+    """extract.hip reads 14 atom-type, 3 charge, 2 hs, 360 bond-type, 60 rho and 60 omega planes: the maps of another head list
+    (multi_gpu_train.py:47's 90 bond-type and 30 rho / omega planes) are refused with the shape named"""
+    from abcnet_amd.ops import PeakExtractor
+    B, h, w = 2, 8, 8
+    am, bm = torch.zeros(B, 1, h, w), torch.zeros(B, 1, h, w)
+    with pytest.raises(ValueError, match=r"head 1 must be \[2, 14, 8, 8\].*got \(2, 20, 8, 8\)"):
+        PeakExtractor([torch.zeros(B, c, h, w) for c in [1, 20, 5, 1, 90, 90, 30, 30]], am, bm)
+    with pytest.raises(ValueError, match=r"head 5 must be \[2, 360, 8, 8\].*got \(2, 90, 8, 8\)"):
+        PeakExtractor([torch.zeros(B, c, h, w) for c in [1, 14, 3, 2, 1, 90, 30, 30]], am, bm)
+    with pytest.raises(ValueError, match=r"head 7 must be \[2, 60, 8, 8\].*got \(2, 30, 8, 8\)"):
+        PeakExtractor([torch.zeros(B, c, h, w) for c in [1, 14, 3, 2, 1, 360, 60, 30]], am, bm)
+    with pytest.raises(ValueError, match=r"head 1 must be \[2, 14, 8, 8\]"):
+        PeakExtractor([torch.zeros(B, c, h, w) for c in [1, 21, 5, 1, 4, 2]] + [None, None], am, bm)
+    with pytest.raises(ValueError, match="8 head maps"):
+        PeakExtractor([torch.zeros(B, c, h, w) for c in [1, 21, 5, 1, 4, 2]], am, bm)
+    good = [torch.zeros(B, c, h, w) for c in HEADS]
+    with pytest.raises(ValueError, match="atom_mask"):
+        PeakExtractor(good, torch.zeros(B, 60, h, w), bm)
+    with pytest.raises(ValueError, match="btype_idx"):
+        PeakExtractor(good[:5] + [None] + good[6:], am, bm, btype_idx=torch.zeros((B, 30, h, w), dtype=torch.uint8))
+    with pytest.raises(L.AbcNetHipError, match="device"):
+        PeakExtractor(good, am, bm)
+
+
+@pytest.mark.parametrize("heads", [[1, 21, 5, 1, 4, 2], [3], [1, 20, 5, 1, 90, 90, 30, 30], [1, 14, 3, 2, 1, 360, 30, 60]])
+def test_inference_runner_and_model_nms_refuse_other_head_lists(heads):
+    """the NMS of img2smiles2.py:61-79 needs 8 heads with one-plane centre maps (heads 0, 4) and as many rho as omega bins (heads
+    6, 7): InferenceRunner and model.nms refuse other lists with a clear error, not an IndexError or a read past a map"""
+    from abcnet_amd.infer import InferenceRunner
+    from abcnet_amd.unet import UNet
+    m = UNet(1, heads)
+    with pytest.raises(ValueError, match=r"InferenceRunner.*heads \[%s\]" % ", ".join(map(str, heads))):
+        InferenceRunner(m, 2, 64, 64)
+    with pytest.raises(ValueError, match=r"model.nms.*heads \[%s\]" % ", ".join(map(str, heads))):
+        m.nms(torch.zeros(2, 1, 64, 64))
+
+
+def test_inference_runner_extract_and_trainer_refuse_other_head_lists():
+    """InferenceRunner(extract=True) needs the head widths extract.hip reads (train.py:47); the fused training step (loss of
+    train.py:95-137, meters, fused heads pass) likewise: both refuse another list with the heads named, before any device work"""
+    from abcnet_amd.infer import InferenceRunner
+    from abcnet_amd.train import Trainer
+    from abcnet_amd.unet import UNet
+    # (multi_gpu_train.py:47's list: its bond-centre map is head 3, head 4 the 90 bond-type planes -- not img2smiles2.py's maps)
+    with pytest.raises(ValueError, match=r"InferenceRunner.*heads \[1, 20, 5, 1, 90, 90, 30, 30\]"):
+        InferenceRunner(UNet(1, [1, 20, 5, 1, 90, 90, 30, 30]), 2, 64, 64, extract=True)
+    with pytest.raises(ValueError, match=r"extract=True.*heads \[1, 14, 3, 2, 1, 360, 30, 30\]"):
+        InferenceRunner(UNet(1, [1, 14, 3, 2, 1, 360, 30, 30]), 2, 64, 64, extract=True)
+    for _v, cin, heads, _B, _H, _W in OTHER_HEADS:
+        for fused in (True, False):
+            with pytest.raises(ValueError, match=r"Trainer.*heads \[%s\]" % ", ".join(map(str, heads))):
+                Trainer(UNet(cin, heads, dtype="bf16"), 2, 64, 64, fused_heads=fused)

@@ -183,10 +183,21 @@ def test_conv_narrow_plain_input(lib, case):
         assert (rest == 7.0).all()
 
 
+HEAD_WIDTHS = [14, 60, 1, 360, 2, 3, 4, 5, 20, 21, 30, 33, 90]     # every head width of the reference's lists (33: Cout_pad = 64)
+
+
+def chan_bar(dt):
+    return U.CHAN_BAR_BF16 if dt == L.BF16 else 1e-4
+
+
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("Cout,W", [(14, 32), (60, 24), (1, 20), (360, 18)])
+@pytest.mark.parametrize("Cout,W", [(14, 32), (60, 24), (1, 20), (360, 18), (2, 16), (3, 24), (4, 32), (5, 16), (20, 24), (21, 32),
+                                    (30, 16), (33, 24), (90, 32), (33, 18)])
 def test_head_conv1x1_writes_nchw(lib, dt, Cout, W):
-    """heads' 1x1 conv (unet.py:70): BN+LeakyReLU+dropout on load, channel-offset input, NCHW f32 output"""
+    """heads' 1x1 conv (unet.py:70): BN+LeakyReLU+dropout on load, channel-offset input, NCHW f32 output into channels
+    cout_off .. cout_off + Cout of a wider planar buffer; every channel against an f64 reference over the same bf16 operands, and
+    every channel the descriptor does not own (the Cout_pad - Cout padding rows included) keeps its sentinel bit for bit.  (W = 18:
+    16 x 18 pixels are no multiple of 64, the general convolution serves the head)"""
     from abcnet_amd.dropout import keep_mask
     g = torch.Generator().manual_seed(31)
     B, H, ld, coff, Cin = 2, 16, 256, 128, 128
@@ -200,19 +211,35 @@ def test_head_conv1x1_writes_nchw(lib, dt, Cout, W):
     keep = keep_mask(idx, seed, p_drop).permute(0, 3, 1, 2).float()
     a = act(x, sc, sh, sl) * keep / (1 - p_drop)
     ref = F.conv2d(q(a[:, coff:coff + Cin], dt), q(w, dt), b)
-    wp = U.pack(lib, w.to(U.DEV), 0, dt, Cout, Cin, 1, -(-Cout // 32) * 32, Cin)
+    ref64 = torch.einsum("bihw,oi->bohw", q(a[:, coff:coff + Cin], dt).double(), q(w, dt).double().view(Cout, Cin)) + b.double().view(1, -1, 1, 1)
+    cpad = -(-Cout // 32) * 32
+    wp = U.pack(lib, w.to(U.DEV), 0, dt, Cout, Cin, 1, cpad, Cin)
     coef = tuple(t.to(U.DEV) for t in (sc, sh, sl))
     y, _ = U.conv(lib, U.nhwc(x, dt), dt, dt, B, H, W, ld, coff, Cin, wp, b.to(U.DEV), Cout, [(0, 0)], H, W, coef=coef, out_dt=L.F32,
                   drop_p=p_drop, drop_seed=seed, planar_out=True)
+    if dt == L.BF16 and (H * W) % 64 == 0:
+        assert U.conv.last_variant == 3      # (the heads' own 1x1 kernel)
+    # the same launch into a wider planar buffer (sentinel-filled; room for the padding rows past cout_off + Cout)
+    cout_off, ctot = 5, 5 + cpad + 3
+    SENT = -1234.5
+    big = torch.full((B, ctot, H, W), SENT, dtype=torch.float32, device=U.DEV)
+    U.conv(lib, U.nhwc(x, dt), dt, dt, B, H, W, ld, coff, Cin, wp, b.to(U.DEV), Cout, [(0, 0)], H, W, coef=coef, out_dt=L.F32,
+           drop_p=p_drop, drop_seed=seed, planar_out=True, out=big, cout_off=cout_off, ctot_out=ctot)
     torch.cuda.synchronize()
     assert tuple(y.shape) == (B, Cout, H, W)
     assert U.relerr(y.cpu(), ref) < U.tol(dt)
+    U.check_channels(y.cpu(), ref64, chan_bar(dt), what="head fwd Cout=%d" % Cout)
+    big = big.cpu()
+    assert torch.equal(big[:, cout_off:cout_off + Cout], y.cpu())
+    rest = torch.cat([big[:, :cout_off], big[:, cout_off + Cout:]], 1)
+    assert torch.equal(rest.view(torch.int32), torch.full_like(rest, SENT).view(torch.int32)), "a store outside the descriptor's channels"
 
 
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("Cn", [14, 60, 1, 360])
+@pytest.mark.parametrize("Cn", HEAD_WIDTHS)
 def test_head_conv1x1_backward_from_nchw(lib, dt, Cn):
-    """data and weight gradient of the heads' 1x1 conv, reading NCHW f32 dlogits with a per-channel scale"""
+    """data and weight gradient of the heads' 1x1 conv, reading NCHW f32 dlogits with a per-channel scale; every channel of both
+    against an f64 reference over the same bf16 operands"""
     g = torch.Generator().manual_seed(33)
     B, H, W, Cin = 2, 16, 24, 128
     f = q(torch.randn((B, Cin, H, W), generator=g), dt).requires_grad_(True)
@@ -220,11 +247,16 @@ def test_head_conv1x1_backward_from_nchw(lib, dt, Cn):
     dl = torch.randn((B, Cn, H, W), generator=g)
     scale = 0.37
     F.conv2d(f, w).backward(q(dl * scale, dt))
+    dlq = q(dl * scale, dt).double()
+    dx64 = torch.einsum("bchw,ci->bihw", dlq, w.detach().double().view(Cn, Cin))
+    dw64 = torch.einsum("bchw,bihw->ci", dlq, f.detach().double())
     dld = dl.to(U.DEV).contiguous()
     cs = (torch.full((Cn,), scale), torch.zeros(Cn), torch.ones(Cn))
     cs = tuple(t.to(U.DEV) for t in cs)
     wd = U.pack(lib, w.detach().to(U.DEV), 1, dt, Cn, Cin, 1, Cin, Cn)
     dx, _ = U.conv(lib, dld, L.F32, dt, B, H, W, 0, 0, Cn, wd, None, Cin, [(0, 0)], H, W, coef=cs, planar_in=Cn)
+    if dt == L.BF16:
+        assert U.conv.last_variant == 4      # (the heads' own data-gradient kernel)
     d = L.WgradDesc()
     U.fill_src(d.p, dld, H, W, 0, cs)
     d.p.planar, d.p.ctot = 1, Cn
@@ -248,10 +280,15 @@ def test_head_conv1x1_backward_from_nchw(lib, dt, Cn):
     torch.cuda.synchronize()
     assert U.relerr(U.to_nchw(dx), f.grad) < U.tol(dt)
     assert U.relerr(dw.cpu().view(Cn, Cin, 1, 1), w.grad) < U.tol(dt)
+    # (the data gradient is stored in bf16: against the reference rounded the same way -- with Cn = 1 there is no sum at all, the
+    #  only difference left would be the store's rounding, 2.2e-3 relative L2)
+    U.check_channels(U.to_nchw(dx), q(dx64.float(), dt), chan_bar(dt), what="head dgrad Cn=%d" % Cn)
+    U.check_channels(dw.cpu().view(Cn, Cin), dw64, chan_bar(dt), dim=0, what="head wgrad Cn=%d" % Cn)
     np.testing.assert_allclose(db.cpu(), (dl * scale).sum((0, 2, 3)), rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("Cn,nsplit", [(14, 3), (360, 5), (60, 1), (1, 7)])
+@pytest.mark.parametrize("Cn,nsplit", [(14, 3), (360, 5), (60, 1), (1, 7), (2, 2), (3, 4), (4, 1), (5, 6), (20, 3), (21, 2), (30, 5),
+                                       (33, 3), (90, 4)])
 def test_head_wgrad_fused_activation(lib, Cn, nsplit):
     """weight gradient of a head's 1x1 conv in bf16 mode (dedicated kernel): NCHW f32 dlogits with a per-channel scale
     against BN + LeakyReLU + dropout applied on load to a channel slice of the NHWC feature map (unet.py:67-70)"""
@@ -297,12 +334,16 @@ def test_head_wgrad_fused_activation(lib, Cn, nsplit):
     got_b = rs.double().sum(0).cpu()
     assert torch.isfinite(rs).all() and (got_b[:Cn] - want_b).abs().max().item() <= 1e-5 * want_b.abs().max().item() + 1e-6
     assert (got_b[Cn:] == 0).all()
+    # the slabs' padding rows (Ca_pad > Cn): written, finite and zero (the reduction never reads them)
+    slab = part.view(nsplit, ca.value, cb.value).cpu()
+    assert torch.isfinite(slab).all() and (slab[:, Cn:] == 0).all()
     dw = torch.zeros((Cn, Cin, 1), dtype=torch.float32, device=U.DEV)
     r = L.WgradReduceDesc()
     r.partial, r.nsplit, r.ntaps, r.Ca, r.Cb, r.Ca_pad, r.Cb_pad, r.dw, r.accumulate = part.data_ptr(), nsplit, 1, Cn, Cin, ca.value, cb.value, dw.data_ptr(), 0
     L.check(lib.abc_wgrad_reduce(C.byref(r), U.stream()), "reduce")
     torch.cuda.synchronize()
     assert U.relerr(dw.cpu().view(Cn, Cin), ref) < U.tol(dt)
+    U.check_channels(dw.cpu().view(Cn, Cin), ref, U.CHAN_BAR_BF16, dim=0, what="head wgrad (fused activation) Cn=%d" % Cn)
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -1138,3 +1179,106 @@ def test_cbam_conv7_forward_and_backward(lib, B, H, W):
     assert (dst.cpu().double() - ref_dst).abs().max() < 1e-4 * max(1.0, ref_dst.abs().max().item())
     assert (dw.cpu().double() - w.grad.reshape(-1)).abs().max() < 2e-5 * max(1.0, w.grad.abs().max().item())
     assert abs(db.cpu().double().item() - b.grad.item()) < 2e-5 * max(1.0, abs(b.grad.item()))
+
+
+@pytest.mark.parametrize("heads", [[1, 21, 5, 1, 4, 2], [1, 20, 5, 1, 90, 90, 30, 30], [2, 7, 33], [1], [90, 2, 33]])
+def test_heads_batched_launches_equal_single_launches(lib, heads):
+    """abc_heads_batch (forward, which = 0; data gradient, which = 1) and abc_wgrad_heads_batch + abc_wgrad_reduce_batch with
+    n = 1 .. 8 heads of mixed widths (the reference's lists): each head's result bit-equal to its own single-descriptor launch
+    (abc_conv_fwd / abc_wgrad + abc_wgrad_reduce) and within the per-channel bar of an f64 reference over the same bf16
+    operands -- the grid sized for the widest head, per-head blockIdx indexing, the unused slots copied from slot 0"""
+    from abcnet_amd.dropout import keep_mask
+    dt, nh = L.BF16, len(heads)
+    g = torch.Generator().manual_seed(37)
+    B, H, W, Cin = 2, 16, 24, 128
+    ld = 128 * nh
+    p_drop, seed = 0.2, 991
+    # forward: the heads' features side by side (as the merged conv1 writes them), BN + LeakyReLU + dropout on load
+    x = q(torch.randn((B, ld, H, W), generator=g), dt)
+    sc, sh = torch.rand(ld, generator=g) * 2 - 0.6, torch.randn(ld, generator=g) * 0.3
+    sl = torch.full((ld,), 0.01)
+    idx = (torch.arange(B * H * W).view(B, H, W, 1) * ld + torch.arange(ld).view(1, 1, 1, ld))
+    keep = keep_mask(idx, seed, p_drop).permute(0, 3, 1, 2).float()
+    a = q(act(x, sc, sh, sl) * keep / (1 - p_drop), dt)
+    xd, coef = U.nhwc(x, dt), tuple(t.to(U.DEV) for t in (sc, sh, sl))
+    ws = [q(torch.randn((c, Cin, 1, 1), generator=g) / Cin ** 0.5, dt) for c in heads]
+    bs = [torch.randn(c, generator=g) for c in heads]
+    keepalive = []
+    items = []
+    for i, c in enumerate(heads):
+        wp = U.pack(lib, ws[i].to(U.DEV), 0, dt, c, Cin, 1, -(-c // 32) * 32, Cin)
+        bd = bs[i].to(U.DEV)
+        keepalive += [wp, bd]
+        U.conv(lib, xd, dt, dt, B, H, W, ld, 128 * i, Cin, wp, bd, c, [(0, 0)], H, W, coef=coef, out_dt=L.F32, drop_p=p_drop,
+               drop_seed=seed, planar_out=True, defer=items)
+        assert U.conv.last_variant == 3
+    descs = (L.ConvDesc * nh)(*[d for d, _w, _s in items])
+    ybat = [torch.full((B, c, H, W), float("nan"), device=U.DEV) for c in heads]
+    for i in range(nh):
+        descs[i].y = ybat[i].data_ptr()
+    L.check(lib.abc_heads_batch(descs, nh, 0, U.stream()), "heads_batch fwd")
+    ysin = [torch.full((B, c, H, W), float("nan"), device=U.DEV) for c in heads]
+    for i, (d, _w, _s) in enumerate(items):
+        d.y = ysin[i].data_ptr()
+        L.check(lib.abc_conv_fwd(C.byref(d), U.stream()), "conv_fwd")
+    # data gradient from the NCHW f32 dlogits, into the heads' slices of one feature-gradient tensor
+    dls = [torch.randn((B, c, H, W), generator=g) for c in heads]
+    scales = [torch.rand(c, generator=g) + 0.2 for c in heads]
+    dlds = [t.to(U.DEV).contiguous() for t in dls]
+    css = [tuple(t.to(U.DEV) for t in (s_, torch.zeros(c), torch.ones(c))) for s_, c in zip(scales, heads)]
+    dfb = torch.full((B, H, W, ld), float("nan"), dtype=torch.bfloat16, device=U.DEV)
+    dfs = torch.full((B, H, W, ld), float("nan"), dtype=torch.bfloat16, device=U.DEV)
+    items = []
+    for i, c in enumerate(heads):
+        wd = U.pack(lib, ws[i].to(U.DEV), 1, dt, c, Cin, 1, Cin, c)
+        keepalive.append(wd)
+        U.conv(lib, dlds[i], L.F32, dt, B, H, W, 0, 0, c, wd, None, Cin, [(0, 0)], H, W, coef=css[i], planar_in=c, ldy=ld, cout_off=128 * i,
+               out=dfb, defer=items)
+        assert U.conv.last_variant == 4
+    descs = (L.ConvDesc * nh)(*[d for d, _w, _s in items])
+    L.check(lib.abc_heads_batch(descs, nh, 1, U.stream()), "heads_batch dgrad")
+    for d, _w, _s in items:
+        d.y = dfs.data_ptr()
+        L.check(lib.abc_conv_fwd(C.byref(d), U.stream()), "conv_fwd dgrad")
+    # weight gradients: each head with its own slabs and K-split count, then the reductions as one launch
+    wds_b, wds_s, red_b, red_s, dws_b, dws_s, parts = [], [], [], [], [], [], []
+    for i, c in enumerate(heads):
+        for batched in (True, False):
+            d = L.WgradDesc()
+            U.fill_src(d.p, dlds[i], H, W, 0, css[i])
+            d.p.planar, d.p.ctot = 1, c
+            U.fill_src(d.q, xd, H, W, ld, coef, False, p_drop, seed)
+            d.dtype_p, d.dtype_q, d.dtype_c = L.F32, dt, dt
+            d.B, d.Hg, d.Wg, d.Hq, d.Wq, d.Ca, d.Cb, d.stride, d.nsplit, d.cq_off = B, H, W, H, W, c, Cin, 1, 1 + (3 * i) % 5, 128 * i
+            L.set_taps(d, [(0, 0)])
+            ca, cb = L.i32(), L.i32()
+            L.check(lib.abc_wgrad_pads(C.byref(d), C.byref(ca), C.byref(cb)), "pads")
+            part = torch.full((d.nsplit * ca.value * cb.value,), float("nan"), dtype=torch.float32, device=U.DEV)
+            parts.append(part)
+            d.partial = part.data_ptr()
+            dw = torch.full((c, Cin, 1), float("nan"), dtype=torch.float32, device=U.DEV)
+            r = L.WgradReduceDesc()
+            r.partial, r.nsplit, r.ntaps, r.Ca, r.Cb, r.Ca_pad, r.Cb_pad, r.dw, r.accumulate = part.data_ptr(), d.nsplit, 1, c, Cin, ca.value, cb.value, dw.data_ptr(), 0
+            (wds_b if batched else wds_s).append(d)
+            (red_b if batched else red_s).append(r)
+            (dws_b if batched else dws_s).append(dw)
+    L.check(lib.abc_wgrad_heads_batch((L.WgradDesc * nh)(*wds_b), nh, U.stream()), "wgrad_heads_batch")
+    L.check(lib.abc_wgrad_reduce_batch((L.WgradReduceDesc * nh)(*red_b), nh, U.stream()), "wgrad_reduce_batch")
+    for d, r in zip(wds_s, red_s):
+        L.check(lib.abc_wgrad(C.byref(d), U.stream()), "wgrad")
+        L.check(lib.abc_wgrad_reduce(C.byref(r), U.stream()), "wgrad_reduce")
+    torch.cuda.synchronize()
+    dfb, dfs = dfb.float().cpu(), dfs.float().cpu()
+    assert torch.equal(dfb, dfs)
+    for i, c in enumerate(heads):
+        assert torch.equal(ybat[i].cpu(), ysin[i].cpu()), "forward head %d" % i
+        assert torch.equal(dws_b[i].cpu(), dws_s[i].cpu()), "weight gradient head %d" % i
+        ai = a[:, 128 * i:128 * (i + 1)].double()
+        y64 = torch.einsum("bihw,oi->bohw", ai, ws[i].double().view(c, Cin)) + bs[i].double().view(1, -1, 1, 1)
+        U.check_channels(ybat[i].cpu(), y64, U.CHAN_BAR_BF16, what="batched fwd head %d (%d)" % (i, c))
+        dlq = q(dls[i] * scales[i].view(1, -1, 1, 1), dt).double()
+        dx64 = torch.einsum("bchw,ci->bhwi", dlq, ws[i].double().view(c, Cin))
+        U.check_channels(dfb[..., 128 * i:128 * (i + 1)], q(dx64.float(), dt), U.CHAN_BAR_BF16, dim=3,      # (stored in bf16)
+                         what="batched dgrad head %d (%d)" % (i, c))
+        dw64 = torch.einsum("bchw,bihw->ci", dlq, ai)
+        U.check_channels(dws_b[i].cpu().view(c, Cin), dw64, U.CHAN_BAR_BF16, dim=0, what="batched wgrad head %d (%d)" % (i, c))

@@ -316,3 +316,89 @@ def test_frozen_trained_fixture_maps_match_reference(golden_dir):
             got = m[j].numpy().astype(np.uint8).reshape(-1)
             assert int((got ^ want).sum()) <= 2, (name, p)
     assert [int(c) for c in gold["nms512_counts"][:2]] == [191, 110]
+
+
+# the reference's other head lists (tests/golden/heads_<variant>.npz, make_golden.py heads): (tag, variant); the lists and input
+# shapes come from the fixture itself
+HEADS_CASES = (("selfcheck", "unet"), ("default", "unet"), ("mgpu", "unet"), ("one", "unet"), ("odd", "unet"), ("default2", "unet2"))
+HEADS_LISTS = {"selfcheck": [1, 21, 5, 1, 4, 2], "default": [1, 21, 5, 1, 4, 2], "mgpu": [1, 20, 5, 1, 90, 90, 30, 30], "one": [3],
+               "odd": [2, 7, 33], "default2": [1, 21, 5, 1, 4, 2]}
+
+
+def heads_case(golden_dir, tag, variant):
+    """(fixture, heads, in_channels, input) of one case of heads_<variant>.npz"""
+    gold = np.load(os.path.join(golden_dir, "heads_%s.npz" % variant))
+    heads = [int(h) for h in gold["%s_heads" % tag]]
+    B, cin, H, W = (int(v) for v in gold["%s_input" % tag])
+    x = synthetic_images(B, max(H, W), seed=7, in_channels=cin)[:, :, :H, :W].contiguous()
+    return gold, heads, cin, x
+
+
+def heads_case_shapes(gold, tag):
+    """the reference's state_dict (keys, shapes) of one case"""
+    keys = [str(k) for k in gold["%s_keys" % tag]]
+    shapes = [tuple(int(d) for d in row[1:1 + row[0]]) for row in gold["%s_shapes" % tag]]
+    return keys, shapes
+
+
+def _bias_before_bn(name):
+    return name.endswith(("double_conv.0.bias", "double_conv.3.bias", "conv1.bias"))
+
+
+@pytest.mark.parametrize("tag,variant", HEADS_CASES)
+def test_other_head_lists_match_reference(tag, variant, golden_dir):
+    """UNet(in_channels, heads) with the reference's other head lists (unet.py:78's default, with unet.py:122-134's own 480 x 480
+    three-channel self-check; multi_gpu_train.py:47's; one head; three odd widths on 72 x 88; unet2.py's default): the oracle's maps
+    (eval and train, dropout p = 0) within 1e-5 of the reference's, and under the surrogate loss sum_i mean(head_i ** 2) its
+    gradients -- the norm of every parameter within 1e-4 relative, leading values of the heads' and of some trunk parameters"""
+    gold, heads, cin, x = heads_case(golden_dir, tag, variant)
+    assert heads == HEADS_LISTS[tag]
+    for mode in ("eval", "train"):
+        sd = uo.clone_state(uo.filled_state(variant, cin, heads, seed=0), requires_grad=(mode == "train"))
+        ys = uo.forward(variant, sd, x, train=(mode == "train"))
+        assert len(ys) == len(heads) == int(gold["%s_%s_nmaps" % (tag, mode)])
+        for i, y in enumerate(ys):
+            k = "%s_%s_head%d" % (tag, mode, i)
+            assert list(y.shape) == list(gold[k + "_shape"]) and y.shape[1] == heads[i]
+            np.testing.assert_allclose(_sample(y), gold[k + "_sample"], rtol=0, atol=1e-5, err_msg=k)
+            if k in gold.files:
+                np.testing.assert_allclose(y.detach().numpy(), gold[k], rtol=0, atol=1e-5, err_msg=k)
+            st = gold[k + "_stats"]
+            assert abs(y.double().norm().item() - st[3]) <= 1e-5 * st[3] + 1e-9, k
+        if mode == "train":
+            loss = sum((y ** 2).mean() for y in ys)
+            loss.backward()
+            assert abs(loss.item() - gold["%s_loss" % tag].item()) <= 1e-6 * abs(gold["%s_loss" % tag].item())
+            names = [k[len(tag) + 7:] for k in gold.files if k.startswith(tag + "_gnorm/")]
+            assert len(names) == sum(1 for k in sd if sd[k].requires_grad) - 1      # (every parameter but s)
+            for name in names:
+                gn = gold["%s_gnorm/%s" % (tag, name)].item()
+                got = sd[name].grad.double()
+                if _bias_before_bn(name):
+                    # mathematically zero (a constant in front of a train-mode BatchNorm): what both hold is cancellation noise
+                    wn = gold["%s_gnorm/%s" % (tag, name[:-4] + "weight")].item()
+                    assert gn <= 1e-2 * wn and got.norm().item() <= 1e-2 * wn, name
+                    continue
+                assert abs(got.norm().item() - gn) <= 1e-4 * gn + 1e-9, name
+                hk = "%s_ghead/%s" % (tag, name)
+                if hk in gold.files:
+                    np.testing.assert_allclose(got.reshape(-1)[:64].numpy(), gold[hk], rtol=2e-3, atol=1e-5 * gn + 1e-9, err_msg=name)
+            assert all(("%s_ghead/out_modules.%d.conv2.weight" % (tag, i)) in gold.files for i in range(len(heads)))
+
+
+@pytest.mark.parametrize("tag,variant", HEADS_CASES)
+def test_other_head_lists_state_dict_layout(tag, variant, golden_dir):
+    """the reference's state_dict for each head list: arch.state_table, the oracle's table and UNet(cin, heads).state_dict() give
+    its keys and shapes in its order"""
+    from abcnet_amd import arch
+    from abcnet_amd.unet import UNet
+    from abcnet_amd.unet2 import UNet as UNet2
+    gold, heads, cin, _x = heads_case(golden_dir, tag, variant)
+    keys, shapes = heads_case_shapes(gold, tag)
+    assert sum(k.endswith("conv2.weight") for k in keys) == len(heads)
+    table = arch.state_table(variant, cin, heads)
+    assert [t[0] for t in table] == keys and [tuple(t[1]) for t in table] == shapes
+    ot = uo.param_table(variant, cin, heads)
+    assert [t[0] for t in ot] == keys and [tuple(t[1]) for t in ot] == shapes
+    sd = (UNet if variant == "unet" else UNet2)(cin, heads).state_dict()
+    assert list(sd.keys()) == keys and [tuple(v.shape) for v in sd.values()] == shapes
