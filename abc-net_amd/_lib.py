@@ -180,9 +180,18 @@ class ConvTDesc(C.Structure):
                 ("Cin", i32), ("Hout", i32), ("Wout", i32), ("ldy", i32), ("cout_off", i32), ("Cout", i32), ("Cout_pad", i32)]
 
 
+class ImageDesc(C.Structure):
+    _fields_ = [("out", vp), ("src", vp), ("src_stride", i64), ("src_pitch", i32), ("src_max_h", i32), ("params", vp),
+                ("params_host", vp), ("B", i32), ("S", i32), ("mode", i32), ("test_max_ink", i32)]
+
+
+IMG_TRAIN, IMG_TEST = 0, 1
+IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
+
+
 _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnApplyDesc, WgradDesc, WgradReduceDesc,
             LossDesc, LossFinDesc, AdamDesc, NmsDesc, CbamChannelDesc, CbamPixDesc, CbamConv7Desc, MetricsDesc, ExtractDesc, RasterDesc,
-            HeadsFusedDesc, HeadsEpi, ConvTDesc, LossScaleDesc, AdamSeg, AdamClass, AdamMultiDesc]
+            HeadsFusedDesc, HeadsEpi, ConvTDesc, LossScaleDesc, AdamSeg, AdamClass, AdamMultiDesc, ImageDesc]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -247,6 +256,7 @@ SYMBOLS = {
     "abc_extract_work_masks": (i64, [P(ExtractDesc)]),
     "abc_extract_peaks": (C.c_int, [P(ExtractDesc), vp]),
     "abc_rasterize_targets": (C.c_int, [P(RasterDesc), vp]),
+    "abc_build_images": (C.c_int, [P(ImageDesc), vp]),
     "abc_metrics_blocks": (C.c_int, [P(MetricsDesc)]),
     "abc_metrics_update": (C.c_int, [P(MetricsDesc), vp]),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),

@@ -1,0 +1,238 @@
+"""Input images on the device: the image half of the reference's src/utils.py:42-81 (MolecularImageDataset.__getitem__) and
+utils_for_test.py:21-27, split into a tiny host half and one kernel.
+
+    host   draw_augment(): the reference's scalar draws (utils.py:44-58, 73, 76) in its order and arithmetic -- resize branch,
+           scale, centring offsets, salt and pepper amounts -- plus a 64-bit noise key;
+    device ImageBuilder: the raw uint8 renders and ten int32 per image go over PCIe; csrc/augment.hip resizes (OpenCV
+           INTER_LINEAR on float32), centres on the white canvas, thresholds and noises them straight into the network's f32 input.
+
+The salt and pepper fields come from a counter hash of (key, pixel) on the device (abc_noise_hash, mirrored by noise_hash
+below), not from np.random's per-pixel stream: per pixel they follow the reference's distribution -- Bernoulli with the drawn
+amounts -- not its bits.  That is the position the dropout mask takes (dropout.py, K7).  No CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+MODES = {"train": L.IMG_TRAIN, "test": L.IMG_TEST}
+
+# one image's draws: the resized size (rows x cols) it takes on the S x S canvas at (ddx, ddy), the reference's scale factors
+# (int 1 when not resized), its salt / pepper amounts and the 64-bit key of its noise fields
+AugmentDraw = namedtuple("AugmentDraw", "rows cols ddx ddy scale_x scale_y salt pepper key")
+
+_M32 = 0xFFFFFFFF
+
+
+def _fmix32(h):
+    m = np.uint64(_M32)
+    h = np.asarray(h, dtype=np.uint64) & m
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85EBCA6B)) & m
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xC2B2AE35)) & m
+    h ^= h >> np.uint64(16)
+    return h
+
+
+def noise_seed(key):
+    """abc_noise_seed (csrc/common.hpp): the per-image 32-bit premix of a 64-bit key"""
+    lo, hi = key & _M32, (key >> 32) & _M32
+    return int(_fmix32(np.uint64(lo ^ 0x5A17F00D) ^ _fmix32(np.uint64((hi * 0x9E3779B1 + 0x7F4A7C15) & _M32))))
+
+
+def noise_hash(idx, key):
+    """numpy mirror of abc_noise_hash(idx, abc_noise_seed(key)) (csrc/common.hpp): uint32 per element index for a 64-bit key"""
+    m = np.uint64(_M32)
+    h = (np.asarray(idx, dtype=np.uint64) * np.uint64(0x9E3779B1)) & m
+    return _fmix32(h ^ np.uint64(noise_seed(key))).astype(np.uint32)
+
+
+def noise_threshold(rate):
+    """uint32 t with  h < t  <=>  h * 2^-32 < rate  (the reference's uniform(0, 1) < amount on a 32-bit uniform); rate >= 1
+    saturates at 2^32 - 1"""
+    t = math.ceil(float(rate) * 4294967296.0)      # (exact: a power-of-two scaling of a double)
+    return max(0, min(t, _M32))
+
+
+def test_ink_max():
+    """the largest byte that utils_for_test.py:22-24, 1 - ((u8 / 255).astype(f32) > 0.2), maps to 1 (checked monotone)"""
+    u8 = np.arange(256, dtype=np.uint8)
+    ink = (1 - ((u8 / 255).astype("float32") > 0.2)).astype(bool)
+    c = int(np.flatnonzero(ink).max())
+    if not (ink[:c + 1].all() and not ink[c + 1:].any()):
+        raise AssertionError("the test-mode threshold is not a byte cut")
+    return c
+
+
+def draw_augment(rng, amount, src_shape, size=512):
+    """utils.py:44-58, 73, 76 for one image of shape src_shape = (rows, cols) with 512 generalised to `size`: the same draws
+    in the same order (rand() < 0.2, rand() < 0.5, uniform(0.8, 1), then uniform(0, amount / 100) and uniform(0, amount)) from
+    `rng` (np.random itself, or a RandomState), then two randint(0, 2^32) for the noise key.  Returns (AugmentDraw,
+    (scale_x, scale_y, ddx, ddy)) -- the second what raster.parse_record takes.  Raises when the image would not fit the canvas."""
+    S = int(size)
+    rows, cols = int(src_shape[0]), int(src_shape[1])
+    scale_x = 1
+    scale_y = 1
+    if rng.rand() < 0.2:
+        if rng.rand() < 0.5:
+            scale_x = rng.uniform(0.8, 1)
+            rows, cols = int(scale_x * S), S          # cv2.resize(img, (S, int(scale_x * S))): dsize is (width, height)
+        else:
+            scale_y = rng.uniform(0.8, 1)
+            rows, cols = S, int(scale_y * S)
+    if not (1 <= rows <= S and 1 <= cols <= S):
+        raise ValueError("draw_augment: a %s source does not fit the %d x %d canvas without a resize" % (tuple(src_shape), S, S))
+    ddx = (S - rows) // 2
+    ddy = (S - cols) // 2
+    salt = rng.uniform(0, amount / 100)
+    pepper = rng.uniform(0, amount)
+    key = int(rng.randint(0, 1 << 32)) | (int(rng.randint(0, 1 << 32)) << 32)
+    return AugmentDraw(rows, cols, ddx, ddy, scale_x, scale_y, float(salt), float(pepper), key), (scale_x, scale_y, ddx, ddy)
+
+
+def param_row(src_shape, draw=None, size=512):
+    """the kernel's int32 parameter row (abc_image_param order); draw=None: the test mode's (no resize, pad or noise)"""
+    sh, sw = int(src_shape[0]), int(src_shape[1])
+    if draw is None:
+        vals = [sh, sw, size, size, 0, 0, 0, 0, 0, 0]
+    else:
+        vals = [sh, sw, draw.rows, draw.cols, draw.ddx, draw.ddy, noise_threshold(draw.salt), noise_threshold(draw.pepper),
+                draw.key & _M32, (draw.key >> 32) & _M32]
+    return np.array(vals, dtype=np.uint64).astype(np.uint32).view(np.int32)
+
+
+class ImageBuilder:
+    """device-side utils.py:42-81 (mode "train") or utils_for_test.py:21-27 (mode "test") for a batch of `batch` uint8 renders
+    into f32 [batch, 1, size, size] -- `out` may be a Trainer's or InferenceRunner's .input_images (then run() writes the network's
+    input in place), otherwise a fresh tensor is allocated.  max_src = (rows, cols) capacity of a source, at most 1024 x 1024."""
+
+    def __init__(self, batch, size, mode="train", amount=0.1, out=None, max_src=None, device="cuda"):
+        if mode not in MODES:
+            raise ValueError("ImageBuilder: mode must be 'train' or 'test', got %r" % (mode,))
+        if not torch.cuda.is_available():
+            raise L.AbcNetHipError("ImageBuilder needs an MI355X; abcnet_amd has no CPU fallback")
+        S = int(size)
+        if S < 8 or S % 8 or S > 8192:
+            raise ValueError("ImageBuilder: size must be a multiple of 8 (8 .. 8192), got %d" % S)
+        max_h, max_w = (S, S) if max_src is None else (int(max_src[0]), int(max_src[1]))
+        if not (1 <= max_h <= 1024 and 1 <= max_w <= 1024):
+            raise ValueError("ImageBuilder: sources are at most 1024 x 1024, got max_src %s" % ((max_h, max_w),))
+        if mode == "test" and (max_h < S or max_w < S):
+            raise ValueError("ImageBuilder(mode='test'): the sources are %d x %d, max_src must hold that" % (S, S))
+        shape = (batch, 1, S, S)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float32, device=device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+            raise L.AbcNetHipError("ImageBuilder: out %s %s does not match the contract %s float32 contiguous on the device "
+                                   "(a %d-channel input is not an image of this loader)" % (tuple(out.shape), out.dtype, shape,
+                                                                                           out.shape[1] if out.dim() == 4 else -1))
+        self.lib = L.load()
+        self.out, self.B, self.S, self.mode, self.amount = out, batch, S, mode, float(amount)
+        self.max_h, self.max_w = max_h, max_w
+        self.pitch = -(-max_w // 16) * 16
+        dev = out.device
+        self.h_src = torch.full((batch, max_h, self.pitch), 255, dtype=torch.uint8, pin_memory=True)
+        self.h_par = torch.zeros((batch, L.IMG_NPARAM), dtype=torch.int32, pin_memory=True)
+        self.d_src, self.d_par = self.h_src.to(dev), self.h_par.to(dev)
+        self._np_src, self._np_par = self.h_src.numpy(), self.h_par.numpy()
+        d = L.ImageDesc()
+        d.out, d.src, d.params = out.data_ptr(), self.d_src.data_ptr(), self.d_par.data_ptr()
+        d.params_host = self.h_par.data_ptr()      # (what the last load staged: checked by every eager call)
+        d.src_stride, d.src_pitch, d.src_max_h = max_h * self.pitch, self.pitch, max_h
+        d.B, d.S, d.mode = batch, S, MODES[mode]
+        d.test_max_ink = test_ink_max() if mode == "test" else 0
+        self.d = d
+        self._copied = None
+
+    def draw(self, rng, src_shapes):
+        """draw_augment for every image of a batch, in order"""
+        return [draw_augment(rng, self.amount, s, self.S) for s in src_shapes]
+
+    def load(self, images_u8, params=None):
+        """images_u8: B 2-d uint8 arrays (decoded grey renders); params: B AugmentDraw (mode "train"), None in mode "test".
+        Host work: the checks and one memcpy per image into pinned staging, then an asynchronous H2D copy."""
+        if len(images_u8) != self.B:
+            raise ValueError("expected %d images" % self.B)
+        if self.mode == "train" and (params is None or len(params) != self.B):
+            raise ValueError("mode 'train' needs one AugmentDraw per image")
+        rows = []
+        for b, img in enumerate(images_u8):
+            img = np.asarray(img)
+            if img.dtype != np.uint8 or img.ndim != 2:
+                raise ValueError("image %d: a 2-d uint8 array, got %s %s" % (b, img.dtype, img.shape))
+            h, w = img.shape
+            if h > self.max_h or w > self.max_w:
+                raise ValueError("image %d: %d x %d exceeds the staging capacity %d x %d" % (b, h, w, self.max_h, self.max_w))
+            if self.mode == "test":
+                if (h, w) != (self.S, self.S):
+                    raise ValueError("image %d: test mode takes %d x %d sources, got %d x %d" % (b, self.S, self.S, h, w))
+                rows.append(param_row((h, w), None, self.S))
+            else:
+                p = params[b]
+                if not (1 <= p.rows <= self.S and 1 <= p.cols <= self.S and 0 <= p.ddx <= self.S - p.rows and 0 <= p.ddy <= self.S - p.cols):
+                    raise ValueError("image %d: %d x %d at (%d, %d) leaves the %d x %d canvas" % (b, p.rows, p.cols, p.ddx, p.ddy, self.S, self.S))
+                rows.append(param_row((h, w), p, self.S))
+        # the pinned staging is reused: the previous load's asynchronous copy must have left it (TargetRasterizer.load)
+        if self._copied is not None:
+            self._copied.synchronize()
+        for b, img in enumerate(images_u8):
+            img = np.asarray(img)
+            self._np_src[b, :img.shape[0], :img.shape[1]] = img
+            self._np_par[b] = rows[b]
+        self.d_src.copy_(self.h_src, non_blocking=True)
+        self.d_par.copy_(self.h_par, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record(torch.cuda.current_stream(self.d_par.device))
+
+    def run(self, stream=None):
+        """one launch (graph-capturable): the f32 batch into self.out"""
+        if stream is None:
+            stream = torch.cuda.current_stream(self.out.device).cuda_stream
+        L.check(self.lib.abc_build_images(C.byref(self.d), stream), "build_images")
+        return self.out
+
+
+class SampleBuilder:
+    """a whole training batch on the device: an ImageBuilder over trainer.input_images and a TargetRasterizer over
+    trainer.targets, fed with the SAME draws (utils.py:42-228 for every image).  sparse=True: the rasteriser's sparse form,
+    registered with trainer.use_sparse_targets."""
+
+    def __init__(self, trainer, amount=0.1, max_src=None, sparse=True, max_atoms=256, max_bonds=256):
+        from .raster import TargetRasterizer
+        img = trainer.input_images
+        B, S = img.shape[0], img.shape[2]
+        if img.shape[3] != S:
+            raise ValueError("SampleBuilder: the augmentation builds square S x S inputs, the Trainer takes %s" % (tuple(img.shape[2:]),))
+        self.trainer = trainer
+        self.images = ImageBuilder(B, S, "train", amount, out=img, max_src=max_src)
+        self.raster = TargetRasterizer(B, trainer.eng.h, trainer.eng.w, max_atoms=max_atoms, max_bonds=max_bonds, targets=trainer.targets,
+                                       sparse=sparse)
+        if sparse:
+            trainer.use_sparse_targets(self.raster)
+        self.B, self.S, self.h = B, S, trainer.eng.h
+
+    def load(self, images_u8, atoms_strings, bonds_strings, rng):
+        """one draw per image (draw_augment), its offsets to both halves; returns the draws"""
+        from .raster import parse_record
+        if not (len(images_u8) == len(atoms_strings) == len(bonds_strings) == self.B):
+            raise ValueError("expected %d images and annotation pairs" % self.B)
+        draws, records = [], []
+        for img, a, q in zip(images_u8, atoms_strings, bonds_strings):
+            dr, offs = draw_augment(rng, self.images.amount, np.shape(img), self.S)
+            draws.append(dr)
+            records.append(parse_record(a, q, *offs, h=self.h))
+        self.images.load(images_u8, draws)
+        self.raster.load(records)
+        return draws
+
+    def run(self, stream=None):
+        self.images.run(stream)
+        self.raster.run(stream)
+        return self.images.out

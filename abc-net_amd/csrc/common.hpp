@@ -126,6 +126,19 @@ __host__ inline uint32_t abc_drop_threshold(float p) {
     const uint32_t f = (uint32_t)t;
     return (double)f < t ? f + 1u : f;
 }
+// Counter-based salt / pepper fields of the input images (augment.hip): the dropout hash's finaliser over (element index, a
+// 32-bit seed premixed once per image from the 64-bit key, with a salt of its own), all 32 bits kept.  Mirrored bit for bit by
+// abcnet_amd.augment.noise_hash (numpy).
+__host__ __device__ inline uint32_t abc_fmix32(uint32_t h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+__host__ __device__ inline uint32_t abc_noise_seed(uint32_t key_lo, uint32_t key_hi) {
+    return abc_fmix32(key_lo ^ 0x5A17F00Du ^ abc_fmix32(key_hi * 0x9E3779B1u + 0x7F4A7C15u));
+}
+__host__ __device__ inline uint32_t abc_noise_hash(uint32_t idx, uint32_t seed) {
+    return abc_fmix32(idx * 0x9E3779B1u ^ seed);
+}
 
 // Compute units left OUT of the persistent grids (abc_set_reserved_cus; process-wide, 0 by default).  Two 256-VGPR workgroups
 // per CU fill the register file of every SIMD, so a kernel of another stream -- RCCL's, during the data-parallel exchange --

@@ -595,6 +595,7 @@ extern "C" int abc_sizeof(int which) {
         case 23: return (int)sizeof(abc_adam_seg);
         case 24: return (int)sizeof(abc_adam_class);
         case 25: return (int)sizeof(abc_adam_multi_desc);
+        case 26: return (int)sizeof(abc_image_desc);
         default: return -1;
     }
 }

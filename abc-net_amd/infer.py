@@ -102,6 +102,11 @@ class InferenceRunner:
         if self.fp8 and not self.eng.fp8_calibrated:
             self.calibrate()
 
+    @property
+    def input_images(self):
+        """the static f32 input buffer [B, C, H, W] the step reads (augment.ImageBuilder(out=...) writes it in place)"""
+        return self.eng.img
+
     def calibrate(self):
         """fp8: set the per-tensor e4m3 scales from the batch in the image buffer (the bf16 folded graph runs once on it), then
         re-pack the weights (their scales fold the input scale in).  No host sync; call again when the data distribution moves."""

@@ -137,6 +137,11 @@ class Trainer:
         for dst, src in zip(self.targets, targets):
             dst.copy_(src, non_blocking=True)
 
+    @property
+    def input_images(self):
+        """the static f32 input buffer [B, C, H, W] the step reads (augment.ImageBuilder(out=...) writes it in place)"""
+        return self.eng.img
+
     def use_sparse_targets(self, rasterizer):
         """rasterizer: a TargetRasterizer(sparse=True, targets=self.targets) -- the fused heads pass then reads only the target planes of
         the 32-pixel groups the rasteriser drew into (FusedHeadsLoss.use_target_flags); None: back to reading every plane.  The loss

@@ -546,6 +546,35 @@ typedef struct abc_raster_desc {
 } abc_raster_desc;
 int abc_rasterize_targets(const abc_raster_desc* d, abc_stream_t stream);
 
+/* Input images (utils.py:42-81, the image half of MolecularImageDataset.__getitem__, with 512 generalised to S; and
+ * utils_for_test.py:21-27) from raw 8-bit renders: writes f32 {0, 1} into out[B][1][S][S].
+ *   mode ABC_IMG_TRAIN: the source (src_h x src_w) resized to rows x cols like OpenCV's INTER_LINEAR on float32 (horizontal pass,
+ *                       then vertical, every multiply and add rounded on its own; an axis of unchanged size is copied), placed
+ *                       at (ddx, ddy) on a white S x S canvas; ink = v / 255 < 0.6f (float32); salt = h(key, 2p) < salt_thr,
+ *                       pepper = h(key, 2p + 1) < pepper_thr with p = x * S + y and h(key, i) = abc_noise_hash(i, abc_noise_seed(key));
+ *                       out = (ink | salt) & ~pepper.
+ *                       The noise matches the reference's np.random fields in distribution, not bit for bit.
+ *   mode ABC_IMG_TEST:  src_h = src_w = S, no resize / pad / noise; out = (byte <= test_max_ink), the largest byte the
+ *                       reference's 1 - ((u8 / 255).astype(f32) > 0.2) maps to 1 (computed by the caller).
+ * params: device int32 [B][ABC_IMG_NPARAM] (thresholds and key halves as uint32 bit patterns).  An image whose parameters
+ * break the contract (rows or cols above S, negative offsets, src_h above src_max_h, src_w above src_pitch, test mode with a
+ * non-S x S source) is written as NaN; params_host (optional: a host copy of the table) is checked at call time instead. */
+enum abc_image_param { ABC_IMG_SRC_H = 0, ABC_IMG_SRC_W, ABC_IMG_ROWS, ABC_IMG_COLS, ABC_IMG_DDX, ABC_IMG_DDY, ABC_IMG_SALT_THR,
+                       ABC_IMG_PEPPER_THR, ABC_IMG_KEY_LO, ABC_IMG_KEY_HI, ABC_IMG_NPARAM };
+enum abc_image_mode { ABC_IMG_TRAIN = 0, ABC_IMG_TEST = 1 };
+typedef struct abc_image_desc {
+    float* out;                     /* [B][1][S][S] f32, 16-byte aligned */
+    const uint8_t* src;             /* image b at src + b * src_stride, its row i at + i * src_pitch (16-byte aligned) */
+    int64_t src_stride;             /* bytes between images, >= src_max_h * src_pitch, multiple of 16 */
+    int32_t src_pitch;              /* bytes between rows, multiple of 16, <= 1024 */
+    int32_t src_max_h;              /* rows an image slot holds, <= 1024 */
+    const int32_t* params;          /* device [B][ABC_IMG_NPARAM] */
+    const int32_t* params_host;     /* optional host copy of params, validated at call time (NULL: not checked) */
+    int32_t B, S, mode;             /* S a multiple of 8 (one thread writes 8 consecutive pixels), 8 <= S <= 8192 */
+    int32_t test_max_ink;           /* ABC_IMG_TEST: ink iff byte <= test_max_ink */
+} abc_image_desc;
+int abc_build_images(const abc_image_desc* d, abc_stream_t stream);
+
 /* Candidate extraction for the SMILES decoder (img2smiles2.py:113-191; replaces its per-pixel .cpu().item() loops):
  * from the NMS masks of abc_nms_peaks and the raw head maps (all NCHW f32) to compact ordered lists per image.
  *   atoms[b][i] = (x, y, type, charge, hs)      raster order, greedy suppression within squared distance < 4
@@ -670,7 +699,7 @@ int abc_concat_f32(const float* const* srcs, const int32_t* counts, int32_t n, f
 /* *p += inc (one thread): the per-step dropout salt */
 int abc_counter_add_u32(uint32_t* p, uint32_t inc, abc_stream_t stream);
 
-/* sizeof(descriptor #which) in declaration order (abc_act_src = 0 ... abc_nms_desc = 12, abc_cbam_channel_desc = 13, abc_cbam_pix_desc = 14, abc_cbam_conv7_desc = 15, abc_metrics_desc = 16, abc_extract_desc = 17, abc_raster_desc = 18, abc_heads_fused_desc = 19, abc_heads_epi = 20, abc_convt_desc = 21, abc_loss_scale_desc = 22, abc_adam_seg = 23, abc_adam_class = 24, abc_adam_multi_desc = 25):
+/* sizeof(descriptor #which) in declaration order (abc_act_src = 0 ... abc_nms_desc = 12, abc_cbam_channel_desc = 13, abc_cbam_pix_desc = 14, abc_cbam_conv7_desc = 15, abc_metrics_desc = 16, abc_extract_desc = 17, abc_raster_desc = 18, abc_heads_fused_desc = 19, abc_heads_epi = 20, abc_convt_desc = 21, abc_loss_scale_desc = 22, abc_adam_seg = 23, abc_adam_class = 24, abc_adam_multi_desc = 25, abc_image_desc = 26):
  * lets a foreign-language binding check its mirror structs at load time */
 int abc_sizeof(int which);
 const char* abc_last_error(void);
