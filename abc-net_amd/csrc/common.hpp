@@ -24,25 +24,6 @@ struct f8 {
     __device__ inline explicit operator float() const { return __builtin_amdgcn_cvt_f32_fp8((int)v, 0); }
 };
 
-// Timing ablations (ABC_*_DBG bit masks that skip phases of a kernel: results invalid) and in-kernel phase timestamps exist
-// only in a debug build (ABC_KERNEL_DEBUG=1 ./build_hip.sh); the production library compiles them out.
-#ifdef ABC_KERNEL_DEBUG
-#define ABC_DBG(x) (x)
-#define ABC_PROF(p) (p)
-#else
-#define ABC_DBG(x) 0
-#define ABC_PROF(p) ((long long*)nullptr)
-#endif
-
-// Experiment switches (kernel / tile choices of measured A/B runs) are read from the environment by the DEBUG build only:
-// the production library never looks at the environment, its kernel choice is a function of the descriptor alone.
-#ifdef ABC_KERNEL_DEBUG
-#include <stdlib.h>
-inline const char* abc_knob(const char* name) { return getenv(name); }
-#else
-inline const char* abc_knob(const char*) { return nullptr; }
-#endif
-
 #define ABC_MAX_TAPS 49
 #define ABC_WAVE 64
 

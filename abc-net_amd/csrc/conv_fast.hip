@@ -21,24 +21,7 @@
 
 using namespace abc_cf;
 
-// Round-5 experiments on the 192 x 128 weights-direct tile, compiled into the DEBUG flavour only (ABC_KERNEL_DEBUG=1 ./build_hip.sh) and
-// selected there by the hooks abc_debug_conv_nw / _lp / _var (profiles/tools/ab_conv128.py).  All three are exact (bit-identical
-// outputs); none is faster than the form below (profiles/README.md "Round 5"):
-//   conv_fast8.hip    8-wave workgroups (3 x 1 MFMA tiles per wave, 128 VGPRs, four waves per SIMD): 10-17 % SLOWER
-//   conv_fast_lp.hip  lane = pixel epilogue (MFMA operands swapped, 16-byte stores from registers, no LDS staging, no barrier at the tile's
-//                     end, statistics by a cross-lane butterfly): within 2 % either way; with act_bwd in the epilogue 15 % slower
-//                     ... and VAR: the four waves side by side along N (half the weight-fragment loads), s_setprio around the MFMA groups: +-1 %
-#ifdef ABC_KERNEL_DEBUG
-int abc_conv_fast_launch8(const FastK& k, const abc_fast_geom& g, int epi, hipStream_t st);
-int abc_conv_fast_launch_lp(const FastK& k, const abc_fast_geom& g, int epi, hipStream_t st);
-#endif
-
 namespace {
-
-static long long* g_prof = nullptr;
-static int g_force_var = 0;     // measurement hook (abc_debug_conv_var): VAR of conv_fast_body.hpp for the 192 x 128 weights-direct tile
-static int g_force_lp = 0;      // measurement hook (abc_debug_conv_lp, DEBUG flavour): 1 = plan the lane = pixel form (conv_fast_lp.hip) where it applies
-static int g_force_nw = 0;     // measurement hook (abc_debug_conv_nw): 8 = plan the 8-wave form (conv_fast8.hip) where it applies
 
 // Up to four convolutions of ONE geometry as one launch, blockIdx.y picks the descriptor: the four output-parity phases of a
 // ConvTranspose2d(k3, s2) forward (unet.py:44) -- each a 1 / 2 / 2 / 4-tap convolution over the same input into interleaved output
@@ -56,24 +39,14 @@ int launch_inst(const FastK& k, const abc_fast_geom& g, hipStream_t st) {
     }
     if constexpr (BN >= 64 && STRIDE == 1 && CK == 32 && sizeof(CT) == 2) {
         // 3x3 (any 9-tap list) over 64-byte chunks: weights straight from global memory into the MFMA operands
-#ifdef ABC_KERNEL_DEBUG
-        if constexpr (BN == 128 && MT == 6 && sizeof(InT) == 2 && sizeof(OutT) == 2 && (EPI == 0 || EPI == 2)) {
-            if (g.wd == 9 && g.nw == 8) return abc_conv_fast_launch8(k, g, EPI, st);
-            if (g.wd == 9 && (g.lp || g.var)) return abc_conv_fast_launch_lp(k, g, EPI, st);
-        }
-#endif
         if constexpr (((BN == 128 && (MT == 6 || MT == 4)) || (BN == 64 && MT == 8)) && sizeof(InT) == 2 && sizeof(OutT) == 2 && (EPI == 0 || EPI == 2)) {
             // the 16x16x32 form of the same tile (whole tiles, sums and squares only: abc_fast_geom.m16)
-            if (g.wd == 9 && g.m16) return launch_st<InT, CT, OutT, CK, BN, STRIDE, MT, false, 9, EPI, 4, false, 0, true>(k, g, st);
+            if (g.wd == 9 && g.m16) return launch_st<InT, CT, OutT, CK, BN, STRIDE, MT, false, 9, EPI, true>(k, g, st);
         }
         if (g.wd == 9) return launch_st<InT, CT, OutT, CK, BN, STRIDE, MT, false, 9, EPI>(k, g, st);
     }
     if constexpr (BN >= 64 && STRIDE == 2 && MT == 4 && CK == 32 && sizeof(InT) == 2 && sizeof(CT) == 2 && sizeof(OutT) == 2 && EPI == 0) {
         if (g.wd == 9) return launch_st<InT, CT, OutT, CK, BN, STRIDE, MT, false, 9, EPI>(k, g, st);
-    }
-    if constexpr (BN == 32 && MT == 8 && STRIDE == 1 && CK == 32 && sizeof(CT) == 2 && EPI == 0) {
-        // unet2's 5x5 32 -> 32 convolutions: 25 taps, a ring of 5
-        if (g.wd == 25) return launch_st<InT, CT, OutT, CK, BN, STRIDE, MT, false, 25>(k, g, st);
     }
     return launch_st<InT, CT, OutT, CK, BN, STRIDE, MT, false, 0, EPI>(k, g, st);
 }
@@ -106,20 +79,9 @@ int launch_bn(const FastK& k, const abc_fast_geom& g, int stride, hipStream_t st
 
 }  // namespace
 
-// debugging hook (not part of the public ABI): device buffer of 8 x int64 per workgroup for phase timestamps
-extern "C" void abc_debug_conv_prof(void* p) { g_prof = (long long*)p; }
-// measurement hook (not part of the public ABI; profiles/tools/ab_conv128.py): 8 = plan the 8-wave form (conv_fast8.hip: measured SLOWER, profiles/README.md round 5) where it applies, 0 = default.
-// Process-wide and read at plan AND launch time: set it before any plan is built, never between a plan and its launches.
-#ifdef ABC_KERNEL_DEBUG
-extern "C" void abc_debug_conv_nw(int nw) { g_force_nw = nw; }
-extern "C" void abc_debug_conv_lp(int lp) { g_force_lp = lp; }
-extern "C" void abc_debug_conv_var(int var) { g_force_var = var; }
-#endif
-
 // Geometry of the lean kernel for this descriptor, or eligible = 0 (-> the general kernel of conv_igemm.hip).
 int abc_conv_fast_geom(const abc_conv_desc* d, abc_fast_geom* g) {
     g->eligible = 0;
-    if (abc_knob("ABC_CONV_NOFAST")) return ABC_OK;
     if (d->src.pool || d->src.planar || d->src.drop_p > 0.f || d->planar_out) return ABC_OK;
     const int csz = abc_dsize(d->dtype_c);
     const bool f8 = d->dtype_c == ABC_FP8 || d->dtype_out == ABC_FP8 || d->dtype_in == ABC_FP8;
@@ -155,17 +117,13 @@ int abc_conv_fast_geom(const abc_conv_desc* d, abc_fast_geom* g) {
     // prologue + epilogue; rounds = ceil(tiles / 512 slots).  Deep layers (12x12 .. 24x24 pixels, K loops of 80 .. 160
     // stages) thus get narrow tiles with few tap groups, wide layers the biggest tile that fits the registers.
     const int bn_nat = (d->Cout_pad % 128 == 0) ? 128 : (d->Cout_pad % 64 == 0 ? 64 : 32);
-    const char* force = abc_knob("ABC_CONV_MT");
-    const char* force_bn = abc_knob("ABC_CONV_BN");
     int best = -1, best_bn = 0;
     double best_cost = 0;
     for (int bn = bn_nat; bn >= 32; bn >>= 1) {
         if (bn < 64 && bn != bn_nat) break;          // only 128 -> 64 is offered as a narrower tile
-        if (force_bn && atoi(force_bn) != bn) continue;
         const int cand_all[4] = {8, 6, 4, 2};
         for (int ci = 0; ci < 4; ++ci) {
             const int mt = cand_all[ci];
-            if (force && atoi(force) != mt) continue;
             if (mt == 6 && (bn != 128 || d->stride != 1)) continue;
             if ((f8 || d->heads_epi != nullptr) && (mt != 6 || bn != 128)) continue;
             if (mt == 8 && bn == 128) continue;  // 4 x 2 tiles per wave + staging registers exceed 256 VGPRs
@@ -196,10 +154,9 @@ int abc_conv_fast_geom(const abc_conv_desc* d, abc_fast_geom* g) {
     g->MT = best;
     g->BN = best_bn;
     g->nbn = d->Cout_pad / g->BN;
-    g->nw = 4;
-    int tn = g->BN >= 64 ? g->BN / 64 : 1;
-    int stg = 4 * 32 * (tn * 32 * osz + 16);
-    int red = 4 * 4 * g->BN * 4;
+    const int tn = g->BN >= 64 ? g->BN / 64 : 1;
+    const int stg = 4 * 32 * (tn * 32 * osz + 16);
+    const int red = 4 * 4 * g->BN * 4;
     const int prow = 2 * g->MT;
     g->HH = (prow - 1) * d->stride + (dymax - dymin) + 1;
     g->HW = 15 * d->stride + (dxmax - dxmin) + 1;
@@ -211,7 +168,6 @@ int abc_conv_fast_geom(const abc_conv_desc* d, abc_fast_geom* g) {
     // stages amortise the per-stage control code; a second halo buffer hides the chunk turn-over.  Prefer the big
     // stage, then the second halo buffer, as the 80 KB allow.
     int sr = SR_MAX;
-    { const char* e = abc_knob("ABC_CONV_SR"); if (e) sr = atoi(e); }
     int tg = 1, abufs = 1;
     for (;;) {
         tg = sr / g->BN; if (tg < 1) tg = 1;
@@ -225,41 +181,20 @@ int abc_conv_fast_geom(const abc_conv_desc* d, abc_fast_geom* g) {
     (void)abufs;
     // weights-direct main loop (3x3 over 64-byte bf16 chunks, tiles of >= 64 channels): no weights in LDS at all
     {
-        const char* e = abc_knob("ABC_CONV_NOWD");   // "1": never; "2": only the 192 x 128 tile (experiments)
-        const int lim = e ? atoi(e) : 0;
         // (stride 2, bf16 in and out: the data gradients of the transposed convolutions -- 9 taps over a 17 x 33-pixel halo per 8 x 16 tile)
-        const bool s2 = d->stride == 2 && g->MT == 4 && d->dtype_in == ABC_BF16 && d->dtype_c == ABC_BF16 && d->dtype_out == ABC_BF16 && !abc_knob("ABC_CONV_NOWD_S2");
-        g->wd = (csz <= 2 && CKB == 64 && g->BN >= 64 && (d->stride == 1 || s2) && d->ntaps == 9 && lim != 1 && (lim != 2 || (g->BN == 128 && g->MT == 6))) ? 9 : 0;
+        const bool s2 = d->stride == 2 && g->MT == 4 && d->dtype_in == ABC_BF16 && d->dtype_c == ABC_BF16 && d->dtype_out == ABC_BF16;
+        g->wd = (csz <= 2 && CKB == 64 && g->BN >= 64 && (d->stride == 1 || s2) && d->ntaps == 9) ? 9 : 0;
         if (f8 && (g->wd != 9 || g->BN != 128 || g->MT != 6)) return ABC_OK;
-        // (25-tap form for unet2's 5x5 32 -> 32 layers: measured SLOWER than the LDS-staged weights, 136 vs 121 us -- a
-        //  32-channel tile has only 4 MFMAs per tap to cover the global-load latency of the ring; opt-in for experiments)
-        if (csz == 2 && g->CK == 32 && g->BN == 32 && g->MT == 8 && d->stride == 1 && d->ntaps == 25 && abc_knob("ABC_CONV_WD25")) g->wd = 25;
     }
     if (g->wd) g->sB_bytes = 0;
-    // eight waves per workgroup (conv_fast8.hip): the bf16 192 x 128 weights-direct tile, plain or with act_bwd in the epilogue
-    if (g->wd == 9 && g->BN == 128 && g->MT == 6 && !f8 && d->dtype_in == ABC_BF16 && d->dtype_c == ABC_BF16 && d->dtype_out == ABC_BF16 &&
-        d->heads_epi == nullptr && g_force_nw == 8) {
-        g->nw = 8; tn = 1;
-        stg = 8 * 32 * (tn * 32 * osz + 16);
-    }
-    // lane = pixel epilogue (conv_fast_lp.hip): the bf16 192 x 128 weights-direct tile storing whole channel octets, sums and squares only
-    g->lp = (g->wd == 9 && g->nw == 4 && g->BN == 128 && g->MT == 6 && !f8 && d->dtype_in == ABC_BF16 && d->dtype_c == ABC_BF16 && d->dtype_out == ABC_BF16 &&
-             d->heads_epi == nullptr && d->stats_rows != 4 && !d->accumulate && d->Cout % 8 == 0 && (d->ldy | d->cout_off) % 8 == 0 && g_force_lp == 1) ? 1 : 0;
-    if (g->lp) { stg = 0; red = 0; }       // (no staging, no reduction through LDS)
-    g->var = 0;
-    if (g_force_var && g->wd == 9 && g->nw == 4 && g->BN == 128 && g->MT == 6 && !f8 && d->dtype_in == ABC_BF16 && d->dtype_c == ABC_BF16 && d->dtype_out == ABC_BF16 &&
-        d->heads_epi == nullptr) {
-        g->var = g_force_var & 3;
-        if ((g->var & 1) && !g->lp) stg = 4 * 32 * (32 * osz + 16);      // (1 x 4 waves: 32-channel staging rows)
-    }
     // v_mfma_f32_16x16x32_bf16 form (conv_fast_body.hpp M16): the bf16 192 x 128 weights-direct tile where every tile takes the whole-tile epilogue
     // (192 x 128 pixels x channels everywhere; 128 x 128 and 256 x 64 where the epilogue carries no statistics -- the folded inference graph:
     //  +3 % on b64 @ 512 x 512 with them; in the training step, whose epilogues sum and square every value, they measure the same or slightly
     //  slower in this form, 5.924 -> 5.930 ms same box)
     const bool m16_shape = (g->BN == 128 && g->MT == 6) || (d->stats == nullptr && ((g->BN == 128 && g->MT == 4) || (g->BN == 64 && g->MT == 8)));
-    g->m16 = (g->wd == 9 && g->nw == 4 && !g->lp && !g->var && m16_shape && d->stride == 1 && !f8 && d->dtype_in == ABC_BF16 && d->dtype_c == ABC_BF16 &&
+    g->m16 = (g->wd == 9 && m16_shape && d->stride == 1 && !f8 && d->dtype_in == ABC_BF16 && d->dtype_c == ABC_BF16 &&
               d->dtype_out == ABC_BF16 && d->heads_epi == nullptr && d->stats_rows != 4 && !d->accumulate && d->Cout % 8 == 0 && (d->ldy | d->cout_off) % 8 == 0 &&
-              d->Wg % 16 == 0 && (d->Hg % (2 * g->MT) == 0 || d->stats == nullptr) && !abc_knob("ABC_CONV_NOM16")) ? 1 : 0;
+              d->Wg % 16 == 0 && (d->Hg % (2 * g->MT) == 0 || d->stats == nullptr)) ? 1 : 0;
     // whole weight set resident (narrow layers: one chunk, one n-block): persistent workgroups
     g->b_static = (!actb && !g->wd && g->BN == 32 && nchunks == 1 && g->nbn == 1 && g->sA_bytes + g->ngroups * g->sB_bytes + stg + red <= budget &&
                    abc_cdiv(g->HH * g->HW * segs, FT) <= fa_static(g->MT)) ? 1 : 0;
@@ -284,8 +219,8 @@ int abc_conv_fast_geom(const abc_conv_desc* d, abc_fast_geom* g) {
     if (g->lds < g->red_off + red) g->lds = g->red_off + red;
     g->ystg_off = abc_roundup(g->lds, 256);      // (behind everything: the tap and coefficient tables outlive the tile)
     if (actb) g->lds = g->ystg_off + stg;
-    g->epi_off = abc_roundup(g->lds, 256);       // LP, M16: [2][1 or 6][BN] floats
-    if (g->lp || g->m16) g->lds = g->epi_off + 2 * (actb ? 6 : 1) * g->BN * 4;
+    g->epi_off = abc_roundup(g->lds, 256);       // M16: [2][1 or 6][BN] floats
+    if (g->m16) g->lds = g->epi_off + 2 * (actb ? 6 : 1) * g->BN * 4;
     if (g->lds > LDS_WG) return ABC_OK;
     g->tiles_x = abc_cdiv(d->Wg, 16);
     g->tiles_y = abc_cdiv(d->Hg, prow);
@@ -293,7 +228,7 @@ int abc_conv_fast_geom(const abc_conv_desc* d, abc_fast_geom* g) {
     // persistent workgroups: three per CU with resident weights; two per CU (512 slots) on the weights-direct loop when
     // there are more tiles than slots (measured on one box, same run: 6144 tiles 482 -> 463 us, 5632 tiles 473 -> 448 us)
     const int slots3 = abc_wg_slots(3), slots2 = abc_wg_slots(2);      // (768 / 512 unless CUs are reserved, abc_set_reserved_cus)
-    g->nwg = g->b_static ? (g->ntiles < slots3 ? g->ntiles : slots3) : ((g->wd && g->ntiles > slots2 && !abc_knob("ABC_CONV_NOPERSIST")) ? slots2 : g->ntiles);
+    g->nwg = g->b_static ? (g->ntiles < slots3 ? g->ntiles : slots3) : ((g->wd && g->ntiles > slots2) ? slots2 : g->ntiles);
     if (d->heads_epi != nullptr) {
         // heads in the epilogue: the 192 x 128 weights-direct tile, finished input, every 128-channel block a head
         if (!(g->wd == 9 && g->BN == 128 && g->MT == 6) || d->src.scale != nullptr || !d->out_act || d->stats != nullptr || d->accumulate ||
@@ -326,10 +261,6 @@ static void fill_fastk(const abc_conv_desc* d, const abc_fast_geom& g, FastK& k)
     k.ab_sc = d->actbwd_scale; k.ab_sh = d->actbwd_shift; k.ab_sl = d->actbwd_slope; k.ab_mu = d->actbwd_mean; k.ab_is = d->actbwd_invstd;
     k.ystg_off = g.ystg_off;
     k.epi_off = g.epi_off;
-    { const char* e = abc_knob("ABC_CONV_DBG"); k.dbg = e ? atoi(e) : 0; }  // timing ablations only (results invalid)
-    k.prof = g_prof;
-    { const char* e = abc_knob("ABC_CONV_PROF_ROUND"); k.prof_round = e ? atoi(e) : -1; }
-    { const char* e = abc_knob("ABC_CONV_STAGGER"); k.stagger = e ? atoi(e) : 0; }
     k.bytesA = (unsigned)((int64_t)d->B * d->src.Hx * d->src.Wx * d->src.ldx * abc_dsize(d->dtype_in));
     k.bytesW = (unsigned)((int64_t)d->ntaps * k.nchunks * d->Cout_pad * g.CK * abc_dsize(d->dtype_c));
     for (int t = 0; t < d->ntaps; ++t) {

@@ -1,5 +1,4 @@
-// The lean convolution kernel's device code (see conv_fast.hip for the design notes): shared by conv_fast.hip (4-wave workgroups)
-// and conv_fast8.hip (8-wave workgroups on the 192-pixel x 128-channel weights-direct tile).
+// The lean convolution kernel's device code (see conv_fast.hip for the design notes).
 #pragma once
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
@@ -8,10 +7,6 @@
 #include <stdlib.h>
 #include <math.h>
 #include <type_traits>
-
-#ifndef ABC_DEEP_TM
-#define ABC_DEEP_TM 2      // deep operand pipelining (DEEP below) for wave tiles of up to this many 32-pixel M-tiles x one 32-channel N-tile
-#endif
 
 namespace abc_cf {
 
@@ -38,48 +33,27 @@ struct FastK {
     int Hg, Wg, Hout, Wout, ldy, cout_off, Cout, Cout_pad, om, oy0, ox0;
     int ntaps, tg, ngroups, dy_min, dx_min, HH, HW, RS, magic;
     int tiles_x, tiles_y, nblocks_n, ntiles;
-    int sA_bytes, a_bufs, sB_off, sB_bytes, tap_off, coef_off, cstride, stats_rows, accumulate, b_static, stg_off, red_off, dbg, stagger;
+    int sA_bytes, a_bufs, sB_off, sB_bytes, tap_off, coef_off, cstride, stats_rows, accumulate, b_static, stg_off, red_off;
+    // (field order below: it keeps the argument offsets the kernels were tuned with -- other orders of the same fields moved the
+    //  register allocation of several instantiations by a VGPR or into scratch)
+    int ystg_off;                   // a second staging region (the y_raw tile's way into the accumulator layout)
+    int epi_off;                    // M16: the epilogue's per-channel tables, [2 rounds][1 (bias) + 5 (ACTB)][BN] floats
     int out_act; float out_slope;   // epilogue activation (BatchNorm folded into the weights: eval mode)
     const float* oscale;            // fp8 compute: per output channel, accumulator -> real value (s_in * s_w[n])
     const float* oquant;            // fp8 output: 1 / s_out (device), applied before the rounding to e4m3
-    int oq_stride;                  // 0: a scalar; 1: one per n-block (128 output channels)
     const abc_heads_epi* hepi;      // HEPI: per n-block (= head) the 1x1 convolution computed in this tile's epilogue
     // ACTB (abc_conv_desc.actbwd_*): this data gradient is d(activation output) of the producing layer; the epilogue turns it into
     // d(BatchNorm output) and sums that layer's BatchNorm-backward statistics -- bn_act.hip's act_bwd pass, not run
     const void* ab_y; int ab_ld;    // the producer's raw convolution output (already at its channel 0), its row length
     const float *ab_sc, *ab_sh, *ab_sl, *ab_mu, *ab_is;
-    int ystg_off;                   // a second staging region (the y_raw tile's way into the accumulator layout)
-    int epi_off;                    // LP: the epilogue's per-channel tables, [2 rounds][1 (bias) + 5 (ACTB)][BN] floats
     unsigned bytesA, bytesW;
-    long long* prof;  // debugging: per-workgroup phase timestamps (null in production)
-    int prof_round;   // debugging: stamp the tile of this round only (< 0: every round, the last one stays)
+    int oq_stride;                  // fp8 output: 0 = oquant is a scalar; 1: one per n-block (128 output channels)
     int8_t ty[ABC_MAX_TAPS], tx[ABC_MAX_TAPS];
 };
 
 __device__ inline void lds_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// Sum of v[k] over the 32 lanes of a wave half, for 16 values at once: a halving butterfly (each step a lane keeps half of its values and
-// adds its partner's copies of them).  On return the lane with index r (0..31 inside its half) holds the total of v[(r >> 1) & 15]; the
-// order of the additions is fixed.  Step 1 pairs lane r with r ^ 16 through v_permlane16_swap (rows 0 <-> 1 of the half: after the swap
-// BOTH registers of a pair hold what this lane keeps -- its own and the partner's), steps 2-5 with r ^ 15, r ^ 7, r ^ 3, r ^ 1 through DPP.
-__device__ inline float lane_reduce16(const float* v, int r) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    float w[8], u[4], x[2];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const u32x2 p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[t]), __float_as_uint(v[t + 8]), false, false);
-        w[t] = __uint_as_float(p[0]) + __uint_as_float(p[1]);
-    }
-    const bool b3 = (r >> 3) & 1, b2 = (r >> 2) & 1, b1 = (r >> 1) & 1;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) u[t] = (b3 ? w[t + 4] : w[t]) + dpp_mov<0x140>(b3 ? w[t] : w[t + 4]);      // row_mirror: r ^ 15
-#pragma unroll
-    for (int t = 0; t < 2; ++t) x[t] = (b2 ? u[t + 2] : u[t]) + dpp_mov<0x141>(b2 ? u[t] : u[t + 2]);      // row_half_mirror: r ^ 7
-    const float y = (b1 ? x[1] : x[0]) + dpp_mov<0x1B>(b1 ? x[0] : x[1]);                                  // quad_perm [3,2,1,0]: r ^ 3
-    return y + dpp_mov<0xB1>(y);                                                                            // quad_perm [1,0,3,2]: r ^ 1
-}
-
-// WD ("weights direct", 0 = off, else the tap count 9 or 25): the main loop below that streams the B operand from global
+// WD ("weights direct", 0 = off, 9 = a 9-tap list): the main loop below that streams the B operand from global
 // memory (see there).
 // HEPI ("heads in the epilogue", folded inference graph): the tile's 128 output channels are one head's finished features
 // (unet.py:66-69 with BatchNorm folded); the head's 1x1 convolution (unet.py:70) is computed from them right here and the f32
@@ -92,26 +66,16 @@ __device__ inline float lane_reduce16(const float* v, int r) {
 // FLOP/s in bare loops): a timing probe that issued two 16x16x32 per 32x32x16 on the same registers read 295 -> 245 us on the heads' conv1
 // and 45 -> 41.5 us on a trunk layer before this form existed.  The epilogue differs in its lane mapping only (a lane owns two channels
 // x eight pixels of a 32 x 32 block instead of one channel x sixteen pixels); the store sweep is the same.
-template <typename InT, typename CT, typename OutT, int CK, int BN, int STRIDE, int MT, bool STATIC, int WD = 0, int EPI = 0, int NW = 4, bool LP = false, int VAR = 0, bool M16 = false>
+template <typename InT, typename CT, typename OutT, int CK, int BN, int STRIDE, int MT, bool STATIC, int WD = 0, int EPI = 0, bool M16 = false>
 __device__ __forceinline__ void conv_fast_body(const FastK& a) {
-    // NW waves per workgroup.  8 (the 192-pixel x 128-channel weights-direct tile only): the SAME tile, halo and grid, but a wave owns
-    // 3 x 1 instead of 3 x 2 MFMA tiles -- 48 accumulator registers, the kernel fits 128 VGPRs, two workgroups = FOUR waves per SIMD:
-    // a tile's life (prologue, main loop, epilogue) was what bounded the 4-wave form, whose lone wave per SIMD and workgroup runs
-    // its main loop at a third of the matrix pipe's rate (profiles/HISTORY.md section 3)
-    constexpr int FT = 64 * NW;
-    static_assert(NW == 4 || (NW == 8 && WD == 9 && BN == 128 && MT == 6 && !STATIC), "8-wave workgroups: the 192 x 128 weights-direct tile");
     constexpr int CKB = CK * (int)sizeof(CT);
     constexpr int PS = CKB + 16;
     constexpr int LHB = CKB / 2;
     constexpr int NR = LHB / 16;
     constexpr int SEGS = CKB / 16;
     constexpr int NT = BN / 32;
-    // VAR (experiments, measured in profiles/README.md round 5): bit 0 = the four waves side by side along N (1 x 4: a wave owns all of the
-    // tile's pixels for 32 channels -- half the weight-fragment loads per MFMA, twice the LDS fragment reads); bit 1 = s_setprio around the MFMA groups
-    constexpr bool W14 = (VAR & 1) != 0, SPRIO = (VAR & 2) != 0;
-    static_assert(!W14 || (NW == 4 && NT == 4 && WD == 9), "1 x 4 waves: the 128-channel weights-direct tile");
-    constexpr int WN = (NW == 8 || W14) ? 4 : ((NT >= 2) ? 2 : 1);
-    constexpr int WM = NW / WN;
+    constexpr int WN = (NT >= 2) ? 2 : 1;
+    constexpr int WM = (FT / 64) / WN;
     constexpr int TM = MT / WM;
     constexpr int TN = NT / WN;
     static_assert(TM >= 1 && TM * WM == MT && TN >= 1 && TN * WN == NT, "tile/wave layout");
@@ -122,18 +86,9 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
     static_assert(!F8C || WD == 9, "fp8 compute is served by the 9-tap weights-direct loop");
     constexpr bool HEPI = EPI == 1;     // the heads' 1x1 convolutions in the epilogue
     constexpr bool ACTB = EPI == 2;     // the activation / BatchNorm-statistics backward pass of the PRODUCER of this data gradient in the epilogue
-    static_assert(!HEPI || (WD == 9 && BN == 128 && MT == 6 && sizeof(CT) <= 2 && NW == 4), "heads epilogue: the 192 x 128 weights-direct tile");
+    static_assert(!HEPI || (WD == 9 && BN == 128 && MT == 6 && sizeof(CT) <= 2), "heads epilogue: the 192 x 128 weights-direct tile");
     static_assert(!ACTB || (!STATIC && sizeof(OutT) == 2 && sizeof(CT) == 2), "act_bwd epilogue: bf16 gradients, streamed weights");
-    // LP ("lane = pixel"): the MFMA operands swapped -- A = the weight fragment, B = the pixel fragment, the SAME registers -- so that a
-    // lane of the accumulator holds 16 CHANNELS of ONE pixel (register k = channel (k & 3) + 8 (k >> 2) + 4 h of the n-tile) instead of 16
-    // pixels of one channel.  Four consecutive channels pack into 8 bytes, one v_permlane32_swap per dword pairs them with the other lane
-    // half's four (cdna_hip_programming.md T21), and the tile leaves in 16-byte stores straight from registers: NO LDS staging, no wait on
-    // an LDS round trip, no workgroup barrier between a tile's last MFMA and the next tile's first halo commit (the staging aliased the
-    // halo buffers; the statistics went through an LDS reduction behind a barrier).  Per-channel sums now run ACROSS lanes: a halving
-    // butterfly (v_permlane16_swap + DPP mirrors: 38 instructions per 16 channels, fixed order) leaves each channel's total in one lane, and
-    // every wave writes its own partial row (rows per tile = WM).  Measured: profiles/README.md round 5.
-    static_assert(!LP || (WD == 9 && !STATIC && !HEPI && sizeof(OutT) == 2 && sizeof(CT) == 2 && NW == 4), "lane = pixel: the bf16 weights-direct kernels");
-    static_assert(!M16 || (WD == 9 && !STATIC && !HEPI && !LP && VAR == 0 && NW == 4 && STRIDE == 1 && sizeof(InT) == 2 && sizeof(CT) == 2 && sizeof(OutT) == 2 && BN >= 64),
+    static_assert(!M16 || (WD == 9 && !STATIC && !HEPI && STRIDE == 1 && sizeof(InT) == 2 && sizeof(CT) == 2 && sizeof(OutT) == 2 && BN >= 64),
                   "16x16x32 form: the bf16 weights-direct kernels, stride 1");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -146,8 +101,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
     const int lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
-    long long* prof = ABC_PROF(a.prof ? a.prof + (size_t)blockIdx.x * 8 : nullptr);
-    if (prof && tid == 0) { prof[0] = wall_clock64(); unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); prof[6] = ((long long)xcc << 32) | hw; }
 
     if (tid < a.ntaps) sTap[tid] = a.ty[tid] * a.RS + a.tx[tid] * PS;
     const bool has_coef = a.scale != nullptr;
@@ -191,12 +144,12 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
     const unsigned bvoff0 = (unsigned)tl0 * tap_stride + (unsigned)rem0 * 16u;
     const int bdst0 = (tl0 * BN + rem0 / SEGS) * PS + (rem0 % SEGS) * 16;
     u32x4 breg[2][NB];
-    constexpr bool DEEP = WD == 9 && !F8C && !STATIC && NW == 4 && !LP && !M16 && TN == 1 && TM <= ABC_DEEP_TM;      // (see the weights-direct loop)
+    constexpr bool DEEP = WD == 9 && !F8C && !STATIC && !M16 && TN == 1 && TM <= 2;      // (see the weights-direct loop)
     // DEEP2 (measured, off): the halo of chunk c + 2 in flight while chunk c multiplies (two staging register sets, chunk k in set k & 1).
     // It does NOT help -- 24.8 -> 26.2 us on the 24 x 24 layers, 24.3 -> 26.7 us on the 12 x 12 ones: a chunk's end waits for the commit's
     // arithmetic and the barrier, not for the halo loads (profiles/README.md round 5)
     constexpr bool DEEP2 = false;
-    HaloTile<InT, CT, CK, STATIC ? fa_static(MT) : (STRIDE == 2 ? fa_stride2() : (fa_max(MT) + NW / 4 - 1) / (NW / 4)), FT, DEEP2 ? 2 : 1> apre;
+    HaloTile<InT, CT, CK, STATIC ? fa_static(MT) : (STRIDE == 2 ? fa_stride2() : fa_max(MT)), FT, DEEP2 ? 2 : 1> apre;
 
     unsigned w_n0 = 0;  // byte offset of the n-block's first weight row
     auto b_issue = [&](u32x4* set, int c, int g) {
@@ -238,14 +191,9 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
         const int cnt = q + (x < rem ? 1 : 0), b0 = x * q + (x < rem ? x : rem);
         return i < cnt ? base + b0 + i : -1;
     };
-    // LP with two halo buffers: the buffer parity runs on ACROSS tiles (a tile's first chunk goes into the buffer its predecessor's last
-    // chunk did not use), so that a wave may commit the next tile's first chunk while others still read the last chunk of this one
-    int cpar = 0;
     float* const sEpi = (float*)(smem + a.epi_off);
-    constexpr int NTAB = ACTB ? 6 : 1;      // LP: rows of the epilogue table (bias; act_bwd: scale, shift, slope, mean, 1 / std)
+    constexpr int NTAB = ACTB ? 6 : 1;      // M16: rows of the epilogue table (bias; act_bwd: scale, shift, slope, mean, 1 / std)
     for (int round = 0, tile = tile_of(0); tile >= 0; tile = tile_of(++round)) {
-        const bool pr = prof && tid == 0 && (a.prof_round < 0 || a.prof_round == round);
-        if (pr) { prof[5] = wall_clock64(); prof[7] = round; }
         int id = tile;
         const int nb = id % a.nblocks_n; id /= a.nblocks_n;
         const int mblock = id;
@@ -263,18 +211,17 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + (wn * TN + j) * 32 + r;
             nval[j] = n < a.Cout;
-            bv[j] = (!LP && !M16 && a.bias != nullptr && nval[j]) ? a.bias[n] : 0.f;
+            bv[j] = (!M16 && a.bias != nullptr && nval[j]) ? a.bias[n] : 0.f;
             osc[j] = (F8C && nval[j]) ? a.oscale[n] : 1.f;
         }
-        // LP: the epilogue reads its per-channel constants from an LDS table of the n-block (a lane owns 16 channels of every n-tile);
-        // loaded here, written behind the halo commit, visible after the barrier that opens the main loop.  Two copies (round parity):
-        // a wave in the next tile's prologue must not overwrite what a slower wave's epilogue still reads.
-        // (M16 too: its lanes own two channels per n-tile -- twice the lane constants of the 32x32 form, and held in registers across the main
-        //  loop they pushed its operand addresses into scratch, reloaded between the MFMA groups behind the whole weight ring)
-        constexpr bool ETAB = LP || M16;
-        float etab[ETAB ? NTAB : 1];
-        const bool etab_fill = ETAB && (first_tile || a.nblocks_n > 1) && tid < BN;
-        if constexpr (ETAB) {
+        // M16: the epilogue reads its per-channel constants from an LDS table of the n-block (its lanes own two channels per n-tile -- twice
+        // the lane constants of the 32x32 form, and held in registers across the main loop they pushed its operand addresses into scratch,
+        // reloaded between the MFMA groups behind the whole weight ring); loaded here, written behind the halo commit, visible after the
+        // barrier that opens the main loop.  Two copies (round parity): a wave in the next tile's prologue must not overwrite what a slower
+        // wave's epilogue still reads.
+        float etab[M16 ? NTAB : 1];
+        const bool etab_fill = M16 && (first_tile || a.nblocks_n > 1) && tid < BN;
+        if constexpr (M16) {
             if (etab_fill) {
                 const int n = n0 + tid;
                 const bool ok = n < a.Cout;
@@ -287,7 +234,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
         }
         const float oq = F8O ? a.oquant[nb * a.oq_stride] : 1.f;
         float csc[ACTB ? TN : 1], csh[ACTB ? TN : 1], csl[ACTB ? TN : 1], cmu[ACTB ? TN : 1];
-        if constexpr (ACTB && !LP && !M16) {
+        if constexpr (ACTB && !M16) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int n = n0 + (wn * TN + j) * 32 + r;
@@ -333,7 +280,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
         // the matrix pipe 10-20 % busy).  So: the weight fragments of a WHOLE chunk in flight (ring of 9: TN = 1, 72 registers -- these
         // instantiations use 120-150 of their 256) and the pixel fragments of tap t + 2 read while tap t multiplies.
         // Measured (same box, rocprofv3 of the graph run): the 64-channel blocks at 24 x 24 26.4 -> 24.8 us, at 12 x 12 29.3 -> 24.3 us.
-        constexpr int RING = WD == 25 ? 5 : ((DEEP && TM <= 2) ? 9 : 3);        // taps in flight; divides the tap count
+        constexpr int RING = DEEP ? 9 : 3;        // taps in flight; divides the tap count
         static_assert(WNT % RING == 0 || !WD, "ring must divide the tap count");
         u32x4 bq[(WD && !F8C) ? RING : 1][TN][2];
         i32x8 bq8[F8C ? RING : 1][TN];     // e4m3: a tile's B operand is one 8-register tuple (both 16-byte halves)
@@ -385,11 +332,9 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
 #pragma unroll
                 for (int k = 0; k < 16; ++k) acc[i][j][k] = 0.f;
         }
-        if constexpr (!LP) {
-            if (!first_tile) __syncthreads();  // previous tile's epilogue staging (aliases the halo buffer) is drained
-        }
-        apre.commit(sA + ((LP && a.a_bufs == 2) ? (cpar & 1) * a.sA_bytes : 0), lcoef, a.cstride, tid);
-        if constexpr (ETAB) {
+        if (!first_tile) __syncthreads();  // previous tile's epilogue staging (aliases the halo buffer) is drained
+        apre.commit(sA, lcoef, a.cstride, tid);
+        if constexpr (M16) {
             if (etab_fill) {
                 float* tb = sEpi + ((a.nblocks_n > 1) ? (round & 1) : 0) * (NTAB * BN) + tid;      // (one n-block: written once, never overwritten)
 #pragma unroll
@@ -406,7 +351,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
         for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(bv[j]), "v"(osc[j]));
         }
         asm volatile("" :: "v"(oq));
-        if constexpr (ACTB && !LP && !M16) {
+        if constexpr (ACTB && !M16) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(csc[j]), "v"(csh[j]), "v"(csl[j]), "v"(cmu[j]));
         }
@@ -425,7 +370,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                 apre.issue(rsA, 0u);
             }
         }
-        if (pr) prof[1] = wall_clock64();
 
         // ---- main loop, unrolled by 2 so that the two register sets have fixed names.  Stage s: its weights sit in
         // sB[s & 1]; set s & 1 is free (committed at the end of stage s-1) and takes the loads of stage s + 2; the next
@@ -434,7 +378,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
             static_assert(NR == 2 && !STATIC, "WD: 64-byte chunks, streamed weights");
             auto chunk = [&](auto PARV, const int c) {
                 constexpr int PAR = decltype(PARV)::value;      // DEEP2: c & 1, the staging set that held this chunk and takes chunk c + 2
-                const char* sAc = sA + ((a.a_bufs == 2) ? ((c + cpar) & 1) * a.sA_bytes : 0);
+                const char* sAc = sA + ((a.a_bufs == 2) ? (c & 1) * a.sA_bytes : 0);
                 const bool more = c + 1 < a.nchunks;
                 if (DEEP2 ? (c + 2 < a.nchunks) : more) {
                     if constexpr (DEEP2) apre.template issue<PAR>(rsA, (unsigned)((c + 2) * CK) * (unsigned)sizeof(InT));
@@ -484,7 +428,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                     }
                 } else if constexpr (DEEP) {
                     // pixel fragments: a ring of AD taps (both 16-byte halves), AD - 1 taps ahead of the MFMAs
-                    constexpr int AD = TM <= 2 ? 3 : 2;
+                    constexpr int AD = 3;
                     frag_t fr[AD][2][TM];
                     auto fr_read = [&](int t) {
                         const int aoff = a.ty[t] * a.RS + a.tx[t] * PS;
@@ -556,30 +500,20 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
 #pragma unroll
                     for (int i = 0; i < TM; ++i) fa1[i] = *(const frag_t*)(sAc + aBase[i] + aoff + 16);
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (SPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            if constexpr (LP) mma16B(acc[i][j], *(const frag_t*)&bq[slot][j][0], fa0[i]);
-                            else mma16B(acc[i][j], fa0[i], *(const frag_t*)&bq[slot][j][0]);
-                        }
-                    if constexpr (SPRIO) __builtin_amdgcn_s_setprio(0);
+                        for (int j = 0; j < TN; ++j) mma16B(acc[i][j], fa0[i], *(const frag_t*)&bq[slot][j][0]);
                     __builtin_amdgcn_sched_barrier(0);
                     if (t < WNT - 1) {
 #pragma unroll
                         for (int i = 0; i < TM; ++i) fa0[i] = *(const frag_t*)(sAc + aBase[i] + aoff_n);
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (SPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            if constexpr (LP) mma16B(acc[i][j], *(const frag_t*)&bq[slot][j][1], fa1[i]);
-                            else mma16B(acc[i][j], fa1[i], *(const frag_t*)&bq[slot][j][1]);
-                        }
-                    if constexpr (SPRIO) __builtin_amdgcn_s_setprio(0);
+                        for (int j = 0; j < TN; ++j) mma16B(acc[i][j], fa1[i], *(const frag_t*)&bq[slot][j][1]);
                     __builtin_amdgcn_sched_barrier(0);
                     // the slot is free: tap t + RING (of this chunk or the next; past the last chunk the offsets run off
                     // the buffer and the loads return zeros -- unconditional, so that vmcnt stays exact)
@@ -589,15 +523,13 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                 if (more) {
                     constexpr int CS = DEEP2 ? 1 - PAR : 0;      // the set that holds chunk c + 1
                     if (a.a_bufs == 2) {
-                        apre.template commit<CS>(sA + ((c + 1 + cpar) & 1) * a.sA_bytes, lcoef ? lcoef + (c + 1) * CK : nullptr, a.cstride, tid);
+                        apre.template commit<CS>(sA + ((c + 1) & 1) * a.sA_bytes, lcoef ? lcoef + (c + 1) * CK : nullptr, a.cstride, tid);
                     } else {
                         __syncthreads();
                         apre.template commit<CS>(sA, lcoef ? lcoef + (c + 1) * CK : nullptr, a.cstride, tid);
                     }
                 }
-                // next chunk's halo visible; after the last chunk: the halo is dead (the epilogue aliases it) -- LP's epilogue uses no
-                // LDS staging, and with two halo buffers the next tile's first chunk goes into the OTHER buffer: no barrier there
-                if (!(LP && !more && a.a_bufs == 2)) __syncthreads();
+                __syncthreads();  // next chunk's halo visible; after the last chunk: the halo is dead (the epilogue aliases it)
             };
             if constexpr (DEEP2) {
                 // (two chunks per trip: the staging set of a chunk is a compile-time index)
@@ -622,7 +554,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                     // (unconditional: past the last stage the offsets run off the buffer and the loads return zeros;
                     //  a conditional issue would make the compiler drain ALL loads before every commit)
                     if constexpr (!STATIC) issue_next(breg[d]);
-                    if (g == 0 && c + 1 < a.nchunks && !(ABC_DBG(a.dbg) & 2)) apre.issue(rsA, (unsigned)((c + 1) * CK) * (unsigned)sizeof(InT));
+                    if (g == 0 && c + 1 < a.nchunks) apre.issue(rsA, (unsigned)((c + 1) * CK) * (unsigned)sizeof(InT));
 
                     {
                         const char* sAc = sA + ((a.a_bufs == 2) ? (c & 1) * a.sA_bytes : 0);
@@ -632,7 +564,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                         // fragment reads software-pipelined one K-step ahead of the MFMAs (two named register sets;
                         // every read unconditional -- the step after the last re-reads the last tap -- so that the
                         // compiler can count lgkmcnt exactly instead of draining the LDS queue before each MFMA group)
-                        const int ntl = (ABC_DBG(a.dbg) & 4) ? 0 : tcnt;
                         if constexpr (NR == 2) {
                             frag_t fa0[TM], fb0[TN], fa1[TM], fb1[TN];
                             int aoff = sTap[t0];
@@ -640,7 +571,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                             for (int i = 0; i < TM; ++i) fa0[i] = *(const frag_t*)(sAc + aBase[i] + aoff);
 #pragma unroll
                             for (int j = 0; j < TN; ++j) fb0[j] = *(const frag_t*)(sBc + bBase[j]);
-                            for (int tl = 0; tl < ntl; ++tl) {
+                            for (int tl = 0; tl < tcnt; ++tl) {
                                 const int tn = min(tl + 1, tcnt - 1);
                                 const int boff = tl * BN * PS;
                                 const int aoff_n = sTap[t0 + tn];
@@ -667,7 +598,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                                 aoff = aoff_n;
                             }
                         } else {
-                            for (int tl = 0; tl < ntl; ++tl) {
+                            for (int tl = 0; tl < tcnt; ++tl) {
                                 const int aoff = sTap[t0 + tl];
                                 const int boff = tl * BN * PS;
                                 frag_t fa[TM], fb[TN];
@@ -684,9 +615,9 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                     }
 
                     if constexpr (!STATIC) {
-                        if (has_next && !(ABC_DBG(a.dbg) & 8)) b_commit(breg[1 - d], gn, sB + (1 - d) * a.sB_bytes);
+                        if (has_next) b_commit(breg[1 - d], gn, sB + (1 - d) * a.sB_bytes);
                     }
-                    if (closes && !(ABC_DBG(a.dbg) & 16)) {
+                    if (closes) {
                         if (a.a_bufs == 2) {
                             apre.commit(sA + (cn & 1) * a.sA_bytes, lcoef ? lcoef + cn * CK : nullptr, a.cstride, tid);
                         } else {
@@ -701,7 +632,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
         }
         }
 
-        if (pr) prof[2] = wall_clock64();
         if constexpr (HEPI) {
             // ---- 1. the tile's activated features, [pixel][128 channels] in the compute type, into LDS (the halo buffers are dead)
             constexpr int FROW = 128 * (int)sizeof(CT) + 16;
@@ -795,146 +725,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                 }
             }
             continue;      // (the next tile's prologue synchronises before it re-uses the LDS; no statistics in the folded graph)
-        }
-        if constexpr (LP) {
-            // ---- lane = pixel epilogue (see LP above): everything from registers.  Lane (r, h) holds pixel r of M-tile i -- patch row
-            // 2 (wm TM + i) + (r >> 4), column r & 15 -- and, of n-tile j, channels 8 q + 4 h + e in registers 4 q + e (q, e = 0..3).
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            constexpr int TW = TN * 32;
-            const int tl = abc_launder(tid), ll = tl & 63, wl = tl >> 6, rl = ll & 31, hl = ll >> 5;
-            const int wml = wl / WN, wnl = wl % WN;
-            const float* tab = sEpi + ((a.nblocks_n > 1) ? (round & 1) : 0) * (NTAB * BN) + wnl * TW + 4 * hl;     // + j * 32 + 8 q: the lane's four channels
-            OutT* yo = (OutT*)a.y;
-            const OutT* ytile = yo + (((size_t)(b * a.Hout + gy0 * a.om + a.oy0) * a.Wout + gx0 * a.om + a.ox0) * a.ldy + a.cout_off + n0);
-            const __amdgpu_buffer_rsrc_t rsY = abc_make_rsrc(ytile, 0x80000000u);
-            const unsigned istep = (unsigned)(2 * a.om * a.Wout * a.ldy) * (unsigned)sizeof(OutT);   // bytes per M-tile (two pixel rows)
-            // a store = 16 bytes per lane: lanes < 32 the channels 16 p .. 16 p + 7 of their pixel, lanes >= 32 the next eight
-            const bool col_ok = gx0 + (rl & 15) < a.Wg;
-            const int rlim = a.Hg - gy0 - (rl >> 4);          // patch rows 2 m with 2 m < rlim lie inside the map (for this lane's row parity)
-            const unsigned voff0 = (unsigned)(wml * TM) * istep +
-                                   (unsigned)((((rl >> 4) * a.Wout + (rl & 15)) * a.om * a.ldy + wnl * TW + 8 * hl) * (int)sizeof(OutT));
-            const float slope = a.out_act ? a.out_slope : 1.f;
-            const bool want_stats = a.stats != nullptr;
-            const bool whole_tile = (gy0 + 2 * MT <= a.Hg) && (gx0 + 16 <= a.Wg);      // (wave-uniform)
-            // Loop order: (n-tile j, channel octet pair p2) outside, the TM M-tiles inside -- the per-channel constants of 8 channels stay in
-            // registers for three stores; the statistics of an n-tile are complete after its two octet pairs.
-            // ACTB: y_raw of this tile in the STORE layout (16 bytes = eight channels of the lane's pixel); the TM loads of an octet pair
-            // are issued one pair ahead of their use.
-            __amdgpu_buffer_rsrc_t rsYR = rsY;
-            unsigned voffy = 0, istep_y = 0;
-            u32x4 yq[ACTB ? 2 : 1][ACTB ? TM : 1];
-            auto yq_load = [&](int set, int jp) {      // jp = 2 j + p2
-                if constexpr (ACTB) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-                        yq[set][i] = __builtin_amdgcn_raw_buffer_load_b128(rsYR, voffy, (unsigned)i * istep_y + (unsigned)(jp * 16 * 2), 0);
-                }
-            };
-            if constexpr (ACTB) {
-                const bf16* yrt = (const bf16*)a.ab_y + (((size_t)(b * a.Hg + gy0) * a.Wg + gx0) * a.ab_ld + n0);
-                rsYR = abc_make_rsrc(yrt, 0x80000000u);
-                istep_y = (unsigned)(2 * a.Wg * a.ab_ld) * 2u;
-                voffy = (unsigned)(wml * TM) * istep_y + (unsigned)((((rl >> 4) * a.Wg + (rl & 15)) * a.ab_ld + wnl * TW + 8 * hl) * 2);
-                yq_load(0, 0);
-            }
-            float s1[16], s2[16];
-            float* srow = want_stats ? a.stats + ((size_t)(mblock * WM + wml) * 2) * a.Cout + n0 + wnl * TW : nullptr;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) { s1[k] = 0.f; s2[k] = 0.f; }
-#pragma unroll
-                for (int p2 = 0; p2 < 2; ++p2) {
-                    const int jp = 2 * j + p2;
-                    if constexpr (ACTB) {
-                        if (jp + 1 < 2 * TN) yq_load((jp + 1) & 1, jp + 1);
-                    }
-                    // the lane's constants of quads 2 p2, 2 p2 + 1 of n-tile j: 16-byte LDS reads (four consecutive channels each)
-                    f32x4 cb[2], c_sc[ACTB ? 2 : 1], c_sh[ACTB ? 2 : 1], c_sl[ACTB ? 2 : 1], c_mu[ACTB ? 2 : 1];
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq) {
-                        const float* tq = tab + j * 32 + 8 * (2 * p2 + qq);
-                        cb[qq] = *(const f32x4*)tq;
-                        if constexpr (ACTB) {
-                            c_sc[qq] = *(const f32x4*)(tq + 1 * BN); c_sh[qq] = *(const f32x4*)(tq + 2 * BN);
-                            c_sl[qq] = *(const f32x4*)(tq + 3 * BN); c_mu[qq] = *(const f32x4*)(tq + 4 * BN);
-                        }
-                    }
-                    const bool chan_ok = n0 + wnl * TW + j * 32 + p2 * 16 + 8 * hl < a.Cout;
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) {
-                        const bool pix_ok = col_ok && (2 * (wml * TM + i) < rlim);
-                        unsigned xa[ACTB ? 4 : 1];      // y_raw in the accumulator layout: word 2 qq + w = channels 8 (2 p2 + qq) + 4 h + 2 w, + 1
-                        if constexpr (ACTB) {
-                            const u32x4 yv4 = yq[jp & 1][i];
-#pragma unroll
-                            for (int w = 0; w < 2; ++w) {
-                                // the inverse of the store's swap (an involution): the store layout's 16 bytes -> quads 2 p2 (lanes' own h) and 2 p2 + 1
-                                const u32x2 t = __builtin_amdgcn_permlane32_swap(yv4[w], yv4[2 + w], false, false);
-                                xa[w] = t[0]; xa[2 + w] = t[1];
-                            }
-                        }
-                        unsigned d[2][2];
-#pragma unroll
-                        for (int qq = 0; qq < 2; ++qq)
-#pragma unroll
-                            for (int w = 0; w < 2; ++w) {
-                                const int k = 4 * (2 * p2 + qq) + 2 * w;
-                                const f32x2 v = (f32x2){acc[i][j][k], acc[i][j][k + 1]} + (f32x2){cb[qq][2 * w], cb[qq][2 * w + 1]};
-                                f32x2 vo;
-                                if constexpr (ACTB) {
-                                    // g = dA where BatchNorm(y_raw) > 0, slope * dA elsewhere (unet.py:14,17 backward); sums of g and g (y_raw - mean)
-                                    const unsigned xw = xa[2 * qq + w];
-                                    const f32x2 x = {__uint_as_float(xw << 16), __uint_as_float(xw & 0xFFFF0000u)};
-                                    const f32x2 yv = __builtin_elementwise_fma(x, (f32x2){c_sc[qq][2 * w], c_sc[qq][2 * w + 1]}, (f32x2){c_sh[qq][2 * w], c_sh[qq][2 * w + 1]});
-                                    const f32x2 f = {yv.x > 0.f ? 1.f : c_sl[qq][2 * w], yv.y > 0.f ? 1.f : c_sl[qq][2 * w + 1]};
-                                    vo = v * f;
-                                    const f32x2 xm = x - (f32x2){c_mu[qq][2 * w], c_mu[qq][2 * w + 1]};
-                                    s1[k] += vo.x; s1[k + 1] += vo.y;
-                                    s2[k] = fmaf(vo.x, xm.x, s2[k]); s2[k + 1] = fmaf(vo.y, xm.y, s2[k + 1]);
-                                } else {
-                                    if (want_stats) {
-                                        const f32x2 vs = (whole_tile || pix_ok) ? v : (f32x2){0.f, 0.f};
-                                        s1[k] += vs.x; s1[k + 1] += vs.y;
-                                        s2[k] = fmaf(vs.x, vs.x, s2[k]); s2[k + 1] = fmaf(vs.y, vs.y, s2[k + 1]);
-                                    }
-                                    const f32x2 m = v * slope;
-                                    vo = (f32x2){fmaxf(v.x, m.x), fmaxf(v.y, m.y)};
-                                }
-                                typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-                                const bf16x2 pk = __builtin_convertvector(vo, bf16x2);
-                                d[qq][w] = *(const unsigned*)&pk;
-                            }
-                        // quads (2 p2, 2 p2 + 1) -> eight consecutive channels per lane: lanes < 32 keep their quad 2 p2 and take the upper half's,
-                        // lanes >= 32 take the lower half's quad 2 p2 + 1 and keep their own (T21)
-                        u32x4 st;
-#pragma unroll
-                        for (int w = 0; w < 2; ++w) {
-                            const u32x2 t = __builtin_amdgcn_permlane32_swap(d[0][w], d[1][w], false, false);
-                            st[w] = t[0]; st[2 + w] = t[1];
-                        }
-                        __builtin_amdgcn_raw_buffer_store_b128(st, rsY, (pix_ok && chan_ok && !(ABC_DBG(a.dbg) & 128)) ? voff0 : 0xFFFFFFF0u, (unsigned)i * istep + (unsigned)(jp * 16 * (int)sizeof(OutT)), 0);
-                        // (the store-data hazard of the 4-wave epilogue below: keep the data registers live two wait states past the store)
-#if defined(__HIP_DEVICE_COMPILE__)
-                        asm volatile("s_nop 1" :: "v"(st));
-#endif
-                    }
-                }
-                if (want_stats) {
-                    // per-channel totals over the wave's 32 x TM pixels: a halving butterfly over the 32 lanes of a half -- after it lane r
-                    // holds the total of its half's channel k = r >> 1 (both lanes of a pair the same), summed in a fixed order
-                    const int kk = (rl >> 1) & 15;
-                    const int cl = (kk & 3) + 8 * (kk >> 2) + 4 * hl;       // channel of the n-tile
-                    float t1 = lane_reduce16(s1, rl), t2 = lane_reduce16(s2, rl);
-                    if constexpr (ACTB) t2 *= tab[5 * BN - 4 * hl + j * 32 + cl];      // (the row act_bwd writes: sum of g (y_raw - mean) / std)
-                    if (!(rl & 1) && n0 + wnl * TW + j * 32 + cl < a.Cout) { srow[j * 32 + cl] = t1; srow[a.Cout + j * 32 + cl] = t2; }
-                }
-            }
-            if (pr) prof[3] = wall_clock64();
-            if (pr) prof[4] = wall_clock64();
-            if (a.a_bufs == 2) cpar += a.nchunks;
-            continue;
         }
         if constexpr (M16) {
             // ---- the epilogue below in the 16x16 accumulator layout: lane (m16, q16) holds, of every 32-pixel x 32-channel block (i, j),
@@ -1105,7 +895,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
             else if (!a.out_act) store_tiles(std::false_type{}, std::true_type{});
             else if (a.stats == nullptr) store_tiles(std::true_type{}, std::false_type{});
             else store_tiles(std::true_type{}, std::true_type{});
-            if (pr) prof[3] = wall_clock64();
             if (a.stats != nullptr) {
                 // a channel's sums sit in the four lanes m16 + 16 q: added as (own + lane ^ 16) + (lane ^ 32's same), then the WM waves in order.
                 // A halving butterfly on the VALU (v_permlane16_swap, v_permlane32_swap) instead of two ds_bpermute per value: of the lane's
@@ -1153,7 +942,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                     a.stats[((size_t)mblock * 2 + 1) * a.Cout + n0 + tid] = v2;
                 }
             }
-            if (pr) prof[4] = wall_clock64();
             continue;
         }
         // ---- epilogue: bias, statistics of the f32 values, store through a wave-private LDS transpose
@@ -1180,8 +968,7 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
         //  inference graph -- take the fast path too when no statistics are asked for: their missing rows get the dropped offset)
         const bool rows_ok = gy0 + 2 * MT <= a.Hg;
         const bool whole = ACTB || ((rows_ok || a.stats == nullptr) && (gx0 + 16 <= a.Wg) && (a.Cout % EV == 0) && !a.accumulate && vec_ok);
-        if (ABC_DBG(a.dbg) & 64) {
-        } else if (whole) {
+        if (whole) {
             // (laundered: computed from the plain thread index, the lane parts of the staging addresses and store offsets are hoisted
             //  out of the tile loop, live through the main loop, get spilled, and come back as scratch round trips in front of the
             //  stores -- each a vmcnt(0) wait that also drains the next tile's halo prefetch)
@@ -1395,7 +1182,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
             lds_wave_sync();
         }
         }
-        if (pr) prof[3] = wall_clock64();
         if (a.stats != nullptr) {
             float* red = (float*)(smem + a.red_off);  // [WM][4][BN], clear of the transpose regions
             const int rows = a.stats_rows == 4 ? 4 : 2;
@@ -1434,7 +1220,6 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
                 }
             }
         }
-        if (pr) prof[4] = wall_clock64();
     }
     if constexpr (STATIC) {
         if (a.stats != nullptr && a.stats_rows != 4 && tid < BN && tid < a.Cout) {
@@ -1444,17 +1229,17 @@ __device__ __forceinline__ void conv_fast_body(const FastK& a) {
     }
 }
 
-template <typename InT, typename CT, typename OutT, int CK, int BN, int STRIDE, int MT, bool STATIC, int WD = 0, int EPI = 0, int NW = 4, bool LP = false, int VAR = 0, bool M16 = false>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? 4 : (STATIC ? 3 : 2))) void conv_fast_kernel(const FastK a) {
-    conv_fast_body<InT, CT, OutT, CK, BN, STRIDE, MT, STATIC, WD, EPI, NW, LP, VAR, M16>(a);
+template <typename InT, typename CT, typename OutT, int CK, int BN, int STRIDE, int MT, bool STATIC, int WD = 0, int EPI = 0, bool M16 = false>
+__global__ __launch_bounds__(FT, (STATIC ? 3 : 2)) void conv_fast_kernel(const FastK a) {
+    conv_fast_body<InT, CT, OutT, CK, BN, STRIDE, MT, STATIC, WD, EPI, M16>(a);
 }
 
-template <typename InT, typename CT, typename OutT, int CK, int BN, int STRIDE, int MT, bool STATIC, int WD = 0, int EPI = 0, int NW = 4, bool LP = false, int VAR = 0, bool M16 = false>
+template <typename InT, typename CT, typename OutT, int CK, int BN, int STRIDE, int MT, bool STATIC, int WD = 0, int EPI = 0, bool M16 = false>
 int launch_st(const FastK& k, const abc_fast_geom& g, hipStream_t st) {
-    auto fn = conv_fast_kernel<InT, CT, OutT, CK, BN, STRIDE, MT, STATIC, WD, EPI, NW, LP, VAR, M16>;
+    auto fn = conv_fast_kernel<InT, CT, OutT, CK, BN, STRIDE, MT, STATIC, WD, EPI, M16>;
     static unsigned long long lds_ok = 0;
     if (int rc = abc_allow_lds((const void*)fn, LDS_WG, &lds_ok)) return rc;
-    hipLaunchKernelGGL(fn, dim3(g.nwg), dim3(64 * NW), g.lds, st, k);
+    hipLaunchKernelGGL(fn, dim3(g.nwg), dim3(FT), g.lds, st, k);
     return abc_check_launch("conv_fast");
 }
 

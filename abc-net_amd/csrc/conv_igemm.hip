@@ -39,7 +39,7 @@ struct ConvK {
     int Hg, Wg, Hout, Wout, ldy, cout_off, Cout, Cout_pad;
     int om, oy0, ox0;
     int ntaps, tg, ngroups, dy_min, dx_min, HH, HW, RS;
-    int tiles_x, tiles_y, nblocks_n, sA_bytes, a_bufs, sB_off, sB_bytes, tap_off, coef_off, cstride, planar_out, ctot_out, fast_a, dbg, ntiles, b_static, stg_off, stats_rows, accumulate, magic, out_act;
+    int tiles_x, tiles_y, nblocks_n, sA_bytes, a_bufs, sB_off, sB_bytes, tap_off, coef_off, cstride, planar_out, ctot_out, fast_a, ntiles, b_static, stg_off, stats_rows, accumulate, magic, out_act;
     float out_slope;
     unsigned bytesA, bytesW;
     int8_t ty[ABC_MAX_TAPS], tx[ABC_MAX_TAPS];
@@ -191,14 +191,14 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_kernel(const ConvK a) {
         if (gn == a.ngroups) { gn = 0; cn = c + 1; }
         const bool has_next = (s + 1 < nstages);
         const bool new_chunk = has_next && (gn == 0);
-        if (has_next && !(ABC_DBG(a.dbg) & 1)) b_issue(cn, gn);
+        if (has_next) b_issue(cn, gn);
         if (s == nstages - 1 && more) {
             decode(next_tile);
             if (!a.b_static) b_issue(0, 0);
             if constexpr (FAST) apre.issue(rsA, gA, b, iy0, ix0, a.cin_off, tid, 1 << 30);
         }
         if constexpr (FAST) {
-            if (new_chunk && !(ABC_DBG(a.dbg) & 2)) apre.issue(rsA, gA, b, iy0, ix0, a.cin_off + cn * CK, tid, 1 << 30);
+            if (new_chunk) apre.issue(rsA, gA, b, iy0, ix0, a.cin_off + cn * CK, tid, 1 << 30);
         }
 
         // ---- MFMA over the taps of this stage
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_kernel(const ConvK a) {
             const char* sBc = sB + (s & 1) * a.sB_bytes;
             const int t0 = g * a.tg;
             const int tcnt = min(a.tg, a.ntaps - t0);
-            for (int tl = 0; tl < ((ABC_DBG(a.dbg) & 4) ? 0 : tcnt); ++tl) {
+            for (int tl = 0; tl < tcnt; ++tl) {
                 const int aoff = sTap[t0 + tl];
                 const int boff = tl * BN * PS;
 #pragma unroll
@@ -225,12 +225,12 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_kernel(const ConvK a) {
             }
         }
 
-        if (has_next && !(ABC_DBG(a.dbg) & 8)) b_commit(gn, sB + ((s + 1) & 1) * a.sB_bytes);
+        if (has_next) b_commit(gn, sB + ((s + 1) & 1) * a.sB_bytes);
         if (new_chunk) {
             if (a.a_bufs == 2) {
                 // the other halo buffer was last read in chunk c-1: free since the barrier that ended it
                 if constexpr (FAST) {
-                    if (!(ABC_DBG(a.dbg) & 16)) apre.commit(sA + (cn & 1) * a.sA_bytes, a.RS, PS, gA, lcoef ? lcoef + cn * CK : nullptr, a.cstride, tid, 1 << 30);
+                    apre.commit(sA + (cn & 1) * a.sA_bytes, a.RS, PS, gA, lcoef ? lcoef + cn * CK : nullptr, a.cstride, tid, 1 << 30);
                 }
             } else {
                 __syncthreads();  // every wave is done reading this chunk's halo
@@ -260,8 +260,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_kernel(const ConvK a) {
         bv[j] = (a.bias != nullptr && nval[j]) ? a.bias[n] : 0.f;
     }
     const bool planar = (sizeof(OutT) == 4) && a.planar_out;
-    if (ABC_DBG(a.dbg) & 64) {
-    } else if (!planar) {
+    if (!planar) {
         constexpr int TW = TN * 32;                       // channels of this wave's tile row
         constexpr int ROWB = TW * (int)sizeof(OutT) + 16;  // padded LDS row (bytes)
         constexpr int EV = 16 / (int)sizeof(OutT);         // elements per 16-byte store
@@ -334,7 +333,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_kernel(const ConvK a) {
             }
         }
     }
-    if (a.stats != nullptr && !(ABC_DBG(a.dbg) & 128)) {
+    if (a.stats != nullptr) {
         __syncthreads();  // LDS reuse
         float* red = (float*)(smem + a.stg_off);  // [WM][4][BN]
         const int rows = a.stats_rows == 4 ? 4 : 2;
@@ -561,7 +560,7 @@ extern "C" int abc_conv_stat_blocks(const abc_conv_desc* d) {
         if (abc_conv_narrow_ok(d)) return abc_conv_narrow_stat_blocks(d);
     }
     abc_fast_geom f;
-    if (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible) return (f.b_static && d->stats_rows != 4) ? f.nwg : f.tiles_x * f.tiles_y * d->B * (f.lp ? 2 : 1);   // (resident weights: one row per workgroup; lane = pixel epilogue: one row per wave row, WM = 2)
+    if (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible) return (f.b_static && d->stats_rows != 4) ? f.nwg : f.tiles_x * f.tiles_y * d->B;   // (resident weights: one row per workgroup)
     Geom g;
     if (conv_geom(d, &g)) return -1;
     return g.tiles_x * g.tiles_y * d->B;
@@ -634,7 +633,6 @@ extern "C" int abc_conv_fwd(const abc_conv_desc* d, abc_stream_t stream) {
     k.magic = 65536 / g.HW + 1;
     k.bytesA = (unsigned)((int64_t)d->B * d->src.Hx * d->src.Wx * d->src.ldx * (d->dtype_in == ABC_BF16 ? 2 : 4));
     k.bytesW = (unsigned)((int64_t)d->ntaps * k.nchunks * d->Cout_pad * g.CK * (d->dtype_c == ABC_BF16 ? 2 : 4));
-    { const char* e = abc_knob("ABC_CONV_DBG"); k.dbg = e ? atoi(e) : 0; }  // timing ablations only (results invalid)
     for (int t = 0; t < d->ntaps; ++t) {
         k.ty[t] = (int8_t)(d->tap_dy[t] - g.dy_min);
         k.tx[t] = (int8_t)(d->tap_dx[t] - g.dx_min);

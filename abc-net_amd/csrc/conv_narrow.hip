@@ -865,13 +865,13 @@ static bool route_n16(const abc_conv_desc* d) {
     if (d->Hin % 8 || d->Win % 16 || (d->ldy % 4) || (d->cout_off % 4)) return false;
     for (int t = 0; t < 9; ++t)
         if (d->tap_dy[t] != t / 3 - 1 || d->tap_dx[t] != t % 3 - 1) return false;
-    return abc_knob("ABC_CONV_NON16") == nullptr;
+    return true;
 }
 
 // 32 -> 32 channels, the full 5x5 square in row-major tap order, whole 4 x 16 tiles go to conv_n32r2_kernel
 static bool route_n32r2(const abc_conv_desc* d) {
     if (d->Cin != 32 || d->Cout != 32 || (d->ntaps != 25 && d->ntaps != 9)) return false;
-    if (d->ntaps == 9 && (d->stats_rows == 4 || abc_knob("ABC_CONV_NON32R1"))) return false;
+    if (d->ntaps == 9 && d->stats_rows == 4) return false;
     if (d->stem_x != nullptr) return false;
     if (d->src.scale != nullptr && d->out_act) return false;
     // second output (the 2x2 max-pool of the stored tensor): the plain form
@@ -886,8 +886,7 @@ static bool route_n32r2(const abc_conv_desc* d) {
         fwd = fwd && d->tap_dy[t] == t / kw - rr && d->tap_dx[t] == t % kw - rr;
         mir = mir && d->tap_dy[t] == rr - t / kw && d->tap_dx[t] == rr - t % kw;
     }
-    if (!fwd && !mir) return false;
-    return abc_knob("ABC_CONV_NON32R2") == nullptr;
+    return fwd || mir;
 }
 // workgroups per image (a workgroup's tiles belong to one image: the four-row statistics of unet2's CBAM are per image); grid = B x this
 static int n32r2_wpi(const abc_conv_desc* d) {
@@ -912,7 +911,6 @@ static void narrow_grid(const abc_conv_desc* d, int* nwg, int* tpw) {
 // BatchNorm partial sums of the outputs (2 rows).  (32 input channels with BOTH the transform and the sums does not fit the
 // registers: that one stays on conv_fast.)
 int abc_conv_narrow_ok(const abc_conv_desc* d) {
-    if (abc_knob("ABC_CONV_NONARROW")) return 0;
     if (d->dtype_in != ABC_BF16 || d->dtype_c != ABC_BF16 || d->dtype_out != ABC_BF16) return 0;
     if (d->src.pool || d->src.planar || d->src.drop_p > 0.f || d->planar_out) return 0;
     if (d->stride != 1 || d->om != 1 || d->oy0 || d->ox0) return 0;
@@ -933,10 +931,9 @@ int abc_conv_narrow_ok(const abc_conv_desc* d) {
                                    !d->actbwd_slope || !d->actbwd_mean || !d->actbwd_invstd ||
                                    (int64_t)d->B * d->Hin * d->Win * d->actbwd_ld * 2 >= (int64_t(1) << 31))) return 0;
     if (d->src.scale != nullptr && d->Cin == 32 && !route_n32r2(d)) return 0;             // transform + sums + 72 weight registers do not fit
-    if (d->src.scale != nullptr && abc_knob("ABC_CONV_NONARROW_XF")) return 0;
     if (d->stem_x != nullptr && (d->Cin != 16 || d->ntaps != 9 || d->src.scale != nullptr || d->stats != nullptr || !d->stem_w || !d->stem_scale || !d->stem_bias)) return 0;
     const int R = d->ntaps == 9 ? 1 : 2;
-    if (R == 2 && (d->Cin != 32 || (d->src.scale != nullptr && !route_n32r2(d)) || abc_knob("ABC_CONV_NONARROW5"))) return 0;
+    if (R == 2 && (d->Cin != 32 || (d->src.scale != nullptr && !route_n32r2(d)))) return 0;
     for (int t = 0; t < d->ntaps; ++t)
         if (d->tap_dy[t] < -R || d->tap_dy[t] > R || d->tap_dx[t] < -R || d->tap_dx[t] > R) return 0;
     return (int64_t)d->B * d->Hin * d->Win * d->src.ldx * 2 < (int64_t(1) << 31);

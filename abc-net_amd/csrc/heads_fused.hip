@@ -58,7 +58,7 @@ struct HFK {
     float* bnpart;      // [nchunk][2][ld]
     float* dwsmall;     // [nchunk][HF_SMALL_ROWS][128 + 1]: the small heads' conv2 weight / bias gradient partials (see run_head)
     double* losspart;   // [nchunk][16]
-    int HW, nchunk, dbg;
+    int HW, nchunk;
     HFHead hd[HF_NH];
 };
 
@@ -113,7 +113,6 @@ template <int HEAD>
 __device__ inline void small_head_wgrad(const HFK& a, const Ctx& c, const bf16x8* fb) {
     constexpr int CH = hf_ch(HEAD);
     const int r = c.r, h = c.h, lane = c.lane;
-    if (ABC_DBG(a.dbg) & 32) return;
     char* img = c.ot + WV_AIMG;
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) *(bf16x8*)(img + r * AROW + (16 * kk + 8 * h) * 2) = fb[kk];
@@ -311,8 +310,8 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
     const uint32_t tword = a.tflags ? (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tflags[c.pix0 >> 5]) : 0xFFFFFFFFu;
     const bool tz = !((tword >> (HEAD == 6 ? 5 : HEAD)) & 1u);      // (rho reads the bond-type targets' bins: their flag)
     if constexpr (HEAD == 1 || HEAD == 2 || HEAD == 3 || HEAD == 5) {
-        // the softmax heads contribute nothing where no pixel of the wave has a target: run_head_skip (ABC_HF_DBG bit 6: the A/B)
-        if (tz && !(ABC_DBG(a.dbg) & 64)) { run_head_skip<HEAD>(a, c, lsum); return; }
+        // the softmax heads contribute nothing where no pixel of the wave has a target: run_head_skip
+        if (tz) { run_head_skip<HEAD>(a, c, lsum); return; }
     }
     const size_t thw = tz ? (size_t)0 : (size_t)a.HW;
     const uint32_t tloff = tz ? (uint32_t)lane : loff;
@@ -408,7 +407,6 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
         for (int k = 0; k < 16; ++k) accD[mi][k] = 0.f;
     bf16x8 wt[8], bqp[2];
     auto dgrad_mfma = [&]() {
-        if (ABC_DBG(a.dbg) & 8) return;
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -441,7 +439,6 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
                 float z[6], t[6], dz[6], dn = 0.f;
 #pragma unroll
                 for (int k = 0; k < 6; ++k) { z[k] = v[8 * gi + k]; t[k] = tn[6 * gi + k]; }
-                if (ABC_DBG(a.dbg) & 1) { for (int k = 0; k < 6; ++k) dz[k] = z[k] * t[k]; dn = t[0]; } else
                 num += (double)class_focal<6, true>(z, t, nullptr, dz, &dn);
                 den += (double)dn;
                 c.dnl[(2 * mt + gi) * 64 + lane] = dn;
@@ -462,7 +459,7 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
                 load_t5(mtn);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (st_logits && !(ABC_DBG(a.dbg) & 2)) {
+            if (st_logits) {
 #pragma unroll
                 for (int gi = 0; gi < 2; ++gi)
 #pragma unroll
@@ -527,19 +524,17 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
         // ---- d(logits) as bf16: [row][pixel] tile -> the blocked buffer of the weight gradient
         bqp[0] = pack_frag<bf16>(dlv);
         bqp[1] = pack_frag<bf16>(dlv + 8);
-        if (!(ABC_DBG(a.dbg) & 4)) {
-            char* tl = c.ot;
+        char* tl = c.ot;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) *(bf16*)(tl + ((k & 3) + 8 * (k >> 2) + 4 * h) * TROW + r * 2) = bqp[k >> 3][k & 7];
-            lds_sync();
+        for (int k = 0; k < 16; ++k) *(bf16*)(tl + ((k & 3) + 8 * (k >> 2) + 4 * h) * TROW + r * 2) = bqp[k >> 3][k & 7];
+        lds_sync();
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int q = lane + 64 * j, row = q >> 2, part = q & 3;
-                const u32x4 t = *(const u32x4*)(tl + row * TROW + part * 16);
-                *(u32x4*)((char*)(hd.dlb + ((size_t)c.chunk * CPAD + 32 * mt) * 128) + (uint32_t)((row * 128 + 32 * c.wave + part * 8) * 2)) = t;
-            }
-            lds_sync();
+        for (int j = 0; j < 2; ++j) {
+            const int q = lane + 64 * j, row = q >> 2, part = q & 3;
+            const u32x4 t = *(const u32x4*)(tl + row * TROW + part * 16);
+            *(u32x4*)((char*)(hd.dlb + ((size_t)c.chunk * CPAD + 32 * mt) * 128) + (uint32_t)((row * 128 + 32 * c.wave + part * 8) * 2)) = t;
         }
+        lds_sync();
         if constexpr (!PIPE) {
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -561,65 +556,63 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
     // element (kk = 2 mi + (k >> 3), j = k & 7) of this lane's own feature fragments.  g and g * xhat are formed here, then go
     // through the wave's LDS tile (half a slice at a time) so that a lane owns 8 consecutive channels of a pixel: 16-byte stores
     // of g, and per-channel sums over the wave's pixels for BatchNorm's backward.
-    if (!(ABC_DBG(a.dbg) & 16)) {
-        char* ot = c.ot;
-        const int sg = lane & 7, pg = lane >> 3;
-        float* ws = c.wsum + c.nslice * 256;
+    char* ot = c.ot;
+    const int sg = lane & 7, pg = lane >> 3;
+    float* ws = c.wsum + c.nslice * 256;
 #pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            float gv[2][16], gx[2][16];
+    for (int half = 0; half < 2; ++half) {
+        float gv[2][16], gx[2][16];
 #pragma unroll
-            for (int m2 = 0; m2 < 2; ++m2) {
-                const int mi = 2 * half + m2;
+        for (int m2 = 0; m2 < 2; ++m2) {
+            const int mi = 2 * half + m2;
 #pragma unroll
-                for (int k8 = 0; k8 < 2; ++k8) {
-                    const int kk = 2 * mi + k8, cc = 16 * kk + 8 * h;
-                    float sl[8], mu[8], is[8];
-                    LoadVec<float, 8>::ld(cf + 256 + cc, sl); LoadVec<float, 8>::ld(cf + 384 + cc, mu); LoadVec<float, 8>::ld(cf + 512 + cc, is);
-                    const uint32_t kb = kbits[kk >> 2] >> (8 * (kk & 3)), pb = pbits[kk >> 2] >> (8 * (kk & 3));
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const uint32_t w = raw[kk][j >> 1];
-                        const float x = __uint_as_float((j & 1) ? (w & 0xFFFF0000u) : (w << 16));
-                        const float m1 = ((pb >> j) & 1u) ? c.dscale : sl[j] * c.dscale;
-                        const float gg = ((kb >> j) & 1u) ? accD[mi][8 * k8 + j] * m1 : 0.f;
-                        gv[m2][8 * k8 + j] = gg;
-                        gx[m2][8 * k8 + j] = gg * ((x - mu[j]) * is[j]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-                for (int m2 = 0; m2 < 2; ++m2)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        bf16x4 o;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) o[j] = (bf16)(pass ? gx[m2][4 * q + j] : gv[m2][4 * q + j]);
-                        *(bf16x4*)(ot + r * HROW + (32 * m2 + 16 * (q >> 1) + 8 * h + 4 * (q & 1)) * 2) = o;
-                    }
-                lds_sync();
-                float acc8[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc8[j] = 0.f;
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const int px = it * 8 + pg;
-                    const bf16x8 tv = *(const bf16x8*)(ot + px * HROW + sg * 16);
-                    if (pass == 0) *(bf16x8*)(a.g + (size_t)(c.pix0 + px) * a.ld + slice + 64 * half + sg * 8) = tv;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc8[j] += (float)tv[j];
-                }
-                lds_sync();
+            for (int k8 = 0; k8 < 2; ++k8) {
+                const int kk = 2 * mi + k8, cc = 16 * kk + 8 * h;
+                float sl[8], mu[8], is[8];
+                LoadVec<float, 8>::ld(cf + 256 + cc, sl); LoadVec<float, 8>::ld(cf + 384 + cc, mu); LoadVec<float, 8>::ld(cf + 512 + cc, is);
+                const uint32_t kb = kbits[kk >> 2] >> (8 * (kk & 3)), pb = pbits[kk >> 2] >> (8 * (kk & 3));
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    acc8[j] += __shfl_xor(acc8[j], 8); acc8[j] += __shfl_xor(acc8[j], 16); acc8[j] += __shfl_xor(acc8[j], 32);
+                    const uint32_t w = raw[kk][j >> 1];
+                    const float x = __uint_as_float((j & 1) ? (w & 0xFFFF0000u) : (w << 16));
+                    const float m1 = ((pb >> j) & 1u) ? c.dscale : sl[j] * c.dscale;
+                    const float gg = ((kb >> j) & 1u) ? accD[mi][8 * k8 + j] * m1 : 0.f;
+                    gv[m2][8 * k8 + j] = gg;
+                    gx[m2][8 * k8 + j] = gg * ((x - mu[j]) * is[j]);
                 }
-                if (lane < 8) {
+            }
+        }
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) ws[pass * 128 + 64 * half + sg * 8 + j] = acc8[j];
+        for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+            for (int m2 = 0; m2 < 2; ++m2)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    bf16x4 o;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[j] = (bf16)(pass ? gx[m2][4 * q + j] : gv[m2][4 * q + j]);
+                    *(bf16x4*)(ot + r * HROW + (32 * m2 + 16 * (q >> 1) + 8 * h + 4 * (q & 1)) * 2) = o;
                 }
+            lds_sync();
+            float acc8[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc8[j] = 0.f;
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int px = it * 8 + pg;
+                const bf16x8 tv = *(const bf16x8*)(ot + px * HROW + sg * 16);
+                if (pass == 0) *(bf16x8*)(a.g + (size_t)(c.pix0 + px) * a.ld + slice + 64 * half + sg * 8) = tv;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc8[j] += (float)tv[j];
+            }
+            lds_sync();
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                acc8[j] += __shfl_xor(acc8[j], 8); acc8[j] += __shfl_xor(acc8[j], 16); acc8[j] += __shfl_xor(acc8[j], 32);
+            }
+            if (lane < 8) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ws[pass * 128 + 64 * half + sg * 8 + j] = acc8[j];
             }
         }
     }
@@ -653,7 +646,6 @@ __global__ __launch_bounds__(256, 2) void heads_fused_kernel(const HFK a) {
     c.ot = smem + c.wave * WV;
     c.dnl = (float*)(smem + c.wave * WV + WV_DN);
     const int group = blockIdx.y;
-    if (ABC_DBG(a.dbg) & (256 << group)) return;    // (debug build: time the work types one by one)
     c.wsum = (float*)(smem + LDS_BSUM) + c.wave * 512;
     c.nslice = 0;
     c.dscale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
@@ -769,7 +761,6 @@ extern "C" int abc_heads_fused_fwd_bwd(const abc_heads_fused_desc* d, abc_stream
     k.tflags = d->target_flags; k.tzero = (const char*)d->zero_bytes;
     k.bnpart = d->bn_partial; k.losspart = d->loss_partial; k.dwsmall = d->wgrad_work;
     k.HW = d->h * d->w; k.nchunk = abc_heads_fused_chunks(d);
-    { const char* e = abc_knob("ABC_HF_DBG"); k.dbg = e ? atoi(e) : 0; }   // (debug build only: phase ablations)
     size_t row0 = 0;
     for (int i = 0; i < HF_NH; ++i) {
         const int cpad = hf_tiles(i) * 32;

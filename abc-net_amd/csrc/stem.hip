@@ -272,7 +272,6 @@ constexpr int STEM_ROWS = 8;
 
 // 1 when the one-channel kernel takes this descriptor; *stat_blocks = statistics partials it writes
 int abc_conv_stem_ok(const abc_conv_desc* d, int* stat_blocks) {
-    if (abc_knob("ABC_CONV_NOSTEM")) return 0;
     if (d->Cin != 1 || d->cin_off != 0 || d->src.ldx != 1 || d->dtype_in != ABC_F32 || d->src.scale || d->src.pool || d->src.planar ||
         d->src.drop_p > 0.f)
         return 0;
@@ -308,7 +307,7 @@ int abc_conv_stem_launch(const abc_conv_desc* d, abc_stream_t stream) {
     const int kw = d->ntaps == 9 ? 3 : (d->ntaps == 25 ? 5 : 0);
     bool square = kw != 0 && (d->Wg % 4) == 0;
     for (int t = 0; square && t < d->ntaps; ++t) square = d->tap_dy[t] == t / kw - kw / 2 && d->tap_dx[t] == t % kw - kw / 2;
-    if (square && !abc_knob("ABC_STEM_SCALAR")) {
+    if (square) {
         if (kw == 5) {
             if (d->dtype_c == ABC_F32) hipLaunchKernelGGL((stem_conv4_kernel<float, float, 5, 4>), dim3(nwg), dim3(256), 0, st, k);
             else if (d->dtype_out == ABC_BF16) hipLaunchKernelGGL((stem_conv4_kernel<bf16, bf16, 5, 4>), dim3(nwg), dim3(256), 0, st, k);

@@ -34,7 +34,7 @@ namespace {
 
 constexpr int MAXT_FAST = 9;  // taps per workgroup (accumulator budget: 9 x 16 VGPRs)
 constexpr int MAXT_SLOW = 5;  // the general loader needs the registers: fewer taps per workgroup, more tap groups
-constexpr int WTHR_HOST = 512;  // 8 waves (the default workgroup)
+constexpr int WTHR_HOST = 512;  // 8 waves per workgroup
 
 struct WgK {
     ActSrc p, q;
@@ -42,11 +42,14 @@ struct WgK {
     int B, Hg, Wg, Hq, Wq;
     int cp_off, Ca, cq_off, Cb, Ca_pad, Cb_pad;
     int ntaps, tgw, nsplit, npatch, tiles_x, tiles_y;
-    int dy_min, dx_min, HH, HW, PSWP, PSWQ, sP_bytes, sQ_bytes, coef_off, cstrP, cstrQ, nta, ntb, fast_p, fast_q, nbuf, dbg, magicQ, k3;
+    int dy_min, dx_min, HH, HW, PSWP, PSWQ, sP_bytes, sQ_bytes, coef_off, cstrP, cstrQ, nta, ntb, fast_p, fast_q, nbuf;
+    unsigned bytesP2;        // (here, not beside bytesP: this order keeps the argument offsets the kernels were tuned with -- a shift of
+                             //  the fields below by four bytes changed their register allocation, and the 4 x 2 dual form spilled)
+    int magicQ, k3;
     unsigned mg_tx, mg_ty;   // ceil(2^32 / tiles_x), ceil(2^32 / tiles_y): the patch index is split by two multiply-highs (scalar), not divisions
     int regP;                // P's patches are whole and P has no halo: its segment offsets are affine in the segment index
     int qtab_off;            // > 0: LDS byte offset of Q's segment table (HaloFetch::table_setup): whole patches, 3x3 halo, stride 1
-    unsigned bytesP, bytesQ, bytesP2;
+    unsigned bytesP, bytesQ;
     const void* p2; void* p_out; int ld_p2, cp2_off, ld_pout;  // BN-backward correction fused into the load of P (DUAL)
     int8_t ty[ABC_MAX_TAPS], tx[ABC_MAX_TAPS];
 };
@@ -71,20 +74,17 @@ __device__ inline void stage_slow(char* dst, int RS, int PS, int HH, int HW, int
 // of the patch rows (wave w owns taps w, w + 8, w + 16, w + 24: <= 4 accumulators), every wave walks the whole patch, and
 // ONE workgroup pass covers all taps.  With the row split 25 taps ran as 3 tap groups (grid.y) that each re-staged both
 // operands: 596 MB fetched per launch against 302 MB algorithmic (profiles/r01_f_unet2_pmc_summary.json).
-// NW = waves per workgroup: 8 (one workgroup per CU), or 4 with 2 x 2 tile pairs and a single LDS buffer, so that TWO
-// workgroups share a CU: more bytes of prefetch in flight per CU (the kernel is bound by memory-level parallelism, DESIGN.md
-// section 8) and one workgroup's commit phase under the other's MFMA block.
-template <typename PT, typename QT, typename CT, int AT, int BT, int STRIDE, bool FAST, int PM, bool K3, bool DUAL = false, bool TS = false, int NW = 8>
-__global__ __launch_bounds__(NW * 64, 2) void wgrad_kernel(const WgK a) {
-    constexpr int WTHR = NW * 64;
+template <typename PT, typename QT, typename CT, int AT, int BT, int STRIDE, bool FAST, int PM, bool K3, bool DUAL = false, bool TS = false>
+__global__ __launch_bounds__(WTHR_HOST, 2) void wgrad_kernel(const WgK a) {
+    constexpr int WTHR = WTHR_HOST;
     static_assert(!TS || (AT == 1 && BT == 1 && FAST && !K3 && sizeof(CT) == 2), "tap split: one bf16 tile pair on the prefetch path");
     constexpr int MAXT = TS ? 4 : (FAST ? MAXT_FAST : MAXT_SLOW);
-    constexpr int RSPLIT = TS ? 1 : NW / (AT * BT);   // waves sharing one tile pair, splitting the patch rows
+    constexpr int RSPLIT = TS ? 1 : (WTHR / 64) / (AT * BT);   // waves sharing one tile pair, splitting the patch rows
     constexpr int PROWS = 8 * PM;           // patch rows (x 16 columns)
     constexpr int ROWS = PROWS / RSPLIT;    // patch rows per wave
     constexpr int CWP = AT * 32, CWQ = BT * 32;
     constexpr int NPF_P = (PROWS * 16 * (CWP / Frag<CT>::NV) + WTHR - 1) / WTHR;
-    constexpr int NPF_Q = NW == 4 ? 6 : ((PM > 1 || STRIDE == 2) ? 5 : ((sizeof(CT) == 2) ? 4 : 6));  // (stride 2: 17 x 33 halo pixels)
+    constexpr int NPF_Q = (PM > 1 || STRIDE == 2) ? 5 : ((sizeof(CT) == 2) ? 4 : 6);  // (stride 2: 17 x 33 halo pixels)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int buf_bytes = a.sP_bytes + a.sQ_bytes;
     float* sCoefP = (float*)(smem + a.coef_off);
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wgrad_kernel(const WgK a) {
     //  unit -- the two runtime divisions cost ~50 vector instructions per call, twice per patch)
     // Q's segment geometry once per kernel (FAST && the host found room for the table: a.qtab_off)
     // (compiled into the instantiations whose waves own a tile pair each: the narrow-layer forms are at their register limit)
-    constexpr bool QTAB = FAST && K3 && STRIDE == 1 && NW == 8 && !TS && sizeof(CT) == 2 && sizeof(QT) == 2 && AT * BT >= 4;
+    constexpr bool QTAB = FAST && K3 && STRIDE == 1 && !TS && sizeof(CT) == 2 && sizeof(QT) == 2 && AT * BT >= 4;
     unsigned qmask = 0;
     if constexpr (QTAB) {
         if (a.qtab_off) qmask = pq.table_setup(qtab, gQ, a.HW * PSWQ, PSWQ, tid, cvalQ, PROWS, a.dy_min, a.dx_min);
@@ -305,9 +305,9 @@ __global__ __launch_bounds__(NW * 64, 2) void wgrad_kernel(const WgK a) {
             prepare(has_next ? next : patch, has_next);
             if (it < 0) fire_all();     // prologue: nothing to hide behind
         } else {
-            if (has_next && !(ABC_DBG(a.dbg) & 1)) issue(next);
+            if (has_next) issue(next);
         }
-        if (it >= 0 && !(ABC_DBG(a.dbg) & 4)) {
+        if (it >= 0) {
             const char* sP = smem + ((a.nbuf == 2) ? (it & 1) * buf_bytes : 0);
             const char* sQ = sP + a.sP_bytes;
             // ROT (stride 1, fully unrolled K-steps): tap (dy, dx) of patch row r reads the SAME fragment as tap (dy - 1, dx) of row
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(NW * 64, 2) void wgrad_kernel(const WgK a) {
             }
             if (a.nbuf == 1) __syncthreads();  // single buffer: everyone is done reading before it is refilled
         }
-        if (has_next && !(ABC_DBG(a.dbg) & 2)) commit(next, smem + ((a.nbuf == 2) ? ((it + 1) & 1) * buf_bytes : 0));
+        if (has_next) commit(next, smem + ((a.nbuf == 2) ? ((it + 1) & 1) * buf_bytes : 0));
         __syncthreads();
     }
 
@@ -716,7 +716,6 @@ __global__ __launch_bounds__(512, 2) void head_wgrad_blocked_kernel(const HeadWg
 }
 
 static bool head_ok(const abc_wgrad_desc* d) {
-    if (abc_knob("ABC_WGRAD_NOHEAD")) return false;
     if (!d->p.planar || d->dtype_p != ABC_F32 || d->dtype_q != ABC_BF16 || d->dtype_c != ABC_BF16) return false;
     if (d->ntaps != 1 || d->tap_dy[0] != 0 || d->tap_dx[0] != 0 || d->stride != 1 || d->Cb != 128 || d->cp_off != 0) return false;
     if (d->q.pool || d->q.planar || d->p.pool || d->p.drop_p > 0.f || (d->Hg * d->Wg) % 128) return false;
@@ -986,7 +985,6 @@ static bool c1_quad(const abc_wgrad_desc* d) {
 }
 
 static bool c1_ok(const abc_wgrad_desc* d) {
-    if (abc_knob("ABC_WGRAD_NOC1")) return false;
     if (d->Cb != 1 || d->cq_off != 0 || d->q.ldx != 1 || d->dtype_q != ABC_F32 || d->q.scale || d->q.pool || d->q.planar || d->q.drop_p > 0.f) return false;
     // (a transform on P only as the BatchNorm-backward correction of abc_wgrad_desc.p_dual: bf16)
     // (25 taps on the four-pixel form only: the scalar form measured 332 us fused against 157 + 113 us with the separate apply pass)
@@ -1098,7 +1096,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const ReduceBat
 
 struct WGeom {
     int AT, BT, dy_min, dx_min, HH, HW, PSWP, PSWQ, sP_bytes, sQ_bytes, coef_off, cstrP, cstrQ, lds, tgw, ngroups, nta, ntb, npatch,
-        tiles_x, tiles_y, fast_p, fast_q, nbuf, PM, ts, nw;
+        tiles_x, tiles_y, fast_p, fast_q, nbuf, PM, ts;
 };
 
 static int psw_for(int cw, int csz) {
@@ -1172,7 +1170,6 @@ static int wgeom(const abc_wgrad_desc* d, WGeom* g) {
     const int ta = abc_cdiv(d->Ca, 32), tb = abc_cdiv(d->Cb, 32);
     // 32x32 tile pairs per workgroup (one pair per wave, the remaining waves split the patch rows).  Ragged channel
     // tails are fine (zero-filled): wide tiles are what keeps the operands from being re-staged per pair.
-    static const bool no42 = abc_knob("ABC_WGRAD_NO42") != nullptr;  // (experiment switch)
     // 4 x 2 pairs where a workgroup has patches to amortise its 295 KB slab over: with one round of <= 256 workgroups (the engine's
     // split rule: nsplit = min(patches / 2, 256 / tiles)) the 48 x 48 and smaller maps leave 2-5 patches per workgroup, the kernel is
     // prologue + slab store, and 2 x 2 pairs halve the slabs written here and re-read by the reduction (per layer: launch +0..5 us,
@@ -1180,41 +1177,23 @@ static int wgeom(const abc_wgrad_desc* d, WGeom* g) {
     const int patches = d->B * abc_cdiv(d->Hg, 8) * abc_cdiv(d->Wg, 16);
     const int tiles42 = abc_cdiv(d->Ca, 128) * abc_cdiv(d->Cb, 64);
     const int ns42 = std::max(1, std::min(std::max(1, patches / 2), 256 / std::max(1, tiles42)));
-    const bool few = patches < 6 * ns42 && !abc_knob("ABC_WGRAD_42_ALWAYS");
-    if (!no42 && !few && d->stride == 1 && csz == 2 && ta >= 3 && tb >= 2) { g->AT = 4; g->BT = 2; }
+    const bool few = patches < 6 * ns42;
+    if (!few && d->stride == 1 && csz == 2 && ta >= 3 && tb >= 2) { g->AT = 4; g->BT = 2; }
     else if (d->stride == 1 && ta >= 2 && tb >= 2) { g->AT = 2; g->BT = 2; }
     else if (d->stride == 1 && csz == 2 && ta == 1 && tb >= 4) { g->AT = 1; g->BT = 4; }
     // ConvTranspose (stride 2): two P tiles share one staging of Q's 17 x 33-pixel halo (a 32-channel halo is what the prefetch path holds;
     // 64 x 64 pairs fall to the general loader: 150 us against 41).  41 -> 32 us per launch
-    else if (d->stride == 2 && csz == 2 && d->dtype_p == ABC_BF16 && d->dtype_q == ABC_BF16 && ta >= 2 && !abc_knob("ABC_WGRAD_S2_11")) { g->AT = 2; g->BT = 1; }
+    else if (d->stride == 2 && csz == 2 && d->dtype_p == ABC_BF16 && d->dtype_q == ABC_BF16 && ta >= 2) { g->AT = 2; g->BT = 1; }
     else { g->AT = 1; g->BT = 1; }
     // narrow layers (one tile pair, 8-way row split) take 32-row patches when both operands can be prefetched:
     // 4 K-steps per wave between barriers instead of 1
-    g->ts = 0; g->nw = 8;
-    // (experiment, ABC_WGRAD_NW4=1) wide bf16 3x3 layers as 4-wave workgroups on 2 x 2 tile pairs, two per CU
-    static const bool nw4 = abc_knob("ABC_WGRAD_NW4") != nullptr;
-    if (nw4 && g->AT == 4 && g->BT == 2 && d->ntaps == 9 && d->dtype_p == ABC_BF16 && d->dtype_q == ABC_BF16) {
-        g->AT = 2; g->BT = 2;
-        int rc = wgeom_pm(d, g, 1);
-        const int segq = 64 / 8;
-        if (rc == ABC_OK && g->fast_p && fast_ok(d->q, csz, d->Cb - (g->ntb - 1) * 64, (int64_t)d->B * d->q.Hx * d->q.Wx * d->q.ldx * 2) &&
-            abc_cdiv(g->HH * g->HW * segq, 256) <= 6) {
-            g->fast_q = 1; g->nw = 4; g->nbuf = 1;
-            g->coef_off = g->sP_bytes + g->sQ_bytes;
-            g->lds = g->coef_off + 3 * (64 + 64) * 4 + 256;
-            if (g->lds < 4 * 16 * 64 * 4) g->lds = 4 * 16 * 64 * 4;
-            g->ngroups = 1; g->tgw = d->ntaps;
-            return ABC_OK;
-        }
-        g->AT = 4; g->BT = 2;
-    }
+    g->ts = 0;
     if (g->AT == 1 && g->BT == 1 && d->stride == 1 && csz == 2 && d->Hg % 32 == 0) {
         int rc = wgeom_pm(d, g, 4);
         if (rc == ABC_OK && g->fast_p && g->fast_q) return ABC_OK;
     }
     // more than 9 taps on one tile pair (5x5): split the taps over the waves, one pass over the operands
-    static const bool nots = abc_knob("ABC_WGRAD_NOTS") != nullptr;  // (experiment switch)
-    if (!nots && g->AT == 1 && g->BT == 1 && d->stride == 1 && csz == 2 && d->ntaps > MAXT_FAST && d->ntaps <= 32 &&
+    if (g->AT == 1 && g->BT == 1 && d->stride == 1 && csz == 2 && d->ntaps > MAXT_FAST && d->ntaps <= 32 &&
         d->dtype_p == ABC_BF16 && d->dtype_q == ABC_BF16) {
         for (int pm = (d->Hg % 16 == 0) ? 2 : 1; pm >= 1; --pm) {
             int rc = wgeom_pm(d, g, pm);
@@ -1224,13 +1203,13 @@ static int wgeom(const abc_wgrad_desc* d, WGeom* g) {
     return wgeom_pm(d, g, 1);
 }
 
-template <typename PT, typename QT, typename CT, int AT, int BT, int STRIDE, bool FAST, int PM, bool K3, bool DUAL = false, bool TS = false, int NW = 8>
+template <typename PT, typename QT, typename CT, int AT, int BT, int STRIDE, bool FAST, int PM, bool K3, bool DUAL = false, bool TS = false>
 static int wlaunch3(const WgK& k, const WGeom& g, int nsplit, hipStream_t st) {
-    auto fn = wgrad_kernel<PT, QT, CT, AT, BT, STRIDE, FAST, PM, K3, DUAL, TS, NW>;
+    auto fn = wgrad_kernel<PT, QT, CT, AT, BT, STRIDE, FAST, PM, K3, DUAL, TS>;
     static unsigned long long lds_ok = 0;
     if (int rc = abc_allow_lds((const void*)fn, 160 * 1024, &lds_ok)) return rc;
     const int lds = k.qtab_off ? k.qtab_off + (PM > 1 ? 5 : 4) * WTHR_HOST * 4 : g.lds;     // (+ Q's segment table)
-    hipLaunchKernelGGL(fn, dim3(g.nta * g.ntb * nsplit, g.ngroups), dim3(NW * 64), lds, st, k);
+    hipLaunchKernelGGL(fn, dim3(g.nta * g.ntb * nsplit, g.ngroups), dim3(WTHR_HOST), lds, st, k);
     return abc_check_launch("wgrad");
 }
 
@@ -1256,13 +1235,6 @@ template <typename PT, typename QT, typename CT>
 static int wdispatch(const WgK& k, const WGeom& g, int stride, int nsplit, hipStream_t st) {
     if constexpr (sizeof(CT) == 2) {
         if (g.AT == 4) return wlaunch<PT, QT, CT, 4, 2, 1>(k, g, nsplit, st);
-    }
-    if constexpr (sizeof(CT) == 2 && sizeof(PT) == 2 && sizeof(QT) == 2) {
-        if (g.AT == 2 && g.nw == 4) {
-            if (k.k3 && k.p2 != nullptr) return wlaunch3<PT, QT, CT, 2, 2, 1, true, 1, true, true, false, 4>(k, g, nsplit, st);
-            if (k.k3) return wlaunch3<PT, QT, CT, 2, 2, 1, true, 1, true, false, false, 4>(k, g, nsplit, st);
-            return wlaunch3<PT, QT, CT, 2, 2, 1, true, 1, false, false, false, 4>(k, g, nsplit, st);
-        }
     }
     if constexpr (sizeof(CT) == 2 && sizeof(PT) == 2 && sizeof(QT) == 2) {
         if (g.AT == 2 && g.BT == 1 && stride == 2) return wlaunch<PT, QT, CT, 2, 1, 2>(k, g, nsplit, st);
@@ -1483,8 +1455,7 @@ extern "C" int abc_wgrad_blocks(const abc_wgrad_desc* d) {
     if (abc_wgrad_narrow_ok(d) || abc_wgrad_n32r2_ok(d)) return 1;
     WGeom g;
     if (wgeom(d, &g)) return -1;
-    // (4-wave workgroups sit two to a CU: half as many CU-fills per split, so that the caller's nsplit doubles)
-    return g.nw == 4 ? (g.nta * g.ntb * g.ngroups + 1) / 2 : g.nta * g.ntb * g.ngroups;
+    return g.nta * g.ntb * g.ngroups;
 }
 
 extern "C" int abc_wgrad(const abc_wgrad_desc* d, abc_stream_t stream) {
@@ -1526,7 +1497,7 @@ extern "C" int abc_wgrad(const abc_wgrad_desc* d, abc_stream_t stream) {
     // Q's segment table: the static 3x3 step of the 8-wave bf16 prefetch path over whole patches of a same-size image whose offsets
     // fit the entry (relative offset < 16 MB, LDS image < 64 KB), when the table (segments per thread x 512 x 4 bytes) fits the LDS
     k.qtab_off = 0;
-    if (k.k3 && d->stride == 1 && g.fast_p && g.fast_q && g.nw == 8 && !g.ts && g.AT * g.BT >= 4 && d->dtype_c == ABC_BF16 && d->dtype_q == ABC_BF16 &&
+    if (k.k3 && d->stride == 1 && g.fast_p && g.fast_q && !g.ts && g.AT * g.BT >= 4 && d->dtype_c == ABC_BF16 && d->dtype_q == ABC_BF16 &&
         d->Hg % (8 * g.PM) == 0 && d->Wg % 16 == 0 && d->Hq == d->Hg && d->Wq == d->Wg && d->q.Hx == d->Hq && d->q.Wx == d->Wq &&
         (int64_t)(g.HH * d->q.Wx + g.HW) * d->q.ldx * 2 < (int64_t(1) << 24) && g.sQ_bytes < 65536) {
         const int npf_q = g.PM > 1 ? 5 : 4;
@@ -1544,7 +1515,6 @@ extern "C" int abc_wgrad(const abc_wgrad_desc* d, abc_stream_t stream) {
         if (d->tap_dy[t] - g.dy_min != t / 3 || d->tap_dx[t] - g.dx_min != t % 3) k.k3 = 0;
     k.bytesP = (unsigned)((int64_t)d->B * d->p.Hx * d->p.Wx * d->p.ldx * (d->dtype_p == ABC_BF16 ? 2 : 4));
     k.bytesQ = (unsigned)((int64_t)d->B * d->q.Hx * d->q.Wx * d->q.ldx * (d->dtype_q == ABC_BF16 ? 2 : 4));
-    { const char* e = abc_knob("ABC_WGRAD_DBG"); k.dbg = e ? atoi(e) : 0; }  // timing ablations only (results invalid)
     for (int t = 0; t < d->ntaps; ++t) { k.ty[t] = (int8_t)(d->tap_dy[t] - g.dy_min); k.tx[t] = (int8_t)(d->tap_dx[t] - g.dx_min); }
     hipStream_t st = (hipStream_t)stream;
     if (d->dtype_c == ABC_F32) {
@@ -1596,8 +1566,7 @@ extern "C" int abc_wgrad_reduce(const abc_wgrad_reduce_desc* d, abc_stream_t str
         hipLaunchKernelGGL(wgrad_reduce_wave_kernel, dim3((int)n), dim3(64), 0, (hipStream_t)stream, *d);
         return abc_check_launch("wgrad_reduce");
     }
-    static const bool scalar_only = abc_knob("ABC_WGRAD_REDUCE_SCALAR") != nullptr;   // (A/B runs)
-    if (!scalar_only && d->Cb % 4 == 0 && d->Cb_pad % 4 == 0 && ((uintptr_t)d->partial & 15) == 0 && d->nsplit >= 16 && (n >= 16384 || d->nsplit >= 64)) {
+    if (d->Cb % 4 == 0 && d->Cb_pad % 4 == 0 && ((uintptr_t)d->partial & 15) == 0 && d->nsplit >= 16 && (n >= 16384 || d->nsplit >= 64)) {
         hipLaunchKernelGGL(wgrad_reduce_vec_kernel, dim3((int)((n / 4 + 63) / 64)), dim3(256), 0, (hipStream_t)stream, *d);
         return abc_check_launch("wgrad_reduce");
     }

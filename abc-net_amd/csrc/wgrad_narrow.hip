@@ -31,7 +31,6 @@ struct WnK {
     int B, H, W, ldg, cg_off, ldy2, cy2_off, ldx, cx_off, ld_out;
     int tiles_x, tiles_y, ntiles;
     unsigned bytesG, bytesY2, bytesX, bytesOut;
-    int dbg;                             // debug build: phase-skipping ablations (bit 0 loads, 1 commit, 2 MFMA phase, 3 dY store)
 };
 
 constexpr int PRS = 128 * 2 + 16;            // P^T row: 128 pixels bf16 + pad (17 16-byte slots: 16 channels on 16 distinct slots)
@@ -299,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_n32r2_kernel(const WnK a) {
     char* wQ = sQ + 4 * q4 * Q32CS + (q4 >> 2) * 32 + i8 * 4;                                    // + 32 gw, + c * Q32CS
 
     const int first = blockIdx.x, step = gridDim.x;
-    if (first < a.ntiles && !(ABC_DBG(a.dbg) & 1)) issue(first);
+    if (first < a.ntiles) issue(first);
     for (int tile = first; tile < a.ntiles; tile += step) {
         int id = tile;
         const int tx = id % a.tiles_x; id /= a.tiles_x;
@@ -307,92 +306,86 @@ __global__ __launch_bounds__(256, 2) void wgrad_n32r2_kernel(const WnK a) {
         const int b = id / a.tiles_y;
         const unsigned pixbase = (unsigned)((b * a.H + ty * 8) * a.W + tx * 16);
         const int m = border(tx, ty);
-        if (!(ABC_DBG(a.dbg) & 2)) {
-            float ca[DUAL ? 4 : 1], cb[DUAL ? 4 : 1], cc[DUAL ? 4 : 1];
-            if constexpr (DUAL) { LoadVec<float, 4>::ld(&scoef[0][4 * q4], ca); LoadVec<float, 4>::ld(&scoef[1][4 * q4], cb); LoadVec<float, 4>::ld(&scoef[2][4 * q4], cc); }
+        float ca[DUAL ? 4 : 1], cb[DUAL ? 4 : 1], cc[DUAL ? 4 : 1];
+        if constexpr (DUAL) { LoadVec<float, 4>::ld(&scoef[0][4 * q4], ca); LoadVec<float, 4>::ld(&scoef[1][4 * q4], cb); LoadVec<float, 4>::ld(&scoef[2][4 * q4], cc); }
 #pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int r = wave + 4 * it;
+        for (int it = 0; it < 2; ++it) {
+            const int r = wave + 4 * it;
+            unsigned o[4];
+            if constexpr (DUAL) {
+                float v[2][4];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    v[e][0] = fmaf(ca[0], bf_lo(rg[it][e].x), fmaf(cb[0], bf_lo(ry[it][e].x), cc[0]));
+                    v[e][1] = fmaf(ca[1], bf_hi(rg[it][e].x), fmaf(cb[1], bf_hi(ry[it][e].x), cc[1]));
+                    v[e][2] = fmaf(ca[2], bf_lo(rg[it][e].y), fmaf(cb[2], bf_lo(ry[it][e].y), cc[2]));
+                    v[e][3] = fmaf(ca[3], bf_hi(rg[it][e].y), fmaf(cb[3], bf_hi(ry[it][e].y), cc[3]));
+                    if (a.dy_out != nullptr)
+                        __builtin_amdgcn_raw_buffer_store_b64((u32x2){pk2(v[e][0], v[e][1]), pk2(v[e][2], v[e][3])}, rsO, voO,
+                                                              (pixbase + (unsigned)(r * a.W) + 8 * e) * (unsigned)a.ld_out * 2u, 0);
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) o[c] = pk2(v[0][c], v[1][c]);
+            } else {
+                o[0] = __builtin_amdgcn_perm(rg[it][1].x, rg[it][0].x, 0x05040100u); o[1] = __builtin_amdgcn_perm(rg[it][1].x, rg[it][0].x, 0x07060302u);
+                o[2] = __builtin_amdgcn_perm(rg[it][1].y, rg[it][0].y, 0x05040100u); o[3] = __builtin_amdgcn_perm(rg[it][1].y, rg[it][0].y, 0x07060302u);
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) *(unsigned*)(wP + r * 32 + c * P32RS) = o[c];
+        }
+        float qsc[QT ? 4 : 1], qsh[QT ? 4 : 1], qsl[QT ? 4 : 1];
+        if constexpr (QT) { LoadVec<float, 4>::ld(&scoef[3][4 * q4], qsc); LoadVec<float, 4>::ld(&scoef[4][4 * q4], qsh); LoadVec<float, 4>::ld(&scoef[5][4 * q4], qsl); }
+#pragma unroll
+        for (int it = 0; it < 5; ++it) {
+            const int gw = wave + 4 * it;
+            if (gw < 18) {
                 unsigned o[4];
-                if constexpr (DUAL) {
+                if constexpr (QT) {
                     float v[2][4];
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
-                        v[e][0] = fmaf(ca[0], bf_lo(rg[it][e].x), fmaf(cb[0], bf_lo(ry[it][e].x), cc[0]));
-                        v[e][1] = fmaf(ca[1], bf_hi(rg[it][e].x), fmaf(cb[1], bf_hi(ry[it][e].x), cc[1]));
-                        v[e][2] = fmaf(ca[2], bf_lo(rg[it][e].y), fmaf(cb[2], bf_lo(ry[it][e].y), cc[2]));
-                        v[e][3] = fmaf(ca[3], bf_hi(rg[it][e].y), fmaf(cb[3], bf_hi(ry[it][e].y), cc[3]));
-                        if (a.dy_out != nullptr && !(ABC_DBG(a.dbg) & 8))
-                            __builtin_amdgcn_raw_buffer_store_b64((u32x2){pk2(v[e][0], v[e][1]), pk2(v[e][2], v[e][3])}, rsO, voO,
-                                                                  (pixbase + (unsigned)(r * a.W) + 8 * e) * (unsigned)a.ld_out * 2u, 0);
+                        v[e][0] = abc_act(bf_lo(rx[it][e].x), qsc[0], qsh[0], qsl[0]);
+                        v[e][1] = abc_act(bf_hi(rx[it][e].x), qsc[1], qsh[1], qsl[1]);
+                        v[e][2] = abc_act(bf_lo(rx[it][e].y), qsc[2], qsh[2], qsl[2]);
+                        v[e][3] = abc_act(bf_hi(rx[it][e].y), qsc[3], qsh[3], qsl[3]);
                     }
 #pragma unroll
                     for (int c = 0; c < 4; ++c) o[c] = pk2(v[0][c], v[1][c]);
-                } else {
-                    o[0] = __builtin_amdgcn_perm(rg[it][1].x, rg[it][0].x, 0x05040100u); o[1] = __builtin_amdgcn_perm(rg[it][1].x, rg[it][0].x, 0x07060302u);
-                    o[2] = __builtin_amdgcn_perm(rg[it][1].y, rg[it][0].y, 0x05040100u); o[3] = __builtin_amdgcn_perm(rg[it][1].y, rg[it][0].y, 0x07060302u);
-                }
+                    if (m != 0) {              // (the padding of the convolution is zero AFTER the activation)
+                        const unsigned keep = (outside(m, it, 0) ? 0u : 0x0000FFFFu) | (outside(m, it, 1) ? 0u : 0xFFFF0000u);
 #pragma unroll
-                for (int c = 0; c < 4; ++c) *(unsigned*)(wP + r * 32 + c * P32RS) = o[c];
-            }
-        }
-        if (!(ABC_DBG(a.dbg) & 2)) {
-            float qsc[QT ? 4 : 1], qsh[QT ? 4 : 1], qsl[QT ? 4 : 1];
-            if constexpr (QT) { LoadVec<float, 4>::ld(&scoef[3][4 * q4], qsc); LoadVec<float, 4>::ld(&scoef[4][4 * q4], qsh); LoadVec<float, 4>::ld(&scoef[5][4 * q4], qsl); }
-#pragma unroll
-            for (int it = 0; it < 5; ++it) {
-                const int gw = wave + 4 * it;
-                if (gw < 18) {
-                    unsigned o[4];
-                    if constexpr (QT) {
-                        float v[2][4];
-#pragma unroll
-                        for (int e = 0; e < 2; ++e) {
-                            v[e][0] = abc_act(bf_lo(rx[it][e].x), qsc[0], qsh[0], qsl[0]);
-                            v[e][1] = abc_act(bf_hi(rx[it][e].x), qsc[1], qsh[1], qsl[1]);
-                            v[e][2] = abc_act(bf_lo(rx[it][e].y), qsc[2], qsh[2], qsl[2]);
-                            v[e][3] = abc_act(bf_hi(rx[it][e].y), qsc[3], qsh[3], qsl[3]);
-                        }
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) o[c] = pk2(v[0][c], v[1][c]);
-                        if (m != 0) {              // (the padding of the convolution is zero AFTER the activation)
-                            const unsigned keep = (outside(m, it, 0) ? 0u : 0x0000FFFFu) | (outside(m, it, 1) ? 0u : 0xFFFF0000u);
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) o[c] &= keep;
-                        }
-                    } else {
-                        o[0] = __builtin_amdgcn_perm(rx[it][1].x, rx[it][0].x, 0x05040100u); o[1] = __builtin_amdgcn_perm(rx[it][1].x, rx[it][0].x, 0x07060302u);
-                        o[2] = __builtin_amdgcn_perm(rx[it][1].y, rx[it][0].y, 0x05040100u); o[3] = __builtin_amdgcn_perm(rx[it][1].y, rx[it][0].y, 0x07060302u);
+                        for (int c = 0; c < 4; ++c) o[c] &= keep;
                     }
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) *(unsigned*)(wQ + gw * 32 + c * Q32CS) = o[c];
+                } else {
+                    o[0] = __builtin_amdgcn_perm(rx[it][1].x, rx[it][0].x, 0x05040100u); o[1] = __builtin_amdgcn_perm(rx[it][1].x, rx[it][0].x, 0x07060302u);
+                    o[2] = __builtin_amdgcn_perm(rx[it][1].y, rx[it][0].y, 0x05040100u); o[3] = __builtin_amdgcn_perm(rx[it][1].y, rx[it][0].y, 0x07060302u);
                 }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) *(unsigned*)(wQ + gw * 32 + c * Q32CS) = o[c];
             }
         }
         __syncthreads();               // the tile's images are complete
-        if (tile + step < a.ntiles && !(ABC_DBG(a.dbg) & 1)) issue(tile + step);      // (the next tile's loads fly under the MFMAs)
-        if (!(ABC_DBG(a.dbg) & 4)) {
-            bf16x8 fa[4];
+        if (tile + step < a.ntiles) issue(tile + step);      // (the next tile's loads fly under the MFMAs)
+        bf16x8 fa[4];
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) fa[ks] = *(const bf16x8*)(aP + ks * 64);
+        for (int ks = 0; ks < 4; ++ks) fa[ks] = *(const bf16x8*)(aP + ks * 64);
 #pragma unroll
-            for (int w = 0; w < 11; ++w) {
-                const char* rp = aQ + w * Q32ROW;
-                const u32x4 wl = *(const u32x4*)rp, wh = *(const u32x4*)(rp + 16);
-                typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
-                const u32x8 t = __builtin_shufflevector(wl, wh, 0, 1, 2, 3, 4, 5, 6, 7);
-                const u32x4 f1 = __builtin_shufflevector(t, t, 1, 2, 3, 4), f2 = __builtin_shufflevector(t, t, 2, 3, 4, 5),
-                            f3 = __builtin_shufflevector(t, t, 3, 4, 5, 6);
+        for (int w = 0; w < 11; ++w) {
+            const char* rp = aQ + w * Q32ROW;
+            const u32x4 wl = *(const u32x4*)rp, wh = *(const u32x4*)(rp + 16);
+            typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
+            const u32x8 t = __builtin_shufflevector(wl, wh, 0, 1, 2, 3, 4, 5, 6, 7);
+            const u32x4 f1 = __builtin_shufflevector(t, t, 1, 2, 3, 4), f2 = __builtin_shufflevector(t, t, 2, 3, 4, 5),
+                        f3 = __builtin_shufflevector(t, t, 3, 4, 5, 6);
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int dy = w - 2 * ks;
-                    if (dy >= 0 && dy < 5) {
-                        acc[dy][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&wl, acc[dy][0], 0, 0, 0);
-                        acc[dy][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&f1, acc[dy][1], 0, 0, 0);
-                        acc[dy][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&f2, acc[dy][2], 0, 0, 0);
-                        acc[dy][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&f3, acc[dy][3], 0, 0, 0);
-                        acc[dy][4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&wh, acc[dy][4], 0, 0, 0);
-                    }
+            for (int ks = 0; ks < 4; ++ks) {
+                const int dy = w - 2 * ks;
+                if (dy >= 0 && dy < 5) {
+                    acc[dy][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&wl, acc[dy][0], 0, 0, 0);
+                    acc[dy][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&f1, acc[dy][1], 0, 0, 0);
+                    acc[dy][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&f2, acc[dy][2], 0, 0, 0);
+                    acc[dy][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&f3, acc[dy][3], 0, 0, 0);
+                    acc[dy][4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks], *(const bf16x8*)&wh, acc[dy][4], 0, 0, 0);
                 }
             }
         }
@@ -412,7 +405,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_n32r2_kernel(const WnK a) {
 
 // 1 when the 16-channel kernel takes this descriptor
 int abc_wgrad_narrow_ok(const abc_wgrad_desc* d) {
-    if (abc_knob("ABC_WGRAD_NONARROW")) return 0;
     if (d->Ca != 16 || d->Cb != 16 || d->ntaps != 9 || d->stride != 1) return 0;
     if (d->dtype_p != ABC_BF16 || d->dtype_q != ABC_BF16 || d->dtype_c != ABC_BF16) return 0;
     for (int t = 0; t < 9; ++t)
@@ -440,7 +432,7 @@ int abc_wgrad_narrow_launch(const abc_wgrad_desc* d, abc_stream_t stream) {
     k.bytesG = (unsigned)((int64_t)d->B * d->Hg * d->Wg * d->p.ldx * 2);
     k.bytesY2 = dual ? (unsigned)((int64_t)d->B * d->Hg * d->Wg * d->ld_p2 * 2) : 0u;
     k.bytesX = (unsigned)((int64_t)d->B * d->Hg * d->Wg * d->q.ldx * 2);
-    k.bytesOut = 0u; k.dbg = 0;
+    k.bytesOut = 0u;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(d->nsplit), blk(256);
     if (dual && qt) hipLaunchKernelGGL((wgrad_narrow16_kernel<true, true>), grid, blk, 0, st, k);
@@ -452,7 +444,6 @@ int abc_wgrad_narrow_launch(const abc_wgrad_desc* d, abc_stream_t stream) {
 
 // 1 when the 5x5 32-channel kernel takes this descriptor
 int abc_wgrad_n32r2_ok(const abc_wgrad_desc* d) {
-    if (abc_knob("ABC_WGRAD_NON32R2")) return 0;
     if (d->Ca != 32 || d->Cb != 32 || d->ntaps != 25 || d->stride != 1) return 0;
     if (d->dtype_p != ABC_BF16 || d->dtype_q != ABC_BF16 || d->dtype_c != ABC_BF16) return 0;
     for (int t = 0; t < 25; ++t)
@@ -481,7 +472,6 @@ int abc_wgrad_n32r2_launch(const abc_wgrad_desc* d, abc_stream_t stream) {
     k.bytesY2 = dual ? (unsigned)((int64_t)d->B * d->Hg * d->Wg * d->ld_p2 * 2) : 0u;
     k.bytesX = (unsigned)((int64_t)d->B * d->Hg * d->Wg * d->q.ldx * 2);
     k.bytesOut = dual && d->p_out ? (unsigned)((int64_t)d->B * d->Hg * d->Wg * d->ld_pout * 2) : 0u;
-    k.dbg = abc_knob("ABC_W32_DBG") ? atoi(abc_knob("ABC_W32_DBG")) : 0;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(d->nsplit), blk(256);
     if (dual && qt) hipLaunchKernelGGL((wgrad_n32r2_kernel<true, true>), grid, blk, 0, st, k);

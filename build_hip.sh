@@ -3,15 +3,11 @@
 set -e
 cd "$(dirname "$0")/abc-net_amd/csrc"
 OUT=../libabcnet_hip.so
-FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result $ABC_EXTRA_FLAGS"   # (ABC_EXTRA_FLAGS: -D switches of measured A/B builds, e.g. -DABC_DEEP_TM=4)
+FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result $ABC_EXTRA_FLAGS"   # (ABC_EXTRA_FLAGS: extra compiler flags of measured A/B builds, e.g. -fno-unroll-loops)
 [ -n "$ABC_RESOURCE_USAGE" ] && FLAGS="$FLAGS -Rpass-analysis=kernel-resource-usage"
-# debug build (ABC_KERNEL_DEBUG=1 ./build_hip.sh): phase-skipping ablations, in-kernel phase timestamps and the
-# environment-driven experiment switches (abc_knob in common.hpp); the production library reads no environment variable
-FLAVOUR=production
-[ -n "$ABC_KERNEL_DEBUG" ] && FLAGS="$FLAGS -DABC_KERNEL_DEBUG=1" && FLAVOUR=debug
-# (objects of the other flavour must not be linked)
-[ "$(cat .build_flavour 2>/dev/null)" != "$FLAVOUR" ] && rm -f *.o *.d
-echo $FLAVOUR > .build_flavour
+# (objects compiled under other flags must not be linked: a change of FLAGS recompiles everything)
+[ "$(cat .build_flavour 2>/dev/null)" != "$FLAGS" ] && rm -f *.o *.d
+echo "$FLAGS" > .build_flavour
 
 # an object is stale when its source or ANY header it included last time (the -MD dependency file) is newer
 stale() {
@@ -27,7 +23,7 @@ stale() {
 
 OBJS=""
 pids=""
-for f in conv_igemm conv_fast conv_fast8 conv_fast_lp convt_fused conv_narrow stem heads heads_fused wgrad wgrad_narrow bn_act loss misc optim cbam metrics extract raster augment; do
+for f in conv_igemm conv_fast convt_fused conv_narrow stem heads heads_fused wgrad wgrad_narrow bn_act loss misc optim cbam metrics extract raster augment; do
   if stale $f; then
     hipcc $FLAGS -MD -MF $f.d -c $f.hip -o $f.o &
     pids="$pids $!"

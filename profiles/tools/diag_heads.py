@@ -1,4 +1,4 @@
-import os, sys
+import sys
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 import torch
 import abcnet_amd
@@ -15,7 +15,6 @@ def one():
     tr.load_batch(x.cuda(), [t.cuda() for t in tg]); tr.step(); torch.cuda.synchronize()
     return m, m._flat_grad.clone()
 m1, g1 = one()
-os.environ["ABC_NO_HEADS_BATCH"] = "1"
 m2, g2 = one()
 rows = []
 for name, (off, n) in m1._lay_p.items():

@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/hfprof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-P="python3 $R/scratch/hf_time.py 0"
+P="python3 $R/profiles/tools/hf_time.py"
 cd $R
 timeout -k 10 150 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/mem -- $P > $O/mem.log 2>&1
 echo fetch done

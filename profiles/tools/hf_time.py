@@ -7,8 +7,6 @@ from abcnet_amd.engine import head_offsets
 from abcnet_amd.synthetic import synthetic_targets
 HEADS = [1, 14, 3, 2, 1, 360, 60, 60]
 DEV = "cuda"
-if os.environ.get("ABC_TOOL_LIB"):
-    L.LIB_PATH = os.path.abspath(os.environ["ABC_TOOL_LIB"])
 lib = L.load()
 B, hw, ld = 16, 96, 1024
 npix = B * hw * hw
@@ -54,10 +52,8 @@ def t(fn, n=10):
     for _ in range(n): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1000
-args = sys.argv[1:]
-if args and args[0] == "--flags":
+if sys.argv[1:] == ["--flags"]:
     # the rasteriser's group flags, from the dense maps: bit i = some pixel of the 32-pixel group has a target of head i (rho: the bond types')
-    args = args[1:]
     fl = torch.zeros(npix // 32, dtype=torch.int32, device=DEV)
     for i, tt in enumerate(tg):
         m = tt.reshape(B, -1, hw * hw)
@@ -66,8 +62,5 @@ if args and args[0] == "--flags":
     zb = torch.zeros(512, dtype=torch.uint8, device=DEV)
     d.target_flags, d.zero_bytes = fl.data_ptr(), zb.data_ptr()
     print("flagged groups per head:", [round(float(((fl >> i) & 1).float().mean()), 3) for i in range(8)])
-for dbg in [int(x, 0) for x in (args or ["0"])]:
-    os.environ["ABC_HF_DBG"] = str(dbg)     # bits 0-6: phase ablations of heads_fused.hip; 256 << g: work type g not run
-    print("dbg %3d: fwd_bwd %.1f us" % (dbg, t(lambda: L.check(lib.abc_heads_fused_fwd_bwd(C.byref(d), st), "f"))), flush=True)
-os.environ["ABC_HF_DBG"] = "0"
+print("fwd_bwd %.1f us" % t(lambda: L.check(lib.abc_heads_fused_fwd_bwd(C.byref(d), st), "f")), flush=True)
 print("wgrad %.1f us" % t(lambda: L.check(lib.abc_heads_fused_wgrad(C.byref(d), st), "w")))

@@ -1,6 +1,5 @@
 # unet2's 5x5 32 -> 32 weight gradient alone (wgrad_n32r2_kernel): python profiles/tools/time_w32.py [nsplit ...]
-# (debug build: ABC_W32_DBG = phase-skipping ablations, bit 0 loads, 1 commit, 2 MFMA phase, 3 dY store)
-import sys, os, ctypes as C
+import sys, ctypes as C
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 import torch
 import abcnet_amd
@@ -36,4 +35,4 @@ for nsplit in [int(v) for v in sys.argv[1:]] or [512]:
     e0.record()
     for _ in range(20): run()
     e1.record(); torch.cuda.synchronize()
-    print("wgrad 32x32 5x5 dual+QT tile=(%d,%d) nsplit=%d dbg=%s: %.1f us" % (at_.value, bt_.value, nsplit, os.environ.get("ABC_W32_DBG", "0"), e0.elapsed_time(e1) / 20 * 1000), flush=True)
+    print("wgrad 32x32 5x5 dual+QT tile=(%d,%d) nsplit=%d: %.1f us" % (at_.value, bt_.value, nsplit, e0.elapsed_time(e1) / 20 * 1000), flush=True)

@@ -3,6 +3,8 @@ mirror structs match the library, and the host-side logic (architecture table, p
 sampler, dropout mirror, gloo gradient reducer at world size 2) behaves.  No kernel is launched here."""
 import os
 import re
+import shutil
+import subprocess
 import sys
 
 import pytest
@@ -26,6 +28,22 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "library does not export %s" % name
         assert name in L.SYMBOLS, "binding does not cover %s" % name
     assert set(L.SYMBOLS) <= declared | {"abc_sizeof"}
+    # the library exports exactly the header's functions, and never reads the environment
+    every = set(re.findall(r"^[A-Za-z_][\w \t*]*?\b(abc_[a-z0-9_]+)\s*\(", hdr, flags=re.M))
+    exported = {s for s in _dynamic_symbols("--defined-only") if s.startswith("abc_")}
+    assert exported == every, (sorted(exported - every), sorted(every - exported))
+    assert "getenv" not in _dynamic_symbols("--undefined-only")
+
+
+def _dynamic_symbols(which):
+    """names in the library's dynamic symbol table (which: --defined-only / --undefined-only); binutils nm from PATH,
+    else an llvm-nm (PATH, then ROCm's) -- both print the name last and take the same flags"""
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or next(
+        (p for p in ("/opt/rocm/llvm/bin/llvm-nm", "/opt/rocm/lib/llvm/bin/llvm-nm") if os.path.exists(p)), None)
+    assert nm, "no nm or llvm-nm found to list the library's dynamic symbols"
+    r = subprocess.run([nm, "-D", which, L.LIB_PATH], capture_output=True, text=True)
+    assert r.returncode == 0, "%s -D %s failed: %s" % (nm, which, r.stderr.strip())
+    return {line.split()[-1].split("@")[0] for line in r.stdout.splitlines() if line.split()}
 
 
 def test_status_and_error_text_without_gpu():
