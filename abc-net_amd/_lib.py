@@ -185,13 +185,20 @@ class ImageDesc(C.Structure):
                 ("params_host", vp), ("B", i32), ("S", i32), ("mode", i32), ("test_max_ink", i32)]
 
 
+class AssembleDesc(C.Structure):
+    _fields_ = [("counts", vp), ("atoms", vp), ("bonds", vp), ("bond_rho", vp), ("trig", vp), ("B", i32), ("cap_atoms", i32),
+                ("cap_bonds", i32), ("cap_mol_bonds", i32), ("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp),
+                ("work", vp)]
+
+
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
+MOL_EMPTY, MOL_TRUNCATED = 1, 2     # abc_mol_status
 
 
 _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnApplyDesc, WgradDesc, WgradReduceDesc,
             LossDesc, LossFinDesc, AdamDesc, NmsDesc, CbamChannelDesc, CbamPixDesc, CbamConv7Desc, MetricsDesc, ExtractDesc, RasterDesc,
-            HeadsFusedDesc, HeadsEpi, ConvTDesc, LossScaleDesc, AdamSeg, AdamClass, AdamMultiDesc, ImageDesc]
+            HeadsFusedDesc, HeadsEpi, ConvTDesc, LossScaleDesc, AdamSeg, AdamClass, AdamMultiDesc, ImageDesc, AssembleDesc]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -255,6 +262,8 @@ SYMBOLS = {
     "abc_extract_work_ints": (i64, [P(ExtractDesc)]),
     "abc_extract_work_masks": (i64, [P(ExtractDesc)]),
     "abc_extract_peaks": (C.c_int, [P(ExtractDesc), vp]),
+    "abc_assemble_work_ints": (i64, [P(AssembleDesc)]),
+    "abc_assemble_graphs": (C.c_int, [P(AssembleDesc), vp]),
     "abc_rasterize_targets": (C.c_int, [P(RasterDesc), vp]),
     "abc_build_images": (C.c_int, [P(ImageDesc), vp]),
     "abc_metrics_blocks": (C.c_int, [P(MetricsDesc)]),

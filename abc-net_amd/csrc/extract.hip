@@ -2,7 +2,7 @@
 //
 // The reference walks the NMS masks with per-pixel `.cpu().item()` calls (hundreds of host round trips per image).
 // Here one workgroup per image turns the head maps into two compact, ORDERED lists -- the wire format into the
-// unchanged CPU graph-assembly / RDKit stage (img2smiles2.py:193-344):
+// graph-assembly stage (img2smiles2.py:193-311: assemble.hip, or the reference's own code on the host):
 //   atoms : (x, y, type, charge, hs)           raster order, greedy suppression of peaks within squared distance < 4
 //                                              of an already accepted atom (img2smiles2.py:171-191)
 //   bonds : (x, y, omega bin, type) + |rho|    raster order of the bond peaks, bins ascending; a bin survives unless the
@@ -18,39 +18,12 @@
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
+#include "block_scan.hpp"
 
 namespace {
 
 constexpr int XT = 1024;          // threads per workgroup
 constexpr int MAX_BPEAKS = 4096;  // bond peaks per image held for phase C (more are counted, not expanded)
-
-// exclusive prefix sum of v over the workgroup (v may pack two 16-bit counters); wt = LDS scratch [XT / 64 + 1]
-__device__ inline unsigned block_excl_scan(unsigned v, unsigned* wt, unsigned* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();  // wt may still be read from the previous call
-    if (lane == 63) wt[wave] = inc;
-    __syncthreads();
-    if (wave == 0) {
-        const unsigned x = lane < XT / 64 ? wt[lane] : 0u;
-        unsigned s = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned t = __shfl_up(s, o);
-            if (lane >= o) s += t;
-        }
-        if (lane < XT / 64) wt[lane] = s - x;
-        if (lane == XT / 64 - 1) wt[XT / 64] = s;
-    }
-    __syncthreads();
-    *total = wt[XT / 64];
-    return wt[wave] + inc - v;
-}
 
 template <int K>
 __device__ inline int argmax_plane(const float* p, size_t stride) {  // first maximum, as torch.argmax
@@ -83,7 +56,7 @@ __global__ __launch_bounds__(XT) void extract_kernel(const abc_extract_desc d) {
         const int p = p0 + tid;
         const bool fa = p < hw && am[p] != 0.f, fb = p < hw && bm[p] != 0.f;
         unsigned tot;
-        const unsigned ex = block_excl_scan((fa ? 1u : 0u) | (fb ? 0x10000u : 0u), wt, &tot);
+        const unsigned ex = block_excl_scan<XT>((fa ? 1u : 0u) | (fb ? 0x10000u : 0u), wt, &tot);
         const int ia = na + (int)(ex & 0xFFFFu), ib = nb + (int)(ex >> 16);
         if (fa && ia < d.cap_atoms) atom_px[ia] = p;
         if (fb && ib < MAX_BPEAKS) bond_px[ib] = p;
@@ -156,7 +129,7 @@ __global__ __launch_bounds__(XT) void extract_kernel(const abc_extract_desc d) {
     for (int q = 0; q < 4; ++q) { const int i = tid * 4 + q; c4[q] = i < nb_l ? cnt[i] : 0; s4 += c4[q]; }
     unsigned tot_b;
     // (totals can exceed 16 bits: plain 32-bit scan, nothing packed)
-    unsigned ex = block_excl_scan((unsigned)s4, wt, &tot_b);
+    unsigned ex = block_excl_scan<XT>((unsigned)s4, wt, &tot_b);
 #pragma unroll
     for (int q = 0; q < 4; ++q) { const int i = tid * 4 + q; if (i < nb_l) cnt[i] = (int)ex; ex += (unsigned)c4[q]; }
     __syncthreads();

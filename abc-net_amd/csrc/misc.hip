@@ -596,6 +596,7 @@ extern "C" int abc_sizeof(int which) {
         case 24: return (int)sizeof(abc_adam_class);
         case 25: return (int)sizeof(abc_adam_multi_desc);
         case 26: return (int)sizeof(abc_image_desc);
+        case 27: return (int)sizeof(abc_assemble_desc);
         default: return -1;
     }
 }

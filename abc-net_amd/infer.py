@@ -6,8 +6,9 @@
 One step = eval-mode forward (running-statistics BatchNorm folded into the convolution weights / biases at refresh()
 time, activations in the convolutions' epilogues, no dropout) + the peak-NMS kernel, on a batch already resident in HBM, replayed from one hipGraph.  The weights do not change between
 steps, so re-packing them and deriving the eval-mode BatchNorm coefficients happens in `refresh()`, not in the step;
-call it again after `load_state_dict`.  The SMILES assembly that follows in the reference (img2smiles2.py:104-344, RDKit) is out of
-scope: the step ends with the four mask / |rho| maps the decoder reads.
+call it again after `load_state_dict`.  The step ends with the four mask / |rho| maps the decoder reads; opt-in, the candidate
+lists (extract=True, img2smiles2.py:113-191) and the assembled molecules (assemble=True, :193-311) in the same graph.  RDKit
+(generate_smiles.py:115-119) is out of scope.
 """
 from __future__ import annotations
 
@@ -20,7 +21,8 @@ from . import _lib as L
 
 class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
-                 fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False):
+                 fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
+                 assemble=False, cap_mol_bonds=None):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -33,7 +35,11 @@ class InferenceRunner:
         decode (with nms_in_heads): store only what the decoder of img2smiles2.py:104-191 reads -- |rho| instead of the raw rho map
         (:73) and, for the 360 bond-type planes, their six-way arg max per omega bin as a uint8 map (:71,112; .btype_idx);
         .logits[5] and .logits[6] are then None, the candidate lists (extract=True) are unchanged bit for bit.  1.7 GB less written
-        per batch of 64 at 512 x 512"""
+        per batch of 64 at 512 x 512
+        assemble (implies extract): the graph assembly of img2smiles2.py:193-311 (ops.GraphAssembler) on the candidate lists, in the same
+        captured graph after the extractor; molecules() returns the result.  It reads the lists, not the maps: the same with
+        decode=True and fp8=True"""
+        extract = bool(extract) or bool(assemble)
         from .ops import EXTRACT_HEADS, check_nms_heads
         check_nms_heads(model.heads, "InferenceRunner")
         if extract and list(model.heads) != EXTRACT_HEADS:
@@ -86,6 +92,11 @@ class InferenceRunner:
             from .ops import PeakExtractor
             self.extractor = PeakExtractor(lg, self.atom_mask, self.bond_mask, cap_atoms=cap_atoms, cap_bonds=cap_bonds,
                                            btype_idx=self.btype_idx if self.decode else None, rho_abs=self.rho_abs if self.decode else None)
+        self.assembler = None
+        if assemble:
+            from .ops import GraphAssembler
+            with torch.cuda.device(dev):
+                self.assembler = GraphAssembler.from_extractor(self.extractor, cap_mol_bonds=cap_mol_bonds)
         self.use_graph = use_graph
         self._graph = None
         self.steps = 0
@@ -127,12 +138,21 @@ class InferenceRunner:
         L.check(self.eng.lib.abc_nms_peaks(C.byref(self._nms), st), "nms_peaks")
         if self.extractor is not None:
             self.extractor.run(st)
+        if self.assembler is not None:
+            self.assembler.run(st)
 
     def candidates(self):
         """the per-image atom / bond candidate lists of the last step (host sync; needs extract=True)"""
         if self.extractor is None:
             raise L.AbcNetHipError("InferenceRunner was built without extract=True")
         return self.extractor.lists()
+
+    def molecules(self):
+        """the assembled molecule (decode.Molecule) of every image of the last step, None where the reference finds no key point
+        (host sync; needs assemble=True); `Chem.MolFromMolBlock(m.molblock())` is the reference's next call"""
+        if self.assembler is None:
+            raise L.AbcNetHipError("InferenceRunner was built without assemble=True")
+        return self.assembler.molecules()
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""

@@ -1,5 +1,6 @@
 """Thin host wrappers over single C-ABI kernels used outside the engine's static plan:
-fused loss (train.py:95-137), inference NMS (img2smiles2.py:61-79), fused Adam (train.py:55,141)."""
+fused loss (train.py:95-137), inference NMS (img2smiles2.py:61-79), candidate extraction and graph assembly
+(img2smiles2.py:113-311), fused Adam (train.py:55,141)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -210,7 +211,7 @@ def nms_peaks(atom, bond, rho, omega):
 
 class PeakExtractor:
     """img2smiles2.py:113-191 on the device: NMS masks + raw head maps -> compact ordered candidate lists (the wire
-    format into the unchanged CPU graph-assembly stage).  Static buffers, one launch, graph-capture safe; `lists()` is the
+    format into the graph-assembly stage: GraphAssembler below, or the reference's own code on the host).  Static buffers, one launch, graph-capture safe; `lists()` is the
     only host sync (one small D2H per batch instead of hundreds of .item() calls per image)."""
 
     def __init__(self, logits, atom_mask, bond_mask, cap_atoms=512, cap_bonds=16384, btype_idx=None, rho_abs=None):
@@ -278,6 +279,76 @@ class PeakExtractor:
             trunc = a > self.cap_atoms or m > self.cap_bonds or int(cnt[b, 0]) > self.cap_atoms or int(cnt[b, 2]) > 4096
             a, m = min(a, self.cap_atoms), min(m, self.cap_bonds)
             out.append({"atoms": atoms[b, :a], "bonds": bonds[b, :m], "rho": rho[b, :m], "counts": cnt[b].tolist(), "truncated": trunc})
+        return out
+
+
+class GraphAssembler:
+    """img2smiles2.py:193-311 on the device: the extractor's candidate lists -> the molecule of every image (csrc/assemble.hip:
+    bond ends by float64 arg-mins in the reference's operation order, first bond of every atom pair, valence repair, atom
+    compaction, implicit-hydrogen list).  Reads the list buffers in place; static outputs, one launch, graph-capture safe;
+    `molecules()` is the only host sync (one small D2H per batch).
+
+    An image without an atom peak or without a bond peak gives None (the reference's results.append(None), :126-129).  One input
+    the reference does not define -- bond peaks exist but no candidate survives the bin rule; its np.flip raises on the empty
+    array -- gives a molecule with zero atoms and zero bonds here, the same as "no bond survives the edge filter"."""
+
+    def __init__(self, counts, atoms, bonds, bond_rho, cap_mol_bonds=None):
+        """counts int32 [B, 4], atoms int32 [B, cap_atoms, 5], bonds int32 [B, cap_bonds, 4], bond_rho f32 [B, cap_bonds]: device
+        tensors of PeakExtractor's layout (its own buffers, or hand-made lists).  cap_mol_bonds: bonds kept per image (default
+        4 * cap_atoms, at most cap_bonds); more are reported as `truncated`."""
+        from .decode import omega_table
+        for t, dt in ((counts, torch.int32), (atoms, torch.int32), (bonds, torch.int32), (bond_rho, torch.float32)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == dt):
+                raise L.AbcNetHipError("GraphAssembler wants contiguous int32 / f32 device tensors of the extractor's layout (no CPU fallback)")
+        if atoms.dim() != 3 or atoms.shape[2] != 5 or bonds.dim() != 3 or bonds.shape[2] != 4:
+            raise ValueError("GraphAssembler: atoms must be [B, cap_atoms, 5] and bonds [B, cap_bonds, 4], got %s and %s"
+                             % (tuple(atoms.shape), tuple(bonds.shape)))
+        B, cap_atoms, cap_bonds = atoms.shape[0], atoms.shape[1], bonds.shape[1]
+        if tuple(counts.shape) != (B, 4) or bonds.shape[0] != B or tuple(bond_rho.shape) != (B, cap_bonds):
+            raise ValueError("GraphAssembler: counts must be [%d, 4] and bond_rho [%d, %d], got %s and %s"
+                             % (B, B, cap_bonds, tuple(counts.shape), tuple(bond_rho.shape)))
+        if cap_mol_bonds is None:
+            cap_mol_bonds = min(4 * cap_atoms, cap_bonds)
+        lib = L.load()
+        self.lib = lib
+        dev = atoms.device
+        self.trig = torch.from_numpy(omega_table()).to(dev)
+        d = L.AssembleDesc()
+        d.counts, d.atoms, d.bonds, d.bond_rho, d.trig = counts.data_ptr(), atoms.data_ptr(), bonds.data_ptr(), bond_rho.data_ptr(), self.trig.data_ptr()
+        d.B, d.cap_atoms, d.cap_bonds, d.cap_mol_bonds = B, cap_atoms, cap_bonds, cap_mol_bonds
+        self.mol_counts = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+        self.mol_atoms = torch.zeros((B, cap_atoms, 5), dtype=torch.int32, device=dev)
+        self.mol_bonds = torch.zeros((B, max(cap_mol_bonds, 1), 4), dtype=torch.int32, device=dev)
+        self.mol_implh = torch.zeros((B, cap_atoms), dtype=torch.int32, device=dev)
+        self.work = torch.zeros((max(lib.abc_assemble_work_ints(C.byref(d)), 1),), dtype=torch.int32, device=dev)
+        d.mol_counts, d.mol_atoms, d.mol_bonds, d.mol_implh = (self.mol_counts.data_ptr(), self.mol_atoms.data_ptr(), self.mol_bonds.data_ptr(),
+                                                               self.mol_implh.data_ptr())
+        d.work = self.work.data_ptr()
+        self.d, self.keep = d, (counts, atoms, bonds, bond_rho)
+        self.B, self.cap_atoms, self.cap_bonds, self.cap_mol_bonds = B, cap_atoms, cap_bonds, cap_mol_bonds
+
+    @classmethod
+    def from_extractor(cls, ex, cap_mol_bonds=None):
+        return cls(ex.counts, ex.atoms, ex.bonds, ex.bond_rho, cap_mol_bonds=cap_mol_bonds)
+
+    def run(self, stream=None):
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        L.check(self.lib.abc_assemble_graphs(C.byref(self.d), stream), "assemble_graphs")
+
+    def molecules(self):
+        """per image: a decode.Molecule, or None for an image without an atom peak or without a bond peak (host sync)"""
+        from .decode import Molecule
+        cnt = self.mol_counts.cpu().numpy()
+        na, nb, nh = (int(cnt[:, i].max()) for i in range(3))
+        atoms, bonds, implh = self.mol_atoms[:, :na].cpu().numpy(), self.mol_bonds[:, :nb].cpu().numpy(), self.mol_implh[:, :nh].cpu().numpy()
+        out = []
+        for b in range(self.B):
+            a, m, k, status = (int(v) for v in cnt[b])
+            if status & L.MOL_EMPTY:
+                out.append(None)
+                continue
+            out.append(Molecule.from_device_rows(atoms[b, :a], bonds[b, :m], implh[b, :k], truncated=bool(status & L.MOL_TRUNCATED)))
         return out
 
 

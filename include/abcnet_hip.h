@@ -603,6 +603,34 @@ int64_t abc_extract_work_ints(const abc_extract_desc* d);
 int64_t abc_extract_work_masks(const abc_extract_desc* d);
 int abc_extract_peaks(const abc_extract_desc* d, abc_stream_t stream);
 
+/* Graph assembly for the SMILES decoder (img2smiles2.py:193-311): from the candidate lists of abc_extract_peaks (read in place)
+ * to the molecule the reference hands to its mol-block writer.  One workgroup per image, float64 decisions in the reference's
+ * operation order (csrc/assemble.hip), no allocation, no sync.
+ *   bond ends    every candidate attaches to two accepted atoms (arg-min of the reference's two distances, first minimum wins);
+ *   edge filter  a candidate with both ends on one atom (or rho == 0 / not finite) is dropped; of the rest the FIRST of every unordered atom pair stays;
+ *   repair       an atom whose valence count exceeds its type's maximum becomes O, N, C, P, S, Cl for a count of 2..7;
+ *   compaction   atoms no kept bond touches are dropped, the rest are numbered from 1 in list order;
+ *   implicit H   atoms at a kept aromatic bond that are not carbon and have hs != 0, in order of first appearance.
+ * mol_counts[b] = (atoms, bonds, implicit-H entries, status bits).  ABC_MOL_EMPTY: no atom peak or no bond peak (the
+ * reference's results.append(None)); ABC_MOL_TRUNCATED: the extractor truncated a list or cap_mol_bonds was hit (the stored
+ * molecule is then built from the truncated lists).  Bond peaks without a surviving candidate give zero atoms and zero bonds. */
+enum abc_mol_status { ABC_MOL_EMPTY = 1, ABC_MOL_TRUNCATED = 2 };
+typedef struct abc_assemble_desc {
+    const int32_t* counts;    /* [B][4]            as abc_extract_desc.counts */
+    const int32_t* atoms;     /* [B][cap_atoms][5] */
+    const int32_t* bonds;     /* [B][cap_bonds][4] */
+    const float* bond_rho;    /* [B][cap_bonds] */
+    const double* trig;       /* device [2][60]: cos, then sin, of k * (pi / 30) + pi / 60 - pi / 2 (computed by the caller) */
+    int32_t B, cap_atoms, cap_bonds, cap_mol_bonds;   /* cap_atoms 1..2048 */
+    int32_t* mol_counts;      /* [B][4] */
+    int32_t* mol_atoms;       /* [B][cap_atoms][5]      (x, y, vocabulary index after repair, charge VALUE, hs) */
+    int32_t* mol_bonds;       /* [B][cap_mol_bonds][4]  (end 1, end 2 (1-based), order 1..6, index of the source candidate) */
+    int32_t* mol_implh;       /* [B][cap_atoms]         1-based atom indices */
+    int32_t* work;            /* scratch, abc_assemble_work_ints() int32 */
+} abc_assemble_desc;
+int64_t abc_assemble_work_ints(const abc_assemble_desc* d);
+int abc_assemble_graphs(const abc_assemble_desc* d, abc_stream_t stream);
+
 /* The 17 training meters of train.py:145-215 (each an AverageMeter.update(num/den, den), meter.py:12-16), from the
  * NCHW f32 head maps and the targets of the loss; replaces 34 host round trips per step by one device-side table.
  * Meter order: atom_targets {precision, precision3, recall, recall3}, atom_types_acc, atom_charges_acc, atom_hs_acc,
@@ -699,7 +727,7 @@ int abc_concat_f32(const float* const* srcs, const int32_t* counts, int32_t n, f
 /* *p += inc (one thread): the per-step dropout salt */
 int abc_counter_add_u32(uint32_t* p, uint32_t inc, abc_stream_t stream);
 
-/* sizeof(descriptor #which) in declaration order (abc_act_src = 0 ... abc_nms_desc = 12, abc_cbam_channel_desc = 13, abc_cbam_pix_desc = 14, abc_cbam_conv7_desc = 15, abc_metrics_desc = 16, abc_extract_desc = 17, abc_raster_desc = 18, abc_heads_fused_desc = 19, abc_heads_epi = 20, abc_convt_desc = 21, abc_loss_scale_desc = 22, abc_adam_seg = 23, abc_adam_class = 24, abc_adam_multi_desc = 25, abc_image_desc = 26):
+/* sizeof(descriptor #which) in declaration order (abc_act_src = 0 ... abc_nms_desc = 12, abc_cbam_channel_desc = 13, abc_cbam_pix_desc = 14, abc_cbam_conv7_desc = 15, abc_metrics_desc = 16, abc_extract_desc = 17, abc_raster_desc = 18, abc_heads_fused_desc = 19, abc_heads_epi = 20, abc_convt_desc = 21, abc_loss_scale_desc = 22, abc_adam_seg = 23, abc_adam_class = 24, abc_adam_multi_desc = 25, abc_image_desc = 26, abc_assemble_desc = 27):
  * lets a foreign-language binding check its mirror structs at load time */
 int abc_sizeof(int which);
 const char* abc_last_error(void);

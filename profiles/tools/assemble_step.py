@@ -1,0 +1,175 @@
+"""The device graph assembly (csrc/assemble.hip, ops.GraphAssembler) measured on config 5, one process: b64 @ 512 x 512, the
+frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(seed 777).
+
+  step     InferenceRunner.step() with extract=True against assemble=True (graph replay, alternating blocks, median device time)
+  launch   abc_assemble_graphs alone on the lists of that batch (device events around back-to-back launches, so launch gaps
+           count; the kernel's own time: run --parts launch under `rocprofv3 --kernel-trace --stats --`)
+  host     candidates() against molecules(): wall time of the D2H copies plus the host work, and the bytes each copies
+  graphs   the share of images whose assembled graph equals the drawn annotation: the same bonded atoms (head-map cell, element,
+           charge) and the same bonds (unordered pair of cells, order; a wedge counts as order 5 / 6).  Reported, not a test.
+
+One JSON line per measurement.
+
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+import torch  # noqa: E402
+
+import abcnet_amd  # noqa: E402,F401
+from abcnet_amd.infer import InferenceRunner  # noqa: E402
+from abcnet_amd.synthetic import drawn_molecules  # noqa: E402
+from abcnet_amd.unet import UNet  # noqa: E402
+
+HEADS = [1, 14, 3, 2, 1, 360, 60, 60]
+B, S = 64, 512
+
+
+def runners():
+    from make_trained_fixture import unpack_state
+    m = UNet(1, HEADS, dtype="bf16", dropout_p=0.2)
+    m.load_state_dict(unpack_state(os.path.join(ROOT, "tests", "golden", "trained_unet_state.npz")))
+    m = m.to("cuda").eval()
+    x, notes = drawn_molecules(B, S, seed=777)
+    out = {}
+    for name, kw in (("extract=True", dict(extract=True)), ("assemble=True", dict(assemble=True))):
+        r = InferenceRunner(m, B, S, S, use_graph=True, **kw)
+        r.load_batch(x.to("cuda"))
+        out[name] = r
+    return out, notes
+
+
+def part_step(rs, steps, warmup):
+    for r in rs.values():
+        for _ in range(warmup):
+            r.step()
+    torch.cuda.synchronize()
+    times = {k: [] for k in rs}
+    for blk in range(4):
+        for name, r in (rs.items() if blk % 2 == 0 else reversed(list(rs.items()))):
+            ev = []
+            for _ in range(steps // 4):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                r.step()
+                e1.record()
+                ev.append((e0, e1))
+            torch.cuda.synchronize()
+            times[name] += [a.elapsed_time(b) for a, b in ev]
+    med = {k: statistics.median(v) for k, v in times.items()}
+    for k, v in times.items():
+        print(json.dumps({"part": "step", "form": k, "batch": B, "size": S, "steps": len(v), "ms_per_step_median": round(med[k], 4),
+                          "ms_min": round(min(v), 4), "img_per_s": round(B * 1000.0 / med[k], 1)}), flush=True)
+    print(json.dumps({"part": "step", "assemble_minus_extract_ms": round(med["assemble=True"] - med["extract=True"], 4)}), flush=True)
+
+
+def part_launch(r, iters=200):
+    asm = r.assembler
+    for _ in range(10):
+        asm.run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        asm.run()
+    e1.record()
+    torch.cuda.synchronize()
+    cnt = r.extractor.counts.cpu()
+    print(json.dumps({"part": "launch", "batch": B, "us_per_launch": round(e0.elapsed_time(e1) * 1000 / iters, 2),
+                      "atoms_per_image_mean": round(float(cnt[:, 1].float().mean()), 1), "candidates_per_image_mean": round(float(cnt[:, 3].float().mean()), 1),
+                      "candidates_per_image_max": int(cnt[:, 3].max()),
+                      "method": "device events around %d back-to-back launches (launch gaps included)" % iters}), flush=True)
+
+
+def part_host(r, reps=20):
+    def timed(f):
+        f()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            out = f()
+        return (time.perf_counter() - t0) * 1000 / reps, out
+    t_c, lists = timed(r.candidates)
+    t_m, mols = timed(r.molecules)
+    cnt, mc = r.extractor.counts.cpu(), r.assembler.mol_counts.cpu()
+    na, nb = int(cnt[:, 1].max()), int(cnt[:, 3].max())
+    bytes_c = B * (16 + na * 20 + nb * 16 + nb * 4)
+    bytes_m = B * (16 + int(mc[:, 0].max()) * 20 + int(mc[:, 1].max()) * 16 + int(mc[:, 2].max()) * 4)
+    t0 = time.perf_counter()
+    blocks = [m.molblock() for m in mols if m is not None]
+    t_b = (time.perf_counter() - t0) * 1000
+    print(json.dumps({"part": "host", "candidates_ms": round(t_c, 3), "molecules_ms": round(t_m, 3), "candidates_d2h_bytes": bytes_c,
+                      "molecules_d2h_bytes": bytes_m, "molblock_ms_per_batch": round(t_b, 3), "molecules": len(blocks),
+                      "note": "wall time of one call per batch of %d: D2H copies + host list building, one host thread" % B}), flush=True)
+
+
+def annotated_graph(atoms_s, bonds_s):
+    atoms = {}
+    for a in atoms_s.strip(";").split(";"):
+        el, rest = a.split(":")
+        f = [int(v) for v in rest.split(",")]
+        atoms[(f[0] // 4, f[1] // 4)] = (el, f[2])
+    pts = list(atoms)
+
+    def nearest(x, y):
+        return min(pts, key=lambda p: (p[0] - x / 4) ** 2 + (p[1] - y / 4) ** 2)
+    bonds = set()
+    for b in bonds_s.strip(";").split(";") if bonds_s else []:
+        order, rest = b.split(":")
+        x, y, dx, dy, stereo, _direction = (int(v) for v in rest.split(","))
+        code = {1: 5, 6: 6}.get(stereo, int(order))
+        bonds.add((frozenset((nearest(x - dx, y - dy), nearest(x + dx, y + dy))), code))
+    shown = set().union(*[set(p) for p, _ in bonds]) if bonds else set()
+    return {(p,) + atoms[p] for p in shown}, bonds
+
+
+def part_graphs(r, notes):
+    mols = r.molecules()
+    same = atoms_same = bonds_same = 0
+    for m, (a, b) in zip(mols, notes):
+        want_a, want_b = annotated_graph(a, b)
+        if m is None:
+            continue
+        got_a = {(tuple(p), s, c) for p, s, c in zip(m.positions, m.symbols, m.charges)}
+        got_b = {(frozenset((tuple(m.positions[i - 1]), tuple(m.positions[j - 1]))), o) for (i, j), o in zip(m.bonds, m.orders)}
+        atoms_same += got_a == want_a
+        bonds_same += got_b == want_b
+        same += got_a == want_a and got_b == want_b
+    print(json.dumps({"part": "graphs", "images": len(mols), "none": sum(m is None for m in mols), "truncated": sum(bool(m and m.truncated) for m in mols),
+                      "graph_equals_annotation": same, "atoms_equal": atoms_same, "bonds_equal": bonds_same,
+                      "share": round(same / len(mols), 4)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--parts", default="step,launch,host,graphs")
+    a = ap.parse_args()
+    parts = a.parts.split(",")
+    rs, notes = runners()
+    for r in rs.values():
+        for _ in range(2):
+            r.step()
+    torch.cuda.synchronize()
+    if "step" in parts:
+        part_step(rs, a.steps, a.warmup)
+    if "launch" in parts:
+        part_launch(rs["assemble=True"])
+    if "host" in parts:
+        part_host(rs["assemble=True"])
+    if "graphs" in parts:
+        part_graphs(rs["assemble=True"], notes)
+
+
+if __name__ == "__main__":
+    main()
