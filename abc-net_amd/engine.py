@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -70,6 +71,16 @@ def convT_dgrad_taps(crop_y=True, crop_x=True):
 
 
 TAPS_CONVT_DGRAD = convT_dgrad_taps()
+
+
+class Op(NamedTuple):
+    """one launch of a plan: fn(*args, stream).  args keeps what it points to alive (byref objects hold their structure); it is a list
+    because a workspace pointer may be patched in once the plan knows its size (_finish_build)"""
+    fn: object
+    args: list
+    what: str
+    writes: tuple   # names of parameters whose GRADIENT is final once this op has run (bucketed all-reduce)
+    meta: dict      # {kernel, flops, bytes}: algorithmic work of this launch (for the roofline report)
 
 
 class Src:
@@ -209,7 +220,7 @@ class Engine:
         # step), added to drop_seed by every kernel that applies or replays the mask
         self.drop_salt = torch.zeros(1, dtype=torch.int32, device=device)
         self.head_off = head_offsets(self.heads)
-        self.keep = []  # ctypes descriptors and tensors referenced by raw pointer
+        self.keep = []  # tensors referenced by raw pointer (an op keeps its own descriptors alive: Op.args)
         self.pack_ops, self.fwd_ops, self.bwd_ops = [], [], []
         self._pack_descs = []
         self._w_layout = {}   # packed weight buffer -> abc_pack_desc.layout its consuming conv wants
@@ -287,12 +298,20 @@ class Engine:
         return t, coef
 
     # ------------------------------------------------------------------ op emitters
-    def _emit(self, ops, fn, desc, what, writes=(), meta=None):
-        """writes = names of parameters whose GRADIENT is final once this op has run (bucketed all-reduce);
-        meta = {kernel, flops, bytes}: algorithmic work of this launch (for the roofline report)"""
-        self.keep.append(desc)
-        ref = C.byref(desc)
-        ops.append((fn, ref, what, tuple(writes), meta or {"kernel": what.split(" ")[0], "flops": 0, "bytes": 0}))
+    def _emit(self, ops, fn, args, what, writes=(), meta=None):
+        """append the launch fn(*args, stream) to ops; ctypes structures among args go by reference.  Returns the op's argument list"""
+        args = [C.byref(a) if isinstance(a, C.Structure) else a for a in args]
+        ops.append(Op(fn, args, what, tuple(writes), meta or {"kernel": what.split(" ")[0], "flops": 0, "bytes": 0}))
+        return args
+
+    def _ew_meta(self, kernel, npix, Cn, passes, dt=None):
+        """meta of an element-wise launch: `passes` tensors of npix x Cn elements read or written"""
+        return {"kernel": kernel, "flops": 0, "bytes": float(npix * Cn * self._esz(self.dt if dt is None else dt) * passes)}
+
+    def _batch(self, descs, metas, kernel):
+        """descriptors collected for one batched launch -> (ctypes array of them, meta with their flops and bytes summed)"""
+        arr = (type(descs[0]) * len(descs))(*descs)
+        return arr, {"kernel": kernel, "flops": sum(m["flops"] for m in metas), "bytes": sum(m["bytes"] for m in metas)}
 
     # ---- a weight gradient's slab reduction is independent of everything until the optimiser: it waits (_pending_reduce) for the
     # next BatchNorm-backward finaliser of the plan -- a dependent ~5 us launch of C blocks -- and rides in ITS launch
@@ -302,21 +321,18 @@ class Engine:
         if pr is not None:
             self._pending_reduce = None
             pops, rd, what, writes, meta = pr
-            self._emit(pops, self.lib.abc_wgrad_reduce, rd, what, writes=writes, meta=meta)
+            self._emit(pops, self.lib.abc_wgrad_reduce, (rd,), what, writes=writes, meta=meta)
 
     def _emit_bn_bwd(self, ops, f, what, writes):
         pr = getattr(self, "_pending_reduce", None)
         if pr is None or pr[0] is not ops or not self.merge_reduce:
             self._flush_reduce(ops)
-            self._emit(ops, self.lib.abc_bn_finalize_bwd, f, what, writes=writes)
+            self._emit(ops, self.lib.abc_bn_finalize_bwd, (f,), what, writes=writes)
             return
         self._pending_reduce = None
         _pops, rd, rwhat, rwrites, rmeta = pr
-        self.keep += [rd, f]
-        lib = self.lib
         meta = {"ws": rmeta.get("ws", 0), "kernel": "wgrad_reduce+bn_bwd", "flops": 0, "bytes": rmeta["bytes"]}
-        ops.append((lambda _r, st, a=(rd, f): lib.abc_wgrad_reduce_bn_bwd(C.byref(a[0]), C.byref(a[1]), st), None,
-                    rwhat + " + " + what, tuple(rwrites) + tuple(writes), meta))
+        self._emit(ops, self.lib.abc_wgrad_reduce_bn_bwd, (rd, f), rwhat + " + " + what, tuple(rwrites) + tuple(writes), meta)
 
     def _dn(self, dt):
         return {L.BF16: "bf16", L.F32: "f32", L.FP8: "fp8"}[dt]
@@ -345,7 +361,6 @@ class Engine:
         total = red_real if red_total is None else red_total
         ck = self.lib.abc_conv_chunk(cdt, total)
         d.rows_pad, d.red_pad, d.red_total, d.red_off, d.ck = rows_pad, -(-red_real // ck) * ck, total, red_off, ck
-        self.keep.append(d)
         self._pack_descs.append(d)
 
     def packed(self, ntaps, red, rows_pad, cdt=None):
@@ -354,6 +369,15 @@ class Engine:
         if ck <= 0:
             raise ValueError("no K-chunk for %d reduction channels in %s" % (red, self._dn(cdt)))
         return self.new((ntaps * (-(-red // ck)) * rows_pad * ck,), self._tdt(cdt))
+
+    def _pack_weights(self, wname, mode, cout, cin, k):
+        """buffer + pack item of a k x k convolution's weights in the compute dtype: abc_pack_desc.mode 0 = the forward convolution (cout rows
+        over cin), 1 = its data gradient (transposed: cin rows over cout), 3 = a ConvTranspose2d's data gradient; rows padded to 32"""
+        rows, red = (cout, cin) if mode == 0 else (cin, cout)
+        rows_pad = -(-rows // 32) * 32
+        w = self.packed(k * k, red, rows_pad)
+        self.emit_pack(wname, w, mode, cout, cin, k, rows_pad, red)
+        return w
 
     def emit_conv(self, ops, src: Src, w, bias, y, y_dt, Hout, Wout, ldy, cout_off, Cout, taps, stats=None, stride=1,
                   grid=None, om=1, oy0=0, ox0=0, cin_off=None, Cin=None, what="conv", planar_out=False, stats_rows=2,
@@ -422,26 +446,19 @@ class Engine:
         if collect is not None:
             collect.append((d, what, meta))
         else:
-            self._emit(ops, self.lib.abc_conv_fwd, d, what, meta=meta)
+            self._emit(ops, self.lib.abc_conv_fwd, (d,), what, meta=meta)
         return st, nblk
 
     def emit_conv_batch(self, ops, items, what):
         """convolutions collected by emit_conv(collect=...) as ONE launch where the library serves them so (abc_conv_fwd_batch: the four
         output-parity phases of a ConvTranspose2d forward, unet.py:44, share a tile geometry of the lean kernel), else one launch each"""
-        arr = (L.ConvDesc * len(items))()
-        for i, (d, _w, _m) in enumerate(items):
-            arr[i] = d
-        if not self.lib.abc_conv_batch_ok(arr, len(items)):
+        n = len(items)
+        arr, meta = self._batch([d for d, _w, _m in items], [m for _d, _w, m in items], items[0][2]["kernel"].replace("<", "_x%d<" % n, 1))
+        if not self.lib.abc_conv_batch_ok(arr, n):
             for d, w, m in items:
-                self._emit(ops, self.lib.abc_conv_fwd, d, w, meta=m)
+                self._emit(ops, self.lib.abc_conv_fwd, (d,), w, meta=m)
             return
-        self.keep.append(arr)
-        self.keep.append([d for d, _w, _m in items])
-        lib, n = self.lib, len(items)
-        k0 = items[0][2]["kernel"]
-        meta = {"kernel": k0.replace("<", "_x%d<" % n, 1), "flops": sum(m["flops"] for _d, _w, m in items),
-                "bytes": sum(m["bytes"] for _d, _w, m in items)}
-        ops.append((lambda _r, st, a=arr: lib.abc_conv_fwd_batch(a, n, st), None, what, (), meta))
+        self._emit(ops, self.lib.abc_conv_fwd_batch, (arr, n), what, meta=meta)
 
     def emit_heads_batch(self, ops, items, which, what):
         """the heads' 1x1 convolutions collected by emit_conv(collect=...) as ONE launch (abc_heads_batch) when every one of
@@ -450,26 +467,14 @@ class Engine:
         ok = 1 <= len(items) <= 8 and all(self.lib.abc_conv_variant(C.byref(d)) == want for d, _w, _m in items) and self.batched_heads
         if not ok:
             for d, w, m in items:
-                self._emit(ops, self.lib.abc_conv_fwd, d, w, meta=m)
+                self._emit(ops, self.lib.abc_conv_fwd, (d,), w, meta=m)
             return
-        arr = (L.ConvDesc * len(items))()
-        for i, (d, _w, _m) in enumerate(items):
-            arr[i] = d
-        self.keep.append(arr)
-        self.keep.append([d for d, _w, _m in items])
-        lib, n = self.lib, len(items)
-        meta = {"kernel": "heads_%s_batch" % ("fwd" if which == 0 else "dgrad"), "flops": sum(m["flops"] for _d, _w, m in items),
-                "bytes": sum(m["bytes"] for _d, _w, m in items)}
-        ops.append((lambda _r, st, a=arr: lib.abc_heads_batch(a, n, which, st), None, what, (), meta))
+        arr, meta = self._batch([d for d, _w, _m in items], [m for _d, _w, m in items], "heads_%s_batch" % ("fwd" if which == 0 else "dgrad"))
+        self._emit(ops, self.lib.abc_heads_batch, (arr, len(items), which), what, meta=meta)
 
-    def emit_wgrad(self, ops, p: Src, q: Src, Ca, Cb, taps, stride, wname, what, cp_off=None, cq_off=None, dual=None, rowsum_to=None,
-                   collect=None, nsplit=None):
-        """dual = (y_raw tensor, ld, channel offset, dY pointer, dY pixel stride): fuse the BatchNorm-backward correction into the load of P
-        (p = act_bwd output with coef = (ca, cc, cb)); returns False without emitting anything when the library does not
-        serve this descriptor that way.
-        collect: a list -- nothing is emitted; the launch and its reductions are appended as a dict for
-        emit_wgrad_heads_batch, and the split-K slabs get their OWN buffer (the batched heads run concurrently)"""
-        dw_ptr = self.G(wname)
+    def _wgrad_desc(self, p: Src, q: Src, Ca, Cb, taps, stride, cp_off=None, cq_off=None, dual=None):
+        """the descriptor of a weight gradient and the library's geometry for it: (desc, (ca_pad, cb_pad), (a-tile, b-tile), default
+        K-split, meta without its bytes); None when `dual` (emit_wgrad) is asked for and the library does not serve the descriptor so"""
         d = L.WgradDesc()
         p.fill(d.p)
         q.fill(d.q)
@@ -485,72 +490,84 @@ class Engine:
             y2, ld2, c2, out_ptr, ld_out = dual
             d.p2, d.ld_p2, d.cp2_off, d.p_dual, d.p_out, d.ld_pout = y2.data_ptr(), ld2, c2, 1, out_ptr, ld_out
             if not self.lib.abc_wgrad_fuses_apply(C.byref(d)):
-                return False
-        ca_pad, cb_pad = L.i32(), L.i32()
+                return None
+        ca_pad, cb_pad, at_, bt_ = L.i32(), L.i32(), L.i32(), L.i32()
         L.check(self.lib.abc_wgrad_pads(C.byref(d), C.byref(ca_pad), C.byref(cb_pad)), "wgrad_pads")
-        ca_pad, cb_pad = ca_pad.value, cb_pad.value
+        L.check(self.lib.abc_wgrad_tile(C.byref(d), C.byref(at_), C.byref(bt_)), "wgrad_tile")
         per_split = self.lib.abc_wgrad_blocks(C.byref(d))
         npatch = self.B * (-(-gh // 8)) * (-(-gw // 16))
-        nsplit_arg = nsplit
         # one 8-wave workgroup per CU is resident: a single round of ~256 workgroups keeps the split-K slabs small
         nsplit = max(1, min(max(1, npatch // 2), 256 // per_split))
-        at_, bt_ = L.i32(), L.i32()
-        L.check(self.lib.abc_wgrad_tile(C.byref(d), C.byref(at_), C.byref(bt_)), "wgrad_tile")
-        if (at_.value, bt_.value) == (0, 1):   # one-channel kernel: 256-thread workgroups streaming dY, two per CU (184-200 registers
+        meta = {"kernel": "wgrad<%s,%s,%s,%dx%d,S%d>" % (self._dn(p.dt), self._dn(q.dt), self._dn(self.dt), at_.value, bt_.value, stride),
+                "flops": 2.0 * self.B * gh * gw * Ca * Cb * len(taps)}
+        return d, (ca_pad.value, cb_pad.value), (at_.value, bt_.value), nsplit, meta
+
+    def _reduce_desc(self, partial, nsplit, ntaps, Ca, Cb, ca_pad, cb_pad, dw):
+        """slab reduction: dw[Ca][Cb][ntaps] = sum over nsplit slabs of [ntaps][ca_pad][cb_pad] at `partial` (None: the shared workspace)"""
+        r = L.WgradReduceDesc()
+        r.partial, r.nsplit, r.ntaps, r.Ca, r.Cb, r.Ca_pad, r.Cb_pad, r.dw, r.accumulate = partial, nsplit, ntaps, Ca, Cb, ca_pad, cb_pad, dw, 0
+        return r
+
+    def emit_wgrad(self, ops, p: Src, q: Src, Ca, Cb, taps, stride, wname, what, cp_off=None, cq_off=None, dual=None, rowsum_to=None,
+                   collect=None, nsplit=None):
+        """dual = (y_raw tensor, ld, channel offset, dY pointer, dY pixel stride): fuse the BatchNorm-backward correction into the load of P
+        (p = act_bwd output with coef = (ca, cc, cb)); returns False without emitting anything when the library does not
+        serve this descriptor that way.
+        collect: a list -- nothing is emitted; the launch and its reductions are appended as (desc, what, meta, reductions) for
+        emit_wgrad_heads_batch, and the split-K slabs get their OWN buffer (the batched heads run concurrently)"""
+        got = self._wgrad_desc(p, q, Ca, Cb, taps, stride, cp_off, cq_off, dual)
+        if got is None:
+            return False
+        d, (ca_pad, cb_pad), tile, nsplit_default, meta = got
+        gh, gw = p.lh()
+        qh, qw = q.lh()
+        nsplit_arg, nsplit = nsplit, nsplit_default
+        if tile == (0, 1):   # one-channel kernel: 256-thread workgroups streaming dY, two per CU (184-200 registers
             # with the BatchNorm-backward apply fused): ONE round of <= 512, 12 rows per pass (768 workgroups of 8 rows ran 1.5 rounds)
             nsplit = min(-(-self.B * gh // 12), 512)
-        elif (at_.value, bt_.value) == (0, 2):   # 16-channel kernel: a wave per 8 x 16 tile run, 256-thread workgroups two to a CU (197 registers), 9 KB slabs
+        elif tile == (0, 2):   # 16-channel kernel: a wave per 8 x 16 tile run, 256-thread workgroups two to a CU (197 registers), 9 KB slabs
             nsplit = max(1, min(512, self.B * (gh // 8) * (gw // 16) // 8))
-        elif (at_.value, bt_.value) == (0, 3):   # 5x5 32-channel kernel: five-wave workgroups two to a CU, one 8 x 16 tile at a time, 100 KB slabs
+        elif tile == (0, 3):   # 5x5 32-channel kernel: five-wave workgroups two to a CU, one 8 x 16 tile at a time, 100 KB slabs
             nsplit = max(1, min(512, self.B * (gh // 8) * (gw // 16) // 4))
-        elif nsplit_arg is not None and (at_.value, bt_.value) == (0, 0):
+        elif nsplit_arg is not None and tile == (0, 0):
             nsplit = max(1, min(nsplit_arg, self.B * gh * gw // 128))   # the heads' kernel splits whole 128-pixel chunks
         d.nsplit = nsplit
         need = nsplit * len(taps) * ca_pad * cb_pad
         self._ws_need = max(self._ws_need, need)
         # (one workspace for the split-K slabs: a layer's reduction runs before the next layer's weight gradient, in stream order)
         wsk = 0
-        r = L.WgradReduceDesc()
-        r.nsplit, r.ntaps, r.Ca, r.Cb, r.Ca_pad, r.Cb_pad, r.dw, r.accumulate = nsplit, len(taps), Ca, Cb, ca_pad, cb_pad, dw_ptr, 0
+        r = self._reduce_desc(None, nsplit, len(taps), Ca, Cb, ca_pad, cb_pad, self.G(wname))
         if collect is not None:
             own = self.new((need,), torch.float32)
             d.partial = r.partial = own.data_ptr()
         else:
             self._ws_users += [(d, wsk), (r, wsk)]
-        meta = {"ws": wsk, "kernel": "wgrad<%s,%s,%s,%dx%d,S%d>" % (self._dn(p.dt), self._dn(q.dt), self._dn(self.dt), at_.value, bt_.value, stride),
-                "flops": 2.0 * self.B * gh * gw * Ca * Cb * len(taps),
-                # both operands once, the split-K slabs this launch writes, and (DUAL) the y_raw it reads + the dY it writes
-                "bytes": float(self.B * gh * gw * Ca * self._esz(p.dt) + self.B * qh * qw * (4 if q.pool else 1) * Cb * self._esz(q.dt)
-                               + need * 4 + (2 * self.B * gh * gw * Ca * self._esz(self.dt) if dual is not None else 0)),
-                # the OPERANDS alone: dY + X read once, dW written once (what a weight gradient has to move whatever its algorithm)
-                "operand_bytes": float(self.B * gh * gw * Ca * self._esz(p.dt) + self.B * qh * qw * (4 if q.pool else 1) * Cb * self._esz(q.dt)
-                                       + Ca * Cb * len(taps) * 4)}
-        post = []
+        operands = self.B * gh * gw * Ca * self._esz(p.dt) + self.B * qh * qw * (4 if q.pool else 1) * Cb * self._esz(q.dt)
+        meta["ws"] = wsk
+        # both operands once, the split-K slabs this launch writes, and (DUAL) the y_raw it reads + the dY it writes
+        meta["bytes"] = float(operands + need * 4 + (2 * self.B * gh * gw * Ca * self._esz(self.dt) if dual is not None else 0))
+        # the OPERANDS alone: dY + X read once, dW written once (what a weight gradient has to move whatever its algorithm)
+        meta["operand_bytes"] = float(operands + Ca * Cb * len(taps) * 4)
         if collect is None:
             self._flush_reduce(ops)      # (the previous layer's slabs sit in the workspace this launch overwrites)
-            self._emit(ops, self.lib.abc_wgrad, d, what, meta=meta)
-        fused_rowsum = False
-        if rowsum_to is not None and self.lib.abc_wgrad_rowsum_ok(C.byref(d)):
+            self._emit(ops, self.lib.abc_wgrad, (d,), what, meta=meta)
+        post = [(r, what + " reduce", (wname,) if wname else (),
+                 {"ws": wsk, "kernel": "wgrad_reduce", "flops": 0, "bytes": float(need * 4 + Ca * Cb * len(taps) * 4)})]
+        fused_rowsum = rowsum_to is not None and bool(self.lib.abc_wgrad_rowsum_ok(C.byref(d)))
+        if fused_rowsum:
             # the heads' kernel also leaves per-split row sums of P = the conv's bias gradient (no separate pass over dL)
             rs = self.new((nsplit, ca_pad), torch.float32)
             d.rowsum_partial = rs.data_ptr()
-            r2 = L.WgradReduceDesc()
-            r2.partial, r2.nsplit, r2.ntaps, r2.Ca, r2.Cb, r2.Ca_pad, r2.Cb_pad, r2.dw, r2.accumulate = rs.data_ptr(), nsplit, 1, Ca, 1, ca_pad, 1, self.G(rowsum_to), 0
-            fused_rowsum = True
-        post.append((r, what + " reduce", (wname,) if wname else (),
-                     {"ws": wsk, "kernel": "wgrad_reduce", "flops": 0, "bytes": float(need * 4 + Ca * Cb * len(taps) * 4)}))
-        if fused_rowsum:
-            post.append((r2, "dbias " + what[6:] + " reduce", (rowsum_to,),
-                         {"kernel": "wgrad_reduce", "flops": 0, "bytes": float(nsplit * ca_pad * 4)}))
+            post.append((self._reduce_desc(rs.data_ptr(), nsplit, 1, Ca, 1, ca_pad, 1, self.G(rowsum_to)), "dbias " + what[6:] + " reduce",
+                         (rowsum_to,), {"kernel": "wgrad_reduce", "flops": 0, "bytes": float(nsplit * ca_pad * 4)}))
         if collect is not None:
-            collect.append({"d": d, "what": what, "meta": meta, "post": post})
+            collect.append((d, what, meta, post))
         else:
             for k, (rd, w, wr, m) in enumerate(post):
                 if k == 0 and self.merge_reduce and self.train:
-                    self.keep.append(rd)
                     self._pending_reduce = (ops, rd, w, wr, m)
                 else:
-                    self._emit(ops, self.lib.abc_wgrad_reduce, rd, w, writes=wr, meta=m)
+                    self._emit(ops, self.lib.abc_wgrad_reduce, (rd,), w, writes=wr, meta=m)
         return "rowsum" if fused_rowsum else True
 
     def emit_wgrad_heads_batch(self, ops, items, what):
@@ -560,81 +577,57 @@ class Engine:
             at_, bt_ = L.i32(), L.i32()
             L.check(self.lib.abc_wgrad_tile(C.byref(d), C.byref(at_), C.byref(bt_)), "wgrad_tile")
             return at_.value, bt_.value
-        ok = 1 <= len(items) <= 8 and all(tile(it["d"]) == (0, 0) for it in items) and self.batched_heads
+        ok = 1 <= len(items) <= 8 and all(tile(d) == (0, 0) for d, _w, _m, _p in items) and self.batched_heads
         if ok:
-            arr = (L.WgradDesc * len(items))()
-            for i, it in enumerate(items):
-                arr[i] = it["d"]
-            self.keep.append(arr)
-            lib, n = self.lib, len(items)
-            meta = {"kernel": "heads_wgrad_batch", "flops": sum(it["meta"]["flops"] for it in items), "bytes": sum(it["meta"]["bytes"] for it in items)}
-            ops.append((lambda _r, st, a=arr: lib.abc_wgrad_heads_batch(a, n, st), None, what, (), meta))
+            arr, meta = self._batch([d for d, _w, _m, _p in items], [m for _d, _w, m, _p in items], "heads_wgrad_batch")
+            self._emit(ops, self.lib.abc_wgrad_heads_batch, (arr, len(items)), what, meta=meta)
         else:
-            for it in items:
-                self._emit(ops, self.lib.abc_wgrad, it["d"], it["what"], meta=it["meta"])
-        posts = [p for it in items for p in it["post"]]
-        self.keep.append([it["d"] for it in items])
+            for d, w, m, _p in items:
+                self._emit(ops, self.lib.abc_wgrad, (d,), w, meta=m)
+        posts = [p for _d, _w, _m, post in items for p in post]
         if ok and len(posts) <= 16:
             # the 8 weight-gradient and 8 bias row-sum reductions as one launch too
-            rarr = (L.WgradReduceDesc * len(posts))()
-            for i, (rd, _w, _wr, _m) in enumerate(posts):
-                rarr[i] = rd
-            self.keep.append(rarr)
-            self.keep.append([rd for rd, _w, _wr, _m in posts])
-            lib, nr = self.lib, len(posts)
-            writes = tuple(w for _rd, _w, wr, _m in posts for w in wr)
-            ops.append((lambda _r, st, a=rarr: lib.abc_wgrad_reduce_batch(a, nr, st), None, what + " reduce", writes,
-                        {"kernel": "wgrad_reduce_batch", "flops": 0, "bytes": sum(m["bytes"] for _rd, _w, _wr, m in posts)}))
+            rarr, meta = self._batch([rd for rd, _w, _wr, _m in posts], [m for _rd, _w, _wr, m in posts], "wgrad_reduce_batch")
+            self._emit(ops, self.lib.abc_wgrad_reduce_batch, (rarr, len(posts)), what + " reduce",
+                       tuple(w for _rd, _w, wr, _m in posts for w in wr), meta)
         else:
             for rd, w, wr, m in posts:
-                self._emit(ops, self.lib.abc_wgrad_reduce, rd, w, writes=wr, meta=m)
+                self._emit(ops, self.lib.abc_wgrad_reduce, (rd,), w, writes=wr, meta=m)
 
     def emit_colsum(self, ops, t, dt, npix, ld, c_off, Cn, chan_scale, bname, what):
-        out_ptr = self.G(bname)
         nb = self.lib.abc_colsum_blocks(npix)
         self._colsum_need = max(self._colsum_need, nb * Cn)
-        args = [t.data_ptr(), dt, npix, ld, c_off, Cn, None if chan_scale is None else chan_scale.data_ptr(), None, out_ptr]
-        self._colsum_users.append(args)
-        lib = self.lib
-
-        def fn(_ref, stream, a=args):
-            return lib.abc_colsum(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], stream)
-
-        ops.append((fn, None, what, (bname,), {"kernel": "colsum", "flops": 0, "bytes": float(npix * Cn * self._esz(dt))}))
+        # (argument 7 is the workspace: _finish_build patches it in)
+        self._colsum_users.append(self._emit(
+            ops, self.lib.abc_colsum, (t.data_ptr(), dt, npix, ld, c_off, Cn, None if chan_scale is None else chan_scale.data_ptr(), None, self.G(bname)),
+            what, (bname,), self._ew_meta("colsum", npix, Cn, 1, dt)))
 
     def emit_colsum_w1(self, ops, t, dt, npix, ld, c_off, Cn, img, bname, wname, what):
         """bias AND weight gradient of a 1x1 convolution over a one-channel f32 image in one pass over d(out) (abc_colsum_w1):
         unet2's first res_conv (unet2.py:62,135)"""
         nb = self.lib.abc_colsum_blocks(npix)
         self._colsum_need = max(self._colsum_need, 2 * nb * Cn)
-        args = [t.data_ptr(), dt, npix, ld, c_off, Cn, img.data_ptr(), None, self.G(bname), self.G(wname)]
-        self._colsum_users.append(args)
-        lib = self.lib
-
-        def fn(_ref, stream, a=args):
-            return lib.abc_colsum_w1(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], stream)
-
-        ops.append((fn, None, what, (bname, wname), {"kernel": "colsum_w1", "flops": 0, "bytes": float(npix * (Cn * self._esz(dt) + 4))}))
+        self._colsum_users.append(self._emit(
+            ops, self.lib.abc_colsum_w1, (t.data_ptr(), dt, npix, ld, c_off, Cn, img.data_ptr(), None, self.G(bname), self.G(wname)),
+            what, (bname, wname), {"kernel": "colsum_w1", "flops": 0, "bytes": float(npix * (Cn * self._esz(dt) + 4))}))
 
     # ------------------------------------------------------------------ layers
     def conv_bn(self, cname, bname, src: Src, cout, k, dst, slope, recname=None, stats_rows=2, force_stats=False, stat_out=None,
                 collect_fin=None, shared=None):
         """conv (+bias) -> raw output into dst=(tensor, coef, H, W, ld, coff); BN stats/coefficients.
         stat_out = (mean, invstd) tensors to use instead of fresh ones (slices of a shared array: the heads);
-        collect_fin: a list -- the train-mode finalisation is appended as (desc, what) instead of being emitted;
+        collect_fin: a list -- the train-mode finalisation's descriptor is appended instead of being emitted;
         shared = (stats, nblk): the convolution itself was emitted by the caller as part of a wider one whose statistics
         partials are [nblk][rows][ld] -- this layer's columns start at coff"""
         yt, coef, H, W, ld, coff = dst
         cin = src.C
         taps = taps_square(k)
-        rows_pad = -(-cout // 32) * 32
         if self.fold:
             return self._conv_bn_folded(cname, bname, src, cout, k, dst, slope, shared)
         if shared is not None:
             stats, nblk = shared
         else:
-            wf = self.packed(len(taps), cin, rows_pad)
-            self.emit_pack(cname + ".weight", wf, 0, cout, cin, k, rows_pad, cin)
+            wf = self._pack_weights(cname + ".weight", 0, cout, cin, k)
             stats, nblk = self.emit_conv(self.fwd_ops, src, wf, self.P(cname + ".bias"), yt, self.dt, H, W, ld, coff, cout, taps,
                                          stats=self.train or force_stats, what="fwd " + cname, stats_rows=stats_rows)
         rec = Rec(kind="conv", cname=cname, bname=bname, src=src, cin=cin, cout=cout, k=k, taps=taps, y=yt, H=H, W=W, ld=ld,
@@ -655,17 +648,15 @@ class Engine:
             d.num_batches_tracked = self.Cn(bname + ".num_batches_tracked")
             d.eps, d.momentum = BN_EPS, BN_MOM
             if collect_fin is not None:
-                self.keep.append(d)
-                collect_fin.append((d, "bn " + bname))
+                collect_fin.append(d)
             else:
-                self._emit(self.fwd_ops, self.lib.abc_bn_finalize_fwd, d, "bn " + bname)
+                self._emit(self.fwd_ops, self.lib.abc_bn_finalize_fwd, (d,), "bn " + bname)
         else:
-            lib = self.lib
             a = (self.P(bname + ".weight"), self.P(bname + ".bias"), self.Bf(bname + ".running_mean"),
                  self.Bf(bname + ".running_var"), rec.scale.data_ptr(), rec.shift.data_ptr(), cout, BN_EPS)
             # eval-mode coefficients are functions of the parameters alone: they are refreshed with the weight packing
             # (every call on the module path, once per weight load in InferenceRunner), not inside the forward plan
-            self.pack_ops.append((lambda _r, st, a=a: lib.abc_bn_eval_coeffs(*a, st), None, "bn-eval " + bname, (), {"kernel": "bn_eval", "flops": 0, "bytes": 0}))
+            self._emit(self.pack_ops, self.lib.abc_bn_eval_coeffs, a, "bn-eval " + bname, meta={"kernel": "bn_eval", "flops": 0, "bytes": 0})
         rec.stats, rec.nblk = stats, nblk
         self.recs.append(rec)
         out = Src(yt, self.dt, H, W, ld, coff, cout, coef=coef, producer=rec)
@@ -673,11 +664,9 @@ class Engine:
 
     def _fold_coeffs(self, cname, bname, cout, scale_t, bias_t):
         """pack-time op: scale_t = gamma / sqrt(running_var + eps), bias_t = (conv bias - running_mean) * scale_t + beta"""
-        lib = self.lib
         a = (self.P(bname + ".weight"), self.P(bname + ".bias"), self.Bf(bname + ".running_mean"), self.Bf(bname + ".running_var"),
              self.P(cname + ".bias"), scale_t.data_ptr(), bias_t.data_ptr(), cout, BN_EPS)
-        self.pack_ops.append((lambda _r, st, a=a: lib.abc_bn_eval_fold(*a, st), None, "bn-fold " + bname, (),
-                              {"kernel": "bn_fold", "flops": 0, "bytes": 0}))
+        self._emit(self.pack_ops, self.lib.abc_bn_eval_fold, a, "bn-fold " + bname, meta={"kernel": "bn_fold", "flops": 0, "bytes": 0})
 
     def _conv_bn_folded(self, cname, bname, src, cout, k, dst, slope, shared):
         """eval-mode conv + BatchNorm + activation as ONE convolution (see __init__): returns (rec, Src with no transform)"""
@@ -720,11 +709,8 @@ class Engine:
     def _fp8_weight_scales(self, wname, rows, K, fold, s_in, qmul, deq):
         """pack-time op (before the weight packing): per output row the e4m3 scale of the BatchNorm-folded weight --
         qmul = fold / s_w (what the packing multiplies the master weight with), deq = s_w * s_in (the convolution's out_scale)"""
-        lib = self.lib
         a = (self.P(wname), rows, K, None if fold is None else fold.data_ptr(), s_in.data_ptr(), qmul.data_ptr(), deq.data_ptr())
-        self.keep += [fold, s_in, qmul, deq]
-        self.pack_ops.append((lambda _r, st, a=a: lib.abc_fp8_weight_scales(*a, st), None, "fp8 scales " + wname, (),
-                              {"kernel": "fp8_weight_scales", "flops": 0, "bytes": 0}))
+        self._emit(self.pack_ops, self.lib.abc_fp8_weight_scales, a, "fp8 scales " + wname, meta={"kernel": "fp8_weight_scales", "flops": 0, "bytes": 0})
         return qmul, deq
 
     def calibrate_fp8(self, ref, stream, margin=1.0):
@@ -805,10 +791,8 @@ class Engine:
             return r
         a = L.ActSrc()
         s.fill(a)
-        lib = self.lib
-        args = (a, s.dt, s.coff, s.C, self.B, out.data_ptr(), self.dt, s.C)
-        self.fwd_ops.append((lambda _r, st, g=args: lib.abc_pool_act(C.byref(g[0]), *g[1:], st), None, "pool", (),
-                             {"kernel": "pool_act", "flops": 0, "bytes": float(self.B * s.H * s.W * s.C * self._esz(s.dt) * 1.25)}))
+        self._emit(self.fwd_ops, self.lib.abc_pool_act, (a, s.dt, s.coff, s.C, self.B, out.data_ptr(), self.dt, s.C), "pool",
+                   meta=self._ew_meta("pool_act", self.B * s.H * s.W, s.C, 1.25, s.dt))
         r = Src(out, self.dt, Ho, Wo, s.C, 0, s.C, coef=None, pool=False, producer=s.producer)
         r.via_pool = True
         return r
@@ -859,27 +843,24 @@ class Engine:
                                grid=(gh, gw), om=2, oy0=py, ox0=px, what="fwd %s.up phase %d%d" % (name, py, px), collect=items)
                 phases.append(wp)
         if fused is not None:
-            self.keep.append(fused)
-            lib = self.lib
             meta = {"kernel": "convt_fused<bf16>", "flops": 2.0 * self.B * lh * lw * cin * half * 9,
                     "bytes": float(self.B * lh * lw * cin * 2 + self.B * Hs * Ws * half * 2)}
-            self.fwd_ops.append((lambda _r, st, d=fused: lib.abc_convt_fused_fwd(C.byref(d), st), None, "fwd %s.up (4 phases, one pass)" % name, (), meta))
+            self._emit(self.fwd_ops, self.lib.abc_convt_fused_fwd, (fused,), "fwd %s.up (4 phases, one pass)" % name, meta=meta)
         else:
             self.emit_conv_batch(self.fwd_ops, items, "fwd %s.up (4 phases)" % name)
         rec = Rec(kind="convT", cname=name + ".up", src=low, cin=cin, cout=half, H=Hs, W=Ws, ld=Ctot, coff=half, y=cat,
                   taps_bwd=convT_dgrad_taps(crop_y, crop_x))
         self.recs.append(rec)
         cat_src = Src(cat, self.dt, Hs, Ws, Ctot, 0, Ctot, coef=None if self.fold else cat_coef, producer=("cat", None))
+        # who receives the two halves of d(cat) (_route): the skip half belongs to whoever wrote channels [0:half) of the cat buffer -- in
+        # unet the conv that did, in unet2 the block the caller names
+        if skip_producer is None:
+            skip_producer = [r for r in self.recs if r.kind == "conv" and r.y is cat and r.coff == 0][0]
+        cat_src.cat = (skip_producer, rec)
         if self.variant == "unet2":
-            cat_src.cat = (skip_producer, rec)
             self.units2.append(("convT", rec))
-            out = self.block2(name + ".conv", cat_src, cout, 3)
-            return out, rec
-        out = self.double_conv(name + ".conv", cat_src, cout, 3)
-        # remember who receives the two halves of d(cat)
-        first = [r for r in self.recs if r.kind == "conv" and r.cname == name + ".conv.double_conv.0"][0]
-        first.cat_upper = rec
-        return out, rec
+            return self.block2(name + ".conv", cat_src, cout, 3), rec
+        return self.double_conv(name + ".conv", cat_src, cout, 3), rec
 
     # ------------------------------------------------------------------ build
     def _image_src(self):
@@ -899,9 +880,8 @@ class Engine:
         S = [(H >> i, W >> i) for i in range(6)]
         img_src = self._image_src()
         if self.drop_p > 0:
-            lib, sp = self.lib, self.drop_salt.data_ptr()
-            self.fwd_ops.append((lambda _r, st: lib.abc_counter_add_u32(sp, DROP_STEP, st), None, "dropout step", (),
-                                 {"kernel": "counter_add", "flops": 0, "bytes": 0}))
+            self._emit(self.fwd_ops, self.lib.abc_counter_add_u32, (self.drop_salt.data_ptr(), DROP_STEP), "dropout step",
+                       meta={"kernel": "counter_add", "flops": 0, "bytes": 0})
         x = None
         if self.fold and self.dt == L.BF16 and self.in_channels == 1:
             x = self._stem_fused_double_conv("inc1", img_src, 16)
@@ -945,9 +925,8 @@ class Engine:
             elems += ntaps * pd.red_pad * pd.rows_pad
         table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.dev)
         self.keep.append(table)
-        a = (table.data_ptr(), len(self._pack_descs), first)
-        self.pack_ops.append((lambda _r, st, a=a: lib.abc_pack_batch(a[0], a[1], a[2], st), None, "pack weights", (),
-                              {"kernel": "pack_batch", "flops": 0, "bytes": float(elems * (2 if self.dt == L.BF16 else 4) + elems * 4)}))
+        self._emit(self.pack_ops, lib.abc_pack_batch, (table.data_ptr(), len(self._pack_descs), first), "pack weights",
+                   meta={"kernel": "pack_batch", "flops": 0, "bytes": float(elems * (2 if self.dt == L.BF16 else 4) + elems * 4)})
         # shared workspaces
         self.ws = [self.new((max(self._ws_need, 4),), torch.float32)]
         for d, k in self._ws_users:
@@ -1015,8 +994,7 @@ class Engine:
                                        [(0, 0)], what="fwd %s.conv2" % p, planar_out=True, collect=head_convs, cdt=L.FP8, out_scale=deq)
                     self.head2.append(Rec(kind="head2", cname=p + ".conv2", src=f, cout=hc, idx=i))
                     continue
-                w2 = self.packed(1, 128, rows_pad)
-                self.emit_pack(p + ".conv2.weight", w2, 0, hc, 128, 1, rows_pad, 128)
+                w2 = self._pack_weights(p + ".conv2.weight", 0, hc, 128, 1)
                 if self.hepi is not None:
                     epi_items.append((w2, self.P(p + ".conv2.bias"), None, self.logits[i], hc, rows_pad))
                 else:
@@ -1024,14 +1002,9 @@ class Engine:
                                    [(0, 0)], what="fwd %s.conv2" % p, planar_out=True, collect=head_convs)
             self.head2.append(Rec(kind="head2", cname=p + ".conv2", src=f, cout=hc, idx=i))
         if head_fins:
-            arr = (L.BnFwdDesc * len(head_fins))()
-            for i, (d, _w) in enumerate(head_fins):
-                arr[i] = d
-            self.keep.append(arr)
-            lib, n = self.lib, len(head_fins)
-            pstride = 128 * nh if shared is not None else 0
-            self.fwd_ops.append((lambda _r, st, a=arr: lib.abc_bn_finalize_fwd_batch(a, n, pstride, st), None, "bn out_modules.*.bn", (),
-                                 {"kernel": "bn", "flops": 0, "bytes": 0}))
+            arr = (L.BnFwdDesc * len(head_fins))(*head_fins)
+            self._emit(self.fwd_ops, self.lib.abc_bn_finalize_fwd_batch, (arr, len(head_fins), 128 * nh if shared is not None else 0),
+                       "bn out_modules.*.bn", meta={"kernel": "bn", "flops": 0, "bytes": 0})
         if fused:
             self._heads_fused_setup()
             return
@@ -1110,8 +1083,7 @@ class Engine:
             d.w2[i], d.b2[i], d.logits[i] = self.P(p + ".weight"), self.P(p + ".bias"), self.logits[i].data_ptr()
             d.dw2[i], d.db2[i], d.chan_off[i] = self.G(p + ".weight"), self.G(p + ".bias"), self.head_off[i]
         self.hf, self.hf_chunks = d, nchunk
-        self.pack_ops.append((lambda _r, st: lib.abc_heads_fused_pack(C.byref(d), st), None, "pack out_modules.*.conv2", (),
-                              {"kernel": "heads_fused_pack", "flops": 0, "bytes": 0}))
+        self._emit(self.pack_ops, lib.abc_heads_fused_pack, (d,), "pack out_modules.*.conv2", meta={"kernel": "heads_fused_pack", "flops": 0, "bytes": 0})
 
     def _heads_conv1_merged(self, trunk: Src, h, w):
         """pack the eight conv1 weights one below the other ([tap][chunk][8 x 128][CK]), gather their biases, emit the one
@@ -1147,34 +1119,25 @@ class Engine:
             self.emit_pack("out_modules.%d.conv1.weight" % i, wf, 0, 128, 128, 3, 128, 128, rows_total=Ct, rows_off=128 * i)
         srcs = (C.c_void_p * nh)(*[self.P("out_modules.%d.conv1.bias" % i) for i in range(nh)])
         counts = (C.c_int32 * nh)(*([128] * nh))
-        self.keep += [srcs, counts]
-        lib, bp = self.lib, bias_all.data_ptr()
-        self.pack_ops.append((lambda _r, st: lib.abc_concat_f32(srcs, counts, nh, bp, st), None, "gather out_modules.*.conv1.bias", (),
-                              {"kernel": "concat", "flops": 0, "bytes": 0}))
+        bp = bias_all.data_ptr()
+        self._emit(self.pack_ops, self.lib.abc_concat_f32, (srcs, counts, nh, bp), "gather out_modules.*.conv1.bias",
+                   meta={"kernel": "concat", "flops": 0, "bytes": 0})
         return self.emit_conv(self.fwd_ops, trunk, wf, bp, self.hfeat, self.dt, h, w, Ct, 0, Ct, taps, stats=self.train,
                               what="fwd out_modules.*.conv1")
 
     # ------------------------------------------------------------------ backward plan
-    def _bn_backward(self, ops, rec, same, pool, drop=None, defer=False):
-        """act_bwd + bn finalize + apply for rec; returns Src of dY (plain).
-        defer=True: the apply pass is NOT emitted; returns (Src of g with coef = (ca, cc, cb) for a consumer that applies
-        dY = ca*g + cb*y_raw + cc on load, emit_apply) where emit_apply() emits the classic in-place pass and returns
-        the plain Src -- the caller picks one"""
-        fg = getattr(rec, "fused_g", None)
-        if fg is not None:
-            # the data gradient that produced d(activation output) already stored g and the partial sums (emit_conv(actbwd=rec))
-            assert pool is None and drop is None
-            return self._bn_finish(ops, rec, fg[1], fg[2], fg[0], defer=defer, keep_g=True)
+    def _act_bwd(self, ops, rec, same, pool, g_ptr, ld_g, drop=None):
+        """emit the activation backward of rec: g = d(BatchNorm output) at g_ptr (pixel stride ld_g) from the gradients wrt the activated
+        output (same = full resolution, pool = pooled: (tensor, ld, channel offset)) + the BatchNorm-backward partial sums;
+        drop = (p, seed): behind a dropout.  Returns (partials, nblk)"""
         C_ = rec.cout
-        g = self.new((self.B, rec.H, rec.W, C_))
-        rec.g = g      # (handle for the in-situ parity tests)
         d = L.ActBwdDesc()
         d.y_raw, d.ld_y = rec.y.data_ptr(), rec.ld
         if same is not None:
             d.dA_same, d.ld_same, d.csame_off = same[0].data_ptr(), same[1], same[2]
         if pool is not None:
             d.dA_pool, d.ld_pool, d.cpool_off = pool[0].data_ptr(), pool[1], pool[2]
-        d.g, d.ld_g = g.data_ptr(), C_
+        d.g, d.ld_g = g_ptr, ld_g
         d.scale, d.shift, d.slope = rec.scale.data_ptr(), rec.shift.data_ptr(), rec.slopes.data_ptr()
         d.mean, d.invstd = rec.mean.data_ptr(), rec.invstd.data_ptr()
         d.dtype, d.B, d.H, d.W, d.C, d.cy_off = self.dt, self.B, rec.H, rec.W, C_, rec.coff
@@ -1184,33 +1147,70 @@ class Engine:
         part = self.new((nblk, 2, C_), torch.float32)
         d.partial = part.data_ptr()
         nsrc = (1 if d.dA_same else 0) + (0.25 if d.dA_pool else 0)
-        self._emit(ops, self.lib.abc_act_bwd, d, "act_bwd " + rec.bname,
-                   meta={"kernel": "act_bwd", "flops": 0, "bytes": float(self.B * rec.H * rec.W * C_ * self._esz(self.dt) * (2 + nsrc))})
-        k1, k2, gs = (self.new((C_,), torch.float32) for _ in range(3))
+        self._emit(ops, self.lib.abc_act_bwd, (d,), "act_bwd " + rec.bname, meta=self._ew_meta("act_bwd", self.B * rec.H * rec.W, C_, 2 + nsrc))
+        return part, nblk
+
+    def _bn_bwd_desc(self, rec, part_ptr, nblk, coefs=None, in_scale=None):
+        """the BatchNorm-backward finaliser of rec over the nblk partial rows at part_ptr: (descriptor, (k1, k2, gscale) for the apply
+        pass, the parameters whose gradients it writes).  coefs = (ca, cb, cc) tensors: it also leaves the coefficients of the deferred
+        apply dY = ca * g + cb * y_raw + cc; in_scale: per-channel factor on the partial sums (the fused heads pass's loss weights)"""
+        C_ = rec.cout
+        k = tuple(self.new((C_,), torch.float32) for _ in range(3))
         f = L.BnBwdDesc()
-        f.partial, f.nblk, f.C, f.count = part.data_ptr(), nblk, C_, float(self.B * rec.H * rec.W)
+        f.partial, f.nblk, f.C, f.count = part_ptr, nblk, C_, float(self.B * rec.H * rec.W)
         f.gamma, f.invstd = self.P(rec.bname + ".weight"), rec.invstd.data_ptr()
         f.dgamma, f.dbeta = self.G(rec.bname + ".weight"), self.G(rec.bname + ".bias")
-        f.k1, f.k2, f.gscale = k1.data_ptr(), k2.data_ptr(), gs.data_ptr()
-        if defer:
-            ca, cb, cc = (self.new((C_,), torch.float32) for _ in range(3))
-            f.mean, f.ca, f.cb, f.cc = rec.mean.data_ptr(), ca.data_ptr(), cb.data_ptr(), cc.data_ptr()
-        self._emit_bn_bwd(ops, f, "bn_bwd " + rec.bname, (rec.bname + ".weight", rec.bname + ".bias"))
+        f.k1, f.k2, f.gscale = (t.data_ptr() for t in k)
+        if coefs is not None:
+            f.mean = rec.mean.data_ptr()
+            f.ca, f.cb, f.cc = (t.data_ptr() for t in coefs)
+        f.in_scale = in_scale
+        return f, k, (rec.bname + ".weight", rec.bname + ".bias")
+
+    def _bn_backward(self, ops, rec, same=None, pool=None, drop=None, defer=False, g=None, partials=None, in_place=False):
+        """act_bwd + bn finalize + apply for rec; returns Src of dY (plain).
+        g = (tensor, ld, channel offset): where g lives -- a channel slice of a shared buffer (the heads), or a tensor written elsewhere;
+        default a fresh buffer, kept as rec.g;
+        partials = (partial sums, nblk): g and the partial sums were produced elsewhere (CBAM bwd3; a data gradient with the act_bwd pass
+        in its epilogue, rec.fused_g) -- no act_bwd pass;
+        in_place: the apply pass overwrites g; default a buffer of its own (g stays intact for the in-situ parity tests);
+        defer=True: the apply pass is NOT emitted; returns (Src of g with coef = (ca, cc, cb) for a consumer that applies
+        dY = ca*g + cb*y_raw + cc on load, emit_apply) where emit_apply() emits the classic pass and returns the plain Src -- the
+        caller picks one"""
+        C_ = rec.cout
+        fg = getattr(rec, "fused_g", None)
+        if fg is not None:
+            # the data gradient that produced d(activation output) already stored g and the partial sums (emit_conv(actbwd=rec))
+            assert pool is None and drop is None
+            g, partials = (fg[0], C_, 0), fg[1:]
+        if g is None:
+            g = (self.new((self.B, rec.H, rec.W, C_)), C_, 0)
+            rec.g = g[0]      # (handle for the in-situ parity tests)
+        gt, ld_g, g_off = g
+        g_ptr = gt.data_ptr() + g_off * gt.element_size()
+        part, nblk = partials or self._act_bwd(ops, rec, same, pool, g_ptr, ld_g, drop)
+        coefs = tuple(self.new((C_,), torch.float32) for _ in range(3)) if defer else None
+        f, (k1, k2, gs), writes = self._bn_bwd_desc(rec, part.data_ptr(), nblk, coefs)
+        self._emit_bn_bwd(ops, f, "bn_bwd " + rec.bname, writes)
         a = L.BnApplyDesc()
-        a.g, a.ld_g, a.y_raw, a.ld_y, a.cy_off = g.data_ptr(), C_, rec.y.data_ptr(), rec.ld, rec.coff
+        a.g, a.ld_g, a.y_raw, a.ld_y, a.cy_off = g_ptr, ld_g, rec.y.data_ptr(), rec.ld, rec.coff
         a.mean, a.invstd, a.k1, a.k2, a.gscale = rec.mean.data_ptr(), rec.invstd.data_ptr(), k1.data_ptr(), k2.data_ptr(), gs.data_ptr()
         a.dtype, a.C, a.npix = self.dt, C_, self.B * rec.H * rec.W
 
         def emit_apply():
-            dy = self.new((self.B, rec.H, rec.W, C_))      # (g is kept: the in-situ parity tests read it)
-            a.out, a.ld_out = dy.data_ptr(), C_
-            self._emit(ops, self.lib.abc_bn_apply_bwd, a, "bn_apply " + rec.bname,
-                       meta={"kernel": "bn_apply", "flops": 0, "bytes": float(self.B * rec.H * rec.W * C_ * self._esz(self.dt) * 3)})
-            rec.dY = dy
-            return Src(dy, self.dt, rec.H, rec.W, C_, 0, C_)
+            out = g
+            if not in_place:
+                out = (self.new((self.B, rec.H, rec.W, C_)), C_, 0)
+                a.out, a.ld_out = out[0].data_ptr(), C_
+            self._emit(ops, self.lib.abc_bn_apply_bwd, (a,), "bn_apply " + rec.bname, meta=self._ew_meta("bn_apply", self.B * rec.H * rec.W, C_, 3))
+            if out[1] == C_:      # (handle for the in-situ parity tests: not for a slice of a wider shared buffer)
+                rec.dY = out[0]
+            return Src(out[0], self.dt, rec.H, rec.W, out[1], out[2], C_)
 
         if defer:
-            return Src(g, self.dt, rec.H, rec.W, C_, 0, C_, coef=(ca, cc, cb)), emit_apply
+            assert g_off == 0      # (the deferred coefficients are indexed by the absolute channel of g)
+            ca, cb, cc = coefs
+            return Src(gt, self.dt, rec.H, rec.W, ld_g, 0, C_, coef=(ca, cc, cb)), emit_apply
         return emit_apply()
 
     def _conv_backward(self, ops, rec, dY, want_dgrad=True, into=None):
@@ -1238,9 +1238,7 @@ class Engine:
         if not want_dgrad or prod is None:
             return None
         lh, lw = rec.src.lh()
-        rows_pad = -(-rec.cin // 32) * 32
-        wd = self.packed(len(rec.taps), rec.cout, rows_pad)
-        self.emit_pack(rec.cname + ".weight", wd, 1, rec.cout, rec.cin, rec.k, rows_pad, rec.cout)
+        wd = self._pack_weights(rec.cname + ".weight", 1, rec.cout, rec.cin, rec.k)
         rec.dsrc_accumulated = False
         if into is not None and self.dt == L.BF16 and tuple(into.shape) == (self.B, lh, lw, rec.cin):
             got = self.emit_conv(ops, dY, wd, None, into, self.dt, lh, lw, rec.cin, 0, rec.cin, taps_mirror(rec.taps),
@@ -1284,21 +1282,17 @@ class Engine:
             return None
         return p
 
-    def _route(self, rec, dsrc):
-        """hand d(src) of `rec` to whoever produced src"""
-        src = rec.src
-        prod = src.producer
-        if isinstance(prod, tuple) and prod[0] == "cat":
-            half = rec.cin // 2
-            up = rec.cat_upper
-            up.grad_out = (dsrc, rec.cin, half)
-            # the skip half belongs to the conv that wrote channels [0:half) of the cat buffer
-            skip = [r for r in self.recs if r.kind == "conv" and r.y is src.t and r.coff == 0][0]
-            skip.grad_same = (dsrc, rec.cin, 0)
+    def _route(self, src, cin, dsrc):
+        """hand d(src), cin channels wide, to whoever produced src: the two halves of a skip concatenation to the layer that wrote the
+        skip half and to the transposed convolution (up), anything else to its producer as a pooled or a full-resolution gradient"""
+        if getattr(src, "cat", None) is not None:
+            skip, up = src.cat
+            up.grad_out = (dsrc, cin, cin // 2)
+            skip.grad_same = (dsrc, cin, 0)
         elif src.pool or getattr(src, "via_pool", False):
-            prod.grad_pool = (dsrc, rec.cin, 0)
+            src.producer.grad_pool = (dsrc, cin, 0)
         else:
-            prod.grad_same = (dsrc, rec.cin, 0)
+            src.producer.grad_same = (dsrc, cin, 0)
 
     def _build_backward(self):
         ops = self.bwd_ops
@@ -1310,7 +1304,7 @@ class Engine:
                 dY = self._bn_backward(ops, rec, rec.grad_same, rec.grad_pool, defer=True)
                 dsrc = self._conv_backward(ops, rec, dY)
                 if dsrc is not None:
-                    self._route(rec, dsrc)
+                    self._route(rec.src, rec.cin, dsrc)
             else:
                 self._convT_backward(ops, rec)
 
@@ -1342,13 +1336,11 @@ class Engine:
             got = self.emit_wgrad(ops, dl, r2.src, hc, 128, [(0, 0)], 1, r2.cname + ".weight", "wgrad " + r2.cname,
                                   rowsum_to=r2.cname + ".bias", collect=head_wgrads, nsplit=head_splits[i])
             if got != "rowsum":
-                lib = self.lib
-                psw = self.new((lib.abc_plane_sum_work(hc),), torch.float32)
+                psw = self.new((self.lib.abc_plane_sum_work(hc),), torch.float32)
                 a = (self.dlogits[i].data_ptr(), B, hc, h * w, cs.data_ptr(), psw.data_ptr(), self.G(r2.cname + ".bias"))
-                ops.append((lambda _r, st, a=a: lib.abc_plane_sum(*a, st), None, "dbias " + r2.cname, (r2.cname + ".bias",),
-                            {"kernel": "plane_sum", "flops": 0, "bytes": float(B * hc * h * w * 4)}))
-            wd = self.packed(1, hc, 128)
-            self.emit_pack(r2.cname + ".weight", wd, 1, hc, 128, 1, 128, hc)
+                self._emit(ops, self.lib.abc_plane_sum, a, "dbias " + r2.cname, (r2.cname + ".bias",),
+                           {"kernel": "plane_sum", "flops": 0, "bytes": float(B * hc * h * w * 4)})
+            wd = self._pack_weights(r2.cname + ".weight", 1, hc, 128, 1)
             self.emit_conv(ops, dl, wd, None, dfeat, self.dt, h, w, 128 * nh, 128 * i, 128, [(0, 0)], what="dgrad " + r2.cname,
                            collect=head_dgrads)
         self.emit_wgrad_heads_batch(ops, head_wgrads, "wgrad out_modules.*.conv2")
@@ -1356,44 +1348,51 @@ class Engine:
         # ---- heads' BN + conv1: per-head BN backward, ONE data-gradient conv over the 8x128 concatenated channels
         taps = taps_square(3)
         dyh = self.new((B, h, w, 128 * nh))
-        wd_all = self.packed(9, 128 * nh, 128)
         merged = None
+        drop = (self.drop_p, self.drop_seed) if self.drop_p > 0 else None
         # (the one act_bwd pass over 128 x nh channels takes 16 nh bf16 vectors per pixel, which must divide its 256 threads: 1, 2, 4
         #  or 8 heads; unet.py's default six heads and other counts take the per-head passes below)
         if self.dt == L.BF16 and self.batched_heads and nh in (1, 2, 4, 8):
-            merged = self._heads_act_bwd_merged(ops, dfeat)
+            # BN -> LeakyReLU -> Dropout backward of ALL heads as one pass over the 8 x 128 channels of hfeat / dfeat (their
+            # coefficient and statistics arrays sit side by side), one batched finalisation
+            g = self.new((B, h, w, 128 * nh))
+            sc, sh, sl = self.hcoef
+            wide = Rec(bname="out_modules.*.bn", y=self.hfeat, ld=128 * nh, coff=0, cout=128 * nh, H=h, W=w, scale=sc, shift=sh, slopes=sl,
+                       mean=self.hmean, invstd=self.hinvstd)
+            part, nblk = self._act_bwd(ops, wide, (dfeat, 128 * nh, 0), None, g.data_ptr(), 128 * nh, drop)
+            merged = self._heads_bn_bwd_batch(ops, g, part, nblk)
         one_wgrad = merged is not None and self._heads_conv1_wgrad_merged(ops, merged, dyh, taps)
         for i, rec in enumerate(self.head_recs):
-            drop = (self.drop_p, self.drop_seed) if self.drop_p > 0 else None
             if one_wgrad:
-                pass
-            elif merged is not None:
-                ok = self.emit_wgrad(ops, merged[i], rec.src, 128, 128, taps, 1, rec.cname + ".weight", "wgrad " + rec.cname,
-                                     dual=(rec.y, rec.ld, rec.coff, dyh.data_ptr() + 128 * i * dyh.element_size(), 128 * nh))
-                if not ok:
-                    raise RuntimeError("fused BN-backward apply was refused for " + rec.cname)
-            elif self.dt == L.BF16:
+                continue
+            if self.dt == L.BF16:
                 # bf16: the weight-gradient kernel applies the BN-backward correction on load and writes dY into this
                 # head's channel slice of dyh (no separate apply pass)
-                gsrc, _apply = self._bn_backward(ops, rec, (dfeat, 128 * nh, 128 * i), None, drop=drop, defer=True)
+                gsrc = merged[i] if merged is not None else self._bn_backward(ops, rec, (dfeat, 128 * nh, 128 * i), drop=drop, defer=True)[0]
                 ok = self.emit_wgrad(ops, gsrc, rec.src, 128, 128, taps, 1, rec.cname + ".weight", "wgrad " + rec.cname,
                                      dual=(rec.y, rec.ld, rec.coff, dyh.data_ptr() + 128 * i * dyh.element_size(), 128 * nh))
                 if not ok:
                     raise RuntimeError("fused BN-backward apply was refused for " + rec.cname)
             else:
-                dY = self._bn_backward_into(ops, rec, (dfeat, 128 * nh, 128 * i), dyh, 128 * nh, 128 * i, drop)
+                dY = self._bn_backward(ops, rec, (dfeat, 128 * nh, 128 * i), drop=drop, g=(dyh, 128 * nh, 128 * i), in_place=True)
                 self.emit_wgrad(ops, dY, rec.src, 128, 128, taps, 1, rec.cname + ".weight", "wgrad " + rec.cname)
-            self.emit_pack(rec.cname + ".weight", wd_all, 1, 128, 128, 3, 128, 128, red_total=128 * nh, red_off=128 * i)
-        dtrunk = self.new((B, h, w, 128))
-        dy_all = Src(dyh, self.dt, h, w, 128 * nh, 0, 128 * nh)
-        self._heads_conv1_dgrad(ops, dy_all, wd_all, dtrunk, taps)
+        self._heads_conv1_dgrad(ops, dyh, taps)
 
-    def _heads_conv1_dgrad(self, ops, dy_all, wd_all, dtrunk, taps):
-        """the eight heads' conv1 data gradients as ONE 8 x 128 -> 128 convolution (unet.py:66,116-118 backward); the trunk's last layer
-        has no reader but the heads, so its act_bwd pass rides in this launch's epilogue where the library serves it"""
+    def _heads_conv1_dgrad(self, ops, dyh, taps):
+        """the tail of both heads-backward plans: the eight heads' conv1 data gradients as ONE 8 x 128 -> 128 convolution over dyh, their dY
+        side by side (unet.py:66,116-118 backward); the trunk's last layer has no reader but the heads, so its act_bwd pass rides in
+        this launch's epilogue where the library serves it"""
         h, w = self.h, self.w
+        Ct = 128 * len(self.heads)
+        wd_all = self.packed(9, Ct, 128)
+        for i, rec in enumerate(self.head_recs):
+            self.emit_pack(rec.cname + ".weight", wd_all, 1, 128, 128, 3, 128, 128, red_total=Ct, red_off=128 * i)
+        dtrunk = self.new((self.B, h, w, 128))
+        self.dyh, self.dtrunk = dyh, dtrunk      # (handles for the in-situ parity tests)
+        dy_all = Src(dyh, self.dt, h, w, Ct, 0, Ct)
         p = self.trunk.producer
         what = "dgrad heads.conv1"
+        p.grad_same = (dtrunk, 128, 0)
         if (self.actbwd_epilogue and self.train and self.dt == L.BF16 and isinstance(p, Rec) and p.kind == "conv" and self.trunk.t is p.y and
                 not self.trunk.pool and self.trunk.drop_p == 0 and p.coff == 0 and p.ld == p.cout == 128 and (p.H, p.W) == (h, w) and
                 all(getattr(r, "is_head", False) for r in self.recs + list(self.head_recs)
@@ -1404,10 +1403,29 @@ class Engine:
                 p.fused_g = (dtrunk, got[0], got[1])
                 p.g = dtrunk
                 self.heads_dgrad_is_g = True
-                p.grad_same = (dtrunk, 128, 0)
                 return
         self.emit_conv(ops, dy_all, wd_all, None, dtrunk, self.dt, h, w, 128, 0, 128, taps_mirror(taps), what=what)
-        p.grad_same = (dtrunk, 128, 0)
+
+    def _heads_bn_bwd_batch(self, ops, g, part, nblk, in_scale=None):
+        """the finalisers of all heads' BatchNorm backward as one launch, from partial sums [nblk][2][nh x 128] (in_scale: the flat
+        per-channel loss-scale array, each head's factors from its offset); returns per head the Src of its 128 channels of g with the
+        deferred-apply coefficients (as _bn_backward(defer=True))"""
+        nh = len(self.heads)
+        Ct = 128 * nh
+        # the deferred-apply coefficients are indexed by the ABSOLUTE channel of g (abc_act_src): one array of 8 x 128 per
+        # quantity, every head's finalisation writing its own slice
+        ca_all, cb_all, cc_all = (self.new((Ct,), torch.float32) for _ in range(3))
+        descs, writes, out = [], (), []
+        for i, rec in enumerate(self.head_recs):
+            sl = slice(128 * i, 128 * (i + 1))
+            f, _k, wr = self._bn_bwd_desc(rec, part.data_ptr() + 4 * 128 * i, nblk, (ca_all[sl], cb_all[sl], cc_all[sl]),
+                                          None if in_scale is None else in_scale.data_ptr() + 4 * self.head_off[i])
+            descs.append(f)
+            writes += wr
+            out.append(Src(g, self.dt, rec.H, rec.W, Ct, 128 * i, 128, coef=(ca_all, cc_all, cb_all)))
+        self._emit(ops, self.lib.abc_bn_finalize_bwd_batch, ((L.BnBwdDesc * nh)(*descs), nh, Ct), "bn_bwd out_modules.*.bn", writes,
+                   {"kernel": "bn_bwd", "flops": 0, "bytes": 0})
+        return out
 
     def _heads_backward_fused(self, ops):
         """backward plan behind the fused heads pass: conv2's weight / bias gradients from the blocked d(logits), the eight
@@ -1415,41 +1433,17 @@ class Engine:
         B, h, w = self.B, self.h, self.w
         nh = len(self.heads)
         Ct = 128 * nh
-        lib, d = self.lib, self.hf
         npx = B * h * w
         writes = tuple(n for i in range(nh) for n in ("out_modules.%d.conv2.weight" % i, "out_modules.%d.conv2.bias" % i))
-        ops.append((lambda _r, st: lib.abc_heads_fused_wgrad(C.byref(d), st), None, "wgrad out_modules.*.conv2", writes,
-                    {"kernel": "heads_fused_wgrad", "flops": 2.0 * npx * sum(self.heads) * 128,
-                     "bytes": float(npx * Ct * 2 + self.hf_dl.numel() * 2 + self.hf_work.numel() * 4)}))
-        arr = (L.BnBwdDesc * nh)()
-        merged, bwrites = [], []
-        ca_all, cb_all, cc_all = (self.new((Ct,), torch.float32) for _ in range(3))
-        for i, rec in enumerate(self.head_recs):
-            k1, k2, gs = (self.new((128,), torch.float32) for _ in range(3))
-            ca, cb, cc = (t[128 * i:128 * (i + 1)] for t in (ca_all, cb_all, cc_all))
-            f = arr[i]
-            f.partial, f.nblk, f.C, f.count = self.hf_bnpart.data_ptr() + 4 * 128 * i, self.hf_chunks, 128, float(npx)
-            f.gamma, f.invstd = self.P(rec.bname + ".weight"), rec.invstd.data_ptr()
-            f.dgamma, f.dbeta = self.G(rec.bname + ".weight"), self.G(rec.bname + ".bias")
-            f.k1, f.k2, f.gscale = k1.data_ptr(), k2.data_ptr(), gs.data_ptr()
-            f.mean, f.ca, f.cb, f.cc = rec.mean.data_ptr(), ca.data_ptr(), cb.data_ptr(), cc.data_ptr()
-            f.in_scale = self.chan_scale.data_ptr() + 4 * self.head_off[i]
-            bwrites += [rec.bname + ".weight", rec.bname + ".bias"]
-            merged.append(Src(self.hf_g, self.dt, h, w, Ct, 128 * i, 128, coef=(ca_all, cc_all, cb_all)))
-        self.keep.append(arr)
-        ops.append((lambda _r, st, a=arr: lib.abc_bn_finalize_bwd_batch(a, nh, Ct, st), None, "bn_bwd out_modules.*.bn", tuple(bwrites),
-                    {"kernel": "bn_bwd", "flops": 0, "bytes": 0}))
+        self._emit(ops, self.lib.abc_heads_fused_wgrad, (self.hf,), "wgrad out_modules.*.conv2", writes,
+                   {"kernel": "heads_fused_wgrad", "flops": 2.0 * npx * sum(self.heads) * 128,
+                    "bytes": float(npx * Ct * 2 + self.hf_dl.numel() * 2 + self.hf_work.numel() * 4)})
+        merged = self._heads_bn_bwd_batch(ops, self.hf_g, self.hf_bnpart, self.hf_chunks, in_scale=self.chan_scale)
         taps = taps_square(3)
         dyh = self.new((B, h, w, Ct))
-        wd_all = self.packed(9, Ct, 128)
         if not self._heads_conv1_wgrad_merged(ops, merged, dyh, taps):
             raise RuntimeError("fused heads: the merged conv1 weight gradient was refused")
-        for i, rec in enumerate(self.head_recs):
-            self.emit_pack(rec.cname + ".weight", wd_all, 1, 128, 128, 3, 128, 128, red_total=Ct, red_off=128 * i)
-        dtrunk = self.new((B, h, w, 128))
-        self.dyh, self.dtrunk = dyh, dtrunk
-        dy_all = Src(dyh, self.dt, h, w, Ct, 0, Ct)
-        self._heads_conv1_dgrad(ops, dy_all, wd_all, dtrunk, taps)
+        self._heads_conv1_dgrad(ops, dyh, taps)
 
     def _heads_conv1_wgrad_merged(self, ops, merged, dyh, taps):
         """The eight heads' conv1 weight gradients (unet.py:66, 8 x [128,128,3,3]) as ONE weight gradient with 8 x 128
@@ -1460,99 +1454,28 @@ class Engine:
         fused BatchNorm-backward load for this descriptor (the caller then emits one launch per head)."""
         nh = len(self.heads)
         Ct = 128 * nh
-        r0 = self.head_recs[0]
-        q = r0.src
+        q = self.head_recs[0].src
         g0 = merged[0]
         p = Src(g0.t, self.dt, g0.H, g0.W, Ct, 0, Ct, coef=g0.coef)
-        d = L.WgradDesc()
-        p.fill(d.p)
-        q.fill(d.q)
-        d.dtype_p, d.dtype_q, d.dtype_c = p.dt, q.dt, self.dt
-        gh, gw = p.lh()
-        d.B, d.Hg, d.Wg, d.Hq, d.Wq = self.B, gh, gw, gh, gw
-        d.cp_off, d.cq_off, d.Ca, d.Cb, d.stride = 0, q.coff, Ct, 128, 1
-        L.set_taps(d, taps)
-        d.p2, d.ld_p2, d.cp2_off, d.p_dual, d.p_out, d.ld_pout = self.hfeat.data_ptr(), Ct, 0, 1, dyh.data_ptr(), Ct
-        if not self.lib.abc_wgrad_fuses_apply(C.byref(d)):
+        got = self._wgrad_desc(p, q, Ct, 128, taps, 1, dual=(self.hfeat, Ct, 0, dyh.data_ptr(), Ct))
+        if got is None:
             return False
-        ca_pad, cb_pad = L.i32(), L.i32()
-        L.check(self.lib.abc_wgrad_pads(C.byref(d), C.byref(ca_pad), C.byref(cb_pad)), "wgrad_pads")
-        ca_pad, cb_pad = ca_pad.value, cb_pad.value
-        per_split = self.lib.abc_wgrad_blocks(C.byref(d))
-        npatch = self.B * (-(-gh // 8)) * (-(-gw // 16))
-        nsplit = max(1, min(max(1, npatch // 2), 256 // per_split))
+        d, (ca_pad, cb_pad), _tile, nsplit, meta = got      # (the default K-split: emit_wgrad's per-tile overrides are not for this launch)
         d.nsplit = nsplit
         need = nsplit * len(taps) * ca_pad * cb_pad
         slabs = self.new((need,), torch.float32)
         d.partial = slabs.data_ptr()
-        at_, bt_ = L.i32(), L.i32()
-        L.check(self.lib.abc_wgrad_tile(C.byref(d), C.byref(at_), C.byref(bt_)), "wgrad_tile")
-        esz = self._esz(self.dt)
-        npx = self.B * gh * gw
-        meta = {"kernel": "wgrad<%s,%s,%s,%dx%d,S1>" % (self._dn(p.dt), self._dn(q.dt), self._dn(self.dt), at_.value, bt_.value),
-                "flops": 2.0 * npx * Ct * 128 * len(taps),
-                # g + y_raw read, dY written, Q read once, the slabs written
-                "bytes": float(3 * npx * Ct * esz + npx * 128 * self._esz(q.dt) + need * 4)}
-        self._emit(ops, self.lib.abc_wgrad, d, "wgrad out_modules.*.conv1", meta=meta)
-        rarr = (L.WgradReduceDesc * nh)()
-        writes = []
-        for i, rec in enumerate(self.head_recs):
-            r = rarr[i]
-            r.partial = slabs.data_ptr() + 4 * 128 * i * cb_pad      # this head's 128 rows of every slab
-            r.nsplit, r.ntaps, r.Ca, r.Cb, r.Ca_pad, r.Cb_pad = nsplit, len(taps), 128, 128, ca_pad, cb_pad
-            r.dw, r.accumulate = self.G(rec.cname + ".weight"), 0
-            writes.append(rec.cname + ".weight")
-        self.keep.append(rarr)
-        lib = self.lib
-        ops.append((lambda _r, st, a=rarr: lib.abc_wgrad_reduce_batch(a, nh, st), None, "wgrad out_modules.*.conv1 reduce", tuple(writes),
-                    {"kernel": "wgrad_reduce_batch", "flops": 0, "bytes": float(need * 4 + Ct * 128 * len(taps) * 4)}))
+        npx = self.B * g0.H * g0.W
+        # g + y_raw read, dY written, Q read once, the slabs written
+        meta["bytes"] = float(3 * npx * Ct * self._esz(self.dt) + npx * 128 * self._esz(q.dt) + need * 4)
+        self._emit(ops, self.lib.abc_wgrad, (d,), "wgrad out_modules.*.conv1", meta=meta)
+        # (this head's 128 rows of every slab)
+        reduces = [self._reduce_desc(slabs.data_ptr() + 4 * 128 * i * cb_pad, nsplit, len(taps), 128, 128, ca_pad, cb_pad, self.G(rec.cname + ".weight"))
+                   for i, rec in enumerate(self.head_recs)]
+        self._emit(ops, self.lib.abc_wgrad_reduce_batch, ((L.WgradReduceDesc * nh)(*reduces), nh), "wgrad out_modules.*.conv1 reduce",
+                   tuple(rec.cname + ".weight" for rec in self.head_recs),
+                   {"kernel": "wgrad_reduce_batch", "flops": 0, "bytes": float(need * 4 + Ct * 128 * len(taps) * 4)})
         return True
-
-    def _heads_act_bwd_merged(self, ops, dfeat):
-        """BN -> LeakyReLU -> Dropout backward of ALL heads as one pass over the 8 x 128 channels of hfeat / dfeat (their
-        coefficient and statistics arrays sit side by side), one batched finalisation; returns per head the Src of g with
-        the deferred-apply coefficients (as _bn_backward(defer=True))"""
-        nh = len(self.heads)
-        Ct = 128 * nh
-        r0 = self.head_recs[0]
-        B, H, W = self.B, r0.H, r0.W
-        g = self.new((B, H, W, Ct))
-        d = L.ActBwdDesc()
-        d.y_raw, d.ld_y = self.hfeat.data_ptr(), Ct
-        d.dA_same, d.ld_same, d.csame_off = dfeat.data_ptr(), Ct, 0
-        d.g, d.ld_g = g.data_ptr(), Ct
-        sc, sh, sl = self.hcoef
-        d.scale, d.shift, d.slope = sc.data_ptr(), sh.data_ptr(), sl.data_ptr()
-        d.mean, d.invstd = self.hmean.data_ptr(), self.hinvstd.data_ptr()
-        d.dtype, d.B, d.H, d.W, d.C, d.cy_off = self.dt, B, H, W, Ct, 0
-        if self.drop_p > 0:
-            d.drop_p, d.drop_seed, d.drop_ld, d.drop_salt = self.drop_p, self.drop_seed, Ct, self.drop_salt.data_ptr()
-        nblk = self.lib.abc_act_bwd_blocks(C.byref(d))
-        part = self.new((nblk, 2, Ct), torch.float32)
-        d.partial = part.data_ptr()
-        self._emit(ops, self.lib.abc_act_bwd, d, "act_bwd out_modules.*.bn",
-                   meta={"kernel": "act_bwd", "flops": 0, "bytes": float(B * H * W * Ct * self._esz(self.dt) * 3)})
-        arr = (L.BnBwdDesc * nh)()
-        out, writes = [], []
-        # the deferred-apply coefficients are indexed by the ABSOLUTE channel of g (abc_act_src): one array of 8 x 128 per
-        # quantity, every head's finalisation writing its own slice
-        ca_all, cb_all, cc_all = (self.new((Ct,), torch.float32) for _ in range(3))
-        for i, rec in enumerate(self.head_recs):
-            k1, k2, gs = (self.new((128,), torch.float32) for _ in range(3))
-            ca, cb, cc = (t[128 * i:128 * (i + 1)] for t in (ca_all, cb_all, cc_all))
-            f = arr[i]
-            f.partial, f.nblk, f.C, f.count = part.data_ptr() + 4 * 128 * i, nblk, 128, float(B * H * W)
-            f.gamma, f.invstd = self.P(rec.bname + ".weight"), rec.invstd.data_ptr()
-            f.dgamma, f.dbeta = self.G(rec.bname + ".weight"), self.G(rec.bname + ".bias")
-            f.k1, f.k2, f.gscale = k1.data_ptr(), k2.data_ptr(), gs.data_ptr()
-            f.mean, f.ca, f.cb, f.cc = rec.mean.data_ptr(), ca.data_ptr(), cb.data_ptr(), cc.data_ptr()
-            writes += [rec.bname + ".weight", rec.bname + ".bias"]
-            out.append(Src(g, self.dt, H, W, Ct, 128 * i, 128, coef=(ca_all, cc_all, cb_all)))
-        self.keep.append(arr)
-        lib = self.lib
-        ops.append((lambda _r, st, a=arr: lib.abc_bn_finalize_bwd_batch(a, nh, Ct, st), None, "bn_bwd out_modules.*.bn", tuple(writes),
-                    {"kernel": "bn_bwd", "flops": 0, "bytes": 0}))
-        return out
 
     def _convT_backward(self, ops, rec):
         """ConvTranspose2d(k3,s2) backward: bias (column sums of dOut), weight (stride-2 wgrad), data (stride-2 gather)"""
@@ -1563,49 +1486,12 @@ class Engine:
         self.emit_colsum(ops, dcat, self.dt, B * hs * ws, ld, coff, rec.cout, None, rec.cname + ".bias", "dbias " + rec.cname)
         self.emit_wgrad(ops, rec.src, dOut, rec.cin, rec.cout, rec.taps_bwd, 2, rec.cname + ".weight", "wgrad " + rec.cname)
         lh, lw = rec.src.lh()
-        rows_pad = -(-rec.cin // 32) * 32
-        wd = self.packed(9, rec.cout, rows_pad)
-        self.emit_pack(rec.cname + ".weight", wd, 3, rec.cout, rec.cin, 3, rows_pad, rec.cout)
+        wd = self._pack_weights(rec.cname + ".weight", 3, rec.cout, rec.cin, 3)
         dsrc = self.new((B, lh, lw, rec.cin))
         rec.dsrc = dsrc
         self.emit_conv(ops, dOut, wd, None, dsrc, self.dt, lh, lw, rec.cin, 0, rec.cin, rec.taps_bwd, stride=2,
                        what="dgrad " + rec.cname)
         rec.src.producer.grad_same = (dsrc, rec.cin, 0)
-
-    def _bn_backward_into(self, ops, rec, same, gbuf, ld_g, g_off, drop):
-        """as _bn_backward, but G/dY live in a channel slice of a shared buffer (the heads)"""
-        C_ = rec.cout
-        esz = gbuf.element_size()
-        gptr = gbuf.data_ptr() + g_off * esz
-        d = L.ActBwdDesc()
-        d.y_raw, d.ld_y = rec.y.data_ptr(), rec.ld
-        d.dA_same, d.ld_same, d.csame_off = same[0].data_ptr(), same[1], same[2]
-        d.g, d.ld_g = gptr, ld_g
-        d.scale, d.shift, d.slope = rec.scale.data_ptr(), rec.shift.data_ptr(), rec.slopes.data_ptr()
-        d.mean, d.invstd = rec.mean.data_ptr(), rec.invstd.data_ptr()
-        d.dtype, d.B, d.H, d.W, d.C, d.cy_off = self.dt, self.B, rec.H, rec.W, C_, rec.coff
-        if drop is not None:
-            d.drop_p, d.drop_seed, d.drop_ld, d.drop_salt = drop[0], drop[1], rec.ld, self.drop_salt.data_ptr()
-        nblk = self.lib.abc_act_bwd_blocks(C.byref(d))
-        part = self.new((nblk, 2, C_), torch.float32)
-        d.partial = part.data_ptr()
-        nsrc = (1 if d.dA_same else 0) + (0.25 if d.dA_pool else 0)
-        self._emit(ops, self.lib.abc_act_bwd, d, "act_bwd " + rec.bname,
-                   meta={"kernel": "act_bwd", "flops": 0, "bytes": float(self.B * rec.H * rec.W * C_ * self._esz(self.dt) * (2 + nsrc))})
-        k1, k2, gs = (self.new((C_,), torch.float32) for _ in range(3))
-        f = L.BnBwdDesc()
-        f.partial, f.nblk, f.C, f.count = part.data_ptr(), nblk, C_, float(self.B * rec.H * rec.W)
-        f.gamma, f.invstd = self.P(rec.bname + ".weight"), rec.invstd.data_ptr()
-        f.dgamma, f.dbeta = self.G(rec.bname + ".weight"), self.G(rec.bname + ".bias")
-        f.k1, f.k2, f.gscale = k1.data_ptr(), k2.data_ptr(), gs.data_ptr()
-        self._emit_bn_bwd(ops, f, "bn_bwd " + rec.bname, (rec.bname + ".weight", rec.bname + ".bias"))
-        a = L.BnApplyDesc()
-        a.g, a.ld_g, a.y_raw, a.ld_y, a.cy_off = gptr, ld_g, rec.y.data_ptr(), rec.ld, rec.coff
-        a.mean, a.invstd, a.k1, a.k2, a.gscale = rec.mean.data_ptr(), rec.invstd.data_ptr(), k1.data_ptr(), k2.data_ptr(), gs.data_ptr()
-        a.dtype, a.C, a.npix = self.dt, C_, self.B * rec.H * rec.W
-        self._emit(ops, self.lib.abc_bn_apply_bwd, a, "bn_apply " + rec.bname,
-                   meta={"kernel": "bn_apply", "flops": 0, "bytes": float(self.B * rec.H * rec.W * C_ * self._esz(self.dt) * 3)})
-        return Src(gbuf, self.dt, rec.H, rec.W, ld_g, g_off, C_)
 
     # ------------------------------------------------------------------ unet2 (CBAM + residual, unet2.py)
     def f32buf(self, *shape, fill=0.0):
@@ -1636,14 +1522,12 @@ class Engine:
         ch.ca, ch.avgz, ch.maxz = blk.ca.data_ptr(), blk.avgz.data_ptr(), blk.maxz.data_ptr()
         ch.hid_avg, ch.hid_max = blk.hid_a.data_ptr(), blk.hid_m.data_ptr()
         ch.ext, ch.first = blk.ext.data_ptr(), blk.first.data_ptr()
-        self._emit(self.fwd_ops, lib.abc_cbam_channel_fwd, ch, "cbam_channel " + prefix)
+        self._emit(self.fwd_ops, lib.abc_cbam_channel_fwd, (ch,), "cbam_channel " + prefix)
         blk.st, blk.amax, blk.sa = self.f32buf(B, H, W, 2), self.new((B, H, W), torch.int32), self.f32buf(B, H, W)
         # residual branch (unet2.py:62-65,72)
         if cin != cout:
             tr = self.new((B, H, W, cout))
-            rows_pad = -(-cout // 32) * 32
-            wr = self.packed(1, cin, rows_pad)
-            self.emit_pack(prefix + ".res_conv.weight", wr, 0, cout, cin, 1, rows_pad, cin)
+            wr = self._pack_weights(prefix + ".res_conv.weight", 0, cout, cin, 1)
             self.emit_conv(self.fwd_ops, xin, wr, self.P(prefix + ".res_conv.bias"), tr, self.dt, H, W, cout, 0, cout, [(0, 0)],
                            what="fwd %s.res_conv" % prefix)
             res = (tr, cout, 0, 0)
@@ -1667,17 +1551,14 @@ class Engine:
             return d
 
         blk.pix = pix
-        esz = self._esz(self.dt)
         npx = B * H * W
-        self._emit(self.fwd_ops, lib.abc_cbam_spatial_stats, pix(), "cbam_spatial_stats " + prefix,
-                   meta={"kernel": "cbam_spatial_stats", "flops": 0, "bytes": float(npx * cout * esz)})
+        self._emit(self.fwd_ops, lib.abc_cbam_spatial_stats, (pix(),), "cbam_spatial_stats " + prefix, meta=self._ew_meta("cbam_spatial_stats", npx, cout, 1))
         c7 = L.CbamConv7Desc()
         sp = p + ".5.spatial_attention.conv2d"
         c7.st, c7.w7, c7.b7, c7.sa = blk.st.data_ptr(), self.P(sp + ".weight"), self.P(sp + ".bias"), blk.sa.data_ptr()
         c7.B, c7.H, c7.W = B, H, W
-        self._emit(self.fwd_ops, lib.abc_cbam_conv7_fwd, c7, "cbam_conv7 " + prefix)
-        self._emit(self.fwd_ops, lib.abc_cbam_apply_fwd, pix(), "cbam_apply " + prefix,
-                   meta={"kernel": "cbam_apply", "flops": 0, "bytes": float(npx * cout * esz * 3)})
+        self._emit(self.fwd_ops, lib.abc_cbam_conv7_fwd, (c7,), "cbam_conv7 " + prefix)
+        self._emit(self.fwd_ops, lib.abc_cbam_apply_fwd, (pix(),), "cbam_apply " + prefix, meta=self._ew_meta("cbam_apply", npx, cout, 3))
         self.units2.append(("blk", blk))
         return Src(to, self.dt, H, W, ld_o, coff_o, cout, coef=None, producer=blk)
 
@@ -1721,7 +1602,6 @@ class Engine:
             blk = u
             H, W, Cc = blk.H, blk.W, blk.cout
             npx = B * H * W
-            esz = self._esz(self.dt)
             g = self.new((B, H, W, Cc))
             dz = self.new((B, H, W, Cc))
             du, dst = self.f32buf(B, H, W), self.f32buf(B, H, W, 2)
@@ -1740,8 +1620,7 @@ class Engine:
                 d1.d_same, d1.ld_same, d1.csame_off = blk.grad_same[0].data_ptr(), blk.grad_same[1], blk.grad_same[2]
             if blk.grad_pool is not None:
                 d1.d_pool, d1.ld_pool, d1.cpool_off = blk.grad_pool[0].data_ptr(), blk.grad_pool[1], blk.grad_pool[2]
-            self._emit(ops, lib.abc_cbam_bwd1, d1, "cbam_bwd1 " + blk.prefix,
-                       meta={"kernel": "cbam_bwd1", "flops": 0, "bytes": float(npx * Cc * esz * 4)})
+            self._emit(ops, lib.abc_cbam_bwd1, (d1,), "cbam_bwd1 " + blk.prefix, meta=self._ew_meta("cbam_bwd1", npx, Cc, 4))
             p = blk.prefix + ".double_conv"
             sp = p + ".5.spatial_attention.conv2d"
             c7 = L.CbamConv7Desc()
@@ -1751,13 +1630,12 @@ class Engine:
             part7 = self.f32buf(nb7, 99)
             c7.dw_partial, c7.dw7, c7.db7 = part7.data_ptr(), self.G(sp + ".weight"), self.G(sp + ".bias")
             # (the reduction of part7 rides in the first launch of this block's channel-attention backward below)
-            self._emit(ops, lib.abc_cbam_conv7_bwd_partial, c7, "cbam_conv7_bwd " + blk.prefix)
+            self._emit(ops, lib.abc_cbam_conv7_bwd_partial, (c7,), "cbam_conv7_bwd " + blk.prefix)
             d2 = pix()
             nb2 = lib.abc_cbam_bwd2_blocks(C.byref(d2))
             part2 = self.f32buf(B, nb2, Cc)
             d2.partial = part2.data_ptr()
-            self._emit(ops, lib.abc_cbam_bwd2, d2, "cbam_bwd2 " + blk.prefix,
-                       meta={"kernel": "cbam_bwd2", "flops": 0, "bytes": float(npx * Cc * esz * 3)})
+            self._emit(ops, lib.abc_cbam_bwd2, (d2,), "cbam_bwd2 " + blk.prefix, meta=self._ew_meta("cbam_bwd2", npx, Cc, 3))
             m = p + ".5.channel_attention.shared_MLP"
             ch = L.CbamChannelDesc()
             ch.partial, ch.tiles_per_img, ch.B, ch.C, ch.mid, ch.HW = part2.data_ptr(), nb2, B, Cc, blk.mid, float(H * W)
@@ -1767,23 +1645,20 @@ class Engine:
             ch.dw1, ch.db1, ch.dw2, ch.db2 = self.G(m + ".0.weight"), self.G(m + ".0.bias"), self.G(m + ".2.weight"), self.G(m + ".2.bias")
             ch.d_avgz, ch.d_maxz = d_avgz.data_ptr(), d_maxz.data_ptr()
             ch.work = self.f32buf(B * (Cc + 2 * blk.mid)).data_ptr()
-            self.keep += [ch, c7]
-            ops.append((lambda _r, st, a=(ch, c7): lib.abc_cbam_channel_bwd_c7(C.byref(a[0]), C.byref(a[1]), st), None,
-                        "cbam_channel_bwd " + blk.prefix + " + conv7 reduce",
-                        (m + ".0.weight", m + ".0.bias", m + ".2.weight", m + ".2.bias", sp + ".weight", sp + ".bias"),
-                        {"kernel": "cbam_channel_bwd", "flops": 0, "bytes": 0}))
+            self._emit(ops, lib.abc_cbam_channel_bwd_c7, (ch, c7), "cbam_channel_bwd " + blk.prefix + " + conv7 reduce",
+                       (m + ".0.weight", m + ".0.bias", m + ".2.weight", m + ".2.bias", sp + ".weight", sp + ".bias"),
+                       {"kernel": "cbam_channel_bwd", "flops": 0, "bytes": 0})
             d3 = pix()
             nb3 = lib.abc_cbam_bwd3_blocks(C.byref(d3))
             part3 = self.f32buf(nb3, 2, Cc)
             d3.partial = part3.data_ptr()
-            self._emit(ops, lib.abc_cbam_bwd3, d3, "cbam_bwd3 " + blk.prefix,
-                       meta={"kernel": "cbam_bwd3", "flops": 0, "bytes": float(npx * Cc * esz * 3)})
+            self._emit(ops, lib.abc_cbam_bwd3, (d3,), "cbam_bwd3 " + blk.prefix, meta=self._ew_meta("cbam_bwd3", npx, Cc, 3))
             # BN2 backward on d_z, then the second conv
             rec2, rec1 = blk.rec2, blk.rec1
             # (the BN-backward apply fused into the weight gradient's load, as unet does: neutral in round 1 -- bn_apply -0.27 ms,
             #  dual weight gradients +0.33 ms -- +0.9 % since the weight-gradient kernel's prefetch got cheaper: 1231 -> 1242 img/s)
             defer2 = True
-            dY2 = self._bn_finish(ops, rec2, part3, nb3, dz, defer=defer2)
+            dY2 = self._bn_backward(ops, rec2, defer=defer2, g=(dz, Cc, 0), partials=(part3, nb3), in_place=True)
             dA1 = self._conv_backward(ops, rec2, dY2)
             rec1.grad_same = (dA1, rec1.cout, 0)
             dY1 = self._bn_backward(ops, rec1, rec1.grad_same, None, defer=defer2)
@@ -1804,64 +1679,14 @@ class Engine:
                     self.emit_wgrad(ops, gsrc, xin, blk.cout, blk.cin, [(0, 0)], 1, rname + ".weight", "wgrad " + rname)
                     self.emit_colsum(ops, g, self.dt, npx, Cc, 0, Cc, None, rname + ".bias", "dbias " + rname)
                 if has_prod:
-                    rows_pad = -(-blk.cin // 32) * 32
-                    wd = self.packed(1, blk.cout, rows_pad)
-                    self.emit_pack(rname + ".weight", wd, 1, blk.cout, blk.cin, 1, rows_pad, blk.cout)
+                    wd = self._pack_weights(rname + ".weight", 1, blk.cout, blk.cin, 1)
                     self.emit_conv(ops, gsrc, wd, None, d_x, self.dt, H, W, blk.cin, 0, blk.cin, [(0, 0)], what="dgrad " + rname,
                                    accumulate=True)
             elif has_prod and not rec1.dsrc_accumulated:
-                a = (d_x.data_ptr(), blk.cin, 0, g.data_ptr(), Cc, 0, Cc, npx, self.dt)
-                ops.append((lambda _r, st, a=a: lib.abc_add_into(*a, st), None, "d_x += g " + blk.prefix, (),
-                            {"kernel": "add_into", "flops": 0, "bytes": float(npx * Cc * esz * 3)}))
+                self._emit(ops, lib.abc_add_into, (d_x.data_ptr(), blk.cin, 0, g.data_ptr(), Cc, 0, Cc, npx, self.dt), "d_x += g " + blk.prefix,
+                           meta=self._ew_meta("add_into", npx, Cc, 3))
             if has_prod:
-                self._route2(blk, d_x)
-
-    def _route2(self, blk, d_x):
-        src = blk.xin
-        if getattr(src, "cat", None) is not None:
-            skip_prod, up_rec = src.cat
-            half = blk.cin // 2
-            up_rec.grad_out = (d_x, blk.cin, half)
-            skip_prod.grad_same = (d_x, blk.cin, 0)
-        elif src.pool or getattr(src, "via_pool", False):
-            src.producer.grad_pool = (d_x, blk.cin, 0)
-        else:
-            src.producer.grad_same = (d_x, blk.cin, 0)
-
-    def _bn_finish(self, ops, rec, part, nblk, gbuf, defer=False, keep_g=False):
-        """bn_finalize_bwd + bn_apply for a BN whose G and partials were produced elsewhere (CBAM bwd3; a data gradient with the
-        act_bwd pass in its epilogue).
-        defer=True: as _bn_backward(defer=True) -- the apply pass is left to the weight-gradient kernel's load where it can;
-        keep_g: the apply pass writes a buffer of its own (g stays intact for the in-situ parity tests)"""
-        C_ = rec.cout
-        k1, k2, gs = (self.new((C_,), torch.float32) for _ in range(3))
-        f = L.BnBwdDesc()
-        f.partial, f.nblk, f.C, f.count = part.data_ptr(), nblk, C_, float(self.B * rec.H * rec.W)
-        f.gamma, f.invstd = self.P(rec.bname + ".weight"), rec.invstd.data_ptr()
-        f.dgamma, f.dbeta = self.G(rec.bname + ".weight"), self.G(rec.bname + ".bias")
-        f.k1, f.k2, f.gscale = k1.data_ptr(), k2.data_ptr(), gs.data_ptr()
-        if defer:
-            ca, cb, cc = (self.new((C_,), torch.float32) for _ in range(3))
-            f.mean, f.ca, f.cb, f.cc = rec.mean.data_ptr(), ca.data_ptr(), cb.data_ptr(), cc.data_ptr()
-        self._emit_bn_bwd(ops, f, "bn_bwd " + rec.bname, (rec.bname + ".weight", rec.bname + ".bias"))
-        a = L.BnApplyDesc()
-        a.g, a.ld_g, a.y_raw, a.ld_y, a.cy_off = gbuf.data_ptr(), C_, rec.y.data_ptr(), rec.ld, rec.coff
-        a.mean, a.invstd, a.k1, a.k2, a.gscale = rec.mean.data_ptr(), rec.invstd.data_ptr(), k1.data_ptr(), k2.data_ptr(), gs.data_ptr()
-        a.dtype, a.C, a.npix = self.dt, C_, self.B * rec.H * rec.W
-
-        def emit_apply():
-            out = gbuf
-            if keep_g:
-                out = self.new((self.B, rec.H, rec.W, C_))
-                a.out, a.ld_out = out.data_ptr(), C_
-            self._emit(ops, self.lib.abc_bn_apply_bwd, a, "bn_apply " + rec.bname,
-                       meta={"kernel": "bn_apply", "flops": 0, "bytes": float(self.B * rec.H * rec.W * C_ * self._esz(self.dt) * 3)})
-            rec.dY = out
-            return Src(out, self.dt, rec.H, rec.W, C_, 0, C_)
-
-        if defer:
-            return Src(gbuf, self.dt, rec.H, rec.W, C_, 0, C_, coef=(ca, cc, cb)), emit_apply
-        return emit_apply()
+                self._route(xin, blk.cin, d_x)
 
     # ------------------------------------------------------------------ execution
     def _run(self, ops, stream):
@@ -1875,8 +1700,8 @@ class Engine:
             raise L.AbcNetHipError("the library's reserved-CU count changed from %d to %d since this plan was built: its grids and "
                                    "statistics buffers were sized for the old value (abc_set_reserved_cus is process-wide; use "
                                    "abcnet_amd.engine.set_reserved_cus, which refuses while plans exist)" % (self.reserved_cus, self.lib.abc_get_reserved_cus()))
-        for fn, ref, what, _w, m in ops:
-            rc = fn(ref, stream)
+        for fn, args, what, _w, _m in ops:
+            rc = fn(*args, stream)
             if rc != 0:
                 L.check(rc, what)
 

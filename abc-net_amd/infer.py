@@ -185,10 +185,10 @@ class InferenceRunner:
         acc = {}
         for _ in range(iters):
             marks = []
-            for fn, ref, what, _w, meta in eng.fwd_ops:
+            for fn, args, what, _w, meta in eng.fwd_ops:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-                rc = fn(ref, st)
+                rc = fn(*args, st)
                 e1.record(stream)
                 if rc != 0:
                     L.check(rc, what)

@@ -100,7 +100,7 @@ class Trainer:
         names = list(model._lay_p.keys())
         sizes = [model._lay_p[n][1] for n in names]
         ready = {n: -1 for n in names}
-        for j, (_fn, _ref, _what, writes, _meta) in enumerate(eng.bwd_ops):
+        for j, (_fn, _args, _what, writes, _meta) in enumerate(eng.bwd_ops):
             for n in writes:
                 ready[n] = max(ready[n], j)
         rd = [ready[n] for n in names]
@@ -376,10 +376,10 @@ class Trainer:
                     else:
                         marks.append(("loss_fwd_bwd+finalize", 0.0, float(eng.B * eng.h * eng.w * (501 * 4 * 2 + 381 * 4 + 120 * 8)), e0, e1))
                     continue
-                for fn, ref, what, _w, meta in ops:
+                for fn, args, what, _w, meta in ops:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(stream)
-                    rc = fn(ref, st)
+                    rc = fn(*args, st)
                     e1.record(stream)
                     if rc != 0:
                         L.check(rc, what)

@@ -1,0 +1,219 @@
+"""Fingerprint of the launch plans the engine builds, without a GPU.
+
+    python profiles/tools/plan_fingerprint.py [--repo TREE] [--only SUBSTRING] [--dump DIR]
+
+Builds every plan of CONFIGS with Engine(..., device="cpu") and replays pack_ops, fwd_ops and bwd_ops against a proxy of the library that
+forwards the plan-time queries and, for a launch (any call whose last argument is the replay's stream), records the function name and
+every argument instead of launching: scalars as they are, ctypes structures and arrays (through byref()._obj too) field by field.  Every
+pointer -- argument or field -- becomes (owner ordinal, byte offset): the owner is the tensor storage that holds the address, numbered in
+order of first appearance, so that a change of allocation order does not show; at its first appearance the owner's shape, dtype and a
+hash of its contents are recorded as well.  Each op's label, `writes` and `meta` go in beside its call.  One SHA-256 per plan; --dump
+keeps the full text per plan for diffing.  Two trees build the same plans exactly when their columns of hashes agree: run this same file
+on both (--repo names the tree whose package is imported; it needs its libabcnet_hip.so)."""
+import argparse
+import ctypes as C
+import gc
+import hashlib
+import os
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--repo", default=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ap.add_argument("--only", default="")
+ap.add_argument("--dump", default=None)
+args = ap.parse_args()
+sys.path.insert(0, args.repo)
+sys.path.insert(0, os.path.join(args.repo, "tests"))
+
+import torch  # noqa: E402
+import abcnet_amd  # noqa: E402,F401
+from abcnet_amd import _lib as L  # noqa: E402
+from abcnet_amd.engine import Engine  # noqa: E402
+from abcnet_amd.unet import UNet  # noqa: E402
+from abcnet_amd.unet2 import UNet as UNet2  # noqa: E402
+from test_cabi_and_host import HEADS, OTHER_HEADS  # noqa: E402
+
+STREAM = 0x5EED0000
+
+
+class Proxy:
+    """stands in for the loaded library: queries go through, launches on STREAM are recorded"""
+
+    def __init__(self, real):
+        self.real, self.rec = real, None
+
+    def __getattr__(self, name):
+        fn = getattr(self.real, name)
+        types = L.SYMBOLS[name][1] if name in L.SYMBOLS else None
+
+        def call(*a):
+            if self.rec is not None and a and a[-1] == STREAM and isinstance(a[-1], int):
+                self.rec.call(name, a[:-1], types)
+                return 0
+            return fn(*a)
+        return call
+
+
+def tensors_of(x, depth=0):
+    if isinstance(x, torch.Tensor):
+        yield x
+    elif isinstance(x, (list, tuple)) and depth < 4:
+        for y in x:
+            yield from tensors_of(y, depth + 1)
+    elif isinstance(x, dict) and depth < 4:
+        for y in x.values():
+            yield from tensors_of(y, depth + 1)
+
+
+class Recorder:
+    def __init__(self, eng):
+        self.lines, self.ordinal = [], {}
+        # owners: every tensor storage the plan can point into -- the four arenas, the plan's buffers, what the engine holds by attribute
+        cands = [eng.params, eng.grads, eng.buffers, eng.counters]
+        cands += [raw for raw, _n, _s, _d in eng._guarded]
+        cands += list(tensors_of(eng.keep))
+        for v in vars(eng).values():
+            cands += list(tensors_of(v))
+        for op in eng.pack_ops + eng.fwd_ops + eng.bwd_ops:      # (tensors an op keeps alive itself)
+            cands += list(tensors_of(list(op[1]) if isinstance(op[1], (list, tuple)) else []))
+        own = {}
+        for t in cands:
+            st = t.untyped_storage()
+            key = st.data_ptr()
+            size = t.numel() * t.element_size()
+            if key not in own or size > own[key][2]:
+                own[key] = (key, st.nbytes(), size, t)
+        self.owners = sorted(own.values(), key=lambda o: o[0])
+        # the two device tables that hold addresses are recorded through what they were written from, not as bytes: the weight-packing
+        # table (abc_pack_item_fill's items: the engine's PackDesc list, in order) and the heads-epilogue table (HeadsEpi structures)
+        self.tables, self.pack_descs = {}, eng._pack_descs
+        hepi = getattr(eng, "hepi", None)
+        if hepi is not None:
+            self.tables[hepi.untyped_storage().data_ptr()] = \
+                lambda: "heads_epi " + self.value((L.HeadsEpi * (hepi.numel() // C.sizeof(L.HeadsEpi))).from_buffer_copy(hepi.numpy().tobytes()))
+
+    def pointer(self, p):
+        if not p:
+            return "null"
+        if p == STREAM:
+            return "stream"
+        lo, hi = 0, len(self.owners)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if self.owners[mid][0] <= p:
+                lo = mid
+            else:
+                hi = mid
+        base, nbytes, _size, t = self.owners[lo]
+        if not (base <= p < base + max(nbytes, 1)):
+            raise RuntimeError("pointer %#x lies in no tensor the plan owns" % p)
+        if base not in self.ordinal:
+            self.ordinal[base] = len(self.ordinal)
+            whole = torch.empty(0, dtype=torch.uint8).set_(t.untyped_storage())
+            esz = t.element_size()
+            rows = whole[:whole.numel() // esz * esz].view(-1, esz)
+            if base in self.tables:
+                content = self.tables[base]()
+            elif rows.numel() and bool((rows == rows[0]).all()):
+                content = "const " + bytes(rows[0].tolist()).hex()
+            else:
+                content = hashlib.sha256(whole.numpy().tobytes()).hexdigest()
+            self.lines.append("  owner %d: shape %s %s, %d bytes, %s" % (self.ordinal[base], tuple(t.shape), t.dtype, nbytes, content))
+        return "(%d+%d)" % (self.ordinal[base], p - base)
+
+    def value(self, v, ctype=None):
+        if type(v).__name__ == "CArgObject":      # byref(x)
+            return self.value(v._obj)
+        if isinstance(v, C.Structure):
+            return "{" + ", ".join("%s=%s" % (n, self.value(getattr(v, n), ft)) for n, ft in v._fields_) + "}"
+        if isinstance(v, C.Array):
+            return "[" + ", ".join(self.value(x, v._type_) for x in v) + "]"
+        if isinstance(v, C.c_void_p):
+            return self.pointer(v.value)
+        if isinstance(v, C._SimpleCData):
+            return repr(v.value)
+        if ctype is not None and (ctype is C.c_void_p or hasattr(ctype, "contents")):
+            return self.pointer(v)
+        return repr(v)
+
+    def call(self, name, a, types):
+        if types is None or len(types) != len(a) + 1:
+            raise RuntimeError("%s: %d arguments for %s" % (name, len(a) + 1, types))
+        if name == "abc_pack_batch":
+            self.tables[a[0]] = lambda: "pack items " + " ".join(self.value(pd) for pd in self.pack_descs)
+        self.lines.append("  call %s(%s)" % (name, ", ".join(self.value(v, t) for v, t in zip(a, types))))
+
+
+def fingerprint(eng, proxy):
+    rec = Recorder(eng)
+    proxy.rec = rec
+    try:
+        for title, ops in (("pack", eng.pack_ops), ("forward", eng.fwd_ops), ("backward", eng.bwd_ops)):
+            rec.lines.append("%s: %d ops" % (title, len(ops)))
+            for op in ops:
+                rec.lines.append(" op %r writes=%r meta=%r" % (op[2], tuple(op[3]), sorted(op[4].items())))
+                n = len(rec.lines)
+                eng._run([op], STREAM)
+                if sum(ln.startswith("  call") for ln in rec.lines[n:]) != 1:
+                    raise RuntimeError("op %r made no single launch" % (op[2],))
+    finally:
+        proxy.rec = None
+    text = "\n".join(rec.lines) + "\n"
+    return hashlib.sha256(text.encode()).hexdigest(), text
+
+
+def configs():
+    big = (16, 384, 384)
+    out = [("unet bf16 train 16x384x384 fused_heads", "unet", 1, HEADS, big, "bf16", True, dict(fused_heads=True))]
+    for k in ("actbwd_epilogue", "merge_reduce", "dual_wgrad", "fused_convt"):
+        out.append(("unet bf16 train 16x384x384 fused_heads %s=False" % k, "unet", 1, HEADS, big, "bf16", True, {"fused_heads": True, k: False}))
+    out.append(("unet bf16 train 16x384x384 fused_heads=False", "unet", 1, HEADS, big, "bf16", True, dict(fused_heads=False)))
+    out.append(("unet bf16 train 16x384x384 fused_heads=False batched_heads=False", "unet", 1, HEADS, big, "bf16", True,
+                dict(fused_heads=False, batched_heads=False)))
+    out.append(("unet fp32 train 2x64x64", "unet", 1, HEADS, (2, 64, 64), "fp32", True, {}))
+    out.append(("unet fp32 train 1x72x88", "unet", 1, HEADS, (1, 72, 88), "fp32", True, {}))
+    out.append(("unet2 bf16 train 16x384x384", "unet2", 1, HEADS, big, "bf16", True, {}))
+    out.append(("unet2 fp32 train 1x72x88", "unet2", 1, HEADS, (1, 72, 88), "fp32", True, {}))
+    for variant, cin, heads, B, H, W in OTHER_HEADS:
+        for dtype in ("bf16", "fp32"):
+            for train in (True, False):
+                out.append(("%s in%d heads %s %s %s %dx%dx%d fused_heads" % (variant, cin, heads, dtype, "train" if train else "eval", B, H, W),
+                            variant, cin, heads, (B, H, W), dtype, train, dict(fused_heads=True)))
+    small = (2, 64, 64)
+    for label, kw in (("", {}), (" fold_bn", dict(fold_bn=True)), (" fold_bn nms_heads", dict(fold_bn=True, nms_heads=True)),
+                      (" fold_bn nms_heads decode", dict(fold_bn=True, nms_heads=True, decode=True)),
+                      (" fold_bn heads_epilogue", dict(fold_bn=True, heads_epilogue=True)), (" fold_bn fp8", dict(fold_bn=True, fp8=True))):
+        out.append(("unet bf16 eval 2x64x64" + label, "unet", 1, HEADS, small, "bf16", False, kw))
+    out.append(("unet2 bf16 eval 2x64x64", "unet2", 1, HEADS, small, "bf16", False, {}))
+    out.append(("unet bf16 train 2x64x64 fused_heads guards", "unet", 1, HEADS, small, "bf16", True, dict(fused_heads=True, guards=True)))
+    out.append(("unet2 fp32 train 2x64x64 guards", "unet2", 1, HEADS, small, "fp32", True, dict(guards=True)))
+    return out
+
+
+def main():
+    proxy = Proxy(L.load())
+    L._lib = proxy
+    if args.dump:
+        os.makedirs(args.dump, exist_ok=True)
+    for i, (name, variant, cin, heads, (B, H, W), dtype, train, kw) in enumerate(configs()):
+        if args.only not in name:
+            continue
+        torch.manual_seed(1234)
+        m = (UNet if variant == "unet" else UNet2)(cin, heads, dtype=dtype)
+        m._flat_grad = torch.zeros_like(m._flat.data)
+        try:
+            eng = Engine(variant, cin, heads, m._flat.data, m._flat_grad, m._flat_buf, m._counters, (m._lay_p, m._lay_b, m._lay_c), B, H, W,
+                         dtype, train, device="cpu", **kw)
+        except Exception as e:      # noqa: BLE001  (a plan that does not build without a GPU is reported, not hidden)
+            print("%-100s DOES NOT BUILD: %s: %s" % (name, type(e).__name__, str(e)[:120]), flush=True)
+            continue
+        digest, text = fingerprint(eng, proxy)
+        print("%-100s %s" % (name, digest), flush=True)
+        if args.dump:
+            with open(os.path.join(args.dump, "%02d.txt" % i), "w") as f:
+                f.write(name + "\n" + text)
+        del eng, m
+        gc.collect()
+
+
+main()
