@@ -1,6 +1,6 @@
 """Fingerprint of the launch plans the engine builds, without a GPU.
 
-    python profiles/tools/plan_fingerprint.py [--repo TREE] [--only SUBSTRING] [--dump DIR]
+    python profiles/tools/plan_fingerprint.py [--repo TREE] [--only SUBSTRING] [--dump DIR] [--routes FILE]
 
 Builds every plan of CONFIGS with Engine(..., device="cpu") and replays pack_ops, fwd_ops and bwd_ops against a proxy of the library that
 forwards the plan-time queries and, for a launch (any call whose last argument is the replay's stream), records the function name and
@@ -9,7 +9,13 @@ pointer -- argument or field -- becomes (owner ordinal, byte offset): the owner 
 order of first appearance, so that a change of allocation order does not show; at its first appearance the owner's shape, dtype and a
 hash of its contents are recorded as well.  Each op's label, `writes` and `meta` go in beside its call.  One SHA-256 per plan; --dump
 keeps the full text per plan for diffing.  Two trees build the same plans exactly when their columns of hashes agree: run this same file
-on both (--repo names the tree whose package is imported; it needs its libabcnet_hip.so)."""
+on both (--repo names the tree whose package is imported; it needs its libabcnet_hip.so).
+
+--routes FILE collects every distinct abc_wgrad_desc the plans hand to the library, query or launch, and writes them as JSON with the
+answers of that tree's library to abc_wgrad_rowsum_ok / _fuses_apply / _pads / _tile / _blocks: the fixture tests/golden/wgrad_routes.json
+(tests/test_cabi_and_host.py rebuilds the descriptors from it), a table of numbers with one row per descriptor.  Pointers are kept as
+null / non-null only; the distinct abc_wgrad_reduce_desc are counted (no query takes one)."""
+import json
 import argparse
 import ctypes as C
 import gc
@@ -21,6 +27,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--repo", default=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 ap.add_argument("--only", default="")
 ap.add_argument("--dump", default=None)
+ap.add_argument("--routes", default=None)
 args = ap.parse_args()
 sys.path.insert(0, args.repo)
 sys.path.insert(0, os.path.join(args.repo, "tests"))
@@ -41,17 +48,94 @@ class Proxy:
 
     def __init__(self, real):
         self.real, self.rec = real, None
+        self.wgrads, self.reduces = {}, set()      # (--routes) distinct descriptors seen, in order of first appearance
+
+    def note(self, v):
+        v = getattr(v, "_obj", v)      # byref(x)
+        if isinstance(v, C.Array):
+            for x in v:
+                self.note(x)
+        elif isinstance(v, L.WgradDesc):
+            f = desc_fields(v)
+            self.wgrads.setdefault(json.dumps(f, sort_keys=True), f)
+        elif isinstance(v, L.WgradReduceDesc):
+            self.reduces.add(json.dumps(desc_fields(v), sort_keys=True))
 
     def __getattr__(self, name):
         fn = getattr(self.real, name)
         types = L.SYMBOLS[name][1] if name in L.SYMBOLS else None
 
         def call(*a):
+            if args.routes:
+                for v in a:
+                    self.note(v)
             if self.rec is not None and a and a[-1] == STREAM and isinstance(a[-1], int):
                 self.rec.call(name, a[:-1], types)
                 return 0
             return fn(*a)
         return call
+
+
+def desc_fields(v, prefix=""):
+    """a descriptor as plain data, nested fields as "p.Hx": pointers as null / non-null, tap arrays up to ntaps.  What the engine fills in
+    only after it has asked (nsplit, the slab pointers) is left out: no query can depend on it"""
+    out = {}
+    for n, ft in v._fields_:
+        x = getattr(v, n)
+        if isinstance(v, L.WgradDesc) and n in ("nsplit", "partial", "rowsum_partial"):
+            continue
+        if isinstance(x, C.Structure):
+            out.update(desc_fields(x, n + "."))
+        elif isinstance(x, C.Array):
+            out[n] = list(x)[:max(0, v.ntaps)]
+        else:
+            out[prefix + n] = int(bool(x)) if ft is C.c_void_p else x
+    return out
+
+
+def desc_build(f):
+    """the inverse: a non-null pointer is a dummy address (the queries read through none of them)"""
+    v = L.WgradDesc()
+    for name, x in f.items():
+        o, n = v, name
+        if "." in name:
+            o, n = getattr(v, name.split(".")[0]), name.split(".")[1]
+        if isinstance(x, list):
+            for i, t in enumerate(x):
+                getattr(o, n)[i] = t
+        elif dict(o._fields_)[n] is C.c_void_p:
+            setattr(o, n, 0x1000 if x else None)
+        else:
+            setattr(o, n, x)
+    return v
+
+
+ANSWERS = ("rowsum_ok", "fuses_apply", "pads_rc", "ca_pad", "cb_pad", "tile_rc", "at", "bt", "blocks")
+
+
+def answers(lib, d):
+    ca, cb, at, bt = C.c_int32(-7), C.c_int32(-7), C.c_int32(-7), C.c_int32(-7)
+    rp, rt = lib.abc_wgrad_pads(C.byref(d), C.byref(ca), C.byref(cb)), lib.abc_wgrad_tile(C.byref(d), C.byref(at), C.byref(bt))
+    return [lib.abc_wgrad_rowsum_ok(C.byref(d)), lib.abc_wgrad_fuses_apply(C.byref(d)), rp, ca.value, cb.value, rt, at.value, bt.value,
+            lib.abc_wgrad_blocks(C.byref(d))]
+
+
+def routes_table(lib, descs):
+    """the fixture: one row of numbers per descriptor -- its own fields in `columns` order, where "p", "q" and "taps" are indices into the
+    tables of distinct operands (fields in `operand` order) and tap lists -- then ANSWERS"""
+    names = [n for n in descs[0] if n not in ("tap_dy", "tap_dx") and any(f[n] for f in descs)]      # (zero everywhere: left out)
+    opnd = sorted({n[2:] for n in names if "." in n}, key=[n for n, _t in L.ActSrc._fields_].index)
+    cols = [n for n in names if "." not in n]
+    tabs, rows = {"p": [], "q": [], "taps": []}, []
+
+    def index(tab, x):
+        if x not in tab:
+            tab.append(x)
+        return tab.index(x)
+    for f in descs:
+        rows.append([index(tabs[o], [f[o + "." + n] for n in opnd]) for o in "pq"] + [f[n] for n in cols] +
+                    [index(tabs["taps"], [f["tap_dy"], f["tap_dx"]])] + answers(lib, desc_build(f)))
+    return dict(tabs, columns=["p", "q"] + cols + ["taps"] + list(ANSWERS), operand=opnd, rows=rows)
 
 
 def tensors_of(x, depth=0):
@@ -214,6 +298,14 @@ def main():
                 f.write(name + "\n" + text)
         del eng, m
         gc.collect()
+    if args.routes:
+        tab = routes_table(proxy.real, list(proxy.wgrads.values()))
+        rows = tab.pop("rows")
+        enc = lambda x: json.dumps(x, separators=(",", ":"))      # noqa: E731
+        with open(args.routes, "w") as f:
+            f.write("{" + "".join('"%s":%s,\n' % (k, enc(tab[k])) for k in ("columns", "operand", "p", "q", "taps")) + '"rows":[\n')
+            f.write(",\n".join(",".join(enc(r) for r in rows[i:i + 8]) for i in range(0, len(rows), 8)) + "\n]}\n")
+        print("%d distinct abc_wgrad_desc, %d distinct abc_wgrad_reduce_desc" % (len(rows), len(proxy.reduces)), file=sys.stderr)
 
 
 main()

@@ -606,3 +606,39 @@ def test_inference_runner_extract_and_trainer_refuse_other_head_lists():
         for fused in (True, False):
             with pytest.raises(ValueError, match=r"Trainer.*heads \[%s\]" % ", ".join(map(str, heads))):
                 Trainer(UNet(cin, heads, dtype="bf16"), 2, 64, 64, fused_heads=fused)
+
+
+def test_wgrad_routes_match_the_recorded_answers(golden_dir):
+    """every distinct abc_wgrad_desc the 44 plans of profiles/tools/plan_fingerprint.py hand to the library gets the recorded answer from
+    all five routing queries: which kernel family serves it, its slab extents, its workgroups per split, whether it applies the
+    BatchNorm-backward correction on load and whether it writes row sums.  tests/golden/wgrad_routes.json (written by that tool's
+    --routes) is a table: a row holds a descriptor's fields in `columns` order (pointers as 0 / 1; fields that are zero in every row,
+    and nsplit and the slab pointers, which the engine sets from the answers, left out), where "p", "q" and "taps" are indices into
+    the tables of distinct operands (fields in `operand` order) and tap lists, and then the nine answers"""
+    import ctypes as C
+    import json
+    with open(os.path.join(golden_dir, "wgrad_routes.json")) as f:
+        tab = json.load(f)
+    cols, lib = tab["columns"], L.load()
+    nf = cols.index("taps")
+    assert cols[:2] == ["p", "q"] and cols[nf + 1:] == ["rowsum_ok", "fuses_apply", "pads_rc", "ca_pad", "cb_pad", "tile_rc", "at", "bt", "blocks"]
+    assert len(tab["rows"]) > 600
+    tiles = set()
+    for row in tab["rows"]:
+        d = L.WgradDesc()
+        fields = [(d, n, x) for n, x in zip(cols[2:nf], row[2:])]
+        fields += [(getattr(d, o), n, x) for o, i in zip("pq", row) for n, x in zip(tab["operand"], tab[o][i])]
+        for o, n, x in fields:
+            if dict(o._fields_)[n] is C.c_void_p:
+                x = 0x1000 if x else None      # (non-null: the queries read through no pointer)
+            setattr(o, n, x)
+        for i, (dy, dx) in enumerate(zip(*tab["taps"][row[nf]])):
+            d.tap_dy[i], d.tap_dx[i] = dy, dx
+        ca, cb, at, bt = C.c_int32(-7), C.c_int32(-7), C.c_int32(-7), C.c_int32(-7)
+        rp, rt = lib.abc_wgrad_pads(C.byref(d), C.byref(ca), C.byref(cb)), lib.abc_wgrad_tile(C.byref(d), C.byref(at), C.byref(bt))
+        got = [lib.abc_wgrad_rowsum_ok(C.byref(d)), lib.abc_wgrad_fuses_apply(C.byref(d)), rp, ca.value, cb.value, rt, at.value, bt.value,
+               lib.abc_wgrad_blocks(C.byref(d))]
+        assert got == row[nf + 1:], dict(zip(cols, row))
+        tiles.add((at.value, bt.value))
+    # the fixture reaches every family: head, one-channel, 16-channel, 5x5 32-channel, and each tile shape of the general kernel
+    assert tiles >= {(0, 0), (0, 1), (0, 2), (0, 3), (1, 1), (2, 1), (2, 2), (1, 4), (4, 2)}

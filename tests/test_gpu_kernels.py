@@ -411,6 +411,91 @@ def test_wgrad_fused_bn_apply(lib, Cout, Cin, k, qt):
     assert U.relerr(dw.cpu().view(Cout, Cin, k, k), w.grad) < U.tol(dt)
 
 
+def _wgrad_3x3(lib, p, pcoef, xd, qcoef, B, H, W, Ca, Cb, nsplit, tile, dual=None):
+    """one bf16 3x3 stride-1 weight gradient through abc_wgrad + abc_wgrad_reduce, run twice (bitwise reproducible), after holding
+    abc_wgrad_tile to `tile`; dual = (y_raw, ld, channel offset, p_out): the BatchNorm-backward correction on load of P"""
+    dt = L.BF16
+    d = L.WgradDesc()
+    U.fill_src(d.p, p, H, W, Ca, pcoef)
+    U.fill_src(d.q, xd, H, W, Cb, qcoef)
+    d.dtype_p, d.dtype_q, d.dtype_c = dt, dt, dt
+    d.B, d.Hg, d.Wg, d.Hq, d.Wq, d.Ca, d.Cb, d.stride, d.nsplit = B, H, W, H, W, Ca, Cb, 1, nsplit
+    L.set_taps(d, taps_square(3))
+    if dual is not None:
+        d.p2, d.ld_p2, d.cp2_off, d.p_dual, d.p_out, d.ld_pout = dual[0].data_ptr(), dual[1], dual[2], 1, dual[3].data_ptr(), Ca
+        assert lib.abc_wgrad_fuses_apply(C.byref(d)) == 1
+    at_, bt_, ca_, cb_ = L.i32(), L.i32(), L.i32(), L.i32()
+    L.check(lib.abc_wgrad_tile(C.byref(d), C.byref(at_), C.byref(bt_)), "tile")
+    assert (at_.value, bt_.value) == tile
+    L.check(lib.abc_wgrad_pads(C.byref(d), C.byref(ca_), C.byref(cb_)), "pads")
+    outs = []
+    for _ in range(2):
+        part = torch.zeros(nsplit * 9 * ca_.value * cb_.value, dtype=torch.float32, device=U.DEV)
+        d.partial = part.data_ptr()
+        L.check(lib.abc_wgrad(C.byref(d), U.stream()), "wgrad")
+        dw = torch.zeros((Ca, Cb, 9), dtype=torch.float32, device=U.DEV)
+        r = L.WgradReduceDesc()
+        r.partial, r.nsplit, r.ntaps, r.Ca, r.Cb, r.Ca_pad, r.Cb_pad, r.dw, r.accumulate = part.data_ptr(), nsplit, 9, Ca, Cb, ca_.value, cb_.value, dw.data_ptr(), 0
+        L.check(lib.abc_wgrad_reduce(C.byref(r), U.stream()), "reduce")
+        torch.cuda.synchronize()
+        outs.append(dw.cpu().view(Ca, Cb, 3, 3))
+    assert torch.equal(outs[0], outs[1])
+    return outs[0]
+
+
+_SEGTAB_REF = {}
+
+
+def _segtab_case(Ca, Cb, B, H, W):
+    """operands and torch's weight gradient of one 3x3 case, computed once: dY = ca * g + cb * y_raw + cc (so that the same reference
+    serves the plain launch, P = dY, and the one that applies the correction on load), X activated on load"""
+    key = (Ca, Cb, B, H, W)
+    if key not in _SEGTAB_REF:
+        dt = L.BF16
+        g_ = torch.Generator().manual_seed(61)
+        ldy, coff = Ca + 32, 16
+        gq = q(torch.randn((B, Ca, H, W), generator=g_), dt)
+        yq = q(torch.randn((B, ldy, H, W), generator=g_), dt)
+        ca, cb, cc = (torch.randn(Ca, generator=g_) * s_ for s_ in (1.0, 0.3, 0.05))
+        dy = q(ca.view(1, -1, 1, 1) * gq + cb.view(1, -1, 1, 1) * yq[:, coff:coff + Ca] + cc.view(1, -1, 1, 1), dt)
+        x = q(torch.randn((B, Cb, H, W), generator=g_), dt)
+        sc, sh = torch.rand(Cb, generator=g_) * 2 - 0.6, torch.randn(Cb, generator=g_) * 0.3
+        sl = torch.tensor([0.0, 0.01, 1.0])[torch.randint(0, 3, (Cb,), generator=g_)]
+        w = torch.zeros((Ca, Cb, 3, 3), requires_grad=True)
+        F.conv2d(q(act(x, sc, sh, sl), dt), w, None, padding=1).backward(dy)
+        _SEGTAB_REF[key] = dict(gq=gq, yq=yq, dy=dy, x=x, pcoef=(ca, cc, cb), qcoef=(sc, sh, sl), ldy=ldy, coff=coff, ref=w.grad.clone())
+    return _SEGTAB_REF[key]
+
+
+@pytest.mark.parametrize("H,nsplit", [(24, 2), (24, 3), (20, 2), (20, 3)])
+def test_wgrad_segment_table_2x2(lib, H, nsplit):
+    """the 2 x 2-pair bf16 3x3 weight gradient with Q's segment table in LDS (HaloFetch::table_setup / prepare_tab: whole 8 x 16 patches of a
+    same-size image, stride 1): B = 1 at 24 x 48 is 3 x 3 patches, the interior one and every border kind of the table's `border` mask.
+    H = 20 is the same layer with a ragged last patch row: the table is ineligible and the general prepare runs"""
+    Ca, Cb, B, W, dt = 64, 64, 1, 48, L.BF16
+    c = _segtab_case(Ca, Cb, B, H, W)
+    qcoef = tuple(t.to(U.DEV) for t in c["qcoef"])
+    dw = _wgrad_3x3(lib, U.nhwc(c["dy"], dt), None, U.nhwc(c["x"], dt), qcoef, B, H, W, Ca, Cb, nsplit, (2, 2))
+    assert U.relerr(dw, c["ref"]) < U.tol(dt)
+
+
+def test_wgrad_segment_table_4x2(lib):
+    """the 4 x 2-pair form with Q's segment table, plain and with the BatchNorm-backward correction on load of P.  wgeom takes 4 x 2 pairs
+    when patches >= 6 * min(patches / 2, 256 / tiles42): Ca = 512, Cb = 256 is tiles42 = 16, and B = 1 at 64 x 192 (96 patches) the
+    smallest map that qualifies"""
+    Ca, Cb, B, H, W, dt, nsplit = 512, 256, 1, 64, 192, L.BF16, 5
+    c = _segtab_case(Ca, Cb, B, H, W)
+    xd = U.nhwc(c["x"], dt)
+    qcoef = tuple(t.to(U.DEV) for t in c["qcoef"])
+    dw = _wgrad_3x3(lib, U.nhwc(c["dy"], dt), None, xd, qcoef, B, H, W, Ca, Cb, nsplit, (4, 2))
+    assert U.relerr(dw, c["ref"]) < U.tol(dt)
+    out = torch.zeros((B, H, W, Ca), dtype=U.tdt(dt), device=U.DEV)
+    pcoef = tuple(t.to(U.DEV) for t in c["pcoef"])
+    dw = _wgrad_3x3(lib, U.nhwc(c["gq"], dt), pcoef, xd, qcoef, B, H, W, Ca, Cb, nsplit, (4, 2), dual=(U.nhwc(c["yq"], dt), c["ldy"], c["coff"], out))
+    assert U.relerr(U.to_nchw(out), c["dy"]) < 1e-2           # bf16 rounding of the same f32 formula
+    assert U.relerr(dw, c["ref"]) < U.tol(dt)
+
+
 @pytest.mark.parametrize("k,Cout,W,nsplit", [(3, 16, 72, 7), (5, 32, 72, 7), (3, 16, 70, 5), (5, 32, 40, 3), (5, 8, 64, 11), (3, 32, 384, 9)])
 def test_wgrad_one_channel_fused_bn_apply(lib, k, Cout, W, nsplit):
     """the first convolution's weight gradient (unet.py:12 with one input channel: the plain-FMA kernel) with p_dual: the
