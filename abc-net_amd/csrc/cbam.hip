@@ -93,16 +93,18 @@ __global__ __launch_bounds__(1024) void cbam_channel_fwd_kernel(const abc_cbam_c
         }
         __syncthreads();
     }
-    // hidden unit j: 256 / mid lanes share the dot products (mid <= 32 is a power of two)
+    // hidden unit j: min(256 / mid, 64) lanes of ONE wave share the dot products (mid <= 32 is a power of two)
     {
-        // (the first 256 threads, as when the workgroup had no more)
-        const int per = 256 / d.mid;                  // lanes per hidden unit (>= 8)
+        // (the first 256 threads, as when the workgroup had no more; the xor tree below stays inside a wave, so a unit spans at most
+        //  64 lanes, and lanes whose unit index is past mid sit out)
+        const int per = 256 / d.mid < 64 ? 256 / d.mid : 64;   // lanes per hidden unit (>= 8)
         const int j = (threadIdx.x & 255) / per, sub = (threadIdx.x & 255) % per;
+        const bool on = threadIdx.x < 256 && j < d.mid;
         float sa = 0.f, sb = 0.f;
-        if (threadIdx.x < 256)
+        if (on)
             for (int c = sub; c < d.C; c += per) { const float w = d.w1[(size_t)j * d.C + c]; sa += w * av[c]; sb += w * mx[c]; }
-        for (int o = 1; o < per && o < 64; o <<= 1) { sa += __shfl_xor(sa, o); sb += __shfl_xor(sb, o); }
-        if (sub == 0 && threadIdx.x < 256) {
+        for (int o = 1; o < per; o <<= 1) { sa += __shfl_xor(sa, o); sb += __shfl_xor(sb, o); }
+        if (sub == 0 && on) {
             sa = fmaxf(sa + d.b1[j], 0.f); sb = fmaxf(sb + d.b1[j], 0.f);
             ha[j] = sa; hm[j] = sb;
             d.hid_avg[(size_t)n * d.mid + j] = sa;

@@ -48,9 +48,10 @@ def pack(lib, w, mode, dt, Cout, Cin, k, rows_pad, red_real, py=0, px=0):
 
 def conv(lib, x, dt_in, dt, B, Hx, Wx, ldx, cin_off, Cin, wp, bias, Cout, taps, Hout, Wout, ldy=None, cout_off=0, coef=None,
          pool=False, stride=1, grid=None, om=1, oy0=0, ox0=0, out=None, out_dt=None, stats=False, drop_p=0.0, drop_seed=0,
-         planar_in=0, planar_out=False, out_slope=None, pool_out=None, stem=None, actbwd=None, defer=None, ctot_out=None):
+         planar_in=0, planar_out=False, out_slope=None, pool_out=None, stem=None, actbwd=None, defer=None, ctot_out=None, stats_rows=2):
     """actbwd: (y_raw, ld, coff, scale, shift, slope, mean, invstd) -> abc_conv_desc.actbwd_*; conv.last_actbwd_ok tells whether the
-    library honoured it (else the plain convolution ran)"""
+    library honoured it (else the plain convolution ran).  stats_rows: 2 (sum, sum of squares per row of the statistics buffer) or 4
+    (+ max, min of the values as stored, per image and per tile: what unet2's CBAM reads)"""
     out_dt = dt if out_dt is None else out_dt
     ldy = Cout if ldy is None else ldy
     ctot_out = Cout if ctot_out is None else ctot_out      # (planar output: [B][ctot_out][Hout][Wout], channels cout_off ..)
@@ -74,6 +75,8 @@ def conv(lib, x, dt_in, dt, B, Hx, Wx, ldx, cin_off, Cin, wp, bias, Cout, taps, 
     if stem is not None:   # (image, first-layer weights, scale, bias, slope): device f32 tensors
         d.stem_x, d.stem_w, d.stem_scale, d.stem_bias, d.stem_slope = stem[0].data_ptr(), stem[1].data_ptr(), stem[2].data_ptr(), stem[3].data_ptr(), stem[4]
     L.set_taps(d, taps)
+    if stats:
+        d.stats_rows = stats_rows      # (before the queries below: the variant and the row count depend on it)
     conv.last_actbwd_ok = False
     if actbwd is not None:
         yr, ld_y, coff, sc, sh, sl, mu, istd = actbwd
@@ -95,7 +98,7 @@ def conv(lib, x, dt_in, dt, B, Hx, Wx, ldx, cin_off, Cin, wp, bias, Cout, taps, 
     st = None
     if stats:
         nblk = lib.abc_conv_stat_blocks(C.byref(d))
-        st = torch.zeros((nblk, 2, Cout), dtype=torch.float32, device=DEV)
+        st = torch.zeros((nblk, stats_rows, Cout), dtype=torch.float32, device=DEV)
         d.stats = st.data_ptr()
     if defer is not None:
         defer.append((d, wp, st))      # (the launch is the caller's: abc_conv_fwd_batch over several descriptors)

@@ -183,6 +183,81 @@ def test_conv_narrow_plain_input(lib, case):
         assert (rest == 7.0).all()
 
 
+# the kernel that serves each case (abc_conv_variant: 0 conv_igemm, 1 the lean kernel of conv_fast, 5 conv_narrow), per dtype (f32, bf16),
+# and the rows per image it writes: one per tile of 16 columns x 4 rows (64 / 128 output channels on the lean kernel), x 8 rows
+# (32 output channels; conv_igemm here), x 16 rows (the lean kernel's 5x5); conv_n32r2 one per workgroup, eight 4 x 16 tiles each
+STAT4_CASES = [
+    dict(Cin=64, Cout=64, k=3, H=24, W=48, coef=True, variant=(1, 1), tiles=(18, 18)),       # lean kernel, whole 4 x 16 tiles
+    dict(Cin=64, Cout=128, k=3, H=20, W=32, coef=True, variant=(1, 1), tiles=(10, 10)),      # ... two blocks of output channels
+    dict(Cin=64, Cout=64, k=3, H=24, W=40, coef=True, variant=(1, 1), tiles=(18, 18)),       # its general epilogue: ragged W
+    dict(Cin=64, Cout=128, k=3, H=20, W=36, coef=True, variant=(1, 1), tiles=(15, 15)),
+    dict(Cin=128, Cout=32, k=3, H=22, W=42, coef=True, variant=(1, 1), tiles=(9, 9)),      # ... ragged rows (8-row tiles) and ragged W
+    dict(Cin=32, Cout=64, k=3, H=22, W=42, pool=True, variant=(0, 0), tiles=(9, 9)),       # conv_igemm: pooled input (from 44 x 84)
+    dict(Cin=32, Cout=32, k=5, H=20, W=48, coef=True, variant=(1, 5), tiles=(6, 2)),       # bf16: the 5x5 32 -> 32 kernel of conv_narrow (n32r2)
+    dict(Cin=32, Cout=32, k=5, H=20, W=48, variant=(1, 5), tiles=(6, 2)),
+]
+
+
+def test_four_row_cases_reach_every_family():
+    assert {c["variant"][i] for c in STAT4_CASES for i in (0, 1)} == {0, 1, 5}
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("case", STAT4_CASES)
+def test_conv_four_row_statistics(lib, dt, case):
+    """stats_rows = 4 (what unet2's CBAM reads: per image and per tile, rows 2 / 3 = max / min of the values AS STORED) in the three
+    kernel families that serve it.  The three images get disjoint output ranges (positive weights, inputs 16x apart), so a row that
+    mixed two images shows; max / min over an image's rows are bit-equal to the max / min of that image in the kernel's own output."""
+    g = torch.Generator().manual_seed(17)
+    B, Cin, Cout, k, H, W = 3, case["Cin"], case["Cout"], case["k"], case["H"], case["W"]
+    pool = case.get("pool", False)
+    Hx, Wx = (2 * H, 2 * W) if pool else (H, W)
+    amp = torch.tensor([1 / 64, 1 / 4, 4.0]).view(B, 1, 1, 1)
+    x = q(amp * (1 + 0.25 * torch.rand((B, Cin, Hx, Wx), generator=g)), dt)
+    w = (0.75 + 0.25 * torch.rand((Cout, Cin, k, k), generator=g)) / (Cin * k * k)
+    b = torch.rand(Cout, generator=g) * 0.01
+    coef, xin = None, x
+    if case.get("coef") or pool:
+        sc = 0.9 + 0.2 * torch.rand(Cin, generator=g)
+        sh = torch.rand(Cin, generator=g) * 0.001
+        sl = torch.tensor([0.0, 0.01, 1.0])[torch.randint(0, 3, (Cin,), generator=g)]
+        coef = tuple(t.to(U.DEV) for t in (sc, sh, sl))
+        xin = act(x, sc, sh, sl)
+    if pool:
+        xin = F.max_pool2d(xin, 2)
+    ref = F.conv2d(q(xin, dt).double(), q(w, dt).double(), b.double(), padding=(k - 1) // 2)
+    lo, hi = ref.amin((2, 3)), ref.amax((2, 3))                       # [B][Cout]
+    assert (hi[:-1] * 2 < lo[1:]).all(), "the images' output ranges are not disjoint"
+    xd = x.permute(0, 2, 3, 1).contiguous().to(U.tdt(dt)).to(U.DEV)
+    wp = U.pack(lib, w.to(U.DEV), 0, dt, Cout, Cin, k, -(-Cout // 32) * 32, Cin)
+    y, st = U.conv(lib, xd, dt, dt, B, Hx, Wx, Cin, 0, Cin, wp, b.to(U.DEV), Cout, taps_square(k), H, W, coef=coef, pool=pool, stats=True,
+                   stats_rows=4)
+    torch.cuda.synchronize()
+    assert U.conv.last_variant == case["variant"][0 if dt == L.F32 else 1], U.conv.last_variant
+    got = U.to_nchw(y)
+    assert U.relerr(got, ref) < U.tol(dt), U.relerr(got, ref)
+    # rows: B * tiles_per_img of them, an image's rows together
+    nblk = st.shape[0]
+    tpi = case["tiles"][0 if dt == L.F32 else 1]
+    assert st.shape == (B * tpi, 4, Cout), (nblk, B * tpi)
+    rows = st.cpu().view(B, tpi, 4, Cout)
+    assert (rows[:, :, 2] > 0).all() and (rows[:, :, 0] > 0).all() and (rows[:, :, 1] > 0).all(), "a row was never written (outputs are positive)"
+    eps = U.tol(dt) * hi
+    assert (rows[:, :, 2] <= (hi + eps)[:, None]).all() and (rows[:, :, 3] >= (lo - eps)[:, None]).all(), "a row holds values of another image"
+    # max / min of the stored tensor, bit for bit
+    assert torch.equal(rows[:, :, 2].amax(1), got.amax((2, 3)))
+    assert torch.equal(rows[:, :, 3].amin(1), got.amin((2, 3)))
+    # per image, rows 0 / 1 are that image's sums ...
+    n1 = H * W
+    np.testing.assert_allclose(rows[:, :, 0].double().sum(1) / n1, ref.mean((2, 3)), rtol=U.tol(dt, 1e-4, 2e-2))
+    np.testing.assert_allclose(rows[:, :, 1].double().sum(1) / n1, (ref ** 2).mean((2, 3)), rtol=U.tol(dt, 1e-4, 3e-2))
+    # ... and over all rows the bounds of test_conv_forward
+    s = st.double().sum(0).cpu()
+    n = B * H * W
+    np.testing.assert_allclose(s[0] / n, ref.mean((0, 2, 3)), atol=U.tol(dt, 1e-4, 2e-2))
+    np.testing.assert_allclose(s[1] / n, (ref ** 2).mean((0, 2, 3)), rtol=U.tol(dt, 1e-4, 3e-2), atol=1e-4)
+
+
 HEAD_WIDTHS = [14, 60, 1, 360, 2, 3, 4, 5, 20, 21, 30, 33, 90]     # every head width of the reference's lists (33: Cout_pad = 64)
 
 
