@@ -191,6 +191,14 @@ class AssembleDesc(C.Structure):
                 ("work", vp)]
 
 
+class EvalDesc(C.Structure):
+    _fields_ = [("atom_mask", vp), ("bond_mask", vp), ("omega_mask", vp), ("rho_abs", vp), ("types", vp), ("charges", vp), ("hs", vp),
+                ("btypes", vp), ("btype_idx", vp), ("t_atom", vp), ("t_types", vp), ("t_charges", vp), ("t_hs", vp), ("t_bond", vp),
+                ("t_btypes", vp), ("t_rho", vp), ("t_omega", vp), ("n_valid", vp), ("B", i32), ("h", i32), ("w", i32), ("partial", vp),
+                ("counts_last", vp), ("counts_totals", vp), ("meters_last", vp), ("meters_totals", vp)]
+
+
+EVAL_NCOUNT = 301   # ABC_EVAL_NCOUNT
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
 MOL_EMPTY, MOL_TRUNCATED = 1, 2     # abc_mol_status
@@ -268,6 +276,9 @@ SYMBOLS = {
     "abc_build_images": (C.c_int, [P(ImageDesc), vp]),
     "abc_metrics_blocks": (C.c_int, [P(MetricsDesc)]),
     "abc_metrics_update": (C.c_int, [P(MetricsDesc), vp]),
+    "abc_eval_tables_blocks": (C.c_int, [P(EvalDesc)]),
+    "abc_eval_tables_update": (C.c_int, [P(EvalDesc), vp]),
+    "abc_eval_desc_size": (C.c_int, []),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "abc_plane_sum_work": (C.c_int, [i32]),
     "abc_cbam_channel_fwd": (C.c_int, [P(CbamChannelDesc), vp]),
@@ -336,6 +347,9 @@ def load():
         n = lib.abc_sizeof(i)
         if n != C.sizeof(st):
             raise AbcNetHipError("struct #%d (%s): binding has %d bytes, library %d" % (i, st.__name__, C.sizeof(st), n))
+    # (abc_eval_desc is not in abc_sizeof's list: it reports its own size)
+    if lib.abc_eval_desc_size() != C.sizeof(EvalDesc):
+        raise AbcNetHipError("struct EvalDesc: binding has %d bytes, library %d" % (C.sizeof(EvalDesc), lib.abc_eval_desc_size()))
     _lib = lib
     return lib
 

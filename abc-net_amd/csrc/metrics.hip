@@ -16,11 +16,12 @@
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
+#include "meter_sums.hpp"
 
 namespace {
 
 constexpr float LO = 1e-5f, HI = 1.f - 1e-5f;
-constexpr int NSUM = 24;
+constexpr int NSUM = ABC_METER_NSUM;
 
 __device__ inline float act_sig(float z) { return fminf(fmaxf(1.f / (1.f + expf(-z)), LO), HI); }
 
@@ -58,17 +59,6 @@ __device__ inline void class_acc(const float* z, const float* t, double* num, do
     }
     *den += (double)st;
     if (at == az) *num += (double)st;
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ inline unsigned long long circ3(unsigned long long m) {  // 60-bit circular dilation by one bin either way
-    const unsigned long long M60 = (1ull << 60) - 1;
-    return (m | ((m << 1) & M60) | (m >> 59) | (m >> 1) | ((m & 1ull) << 59)) & M60;
 }
 
 __global__ __launch_bounds__(256) void metrics_sums_kernel(const abc_metrics_desc d) {
@@ -145,14 +135,14 @@ __global__ __launch_bounds__(256) void metrics_sums_kernel(const abc_metrics_des
 #undef PL
         s[19] = (double)__popcll(tom & temp);
         s[20] = (double)__popcll(temp);
-        s[21] = (double)__popcll(tom & circ3(temp));
+        s[21] = (double)__popcll(tom & abc_circ3(temp));
         s[22] = (double)__popcll(tom);
-        s[23] = (double)__popcll(circ3(tom) & temp);
+        s[23] = (double)__popcll(abc_circ3(tom) & temp);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < NSUM; ++i) {
-        const double a = wave_sum(s[i]);
+        const double a = abc_wave_sum(s[i]);
         if (lane == 0) sm[wave][i] = a;
     }
     __syncthreads();
@@ -178,11 +168,8 @@ __global__ __launch_bounds__(1024) void metrics_finalize_kernel(const abc_metric
     }
     __syncthreads();
     if (t < 17) {
-        // meter -> (numerator slot, denominator slot); order = METER_NAMES of oracle/metrics_oracle.py
-        const int ni[17] = {0, 1, 0, 3, 10, 12, 14, 5, 6, 5, 8, 16, 18, 19, 21, 19, 23};
-        const int di[17] = {2, 2, 4, 4, 11, 13, 15, 7, 7, 9, 9, 17, 17, 20, 22, 22, 20};
-        const double num = tot[ni[t]];
-        const double den = tot[di[t]] + (t == 6 ? 0.01 : 0.0);   // atom_hs: 0.01 + sum (train.py:171-172)
+        const double num = tot[abc_meter_num_slot(t)];
+        const double den = tot[abc_meter_den_slot(t)] + (t == 6 ? 0.01 : 0.0);   // atom_hs: 0.01 + sum (train.py:171-172)
         d.last[2 * t] = num; d.last[2 * t + 1] = den;
         d.totals[2 * t] += num; d.totals[2 * t + 1] += den;
     }

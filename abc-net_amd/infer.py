@@ -9,6 +9,10 @@ steps, so re-packing them and deriving the eval-mode BatchNorm coefficients happ
 call it again after `load_state_dict`.  The step ends with the four mask / |rho| maps the decoder reads; opt-in, the candidate
 lists (extract=True, img2smiles2.py:113-191) and the assembled molecules (assemble=True, :193-311) in the same graph.  RDKit
 (generate_smiles.py:115-119) is out of scope.
+
+evaluate=True makes the step the loop body of the reference's src/test_accuracy.py:94-269 as well: the targets of the batch sit in
+static device buffers and one more launch sequence after the NMS (ops.EvalTables) adds the batch to the per-class tables and the 17
+inference-flavour meters; evaluation() reads them.
 """
 from __future__ import annotations
 
@@ -22,7 +26,7 @@ from . import _lib as L
 class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
-                 assemble=False, cap_mol_bonds=None):
+                 assemble=False, cap_mol_bonds=None, evaluate=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -38,7 +42,11 @@ class InferenceRunner:
         per batch of 64 at 512 x 512
         assemble (implies extract): the graph assembly of img2smiles2.py:193-311 (ops.GraphAssembler) on the candidate lists, in the same
         captured graph after the extractor; molecules() returns the result.  It reads the lists, not the maps: the same with
-        decode=True and fp8=True"""
+        decode=True and fp8=True
+        evaluate: the evaluation tables of test_accuracy.py:105-298 (ops.EvalTables) in the same captured graph after the NMS, from the
+        masks, |rho|, the atom heads and the bond-type maps (decode: their arg-max map) against .eval_targets, the static target
+        buffers load_batch(imgs, targets, n_valid) fills; only the first .n_valid images count (a device int32, so a replayed graph
+        evaluates a short last batch); evaluation() / reset_evaluation()"""
         extract = bool(extract) or bool(assemble)
         from .ops import EXTRACT_HEADS, check_nms_heads
         check_nms_heads(model.heads, "InferenceRunner")
@@ -97,6 +105,19 @@ class InferenceRunner:
             from .ops import GraphAssembler
             with torch.cuda.device(dev):
                 self.assembler = GraphAssembler.from_extractor(self.extractor, cap_mol_bonds=cap_mol_bonds)
+        self.evaluator = None
+        if evaluate:
+            from .ops import EvalTables
+            if list(model.heads) != EXTRACT_HEADS:
+                raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (EXTRACT_HEADS, list(model.heads)))
+            B, h, w = eng.B, eng.h, eng.w
+            shapes = [(B, 1), (B, 14), (B, 3), (B, 2), (B, 1), (B, 6, 60), (B, 60), (B, 60)]
+            with torch.cuda.device(dev):
+                self.eval_targets = [torch.zeros(s + (h, w), dtype=torch.float64 if i >= 6 else torch.float32, device=dev)
+                                     for i, s in enumerate(shapes)]
+                self.n_valid = torch.full((1,), B, dtype=torch.int32, device=dev)
+                self.evaluator = EvalTables(self.atom_mask, self.bond_mask, self.omega_mask, self.rho_abs, lg, self.eval_targets,
+                                            btype_idx=self.btype_idx if self.decode else None, n_valid=self.n_valid)
         self.use_graph = use_graph
         self._graph = None
         self.steps = 0
@@ -108,8 +129,17 @@ class InferenceRunner:
         with torch.cuda.device(self.dev):
             self.eng.run_pack(torch.cuda.current_stream().cuda_stream)
 
-    def load_batch(self, imgs):
+    def load_batch(self, imgs, targets=None, n_valid=None):
+        """targets (evaluate=True): the 8 target maps of the batch, copied into .eval_targets; n_valid: how many of its images count
+        (default: all; rows past it may hold anything)"""
         self.eng.img.copy_(imgs.reshape(self.eng.img.shape), non_blocking=True)
+        if targets is not None or n_valid is not None:
+            if self.evaluator is None:
+                raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
+            if targets is not None:
+                for dst, t in zip(self.eval_targets, targets):
+                    dst.copy_(t.reshape(dst.shape), non_blocking=True)
+            self.n_valid.fill_(self.eng.B if n_valid is None else int(n_valid))
         if self.fp8 and not self.eng.fp8_calibrated:
             self.calibrate()
 
@@ -140,6 +170,19 @@ class InferenceRunner:
             self.extractor.run(st)
         if self.assembler is not None:
             self.assembler.run(st)
+        if self.evaluator is not None:
+            self.evaluator.run(st)
+
+    def evaluation(self):
+        """the tables and meters accumulated since the last reset_evaluation() (ops.EvalTables.result(); host sync; needs evaluate=True)"""
+        if self.evaluator is None:
+            raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
+        return self.evaluator.result()
+
+    def reset_evaluation(self):
+        if self.evaluator is None:
+            raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
+        self.evaluator.reset()
 
     def candidates(self):
         """the per-image atom / bond candidate lists of the last step (host sync; needs extract=True)"""

@@ -176,6 +176,122 @@ class FusedMetrics:
         return out
 
 
+EVAL_TABLES = ["atom_detection", "atom_type", "atom_charge", "bond_detection", "bond_type"]   # test_accuracy.py:33-38
+
+
+def eval_tables_from_counts(counts):
+    """the 301 counts of abc_eval_desc (any integer array) -> the five float64 [n, 4] tables of test_accuracy.py:33-38
+    (columns tp, tn, fp, fn; the detection tables never write tn) and the three confusion matrices C[target][predicted]"""
+    import numpy as np
+    c = np.asarray(counts).astype(np.float64)
+    out, conf = {}, {}
+    for name, off, n in (("atom_detection", 0, 14), ("bond_detection", 42, 6)):
+        d = c[off:off + 3 * n].reshape(n, 3)
+        out[name] = np.stack([d[:, 0], np.zeros(n), d[:, 1], d[:, 2]], axis=1)
+    for name, off, n in (("atom_type", 60, 14), ("atom_charge", 256, 3), ("bond_type", 265, 6)):
+        m = c[off:off + n * n].reshape(n, n)
+        tp, row, col = np.diag(m), m.sum(1), m.sum(0)
+        out[name] = np.stack([tp, m.sum() - row - col + tp, col - tp, row - tp], axis=1)
+        conf[name] = m
+    return out, conf
+
+
+class EvalTables:
+    """The per-class tables and the 17 inference-flavour meters of test_accuracy.py:105-298 as one device-resident table
+    (csrc/eval_tables.hip).  Inputs are what an inference step leaves on the device -- the masks and |rho| of nms_peaks /
+    InferenceRunner, the 8 head maps (decode mode: logits[5] / logits[6] may be None, the bond type then comes from
+    `btype_idx`) -- and the 8 target maps of the loss.  `run` adds the current batch, `result` reads (the only host sync),
+    `reset` starts over.  n_valid: a 1-element int32 DEVICE tensor; only images 0 .. n_valid - 1 count (read by the kernel, so a
+    captured graph can evaluate a short last batch).
+
+    The running totals are plain sums of counts and of (num, den) pairs: ranks that evaluate disjoint images can add (all-reduce)
+    `counts_totals` and `meters_totals` and derive everything else from the sums."""
+
+    def __init__(self, atom_mask, bond_mask, omega_mask, rho_abs, logits, targets, btype_idx=None, n_valid=None):
+        if len(logits) != 8 or len(targets) != 8 or logits[1] is None:
+            raise ValueError("EvalTables wants the 8 head maps and the 8 target maps of heads %s" % (EXTRACT_HEADS,))
+        B, _, h, w = logits[1].shape
+        for i, (t, c) in enumerate(zip(logits, EXTRACT_HEADS)):
+            if t is None and (i == 6 or (i == 5 and btype_idx is not None)):
+                continue      # (|rho| comes as rho_abs; decode mode stores neither the raw rho nor the 360 bond-type planes)
+            if t is None or tuple(t.shape) != (B, c, h, w):
+                raise ValueError("EvalTables: head %d must be [%d, %d, %d, %d] (heads %s), got %s"
+                                 % (i, B, c, h, w, EXTRACT_HEADS, None if t is None else tuple(t.shape)))
+        for name, t, c in (("atom_mask", atom_mask, 1), ("bond_mask", bond_mask, 1), ("omega_mask", omega_mask, 60), ("rho_abs", rho_abs, 60)):
+            if tuple(t.shape) != (B, c, h, w):
+                raise ValueError("EvalTables: %s must be [%d, %d, %d, %d], got %s" % (name, B, c, h, w, tuple(t.shape)))
+        if btype_idx is not None and tuple(btype_idx.shape) != (B, 60, h, w):
+            raise ValueError("EvalTables: btype_idx must be [%d, 60, %d, %d], got %s" % (B, h, w, tuple(btype_idx.shape)))
+        exp = [(B, 1), (B, 14), (B, 3), (B, 2), (B, 1), (B, 6, 60), (B, 60), (B, 60)]
+        dts = [torch.float32] * 6 + [torch.float64] * 2
+        for t, e, dt in zip(targets, exp, dts):
+            if tuple(t.shape) != tuple(e) + (h, w) or t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+                raise L.AbcNetHipError("EvalTables: target %s %s does not match the contract %s %s (device tensors; no CPU "
+                                       "fallback)" % (tuple(t.shape), t.dtype, e, dt))
+        read = [atom_mask, bond_mask, omega_mask, rho_abs, logits[1], logits[2], logits[3]] + ([logits[5]] if btype_idx is None else [])
+        for t in read:
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
+                raise L.AbcNetHipError("EvalTables wants contiguous f32 device tensors (no CPU fallback)")
+        if btype_idx is not None and not (btype_idx.is_cuda and btype_idx.is_contiguous() and btype_idx.dtype == torch.uint8):
+            raise L.AbcNetHipError("EvalTables: btype_idx must be a contiguous uint8 device tensor")
+        if n_valid is not None and not (n_valid.is_cuda and n_valid.dtype == torch.int32 and n_valid.numel() == 1):
+            raise L.AbcNetHipError("EvalTables: n_valid must be a one-element int32 device tensor")
+        lib = L.load()
+        self.lib = lib
+        dev = atom_mask.device
+        d = L.EvalDesc()
+        d.atom_mask, d.bond_mask, d.omega_mask, d.rho_abs = (t.data_ptr() for t in (atom_mask, bond_mask, omega_mask, rho_abs))
+        d.types, d.charges, d.hs = logits[1].data_ptr(), logits[2].data_ptr(), logits[3].data_ptr()
+        d.btypes = None if btype_idx is not None else logits[5].data_ptr()
+        d.btype_idx = None if btype_idx is None else btype_idx.data_ptr()
+        (d.t_atom, d.t_types, d.t_charges, d.t_hs, d.t_bond, d.t_btypes, d.t_rho, d.t_omega) = (t.data_ptr() for t in targets)
+        d.n_valid = None if n_valid is None else n_valid.data_ptr()
+        d.B, d.h, d.w = B, h, w
+        nblk = lib.abc_eval_tables_blocks(C.byref(d))
+        if nblk < 1:
+            L.check(nblk, "eval_tables_blocks")
+        self.partial = torch.zeros((nblk, 24), dtype=torch.float64, device=dev)
+        # (uint64 on the device; int64 here: the counts stay far below 2^63)
+        self.counts_last = torch.zeros(L.EVAL_NCOUNT, dtype=torch.int64, device=dev)
+        self.counts_totals = torch.zeros(L.EVAL_NCOUNT, dtype=torch.int64, device=dev)
+        self.meters_last = torch.zeros((17, 2), dtype=torch.float64, device=dev)
+        self.meters_totals = torch.zeros((17, 2), dtype=torch.float64, device=dev)
+        d.partial = self.partial.data_ptr()
+        d.counts_last, d.counts_totals = self.counts_last.data_ptr(), self.counts_totals.data_ptr()
+        d.meters_last, d.meters_totals = self.meters_last.data_ptr(), self.meters_totals.data_ptr()
+        self.d = d
+        self.keep = (atom_mask, bond_mask, omega_mask, rho_abs, list(logits), list(targets), btype_idx, n_valid)
+
+    def run(self, stream=None):
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        L.check(self.lib.abc_eval_tables_update(C.byref(self.d), stream), "eval_tables_update")
+
+    def reset(self):
+        self.counts_totals.zero_()
+        self.meters_totals.zero_()
+
+    def result(self):
+        """dict (device sync): the five tables of test_accuracy.py:33-38 as float64 [n, 4] (tp, tn, fp, fn) under their names,
+        "confusion" {atom_type, atom_charge, bond_type: C[target][predicted]}, "precision" / "recall" {table: tp / (tp + fp + 1e-4),
+        tp / (tp + fn + 1e-4)} (lines 285-298), "meters" {name: {"sum", "count", "avg", "val"}} (the AverageMeter fields), and
+        "last": the tables of the last call alone"""
+        counts, last = self.counts_totals.cpu().numpy(), self.counts_last.cpu().numpy()
+        tot, lm = self.meters_totals.cpu(), self.meters_last.cpu()
+        out, conf = eval_tables_from_counts(counts)
+        out["confusion"] = conf
+        out["precision"] = {k: out[k][:, 0] / (out[k][:, 0] + out[k][:, 2] + 1e-4) for k in EVAL_TABLES}
+        out["recall"] = {k: out[k][:, 0] / (out[k][:, 0] + out[k][:, 3] + 1e-4) for k in EVAL_TABLES}
+        out["last"] = eval_tables_from_counts(last)[0]
+        meters = {}
+        for i, n in enumerate(METER_NAMES):
+            s, c = tot[i, 0].item(), tot[i, 1].item()
+            ln, ld = lm[i, 0].item(), lm[i, 1].item()
+            meters[n] = {"sum": s, "count": c, "avg": s / c if c else float("nan"), "val": ln / ld if ld else float("nan")}
+        out["meters"] = meters
+        return out
+
+
 def check_nms_heads(heads, what):
     """img2smiles2.py:61-79 reads heads 0 and 4 as one-plane centre maps and heads 6 and 7 as rho / omega maps of the same
     number of bins: refuse a head list that does not have that form (the NMS kernel would read and write past its maps)"""

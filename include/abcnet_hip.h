@@ -649,6 +649,44 @@ typedef struct abc_metrics_desc {
 int abc_metrics_blocks(const abc_metrics_desc* d);
 int abc_metrics_update(const abc_metrics_desc* d, abc_stream_t stream);
 
+/* The evaluation tables of test_accuracy.py:105-298 from what an inference step leaves on the device: the 3x3 centre masks,
+ * the omega-bin mask and |rho| of abc_nms_peaks (the raw-logit "> -1" NMS, not the "> 0.25" of the training meters), the
+ * logits of the atom heads, the bond-type head as raw planes or as its arg-max map, and the eight target maps.  One pass,
+ * one thread per map pixel (csrc/eval_tables.hip): target planes are read everywhere, predictions only where a target
+ * gives them weight.  No allocation, no sync: it may sit inside a captured graph.
+ *   counts[301] (uint64, exact, independent of the order of the workgroups):
+ *     [  0.. 41] atom_det[14][3]  (tp, fp, fn) of the atom centres by the pixel's target class (arg max of t_types,
+ *                                 first index on ties, 0 where every plane is 0):
+ *                                 tp = A & dil3(Ta), fp = A & !dil3(Ta), fn = Ta & !dil3(A)   (dil3: zero-padded 3x3 max)
+ *     [ 42.. 59] bond_det[6][3]   the same for the bond centres, class = arg max over types of the sum over the bins
+ *     [ 60..255] type[14][14]     confusion C[t][p] += #{target planes == 1} with t / p the arg max of targets / logits
+ *     [256..264] charge[3][3]
+ *     [265..300] btype[6][6]      per (pixel, omega bin), channel = type * 60 + bin
+ *     The reference's (tp, tn, fp, fn) of class i are C[i][i], total - row i - column i + C[i][i], column i - C[i][i],
+ *     row i - C[i][i].
+ *   meters[17][2]: (num, den) of the 17 meters in the order of abc_metrics_desc, inference flavour (lines 188-269).
+ * `last` holds this call alone, `totals` the running plain sums (a multi-rank caller may all-reduce them). */
+enum { ABC_EVAL_NCOUNT = 301 };
+typedef struct abc_eval_desc {
+    const float* atom_mask; const float* bond_mask;              /* [B][1][h][w], 0 / 1 */
+    const float* omega_mask; const float* rho_abs;               /* [B][60][h][w]: 0 / 1, |rho| */
+    const float* types; const float* charges; const float* hs;   /* [B][14|3|2][h][w] logits */
+    /* the bond-type prediction: exactly one of the raw planes [B][360][h][w] and the arg-max map uint8 [B][60][h][w] of
+     * decode mode (abc_conv_desc.head_aux_mode 3) */
+    const float* btypes; const uint8_t* btype_idx;
+    const float* t_atom; const float* t_types; const float* t_charges; const float* t_hs; const float* t_bond;
+    const float* t_btypes; const double* t_rho; const double* t_omega;
+    const int32_t* n_valid;    /* optional DEVICE int32: only images 0 .. *n_valid - 1 count (clamped to 0 .. B); NULL: all B */
+    int32_t B, h, w;
+    double* partial;           /* scratch [abc_eval_tables_blocks][24] */
+    uint64_t* counts_last; uint64_t* counts_totals;   /* [ABC_EVAL_NCOUNT] */
+    double* meters_last; double* meters_totals;       /* [17][2] */
+} abc_eval_desc;
+int abc_eval_tables_blocks(const abc_eval_desc* d);
+int abc_eval_tables_update(const abc_eval_desc* d, abc_stream_t stream);
+/* sizeof(abc_eval_desc), for a binding's mirror struct (this descriptor is not part of abc_sizeof's list) */
+int abc_eval_desc_size(void);
+
 /* ---- unet2: CBAM attention + residual (unet2.py:6-74).  See csrc/cbam.hip for the pass structure. ---- */
 typedef struct abc_cbam_channel_desc { /* ChannelAttentionModule (unet2.py:6-22), one MLP evaluation per image */
     const float* partial;  /* fwd: conv stats [B*tiles_per_img][4][C] (sum,sumsq,max,min of y2); bwd: [B*tiles_per_img][C] */
