@@ -278,6 +278,7 @@ SYMBOLS = {
     "abc_metrics_update": (C.c_int, [P(MetricsDesc), vp]),
     "abc_eval_tables_blocks": (C.c_int, [P(EvalDesc)]),
     "abc_eval_tables_update": (C.c_int, [P(EvalDesc), vp]),
+    "abc_eval_tables_update_sparse": (C.c_int, [P(EvalDesc), vp, vp]),
     "abc_eval_desc_size": (C.c_int, []),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "abc_plane_sum_work": (C.c_int, [i32]),

@@ -200,17 +200,20 @@ class ImageBuilder:
 
 
 class SampleBuilder:
-    """a whole training batch on the device: an ImageBuilder over trainer.input_images and a TargetRasterizer over
-    trainer.targets, fed with the SAME draws (utils.py:42-228 for every image).  sparse=True: the rasteriser's sparse form,
-    registered with trainer.use_sparse_targets."""
+    """a whole batch on the device: an ImageBuilder over owner.input_images and a TargetRasterizer over owner.targets, fed with
+    the SAME draws (utils.py:42-228 for every image).  `owner` is a Trainer, or an InferenceRunner(evaluate=True) -- the loop of
+    test_accuracy.py:94-269 reads the same MolecularImageDataset.  sparse=True: the rasteriser's sparse form, registered with
+    owner.use_sparse_targets.  Over a runner load() takes n <= B samples (a short last batch): the rows past n get an empty
+    record and a blank image, and owner.n_valid becomes n."""
 
     def __init__(self, trainer, amount=0.1, max_src=None, sparse=True, max_atoms=256, max_bonds=256):
         from .raster import TargetRasterizer
         img = trainer.input_images
         B, S = img.shape[0], img.shape[2]
         if img.shape[3] != S:
-            raise ValueError("SampleBuilder: the augmentation builds square S x S inputs, the Trainer takes %s" % (tuple(img.shape[2:]),))
+            raise ValueError("SampleBuilder: the augmentation builds square S x S inputs, the %s takes %s" % (type(trainer).__name__, tuple(img.shape[2:]),))
         self.trainer = trainer
+        self.short_batches = hasattr(trainer, "n_valid")      # (an evaluating InferenceRunner counts its first n_valid images)
         self.images = ImageBuilder(B, S, "train", amount, out=img, max_src=max_src)
         self.raster = TargetRasterizer(B, trainer.eng.h, trainer.eng.w, max_atoms=max_atoms, max_bonds=max_bonds, targets=trainer.targets,
                                        sparse=sparse)
@@ -221,15 +224,25 @@ class SampleBuilder:
     def load(self, images_u8, atoms_strings, bonds_strings, rng):
         """one draw per image (draw_augment), its offsets to both halves; returns the draws"""
         from .raster import parse_record
-        if not (len(images_u8) == len(atoms_strings) == len(bonds_strings) == self.B):
-            raise ValueError("expected %d images and annotation pairs" % self.B)
+        n = len(images_u8)
+        if not (n == len(atoms_strings) == len(bonds_strings)) or not (n == self.B or (self.short_batches and 0 <= n < self.B)):
+            raise ValueError("expected %s%d images and annotation pairs" % ("up to " if self.short_batches else "", self.B))
         draws, records = [], []
         for img, a, q in zip(images_u8, atoms_strings, bonds_strings):
             dr, offs = draw_augment(rng, self.images.amount, np.shape(img), self.S)
             draws.append(dr)
             records.append(parse_record(a, q, *offs, h=self.h))
-        self.images.load(images_u8, draws)
-        self.raster.load(records)
+        if n < self.B:      # a white 1 x 1 source, copied without noise, and nothing to draw
+            images_u8 = list(images_u8) + [np.full((1, 1), 255, dtype=np.uint8)] * (self.B - n)
+            blank = AugmentDraw(1, 1, 0, 0, 1, 1, 0.0, 0.0, 0)
+            empty = (np.zeros((0, 5), dtype=np.int32), np.zeros((0, 5), dtype=np.int32), np.zeros(0, dtype=np.float64))
+            self.images.load(images_u8, draws + [blank] * (self.B - n))
+            self.raster.load(records + [empty] * (self.B - n))
+        else:
+            self.images.load(images_u8, draws)
+            self.raster.load(records)
+        if self.short_batches:
+            self.trainer.n_valid.fill_(n)
         return draws
 
     def run(self, stream=None):

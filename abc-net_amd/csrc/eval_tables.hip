@@ -18,6 +18,8 @@
 //                      Integer results go to a per-workgroup LDS table (ds_add_u32; at most 256 * 60 * 6 per entry) that is
 //                      flushed with 64-bit vector atomics, non-zero entries only: exact whatever the order.  The 24 floating
 //                      sums behind the meters leave as per-workgroup double partials.
+//                      abc_eval_tables_update_sparse: the same pass under the rasteriser's group flags -- target planes are read
+//                      only in the 32-pixel groups an atom / a bond was drawn into (eval_tables_body<true>).
 //   pass 2  finalize : fixed-order reduction of the partials -> (num, den) of this call and the running totals; running
 //                      counts += counts of this call.  Two runs on the same input agree bit for bit.
 //
@@ -78,7 +80,19 @@ __device__ inline int class_head(const float* t, const float* z, size_t hw, doub
     return at;
 }
 
-__global__ __launch_bounds__(256) void eval_tables_kernel(const abc_eval_desc d) {
+// SPARSE: `flags` is abc_raster_desc.group_flags of the rasteriser that drew the target maps, one word per 32 pixels of the
+// flattened batch -- half a wave, so every branch on a word is half-wave-uniform.  A group without bits 0-3 holds no atom-side
+// target, one without bits 4-7 no bond-side target: what the dense form reads there is an exact zero and adds an exact zero,
+// so the thread skips the loads and keeps the zeros its sums start with.  A 3x3 neighbour in another group is judged by that
+// group's word.  The order of every per-thread sum and of the reductions is the dense form's.
+template <bool SPARSE>
+__device__ __forceinline__ bool target_is_centre(const float* T, const uint32_t* flags, uint32_t bits, size_t img0, int o) {
+    if (SPARSE && !(flags[(img0 + o) / 32] & bits)) return false;
+    return T[o] == 1.f;
+}
+
+template <bool SPARSE>
+__device__ __forceinline__ void eval_tables_body(const abc_eval_desc& d, const uint32_t* flags) {
     __shared__ double sm[4][NSUM];
     __shared__ unsigned cnt[NCOUNT];
     for (int i = threadIdx.x; i < NCOUNT; i += 256) cnt[i] = 0;
@@ -93,20 +107,24 @@ __global__ __launch_bounds__(256) void eval_tables_kernel(const abc_eval_desc d)
     if (p < npix && p / hw < nv) {
         const int b = (int)(p / hw), yx = (int)(p % hw);
         const int y = yx / d.w, x = yx % d.w;
+        const size_t img0 = (size_t)b * hw;
+        const uint32_t word = SPARSE ? flags[p / 32] : 0xFFu;
+        const bool has_atom = (word & 0x0Fu) != 0, has_bond = (word & 0xF0u) != 0;
         // ---- centre maps: precision / precision3 / recall / recall3 (lines 188-202, 217-231) and the detection outcome
         bool pk[2], tc[2], t3[2], p3[2];
 #pragma unroll
         for (int which = 0; which < 2; ++which) {
             const float* T = (which ? d.t_bond : d.t_atom) + (size_t)b * hw;
             const float* P = (which ? d.bond_mask : d.atom_mask) + (size_t)b * hw;
-            const bool t = T[yx] == 1.f, k = P[yx] != 0.f;
+            const uint32_t bits = which ? 0xF0u : 0x0Fu;
+            const bool t = (which ? has_bond : has_atom) && T[yx] == 1.f, k = P[yx] != 0.f;
             bool tn = false, pn = false;
             if (t || k)
                 for (int dy = -1; dy <= 1; ++dy)
                     for (int dx = -1; dx <= 1; ++dx) {
                         const int yy = y + dy, xx = x + dx;
                         if (yy >= 0 && yy < d.h && xx >= 0 && xx < d.w) {
-                            if (k) tn |= T[yy * d.w + xx] == 1.f;
+                            if (k) tn |= target_is_centre<SPARSE>(T, flags, bits, img0, yy * d.w + xx);
                             if (t) pn |= P[yy * d.w + xx] != 0.f;
                         }
                     }
@@ -119,9 +137,12 @@ __global__ __launch_bounds__(256) void eval_tables_kernel(const abc_eval_desc d)
             pk[which] = k; tc[which] = t; t3[which] = tn; p3[which] = pn;
         }
         // ---- atom heads
-        const int ca = class_head<14>(d.t_types + (size_t)b * 14 * hw + yx, d.types + (size_t)b * 14 * hw + yx, hw, &s[10], &s[11], cnt + O_TYPE);
-        class_head<3>(d.t_charges + (size_t)b * 3 * hw + yx, d.charges + (size_t)b * 3 * hw + yx, hw, &s[12], &s[13], cnt + O_CHARGE);
-        class_head<2>(d.t_hs + (size_t)b * 2 * hw + yx, d.hs + (size_t)b * 2 * hw + yx, hw, &s[14], &s[15], nullptr);
+        int ca = 0;     // (all-zero target planes: class 0, and no weight for any of the three heads)
+        if (has_atom) {
+            ca = class_head<14>(d.t_types + (size_t)b * 14 * hw + yx, d.types + (size_t)b * 14 * hw + yx, hw, &s[10], &s[11], cnt + O_TYPE);
+            class_head<3>(d.t_charges + (size_t)b * 3 * hw + yx, d.charges + (size_t)b * 3 * hw + yx, hw, &s[12], &s[13], cnt + O_CHARGE);
+            class_head<2>(d.t_hs + (size_t)b * 2 * hw + yx, d.hs + (size_t)b * 2 * hw + yx, hw, &s[14], &s[15], nullptr);
+        }
         if (pk[0]) atomicAdd(&cnt[O_ADET + ca * 3 + (t3[0] ? 0 : 1)], 1u);
         if (tc[0] && !p3[0]) atomicAdd(&cnt[O_ADET + ca * 3 + 2], 1u);
         // ---- per omega bin: bond types (6-way, channel = type * 60 + bin), rho MAE, omega mask / target bits
@@ -129,7 +150,7 @@ __global__ __launch_bounds__(256) void eval_tables_kernel(const abc_eval_desc d)
         float mass[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // sum over the bins of every type's target plane (line 166)
         const float* TB = d.t_btypes + (size_t)b * 360 * hw + yx;
         const size_t bin0 = (size_t)b * 60 * hw + yx;
-        for (int o = 0; o < 60; ++o) {
+        for (int o = 0; o < (has_bond ? 60 : 0); ++o) {     // (no bond-side target: mass, tom and temp stay 0)
             float st = 0.f, best = 0.f;
             int wgt = 0, at = 0;
 #pragma unroll
@@ -179,6 +200,9 @@ __global__ __launch_bounds__(256) void eval_tables_kernel(const abc_eval_desc d)
     }
 }
 
+__global__ __launch_bounds__(256) void eval_tables_kernel(const abc_eval_desc d) { eval_tables_body<false>(d, nullptr); }
+__global__ __launch_bounds__(256) void eval_tables_sparse_kernel(const abc_eval_desc d, const uint32_t* flags) { eval_tables_body<true>(d, flags); }
+
 __global__ __launch_bounds__(1024) void eval_finalize_kernel(const abc_eval_desc d, int nblk) {
     __shared__ double red[32][NSUM];
     __shared__ double tot[NSUM];
@@ -214,7 +238,7 @@ extern "C" int abc_eval_tables_blocks(const abc_eval_desc* d) {
     return abc_cdiv(d->B * d->h * d->w, 256);
 }
 
-extern "C" int abc_eval_tables_update(const abc_eval_desc* d, abc_stream_t stream) {
+static int eval_tables_launch(const abc_eval_desc* d, const uint32_t* target_flags, bool sparse, abc_stream_t stream) {
     if (d->B < 1 || d->h < 1 || d->w < 1) return abc_fail(ABC_EINVAL, "eval_tables: empty");
     if ((int64_t)d->B * d->h * d->w > (int64_t)INT32_MAX) return abc_fail(ABC_EINVAL, "eval_tables: more than 2^31 - 1 pixels");
     if (!d->partial || !d->counts_last || !d->counts_totals || !d->meters_last || !d->meters_totals)
@@ -225,9 +249,18 @@ extern "C" int abc_eval_tables_update(const abc_eval_desc* d, abc_stream_t strea
         return abc_fail(ABC_EINVAL, "eval_tables: null target map");
     if ((d->btypes != nullptr) == (d->btype_idx != nullptr))
         return abc_fail(ABC_EINVAL, "eval_tables: exactly one of btypes (raw planes) and btype_idx (arg-max map) must be given");
+    if (sparse && !target_flags) return abc_fail(ABC_EINVAL, "eval_tables: null target_flags");
+    if (sparse && ((int64_t)d->h * d->w) % 32) return abc_fail(ABC_EINVAL, "eval_tables: target_flags needs h * w a multiple of 32");
     const int nb = abc_eval_tables_blocks(d);
     hipLaunchKernelGGL(eval_clear_kernel, dim3(1), dim3(320), 0, (hipStream_t)stream, *d);
-    hipLaunchKernelGGL(eval_tables_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, *d);
+    if (sparse) hipLaunchKernelGGL(eval_tables_sparse_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, *d, target_flags);
+    else hipLaunchKernelGGL(eval_tables_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, *d);
     hipLaunchKernelGGL(eval_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, *d, nb);
     return abc_check_launch("eval_tables_update");
+}
+
+extern "C" int abc_eval_tables_update(const abc_eval_desc* d, abc_stream_t stream) { return eval_tables_launch(d, nullptr, false, stream); }
+
+extern "C" int abc_eval_tables_update_sparse(const abc_eval_desc* d, const uint32_t* target_flags, abc_stream_t stream) {
+    return eval_tables_launch(d, target_flags, true, stream);
 }

@@ -46,7 +46,9 @@ class InferenceRunner:
         evaluate: the evaluation tables of test_accuracy.py:105-298 (ops.EvalTables) in the same captured graph after the NMS, from the
         masks, |rho|, the atom heads and the bond-type maps (decode: their arg-max map) against .eval_targets, the static target
         buffers load_batch(imgs, targets, n_valid) fills; only the first .n_valid images count (a device int32, so a replayed graph
-        evaluates a short last batch); evaluation() / reset_evaluation()"""
+        evaluates a short last batch); evaluation() / reset_evaluation().  The targets may instead be drawn on the device from
+        annotation records: .targets names the same buffers for raster.TargetRasterizer / augment.SampleBuilder(self), and
+        use_sparse_targets(rasterizer) lets the evaluation launches read them only where something was drawn"""
         extract = bool(extract) or bool(assemble)
         from .ops import EXTRACT_HEADS, check_nms_heads
         check_nms_heads(model.heads, "InferenceRunner")
@@ -106,8 +108,8 @@ class InferenceRunner:
             with torch.cuda.device(dev):
                 self.assembler = GraphAssembler.from_extractor(self.extractor, cap_mol_bonds=cap_mol_bonds)
         self.evaluator = None
+        self._rasterizer = None
         if evaluate:
-            from .ops import EvalTables
             if list(model.heads) != EXTRACT_HEADS:
                 raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (EXTRACT_HEADS, list(model.heads)))
             B, h, w = eng.B, eng.h, eng.w
@@ -116,8 +118,7 @@ class InferenceRunner:
                 self.eval_targets = [torch.zeros(s + (h, w), dtype=torch.float64 if i >= 6 else torch.float32, device=dev)
                                      for i, s in enumerate(shapes)]
                 self.n_valid = torch.full((1,), B, dtype=torch.int32, device=dev)
-                self.evaluator = EvalTables(self.atom_mask, self.bond_mask, self.omega_mask, self.rho_abs, lg, self.eval_targets,
-                                            btype_idx=self.btype_idx if self.decode else None, n_valid=self.n_valid)
+            self._build_evaluator(None)
         self.use_graph = use_graph
         self._graph = None
         self.steps = 0
@@ -129,14 +130,55 @@ class InferenceRunner:
         with torch.cuda.device(self.dev):
             self.eng.run_pack(torch.cuda.current_stream().cuda_stream)
 
+    def _build_evaluator(self, target_flags):
+        from .ops import EvalTables
+        old = self.evaluator
+        with torch.cuda.device(self.dev):
+            self.evaluator = EvalTables(self.atom_mask, self.bond_mask, self.omega_mask, self.rho_abs, list(self.eng.logits), self.eval_targets,
+                                        btype_idx=self.btype_idx if self.decode else None, n_valid=self.n_valid, target_flags=target_flags)
+            if old is not None:      # (what was accumulated so far stays)
+                self.evaluator.counts_totals.copy_(old.counts_totals)
+                self.evaluator.meters_totals.copy_(old.meters_totals)
+                self.evaluator.counts_last.copy_(old.counts_last)
+                self.evaluator.meters_last.copy_(old.meters_last)
+
+    @property
+    def targets(self):
+        """evaluate=True: .eval_targets under the name augment.SampleBuilder and raster.TargetRasterizer(targets=...) callers use"""
+        if self.evaluator is None:
+            raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
+        return self.eval_targets
+
+    def use_sparse_targets(self, rasterizer):
+        """rasterizer: a TargetRasterizer(sparse=True, targets=self.targets) -- the evaluation launches then read only the target planes
+        of the 32-pixel groups the rasteriser drew into (abc_eval_tables_update_sparse), and the batch's targets come from
+        `rasterizer.load(records); rasterizer.run()` in front of step() instead of a dense copy; None: back to reading every plane.
+        The tables and meters are unchanged bit for bit."""
+        if self.evaluator is None:
+            raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
+        if rasterizer is None:
+            self._build_evaluator(None)
+            self._rasterizer = None
+        else:
+            if not getattr(rasterizer, "sparse", False) or any(a.data_ptr() != b.data_ptr() for a, b in zip(rasterizer.targets, self.eval_targets)):
+                raise L.AbcNetHipError("use_sparse_targets: a TargetRasterizer(sparse=True) over this InferenceRunner's own target tensors")
+            rasterizer.invalidate()      # (an earlier dense load may have left maps the records know nothing about)
+            self._build_evaluator(rasterizer.group_flags)
+            self._rasterizer = rasterizer
+        self._graph = None
+
     def load_batch(self, imgs, targets=None, n_valid=None):
         """targets (evaluate=True): the 8 target maps of the batch, copied into .eval_targets; n_valid: how many of its images count
-        (default: all; rows past it may hold anything)"""
+        (default: all; rows past it may hold anything).  Under use_sparse_targets() the targets come from the rasteriser: images and
+        n_valid only."""
         self.eng.img.copy_(imgs.reshape(self.eng.img.shape), non_blocking=True)
         if targets is not None or n_valid is not None:
             if self.evaluator is None:
                 raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
             if targets is not None:
+                if self._rasterizer is not None:
+                    raise L.AbcNetHipError("load_batch(dense targets) under use_sparse_targets(): the rasteriser's group flags would no longer "
+                                           "describe the maps; load records into the rasteriser, or call use_sparse_targets(None) first")
                 for dst, t in zip(self.eval_targets, targets):
                     dst.copy_(t.reshape(dst.shape), non_blocking=True)
             self.n_valid.fill_(self.eng.B if n_valid is None else int(n_valid))

@@ -202,12 +202,14 @@ class EvalTables:
     InferenceRunner, the 8 head maps (decode mode: logits[5] / logits[6] may be None, the bond type then comes from
     `btype_idx`) -- and the 8 target maps of the loss.  `run` adds the current batch, `result` reads (the only host sync),
     `reset` starts over.  n_valid: a 1-element int32 DEVICE tensor; only images 0 .. n_valid - 1 count (read by the kernel, so a
-    captured graph can evaluate a short last batch).
+    captured graph can evaluate a short last batch).  target_flags: TargetRasterizer(sparse=True).group_flags of the rasteriser
+    that draws THESE target tensors (int32 or uint32, B * h * w / 32 words) -- `run` then reads the target planes only in the
+    32-pixel groups an atom / a bond was drawn into (abc_eval_tables_update_sparse); the results are the dense call's bit for bit.
 
     The running totals are plain sums of counts and of (num, den) pairs: ranks that evaluate disjoint images can add (all-reduce)
     `counts_totals` and `meters_totals` and derive everything else from the sums."""
 
-    def __init__(self, atom_mask, bond_mask, omega_mask, rho_abs, logits, targets, btype_idx=None, n_valid=None):
+    def __init__(self, atom_mask, bond_mask, omega_mask, rho_abs, logits, targets, btype_idx=None, n_valid=None, target_flags=None):
         if len(logits) != 8 or len(targets) != 8 or logits[1] is None:
             raise ValueError("EvalTables wants the 8 head maps and the 8 target maps of heads %s" % (EXTRACT_HEADS,))
         B, _, h, w = logits[1].shape
@@ -236,6 +238,13 @@ class EvalTables:
             raise L.AbcNetHipError("EvalTables: btype_idx must be a contiguous uint8 device tensor")
         if n_valid is not None and not (n_valid.is_cuda and n_valid.dtype == torch.int32 and n_valid.numel() == 1):
             raise L.AbcNetHipError("EvalTables: n_valid must be a one-element int32 device tensor")
+        if target_flags is not None:
+            if (h * w) % 32:
+                raise L.AbcNetHipError("EvalTables: target_flags needs h * w a multiple of 32")
+            if not (target_flags.is_cuda and target_flags.is_contiguous() and target_flags.dtype in (torch.int32, torch.uint32)
+                    and target_flags.numel() == B * h * w // 32):
+                raise L.AbcNetHipError("EvalTables: target_flags must be a contiguous int32 / uint32 device tensor of %d words"
+                                       % (B * h * w // 32))
         lib = L.load()
         self.lib = lib
         dev = atom_mask.device
@@ -260,12 +269,16 @@ class EvalTables:
         d.counts_last, d.counts_totals = self.counts_last.data_ptr(), self.counts_totals.data_ptr()
         d.meters_last, d.meters_totals = self.meters_last.data_ptr(), self.meters_totals.data_ptr()
         self.d = d
+        self.target_flags = target_flags
         self.keep = (atom_mask, bond_mask, omega_mask, rho_abs, list(logits), list(targets), btype_idx, n_valid)
 
     def run(self, stream=None):
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
-        L.check(self.lib.abc_eval_tables_update(C.byref(self.d), stream), "eval_tables_update")
+        if self.target_flags is not None:
+            L.check(self.lib.abc_eval_tables_update_sparse(C.byref(self.d), self.target_flags.data_ptr(), stream), "eval_tables_update_sparse")
+        else:
+            L.check(self.lib.abc_eval_tables_update(C.byref(self.d), stream), "eval_tables_update")
 
     def reset(self):
         self.counts_totals.zero_()

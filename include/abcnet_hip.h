@@ -684,6 +684,11 @@ typedef struct abc_eval_desc {
 } abc_eval_desc;
 int abc_eval_tables_blocks(const abc_eval_desc* d);
 int abc_eval_tables_update(const abc_eval_desc* d, abc_stream_t stream);
+/* as abc_eval_tables_update; target_flags = abc_raster_desc.group_flags of the rasteriser that drew d's target maps
+ * (uint32 [B * h * w / 32]); h * w a multiple of 32.  In a group without bits 0-3 no atom-side target plane is read, in one
+ * without bits 4-7 no bond-side plane: the maps must be zero there, as the rasteriser leaves them.  counts_* and meters_* are
+ * the dense call's, bit for bit. */
+int abc_eval_tables_update_sparse(const abc_eval_desc* d, const uint32_t* target_flags, abc_stream_t stream);
 /* sizeof(abc_eval_desc), for a binding's mirror struct (this descriptor is not part of abc_sizeof's list) */
 int abc_eval_desc_size(void);
 

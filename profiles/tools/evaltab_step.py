@@ -1,15 +1,23 @@
-"""The evaluation tables (csrc/eval_tables.hip, ops.EvalTables, InferenceRunner(evaluate=True)) measured three ways, one process,
-b64 @ 512 x 512 bf16 (128 x 128 maps), synthetic targets of 30 atoms and 32 bonds per image:
+"""The evaluation tables (csrc/eval_tables.hip, ops.EvalTables, InferenceRunner(evaluate=True)) measured five ways, one process,
+b64 @ 512 x 512 bf16 (128 x 128 maps), synthetic targets of 30 atoms and 32 bonds per image (step, kernel, torch) or the
+annotation records of synthetic.drawn_molecules, the repo's molecule generator (sparse, loop):
 
   step    InferenceRunner.step() with and without evaluate=True (captured graphs, alternating blocks, median per-step device time)
   kernel  the evaluation launch sequence alone (device events around back-to-back launches after a warm-up, so launch gaps count),
           with the bytes of the target planes it has to read over that time
   torch   the oracle's torch restatement of test_accuracy.py:105-269 (tests/evaltab_oracle.py) on the same DEVICE tensors: the
           reference's own way, about 330 reductions each followed by a host read
+  sparse  the evaluation launch sequence alone, abc_eval_tables_update against abc_eval_tables_update_sparse on the SAME maps
+          (drawn by TargetRasterizer(sparse=True) from the generator's records): a device event pair around every update,
+          alternating blocks of the two forms, median; the results are compared bit for bit on the way
+  loop    one evaluation batch end to end, wall clock with a device sync per batch, two ways:
+            dense    the eight dense maps in pinned host memory -> load_batch(imgs, targets) -> step()   (the host rasteriser that
+                     has to build those maps first, utils.py:83-228, is NOT in the figure)
+            records  uint8 renders and annotation strings -> SampleBuilder.load() / run() -> step()       (parsing included)
 
 One JSON line per measurement.
 
-    python profiles/tools/evaltab_step.py [--batch 64] [--size 512] [--steps 40] [--warmup 10] [--parts step,kernel,torch]
+    python profiles/tools/evaltab_step.py [--batch 64] [--size 512] [--steps 40] [--warmup 10] [--parts step,kernel,torch,sparse,loop]
 """
 import argparse
 import json
@@ -26,7 +34,7 @@ import torch  # noqa: E402
 
 import abcnet_amd  # noqa: E402,F401
 from abcnet_amd.infer import InferenceRunner  # noqa: E402
-from abcnet_amd.synthetic import synthetic_images, synthetic_targets  # noqa: E402
+from abcnet_amd.synthetic import drawn_molecules, synthetic_images, synthetic_targets  # noqa: E402
 from abcnet_amd.unet import UNet  # noqa: E402
 import evaltab_oracle as eo  # noqa: E402
 
@@ -108,6 +116,96 @@ def main():
         torch.cuda.synchronize()
         print(json.dumps({"part": "torch", "batch": B, "size": S, "ms_per_batch": round((time.perf_counter() - t0) * 1000 / reps, 2),
                           "method": "wall clock, tests/evaltab_oracle.evaluate on the device tensors, %d repetitions after one warm-up" % reps}),
+              flush=True)
+    if "sparse" in parts or "loop" in parts:
+        records_parts(a, parts, ev, x)
+
+
+def records_parts(a, parts, ev, x):
+    """the `sparse` and `loop` parts: both run on the records of synthetic.drawn_molecules"""
+    import numpy as np
+    from abcnet_amd.augment import SampleBuilder
+    from abcnet_amd.ops import EvalTables
+    B, S = a.batch, a.size
+    # (eight distinct molecules, repeated: the generator is host code)
+    imgs, ann = drawn_molecules(min(B, 8), S, seed=5)
+    renders = [np.ascontiguousarray(255 - 255 * imgs[b % len(ann), 0].numpy().astype(np.uint8)) for b in range(B)]
+    atoms_s, bonds_s = [ann[b % len(ann)][0] for b in range(B)], [ann[b % len(ann)][1] for b in range(B)]
+    n_items = (sum(len(s.split(";")) - 1 for s in atoms_s) / B, sum(len(s.split(";")) - 1 for s in bonds_s) / B)
+    sb = SampleBuilder(ev, amount=0.1, max_src=(S, S), sparse=True)      # (registers its rasteriser: ev evaluates sparsely from here on)
+    rng = np.random.RandomState(0)
+    sb.load(renders, atoms_s, bonds_s, rng)
+    sb.run()
+    ev.step()
+    torch.cuda.synchronize()
+    flags = sb.raster.group_flags
+    fl = flags.cpu()
+    groups = {"groups": fl.numel(), "no_bit": int((fl == 0).sum()), "atom_bits": int(((fl & 0x0F) != 0).sum()), "bond_bits": int(((fl & 0xF0) != 0).sum())}
+    if "sparse" in parts:
+        old = ev.evaluator
+        mk = lambda f: EvalTables(*old.keep[:4], old.keep[4], old.keep[5], btype_idx=old.keep[6], n_valid=old.keep[7], target_flags=f)  # noqa: E731
+        forms = {"dense": mk(None), "sparse": mk(flags)}
+        for f in forms.values():
+            for _ in range(a.warmup):
+                f.run()
+        torch.cuda.synchronize()
+        same = all(torch.equal(getattr(forms["dense"], k), getattr(forms["sparse"], k)) for k in ("counts_last", "meters_last"))
+        times = {k: [] for k in forms}
+        for blk in range(4):
+            for name, f in (forms.items() if blk % 2 == 0 else reversed(list(forms.items()))):
+                marks = []
+                for _ in range(a.steps // 4):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    f.run()
+                    e1.record()
+                    marks.append((e0, e1))
+                torch.cuda.synchronize()
+                times[name] += [p.elapsed_time(q) for p, q in marks]
+        med = {k: statistics.median(v) for k, v in times.items()}
+        for k, v in times.items():
+            print(json.dumps({"part": "sparse", "form": k, "batch": B, "size": S, "updates": len(v), "ms_per_update_median": round(med[k], 4),
+                              "ms_min": round(min(v), 4)}), flush=True)
+        print(json.dumps(dict({"part": "sparse", "sparse_over_dense": round(med["sparse"] / med["dense"], 4), "bit_identical": same,
+                               "atoms_per_image": n_items[0], "bonds_per_image": n_items[1],
+                               "method": "device event pair around every update (3 launches), alternating blocks"}, **groups)), flush=True)
+    if "loop" in parts:
+        reps = max(4, a.steps // 4)
+
+        def wall(fn):
+            for _ in range(2):
+                fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1000)
+            return ts
+
+        def records_loop():
+            sb.load(renders, atoms_s, bonds_s, rng)
+            sb.run()
+            ev.step()
+
+        t_rec = wall(records_loop)
+        # the parent interface: dense maps (here: the ones the rasteriser just drew, copied out once) in pinned host memory
+        h_tg = [t.cpu().pin_memory() for t in ev.targets]
+        h_x = x.cpu().pin_memory()
+        ev.use_sparse_targets(None)
+
+        def dense_loop():
+            ev.load_batch(h_x, h_tg)
+            ev.step()
+
+        t_den = wall(dense_loop)
+        nbytes = sum(t.numel() * t.element_size() for t in h_tg)
+        for name, ts, note in (("dense", t_den, "pinned dense maps -> load_batch -> step; the host rasteriser is not included"),
+                               ("records", t_rec, "uint8 renders + annotation strings -> SampleBuilder.load / run -> step; parsing included")):
+            print(json.dumps({"part": "loop", "form": name, "batch": B, "size": S, "batches": len(ts), "ms_per_batch_median": round(statistics.median(ts), 3),
+                              "ms_min": round(min(ts), 3), "method": "wall clock, device sync per batch; " + note}), flush=True)
+        print(json.dumps({"part": "loop", "dense_target_bytes": nbytes, "records_over_dense": round(statistics.median(t_rec) / statistics.median(t_den), 4)}),
               flush=True)
 
 
