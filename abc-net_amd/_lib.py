@@ -198,7 +198,16 @@ class EvalDesc(C.Structure):
                 ("counts_last", vp), ("counts_totals", vp), ("meters_last", vp), ("meters_totals", vp)]
 
 
+class GraphScoreDesc(C.Structure):
+    _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("rec_atoms", vp), ("rec_bonds", vp), ("rec_counts", vp),
+                ("n_valid", vp), ("B", i32), ("cap_atoms", i32), ("cap_mol_bonds", i32), ("max_atoms", i32), ("max_bonds", i32),
+                ("radius", i32), ("rows", vp), ("totals", vp)]
+
+
 EVAL_NCOUNT = 301   # ABC_EVAL_NCOUNT
+# the ABC_GS_* columns of abc_graph_score_desc.rows / .totals
+GRAPH_SCORE_COLUMNS = ("counted", "none", "truncated", "exact", "atoms_equal", "bonds_equal", "atoms_true", "atoms_pred",
+                       "atoms_located", "atoms_matched", "bonds_true", "bonds_pred", "bonds_paired", "bonds_matched")
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
 MOL_EMPTY, MOL_TRUNCATED = 1, 2     # abc_mol_status
@@ -280,6 +289,8 @@ SYMBOLS = {
     "abc_eval_tables_update": (C.c_int, [P(EvalDesc), vp]),
     "abc_eval_tables_update_sparse": (C.c_int, [P(EvalDesc), vp, vp]),
     "abc_eval_desc_size": (C.c_int, []),
+    "abc_graph_score_update": (C.c_int, [P(GraphScoreDesc), vp]),
+    "abc_graph_score_desc_size": (C.c_int, []),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "abc_plane_sum_work": (C.c_int, [i32]),
     "abc_cbam_channel_fwd": (C.c_int, [P(CbamChannelDesc), vp]),
@@ -348,9 +359,11 @@ def load():
         n = lib.abc_sizeof(i)
         if n != C.sizeof(st):
             raise AbcNetHipError("struct #%d (%s): binding has %d bytes, library %d" % (i, st.__name__, C.sizeof(st), n))
-    # (abc_eval_desc is not in abc_sizeof's list: it reports its own size)
+    # (abc_eval_desc and abc_graph_score_desc are not in abc_sizeof's list: they report their own sizes)
     if lib.abc_eval_desc_size() != C.sizeof(EvalDesc):
         raise AbcNetHipError("struct EvalDesc: binding has %d bytes, library %d" % (C.sizeof(EvalDesc), lib.abc_eval_desc_size()))
+    if lib.abc_graph_score_desc_size() != C.sizeof(GraphScoreDesc):
+        raise AbcNetHipError("struct GraphScoreDesc: binding has %d bytes, library %d" % (C.sizeof(GraphScoreDesc), lib.abc_graph_score_desc_size()))
     _lib = lib
     return lib
 

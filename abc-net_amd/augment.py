@@ -223,15 +223,18 @@ class SampleBuilder:
 
     def load(self, images_u8, atoms_strings, bonds_strings, rng):
         """one draw per image (draw_augment), its offsets to both halves; returns the draws"""
-        from .raster import parse_record
+        from .raster import parse_graph, parse_record
         n = len(images_u8)
         if not (n == len(atoms_strings) == len(bonds_strings)) or not (n == self.B or (self.short_batches and 0 <= n < self.B)):
             raise ValueError("expected %s%d images and annotation pairs" % ("up to " if self.short_batches else "", self.B))
-        draws, records = [], []
+        scored = getattr(self.trainer, "scorer", None) is not None      # (an InferenceRunner(score_graphs=True))
+        draws, records, graphs = [], [], []
         for img, a, q in zip(images_u8, atoms_strings, bonds_strings):
             dr, offs = draw_augment(rng, self.images.amount, np.shape(img), self.S)
             draws.append(dr)
             records.append(parse_record(a, q, *offs, h=self.h))
+            if scored:
+                graphs.append(parse_graph(a, q, *offs, h=self.h))
         if n < self.B:      # a white 1 x 1 source, copied without noise, and nothing to draw
             images_u8 = list(images_u8) + [np.full((1, 1), 255, dtype=np.uint8)] * (self.B - n)
             blank = AugmentDraw(1, 1, 0, 0, 1, 1, 0.0, 0.0, 0)
@@ -241,6 +244,8 @@ class SampleBuilder:
         else:
             self.images.load(images_u8, draws)
             self.raster.load(records)
+        if scored:
+            self.trainer.load_graphs(graphs)
         if self.short_batches:
             self.trainer.n_valid.fill_(n)
         return draws

@@ -12,7 +12,8 @@ lists (extract=True, img2smiles2.py:113-191) and the assembled molecules (assemb
 
 evaluate=True makes the step the loop body of the reference's src/test_accuracy.py:94-269 as well: the targets of the batch sit in
 static device buffers and one more launch sequence after the NMS (ops.EvalTables) adds the batch to the per-class tables and the 17
-inference-flavour meters; evaluation() reads them.
+inference-flavour meters; evaluation() reads them.  score_graphs=True adds the score after assembly to that step: the assembled
+molecules against the annotated graphs (ops.GraphScore), accumulated like the tables.
 """
 from __future__ import annotations
 
@@ -26,7 +27,7 @@ from . import _lib as L
 class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
-                 assemble=False, cap_mol_bonds=None, evaluate=False):
+                 assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -48,7 +49,14 @@ class InferenceRunner:
         buffers load_batch(imgs, targets, n_valid) fills; only the first .n_valid images count (a device int32, so a replayed graph
         evaluates a short last batch); evaluation() / reset_evaluation().  The targets may instead be drawn on the device from
         annotation records: .targets names the same buffers for raster.TargetRasterizer / augment.SampleBuilder(self), and
-        use_sparse_targets(rasterizer) lets the evaluation launches read them only where something was drawn"""
+        use_sparse_targets(rasterizer) lets the evaluation launches read them only where something was drawn
+        score_graphs (needs assemble=True and evaluate=True): the score after assembly (ops.GraphScore) in the same captured graph
+        after the assembler -- the molecules of the step against the graph records load_graphs(records) staged
+        (raster.parse_graph; augment.SampleBuilder(self).load stages them itself), located within score_radius cells, on the
+        first .n_valid images; evaluation()["molecules"] holds the running result"""
+        if score_graphs and not (assemble and evaluate):
+            raise ValueError("InferenceRunner(score_graphs=True) scores the assembled molecules of an evaluating step: it needs "
+                             "assemble=True and evaluate=True")
         extract = bool(extract) or bool(assemble)
         from .ops import EXTRACT_HEADS, check_nms_heads
         check_nms_heads(model.heads, "InferenceRunner")
@@ -119,6 +127,11 @@ class InferenceRunner:
                                      for i, s in enumerate(shapes)]
                 self.n_valid = torch.full((1,), B, dtype=torch.int32, device=dev)
             self._build_evaluator(None)
+        self.scorer = None
+        if score_graphs:
+            from .ops import GraphScore
+            with torch.cuda.device(dev):
+                self.scorer = GraphScore.from_assembler(self.assembler, radius=score_radius, n_valid=self.n_valid)
         self.use_graph = use_graph
         self._graph = None
         self.steps = 0
@@ -212,6 +225,8 @@ class InferenceRunner:
             self.extractor.run(st)
         if self.assembler is not None:
             self.assembler.run(st)
+        if self.scorer is not None:
+            self.scorer.run(st)
         if self.evaluator is not None:
             self.evaluator.run(st)
 
@@ -219,12 +234,25 @@ class InferenceRunner:
         """the tables and meters accumulated since the last reset_evaluation() (ops.EvalTables.result(); host sync; needs evaluate=True)"""
         if self.evaluator is None:
             raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
-        return self.evaluator.result()
+        out = self.evaluator.result()
+        if self.scorer is not None:
+            out["molecules"] = self.scorer.result()
+        return out
 
     def reset_evaluation(self):
         if self.evaluator is None:
             raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
         self.evaluator.reset()
+        if self.scorer is not None:
+            self.scorer.reset()
+
+    def load_graphs(self, records):
+        """score_graphs=True: the graph records (raster.parse_graph) of the batch, n <= batch of them (the rows past n get an empty
+        record; n_valid says how many images count)"""
+        if self.scorer is None:
+            raise L.AbcNetHipError("InferenceRunner was built without score_graphs=True")
+        with torch.cuda.device(self.dev):
+            self.scorer.load(records)
 
     def candidates(self):
         """the per-image atom / bond candidate lists of the last step (host sync; needs extract=True)"""
@@ -241,6 +269,8 @@ class InferenceRunner:
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""
+        if self.scorer is not None and not self.scorer.loaded:
+            raise L.AbcNetHipError("InferenceRunner(score_graphs=True): no graph records were loaded (load_graphs, or SampleBuilder.load)")
         with torch.cuda.device(self.dev):
             self._step()
 

@@ -1,6 +1,6 @@
 """Thin host wrappers over single C-ABI kernels used outside the engine's static plan:
 fused loss (train.py:95-137), inference NMS (img2smiles2.py:61-79), candidate extraction and graph assembly
-(img2smiles2.py:113-311), fused Adam (train.py:55,141)."""
+(img2smiles2.py:113-311), the score of the assembled molecules against their annotations, fused Adam (train.py:55,141)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -478,6 +478,121 @@ class GraphAssembler:
                 out.append(None)
                 continue
             out.append(Molecule.from_device_rows(atoms[b, :a], bonds[b, :m], implh[b, :k], truncated=bool(status & L.MOL_TRUNCATED)))
+        return out
+
+
+class GraphScore:
+    """how many assembled molecules ARE the annotated molecule (csrc/graph_score.hip, abc_graph_score_update): the molecules of a
+    GraphAssembler, read in place, against the graph records of raster.parse_graph -- bonded atoms located by mutual nearest cell
+    within `radius`, matched by symbol and charge; bonds paired by their located ends, matched by order.  One launch, static
+    buffers, graph-capture safe; the 14 columns (L.GRAPH_SCORE_COLUMNS) of every image of the last call in .rows, their running
+    sums in .totals; `result()` is the only host sync."""
+
+    MAX_RECORD = 1024      # abc_graph_score_desc: max_atoms, max_bonds <= 1024
+
+    def __init__(self, mol_counts, mol_atoms, mol_bonds, max_atoms=256, max_bonds=256, radius=0, n_valid=None):
+        """mol_counts int32 [B, 4], mol_atoms int32 [B, cap_atoms, 5], mol_bonds int32 [B, cap_mol_bonds, 4]: device tensors of
+        GraphAssembler's layout (its own buffers, or hand-made rows); max_atoms / max_bonds: the capacity of a record;
+        radius >= 0 in cells; n_valid: a one-element int32 device tensor, only the first n_valid images count"""
+        for name, t in (("mol_counts", mol_counts), ("mol_atoms", mol_atoms), ("mol_bonds", mol_bonds)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("GraphScore: %s must be a tensor, got %s" % (name, type(t).__name__))
+        if mol_atoms.dim() != 3 or mol_atoms.shape[2] != 5 or mol_bonds.dim() != 3 or mol_bonds.shape[2] != 4:
+            raise ValueError("GraphScore: mol_atoms must be [B, cap_atoms, 5] and mol_bonds [B, cap_mol_bonds, 4], got %s and %s"
+                             % (tuple(mol_atoms.shape), tuple(mol_bonds.shape)))
+        B, cap_atoms, cap_mol_bonds = mol_atoms.shape[0], mol_atoms.shape[1], mol_bonds.shape[1]
+        if tuple(mol_counts.shape) != (B, 4) or mol_bonds.shape[0] != B:
+            raise ValueError("GraphScore: mol_counts must be [%d, 4] and mol_bonds [%d, cap_mol_bonds, 4], got %s and %s"
+                             % (B, B, tuple(mol_counts.shape), tuple(mol_bonds.shape)))
+        if B < 1 or not (1 <= cap_atoms <= 2048) or cap_mol_bonds < 1:
+            raise ValueError("GraphScore: B >= 1, cap_atoms 1..2048 and cap_mol_bonds >= 1, got %d, %d, %d" % (B, cap_atoms, cap_mol_bonds))
+        max_atoms, max_bonds, radius = int(max_atoms), int(max_bonds), int(radius)
+        if not (1 <= max_atoms <= self.MAX_RECORD and 1 <= max_bonds <= self.MAX_RECORD):
+            raise ValueError("GraphScore: max_atoms and max_bonds must be 1..%d, got %d and %d" % (self.MAX_RECORD, max_atoms, max_bonds))
+        if not (0 <= radius <= 32768):
+            raise ValueError("GraphScore: radius must be 0..32768 cells, got %d" % radius)
+        if n_valid is not None and not (isinstance(n_valid, torch.Tensor) and n_valid.numel() == 1):
+            raise ValueError("GraphScore: n_valid must be a one-element int32 device tensor")
+        for t in (mol_counts, mol_atoms, mol_bonds) + (() if n_valid is None else (n_valid,)):
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32):
+                raise L.AbcNetHipError("GraphScore wants contiguous int32 device tensors of the assembler's layout (no CPU fallback)")
+        self.lib = L.load()
+        dev = mol_atoms.device
+        self.B, self.cap_atoms, self.cap_mol_bonds = B, cap_atoms, cap_mol_bonds
+        self.max_atoms, self.max_bonds, self.radius = max_atoms, max_bonds, radius
+        pin = dict(pin_memory=True)
+        self.h_atoms = torch.zeros((B, max_atoms, 4), dtype=torch.int32, **pin)
+        self.h_bonds = torch.zeros((B, max_bonds, 3), dtype=torch.int32, **pin)
+        self.h_cnt = torch.zeros((2, B), dtype=torch.int32, **pin)
+        self.d_atoms, self.d_bonds, self.d_cnt = self.h_atoms.to(dev), self.h_bonds.to(dev), self.h_cnt.to(dev)
+        self.rows = torch.zeros((B, len(L.GRAPH_SCORE_COLUMNS)), dtype=torch.int32, device=dev)
+        # (uint64 on the device; int64 here: the sums stay far below 2^63)
+        self.totals = torch.zeros(len(L.GRAPH_SCORE_COLUMNS), dtype=torch.int64, device=dev)
+        d = L.GraphScoreDesc()
+        d.mol_counts, d.mol_atoms, d.mol_bonds = mol_counts.data_ptr(), mol_atoms.data_ptr(), mol_bonds.data_ptr()
+        d.rec_atoms, d.rec_bonds, d.rec_counts = self.d_atoms.data_ptr(), self.d_bonds.data_ptr(), self.d_cnt.data_ptr()
+        d.n_valid = None if n_valid is None else n_valid.data_ptr()
+        d.B, d.cap_atoms, d.cap_mol_bonds, d.max_atoms, d.max_bonds, d.radius = B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds, radius
+        d.rows, d.totals = self.rows.data_ptr(), self.totals.data_ptr()
+        self.d, self.keep = d, (mol_counts, mol_atoms, mol_bonds, n_valid)
+        self.loaded = False
+        self._copied = None
+
+    @classmethod
+    def from_assembler(cls, asm, max_atoms=256, max_bonds=256, radius=0, n_valid=None):
+        return cls(asm.mol_counts, asm.mol_atoms, asm.mol_bonds, max_atoms=max_atoms, max_bonds=max_bonds, radius=radius, n_valid=n_valid)
+
+    def load(self, graphs):
+        """graphs = list of n <= B (atoms [k, 4], bonds [m, 3]) pairs from raster.parse_graph; the rows past n get an empty record.
+        Asynchronous H2D of a few KB through pinned staging (as TargetRasterizer.load)."""
+        import numpy as np
+        if len(graphs) > self.B:
+            raise ValueError("expected at most %d graph records, got %d" % (self.B, len(graphs)))
+        recs = []
+        for b, (a, q) in enumerate(graphs):
+            a, q = np.asarray(a), np.asarray(q)
+            if a.ndim != 2 or a.shape[1] != 4 or q.ndim != 2 or q.shape[1] != 3:
+                raise ValueError("record %d: atoms must be [n, 4] and bonds [m, 3], got %s and %s" % (b, a.shape, q.shape))
+            if len(a) > self.max_atoms or len(q) > self.max_bonds:
+                raise ValueError("record %d has %d atoms / %d bonds (capacity %d / %d)" % (b, len(a), len(q), self.max_atoms, self.max_bonds))
+            if len(q) and not ((0 <= q[:, 0]) & (q[:, 0] < q[:, 1]) & (q[:, 1] < len(a))).all():
+                raise ValueError("record %d: every bond must name atoms 0 <= i < j < %d" % (b, len(a)))
+            recs.append((np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(q, dtype=np.int32)))
+        # the pinned staging is reused: the previous load's asynchronous copies must have left it (TargetRasterizer.load)
+        if self._copied is not None:
+            self._copied.synchronize()
+        self.h_cnt.zero_()
+        for b, (a, q) in enumerate(recs):
+            self.h_cnt[0, b], self.h_cnt[1, b] = len(a), len(q)
+            if len(a):
+                self.h_atoms[b, :len(a)] = torch.from_numpy(a)
+            if len(q):
+                self.h_bonds[b, :len(q)] = torch.from_numpy(q)
+        self.d_atoms.copy_(self.h_atoms, non_blocking=True)
+        self.d_bonds.copy_(self.h_bonds, non_blocking=True)
+        self.d_cnt.copy_(self.h_cnt, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record(torch.cuda.current_stream(self.d_cnt.device))
+        self.loaded = True
+
+    def run(self, stream=None):
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        L.check(self.lib.abc_graph_score_update(C.byref(self.d), stream), "graph_score_update")
+
+    def reset(self):
+        self.totals.zero_()
+
+    def result(self):
+        """dict (device sync): the 14 running totals under their names (int), "share_exact" = exact / counted, "share_atoms" =
+        atoms_matched / atoms_true, "share_bonds" = bonds_matched / bonds_true (nan for an empty denominator), and "rows": the
+        int32 [B, 14] table of the last call"""
+        tot = self.totals.cpu().tolist()
+        out = {k: int(v) for k, v in zip(L.GRAPH_SCORE_COLUMNS, tot)}
+        for share, num, den in (("share_exact", "exact", "counted"), ("share_atoms", "atoms_matched", "atoms_true"),
+                                ("share_bonds", "bonds_matched", "bonds_true")):
+            out[share] = out[num] / out[den] if out[den] else float("nan")
+        out["rows"] = self.rows.cpu().numpy()
         return out
 
 

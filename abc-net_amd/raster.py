@@ -71,6 +71,56 @@ def parse_record(atoms_string, bonds_string, scale_x=1, scale_y=1, ddx=0, ddy=0,
             np.array(rhos, dtype=np.float64))
 
 
+def parse_graph(atoms_string, bonds_string, scale_x=1, scale_y=1, ddx=0, ddy=0, h=128):
+    """the annotated molecule as a graph on the head-map grid, for ops.GraphScore: (atoms int32 [n,4], bonds int32 [m,3]).
+    atoms[i] = (x, y, element, charge): the cell of parse_record, the ATOM_VOCAB index (-1 for an element outside the vocabulary)
+    and the annotated charge as written.  bonds[k] = (i, j, code): i < j 0-based atom indices and parse_record's bond type index
+    + 1 (1-4 the orders, 5 a wedge of stereo 1 / 5, 6 of stereo 6).  An end of a bond is the atom nearest to centre -/+ half vector,
+    measured between the transformed, un-floored positions in float64 (the first atom of the string wins a tie); a bond whose
+    ends are one atom, or whose pair an earlier bond has, is dropped; the others keep the order of the string."""
+    atoms, px, py = [], [], []
+    for atom_string in atoms_string.split(';')[:-1]:
+        atom, position = atom_string.split(':')
+        if len(atom) == 1:
+            atom = atom.upper()
+        f = position.split(',')
+        fx, fy = int(f[0]) * scale_x + ddx, int(f[1]) * scale_y + ddy
+        x, y = int(fx) // 4, int(fy) // 4
+        if not (0 <= x < h and 0 <= y < h):
+            raise ValueError("atom at (%d, %d) falls outside the %d x %d map" % (x, y, h, h))
+        atoms.append((x, y, ATOM_VOCAB.get(atom, -1), int(f[2])))
+        px.append(float(fx))
+        py.append(float(fy))
+
+    def nearest(ex, ey):
+        best, at = None, -1
+        for i in range(len(atoms)):
+            dx, dy = px[i] - ex, py[i] - ey
+            d2 = dx * dx + dy * dy
+            if best is None or d2 < best:
+                best, at = d2, i
+        return at
+
+    bonds, seen = [], set()
+    for bond_string in bonds_string.split(';')[:-1]:
+        bond, position = bond_string.split(':')
+        type_idx = BOND_VOCAB.get(int(bond), 0)
+        f = position.split(',')
+        X, Y, DX, DY, stereo = int(f[0]), int(f[1]), int(f[2]), int(f[3]), int(f[4])
+        if stereo == 5 or stereo == 1:
+            type_idx = 4
+        elif stereo == 6:
+            type_idx = 5
+        i = nearest(float((X - DX) * scale_x + ddx), float((Y - DY) * scale_y + ddy))
+        j = nearest(float((X + DX) * scale_x + ddx), float((Y + DY) * scale_y + ddy))
+        pair = (min(i, j), max(i, j))
+        if i == j or pair in seen:
+            continue
+        seen.add(pair)
+        bonds.append(pair + (type_idx + 1,))
+    return np.array(atoms, dtype=np.int32).reshape(-1, 4), np.array(bonds, dtype=np.int32).reshape(-1, 3)
+
+
 class TargetRasterizer:
     """device-side utils.py:83-228 for a batch; `targets` may be the Trainer's static target tensors (then `run` writes
     the loss inputs in place), otherwise fresh ones are allocated with the reference collate shapes / dtypes"""

@@ -692,6 +692,40 @@ int abc_eval_tables_update_sparse(const abc_eval_desc* d, const uint32_t* target
 /* sizeof(abc_eval_desc), for a binding's mirror struct (this descriptor is not part of abc_sizeof's list) */
 int abc_eval_desc_size(void);
 
+/* The score AFTER assembly: how many assembled molecules (abc_assemble_graphs, read in place) are the annotated molecule
+ * (raster.parse_graph records).  One workgroup per image, integer arithmetic only, no allocation, no sync (csrc/graph_score.hip).
+ *   T        the annotated atoms that occur in at least one record bond (the assembler drops unbonded atoms too);
+ *   P        the molecule's atoms;  near_P(a) / near_T(p): the atom of the other side at the least squared cell distance, the
+ *            lowest row / record index on ties, defined only within radius^2;
+ *   located  a in T and p in P that are each other's nearest;
+ *   matched  a located pair with the same symbol (vocabulary index 0 reads as carbon on the predicted side; an annotated
+ *            element of -1, outside the vocabulary, never matches) and the same charge value;
+ *   paired   a molecule bond whose two ends are located and whose annotated pair the record lists (a record that lists a
+ *            pair twice answers with its first listing);  matched: its order is also the record's code.
+ * rows[b] (overwritten by every call; all zero for b >= *n_valid) and totals (+= the column sums, 64-bit integer atomics:
+ * exact in any launch order) have the ABC_GS_* columns.  counted is 1 for every image below n_valid.  An ABC_MOL_EMPTY image
+ * adds none = 1, atoms_true and bonds_true, and nothing else; a truncated molecule is scored as stored, with truncated = 1.
+ * atoms_equal: atoms_matched == |T| == atoms_pred; bonds_equal: bonds_matched == bonds_true == bonds_pred; exact: both. */
+enum { ABC_GS_COUNTED = 0, ABC_GS_NONE, ABC_GS_TRUNCATED, ABC_GS_EXACT, ABC_GS_ATOMS_EQUAL, ABC_GS_BONDS_EQUAL, ABC_GS_ATOMS_TRUE,
+       ABC_GS_ATOMS_PRED, ABC_GS_ATOMS_LOCATED, ABC_GS_ATOMS_MATCHED, ABC_GS_BONDS_TRUE, ABC_GS_BONDS_PRED, ABC_GS_BONDS_PAIRED,
+       ABC_GS_BONDS_MATCHED, ABC_GS_NCOL = 14 };
+typedef struct abc_graph_score_desc {
+    const int32_t* mol_counts;   /* [B][4]                 as abc_assemble_desc.mol_counts */
+    const int32_t* mol_atoms;    /* [B][cap_atoms][5]      (x, y, vocabulary index, charge value, hs) */
+    const int32_t* mol_bonds;    /* [B][cap_mol_bonds][4]  (end 1, end 2 (1-based), order, source candidate) */
+    const int32_t* rec_atoms;    /* [B][max_atoms][4]      (x, y, vocabulary index or -1, charge value) */
+    const int32_t* rec_bonds;    /* [B][max_bonds][3]      (i, j (0-based, i < j), code 1..6) */
+    const int32_t* rec_counts;   /* [2][B]                 atoms, then bonds, of every record */
+    const int32_t* n_valid;      /* optional DEVICE int32: only images 0 .. *n_valid - 1 count (clamped to 0 .. B); NULL: all B */
+    int32_t B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds;   /* cap_atoms 1..2048, max_atoms 1..1024, max_bonds 1..1024 */
+    int32_t radius;              /* >= 0, in cells */
+    int32_t* rows;               /* [B][ABC_GS_NCOL] */
+    uint64_t* totals;            /* [ABC_GS_NCOL] */
+} abc_graph_score_desc;
+int abc_graph_score_update(const abc_graph_score_desc* d, abc_stream_t stream);
+/* sizeof(abc_graph_score_desc), for a binding's mirror struct (as abc_eval_desc_size: not part of abc_sizeof's list) */
+int abc_graph_score_desc_size(void);
+
 /* ---- unet2: CBAM attention + residual (unet2.py:6-74).  See csrc/cbam.hip for the pass structure. ---- */
 typedef struct abc_cbam_channel_desc { /* ChannelAttentionModule (unet2.py:6-22), one MLP evaluation per image */
     const float* partial;  /* fwd: conv stats [B*tiles_per_img][4][C] (sum,sumsq,max,min of y2); bwd: [B*tiles_per_img][C] */

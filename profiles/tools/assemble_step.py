@@ -7,10 +7,13 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
   host     candidates() against molecules(): wall time of the D2H copies plus the host work, and the bytes each copies
   graphs   the share of images whose assembled graph equals the drawn annotation: the same bonded atoms (head-map cell, element,
            charge) and the same bonds (unordered pair of cells, order; a wedge counts as order 5 / 6).  Reported, not a test.
+           Beside it the device's own count: InferenceRunner(score_graphs=True) at radius 0 (csrc/graph_score.hip), one sync.
+  score    abc_graph_score_update alone (as `launch`), and InferenceRunner.step() with assemble=True, evaluate=True against the
+           same with score_graphs=True (as `step`); the targets of both come from the annotation records (sparse rasteriser)
 
 One JSON line per measurement.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score]
 """
 import argparse
 import json
@@ -34,21 +37,42 @@ HEADS = [1, 14, 3, 2, 1, 360, 60, 60]
 B, S = 64, 512
 
 
-def runners():
+def model():
     from make_trained_fixture import unpack_state
     m = UNet(1, HEADS, dtype="bf16", dropout_p=0.2)
     m.load_state_dict(unpack_state(os.path.join(ROOT, "tests", "golden", "trained_unet_state.npz")))
-    m = m.to("cuda").eval()
-    x, notes = drawn_molecules(B, S, seed=777)
+    return m.to("cuda").eval()
+
+
+def runners(m, x):
     out = {}
     for name, kw in (("extract=True", dict(extract=True)), ("assemble=True", dict(assemble=True))):
         r = InferenceRunner(m, B, S, S, use_graph=True, **kw)
         r.load_batch(x.to("cuda"))
         out[name] = r
-    return out, notes
+    return out
 
 
-def part_step(rs, steps, warmup):
+def scoring_runners(m, x, notes):
+    """the evaluating step without and with the score after assembly; targets drawn once from the annotation records"""
+    from abcnet_amd.raster import TargetRasterizer, parse_graph, parse_record
+    recs = [parse_record(a, b, h=S // 4) for a, b in notes]
+    graphs = [parse_graph(a, b, h=S // 4) for a, b in notes]
+    out = {}
+    for name, kw in (("assemble+evaluate", {}), ("assemble+evaluate+score", dict(score_graphs=True, score_radius=0))):
+        r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, evaluate=True, **kw)
+        rz = TargetRasterizer(B, S // 4, targets=r.targets, sparse=True)
+        r.use_sparse_targets(rz)
+        rz.load(recs)
+        rz.run()
+        r.load_batch(x.to("cuda"))
+        if r.scorer is not None:
+            r.load_graphs(graphs)
+        out[name] = r
+    return out
+
+
+def part_step(rs, steps, warmup, part="step", diff=("assemble=True", "extract=True"), diff_name="assemble_minus_extract_ms"):
     for r in rs.values():
         for _ in range(warmup):
             r.step()
@@ -67,24 +91,28 @@ def part_step(rs, steps, warmup):
             times[name] += [a.elapsed_time(b) for a, b in ev]
     med = {k: statistics.median(v) for k, v in times.items()}
     for k, v in times.items():
-        print(json.dumps({"part": "step", "form": k, "batch": B, "size": S, "steps": len(v), "ms_per_step_median": round(med[k], 4),
+        print(json.dumps({"part": part, "form": k, "batch": B, "size": S, "steps": len(v), "ms_per_step_median": round(med[k], 4),
                           "ms_min": round(min(v), 4), "img_per_s": round(B * 1000.0 / med[k], 1)}), flush=True)
-    print(json.dumps({"part": "step", "assemble_minus_extract_ms": round(med["assemble=True"] - med["extract=True"], 4)}), flush=True)
+    print(json.dumps({"part": part, diff_name: round(med[diff[0]] - med[diff[1]], 4)}), flush=True)
 
 
-def part_launch(r, iters=200):
-    asm = r.assembler
+def launch_us(run, iters=200):
     for _ in range(10):
-        asm.run()
+        run()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(iters):
-        asm.run()
+        run()
     e1.record()
     torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1000 / iters
+
+
+def part_launch(r, iters=200):
+    us = launch_us(r.assembler.run, iters)
     cnt = r.extractor.counts.cpu()
-    print(json.dumps({"part": "launch", "batch": B, "us_per_launch": round(e0.elapsed_time(e1) * 1000 / iters, 2),
+    print(json.dumps({"part": "launch", "batch": B, "us_per_launch": round(us, 2),
                       "atoms_per_image_mean": round(float(cnt[:, 1].float().mean()), 1), "candidates_per_image_mean": round(float(cnt[:, 3].float().mean()), 1),
                       "candidates_per_image_max": int(cnt[:, 3].max()),
                       "method": "device events around %d back-to-back launches (launch gaps included)" % iters}), flush=True)
@@ -132,6 +160,35 @@ def annotated_graph(atoms_s, bonds_s):
     return {(p,) + atoms[p] for p in shown}, bonds
 
 
+def part_score(rs, steps, warmup, iters=200):
+    r = rs["assemble+evaluate+score"]
+    sc = r.scorer
+    keep = sc.totals.clone()
+    us = launch_us(sc.run, iters)
+    us_asm, us_eval = launch_us(r.assembler.run, iters), launch_us(r.evaluator.run, iters)
+    sc.totals.copy_(keep)
+    r.reset_evaluation()
+    mc, rc = r.assembler.mol_counts.cpu(), sc.d_cnt.cpu()
+    print(json.dumps({"part": "score", "what": "launch", "batch": B, "us_per_launch": round(us, 2), "assemble_us_per_launch": round(us_asm, 2),
+                      "evaluation_us_per_call": round(us_eval, 2), "molecule_atoms_mean": round(float(mc[:, 0].float().mean()), 1),
+                      "molecule_bonds_mean": round(float(mc[:, 1].float().mean()), 1), "record_atoms_mean": round(float(rc[0].float().mean()), 1),
+                      "record_bonds_mean": round(float(rc[1].float().mean()), 1),
+                      "method": "device events around %d back-to-back launches (launch gaps included)" % iters}), flush=True)
+    part_step(rs, steps, warmup, part="score", diff=("assemble+evaluate+score", "assemble+evaluate"), diff_name="score_minus_plain_ms")
+
+
+def part_graphs_device(r):
+    """the device's count of the same thing: the scorer's rows of the last step (radius 0)"""
+    from abcnet_amd._lib import GRAPH_SCORE_COLUMNS
+    r.reset_evaluation()
+    r.step()
+    res = r.evaluation()["molecules"]
+    out = {"part": "graphs", "where": "device", "images": res["counted"]}
+    out.update({k: res[k] for k in GRAPH_SCORE_COLUMNS[1:]})
+    out["share"] = round(res["share_exact"], 4)
+    print(json.dumps(out), flush=True)
+
+
 def part_graphs(r, notes):
     mols = r.molecules()
     same = atoms_same = bonds_same = 0
@@ -144,7 +201,7 @@ def part_graphs(r, notes):
         atoms_same += got_a == want_a
         bonds_same += got_b == want_b
         same += got_a == want_a and got_b == want_b
-    print(json.dumps({"part": "graphs", "images": len(mols), "none": sum(m is None for m in mols), "truncated": sum(bool(m and m.truncated) for m in mols),
+    print(json.dumps({"part": "graphs", "where": "host", "images": len(mols), "none": sum(m is None for m in mols), "truncated": sum(bool(m and m.truncated) for m in mols),
                       "graph_equals_annotation": same, "atoms_equal": atoms_same, "bonds_equal": bonds_same,
                       "share": round(same / len(mols), 4)}), flush=True)
 
@@ -156,8 +213,11 @@ def main():
     ap.add_argument("--parts", default="step,launch,host,graphs")
     a = ap.parse_args()
     parts = a.parts.split(",")
-    rs, notes = runners()
-    for r in rs.values():
+    m = model()
+    x, notes = drawn_molecules(B, S, seed=777)
+    rs = runners(m, x) if set(parts) & {"step", "launch", "host"} else {}
+    ss = scoring_runners(m, x, notes) if set(parts) & {"graphs", "score"} else {}
+    for r in list(rs.values()) + list(ss.values()):
         for _ in range(2):
             r.step()
     torch.cuda.synchronize()
@@ -168,7 +228,10 @@ def main():
     if "host" in parts:
         part_host(rs["assemble=True"])
     if "graphs" in parts:
-        part_graphs(rs["assemble=True"], notes)
+        part_graphs(ss["assemble+evaluate+score"], notes)
+        part_graphs_device(ss["assemble+evaluate+score"])
+    if "score" in parts:
+        part_score(ss, a.steps, a.warmup)
 
 
 if __name__ == "__main__":
