@@ -148,6 +148,129 @@ def test_adam_matches_torch_on_plain_tensors():
     assert all(p.grad is None for p in pb)
 
 
+def _assert_state_close(oa, pa, ob, pb, gmax):
+    """exp_avg_sq is a sum of positive terms: the params' tolerance.  exp_avg is a signed average of gradients of magnitude up to gmax
+    (_grads draws them at scales 0.1, 1 and 10) and may cancel to nothing, while its error stays that of its terms -- the kernel's
+    f32 1 - beta1 is one ulp from torch's f32 0.2, and each update rounds once: the params' atol of 1e-7, which is for unit-size
+    terms, times gmax."""
+    for p, q, gm in zip(pa, pb, gmax):
+        assert oa.state[p]["step"].item() == ob.state[q]["step"].item()
+        torch.testing.assert_close(ob.state[q]["exp_avg"], oa.state[p]["exp_avg"], rtol=1e-5, atol=1e-7 * max(1.0, gm))
+        torch.testing.assert_close(ob.state[q]["exp_avg_sq"], oa.state[p]["exp_avg_sq"], rtol=1e-5, atol=1e-7)
+
+
+def _track_gmax(gmax, grads):
+    return [max(m, 0.0 if g is None else g.abs().max().item()) for m, g in zip(gmax, grads)]
+
+
+def test_adam_misaligned_segments_leave_their_neighbours_alone():
+    """params that are views into one flat buffer at element offsets 1, 2, 3 mod 4, their grads views of a second buffer at other
+    offsets mod 4 (one of them aligned): abc_adam_multi's scalar path for a segment whose p | g | m | v is not 16-byte aligned, on
+    counts below, at and above one chunk.  Gaps between the views hold a sentinel that no step may touch."""
+    counts = [1, 3, 5, 1023, 1024, 1025, 2051]
+    sent = -7.25
+    po, go, spans = 0, 0, []
+    for k, n in enumerate(counts):
+        pm = (1, 2, 3)[k % 3]
+        gm = (pm + 1 + k // 3) % 4 if (pm + 1 + k // 3) % 4 != pm else (pm + 2) % 4
+        po += 8 + (pm - po) % 4       # at least 8 sentinels before each view, so that no two are adjacent
+        go += 8 + (gm - go) % 4
+        assert po % 4 == pm and go % 4 == gm and pm != gm and pm != 0
+        spans.append((po, go, n))
+        po, go = po + n, go + n
+    g = torch.Generator().manual_seed(21)
+    pbuf = torch.full((po + 8,), sent, device=DEV)
+    gbuf = torch.full((go + 8,), sent, device=DEV)
+    pgap, ggap = torch.ones(po + 8, dtype=torch.bool, device=DEV), torch.ones(go + 8, dtype=torch.bool, device=DEV)
+    pa, pb = [], []
+    for o, og, n in spans:
+        init = torch.randn(n, generator=g).to(DEV)
+        v = pbuf[o:o + n]
+        v.copy_(init)
+        pgap[o:o + n] = False
+        ggap[og:og + n] = False
+        pb.append(v.requires_grad_(True))
+        pa.append(init.clone().requires_grad_(True))
+    assert all(p.data_ptr() % 16 != 0 for p in pb)
+    oa = torch.optim.Adam(pa, lr=1e-2, betas=(0.8, 0.99), weight_decay=1e-3, foreach=False)
+    ob = Adam(pb, lr=1e-2, betas=(0.8, 0.99), weight_decay=1e-3)
+    gmax = [0.0] * len(pa)
+    for k in range(4):
+        gr = _grads(pa, 30 + k)
+        gmax = _track_gmax(gmax, gr)
+        _set_grads(pa, gr)
+        for p, (o, og, n), x in zip(pb, spans, gr):
+            p.grad = gbuf[og:og + n]
+            p.grad.copy_(x)
+            assert p.grad.data_ptr() == gbuf.data_ptr() + 4 * og
+        assert sum(p.grad.data_ptr() % 16 == 0 for p in pb) >= 1 and sum(p.grad.data_ptr() % 16 != 0 for p in pb) >= 4
+        oa.step()
+        ob.step()
+        assert ob.last_segments == len(counts)
+        _assert_params_close(pb, pa)
+    _assert_state_close(oa, pa, ob, pb, gmax)
+    assert (pbuf[pgap] == sent).all() and (gbuf[ggap] == sent).all()
+    for p, x in zip(pb, gr):
+        assert torch.equal(p.grad, x)         # the gradients are read, never written
+
+
+def test_adam_aligned_segments_with_tails_across_chunks():
+    """separate allocations of 1025, 2050 and 4099 elements: the vector path's last 1, 2 and 3 elements, each in a chunk after full
+    ones, with weight decay"""
+    g = torch.Generator().manual_seed(22)
+    init = [torch.randn(n, generator=g) for n in (1025, 2050, 4099)]
+    pa = [x.to(DEV).requires_grad_(True) for x in init]
+    pb = [x.to(DEV).requires_grad_(True) for x in init]
+    assert all(p.data_ptr() % 16 == 0 for p in pb)
+    oa = torch.optim.Adam(pa, lr=1e-2, betas=(0.8, 0.99), weight_decay=1e-2, foreach=False)
+    ob = Adam(pb, lr=1e-2, betas=(0.8, 0.99), weight_decay=1e-2)
+    gmax = [0.0] * len(pa)
+    for k in range(4):
+        gr = _grads(pa, 40 + k)
+        gmax = _track_gmax(gmax, gr)
+        _set_grads(pa, gr)
+        _set_grads(pb, gr)
+        assert all(p.grad.data_ptr() % 16 == 0 for p in pb)
+        oa.step()
+        ob.step()
+        assert ob.last_segments == 3
+        _assert_params_close(pb, pa)
+    _assert_state_close(oa, pa, ob, pb, gmax)
+
+
+def test_adam_more_classes_than_one_launch_takes():
+    """40 param groups with their own lr: 40 (group, step) classes, two launches of abc_adam_multi (32 + 8), the second with its
+    classes renumbered from 0 and its segments further down the uploaded table.  Two groups decay, and one param skips step 2 so
+    that its step count (its bias corrections) differs from its neighbours'."""
+    from abcnet_amd import _lib as L
+    ngroups = 40
+    assert ngroups > L.ADAM_MAX_CLASSES
+    g = torch.Generator().manual_seed(23)
+    init = [torch.randn(5 + k, generator=g) for k in range(ngroups)]
+    pa = [x.to(DEV).requires_grad_(True) for x in init]
+    pb = [x.to(DEV).requires_grad_(True) for x in init]
+    groups = lambda ps: [{"params": [p], "lr": 1e-3 * (1 + k), "weight_decay": 1e-2 if k in (3, 36) else 0}
+                         for k, p in enumerate(ps)]
+    oa = torch.optim.Adam(groups(pa), betas=(0.8, 0.99), foreach=False)
+    ob = Adam(groups(pb), betas=(0.8, 0.99))
+    before = [p.detach().clone() for p in pb]
+    gmax = [0.0] * len(pa)
+    for k in range(4):
+        gr = _grads(pa, 50 + k, none_at=(34,) if k == 2 else ())
+        gmax = _track_gmax(gmax, gr)
+        _set_grads(pa, gr)
+        _set_grads(pb, gr)
+        oa.step()
+        ob.step()
+        assert ob.last_segments == ngroups - (1 if k == 2 else 0)
+        _assert_params_close(pb, pa)
+    _assert_state_close(oa, pa, ob, pb, gmax)
+    assert ob.state[pb[34]]["step"].item() == 3.0 and ob.state[pb[35]]["step"].item() == 4.0
+    # groups 33-40 (the second launch) did move, each as torch moved it under its own lr
+    for k in range(L.ADAM_MAX_CLASSES, ngroups):
+        assert (pb[k].detach() != before[k]).all(), k
+
+
 def test_adam_state_dict_interchanges_with_torch():
     ma, mb = _stack(), _stack()
     pa, pb = list(ma.parameters()), list(mb.parameters())
