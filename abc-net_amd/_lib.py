@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libabcnet_hip.so")
 
 F32, BF16, FP8 = 0, 1, 2
 MAX_TAPS = 49
+OMEGA_RAW, OMEGA_PEAKS = 0, 1      # enum abc_omega_rule (abc_extract_desc.omega_rule)
 
 vp, i32, u32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_float, C.c_double
 
@@ -156,7 +157,8 @@ class MetricsDesc(C.Structure):
 class ExtractDesc(C.Structure):
     _fields_ = [("atom_mask", vp), ("bond_mask", vp), ("types", vp), ("charges", vp), ("hs", vp), ("btypes", vp), ("rho", vp),
                 ("omega", vp), ("B", i32), ("h", i32), ("w", i32), ("cap_atoms", i32), ("cap_bonds", i32), ("counts", vp),
-                ("atoms", vp), ("bonds", vp), ("bond_rho", vp), ("work", vp), ("work_masks", vp), ("btype_idx", vp)]
+                ("atoms", vp), ("bonds", vp), ("bond_rho", vp), ("work", vp), ("work_masks", vp), ("btype_idx", vp),
+                ("omega_rule", i32)]
 
 
 class RasterDesc(C.Structure):

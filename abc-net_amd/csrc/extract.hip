@@ -6,14 +6,23 @@
 //   atoms : (x, y, type, charge, hs)           raster order, greedy suppression of peaks within squared distance < 4
 //                                              of an already accepted atom (img2smiles2.py:171-191)
 //   bonds : (x, y, omega bin, type) + |rho|    raster order of the bond peaks, bins ascending; a bin survives unless the
-//                                              opposite direction wins (img2smiles2.py:128-169; the rule is applied to
-//                                              every bin whose RAW omega logit is non-zero, as the reference does)
+//                                              opposite direction wins (img2smiles2.py:128-169).  Which bins are
+//                                              tried is the launch's omega rule (abc_extract_desc.omega_rule):
+//                                                ABC_OMEGA_RAW   every bin whose RAW omega logit is non-zero
+//                                                                (img2smiles2.py:139, the default)
+//                                                ABC_OMEGA_PEAKS every bin that is a circular 3-tap peak of the omega
+//                                                                logits above -1 (the mask of img2smiles3.py:75-81, walked
+//                                                                by img2smiles.py:139 and img2smiles3.py:140; no v != 0
+//                                                                test).  The mask is recomputed in the wave from the raw
+//                                                                logits with abc_nms_peaks' comparison: nothing is read
+//                                                                from the stored omega_mask
 // x = row, y = column, as in the reference.  Order and content are bit-exact with the reference lists (integer work;
 // |rho| is the f32 the reference reads with .item()).
 //
 // Phases (1024 threads = 16 waves): (A) ordered compaction of both peak masks by block-wide prefix sums over 1024-pixel
 // chunks; (B) wave 0 runs the sequential greedy suppression over the compacted atom peaks, all waves then fill in the
-// arg-max classes; (C) one wave per bond peak evaluates the 60 bins (lane = bin, opposite bins by shuffles), a block
+// arg-max classes; (C) one wave per bond peak evaluates the 60 bins (lane = bin, opposite bins and -- rule PEAKS -- the two
+// circular neighbours by shuffles from lanes 0..59 only), a block
 // scan of the per-peak counts gives every peak its output range, a second sweep writes the candidates.
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
@@ -37,6 +46,7 @@ __device__ inline int argmax_plane(const float* p, size_t stride) {  // first ma
     return best;
 }
 
+template <int RULE>   // abc_omega_rule: one kernel per rule, so rule RAW carries none of the peak test
 __global__ __launch_bounds__(XT) void extract_kernel(const abc_extract_desc d) {
     __shared__ unsigned wt[XT / 64 + 1];
     __shared__ int cnt[MAX_BPEAKS];
@@ -118,7 +128,16 @@ __global__ __launch_bounds__(XT) void extract_kernel(const abc_extract_desc d) {
         const float o1 = __shfl(v, i1 & 63), o2 = __shfl(v, i2 & 63);
         const float mo = fmaxf(o1, o2);
         const bool drop = (k <= 29) ? (v < mo) : (v <= mo);
-        const bool keep = k < 60 && v != 0.f && !drop;
+        bool keep;
+        if (RULE == ABC_OMEGA_PEAKS) {
+            // circular 3-tap peak above -1 (img2smiles3.py:75-81): bins 0 and 59 are each other's neighbours
+            const int kp = k >= 60 ? 0 : (k == 0 ? 59 : k - 1), kn = k >= 59 ? 0 : k + 1;
+            const float vp = __shfl(v, kp), vn = __shfl(v, kn);
+            const float mx = fmaxf(v, fmaxf(vp, vn));
+            keep = k < 60 && mx == v && v > -1.f && !drop;
+        } else {
+            keep = k < 60 && v != 0.f && !drop;
+        }
         const unsigned long long m = __ballot(keep);
         if (lane == 0) { masks[i] = m; cnt[i] = __popcll(m); }
     }
@@ -164,6 +183,11 @@ extern "C" int abc_extract_peaks(const abc_extract_desc* d, abc_stream_t stream)
     if (d->cap_atoms < 1 || d->cap_atoms > 2048 || d->cap_bonds < 1) return abc_fail(ABC_EINVAL, "extract: cap_atoms must be 1..2048, cap_bonds >= 1");
     if (d->h >= 65536 || d->w >= 65536) return abc_fail(ABC_EUNSUPPORTED, "extract: map too large");
     if (!d->work || !d->work_masks || !d->counts || !d->atoms || !d->bonds || !d->bond_rho) return abc_fail(ABC_EINVAL, "extract: null buffer");
-    hipLaunchKernelGGL(extract_kernel, dim3(d->B), dim3(XT), 0, (hipStream_t)stream, *d);
+    if (d->omega_rule != ABC_OMEGA_RAW && d->omega_rule != ABC_OMEGA_PEAKS)
+        return abc_fail(ABC_EINVAL, "extract: omega_rule must be ABC_OMEGA_RAW (0) or ABC_OMEGA_PEAKS (1)");
+    if (d->omega_rule == ABC_OMEGA_PEAKS)
+        hipLaunchKernelGGL(extract_kernel<ABC_OMEGA_PEAKS>, dim3(d->B), dim3(XT), 0, (hipStream_t)stream, *d);
+    else
+        hipLaunchKernelGGL(extract_kernel<ABC_OMEGA_RAW>, dim3(d->B), dim3(XT), 0, (hipStream_t)stream, *d);
     return abc_check_launch("extract_peaks");
 }

@@ -27,7 +27,7 @@ from . import _lib as L
 class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
-                 assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0):
+                 assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw"):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -53,7 +53,14 @@ class InferenceRunner:
         score_graphs (needs assemble=True and evaluate=True): the score after assembly (ops.GraphScore) in the same captured graph
         after the assembler -- the molecules of the step against the graph records load_graphs(records) staged
         (raster.parse_graph; augment.SampleBuilder(self).load stages them itself), located within score_radius cells, on the
-        first .n_valid images; evaluation()["molecules"] holds the running result"""
+        first .n_valid images; evaluation()["molecules"] holds the running result
+        omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
+        (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
+        decode and fp8 work with either; .omega_rule names the one chosen"""
+        from .ops import OMEGA_RULES
+        if omega_rule not in OMEGA_RULES:
+            raise ValueError("InferenceRunner: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
+        self.omega_rule = omega_rule
         if score_graphs and not (assemble and evaluate):
             raise ValueError("InferenceRunner(score_graphs=True) scores the assembled molecules of an evaluating step: it needs "
                              "assemble=True and evaluate=True")
@@ -109,7 +116,8 @@ class InferenceRunner:
         if extract:
             from .ops import PeakExtractor
             self.extractor = PeakExtractor(lg, self.atom_mask, self.bond_mask, cap_atoms=cap_atoms, cap_bonds=cap_bonds,
-                                           btype_idx=self.btype_idx if self.decode else None, rho_abs=self.rho_abs if self.decode else None)
+                                           btype_idx=self.btype_idx if self.decode else None, rho_abs=self.rho_abs if self.decode else None,
+                                           omega_rule=omega_rule)
         self.assembler = None
         if assemble:
             from .ops import GraphAssembler

@@ -338,16 +338,27 @@ def nms_peaks(atom, bond, rho, omega):
     return am, bm, r, om
 
 
+OMEGA_RULES = {"raw": L.OMEGA_RAW, "peaks": L.OMEGA_PEAKS}      # PeakExtractor(omega_rule=...) -> enum abc_omega_rule
+
+
 class PeakExtractor:
     """img2smiles2.py:113-191 on the device: NMS masks + raw head maps -> compact ordered candidate lists (the wire
     format into the graph-assembly stage: GraphAssembler below, or the reference's own code on the host).  Static buffers, one launch, graph-capture safe; `lists()` is the
-    only host sync (one small D2H per batch instead of hundreds of .item() calls per image)."""
+    only host sync (one small D2H per batch instead of hundreds of .item() calls per image).
 
-    def __init__(self, logits, atom_mask, bond_mask, cap_atoms=512, cap_bonds=16384, btype_idx=None, rho_abs=None):
+    omega_rule: which omega bins of a bond peak are tried as candidates before the opposite-direction test.  "raw" (the default):
+    every bin whose raw logit is non-zero, img2smiles2.py:139 -- the driver this package is measured against.  "peaks": every bin
+    that is a circular 3-tap peak of the omega logits above -1 (the mask of img2smiles3.py:75-81), as img2smiles.py:139 and
+    img2smiles3.py:140 walk it; the kernel recomputes the mask from logits[7], omega_mask is not an input.  `.omega_rule` names it."""
+
+    def __init__(self, logits, atom_mask, bond_mask, cap_atoms=512, cap_bonds=16384, btype_idx=None, rho_abs=None, omega_rule="raw"):
         """btype_idx / rho_abs (decode mode, InferenceRunner(decode=True)): the uint8 arg-max map of the bond-type head and the |rho| map
         the heads kernel wrote instead of the raw maps logits[5] / logits[6] (which may then be None)"""
         # (extract.hip reads the head widths of train.py:47 -- 14 atom types, 3 charges, 2 hs, 360 bond-type planes, 60 rho and 60
         #  omega planes -- and one-plane masks: every shape is checked here, before the device is touched)
+        if omega_rule not in OMEGA_RULES:
+            raise ValueError("PeakExtractor: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
+        self.omega_rule = omega_rule
         if len(logits) != 8 or logits[0] is None:
             raise ValueError("PeakExtractor wants the 8 head maps of heads %s, got %d" % (EXTRACT_HEADS, len(logits)))
         B, _, h, w = logits[0].shape
@@ -380,6 +391,7 @@ class PeakExtractor:
         d.rho = rho_abs.data_ptr() if rho_abs is not None else logits[6].data_ptr()
         d.omega = logits[7].data_ptr()
         d.B, d.h, d.w, d.cap_atoms, d.cap_bonds = B, h, w, cap_atoms, cap_bonds
+        d.omega_rule = OMEGA_RULES[omega_rule]
         self.counts = torch.zeros((B, 4), dtype=torch.int32, device=dev)
         self.atoms = torch.zeros((B, cap_atoms, 5), dtype=torch.int32, device=dev)
         self.bonds = torch.zeros((B, cap_bonds, 4), dtype=torch.int32, device=dev)

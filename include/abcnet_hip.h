@@ -580,9 +580,18 @@ int abc_build_images(const abc_image_desc* d, abc_stream_t stream);
  *   atoms[b][i] = (x, y, type, charge, hs)      raster order, greedy suppression within squared distance < 4
  *   bonds[b][i] = (x, y, omega bin, type), bond_rho[b][i] = |rho|   raster order of bond peaks, bins ascending,
  *                                                 a bin kept unless its opposite direction wins (lines 141-157)
+ *   which bins are tried is omega_rule:
+ *     ABC_OMEGA_RAW   (0, the default: img2smiles2.py:139) every bin whose RAW omega logit is non-zero -- the reference computes
+ *                     the omega peak mask (img2smiles2.py:73-79) and does not read it;
+ *     ABC_OMEGA_PEAKS (1: img2smiles.py:139, img2smiles3.py:140) every bin k with
+ *                     v[k] == max(v[(k+59)%60], v[k], v[(k+1)%60]) && v[k] > -1   (the mask of img2smiles3.py:75-81);
+ *                     a peak whose logit is exactly 0 is tried.  The kernel recomputes the mask from the raw logits with
+ *                     abc_nms_peaks' comparison (on finite logits the kept bins are a subset of its omega_mask); omega_mask
+ *                     itself is not an input.
  *   counts[b]   = (atom peaks, atoms accepted, bond peaks, bond candidates) -- true totals; the lists hold at most
  *                 cap_atoms / cap_bonds entries (and at most 4096 bond peaks per image are expanded).
  * x = row, y = column as in the reference. */
+enum abc_omega_rule { ABC_OMEGA_RAW = 0, ABC_OMEGA_PEAKS = 1 };
 typedef struct abc_extract_desc {
     const float* atom_mask; const float* bond_mask;               /* [B][1][h][w] */
     const float* types; const float* charges; const float* hs;    /* [B][14|3|2][h][w] logits */
@@ -598,6 +607,7 @@ typedef struct abc_extract_desc {
      * (abc_conv_desc.head_aux_mode 3, uint8 [B][60][h][w]) instead of six raw planes -- btypes may then be NULL; rho may be the |rho|
      * map (the kernel takes the absolute value either way) */
     const uint8_t* btype_idx;
+    int32_t omega_rule;   /* enum abc_omega_rule; any other value: ABC_EINVAL at call time.  A zeroed descriptor is ABC_OMEGA_RAW */
 } abc_extract_desc;
 int64_t abc_extract_work_ints(const abc_extract_desc* d);
 int64_t abc_extract_work_masks(const abc_extract_desc* d);

@@ -11,9 +11,13 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
   score    abc_graph_score_update alone (as `launch`), and InferenceRunner.step() with assemble=True, evaluate=True against the
            same with score_graphs=True (as `step`); the targets of both come from the annotation records (sparse rasteriser)
 
-One JSON line per measurement.
+  --omega-rule {raw,peaks}: the extractor's candidate rule of every runner built here (InferenceRunner(omega_rule=...): "raw" is
+           img2smiles2.py:139, "peaks" img2smiles.py:139 / img2smiles3.py:140); `graphs` and `score` then also report the candidates
+           per image and abc_extract_peaks alone (as `launch`).  profiles/r09_omega_rule.md is one run per rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score]
+One JSON line per measurement, each naming the rule.
+
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score] [--omega-rule raw]
 """
 import argparse
 import json
@@ -35,6 +39,11 @@ from abcnet_amd.unet import UNet  # noqa: E402
 
 HEADS = [1, 14, 3, 2, 1, 360, 60, 60]
 B, S = 64, 512
+RULE = "raw"      # --omega-rule
+
+
+def emit(d):
+    print(json.dumps(dict(d, omega_rule=RULE)), flush=True)
 
 
 def model():
@@ -47,7 +56,7 @@ def model():
 def runners(m, x):
     out = {}
     for name, kw in (("extract=True", dict(extract=True)), ("assemble=True", dict(assemble=True))):
-        r = InferenceRunner(m, B, S, S, use_graph=True, **kw)
+        r = InferenceRunner(m, B, S, S, use_graph=True, omega_rule=RULE, **kw)
         r.load_batch(x.to("cuda"))
         out[name] = r
     return out
@@ -60,7 +69,7 @@ def scoring_runners(m, x, notes):
     graphs = [parse_graph(a, b, h=S // 4) for a, b in notes]
     out = {}
     for name, kw in (("assemble+evaluate", {}), ("assemble+evaluate+score", dict(score_graphs=True, score_radius=0))):
-        r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, evaluate=True, **kw)
+        r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, evaluate=True, omega_rule=RULE, **kw)
         rz = TargetRasterizer(B, S // 4, targets=r.targets, sparse=True)
         r.use_sparse_targets(rz)
         rz.load(recs)
@@ -91,9 +100,9 @@ def part_step(rs, steps, warmup, part="step", diff=("assemble=True", "extract=Tr
             times[name] += [a.elapsed_time(b) for a, b in ev]
     med = {k: statistics.median(v) for k, v in times.items()}
     for k, v in times.items():
-        print(json.dumps({"part": part, "form": k, "batch": B, "size": S, "steps": len(v), "ms_per_step_median": round(med[k], 4),
-                          "ms_min": round(min(v), 4), "img_per_s": round(B * 1000.0 / med[k], 1)}), flush=True)
-    print(json.dumps({"part": part, diff_name: round(med[diff[0]] - med[diff[1]], 4)}), flush=True)
+        emit({"part": part, "form": k, "batch": B, "size": S, "steps": len(v), "ms_per_step_median": round(med[k], 4),
+              "ms_min": round(min(v), 4), "img_per_s": round(B * 1000.0 / med[k], 1)})
+    emit({"part": part, diff_name: round(med[diff[0]] - med[diff[1]], 4)})
 
 
 def launch_us(run, iters=200):
@@ -112,10 +121,10 @@ def launch_us(run, iters=200):
 def part_launch(r, iters=200):
     us = launch_us(r.assembler.run, iters)
     cnt = r.extractor.counts.cpu()
-    print(json.dumps({"part": "launch", "batch": B, "us_per_launch": round(us, 2),
-                      "atoms_per_image_mean": round(float(cnt[:, 1].float().mean()), 1), "candidates_per_image_mean": round(float(cnt[:, 3].float().mean()), 1),
-                      "candidates_per_image_max": int(cnt[:, 3].max()),
-                      "method": "device events around %d back-to-back launches (launch gaps included)" % iters}), flush=True)
+    emit({"part": "launch", "batch": B, "us_per_launch": round(us, 2),
+          "atoms_per_image_mean": round(float(cnt[:, 1].float().mean()), 1), "candidates_per_image_mean": round(float(cnt[:, 3].float().mean()), 1),
+          "candidates_per_image_max": int(cnt[:, 3].max()),
+          "method": "device events around %d back-to-back launches (launch gaps included)" % iters})
 
 
 def part_host(r, reps=20):
@@ -135,9 +144,9 @@ def part_host(r, reps=20):
     t0 = time.perf_counter()
     blocks = [m.molblock() for m in mols if m is not None]
     t_b = (time.perf_counter() - t0) * 1000
-    print(json.dumps({"part": "host", "candidates_ms": round(t_c, 3), "molecules_ms": round(t_m, 3), "candidates_d2h_bytes": bytes_c,
-                      "molecules_d2h_bytes": bytes_m, "molblock_ms_per_batch": round(t_b, 3), "molecules": len(blocks),
-                      "note": "wall time of one call per batch of %d: D2H copies + host list building, one host thread" % B}), flush=True)
+    emit({"part": "host", "candidates_ms": round(t_c, 3), "molecules_ms": round(t_m, 3), "candidates_d2h_bytes": bytes_c,
+          "molecules_d2h_bytes": bytes_m, "molblock_ms_per_batch": round(t_b, 3), "molecules": len(blocks),
+          "note": "wall time of one call per batch of %d: D2H copies + host list building, one host thread" % B})
 
 
 def annotated_graph(atoms_s, bonds_s):
@@ -166,14 +175,16 @@ def part_score(rs, steps, warmup, iters=200):
     keep = sc.totals.clone()
     us = launch_us(sc.run, iters)
     us_asm, us_eval = launch_us(r.assembler.run, iters), launch_us(r.evaluator.run, iters)
+    us_ext = launch_us(r.extractor.run, iters)
     sc.totals.copy_(keep)
     r.reset_evaluation()
     mc, rc = r.assembler.mol_counts.cpu(), sc.d_cnt.cpu()
-    print(json.dumps({"part": "score", "what": "launch", "batch": B, "us_per_launch": round(us, 2), "assemble_us_per_launch": round(us_asm, 2),
-                      "evaluation_us_per_call": round(us_eval, 2), "molecule_atoms_mean": round(float(mc[:, 0].float().mean()), 1),
-                      "molecule_bonds_mean": round(float(mc[:, 1].float().mean()), 1), "record_atoms_mean": round(float(rc[0].float().mean()), 1),
-                      "record_bonds_mean": round(float(rc[1].float().mean()), 1),
-                      "method": "device events around %d back-to-back launches (launch gaps included)" % iters}), flush=True)
+    emit({"part": "score", "what": "launch", "batch": B, "us_per_launch": round(us, 2), "assemble_us_per_launch": round(us_asm, 2),
+          "extract_us_per_launch": round(us_ext, 2),
+          "evaluation_us_per_call": round(us_eval, 2), "molecule_atoms_mean": round(float(mc[:, 0].float().mean()), 1),
+          "molecule_bonds_mean": round(float(mc[:, 1].float().mean()), 1), "record_atoms_mean": round(float(rc[0].float().mean()), 1),
+          "record_bonds_mean": round(float(rc[1].float().mean()), 1),
+          "method": "device events around %d back-to-back launches (launch gaps included)" % iters})
     part_step(rs, steps, warmup, part="score", diff=("assemble+evaluate+score", "assemble+evaluate"), diff_name="score_minus_plain_ms")
 
 
@@ -183,10 +194,12 @@ def part_graphs_device(r):
     r.reset_evaluation()
     r.step()
     res = r.evaluation()["molecules"]
-    out = {"part": "graphs", "where": "device", "images": res["counted"]}
+    cnt = r.extractor.counts.cpu()
+    out = {"part": "graphs", "where": "device", "images": res["counted"], "candidates_per_image_mean": round(float(cnt[:, 3].float().mean()), 1),
+           "candidates_per_image_max": int(cnt[:, 3].max()), "bond_peaks_per_image_mean": round(float(cnt[:, 2].float().mean()), 1)}
     out.update({k: res[k] for k in GRAPH_SCORE_COLUMNS[1:]})
     out["share"] = round(res["share_exact"], 4)
-    print(json.dumps(out), flush=True)
+    emit(out)
 
 
 def part_graphs(r, notes):
@@ -201,9 +214,9 @@ def part_graphs(r, notes):
         atoms_same += got_a == want_a
         bonds_same += got_b == want_b
         same += got_a == want_a and got_b == want_b
-    print(json.dumps({"part": "graphs", "where": "host", "images": len(mols), "none": sum(m is None for m in mols), "truncated": sum(bool(m and m.truncated) for m in mols),
-                      "graph_equals_annotation": same, "atoms_equal": atoms_same, "bonds_equal": bonds_same,
-                      "share": round(same / len(mols), 4)}), flush=True)
+    emit({"part": "graphs", "where": "host", "images": len(mols), "none": sum(m is None for m in mols), "truncated": sum(bool(m and m.truncated) for m in mols),
+          "graph_equals_annotation": same, "atoms_equal": atoms_same, "bonds_equal": bonds_same,
+          "share": round(same / len(mols), 4)})
 
 
 def main():
@@ -211,7 +224,10 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--parts", default="step,launch,host,graphs")
+    ap.add_argument("--omega-rule", choices=("raw", "peaks"), default="raw")
     a = ap.parse_args()
+    global RULE
+    RULE = a.omega_rule
     parts = a.parts.split(",")
     m = model()
     x, notes = drawn_molecules(B, S, seed=777)
