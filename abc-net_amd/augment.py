@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .contract import PinnedStaging, require_device_tensor, stream_or_current
 
 MODES = {"train": L.IMG_TRAIN, "test": L.IMG_TEST}
 
@@ -129,18 +130,18 @@ class ImageBuilder:
         shape = (batch, 1, S, S)
         if out is None:
             out = torch.zeros(shape, dtype=torch.float32, device=device)
-        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
-            raise L.AbcNetHipError("ImageBuilder: out %s %s does not match the contract %s float32 contiguous on the device "
-                                   "(a %d-channel input is not an image of this loader)" % (tuple(out.shape), out.dtype, shape,
-                                                                                           out.shape[1] if out.dim() == 4 else -1))
+        if tuple(out.shape) != shape:
+            raise L.AbcNetHipError("ImageBuilder: out %s does not match the contract %s (a %d-channel input is not an image of this "
+                                   "loader)" % (tuple(out.shape), shape, out.shape[1] if out.dim() == 4 else -1))
+        require_device_tensor(out, torch.float32, "ImageBuilder: out")
         self.lib = L.load()
         self.out, self.B, self.S, self.mode, self.amount = out, batch, S, mode, float(amount)
         self.max_h, self.max_w = max_h, max_w
         self.pitch = -(-max_w // 16) * 16
         dev = out.device
-        self.h_src = torch.full((batch, max_h, self.pitch), 255, dtype=torch.uint8, pin_memory=True)
-        self.h_par = torch.zeros((batch, L.IMG_NPARAM), dtype=torch.int32, pin_memory=True)
-        self.d_src, self.d_par = self.h_src.to(dev), self.h_par.to(dev)
+        self.staging = PinnedStaging(dev, {"src": ((batch, max_h, self.pitch), torch.uint8, 255), "par": ((batch, L.IMG_NPARAM), torch.int32)})
+        self.h_src, self.h_par = self.staging.host.values()
+        self.d_src, self.d_par = self.staging.dev.values()
         self._np_src, self._np_par = self.h_src.numpy(), self.h_par.numpy()
         d = L.ImageDesc()
         d.out, d.src, d.params = out.data_ptr(), self.d_src.data_ptr(), self.d_par.data_ptr()
@@ -149,7 +150,6 @@ class ImageBuilder:
         d.B, d.S, d.mode = batch, S, MODES[mode]
         d.test_max_ink = test_ink_max() if mode == "test" else 0
         self.d = d
-        self._copied = None
 
     def draw(self, rng, src_shapes):
         """draw_augment for every image of a batch, in order"""
@@ -179,23 +179,16 @@ class ImageBuilder:
                 if not (1 <= p.rows <= self.S and 1 <= p.cols <= self.S and 0 <= p.ddx <= self.S - p.rows and 0 <= p.ddy <= self.S - p.cols):
                     raise ValueError("image %d: %d x %d at (%d, %d) leaves the %d x %d canvas" % (b, p.rows, p.cols, p.ddx, p.ddy, self.S, self.S))
                 rows.append(param_row((h, w), p, self.S))
-        # the pinned staging is reused: the previous load's asynchronous copy must have left it (TargetRasterizer.load)
-        if self._copied is not None:
-            self._copied.synchronize()
+        self.staging.wait()
         for b, img in enumerate(images_u8):
             img = np.asarray(img)
             self._np_src[b, :img.shape[0], :img.shape[1]] = img
             self._np_par[b] = rows[b]
-        self.d_src.copy_(self.h_src, non_blocking=True)
-        self.d_par.copy_(self.h_par, non_blocking=True)
-        self._copied = torch.cuda.Event()
-        self._copied.record(torch.cuda.current_stream(self.d_par.device))
+        self.staging.commit()
 
     def run(self, stream=None):
         """one launch (graph-capturable): the f32 batch into self.out"""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.out.device).cuda_stream
-        L.check(self.lib.abc_build_images(C.byref(self.d), stream), "build_images")
+        L.check(self.lib.abc_build_images(C.byref(self.d), stream_or_current(stream, self.out.device)), "build_images")
         return self.out
 
 

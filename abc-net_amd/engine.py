@@ -1018,7 +1018,7 @@ class Engine:
             self.keep.append(epi_items)
             return
         # (the eight conv1 launches above write the eight slices of hfeat; the eight 1x1 convolutions go as one launch)
-        if self.nms_heads and self.heads == [1, 14, 3, 2, 1, 360, 60, 60] and len(head_convs) == 8:
+        if self.nms_heads and self.heads == arch.TRAIN_HEADS and len(head_convs) == 8:
             d6, d7 = head_convs[6][0], head_convs[7][0]
             rho, om = self.new((self.B, 60, h, w), torch.float32), self.new((self.B, 60, h, w), torch.float32)
             d6.head_aux, d6.head_aux_mode = rho.data_ptr(), 1

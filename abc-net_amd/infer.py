@@ -22,6 +22,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .contract import HEADS, alloc_targets, check_sparse_rasterizer, current_stream, refuse_dense_targets, resolve_device
 
 
 class InferenceRunner:
@@ -65,19 +66,12 @@ class InferenceRunner:
             raise ValueError("InferenceRunner(score_graphs=True) scores the assembled molecules of an evaluating step: it needs "
                              "assemble=True and evaluate=True")
         extract = bool(extract) or bool(assemble)
-        from .ops import EXTRACT_HEADS, check_nms_heads
+        from .ops import check_nms_heads
         check_nms_heads(model.heads, "InferenceRunner")
-        if extract and list(model.heads) != EXTRACT_HEADS:
-            raise ValueError("InferenceRunner(extract=True): the peak extractor reads heads %s, got heads %s" % (EXTRACT_HEADS, list(model.heads)))
-        if not torch.cuda.is_available():
-            raise L.AbcNetHipError("InferenceRunner needs an MI355X; abcnet_amd has no CPU fallback")
+        if extract and tuple(model.heads) != HEADS:
+            raise ValueError("InferenceRunner(extract=True): the peak extractor reads heads %s, got heads %s" % (list(HEADS), list(model.heads)))
+        self.dev = dev = resolve_device(model, device, "InferenceRunner")
         self.model = model
-        dev = torch.device(device or next(model.parameters()).device)
-        if dev.type != "cuda":
-            raise L.AbcNetHipError("InferenceRunner: the model must live on a GPU (got %s); abcnet_amd has no CPU fallback" % dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.dev = dev
         model.eval()
         with torch.cuda.device(dev):
             x0 = torch.zeros((batch, model.n_channels, height, width), device=dev)
@@ -126,14 +120,11 @@ class InferenceRunner:
         self.evaluator = None
         self._rasterizer = None
         if evaluate:
-            if list(model.heads) != EXTRACT_HEADS:
-                raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (EXTRACT_HEADS, list(model.heads)))
-            B, h, w = eng.B, eng.h, eng.w
-            shapes = [(B, 1), (B, 14), (B, 3), (B, 2), (B, 1), (B, 6, 60), (B, 60), (B, 60)]
+            if tuple(model.heads) != HEADS:
+                raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (list(HEADS), list(model.heads)))
             with torch.cuda.device(dev):
-                self.eval_targets = [torch.zeros(s + (h, w), dtype=torch.float64 if i >= 6 else torch.float32, device=dev)
-                                     for i, s in enumerate(shapes)]
-                self.n_valid = torch.full((1,), B, dtype=torch.int32, device=dev)
+                self.eval_targets = alloc_targets(eng.B, eng.h, eng.w, dev)
+                self.n_valid = torch.full((1,), eng.B, dtype=torch.int32, device=dev)
             self._build_evaluator(None)
         self.scorer = None
         if score_graphs:
@@ -149,7 +140,7 @@ class InferenceRunner:
         """re-pack the (changed) weights and re-derive the eval-mode BatchNorm coefficients (both functions of the
         parameters alone; call again after load_state_dict)"""
         with torch.cuda.device(self.dev):
-            self.eng.run_pack(torch.cuda.current_stream().cuda_stream)
+            self.eng.run_pack(current_stream())
 
     def _build_evaluator(self, target_flags):
         from .ops import EvalTables
@@ -181,8 +172,7 @@ class InferenceRunner:
             self._build_evaluator(None)
             self._rasterizer = None
         else:
-            if not getattr(rasterizer, "sparse", False) or any(a.data_ptr() != b.data_ptr() for a, b in zip(rasterizer.targets, self.eval_targets)):
-                raise L.AbcNetHipError("use_sparse_targets: a TargetRasterizer(sparse=True) over this InferenceRunner's own target tensors")
+            check_sparse_rasterizer(rasterizer, self.eval_targets, "InferenceRunner")
             rasterizer.invalidate()      # (an earlier dense load may have left maps the records know nothing about)
             self._build_evaluator(rasterizer.group_flags)
             self._rasterizer = rasterizer
@@ -197,9 +187,7 @@ class InferenceRunner:
             if self.evaluator is None:
                 raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
             if targets is not None:
-                if self._rasterizer is not None:
-                    raise L.AbcNetHipError("load_batch(dense targets) under use_sparse_targets(): the rasteriser's group flags would no longer "
-                                           "describe the maps; load records into the rasteriser, or call use_sparse_targets(None) first")
+                refuse_dense_targets(self._rasterizer)
                 for dst, t in zip(self.eval_targets, targets):
                     dst.copy_(t.reshape(dst.shape), non_blocking=True)
             self.n_valid.fill_(self.eng.B if n_valid is None else int(n_valid))
@@ -217,7 +205,7 @@ class InferenceRunner:
         if not self.fp8:
             return
         with torch.cuda.device(self.dev):
-            st = torch.cuda.current_stream().cuda_stream
+            st = current_stream()
             ref = self._ref
             ref.img.copy_(self.eng.img)
             ref.run_pack(st)
@@ -287,12 +275,12 @@ class InferenceRunner:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._run(torch.cuda.current_stream().cuda_stream)
+                self._run(current_stream())
             self._graph = g
         if self._graph is not None:
             self._graph.replay()
         else:
-            self._run(torch.cuda.current_stream().cuda_stream)
+            self._run(current_stream())
         self.steps += 1
 
     @property
@@ -301,6 +289,7 @@ class InferenceRunner:
 
     def profile(self, iters=3):
         """eager steps with a HIP event pair around every launch on the launch stream (as Trainer.profile)"""
+        from .ops import fold_marks, per_iteration, timed
         eng = self.eng
         torch.cuda.set_device(self.dev)
         stream = torch.cuda.current_stream(self.dev)
@@ -309,26 +298,10 @@ class InferenceRunner:
         for _ in range(iters):
             marks = []
             for fn, args, what, _w, meta in eng.fwd_ops:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                rc = fn(*args, st)
-                e1.record(stream)
-                if rc != 0:
-                    L.check(rc, what)
-                marks.append((meta["kernel"], meta["flops"], meta["bytes"], e0, e1))
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            L.check(eng.lib.abc_nms_peaks(C.byref(self._nms), st), "nms_peaks")
-            e1.record(stream)
-            marks.append(("nms", 0.0, float(eng.B * eng.h * eng.w * (2 if self.nms_in_heads else 122) * 4 * 2), e0, e1))
+                L.check(timed(stream, marks, meta["kernel"], meta["flops"], meta["bytes"], lambda: fn(*args, st)), what)
+            L.check(timed(stream, marks, "nms", 0.0, float(eng.B * eng.h * eng.w * (2 if self.nms_in_heads else 122) * 4 * 2),
+                          lambda: eng.lib.abc_nms_peaks(C.byref(self._nms), st)), "nms_peaks")
             torch.cuda.synchronize()
-            for k, fl, by, a, b in marks:
-                r = acc.setdefault(k, {"calls": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0})
-                r["calls"] += 1
-                r["ms"] += a.elapsed_time(b)
-                r["flops"] += fl
-                r["bytes"] += by
-        for r in acc.values():
-            for f in ("calls", "ms", "flops", "bytes"):
-                r[f] /= iters
+            fold_marks(acc, marks, ("flops", "bytes"))
+        per_iteration(acc, iters)
         return acc

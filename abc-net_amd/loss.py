@@ -5,7 +5,7 @@
 
 ``preds`` are the 8 NCHW f32 device maps of heads [1,14,3,2,1,360,60,60] (train.py:47) from any producer (UNet,
 nn.DataParallel(UNet), a plain torch module); ``targets`` the 8 tensors of collate_fn in the contract of
-ops.FusedLoss._check_targets (rho / omega f64); ``s`` the 10 uncertainty weights (model.s / model.module.s).
+contract.check_targets (rho / omega f64); ``s`` the 10 uncertainty weights (model.s / model.module.s).
 The result is a 0-d f64 device tensor, as in the reference, and nothing here synchronises with the host.
 
 Forward: abc_loss_fwd_bwd (activations, the 8 terms' partial sums and the unscaled d(numerator)/d(logits) in one pass)
@@ -22,11 +22,8 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
-from .ops import HEAD_NAMES
-
-HEADS = (1, 14, 3, 2, 1, 360, 60, 60)
-TARGET_CHANNELS = ((1,), (14,), (3,), (2,), (1,), (6, 60), (60,), (60,))
-TARGET_DTYPES = (torch.float32,) * 6 + (torch.float64,) * 2
+from .contract import HEADS, TARGET_CHANNELS, TARGET_DTYPES, check_targets, current_stream, set_target_ptrs  # noqa: F401
+from .ops import _fin_desc, terms_dict  # noqa: F401
 
 
 def _check(preds, targets, s):
@@ -45,11 +42,8 @@ def _check(preds, targets, s):
                          % (list(HEADS), [tuple(p.shape) for p in preds]))
     if any(p.dtype != torch.float32 for p in preds):
         raise ValueError("abc_loss: preds must be float32, got %s" % sorted({str(p.dtype) for p in preds}))
-    for i, (t, c, dt) in enumerate(zip(targets, TARGET_CHANNELS, TARGET_DTYPES)):
-        exp = (B,) + c + (h, w)
-        if tuple(t.shape) != exp or t.dtype != dt:
-            raise ValueError("abc_loss: target %d (%s) is %s %s, the contract is %s %s (collate_fn order; rho / omega f64)"
-                             % (i, HEAD_NAMES[i], tuple(t.shape), t.dtype, exp, dt))
+    # (forward() makes the targets contiguous itself, as it does the predictions)
+    check_targets(targets, B, h, w, "abc_loss", ValueError, require_cuda=False, require_contiguous=False)
     if tuple(s.shape) != (10,) or s.dtype != torch.float32:
         raise ValueError("abc_loss: s must be the 10 float32 uncertainty weights (model.s), got %s %s" % (tuple(s.shape), s.dtype))
     dev = preds[0].device
@@ -72,7 +66,7 @@ class _AbcLossFn(torch.autograd.Function):
         dl = [torch.empty_like(z) for z in logits]
         for i in range(8):
             d.logits[i], d.dlogits[i] = logits[i].data_ptr(), dl[i].data_ptr()
-        (d.t_atom, d.t_types, d.t_charges, d.t_hs, d.t_bond, d.t_btypes, d.t_rho, d.t_omega) = (t.data_ptr() for t in tg)
+        set_target_ptrs(d, tg)
         d.B, d.h, d.w = B, h, w
         nblk = lib.abc_loss_blocks(C.byref(d))
         partial = torch.empty((nblk, 16), dtype=torch.float64, device=dev)
@@ -80,15 +74,10 @@ class _AbcLossFn(torch.autograd.Function):
         head_scale = torch.empty(8, dtype=torch.float32, device=dev)
         ds = torch.empty(10, dtype=torch.float32, device=dev)
         d.partial = partial.data_ptr()
-        f = L.LossFinDesc()
-        f.partial, f.nblk, f.s, f.ds, f.out = partial.data_ptr(), nblk, s.data_ptr(), ds.data_ptr(), out.data_ptr()
         # one factor per head: channel i of head_scale is head i's
-        f.chan_scale, f.nchan = head_scale.data_ptr(), 8
-        for i in range(8):
-            f.chan_off[i], f.head_c[i] = i, 1
-        f.grad_scale = 1.0
+        f = _fin_desc(partial, s.data_ptr(), ds.data_ptr(), out, head_scale, range(8), [1] * 8, 1.0)
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = current_stream(dev)
             L.check(lib.abc_loss_fwd_bwd(C.byref(d), st), "loss_fwd_bwd")
             L.check(lib.abc_loss_finalize(C.byref(f), st), "loss_finalize")
         ctx.dl, ctx.ds, ctx.head_scale = dl, ds, head_scale
@@ -109,7 +98,7 @@ class _AbcLossFn(torch.autograd.Function):
             d.dlogits[i], d.n[i] = dl[i].data_ptr(), dl[i].numel()
         d.head_scale, d.ds, d.grad_out = ctx.head_scale.data_ptr(), ds.data_ptr(), g.data_ptr()
         with torch.cuda.device(dev):
-            L.check(L.load().abc_loss_scale_grads(C.byref(d), torch.cuda.current_stream(dev).cuda_stream), "loss_scale_grads")
+            L.check(L.load().abc_loss_scale_grads(C.byref(d), current_stream(dev)), "loss_scale_grads")
         ctx.dl = ctx.ds = ctx.head_scale = None
         return (None, None, ds) + tuple(dl)
 
@@ -122,16 +111,6 @@ def abc_loss(preds, targets, s, return_terms=False):
     box = []
     total = _AbcLossFn.apply(box, list(targets), s, *preds)
     return (total, box[0]) if return_terms else total
-
-
-def terms_dict(out):
-    """the 17-entry vector of abc_loss(..., return_terms=True) as {total, <head>, raw_<head>} floats (host sync)"""
-    o = out.detach().cpu()
-    r = {"total": o[0].item()}
-    for i, n in enumerate(HEAD_NAMES):
-        r[n] = o[1 + i].item()
-        r["raw_" + n] = o[9 + i].item()
-    return r
 
 
 class ABCLoss(nn.Module):

@@ -8,47 +8,59 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .contract import (HEAD_NAMES, HEADS, PinnedStaging, check_head_maps, check_targets, current_stream, require_device_tensor,
+                       set_target_ptrs, stream_or_current)
 
-EXTRACT_HEADS = [1, 14, 3, 2, 1, 360, 60, 60]   # the head widths extract.hip reads (train.py:47)
-HEAD_NAMES = ["atom_t", "atom_types", "atom_charges", "atom_hs", "bond_t", "bond_types", "bond_rhos", "bond_omega"]
+EXTRACT_HEADS = HEADS      # the head widths extract.hip reads (train.py:47)
+
+
+def _fin_desc(partial, s_ptr, ds_ptr, out, chan_scale, chan_off, head_c, grad_scale):
+    """abc_loss_finalize's descriptor: the partial sums of a loss pass -> `out` (17 terms), d(s), and one gradient factor per
+    channel of `chan_scale`, head i's at chan_off[i] .. chan_off[i] + head_c[i]"""
+    f = L.LossFinDesc()
+    f.partial, f.nblk, f.s, f.ds, f.out = partial.data_ptr(), partial.shape[0], s_ptr, ds_ptr, out.data_ptr()
+    f.chan_scale, f.nchan = chan_scale.data_ptr(), chan_scale.numel()
+    for i in range(8):
+        f.chan_off[i], f.head_c[i] = chan_off[i], head_c[i]
+    f.grad_scale = grad_scale
+    return f
+
+
+def terms_dict(out):
+    """the 17-entry vector of a loss (FusedLoss.out, abc_loss(..., return_terms=True)) as {total, <head>, raw_<head>} floats
+    (host sync)"""
+    o = out.detach().cpu()
+    r = {"total": o[0].item()}
+    for i, n in enumerate(HEAD_NAMES):
+        r[n] = o[1 + i].item()
+        r["raw_" + n] = o[9 + i].item()
+    return r
 
 
 class FusedLoss:
     """activation + 8-term loss + dlogits for fixed shapes; targets are read from the given (static) tensors"""
 
     def __init__(self, eng, targets, s_ptr, ds_ptr, grad_scale=1.0):
-        lib = eng.lib
-        self.eng, self.lib = eng, lib
+        self.eng, self.lib = eng, eng.lib
         self.targets = targets  # keep alive
-        self._check_targets(eng, targets)
+        check_targets(targets, eng.B, eng.h, eng.w, "fused loss", ValueError, require_cuda=False)
+        if tuple(eng.heads) != HEADS:
+            raise ValueError("the fused loss is defined for heads %s (train.py:47), got heads %s" % (list(HEADS), eng.heads))
+        self.d, self.partial = self._loss_desc(eng, targets)
+        self.nblk = self.partial.shape[0]
+        self.out = torch.zeros(17, dtype=torch.float64, device=eng.logits[0].device)
+        self.f = _fin_desc(self.partial, s_ptr, ds_ptr, self.out, eng.chan_scale, eng.head_off, eng.heads, grad_scale)
+
+    def _loss_desc(self, eng, targets):
+        """(the descriptor of the loss pass, its [nblk, 16] partial sums)"""
         d = L.LossDesc()
         for i in range(8):
             d.logits[i], d.dlogits[i] = eng.logits[i].data_ptr(), eng.dlogits[i].data_ptr()
-        (d.t_atom, d.t_types, d.t_charges, d.t_hs, d.t_bond, d.t_btypes, d.t_rho, d.t_omega) = (t.data_ptr() for t in targets)
+        set_target_ptrs(d, targets)
         d.B, d.h, d.w = eng.B, eng.h, eng.w
-        self.nblk = lib.abc_loss_blocks(C.byref(d))
-        dev = eng.logits[0].device
-        self.partial = torch.zeros((self.nblk, 16), dtype=torch.float64, device=dev)
-        d.partial = self.partial.data_ptr()
-        self.out = torch.zeros(17, dtype=torch.float64, device=dev)
-        f = L.LossFinDesc()
-        f.partial, f.nblk, f.s, f.ds, f.out = self.partial.data_ptr(), self.nblk, s_ptr, ds_ptr, self.out.data_ptr()
-        f.chan_scale, f.nchan = eng.chan_scale.data_ptr(), eng.chan_scale.numel()
-        for i in range(8):
-            f.chan_off[i] = eng.head_off[i]
-            f.head_c[i] = eng.heads[i]
-        f.grad_scale = grad_scale
-        self.d, self.f = d, f
-
-    @staticmethod
-    def _check_targets(eng, targets):
-        exp = [(eng.B, 1), (eng.B, 14), (eng.B, 3), (eng.B, 2), (eng.B, 1), (eng.B, 6, 60), (eng.B, 60), (eng.B, 60)]
-        dts = [torch.float32] * 6 + [torch.float64] * 2
-        for t, e, dt in zip(targets, exp, dts):
-            if tuple(t.shape) != tuple(e) + (eng.h, eng.w) or t.dtype != dt or not t.is_contiguous():
-                raise ValueError("target %s %s does not match the contract %s %s" % (tuple(t.shape), t.dtype, e, dt))
-        if eng.heads != [1, 14, 3, 2, 1, 360, 60, 60]:
-            raise ValueError("the fused loss is defined for heads [1,14,3,2,1,360,60,60] (train.py:47), got heads %s" % (eng.heads,))
+        partial = torch.zeros((self.lib.abc_loss_blocks(C.byref(d)), 16), dtype=torch.float64, device=eng.logits[0].device)
+        d.partial = partial.data_ptr()
+        return d, partial
 
     def run(self, stream):
         L.check(self.lib.abc_loss_fwd_bwd(C.byref(self.d), stream), "loss_fwd_bwd")
@@ -60,12 +72,7 @@ class FusedLoss:
 
     def result(self):
         """dict: total + weighted terms + raw terms (device sync)"""
-        o = self.out.cpu()
-        r = {"total": o[0].item()}
-        for i, n in enumerate(HEAD_NAMES):
-            r[n] = o[1 + i].item()
-            r["raw_" + n] = o[9 + i].item()
-        return r
+        return terms_dict(self.out)
 
 
 class FusedHeadsLoss(FusedLoss):
@@ -76,25 +83,15 @@ class FusedHeadsLoss(FusedLoss):
     def __init__(self, eng, targets, s_ptr, ds_ptr, grad_scale=1.0, keep_logits=True):
         """keep_logits=False: the logits never leave the kernel (eng.logits keep their old contents) -- for a training
         loop without the meters of train.py:145-215, the only other reader of the outputs"""
-        lib = eng.lib
-        self.eng, self.lib = eng, lib
-        self.targets = targets
-        self._check_targets(eng, targets)
-        d = eng.hf
+        self.keep_logits = keep_logits
+        super().__init__(eng, targets, s_ptr, ds_ptr, grad_scale)
+
+    def _loss_desc(self, eng, targets):
+        d = eng.hf      # (the engine's own descriptor and partial sums: the pass is part of its plan)
         for i in range(8):
-            d.logits[i] = eng.logits[i].data_ptr() if keep_logits else None
-        (d.t_atom, d.t_types, d.t_charges, d.t_hs, d.t_bond, d.t_btypes, d.t_rho, d.t_omega) = (t.data_ptr() for t in targets)
-        self.nblk = eng.hf_lossblocks
-        self.partial = eng.hf_losspart
-        self.out = torch.zeros(17, dtype=torch.float64, device=eng.logits[0].device)
-        f = L.LossFinDesc()
-        f.partial, f.nblk, f.s, f.ds, f.out = self.partial.data_ptr(), self.nblk, s_ptr, ds_ptr, self.out.data_ptr()
-        f.chan_scale, f.nchan = eng.chan_scale.data_ptr(), eng.chan_scale.numel()
-        for i in range(8):
-            f.chan_off[i] = eng.head_off[i]
-            f.head_c[i] = eng.heads[i]
-        f.grad_scale = grad_scale
-        self.d, self.f = d, f
+            d.logits[i] = eng.logits[i].data_ptr() if self.keep_logits else None
+        set_target_ptrs(d, targets)
+        return d, eng.hf_losspart
 
     def use_target_flags(self, flags):
         """flags: TargetRasterizer(sparse=True).group_flags of the rasteriser that draws THESE target tensors (or None: read every
@@ -105,8 +102,7 @@ class FusedHeadsLoss(FusedLoss):
             self._tflags = None
             return
         n = self.eng.B * self.eng.h * self.eng.w // 32
-        if flags.dtype not in (torch.int32, torch.uint32) or flags.numel() != n or not flags.is_cuda or not flags.is_contiguous():
-            raise L.AbcNetHipError("target flags: one 32-bit word per 32 pixels of the batch (%d words) on the device" % n)
+        _check_target_flags(flags, n, "target flags")
         self._tzero = torch.zeros(512, dtype=torch.uint8, device=flags.device)
         self._tflags = flags
         self.d.target_flags, self.d.zero_bytes = flags.data_ptr(), self._tzero.data_ptr()
@@ -114,6 +110,13 @@ class FusedHeadsLoss(FusedLoss):
     def run(self, stream):
         L.check(self.lib.abc_heads_fused_fwd_bwd(C.byref(self.d), stream), "heads_fused_fwd_bwd")
         L.check(self.lib.abc_loss_finalize(C.byref(self.f), stream), "loss_finalize")
+
+
+def _check_target_flags(flags, n, what):
+    """TargetRasterizer(sparse=True).group_flags: one 32-bit word per 32 pixels of the batch"""
+    require_device_tensor(flags, (torch.int32, torch.uint32), what)
+    if flags.numel() != n:
+        raise L.AbcNetHipError("%s: one 32-bit word per 32 pixels of the batch (%d words), got %d" % (what, n, flags.numel()))
 
 
 METER_NAMES = [
@@ -125,6 +128,23 @@ METER_NAMES = [
 ]
 
 
+def meters_dict(totals, last=None, extra=None):
+    """a [17, 2] table of (sum, count) rows -> {name: {"sum", "count", "avg"}} in METER_NAMES order (nan for an empty count);
+    last: the table of the last batch alone adds "val", the AverageMeter field; extra: {key: 17 values} adds a column each"""
+    totals = totals.cpu()
+    out = {}
+    for i, n in enumerate(METER_NAMES):
+        s, c = totals[i, 0].item(), totals[i, 1].item()
+        out[n] = {"sum": s, "count": c, "avg": s / c if c else float("nan")}
+    if last is not None:
+        for n, (ln, ld) in zip(METER_NAMES, last.cpu().tolist()):
+            out[n]["val"] = ln / ld if ld else float("nan")
+    for key, column in (extra or {}).items():
+        for n, v in zip(METER_NAMES, column.cpu().tolist()):
+            out[n][key] = v
+    return out
+
+
 class FusedMetrics:
     """The 17 AverageMeters of train.py:145-215 as one device-resident table: `run` adds the current batch
     (logits + targets already in HBM), `result` reads it (the only host sync), `reset` is the new-epoch
@@ -134,21 +154,16 @@ class FusedMetrics:
         lib = L.load()
         self.lib = lib
         B, _, h, w = logits[0].shape
-        exp = [(B, 1), (B, 14), (B, 3), (B, 2), (B, 1), (B, 6, 60), (B, 60), (B, 60)]
-        dts = [torch.float32] * 6 + [torch.float64] * 2
-        for t, e, dt in zip(targets, exp, dts):
-            if tuple(t.shape) != tuple(e) + (h, w) or t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
-                raise L.AbcNetHipError("metrics: target %s %s does not match the contract %s %s (device tensors; no CPU "
-                                       "fallback)" % (tuple(t.shape), t.dtype, e, dt))
-        for t, c in zip(logits, [1, 14, 3, 2, 1, 360, 60, 60]):
+        check_targets(targets, B, h, w, "metrics", L.AbcNetHipError)
+        for t, c in zip(logits, HEADS):
             if tuple(t.shape) != (B, c, h, w) or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
-                raise L.AbcNetHipError("metrics: logits must be the 8 contiguous NCHW f32 device maps of heads [1,14,3,2,1,360,60,60]")
+                raise L.AbcNetHipError("metrics: logits must be the 8 contiguous NCHW f32 device maps of heads %s" % (list(HEADS),))
         self.keep = (list(logits), list(targets))
         dev = logits[0].device
         d = L.MetricsDesc()
         for i in range(8):
             d.logits[i] = logits[i].data_ptr()
-        (d.t_atom, d.t_types, d.t_charges, d.t_hs, d.t_bond, d.t_btypes, d.t_rho, d.t_omega) = (t.data_ptr() for t in targets)
+        set_target_ptrs(d, targets)
         d.B, d.h, d.w = B, h, w
         self.peaks = torch.zeros((2, B, h, w), dtype=torch.uint8, device=dev)
         self.partial = torch.zeros((lib.abc_metrics_blocks(C.byref(d)), 24), dtype=torch.float64, device=dev)
@@ -158,22 +173,14 @@ class FusedMetrics:
         self.d = d
 
     def run(self, stream=None):
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        L.check(self.lib.abc_metrics_update(C.byref(self.d), stream), "metrics_update")
+        L.check(self.lib.abc_metrics_update(C.byref(self.d), stream_or_current(stream)), "metrics_update")
 
     def reset(self):
         self.totals.zero_()
 
     def result(self):
         """{name: {"sum", "count", "avg", "val"}} -- the AverageMeter fields (device sync)"""
-        tot, last = self.totals.cpu(), self.last.cpu()
-        out = {}
-        for i, n in enumerate(METER_NAMES):
-            s, c = tot[i, 0].item(), tot[i, 1].item()
-            ln, ld = last[i, 0].item(), last[i, 1].item()
-            out[n] = {"sum": s, "count": c, "avg": s / c if c else float("nan"), "val": ln / ld if ld else float("nan")}
-        return out
+        return meters_dict(self.totals, self.last)
 
 
 EVAL_TABLES = ["atom_detection", "atom_type", "atom_charge", "bond_detection", "bond_type"]   # test_accuracy.py:33-38
@@ -211,40 +218,29 @@ class EvalTables:
 
     def __init__(self, atom_mask, bond_mask, omega_mask, rho_abs, logits, targets, btype_idx=None, n_valid=None, target_flags=None):
         if len(logits) != 8 or len(targets) != 8 or logits[1] is None:
-            raise ValueError("EvalTables wants the 8 head maps and the 8 target maps of heads %s" % (EXTRACT_HEADS,))
+            raise ValueError("EvalTables wants the 8 head maps and the 8 target maps of heads %s" % (list(HEADS),))
         B, _, h, w = logits[1].shape
-        for i, (t, c) in enumerate(zip(logits, EXTRACT_HEADS)):
-            if t is None and (i == 6 or (i == 5 and btype_idx is not None)):
-                continue      # (|rho| comes as rho_abs; decode mode stores neither the raw rho nor the 360 bond-type planes)
-            if t is None or tuple(t.shape) != (B, c, h, w):
-                raise ValueError("EvalTables: head %d must be [%d, %d, %d, %d] (heads %s), got %s"
-                                 % (i, B, c, h, w, EXTRACT_HEADS, None if t is None else tuple(t.shape)))
+        # (|rho| comes as rho_abs; decode mode stores neither the raw rho nor the 360 bond-type planes)
+        check_head_maps(logits, B, h, w, {6} if btype_idx is None else {5, 6}, "EvalTables")
         for name, t, c in (("atom_mask", atom_mask, 1), ("bond_mask", bond_mask, 1), ("omega_mask", omega_mask, 60), ("rho_abs", rho_abs, 60)):
             if tuple(t.shape) != (B, c, h, w):
                 raise ValueError("EvalTables: %s must be [%d, %d, %d, %d], got %s" % (name, B, c, h, w, tuple(t.shape)))
         if btype_idx is not None and tuple(btype_idx.shape) != (B, 60, h, w):
             raise ValueError("EvalTables: btype_idx must be [%d, 60, %d, %d], got %s" % (B, h, w, tuple(btype_idx.shape)))
-        exp = [(B, 1), (B, 14), (B, 3), (B, 2), (B, 1), (B, 6, 60), (B, 60), (B, 60)]
-        dts = [torch.float32] * 6 + [torch.float64] * 2
-        for t, e, dt in zip(targets, exp, dts):
-            if tuple(t.shape) != tuple(e) + (h, w) or t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
-                raise L.AbcNetHipError("EvalTables: target %s %s does not match the contract %s %s (device tensors; no CPU "
-                                       "fallback)" % (tuple(t.shape), t.dtype, e, dt))
+        check_targets(targets, B, h, w, "EvalTables", L.AbcNetHipError)
         read = [atom_mask, bond_mask, omega_mask, rho_abs, logits[1], logits[2], logits[3]] + ([logits[5]] if btype_idx is None else [])
         for t in read:
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-                raise L.AbcNetHipError("EvalTables wants contiguous f32 device tensors (no CPU fallback)")
-        if btype_idx is not None and not (btype_idx.is_cuda and btype_idx.is_contiguous() and btype_idx.dtype == torch.uint8):
-            raise L.AbcNetHipError("EvalTables: btype_idx must be a contiguous uint8 device tensor")
-        if n_valid is not None and not (n_valid.is_cuda and n_valid.dtype == torch.int32 and n_valid.numel() == 1):
-            raise L.AbcNetHipError("EvalTables: n_valid must be a one-element int32 device tensor")
+            require_device_tensor(t, torch.float32, "EvalTables: every mask and head map read")
+        if btype_idx is not None:
+            require_device_tensor(btype_idx, torch.uint8, "EvalTables: btype_idx")
+        if n_valid is not None:
+            require_device_tensor(n_valid, torch.int32, "EvalTables: n_valid (one element)")
+            if n_valid.numel() != 1:
+                raise L.AbcNetHipError("EvalTables: n_valid must be a one-element int32 device tensor")
         if target_flags is not None:
             if (h * w) % 32:
                 raise L.AbcNetHipError("EvalTables: target_flags needs h * w a multiple of 32")
-            if not (target_flags.is_cuda and target_flags.is_contiguous() and target_flags.dtype in (torch.int32, torch.uint32)
-                    and target_flags.numel() == B * h * w // 32):
-                raise L.AbcNetHipError("EvalTables: target_flags must be a contiguous int32 / uint32 device tensor of %d words"
-                                       % (B * h * w // 32))
+            _check_target_flags(target_flags, B * h * w // 32, "EvalTables: target_flags")
         lib = L.load()
         self.lib = lib
         dev = atom_mask.device
@@ -253,7 +249,7 @@ class EvalTables:
         d.types, d.charges, d.hs = logits[1].data_ptr(), logits[2].data_ptr(), logits[3].data_ptr()
         d.btypes = None if btype_idx is not None else logits[5].data_ptr()
         d.btype_idx = None if btype_idx is None else btype_idx.data_ptr()
-        (d.t_atom, d.t_types, d.t_charges, d.t_hs, d.t_bond, d.t_btypes, d.t_rho, d.t_omega) = (t.data_ptr() for t in targets)
+        set_target_ptrs(d, targets)
         d.n_valid = None if n_valid is None else n_valid.data_ptr()
         d.B, d.h, d.w = B, h, w
         nblk = lib.abc_eval_tables_blocks(C.byref(d))
@@ -273,8 +269,7 @@ class EvalTables:
         self.keep = (atom_mask, bond_mask, omega_mask, rho_abs, list(logits), list(targets), btype_idx, n_valid)
 
     def run(self, stream=None):
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
+        stream = stream_or_current(stream)
         if self.target_flags is not None:
             L.check(self.lib.abc_eval_tables_update_sparse(C.byref(self.d), self.target_flags.data_ptr(), stream), "eval_tables_update_sparse")
         else:
@@ -290,18 +285,12 @@ class EvalTables:
         tp / (tp + fn + 1e-4)} (lines 285-298), "meters" {name: {"sum", "count", "avg", "val"}} (the AverageMeter fields), and
         "last": the tables of the last call alone"""
         counts, last = self.counts_totals.cpu().numpy(), self.counts_last.cpu().numpy()
-        tot, lm = self.meters_totals.cpu(), self.meters_last.cpu()
         out, conf = eval_tables_from_counts(counts)
         out["confusion"] = conf
         out["precision"] = {k: out[k][:, 0] / (out[k][:, 0] + out[k][:, 2] + 1e-4) for k in EVAL_TABLES}
         out["recall"] = {k: out[k][:, 0] / (out[k][:, 0] + out[k][:, 3] + 1e-4) for k in EVAL_TABLES}
         out["last"] = eval_tables_from_counts(last)[0]
-        meters = {}
-        for i, n in enumerate(METER_NAMES):
-            s, c = tot[i, 0].item(), tot[i, 1].item()
-            ln, ld = lm[i, 0].item(), lm[i, 1].item()
-            meters[n] = {"sum": s, "count": c, "avg": s / c if c else float("nan"), "val": ln / ld if ld else float("nan")}
-        out["meters"] = meters
+        out["meters"] = meters_dict(self.meters_totals, self.meters_last)
         return out
 
 
@@ -326,15 +315,14 @@ def nms_peaks(atom, bond, rho, omega):
         raise ValueError("nms_peaks: atom and bond must be [B,1,h,w] and rho and omega [B,n,h,w] with the same B, h, w and n; got "
                          "atom %s, bond %s, rho %s, omega %s" % tuple(shapes))
     for t in (atom, bond, rho, omega):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-            raise L.AbcNetHipError("nms_peaks wants contiguous f32 device tensors (no CPU fallback)")
+        require_device_tensor(t, torch.float32, "nms_peaks: every map")
     lib = L.load()
     am, bm, r, om = torch.empty_like(atom), torch.empty_like(bond), torch.empty_like(rho), torch.empty_like(omega)
     d = L.NmsDesc()
     d.atom, d.bond, d.rho, d.omega = atom.data_ptr(), bond.data_ptr(), rho.data_ptr(), omega.data_ptr()
     d.B, d.h, d.w, d.n_omega = B, h, w, n
     d.atom_mask, d.bond_mask, d.rho_abs, d.omega_mask = am.data_ptr(), bm.data_ptr(), r.data_ptr(), om.data_ptr()
-    L.check(lib.abc_nms_peaks(C.byref(d), torch.cuda.current_stream().cuda_stream), "nms_peaks")
+    L.check(lib.abc_nms_peaks(C.byref(d), current_stream()), "nms_peaks")
     return am, bm, r, om
 
 
@@ -360,14 +348,10 @@ class PeakExtractor:
             raise ValueError("PeakExtractor: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
         self.omega_rule = omega_rule
         if len(logits) != 8 or logits[0] is None:
-            raise ValueError("PeakExtractor wants the 8 head maps of heads %s, got %d" % (EXTRACT_HEADS, len(logits)))
+            raise ValueError("PeakExtractor wants the 8 head maps of heads %s, got %d" % (list(HEADS), len(logits)))
         B, _, h, w = logits[0].shape
-        for i, (t, c) in enumerate(zip(logits, EXTRACT_HEADS)):
-            if t is None and ((i == 5 and btype_idx is not None) or (i == 6 and rho_abs is not None)):
-                continue
-            if t is None or tuple(t.shape) != (B, c, h, w):
-                raise ValueError("PeakExtractor: head %d must be [%d, %d, %d, %d] (heads %s), got %s"
-                                 % (i, B, c, h, w, EXTRACT_HEADS, None if t is None else tuple(t.shape)))
+        optional = ({5} if btype_idx is not None else set()) | ({6} if rho_abs is not None else set())
+        check_head_maps(logits, B, h, w, optional, "PeakExtractor")
         for name, t, c in (("atom_mask", atom_mask, 1), ("bond_mask", bond_mask, 1), ("rho_abs", rho_abs, 60)):
             if t is not None and tuple(t.shape) != (B, c, h, w):
                 raise ValueError("PeakExtractor: %s must be [%d, %d, %d, %d], got %s" % (name, B, c, h, w, tuple(t.shape)))
@@ -375,13 +359,11 @@ class PeakExtractor:
             raise ValueError("PeakExtractor: btype_idx must be [%d, 60, %d, %d], got %s" % (B, h, w, tuple(btype_idx.shape)))
         lib = L.load()
         self.lib = lib
-        need = [t for i, t in enumerate(logits) if not ((i == 5 and btype_idx is not None) or (i == 6 and rho_abs is not None))]
+        need = [t for i, t in enumerate(logits) if i not in optional]
         for t in need + [atom_mask, bond_mask] + ([rho_abs] if rho_abs is not None else []):
-            if t is None or not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-                raise L.AbcNetHipError("PeakExtractor wants contiguous f32 device tensors (no CPU fallback)")
-        if btype_idx is not None and not (btype_idx.is_cuda and btype_idx.is_contiguous() and btype_idx.dtype == torch.uint8 and
-                                          tuple(btype_idx.shape) == (B, 60, h, w)):
-            raise L.AbcNetHipError("PeakExtractor: btype_idx must be a contiguous uint8 device tensor [B, 60, h, w]")
+            require_device_tensor(t, torch.float32, "PeakExtractor: every mask and head map read")
+        if btype_idx is not None:
+            require_device_tensor(btype_idx, torch.uint8, "PeakExtractor: btype_idx")
         dev = logits[0].device
         d = L.ExtractDesc()
         d.atom_mask, d.bond_mask = atom_mask.data_ptr(), bond_mask.data_ptr()
@@ -404,9 +386,7 @@ class PeakExtractor:
         self.B, self.cap_atoms, self.cap_bonds = B, cap_atoms, cap_bonds
 
     def run(self, stream=None):
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        L.check(self.lib.abc_extract_peaks(C.byref(self.d), stream), "extract_peaks")
+        L.check(self.lib.abc_extract_peaks(C.byref(self.d), stream_or_current(stream)), "extract_peaks")
 
     def lists(self):
         """per image: dict(atoms int32 [n,5], bonds int32 [m,4], rho f32 [m], counts (4,), truncated bool) on the host"""
@@ -438,9 +418,9 @@ class GraphAssembler:
         tensors of PeakExtractor's layout (its own buffers, or hand-made lists).  cap_mol_bonds: bonds kept per image (default
         4 * cap_atoms, at most cap_bonds); more are reported as `truncated`."""
         from .decode import omega_table
-        for t, dt in ((counts, torch.int32), (atoms, torch.int32), (bonds, torch.int32), (bond_rho, torch.float32)):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == dt):
-                raise L.AbcNetHipError("GraphAssembler wants contiguous int32 / f32 device tensors of the extractor's layout (no CPU fallback)")
+        for name, t, dt in (("counts", counts, torch.int32), ("atoms", atoms, torch.int32), ("bonds", bonds, torch.int32),
+                            ("bond_rho", bond_rho, torch.float32)):
+            require_device_tensor(t, dt, "GraphAssembler: %s (the extractor's layout)" % name)
         if atoms.dim() != 3 or atoms.shape[2] != 5 or bonds.dim() != 3 or bonds.shape[2] != 4:
             raise ValueError("GraphAssembler: atoms must be [B, cap_atoms, 5] and bonds [B, cap_bonds, 4], got %s and %s"
                              % (tuple(atoms.shape), tuple(bonds.shape)))
@@ -473,9 +453,7 @@ class GraphAssembler:
         return cls(ex.counts, ex.atoms, ex.bonds, ex.bond_rho, cap_mol_bonds=cap_mol_bonds)
 
     def run(self, stream=None):
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        L.check(self.lib.abc_assemble_graphs(C.byref(self.d), stream), "assemble_graphs")
+        L.check(self.lib.abc_assemble_graphs(C.byref(self.d), stream_or_current(stream)), "assemble_graphs")
 
     def molecules(self):
         """per image: a decode.Molecule, or None for an image without an atom peak or without a bond peak (host sync)"""
@@ -526,17 +504,15 @@ class GraphScore:
         if n_valid is not None and not (isinstance(n_valid, torch.Tensor) and n_valid.numel() == 1):
             raise ValueError("GraphScore: n_valid must be a one-element int32 device tensor")
         for t in (mol_counts, mol_atoms, mol_bonds) + (() if n_valid is None else (n_valid,)):
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32):
-                raise L.AbcNetHipError("GraphScore wants contiguous int32 device tensors of the assembler's layout (no CPU fallback)")
+            require_device_tensor(t, torch.int32, "GraphScore: mol_counts, mol_atoms, mol_bonds (the assembler's layout) and n_valid")
         self.lib = L.load()
         dev = mol_atoms.device
         self.B, self.cap_atoms, self.cap_mol_bonds = B, cap_atoms, cap_mol_bonds
         self.max_atoms, self.max_bonds, self.radius = max_atoms, max_bonds, radius
-        pin = dict(pin_memory=True)
-        self.h_atoms = torch.zeros((B, max_atoms, 4), dtype=torch.int32, **pin)
-        self.h_bonds = torch.zeros((B, max_bonds, 3), dtype=torch.int32, **pin)
-        self.h_cnt = torch.zeros((2, B), dtype=torch.int32, **pin)
-        self.d_atoms, self.d_bonds, self.d_cnt = self.h_atoms.to(dev), self.h_bonds.to(dev), self.h_cnt.to(dev)
+        self.staging = PinnedStaging(dev, {"atoms": ((B, max_atoms, 4), torch.int32), "bonds": ((B, max_bonds, 3), torch.int32),
+                                           "cnt": ((2, B), torch.int32)})
+        self.h_atoms, self.h_bonds, self.h_cnt = self.staging.host.values()
+        self.d_atoms, self.d_bonds, self.d_cnt = self.staging.dev.values()
         self.rows = torch.zeros((B, len(L.GRAPH_SCORE_COLUMNS)), dtype=torch.int32, device=dev)
         # (uint64 on the device; int64 here: the sums stay far below 2^63)
         self.totals = torch.zeros(len(L.GRAPH_SCORE_COLUMNS), dtype=torch.int64, device=dev)
@@ -548,7 +524,6 @@ class GraphScore:
         d.rows, d.totals = self.rows.data_ptr(), self.totals.data_ptr()
         self.d, self.keep = d, (mol_counts, mol_atoms, mol_bonds, n_valid)
         self.loaded = False
-        self._copied = None
 
     @classmethod
     def from_assembler(cls, asm, max_atoms=256, max_bonds=256, radius=0, n_valid=None):
@@ -556,7 +531,7 @@ class GraphScore:
 
     def load(self, graphs):
         """graphs = list of n <= B (atoms [k, 4], bonds [m, 3]) pairs from raster.parse_graph; the rows past n get an empty record.
-        Asynchronous H2D of a few KB through pinned staging (as TargetRasterizer.load)."""
+        Asynchronous H2D of a few KB through pinned staging."""
         import numpy as np
         if len(graphs) > self.B:
             raise ValueError("expected at most %d graph records, got %d" % (self.B, len(graphs)))
@@ -570,9 +545,7 @@ class GraphScore:
             if len(q) and not ((0 <= q[:, 0]) & (q[:, 0] < q[:, 1]) & (q[:, 1] < len(a))).all():
                 raise ValueError("record %d: every bond must name atoms 0 <= i < j < %d" % (b, len(a)))
             recs.append((np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(q, dtype=np.int32)))
-        # the pinned staging is reused: the previous load's asynchronous copies must have left it (TargetRasterizer.load)
-        if self._copied is not None:
-            self._copied.synchronize()
+        self.staging.wait()
         self.h_cnt.zero_()
         for b, (a, q) in enumerate(recs):
             self.h_cnt[0, b], self.h_cnt[1, b] = len(a), len(q)
@@ -580,17 +553,11 @@ class GraphScore:
                 self.h_atoms[b, :len(a)] = torch.from_numpy(a)
             if len(q):
                 self.h_bonds[b, :len(q)] = torch.from_numpy(q)
-        self.d_atoms.copy_(self.h_atoms, non_blocking=True)
-        self.d_bonds.copy_(self.h_bonds, non_blocking=True)
-        self.d_cnt.copy_(self.h_cnt, non_blocking=True)
-        self._copied = torch.cuda.Event()
-        self._copied.record(torch.cuda.current_stream(self.d_cnt.device))
+        self.staging.commit()
         self.loaded = True
 
     def run(self, stream=None):
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        L.check(self.lib.abc_graph_score_update(C.byref(self.d), stream), "graph_score_update")
+        L.check(self.lib.abc_graph_score_update(C.byref(self.d), stream_or_current(stream)), "graph_score_update")
 
     def reset(self):
         self.totals.zero_()
@@ -606,6 +573,34 @@ class GraphScore:
             out[share] = out[num] / out[den] if out[den] else float("nan")
         out["rows"] = self.rows.cpu().numpy()
         return out
+
+
+def timed(stream, marks, label, flops, nbytes, fn, operand_bytes=None):
+    """profile(): fn() between a HIP event pair recorded on `stream` (a torch stream, the one fn launches on); the pair and the
+    launch's accounting go to `marks`.  Returns what fn returned."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    rc = fn()
+    e1.record(stream)
+    marks.append((label, e0, e1, {"flops": flops, "bytes": nbytes, "operand_bytes": nbytes if operand_bytes is None else operand_bytes}))
+    return rc
+
+
+def fold_marks(acc, marks, fields):
+    """profile(), after a device sync: add every mark of one iteration to acc[label] = {"calls", "ms", *fields}"""
+    for label, e0, e1, cost in marks:
+        r = acc.setdefault(label, dict({"calls": 0, "ms": 0.0}, **{f: 0.0 for f in fields}))
+        r["calls"] += 1
+        r["ms"] += e0.elapsed_time(e1)
+        for f in fields:
+            r[f] += cost[f]
+
+
+def per_iteration(acc, iters):
+    for r in acc.values():
+        for f in r:
+            r[f] /= iters
+    return acc
 
 
 class FusedAdam:
@@ -625,6 +620,4 @@ class FusedAdam:
         self.d = d
 
     def step(self, stream=None):
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        L.check(self.lib.abc_adam_step(C.byref(self.d), stream), "adam_step")
+        L.check(self.lib.abc_adam_step(C.byref(self.d), stream_or_current(stream)), "adam_step")

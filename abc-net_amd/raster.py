@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .contract import PinnedStaging, alloc_targets, check_targets, set_target_ptrs, stream_or_current
 
 ATOM_VOCAB = {'<unkonw>': 0, 'C': 1, 'N': 2, 'O': 3, 'P': 4, 'F': 5, 'Cl': 6, 'S': 7, 'Br': 8, 'B': 9,
               'Se': 10, 'I': 11, 'H': 12, 'Si': 13}        # utils.py:12-13
@@ -135,26 +136,19 @@ class TargetRasterizer:
             raise L.AbcNetHipError("TargetRasterizer needs an MI355X; abcnet_amd has no CPU fallback")
         self.lib = L.load()
         B = batch
-        shapes = [(B, 1, h, w), (B, 14, h, w), (B, 3, h, w), (B, 2, h, w), (B, 1, h, w), (B, 6, 60, h, w), (B, 60, h, w), (B, 60, h, w)]
-        dts = [torch.float32] * 6 + [torch.float64] * 2
         if targets is None:
-            targets = [torch.zeros(s, dtype=dt, device=device) for s, dt in zip(shapes, dts)]
-        for t, s, dt in zip(targets, shapes, dts):
-            if tuple(t.shape) != s or t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
-                raise L.AbcNetHipError("raster: target %s %s does not match the contract %s %s on the device" % (tuple(t.shape), t.dtype, s, dt))
+            targets = alloc_targets(B, h, w, device)
+        check_targets(targets, B, h, w, "raster", L.AbcNetHipError)
         self.targets = list(targets)
         dev = targets[0].device
         self.B, self.h, self.w, self.max_atoms, self.max_bonds = B, h, w, max_atoms, max_bonds
         # host staging (pinned) + device record buffers
-        pin = dict(pin_memory=True)
-        self.h_atoms = torch.zeros((B, max_atoms, 5), dtype=torch.int32, **pin)
-        self.h_bonds = torch.zeros((B, max_bonds, 5), dtype=torch.int32, **pin)
-        self.h_rho = torch.zeros((B, max_bonds), dtype=torch.float64, **pin)
-        self.h_cnt = torch.zeros((2, B), dtype=torch.int32, **pin)
-        self.d_atoms, self.d_bonds = self.h_atoms.to(dev), self.h_bonds.to(dev)
-        self.d_rho, self.d_cnt = self.h_rho.to(dev), self.h_cnt.to(dev)
+        self.staging = PinnedStaging(dev, {"atoms": ((B, max_atoms, 5), torch.int32), "bonds": ((B, max_bonds, 5), torch.int32),
+                                           "rho": ((B, max_bonds), torch.float64), "cnt": ((2, B), torch.int32)})
+        self.h_atoms, self.h_bonds, self.h_rho, self.h_cnt = self.staging.host.values()
+        self.d_atoms, self.d_bonds, self.d_rho, self.d_cnt = self.staging.dev.values()
         d = L.RasterDesc()
-        (d.t_atom, d.t_types, d.t_charges, d.t_hs, d.t_bond, d.t_btypes, d.t_rho, d.t_omega) = (t.data_ptr() for t in self.targets)
+        set_target_ptrs(d, self.targets)
         d.B, d.h, d.w, d.max_atoms, d.max_bonds = B, h, w, max_atoms, max_bonds
         d.atoms, d.bonds, d.rho = self.d_atoms.data_ptr(), self.d_bonds.data_ptr(), self.d_rho.data_ptr()
         d.n_atoms, d.n_bonds = self.d_cnt[0].data_ptr(), self.d_cnt[1].data_ptr()
@@ -179,32 +173,22 @@ class TargetRasterizer:
         """records = list of B (atoms, bonds, rho) triples from parse_record; async H2D of a few KB"""
         if len(records) != self.B:
             raise ValueError("expected %d records" % self.B)
-        # the pinned staging buffers are reused: the previous load's asynchronous copies must have left them before they are
-        # overwritten (a loop that never syncs runs many steps ahead of the device -- the maps would be rasterised from a
-        # LATER batch's records)
-        if getattr(self, "_copied", None) is not None:
-            self._copied.synchronize()
-        for b, (a, q, r) in enumerate(records):
+        for b, (a, q, _r) in enumerate(records):
             if len(a) > self.max_atoms or len(q) > self.max_bonds:
                 raise ValueError("record %d has %d atoms / %d bonds (capacity %d / %d)" % (b, len(a), len(q), self.max_atoms, self.max_bonds))
+        self.staging.wait()
+        for b, (a, q, r) in enumerate(records):
             self.h_cnt[0, b], self.h_cnt[1, b] = len(a), len(q)
             if len(a):
                 self.h_atoms[b, :len(a)] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
             if len(q):
                 self.h_bonds[b, :len(q)] = torch.from_numpy(np.ascontiguousarray(q, dtype=np.int32))
                 self.h_rho[b, :len(q)] = torch.from_numpy(np.ascontiguousarray(r, dtype=np.float64))
-        self.d_atoms.copy_(self.h_atoms, non_blocking=True)
-        self.d_bonds.copy_(self.h_bonds, non_blocking=True)
-        self.d_rho.copy_(self.h_rho, non_blocking=True)
-        self.d_cnt.copy_(self.h_cnt, non_blocking=True)
-        self._copied = torch.cuda.Event()
-        self._copied.record(torch.cuda.current_stream(self.d_cnt.device))
+        self.staging.commit()
 
     def run(self, stream=None):
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
         if self.sparse:
             self.d.incremental = 1 if self._drawn else 0
-        L.check(self.lib.abc_rasterize_targets(C.byref(self.d), stream), "rasterize_targets")
+        L.check(self.lib.abc_rasterize_targets(C.byref(self.d), stream_or_current(stream)), "rasterize_targets")
         self._drawn = True
         return self.targets

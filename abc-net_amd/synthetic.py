@@ -12,6 +12,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .contract import alloc_targets
+
 
 def synthetic_images(batch: int, size: int, seed: int = 7, p: float = 0.1, in_channels: int = 1):
     """Bernoulli(p) ink in {0,1}, f32 [B,C,S,S] (ink = 1)."""
@@ -26,14 +28,7 @@ def synthetic_targets(batch: int, h: int, seed: int = 1, n_atoms: int = 30, n_bo
     bond_types[B,6,60,h,h] f32, bond_rhos[B,60,h,h] f64, bond_omega[B,60,h,h] f64."""
     g = torch.Generator().manual_seed(seed)
     ri = lambda hi, n: torch.randint(0, hi, (n,), generator=g).tolist()
-    at = torch.zeros(batch, 1, h, h)
-    aty = torch.zeros(batch, 14, h, h)
-    ach = torch.zeros(batch, 3, h, h)
-    ahs = torch.zeros(batch, 2, h, h)
-    bt = torch.zeros(batch, 1, h, h)
-    bty = torch.zeros(batch, 6, 60, h, h)
-    rho = torch.zeros(batch, 60, h, h, dtype=torch.float64)
-    om = torch.zeros(batch, 60, h, h, dtype=torch.float64)
+    at, aty, ach, ahs, bt, bty, rho, om = alloc_targets(batch, h, h, "cpu")
     for b in range(batch):
         xs, ys = ri(h, n_atoms), ri(h, n_atoms)
         ty, ch, hs = ri(14, n_atoms), ri(3, n_atoms), ri(3, n_atoms)

@@ -15,8 +15,8 @@ import torch
 
 from . import _lib as L
 from . import distributed as D
-from .arch import TRAIN_HEADS
-from .ops import FusedAdam, FusedHeadsLoss, FusedLoss, FusedMetrics
+from .contract import HEADS, alloc_targets, check_sparse_rasterizer, current_stream, refuse_dense_targets, resolve_device
+from .ops import FusedAdam, FusedHeadsLoss, FusedLoss, FusedMetrics, fold_marks, meters_dict, per_iteration, timed
 
 
 class Trainer:
@@ -49,20 +49,13 @@ class Trainer:
         fused_convt=False: the ConvTranspose forward as four batched phase convolutions (Engine(fused_convt=...): the A/B of convt_fused.hip).
         force_exchange: segment the plan and run the bucket exchanges although the group has one rank (testing RCCL's launch
         mechanics between graph segments on a one-GPU box)."""
-        if list(model.heads) != TRAIN_HEADS:
+        if tuple(model.heads) != HEADS:
             # (the fused loss, the meters and the fused heads pass read the maps of train.py:47; other lists train through the
             #  module's autograd, forward() + loss.backward())
             raise ValueError("Trainer: the fused training step is defined for heads %s (train.py:47), got heads %s"
-                             % (TRAIN_HEADS, list(model.heads)))
-        if not torch.cuda.is_available():
-            raise L.AbcNetHipError("Trainer needs an MI355X; abcnet_amd has no CPU fallback")
+                             % (list(HEADS), list(model.heads)))
+        self.dev = dev = resolve_device(model, device, "Trainer")
         self.model = model
-        dev = torch.device(device or next(model.parameters()).device)
-        if dev.type != "cuda":
-            raise L.AbcNetHipError("Trainer: the model must live on a GPU (got %s); abcnet_amd has no CPU fallback" % dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.dev = dev
         dist_on = torch.distributed.is_initialized()
         self.world = torch.distributed.get_world_size(process_group) if dist_on else 1
         self.rank = torch.distributed.get_rank(process_group) if dist_on else 0
@@ -83,11 +76,7 @@ class Trainer:
             self.eng = model._engine_for(x0, True, fused_heads=fused_heads, batched_heads=batched_heads, guards=guards,
                                          actbwd_epilogue=actbwd_epilogue, merge_reduce=merge_reduce, dual_wgrad=dual_wgrad, fused_convt=fused_convt)
         eng = self.eng
-        h, w = eng.h, eng.w
-        B = batch
-        shapes = [(B, 1, h, w), (B, 14, h, w), (B, 3, h, w), (B, 2, h, w), (B, 1, h, w), (B, 6, 60, h, w), (B, 60, h, w), (B, 60, h, w)]
-        dts = [torch.float32] * 6 + [torch.float64] * 2
-        self.targets = [torch.zeros(s, dtype=dt, device=dev) for s, dt in zip(shapes, dts)]
+        self.targets = alloc_targets(batch, eng.h, eng.w, dev)
         off_s, _ = model._lay_p["s"]
         extra = {"keep_logits": bool(keep_logits or metrics)} if eng.hf is not None else {}
         self.loss = (FusedHeadsLoss if eng.hf is not None else FusedLoss)(
@@ -131,9 +120,7 @@ class Trainer:
         self.eng.img.copy_(imgs.reshape(self.eng.img.shape), non_blocking=True)
         if targets is None:
             return
-        if getattr(self, "_rasterizer", None) is not None:
-            raise L.AbcNetHipError("load_batch(dense targets) under use_sparse_targets(): the rasteriser's group flags would no longer "
-                                   "describe the maps; load records into the rasteriser, or call use_sparse_targets(None) first")
+        refuse_dense_targets(getattr(self, "_rasterizer", None))
         for dst, src in zip(self.targets, targets):
             dst.copy_(src, non_blocking=True)
 
@@ -152,8 +139,7 @@ class Trainer:
             self.loss.use_target_flags(None)
             self._rasterizer = None
         else:
-            if not getattr(rasterizer, "sparse", False) or any(a.data_ptr() != b.data_ptr() for a, b in zip(rasterizer.targets, self.targets)):
-                raise L.AbcNetHipError("use_sparse_targets: a TargetRasterizer(sparse=True) over this Trainer's own target tensors")
+            check_sparse_rasterizer(rasterizer, self.targets, "Trainer")
             self.loss.use_target_flags(rasterizer.group_flags)
             self._rasterizer = rasterizer
         self._graphs = None
@@ -195,7 +181,7 @@ class Trainer:
         return segs
 
     def _run_segment(self, k):
-        st = torch.cuda.current_stream(self.dev).cuda_stream
+        st = current_stream(self.dev)
         for fn in self._segments[k]:
             fn(st)
 
@@ -283,7 +269,6 @@ class Trainer:
         (sync_buffers(): a COLLECTIVE when world > 1, so every rank has to call evaluate(), as every rank runs the reference's
         eval loop).  One host sync at the end.  Returns {meter: {"sum", "count", "avg": over all ranks' images,
         "rank_mean": the reference's mean of per-rank averages}}."""
-        from .ops import METER_NAMES
         model, eng_t = self.model, self.eng
         with torch.cuda.device(self.dev):
             if self.world > 1 and self.broadcast_buffers:
@@ -295,7 +280,7 @@ class Trainer:
                 tg = [torch.zeros_like(t) for t in self.targets]
                 self._eval = (eng, tg, FusedMetrics(eng.logits, tg))
             eng, tg, meters = self._eval
-            st = torch.cuda.current_stream().cuda_stream
+            st = current_stream()
             meters.reset()
             eng.run_pack(st)                    # the weights moved since the last call: re-pack (and re-fold BatchNorm) once
             for imgs, targets in batches:
@@ -305,12 +290,7 @@ class Trainer:
                 eng.run_forward(st)
                 meters.run(st)
             glob, rank_mean = D.reduce_meters(meters.totals, self.group)
-            glob, rank_mean = glob.cpu(), rank_mean.cpu()
-        out = {}
-        for i, n in enumerate(METER_NAMES):
-            s, c = glob[i, 0].item(), glob[i, 1].item()
-            out[n] = {"sum": s, "count": c, "avg": s / c if c else float("nan"), "rank_mean": rank_mean[i].item()}
-        return out
+        return meters_dict(glob, extra={"rank_mean": rank_mean})
 
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self):
@@ -359,48 +339,28 @@ class Trainer:
         torch.cuda.set_device(self.dev)
         stream = torch.cuda.current_stream(self.dev)
         st = stream.cuda_stream
-        groups = [eng.pack_ops, eng.fwd_ops, None, eng.bwd_ops]
         acc = {}
         by_op = os.environ.get("ABC_BENCH_OPS")  # (diagnostics: one row per launch label instead of per kernel)
+        n_px = eng.B * eng.h * eng.w
+        if eng.hf is not None:   # features read twice, targets, logits + blocked d(logits) + g written
+            loss_cost = ("heads_fused+finalize", 2.0 * 2 * n_px * 128 * 501, float(n_px * (1024 * 2 * 3 + 501 * 4 + 768 * 2 + 381 * 4 + 120 * 8)))
+        else:
+            loss_cost = ("loss_fwd_bwd+finalize", 0.0, float(n_px * (501 * 4 * 2 + 381 * 4 + 120 * 8)))
+
+        def launches(ops):
+            for fn, args, what, _w, meta in ops:
+                L.check(timed(stream, marks, meta["kernel"] + " | " + what if by_op else meta["kernel"], meta["flops"], meta["bytes"],
+                              lambda: fn(*args, st), meta.get("operand_bytes")), what)
+
         for _ in range(iters):
             marks = []
-            for ops in groups:
-                if ops is None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(stream)
-                    self.loss.run(st)
-                    e1.record(stream)
-                    if eng.hf is not None:   # features read twice, targets, logits + blocked d(logits) + g written
-                        marks.append(("heads_fused+finalize", 2.0 * 2 * eng.B * eng.h * eng.w * 128 * 501,
-                                      float(eng.B * eng.h * eng.w * (1024 * 2 * 3 + 501 * 4 + 768 * 2 + 381 * 4 + 120 * 8)), e0, e1))
-                    else:
-                        marks.append(("loss_fwd_bwd+finalize", 0.0, float(eng.B * eng.h * eng.w * (501 * 4 * 2 + 381 * 4 + 120 * 8)), e0, e1))
-                    continue
-                for fn, args, what, _w, meta in ops:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(stream)
-                    rc = fn(*args, st)
-                    e1.record(stream)
-                    if rc != 0:
-                        L.check(rc, what)
-                    marks.append((meta["kernel"] + " | " + what if by_op else meta["kernel"], meta["flops"], meta["bytes"], e0, e1,
-                                  meta.get("operand_bytes", meta["bytes"])))
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            self.opt.step(st)
-            e1.record(stream)
-            marks.append(("adam", 0.0, float(self.model._flat.numel() * 28), e0, e1))
+            launches(eng.pack_ops)
+            launches(eng.fwd_ops)
+            timed(stream, marks, *loss_cost, lambda: self.loss.run(st))
+            launches(eng.bwd_ops)
+            timed(stream, marks, "adam", 0.0, float(self.model._flat.numel() * 28), lambda: self.opt.step(st))
             torch.cuda.synchronize()
-            for mk in marks:
-                k, fl, by, a, b = mk[:5]
-                r = acc.setdefault(k, {"calls": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0, "operand_bytes": 0.0})
-                r["calls"] += 1
-                r["ms"] += a.elapsed_time(b)
-                r["flops"] += fl
-                r["bytes"] += by
-                r["operand_bytes"] += mk[5] if len(mk) > 5 else by
-        for r in acc.values():
-            for f in ("calls", "ms", "flops", "bytes", "operand_bytes"):
-                r[f] /= iters
+            fold_marks(acc, marks, ("flops", "bytes", "operand_bytes"))
+        per_iteration(acc, iters)
         self.steps += iters
         return acc
