@@ -319,6 +319,9 @@ SYMBOLS = {
     "abc_fp8_weight_scales": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp]),
     "abc_concat_f32": (C.c_int, [vp, vp, i32, vp, vp]),
     "abc_counter_add_u32": (C.c_int, [vp, u32, vp]),
+    "abc_grad_pack_bf16": (C.c_int, [vp, vp, i64, vp]),
+    "abc_grad_reduce_bf16": (C.c_int, [vp, vp, i32, i64, vp]),
+    "abc_grad_unpack_bf16": (C.c_int, [vp, vp, i64, vp]),
     "abc_pool_act": (C.c_int, [vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "abc_sizeof": (C.c_int, [C.c_int]),
     "abc_last_error": (C.c_char_p, []),

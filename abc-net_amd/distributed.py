@@ -201,15 +201,31 @@ class GradReducer:
 
     Whatever the mode, every rank ends with bit-identical sums (each shard is reduced by ONE rank, then copied).  The chosen
     mode is self-checked once against all_reduce on a small tensor at construction (a collective: all ranks construct the
-    reducer together, as they construct the Trainer); a mode the backend does not serve falls back to "all_reduce"."""
+    reducer together, as they construct the Trainer); a mode the backend does not serve falls back to "all_reduce".
+
+    wire_dtype "bf16" (mode "direct" only; opt-in): both legs carry 2 bytes per element.  Per bucket g[lo:hi] of W x n elements,
+    on the communication stream: send = bf16(g[lo:hi]) (round-to-nearest-even); all_to_all_single; this rank's shard =
+    bf16(((f32(row 0) + f32(row 1)) + ...) + f32(row W-1)), plain f32 adds of the received rows in rank order;
+    all_gather_into_tensor; g[lo:hi] = f32(gathered), this rank's own shard included -- so every rank still ends with
+    bit-identical gradients.  Pack, sum and unpack are one launch each of csrc/exchange.hip (abc_grad_pack_bf16,
+    abc_grad_reduce_bf16, abc_grad_unpack_bf16); on CPU tensors (the gloo test path) the same arithmetic in torch ops.  The
+    gradients are rounded to bf16 twice: |result - sum_q g_q| <= 2^-9 (sum_q |g_q| + |sum_q g_q|) plus the f32 summation error
+    (DESIGN.md section 5)."""
 
     MODES = ("rs_ag", "direct", "all_reduce")
+    WIRE_DTYPES = ("f32", "bf16")
+    MAX_BF16_WORLD = 64      # abc_grad_reduce_bf16 takes up to 64 rows
 
-    def __init__(self, flat_grad, buckets, group=None, mode="rs_ag", force=False):
+    def __init__(self, flat_grad, buckets, group=None, mode="rs_ag", force=False, wire_dtype="f32"):
         """force: run the exchange although the group has ONE rank (a sum over one rank: the identity) -- the RCCL launch
-        mechanics between the hipGraph segments on a one-GPU box (tests/rccl_world1_worker.py)"""
+        mechanics between the hipGraph segments on a one-GPU box (tests/rccl_world1_worker.py)
+        wire_dtype: "f32", or "bf16" with mode "direct"; .wire_dtype tells what actually runs ("f32" after a fallback)"""
         if mode not in self.MODES:
             raise ValueError("GradReducer mode %r" % (mode,))
+        if wire_dtype not in self.WIRE_DTYPES:
+            raise ValueError("GradReducer wire_dtype %r" % (wire_dtype,))
+        if wire_dtype == "bf16" and mode != "direct":
+            raise ValueError("GradReducer wire_dtype 'bf16' needs mode 'direct' (RCCL's own reductions would accumulate in bf16), got mode %r" % (mode,))
         self.g, self.buckets, self.group = flat_grad, buckets, group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -225,19 +241,34 @@ class GradReducer:
         for b in buckets:
             self.by_ready.setdefault(b[2], []).append(b)
         self.mode = "all_reduce"
+        self.wire_dtype = "f32"
         self.fallback_reason = None
         self.active = self.world > 1 or (bool(force) and dist.is_initialized())
+        self._stage = self._wire = None
         if self.active and mode != "all_reduce":
             if any((hi - lo) % self.world for lo, hi, _ in buckets):
                 self.fallback_reason = "bucket sizes do not divide by the world size"
+            elif wire_dtype == "bf16" and self.world > self.MAX_BF16_WORLD:
+                self.fallback_reason = "the bf16 exchange sums at most %d ranks' rows" % self.MAX_BF16_WORLD
+            elif wire_dtype == "bf16" and flat_grad.dtype != torch.float32:
+                self.fallback_reason = "the bf16 exchange takes f32 gradients"
             else:
-                self._stage = None
-                if mode == "direct":
+                largest = max([64 * self.world] + [hi - lo for lo, hi, _ in buckets])
+                if wire_dtype == "bf16":
+                    # send, receive and gather buffers of the largest bucket, allocated HERE and never in bucket_ready(): memory the
+                    # caching allocator hands out on the side stream would need record_stream bookkeeping.  Real bf16 tensors: gloo
+                    # serves both collectives for bf16 and refuses int16.
+                    self._wire = tuple(torch.empty(largest, dtype=torch.bfloat16, device=self.dev) for _ in range(3))
+                    if self.cuda:
+                        from . import _lib
+                        self._lib, self._abi = _lib.load(), _lib
+                elif mode == "direct":
                     self._stage = torch.empty(max(hi - lo for lo, hi, _ in buckets), dtype=flat_grad.dtype, device=self.dev)
-                self.mode = mode
+                self.mode, self.wire_dtype = mode, wire_dtype
                 self.fallback_reason = self._self_check()
                 if self.fallback_reason is not None:
-                    self.mode = "all_reduce"
+                    self.mode, self.wire_dtype = "all_reduce", "f32"
+                    self._stage = self._wire = None
 
     # -- one bucket, synchronous on the current (communication) stream / thread
     def _exchange(self, view, mode, stage=None):
@@ -255,20 +286,63 @@ class GradReducer:
             torch.sum(recv.view(w, n), dim=0, out=shard)       # rows in rank order on every rank: a fixed summation order
         dist.all_gather_into_tensor(view, shard, group=self.group)
 
+    def _exchange_bf16(self, view):
+        """one bucket over the bf16 wire (class docstring): pack, all-to-all, rank-ordered f32 sum, all-gather, unpack"""
+        w, r = self.world, self.rank
+        total = view.numel()
+        n = total // w
+        send, recv, gath = (t[:total] for t in self._wire)
+        shard = gath[r * n:(r + 1) * n]
+        if self.cuda:
+            lib, abi = self._lib, self._abi
+            st = torch.cuda.current_stream(self.dev).cuda_stream
+            abi.check(lib.abc_grad_pack_bf16(view.data_ptr(), send.data_ptr(), total, st), "grad_pack_bf16")
+            dist.all_to_all_single(recv, send, group=self.group)
+            abi.check(lib.abc_grad_reduce_bf16(recv.data_ptr(), shard.data_ptr(), w, n, st), "grad_reduce_bf16")
+            dist.all_gather_into_tensor(gath, shard, group=self.group)
+            abi.check(lib.abc_grad_unpack_bf16(gath.data_ptr(), view.data_ptr(), total, st), "grad_unpack_bf16")
+        else:      # CPU tensors over gloo (the device-agnostic test path of this class): the same arithmetic in torch ops
+            send.copy_(view.to(torch.bfloat16))
+            dist.all_to_all_single(recv, send, group=self.group)
+            acc = recv[:n].float()
+            for q in range(1, w):                      # rows in rank order on every rank: a fixed summation order
+                acc = acc + recv[q * n:(q + 1) * n].float()
+            shard.copy_(acc.to(torch.bfloat16))
+            dist.all_gather_into_tensor(gath, shard, group=self.group)
+            view.copy_(gath.float())
+
+    def wire_bytes_per_step(self, world=None):
+        """bytes THIS rank sends per step over both legs of the exchange, (W - 1) / W x elements x bytes per element and leg, summed
+        over the buckets (0 when nothing is exchanged).  Arithmetic on the plan, not a measurement.  world: evaluate the formula
+        for another world size over the same buckets (the tool's W = 2, 4, 8 table on a one-GPU box)."""
+        w = self.world if world is None else int(world)
+        if world is None and not self.active:
+            return 0
+        b = 2 if self.wire_dtype == "bf16" else self.g.element_size()
+        return sum(2 * (w - 1) * (hi - lo) * b // w for lo, hi, _ in self.buckets)
+
     def _self_check(self):
         """the chosen mode against all_reduce, first on 64 x world elements (does the backend serve it at all?), then on
         a scratch tensor of every DISTINCT REAL bucket size of the plan (the aliased in-place collectives at the sizes, shard
         boundaries and padded tail they will run with; small-integer values, so that the sums are exact in any order and the
-        comparison is bit for bit); returns None or the reason for falling back"""
+        comparison is bit for bit -- over the bf16 wire per-rank values in {0, 1, 2}, whose sums over up to 64 ranks are
+        integers <= 128: exact in bf16's 8 significant bits); returns None or the reason for falling back"""
         w = self.world
         sizes = [64 * w] + sorted(set(hi - lo for lo, hi, _ in self.buckets))
         try:
             for n in sizes:
-                t = (torch.arange(n, dtype=torch.int64, device=self.dev) % 7 + 1).to(self.g.dtype) * (self.rank + 1)
+                i = torch.arange(n, dtype=torch.int64, device=self.dev)
+                if self.wire_dtype == "bf16":
+                    t = ((i + self.rank) % 3).to(self.g.dtype)
+                else:
+                    t = (i % 7 + 1).to(self.g.dtype) * (self.rank + 1)
                 want = t.clone()
                 dist.all_reduce(want, op=dist.ReduceOp.SUM, group=self.group)
-                stage = torch.empty_like(t) if self.mode == "direct" else None
-                self._exchange(t, self.mode, stage)
+                if self.wire_dtype == "bf16":
+                    self._exchange_bf16(t)
+                else:
+                    stage = torch.empty_like(t) if self.mode == "direct" else None
+                    self._exchange(t, self.mode, stage)
                 ok = torch.tensor([1.0 if torch.equal(t, want) else 0.0], dtype=torch.float32, device=self.dev)
                 dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=self.group)
                 if ok.item() != 1.0:
@@ -286,9 +360,14 @@ class GradReducer:
             ev.record(torch.cuda.current_stream(self.dev))
             with torch.cuda.stream(self.comm_stream):
                 self.comm_stream.wait_event(ev)
-                self._exchange(view, self.mode, self._stage if self.mode == "direct" else None)
+                if self.wire_dtype == "bf16":
+                    self._exchange_bf16(view)
+                else:
+                    self._exchange(view, self.mode, self._stage if self.mode == "direct" else None)
         elif self.mode == "all_reduce":
             self._pending.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+        elif self.wire_dtype == "bf16":
+            self._exchange_bf16(view)
         else:
             self._exchange(view, self.mode, self._stage if self.mode == "direct" else None)
 

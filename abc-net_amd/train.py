@@ -23,7 +23,7 @@ class Trainer:
     def __init__(self, model, batch, height, width, lr=2.5e-4, weight_decay=1e-8, use_graph=True, bucket_mb=8.0,
                  process_group=None, device=None, metrics=False, broadcast_buffers="lazy", fused_heads=True, keep_logits=True,
                  batched_heads=True, exchange="all_reduce", force_exchange=False, guards=False, actbwd_epilogue=True, merge_reduce=True,
-                 reserve_cus=None, dual_wgrad=True, fused_convt=True):
+                 reserve_cus=None, dual_wgrad=True, fused_convt=True, exchange_dtype="f32"):
         """broadcast_buffers: how DDP's per-forward buffer broadcast (multi_gpu_train.py:52, broadcast_buffers=True) is
         mirrored when world > 1 -- "step": rank 0's BatchNorm buffers are broadcast at the start of every step, literally
         as DDP does; "lazy" (default): when sync_buffers() is called -- evaluate() calls it; before a checkpoint of a rank
@@ -48,7 +48,16 @@ class Trainer:
         dual_wgrad=False: the BatchNorm-backward apply as passes of their own (Engine(dual_wgrad=...): the A/B of that fusion).
         fused_convt=False: the ConvTranspose forward as four batched phase convolutions (Engine(fused_convt=...): the A/B of convt_fused.hip).
         force_exchange: segment the plan and run the bucket exchanges although the group has one rank (testing RCCL's launch
-        mechanics between graph segments on a one-GPU box)."""
+        mechanics between graph segments on a one-GPU box).
+        exchange_dtype: "f32" (default), or "bf16" with exchange="direct" (GradReducer(wire_dtype="bf16")): the gradients are
+        rounded to bf16 twice per step (before the all-to-all and after the rank-ordered f32 sum), so that
+        |result - sum_q g_q| <= 2^-9 (sum_q |g_q| + |sum_q g_q|) plus the f32 summation error; unmeasured at world > 1; not the
+        default."""
+        if exchange_dtype not in D.GradReducer.WIRE_DTYPES:
+            raise ValueError("Trainer: exchange_dtype must be one of %s, got %r" % (D.GradReducer.WIRE_DTYPES, exchange_dtype))
+        if exchange_dtype == "bf16" and exchange != "direct":
+            raise ValueError("Trainer: exchange_dtype='bf16' needs exchange='direct' (the local f32 sum between all-to-all and "
+                             "all-gather), got exchange=%r" % (exchange,))
         if tuple(model.heads) != HEADS:
             # (the fused loss, the meters and the fused heads pass read the maps of train.py:47; other lists train through the
             #  module's autograd, forward() + loss.backward())
@@ -101,9 +110,11 @@ class Trainer:
                 and store.data_ptr() == model._flat_grad.data_ptr():
             # bucket boundaries on multiples of 128 x world elements of the padded store: every bucket splits evenly
             self.buckets = D.align_buckets(self.buckets, sizes, rd, align, store.numel())
-            self.reducer = D.GradReducer(store, self.buckets, process_group, mode=exchange, force=force_exchange)
+            self.reducer = D.GradReducer(store, self.buckets, process_group, mode=exchange, force=force_exchange, wire_dtype=exchange_dtype)
         else:
             self.reducer = D.GradReducer(model._flat_grad, self.buckets, process_group, mode="all_reduce", force=force_exchange)
+            if self.exchange_on and exchange_dtype == "bf16":      # (asked for and not served: said, never silent)
+                self.reducer.fallback_reason = "the gradient store does not split into buckets of 128 x world elements: f32 all_reduce instead of the bf16 exchange"
         self.use_graph = use_graph
         self._graphs = None
         self._segments = self._plan_segments()

@@ -814,6 +814,19 @@ int abc_concat_f32(const float* const* srcs, const int32_t* counts, int32_t n, f
 /* *p += inc (one thread): the per-step dropout salt */
 int abc_counter_add_u32(uint32_t* p, uint32_t inc, abc_stream_t stream);
 
+/* The bf16 wire format of the data-parallel gradient exchange (multi_gpu_train.py:44-52,114-119).  bf16(x) is
+ * round-to-nearest-even on the f32 bit pattern u: (u + 0x7FFF + ((u >> 16) & 1)) >> 16; any NaN becomes a quiet NaN (never Inf),
+ * +-0 and +-Inf are kept, f32 subnormals are rounded (not flushed), finite values above the largest bf16 become Inf.
+ *   abc_grad_pack_bf16:   dst[i] = bf16(src[i]), i in [0, n)
+ *   abc_grad_reduce_bf16: recv is [W][n] bf16, 1 <= W <= 64; acc = f32(recv[0][i]), then acc = acc + f32(recv[q][i]) for
+ *                         q = 1 .. W-1 in that order (plain f32 adds), dst[i] = bf16(acc)
+ *   abc_grad_unpack_bf16: dst[i] = f32(src[i]) (exact)
+ * Any n >= 1 and any element-aligned pointers (f32: 4 bytes, bf16: 2); source and destination must not overlap.  One launch
+ * each, no allocation, no synchronisation. */
+int abc_grad_pack_bf16(const float* src, void* dst, int64_t n, abc_stream_t stream);
+int abc_grad_reduce_bf16(const void* recv, void* dst, int32_t W, int64_t n, abc_stream_t stream);
+int abc_grad_unpack_bf16(const void* src, float* dst, int64_t n, abc_stream_t stream);
+
 /* sizeof(descriptor #which) in declaration order (abc_act_src = 0 ... abc_nms_desc = 12, abc_cbam_channel_desc = 13, abc_cbam_pix_desc = 14, abc_cbam_conv7_desc = 15, abc_metrics_desc = 16, abc_extract_desc = 17, abc_raster_desc = 18, abc_heads_fused_desc = 19, abc_heads_epi = 20, abc_convt_desc = 21, abc_loss_scale_desc = 22, abc_adam_seg = 23, abc_adam_class = 24, abc_adam_multi_desc = 25, abc_image_desc = 26, abc_assemble_desc = 27):
  * lets a foreign-language binding check its mirror structs at load time */
 int abc_sizeof(int which);
