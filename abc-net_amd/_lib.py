@@ -206,10 +206,20 @@ class GraphScoreDesc(C.Structure):
                 ("radius", i32), ("rows", vp), ("totals", vp)]
 
 
+class GraphSimilarityDesc(C.Structure):
+    _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("rec_atoms", vp), ("rec_bonds", vp), ("rec_counts", vp),
+                ("n_valid", vp), ("B", i32), ("cap_atoms", i32), ("cap_mol_bonds", i32), ("max_atoms", i32), ("max_bonds", i32),
+                ("rows", vp), ("totals", vp), ("ids_out", vp)]
+
+
 EVAL_NCOUNT = 301   # ABC_EVAL_NCOUNT
 # the ABC_GS_* columns of abc_graph_score_desc.rows / .totals
 GRAPH_SCORE_COLUMNS = ("counted", "none", "truncated", "exact", "atoms_equal", "bonds_equal", "atoms_true", "atoms_pred",
                        "atoms_located", "atoms_matched", "bonds_true", "bonds_pred", "bonds_paired", "bonds_matched")
+# the ABC_SIM_* columns of abc_graph_similarity_desc.rows / .totals
+GRAPH_SIM_COLUMNS = ("counted", "none", "truncated", "size_equal", "refine_equal", "dice_one", "atoms_pred", "atoms_true",
+                     "envs_pred", "envs_true", "envs_common", "dice_q20")
+GRAPH_SIM_IDS = 2048    # ABC_SIM_IDS: ids_out is uint64 [B][2][GRAPH_SIM_IDS]
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
 MOL_EMPTY, MOL_TRUNCATED = 1, 2     # abc_mol_status
@@ -293,6 +303,8 @@ SYMBOLS = {
     "abc_eval_desc_size": (C.c_int, []),
     "abc_graph_score_update": (C.c_int, [P(GraphScoreDesc), vp]),
     "abc_graph_score_desc_size": (C.c_int, []),
+    "abc_graph_similarity_update": (C.c_int, [P(GraphSimilarityDesc), vp]),
+    "abc_graph_similarity_desc_size": (C.c_int, []),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "abc_plane_sum_work": (C.c_int, [i32]),
     "abc_cbam_channel_fwd": (C.c_int, [P(CbamChannelDesc), vp]),
@@ -364,11 +376,14 @@ def load():
         n = lib.abc_sizeof(i)
         if n != C.sizeof(st):
             raise AbcNetHipError("struct #%d (%s): binding has %d bytes, library %d" % (i, st.__name__, C.sizeof(st), n))
-    # (abc_eval_desc and abc_graph_score_desc are not in abc_sizeof's list: they report their own sizes)
+    # (abc_eval_desc, abc_graph_score_desc and abc_graph_similarity_desc are not in abc_sizeof's list: they report their own sizes)
     if lib.abc_eval_desc_size() != C.sizeof(EvalDesc):
         raise AbcNetHipError("struct EvalDesc: binding has %d bytes, library %d" % (C.sizeof(EvalDesc), lib.abc_eval_desc_size()))
     if lib.abc_graph_score_desc_size() != C.sizeof(GraphScoreDesc):
         raise AbcNetHipError("struct GraphScoreDesc: binding has %d bytes, library %d" % (C.sizeof(GraphScoreDesc), lib.abc_graph_score_desc_size()))
+    if lib.abc_graph_similarity_desc_size() != C.sizeof(GraphSimilarityDesc):
+        raise AbcNetHipError("struct GraphSimilarityDesc: binding has %d bytes, library %d"
+                             % (C.sizeof(GraphSimilarityDesc), lib.abc_graph_similarity_desc_size()))
     _lib = lib
     return lib
 

@@ -1,0 +1,268 @@
+// The graded score after assembly: how NEAR is the molecule abc_assemble_graphs built to the annotated molecule, without reading a
+// position?  (The reference's graded number is the Dice similarity of radius-3 Morgan fingerprints, cal_acc.py:38-43, through
+// RDKit; this is the same idea on environments this file defines itself, exactly, in integers -- the contract is in
+// include/abcnet_hip.h and DESIGN.md section 7.)
+//
+// One workgroup per image; integers only (uint64, wrapping), so every id is a pure function of the graph and the totals do not
+// depend on the order of the workgroups.  Side 0 is the molecule, side 1 the record.
+//
+//   (A) degrees: one thread per bond row, a 64-bit integer LDS add per valid end (acc); the record's atoms with a bond (the set T of
+//       graph_score.hip) are numbered in index order by a workgroup scan (remap); id_0 of every atom
+//   (B) rounds r = 1 .. 3: one thread per bond row, acc[a] += mix(mix(id[j]) + order) for both ends -- the sum is commutative, so no
+//       order of rows or atoms can change an id; then id_r[a] = mix(mix(id[a] + r) + acc[a]), kept as layer r of the fingerprint.
+//       Bond rows are never held in LDS, so no bond capacity bounds the launch: row `tid` of each side stays in registers, the rows
+//       past the workgroup's 256 threads are read from global memory again every round
+//   (C) the multiset intersection of the two fingerprints by counting: a molecule element is common when fewer equal elements stand
+//       before it in its own list than the record's list holds
+//   (D) only when the atom and valid-bond counts are equal: the same recurrence on to T = min(n, 64) rounds and the same counting on
+//       the two id_T lists (colour refinement)
+//   (E) lane 0 writes the row and adds it to the totals (64-bit atomicAdd, non-zero columns only)
+//
+// Every index read from a row is range-checked before it addresses anything: hand-made rows may hold any int32.
+#include "common.hpp"
+#include "../../include/abcnet_hip.h"
+#include "capi_util.hpp"
+#include "block_scan.hpp"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int GT = 256;              // threads per workgroup
+constexpr int MAX_ATOMS = 512;       // cap_atoms, max_atoms <= 512: ids, sums and four fingerprint layers of both sides in 48 KB of LDS
+constexpr int RADIUS = 3;            // fingerprint layers 0 .. 3
+constexpr int MAX_ROUNDS = 64;       // refinement rounds of refine_equal
+constexpr int FP = (RADIUS + 1) * MAX_ATOMS;
+constexpr int NCOL = ABC_SIM_NCOL;
+static_assert(FP == ABC_SIM_IDS, "ids_out holds one fingerprint per side");
+static_assert(MAX_ATOMS == 2 * GT, "the record scan numbers two atoms per thread");
+
+__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// the splitmix64 finaliser
+__device__ inline u64 mix(u64 x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+// the class of a vocabulary index: 0 (the reference's unknown) decodes to carbon, img2smiles2.py:24-25; anything outside the
+// vocabulary (a record's -1) is class 0, which equals only itself
+__device__ inline int atom_class(int t) { return t < 0 || t > 13 ? 0 : (t == 0 ? 1 : t); }
+// a wedge is a single bond (generate_smiles.py:58-68)
+__device__ inline int bond_class(int c) { return c == 5 || c == 6 ? 1 : (c >= 1 && c <= 4 ? c : 0); }
+__device__ inline u64 id0(int cls, int charge, u64 degree) { return mix(mix(mix((u64)(cls + 1)) + (u64)(long long)charge) + degree); }
+
+// the ends of molecule row q / record row k as atom indices of their side, false for a row that names no pair
+__device__ inline bool mol_ends(const int* pb, int q, int na, int& e1, int& e2) {
+    const int r1 = pb[q * 4], r2 = pb[q * 4 + 1];      // 1-based
+    if (r1 < 1 || r2 < 1 || r1 > na || r2 > na || r1 == r2) return false;
+    e1 = r1 - 1, e2 = r2 - 1;
+    return true;
+}
+__device__ inline bool rec_ends(const int* rb, int k, int nt, int& i, int& j) {
+    i = rb[k * 3], j = rb[k * 3 + 1];
+    return i >= 0 && j >= 0 && i < nt && j < nt && i != j;
+}
+
+// this thread's share of the size of the multiset intersection of A and B (LDS lists; every read of the inner loops is a broadcast)
+__device__ inline int common_share(const u64* A, int nA, const u64* Bv, int nB, int tid) {
+    int c = 0;
+    for (int k = tid; k < nA; k += GT) {
+        const u64 e = A[k];
+        int before = 0, there = 0;
+        for (int i = 0; i < nA; ++i) before += (i < k) & (A[i] == e);
+        for (int i = 0; i < nB; ++i) there += Bv[i] == e;
+        c += before < there;
+    }
+    return c;
+}
+
+__global__ __launch_bounds__(GT) void graph_sim_kernel(const abc_graph_similarity_desc d) {
+    __shared__ u64 cur[2][MAX_ATOMS];    // id_r of every atom
+    __shared__ u64 acc[2][MAX_ATOMS];    // degree, then the neighbour sum of the round
+    __shared__ u64 fp[2][FP];            // layer-major, atom-minor: id_r[a] at r * n + a
+    __shared__ int remap[MAX_ATOMS];     // record atom -> its number in T, -1 outside T
+    __shared__ unsigned wt[GT / 64 + 1];
+    __shared__ int cnt[4];               // valid molecule bonds, valid record bonds, envs_common, common id_T
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int* row = d.rows + (size_t)b * NCOL;
+    const int nv = d.n_valid != nullptr ? clampi(*d.n_valid, 0, d.B) : d.B;
+    if (b >= nv) {
+        if (tid < NCOL) row[tid] = 0;
+        return;
+    }
+    const int nt = clampi(d.rec_counts[b], 0, d.max_atoms), m = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
+    const int* mc = d.mol_counts + (size_t)b * 4;
+    const int status = mc[3];
+    const bool empty = (status & ABC_MOL_EMPTY) != 0;
+    const int na = empty ? 0 : clampi(mc[0], 0, d.cap_atoms), nb = empty ? 0 : clampi(mc[1], 0, d.cap_mol_bonds);
+    const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * 5;
+    const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * 4;
+    const int* ra = d.rec_atoms + (size_t)b * d.max_atoms * 4;
+    const int* rb = d.rec_bonds + (size_t)b * d.max_bonds * 3;
+
+    // row `tid` of each side, kept through every round (tens of bonds per drawing: most launches read no bond row twice)
+    int pi = 0, pj = 0, ti = 0, tj = 0;
+    const bool pv = tid < nb && mol_ends(pb, tid, na, pi, pj), tv = tid < m && rec_ends(rb, tid, nt, ti, tj);
+    const u64 po = pv ? (u64)bond_class(pb[tid * 4 + 2]) : 0, to = tv ? (u64)bond_class(rb[tid * 3 + 2]) : 0;
+
+    // ---- (A) degrees, T, id_0
+    if (tid < 4) cnt[tid] = 0;
+    for (int a = tid; a < MAX_ATOMS; a += GT) acc[0][a] = acc[1][a] = 0;
+    __syncthreads();
+    {
+        int valid_p = pv, valid_t = tv, i, j;
+        if (pv) {
+            atomicAdd(&acc[0][pi], 1ull);
+            atomicAdd(&acc[0][pj], 1ull);
+        }
+        if (tv) {
+            atomicAdd(&acc[1][ti], 1ull);
+            atomicAdd(&acc[1][tj], 1ull);
+        }
+        for (int q = tid + GT; q < nb; q += GT) {
+            if (!mol_ends(pb, q, na, i, j)) continue;
+            ++valid_p;
+            atomicAdd(&acc[0][i], 1ull);
+            atomicAdd(&acc[0][j], 1ull);
+        }
+        for (int k = tid + GT; k < m; k += GT) {
+            if (!rec_ends(rb, k, nt, i, j)) continue;
+            ++valid_t;
+            atomicAdd(&acc[1][i], 1ull);
+            atomicAdd(&acc[1][j], 1ull);
+        }
+        if (valid_p) atomicAdd(cnt + 0, valid_p);
+        if (valid_t) atomicAdd(cnt + 1, valid_t);
+    }
+    __syncthreads();
+    // (record atoms 2 tid and 2 tid + 1: their degrees stay in registers across the scan)
+    const int a0 = 2 * tid, a1 = 2 * tid + 1;
+    const u64 deg0 = a0 < nt ? acc[1][a0] : 0, deg1 = a1 < nt ? acc[1][a1] : 0;
+    const unsigned f0 = deg0 != 0, f1 = deg1 != 0;
+    unsigned total;
+    const unsigned r0 = block_excl_scan<GT>(f0 + f1, wt, &total), r1 = r0 + f0;
+    const int n_t = (int)total;          // |T|
+    for (int a = tid; a < na; a += GT) {
+        const u64 id = id0(atom_class(pa[a * 5 + 2]), pa[a * 5 + 3], acc[0][a]);
+        cur[0][a] = fp[0][a] = id;
+        acc[0][a] = 0;
+    }
+    remap[a0] = f0 ? (int)r0 : -1;
+    remap[a1] = f1 ? (int)r1 : -1;
+    if (f0) cur[1][r0] = fp[1][r0] = id0(atom_class(ra[a0 * 4 + 2]), ra[a0 * 4 + 3], deg0);
+    if (f1) cur[1][r1] = fp[1][r1] = id0(atom_class(ra[a1 * 4 + 2]), ra[a1 * 4 + 3], deg1);
+    acc[1][a0] = acc[1][a1] = 0;         // (every degree was read before the scan's barriers)
+    __syncthreads();
+    if (tv) ti = remap[ti], tj = remap[tj];      // (both in T: this row is one of those that put them there)
+    const int valid_p = cnt[0], valid_t = cnt[1];
+    const bool size_equal = !empty && na == n_t && valid_p == valid_t;
+    const int rounds_t = min(na, MAX_ROUNDS);
+    const int rounds = size_equal ? max(rounds_t, RADIUS) : RADIUS;
+
+    // ---- (B) and (D): the rounds; (C) after the third
+    for (int r = 1; r <= rounds; ++r) {
+        int i, j;
+        if (pv) {
+            atomicAdd(&acc[0][pi], mix(mix(cur[0][pj]) + po));
+            atomicAdd(&acc[0][pj], mix(mix(cur[0][pi]) + po));
+        }
+        if (tv) {
+            atomicAdd(&acc[1][ti], mix(mix(cur[1][tj]) + to));
+            atomicAdd(&acc[1][tj], mix(mix(cur[1][ti]) + to));
+        }
+        for (int q = tid + GT; q < nb; q += GT) {
+            if (!mol_ends(pb, q, na, i, j)) continue;
+            const u64 o = (u64)bond_class(pb[q * 4 + 2]);
+            atomicAdd(&acc[0][i], mix(mix(cur[0][j]) + o));
+            atomicAdd(&acc[0][j], mix(mix(cur[0][i]) + o));
+        }
+        for (int k = tid + GT; k < m; k += GT) {
+            if (!rec_ends(rb, k, nt, i, j)) continue;
+            const u64 o = (u64)bond_class(rb[k * 3 + 2]);
+            i = remap[i], j = remap[j];
+            atomicAdd(&acc[1][i], mix(mix(cur[1][j]) + o));
+            atomicAdd(&acc[1][j], mix(mix(cur[1][i]) + o));
+        }
+        __syncthreads();
+        for (int a = tid; a < na; a += GT) {
+            const u64 id = mix(mix(cur[0][a] + (u64)r) + acc[0][a]);
+            cur[0][a] = id;
+            acc[0][a] = 0;
+            if (r <= RADIUS) fp[0][r * na + a] = id;
+        }
+        for (int a = tid; a < n_t; a += GT) {
+            const u64 id = mix(mix(cur[1][a] + (u64)r) + acc[1][a]);
+            cur[1][a] = id;
+            acc[1][a] = 0;
+            if (r <= RADIUS) fp[1][r * n_t + a] = id;
+        }
+        __syncthreads();
+        if (r == RADIUS) {
+            const int c = common_share(fp[0], (RADIUS + 1) * na, fp[1], (RADIUS + 1) * n_t, tid);
+            if (c) atomicAdd(cnt + 2, c);
+        }
+    }
+    if (size_equal) {
+        // id_T: a fingerprint layer while T <= 3 (na == n_t here), the current ids after that
+        const u64* A = rounds_t <= RADIUS ? fp[0] + rounds_t * na : cur[0];
+        const u64* Bv = rounds_t <= RADIUS ? fp[1] + rounds_t * na : cur[1];
+        const int c = common_share(A, na, Bv, na, tid);
+        if (c) atomicAdd(cnt + 3, c);
+    }
+    if (d.ids_out != nullptr) {
+        u64* out = (u64*)d.ids_out + (size_t)b * 2 * FP;
+        for (int k = tid; k < FP; k += GT) {
+            out[k] = k < (RADIUS + 1) * na ? fp[0][k] : 0;
+            out[FP + k] = k < (RADIUS + 1) * n_t ? fp[1][k] : 0;
+        }
+    }
+    __syncthreads();
+
+    // ---- (E)
+    if (tid == 0) {
+        int r[NCOL];
+#pragma unroll
+        for (int i = 0; i < NCOL; ++i) r[i] = 0;
+        const int envs_p = (RADIUS + 1) * na, envs_t = (RADIUS + 1) * n_t, common = cnt[2];
+        r[ABC_SIM_COUNTED] = 1;
+        r[ABC_SIM_ENVS_TRUE] = envs_t;
+        if (empty) {
+            r[ABC_SIM_NONE] = 1;
+        } else {
+            r[ABC_SIM_TRUNCATED] = (status & ABC_MOL_TRUNCATED) ? 1 : 0;
+            r[ABC_SIM_SIZE_EQUAL] = size_equal;
+            r[ABC_SIM_REFINE_EQUAL] = size_equal && cnt[3] == na;
+            r[ABC_SIM_DICE_ONE] = common > 0 && common == envs_p && common == envs_t;
+            r[ABC_SIM_ATOMS_PRED] = na;
+            r[ABC_SIM_ATOMS_TRUE] = n_t;
+            r[ABC_SIM_ENVS_PRED] = envs_p;
+            r[ABC_SIM_ENVS_COMMON] = common;
+            r[ABC_SIM_DICE_Q20] = envs_p + envs_t ? (int)((((u64)common * 2) << 20) / (u64)(envs_p + envs_t)) : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < NCOL; ++i) {
+            row[i] = r[i];
+            if (r[i] != 0) atomicAdd((u64*)&d.totals[i], (u64)r[i]);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int abc_graph_similarity_desc_size(void) { return (int)sizeof(abc_graph_similarity_desc); }
+
+extern "C" int abc_graph_similarity_update(const abc_graph_similarity_desc* d, abc_stream_t stream) {
+    if (d->B < 1) return abc_fail(ABC_EINVAL, "graph_similarity: empty");
+    if (d->cap_atoms < 1 || d->cap_atoms > MAX_ATOMS) return abc_fail(ABC_EINVAL, "graph_similarity: cap_atoms must be 1..512");
+    if (d->cap_mol_bonds < 1) return abc_fail(ABC_EINVAL, "graph_similarity: cap_mol_bonds must be >= 1");
+    if (d->max_atoms < 1 || d->max_atoms > MAX_ATOMS) return abc_fail(ABC_EINVAL, "graph_similarity: max_atoms must be 1..512");
+    if (d->max_bonds < 1) return abc_fail(ABC_EINVAL, "graph_similarity: max_bonds must be >= 1");
+    if (!d->mol_counts || !d->mol_atoms || !d->mol_bonds) return abc_fail(ABC_EINVAL, "graph_similarity: null molecule buffer");
+    if (!d->rec_atoms || !d->rec_bonds || !d->rec_counts) return abc_fail(ABC_EINVAL, "graph_similarity: null record buffer");
+    if (!d->rows || !d->totals) return abc_fail(ABC_EINVAL, "graph_similarity: null output");
+    hipLaunchKernelGGL(graph_sim_kernel, dim3(d->B), dim3(GT), 0, (hipStream_t)stream, *d);
+    return abc_check_launch("graph_similarity_update");
+}

@@ -13,7 +13,8 @@ lists (extract=True, img2smiles2.py:113-191) and the assembled molecules (assemb
 evaluate=True makes the step the loop body of the reference's src/test_accuracy.py:94-269 as well: the targets of the batch sit in
 static device buffers and one more launch sequence after the NMS (ops.EvalTables) adds the batch to the per-class tables and the 17
 inference-flavour meters; evaluation() reads them.  score_graphs=True adds the score after assembly to that step: the assembled
-molecules against the annotated graphs (ops.GraphScore), accumulated like the tables.
+molecules against the annotated graphs (ops.GraphScore), accumulated like the tables; score_similarity=True the graded,
+position-free score of the same molecules (ops.GraphSimilarity).
 """
 from __future__ import annotations
 
@@ -28,7 +29,8 @@ from .contract import HEADS, alloc_targets, check_sparse_rasterizer, current_str
 class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
-                 assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw"):
+                 assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
+                 score_similarity=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -55,6 +57,10 @@ class InferenceRunner:
         after the assembler -- the molecules of the step against the graph records load_graphs(records) staged
         (raster.parse_graph; augment.SampleBuilder(self).load stages them itself), located within score_radius cells, on the
         first .n_valid images; evaluation()["molecules"] holds the running result
+        score_similarity (needs assemble=True and evaluate=True): the environment similarity of the assembled molecules to the same
+        graph records (ops.GraphSimilarity: the graded, position-free stand-in for cal_acc.py's fingerprint similarity), in the same
+        captured graph after the assembler; with score_graphs=True it reads the records the scorer staged, without it load_graphs
+        fills its own; evaluation()["similarity"] holds the running result
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
@@ -64,6 +70,9 @@ class InferenceRunner:
         self.omega_rule = omega_rule
         if score_graphs and not (assemble and evaluate):
             raise ValueError("InferenceRunner(score_graphs=True) scores the assembled molecules of an evaluating step: it needs "
+                             "assemble=True and evaluate=True")
+        if score_similarity and not (assemble and evaluate):
+            raise ValueError("InferenceRunner(score_similarity=True) scores the assembled molecules of an evaluating step: it needs "
                              "assemble=True and evaluate=True")
         extract = bool(extract) or bool(assemble)
         from .ops import check_nms_heads
@@ -131,6 +140,11 @@ class InferenceRunner:
             from .ops import GraphScore
             with torch.cuda.device(dev):
                 self.scorer = GraphScore.from_assembler(self.assembler, radius=score_radius, n_valid=self.n_valid)
+        self.similarity = None
+        if score_similarity:
+            from .ops import GraphSimilarity
+            with torch.cuda.device(dev):
+                self.similarity = GraphSimilarity.from_assembler(self.assembler, n_valid=self.n_valid, records=self.scorer)
         self.use_graph = use_graph
         self._graph = None
         self.steps = 0
@@ -223,6 +237,8 @@ class InferenceRunner:
             self.assembler.run(st)
         if self.scorer is not None:
             self.scorer.run(st)
+        if self.similarity is not None:
+            self.similarity.run(st)
         if self.evaluator is not None:
             self.evaluator.run(st)
 
@@ -233,6 +249,8 @@ class InferenceRunner:
         out = self.evaluator.result()
         if self.scorer is not None:
             out["molecules"] = self.scorer.result()
+        if self.similarity is not None:
+            out["similarity"] = self.similarity.result()
         return out
 
     def reset_evaluation(self):
@@ -241,14 +259,17 @@ class InferenceRunner:
         self.evaluator.reset()
         if self.scorer is not None:
             self.scorer.reset()
+        if self.similarity is not None:
+            self.similarity.reset()
 
     def load_graphs(self, records):
-        """score_graphs=True: the graph records (raster.parse_graph) of the batch, n <= batch of them (the rows past n get an empty
-        record; n_valid says how many images count)"""
-        if self.scorer is None:
+        """score_graphs=True or score_similarity=True: the graph records (raster.parse_graph) of the batch, n <= batch of them (the
+        rows past n get an empty record; n_valid says how many images count); staged once, whichever of the two read them"""
+        op = self.scorer if self.scorer is not None else self.similarity
+        if op is None:
             raise L.AbcNetHipError("InferenceRunner was built without score_graphs=True")
         with torch.cuda.device(self.dev):
-            self.scorer.load(records)
+            op.load(records)
 
     def candidates(self):
         """the per-image atom / bond candidate lists of the last step (host sync; needs extract=True)"""
@@ -265,8 +286,9 @@ class InferenceRunner:
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""
-        if self.scorer is not None and not self.scorer.loaded:
-            raise L.AbcNetHipError("InferenceRunner(score_graphs=True): no graph records were loaded (load_graphs, or SampleBuilder.load)")
+        for op in (self.scorer, self.similarity):
+            if op is not None and not op.loaded:
+                raise L.AbcNetHipError("InferenceRunner(score_graphs=True): no graph records were loaded (load_graphs, or SampleBuilder.load)")
         with torch.cuda.device(self.dev):
             self._step()
 

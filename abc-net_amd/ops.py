@@ -471,6 +471,33 @@ class GraphAssembler:
         return out
 
 
+def stage_graph_records(op, graphs):
+    """GraphScore.load / GraphSimilarity.load: the records into op's pinned staging (op.B, .max_atoms, .max_bonds, .staging, .h_*)"""
+    import numpy as np
+    if len(graphs) > op.B:
+        raise ValueError("expected at most %d graph records, got %d" % (op.B, len(graphs)))
+    recs = []
+    for b, (a, q) in enumerate(graphs):
+        a, q = np.asarray(a), np.asarray(q)
+        if a.ndim != 2 or a.shape[1] != 4 or q.ndim != 2 or q.shape[1] != 3:
+            raise ValueError("record %d: atoms must be [n, 4] and bonds [m, 3], got %s and %s" % (b, a.shape, q.shape))
+        if len(a) > op.max_atoms or len(q) > op.max_bonds:
+            raise ValueError("record %d has %d atoms / %d bonds (capacity %d / %d)" % (b, len(a), len(q), op.max_atoms, op.max_bonds))
+        if len(q) and not ((0 <= q[:, 0]) & (q[:, 0] < q[:, 1]) & (q[:, 1] < len(a))).all():
+            raise ValueError("record %d: every bond must name atoms 0 <= i < j < %d" % (b, len(a)))
+        recs.append((np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(q, dtype=np.int32)))
+    op.staging.wait()
+    op.h_cnt.zero_()
+    for b, (a, q) in enumerate(recs):
+        op.h_cnt[0, b], op.h_cnt[1, b] = len(a), len(q)
+        if len(a):
+            op.h_atoms[b, :len(a)] = torch.from_numpy(a)
+        if len(q):
+            op.h_bonds[b, :len(q)] = torch.from_numpy(q)
+    op.staging.commit()
+    op.loaded = True
+
+
 class GraphScore:
     """how many assembled molecules ARE the annotated molecule (csrc/graph_score.hip, abc_graph_score_update): the molecules of a
     GraphAssembler, read in place, against the graph records of raster.parse_graph -- bonded atoms located by mutual nearest cell
@@ -532,29 +559,7 @@ class GraphScore:
     def load(self, graphs):
         """graphs = list of n <= B (atoms [k, 4], bonds [m, 3]) pairs from raster.parse_graph; the rows past n get an empty record.
         Asynchronous H2D of a few KB through pinned staging."""
-        import numpy as np
-        if len(graphs) > self.B:
-            raise ValueError("expected at most %d graph records, got %d" % (self.B, len(graphs)))
-        recs = []
-        for b, (a, q) in enumerate(graphs):
-            a, q = np.asarray(a), np.asarray(q)
-            if a.ndim != 2 or a.shape[1] != 4 or q.ndim != 2 or q.shape[1] != 3:
-                raise ValueError("record %d: atoms must be [n, 4] and bonds [m, 3], got %s and %s" % (b, a.shape, q.shape))
-            if len(a) > self.max_atoms or len(q) > self.max_bonds:
-                raise ValueError("record %d has %d atoms / %d bonds (capacity %d / %d)" % (b, len(a), len(q), self.max_atoms, self.max_bonds))
-            if len(q) and not ((0 <= q[:, 0]) & (q[:, 0] < q[:, 1]) & (q[:, 1] < len(a))).all():
-                raise ValueError("record %d: every bond must name atoms 0 <= i < j < %d" % (b, len(a)))
-            recs.append((np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(q, dtype=np.int32)))
-        self.staging.wait()
-        self.h_cnt.zero_()
-        for b, (a, q) in enumerate(recs):
-            self.h_cnt[0, b], self.h_cnt[1, b] = len(a), len(q)
-            if len(a):
-                self.h_atoms[b, :len(a)] = torch.from_numpy(a)
-            if len(q):
-                self.h_bonds[b, :len(q)] = torch.from_numpy(q)
-        self.staging.commit()
-        self.loaded = True
+        stage_graph_records(self, graphs)
 
     def run(self, stream=None):
         L.check(self.lib.abc_graph_score_update(C.byref(self.d), stream_or_current(stream)), "graph_score_update")
@@ -571,6 +576,111 @@ class GraphScore:
         for share, num, den in (("share_exact", "exact", "counted"), ("share_atoms", "atoms_matched", "atoms_true"),
                                 ("share_bonds", "bonds_matched", "bonds_true")):
             out[share] = out[num] / out[den] if out[den] else float("nan")
+        out["rows"] = self.rows.cpu().numpy()
+        return out
+
+
+class GraphSimilarity:
+    """how NEAR the assembled molecules are to the annotated ones, free of positions (csrc/graph_sim.hip,
+    abc_graph_similarity_update): the multiset of the radius-0..3 atom environments of a GraphAssembler's molecule, read in place,
+    against that of the raster.parse_graph record -- the stand-in for the Dice similarity of Morgan fingerprints of cal_acc.py:38-43
+    (the exact definition: include/abcnet_hip.h; what of RDKit's it leaves out: DESIGN.md section 7).  One launch, static buffers,
+    graph-capture safe; the 12 columns (L.GRAPH_SIM_COLUMNS) of every image of the last call in .rows, their running sums in
+    .totals; `result()` is the only host sync.  `refine_equal` is an UPPER bound of "the same molecule" (colour refinement),
+    GraphScore's `exact` the positional lower one."""
+
+    MAX_ATOMS = 512        # abc_graph_similarity_desc: cap_atoms, max_atoms <= 512
+
+    def __init__(self, mol_counts, mol_atoms, mol_bonds, max_atoms=256, max_bonds=256, n_valid=None, records=None, debug_ids=False):
+        """mol_counts, mol_atoms, mol_bonds, n_valid: as GraphScore; max_atoms / max_bonds: the capacity of a record.
+        records: a GraphScore over the same batch -- its staged record buffers are read in place (no second staging: `load` is
+        refused here, `loaded` follows the scorer, max_atoms / max_bonds are the scorer's).  debug_ids: keep the fingerprint ids of
+        every image in .ids (int64 [B, 2, 2048] holding the uint64 bit patterns: molecule, then record; layer-major, atom-minor)"""
+        for name, t in (("mol_counts", mol_counts), ("mol_atoms", mol_atoms), ("mol_bonds", mol_bonds)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("GraphSimilarity: %s must be a tensor, got %s" % (name, type(t).__name__))
+        if mol_atoms.dim() != 3 or mol_atoms.shape[2] != 5 or mol_bonds.dim() != 3 or mol_bonds.shape[2] != 4:
+            raise ValueError("GraphSimilarity: mol_atoms must be [B, cap_atoms, 5] and mol_bonds [B, cap_mol_bonds, 4], got %s and %s"
+                             % (tuple(mol_atoms.shape), tuple(mol_bonds.shape)))
+        B, cap_atoms, cap_mol_bonds = mol_atoms.shape[0], mol_atoms.shape[1], mol_bonds.shape[1]
+        if tuple(mol_counts.shape) != (B, 4) or mol_bonds.shape[0] != B:
+            raise ValueError("GraphSimilarity: mol_counts must be [%d, 4] and mol_bonds [%d, cap_mol_bonds, 4], got %s and %s"
+                             % (B, B, tuple(mol_counts.shape), tuple(mol_bonds.shape)))
+        if B < 1 or not (1 <= cap_atoms <= self.MAX_ATOMS) or cap_mol_bonds < 1:
+            raise ValueError("GraphSimilarity: B >= 1, cap_atoms 1..%d (the limit of a molecule here: %d atoms) and cap_mol_bonds >= 1, "
+                             "got %d, %d, %d" % (self.MAX_ATOMS, self.MAX_ATOMS, B, cap_atoms, cap_mol_bonds))
+        if records is not None:
+            if not isinstance(records, GraphScore):
+                raise ValueError("GraphSimilarity: records must be a GraphScore, got %s" % type(records).__name__)
+            if records.B != B:
+                raise ValueError("GraphSimilarity: records stages %d images, the molecules are %d" % (records.B, B))
+            max_atoms, max_bonds = records.max_atoms, records.max_bonds
+        max_atoms, max_bonds = int(max_atoms), int(max_bonds)
+        if not (1 <= max_atoms <= self.MAX_ATOMS) or max_bonds < 1:
+            raise ValueError("GraphSimilarity: max_atoms must be 1..%d (the limit of a molecule here: %d atoms) and max_bonds >= 1, "
+                             "got %d and %d" % (self.MAX_ATOMS, self.MAX_ATOMS, max_atoms, max_bonds))
+        if n_valid is not None and not (isinstance(n_valid, torch.Tensor) and n_valid.numel() == 1):
+            raise ValueError("GraphSimilarity: n_valid must be a one-element int32 device tensor")
+        for t in (mol_counts, mol_atoms, mol_bonds) + (() if n_valid is None else (n_valid,)):
+            require_device_tensor(t, torch.int32, "GraphSimilarity: mol_counts, mol_atoms, mol_bonds (the assembler's layout) and n_valid")
+        self.lib = L.load()
+        dev = mol_atoms.device
+        self.B, self.cap_atoms, self.cap_mol_bonds = B, cap_atoms, cap_mol_bonds
+        self.max_atoms, self.max_bonds = max_atoms, max_bonds
+        self.records = records
+        if records is None:
+            self.staging = PinnedStaging(dev, {"atoms": ((B, max_atoms, 4), torch.int32), "bonds": ((B, max_bonds, 3), torch.int32),
+                                               "cnt": ((2, B), torch.int32)})
+            self.h_atoms, self.h_bonds, self.h_cnt = self.staging.host.values()
+            self.d_atoms, self.d_bonds, self.d_cnt = self.staging.dev.values()
+            self._loaded = False
+        else:
+            self.staging = None
+            self.d_atoms, self.d_bonds, self.d_cnt = records.d_atoms, records.d_bonds, records.d_cnt
+        self.rows = torch.zeros((B, len(L.GRAPH_SIM_COLUMNS)), dtype=torch.int32, device=dev)
+        # (uint64 on the device; int64 here: the sums stay far below 2^63)
+        self.totals = torch.zeros(len(L.GRAPH_SIM_COLUMNS), dtype=torch.int64, device=dev)
+        self.ids = torch.zeros((B, 2, L.GRAPH_SIM_IDS), dtype=torch.int64, device=dev) if debug_ids else None
+        d = L.GraphSimilarityDesc()
+        d.mol_counts, d.mol_atoms, d.mol_bonds = mol_counts.data_ptr(), mol_atoms.data_ptr(), mol_bonds.data_ptr()
+        d.rec_atoms, d.rec_bonds, d.rec_counts = self.d_atoms.data_ptr(), self.d_bonds.data_ptr(), self.d_cnt.data_ptr()
+        d.n_valid = None if n_valid is None else n_valid.data_ptr()
+        d.B, d.cap_atoms, d.cap_mol_bonds, d.max_atoms, d.max_bonds = B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds
+        d.rows, d.totals, d.ids_out = self.rows.data_ptr(), self.totals.data_ptr(), L.ptr(self.ids)
+        self.d, self.keep = d, (mol_counts, mol_atoms, mol_bonds, n_valid)
+
+    @classmethod
+    def from_assembler(cls, asm, max_atoms=256, max_bonds=256, n_valid=None, records=None, debug_ids=False):
+        return cls(asm.mol_counts, asm.mol_atoms, asm.mol_bonds, max_atoms=max_atoms, max_bonds=max_bonds, n_valid=n_valid, records=records,
+                   debug_ids=debug_ids)
+
+    @property
+    def loaded(self):
+        return self._loaded if self.records is None else self.records.loaded
+
+    @loaded.setter
+    def loaded(self, value):
+        self._loaded = bool(value)
+
+    def load(self, graphs):
+        """as GraphScore.load; refused when the records are a GraphScore's (load them there, once)"""
+        if self.records is not None:
+            raise ValueError("GraphSimilarity(records=scorer) reads the scorer's records: load them with scorer.load")
+        stage_graph_records(self, graphs)
+
+    def run(self, stream=None):
+        L.check(self.lib.abc_graph_similarity_update(C.byref(self.d), stream_or_current(stream)), "graph_similarity_update")
+
+    def reset(self):
+        self.totals.zero_()
+
+    def result(self):
+        """dict (device sync): the 12 running totals under their names (int), "similarity" = dice_q20 / 2^20 / counted, the mean
+        Dice similarity over every counted image, an image without a molecule counting 0 as a failed row does in cal_acc.py:45-47
+        (nan when nothing was counted), and "rows": the int32 [B, 12] table of the last call"""
+        tot = self.totals.cpu().tolist()
+        out = {k: int(v) for k, v in zip(L.GRAPH_SIM_COLUMNS, tot)}
+        out["similarity"] = out["dice_q20"] / float(1 << 20) / out["counted"] if out["counted"] else float("nan")
         out["rows"] = self.rows.cpu().numpy()
         return out
 

@@ -736,6 +736,49 @@ int abc_graph_score_update(const abc_graph_score_desc* d, abc_stream_t stream);
 /* sizeof(abc_graph_score_desc), for a binding's mirror struct (as abc_eval_desc_size: not part of abc_sizeof's list) */
 int abc_graph_score_desc_size(void);
 
+/* The GRADED score after assembly, free of positions: the similarity of the atom environments of the assembled molecule and of
+ * the annotated one (the stand-in for the Dice similarity of radius-3 Morgan fingerprints of cal_acc.py:38-43; DESIGN.md section 7
+ * lists what of RDKit's fingerprint it leaves out).  One workgroup per image, uint64 wrapping arithmetic only, no allocation, no
+ * sync (csrc/graph_sim.hip).  The molecule rows and the records are abc_graph_score_desc's, read the same way.
+ *   atoms    molecule: all mol_counts[b][0] rows; record: the set T of abc_graph_score_update (atoms some valid bond row names);
+ *   class    of a vocabulary index t: 1 for t = 0 (carbon), t for 1..13, 0 ("unknown", equal only to itself) for anything else
+ *            (a record's -1); the charge value counts as stored, hs does not (a record has none);
+ *   bonds    a row is valid when both ends are in range and differ; order class: codes 5 and 6 are 1 (a wedge is a single bond),
+ *            1..4 stay, anything else is 0; a pair listed twice counts twice (a multigraph); no degree cap;
+ *   mix(x)   the splitmix64 finaliser: x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31;
+ *   id_0[a]  mix(mix(mix(class + 1) + (uint64)(int64)charge) + degree), degree = the valid rows naming a;
+ *   id_r[a]  mix(mix(id_{r-1}[a] + r) + acc), acc = the sum over the valid rows (a, j, order class o) of mix(mix(id_{r-1}[j]) + o)
+ *            (the neighbour term is mixed twice: with one mix it is the self term's function at r = o = 1).
+ * The fingerprint of a side is the multiset {id_r[a] : r = 0..3}, 4 n elements.  envs_common is the size of the multiset
+ * intersection, dice_q20 = floor(2 envs_common 2^20 / (envs_pred + envs_true)) (0 for an empty denominator), dice_one: common ==
+ * pred == true > 0.  size_equal: the atom counts and the valid bond counts are equal; refine_equal: size_equal, and the multisets
+ * of id_T are equal after T = min(n, 64) rounds of the same recurrence -- colour refinement, necessary for isomorphism and not
+ * sufficient (decalin and bicyclopentyl pass): an UPPER bound of "the same molecule", as ABC_GS_EXACT is the positional lower one.
+ * rows[b] (overwritten by every call; all zero for b >= *n_valid) and totals (+= the column sums, 64-bit integer atomics) have
+ * the ABC_SIM_* columns.  An ABC_MOL_EMPTY image adds counted, none and envs_true, and nothing else.  The mean similarity is
+ * totals[dice_q20] / 2^20 / totals[counted]. */
+enum { ABC_SIM_COUNTED = 0, ABC_SIM_NONE, ABC_SIM_TRUNCATED, ABC_SIM_SIZE_EQUAL, ABC_SIM_REFINE_EQUAL, ABC_SIM_DICE_ONE,
+       ABC_SIM_ATOMS_PRED, ABC_SIM_ATOMS_TRUE, ABC_SIM_ENVS_PRED, ABC_SIM_ENVS_TRUE, ABC_SIM_ENVS_COMMON, ABC_SIM_DICE_Q20,
+       ABC_SIM_NCOL = 12, ABC_SIM_IDS = 2048 };
+typedef struct abc_graph_similarity_desc {
+    const int32_t* mol_counts;   /* [B][4]                 as abc_graph_score_desc */
+    const int32_t* mol_atoms;    /* [B][cap_atoms][5] */
+    const int32_t* mol_bonds;    /* [B][cap_mol_bonds][4] */
+    const int32_t* rec_atoms;    /* [B][max_atoms][4] */
+    const int32_t* rec_bonds;    /* [B][max_bonds][3] */
+    const int32_t* rec_counts;   /* [2][B] */
+    const int32_t* n_valid;      /* optional DEVICE int32, as abc_graph_score_desc */
+    int32_t B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds;   /* cap_atoms 1..512, max_atoms 1..512; the bond capacities >= 1 */
+    int32_t* rows;               /* [B][ABC_SIM_NCOL] */
+    uint64_t* totals;            /* [ABC_SIM_NCOL] */
+    /* optional (debug): [B][2][ABC_SIM_IDS], the fingerprint ids of the molecule, then of the record, of every image below
+     * *n_valid: id_r of the side's a-th atom (the record's: the a-th of T in index order) at r * n + a, zero past 4 n */
+    uint64_t* ids_out;
+} abc_graph_similarity_desc;
+int abc_graph_similarity_update(const abc_graph_similarity_desc* d, abc_stream_t stream);
+/* sizeof(abc_graph_similarity_desc), for a binding's mirror struct (as abc_graph_score_desc_size) */
+int abc_graph_similarity_desc_size(void);
+
 /* ---- unet2: CBAM attention + residual (unet2.py:6-74).  See csrc/cbam.hip for the pass structure. ---- */
 typedef struct abc_cbam_channel_desc { /* ChannelAttentionModule (unet2.py:6-22), one MLP evaluation per image */
     const float* partial;  /* fwd: conv stats [B*tiles_per_img][4][C] (sum,sumsq,max,min of y2); bwd: [B*tiles_per_img][C] */

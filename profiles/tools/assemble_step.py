@@ -10,6 +10,9 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            Beside it the device's own count: InferenceRunner(score_graphs=True) at radius 0 (csrc/graph_score.hip), one sync.
   score    abc_graph_score_update alone (as `launch`), and InferenceRunner.step() with assemble=True, evaluate=True against the
            same with score_graphs=True (as `step`); the targets of both come from the annotation records (sparse rasteriser)
+  similarity  abc_graph_similarity_update alone beside abc_graph_score_update (as `launch`), the fixture's mean environment similarity,
+           refine_equal and exact (InferenceRunner(score_graphs=True, score_similarity=True), one step, csrc/graph_sim.hip), and
+           step() with score_graphs=True against the same with score_similarity=True as well (as `step`)
 
   --omega-rule {raw,peaks}: the extractor's candidate rule of every runner built here (InferenceRunner(omega_rule=...): "raw" is
            img2smiles2.py:139, "peaks" img2smiles.py:139 / img2smiles3.py:140); `graphs` and `score` then also report the candidates
@@ -17,7 +20,7 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score] [--omega-rule raw]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity] [--omega-rule raw]
 """
 import argparse
 import json
@@ -62,20 +65,24 @@ def runners(m, x):
     return out
 
 
-def scoring_runners(m, x, notes):
-    """the evaluating step without and with the score after assembly; targets drawn once from the annotation records"""
+def scoring_runners(m, x, notes, similarity=False):
+    """the evaluating step without and with the score after assembly (similarity: and with the environment similarity on top);
+    targets drawn once from the annotation records"""
     from abcnet_amd.raster import TargetRasterizer, parse_graph, parse_record
     recs = [parse_record(a, b, h=S // 4) for a, b in notes]
     graphs = [parse_graph(a, b, h=S // 4) for a, b in notes]
     out = {}
-    for name, kw in (("assemble+evaluate", {}), ("assemble+evaluate+score", dict(score_graphs=True, score_radius=0))):
+    forms = [("assemble+evaluate", {}), ("assemble+evaluate+score", dict(score_graphs=True, score_radius=0))]
+    if similarity:
+        forms.append(("assemble+evaluate+score+similarity", dict(score_graphs=True, score_radius=0, score_similarity=True)))
+    for name, kw in forms:
         r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, evaluate=True, omega_rule=RULE, **kw)
         rz = TargetRasterizer(B, S // 4, targets=r.targets, sparse=True)
         r.use_sparse_targets(rz)
         rz.load(recs)
         rz.run()
         r.load_batch(x.to("cuda"))
-        if r.scorer is not None:
+        if r.scorer is not None or r.similarity is not None:
             r.load_graphs(graphs)
         out[name] = r
     return out
@@ -188,6 +195,34 @@ def part_score(rs, steps, warmup, iters=200):
     part_step(rs, steps, warmup, part="score", diff=("assemble+evaluate+score", "assemble+evaluate"), diff_name="score_minus_plain_ms")
 
 
+def part_similarity(rs, steps, warmup, iters=200):
+    from abcnet_amd._lib import GRAPH_SIM_COLUMNS
+    r = rs["assemble+evaluate+score+similarity"]
+    sim, sc = r.similarity, r.scorer
+    keep = sim.totals.clone(), sc.totals.clone()
+    us = [(launch_us(sim.run, iters), launch_us(sc.run, iters)) for _ in range(3)]      # the two launches alternated, three figures each
+    sim.totals.copy_(keep[0])
+    sc.totals.copy_(keep[1])
+    emit({"part": "similarity", "what": "launch", "batch": B, "us_per_launch": [round(a, 2) for a, _ in us],
+          "graph_score_us_per_launch": [round(b, 2) for _, b in us],
+          "method": "device events around %d back-to-back launches (launch gaps included)" % iters})
+    r.reset_evaluation()
+    r.step()
+    ev = r.evaluation()
+    res = ev["similarity"]
+    out = {"part": "similarity", "what": "fixture", "images": res["counted"], "similarity": round(res["similarity"], 4),
+           "exact": ev["molecules"]["exact"]}
+    out.update({k: res[k] for k in GRAPH_SIM_COLUMNS[1:]})
+    rows = res["rows"]
+    q = sorted(rows[:, GRAPH_SIM_COLUMNS.index("dice_q20")].tolist())
+    out["dice_min_median_max"] = [round(v / float(1 << 20), 4) for v in (q[0], q[len(q) // 2], q[-1])]
+    emit(out)
+    r.reset_evaluation()
+    pair = {k: rs[k] for k in ("assemble+evaluate+score", "assemble+evaluate+score+similarity")}
+    part_step(pair, steps, warmup, part="similarity", diff=("assemble+evaluate+score+similarity", "assemble+evaluate+score"),
+              diff_name="similarity_minus_score_ms")
+
+
 def part_graphs_device(r):
     """the device's count of the same thing: the scorer's rows of the last step (radius 0)"""
     from abcnet_amd._lib import GRAPH_SCORE_COLUMNS
@@ -232,7 +267,7 @@ def main():
     m = model()
     x, notes = drawn_molecules(B, S, seed=777)
     rs = runners(m, x) if set(parts) & {"step", "launch", "host"} else {}
-    ss = scoring_runners(m, x, notes) if set(parts) & {"graphs", "score"} else {}
+    ss = scoring_runners(m, x, notes, similarity="similarity" in parts) if set(parts) & {"graphs", "score", "similarity"} else {}
     for r in list(rs.values()) + list(ss.values()):
         for _ in range(2):
             r.step()
@@ -247,7 +282,9 @@ def main():
         part_graphs(ss["assemble+evaluate+score"], notes)
         part_graphs_device(ss["assemble+evaluate+score"])
     if "score" in parts:
-        part_score(ss, a.steps, a.warmup)
+        part_score({k: ss[k] for k in ("assemble+evaluate", "assemble+evaluate+score")}, a.steps, a.warmup)
+    if "similarity" in parts:
+        part_similarity(ss, a.steps, a.warmup)
 
 
 if __name__ == "__main__":
