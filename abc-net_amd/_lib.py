@@ -212,6 +212,11 @@ class GraphSimilarityDesc(C.Structure):
                 ("rows", vp), ("totals", vp), ("ids_out", vp)]
 
 
+class MolBlockDesc(C.Structure):
+    _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp), ("B", i32), ("cap_atoms", i32),
+                ("cap_mol_bonds", i32), ("text", vp), ("index", vp), ("work", vp), ("cap_text", i64)]
+
+
 EVAL_NCOUNT = 301   # ABC_EVAL_NCOUNT
 # the ABC_GS_* columns of abc_graph_score_desc.rows / .totals
 GRAPH_SCORE_COLUMNS = ("counted", "none", "truncated", "exact", "atoms_equal", "bonds_equal", "atoms_true", "atoms_pred",
@@ -223,6 +228,7 @@ GRAPH_SIM_IDS = 2048    # ABC_SIM_IDS: ids_out is uint64 [B][2][GRAPH_SIM_IDS]
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
 MOL_EMPTY, MOL_TRUNCATED = 1, 2     # abc_mol_status
+TEXT_BAD_ROW, TEXT_OVERFLOW = 4, 8  # abc_text_status (the status words of abc_write_molblocks)
 
 
 _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnApplyDesc, WgradDesc, WgradReduceDesc,
@@ -305,6 +311,9 @@ SYMBOLS = {
     "abc_graph_score_desc_size": (C.c_int, []),
     "abc_graph_similarity_update": (C.c_int, [P(GraphSimilarityDesc), vp]),
     "abc_graph_similarity_desc_size": (C.c_int, []),
+    "abc_molblock_text_bytes": (i64, [P(MolBlockDesc)]),
+    "abc_write_molblocks": (C.c_int, [P(MolBlockDesc), vp]),
+    "abc_molblock_desc_size": (C.c_int, []),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "abc_plane_sum_work": (C.c_int, [i32]),
     "abc_cbam_channel_fwd": (C.c_int, [P(CbamChannelDesc), vp]),
@@ -376,7 +385,7 @@ def load():
         n = lib.abc_sizeof(i)
         if n != C.sizeof(st):
             raise AbcNetHipError("struct #%d (%s): binding has %d bytes, library %d" % (i, st.__name__, C.sizeof(st), n))
-    # (abc_eval_desc, abc_graph_score_desc and abc_graph_similarity_desc are not in abc_sizeof's list: they report their own sizes)
+    # (abc_eval_desc, abc_graph_score_desc, abc_graph_similarity_desc and abc_molblock_desc are not in abc_sizeof's list: they report their own sizes)
     if lib.abc_eval_desc_size() != C.sizeof(EvalDesc):
         raise AbcNetHipError("struct EvalDesc: binding has %d bytes, library %d" % (C.sizeof(EvalDesc), lib.abc_eval_desc_size()))
     if lib.abc_graph_score_desc_size() != C.sizeof(GraphScoreDesc):
@@ -384,6 +393,8 @@ def load():
     if lib.abc_graph_similarity_desc_size() != C.sizeof(GraphSimilarityDesc):
         raise AbcNetHipError("struct GraphSimilarityDesc: binding has %d bytes, library %d"
                              % (C.sizeof(GraphSimilarityDesc), lib.abc_graph_similarity_desc_size()))
+    if lib.abc_molblock_desc_size() != C.sizeof(MolBlockDesc):
+        raise AbcNetHipError("struct MolBlockDesc: binding has %d bytes, library %d" % (C.sizeof(MolBlockDesc), lib.abc_molblock_desc_size()))
     _lib = lib
     return lib
 

@@ -7,7 +7,8 @@ One step = eval-mode forward (running-statistics BatchNorm folded into the convo
 time, activations in the convolutions' epilogues, no dropout) + the peak-NMS kernel, on a batch already resident in HBM, replayed from one hipGraph.  The weights do not change between
 steps, so re-packing them and deriving the eval-mode BatchNorm coefficients happens in `refresh()`, not in the step;
 call it again after `load_state_dict`.  The step ends with the four mask / |rho| maps the decoder reads; opt-in, the candidate
-lists (extract=True, img2smiles2.py:113-191) and the assembled molecules (assemble=True, :193-311) in the same graph.  RDKit
+lists (extract=True, img2smiles2.py:113-191), the assembled molecules (assemble=True, :193-311) and their mol block text
+(molblocks=True, generate_smiles.py:18-105) in the same graph.  RDKit
 (generate_smiles.py:115-119) is out of scope.
 
 evaluate=True makes the step the loop body of the reference's src/test_accuracy.py:94-269 as well: the targets of the batch sit in
@@ -30,7 +31,7 @@ class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
                  assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
-                 score_similarity=False):
+                 score_similarity=False, molblocks=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -61,6 +62,9 @@ class InferenceRunner:
         graph records (ops.GraphSimilarity: the graded, position-free stand-in for cal_acc.py's fingerprint similarity), in the same
         captured graph after the assembler; with score_graphs=True it reads the records the scorer staged, without it load_graphs
         fills its own; evaluation()["similarity"] holds the running result
+        molblocks (needs assemble=True): the mol block text of the assembled molecules (ops.MolBlockWriter), written in the same
+        captured graph right after the assembler; molblocks() returns the strings that go into Chem.MolFromMolBlock -- two small
+        copies per batch instead of molecules() and Molecule.molblock() per image on the host
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
@@ -74,6 +78,9 @@ class InferenceRunner:
         if score_similarity and not (assemble and evaluate):
             raise ValueError("InferenceRunner(score_similarity=True) scores the assembled molecules of an evaluating step: it needs "
                              "assemble=True and evaluate=True")
+        if molblocks and not assemble:
+            raise ValueError("InferenceRunner(molblocks=True) writes the text of the assembled molecules of the step: it needs "
+                             "assemble=True")
         extract = bool(extract) or bool(assemble)
         from .ops import check_nms_heads
         check_nms_heads(model.heads, "InferenceRunner")
@@ -126,6 +133,11 @@ class InferenceRunner:
             from .ops import GraphAssembler
             with torch.cuda.device(dev):
                 self.assembler = GraphAssembler.from_extractor(self.extractor, cap_mol_bonds=cap_mol_bonds)
+        self.texter = None
+        if molblocks:
+            from .ops import MolBlockWriter
+            with torch.cuda.device(dev):
+                self.texter = MolBlockWriter.from_assembler(self.assembler)
         self.evaluator = None
         self._rasterizer = None
         if evaluate:
@@ -235,6 +247,8 @@ class InferenceRunner:
             self.extractor.run(st)
         if self.assembler is not None:
             self.assembler.run(st)
+        if self.texter is not None:
+            self.texter.run(st)
         if self.scorer is not None:
             self.scorer.run(st)
         if self.similarity is not None:
@@ -283,6 +297,14 @@ class InferenceRunner:
         if self.assembler is None:
             raise L.AbcNetHipError("InferenceRunner was built without assemble=True")
         return self.assembler.molecules()
+
+    def molblocks(self):
+        """the mol block (str) of every image of the last step, written on the device: what `m.molblock()` gives for the m of
+        molecules(), None where that is None (host sync; needs molblocks=True)"""
+        if self.texter is None:
+            raise L.AbcNetHipError("InferenceRunner was built without molblocks=True")
+        with torch.cuda.device(self.dev):
+            return self.texter.molblocks()
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""

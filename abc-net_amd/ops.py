@@ -1,6 +1,7 @@
 """Thin host wrappers over single C-ABI kernels used outside the engine's static plan:
 fused loss (train.py:95-137), inference NMS (img2smiles2.py:61-79), candidate extraction and graph assembly
-(img2smiles2.py:113-311), the score of the assembled molecules against their annotations, fused Adam (train.py:55,141)."""
+(img2smiles2.py:113-311), the mol block text of the assembled molecules (generate_smiles.py:18-105), their score against their
+annotations, fused Adam (train.py:55,141)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -469,6 +470,83 @@ class GraphAssembler:
                 continue
             out.append(Molecule.from_device_rows(atoms[b, :a], bonds[b, :m], implh[b, :k], truncated=bool(status & L.MOL_TRUNCATED)))
         return out
+
+
+class MolBlockWriter:
+    """the mol block text of the assembled molecules, written on the device (csrc/molblock.hip, abc_write_molblocks): the bytes of
+    `Molecule.from_device_rows(...).molblock()` for every image of a GraphAssembler's rows, read in place, packed back to back
+    into one static buffer.  Two launches, static buffers, graph-capture safe; `molblocks()` is the only host sync (two small D2H
+    copies per batch, no per-atom host work).  `Molecule.molblock()` stays the host form and the oracle."""
+
+    STATUS_NAMES = ((L.TEXT_BAD_ROW, "ABC_TEXT_BAD_ROW (a vocabulary index outside 0..13 or a position outside 0..199999)"),
+                    (L.TEXT_OVERFLOW, "ABC_TEXT_OVERFLOW (the batch's text does not fit cap_text)"))
+
+    def __init__(self, mol_counts, mol_atoms, mol_bonds, mol_implh, cap_text=None):
+        """mol_counts int32 [B, 4], mol_atoms int32 [B, cap_atoms, 5], mol_bonds int32 [B, cap_mol_bonds, 4], mol_implh int32
+        [B, cap_atoms]: device tensors of GraphAssembler's layout (its own buffers, or hand-made rows).  cap_text: bytes of the
+        text buffer; default B * abc_molblock_text_bytes, the bound of one image with every number at its widest -- 224 867 bytes
+        per image at the runner's default capacities (512 atoms, 2048 bonds), 14.4 MB for a batch of 64; at most 2^31 - 1"""
+        for name, t in (("mol_counts", mol_counts), ("mol_atoms", mol_atoms), ("mol_bonds", mol_bonds), ("mol_implh", mol_implh)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("MolBlockWriter: %s must be a tensor, got %s" % (name, type(t).__name__))
+        if mol_atoms.dim() != 3 or mol_atoms.shape[2] != 5 or mol_bonds.dim() != 3 or mol_bonds.shape[2] != 4:
+            raise ValueError("MolBlockWriter: mol_atoms must be [B, cap_atoms, 5] and mol_bonds [B, cap_mol_bonds, 4], got %s and %s"
+                             % (tuple(mol_atoms.shape), tuple(mol_bonds.shape)))
+        B, cap_atoms, cap_mol_bonds = mol_atoms.shape[0], mol_atoms.shape[1], mol_bonds.shape[1]
+        if tuple(mol_counts.shape) != (B, 4) or mol_bonds.shape[0] != B or tuple(mol_implh.shape) != (B, cap_atoms):
+            raise ValueError("MolBlockWriter: mol_counts must be [%d, 4], mol_bonds [%d, cap_mol_bonds, 4] and mol_implh [%d, %d], got %s, %s "
+                             "and %s" % (B, B, B, cap_atoms, tuple(mol_counts.shape), tuple(mol_bonds.shape), tuple(mol_implh.shape)))
+        if B < 1 or cap_atoms < 1 or cap_mol_bonds < 1:
+            raise ValueError("MolBlockWriter: B, cap_atoms and cap_mol_bonds must be >= 1, got %d, %d, %d" % (B, cap_atoms, cap_mol_bonds))
+        for t in (mol_counts, mol_atoms, mol_bonds, mol_implh):
+            require_device_tensor(t, torch.int32, "MolBlockWriter: mol_counts, mol_atoms, mol_bonds and mol_implh (the assembler's layout)")
+        self.lib = L.load()
+        dev = mol_atoms.device
+        d = L.MolBlockDesc()
+        d.mol_counts, d.mol_atoms, d.mol_bonds, d.mol_implh = mol_counts.data_ptr(), mol_atoms.data_ptr(), mol_bonds.data_ptr(), mol_implh.data_ptr()
+        d.B, d.cap_atoms, d.cap_mol_bonds = B, cap_atoms, cap_mol_bonds
+        self.image_bytes = int(self.lib.abc_molblock_text_bytes(C.byref(d)))
+        cap_text = B * self.image_bytes if cap_text is None else int(cap_text)
+        if not (1 <= cap_text <= 2 ** 31 - 1):
+            raise ValueError("MolBlockWriter: cap_text must be 1..2^31-1 bytes, got %d (B = %d images of at most %d bytes)"
+                             % (cap_text, B, self.image_bytes))
+        self.B, self.cap_atoms, self.cap_mol_bonds, self.cap_text = B, cap_atoms, cap_mol_bonds, cap_text
+        self.text = torch.zeros(cap_text, dtype=torch.uint8, device=dev)
+        self.index = torch.zeros(2 * B + 1, dtype=torch.int32, device=dev)
+        self.work = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.h_index = torch.zeros(2 * B + 1, dtype=torch.int32, pin_memory=True)
+        d.text, d.index, d.work, d.cap_text = self.text.data_ptr(), self.index.data_ptr(), self.work.data_ptr(), cap_text
+        self.d, self.keep = d, (mol_counts, mol_atoms, mol_bonds, mol_implh)
+
+    @classmethod
+    def from_assembler(cls, asm, cap_text=None):
+        return cls(asm.mol_counts, asm.mol_atoms, asm.mol_bonds, asm.mol_implh, cap_text=cap_text)
+
+    def run(self, stream=None):
+        L.check(self.lib.abc_write_molblocks(C.byref(self.d), stream_or_current(stream)), "write_molblocks")
+
+    def _index(self):
+        """(offsets [B + 1], status [B]) of the last run as host lists: one D2H into the pinned buffer (host sync)"""
+        self.h_index.copy_(self.index, non_blocking=True)
+        torch.cuda.current_stream(self.index.device).synchronize()
+        v = self.h_index.tolist()
+        return v[:self.B + 1], v[self.B + 1:]
+
+    def status(self):
+        """the B status words of the last run: abc_mol_status | abc_text_status bits (host sync)"""
+        return self._index()[1]
+
+    def molblocks(self):
+        """per image: the mol block as a str (the argument of Chem.MolFromMolBlock), or None for an image without an atom peak
+        or without a bond peak.  Raises AbcNetHipError when an image was refused (BAD_ROW) or did not fit (OVERFLOW).  Host sync:
+        the index, then the text that was written."""
+        off, status = self._index()
+        for b, s in enumerate(status):
+            for bit, name in self.STATUS_NAMES:
+                if s & bit:
+                    raise L.AbcNetHipError("MolBlockWriter: image %d has status %s" % (b, name))
+        raw = self.text[:off[self.B]].cpu().numpy().tobytes()
+        return [None if s & L.MOL_EMPTY else raw[off[b]:off[b + 1]].decode("ascii") for b, s in enumerate(status)]
 
 
 def stage_graph_records(op, graphs):

@@ -625,6 +625,8 @@ int abc_extract_peaks(const abc_extract_desc* d, abc_stream_t stream);
  * reference's results.append(None)); ABC_MOL_TRUNCATED: the extractor truncated a list or cap_mol_bonds was hit (the stored
  * molecule is then built from the truncated lists).  Bond peaks without a surviving candidate give zero atoms and zero bonds. */
 enum abc_mol_status { ABC_MOL_EMPTY = 1, ABC_MOL_TRUNCATED = 2 };
+/* the bits abc_write_molblocks adds to the two above in its own status words (never in mol_counts) */
+enum abc_text_status { ABC_TEXT_BAD_ROW = 4, ABC_TEXT_OVERFLOW = 8 };
 typedef struct abc_assemble_desc {
     const int32_t* counts;    /* [B][4]            as abc_extract_desc.counts */
     const int32_t* atoms;     /* [B][cap_atoms][5] */
@@ -778,6 +780,48 @@ typedef struct abc_graph_similarity_desc {
 int abc_graph_similarity_update(const abc_graph_similarity_desc* d, abc_stream_t stream);
 /* sizeof(abc_graph_similarity_desc), for a binding's mirror struct (as abc_graph_score_desc_size) */
 int abc_graph_similarity_desc_size(void);
+
+/* The mol block text of the assembled molecules (generate_smiles.py:18-105), written on the device from the rows of
+ * abc_assemble_graphs, read in place: the bytes that go into Chem.MolFromMolBlock, one copy per batch (csrc/molblock.hip; the
+ * contract in full: DESIGN.md section 7).  Two launches on the stream, integers only, no atomics on global memory, no allocation,
+ * no sync; deterministic in any launch order.
+ *   text     the blocks of the batch back to back in image order, no terminator between them; image b is
+ *            text[offsets[b] .. offsets[b+1]), byte for byte what decode.Molecule.from_device_rows(rows of b).molblock() gives
+ *            (ASCII): every %3d / %4d is a MINIMUM width, a coordinate is px / 60 - 1 to four decimals computed as
+ *            q = (2 |px - 60| 500 + 3) / 6 in integer division and printed q / 10000 "." (q % 10000, four digits), negative exactly
+ *            when px < 60 (then after three blanks, else after four); bond ends, orders, charges and implicit-H entries are printed
+ *            as stored (any int32); every count is clamped to its capacity first;
+ *   index    offsets[0 .. B], then status[0 .. B-1];
+ *   status   ABC_MOL_EMPTY / ABC_MOL_TRUNCATED copied from mol_counts (EMPTY: length 0; TRUNCATED: the text of the stored rows);
+ *            ABC_TEXT_BAD_ROW: an atom row with a vocabulary index outside 0..13 or a position outside 0..199999, length 0;
+ *            ABC_TEXT_OVERFLOW: an image is written only if the UNCLIPPED running total of the lengths through it is <= cap_text --
+ *            the first image that does not fit and every image after it have length 0 and this bit, so what is written is a
+ *            prefix of the batch;
+ *   work     scratch int32 [B] (the length of every image, -1 for a refused row). */
+typedef struct abc_molblock_desc {
+    const int32_t* mol_counts;   /* [B][4]                 as abc_assemble_desc.mol_counts */
+    const int32_t* mol_atoms;    /* [B][cap_atoms][5] */
+    const int32_t* mol_bonds;    /* [B][cap_mol_bonds][4] */
+    const int32_t* mol_implh;    /* [B][cap_atoms] */
+    int32_t B, cap_atoms, cap_mol_bonds;   /* all >= 1 */
+    uint8_t* text;               /* [cap_text] */
+    int32_t* index;              /* [2 B + 1] */
+    int32_t* work;               /* [B] */
+    int64_t cap_text;            /* 1 .. 2^31 - 1 */
+} abc_molblock_desc;
+/* Host arithmetic only (no device is touched; of the descriptor only cap_atoms and cap_mol_bonds are read): an upper bound of ONE
+ * image's text at these capacities, 0 for capacities below 1.  Derived line by line with every number at its widest: the head and the
+ * counts line with both counts at max(3, digits of the capacity); cap_atoms atom lines of two 13-column coordinates (four leading
+ * columns, four integer digits -- 199999 / 60 - 1 < 10000 -- and ".dddd") plus the fixed columns; cap_mol_bonds bond lines of four
+ * 11-column numbers ("-2147483648"); a charge line naming every atom (index at max(4, digits), charge at 11 columns); the STY and
+ * SLB lines and four lines per entry for cap_atoms implicit-H entries (entry number at the capacity's digits, atom at 11
+ * columns); the end.  Not tight (a bond line of in-range rows has 13 bytes, not 45): 224 867 bytes at 512 atoms and 2048 bonds. */
+int64_t abc_molblock_text_bytes(const abc_molblock_desc* d);
+/* refuses null pointers, B < 1, capacities < 1, cap_text outside 1 .. 2^31 - 1, and capacities at which
+ * abc_molblock_text_bytes passes 2^31 - 1 */
+int abc_write_molblocks(const abc_molblock_desc* d, abc_stream_t stream);
+/* sizeof(abc_molblock_desc), for a binding's mirror struct (as abc_graph_similarity_desc_size) */
+int abc_molblock_desc_size(void);
 
 /* ---- unet2: CBAM attention + residual (unet2.py:6-74).  See csrc/cbam.hip for the pass structure. ---- */
 typedef struct abc_cbam_channel_desc { /* ChannelAttentionModule (unet2.py:6-22), one MLP evaluation per image */

@@ -14,13 +14,18 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            refine_equal and exact (InferenceRunner(score_graphs=True, score_similarity=True), one step, csrc/graph_sim.hip), and
            step() with score_graphs=True against the same with score_similarity=True as well (as `step`)
 
+  text     the mol block text written on the device (csrc/molblock.hip, InferenceRunner(molblocks=True)): molecules() plus
+           Molecule.molblock() of every image on the host against molblocks() (wall time per batch, alternated, median of the
+           repetitions), abc_write_molblocks alone (its two launches, as `launch`), the bytes molblocks() copies, and step() with
+           assemble=True against the same with molblocks=True (as `step`, with the spread of the block medians)
+
   --omega-rule {raw,peaks}: the extractor's candidate rule of every runner built here (InferenceRunner(omega_rule=...): "raw" is
            img2smiles2.py:139, "peaks" img2smiles.py:139 / img2smiles3.py:140); `graphs` and `score` then also report the candidates
            per image and abc_extract_peaks alone (as `launch`).  profiles/r09_omega_rule.md is one run per rule.
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity] [--omega-rule raw]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,text] [--omega-rule raw]
 """
 import argparse
 import json
@@ -156,6 +161,62 @@ def part_host(r, reps=20):
           "note": "wall time of one call per batch of %d: D2H copies + host list building, one host thread" % B})
 
 
+def part_text(m, x, steps, warmup, reps=30, iters=200):
+    rs = {}
+    for name, kw in (("assemble=True", dict(assemble=True)), ("assemble+molblocks", dict(assemble=True, molblocks=True))):
+        r = InferenceRunner(m, B, S, S, use_graph=True, omega_rule=RULE, **kw)
+        r.load_batch(x.to("cuda"))
+        for _ in range(2):
+            r.step()
+        rs[name] = r
+    torch.cuda.synchronize()
+    r = rs["assemble+molblocks"]
+
+    def host():
+        return [mol.molblock() if mol is not None else None for mol in r.molecules()]
+    want, got = host(), r.molblocks()
+    wall = {"host": [], "device": []}
+    for _ in range(reps):
+        for name, f in (("host", host), ("device", r.molblocks)):
+            t0 = time.perf_counter()
+            f()
+            wall[name].append((time.perf_counter() - t0) * 1000)
+    off = r.texter.index.cpu().tolist()[:B + 1]
+    med = {k: statistics.median(v) for k, v in wall.items()}
+    emit({"part": "text", "what": "host", "batch": B, "molecules_plus_molblock_ms": round(med["host"], 4),
+          "molecules_plus_molblock_ms_min": round(min(wall["host"]), 4), "molblocks_ms": round(med["device"], 4),
+          "molblocks_ms_min": round(min(wall["device"]), 4), "ratio": round(med["host"] / med["device"], 2), "equal": got == want,
+          "molecules": sum(t is not None for t in got), "text_bytes": off[B], "index_bytes": 4 * (2 * B + 1),
+          "cap_text": r.texter.cap_text, "note": "wall time of one call per batch of %d, %d alternated repetitions, one host thread" % (B, reps)})
+    us = [launch_us(r.texter.run, iters) for _ in range(3)]
+    emit({"part": "text", "what": "launch", "batch": B, "us_per_call": [round(v, 2) for v in us],
+          "assemble_us_per_launch": round(launch_us(r.assembler.run, iters), 2),
+          "method": "device events around %d back-to-back calls of two launches each (launch gaps included)" % iters})
+    # the step: block medians of each form as well, for the block-to-block spread
+    for q in rs.values():
+        for _ in range(warmup):
+            q.step()
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in rs}
+    for blk in range(8):
+        for name, q in (rs.items() if blk % 2 == 0 else reversed(list(rs.items()))):
+            ev = []
+            for _ in range(max(steps // 8, 1)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                q.step()
+                e1.record()
+                ev.append((e0, e1))
+            torch.cuda.synchronize()
+            blocks[name].append(statistics.median(a.elapsed_time(b) for a, b in ev))
+    med = {k: statistics.median(v) for k, v in blocks.items()}
+    for k, v in blocks.items():
+        emit({"part": "text", "what": "step", "form": k, "batch": B, "size": S, "blocks": len(v), "ms_per_step_median": round(med[k], 4),
+              "block_medians_min_max": [round(min(v), 4), round(max(v), 4)],
+              "block_spread_percent": round(100 * (max(v) - min(v)) / med[k], 3)})
+    emit({"part": "text", "molblocks_minus_assemble_ms": round(med["assemble+molblocks"] - med["assemble=True"], 4)})
+
+
 def annotated_graph(atoms_s, bonds_s):
     atoms = {}
     for a in atoms_s.strip(";").split(";"):
@@ -285,6 +346,8 @@ def main():
         part_score({k: ss[k] for k in ("assemble+evaluate", "assemble+evaluate+score")}, a.steps, a.warmup)
     if "similarity" in parts:
         part_similarity(ss, a.steps, a.warmup)
+    if "text" in parts:
+        part_text(m, x, a.steps, a.warmup)
 
 
 if __name__ == "__main__":
