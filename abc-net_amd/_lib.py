@@ -217,6 +217,12 @@ class MolBlockDesc(C.Structure):
                 ("cap_mol_bonds", i32), ("text", vp), ("index", vp), ("work", vp), ("cap_text", i64)]
 
 
+class ScanDesc(C.Structure):
+    _fields_ = [("out", vp), ("src", vp), ("src_stride", i64), ("src_pitch", i32), ("src_max_h", i32), ("params", vp),
+                ("params_host", vp), ("B", i32), ("S", i32), ("margin", i32), ("cover_q8", i32), ("polarity", i32), ("hist", vp),
+                ("box", vp), ("geom", vp)]
+
+
 EVAL_NCOUNT = 301   # ABC_EVAL_NCOUNT
 # the ABC_GS_* columns of abc_graph_score_desc.rows / .totals
 GRAPH_SCORE_COLUMNS = ("counted", "none", "truncated", "exact", "atoms_equal", "bonds_equal", "atoms_true", "atoms_pred",
@@ -227,6 +233,12 @@ GRAPH_SIM_COLUMNS = ("counted", "none", "truncated", "size_equal", "refine_equal
 GRAPH_SIM_IDS = 2048    # ABC_SIM_IDS: ids_out is uint64 [B][2][GRAPH_SIM_IDS]
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
+SCAN_NPARAM = 2     # abc_scan_param: src_h, src_w
+SCAN_DARK, SCAN_LIGHT, SCAN_AUTO = 0, 1, 2      # abc_scan_polarity
+SCAN_CONSTANT, SCAN_BAD_PARAMS = 1, 2           # abc_scan_status
+SCAN_NBOX = 8       # ABC_SCAN_NBOX
+# the abc_scan_geom columns of abc_scan_desc.geom
+SCAN_GEOM_COLUMNS = ("thr", "inverted", "status", "y0", "x0", "bh", "bw", "rows", "cols", "ddx", "ddy", "ink")
 MOL_EMPTY, MOL_TRUNCATED = 1, 2     # abc_mol_status
 TEXT_BAD_ROW, TEXT_OVERFLOW = 4, 8  # abc_text_status (the status words of abc_write_molblocks)
 
@@ -301,6 +313,8 @@ SYMBOLS = {
     "abc_assemble_graphs": (C.c_int, [P(AssembleDesc), vp]),
     "abc_rasterize_targets": (C.c_int, [P(RasterDesc), vp]),
     "abc_build_images": (C.c_int, [P(ImageDesc), vp]),
+    "abc_build_scan_images": (C.c_int, [P(ScanDesc), vp]),
+    "abc_scan_desc_size": (C.c_int, []),
     "abc_metrics_blocks": (C.c_int, [P(MetricsDesc)]),
     "abc_metrics_update": (C.c_int, [P(MetricsDesc), vp]),
     "abc_eval_tables_blocks": (C.c_int, [P(EvalDesc)]),
@@ -385,7 +399,7 @@ def load():
         n = lib.abc_sizeof(i)
         if n != C.sizeof(st):
             raise AbcNetHipError("struct #%d (%s): binding has %d bytes, library %d" % (i, st.__name__, C.sizeof(st), n))
-    # (abc_eval_desc, abc_graph_score_desc, abc_graph_similarity_desc and abc_molblock_desc are not in abc_sizeof's list: they report their own sizes)
+    # (abc_eval_desc, abc_graph_score_desc, abc_graph_similarity_desc, abc_molblock_desc and abc_scan_desc are not in abc_sizeof's list: they report their own sizes)
     if lib.abc_eval_desc_size() != C.sizeof(EvalDesc):
         raise AbcNetHipError("struct EvalDesc: binding has %d bytes, library %d" % (C.sizeof(EvalDesc), lib.abc_eval_desc_size()))
     if lib.abc_graph_score_desc_size() != C.sizeof(GraphScoreDesc):
@@ -395,6 +409,8 @@ def load():
                              % (C.sizeof(GraphSimilarityDesc), lib.abc_graph_similarity_desc_size()))
     if lib.abc_molblock_desc_size() != C.sizeof(MolBlockDesc):
         raise AbcNetHipError("struct MolBlockDesc: binding has %d bytes, library %d" % (C.sizeof(MolBlockDesc), lib.abc_molblock_desc_size()))
+    if lib.abc_scan_desc_size() != C.sizeof(ScanDesc):
+        raise AbcNetHipError("struct ScanDesc: binding has %d bytes, library %d" % (C.sizeof(ScanDesc), lib.abc_scan_desc_size()))
     _lib = lib
     return lib
 

@@ -9,6 +9,10 @@ utils_for_test.py:21-27, split into a tiny host half and one kernel.
 The salt and pepper fields come from a counter hash of (key, pixel) on the device (abc_noise_hash, mirrored by noise_hash
 below), not from np.random's per-pixel stream: per pixel they follow the reference's distribution -- Bernoulli with the drawn
 amounts -- not its bits.  That is the position the dropout mask takes (dropout.py, K7).  No CPU fallback.
+
+A third way to build the input, "scan": ScanBuilder takes raw grey scans of any size and background level (what binarize.py's
+offline Otsu step and utils_for_test.py's loader do between them, plus the crop and the fit a scan needs) and csrc/scan.hip
+thresholds, crops, fits and writes them; otsu_threshold and fit_scan below are the pure host mirrors of its rules.
 """
 from __future__ import annotations
 
@@ -190,6 +194,151 @@ class ImageBuilder:
         """one launch (graph-capturable): the f32 batch into self.out"""
         L.check(self.lib.abc_build_images(C.byref(self.d), stream_or_current(stream, self.out.device)), "build_images")
         return self.out
+
+
+# ------------------------------------------------------------------------------------------------------------------ scans
+POLARITIES = {"dark": L.SCAN_DARK, "light": L.SCAN_LIGHT, "auto": L.SCAN_AUTO}
+# the coverage a destination pixel needs (in 1/256 of its source box) when none is given: the one with the best mean environment
+# similarity on the frozen trained fixture, the smaller one on a tie (profiles/r13_scan.md, profiles/tools/scan_step.py)
+DEFAULT_COVER_Q8 = 128
+
+
+def otsu_threshold(hist):
+    """the threshold rule of abc_build_scan_images on a 256-bin histogram (any integer counts, total <= 2^24): the smallest
+    admissible t (both sides non-empty) with maximal sigma(t) = (d * d) / (w0 * w1) in float64, d = S w0 - N s0 exact in int64;
+    None when the image holds a single value.  Pure host arithmetic, bit for bit what the device computes."""
+    h = np.asarray(hist).astype(np.int64).reshape(256)
+    w0 = np.cumsum(h)
+    s0 = np.cumsum(h * np.arange(256, dtype=np.int64))
+    N, S = int(w0[-1]), int(s0[-1])
+    w1 = N - w0
+    ok = (w0 > 0) & (w1 > 0)
+    if not ok.any():
+        return None
+    d = (S * w0 - N * s0).astype(np.float64)
+    num = d * d
+    den = w0.astype(np.float64) * w1.astype(np.float64)
+    sigma = np.full(256, -1.0)
+    sigma[ok] = num[ok] / den[ok]
+    return int(np.argmax(sigma))      # (the first index of the maximum)
+
+
+def fit_scan(bh, bw, size, margin):
+    """the fit rule of abc_build_scan_images: (rows, cols, ddx, ddy) of a bh x bw bounding box on a size x size canvas; never
+    upscales, floor division"""
+    bh, bw, S, margin = int(bh), int(bw), int(size), int(margin)
+    if bh < 1 or bw < 1 or not 0 <= 2 * margin < S:
+        raise ValueError("fit_scan: a box of at least 1 x 1 and 0 <= 2 * margin < size, got %s" % ((bh, bw, S, margin),))
+    lim, m = S - 2 * margin, max(bh, bw)
+    rows, cols = (bh, bw) if m <= lim else (max(1, bh * lim // m), max(1, bw * lim // m))
+    return rows, cols, (S - rows) // 2, (S - cols) // 2
+
+
+def scan_record_offsets(y0, x0, bh, bw, rows, cols, ddx, ddy):
+    """(scale_x, scale_y, ddx', ddy'): the affine map of SOURCE coordinates onto the canvas, what raster.parse_record and
+    parse_graph take -- x * scale_x + ddx' with scale_x = rows / bh and ddx' = ddx - y0 * scale_x (x indexes rows)"""
+    scale_x, scale_y = rows / bh, cols / bw
+    return scale_x, scale_y, ddx - y0 * scale_x, ddy - x0 * scale_y
+
+
+class ScanBuilder:
+    """raw grey scans into f32 [batch, 1, size, size] on the device (csrc/scan.hip; the contract: include/abcnet_hip.h,
+    abc_scan_desc): per image a histogram, an Otsu threshold, the polarity, the ink's bounding box, an aspect-preserving fit
+    with `margin` that never upscales, and a downscale by coverage -- a destination pixel is ink when its source box holds
+    at least one ink pixel and at least cover / 256 of its area.  `out` may be an InferenceRunner's or a Trainer's
+    .input_images, as with ImageBuilder.  max_src = (rows, cols) capacity of a source, at most 4096 x 4096.
+
+    margin defaults to the margin=20 of synthetic.drawn_molecules at 512, scaled: size * 20 // 512.  cover (0 .. 256, in
+    1 / 256) defaults to DEFAULT_COVER_Q8, the value with the best mean environment similarity of the frozen trained fixture
+    in profiles/r13_scan.md -- measured on SYNTHETIC drawings made into scans on the host, because no real scan was
+    available.  No CPU fallback."""
+
+    def __init__(self, batch, size, out=None, max_src=(1024, 1024), margin=None, cover=None, polarity="dark", device="cuda"):
+        if polarity not in POLARITIES:
+            raise ValueError("ScanBuilder: polarity must be 'dark', 'light' or 'auto', got %r" % (polarity,))
+        if not torch.cuda.is_available():
+            raise L.AbcNetHipError("ScanBuilder needs an MI355X; abcnet_amd has no CPU fallback")
+        S = int(size)
+        if S < 8 or S % 8 or S > 8192:
+            raise ValueError("ScanBuilder: size must be a multiple of 8 (8 .. 8192), got %d" % S)
+        max_h, max_w = int(max_src[0]), int(max_src[1])
+        if not (1 <= max_h <= 4096 and 1 <= max_w <= 4096):
+            raise ValueError("ScanBuilder: sources are at most 4096 x 4096, got max_src %s" % ((max_h, max_w),))
+        if not 1 <= batch <= 65535:
+            raise ValueError("ScanBuilder: batch must be 1 .. 65535, got %d" % batch)
+        margin = S * 20 // 512 if margin is None else int(margin)
+        cover = DEFAULT_COVER_Q8 if cover is None else int(cover)
+        if not 0 <= 2 * margin < S:
+            raise ValueError("ScanBuilder: 0 <= 2 * margin < size, got margin %d at size %d" % (margin, S))
+        if not 0 <= cover <= 256:
+            raise ValueError("ScanBuilder: cover is in 1 / 256, 0 .. 256, got %d" % cover)
+        shape = (batch, 1, S, S)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float32, device=device)
+        if tuple(out.shape) != shape:
+            raise L.AbcNetHipError("ScanBuilder: out %s does not match the contract %s (a %d-channel input is not an image of this "
+                                   "loader)" % (tuple(out.shape), shape, out.shape[1] if out.dim() == 4 else -1))
+        require_device_tensor(out, torch.float32, "ScanBuilder: out")
+        self.lib = L.load()
+        self.out, self.B, self.S, self.margin, self.cover, self.polarity = out, batch, S, margin, cover, polarity
+        self.max_h, self.max_w = max_h, max_w
+        self.pitch = -(-max_w // 16) * 16
+        dev = out.device
+        self.staging = PinnedStaging(dev, {"src": ((batch, max_h, self.pitch), torch.uint8, 255), "par": ((batch, L.SCAN_NPARAM), torch.int32)})
+        self.h_src, self.h_par = self.staging.host.values()
+        self.d_src, self.d_par = self.staging.dev.values()
+        self._np_src, self._np_par = self.h_src.numpy(), self.h_par.numpy()
+        self.hist = torch.zeros((batch, 256), dtype=torch.int32, device=dev)             # (uint32 bit patterns)
+        self.box = torch.zeros((batch, L.SCAN_NBOX), dtype=torch.int32, device=dev)
+        self.geom = torch.zeros((batch, len(L.SCAN_GEOM_COLUMNS)), dtype=torch.int32, device=dev)
+        d = L.ScanDesc()
+        d.out, d.src, d.params = out.data_ptr(), self.d_src.data_ptr(), self.d_par.data_ptr()
+        d.params_host = self.h_par.data_ptr()      # (what the last load staged: checked by every eager call)
+        d.src_stride, d.src_pitch, d.src_max_h = max_h * self.pitch, self.pitch, max_h
+        d.B, d.S, d.margin, d.cover_q8, d.polarity = batch, S, margin, cover, POLARITIES[polarity]
+        d.hist, d.box, d.geom = self.hist.data_ptr(), self.box.data_ptr(), self.geom.data_ptr()
+        self.d = d
+
+    def load(self, images_u8):
+        """images_u8: B 2-d uint8 arrays (decoded grey scans), each within max_src.  Host work: the checks and one memcpy per
+        image into pinned staging, then an asynchronous H2D copy."""
+        if len(images_u8) != self.B:
+            raise ValueError("expected %d images" % self.B)
+        imgs = []
+        for b, img in enumerate(images_u8):
+            img = np.asarray(img)
+            if img.dtype != np.uint8 or img.ndim != 2:
+                raise ValueError("image %d: a 2-d uint8 array, got %s %s" % (b, img.dtype, img.shape))
+            h, w = img.shape
+            if h < 1 or w < 1:
+                raise ValueError("image %d: an empty array (%d x %d)" % (b, h, w))
+            if h > self.max_h or w > self.max_w:
+                raise ValueError("image %d: %d x %d exceeds the staging capacity %d x %d" % (b, h, w, self.max_h, self.max_w))
+            imgs.append(img)
+        self.staging.wait()
+        for b, img in enumerate(imgs):
+            self._np_src[b, :img.shape[0], :img.shape[1]] = img
+            self._np_par[b] = img.shape
+        self.staging.commit()
+
+    def run(self, stream=None):
+        """five launches in order on one stream (graph-capturable): the f32 batch into self.out, the geometry rows beside it"""
+        L.check(self.lib.abc_build_scan_images(C.byref(self.d), stream_or_current(stream, self.out.device)), "build_scan_images")
+        return self.out
+
+    def geometry(self):
+        """the geometry rows of the last run() as a structured numpy array [B] with the int32 fields L.SCAN_GEOM_COLUMNS (thr,
+        inverted, status, y0, x0, bh, bw, rows, cols, ddx, ddy, ink).  The only call here that synchronises."""
+        rows = np.ascontiguousarray(self.geom.cpu().numpy())
+        return rows.view(np.dtype([(c, np.int32) for c in L.SCAN_GEOM_COLUMNS])).reshape(self.B)
+
+    def record_offsets(self, b):
+        """(scale_x, scale_y, ddx', ddy') of image b after run(): what raster.parse_record / parse_graph take, so that
+        annotations in the scan's own coordinates can be graded with the evaluators that exist (synchronises: geometry())"""
+        g = self.geometry()[b]
+        if g["status"]:
+            raise ValueError("image %d has no drawing (status %d)" % (b, int(g["status"])))
+        return scan_record_offsets(*(int(g[c]) for c in ("y0", "x0", "bh", "bw", "rows", "cols", "ddx", "ddy")))
 
 
 class SampleBuilder:

@@ -575,6 +575,60 @@ typedef struct abc_image_desc {
 } abc_image_desc;
 int abc_build_images(const abc_image_desc* d, abc_stream_t stream);
 
+/* Raw grey scans of any size into out[B][1][S][S], f32 {0, 1} (csrc/scan.hip): the offline step the reference
+ * only hints at (binarize.py: cv2.threshold(img, 0, 255, THRESH_BINARY + THRESH_OTSU)) composed with utils_for_test.py:21-27, plus
+ * the crop and the fit a scan needs.  Everything is exact integer arithmetic except sigma(t) below.  For image b, src_h x src_w
+ * bytes (params[b]); bytes of its slot outside them are never read into any result.
+ *   histogram  h[v] = the count of byte v; N = src_h * src_w <= 2^24.
+ *   threshold  for t = 0 .. 255: w0 = sum_{v <= t} h[v], s0 = sum_{v <= t} v h[v], w1 = N - w0, S = s0(255),
+ *              d = S w0 - N s0 (int64, exact: |d| < 2^56); t is admissible when w0 > 0 and w1 > 0;
+ *              sigma(t) = ((double)d * (double)d) / ((double)w0 * (double)w1): two multiplies and one divide, each rounded on its
+ *              own, never fused.  Every input is an exact integer, so the value does not depend on the order the histogram was
+ *              summed in, and IEEE float64 anywhere (numpy) gives the same bits.  thr = the SMALLEST admissible t with maximal
+ *              sigma.  No admissible t (one byte value only): status ABC_SCAN_CONSTANT, a blank output.
+ *              sigma is the classical between-class variance up to the constant factor N^2.  It is NOT claimed to be
+ *              bit-identical to OpenCV's Otsu in near-ties: no OpenCV was at hand to check against.
+ *   polarity   ABC_SCAN_DARK: ink = byte <= thr (binarize.py:5 then utils_for_test.py:22-24); ABC_SCAN_LIGHT: ink = byte > thr;
+ *              ABC_SCAN_AUTO: LIGHT when 2 w0(thr) > N (the dark side is the majority), else DARK.
+ *   box        y0, y1, x0, x1 of the ink pixels, inclusive; bh = y1 - y0 + 1, bw = x1 - x0 + 1.
+ *   fit        never upscales.  L = S - 2 margin, m = max(bh, bw); m <= L: rows = bh, cols = bw; else rows = max(1, bh L / m),
+ *              cols = max(1, bw L / m) (floor division in 64 bits); ddx = (S - rows) / 2, ddy = (S - cols) / 2.
+ *   resample   destination (r, c), 0 <= r < rows, 0 <= c < cols, covers source rows y0 + floor(r bh / rows) ..
+ *              y0 + ceil((r + 1) bh / rows) - 1 and columns likewise with bw, cols, x0: never empty, never outside the box.
+ *              n = its ink pixels, a = its area: out = 1 iff n >= 1 and 256 n >= cover_q8 a, written at (ddx + r, ddy + c);
+ *              every other canvas pixel is 0 (the launch owns the whole output).
+ *   geom       int32 [B][ABC_SCAN_NGEOM] per image (abc_scan_geom order); ABC_SCAN_CONSTANT and ABC_SCAN_BAD_PARAMS rows have
+ *              thr = -1 and zeros in every column but the status.
+ * An image whose src_h or src_w is below 1 or above its slot (src_max_h, src_pitch) is written as NaN with ABC_SCAN_BAD_PARAMS;
+ * params_host (optional: a host copy of the table) is checked at call time instead (ABC_EINVAL).
+ * Five launches on the stream, in order, no parallel branch (capturable), no sync, no allocation: hist and box are the caller's
+ * scratch, zeroed / reset by the sequence itself. */
+enum abc_scan_param { ABC_SCAN_SRC_H = 0, ABC_SCAN_SRC_W, ABC_SCAN_NPARAM };
+enum abc_scan_polarity { ABC_SCAN_DARK = 0, ABC_SCAN_LIGHT = 1, ABC_SCAN_AUTO = 2 };
+enum abc_scan_status { ABC_SCAN_CONSTANT = 1, ABC_SCAN_BAD_PARAMS = 2 };
+enum abc_scan_geom { ABC_SCAN_G_THR = 0, ABC_SCAN_G_INVERTED, ABC_SCAN_G_STATUS, ABC_SCAN_G_Y0, ABC_SCAN_G_X0, ABC_SCAN_G_BH,
+                     ABC_SCAN_G_BW, ABC_SCAN_G_ROWS, ABC_SCAN_G_COLS, ABC_SCAN_G_DDX, ABC_SCAN_G_DDY, ABC_SCAN_G_INK, ABC_SCAN_NGEOM };
+enum { ABC_SCAN_NBOX = 8 };         /* scratch words per image of abc_scan_desc.box */
+typedef struct abc_scan_desc {
+    float* out;                     /* [B][1][S][S] f32, 16-byte aligned */
+    const uint8_t* src;             /* image b at src + b * src_stride, its row i at + i * src_pitch (16-byte aligned) */
+    int64_t src_stride;             /* bytes between images, >= src_max_h * src_pitch, multiple of 16 */
+    int32_t src_pitch;              /* bytes between rows, multiple of 16, <= 4096 */
+    int32_t src_max_h;              /* rows an image slot holds, <= 4096 */
+    const int32_t* params;          /* device [B][ABC_SCAN_NPARAM] */
+    const int32_t* params_host;     /* optional host copy of params, validated at call time (NULL: not checked) */
+    int32_t B, S;                   /* 1 <= B <= 65535; S a multiple of 8 (one thread writes 8 consecutive pixels), 8 <= S <= 8192 */
+    int32_t margin;                 /* 0 <= 2 margin < S */
+    int32_t cover_q8;               /* 0 .. 256: the ink coverage (in 1/256) a destination pixel needs; 0: any ink */
+    int32_t polarity;               /* abc_scan_polarity */
+    uint32_t* hist;                 /* scratch [B][256] */
+    int32_t* box;                   /* scratch [B][ABC_SCAN_NBOX] */
+    int32_t* geom;                  /* out [B][ABC_SCAN_NGEOM] */
+} abc_scan_desc;
+int abc_build_scan_images(const abc_scan_desc* d, abc_stream_t stream);
+/* sizeof(abc_scan_desc), for a binding's mirror struct (as abc_molblock_desc_size) */
+int abc_scan_desc_size(void);
+
 /* Candidate extraction for the SMILES decoder (img2smiles2.py:113-191; replaces its per-pixel .cpu().item() loops):
  * from the NMS masks of abc_nms_peaks and the raw head maps (all NCHW f32) to compact ordered lists per image.
  *   atoms[b][i] = (x, y, type, charge, hs)      raster order, greedy suppression within squared distance < 4
