@@ -240,12 +240,19 @@ SCAN_NBOX = 8       # ABC_SCAN_NBOX
 # the abc_scan_geom columns of abc_scan_desc.geom
 SCAN_GEOM_COLUMNS = ("thr", "inverted", "status", "y0", "x0", "bh", "bw", "rows", "cols", "ddx", "ddy", "ink")
 MOL_EMPTY, MOL_TRUNCATED = 1, 2     # abc_mol_status
+# enum abc_decoder_limit: cap_atoms (extract, assemble, score), bond peaks expanded per image, score record capacity, similarity atoms
+MAX_CAP_ATOMS, MAX_BOND_PEAKS, MAX_SCORE_RECORD, MAX_SIM_ATOMS = 2048, 4096, 1024, 512
 TEXT_BAD_ROW, TEXT_OVERFLOW = 4, 8  # abc_text_status (the status words of abc_write_molblocks)
 
 
 _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnApplyDesc, WgradDesc, WgradReduceDesc,
             LossDesc, LossFinDesc, AdamDesc, NmsDesc, CbamChannelDesc, CbamPixDesc, CbamConv7Desc, MetricsDesc, ExtractDesc, RasterDesc,
             HeadsFusedDesc, HeadsEpi, ConvTDesc, LossScaleDesc, AdamSeg, AdamClass, AdamMultiDesc, ImageDesc, AssembleDesc]
+
+# the descriptors that are not in abc_sizeof's list: each reports its own size
+SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_score_desc_size"),
+              (GraphSimilarityDesc, "abc_graph_similarity_desc_size"), (MolBlockDesc, "abc_molblock_desc_size"),
+              (ScanDesc, "abc_scan_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -399,18 +406,10 @@ def load():
         n = lib.abc_sizeof(i)
         if n != C.sizeof(st):
             raise AbcNetHipError("struct #%d (%s): binding has %d bytes, library %d" % (i, st.__name__, C.sizeof(st), n))
-    # (abc_eval_desc, abc_graph_score_desc, abc_graph_similarity_desc, abc_molblock_desc and abc_scan_desc are not in abc_sizeof's list: they report their own sizes)
-    if lib.abc_eval_desc_size() != C.sizeof(EvalDesc):
-        raise AbcNetHipError("struct EvalDesc: binding has %d bytes, library %d" % (C.sizeof(EvalDesc), lib.abc_eval_desc_size()))
-    if lib.abc_graph_score_desc_size() != C.sizeof(GraphScoreDesc):
-        raise AbcNetHipError("struct GraphScoreDesc: binding has %d bytes, library %d" % (C.sizeof(GraphScoreDesc), lib.abc_graph_score_desc_size()))
-    if lib.abc_graph_similarity_desc_size() != C.sizeof(GraphSimilarityDesc):
-        raise AbcNetHipError("struct GraphSimilarityDesc: binding has %d bytes, library %d"
-                             % (C.sizeof(GraphSimilarityDesc), lib.abc_graph_similarity_desc_size()))
-    if lib.abc_molblock_desc_size() != C.sizeof(MolBlockDesc):
-        raise AbcNetHipError("struct MolBlockDesc: binding has %d bytes, library %d" % (C.sizeof(MolBlockDesc), lib.abc_molblock_desc_size()))
-    if lib.abc_scan_desc_size() != C.sizeof(ScanDesc):
-        raise AbcNetHipError("struct ScanDesc: binding has %d bytes, library %d" % (C.sizeof(ScanDesc), lib.abc_scan_desc_size()))
+    for st, size_fn in SELF_SIZED:
+        n = getattr(lib, size_fn)()
+        if n != C.sizeof(st):
+            raise AbcNetHipError("struct %s: binding has %d bytes, library %d" % (st.__name__, C.sizeof(st), n))
     _lib = lib
     return lib
 

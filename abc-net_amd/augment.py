@@ -370,7 +370,7 @@ class SampleBuilder:
         if not (n == len(atoms_strings) == len(bonds_strings)) or not (n == self.B or (self.short_batches and 0 <= n < self.B)):
             raise ValueError("expected %s%d images and annotation pairs" % ("up to " if self.short_batches else "", self.B))
         # (an InferenceRunner(score_graphs=True) or (score_similarity=True): both read graph records)
-        scored = getattr(self.trainer, "scorer", None) is not None or getattr(self.trainer, "similarity", None) is not None
+        scored = getattr(self.trainer, "wants_graph_records", False)
         draws, records, graphs = [], [], []
         for img, a, q in zip(images_u8, atoms_strings, bonds_strings):
             dr, offs = draw_augment(rng, self.images.amount, np.shape(img), self.S)

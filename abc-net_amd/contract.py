@@ -127,3 +127,121 @@ def refuse_dense_targets(rasterizer):
     if rasterizer is not None:
         raise L.AbcNetHipError("load_batch(dense targets) under use_sparse_targets(): the rasteriser's group flags would no longer "
                                "describe the maps; load records into the rasteriser, or call use_sparse_targets(None) first")
+
+
+# ---------- the decoder: rows and records its stages hand to each other; words per row as csrc/mol_rows.hpp, DESIGN.md section 7
+ATOM_W, CAND_W, MOL_BOND_W, REC_ATOM_W, REC_BOND_W = 5, 4, 4, 4, 3
+
+
+def _require_layout(who, names, tensors, shapes):
+    """every one a tensor, then of its shape in shapes(B, cap_a, cap_b), B and cap_a read from tensors[1], cap_b from tensors[2]"""
+    for name, t in zip(names, tensors):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+    dims = tuple(tensors[1].shape[:2]) + tuple(tensors[2].shape[1:2])
+    if len(dims) != 3 or [tuple(t.shape) for t in tensors] != shapes(*dims)[:len(tensors)]:
+        raise ValueError("%s: %s must be %s, got %s" % (who, ", ".join(names[:len(tensors)]), shapes("B", "cap_a", "cap_b")[:len(tensors)],
+                                                        [tuple(t.shape) for t in tensors]))
+    return dims
+
+
+class CandidateLists:
+    """PeakExtractor's output, GraphAssembler's input: int32 counts, atoms and bonds, f32 bond_rho, of SHAPES"""
+    NAMES = ("counts", "atoms", "bonds", "bond_rho")
+    SHAPES = staticmethod(lambda B, cap_atoms, cap_bonds: [(B, 4), (B, cap_atoms, ATOM_W), (B, cap_bonds, CAND_W), (B, cap_bonds)])
+
+    def __init__(self, counts, atoms, bonds, bond_rho):
+        self.tensors = (counts, atoms, bonds, bond_rho)
+        self.B, self.cap_atoms, self.cap_bonds = atoms.shape[0], atoms.shape[1], bonds.shape[1]
+
+    @classmethod
+    def checked(cls, who, counts, atoms=None, bonds=None, bond_rho=None):
+        """a CandidateLists or the four tensors (hand-made lists): type, shape (ValueError), then device and dtype (AbcNetHipError)"""
+        if isinstance(counts, cls):
+            counts, atoms, bonds, bond_rho = counts.tensors
+        _require_layout(who, cls.NAMES, (counts, atoms, bonds, bond_rho), cls.SHAPES)
+        for name, t in zip(cls.NAMES, (counts, atoms, bonds, bond_rho)):
+            require_device_tensor(t, torch.float32 if t is bond_rho else torch.int32, "%s: %s (the extractor's layout)" % (who, name))
+        return cls(counts, atoms, bonds, bond_rho)
+
+
+class MoleculeRows:
+    """GraphAssembler's output, read in place by MolBlockWriter, GraphScore and GraphSimilarity: int32 tensors of SHAPES; a row of
+    mol_counts is (atoms, bonds, implicit-H entries, L.MOL_* status bits); mol_implh is read by the text alone"""
+    NAMES = ("mol_counts", "mol_atoms", "mol_bonds", "mol_implh")
+    SHAPES = staticmethod(lambda B, cap_atoms, cap_mol_bonds: [(B, 4), (B, cap_atoms, ATOM_W), (B, cap_mol_bonds, MOL_BOND_W), (B, cap_atoms)])
+
+    def __init__(self, mol_counts, mol_atoms, mol_bonds, mol_implh=None):
+        self.tensors = (mol_counts, mol_atoms, mol_bonds, mol_implh)
+        self.B, self.cap_atoms, self.cap_mol_bonds, self.device = mol_atoms.shape[0], mol_atoms.shape[1], mol_bonds.shape[1], mol_atoms.device
+
+    @classmethod
+    def checked(cls, who, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, max_cap_atoms=None, need_implh=False, n_valid=None):
+        """a MoleculeRows or the separate tensors (hand-made rows): type, shape, range, n_valid's form (ValueError), then device (AbcNetHipError)"""
+        if isinstance(mol_counts, cls):
+            mol_counts, mol_atoms, mol_bonds, mol_implh = mol_counts.tensors
+        read = (mol_counts, mol_atoms, mol_bonds) + ((mol_implh,) if need_implh else ())
+        B, cap_atoms, cap_mol_bonds = _require_layout(who, cls.NAMES, read, cls.SHAPES)
+        if B < 1 or cap_atoms < 1 or cap_mol_bonds < 1 or (max_cap_atoms is not None and cap_atoms > max_cap_atoms):
+            raise ValueError("%s: B >= 1, cap_atoms %s and cap_mol_bonds >= 1, got %d, %d, %d"
+                             % (who, ">= 1" if max_cap_atoms is None else "1..%d" % max_cap_atoms, B, cap_atoms, cap_mol_bonds))
+        if n_valid is not None and not (isinstance(n_valid, torch.Tensor) and n_valid.numel() == 1):
+            raise ValueError("%s: n_valid must be a one-element int32 device tensor" % who)
+        for t in read + (() if n_valid is None else (n_valid,)):
+            require_device_tensor(t, torch.int32, "%s: %s (the assembler's layout)%s"
+                                  % (who, ", ".join(cls.NAMES[:len(read)]), "" if n_valid is None else " and n_valid"))
+        return cls(mol_counts, mol_atoms, mol_bonds, mol_implh if need_implh else None)
+
+    def fill(self, d):
+        """the mol_*, B and cap_* fields MolBlockDesc, GraphScoreDesc and GraphSimilarityDesc have in common"""
+        d.mol_counts, d.mol_atoms, d.mol_bonds = (t.data_ptr() for t in self.tensors[:3])
+        d.B, d.cap_atoms, d.cap_mol_bonds = self.B, self.cap_atoms, self.cap_mol_bonds
+
+
+class GraphRecords:
+    """One raster.parse_graph record per image in pinned staging and its device twins: atoms int32 [B, max_atoms, 4], bonds int32
+    [B, max_bonds, 3], counts int32 [2, B].  One object may serve several readers of a batch: it is loaded once, by its owner."""
+
+    def __init__(self, B, max_atoms, max_bonds, device):
+        self.B, self.max_atoms, self.max_bonds = int(B), int(max_atoms), int(max_bonds)
+        self.staging = PinnedStaging(device, {"atoms": ((self.B, self.max_atoms, REC_ATOM_W), torch.int32),
+                                              "bonds": ((self.B, self.max_bonds, REC_BOND_W), torch.int32), "cnt": ((2, self.B), torch.int32)})
+        self.loaded = False
+
+    @staticmethod
+    def validate(graphs, B, max_atoms, max_bonds):
+        """the half of load that needs no device: `graphs` as contiguous int32 (atoms [n, 4], bonds [m, 3]) pairs, or ValueError"""
+        import numpy as np
+        if len(graphs) > B:
+            raise ValueError("expected at most %d graph records, got %d" % (B, len(graphs)))
+        recs = []
+        for b, (a, q) in enumerate(graphs):
+            a, q = np.asarray(a), np.asarray(q)
+            if a.ndim != 2 or a.shape[1] != REC_ATOM_W or q.ndim != 2 or q.shape[1] != REC_BOND_W:
+                raise ValueError("record %d: atoms must be [n, 4] and bonds [m, 3], got %s and %s" % (b, a.shape, q.shape))
+            if len(a) > max_atoms or len(q) > max_bonds:
+                raise ValueError("record %d has %d atoms / %d bonds (capacity %d / %d)" % (b, len(a), len(q), max_atoms, max_bonds))
+            if len(q) and not ((0 <= q[:, 0]) & (q[:, 0] < q[:, 1]) & (q[:, 1] < len(a))).all():
+                raise ValueError("record %d: every bond must name atoms 0 <= i < j < %d" % (b, len(a)))
+            recs.append((np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(q, dtype=np.int32)))
+        return recs
+
+    def load(self, graphs):
+        """n <= B (atoms, bonds) pairs of raster.parse_graph; the rows past n get an empty record.  Asynchronous H2D of a few KB."""
+        recs = self.validate(graphs, self.B, self.max_atoms, self.max_bonds)
+        h_atoms, h_bonds, h_cnt = self.staging.host.values()
+        self.staging.wait()
+        h_cnt.zero_()
+        for b, (a, q) in enumerate(recs):
+            h_cnt[0, b], h_cnt[1, b] = len(a), len(q)
+            if len(a):
+                h_atoms[b, :len(a)] = torch.from_numpy(a)
+            if len(q):
+                h_bonds[b, :len(q)] = torch.from_numpy(q)
+        self.staging.commit()
+        self.loaded = True
+
+    def fill(self, d):
+        """the rec_* and max_* fields of GraphScoreDesc and GraphSimilarityDesc"""
+        d.rec_atoms, d.rec_bonds, d.rec_counts = (t.data_ptr() for t in self.staging.dev.values())
+        d.max_atoms, d.max_bonds = self.max_atoms, self.max_bonds

@@ -23,19 +23,21 @@
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
 #include "block_scan.hpp"
+#include "mol_rows.hpp"
 
 #include <climits>
 
 namespace {
 
 constexpr int AT = 1024;            // threads per workgroup
-constexpr int MAX_ATOMS = 2048;     // cap_atoms <= 2048 (as extract.hip)
-constexpr int EXTRACT_MAX_BPEAKS = 4096;   // bond peaks per image extract.hip expands (more: its lists are truncated)
+constexpr int MAX_ATOMS = ABC_MAX_CAP_ATOMS;
+constexpr int EXTRACT_MAX_BPEAKS = ABC_MAX_BOND_PEAKS;      // (more: the extractor's lists are truncated)
+static_assert(MAX_ATOMS <= 1 << 11, "an atom index fits the 11 bits of a pair key");
 constexpr int MAX_CAP_BONDS = 1 << 24;
 
 // img2smiles2.py:32-34 restricted to the vocabulary of utils.py:12-13 (index 0 decodes to 'C', img2smiles2.py:25)
 //                                  ?  C  N  O  P  F  Cl S  Br B  Se I  H  Si
-__constant__ int MAX_VALENCE[14] = {4, 4, 3, 2, 5, 1, 1, 6, 1, 3, 6, 1, 1, 4};
+__constant__ int MAX_VALENCE[N_SYMBOLS] = {4, 4, 3, 2, 5, 1, 1, 6, 1, 3, 6, 1, 1, 4};
 //                               count: 2 -> O, 3 -> N, 4 -> C, 5 -> P, 6 -> S, 7 -> Cl   (vocabulary indices)
 __constant__ int REPAIR_TYPE[8] = {0, 0, 3, 2, 1, 4, 7, 6};
 
@@ -76,8 +78,8 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
         return;
     }
     const int na = max(min(c1, d.cap_atoms), 0), nc = max(min(c3, d.cap_bonds), 0);
-    const int* atoms = d.atoms + (size_t)b * d.cap_atoms * 5;
-    const int* bonds = d.bonds + (size_t)b * d.cap_bonds * 4;
+    const int* atoms = d.atoms + (size_t)b * d.cap_atoms * ATOM_W;
+    const int* bonds = d.bonds + (size_t)b * d.cap_bonds * CAND_W;
     const float* rhos = d.bond_rho + (size_t)b * d.cap_bonds;
     int* pair = d.work + (size_t)b * ((size_t)d.cap_bonds + 2 * (size_t)slots_max);   // per candidate: end 1 << 16 | end 2, or -1
     int* keys = pair + d.cap_bonds;       // pair table: key = lower end << 11 | higher end, -1 = free
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
 
     // ---- (A)
     for (int a = tid; a < na; a += AT) {
-        const int* r = atoms + (size_t)a * 5;
+        const int* r = atoms + (size_t)a * ATOM_W;
         apos[a] = make_double2((double)r[0], (double)r[1]);
         ainfo[a] = (r[2] & 0xFF) | (r[4] != 0 ? 0x100 : 0);
         acount[a] = r[3] == 1 ? -1 : (r[3] == 2 ? 1 : 0);        // -charge (charge_vocab: 0 -> 0, 1 -> +1, 2 -> -1)
@@ -101,7 +103,7 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
 
     // ---- (B) bond ends (:193-210) and the pair table
     for (int i = tid; i < nc; i += AT) {
-        const int* c = bonds + (size_t)i * 4;
+        const int* c = bonds + (size_t)i * CAND_W;
         const int k = c[2];
         const double rho = (double)rhos[i];
         int pr = -1;
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
     __syncthreads();
 
     // ---- (C) the first candidate of every pair, in list order (:212-234); valence counts (:247-255), touched atoms (:236-245)
-    int* mb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * 4;
+    int* mb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
     int kept = 0;
     for (int base = 0; base < nc; base += AT) {
         const int i = base + tid;
@@ -159,8 +161,8 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
         const int pos = kept + (int)block_excl_scan<AT>(keep ? 1u : 0u, wt, &tot);
         if (keep && pos < d.cap_mol_bonds) {
             const int i1 = pr >> 16, i2 = pr & 0xFFFF;
-            const int order = bonds[(size_t)i * 4 + 3] + 1;          // bond_type_devocab
-            int* o = mb + (size_t)pos * 4;
+            const int order = bonds[(size_t)i * CAND_W + 3] + 1;          // bond_type_devocab
+            int* o = mb + (size_t)pos * MOL_BOND_W;
             o[0] = i1; o[1] = i2; o[2] = order; o[3] = i;             // (ends renumbered in (G))
             const int v = order >= 4 ? 1 : order;
             atomicAdd(acount + i1, v); atomicAdd(acount + i2, v);
@@ -176,12 +178,12 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
     // ---- (D) valence repair (:256-271)
     for (int a = tid; a < na; a += AT) {
         const int count = acount[a], info = ainfo[a], type = info & 0xFF;
-        const int maxv = type < 14 ? MAX_VALENCE[type] : 4;
+        const int maxv = type < N_SYMBOLS ? MAX_VALENCE[type] : 4;
         if (maxv < count && count >= 2 && count <= 7) ainfo[a] = (info & ~0xFF) | REPAIR_TYPE[count];
         acount[a] = INT_MAX;
     }
     // ---- (E) atoms some kept bond touches, numbered from 1 in list order (:273-287)
-    int* ma = d.mol_atoms + (size_t)b * d.cap_atoms * 5;
+    int* ma = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
     int natoms = 0;
     for (int base = 0; base < na; base += AT) {       // (the scan's barriers also order (D) before the reads of ainfo below)
         const int a = base + tid;
@@ -189,8 +191,8 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
         unsigned tot;
         const int idx = natoms + (int)block_excl_scan<AT>(shown ? 1u : 0u, wt, &tot);
         if (shown) {
-            const int* r = atoms + (size_t)a * 5;
-            int* o = ma + (size_t)idx * 5;
+            const int* r = atoms + (size_t)a * ATOM_W;
+            int* o = ma + (size_t)idx * ATOM_W;
             o[0] = r[0]; o[1] = r[1]; o[2] = ainfo[a] & 0xFF; o[3] = r[3] == 1 ? 1 : (r[3] == 2 ? -1 : 0); o[4] = r[4];
             anew[a] = idx + 1;
         }
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
 
     // ---- (F) first appearance (bond position, end) of every hetero atom with hs != 0 at an aromatic bond (:299-311)
     for (int p = tid; p < nk; p += AT) {
-        const int* o = mb + (size_t)p * 4;
+        const int* o = mb + (size_t)p * MOL_BOND_W;
         if (o[2] != 4) continue;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(AT) void assemble_kernel(const abc_assemble_desc d,
         const int p = base + tid;
         int f0 = 0, f1 = 0, n0 = 0, n1 = 0;
         if (p < nk) {
-            int* o = mb + (size_t)p * 4;
+            int* o = mb + (size_t)p * MOL_BOND_W;
             const int a0 = o[0], a1 = o[1];
             n0 = anew[a0]; n1 = anew[a1];
             if (o[2] == 4) { f0 = acount[a0] == 2 * p; f1 = acount[a1] == 2 * p + 1; }

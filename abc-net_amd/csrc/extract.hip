@@ -28,11 +28,12 @@
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
 #include "block_scan.hpp"
+#include "mol_rows.hpp"
 
 namespace {
 
 constexpr int XT = 1024;          // threads per workgroup
-constexpr int MAX_BPEAKS = 4096;  // bond peaks per image held for phase C (more are counted, not expanded)
+constexpr int MAX_BPEAKS = ABC_MAX_BOND_PEAKS;  // bond peaks per image held for phase C (more are counted, not expanded)
 
 template <int K>
 __device__ inline int argmax_plane(const float* p, size_t stride) {  // first maximum, as torch.argmax
@@ -50,7 +51,7 @@ template <int RULE>   // abc_omega_rule: one kernel per rule, so rule RAW carrie
 __global__ __launch_bounds__(XT) void extract_kernel(const abc_extract_desc d) {
     __shared__ unsigned wt[XT / 64 + 1];
     __shared__ int cnt[MAX_BPEAKS];
-    __shared__ int acc_xy[2048];   // accepted atoms (x << 16 | y), cap_atoms <= 2048
+    __shared__ int acc_xy[ABC_MAX_CAP_ATOMS];   // accepted atoms (x << 16 | y)
     __shared__ int n_acc_s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hw = d.h * d.w;
@@ -106,9 +107,9 @@ __global__ __launch_bounds__(XT) void extract_kernel(const abc_extract_desc d) {
         const int q = acc_xy[i];
         const int x = q >> 16, y = q & 0xFFFF;
         const size_t px = (size_t)x * d.w + y;
-        int* o = d.atoms + ((size_t)b * d.cap_atoms + i) * 5;
+        int* o = d.atoms + ((size_t)b * d.cap_atoms + i) * ATOM_W;
         o[0] = x; o[1] = y;
-        o[2] = argmax_plane<14>(d.types + (size_t)b * 14 * hw + px, hw);
+        o[2] = argmax_plane<N_SYMBOLS>(d.types + (size_t)b * N_SYMBOLS * hw + px, hw);
         o[3] = argmax_plane<3>(d.charges + (size_t)b * 3 * hw + px, hw);
         o[4] = argmax_plane<2>(d.hs + (size_t)b * 2 * hw + px, hw);
     }
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(XT) void extract_kernel(const abc_extract_desc d) {
         if (lane < 60 && ((m >> lane) & 1ull)) {
             const int slot = cnt[i] + __popcll(m & ((1ull << lane) - 1ull));
             if (slot < d.cap_bonds) {
-                int* o = d.bonds + ((size_t)b * d.cap_bonds + slot) * 4;
+                int* o = d.bonds + ((size_t)b * d.cap_bonds + slot) * CAND_W;
                 o[0] = x; o[1] = y; o[2] = lane;
                 o[3] = d.btype_idx != nullptr ? (int)d.btype_idx[((size_t)b * 60 + lane) * hw + p]
                                               : argmax_plane<6>(d.btypes + ((size_t)b * 360 + lane) * hw + p, (size_t)60 * hw);
@@ -180,7 +181,7 @@ extern "C" int64_t abc_extract_work_masks(const abc_extract_desc* d) { return (i
 
 extern "C" int abc_extract_peaks(const abc_extract_desc* d, abc_stream_t stream) {
     if (d->B < 1 || d->h < 1 || d->w < 1) return abc_fail(ABC_EINVAL, "extract: empty");
-    if (d->cap_atoms < 1 || d->cap_atoms > 2048 || d->cap_bonds < 1) return abc_fail(ABC_EINVAL, "extract: cap_atoms must be 1..2048, cap_bonds >= 1");
+    if (d->cap_atoms < 1 || d->cap_atoms > ABC_MAX_CAP_ATOMS || d->cap_bonds < 1) return abc_fail(ABC_EINVAL, "extract: cap_atoms must be 1..2048, cap_bonds >= 1");
     if (d->h >= 65536 || d->w >= 65536) return abc_fail(ABC_EUNSUPPORTED, "extract: map too large");
     if (!d->work || !d->work_masks || !d->counts || !d->atoms || !d->bonds || !d->bond_rho) return abc_fail(ABC_EINVAL, "extract: null buffer");
     if (d->omega_rule != ABC_OMEGA_RAW && d->omega_rule != ABC_OMEGA_PEAKS)

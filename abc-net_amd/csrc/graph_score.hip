@@ -16,19 +16,16 @@
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
+#include "mol_rows.hpp"
 
 namespace {
 
 constexpr int GT = 256;              // threads per workgroup
-constexpr int MAX_ATOMS = 2048;      // cap_atoms <= 2048 (as assemble.hip)
-constexpr int MAX_REC = 1024;        // max_atoms, max_bonds <= 1024 (pair key = lower index << 10 | higher index)
+constexpr int MAX_ATOMS = ABC_MAX_CAP_ATOMS;
+constexpr int MAX_REC = ABC_MAX_SCORE_RECORD;      // pair key = lower index << 10 | higher index
+static_assert(MAX_REC <= 1 << 10, "a record atom index fits the 10 bits of a pair key");
 constexpr int MAX_RADIUS = 1 << 15;
 constexpr int NCOL = ABC_GS_NCOL;
-
-__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// the symbol class of a vocabulary index: 0 (the reference's unknown) decodes to carbon, img2smiles2.py:24-25; -1 = no symbol
-__device__ inline int symbol_class(int t) { return t < 0 || t > 13 ? -1 : (t == 0 ? 1 : t); }
 
 __global__ __launch_bounds__(GT) void graph_score_kernel(const abc_graph_score_desc d) {
     __shared__ int2 ppos[MAX_ATOMS];     // molecule atoms (x, y)
@@ -39,34 +36,21 @@ __global__ __launch_bounds__(GT) void graph_score_kernel(const abc_graph_score_d
     __shared__ int rkey[MAX_REC];        // record bond: lower end << 10 | higher end, -1 for a row that names no pair
     __shared__ int acc[NCOL];
     const int b = blockIdx.x, tid = threadIdx.x;
-    int* row = d.rows + (size_t)b * NCOL;
-    const int nv = d.n_valid != nullptr ? clampi(*d.n_valid, 0, d.B) : d.B;
-    if (b >= nv) {
-        if (tid < NCOL) row[tid] = 0;
-        return;
-    }
-    const int nt = clampi(d.rec_counts[b], 0, d.max_atoms), m = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
-    const int* mc = d.mol_counts + (size_t)b * 4;
-    const int status = mc[3];
-    const bool empty = (status & ABC_MOL_EMPTY) != 0;
-    const int na = empty ? 0 : clampi(mc[0], 0, d.cap_atoms), nb = empty ? 0 : clampi(mc[1], 0, d.cap_mol_bonds);
-    const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * 5;
-    const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * 4;
-    const int* ra = d.rec_atoms + (size_t)b * d.max_atoms * 4;
-    const int* rb = d.rec_bonds + (size_t)b * d.max_bonds * 3;
+    ScoredImage im;
+    if (!scored_image<NCOL>(d, b, tid, im)) return;
+    const auto [nt, m, status, na, nb, empty, pa, pb, ra, rb] = im;
 
     // ---- (A)
     if (tid < NCOL) acc[tid] = 0;
     for (int a = tid; a < nt; a += GT) {
-        tpos[a] = make_int2(ra[a * 4], ra[a * 4 + 1]);
+        tpos[a] = make_int2(ra[a * REC_ATOM_W], ra[a * REC_ATOM_W + 1]);
         in_t[a] = 0;
     }
-    for (int p = tid; p < na; p += GT) ppos[p] = make_int2(pa[p * 5], pa[p * 5 + 1]);
+    for (int p = tid; p < na; p += GT) ppos[p] = make_int2(pa[p * ATOM_W], pa[p * ATOM_W + 1]);
     __syncthreads();
     for (int k = tid; k < m; k += GT) {
-        const int i = rb[k * 3], j = rb[k * 3 + 1];
-        int key = -1;
-        if (i >= 0 && j >= 0 && i < nt && j < nt && i != j) {
+        int i, j, key = -1;
+        if (rec_ends(rb, k, nt, i, j)) {
             key = (min(i, j) << 10) | max(i, j);
             atomicOr(in_t + i, 1);
             atomicOr(in_t + j, 1);
@@ -112,21 +96,21 @@ __global__ __launch_bounds__(GT) void graph_score_kernel(const abc_graph_score_d
         const int p = near_p[a];
         if (p < 0 || near_t[p] != a) continue;
         ++located;
-        const int want = symbol_class(ra[a * 4 + 2]), got = symbol_class(pa[p * 5 + 2]);
-        if (want >= 0 && want == got && ra[a * 4 + 3] == pa[p * 5 + 3]) ++matched;
+        const int want = symbol_class(ra[a * REC_ATOM_W + 2]), got = symbol_class(pa[p * ATOM_W + 2]);
+        if (want >= 0 && want == got && ra[a * REC_ATOM_W + 3] == pa[p * ATOM_W + 3]) ++matched;
     }
     // ---- (D) paired and matched bonds
     int paired = 0, bmatched = 0;
     for (int q = tid; q < nb; q += GT) {
-        const int e1 = pb[q * 4] - 1, e2 = pb[q * 4 + 1] - 1;
-        if (e1 < 0 || e2 < 0 || e1 >= na || e2 >= na || e1 == e2) continue;
+        int e1, e2;
+        if (!mol_ends(pb, q, na, e1, e2)) continue;
         const int a1 = near_t[e1], a2 = near_t[e2];
         if (a1 < 0 || a2 < 0 || near_p[a1] != e1 || near_p[a2] != e2) continue;
         const int key = (min(a1, a2) << 10) | max(a1, a2);
         for (int k = 0; k < m; ++k) {
             if (rkey[k] != key) continue;
             ++paired;
-            if (rb[k * 3 + 2] == pb[q * 4 + 2]) ++bmatched;
+            if (rb[k * REC_BOND_W + 2] == pb[q * MOL_BOND_W + 2]) ++bmatched;
             break;
         }
     }
@@ -159,11 +143,7 @@ __global__ __launch_bounds__(GT) void graph_score_kernel(const abc_graph_score_d
             r[ABC_GS_BONDS_EQUAL] = r[ABC_GS_BONDS_MATCHED] == m && m == nb;
             r[ABC_GS_EXACT] = r[ABC_GS_ATOMS_EQUAL] && r[ABC_GS_BONDS_EQUAL];
         }
-#pragma unroll
-        for (int i = 0; i < NCOL; ++i) {
-            row[i] = r[i];
-            if (r[i] != 0) atomicAdd((unsigned long long*)&d.totals[i], (unsigned long long)r[i]);
-        }
+        write_row_and_totals<NCOL>(d.rows + (size_t)b * NCOL, d.totals, r);
     }
 }
 

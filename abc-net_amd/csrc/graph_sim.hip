@@ -23,21 +23,20 @@
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
 #include "block_scan.hpp"
+#include "mol_rows.hpp"
 
 namespace {
 
 typedef unsigned long long u64;
 
 constexpr int GT = 256;              // threads per workgroup
-constexpr int MAX_ATOMS = 512;       // cap_atoms, max_atoms <= 512: ids, sums and four fingerprint layers of both sides in 48 KB of LDS
+constexpr int MAX_ATOMS = ABC_MAX_SIM_ATOMS;      // ids, sums and four fingerprint layers of both sides in 48 KB of LDS
 constexpr int RADIUS = 3;            // fingerprint layers 0 .. 3
 constexpr int MAX_ROUNDS = 64;       // refinement rounds of refine_equal
 constexpr int FP = (RADIUS + 1) * MAX_ATOMS;
 constexpr int NCOL = ABC_SIM_NCOL;
 static_assert(FP == ABC_SIM_IDS, "ids_out holds one fingerprint per side");
 static_assert(MAX_ATOMS == 2 * GT, "the record scan numbers two atoms per thread");
-
-__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // the splitmix64 finaliser
 __device__ inline u64 mix(u64 x) {
@@ -47,24 +46,9 @@ __device__ inline u64 mix(u64 x) {
     return x;
 }
 
-// the class of a vocabulary index: 0 (the reference's unknown) decodes to carbon, img2smiles2.py:24-25; anything outside the
-// vocabulary (a record's -1) is class 0, which equals only itself
-__device__ inline int atom_class(int t) { return t < 0 || t > 13 ? 0 : (t == 0 ? 1 : t); }
 // a wedge is a single bond (generate_smiles.py:58-68)
 __device__ inline int bond_class(int c) { return c == 5 || c == 6 ? 1 : (c >= 1 && c <= 4 ? c : 0); }
 __device__ inline u64 id0(int cls, int charge, u64 degree) { return mix(mix(mix((u64)(cls + 1)) + (u64)(long long)charge) + degree); }
-
-// the ends of molecule row q / record row k as atom indices of their side, false for a row that names no pair
-__device__ inline bool mol_ends(const int* pb, int q, int na, int& e1, int& e2) {
-    const int r1 = pb[q * 4], r2 = pb[q * 4 + 1];      // 1-based
-    if (r1 < 1 || r2 < 1 || r1 > na || r2 > na || r1 == r2) return false;
-    e1 = r1 - 1, e2 = r2 - 1;
-    return true;
-}
-__device__ inline bool rec_ends(const int* rb, int k, int nt, int& i, int& j) {
-    i = rb[k * 3], j = rb[k * 3 + 1];
-    return i >= 0 && j >= 0 && i < nt && j < nt && i != j;
-}
 
 // this thread's share of the size of the multiset intersection of A and B (LDS lists; every read of the inner loops is a broadcast)
 __device__ inline int common_share(const u64* A, int nA, const u64* Bv, int nB, int tid) {
@@ -87,26 +71,14 @@ __global__ __launch_bounds__(GT) void graph_sim_kernel(const abc_graph_similarit
     __shared__ unsigned wt[GT / 64 + 1];
     __shared__ int cnt[4];               // valid molecule bonds, valid record bonds, envs_common, common id_T
     const int b = blockIdx.x, tid = threadIdx.x;
-    int* row = d.rows + (size_t)b * NCOL;
-    const int nv = d.n_valid != nullptr ? clampi(*d.n_valid, 0, d.B) : d.B;
-    if (b >= nv) {
-        if (tid < NCOL) row[tid] = 0;
-        return;
-    }
-    const int nt = clampi(d.rec_counts[b], 0, d.max_atoms), m = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
-    const int* mc = d.mol_counts + (size_t)b * 4;
-    const int status = mc[3];
-    const bool empty = (status & ABC_MOL_EMPTY) != 0;
-    const int na = empty ? 0 : clampi(mc[0], 0, d.cap_atoms), nb = empty ? 0 : clampi(mc[1], 0, d.cap_mol_bonds);
-    const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * 5;
-    const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * 4;
-    const int* ra = d.rec_atoms + (size_t)b * d.max_atoms * 4;
-    const int* rb = d.rec_bonds + (size_t)b * d.max_bonds * 3;
+    ScoredImage im;
+    if (!scored_image<NCOL>(d, b, tid, im)) return;
+    const auto [nt, m, status, na, nb, empty, pa, pb, ra, rb] = im;
 
     // row `tid` of each side, kept through every round (tens of bonds per drawing: most launches read no bond row twice)
     int pi = 0, pj = 0, ti = 0, tj = 0;
     const bool pv = tid < nb && mol_ends(pb, tid, na, pi, pj), tv = tid < m && rec_ends(rb, tid, nt, ti, tj);
-    const u64 po = pv ? (u64)bond_class(pb[tid * 4 + 2]) : 0, to = tv ? (u64)bond_class(rb[tid * 3 + 2]) : 0;
+    const u64 po = pv ? (u64)bond_class(pb[tid * MOL_BOND_W + 2]) : 0, to = tv ? (u64)bond_class(rb[tid * REC_BOND_W + 2]) : 0;
 
     // ---- (A) degrees, T, id_0
     if (tid < 4) cnt[tid] = 0;
@@ -146,14 +118,14 @@ __global__ __launch_bounds__(GT) void graph_sim_kernel(const abc_graph_similarit
     const unsigned r0 = block_excl_scan<GT>(f0 + f1, wt, &total), r1 = r0 + f0;
     const int n_t = (int)total;          // |T|
     for (int a = tid; a < na; a += GT) {
-        const u64 id = id0(atom_class(pa[a * 5 + 2]), pa[a * 5 + 3], acc[0][a]);
+        const u64 id = id0(atom_class(pa[a * ATOM_W + 2]), pa[a * ATOM_W + 3], acc[0][a]);
         cur[0][a] = fp[0][a] = id;
         acc[0][a] = 0;
     }
     remap[a0] = f0 ? (int)r0 : -1;
     remap[a1] = f1 ? (int)r1 : -1;
-    if (f0) cur[1][r0] = fp[1][r0] = id0(atom_class(ra[a0 * 4 + 2]), ra[a0 * 4 + 3], deg0);
-    if (f1) cur[1][r1] = fp[1][r1] = id0(atom_class(ra[a1 * 4 + 2]), ra[a1 * 4 + 3], deg1);
+    if (f0) cur[1][r0] = fp[1][r0] = id0(atom_class(ra[a0 * REC_ATOM_W + 2]), ra[a0 * REC_ATOM_W + 3], deg0);
+    if (f1) cur[1][r1] = fp[1][r1] = id0(atom_class(ra[a1 * REC_ATOM_W + 2]), ra[a1 * REC_ATOM_W + 3], deg1);
     acc[1][a0] = acc[1][a1] = 0;         // (every degree was read before the scan's barriers)
     __syncthreads();
     if (tv) ti = remap[ti], tj = remap[tj];      // (both in T: this row is one of those that put them there)
@@ -175,13 +147,13 @@ __global__ __launch_bounds__(GT) void graph_sim_kernel(const abc_graph_similarit
         }
         for (int q = tid + GT; q < nb; q += GT) {
             if (!mol_ends(pb, q, na, i, j)) continue;
-            const u64 o = (u64)bond_class(pb[q * 4 + 2]);
+            const u64 o = (u64)bond_class(pb[q * MOL_BOND_W + 2]);
             atomicAdd(&acc[0][i], mix(mix(cur[0][j]) + o));
             atomicAdd(&acc[0][j], mix(mix(cur[0][i]) + o));
         }
         for (int k = tid + GT; k < m; k += GT) {
             if (!rec_ends(rb, k, nt, i, j)) continue;
-            const u64 o = (u64)bond_class(rb[k * 3 + 2]);
+            const u64 o = (u64)bond_class(rb[k * REC_BOND_W + 2]);
             i = remap[i], j = remap[j];
             atomicAdd(&acc[1][i], mix(mix(cur[1][j]) + o));
             atomicAdd(&acc[1][j], mix(mix(cur[1][i]) + o));
@@ -242,11 +214,7 @@ __global__ __launch_bounds__(GT) void graph_sim_kernel(const abc_graph_similarit
             r[ABC_SIM_ENVS_COMMON] = common;
             r[ABC_SIM_DICE_Q20] = envs_p + envs_t ? (int)((((u64)common * 2) << 20) / (u64)(envs_p + envs_t)) : 0;
         }
-#pragma unroll
-        for (int i = 0; i < NCOL; ++i) {
-            row[i] = r[i];
-            if (r[i] != 0) atomicAdd((u64*)&d.totals[i], (u64)r[i]);
-        }
+        write_row_and_totals<NCOL>(d.rows + (size_t)b * NCOL, d.totals, r);
     }
 }
 

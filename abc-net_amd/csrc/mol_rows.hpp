@@ -1,0 +1,64 @@
+// The rows the decoder's stages hand to each other (extract -> assemble -> mol block / graph score / graph similarity), for the
+// device side; the host side is abc-net_amd/contract.py, the table of every row and count DESIGN.md section 7.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/abcnet_hip.h"
+
+// int32 words per row: atoms of both layouts, bond candidates, molecule bonds, record atoms, record bonds
+constexpr int ATOM_W = 5, CAND_W = 4, MOL_BOND_W = 4, REC_ATOM_W = 4, REC_BOND_W = 3;
+constexpr int N_SYMBOLS = 14;        // the atom vocabulary of utils.py:12-13: indices 0 .. 13
+
+__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// The class of a vocabulary index: 0 (the reference's unknown) decodes to carbon, img2smiles2.py:24-25.  The two differ ON PURPOSE:
+// in graph_score.hip's an unknown matches nothing (-1), in graph_sim.hip's an unknown equals an unknown (class 0 equals only itself).
+__device__ inline int symbol_class(int t) { return t < 0 || t >= N_SYMBOLS ? -1 : (t == 0 ? 1 : t); }
+__device__ inline int atom_class(int t) { return t < 0 || t >= N_SYMBOLS ? 0 : (t == 0 ? 1 : t); }
+
+// the ends of molecule row q / record row k as atom indices of their side, false for a row that names no pair
+__device__ inline bool mol_ends(const int* pb, int q, int na, int& e1, int& e2) {
+    const int r1 = pb[q * MOL_BOND_W], r2 = pb[q * MOL_BOND_W + 1];      // 1-based
+    if (r1 < 1 || r2 < 1 || r1 > na || r2 > na || r1 == r2) return false;
+    e1 = r1 - 1, e2 = r2 - 1;
+    return true;
+}
+__device__ inline bool rec_ends(const int* rb, int k, int nt, int& i, int& j) {
+    i = rb[k * REC_BOND_W], j = rb[k * REC_BOND_W + 1];
+    return i >= 0 && j >= 0 && i < nt && j < nt && i != j;
+}
+
+// image b of a scoring kernel (both descriptors name these fields alike): counts clamped to their capacities, no rows when EMPTY
+struct ScoredImage {
+    int nt, m, status, na, nb;         // record atoms and bonds, abc_mol_status bits, molecule atoms and bonds
+    bool empty;
+    const int *pa, *pb, *ra, *rb;      // mol_atoms, mol_bonds, rec_atoms, rec_bonds of the image
+};
+// false for an image at or past n_valid: its row is zeroed and the workgroup has nothing more to do (uniform)
+template <int NCOL, class Desc>
+__device__ inline bool scored_image(const Desc& d, int b, int tid, ScoredImage& s) {
+    const int nv = d.n_valid != nullptr ? clampi(*d.n_valid, 0, d.B) : d.B;
+    if (b >= nv) {
+        if (tid < NCOL) d.rows[(size_t)b * NCOL + tid] = 0;
+        return false;
+    }
+    s.nt = clampi(d.rec_counts[b], 0, d.max_atoms), s.m = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
+    const int* mc = d.mol_counts + (size_t)b * 4;
+    s.status = mc[3];
+    s.empty = (s.status & ABC_MOL_EMPTY) != 0;
+    s.na = s.empty ? 0 : clampi(mc[0], 0, d.cap_atoms), s.nb = s.empty ? 0 : clampi(mc[1], 0, d.cap_mol_bonds);
+    s.pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
+    s.pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
+    s.ra = d.rec_atoms + (size_t)b * d.max_atoms * REC_ATOM_W;
+    s.rb = d.rec_bonds + (size_t)b * d.max_bonds * REC_BOND_W;
+    return true;
+}
+
+// the end of a scoring kernel, one lane: the row of the image, its non-zero columns added to the totals (64-bit atomicAdd)
+template <int NCOL>
+__device__ inline void write_row_and_totals(int* row, uint64_t* totals, const int (&r)[NCOL]) {
+#pragma unroll
+    for (int i = 0; i < NCOL; ++i) {
+        row[i] = r[i];
+        if (r[i] != 0) atomicAdd((unsigned long long*)&totals[i], (unsigned long long)r[i]);
+    }
+}

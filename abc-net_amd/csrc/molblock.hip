@@ -24,6 +24,7 @@
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
 #include "block_scan.hpp"
+#include "mol_rows.hpp"
 
 namespace {
 
@@ -31,7 +32,6 @@ typedef unsigned long long u64;
 
 constexpr int MT = 256;                  // threads per workgroup
 constexpr int MAX_POS = 199999;          // positions 0 .. 199999: |px - 60| * 500 * 2 + 3 stays far inside int32
-constexpr int N_SYMBOLS = 14;
 
 // utils.py:12-13 inverted, index 0 decoded as carbon (decode.ATOM_SYMBOLS), each padded to the 4 columns of the atom line
 __device__ const char SYMBOLS[N_SYMBOLS * 4 + 1] = "C   C   N   O   P   F   Cl  S   Br  B   Se  I   H   Si  ";
@@ -54,8 +54,6 @@ __device__ const char SYMBOLS[N_SYMBOLS * 4 + 1] = "C   C   N   O   P   F   Cl  
 #define SED_HEAD "M  SED   "
 #define SED_TAIL " IMPL_H1\n"
 #define END_TEXT "M  END\n$$$$"
-
-__device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // decimal digits of u
 __device__ inline int ndig(unsigned u) {
@@ -215,20 +213,20 @@ __global__ __launch_bounds__(MT) void molblock_size_kernel(const abc_molblock_de
         if (tid == 0) d.work[b] = 0;
         return;
     }
-    const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * 5;
-    const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * 4;
+    const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
+    const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
     const int* ph = d.mol_implh + (size_t)b * d.cap_atoms;
     if (tid < 2) flags[tid] = 0;
     __syncthreads();
     unsigned len = 0;
     int charged = 0, bad = 0;
     for (int i = tid; i < c.na; i += MT) {
-        const int* a = pa + i * 5;
+        const int* a = pa + i * ATOM_W;
         bad |= !atom_ok(a);
         len += atom_len(a) + chg_len(i, a[3]);
         charged += a[3] != 0;
     }
-    for (int q = tid; q < c.nb; q += MT) len += bond_len(pb + q * 4);
+    for (int q = tid; q < c.nb; q += MT) len += bond_len(pb + q * MOL_BOND_W);
     for (int k = tid; k < c.nh; k += MT) len += implh_len(k, ph[k]);
     if (charged) atomicAdd(&flags[0], charged);
     if (bad) atomicOr(&flags[1], 1);
@@ -314,8 +312,8 @@ __global__ __launch_bounds__(MT) void molblock_write_kernel(const abc_molblock_d
     o.text = d.text;
     o.end = (int64_t)through[1];
     int64_t pos = (int64_t)through[0];
-    const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * 5;
-    const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * 4;
+    const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
+    const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
     const int* ph = d.mol_implh + (size_t)b * d.cap_atoms;
     unsigned total;
 
@@ -333,7 +331,7 @@ __global__ __launch_bounds__(MT) void molblock_write_kernel(const abc_molblock_d
     unsigned len = 0, chg = 0;
     int charged = 0;
     for (int i = lo; i < hi; ++i) {
-        const int* a = pa + i * 5;
+        const int* a = pa + i * ATOM_W;
         len += atom_len(a);
         chg += chg_len(i, a[3]);
         charged += a[3] != 0;
@@ -341,7 +339,7 @@ __global__ __launch_bounds__(MT) void molblock_write_kernel(const abc_molblock_d
     if (charged) atomicAdd(&charged_all, charged);
     {
         int64_t p = pos + block_excl_scan<MT>(len, wt, &total);
-        for (int i = lo; i < hi; ++i) p = put_atom(o, p, pa + i * 5);
+        for (int i = lo; i < hi; ++i) p = put_atom(o, p, pa + i * ATOM_W);
     }
     pos += total;
 
@@ -350,9 +348,9 @@ __global__ __launch_bounds__(MT) void molblock_write_kernel(const abc_molblock_d
         int blo, bhi;
         my_range(c.nb, tid, blo, bhi);
         len = 0;
-        for (int q = blo; q < bhi; ++q) len += bond_len(pb + q * 4);
+        for (int q = blo; q < bhi; ++q) len += bond_len(pb + q * MOL_BOND_W);
         int64_t p = pos + block_excl_scan<MT>(len, wt, &total);
-        for (int q = blo; q < bhi; ++q) p = put_bond(o, p, pb + q * 4);
+        for (int q = blo; q < bhi; ++q) p = put_bond(o, p, pb + q * MOL_BOND_W);
         pos += total;
     }
 
@@ -362,7 +360,7 @@ __global__ __launch_bounds__(MT) void molblock_write_kernel(const abc_molblock_d
         if (tid == 0) put_int(o, put_lit(o, pos, CHG_HEAD), n_chg, 3);
         pos += LIT_LEN(CHG_HEAD) + int_len(n_chg, 3);
         int64_t p = pos + block_excl_scan<MT>(chg, wt, &total);
-        for (int i = lo; i < hi; ++i) p = put_chg(o, p, i, pa[i * 5 + 3]);
+        for (int i = lo; i < hi; ++i) p = put_chg(o, p, i, pa[i * ATOM_W + 3]);
         pos += total;
         if (tid == 0) o.put(pos, '\n');
         pos += 1;

@@ -24,7 +24,12 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .contract import HEADS, alloc_targets, check_sparse_rasterizer, current_stream, refuse_dense_targets, resolve_device
+from .contract import HEADS, GraphRecords, alloc_targets, check_sparse_rasterizer, current_stream, refuse_dense_targets, resolve_device
+
+
+# the optional stages behind the NMS in launch order, each under the constructor flag that builds it
+STAGES = {"extractor": "extract", "assembler": "assemble", "texter": "molblocks", "scorer": "score_graphs",
+          "similarity": "score_similarity", "evaluator": "evaluate"}
 
 
 class InferenceRunner:
@@ -60,29 +65,26 @@ class InferenceRunner:
         first .n_valid images; evaluation()["molecules"] holds the running result
         score_similarity (needs assemble=True and evaluate=True): the environment similarity of the assembled molecules to the same
         graph records (ops.GraphSimilarity: the graded, position-free stand-in for cal_acc.py's fingerprint similarity), in the same
-        captured graph after the assembler; with score_graphs=True it reads the records the scorer staged, without it load_graphs
-        fills its own; evaluation()["similarity"] holds the running result
+        captured graph after the assembler; both scores read the runner's one contract.GraphRecords (.records), which load_graphs
+        fills; evaluation()["similarity"] holds the running result
         molblocks (needs assemble=True): the mol block text of the assembled molecules (ops.MolBlockWriter), written in the same
         captured graph right after the assembler; molblocks() returns the strings that go into Chem.MolFromMolBlock -- two small
         copies per batch instead of molecules() and Molecule.molblock() per image on the host
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
-        from .ops import OMEGA_RULES
+        from .ops import OMEGA_RULES, GraphAssembler, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, check_nms_heads
         if omega_rule not in OMEGA_RULES:
             raise ValueError("InferenceRunner: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
         self.omega_rule = omega_rule
-        if score_graphs and not (assemble and evaluate):
-            raise ValueError("InferenceRunner(score_graphs=True) scores the assembled molecules of an evaluating step: it needs "
-                             "assemble=True and evaluate=True")
-        if score_similarity and not (assemble and evaluate):
-            raise ValueError("InferenceRunner(score_similarity=True) scores the assembled molecules of an evaluating step: it needs "
-                             "assemble=True and evaluate=True")
+        for flag, on in (("score_graphs", score_graphs), ("score_similarity", score_similarity)):
+            if on and not (assemble and evaluate):
+                raise ValueError("InferenceRunner(%s=True) scores the assembled molecules of an evaluating step: it needs "
+                                 "assemble=True and evaluate=True" % flag)
         if molblocks and not assemble:
             raise ValueError("InferenceRunner(molblocks=True) writes the text of the assembled molecules of the step: it needs "
                              "assemble=True")
         extract = bool(extract) or bool(assemble)
-        from .ops import check_nms_heads
         check_nms_heads(model.heads, "InferenceRunner")
         if extract and tuple(model.heads) != HEADS:
             raise ValueError("InferenceRunner(extract=True): the peak extractor reads heads %s, got heads %s" % (list(HEADS), list(model.heads)))
@@ -122,24 +124,16 @@ class InferenceRunner:
         d.rho_abs, d.omega_mask = self.rho_abs.data_ptr(), self.omega_mask.data_ptr()
         self._nms = d
         # img2smiles2.py:113-191: compact candidate lists for the CPU graph-assembly stage, inside the same graph
-        self.extractor = None
-        if extract:
-            from .ops import PeakExtractor
-            self.extractor = PeakExtractor(lg, self.atom_mask, self.bond_mask, cap_atoms=cap_atoms, cap_bonds=cap_bonds,
-                                           btype_idx=self.btype_idx if self.decode else None, rho_abs=self.rho_abs if self.decode else None,
-                                           omega_rule=omega_rule)
-        self.assembler = None
-        if assemble:
-            from .ops import GraphAssembler
-            with torch.cuda.device(dev):
+        self.extractor = self.assembler = self.texter = self.evaluator = self._rasterizer = None
+        with torch.cuda.device(dev):
+            if extract:
+                self.extractor = PeakExtractor(lg, self.atom_mask, self.bond_mask, cap_atoms=cap_atoms, cap_bonds=cap_bonds,
+                                               btype_idx=self.btype_idx if self.decode else None, rho_abs=self.rho_abs if self.decode else None,
+                                               omega_rule=omega_rule)
+            if assemble:
                 self.assembler = GraphAssembler.from_extractor(self.extractor, cap_mol_bonds=cap_mol_bonds)
-        self.texter = None
-        if molblocks:
-            from .ops import MolBlockWriter
-            with torch.cuda.device(dev):
+            if molblocks:
                 self.texter = MolBlockWriter.from_assembler(self.assembler)
-        self.evaluator = None
-        self._rasterizer = None
         if evaluate:
             if tuple(model.heads) != HEADS:
                 raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (list(HEADS), list(model.heads)))
@@ -147,16 +141,16 @@ class InferenceRunner:
                 self.eval_targets = alloc_targets(eng.B, eng.h, eng.w, dev)
                 self.n_valid = torch.full((1,), eng.B, dtype=torch.int32, device=dev)
             self._build_evaluator(None)
-        self.scorer = None
-        if score_graphs:
-            from .ops import GraphScore
+        self.records = self.scorer = self.similarity = None
+        self.wants_graph_records = bool(score_graphs or score_similarity)      # (one set, staged once per batch, whichever score reads it)
+        if self.wants_graph_records:
             with torch.cuda.device(dev):
-                self.scorer = GraphScore.from_assembler(self.assembler, radius=score_radius, n_valid=self.n_valid)
-        self.similarity = None
-        if score_similarity:
-            from .ops import GraphSimilarity
-            with torch.cuda.device(dev):
-                self.similarity = GraphSimilarity.from_assembler(self.assembler, n_valid=self.n_valid, records=self.scorer)
+                self.records = GraphRecords(eng.B, 256, 256, dev)
+                if score_graphs:
+                    self.scorer = GraphScore.from_assembler(self.assembler, radius=score_radius, n_valid=self.n_valid, records=self.records)
+                if score_similarity:
+                    self.similarity = GraphSimilarity.from_assembler(self.assembler, n_valid=self.n_valid, records=self.records)
+        self._stages = [attr for attr in STAGES if getattr(self, attr) is not None]
         self.use_graph = use_graph
         self._graph = None
         self.steps = 0
@@ -167,6 +161,12 @@ class InferenceRunner:
         parameters alone; call again after load_state_dict)"""
         with torch.cuda.device(self.dev):
             self.eng.run_pack(current_stream())
+
+    def _need(self, attr):
+        op = getattr(self, attr)
+        if op is None:
+            raise L.AbcNetHipError("InferenceRunner was built without %s=True" % STAGES[attr])
+        return op
 
     def _build_evaluator(self, target_flags):
         from .ops import EvalTables
@@ -183,8 +183,7 @@ class InferenceRunner:
     @property
     def targets(self):
         """evaluate=True: .eval_targets under the name augment.SampleBuilder and raster.TargetRasterizer(targets=...) callers use"""
-        if self.evaluator is None:
-            raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
+        self._need("evaluator")
         return self.eval_targets
 
     def use_sparse_targets(self, rasterizer):
@@ -192,8 +191,7 @@ class InferenceRunner:
         of the 32-pixel groups the rasteriser drew into (abc_eval_tables_update_sparse), and the batch's targets come from
         `rasterizer.load(records); rasterizer.run()` in front of step() instead of a dense copy; None: back to reading every plane.
         The tables and meters are unchanged bit for bit."""
-        if self.evaluator is None:
-            raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
+        self._need("evaluator")
         if rasterizer is None:
             self._build_evaluator(None)
             self._rasterizer = None
@@ -210,8 +208,7 @@ class InferenceRunner:
         n_valid only."""
         self.eng.img.copy_(imgs.reshape(self.eng.img.shape), non_blocking=True)
         if targets is not None or n_valid is not None:
-            if self.evaluator is None:
-                raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
+            self._need("evaluator")
             if targets is not None:
                 refuse_dense_targets(self._rasterizer)
                 for dst, t in zip(self.eval_targets, targets):
@@ -243,74 +240,51 @@ class InferenceRunner:
     def _run(self, st):
         self.eng.run_forward(st)
         L.check(self.eng.lib.abc_nms_peaks(C.byref(self._nms), st), "nms_peaks")
-        if self.extractor is not None:
-            self.extractor.run(st)
-        if self.assembler is not None:
-            self.assembler.run(st)
-        if self.texter is not None:
-            self.texter.run(st)
-        if self.scorer is not None:
-            self.scorer.run(st)
-        if self.similarity is not None:
-            self.similarity.run(st)
-        if self.evaluator is not None:
-            self.evaluator.run(st)
+        for attr in self._stages:
+            getattr(self, attr).run(st)
 
     def evaluation(self):
         """the tables and meters accumulated since the last reset_evaluation() (ops.EvalTables.result(); host sync; needs evaluate=True)"""
-        if self.evaluator is None:
-            raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
-        out = self.evaluator.result()
-        if self.scorer is not None:
-            out["molecules"] = self.scorer.result()
-        if self.similarity is not None:
-            out["similarity"] = self.similarity.result()
+        out = self._need("evaluator").result()
+        for attr, key in (("scorer", "molecules"), ("similarity", "similarity")):
+            if attr in self._stages:
+                out[key] = getattr(self, attr).result()
         return out
 
     def reset_evaluation(self):
-        if self.evaluator is None:
-            raise L.AbcNetHipError("InferenceRunner was built without evaluate=True")
-        self.evaluator.reset()
-        if self.scorer is not None:
-            self.scorer.reset()
-        if self.similarity is not None:
-            self.similarity.reset()
+        self._need("evaluator")
+        for attr in ("evaluator", "scorer", "similarity"):
+            if attr in self._stages:
+                getattr(self, attr).reset()
 
     def load_graphs(self, records):
         """score_graphs=True or score_similarity=True: the graph records (raster.parse_graph) of the batch, n <= batch of them (the
         rows past n get an empty record; n_valid says how many images count); staged once, whichever of the two read them"""
-        op = self.scorer if self.scorer is not None else self.similarity
-        if op is None:
-            raise L.AbcNetHipError("InferenceRunner was built without score_graphs=True")
+        if self.records is None:
+            self._need("scorer")
         with torch.cuda.device(self.dev):
-            op.load(records)
+            self.records.load(records)
 
     def candidates(self):
         """the per-image atom / bond candidate lists of the last step (host sync; needs extract=True)"""
-        if self.extractor is None:
-            raise L.AbcNetHipError("InferenceRunner was built without extract=True")
-        return self.extractor.lists()
+        return self._need("extractor").lists()
 
     def molecules(self):
         """the assembled molecule (decode.Molecule) of every image of the last step, None where the reference finds no key point
         (host sync; needs assemble=True); `Chem.MolFromMolBlock(m.molblock())` is the reference's next call"""
-        if self.assembler is None:
-            raise L.AbcNetHipError("InferenceRunner was built without assemble=True")
-        return self.assembler.molecules()
+        return self._need("assembler").molecules()
 
     def molblocks(self):
         """the mol block (str) of every image of the last step, written on the device: what `m.molblock()` gives for the m of
         molecules(), None where that is None (host sync; needs molblocks=True)"""
-        if self.texter is None:
-            raise L.AbcNetHipError("InferenceRunner was built without molblocks=True")
+        texter = self._need("texter")
         with torch.cuda.device(self.dev):
-            return self.texter.molblocks()
+            return texter.molblocks()
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""
-        for op in (self.scorer, self.similarity):
-            if op is not None and not op.loaded:
-                raise L.AbcNetHipError("InferenceRunner(score_graphs=True): no graph records were loaded (load_graphs, or SampleBuilder.load)")
+        if self.records is not None and not self.records.loaded:
+            raise L.AbcNetHipError("InferenceRunner(score_graphs=True): no graph records were loaded (load_graphs, or SampleBuilder.load)")
         with torch.cuda.device(self.dev):
             self._step()
 

@@ -9,8 +9,8 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .contract import (HEAD_NAMES, HEADS, PinnedStaging, check_head_maps, check_targets, current_stream, require_device_tensor,
-                       set_target_ptrs, stream_or_current)
+from .contract import (HEAD_NAMES, HEADS, CandidateLists, GraphRecords, MoleculeRows, check_head_maps, check_targets, current_stream,
+                       require_device_tensor, set_target_ptrs, stream_or_current)
 
 EXTRACT_HEADS = HEADS      # the head widths extract.hip reads (train.py:47)
 
@@ -385,6 +385,7 @@ class PeakExtractor:
         d.work, d.work_masks = self.work.data_ptr(), self.work_masks.data_ptr()
         self.d, self.keep = d, (list(logits), atom_mask, bond_mask, btype_idx, rho_abs)
         self.B, self.cap_atoms, self.cap_bonds = B, cap_atoms, cap_bonds
+        self.candidates = CandidateLists(self.counts, self.atoms, self.bonds, self.bond_rho)
 
     def run(self, stream=None):
         L.check(self.lib.abc_extract_peaks(C.byref(self.d), stream_or_current(stream)), "extract_peaks")
@@ -398,7 +399,7 @@ class PeakExtractor:
         out = []
         for b in range(self.B):
             a, m = int(cnt[b, 1]), int(cnt[b, 3])
-            trunc = a > self.cap_atoms or m > self.cap_bonds or int(cnt[b, 0]) > self.cap_atoms or int(cnt[b, 2]) > 4096
+            trunc = a > self.cap_atoms or m > self.cap_bonds or int(cnt[b, 0]) > self.cap_atoms or int(cnt[b, 2]) > L.MAX_BOND_PEAKS
             a, m = min(a, self.cap_atoms), min(m, self.cap_bonds)
             out.append({"atoms": atoms[b, :a], "bonds": bonds[b, :m], "rho": rho[b, :m], "counts": cnt[b].tolist(), "truncated": trunc})
         return out
@@ -414,21 +415,13 @@ class GraphAssembler:
     the reference does not define -- bond peaks exist but no candidate survives the bin rule; its np.flip raises on the empty
     array -- gives a molecule with zero atoms and zero bonds here, the same as "no bond survives the edge filter"."""
 
-    def __init__(self, counts, atoms, bonds, bond_rho, cap_mol_bonds=None):
-        """counts int32 [B, 4], atoms int32 [B, cap_atoms, 5], bonds int32 [B, cap_bonds, 4], bond_rho f32 [B, cap_bonds]: device
-        tensors of PeakExtractor's layout (its own buffers, or hand-made lists).  cap_mol_bonds: bonds kept per image (default
-        4 * cap_atoms, at most cap_bonds); more are reported as `truncated`."""
+    def __init__(self, counts, atoms=None, bonds=None, bond_rho=None, cap_mol_bonds=None):
+        """a contract.CandidateLists (PeakExtractor.candidates), or its four device tensors (hand-made lists).  cap_mol_bonds: bonds
+        kept per image (default 4 * cap_atoms, at most cap_bonds); more are reported as `truncated`."""
         from .decode import omega_table
-        for name, t, dt in (("counts", counts, torch.int32), ("atoms", atoms, torch.int32), ("bonds", bonds, torch.int32),
-                            ("bond_rho", bond_rho, torch.float32)):
-            require_device_tensor(t, dt, "GraphAssembler: %s (the extractor's layout)" % name)
-        if atoms.dim() != 3 or atoms.shape[2] != 5 or bonds.dim() != 3 or bonds.shape[2] != 4:
-            raise ValueError("GraphAssembler: atoms must be [B, cap_atoms, 5] and bonds [B, cap_bonds, 4], got %s and %s"
-                             % (tuple(atoms.shape), tuple(bonds.shape)))
-        B, cap_atoms, cap_bonds = atoms.shape[0], atoms.shape[1], bonds.shape[1]
-        if tuple(counts.shape) != (B, 4) or bonds.shape[0] != B or tuple(bond_rho.shape) != (B, cap_bonds):
-            raise ValueError("GraphAssembler: counts must be [%d, 4] and bond_rho [%d, %d], got %s and %s"
-                             % (B, B, cap_bonds, tuple(counts.shape), tuple(bond_rho.shape)))
+        lists = CandidateLists.checked("GraphAssembler", counts, atoms, bonds, bond_rho)
+        counts, atoms, bonds, bond_rho = lists.tensors
+        B, cap_atoms, cap_bonds = lists.B, lists.cap_atoms, lists.cap_bonds
         if cap_mol_bonds is None:
             cap_mol_bonds = min(4 * cap_atoms, cap_bonds)
         lib = L.load()
@@ -448,10 +441,11 @@ class GraphAssembler:
         d.work = self.work.data_ptr()
         self.d, self.keep = d, (counts, atoms, bonds, bond_rho)
         self.B, self.cap_atoms, self.cap_bonds, self.cap_mol_bonds = B, cap_atoms, cap_bonds, cap_mol_bonds
+        self.rows = MoleculeRows(self.mol_counts, self.mol_atoms, self.mol_bonds, self.mol_implh)
 
     @classmethod
     def from_extractor(cls, ex, cap_mol_bonds=None):
-        return cls(ex.counts, ex.atoms, ex.bonds, ex.bond_rho, cap_mol_bonds=cap_mol_bonds)
+        return cls(ex.candidates, cap_mol_bonds=cap_mol_bonds)
 
     def run(self, stream=None):
         L.check(self.lib.abc_assemble_graphs(C.byref(self.d), stream_or_current(stream)), "assemble_graphs")
@@ -481,30 +475,17 @@ class MolBlockWriter:
     STATUS_NAMES = ((L.TEXT_BAD_ROW, "ABC_TEXT_BAD_ROW (a vocabulary index outside 0..13 or a position outside 0..199999)"),
                     (L.TEXT_OVERFLOW, "ABC_TEXT_OVERFLOW (the batch's text does not fit cap_text)"))
 
-    def __init__(self, mol_counts, mol_atoms, mol_bonds, mol_implh, cap_text=None):
-        """mol_counts int32 [B, 4], mol_atoms int32 [B, cap_atoms, 5], mol_bonds int32 [B, cap_mol_bonds, 4], mol_implh int32
-        [B, cap_atoms]: device tensors of GraphAssembler's layout (its own buffers, or hand-made rows).  cap_text: bytes of the
-        text buffer; default B * abc_molblock_text_bytes, the bound of one image with every number at its widest -- 224 867 bytes
-        per image at the runner's default capacities (512 atoms, 2048 bonds), 14.4 MB for a batch of 64; at most 2^31 - 1"""
-        for name, t in (("mol_counts", mol_counts), ("mol_atoms", mol_atoms), ("mol_bonds", mol_bonds), ("mol_implh", mol_implh)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("MolBlockWriter: %s must be a tensor, got %s" % (name, type(t).__name__))
-        if mol_atoms.dim() != 3 or mol_atoms.shape[2] != 5 or mol_bonds.dim() != 3 or mol_bonds.shape[2] != 4:
-            raise ValueError("MolBlockWriter: mol_atoms must be [B, cap_atoms, 5] and mol_bonds [B, cap_mol_bonds, 4], got %s and %s"
-                             % (tuple(mol_atoms.shape), tuple(mol_bonds.shape)))
-        B, cap_atoms, cap_mol_bonds = mol_atoms.shape[0], mol_atoms.shape[1], mol_bonds.shape[1]
-        if tuple(mol_counts.shape) != (B, 4) or mol_bonds.shape[0] != B or tuple(mol_implh.shape) != (B, cap_atoms):
-            raise ValueError("MolBlockWriter: mol_counts must be [%d, 4], mol_bonds [%d, cap_mol_bonds, 4] and mol_implh [%d, %d], got %s, %s "
-                             "and %s" % (B, B, B, cap_atoms, tuple(mol_counts.shape), tuple(mol_bonds.shape), tuple(mol_implh.shape)))
-        if B < 1 or cap_atoms < 1 or cap_mol_bonds < 1:
-            raise ValueError("MolBlockWriter: B, cap_atoms and cap_mol_bonds must be >= 1, got %d, %d, %d" % (B, cap_atoms, cap_mol_bonds))
-        for t in (mol_counts, mol_atoms, mol_bonds, mol_implh):
-            require_device_tensor(t, torch.int32, "MolBlockWriter: mol_counts, mol_atoms, mol_bonds and mol_implh (the assembler's layout)")
+    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, cap_text=None):
+        """a contract.MoleculeRows (GraphAssembler.rows), or its four device tensors (hand-made rows).  cap_text: bytes of the text
+        buffer; default B * abc_molblock_text_bytes, the bound of one image with every number at its widest -- 224 867 bytes per
+        image at the runner's default capacities (512 atoms, 2048 bonds), 14.4 MB for a batch of 64; at most 2^31 - 1"""
+        rows = MoleculeRows.checked("MolBlockWriter", mol_counts, mol_atoms, mol_bonds, mol_implh, need_implh=True)
+        B, cap_atoms, cap_mol_bonds = rows.B, rows.cap_atoms, rows.cap_mol_bonds
         self.lib = L.load()
-        dev = mol_atoms.device
+        dev = rows.device
         d = L.MolBlockDesc()
-        d.mol_counts, d.mol_atoms, d.mol_bonds, d.mol_implh = mol_counts.data_ptr(), mol_atoms.data_ptr(), mol_bonds.data_ptr(), mol_implh.data_ptr()
-        d.B, d.cap_atoms, d.cap_mol_bonds = B, cap_atoms, cap_mol_bonds
+        rows.fill(d)
+        d.mol_implh = rows.tensors[3].data_ptr()
         self.image_bytes = int(self.lib.abc_molblock_text_bytes(C.byref(d)))
         cap_text = B * self.image_bytes if cap_text is None else int(cap_text)
         if not (1 <= cap_text <= 2 ** 31 - 1):
@@ -516,11 +497,11 @@ class MolBlockWriter:
         self.work = torch.zeros(B, dtype=torch.int32, device=dev)
         self.h_index = torch.zeros(2 * B + 1, dtype=torch.int32, pin_memory=True)
         d.text, d.index, d.work, d.cap_text = self.text.data_ptr(), self.index.data_ptr(), self.work.data_ptr(), cap_text
-        self.d, self.keep = d, (mol_counts, mol_atoms, mol_bonds, mol_implh)
+        self.d, self.keep = d, rows.tensors
 
     @classmethod
     def from_assembler(cls, asm, cap_text=None):
-        return cls(asm.mol_counts, asm.mol_atoms, asm.mol_bonds, asm.mol_implh, cap_text=cap_text)
+        return cls(asm.rows, cap_text=cap_text)
 
     def run(self, stream=None):
         L.check(self.lib.abc_write_molblocks(C.byref(self.d), stream_or_current(stream)), "write_molblocks")
@@ -549,116 +530,98 @@ class MolBlockWriter:
         return [None if s & L.MOL_EMPTY else raw[off[b]:off[b + 1]].decode("ascii") for b, s in enumerate(status)]
 
 
-def stage_graph_records(op, graphs):
-    """GraphScore.load / GraphSimilarity.load: the records into op's pinned staging (op.B, .max_atoms, .max_bonds, .staging, .h_*)"""
-    import numpy as np
-    if len(graphs) > op.B:
-        raise ValueError("expected at most %d graph records, got %d" % (op.B, len(graphs)))
-    recs = []
-    for b, (a, q) in enumerate(graphs):
-        a, q = np.asarray(a), np.asarray(q)
-        if a.ndim != 2 or a.shape[1] != 4 or q.ndim != 2 or q.shape[1] != 3:
-            raise ValueError("record %d: atoms must be [n, 4] and bonds [m, 3], got %s and %s" % (b, a.shape, q.shape))
-        if len(a) > op.max_atoms or len(q) > op.max_bonds:
-            raise ValueError("record %d has %d atoms / %d bonds (capacity %d / %d)" % (b, len(a), len(q), op.max_atoms, op.max_bonds))
-        if len(q) and not ((0 <= q[:, 0]) & (q[:, 0] < q[:, 1]) & (q[:, 1] < len(a))).all():
-            raise ValueError("record %d: every bond must name atoms 0 <= i < j < %d" % (b, len(a)))
-        recs.append((np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(q, dtype=np.int32)))
-    op.staging.wait()
-    op.h_cnt.zero_()
-    for b, (a, q) in enumerate(recs):
-        op.h_cnt[0, b], op.h_cnt[1, b] = len(a), len(q)
-        if len(a):
-            op.h_atoms[b, :len(a)] = torch.from_numpy(a)
-        if len(q):
-            op.h_bonds[b, :len(q)] = torch.from_numpy(q)
-    op.staging.commit()
-    op.loaded = True
+class _RecordScorer:
+    """What GraphScore and GraphSimilarity share: molecule rows against graph records, one launch per call; the COLUMNS of every image
+    of the last call in .rows (int32), their running sums in .totals.  MAX_RECORD: the largest max_atoms and max_bonds (None: any)."""
+
+    def _bind(self, d, mol, n_valid, records, max_atoms, max_bonds):
+        """check what both take and fill the descriptor fields both have (records: made here when None, else theirs the capacities)"""
+        who = type(self).__name__
+        if records is not None:
+            if not isinstance(records, GraphRecords):
+                raise ValueError("%s: records must be a GraphRecords, got %s" % (who, type(records).__name__))
+            max_atoms, max_bonds = records.max_atoms, records.max_bonds
+        for name, n, top in zip(("max_atoms", "max_bonds"), (int(max_atoms), int(max_bonds)), self.MAX_RECORD):
+            if n < 1 or (top is not None and n > top):
+                raise ValueError("%s: %s must be %s, got %d" % (who, name, ">= 1" if top is None else "1..%d" % top, n))
+        rows = MoleculeRows.checked(who, *mol, max_cap_atoms=self.MAX_CAP_ATOMS, n_valid=n_valid)
+        if records is not None and records.B != rows.B:
+            raise ValueError("%s: records stages %d images, the molecules are %d" % (who, records.B, rows.B))
+        self.lib = L.load()
+        self._own_records = records is None
+        self.records = GraphRecords(rows.B, max_atoms, max_bonds, rows.device) if records is None else records
+        self.B, self.cap_atoms, self.cap_mol_bonds = rows.B, rows.cap_atoms, rows.cap_mol_bonds
+        self.max_atoms, self.max_bonds = self.records.max_atoms, self.records.max_bonds
+        self.rows = torch.zeros((rows.B, len(self.COLUMNS)), dtype=torch.int32, device=rows.device)
+        # (uint64 on the device; int64 here: the sums stay far below 2^63)
+        self.totals = torch.zeros(len(self.COLUMNS), dtype=torch.int64, device=rows.device)
+        rows.fill(d)
+        self.records.fill(d)
+        d.n_valid = L.ptr(n_valid)
+        d.rows, d.totals = self.rows.data_ptr(), self.totals.data_ptr()
+        self.d, self.keep = d, rows.tensors[:3] + (n_valid,)
+
+    @classmethod
+    def from_assembler(cls, asm, **kw):
+        return cls(asm.rows, **kw)
+
+    def run(self, stream=None):
+        L.check(getattr(self.lib, "abc_" + self.UPDATE)(C.byref(self.d), stream_or_current(stream)), self.UPDATE)
+
+    @property
+    def loaded(self):
+        return self.records.loaded
+
+    def load(self, graphs):
+        """GraphRecords.load, for the op that made its records; records handed in are loaded once, by their owner"""
+        if not self._own_records:
+            raise ValueError("%s(records=...) reads records it did not make, a scorer's or a runner's: load them there "
+                             "(GraphRecords.load, InferenceRunner.load_graphs)" % type(self).__name__)
+        self.records.load(graphs)
+
+    def reset(self):
+        self.totals.zero_()
+
+    def _totals(self):
+        """the running totals under their column names (int) and "rows", the table of the last call (device sync)"""
+        out = {k: int(v) for k, v in zip(self.COLUMNS, self.totals.cpu().tolist())}
+        out["rows"] = self.rows.cpu().numpy()
+        return out
 
 
-class GraphScore:
+class GraphScore(_RecordScorer):
     """how many assembled molecules ARE the annotated molecule (csrc/graph_score.hip, abc_graph_score_update): the molecules of a
     GraphAssembler, read in place, against the graph records of raster.parse_graph -- bonded atoms located by mutual nearest cell
     within `radius`, matched by symbol and charge; bonds paired by their located ends, matched by order.  One launch, static
     buffers, graph-capture safe; the 14 columns (L.GRAPH_SCORE_COLUMNS) of every image of the last call in .rows, their running
     sums in .totals; `result()` is the only host sync."""
 
-    MAX_RECORD = 1024      # abc_graph_score_desc: max_atoms, max_bonds <= 1024
+    UPDATE, COLUMNS = "graph_score_update", L.GRAPH_SCORE_COLUMNS
+    MAX_CAP_ATOMS, MAX_RECORD = L.MAX_CAP_ATOMS, (L.MAX_SCORE_RECORD, L.MAX_SCORE_RECORD)
 
-    def __init__(self, mol_counts, mol_atoms, mol_bonds, max_atoms=256, max_bonds=256, radius=0, n_valid=None):
-        """mol_counts int32 [B, 4], mol_atoms int32 [B, cap_atoms, 5], mol_bonds int32 [B, cap_mol_bonds, 4]: device tensors of
-        GraphAssembler's layout (its own buffers, or hand-made rows); max_atoms / max_bonds: the capacity of a record;
-        radius >= 0 in cells; n_valid: a one-element int32 device tensor, only the first n_valid images count"""
-        for name, t in (("mol_counts", mol_counts), ("mol_atoms", mol_atoms), ("mol_bonds", mol_bonds)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("GraphScore: %s must be a tensor, got %s" % (name, type(t).__name__))
-        if mol_atoms.dim() != 3 or mol_atoms.shape[2] != 5 or mol_bonds.dim() != 3 or mol_bonds.shape[2] != 4:
-            raise ValueError("GraphScore: mol_atoms must be [B, cap_atoms, 5] and mol_bonds [B, cap_mol_bonds, 4], got %s and %s"
-                             % (tuple(mol_atoms.shape), tuple(mol_bonds.shape)))
-        B, cap_atoms, cap_mol_bonds = mol_atoms.shape[0], mol_atoms.shape[1], mol_bonds.shape[1]
-        if tuple(mol_counts.shape) != (B, 4) or mol_bonds.shape[0] != B:
-            raise ValueError("GraphScore: mol_counts must be [%d, 4] and mol_bonds [%d, cap_mol_bonds, 4], got %s and %s"
-                             % (B, B, tuple(mol_counts.shape), tuple(mol_bonds.shape)))
-        if B < 1 or not (1 <= cap_atoms <= 2048) or cap_mol_bonds < 1:
-            raise ValueError("GraphScore: B >= 1, cap_atoms 1..2048 and cap_mol_bonds >= 1, got %d, %d, %d" % (B, cap_atoms, cap_mol_bonds))
-        max_atoms, max_bonds, radius = int(max_atoms), int(max_bonds), int(radius)
-        if not (1 <= max_atoms <= self.MAX_RECORD and 1 <= max_bonds <= self.MAX_RECORD):
-            raise ValueError("GraphScore: max_atoms and max_bonds must be 1..%d, got %d and %d" % (self.MAX_RECORD, max_atoms, max_bonds))
-        if not (0 <= radius <= 32768):
-            raise ValueError("GraphScore: radius must be 0..32768 cells, got %d" % radius)
-        if n_valid is not None and not (isinstance(n_valid, torch.Tensor) and n_valid.numel() == 1):
-            raise ValueError("GraphScore: n_valid must be a one-element int32 device tensor")
-        for t in (mol_counts, mol_atoms, mol_bonds) + (() if n_valid is None else (n_valid,)):
-            require_device_tensor(t, torch.int32, "GraphScore: mol_counts, mol_atoms, mol_bonds (the assembler's layout) and n_valid")
-        self.lib = L.load()
-        dev = mol_atoms.device
-        self.B, self.cap_atoms, self.cap_mol_bonds = B, cap_atoms, cap_mol_bonds
-        self.max_atoms, self.max_bonds, self.radius = max_atoms, max_bonds, radius
-        self.staging = PinnedStaging(dev, {"atoms": ((B, max_atoms, 4), torch.int32), "bonds": ((B, max_bonds, 3), torch.int32),
-                                           "cnt": ((2, B), torch.int32)})
-        self.h_atoms, self.h_bonds, self.h_cnt = self.staging.host.values()
-        self.d_atoms, self.d_bonds, self.d_cnt = self.staging.dev.values()
-        self.rows = torch.zeros((B, len(L.GRAPH_SCORE_COLUMNS)), dtype=torch.int32, device=dev)
-        # (uint64 on the device; int64 here: the sums stay far below 2^63)
-        self.totals = torch.zeros(len(L.GRAPH_SCORE_COLUMNS), dtype=torch.int64, device=dev)
+    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, max_atoms=256, max_bonds=256, radius=0, n_valid=None, records=None):
+        """a contract.MoleculeRows (GraphAssembler.rows), or its mol_counts, mol_atoms and mol_bonds device tensors (hand-made rows);
+        max_atoms / max_bonds: the capacity of a record; radius >= 0 in cells; n_valid: a one-element int32 device tensor, only the
+        first n_valid images count; records: a contract.GraphRecords over the same batch, read in place -- default: made here"""
+        self.radius = int(radius)
+        if not (0 <= self.radius <= 32768):
+            raise ValueError("GraphScore: radius must be 0..32768 cells, got %d" % self.radius)
         d = L.GraphScoreDesc()
-        d.mol_counts, d.mol_atoms, d.mol_bonds = mol_counts.data_ptr(), mol_atoms.data_ptr(), mol_bonds.data_ptr()
-        d.rec_atoms, d.rec_bonds, d.rec_counts = self.d_atoms.data_ptr(), self.d_bonds.data_ptr(), self.d_cnt.data_ptr()
-        d.n_valid = None if n_valid is None else n_valid.data_ptr()
-        d.B, d.cap_atoms, d.cap_mol_bonds, d.max_atoms, d.max_bonds, d.radius = B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds, radius
-        d.rows, d.totals = self.rows.data_ptr(), self.totals.data_ptr()
-        self.d, self.keep = d, (mol_counts, mol_atoms, mol_bonds, n_valid)
-        self.loaded = False
-
-    @classmethod
-    def from_assembler(cls, asm, max_atoms=256, max_bonds=256, radius=0, n_valid=None):
-        return cls(asm.mol_counts, asm.mol_atoms, asm.mol_bonds, max_atoms=max_atoms, max_bonds=max_bonds, radius=radius, n_valid=n_valid)
-
-    def load(self, graphs):
-        """graphs = list of n <= B (atoms [k, 4], bonds [m, 3]) pairs from raster.parse_graph; the rows past n get an empty record.
-        Asynchronous H2D of a few KB through pinned staging."""
-        stage_graph_records(self, graphs)
-
-    def run(self, stream=None):
-        L.check(self.lib.abc_graph_score_update(C.byref(self.d), stream_or_current(stream)), "graph_score_update")
-
-    def reset(self):
-        self.totals.zero_()
+        d.radius = self.radius
+        self._bind(d, (mol_counts, mol_atoms, mol_bonds), n_valid, records, max_atoms, max_bonds)
 
     def result(self):
         """dict (device sync): the 14 running totals under their names (int), "share_exact" = exact / counted, "share_atoms" =
         atoms_matched / atoms_true, "share_bonds" = bonds_matched / bonds_true (nan for an empty denominator), and "rows": the
         int32 [B, 14] table of the last call"""
-        tot = self.totals.cpu().tolist()
-        out = {k: int(v) for k, v in zip(L.GRAPH_SCORE_COLUMNS, tot)}
+        out = self._totals()
         for share, num, den in (("share_exact", "exact", "counted"), ("share_atoms", "atoms_matched", "atoms_true"),
                                 ("share_bonds", "bonds_matched", "bonds_true")):
             out[share] = out[num] / out[den] if out[den] else float("nan")
-        out["rows"] = self.rows.cpu().numpy()
         return out
 
 
-class GraphSimilarity:
+class GraphSimilarity(_RecordScorer):
     """how NEAR the assembled molecules are to the annotated ones, free of positions (csrc/graph_sim.hip,
     abc_graph_similarity_update): the multiset of the radius-0..3 atom environments of a GraphAssembler's molecule, read in place,
     against that of the raster.parse_graph record -- the stand-in for the Dice similarity of Morgan fingerprints of cal_acc.py:38-43
@@ -667,99 +630,26 @@ class GraphSimilarity:
     .totals; `result()` is the only host sync.  `refine_equal` is an UPPER bound of "the same molecule" (colour refinement),
     GraphScore's `exact` the positional lower one."""
 
-    MAX_ATOMS = 512        # abc_graph_similarity_desc: cap_atoms, max_atoms <= 512
+    UPDATE, COLUMNS = "graph_similarity_update", L.GRAPH_SIM_COLUMNS
+    MAX_CAP_ATOMS, MAX_RECORD = L.MAX_SIM_ATOMS, (L.MAX_SIM_ATOMS, None)
 
-    def __init__(self, mol_counts, mol_atoms, mol_bonds, max_atoms=256, max_bonds=256, n_valid=None, records=None, debug_ids=False):
-        """mol_counts, mol_atoms, mol_bonds, n_valid: as GraphScore; max_atoms / max_bonds: the capacity of a record.
-        records: a GraphScore over the same batch -- its staged record buffers are read in place (no second staging: `load` is
-        refused here, `loaded` follows the scorer, max_atoms / max_bonds are the scorer's).  debug_ids: keep the fingerprint ids of
-        every image in .ids (int64 [B, 2, 2048] holding the uint64 bit patterns: molecule, then record; layer-major, atom-minor)"""
-        for name, t in (("mol_counts", mol_counts), ("mol_atoms", mol_atoms), ("mol_bonds", mol_bonds)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("GraphSimilarity: %s must be a tensor, got %s" % (name, type(t).__name__))
-        if mol_atoms.dim() != 3 or mol_atoms.shape[2] != 5 or mol_bonds.dim() != 3 or mol_bonds.shape[2] != 4:
-            raise ValueError("GraphSimilarity: mol_atoms must be [B, cap_atoms, 5] and mol_bonds [B, cap_mol_bonds, 4], got %s and %s"
-                             % (tuple(mol_atoms.shape), tuple(mol_bonds.shape)))
-        B, cap_atoms, cap_mol_bonds = mol_atoms.shape[0], mol_atoms.shape[1], mol_bonds.shape[1]
-        if tuple(mol_counts.shape) != (B, 4) or mol_bonds.shape[0] != B:
-            raise ValueError("GraphSimilarity: mol_counts must be [%d, 4] and mol_bonds [%d, cap_mol_bonds, 4], got %s and %s"
-                             % (B, B, tuple(mol_counts.shape), tuple(mol_bonds.shape)))
-        if B < 1 or not (1 <= cap_atoms <= self.MAX_ATOMS) or cap_mol_bonds < 1:
-            raise ValueError("GraphSimilarity: B >= 1, cap_atoms 1..%d (the limit of a molecule here: %d atoms) and cap_mol_bonds >= 1, "
-                             "got %d, %d, %d" % (self.MAX_ATOMS, self.MAX_ATOMS, B, cap_atoms, cap_mol_bonds))
-        if records is not None:
-            if not isinstance(records, GraphScore):
-                raise ValueError("GraphSimilarity: records must be a GraphScore, got %s" % type(records).__name__)
-            if records.B != B:
-                raise ValueError("GraphSimilarity: records stages %d images, the molecules are %d" % (records.B, B))
-            max_atoms, max_bonds = records.max_atoms, records.max_bonds
-        max_atoms, max_bonds = int(max_atoms), int(max_bonds)
-        if not (1 <= max_atoms <= self.MAX_ATOMS) or max_bonds < 1:
-            raise ValueError("GraphSimilarity: max_atoms must be 1..%d (the limit of a molecule here: %d atoms) and max_bonds >= 1, "
-                             "got %d and %d" % (self.MAX_ATOMS, self.MAX_ATOMS, max_atoms, max_bonds))
-        if n_valid is not None and not (isinstance(n_valid, torch.Tensor) and n_valid.numel() == 1):
-            raise ValueError("GraphSimilarity: n_valid must be a one-element int32 device tensor")
-        for t in (mol_counts, mol_atoms, mol_bonds) + (() if n_valid is None else (n_valid,)):
-            require_device_tensor(t, torch.int32, "GraphSimilarity: mol_counts, mol_atoms, mol_bonds (the assembler's layout) and n_valid")
-        self.lib = L.load()
-        dev = mol_atoms.device
-        self.B, self.cap_atoms, self.cap_mol_bonds = B, cap_atoms, cap_mol_bonds
-        self.max_atoms, self.max_bonds = max_atoms, max_bonds
-        self.records = records
-        if records is None:
-            self.staging = PinnedStaging(dev, {"atoms": ((B, max_atoms, 4), torch.int32), "bonds": ((B, max_bonds, 3), torch.int32),
-                                               "cnt": ((2, B), torch.int32)})
-            self.h_atoms, self.h_bonds, self.h_cnt = self.staging.host.values()
-            self.d_atoms, self.d_bonds, self.d_cnt = self.staging.dev.values()
-            self._loaded = False
-        else:
-            self.staging = None
-            self.d_atoms, self.d_bonds, self.d_cnt = records.d_atoms, records.d_bonds, records.d_cnt
-        self.rows = torch.zeros((B, len(L.GRAPH_SIM_COLUMNS)), dtype=torch.int32, device=dev)
-        # (uint64 on the device; int64 here: the sums stay far below 2^63)
-        self.totals = torch.zeros(len(L.GRAPH_SIM_COLUMNS), dtype=torch.int64, device=dev)
-        self.ids = torch.zeros((B, 2, L.GRAPH_SIM_IDS), dtype=torch.int64, device=dev) if debug_ids else None
+    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, max_atoms=256, max_bonds=256, n_valid=None, records=None, debug_ids=False):
+        """the rows, n_valid, max_atoms / max_bonds: as GraphScore.  records: a contract.GraphRecords over the same batch, or a
+        GraphScore, whose records are taken -- read in place (no second staging: `load` is refused here, max_atoms / max_bonds
+        are theirs).  debug_ids: keep the fingerprint ids of every image in .ids (int64 [B, 2, 2048] holding the uint64 bit
+        patterns: molecule, then record; layer-major, atom-minor)"""
         d = L.GraphSimilarityDesc()
-        d.mol_counts, d.mol_atoms, d.mol_bonds = mol_counts.data_ptr(), mol_atoms.data_ptr(), mol_bonds.data_ptr()
-        d.rec_atoms, d.rec_bonds, d.rec_counts = self.d_atoms.data_ptr(), self.d_bonds.data_ptr(), self.d_cnt.data_ptr()
-        d.n_valid = None if n_valid is None else n_valid.data_ptr()
-        d.B, d.cap_atoms, d.cap_mol_bonds, d.max_atoms, d.max_bonds = B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds
-        d.rows, d.totals, d.ids_out = self.rows.data_ptr(), self.totals.data_ptr(), L.ptr(self.ids)
-        self.d, self.keep = d, (mol_counts, mol_atoms, mol_bonds, n_valid)
-
-    @classmethod
-    def from_assembler(cls, asm, max_atoms=256, max_bonds=256, n_valid=None, records=None, debug_ids=False):
-        return cls(asm.mol_counts, asm.mol_atoms, asm.mol_bonds, max_atoms=max_atoms, max_bonds=max_bonds, n_valid=n_valid, records=records,
-                   debug_ids=debug_ids)
-
-    @property
-    def loaded(self):
-        return self._loaded if self.records is None else self.records.loaded
-
-    @loaded.setter
-    def loaded(self, value):
-        self._loaded = bool(value)
-
-    def load(self, graphs):
-        """as GraphScore.load; refused when the records are a GraphScore's (load them there, once)"""
-        if self.records is not None:
-            raise ValueError("GraphSimilarity(records=scorer) reads the scorer's records: load them with scorer.load")
-        stage_graph_records(self, graphs)
-
-    def run(self, stream=None):
-        L.check(self.lib.abc_graph_similarity_update(C.byref(self.d), stream_or_current(stream)), "graph_similarity_update")
-
-    def reset(self):
-        self.totals.zero_()
+        records = records.records if isinstance(records, GraphScore) else records
+        self._bind(d, (mol_counts, mol_atoms, mol_bonds), n_valid, records, max_atoms, max_bonds)
+        self.ids = torch.zeros((self.B, 2, L.GRAPH_SIM_IDS), dtype=torch.int64, device=self.rows.device) if debug_ids else None
+        d.ids_out = L.ptr(self.ids)
 
     def result(self):
         """dict (device sync): the 12 running totals under their names (int), "similarity" = dice_q20 / 2^20 / counted, the mean
         Dice similarity over every counted image, an image without a molecule counting 0 as a failed row does in cal_acc.py:45-47
         (nan when nothing was counted), and "rows": the int32 [B, 12] table of the last call"""
-        tot = self.totals.cpu().tolist()
-        out = {k: int(v) for k, v in zip(L.GRAPH_SIM_COLUMNS, tot)}
+        out = self._totals()
         out["similarity"] = out["dice_q20"] / float(1 << 20) / out["counted"] if out["counted"] else float("nan")
-        out["rows"] = self.rows.cpu().numpy()
         return out
 
 

@@ -629,6 +629,11 @@ int abc_build_scan_images(const abc_scan_desc* d, abc_stream_t stream);
 /* sizeof(abc_scan_desc), for a binding's mirror struct (as abc_molblock_desc_size) */
 int abc_scan_desc_size(void);
 
+/* The capacities of the SMILES decoder's stages below, the sizes of their kernels' LDS arrays (a launch with more is ABC_EINVAL):
+ * cap_atoms of extract, assemble and graph score; bond peaks per image abc_extract_peaks expands; max_atoms and max_bonds of the
+ * graph score; cap_atoms and max_atoms of the graph similarity. */
+enum abc_decoder_limit { ABC_MAX_CAP_ATOMS = 2048, ABC_MAX_BOND_PEAKS = 4096, ABC_MAX_SCORE_RECORD = 1024, ABC_MAX_SIM_ATOMS = 512 };
+
 /* Candidate extraction for the SMILES decoder (img2smiles2.py:113-191; replaces its per-pixel .cpu().item() loops):
  * from the NMS masks of abc_nms_peaks and the raw head maps (all NCHW f32) to compact ordered lists per image.
  *   atoms[b][i] = (x, y, type, charge, hs)      raster order, greedy suppression within squared distance < 4

@@ -246,7 +246,7 @@ def part_score(rs, steps, warmup, iters=200):
     us_ext = launch_us(r.extractor.run, iters)
     sc.totals.copy_(keep)
     r.reset_evaluation()
-    mc, rc = r.assembler.mol_counts.cpu(), sc.d_cnt.cpu()
+    mc, rc = r.assembler.mol_counts.cpu(), r.records.staging.dev["cnt"].cpu()
     emit({"part": "score", "what": "launch", "batch": B, "us_per_launch": round(us, 2), "assemble_us_per_launch": round(us_asm, 2),
           "extract_us_per_launch": round(us_ext, 2),
           "evaluation_us_per_call": round(us_eval, 2), "molecule_atoms_mean": round(float(mc[:, 0].float().mean()), 1),

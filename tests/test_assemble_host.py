@@ -13,17 +13,11 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import abcnet_amd  # noqa: E402,F401
 from abcnet_amd import _lib as L  # noqa: E402
 import assemble_oracle as ao  # noqa: E402
+from molrows import ASSEMBLE_DEFAULTS, ASSEMBLE_POINTERS, fake_desc, assemble_golden as cases  # noqa: E402
 
 RULES = {"both_ends_one_atom", "repeated_pair_first_wins", "rho_zero", "exact_tie_mirrored_atoms", "exact_tie_coincident_atoms",
          "isolated_atom_in_the_middle", "one_atom_only", "charge_minus_enters_count", "charge_plus_enters_count",
          "aromatic_implicit_h_order", "molblock_coordinate_signs", "hundred_atoms"} | {"repair_count_%d" % n for n in range(2, 9)}
-
-
-def cases(golden_dir):
-    g = np.load(os.path.join(golden_dir, "assemble_128.npz"))
-    for ci in range(int(g["n"])):
-        p = "c%d_" % ci
-        yield str(g[p + "name"]), {k[len(p):]: g[k] for k in g.files if k.startswith(p)}
 
 
 def test_golden_holds_the_cases_of_every_rule(golden_dir):
@@ -138,13 +132,7 @@ def test_assemble_desc_declared_in_binding():
 
 
 def _desc(**kw):
-    d = L.AssembleDesc()
-    for f in ("counts", "atoms", "bonds", "bond_rho", "trig", "mol_counts", "mol_atoms", "mol_bonds", "mol_implh", "work"):
-        setattr(d, f, 256)                             # never dereferenced: the refusals come first
-    d.B, d.cap_atoms, d.cap_bonds, d.cap_mol_bonds = 2, 512, 16384, 2048
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
+    return fake_desc(L.AssembleDesc, ASSEMBLE_POINTERS, ASSEMBLE_DEFAULTS, **kw)
 
 
 def test_launcher_refuses_bad_descriptors_on_the_host():

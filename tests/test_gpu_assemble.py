@@ -17,6 +17,7 @@ from abcnet_amd.decode import Molecule  # noqa: E402
 from abcnet_amd.ops import GraphAssembler, PeakExtractor, nms_peaks  # noqa: E402
 from abcnet_amd.synthetic import correlated_logits, drawn_molecules, synthetic_images, synthetic_targets  # noqa: E402
 import assemble_oracle as ao  # noqa: E402
+from molrows import assemble_golden, filled_unet, trained_unet  # noqa: E402
 
 DEV = "cuda"
 
@@ -49,17 +50,8 @@ def _same(got, want, what=""):
         assert got == want and got.sources == want.sources and got.truncated == want.truncated, what
 
 
-def _golden(golden_dir):
-    g = np.load(os.path.join(golden_dir, "assemble_128.npz"))
-    out = []
-    for ci in range(int(g["n"])):
-        p = "c%d_" % ci
-        out.append((str(g[p + "name"]), {k[len(p):]: g[k] for k in g.files if k.startswith(p)}))
-    return out
-
-
 def test_every_golden_case_on_the_device(golden_dir):
-    cases = _golden(golden_dir)
+    cases = assemble_golden(golden_dir)
     asm = GraphAssembler(*_upload([(c["atoms"], c["bonds"], c["rho"]) for _, c in cases], 128, 2048))
     asm.run()
     torch.cuda.synchronize()
@@ -152,21 +144,13 @@ def test_truncation_is_reported(golden_dir):
     full = _extract(lg, cap_atoms=2048, cap_bonds=65536).lists()[0]
     assert torch.equal(l["atoms"], full["atoms"][:len(l["atoms"])]) and len(l["atoms"]) <= 8
     # cap_mol_bonds hit: the first bonds of the reference's list, and the flag
-    c = dict(_golden(golden_dir))["decode_128_image1"]
+    c = dict(assemble_golden(golden_dir))["decode_128_image1"]
     asm = GraphAssembler(*_upload([(c["atoms"], c["bonds"], c["rho"])], 64, 2048), cap_mol_bonds=40)
     asm.run()
     torch.cuda.synchronize()
     m = asm.molecules()[0]
     assert m.truncated and len(m.bonds) == 40 and m.orders == c["bonds_property_list_final"].tolist()[:40]
     _same(m, _mol(ao.assemble_counts([54, 54, 1222, 1222], c["atoms"], c["bonds"], c["rho"], 64, 2048, 40)))
-
-
-def _filled_unet():
-    from abcnet_amd.unet import UNet
-    from oracle import unet_oracle as uo
-    m = UNet(1, uo.HEADS, dtype="fp32", dropout_p=0.0)
-    m.load_state_dict(uo.filled_state("unet", 1, uo.HEADS, seed=0))
-    return m.to(DEV)
 
 
 def _stage_by_stage(lists, cap_atoms, cap_bonds):
@@ -182,7 +166,7 @@ def test_inference_runner_with_assembly():
     """eval forward + NMS + extraction + assembly in one captured graph, replayed == the stages run one by one; and assemble=True leaves
     the candidate lists and the masks bit-identical to a runner built without it"""
     from abcnet_amd.infer import InferenceRunner
-    m = _filled_unet()
+    m = filled_unet(dropout_p=0.0)
     run = InferenceRunner(m, 2, 128, 128, use_graph=True, assemble=True)
     plain = InferenceRunner(m, 2, 128, 128, use_graph=True, extract=True)
     assert run.extractor is not None and plain.assembler is None
@@ -213,11 +197,7 @@ def test_decode_and_fp8_runners_give_the_same_molecules(fp8):
     """the assembly reads lists, not maps: with decode=True (bf16 and e4m3 graphs) the molecules are those of the runner that stores
     every map, and both are the oracle's on the runner's own candidates"""
     from abcnet_amd.infer import InferenceRunner
-    from abcnet_amd.unet import UNet
-    from oracle import unet_oracle as uo
-    m = UNet(1, uo.HEADS, dtype="bf16")
-    m.load_state_dict(uo.filled_state("unet", 1, uo.HEADS, seed=0))
-    m = m.to(DEV)
+    m = filled_unet("bf16")
     run = InferenceRunner(m, 2, 128, 128, use_graph=True, fold_bn=True, fp8=fp8, assemble=True)
     dec = InferenceRunner(m, 2, 128, 128, use_graph=True, fold_bn=True, fp8=fp8, assemble=True, decode=True)
     assert dec.decode and not run.decode
@@ -238,13 +218,8 @@ def test_trained_fixture_molecules_equal_the_oracle(golden_dir):
     """the frozen trained network on drawn molecules at 512 x 512 (what config 5 runs on in practice: clean peaks, a handful of
     candidates per bond): device molecules == oracle on the runner's own candidates.  How many graphs equal the drawn annotation
     is reported by profiles/tools/assemble_step.py, not asserted."""
-    sys.path.insert(0, os.path.join(golden_dir))
-    from make_trained_fixture import unpack_state
     from abcnet_amd.infer import InferenceRunner
-    from abcnet_amd.unet import UNet
-    m = UNet(1, [1, 14, 3, 2, 1, 360, 60, 60], dtype="bf16", dropout_p=0.2)
-    m.load_state_dict(unpack_state(os.path.join(golden_dir, "trained_unet_state.npz")))
-    m = m.to(DEV).eval()
+    m = trained_unet(golden_dir)
     B = 16
     x, _notes = drawn_molecules(B, 512, seed=777)
     run = InferenceRunner(m, B, 512, 512, use_graph=True, assemble=True)

@@ -15,10 +15,10 @@ from abcnet_amd.ops import GraphAssembler, GraphScore, PeakExtractor, nms_peaks 
 from abcnet_amd.raster import TargetRasterizer, parse_graph, parse_record  # noqa: E402
 from abcnet_amd.synthetic import drawn_molecules  # noqa: E402
 import graphscore_oracle as go  # noqa: E402
+from molrows import for_score_oracle, records_to_numpy, trained_unet, upload_molecules  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-EMPTY, TRUNCATED = 1, 2
 COL = {c: i for i, c in enumerate(go.COLUMNS)}
 
 
@@ -29,28 +29,11 @@ def _mol(atoms, bonds, truncated=False):
 
 
 def _for_oracle(m):
-    if m is None:
-        return None
-    return dict(symbols=[go.ATOM_SYMBOLS[a[2]] for a in m["atoms"]], charges=[a[3] for a in m["atoms"]],
-                positions=[[a[0], a[1]] for a in m["atoms"]], bonds=[[q[0], q[1]] for q in m["bonds"]],
-                orders=[q[2] for q in m["bonds"]], truncated=m["truncated"])
+    return for_score_oracle(m, go.ATOM_SYMBOLS)
 
 
 def _upload(mols, cap_atoms, cap_mol_bonds):
-    B = len(mols)
-    cnt = np.zeros((B, 4), dtype=np.int32)
-    atoms = np.full((B, cap_atoms, 5), 7, dtype=np.int32)          # (rows past the counts hold junk: they must not be read)
-    bonds = np.full((B, cap_mol_bonds, 4), 1, dtype=np.int32)
-    for b, m in enumerate(mols):
-        if m is None:
-            cnt[b] = (3, 2, 0, EMPTY | TRUNCATED)                   # (an empty image counts nothing but `none`, whatever else it says)
-            continue
-        cnt[b] = (len(m["atoms"]), len(m["bonds"]), 0, TRUNCATED if m["truncated"] else 0)
-        for i, a in enumerate(m["atoms"]):
-            atoms[b, i] = (a[0], a[1], a[2], a[3], -1)
-        for i, q in enumerate(m["bonds"]):
-            bonds[b, i] = (q[0], q[1], q[2], i)
-    return tuple(torch.from_numpy(t).to(DEV) for t in (cnt, atoms, bonds))
+    return upload_molecules(mols, cap_atoms, cap_mol_bonds, junk_bond=(1, 1, 1, 1))
 
 
 # the annotated graph of most cases: a four-ring C - N+ - O- - Cl and one atom no bond names (not in T)
@@ -100,7 +83,7 @@ def _cases():
 
 def _score(mols, recs, radius, cap_atoms=32, cap_mol_bonds=64, max_atoms=32, max_bonds=32, n_valid=None):
     gs = GraphScore(*_upload(mols, cap_atoms, cap_mol_bonds), max_atoms=max_atoms, max_bonds=max_bonds, radius=radius, n_valid=n_valid)
-    gs.load([(np.array(a, dtype=np.int32).reshape(-1, 4), np.array(q, dtype=np.int32).reshape(-1, 3)) for a, q in recs])
+    gs.load(records_to_numpy(recs))
     return gs
 
 
@@ -264,17 +247,6 @@ def test_device_closed_loop_equals_the_cpu_chain():
 
 
 # ------------------------------------------------------------------------------------------------------------------ the runner
-def _trained_unet(golden_dir):
-    """the frozen trained fixture (tests/golden/trained_unet_state.npz): the network is fully convolutional, so the weights
-    trained at 384 x 384 load at any input size"""
-    sys.path.insert(0, golden_dir)
-    from make_trained_fixture import unpack_state
-    from abcnet_amd.unet import UNet
-    m = UNet(1, [1, 14, 3, 2, 1, 360, 60, 60], dtype="bf16", dropout_p=0.2)
-    m.load_state_dict(unpack_state(os.path.join(golden_dir, "trained_unet_state.npz")))
-    return m.to(DEV).eval()
-
-
 def test_runner_scores_its_own_molecules(golden_dir):
     """batch 4 at 96 x 96 -- drawn_molecules has one atom and no bond at 64, and an 80 x 80 input has a 20 x 20 map, no multiple
     of the 32-pixel groups of SampleBuilder's sparse rasteriser -- a short batch of 3 through SampleBuilder, three steps (eager,
@@ -283,7 +255,7 @@ def test_runner_scores_its_own_molecules(golden_dir):
     from abcnet_amd.infer import InferenceRunner
     B, S, n, radius = 4, 96, 3, 1
     h = S // 4
-    m = _trained_unet(golden_dir)
+    m = trained_unet(golden_dir)
     plain = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, evaluate=True)
     assert plain.scorer is None and "molecules" not in plain.evaluation()
     with pytest.raises(L.AbcNetHipError):

@@ -12,37 +12,23 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import abcnet_amd  # noqa: E402,F401
 from abcnet_amd import _lib as L  # noqa: E402
+from abcnet_amd.contract import GraphRecords  # noqa: E402
 from abcnet_amd.ops import GraphScore, GraphSimilarity  # noqa: E402
 from abcnet_amd.raster import parse_graph  # noqa: E402
 from abcnet_amd.synthetic import drawn_molecules  # noqa: E402
 import graphsim_oracle as so  # noqa: E402
+from molrows import for_score_oracle, records_to_numpy, trained_unet, upload_molecules  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-EMPTY, TRUNCATED = 1, 2
 COL = {c: i for i, c in enumerate(so.COLUMNS)}
 
 
 def _upload(mols, cap_atoms, cap_mol_bonds):
-    B = len(mols)
-    cnt = np.zeros((B, 4), dtype=np.int32)
-    atoms = np.full((B, cap_atoms, 5), 7, dtype=np.int32)          # (rows past the counts hold junk: they must not be read)
-    bonds = np.zeros((B, cap_mol_bonds, 4), dtype=np.int32)
-    bonds[:] = (1, 2, 3, 0)                                         # (a junk row that would be a valid bond)
-    for b, m in enumerate(mols):
-        if m is None:
-            cnt[b] = (3, 2, 0, EMPTY | TRUNCATED)                   # (an empty image counts nothing but `none`, whatever else it says)
-            continue
-        cnt[b] = (len(m["atoms"]), len(m["bonds"]), 0, TRUNCATED if m["truncated"] else 0)
-        for i, a in enumerate(m["atoms"]):
-            atoms[b, i] = (a[0], a[1], a[2], a[3], -1)
-        for i, q in enumerate(m["bonds"]):
-            bonds[b, i] = (q[0], q[1], q[2], i)
-    return tuple(torch.from_numpy(t).to(DEV) for t in (cnt, atoms, bonds))
+    return upload_molecules(mols, cap_atoms, cap_mol_bonds, junk_bond=(1, 2, 3, 0))      # (a junk row that would be a valid bond)
 
 
-def _records(recs):
-    return [(np.array(a, dtype=np.int32).reshape(-1, 4), np.array(q, dtype=np.int32).reshape(-1, 3)) for a, q in recs]
+_records = records_to_numpy
 
 
 def _op(mols, recs, cap_atoms=64, cap_mol_bonds=96, max_atoms=64, max_bonds=96, n_valid=None):
@@ -152,20 +138,21 @@ def test_record_rows_may_hold_any_int32():
     mols = [so.mol([1, 2, 3, 6], [(1, 2, 1), (2, 3, 2), (3, 4, 4)])] * 2              # (the record's sulphur is in no bond)
     gs = _op(mols, [rec, rec], cap_atoms=8, cap_mol_bonds=8, max_atoms=8, max_bonds=16)
     torch.cuda.synchronize()
-    gs.d_atoms.fill_(11)
-    gs.d_bonds[:] = torch.tensor([0, 4, 1], dtype=torch.int32, device=DEV)         # (junk that would be a valid row)
+    d_atoms, d_bonds, d_cnt = gs.records.staging.dev.values()
+    d_atoms.fill_(11)
+    d_bonds[:] = torch.tensor([0, 4, 1], dtype=torch.int32, device=DEV)            # (junk that would be a valid row)
     for b in range(2):
-        gs.d_atoms[b, :5] = torch.tensor(rec[0], dtype=torch.int32, device=DEV)
-    gs.d_bonds[0, :3] = torch.tensor(rec[1], dtype=torch.int32, device=DEV)
-    gs.d_bonds[1, :9] = torch.tensor(bad[:3] + rec[1] + bad[3:], dtype=torch.int32, device=DEV)
-    gs.d_cnt.copy_(torch.tensor([[5, 5], [3, 9]], dtype=torch.int32, device=DEV))
+        d_atoms[b, :5] = torch.tensor(rec[0], dtype=torch.int32, device=DEV)
+    d_bonds[0, :3] = torch.tensor(rec[1], dtype=torch.int32, device=DEV)
+    d_bonds[1, :9] = torch.tensor(bad[:3] + rec[1] + bad[3:], dtype=torch.int32, device=DEV)
+    d_cnt.copy_(torch.tensor([[5, 5], [3, 9]], dtype=torch.int32, device=DEV))
     recs = [rec, (rec[0], bad[:3] + rec[1] + bad[3:])]
     _res, rows = _check(gs, mols, recs)
     assert rows[0]["dice_one"] == 1 and rows[0]["atoms_true"] == 4
     assert rows[1]["atoms_true"] == 4 and rows[1]["size_equal"] == 0 and 0 < rows[1]["envs_common"] < 16
     # counts past the capacities are clamped
-    gs.d_cnt.copy_(torch.tensor([[5, 1 << 30], [3, -7]], dtype=torch.int32, device=DEV))
-    want = so.rows(mols, [rec, (gs.d_atoms[1].cpu().numpy(), np.zeros((0, 3), np.int32))])
+    d_cnt.copy_(torch.tensor([[5, 1 << 30], [3, -7]], dtype=torch.int32, device=DEV))
+    want = so.rows(mols, [rec, (d_atoms[1].cpu().numpy(), np.zeros((0, 3), np.int32))])
     gs.run()
     torch.cuda.synchronize()
     assert gs.result()["rows"].tolist() == want.tolist() and want[1, COL["atoms_true"]] == 0
@@ -237,24 +224,35 @@ def test_n_valid_totals_and_reset():
     assert all(res[c] == 0 for c in so.COLUMNS) and np.isnan(res["similarity"])
 
 
-def test_records_are_shared_with_a_graph_score():
-    """one load, both ops right; the sharer stages nothing and refuses a load of its own"""
+@pytest.mark.parametrize("made_by", ["the scorer", "the caller"])
+def test_records_are_shared_with_a_graph_score(made_by):
+    """one load, both ops right; who did not make the records stages nothing and refuses a load of its own.  The records are the
+    scorer's, taken from it, or a GraphRecords built directly and handed to both."""
     import graphscore_oracle as go
     cases = _cases()[:4]
     mols, recs = [m for _, m, _ in cases], [r for _, _, r in cases]
     rows = _upload(mols, 16, 32)
-    scorer = GraphScore(*rows, max_atoms=16, max_bonds=24, radius=0)
-    sim = GraphSimilarity(*rows, records=scorer, debug_ids=True)
-    assert sim.staging is None and sim.d_atoms is scorer.d_atoms and (sim.max_atoms, sim.max_bonds) == (16, 24) and not sim.loaded
-    with pytest.raises(ValueError, match="scorer"):
-        sim.load(_records(recs))
-    scorer.load(_records(recs))
-    assert sim.loaded
+    if made_by == "the scorer":
+        scorer = GraphScore(*rows, max_atoms=16, max_bonds=24, radius=0)
+        sim = GraphSimilarity(*rows, records=scorer, debug_ids=True)
+        loader, refusers = scorer, [sim]
+    else:
+        loader = GraphRecords(len(mols), 16, 24, DEV)
+        scorer = GraphScore(*rows, radius=0, records=loader)
+        sim = GraphSimilarity(*rows, records=loader, debug_ids=True)
+        assert scorer.records is loader and (scorer.max_atoms, scorer.max_bonds) == (16, 24) and not scorer.loaded
+        refusers = [scorer, sim]
+    # (one GraphRecords, so one staging and one set of device buffers: nothing is staged twice)
+    assert sim.records is scorer.records and (sim.max_atoms, sim.max_bonds) == (16, 24) and not sim.loaded
+    assert sim.d.rec_atoms == scorer.d.rec_atoms == scorer.records.staging.dev["atoms"].data_ptr()
+    for op in refusers:
+        with pytest.raises(ValueError, match="scorer"):
+            op.load(_records(recs))
+    loader.load(_records(recs))
+    assert sim.loaded and scorer.loaded
     scorer.run()
     _check(sim, mols, recs)
-    for_score = [dict(symbols=[go.ATOM_SYMBOLS[a[2]] for a in m["atoms"]], charges=[a[3] for a in m["atoms"]],
-                      positions=[[a[0], a[1]] for a in m["atoms"]], bonds=[[q[0], q[1]] for q in m["bonds"]],
-                      orders=[q[2] for q in m["bonds"]], truncated=m["truncated"]) for m in mols]
+    for_score = [for_score_oracle(m, go.ATOM_SYMBOLS) for m in mols]
     assert scorer.result()["rows"].tolist() == go.rows(for_score, recs, 0).tolist()
     with pytest.raises(ValueError, match="512"):
         GraphSimilarity(*rows, records=GraphScore(*rows, max_atoms=513, max_bonds=24))
@@ -265,16 +263,6 @@ def test_records_are_shared_with_a_graph_score():
 
 
 # ------------------------------------------------------------------------------------------------------------------ the runner
-def _trained_unet(golden_dir):
-    """the frozen trained fixture (tests/golden/trained_unet_state.npz), as tests/test_gpu_graphscore.py loads it"""
-    sys.path.insert(0, golden_dir)
-    from make_trained_fixture import unpack_state
-    from abcnet_amd.unet import UNet
-    m = UNet(1, [1, 14, 3, 2, 1, 360, 60, 60], dtype="bf16", dropout_p=0.2)
-    m.load_state_dict(unpack_state(os.path.join(golden_dir, "trained_unet_state.npz")))
-    return m.to(DEV).eval()
-
-
 def test_runner_grades_its_own_molecules(golden_dir):
     """the twin of test_runner_scores_its_own_molecules: batch 4 at 96 x 96, a short batch of 3 through SampleBuilder, three steps
     (eager, capture + replay, replay), the trained fixture; beside it the same runner without the flag, whose "molecules" must
@@ -283,13 +271,13 @@ def test_runner_grades_its_own_molecules(golden_dir):
     from abcnet_amd.infer import InferenceRunner
     B, S, n = 4, 96, 3
     h = S // 4
-    m = _trained_unet(golden_dir)
+    m = trained_unet(golden_dir)
     kw = dict(use_graph=True, assemble=True, evaluate=True)
     plain = InferenceRunner(m, B, S, S, score_graphs=True, **kw)
     run = InferenceRunner(m, B, S, S, score_graphs=True, score_similarity=True, **kw)
     solo = InferenceRunner(m, B, S, S, score_similarity=True, **kw)
-    assert plain.similarity is None and run.similarity.records is run.scorer and run.similarity.keep[3] is run.n_valid
-    assert run.similarity.ids is None and solo.scorer is None and solo.similarity.records is None
+    assert plain.similarity is None and run.similarity.records is run.scorer.records is run.records and run.similarity.keep[3] is run.n_valid
+    assert run.similarity.ids is None and solo.scorer is None and solo.similarity.records is solo.records is not None
     builders = [SampleBuilder(r, amount=0.1, max_src=(S, S), sparse=True, max_atoms=64, max_bonds=64) for r in (plain, run, solo)]
     for r in (run, solo):
         with pytest.raises(L.AbcNetHipError, match="no graph records"):

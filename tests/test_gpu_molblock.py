@@ -17,6 +17,7 @@ from abcnet_amd import _lib as L  # noqa: E402
 from abcnet_amd.decode import Molecule  # noqa: E402
 from abcnet_amd.ops import GraphAssembler, MolBlockWriter  # noqa: E402
 from abcnet_amd.synthetic import synthetic_images  # noqa: E402
+from molrows import assemble_golden, filled_unet  # noqa: E402
 
 DEV = "cuda"
 POSITIONS = (0, 59, 60, 61, 659, 660, 199999)
@@ -84,18 +85,9 @@ def _check_index(w, texts):
     return off, status
 
 
-def _golden(golden_dir):
-    g = np.load(os.path.join(golden_dir, "assemble_128.npz"))
-    out = []
-    for ci in range(int(g["n"])):
-        p = "c%d_" % ci
-        out.append((str(g[p + "name"]), {k[len(p):]: g[k] for k in g.files if k.startswith(p)}))
-    return out
-
-
 def test_golden_cases_give_the_reference_text(golden_dir):
     """every case of assemble_128.npz in one batch (capacities 128 / 2048): assembler -> writer == the text the reference wrote"""
-    cases = _golden(golden_dir)
+    cases = assemble_golden(golden_dir)
     B, cap_atoms, cap_bonds = len(cases), 128, 2048
     cnt = torch.zeros(B, 4, dtype=torch.int32)
     atoms, bonds = torch.zeros(B, cap_atoms, 5, dtype=torch.int32), torch.zeros(B, cap_bonds, 4, dtype=torch.int32)
@@ -217,11 +209,7 @@ def test_a_short_batch_after_a_long_one_shows_nothing_stale():
 def test_inference_runner_with_molblocks():
     """eager, captured and replayed steps (another batch before the replay): the device text is the host form's of molecules()"""
     from abcnet_amd.infer import InferenceRunner
-    from abcnet_amd.unet import UNet
-    from oracle import unet_oracle as uo
-    m = UNet(1, uo.HEADS, dtype="fp32", dropout_p=0.0)
-    m.load_state_dict(uo.filled_state("unet", 1, uo.HEADS, seed=0))
-    m = m.to(DEV)
+    m = filled_unet(dropout_p=0.0)
     with pytest.raises(ValueError, match="assemble=True"):
         InferenceRunner(m, 2, 128, 128, molblocks=True)
     run = InferenceRunner(m, 2, 128, 128, use_graph=True, assemble=True, molblocks=True)

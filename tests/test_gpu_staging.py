@@ -95,9 +95,10 @@ def test_graph_score_holds_the_second_load():
                 gs.load(item)
         torch.cuda.synchronize()
         assert gs.loaded
-        assert gs.d_cnt.cpu().tolist() == [[2, 0], [1, 0]]
-        assert gs.d_atoms[0, :2].cpu().tolist() == rec_b[0][0].tolist() and gs.d_bonds[0, :1].cpu().tolist() == rec_b[0][1].tolist()
-        assert torch.equal(gs.d_atoms.cpu(), gs.h_atoms) and torch.equal(gs.d_bonds.cpu(), gs.h_bonds)
+        (h_atoms, h_bonds, _), (d_atoms, d_bonds, d_cnt) = gs.records.staging.host.values(), gs.records.staging.dev.values()
+        assert d_cnt.cpu().tolist() == [[2, 0], [1, 0]]
+        assert d_atoms[0, :2].cpu().tolist() == rec_b[0][0].tolist() and d_bonds[0, :1].cpu().tolist() == rec_b[0][1].tolist()
+        assert torch.equal(d_atoms.cpu(), h_atoms) and torch.equal(d_bonds.cpu(), h_bonds)
 
 
 def test_image_builder_holds_the_second_load():

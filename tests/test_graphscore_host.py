@@ -15,6 +15,7 @@ from abcnet_amd import _lib as L  # noqa: E402
 from abcnet_amd.raster import parse_graph, parse_record  # noqa: E402
 from abcnet_amd.synthetic import drawn_molecules, random_annotations  # noqa: E402
 import graphscore_oracle as go  # noqa: E402
+from molrows import SCORE_DEFAULTS, SCORE_POINTERS, fake_desc, Heads as _Heads  # noqa: E402
 
 
 def _same_graph(got, want):
@@ -119,10 +120,6 @@ def test_oracle_score_by_hand():
 
 
 # ---------------------------------------------------------------------------------------------------------------- refusals
-class _Heads:
-    heads = [1, 14, 3, 2, 1, 360, 60, 60]
-
-
 @pytest.mark.parametrize("kw", [dict(), dict(assemble=True), dict(evaluate=True), dict(extract=True, evaluate=True)])
 def test_score_graphs_needs_assemble_and_evaluate(kw):
     from abcnet_amd.infer import InferenceRunner
@@ -164,13 +161,7 @@ def test_symbols_and_descriptor_size():
 
 
 def _desc(**kw):
-    d = L.GraphScoreDesc()
-    for f in ("mol_counts", "mol_atoms", "mol_bonds", "rec_atoms", "rec_bonds", "rec_counts", "rows", "totals"):
-        setattr(d, f, 256)                             # never dereferenced: the refusals come first
-    d.B, d.cap_atoms, d.cap_mol_bonds, d.max_atoms, d.max_bonds, d.radius = 2, 512, 2048, 256, 256, 0
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
+    return fake_desc(L.GraphScoreDesc, SCORE_POINTERS, SCORE_DEFAULTS, **kw)
 
 
 def test_launcher_refuses_bad_descriptors_on_the_host():

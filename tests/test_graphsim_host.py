@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import abcnet_amd  # noqa: E402,F401
 from abcnet_amd import _lib as L  # noqa: E402
 import graphsim_oracle as so  # noqa: E402
+from molrows import SCORE_DEFAULTS, SCORE_POINTERS, fake_desc, Heads as _Heads  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COL = {c: i for i, c in enumerate(so.COLUMNS)}
@@ -188,10 +189,6 @@ def test_empty_and_truncated_rows():
 
 
 # ---------------------------------------------------------------------------------------------------------------- refusals
-class _Heads:
-    heads = [1, 14, 3, 2, 1, 360, 60, 60]
-
-
 @pytest.mark.parametrize("kw", [dict(), dict(assemble=True), dict(evaluate=True), dict(extract=True, evaluate=True)])
 def test_score_similarity_needs_assemble_and_evaluate(kw):
     from abcnet_amd.infer import InferenceRunner
@@ -233,13 +230,7 @@ def test_symbols_and_descriptor_size():
 
 
 def _desc(**kw):
-    d = L.GraphSimilarityDesc()
-    for f in ("mol_counts", "mol_atoms", "mol_bonds", "rec_atoms", "rec_bonds", "rec_counts", "rows", "totals"):
-        setattr(d, f, 256)                             # never dereferenced: the refusals come first
-    d.B, d.cap_atoms, d.cap_mol_bonds, d.max_atoms, d.max_bonds = 2, 512, 2048, 256, 256
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
+    return fake_desc(L.GraphSimilarityDesc, SCORE_POINTERS, SCORE_DEFAULTS, **kw)
 
 
 def test_launcher_refuses_bad_descriptors_on_the_host():
