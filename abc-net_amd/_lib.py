@@ -297,6 +297,7 @@ SYMBOLS = {
     "abc_wgrad_pads": (C.c_int, [P(WgradDesc), P(i32), P(i32)]),
     "abc_wgrad_blocks": (C.c_int, [P(WgradDesc)]),
     "abc_wgrad_tile": (C.c_int, [P(WgradDesc), P(i32), P(i32)]),
+    "abc_wgrad_route_info": (C.c_int, [P(WgradDesc), P(i32)]),
     "abc_wgrad": (C.c_int, [P(WgradDesc), vp]),
     "abc_wgrad_reduce": (C.c_int, [P(WgradReduceDesc), vp]),
     "abc_wgrad_reduce_bn_bwd": (C.c_int, [P(WgradReduceDesc), P(BnBwdDesc), vp]),

@@ -753,6 +753,17 @@ extern "C" int abc_wgrad_tile(const abc_wgrad_desc* d, int32_t* at, int32_t* bt)
     return ABC_OK;
 }
 
+// what the launch will take, for tests that must prove which path their case reaches (read-only: the same wgrad_route answer)
+extern "C" int abc_wgrad_route_info(const abc_wgrad_desc* d, int32_t* info) {
+    WgRoute r;
+    if (int rc = wgrad_route(d, &r)) return rc;
+    const bool gen = r.family == WG_GENERAL;
+    info[0] = (int)r.family; info[1] = r.at; info[2] = r.bt;
+    info[3] = gen ? r.g.PM : 0; info[4] = gen ? r.g.ts : 0; info[5] = (gen && r.g.fast_p && r.g.fast_q) ? 1 : 0;
+    info[6] = gen ? r.k3 : 0; info[7] = (gen && r.qtab_off != 0) ? 1 : 0;
+    return ABC_OK;
+}
+
 extern "C" int abc_wgrad_blocks(const abc_wgrad_desc* d) {
     WgRoute r;
     return wgrad_route(d, &r) ? -1 : r.blocks;

@@ -345,6 +345,10 @@ int abc_wgrad_rowsum_ok(const abc_wgrad_desc* d);
 int abc_wgrad_fuses_apply(const abc_wgrad_desc* d); /* 1: this descriptor (with p_dual set) is served by the fused path */
 int abc_wgrad_pads(const abc_wgrad_desc* d, int32_t* ca_pad, int32_t* cb_pad);
 int abc_wgrad_tile(const abc_wgrad_desc* d, int32_t* at, int32_t* bt); /* 32x32 tile pairs per workgroup: at x bt */
+/* which kernel the launch will take: info[8] = {family (0 head, 1 one-channel, 2 16-channel, 3 5x5 32-channel, 4 general), at, bt, and for
+ * the general kernel (else 0): patch rows / 8 (pm), tap-split form (ts), both operands prefetched (fast), static 3x3 K-step (k3), Q's
+ * segment table in LDS}.  Host only, for tests that must prove their case reaches a path */
+int abc_wgrad_route_info(const abc_wgrad_desc* d, int32_t* info);
 int abc_wgrad_blocks(const abc_wgrad_desc* d); /* workgroups per split: choose nsplit so that blocks*nsplit fills the GPU */
 int abc_wgrad(const abc_wgrad_desc* d, abc_stream_t stream);
 typedef struct abc_wgrad_reduce_desc {
