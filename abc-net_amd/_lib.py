@@ -223,6 +223,11 @@ class ScanDesc(C.Structure):
                 ("box", vp), ("geom", vp)]
 
 
+class StrokeDesc(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("B", i32), ("S", i32), ("drop_isolated", i32), ("max_iter", i32), ("radius", i32),
+                ("skip_stride", i32), ("skip", vp), ("stats", vp)]
+
+
 EVAL_NCOUNT = 301   # ABC_EVAL_NCOUNT
 # the ABC_GS_* columns of abc_graph_score_desc.rows / .totals
 GRAPH_SCORE_COLUMNS = ("counted", "none", "truncated", "exact", "atoms_equal", "bonds_equal", "atoms_true", "atoms_pred",
@@ -239,6 +244,10 @@ SCAN_CONSTANT, SCAN_BAD_PARAMS = 1, 2           # abc_scan_status
 SCAN_NBOX = 8       # ABC_SCAN_NBOX
 # the abc_scan_geom columns of abc_scan_desc.geom
 SCAN_GEOM_COLUMNS = ("thr", "inverted", "status", "y0", "x0", "bh", "bw", "rows", "cols", "ddx", "ddy", "ink")
+STROKE_UNTIL_STABLE = -1    # ABC_STROKE_UNTIL_STABLE: abc_stroke_desc.max_iter
+STROKE_MAX_SIZE = 1024      # ABC_STROKE_MAX_SIZE: the largest canvas abc_normalize_strokes holds in LDS
+# the abc_stroke_stat columns of abc_stroke_desc.stats
+STROKE_STAT_COLUMNS = ("iterations", "converged", "ink_in", "ink_out", "skipped")
 MOL_EMPTY, MOL_TRUNCATED = 1, 2     # abc_mol_status
 # enum abc_decoder_limit: cap_atoms (extract, assemble, score), bond peaks expanded per image, score record capacity, similarity atoms
 MAX_CAP_ATOMS, MAX_BOND_PEAKS, MAX_SCORE_RECORD, MAX_SIM_ATOMS = 2048, 4096, 1024, 512
@@ -253,6 +262,8 @@ _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnAppl
 SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_score_desc_size"),
               (GraphSimilarityDesc, "abc_graph_similarity_desc_size"), (MolBlockDesc, "abc_molblock_desc_size"),
               (ScanDesc, "abc_scan_desc_size")]
+# (that list is pinned, name by name, by tests/test_decoder_contract_host.py) the self-sized descriptors since: checked the same way
+SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -323,6 +334,8 @@ SYMBOLS = {
     "abc_build_images": (C.c_int, [P(ImageDesc), vp]),
     "abc_build_scan_images": (C.c_int, [P(ScanDesc), vp]),
     "abc_scan_desc_size": (C.c_int, []),
+    "abc_normalize_strokes": (C.c_int, [P(StrokeDesc), vp]),
+    "abc_stroke_desc_size": (C.c_int, []),
     "abc_metrics_blocks": (C.c_int, [P(MetricsDesc)]),
     "abc_metrics_update": (C.c_int, [P(MetricsDesc), vp]),
     "abc_eval_tables_blocks": (C.c_int, [P(EvalDesc)]),
@@ -407,7 +420,7 @@ def load():
         n = lib.abc_sizeof(i)
         if n != C.sizeof(st):
             raise AbcNetHipError("struct #%d (%s): binding has %d bytes, library %d" % (i, st.__name__, C.sizeof(st), n))
-    for st, size_fn in SELF_SIZED:
+    for st, size_fn in SELF_SIZED + SELF_SIZED_SINCE:
         n = getattr(lib, size_fn)()
         if n != C.sizeof(st):
             raise AbcNetHipError("struct %s: binding has %d bytes, library %d" % (st.__name__, C.sizeof(st), n))

@@ -12,7 +12,8 @@ amounts -- not its bits.  That is the position the dropout mask takes (dropout.p
 
 A third way to build the input, "scan": ScanBuilder takes raw grey scans of any size and background level (what binarize.py's
 offline Otsu step and utils_for_test.py's loader do between them, plus the crop and the fit a scan needs) and csrc/scan.hip
-thresholds, crops, fits and writes them; otsu_threshold and fit_scan below are the pure host mirrors of its rules.
+thresholds, crops, fits and writes them; otsu_threshold and fit_scan below are the pure host mirrors of its rules.  On request it
+appends ops.StrokeNormalizer (csrc/stroke.hip) as a sixth launch: speckles dropped, strokes thinned and grown back to one width.
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ import torch
 
 from . import _lib as L
 from .contract import PinnedStaging, require_device_tensor, stream_or_current
+from .ops import StrokeNormalizer, stroke_max_iter
 
 MODES = {"train": L.IMG_TRAIN, "test": L.IMG_TEST}
 
@@ -251,11 +253,23 @@ class ScanBuilder:
     margin defaults to the margin=20 of synthetic.drawn_molecules at 512, scaled: size * 20 // 512.  cover (0 .. 256, in
     1 / 256) defaults to DEFAULT_COVER_Q8, the value with the best mean environment similarity of the frozen trained fixture
     in profiles/r13_scan.md -- measured on SYNTHETIC drawings made into scans on the host, because no real scan was
-    available.  No CPU fallback."""
+    available.  No CPU fallback.
 
-    def __init__(self, batch, size, out=None, max_src=(1024, 1024), margin=None, cover=None, polarity="dark", device="cuda"):
+    thin, stroke_radius, drop_isolated: the stroke normalisation of ops.StrokeNormalizer (csrc/stroke.hip), off by default.  With
+    any of them set, run() appends it as a sixth launch on the same stream, over `out` in place, skipping the images whose
+    geometry status is non-zero (a CONSTANT image stays blank, a BAD_PARAMS one keeps its NaN); stroke_stats() returns its rows.
+    The geometry rows do not change: `ink` stays the source's count.  size is then at most L.STROKE_MAX_SIZE.  Recommended where it
+    is used: thin=1, stroke_radius=1, the one setting of twelve that beat the unnormalised scans under both candidate rules in
+    profiles/r14_stroke.md (synthetic scans again, and by little); thinning to the skeleton turns a solid wedge into a line."""
+
+    def __init__(self, batch, size, out=None, max_src=(1024, 1024), margin=None, cover=None, polarity="dark", device="cuda",
+                 thin=None, stroke_radius=None, drop_isolated=False):
         if polarity not in POLARITIES:
             raise ValueError("ScanBuilder: polarity must be 'dark', 'light' or 'auto', got %r" % (polarity,))
+        normalise = stroke_max_iter(thin, "ScanBuilder") != 0 or stroke_radius is not None or bool(drop_isolated)
+        if normalise and int(size) > L.STROKE_MAX_SIZE:
+            raise ValueError("ScanBuilder: thin / stroke_radius / drop_isolated need size <= %d (the normaliser holds an image in "
+                             "LDS), got %d" % (L.STROKE_MAX_SIZE, int(size)))
         if not torch.cuda.is_available():
             raise L.AbcNetHipError("ScanBuilder needs an MI355X; abcnet_amd has no CPU fallback")
         S = int(size)
@@ -298,6 +312,11 @@ class ScanBuilder:
         d.B, d.S, d.margin, d.cover_q8, d.polarity = batch, S, margin, cover, POLARITIES[polarity]
         d.hist, d.box, d.geom = self.hist.data_ptr(), self.box.data_ptr(), self.geom.data_ptr()
         self.d = d
+        # the sixth launch, when asked for: in place over out, the geometry status column as its skip words
+        self.strokes = None
+        if normalise:
+            self.strokes = StrokeNormalizer(out, thin=thin, radius=0 if stroke_radius is None else stroke_radius,
+                                            drop_isolated=drop_isolated, skip=self.geom[:, L.SCAN_GEOM_COLUMNS.index("status")])
 
     def load(self, images_u8):
         """images_u8: B 2-d uint8 arrays (decoded grey scans), each within max_src.  Host work: the checks and one memcpy per
@@ -322,9 +341,19 @@ class ScanBuilder:
         self.staging.commit()
 
     def run(self, stream=None):
-        """five launches in order on one stream (graph-capturable): the f32 batch into self.out, the geometry rows beside it"""
-        L.check(self.lib.abc_build_scan_images(C.byref(self.d), stream_or_current(stream, self.out.device)), "build_scan_images")
+        """five launches in order on one stream (graph-capturable): the f32 batch into self.out, the geometry rows beside it; a
+        sixth, the stroke normaliser, when thin / stroke_radius / drop_isolated ask for it"""
+        stream = stream_or_current(stream, self.out.device)
+        L.check(self.lib.abc_build_scan_images(C.byref(self.d), stream), "build_scan_images")
+        if self.strokes is not None:
+            self.strokes.run(stream)
         return self.out
+
+    def stroke_stats(self):
+        """the normaliser's rows of the last run(): ops.StrokeNormalizer.stats() (synchronises)"""
+        if self.strokes is None:
+            raise ValueError("ScanBuilder: no stroke normalisation was asked for (thin, stroke_radius, drop_isolated)")
+        return self.strokes.stats()
 
     def geometry(self):
         """the geometry rows of the last run() as a structured numpy array [B] with the int32 fields L.SCAN_GEOM_COLUMNS (thr,

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -528,6 +529,75 @@ class MolBlockWriter:
                     raise L.AbcNetHipError("MolBlockWriter: image %d has status %s" % (b, name))
         raw = self.text[:off[self.B]].cpu().numpy().tobytes()
         return [None if s & L.MOL_EMPTY else raw[off[b]:off[b + 1]].decode("ascii") for b, s in enumerate(status)]
+
+
+def stroke_max_iter(thin, what="StrokeNormalizer"):
+    """abc_stroke_desc.max_iter of a `thin` argument: None or 0 -> 0 (no thinning), an int >= 1 -> that bound, "stable" -> until
+    stable"""
+    if thin is None:
+        return 0
+    if isinstance(thin, str):
+        if thin != "stable":
+            raise ValueError("%s: thin must be None, 0, an int >= 1 or 'stable', got %r" % (what, thin))
+        return L.STROKE_UNTIL_STABLE
+    if isinstance(thin, bool) or not isinstance(thin, int) or thin < 0:
+        raise ValueError("%s: thin must be None, 0, an int >= 1 or 'stable', got %r" % (what, thin))
+    return thin
+
+
+class StrokeNormalizer:
+    """stroke width of a {0, 1} batch normalised on the device (csrc/stroke.hip; the contract: include/abcnet_hip.h,
+    abc_stroke_desc): per image, delete the ink pixels without a neighbour (`drop_isolated`), peel the drawing toward its skeleton
+    by the Guo-Hall two-subiteration rule (`thin`: None or 0 for none, an int >= 1 for at most that many iterations, "stable" for
+    until nothing changes), then grow it back by a disk of `radius` 0 .. 3.  `images` is any f32 [B, 1, S, S] device tensor, S a
+    multiple of 8 up to L.STROKE_MAX_SIZE; the result goes to `out`, or over `images` when `out` is None.  `skip`: an int32 device
+    vector of B words (any stride: a column of a table does); an image whose word is non-zero is carried over bit for bit and
+    reported as skipped.  One launch, static buffers, graph-capture safe; stats() is the only host sync.  No CPU fallback."""
+
+    def __init__(self, images, out=None, thin=None, radius=0, drop_isolated=False, skip=None):
+        max_iter = stroke_max_iter(thin)
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= 3:
+            raise ValueError("StrokeNormalizer: radius must be an int in 0 .. 3, got %r" % (radius,))
+        if not torch.cuda.is_available():
+            raise L.AbcNetHipError("StrokeNormalizer needs an MI355X; abcnet_amd has no CPU fallback")
+        require_device_tensor(images, torch.float32, "StrokeNormalizer: images")
+        if images.dim() != 4 or images.shape[1] != 1 or images.shape[2] != images.shape[3] or images.shape[0] < 1:
+            raise L.AbcNetHipError("StrokeNormalizer: images %s is not [B, 1, S, S]" % (tuple(images.shape),))
+        B, S = int(images.shape[0]), int(images.shape[2])
+        if S < 8 or S % 8 or S > L.STROKE_MAX_SIZE:
+            raise ValueError("StrokeNormalizer: the size must be a multiple of 8 (8 .. %d), got %d" % (L.STROKE_MAX_SIZE, S))
+        if out is None:
+            out = images
+        else:
+            require_device_tensor(out, torch.float32, "StrokeNormalizer: out")
+            if tuple(out.shape) != tuple(images.shape) or out.device != images.device:
+                raise L.AbcNetHipError("StrokeNormalizer: out %s does not match images %s" % (tuple(out.shape), tuple(images.shape)))
+        if skip is not None:
+            if not (isinstance(skip, torch.Tensor) and skip.is_cuda and skip.dtype == torch.int32 and skip.device == images.device):
+                raise L.AbcNetHipError("StrokeNormalizer: skip must be an int32 device tensor (no CPU fallback)")
+            if skip.dim() != 1 or skip.shape[0] != B or (B > 1 and skip.stride(0) < 1):
+                raise L.AbcNetHipError("StrokeNormalizer: skip %s is not a vector of %d words" % (tuple(skip.shape), B))
+        self.lib = L.load()
+        self.images, self.out, self.skip, self.B, self.S = images, out, skip, B, S
+        self.thin, self.radius, self.drop_isolated = thin, radius, bool(drop_isolated)
+        self.stat = torch.zeros((B, len(L.STROKE_STAT_COLUMNS)), dtype=torch.int32, device=images.device)
+        d = L.StrokeDesc()
+        d.src, d.dst, d.stats = images.data_ptr(), out.data_ptr(), self.stat.data_ptr()
+        d.B, d.S, d.drop_isolated, d.max_iter, d.radius = B, S, int(self.drop_isolated), max_iter, radius
+        if skip is not None:
+            d.skip, d.skip_stride = skip.data_ptr(), max(1, int(skip.stride(0)))
+        self.d = d
+
+    def run(self, stream=None):
+        """one launch (graph-capturable): the normalised batch into self.out, the stats rows beside it"""
+        L.check(self.lib.abc_normalize_strokes(C.byref(self.d), stream_or_current(stream, self.out.device)), "normalize_strokes")
+        return self.out
+
+    def stats(self):
+        """the stats rows of the last run() as a structured numpy array [B] with the int32 fields L.STROKE_STAT_COLUMNS
+        (iterations, converged, ink_in, ink_out, skipped).  The only call here that synchronises."""
+        rows = np.ascontiguousarray(self.stat.cpu().numpy())
+        return rows.view(np.dtype([(c, np.int32) for c in L.STROKE_STAT_COLUMNS])).reshape(self.B)
 
 
 class _RecordScorer:

@@ -633,6 +633,53 @@ int abc_build_scan_images(const abc_scan_desc* d, abc_stream_t stream);
 /* sizeof(abc_scan_desc), for a binding's mirror struct (as abc_molblock_desc_size) */
 int abc_scan_desc_size(void);
 
+/* Stroke width of a binary drawing, normalised (csrc/stroke.hip): peel it toward its skeleton, then grow it
+ * back to a chosen width.  The augmentation the reference leaves commented out (utils.py:65-71: sm.thin, then sm.dilation with
+ * sm.disk(1)) as a device stage; synthetic._line's lines of 3 pixels are a one-pixel skeleton dilated by disk(1).
+ * src and dst are f32 [B][1][S][S] and may be the same buffer (otherwise they must not overlap).  A pixel is ink iff its value is
+ * > 0.5f (a NaN is paper); the output is exactly 0.0f or 1.0f; pixels outside the canvas are paper.  Per image, in this order:
+ *   despeckle  (drop_isolated 0 / 1) every ink pixel with no ink among its eight neighbours is deleted, all at once.
+ *   thin       max_iter 0: none; k >= 1: at most k iterations; ABC_STROKE_UNTIL_STABLE: until stable.  One iteration is
+ *              subiteration A, then subiteration B; each reads the state as it was before that subiteration and deletes all the
+ *              pixels it flags at once.  Neighbours clockwise from north: p2 = N, p3 = NE, p4 = E, p5 = SE, p6 = S, p7 = SW,
+ *              p8 = W, p9 = NW (north is the row above, west the column before).
+ *                C  = (!p2 & (p3 | p4)) + (!p4 & (p5 | p6)) + (!p6 & (p7 | p8)) + (!p8 & (p9 | p2))
+ *                N1 = (p9 | p2) + (p3 | p4) + (p5 | p6) + (p7 | p8),  N2 = (p2 | p3) + (p4 | p5) + (p6 | p7) + (p8 | p9)
+ *                N  = min(N1, N2),  m_A = (p6 | p7 | !p9) & p8,  m_B = (p2 | p3 | !p5) & p4
+ *              an ink pixel is deleted when C == 1, 2 <= N <= 3 and m == 0 (the Guo-Hall two-subiteration rule, the family of
+ *              skimage.morphology.thin; bit-identity with skimage is NOT claimed: none was at hand to check against).
+ *              Thinning stops after the first iteration that deletes nothing (that iteration is counted; converged = 1), and
+ *              after max_iter iterations (converged = 1 only if the last one deleted nothing).  max_iter 0: 0 iterations,
+ *              converged = 0.
+ *   dilate     radius 0 .. 3: a pixel is ink iff some ink pixel lies at an offset (dy, dx) from it with dy^2 + dx^2 <= radius^2
+ *              (the disk(r) footprints of 1, 5, 13 and 29 pixels), clipped at the canvas.
+ *   stats      int32 [B][ABC_STROKE_NSTAT] (abc_stroke_stat order): iterations, converged, ink_in (after the > 0.5 cut), ink_out,
+ *              skipped.
+ *   skip       optional (NULL: none): image b is skipped when skip[b * skip_stride] != 0 (skip_stride in int32 words, >= 1): its
+ *              pixels are carried from src to dst bit for bit -- in place, nothing is written: a NaN image stays NaN -- and its
+ *              stats row reads 0, 0, 0, 0, 1.
+ * One launch on the stream, one workgroup per image (the bit-packed image lives in LDS), no allocation, no sync, no parallel
+ * branch (capturable).  ABC_EINVAL: a null or misaligned pointer (src, dst: 16 bytes), B < 1, radius outside 0 .. 3,
+ * max_iter < -1, drop_isolated outside 0 / 1, S not a multiple of 8 in 8 .. ABC_STROKE_MAX_SIZE, src and dst overlapping
+ * without being equal. */
+enum { ABC_STROKE_UNTIL_STABLE = -1, ABC_STROKE_MAX_SIZE = 1024 };
+enum abc_stroke_stat { ABC_STROKE_ITERATIONS = 0, ABC_STROKE_CONVERGED, ABC_STROKE_INK_IN, ABC_STROKE_INK_OUT, ABC_STROKE_SKIPPED,
+                       ABC_STROKE_NSTAT };
+typedef struct abc_stroke_desc {
+    const float* src;               /* [B][1][S][S] f32, 16-byte aligned */
+    float* dst;                     /* [B][1][S][S] f32, 16-byte aligned; may equal src */
+    int32_t B, S;                   /* B >= 1; S a multiple of 8, 8 <= S <= ABC_STROKE_MAX_SIZE */
+    int32_t drop_isolated;          /* 0 / 1 */
+    int32_t max_iter;               /* 0, k >= 1 or ABC_STROKE_UNTIL_STABLE */
+    int32_t radius;                 /* 0 .. 3 */
+    int32_t skip_stride;            /* int32 words between the skip words of two images (>= 1 when skip is given) */
+    const int32_t* skip;            /* optional device words, image b at skip[b * skip_stride]; non-zero: leave the image alone */
+    int32_t* stats;                 /* out [B][ABC_STROKE_NSTAT] */
+} abc_stroke_desc;
+int abc_normalize_strokes(const abc_stroke_desc* d, abc_stream_t stream);
+/* sizeof(abc_stroke_desc), for a binding's mirror struct (as abc_scan_desc_size) */
+int abc_stroke_desc_size(void);
+
 /* The capacities of the SMILES decoder's stages below, the sizes of their kernels' LDS arrays (a launch with more is ABC_EINVAL):
  * cap_atoms of extract, assemble and graph score; bond peaks per image abc_extract_peaks expands; max_atoms and max_bonds of the
  * graph score; cap_atoms and max_atoms of the graph similarity. */
