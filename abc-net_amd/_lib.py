@@ -212,6 +212,12 @@ class GraphSimilarityDesc(C.Structure):
                 ("rows", vp), ("totals", vp), ("ids_out", vp)]
 
 
+class GraphIdentityDesc(C.Structure):
+    _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("rec_atoms", vp), ("rec_bonds", vp), ("rec_counts", vp),
+                ("n_valid", vp), ("B", i32), ("cap_atoms", i32), ("cap_mol_bonds", i32), ("max_atoms", i32), ("max_bonds", i32),
+                ("max_tries", i32), ("max_rounds", i32), ("rows", vp), ("totals", vp), ("map_out", vp)]
+
+
 class MolBlockDesc(C.Structure):
     _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp), ("B", i32), ("cap_atoms", i32),
                 ("cap_mol_bonds", i32), ("text", vp), ("index", vp), ("work", vp), ("cap_text", i64)]
@@ -236,6 +242,10 @@ GRAPH_SCORE_COLUMNS = ("counted", "none", "truncated", "exact", "atoms_equal", "
 GRAPH_SIM_COLUMNS = ("counted", "none", "truncated", "size_equal", "refine_equal", "dice_one", "atoms_pred", "atoms_true",
                      "envs_pred", "envs_true", "envs_common", "dice_q20")
 GRAPH_SIM_IDS = 2048    # ABC_SIM_IDS: ids_out is uint64 [B][2][GRAPH_SIM_IDS]
+# the ABC_IDENT_* columns of abc_graph_identity_desc.rows / .totals
+GRAPH_IDENT_COLUMNS = ("counted", "none", "truncated", "size_equal", "same", "different", "undecided", "levels", "tries",
+                       "backtracks", "rounds")
+IDENT_DEFAULT_TRIES, IDENT_DEFAULT_ROUNDS = 4096, 16384     # ABC_IDENT_DEFAULT_TRIES, ABC_IDENT_DEFAULT_ROUNDS
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
 SCAN_NPARAM = 2     # abc_scan_param: src_h, src_w
@@ -263,7 +273,7 @@ SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_scor
               (GraphSimilarityDesc, "abc_graph_similarity_desc_size"), (MolBlockDesc, "abc_molblock_desc_size"),
               (ScanDesc, "abc_scan_desc_size")]
 # (that list is pinned, name by name, by tests/test_decoder_contract_host.py) the self-sized descriptors since: checked the same way
-SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size")]
+SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "abc_graph_identity_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -346,6 +356,8 @@ SYMBOLS = {
     "abc_graph_score_desc_size": (C.c_int, []),
     "abc_graph_similarity_update": (C.c_int, [P(GraphSimilarityDesc), vp]),
     "abc_graph_similarity_desc_size": (C.c_int, []),
+    "abc_graph_identity_update": (C.c_int, [P(GraphIdentityDesc), vp]),
+    "abc_graph_identity_desc_size": (C.c_int, []),
     "abc_molblock_text_bytes": (i64, [P(MolBlockDesc)]),
     "abc_write_molblocks": (C.c_int, [P(MolBlockDesc), vp]),
     "abc_molblock_desc_size": (C.c_int, []),

@@ -24,12 +24,11 @@
 #include "capi_util.hpp"
 #include "block_scan.hpp"
 #include "mol_rows.hpp"
+#include "graph_ids.hpp"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int GT = 256;              // threads per workgroup
+constexpr int GT = 256;            // threads per workgroup
 constexpr int MAX_ATOMS = ABC_MAX_SIM_ATOMS;      // ids, sums and four fingerprint layers of both sides in 48 KB of LDS
 constexpr int RADIUS = 3;            // fingerprint layers 0 .. 3
 constexpr int MAX_ROUNDS = 64;       // refinement rounds of refine_equal
@@ -37,18 +36,6 @@ constexpr int FP = (RADIUS + 1) * MAX_ATOMS;
 constexpr int NCOL = ABC_SIM_NCOL;
 static_assert(FP == ABC_SIM_IDS, "ids_out holds one fingerprint per side");
 static_assert(MAX_ATOMS == 2 * GT, "the record scan numbers two atoms per thread");
-
-// the splitmix64 finaliser
-__device__ inline u64 mix(u64 x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
-// a wedge is a single bond (generate_smiles.py:58-68)
-__device__ inline int bond_class(int c) { return c == 5 || c == 6 ? 1 : (c >= 1 && c <= 4 ? c : 0); }
-__device__ inline u64 id0(int cls, int charge, u64 degree) { return mix(mix(mix((u64)(cls + 1)) + (u64)(long long)charge) + degree); }
 
 // this thread's share of the size of the multiset intersection of A and B (LDS lists; every read of the inner loops is a broadcast)
 __device__ inline int common_share(const u64* A, int nA, const u64* Bv, int nB, int tid) {

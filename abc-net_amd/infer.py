@@ -15,7 +15,8 @@ evaluate=True makes the step the loop body of the reference's src/test_accuracy.
 static device buffers and one more launch sequence after the NMS (ops.EvalTables) adds the batch to the per-class tables and the 17
 inference-flavour meters; evaluation() reads them.  score_graphs=True adds the score after assembly to that step: the assembled
 molecules against the annotated graphs (ops.GraphScore), accumulated like the tables; score_similarity=True the graded,
-position-free score of the same molecules (ops.GraphSimilarity).
+position-free score of the same molecules (ops.GraphSimilarity); score_identity=True the certain, position-free answer whether they ARE
+the annotated molecules (ops.GraphIdentity).
 """
 from __future__ import annotations
 
@@ -29,14 +30,14 @@ from .contract import HEADS, GraphRecords, alloc_targets, check_sparse_rasterize
 
 # the optional stages behind the NMS in launch order, each under the constructor flag that builds it
 STAGES = {"extractor": "extract", "assembler": "assemble", "texter": "molblocks", "scorer": "score_graphs",
-          "similarity": "score_similarity", "evaluator": "evaluate"}
+          "similarity": "score_similarity", "identity": "score_identity", "evaluator": "evaluate"}
 
 
 class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
                  assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
-                 score_similarity=False, molblocks=False):
+                 score_similarity=False, molblocks=False, score_identity=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -67,17 +68,21 @@ class InferenceRunner:
         graph records (ops.GraphSimilarity: the graded, position-free stand-in for cal_acc.py's fingerprint similarity), in the same
         captured graph after the assembler; both scores read the runner's one contract.GraphRecords (.records), which load_graphs
         fills; evaluation()["similarity"] holds the running result
+        score_identity (needs assemble=True and evaluate=True): the verified isomorphism test of the assembled molecules against the
+        same graph records (ops.GraphIdentity: `same` is certain and free of positions, between score_graphs' `exact` and
+        score_similarity's `refine_equal`), in the same captured graph after the similarity; it reads the runner's one
+        contract.GraphRecords too; evaluation()["identity"] holds the running result, `undecided` beside `same`
         molblocks (needs assemble=True): the mol block text of the assembled molecules (ops.MolBlockWriter), written in the same
         captured graph right after the assembler; molblocks() returns the strings that go into Chem.MolFromMolBlock -- two small
         copies per batch instead of molecules() and Molecule.molblock() per image on the host
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
-        from .ops import OMEGA_RULES, GraphAssembler, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, check_nms_heads
+        from .ops import OMEGA_RULES, GraphAssembler, GraphIdentity, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, check_nms_heads
         if omega_rule not in OMEGA_RULES:
             raise ValueError("InferenceRunner: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
         self.omega_rule = omega_rule
-        for flag, on in (("score_graphs", score_graphs), ("score_similarity", score_similarity)):
+        for flag, on in (("score_graphs", score_graphs), ("score_similarity", score_similarity), ("score_identity", score_identity)):
             if on and not (assemble and evaluate):
                 raise ValueError("InferenceRunner(%s=True) scores the assembled molecules of an evaluating step: it needs "
                                  "assemble=True and evaluate=True" % flag)
@@ -141,8 +146,9 @@ class InferenceRunner:
                 self.eval_targets = alloc_targets(eng.B, eng.h, eng.w, dev)
                 self.n_valid = torch.full((1,), eng.B, dtype=torch.int32, device=dev)
             self._build_evaluator(None)
-        self.records = self.scorer = self.similarity = None
-        self.wants_graph_records = bool(score_graphs or score_similarity)      # (one set, staged once per batch, whichever score reads it)
+        self.records = self.scorer = self.similarity = self.identity = None
+        # (one set, staged once per batch, whichever score reads it)
+        self.wants_graph_records = bool(score_graphs or score_similarity or score_identity)
         if self.wants_graph_records:
             with torch.cuda.device(dev):
                 self.records = GraphRecords(eng.B, 256, 256, dev)
@@ -150,6 +156,8 @@ class InferenceRunner:
                     self.scorer = GraphScore.from_assembler(self.assembler, radius=score_radius, n_valid=self.n_valid, records=self.records)
                 if score_similarity:
                     self.similarity = GraphSimilarity.from_assembler(self.assembler, n_valid=self.n_valid, records=self.records)
+                if score_identity:
+                    self.identity = GraphIdentity.from_assembler(self.assembler, n_valid=self.n_valid, records=self.records)
         self._stages = [attr for attr in STAGES if getattr(self, attr) is not None]
         self.use_graph = use_graph
         self._graph = None
@@ -246,20 +254,20 @@ class InferenceRunner:
     def evaluation(self):
         """the tables and meters accumulated since the last reset_evaluation() (ops.EvalTables.result(); host sync; needs evaluate=True)"""
         out = self._need("evaluator").result()
-        for attr, key in (("scorer", "molecules"), ("similarity", "similarity")):
+        for attr, key in (("scorer", "molecules"), ("similarity", "similarity"), ("identity", "identity")):
             if attr in self._stages:
                 out[key] = getattr(self, attr).result()
         return out
 
     def reset_evaluation(self):
         self._need("evaluator")
-        for attr in ("evaluator", "scorer", "similarity"):
+        for attr in ("evaluator", "scorer", "similarity", "identity"):
             if attr in self._stages:
                 getattr(self, attr).reset()
 
     def load_graphs(self, records):
-        """score_graphs=True or score_similarity=True: the graph records (raster.parse_graph) of the batch, n <= batch of them (the
-        rows past n get an empty record; n_valid says how many images count); staged once, whichever of the two read them"""
+        """score_graphs=True, score_similarity=True or score_identity=True: the graph records (raster.parse_graph) of the batch, n <= batch of them (the
+        rows past n get an empty record; n_valid says how many images count); staged once, whichever of them read them"""
         if self.records is None:
             self._need("scorer")
         with torch.cuda.device(self.dev):

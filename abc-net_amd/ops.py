@@ -723,6 +723,48 @@ class GraphSimilarity(_RecordScorer):
         return out
 
 
+class GraphIdentity(_RecordScorer):
+    """whether the assembled molecules ARE the annotated ones, free of positions and with certainty (csrc/graph_ident.hip,
+    abc_graph_identity_update): an individualise-and-refine isomorphism test of a GraphAssembler's molecule, read in place, against
+    the raster.parse_graph record, on the graphs GraphSimilarity defines (the algorithm: include/abcnet_hip.h; what of RDKit's
+    canonical SMILES it leaves out: DESIGN.md section 7).  `same` is a bijection VERIFIED atom by atom and bond by bond, `different`
+    an exhausted search or unequal sizes, `undecided` a budget that ran out -- reported, never hidden.  GraphScore's `exact` <=
+    `same` <= GraphSimilarity's `refine_equal`.  One launch, static buffers, graph-capture safe; the 11 columns
+    (L.GRAPH_IDENT_COLUMNS) of every image of the last call in .rows, their running sums in .totals; `result()` is the only host
+    sync."""
+
+    UPDATE, COLUMNS = "graph_identity_update", L.GRAPH_IDENT_COLUMNS
+    MAX_CAP_ATOMS, MAX_RECORD = L.MAX_SIM_ATOMS, (L.MAX_SIM_ATOMS, None)
+
+    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, max_atoms=256, max_bonds=256, n_valid=None, records=None,
+                 max_tries=None, max_rounds=None, witness=False):
+        """the rows, n_valid, max_atoms / max_bonds and records: as GraphSimilarity (records may also be a GraphScore or a
+        GraphSimilarity, whose records are taken).  max_tries: record-side individualisations per image, max_rounds: refinement rounds
+        per image, both sides -- None: L.IDENT_DEFAULT_TRIES / L.IDENT_DEFAULT_ROUNDS.  witness: keep the bijection of every `same`
+        image in .map (int32 [B, cap_atoms]: the ORIGINAL record atom index of every molecule atom, -1 everywhere else)"""
+        budgets = []
+        for name, v, default in (("max_tries", max_tries, L.IDENT_DEFAULT_TRIES), ("max_rounds", max_rounds, L.IDENT_DEFAULT_ROUNDS)):
+            v = default if v is None else int(v)
+            if not (1 <= v < 1 << 31):
+                raise ValueError("GraphIdentity: %s must be 1..2^31-1, got %d" % (name, v))
+            budgets.append(v)
+        self.max_tries, self.max_rounds = budgets
+        d = L.GraphIdentityDesc()
+        d.max_tries, d.max_rounds = budgets
+        records = records.records if isinstance(records, _RecordScorer) else records
+        self._bind(d, (mol_counts, mol_atoms, mol_bonds), n_valid, records, max_atoms, max_bonds)
+        self.map = torch.full((self.B, self.cap_atoms), -1, dtype=torch.int32, device=self.rows.device) if witness else None
+        d.map_out = L.ptr(self.map)
+
+    def result(self):
+        """dict (device sync): the 11 running totals under their names (int), "share_same" = same / counted, "share_undecided" =
+        undecided / counted (nan when nothing was counted), and "rows": the int32 [B, 11] table of the last call"""
+        out = self._totals()
+        for share, num in (("share_same", "same"), ("share_undecided", "undecided")):
+            out[share] = out[num] / out["counted"] if out["counted"] else float("nan")
+        return out
+
+
 def timed(stream, marks, label, flops, nbytes, fn, operand_bytes=None):
     """profile(): fn() between a HIP event pair recorded on `stream` (a torch stream, the one fn launches on); the pair and the
     launch's accounting go to `marks`.  Returns what fn returned."""

@@ -682,7 +682,7 @@ int abc_stroke_desc_size(void);
 
 /* The capacities of the SMILES decoder's stages below, the sizes of their kernels' LDS arrays (a launch with more is ABC_EINVAL):
  * cap_atoms of extract, assemble and graph score; bond peaks per image abc_extract_peaks expands; max_atoms and max_bonds of the
- * graph score; cap_atoms and max_atoms of the graph similarity. */
+ * graph score; cap_atoms and max_atoms of the graph similarity and of the graph identity. */
 enum abc_decoder_limit { ABC_MAX_CAP_ATOMS = 2048, ABC_MAX_BOND_PEAKS = 4096, ABC_MAX_SCORE_RECORD = 1024, ABC_MAX_SIM_ATOMS = 512 };
 
 /* Candidate extraction for the SMILES decoder (img2smiles2.py:113-191; replaces its per-pixel .cpu().item() loops):
@@ -890,6 +890,59 @@ typedef struct abc_graph_similarity_desc {
 int abc_graph_similarity_update(const abc_graph_similarity_desc* d, abc_stream_t stream);
 /* sizeof(abc_graph_similarity_desc), for a binding's mirror struct (as abc_graph_score_desc_size) */
 int abc_graph_similarity_desc_size(void);
+
+/* The CERTAIN score after assembly, free of positions: is the assembled molecule the annotated one?  An individualise-and-refine
+ * isomorphism test per image between ABC_GS_EXACT (the positional lower bound) and ABC_SIM_REFINE_EQUAL (the upper one).  One
+ * workgroup per image, uint64 wrapping arithmetic only, no allocation, no sync (csrc/graph_ident.hip; its executable form is
+ * tests/graphident_oracle.py).  The graphs -- atoms, classes, charges, valid rows, order classes, multigraph -- mix, id_0 and the
+ * round id_r are abc_graph_similarity_update's, word for word; the rows and records are read the same way.
+ *   sizes     the atom counts and the valid-bond counts are equal (size_equal), else `different`;
+ *   indiv     indiv(id, level) = mix(mix(id) + 0x9E3779B97F4A7C15 (level + 1)), the id of the atom individualised at `level`;
+ *   molecule  walks ONE path to a discrete colouring.  Per level: rounds (r counts on through the levels) until one no longer
+ *             raises the number of distinct ids -- that round is counted, a level has at most n; the level's round count, the sum
+ *             of mix(id) over the atoms and the class count are recorded; not discrete: the cell is the non-singleton class with
+ *             the least id VALUE, its lowest-index atom v gets id[v] = indiv(id[v], level), and the next level starts (its class
+ *             count before the first round is taken as the recorded one plus 1);
+ *   record    is searched depth first doing what the molecule recorded: per level the same number of rounds, after which class
+ *             count and sum must equal the record's (a mismatch proves the branch wrong, the ids being functions of structure
+ *             alone); the candidates of a level are the record atoms whose id is the recorded cell id, in index order, each
+ *             individualised as above (a try); a failed or exhausted level is a backtrack: one level up, the ids rebuilt by
+ *             replaying the choices from id_0;
+ *   leaf      both colourings discrete: atoms are mapped by equal id, then VERIFIED -- class and charge of every atom, and the
+ *             multiset of (mapped end, mapped end, order class) of the molecule's valid rows against the record's, by counting.
+ *             Verified: `same`, certain whatever the hashes did.  Not verified: the search goes on.  Exhausted: `different`;
+ *   budgets   max_rounds is checked before every round of either side (replays included), max_tries before every try; running out
+ *             is `undecided`.  0 selects the defaults below; every loop is bounded by n, a budget or a capacity.
+ *             The defaults were chosen with the oracle.  The largest seen on any test fixture: tries = 254 and rounds = 1018 (170
+ *             disjoint C-C-C, 510 atoms; a 512-carbon chain takes 1008 rounds, a 512-carbon ring 988).  Every pair of the trained
+ *             fixture under both omega rules stays at 2 levels, 0 tries and 7 rounds (profiles/r15_identity.md).
+ * rows[b] (overwritten by every call; all zero for b >= *n_valid) and totals (+= the column sums, 64-bit integer atomics) have the
+ * ABC_IDENT_* columns: levels = the molecule's individualisations, tries, backtracks, rounds (both sides) = the work of the image.
+ * An ABC_MOL_EMPTY image adds counted and none, and nothing else; of every other counted image exactly one of same, different and
+ * undecided is 1 (a size mismatch is `different` with zero work).  Two sides without atoms are `same`.
+ * map_out (optional) is the WITNESS: for a `same` image, the ORIGINAL record atom index of every molecule atom; -1 in every other
+ * word of the [B][cap_atoms] table, which every launch writes entirely. */
+enum { ABC_IDENT_DEFAULT_TRIES = 4096, ABC_IDENT_DEFAULT_ROUNDS = 16384 };
+enum { ABC_IDENT_COUNTED = 0, ABC_IDENT_NONE, ABC_IDENT_TRUNCATED, ABC_IDENT_SIZE_EQUAL, ABC_IDENT_SAME, ABC_IDENT_DIFFERENT,
+       ABC_IDENT_UNDECIDED, ABC_IDENT_LEVELS, ABC_IDENT_TRIES, ABC_IDENT_BACKTRACKS, ABC_IDENT_ROUNDS,
+       ABC_IDENT_NCOL = 11 };
+typedef struct abc_graph_identity_desc {
+    const int32_t* mol_counts;   /* [B][4]                 as abc_graph_score_desc */
+    const int32_t* mol_atoms;    /* [B][cap_atoms][5] */
+    const int32_t* mol_bonds;    /* [B][cap_mol_bonds][4] */
+    const int32_t* rec_atoms;    /* [B][max_atoms][4] */
+    const int32_t* rec_bonds;    /* [B][max_bonds][3] */
+    const int32_t* rec_counts;   /* [2][B] */
+    const int32_t* n_valid;      /* optional DEVICE int32, as abc_graph_score_desc */
+    int32_t B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds;   /* cap_atoms 1..512, max_atoms 1..512; the bond capacities >= 1 */
+    int32_t max_tries, max_rounds;   /* >= 1, or 0: ABC_IDENT_DEFAULT_TRIES / ABC_IDENT_DEFAULT_ROUNDS; negative: ABC_EINVAL */
+    int32_t* rows;               /* [B][ABC_IDENT_NCOL] */
+    uint64_t* totals;            /* [ABC_IDENT_NCOL] */
+    int32_t* map_out;            /* optional: [B][cap_atoms], the witness */
+} abc_graph_identity_desc;
+int abc_graph_identity_update(const abc_graph_identity_desc* d, abc_stream_t stream);
+/* sizeof(abc_graph_identity_desc), for a binding's mirror struct (as abc_graph_similarity_desc_size) */
+int abc_graph_identity_desc_size(void);
 
 /* The mol block text of the assembled molecules (generate_smiles.py:18-105), written on the device from the rows of
  * abc_assemble_graphs, read in place: the bytes that go into Chem.MolFromMolBlock, one copy per batch (csrc/molblock.hip; the

@@ -14,6 +14,12 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            refine_equal and exact (InferenceRunner(score_graphs=True, score_similarity=True), one step, csrc/graph_sim.hip), and
            step() with score_graphs=True against the same with score_similarity=True as well (as `step`)
 
+  identity abc_graph_identity_update alone beside abc_graph_similarity_update (as `launch`); the fixture's verified `same` between
+           `exact` and `refine_equal` with `undecided` and the largest levels / tries / rounds of an image
+           (InferenceRunner(score_graphs=True, score_similarity=True, score_identity=True), one step, csrc/graph_ident.hip); and
+           step() with score_graphs=True, score_similarity=True against the same with score_identity=True as well (as `text`'s
+           step: eight alternated blocks, the spread of the block medians)
+
   text     the mol block text written on the device (csrc/molblock.hip, InferenceRunner(molblocks=True)): molecules() plus
            Molecule.molblock() of every image on the host against molblocks() (wall time per batch, alternated, median of the
            repetitions), abc_write_molblocks alone (its two launches, as `launch`), the bytes molblocks() copies, and step() with
@@ -25,7 +31,7 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,text] [--omega-rule raw]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text] [--omega-rule raw]
 """
 import argparse
 import json
@@ -70,9 +76,9 @@ def runners(m, x):
     return out
 
 
-def scoring_runners(m, x, notes, similarity=False):
-    """the evaluating step without and with the score after assembly (similarity: and with the environment similarity on top);
-    targets drawn once from the annotation records"""
+def scoring_runners(m, x, notes, similarity=False, identity=False):
+    """the evaluating step without and with the score after assembly (similarity: and with the environment similarity on top;
+    identity: and with the verified isomorphism test on top of that); targets drawn once from the annotation records"""
     from abcnet_amd.raster import TargetRasterizer, parse_graph, parse_record
     recs = [parse_record(a, b, h=S // 4) for a, b in notes]
     graphs = [parse_graph(a, b, h=S // 4) for a, b in notes]
@@ -80,6 +86,9 @@ def scoring_runners(m, x, notes, similarity=False):
     forms = [("assemble+evaluate", {}), ("assemble+evaluate+score", dict(score_graphs=True, score_radius=0))]
     if similarity:
         forms.append(("assemble+evaluate+score+similarity", dict(score_graphs=True, score_radius=0, score_similarity=True)))
+    if identity:
+        forms.append(("assemble+evaluate+score+similarity+identity",
+                      dict(score_graphs=True, score_radius=0, score_similarity=True, score_identity=True)))
     for name, kw in forms:
         r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, evaluate=True, omega_rule=RULE, **kw)
         rz = TargetRasterizer(B, S // 4, targets=r.targets, sparse=True)
@@ -87,7 +96,7 @@ def scoring_runners(m, x, notes, similarity=False):
         rz.load(recs)
         rz.run()
         r.load_batch(x.to("cuda"))
-        if r.scorer is not None or r.similarity is not None:
+        if r.records is not None:
             r.load_graphs(graphs)
         out[name] = r
     return out
@@ -284,6 +293,55 @@ def part_similarity(rs, steps, warmup, iters=200):
               diff_name="similarity_minus_score_ms")
 
 
+def part_identity(rs, steps, warmup, iters=200):
+    from abcnet_amd._lib import GRAPH_IDENT_COLUMNS
+    with_id, without = "assemble+evaluate+score+similarity+identity", "assemble+evaluate+score+similarity"
+    r = rs[with_id]
+    ident, sim = r.identity, r.similarity
+    keep = ident.totals.clone(), sim.totals.clone()
+    us = [(launch_us(ident.run, iters), launch_us(sim.run, iters)) for _ in range(3)]      # the two launches alternated, three figures each
+    ident.totals.copy_(keep[0])
+    sim.totals.copy_(keep[1])
+    emit({"part": "identity", "what": "launch", "batch": B, "us_per_launch": [round(a, 2) for a, _ in us],
+          "graph_similarity_us_per_launch": [round(b, 2) for _, b in us],
+          "method": "device events around %d back-to-back launches (launch gaps included)" % iters})
+    r.reset_evaluation()
+    r.step()
+    ev = r.evaluation()
+    res = ev["identity"]
+    out = {"part": "identity", "what": "fixture", "images": res["counted"], "exact": ev["molecules"]["exact"],
+           "refine_equal": ev["similarity"]["refine_equal"], "dice_one": ev["similarity"]["dice_one"]}
+    out.update({k: res[k] for k in GRAPH_IDENT_COLUMNS[1:]})
+    rows = res["rows"]
+    out.update({"max_" + k: int(rows[:, GRAPH_IDENT_COLUMNS.index(k)].max()) for k in ("levels", "tries", "backtracks", "rounds")})
+    out["ordered"] = bool(out["exact"] <= res["same"] <= out["refine_equal"])
+    emit(out)
+    r.reset_evaluation()
+    pair = {k: rs[k] for k in (without, with_id)}
+    for q in pair.values():
+        for _ in range(warmup):
+            q.step()
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in pair}
+    for blk in range(8):
+        for name, q in (pair.items() if blk % 2 == 0 else reversed(list(pair.items()))):
+            ev = []
+            for _ in range(max(steps // 8, 1)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                q.step()
+                e1.record()
+                ev.append((e0, e1))
+            torch.cuda.synchronize()
+            blocks[name].append(statistics.median(a.elapsed_time(b) for a, b in ev))
+    med = {k: statistics.median(v) for k, v in blocks.items()}
+    for k, v in blocks.items():
+        emit({"part": "identity", "what": "step", "form": k, "batch": B, "size": S, "blocks": len(v), "ms_per_step_median": round(med[k], 4),
+              "block_medians_min_max": [round(min(v), 4), round(max(v), 4)],
+              "block_spread_percent": round(100 * (max(v) - min(v)) / med[k], 3)})
+    emit({"part": "identity", "identity_minus_similarity_ms": round(med[with_id] - med[without], 4)})
+
+
 def part_graphs_device(r):
     """the device's count of the same thing: the scorer's rows of the last step (radius 0)"""
     from abcnet_amd._lib import GRAPH_SCORE_COLUMNS
@@ -328,7 +386,9 @@ def main():
     m = model()
     x, notes = drawn_molecules(B, S, seed=777)
     rs = runners(m, x) if set(parts) & {"step", "launch", "host"} else {}
-    ss = scoring_runners(m, x, notes, similarity="similarity" in parts) if set(parts) & {"graphs", "score", "similarity"} else {}
+    ss = {}
+    if set(parts) & {"graphs", "score", "similarity", "identity"}:
+        ss = scoring_runners(m, x, notes, similarity=bool(set(parts) & {"similarity", "identity"}), identity="identity" in parts)
     for r in list(rs.values()) + list(ss.values()):
         for _ in range(2):
             r.step()
@@ -346,6 +406,8 @@ def main():
         part_score({k: ss[k] for k in ("assemble+evaluate", "assemble+evaluate+score")}, a.steps, a.warmup)
     if "similarity" in parts:
         part_similarity(ss, a.steps, a.warmup)
+    if "identity" in parts:
+        part_identity(ss, a.steps, a.warmup)
     if "text" in parts:
         part_text(m, x, a.steps, a.warmup)
 
