@@ -229,6 +229,11 @@ class ScanDesc(C.Structure):
                 ("box", vp), ("geom", vp)]
 
 
+class ScanCleanDesc(C.Structure):
+    _fields_ = [("scratch", vp), ("stats", vp), ("labels_out", vp), ("keep_out", vp), ("cell", i32), ("min_ink", i32),
+                ("keep_q8", i32)]
+
+
 class StrokeDesc(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("B", i32), ("S", i32), ("drop_isolated", i32), ("max_iter", i32), ("radius", i32),
                 ("skip_stride", i32), ("skip", vp), ("stats", vp)]
@@ -254,6 +259,10 @@ SCAN_CONSTANT, SCAN_BAD_PARAMS = 1, 2           # abc_scan_status
 SCAN_NBOX = 8       # ABC_SCAN_NBOX
 # the abc_scan_geom columns of abc_scan_desc.geom
 SCAN_GEOM_COLUMNS = ("thr", "inverted", "status", "y0", "x0", "bh", "bw", "rows", "cols", "ddx", "ddy", "ink")
+SCAN_NO_COMPONENT, SCAN_CLEAN_FAILED = 4, 8     # abc_scan_clean_status: further values of the geometry status column
+SCAN_CLEAN_CELLS = (8, 16, 32, 64)              # the values of abc_scan_clean_desc.cell
+# the abc_scan_clean_stat columns of abc_scan_clean_desc.stats
+SCAN_CLEAN_COLUMNS = ("components", "kept", "ink_kept", "ink_dropped", "heaviest", "occupied_cells")
 STROKE_UNTIL_STABLE = -1    # ABC_STROKE_UNTIL_STABLE: abc_stroke_desc.max_iter
 STROKE_MAX_SIZE = 1024      # ABC_STROKE_MAX_SIZE: the largest canvas abc_normalize_strokes holds in LDS
 # the abc_stroke_stat columns of abc_stroke_desc.stats
@@ -273,7 +282,8 @@ SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_scor
               (GraphSimilarityDesc, "abc_graph_similarity_desc_size"), (MolBlockDesc, "abc_molblock_desc_size"),
               (ScanDesc, "abc_scan_desc_size")]
 # (that list is pinned, name by name, by tests/test_decoder_contract_host.py) the self-sized descriptors since: checked the same way
-SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "abc_graph_identity_desc_size")]
+SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "abc_graph_identity_desc_size"),
+                    (ScanCleanDesc, "abc_scan_clean_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -344,6 +354,9 @@ SYMBOLS = {
     "abc_build_images": (C.c_int, [P(ImageDesc), vp]),
     "abc_build_scan_images": (C.c_int, [P(ScanDesc), vp]),
     "abc_scan_desc_size": (C.c_int, []),
+    "abc_build_scan_images_clean": (C.c_int, [P(ScanDesc), P(ScanCleanDesc), vp]),
+    "abc_scan_clean_desc_size": (C.c_int, []),
+    "abc_scan_clean_scratch_bytes": (i64, [i32, i32, i32, i32]),
     "abc_normalize_strokes": (C.c_int, [P(StrokeDesc), vp]),
     "abc_stroke_desc_size": (C.c_int, []),
     "abc_metrics_blocks": (C.c_int, [P(MetricsDesc)]),

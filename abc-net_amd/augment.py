@@ -14,6 +14,8 @@ A third way to build the input, "scan": ScanBuilder takes raw grey scans of any 
 offline Otsu step and utils_for_test.py's loader do between them, plus the crop and the fit a scan needs) and csrc/scan.hip
 thresholds, crops, fits and writes them; otsu_threshold and fit_scan below are the pure host mirrors of its rules.  On request it
 appends ops.StrokeNormalizer (csrc/stroke.hip) as a sixth launch: speckles dropped, strokes thinned and grown back to one width.
+With clean_cell set it drops dirt and text far from the drawing before the crop (abc_build_scan_images_clean: connected components
+over a coarse grid of cells, weighed by their ink).
 """
 from __future__ import annotations
 
@@ -260,12 +262,37 @@ class ScanBuilder:
     geometry status is non-zero (a CONSTANT image stays blank, a BAD_PARAMS one keeps its NaN); stroke_stats() returns its rows.
     The geometry rows do not change: `ink` stays the source's count.  size is then at most L.STROKE_MAX_SIZE.  Recommended where it
     is used: thin=1, stroke_radius=1, the one setting of twelve that beat the unnormalised scans under both candidate rules in
-    profiles/r14_stroke.md (synthetic scans again, and by little); thinning to the skeleton turns a solid wedge into a line."""
+    profiles/r14_stroke.md (synthetic scans again, and by little); thinning to the skeleton turns a solid wedge into a line.
+
+    clean_cell, clean_min_ink, clean_keep: the cell component filter (the contract: include/abcnet_hip.h, abc_scan_clean_desc), off
+    by default (clean_cell=None is the object above, calling abc_build_scan_images).  With clean_cell in 8 / 16 / 32 / 64, run()
+    calls abc_build_scan_images_clean instead: ink closer than about one cell belongs together, each group of cells is weighed
+    by its ink, and only the groups with at least clean_min_ink ink pixels and at least clean_keep / 256 of the heaviest group's
+    weight are kept; the box and the resample read ink from kept cells only, so a speck of dirt or a caption far from the
+    drawing no longer sets the crop.  An image with nothing kept is blank with status L.SCAN_NO_COMPONENT.  clean_stats() returns
+    the rows of L.SCAN_CLEAN_COLUMNS; debug_cells=True also keeps every cell's label and keep bit for clean_cells().  The stroke
+    launch, when asked for, still follows and still skips rows with non-zero status.  Recommended where scans carry specks of
+    dirt: clean_cell=16, clean_min_ink=64, clean_keep=0, the setting of profiles/r16_scan_clean.md (synthetic scans made dirty
+    on the host; no real scan was available) that dropped every added speck, took ink from no drawing and had the best mean
+    similarity under the `peaks` rule; it keeps a caption of letter-sized blobs.  clean_keep=256 (the heaviest group alone) is
+    NOT recommended: those drawings are several groups at every cell size tried (a label, a second fragment), and it took ink
+    from all of them."""
 
     def __init__(self, batch, size, out=None, max_src=(1024, 1024), margin=None, cover=None, polarity="dark", device="cuda",
-                 thin=None, stroke_radius=None, drop_isolated=False):
+                 thin=None, stroke_radius=None, drop_isolated=False, clean_cell=None, clean_min_ink=0, clean_keep=0,
+                 debug_cells=False):
         if polarity not in POLARITIES:
             raise ValueError("ScanBuilder: polarity must be 'dark', 'light' or 'auto', got %r" % (polarity,))
+        if clean_cell is None:
+            if clean_min_ink or clean_keep or debug_cells:
+                raise ValueError("ScanBuilder: clean_min_ink, clean_keep and debug_cells need clean_cell (one of %s)" % (L.SCAN_CLEAN_CELLS,))
+        else:
+            if isinstance(clean_cell, bool) or clean_cell not in L.SCAN_CLEAN_CELLS:
+                raise ValueError("ScanBuilder: clean_cell must be one of %s or None, got %r" % (L.SCAN_CLEAN_CELLS, clean_cell))
+            if int(clean_min_ink) != clean_min_ink or clean_min_ink < 0 or clean_min_ink >= 2 ** 31:
+                raise ValueError("ScanBuilder: clean_min_ink is a count of ink pixels, an integer >= 0, got %r" % (clean_min_ink,))
+            if int(clean_keep) != clean_keep or not 0 <= clean_keep <= 256:
+                raise ValueError("ScanBuilder: clean_keep is in 1 / 256 of the heaviest component, 0 .. 256, got %r" % (clean_keep,))
         normalise = stroke_max_iter(thin, "ScanBuilder") != 0 or stroke_radius is not None or bool(drop_isolated)
         if normalise and int(size) > L.STROKE_MAX_SIZE:
             raise ValueError("ScanBuilder: thin / stroke_radius / drop_isolated need size <= %d (the normaliser holds an image in "
@@ -312,7 +339,26 @@ class ScanBuilder:
         d.B, d.S, d.margin, d.cover_q8, d.polarity = batch, S, margin, cover, POLARITIES[polarity]
         d.hist, d.box, d.geom = self.hist.data_ptr(), self.box.data_ptr(), self.geom.data_ptr()
         self.d = d
-        # the sixth launch, when asked for: in place over out, the geometry status column as its skip words
+        # the cell component filter, when asked for: its descriptor, its scratch and its outputs
+        self.clean = None
+        if clean_cell is not None:
+            cell = int(clean_cell)
+            self.cap_cells = (-(-max_h // cell), -(-self.pitch // cell))
+            nbytes = self.lib.abc_scan_clean_scratch_bytes(batch, max_h, self.pitch, cell)
+            if nbytes < 0:
+                raise L.AbcNetHipError("scan_clean_scratch_bytes: %s" % self.lib.abc_last_error().decode())
+            self.clean_scratch = torch.zeros(nbytes // 4, dtype=torch.int32, device=dev)
+            self.clean_rows = torch.zeros((batch, len(L.SCAN_CLEAN_COLUMNS)), dtype=torch.int32, device=dev)
+            q = L.ScanCleanDesc()
+            q.scratch, q.stats = self.clean_scratch.data_ptr(), self.clean_rows.data_ptr()
+            q.cell, q.min_ink, q.keep_q8 = cell, int(clean_min_ink), int(clean_keep)
+            self.cell_labels = self.cell_keep = None
+            if debug_cells:
+                self.cell_labels = torch.zeros((batch,) + self.cap_cells, dtype=torch.int32, device=dev)
+                self.cell_keep = torch.zeros((batch,) + self.cap_cells, dtype=torch.uint8, device=dev)
+                q.labels_out, q.keep_out = self.cell_labels.data_ptr(), self.cell_keep.data_ptr()
+            self.clean = q
+        # the last launch, when asked for: in place over out, the geometry status column as its skip words
         self.strokes = None
         if normalise:
             self.strokes = StrokeNormalizer(out, thin=thin, radius=0 if stroke_radius is None else stroke_radius,
@@ -342,12 +388,33 @@ class ScanBuilder:
 
     def run(self, stream=None):
         """five launches in order on one stream (graph-capturable): the f32 batch into self.out, the geometry rows beside it; a
-        sixth, the stroke normaliser, when thin / stroke_radius / drop_isolated ask for it"""
+        sixth, the stroke normaliser, when thin / stroke_radius / drop_isolated ask for it.  With clean_cell set the five are the
+        nine of abc_build_scan_images_clean, the same number whatever the images hold"""
         stream = stream_or_current(stream, self.out.device)
-        L.check(self.lib.abc_build_scan_images(C.byref(self.d), stream), "build_scan_images")
+        if self.clean is None:
+            L.check(self.lib.abc_build_scan_images(C.byref(self.d), stream), "build_scan_images")
+        else:
+            L.check(self.lib.abc_build_scan_images_clean(C.byref(self.d), C.byref(self.clean), stream), "build_scan_images_clean")
         if self.strokes is not None:
             self.strokes.run(stream)
         return self.out
+
+    def clean_stats(self):
+        """the cleaning rows of the last run() as a structured numpy array [B] with the int32 fields L.SCAN_CLEAN_COLUMNS
+        (components, kept, ink_kept, ink_dropped, heaviest, occupied_cells); all zeros for a CONSTANT or BAD_PARAMS image
+        (synchronises)"""
+        if self.clean is None:
+            raise ValueError("ScanBuilder: no cleaning was asked for (clean_cell)")
+        rows = np.ascontiguousarray(self.clean_rows.cpu().numpy())
+        return rows.view(np.dtype([(c, np.int32) for c in L.SCAN_CLEAN_COLUMNS])).reshape(self.B)
+
+    def clean_cells(self):
+        """(labels int32, keep uint8), each [B, cap_ch, cap_cw] over the capacity grid of cells, of the last run(): an occupied
+        cell's label is the smallest cy * cap_cw + cx of its component, every other cell holds -1; keep is 1 for a kept occupied
+        cell (synchronises).  Needs debug_cells=True"""
+        if self.clean is None or self.cell_labels is None:
+            raise ValueError("ScanBuilder: clean_cells() needs clean_cell and debug_cells=True")
+        return self.cell_labels.cpu().numpy(), self.cell_keep.cpu().numpy()
 
     def stroke_stats(self):
         """the normaliser's rows of the last run(): ops.StrokeNormalizer.stats() (synchronises)"""

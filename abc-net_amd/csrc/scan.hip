@@ -13,6 +13,8 @@
 //   fit+write  one thread = 8 consecutive canvas pixels (two 16-byte stores): every workgroup derives the geometry from the
 //              box words, counts ink over each pixel's source box from aligned 8-byte row loads; workgroup 0 of an image
 //              writes its geometry row
+// abc_build_scan_images_clean (the contract: abc_scan_clean_desc) puts four launches between the threshold and the box -- cells,
+// union, flatten, decide, below -- and launches the box and fit+write kernels with a mask argument: nine launches, the same way.
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
@@ -164,7 +166,21 @@ __device__ inline uint32_t ink_bits(uint32_t w, int thr, int inv) {
     return m;
 }
 
-__global__ __launch_bounds__(STHR) void scan_box_kernel(const abc_scan_desc d) {
+// what the masked box and write passes of abc_build_scan_images_clean read beside abc_scan_desc: one keep byte per cell of the
+// capacity grid (image b at keep + b * stride, cell (cy, cx) at cy * cap_cw + cx), cells of 1 << shift pixels
+struct scan_mask {
+    const uint8_t* keep;
+    int64_t stride;
+    int cap_cw, shift;
+};
+
+__device__ inline const scan_mask& mask_of(const scan_mask& k) { return k; }
+
+// launched with d alone this is the box pass of abc_build_scan_images as it always was (the same kernel arguments, the same code);
+// launched with d and a scan_mask it drops the ink outside kept cells
+template <class... M>
+__global__ __launch_bounds__(STHR) void scan_box_kernel(const abc_scan_desc d, const M... mk) {
+    constexpr bool MASKED = sizeof...(M) != 0;
     __shared__ int red[4][STHR / 64];
     const int b = blockIdx.y;
     int32_t* box = d.box + (size_t)b * ABC_SCAN_NBOX;
@@ -186,6 +202,14 @@ __global__ __launch_bounds__(STHR) void scan_box_kernel(const abc_scan_desc d) {
         for (int k = 0; k < 4; ++k) m |= ink_bits(q[k], thr, inv) << (4 * k);
         const int valid = sw - 16 * v;      // >= 1
         if (valid < 16) m &= (1u << valid) - 1u;
+        if constexpr (MASKED) {
+            if (m) {      // (a 16-byte vector lies in one cell, or at cell 8 in the two cells 2 v and 2 v + 1 < cap_cw = pitch / 8)
+                const scan_mask& k = mask_of(mk...);
+                const uint8_t* kr = k.keep + (size_t)b * k.stride + (size_t)((r0 + y) >> k.shift) * k.cap_cw;
+                if (k.shift == 3) m &= (kr[2 * v] ? 0x00FFu : 0u) | (kr[2 * v + 1] ? 0xFF00u : 0u);
+                else if (!kr[(16 * v) >> k.shift]) m = 0u;
+            }
+        }
         if (m) {
             ymin = min(ymin, r0 + y);
             ymax = max(ymax, r0 + y);
@@ -226,7 +250,11 @@ __host__ __device__ inline void scan_fit(int bh, int bw, int S, int margin, int&
     cols = c < 1 ? 1 : (int)c;
 }
 
-__global__ __launch_bounds__(STHR) void scan_write_kernel(const abc_scan_desc d) {
+// launched with d alone this is the fit+write pass of abc_build_scan_images as it always was; launched with d and a scan_mask it
+// counts n over the ink of kept cells only
+template <class... M>
+__global__ __launch_bounds__(STHR) void scan_write_kernel(const abc_scan_desc d, const M... mk) {
+    constexpr bool MASKED = sizeof...(M) != 0;
     const int b = blockIdx.y, S = d.S;
     const int npix = S * S;                                   // (S <= 8192: pixel indices fit 32 bits)
     const int32_t* box = d.box + (size_t)b * ABC_SCAN_NBOX;
@@ -294,6 +322,11 @@ __global__ __launch_bounds__(STHR) void scan_write_kernel(const abc_scan_desc d)
                     if (w != have) {      // (8 w <= xb < src_w <= pitch, a multiple of 16: the word lies inside the row)
                         const uint64_t t = row[w];
                         bits = ink_bits((uint32_t)t, thr, inv) | (ink_bits((uint32_t)(t >> 32), thr, inv) << 4);
+                        if constexpr (MASKED) {      // (cells are multiples of 8 wide: an aligned 8-byte word lies in one cell)
+                            const scan_mask& k = mask_of(mk...);
+                            const uint8_t* kr = k.keep + (size_t)b * k.stride + (size_t)(yy >> k.shift) * k.cap_cw;
+                            if (!kr[(8 * w) >> k.shift]) bits = 0u;
+                        }
                         have = w;
                     }
                     const int lo = max(xa[j] - 8 * w, 0), hi = min(xb[j] - 8 * w, 7);
@@ -312,11 +345,271 @@ __global__ __launch_bounds__(STHR) void scan_write_kernel(const abc_scan_desc d)
     o[1] = (f32x4){y[4], y[5], y[6], y[7]};
 }
 
+// ---- the cell component filter of abc_build_scan_images_clean: four launches between the threshold and the masked box ----
+//   cells      grid as the histogram: ink per cell of 64 source rows in LDS, each cell of the capacity grid stored once (its ink,
+//              itself as its parent when occupied, a zero weight): the sequence resets the whole of its scratch here
+//   union      one thread per cell of the capacity grid: union-find, the larger root hung under the smaller by compare-and-swap
+//   flatten    one thread per cell: parent <- root, the cell's ink added to the root's weight (integer atomics, one per root and wave)
+//   decide     one 1024-thread workgroup per image: H, the keep byte of every cell, the stats row, the debug slices, the status
+// then the masked box and the masked fit+write.  Every loop that follows parents has the static bound ncap (the cells of the
+// capacity grid); parents only decrease, so a correct run cannot reach it; a run that does sets the fail word and never spins.
+constexpr int CTHR = 256;          // threads per workgroup of the union and flatten launches
+constexpr int DTHR = 1024;         // threads of the decide launch's one workgroup per image
+constexpr int CELL_LDS = 4096;     // cells of 64 source rows: (64 / cell) * ceil(4096 / cell) <= 8 * 512
+// the words of an image's meta block in the scratch
+enum { META_FAIL = 0, META_NWORD = 4 };
+
+// an image's slice of abc_scan_clean_desc.scratch: ink, parent and weight per cell, one keep byte per cell, the meta words
+struct clean_view {
+    uint32_t* ink;
+    int* parent;
+    uint32_t* weight;
+    uint8_t* keep;
+    int* meta;
+};
+
+__host__ __device__ inline int64_t clean_keep_words(int64_t ncap) { return (ncap + 3) / 4; }
+// int32 words of scratch per image, a multiple of 4 (16 bytes)
+__host__ __device__ inline int64_t clean_image_words(int64_t ncap) {
+    return (3 * ncap + clean_keep_words(ncap) + META_NWORD + 3) / 4 * 4;
+}
+
+__device__ inline clean_view clean_slice(void* scratch, int b, int ncap) {
+    int32_t* w = (int32_t*)scratch + (size_t)b * clean_image_words(ncap);
+    clean_view v;
+    v.ink = (uint32_t*)w;
+    v.parent = w + ncap;
+    v.weight = (uint32_t*)(w + 2 * (size_t)ncap);
+    v.keep = (uint8_t*)(w + 3 * (size_t)ncap);
+    v.meta = w + 3 * (size_t)ncap + clean_keep_words(ncap);
+    return v;
+}
+
+// the grid of cells a launch works on, derived on the host once
+struct clean_grid {
+    int shift;                     // cell = 1 << shift
+    int cap_ch, cap_cw, ncap;      // the capacity grid and its cells
+};
+
+__global__ __launch_bounds__(STHR) void clean_cells_kernel(const abc_scan_desc d, const abc_scan_clean_desc q, const clean_grid G) {
+    __shared__ uint32_t cnt[CELL_LDS];
+    const int b = blockIdx.y;
+    const int32_t* box = d.box + (size_t)b * ABC_SCAN_NBOX;
+    if (box[BOX_STATUS] != 0) return;      // (uniform: BAD_PARAMS or CONSTANT; no later launch reads this image's scratch)
+    const int32_t* P = d.params + (size_t)b * ABC_SCAN_NPARAM;
+    const int sh = P[ABC_SCAN_SRC_H], sw = P[ABC_SCAN_SRC_W];
+    const int r0 = blockIdx.x * SCAN_ROWS;
+    const int crows = SCAN_ROWS >> G.shift;                  // rows of cells of this workgroup: 64 is a multiple of every cell
+    const int ncell = crows * G.cap_cw;                       // <= CELL_LDS
+    for (int i = threadIdx.x; i < ncell; i += STHR) cnt[i] = 0u;
+    __syncthreads();
+    if (r0 < sh) {                                            // (uniform)
+        const int nrow = min(SCAN_ROWS, sh - r0);
+        const int vpr = (sw + 15) >> 4;
+        const int thr = box[BOX_THR], inv = box[BOX_INV];
+        const uint8_t* src = d.src + (size_t)b * d.src_stride;
+        for (int i = threadIdx.x; i < nrow * vpr; i += STHR) {
+            const int y = i / vpr, v = i - y * vpr;
+            const u32x4 w = load_vec(src, d.src_pitch, r0 + y, v);
+            uint32_t m = 0u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m |= ink_bits(w[k], thr, inv) << (4 * k);
+            const int valid = sw - 16 * v;      // >= 1
+            if (valid < 16) m &= (1u << valid) - 1u;
+            if (!m) continue;
+            uint32_t* row = cnt + (y >> G.shift) * G.cap_cw;
+            if (G.shift == 3) {                               // two cells per vector: 2 v + 1 < cap_cw = pitch / 8
+                const uint32_t lo = (uint32_t)__popc(m & 0xFFu), hi = (uint32_t)__popc(m >> 8);
+                if (lo) atomicAdd(&row[2 * v], lo);
+                if (hi) atomicAdd(&row[2 * v + 1], hi);
+            } else {
+                atomicAdd(&row[(16 * v) >> G.shift], (uint32_t)__popc(m));
+            }
+        }
+    }
+    __syncthreads();
+    const clean_view V = clean_slice(q.scratch, b, G.ncap);
+    const int cy0 = blockIdx.x * crows;
+    for (int i = threadIdx.x; i < ncell; i += STHR) {
+        const int cy = cy0 + i / G.cap_cw;
+        if (cy >= G.cap_ch) break;                            // (the last workgroup's rows past the capacity grid)
+        const int c = cy0 * G.cap_cw + i;
+        const uint32_t n = cnt[i];
+        V.ink[c] = n;
+        V.parent[c] = n ? c : -1;
+        V.weight[c] = 0u;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < META_NWORD) V.meta[threadIdx.x] = 0;
+}
+
+// parents are read and written by atomics alone inside the union launch: they live in L2, no CU's L1 holds a copy that matters
+__device__ inline int clean_parent(const int* parent, int c) { return __hip_atomic_load(parent + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of c, following at most `bound` parents; ok = false when the bound is reached (cannot happen: parent[x] <= x)
+__device__ inline int clean_find(const int* parent, int c, int bound, bool& ok) {
+    for (int it = 0; it < bound; ++it) {
+        const int p = clean_parent(parent, c);
+        if (p == c) return c;
+        c = p;
+    }
+    ok = false;
+    return c;
+}
+
+// one set of a and b: only a root is ever rewritten, and only to a smaller index, so the root of a set is its smallest cell.  Every
+// failed compare-and-swap means that another thread hung that root meanwhile; fewer than ncap roots exist: `bound` tries suffice
+__device__ inline void clean_unite(int* parent, int a, int b, int bound, bool& ok) {
+    for (int it = 0; it < bound && ok; ++it) {
+        a = clean_find(parent, a, bound, ok);
+        b = clean_find(parent, b, bound, ok);
+        if (a == b || !ok) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        if (atomicCAS(&parent[a], a, b) == a) return;
+    }
+    ok = false;
+}
+
+__global__ __launch_bounds__(CTHR) void clean_union_kernel(const abc_scan_desc d, const abc_scan_clean_desc q, const clean_grid G) {
+    const int b = blockIdx.y;
+    if (d.box[(size_t)b * ABC_SCAN_NBOX + BOX_STATUS] != 0) return;
+    const int c = blockIdx.x * CTHR + threadIdx.x;
+    if (c >= G.ncap) return;
+    const clean_view V = clean_slice(q.scratch, b, G.ncap);
+    if (!V.ink[c]) return;
+    const int cy = c / G.cap_cw, cx = c - cy * G.cap_cw;
+    bool ok = true;
+    // W, NW, N, NE.  An occupied N stands for all four: NW and NE are N's own W and E neighbours, and W reaches N as its NE
+    if (cy > 0 && V.ink[c - G.cap_cw]) {
+        clean_unite(V.parent, c, c - G.cap_cw, G.ncap, ok);
+    } else {
+        if (cx > 0 && V.ink[c - 1]) clean_unite(V.parent, c, c - 1, G.ncap, ok);
+        if (cy > 0 && cx > 0 && V.ink[c - G.cap_cw - 1]) clean_unite(V.parent, c, c - G.cap_cw - 1, G.ncap, ok);
+        if (cy > 0 && cx + 1 < G.cap_cw && V.ink[c - G.cap_cw + 1]) clean_unite(V.parent, c, c - G.cap_cw + 1, G.ncap, ok);
+    }
+    if (!ok) atomicOr(&V.meta[META_FAIL], 1);
+}
+
+__global__ __launch_bounds__(CTHR) void clean_flatten_kernel(const abc_scan_desc d, const abc_scan_clean_desc q, const clean_grid G) {
+    const int b = blockIdx.y;
+    if (d.box[(size_t)b * ABC_SCAN_NBOX + BOX_STATUS] != 0) return;      // (uniform)
+    const int c = blockIdx.x * CTHR + threadIdx.x;
+    const clean_view V = clean_slice(q.scratch, b, G.ncap);
+    const uint32_t n = c < G.ncap ? V.ink[c] : 0u;
+    int r = -1;
+    bool todo = false;
+    if (n) {
+        bool ok = true;
+        r = clean_find(V.parent, c, G.ncap, ok);             // (no root changes in this launch: r is final)
+        if (!ok) atomicOr(&V.meta[META_FAIL], 1);
+        else if (r != c) atomicMin(&V.parent[c], r);          // (still a cell of c's set on every path that runs through c)
+        todo = ok;
+    }
+    // the weights: a wave's 64 consecutive cells mostly share a root, and a page's cells all add to one word.  The lanes that share
+    // the first live lane's root sum in the wave and add once, until no lane is left (every lane of the wave runs every round)
+    const int lane = threadIdx.x & 63;
+    for (int round = 0; round < 64; ++round) {                // (a round retires its first live lane at least: 64 suffice)
+        const unsigned long long live = __ballot(todo);
+        if (!live) break;
+        const int lead = __ffsll((long long)live) - 1;
+        const int rr = __shfl(r, lead);
+        const bool mine = todo && r == rr;
+        uint32_t s = mine ? n : 0u;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == lead) atomicAdd(&V.weight[rr], s);
+        if (mine) todo = false;
+    }
+}
+
+// sums (and one maximum) of a DTHR workgroup; every thread calls it, every thread gets the result
+__device__ inline void clean_reduce(int64_t (&v)[4], int& mx, int64_t (*red)[5]) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] += __shfl_xor(v[k], o);
+        mx = max(mx, __shfl_xor(mx, o));
+    }
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();                                          // (red may still be read from the call before)
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) red[wave][k] = v[k];
+        red[wave][4] = mx;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = 0;
+    mx = 0;
+    for (int w = 0; w < DTHR / 64; ++w) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] += red[w][k];
+        mx = max(mx, (int)red[w][4]);
+    }
+}
+
+__global__ __launch_bounds__(DTHR) void clean_decide_kernel(const abc_scan_desc d, const abc_scan_clean_desc q, const clean_grid G) {
+    __shared__ int64_t red[DTHR / 64][5];
+    const int b = blockIdx.x, t = threadIdx.x;
+    int32_t* box = d.box + (size_t)b * ABC_SCAN_NBOX;
+    int32_t* st = q.stats + (size_t)b * ABC_SCAN_NCLEAN;
+    int32_t* lab = q.labels_out ? q.labels_out + (size_t)b * G.ncap : nullptr;
+    uint8_t* kep = q.keep_out ? q.keep_out + (size_t)b * G.ncap : nullptr;
+    if (box[BOX_STATUS] != 0) {                               // (uniform) CONSTANT or BAD_PARAMS: as today, a zero stats row
+        if (t < ABC_SCAN_NCLEAN) st[t] = 0;
+        for (int c = t; c < G.ncap; c += DTHR) {
+            if (lab) lab[c] = -1;
+            if (kep) kep[c] = 0;
+        }
+        return;
+    }
+    const clean_view V = clean_slice(q.scratch, b, G.ncap);
+    const bool failed = V.meta[META_FAIL] != 0;               // (uniform)
+    // the components, the occupied cells and the heaviest weight
+    int64_t s[4] = {0, 0, 0, 0};
+    int H = 0;
+    for (int c = t; c < G.ncap; c += DTHR) {
+        if (!V.ink[c]) continue;
+        s[0] += 1;
+        if (V.parent[c] == c) { s[1] += 1; H = max(H, (int)V.weight[c]); }
+    }
+    clean_reduce(s, H, red);
+    const int occupied = (int)s[0], components = (int)s[1];
+    // the keep rule per cell, from its root's weight
+    int64_t u[4] = {0, 0, 0, 0};
+    int unused = 0;
+    for (int c = t; c < G.ncap; c += DTHR) {
+        const uint32_t n = failed ? 0u : V.ink[c];
+        int label = -1, keep = 0;
+        if (n) {
+            label = V.parent[c];
+            const int64_t w = (int64_t)V.weight[label];
+            keep = w >= (int64_t)q.min_ink && 256 * w >= (int64_t)q.keep_q8 * (int64_t)H;
+            if (keep) { u[0] += n; u[1] += label == c; }
+        }
+        V.keep[c] = (uint8_t)keep;
+        if (lab) lab[c] = label;
+        if (kep) kep[c] = (uint8_t)keep;
+    }
+    clean_reduce(u, unused, red);
+    if (t == 0) {
+        const int ink = box[BOX_INK];
+        if (failed) {
+            for (int k = 0; k < ABC_SCAN_NCLEAN; ++k) st[k] = 0;
+            box[BOX_STATUS] = ABC_SCAN_CLEAN_FAILED;
+        } else {
+            st[ABC_SCAN_C_COMPONENTS] = components; st[ABC_SCAN_C_KEPT] = (int)u[1]; st[ABC_SCAN_C_INK_KEPT] = (int)u[0];
+            st[ABC_SCAN_C_INK_DROPPED] = ink - (int)u[0]; st[ABC_SCAN_C_HEAVIEST] = H; st[ABC_SCAN_C_OCCUPIED] = occupied;
+            if ((int64_t)q.min_ink > (int64_t)H) box[BOX_STATUS] = ABC_SCAN_NO_COMPONENT;      // nothing kept
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int abc_scan_desc_size(void) { return (int)sizeof(abc_scan_desc); }
 
-extern "C" int abc_build_scan_images(const abc_scan_desc* d, abc_stream_t stream) {
+// the guards of abc_build_scan_images, shared with abc_build_scan_images_clean: 0 when d may be launched
+static int scan_guards(const abc_scan_desc* d) {
     if (!d) return abc_fail(ABC_EINVAL, "build_scan_images: null descriptor");
     if (!d->out || !d->src || !d->params || !d->hist || !d->box || !d->geom) return abc_fail(ABC_EINVAL, "build_scan_images: null pointer");
     if (d->B < 1 || d->B > 65535) return abc_fail(ABC_EINVAL, "build_scan_images: B must be 1 .. 65535");
@@ -338,6 +631,11 @@ extern "C" int abc_build_scan_images(const abc_scan_desc* d, abc_stream_t stream
             if (!scan_params_ok(d->params_host + (size_t)b * ABC_SCAN_NPARAM, d->src_max_h, d->src_pitch))
                 return abc_fail(ABC_EINVAL, "build_scan_images: an image's src_h / src_w is below 1 or leaves its slot");
     }
+    return 0;
+}
+
+extern "C" int abc_build_scan_images(const abc_scan_desc* d, abc_stream_t stream) {
+    if (const int rc = scan_guards(d)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const dim3 chunks((unsigned)((d->src_max_h + SCAN_ROWS - 1) / SCAN_ROWS), (unsigned)d->B);
     hipLaunchKernelGGL(scan_zero_kernel, dim3((unsigned)d->B), dim3(256), 0, s, d->hist);
@@ -347,4 +645,52 @@ extern "C" int abc_build_scan_images(const abc_scan_desc* d, abc_stream_t stream
     const int64_t per_img = (int64_t)d->S * d->S / VEC;
     hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)((per_img + STHR - 1) / STHR), (unsigned)d->B), dim3(STHR), 0, s, *d);
     return abc_check_launch("build_scan_images");
+}
+
+extern "C" int abc_scan_clean_desc_size(void) { return (int)sizeof(abc_scan_clean_desc); }
+
+static int clean_shift(int cell) { return cell == 8 ? 3 : cell == 16 ? 4 : cell == 32 ? 5 : cell == 64 ? 6 : -1; }
+
+extern "C" int64_t abc_scan_clean_scratch_bytes(int32_t B, int32_t src_max_h, int32_t src_pitch, int32_t cell) {
+    if (B < 1 || B > 65535 || src_max_h < 1 || src_max_h > 4096 || src_pitch < 16 || src_pitch > 4096 || src_pitch % 16 || clean_shift(cell) < 0)
+        return abc_fail(ABC_EINVAL, "scan_clean_scratch_bytes: B, src_max_h, src_pitch or cell outside abc_build_scan_images_clean's limits");
+    const int64_t ncap = (int64_t)((src_max_h + cell - 1) / cell) * ((src_pitch + cell - 1) / cell);
+    return (int64_t)B * clean_image_words(ncap) * 4;
+}
+
+extern "C" int abc_build_scan_images_clean(const abc_scan_desc* d, const abc_scan_clean_desc* q, abc_stream_t stream) {
+    if (const int rc = scan_guards(d)) return rc;
+    if (!q) return abc_fail(ABC_EINVAL, "build_scan_images_clean: null cleaning descriptor");
+    const int shift = clean_shift(q->cell);
+    if (shift < 0) return abc_fail(ABC_EUNSUPPORTED, "build_scan_images_clean: cell must be 8, 16, 32 or 64");
+    if (q->min_ink < 0) return abc_fail(ABC_EINVAL, "build_scan_images_clean: min_ink must be >= 0");
+    if (q->keep_q8 < 0 || q->keep_q8 > 256) return abc_fail(ABC_EINVAL, "build_scan_images_clean: keep_q8 must be 0 .. 256");
+    if (!q->scratch || !q->stats) return abc_fail(ABC_EINVAL, "build_scan_images_clean: null pointer");
+    if ((uintptr_t)q->scratch % 16) return abc_fail(ABC_EINVAL, "build_scan_images_clean: scratch must be 16-byte aligned");
+    if (((uintptr_t)q->stats | (uintptr_t)q->labels_out) % 4)
+        return abc_fail(ABC_EINVAL, "build_scan_images_clean: stats and labels_out must be 4-byte aligned");
+    clean_grid G;
+    G.shift = shift;
+    G.cap_ch = (d->src_max_h + q->cell - 1) >> shift;
+    G.cap_cw = (d->src_pitch + q->cell - 1) >> shift;
+    G.ncap = G.cap_ch * G.cap_cw;                              // <= 512 * 512
+    scan_mask k;
+    k.keep = (const uint8_t*)q->scratch + 3 * (size_t)G.ncap * 4;      // (clean_slice: the keep bytes follow ink, parent and weight)
+    k.stride = clean_image_words(G.ncap) * 4;
+    k.cap_cw = G.cap_cw;
+    k.shift = shift;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 chunks((unsigned)((d->src_max_h + SCAN_ROWS - 1) / SCAN_ROWS), (unsigned)d->B);
+    const dim3 cells((unsigned)((G.ncap + CTHR - 1) / CTHR), (unsigned)d->B);
+    hipLaunchKernelGGL(scan_zero_kernel, dim3((unsigned)d->B), dim3(256), 0, s, d->hist);
+    hipLaunchKernelGGL(scan_hist_kernel, chunks, dim3(STHR), 0, s, *d);
+    hipLaunchKernelGGL(scan_threshold_kernel, dim3((unsigned)d->B), dim3(256), 0, s, *d);
+    hipLaunchKernelGGL(clean_cells_kernel, chunks, dim3(STHR), 0, s, *d, *q, G);
+    hipLaunchKernelGGL(clean_union_kernel, cells, dim3(CTHR), 0, s, *d, *q, G);
+    hipLaunchKernelGGL(clean_flatten_kernel, cells, dim3(CTHR), 0, s, *d, *q, G);
+    hipLaunchKernelGGL(clean_decide_kernel, dim3((unsigned)d->B), dim3(DTHR), 0, s, *d, *q, G);
+    hipLaunchKernelGGL(scan_box_kernel, chunks, dim3(STHR), 0, s, *d, k);
+    const int64_t per_img = (int64_t)d->S * d->S / VEC;
+    hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)((per_img + STHR - 1) / STHR), (unsigned)d->B), dim3(STHR), 0, s, *d, k);
+    return abc_check_launch("build_scan_images_clean");
 }

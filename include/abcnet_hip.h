@@ -633,6 +633,64 @@ int abc_build_scan_images(const abc_scan_desc* d, abc_stream_t stream);
 /* sizeof(abc_scan_desc), for a binding's mirror struct (as abc_molblock_desc_size) */
 int abc_scan_desc_size(void);
 
+/* abc_build_scan_images with dirt and far-off text dropped before the crop (csrc/scan.hip): connected
+ * components over a coarse grid of cells, weighed by their ink; the box and the resample read ink from kept cells only.  All values
+ * are integers and everything is exact.  thr, inverted and the status come from the threshold above; a pixel (y, x) with y < src_h
+ * and x < src_w is ink by the polarity rule above; bytes of the slot outside the source never count.
+ *   cells       cell is 8, 16, 32 or 64.  Cell (cy, cx) covers rows cy cell .. min(src_h, (cy + 1) cell) - 1 and columns likewise.
+ *               The grid of image b is ch = ceil(src_h / cell) by cw = ceil(src_w / cell); the capacity grid is cap_ch =
+ *               ceil(src_max_h / cell) by cap_cw = ceil(src_pitch / cell).  ink(cy, cx) = the ink pixels in the cell; a cell is
+ *               occupied when ink > 0.
+ *   components  the 8-connected components of the occupied cells.  A component's label is the smallest cy cap_cw + cx among its
+ *               cells, its weight the sum of ink over its cells; H is the largest weight.
+ *   keep rule   a component is kept iff weight >= min_ink and 256 weight >= keep_q8 H, evaluated in 64 bits (min_ink >= 0, keep_q8
+ *               0 .. 256).  keep_q8 = 256 keeps the heaviest component and every component that ties with it; there is no tie-break
+ *               anywhere: the result depends only on the partition and the sums.  min_ink = 0 and keep_q8 = 0 keep everything, and
+ *               then out and geom are abc_build_scan_images' bit for bit.
+ *   box         y0, y1, x0, x1 over the ink pixels that lie in kept cells.
+ *   fit         unchanged.
+ *   resample    unchanged, except that n counts only ink pixels in kept cells; the area a is unchanged.  A source box may straddle
+ *               kept and dropped cells.
+ *   nothing kept  (min_ink > H) status ABC_SCAN_NO_COMPONENT: a blank output; the geometry row keeps thr and inverted, carries the
+ *               status and has zeros elsewhere, but ink still holds the source's count.
+ *   ABC_SCAN_CONSTANT and ABC_SCAN_BAD_PARAMS images behave as above and the cleaning launches skip them.
+ *   geom        layout unchanged; ink stays the thresholded source's count.
+ *   stats       int32 [B][ABC_SCAN_NCLEAN] (abc_scan_clean_stat order): components, kept, ink_kept, ink_dropped, heaviest (H),
+ *               occupied_cells; all zeros for an image whose status was non-zero before cleaning.
+ *   labels_out  optional int32 [B][cap_ch][cap_cw]: an unoccupied cell inside the image's grid holds -1, an occupied cell its
+ *               component's label; cells outside the image's grid, and every cell of a skipped image, hold -1.  Every launch
+ *               writes the whole of image b's slice.
+ *   keep_out    optional uint8 of the same shape: 1 is a kept occupied cell, 0 everything else.
+ * Nine launches on the stream, in order, whatever the images hold: zero, histogram and threshold as above; cells (one pass over the
+ * source on the histogram's grid, each cell's ink summed in LDS and stored once), union (union-find over the cells: an occupied cell
+ * unions with its W, NW, N and NE neighbours, the larger root always hung under the smaller by compare-and-swap), flatten (every
+ * cell to its root, its ink added to the root's weight by integer atomics), decide (H, the keep bytes, stats, labels_out, keep_out
+ * and the status); then the box and the fit+write passes reading the keep bytes.  No parallel branch (capturable), no sync, no
+ * allocation; scratch is the caller's, abc_scan_clean_scratch_bytes of it, 16-byte aligned, and the sequence resets all it uses: a
+ * smaller image after a larger one in the same slot shows nothing stale.  Every loop that follows parents is bounded by the cells of
+ * the capacity grid; parents only decrease, so a correct run cannot reach the bound; an image that does gets the status
+ * ABC_SCAN_CLEAN_FAILED, a blank output, a geometry row as for nothing kept, a zero stats row, and -1 / 0 in labels_out / keep_out.
+ * Every guard of abc_build_scan_images applies to d; ABC_EUNSUPPORTED: cell outside the four values; ABC_EINVAL: min_ink < 0,
+ * keep_q8 outside 0 .. 256, scratch or stats NULL, scratch not 16-byte aligned, stats or labels_out not 4-byte aligned.  Nothing is
+ * launched after a refusal. */
+enum abc_scan_clean_status { ABC_SCAN_NO_COMPONENT = 4, ABC_SCAN_CLEAN_FAILED = 8 };      /* further abc_scan_status values */
+enum abc_scan_clean_stat { ABC_SCAN_C_COMPONENTS = 0, ABC_SCAN_C_KEPT, ABC_SCAN_C_INK_KEPT, ABC_SCAN_C_INK_DROPPED,
+                           ABC_SCAN_C_HEAVIEST, ABC_SCAN_C_OCCUPIED, ABC_SCAN_NCLEAN };
+typedef struct abc_scan_clean_desc {
+    void* scratch;                  /* abc_scan_clean_scratch_bytes(B, src_max_h, src_pitch, cell) bytes, 16-byte aligned */
+    int32_t* stats;                 /* out [B][ABC_SCAN_NCLEAN] */
+    int32_t* labels_out;            /* optional out [B][cap_ch][cap_cw] (NULL: not written) */
+    uint8_t* keep_out;              /* optional out [B][cap_ch][cap_cw] (NULL: not written) */
+    int32_t cell;                   /* 8, 16, 32 or 64 */
+    int32_t min_ink;                /* >= 0 */
+    int32_t keep_q8;                /* 0 .. 256 */
+} abc_scan_clean_desc;
+int abc_build_scan_images_clean(const abc_scan_desc* d, const abc_scan_clean_desc* q, abc_stream_t stream);
+/* sizeof(abc_scan_clean_desc), for a binding's mirror struct (as abc_scan_desc_size) */
+int abc_scan_clean_desc_size(void);
+/* the bytes of abc_scan_clean_desc.scratch for these capacities; ABC_EINVAL (negative) when one of them is outside the limits above */
+int64_t abc_scan_clean_scratch_bytes(int32_t B, int32_t src_max_h, int32_t src_pitch, int32_t cell);
+
 /* Stroke width of a binary drawing, normalised (csrc/stroke.hip): peel it toward its skeleton, then grow it
  * back to a chosen width.  The augmentation the reference leaves commented out (utils.py:65-71: sm.thin, then sm.dilation with
  * sm.disk(1)) as a device stage; synthetic._line's lines of 3 pixels are a one-pixel skeleton dilated by disk(1).
