@@ -174,7 +174,8 @@ class HeadsFusedDesc(C.Structure):
                 ("logits", vp * 8), ("t_atom", vp), ("t_types", vp), ("t_charges", vp), ("t_hs", vp), ("t_bond", vp),
                 ("t_btypes", vp), ("t_rho", vp), ("t_omega", vp), ("dl", vp), ("g", vp), ("bn_partial", vp), ("loss_partial", vp),
                 ("B", i32), ("h", i32), ("w", i32), ("chan_scale", vp), ("chan_off", i32 * 8), ("dw2", vp * 8), ("db2", vp * 8),
-                ("wgrad_work", vp), ("keep_mask", vp), ("target_flags", vp), ("zero_bytes", vp)]
+                ("wgrad_work", vp), ("keep_mask", vp), ("target_flags", vp), ("zero_bytes", vp),
+                ("dl_tiles", vp), ("no_zero_skip", i32), ("pad_", i32)]
 
 
 class ConvTDesc(C.Structure):

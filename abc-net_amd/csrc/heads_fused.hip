@@ -25,6 +25,11 @@
 // Work: grid = (128-pixel chunks, 2 head groups); group 0 = bond types + rho (they share the bond-type targets), group 1 =
 // omega + the five small heads.  HBM-bound: features 0.30 GB + targets 0.37 GB read, logits 0.30 GB + d(logits) 0.23 GB
 // + g 0.30 GB written.
+//
+// Doing less where the targets are zero (ZERO SKIP, in front of run_head_skip): a row tile of a softmax head without a target in
+// any of the wave's 32 pixels -- decided from the target registers themselves, dense maps included -- stores its logits and nothing
+// else; a bond-type tile of that kind is not written to the blocked d(logits) buffer, and the per-chunk tile mask (dl_tiles) tells
+// the weight gradient which tiles were.  The rasteriser's group flags (target_flags) still say "all tiles zero" without a look.
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
@@ -55,6 +60,8 @@ struct HFK {
     const double *t_rho, *t_omega;
     const uint32_t* tflags;   // abc_heads_fused_desc.target_flags (the rasteriser's 32-pixel group flags) or null
     const char* tzero;        // >= 512 zero bytes (with tflags)
+    uint64_t* dl_tiles;       // abc_heads_fused_desc.dl_tiles (which bond-type row tiles fired, one word per chunk) or null
+    int noskip;               // abc_heads_fused_desc.no_zero_skip
     float* bnpart;      // [nchunk][2][ld]
     float* dwsmall;     // [nchunk][HF_SMALL_ROWS][128 + 1]: the small heads' conv2 weight / bias gradient partials (see run_head)
     double* losspart;   // [nchunk][16]
@@ -77,7 +84,8 @@ constexpr int WV_AIMG = 7680, AROW = 128 * 2 + 16;   // small heads: the wave's 
 constexpr int WV = 16384;
 constexpr int LDS_BSUM = 4 * WV;           // the waves' BatchNorm sums: [4 waves][<= 2 slices][2][128] f32 = 8 KB
 constexpr int LDS_LSUM = LDS_BSUM + 4 * 2 * 2 * 128 * 4;   // [4 waves][16] f64
-constexpr int HF_LDS = LDS_LSUM + 4 * 16 * 8;
+constexpr int LDS_TMASK = LDS_LSUM + 4 * 16 * 8;             // [4 waves] u32: the bond-type row tiles that fired (Ctx.tmask)
+constexpr int HF_LDS = LDS_TMASK + 16;
 
 struct Ctx {
     int lane, r, h, wave, chunk, b, yx, nslice;
@@ -87,6 +95,7 @@ struct Ctx {
     float* wsum;     // this wave's BatchNorm sums: [slice of the group][2][128]
     float dscale;
     uint32_t dseed;
+    uint32_t tmask;  // bond types: bit mt = row tile mt fired for this wave (wave-uniform)
 };
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_f;
@@ -150,8 +159,46 @@ __device__ inline void small_head_wgrad(const HFK& a, const Ctx& c, const bf16x8
     __syncthreads();   // the tiles are read by the other waves: the epilogue reuses their space
 }
 
+// The end of a softmax head for a wave in which NO row tile fired (below): dA = W2^T x 0, so g = 0 and its BatchNorm sums are 0;
+// the keep bits the blocked weight gradient takes, and zero loss sums.
+template <int HEAD>
+__device__ inline void zero_tail(const HFK& a, Ctx& c, uint32_t kb0, uint32_t kb1, double* lsum) {
+    const int slice = 128 * HEAD, lane = c.lane;
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
+    const int sg = lane & 7, pg = lane >> 3;
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int it = 0; it < 4; ++it)
+            *(u32x4*)(a.g + (size_t)(c.pix0 + it * 8 + pg) * a.ld + slice + 64 * half + sg * 8) = z4;
+    float* ws = c.wsum + c.nslice * 256;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ws[lane + 64 * i] = 0.f;
+    if constexpr (HEAD >= 5) {
+        if (a.hd[HEAD].keep != nullptr) a.hd[HEAD].keep[2u * c.pix + c.h] = make_uint2(kb0, kb1);
+    }
+    c.nslice += 1;
+    if (lane == 0) {
+        lsum[HEAD] = 0.0;
+        lsum[8 + HEAD] = 0.0;
+        if (HEAD == 5) lsum[8 + 6] = 0.0;
+    }
+}
+
+// ZERO SKIP, per row tile.  A softmax GROUP (the 14 atom types / 3 charges / 2 hydrogen counts of a pixel, the 6 bond types of one
+// omega bin of a pixel) lives in one lane (hf_chan_of_row).  class_focal (loss_math.hpp) on a group with t[k] == 0 for every k:
+// *den += t[k] adds zeros, the `t[k] != 0` branch is never taken so loss = 0 and a[k] = 0, dot = sum a[k] q[k] = 0 and
+// dz[k] = q[k] * (0 - 0) = +0 -- PROVIDED q[k] is finite, i.e. the logits are (a NaN or infinite logit makes q NaN and the full path
+// would store NaN where the skip stores 0; training that has reached that point is lost either way).  A row tile holds, per lane, the
+// groups of one pixel: all of a small head's, or the two omega bins 30 h + 2 mt + {0, 1} of the bond types.  So where NO lane of the
+// wave holds a non-zero target in the tile (one ballot over the target registers the tile has just loaded: wave-uniform, a scalar),
+// the tile adds +0 to the loss numerator and denominator, its per-bin target sums (rho's weights) are +0, its d(logits) are +0 and
+// its data-gradient MFMAs add W2^T x 0 = +0 to accumulators that started at +0: leaving all of that out changes no bit.  What stays
+// is the tile's logits (when somebody reads them: hd.logits).  `t != 0` is true for a NaN target, as in class_focal: such a tile fires.
+// A wave in which no tile of the head fired ends in zero_tail.  no_zero_skip = 1 makes every tile fire.
+//
 // A wave NONE of whose 32 pixels carries a target of a softmax head (atom types, charges, hydrogens, bond types; known from the
-// rasteriser's group flags): every term of class_focal and every derivative is zero there (loss_math.hpp: t[k] == 0 adds nothing to
+// rasteriser's group flags, or for the one-tile heads from their targets): every term of class_focal and every derivative is zero there (loss_math.hpp: t[k] == 0 adds nothing to
 // the numerator or the denominator and leaves a[k] = 0, so dz[k] = q[k] * (0 - 0)) -- for finite logits exactly what the full path
 // computes.  What is left of the head for this wave: its logits (when somebody reads them: hd.logits), zeros for d(logits), g and the
 // BatchNorm sums.  The exp / log / focal arithmetic of the 15-tile bond-type head is the bulk of the fused pass's instruction issue,
@@ -242,14 +289,18 @@ __device__ inline void run_head_skip(const HFK& a, Ctx& c, double* lsum) {
         }
     }
     // ---- d(logits) = 0: the blocked buffer of the weight gradient (the stores of run_head's tile loop), the wave's LDS tile (the
-    // small heads' weight gradient reads it), and for the bond types the per-bin target sums rho takes
+    // small heads' weight gradient reads it), and for the bond types the per-bin target sums rho takes.  Bond types with the tile
+    // mask (dl_tiles): no tile fired, the weight gradient reads none of them and nothing is stored (no_zero_skip: zeros, all bits set)
+    if constexpr (HEAD == 5) c.tmask = a.noskip ? 0x7FFFu : 0u;
+    if (HEAD != 5 || a.dl_tiles == nullptr || a.noskip) {
 #pragma unroll 1
-    for (int mt = 0; mt < NT; ++mt)
+        for (int mt = 0; mt < NT; ++mt)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = lane + 64 * j, row = q >> 2, part = q & 3;
-            *(u32x4*)((char*)(hd.dlb + ((size_t)c.chunk * CPAD + 32 * mt) * 128) + (uint32_t)((row * 128 + 32 * c.wave + part * 8) * 2)) = z4;
-        }
+            for (int j = 0; j < 2; ++j) {
+                const int q = lane + 64 * j, row = q >> 2, part = q & 3;
+                *(u32x4*)((char*)(hd.dlb + ((size_t)c.chunk * CPAD + 32 * mt) * 128) + (uint32_t)((row * 128 + 32 * c.wave + part * 8) * 2)) = z4;
+            }
+    }
     if constexpr (HEAD == 5) {
 #pragma unroll
         for (int j = 0; j < 30; ++j) c.dnl[j * 64 + lane] = 0.f;
@@ -262,27 +313,7 @@ __device__ inline void run_head_skip(const HFK& a, Ctx& c, double* lsum) {
         lds_sync();
         small_head_wgrad<HEAD>(a, c, fb);
     }
-    // ---- g = 0 and its BatchNorm sums (run_head's epilogue: dA = W2^T x 0)
-    {
-        const int sg = lane & 7, pg = lane >> 3;
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-                *(u32x4*)(a.g + (size_t)(c.pix0 + it * 8 + pg) * a.ld + slice + 64 * half + sg * 8) = z4;
-        float* ws = c.wsum + c.nslice * 256;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ws[lane + 64 * i] = 0.f;
-    }
-    if constexpr (HEAD >= 5) {
-        if (hd.keep != nullptr) hd.keep[2u * c.pix + h] = make_uint2(kbits[0], kbits[1]);
-    }
-    c.nslice += 1;
-    if (lane == 0) {
-        lsum[HEAD] = 0.0;
-        lsum[8 + HEAD] = 0.0;
-        if (HEAD == 5) lsum[8 + 6] = 0.0;
-    }
+    zero_tail<HEAD>(a, c, kbits[0], kbits[1], lsum);
 }
 
 // One head for the wave's 32 pixels; its loss numerator / denominator (summed over the wave) go to lsum[HEAD] / lsum[8 + HEAD].
@@ -323,6 +354,18 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
     float* cf = (float*)(c.ot + WV_CF);
     float* bl = (float*)(c.ot + WV_BIAS);
     const uint32_t e0 = c.pix * (uint32_t)a.ld + slice + 8 * h;   // this lane's first feature element
+
+    // the small softmax heads have ONE row tile: where it does not fire (ZERO SKIP above) the wave takes run_head_skip, decided from
+    // the targets themselves (both lane halves read the pixel's planes: the same cache lines; the tile loop finds them in the cache)
+    if constexpr (HEAD == 1 || HEAD == 2 || HEAD == 3) {
+        if (!a.noskip) {
+            const float* tg = HEAD == 1 ? a.t_types : (HEAD == 2 ? a.t_charges : a.t_hs);
+            bool nz = false;
+#pragma unroll
+            for (int k = 0; k < CH; ++k) nz |= *at4(tg, k) != 0.f;
+            if (__builtin_amdgcn_ballot_w64(nz) == 0) { run_head_skip<HEAD>(a, c, lsum); return; }
+        }
+    }
 
     // ---- issue: features, coefficients + bias (-> LDS), the first tile's weights and targets
     u32x4 raw[8];
@@ -413,11 +456,24 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
             for (int mi = 0; mi < 4; ++mi) accD[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wt[4 * u + mi], bqp[u], accD[mi], 0, 0, 0);
     };
 
+    // bond types (ZERO SKIP above), both wave-uniform and in scalar registers: the row tiles that fired so far, and whether the
+    // previous one did (its data-gradient MFMAs are then pending).  Every other head: each tile fires (a small softmax head whose
+    // one tile does not has taken run_head_skip above)
+    uint32_t tmask = 0u;
+    bool prev = false;
 #pragma unroll 1
     for (int mt = 0; mt < NT; ++mt) {
         // ---- data gradient of the previous tile: dA[ci][p] += W2^T x dL, K-step u = registers 8 u .. 8 u + 7 of both halves
-        if (PIPE && mt > 0) dgrad_mfma();
+        if (PIPE && mt > 0 && prev) dgrad_mfma();
         if constexpr (!PIPE) load_fa(mt);
+        bool fired = true;
+        if constexpr (HEAD == 5) {
+            bool nz = false;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) nz |= tn[k] != 0.f;
+            fired = a.noskip != 0 || __builtin_amdgcn_ballot_w64(nz) != 0;
+            tmask |= (fired ? 1u : 0u) << mt;
+        }
         // ---- logits of 32 packed rows x 32 pixels (the accumulators start from the bias)
         f32x16 acc;
 #pragma unroll
@@ -426,24 +482,31 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[4 * q + j] = b4[j];
         }
+        if (fired || st_logits) {   // (a tile that neither fires nor stores its logits needs no forward product)
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], fb[kk], acc, 0, 0, 0);
+            for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], fb[kk], acc, 0, 0, 0);
+        }
         float v[16], dlv[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) { v[k] = acc[k]; dlv[k] = 0.f; }
         // ---- loss + d(logits): register k of lane half h = packed row 32 mt + (k & 3) + 8 (k >> 2) + 4 h (hf_chan_of_row)
         if constexpr (HEAD == 5) {
             // registers 8 gi .. 8 gi + 5 = the six bond types of omega bin 30 h + 2 mt + gi (train.py:101 view)
+            if (fired) {
 #pragma unroll
-            for (int gi = 0; gi < 2; ++gi) {
-                float z[6], t[6], dz[6], dn = 0.f;
+                for (int gi = 0; gi < 2; ++gi) {
+                    float z[6], t[6], dz[6], dn = 0.f;
 #pragma unroll
-                for (int k = 0; k < 6; ++k) { z[k] = v[8 * gi + k]; t[k] = tn[6 * gi + k]; }
-                num += (double)class_focal<6, true>(z, t, nullptr, dz, &dn);
-                den += (double)dn;
-                c.dnl[(2 * mt + gi) * 64 + lane] = dn;
+                    for (int k = 0; k < 6; ++k) { z[k] = v[8 * gi + k]; t[k] = tn[6 * gi + k]; }
+                    num += (double)class_focal<6, true>(z, t, nullptr, dz, &dn);
+                    den += (double)dn;
+                    c.dnl[(2 * mt + gi) * 64 + lane] = dn;
 #pragma unroll
-                for (int k = 0; k < 6; ++k) dlv[8 * gi + k] = dz[k];
+                    for (int k = 0; k < 6; ++k) dlv[8 * gi + k] = dz[k];
+                }
+            } else {
+                c.dnl[(2 * mt) * 64 + lane] = 0.f;
+                c.dnl[(2 * mt + 1) * 64 + lane] = 0.f;
             }
             // ---- loads of the next iteration (weights, targets) and this tile's data-gradient fragments: after the loss
             // arithmetic (its registers are free again), still AHEAD of this tile's stores
@@ -451,11 +514,13 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
             {
                 const int mtn = mt + 1 < NT ? mt + 1 : mt;
                 load_fa(mtn);
+                if (fired) {
 #pragma unroll
-                for (int u = 0; u < 2; ++u)
+                    for (int u = 0; u < 2; ++u)
 #pragma unroll
-                    for (int mi = 0; mi < 4; ++mi)
-                        wt[4 * u + mi] = *(const bf16x8*)((const char*)(hd.w2t + (size_t)((2 * mt + u) * 128 + 32 * mi) * 16) + (uint32_t)(r * 32 + h * 16));
+                        for (int mi = 0; mi < 4; ++mi)
+                            wt[4 * u + mi] = *(const bf16x8*)((const char*)(hd.w2t + (size_t)((2 * mt + u) * 128 + 32 * mi) * 16) + (uint32_t)(r * 32 + h * 16));
+                }
                 load_t5(mtn);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -521,20 +586,31 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
             }
         }
 
-        // ---- d(logits) as bf16: [row][pixel] tile -> the blocked buffer of the weight gradient
-        bqp[0] = pack_frag<bf16>(dlv);
-        bqp[1] = pack_frag<bf16>(dlv + 8);
-        char* tl = c.ot;
+        // ---- d(logits) as bf16: [row][pixel] tile -> the blocked buffer of the weight gradient.  A bond-type tile that did not
+        // fire: nothing with the tile mask (the weight gradient does not read it), zeros without
+        if (fired) {
+            bqp[0] = pack_frag<bf16>(dlv);
+            bqp[1] = pack_frag<bf16>(dlv + 8);
+            char* tl = c.ot;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) *(bf16*)(tl + ((k & 3) + 8 * (k >> 2) + 4 * h) * TROW + r * 2) = bqp[k >> 3][k & 7];
-        lds_sync();
+            for (int k = 0; k < 16; ++k) *(bf16*)(tl + ((k & 3) + 8 * (k >> 2) + 4 * h) * TROW + r * 2) = bqp[k >> 3][k & 7];
+            lds_sync();
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = lane + 64 * j, row = q >> 2, part = q & 3;
-            const u32x4 t = *(const u32x4*)(tl + row * TROW + part * 16);
-            *(u32x4*)((char*)(hd.dlb + ((size_t)c.chunk * CPAD + 32 * mt) * 128) + (uint32_t)((row * 128 + 32 * c.wave + part * 8) * 2)) = t;
+            for (int j = 0; j < 2; ++j) {
+                const int q = lane + 64 * j, row = q >> 2, part = q & 3;
+                const u32x4 t = *(const u32x4*)(tl + row * TROW + part * 16);
+                *(u32x4*)((char*)(hd.dlb + ((size_t)c.chunk * CPAD + 32 * mt) * 128) + (uint32_t)((row * 128 + 32 * c.wave + part * 8) * 2)) = t;
+            }
+            lds_sync();
+        } else if (a.dl_tiles == nullptr) {
+            const u32x4 z4 = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int q = lane + 64 * j, row = q >> 2, part = q & 3;
+                *(u32x4*)((char*)(hd.dlb + ((size_t)c.chunk * CPAD + 32 * mt) * 128) + (uint32_t)((row * 128 + 32 * c.wave + part * 8) * 2)) = z4;
+            }
         }
-        lds_sync();
+        prev = fired;
         if constexpr (!PIPE) {
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -544,10 +620,15 @@ __device__ inline void run_head(const HFK& a, Ctx& c, double* lsum) {
             if (mt + 1 < NT) dgrad_mfma();
         }
     }
+    if constexpr (HEAD == 5) {
+        // no tile fired: dA = 0 (zero_tail; the sums of num / den are sums of nothing)
+        c.tmask = tmask;
+        if (tmask == 0u) { zero_tail<HEAD>(a, c, kbits[0], kbits[1], lsum); return; }
+    }
     // the raw features again (the epilogue's LeakyReLU' / dropout mask / xhat), issued ahead of the last tile's MFMAs
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) raw[kk] = *(const u32x4*)(a.y1 + e0 + 16 * kk);
-    dgrad_mfma();
+    if (!PIPE || prev) dgrad_mfma();
 
     // ---- the small heads also finish conv2's WEIGHT gradient here (small_head_wgrad)
     if constexpr (HEAD < 5) small_head_wgrad<HEAD>(a, c, fb);
@@ -648,6 +729,7 @@ __global__ __launch_bounds__(256, 2) void heads_fused_kernel(const HFK a) {
     const int group = blockIdx.y;
     c.wsum = (float*)(smem + LDS_BSUM) + c.wave * 512;
     c.nslice = 0;
+    c.tmask = 0u;
     c.dscale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     c.dseed = a.drop_seed + ((a.drop_p > 0.f && a.drop_salt) ? *a.drop_salt : 0u);
     double* ls = (double*)(smem + LDS_LSUM);
@@ -665,7 +747,21 @@ __global__ __launch_bounds__(256, 2) void heads_fused_kernel(const HFK a) {
         case 5: run_head<3>(a, c, lsum); break;
         default: run_head<4>(a, c, lsum); break;
     }
+    uint32_t* tm = (uint32_t*)(smem + LDS_TMASK);
+    if (group == 0 && c.lane == 0) tm[c.wave] = c.tmask;
     __syncthreads();
+    // the chunk's tile mask: bit 4 mt + w = row tile mt of the bond types fired for wave w.  Written for every chunk by every launch
+    // (nothing stale survives a replay), one lane, a plain vector store
+    if (group == 0 && a.dl_tiles != nullptr && threadIdx.x == 0) {
+        uint64_t word = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t m = tm[w];
+#pragma unroll
+            for (int mt = 0; mt < 15; ++mt) word |= (uint64_t)((m >> mt) & 1u) << (4 * mt + w);
+        }
+        a.dl_tiles[c.chunk] = word;
+    }
     // one row of 16 sums per 128-pixel chunk; a work type writes the columns of ITS heads (together they cover all 16)
     if (threadIdx.x < 16) {
         const int i = threadIdx.x & 7;   // head of this column (numerator i, denominator 8 + i)
@@ -759,6 +855,7 @@ extern "C" int abc_heads_fused_fwd_bwd(const abc_heads_fused_desc* d, abc_stream
     k.t_btypes = d->t_btypes; k.t_rho = d->t_rho; k.t_omega = d->t_omega;
     if ((d->target_flags != nullptr) != (d->zero_bytes != nullptr)) return abc_fail(ABC_EINVAL, "heads_fused: target_flags and zero_bytes go together");
     k.tflags = d->target_flags; k.tzero = (const char*)d->zero_bytes;
+    k.dl_tiles = d->dl_tiles; k.noskip = d->no_zero_skip != 0;
     k.bnpart = d->bn_partial; k.losspart = d->loss_partial; k.dwsmall = d->wgrad_work;
     k.HW = d->h * d->w; k.nchunk = abc_heads_fused_chunks(d);
     size_t row0 = 0;

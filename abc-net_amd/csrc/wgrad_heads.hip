@@ -27,6 +27,7 @@ struct HeadK {
     unsigned bytesP, bytesQ;
     int cpad_blk;    // BLK: dl = bf16 [chunk][cpad_blk rows][128 pixels], written by the fused heads kernel (heads_fused.hip)
     const uint8_t* keep;   // BLK: the fused kernel's dropout keep bits, 16 bytes per pixel (byte kk + 8 h = channels 16 kk + 8 h ..), or null
+    const uint64_t* tiles; // BLK: abc_heads_fused_desc.dl_tiles (bit 4 mt + w of a chunk's word: rows 32 mt .., pixels 32 w .. of dl are written), or null = all are
 };
 
 constexpr int HQ_PSW = 320;  // pixel stride of the [pixel][128 channel] bf16 LDS image (wgrad Q layout)
@@ -83,8 +84,19 @@ __device__ inline void head_wgrad_body(const HeadK& a, const int split, const in
     const __amdgpu_buffer_rsrc_t rsK = abc_make_rsrc(kmask ? a.keep : (const uint8_t*)a.q, kmask ? (unsigned)a.nchunks * 2048u : 0u);
     const unsigned kbyte = (unsigned)((part & 1) * 8 + (part >> 1));
     const int CPI = a.HW / 128;  // chunks per image
-    auto issue = [&](int c, u32x4 (&qreg)[4], u32x4 (&preg)[8]) {
-        const bool live = c < c1;
+    // BLK with the fused kernel's tile mask (the bond types): the 16 bits of this m-group's four row tiles x the chunk's four
+    // 32-pixel quarters, workgroup-uniform and in a scalar register.  d(logits) is zero wherever a bit is clear, and the buffer is
+    // NOT written there: a 16-byte piece of P (rows of tile i of the group, pixels of quarter (tid & 15) >> 2) whose bit is clear
+    // is loaded with the out-of-range offset (zeros, no traffic -- the memory there is never read).  A chunk with all 16 bits clear
+    // adds +0 to every accumulator and row sum (finite features): all of its loads go out of range (issued all the same, so that
+    // vmcnt stays exact), and it is neither committed to LDS nor multiplied.  The barriers and the buffer parity do not depend on it.
+    auto tmask16 = [&](int c) -> uint32_t {
+        if (!BLK || a.tiles == nullptr) return 0xFFFFu;
+        if (c >= c1) return 0u;
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a.tiles[c] >> (16 * mg))) & 0xFFFFu;
+    };
+    auto issue = [&](int c, const uint32_t m16, u32x4 (&qreg)[4], u32x4 (&preg)[8]) {
+        const bool live = c < c1 && m16 != 0u;
         const int b = c / CPI, pp0 = (c - b * CPI) * 128;
         const unsigned qoff = live ? (unsigned)(((unsigned)(c * 128 + pix0) * (unsigned)a.ldq + (unsigned)(a.cq_off + part * 8)) * 2u) : 0x80000000u;
 #pragma unroll
@@ -99,7 +111,8 @@ __device__ inline void head_wgrad_body(const HeadK& a, const int split, const in
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = mg * 128 + (tid >> 4) + 32 * i;
-                const unsigned poff = (live && row < a.cpad_blk) ? (unsigned)((((unsigned)c * (unsigned)a.cpad_blk + (unsigned)row) * 128u + 8u * (tid & 15)) * 2u) : 0x80000000u;
+                const bool bit = (m16 >> (4 * i + ((tid & 15) >> 2))) & 1u;   // (row >> 5 = 4 mg + i: tile i of the group)
+                const unsigned poff = (live && bit && row < a.cpad_blk) ? (unsigned)((((unsigned)c * (unsigned)a.cpad_blk + (unsigned)row) * 128u + 8u * (tid & 15)) * 2u) : 0x80000000u;
                 preg[i] = __builtin_amdgcn_raw_buffer_load_b128(rsP, poff, 0, 0);
             }
         } else {
@@ -194,22 +207,26 @@ __device__ inline void head_wgrad_body(const HeadK& a, const int split, const in
     constexpr int BUF = HEAD_PBUF + HEAD_QBUF;
     char* const b0 = smem;
     char* const b1 = smem + BUF;
-    issue(c0, qreg0, preg0);
-    issue(c0 + 1, qreg1, preg1);
-    if (c0 < c1) commit(c0, b0, b0 + HEAD_PBUF, qreg0, preg0);
+    // the tile masks of chunks c .. c + 3, read one pair ahead of the loads they steer (issue(c + 2) needs its mask at once)
+    uint32_t mA = tmask16(c0), mB = tmask16(c0 + 1), mC = tmask16(c0 + 2), mD = tmask16(c0 + 3);
+    issue(c0, mA, qreg0, preg0);
+    issue(c0 + 1, mB, qreg1, preg1);
+    if (c0 < c1 && mA != 0u) commit(c0, b0, b0 + HEAD_PBUF, qreg0, preg0);
     __syncthreads();
     // even chunks (relative) live in LDS buffer 0 and come from register set 0, odd ones buffer 1 / set 1
     for (int c = c0; c < c1; c += 2) {
-        issue(c + 2, qreg0, preg0);
-        if (active) compute(b0, b0 + HEAD_PBUF);
-        if (c + 1 < c1) commit(c + 1, b1, b1 + HEAD_PBUF, qreg1, preg1);
+        const uint32_t mE = tmask16(c + 4), mF = tmask16(c + 5);
+        issue(c + 2, mC, qreg0, preg0);
+        if (active && mA != 0u) compute(b0, b0 + HEAD_PBUF);
+        if (c + 1 < c1 && mB != 0u) commit(c + 1, b1, b1 + HEAD_PBUF, qreg1, preg1);
         __syncthreads();
         if (c + 1 < c1) {
-            issue(c + 3, qreg1, preg1);
-            if (active) compute(b1, b1 + HEAD_PBUF);
-            if (c + 2 < c1) commit(c + 2, b0, b0 + HEAD_PBUF, qreg0, preg0);
+            issue(c + 3, mD, qreg1, preg1);
+            if (active && mB != 0u) compute(b1, b1 + HEAD_PBUF);
+            if (c + 2 < c1 && mC != 0u) commit(c + 2, b0, b0 + HEAD_PBUF, qreg0, preg0);
             __syncthreads();
         }
+        mA = mC; mB = mD; mC = mE; mD = mF;
     }
     if (BLK && a.rowsum != nullptr) {
         // a row's 16 pieces sit in 16 consecutive lanes
@@ -271,7 +288,7 @@ static void head_fill(HeadK& k, const abc_wgrad_desc* d) {
     k.nchunks = d->B * k.HW / 128; k.nsplit = d->nsplit; k.mtiles = abc_cdiv(d->Ca, 32); k.Ca_pad = k.mtiles * 32;
     k.drop_p = d->q.drop_p; k.drop_seed = d->q.drop_seed; k.drop_salt = d->q.drop_salt;
     k.bytesP = (unsigned)((int64_t)d->B * d->Ca * k.HW * 4); k.bytesQ = (unsigned)((int64_t)d->B * k.HW * d->q.ldx * 2);
-    k.cpad_blk = 0; k.keep = nullptr;
+    k.cpad_blk = 0; k.keep = nullptr; k.tiles = nullptr;
 }
 
 // both operands lie on the gradient's own grid
@@ -431,6 +448,7 @@ extern "C" int abc_heads_fused_wgrad(const abc_heads_fused_desc* d, abc_stream_t
             k.bytesP = (unsigned)((size_t)nchunk * cpad * 128 * 2); k.bytesQ = (unsigned)((int64_t)d->B * HW * d->ld * 2);
             k.cpad_blk = cpad;
             k.keep = d->keep_mask != nullptr ? (const uint8_t*)d->keep_mask + (size_t)(i - 5) * nchunk * 2048 : nullptr;
+            k.tiles = i == 5 ? d->dl_tiles : nullptr;   // (the bond types: the only head whose tiles the fused pass may leave unwritten)
             if ((size_t)nchunk * cpad * 128 * 2 >= (size_t(1) << 31)) return abc_fail(ABC_EUNSUPPORTED, "heads_fused_wgrad: d(logits) block above 2 GB");
             rk.partial[i] = k.partial; rk.rowsum[i] = k.rowsum;
         }

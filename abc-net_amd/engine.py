@@ -142,8 +142,10 @@ class Engine:
     def __init__(self, variant, in_channels, heads, params, grads, buffers, counters, layout, B, H, W, dtype, train,
                  dropout_p=0.2, device="cuda", drop_seed=0x1234ABCD, fold_bn=False, fused_heads=False, batched_heads=True, fp8=False,
                  guards=False, heads_epilogue=False, actbwd_epilogue=True, merge_reduce=True, nms_heads=False, decode=False,
-                 dual_wgrad=True, fused_convt=True):
-        """merge_reduce=False: every slab reduction and every BatchNorm-backward finaliser a launch of its own;
+                 dual_wgrad=True, fused_convt=True, zero_skip=True):
+        """zero_skip=False: the fused heads pass runs the loss arithmetic of every row tile and stores all of d(logits)
+        (abc_heads_fused_desc.no_zero_skip = 1: the form the zero skip is tested and measured against);
+        merge_reduce=False: every slab reduction and every BatchNorm-backward finaliser a launch of its own;
         dual_wgrad=False: the BatchNorm-backward apply as a pass of its own instead of on the weight gradient's load (the A/B of that
         fusion; part of the engine cache key like the other plan switches);
         actbwd_epilogue=False: every act_bwd pass as a launch of its own (the form the fused epilogue is tested against);
@@ -200,6 +202,7 @@ class Engine:
         # its input (abc_conv_desc.actbwd_*), where the layer has that one reader (_actbwd_target)
         self.actbwd_epilogue = bool(actbwd_epilogue)
         self.merge_reduce = bool(merge_reduce)
+        self.zero_skip = bool(zero_skip)
         self._pending_reduce = None
         self.dt = L.BF16 if dtype == "bf16" else L.F32
         self.tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
@@ -1078,6 +1081,11 @@ class Engine:
             # the dropout keep bits of the three wide heads' features, from the fused pass to its conv2 weight gradient
             self.hf_keep = self.new((3 * B * h * w * 16,), torch.uint8, 0)
             d.keep_mask = self.hf_keep.data_ptr()
+        # which bond-type row tiles carried a target (abc_heads_fused_desc.dl_tiles): the fused pass writes d(logits) only there and
+        # its conv2 weight gradient reads only those; one word per 128-pixel chunk, rewritten by every step
+        self.hf_tiles = self.new((nchunk,), torch.int64, 0)
+        d.dl_tiles = self.hf_tiles.data_ptr()
+        d.no_zero_skip = 0 if self.zero_skip else 1
         for i in range(nh):
             p = "out_modules.%d.conv2" % i
             d.w2[i], d.b2[i], d.logits[i] = self.P(p + ".weight"), self.P(p + ".bias"), self.logits[i].data_ptr()

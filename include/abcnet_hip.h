@@ -487,7 +487,8 @@ typedef struct abc_heads_fused_desc {
     const float* t_atom; const float* t_types; const float* t_charges; const float* t_hs; const float* t_bond;
     const float* t_btypes; const double* t_rho; const double* t_omega;   /* targets, as abc_loss_desc */
     void* dl;                           /* out: d(numerator)/d(logits), bf16, abc_heads_fused_dl_elems() elements:
-                                           per head [chunk][packed rows][128 pixels] (row order: abc_heads_fused_chan_of_row) */
+                                           per head [chunk][packed rows][128 pixels] (row order: abc_heads_fused_chan_of_row);
+                                           with dl_tiles the bond-type rows of tiles whose bit is clear are unspecified (below) */
     void* g;                            /* out: NHWC bf16 [B*h*w][ld]: gradient w.r.t. the BatchNorm outputs, without the head's factor */
     float* bn_partial;                  /* out: [abc_heads_fused_chunks()][2][ld]: sum g, sum g * xhat */
     double* loss_partial;               /* out: [abc_heads_fused_loss_blocks()][16], the layout abc_loss_finalize reduces */
@@ -504,6 +505,17 @@ typedef struct abc_heads_fused_desc {
      * 32 pixels carry no target of a head reads that head's targets from the zero bytes instead of the maps (train.py:107-125 on
      * all-zero targets: identical arithmetic, no HBM traffic -- the maps hold ~62 non-zero 3x3 neighbourhoods per image) */
     const uint32_t* target_flags; const void* zero_bytes;
+    /* ZERO SKIP.  A softmax head (atom types, charges, hydrogens, bond types) adds nothing to its loss and has d(logits) = 0 in a
+     * softmax group all of whose targets are zero (exact for finite logits).  abc_heads_fused_fwd_bwd decides this from the targets it
+     * has just loaded, per 32-row tile of a wave's 32 pixels: a tile without a target stores its logits and runs neither the loss
+     * arithmetic nor the data-gradient MFMAs; a wave without a firing tile writes g = 0 and zero BatchNorm sums.
+     * dl_tiles: optional (both calls or neither), abc_heads_fused_chunks() words, written by every abc_heads_fused_fwd_bwd for every
+     *   chunk: bit 4 mt + w of word c is set iff row tile mt of the bond-type head fired for wave w (pixels 32 w .. 32 w + 31) of chunk c.
+     *   With dl_tiles the bond-type rows of `dl` are written ONLY in tiles whose bit is set -- the 32 rows x 32 pixels of a clear bit are
+     *   unspecified -- and abc_heads_fused_wgrad reads `dl` only where the bit is set.  Without it those tiles are stored as zeros.
+     * no_zero_skip: 0 (a zeroed descriptor) = as above; 1 = every tile takes the full arithmetic and is stored, every used bit of
+     *   dl_tiles is set (the form the skip is tested and measured against). */
+    uint64_t* dl_tiles; int32_t no_zero_skip; int32_t pad_;
 } abc_heads_fused_desc;
 int64_t abc_heads_fused_pack_bytes(void);
 int abc_heads_fused_chunks(const abc_heads_fused_desc* d);
