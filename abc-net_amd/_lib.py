@@ -311,6 +311,7 @@ SYMBOLS = {
     "abc_heads_fused_fwd_bwd": (C.c_int, [P(HeadsFusedDesc), vp]),
     "abc_heads_fused_wgrad": (C.c_int, [P(HeadsFusedDesc), vp]),
     "abc_conv_tile": (C.c_int, [P(ConvDesc), P(i32), P(i32), P(i32)]),
+    "abc_conv_route_info": (C.c_int, [P(ConvDesc), P(i32)]),
     "abc_pack_conv_weights": (C.c_int, [P(PackDesc), vp]),
     "abc_pack_item_bytes": (C.c_int, []),
     "abc_pack_item_fill": (i64, [vp, P(PackDesc), i64]),

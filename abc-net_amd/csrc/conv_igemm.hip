@@ -505,76 +505,116 @@ extern "C" int abc_conv_chunk(int dtype_c, int Cin) {
     return 16;
 }
 
-extern "C" int abc_conv_tile(const abc_conv_desc* d, int32_t* bn, int32_t* mt, int32_t* ck) {
-    if (abc_head_fwd_ok(d)) { *bn = 32; *mt = 2; *ck = abc_conv_chunk(d->dtype_c, d->Cin); return ABC_OK; }   // (a wave: 32 rows x 64 pixels)
-    abc_fast_geom f;
-    if (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible) { *bn = f.BN; *mt = f.MT; *ck = f.CK; return ABC_OK; }
+namespace {
+
+// Which kernel family serves a descriptor, and what the plan must know about it: the ONE place that decides.  The queries the engine
+// sizes its statistics rows, packs its weights and labels its launches from, the batch test and the launch itself all read this.
+enum ConvFamily { CONV_GENERAL, CONV_LEAN, CONV_STEM, CONV_HEAD_FWD, CONV_HEAD_DGRAD, CONV_NARROW };   // abc_conv_variant's numbers
+struct ConvRoute {
+    ConvFamily family;
+    bool served;         // false: the descriptor asks for actbwd_y or heads_epi and no kernel takes that (family is then CONV_GENERAL)
+    int layout;          // abc_pack_desc.layout of the weights: 1 on the weights-direct loop of conv_fast.hip
+    int stat_blocks;     // rows of `stats`; -1: the general kernel, whose turn it would be, refuses the descriptor
+    int bn, mt, ck;      // abc_conv_tile's label: the heads' forward kernel's, else the lean kernel's wherever it is eligible -- also
+                         // where stem, head_dgrad or narrow run -- else the general kernel's
+    bool head_fwd;       // abc_head_fwd_ok(d), whatever else the descriptor asks for
+    abc_fast_geom f;     // f.eligible: the lean kernel takes the descriptor as it stands; its geometry then
+    int geom_rc;         // conv_geom's verdict on the descriptor and, where that is ABC_OK, the general kernel's geometry
     Geom g;
-    int rc = conv_geom(d, &g);
-    if (rc) return rc;
-    *bn = g.BN; *mt = g.MT; *ck = g.CK;
+};
+
+// returns what abc_conv_tile returns: conv_geom's refusal where no kernel's tile labels the descriptor
+static int conv_route(const abc_conv_desc* d, ConvRoute* r) {
+    *r = ConvRoute{};
+    r->stat_blocks = -1;
+    r->geom_rc = conv_geom(d, &r->g);
+    if (d->ntaps > ABC_MAX_TAPS) return r->geom_rc;      // (every question below walks the tap list)
+    // stem, head_fwd, head_dgrad and narrow exclude one another (one input channel; planar output; planar input; 16 or 32 input channels,
+    // nothing planar), the first three exclude the lean kernel (no planes, whole K-chunks), and only narrow's answer reads actbwd_y
+    int stem_blocks = 0;
+    const bool stem = abc_conv_stem_ok(d, &stem_blocks), head_dgrad = abc_head_dgrad_ok(d);
+    r->head_fwd = abc_head_fwd_ok(d);
+    const bool lean = abc_conv_fast_geom(d, &r->f) == ABC_OK && r->f.eligible;
+    r->served = true;
+    if (d->actbwd_y != nullptr) {
+        // act_bwd in the epilogue: by the kernel that would run the plain data gradient anyway -- the narrow-level kernel for its
+        // shapes, else the lean kernel -- and by no other
+        abc_conv_desc plain = *d;
+        plain.actbwd_y = nullptr;
+        if (d->heads_epi != nullptr || stem || r->head_fwd || head_dgrad) r->served = false;
+        else if (abc_conv_narrow_ok(&plain)) { r->served = abc_conv_narrow_ok(d); r->family = CONV_NARROW; }
+        else { r->served = lean; r->family = CONV_LEAN; }
+    } else if (d->heads_epi != nullptr) {      // the heads' epilogue: the lean kernel only
+        r->served = lean; r->family = CONV_LEAN;
+    } else {
+        r->family = stem ? CONV_STEM : r->head_fwd ? CONV_HEAD_FWD : head_dgrad ? CONV_HEAD_DGRAD : abc_conv_narrow_ok(d) ? CONV_NARROW : lean ? CONV_LEAN : CONV_GENERAL;
+    }
+    if (!r->served) r->family = CONV_GENERAL;
+    r->layout = (r->family == CONV_LEAN && r->f.wd) ? 1 : 0;
+    if (r->family == CONV_STEM) r->stat_blocks = stem_blocks;
+    else if (r->family == CONV_NARROW) r->stat_blocks = abc_conv_narrow_stat_blocks(d);
+    else if (lean) r->stat_blocks = (r->f.b_static && d->stats_rows != 4) ? r->f.nwg : r->f.tiles_x * r->f.tiles_y * d->B;   // (resident weights: one row per workgroup)
+    else if (r->geom_rc == ABC_OK) r->stat_blocks = r->g.tiles_x * r->g.tiles_y * d->B;
+    if (r->head_fwd) { r->bn = 32; r->mt = 2; r->ck = abc_conv_chunk(d->dtype_c, d->Cin); }   // (a wave: 32 rows x 64 pixels)
+    else if (lean) { r->bn = r->f.BN; r->mt = r->f.MT; r->ck = r->f.CK; }
+    else { r->bn = r->g.BN; r->mt = r->g.MT; r->ck = r->g.CK; }
+    return (r->head_fwd || lean) ? ABC_OK : r->geom_rc;
+}
+
+static bool grid_exceeds(const abc_conv_desc* d) { return (d->Hg - 1) * d->om + d->oy0 >= d->Hout || (d->Wg - 1) * d->om + d->ox0 >= d->Wout; }
+
+static bool batchable(const abc_conv_desc* d, int n) {
+    // (only descriptors the lean kernel would run anyway)
+    for (int i = 0; i < n; ++i) {
+        ConvRoute r;
+        conv_route(&d[i], &r);
+        if (d[i].stem_x != nullptr || d[i].pool_y != nullptr || d[i].stats != nullptr || r.family != CONV_LEAN || grid_exceeds(&d[i])) return false;
+    }
+    abc_fast_geom g0;
+    return abc_conv_fast_batch_ok(d, n, &g0) != 0;
+}
+
+}  // namespace
+
+extern "C" int abc_conv_tile(const abc_conv_desc* d, int32_t* bn, int32_t* mt, int32_t* ck) {
+    ConvRoute r;
+    if (int rc = conv_route(d, &r)) return rc;
+    *bn = r.bn; *mt = r.mt; *ck = r.ck;
     return ABC_OK;
 }
 
-// the heads' epilogue is served by the lean kernel only; act_bwd in the epilogue by the kernel that would run the plain data gradient
-// anyway -- the narrow-level kernel for its shapes, else the lean kernel -- and by no other
-static bool lean_only(const abc_conv_desc* d) { return d->heads_epi != nullptr; }
-
-// 0: not served; 1: conv_fast.hip; 5: conv_narrow.hip
-static int actbwd_server(const abc_conv_desc* d) {
-    if (d->actbwd_y == nullptr || d->heads_epi != nullptr) return 0;
-    abc_conv_desc p = *d;
-    p.actbwd_y = nullptr;
-    if (abc_conv_stem_ok(&p, nullptr) || abc_head_fwd_ok(&p) || abc_head_dgrad_ok(&p)) return 0;
-    if (abc_conv_narrow_ok(&p)) return abc_conv_narrow_ok(d) ? 5 : 0;
-    abc_fast_geom f;
-    return (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible) ? 1 : 0;
+extern "C" int abc_conv_actbwd_ok(const abc_conv_desc* d) {
+    ConvRoute r;
+    conv_route(d, &r);
+    return (d->actbwd_y != nullptr && r.served) ? 1 : 0;
 }
 
-extern "C" int abc_conv_actbwd_ok(const abc_conv_desc* d) { return actbwd_server(d) != 0 ? 1 : 0; }
-
 extern "C" int abc_conv_variant(const abc_conv_desc* d) {
-    if (d->actbwd_y != nullptr) return actbwd_server(d);
-    if (lean_only(d)) { abc_fast_geom f; return (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible) ? 1 : 0; }
-    if (abc_conv_stem_ok(d, nullptr)) return 2;
-    if (abc_head_fwd_ok(d)) return 3;
-    if (abc_head_dgrad_ok(d)) return 4;
-    if (abc_conv_narrow_ok(d)) return 5;
-    abc_fast_geom f;
-    if (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible) return 1;
-    return 0;
+    ConvRoute r;
+    conv_route(d, &r);
+    return r.family;
 }
 
 extern "C" int abc_conv_weight_layout(const abc_conv_desc* d) {
-    if (d->actbwd_y != nullptr && actbwd_server(d) == 5) return 0;
-    if (lean_only(d) || d->actbwd_y != nullptr) { abc_fast_geom f; return (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible && f.wd) ? 1 : 0; }
-    if (abc_conv_stem_ok(d, nullptr) || abc_head_fwd_ok(d) || abc_head_dgrad_ok(d) || abc_conv_narrow_ok(d)) return 0;
-    abc_fast_geom f;
-    return (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible && f.wd) ? 1 : 0;   // the weights-direct loop of conv_fast.hip
+    ConvRoute r;
+    conv_route(d, &r);
+    return r.layout;
 }
 
 extern "C" int abc_conv_stat_blocks(const abc_conv_desc* d) {
-    if (d->actbwd_y != nullptr && actbwd_server(d) == 5) return abc_conv_narrow_stat_blocks(d);
-    if (!lean_only(d) && d->actbwd_y == nullptr) {
-        { int nb = 0; if (abc_conv_stem_ok(d, &nb)) return nb; }
-        if (abc_conv_narrow_ok(d)) return abc_conv_narrow_stat_blocks(d);
-    }
-    abc_fast_geom f;
-    if (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible) return (f.b_static && d->stats_rows != 4) ? f.nwg : f.tiles_x * f.tiles_y * d->B;   // (resident weights: one row per workgroup)
-    Geom g;
-    if (conv_geom(d, &g)) return -1;
-    return g.tiles_x * g.tiles_y * d->B;
+    ConvRoute r;
+    conv_route(d, &r);
+    return r.stat_blocks;
 }
 
-extern "C" int abc_conv_fwd(const abc_conv_desc* d, abc_stream_t stream);
-static bool batchable(const abc_conv_desc* d, int n) {
-    // (only descriptors the lean kernel would run anyway)
-    for (int i = 0; i < n; ++i)
-        if (d[i].stem_x != nullptr || d[i].pool_y != nullptr || d[i].stats != nullptr || abc_conv_stem_ok(&d[i], nullptr) || abc_head_fwd_ok(&d[i]) ||
-            abc_head_dgrad_ok(&d[i]) || abc_conv_narrow_ok(&d[i]) || (d[i].Hg - 1) * d[i].om + d[i].oy0 >= d[i].Hout || (d[i].Wg - 1) * d[i].om + d[i].ox0 >= d[i].Wout)
-            return false;
-    abc_fast_geom g0;
-    return abc_conv_fast_batch_ok(d, n, &g0) != 0;
+// the plan's one question (read-only: the same conv_route answer): info[7] = {variant, weight_layout, stat_blocks, bn, mt, ck, actbwd_ok};
+// returns, and leaves bn / mt / ck alone, as abc_conv_tile does
+extern "C" int abc_conv_route_info(const abc_conv_desc* d, int32_t* info) {
+    ConvRoute r;
+    const int rc = conv_route(d, &r);
+    info[0] = r.family; info[1] = r.layout; info[2] = r.stat_blocks; info[6] = (d->actbwd_y != nullptr && r.served) ? 1 : 0;
+    if (rc == ABC_OK) { info[3] = r.bn; info[4] = r.mt; info[5] = r.ck; }
+    return rc;
 }
 
 extern "C" int abc_conv_batch_ok(const abc_conv_desc* d, int32_t n) { return (d != nullptr && batchable(d, n)) ? 1 : 0; }
@@ -588,37 +628,58 @@ extern "C" int abc_conv_fwd_batch(const abc_conv_desc* d, int32_t n, abc_stream_
 }
 
 extern "C" int abc_conv_fwd(const abc_conv_desc* d, abc_stream_t stream) {
+    ConvRoute r;
+    conv_route(d, &r);
     if (d->dtype_c == ABC_FP8 || d->dtype_out == ABC_FP8 || d->dtype_in == ABC_FP8) {
-        // the fp8 inference graph: the heads' 1x1 convolution into NCHW f32 (heads.hip), else the lean kernel's weights-direct tile
-        if (abc_head_fwd_ok(d)) return abc_head_fwd_launch(d, stream);
+        // the fp8 inference graph: the heads' 1x1 convolution into NCHW f32 (heads.hip), else the lean kernel's weights-direct tile --
+        // whatever else the descriptor asks for, so by the route's two plain answers and not by its family
+        if (r.head_fwd) return abc_head_fwd_launch(d, stream);
         if (d->src.pool || d->src.planar || d->planar_out || d->src.Hx != d->Hin || d->src.Wx != d->Win || d->stem_x != nullptr || d->pool_y != nullptr)
             return abc_fail(ABC_EUNSUPPORTED, "conv: fp8 needs a plain NHWC input and output");
         if ((d->src.ldx * abc_dsize(d->dtype_in)) % 16 || (d->cin_off * abc_dsize(d->dtype_in)) % 16 || (d->ldy * abc_dsize(d->dtype_out)) % 16 || (d->cout_off * abc_dsize(d->dtype_out)) % 16)
             return abc_fail(ABC_EINVAL, "conv: fp8 tensors must keep 16-byte alignment");
-        if ((d->Hg - 1) * d->om + d->oy0 >= d->Hout || (d->Wg - 1) * d->om + d->ox0 >= d->Wout) return abc_fail(ABC_EINVAL, "conv: output grid exceeds output tensor");
+        if (grid_exceeds(d)) return abc_fail(ABC_EINVAL, "conv: output grid exceeds output tensor");
         if (d->heads_epi != nullptr && d->dtype_out != ABC_FP8) return abc_fail(ABC_EINVAL, "conv: heads_epi with e4m3 operands needs dtype_out = ABC_FP8 (the features' type)");
-        abc_fast_geom f;
-        if (abc_conv_fast_geom(d, &f) != ABC_OK || !f.eligible) return abc_fail(ABC_EUNSUPPORTED, "conv: fp8 is served for 3x3, stride 1, Cin % 64 == 0, Cout % 128 == 0 only");
-        return abc_conv_fast_launch(d, f, stream);
+        if (!r.f.eligible) return abc_fail(ABC_EUNSUPPORTED, "conv: fp8 is served for 3x3, stride 1, Cin % 64 == 0, Cout % 128 == 0 only");
+        return abc_conv_fast_launch(d, r.f, stream);
     }
-    Geom g;
-    int rc = conv_geom(d, &g);  // (also validates the descriptor)
-    if (rc) return rc;
+    if (r.geom_rc) return r.geom_rc;  // (conv_geom also validates the descriptor, whichever family serves it)
+    const Geom& g = r.g;
     if (d->src.pool && (d->src.Hx / 2 != d->Hin || d->src.Wx / 2 != d->Win))
         return abc_fail(ABC_EINVAL, "conv: pooled dims mismatch");
     if (!d->src.pool && (d->src.Hx != d->Hin || d->src.Wx != d->Win)) return abc_fail(ABC_EINVAL, "conv: dims mismatch");
     if (!d->src.planar && d->Cin % 16 == 0 && ((d->src.ldx * (d->dtype_in == ABC_BF16 ? 2 : 4)) % 16 || (d->cin_off % 8)))
         return abc_fail(ABC_EINVAL, "conv: input stride/offset must keep 16-byte alignment");
-    ConvK k;
+    if (d->src.planar && (d->dtype_in != ABC_F32 || d->src.pool || d->src.drop_p > 0.f))
+        return abc_fail(ABC_EUNSUPPORTED, "conv: planar input must be f32 without pool/dropout");
+    if (d->planar_out && (d->dtype_out != ABC_F32 || d->om != 1 || d->oy0 || d->ox0))
+        return abc_fail(ABC_EUNSUPPORTED, "conv: planar output must be f32, unit output stride");
+    if (d->out_act && d->planar_out) return abc_fail(ABC_EUNSUPPORTED, "conv: out_act needs an NHWC output");
+    if (d->accumulate && d->planar_out) return abc_fail(ABC_EUNSUPPORTED, "conv: accumulate needs an NHWC output");
+    // the kernel's grid must address only in-range output pixels
+    if (grid_exceeds(d)) return abc_fail(ABC_EINVAL, "conv: output grid exceeds output tensor");
+    if (!r.served)
+        return d->heads_epi != nullptr ? abc_fail(ABC_EUNSUPPORTED, "conv: heads_epi is served by the 3x3 weights-direct tile only")
+                                       : abc_fail(ABC_EUNSUPPORTED, "conv: actbwd_y is not served for this descriptor (ask abc_conv_actbwd_ok first)");
+    if (d->heads_epi == nullptr && d->actbwd_y == nullptr) {
+        if (d->stem_x != nullptr && r.family != CONV_NARROW) return abc_fail(ABC_EUNSUPPORTED, "conv: the fused first convolution (stem_x) is served by the narrow-level kernel only");
+        if (d->pool_y != nullptr && r.family != CONV_NARROW) return abc_fail(ABC_EUNSUPPORTED, "conv: pool_y is served by the narrow-level kernel only (abc_conv_variant == 5)");
+        if (d->head_aux != nullptr && r.family != CONV_HEAD_FWD) return abc_fail(ABC_EUNSUPPORTED, "conv: head_aux is served by the heads' 1x1 kernel only (abc_conv_variant == 3)");
+    }
+    switch (r.family) {
+        case CONV_STEM: return abc_conv_stem_launch(d, stream);
+        case CONV_HEAD_FWD: return abc_head_fwd_launch(d, stream);
+        case CONV_HEAD_DGRAD: return abc_head_dgrad_launch(d, stream);
+        case CONV_NARROW: return abc_conv_narrow_launch(d, stream);
+        case CONV_LEAN: return abc_conv_fast_launch(d, r.f, stream);
+        case CONV_GENERAL: break;
+    }
+    ConvK k{};
     k.src.x = d->src.x; k.src.scale = d->src.scale; k.src.shift = d->src.shift; k.src.slope = d->src.slope;
     k.src.Hx = d->src.Hx; k.src.Wx = d->src.Wx; k.src.ldx = d->src.ldx; k.src.pool = d->src.pool;
     k.src.drop_p = d->src.drop_p; k.src.drop_seed = d->src.drop_seed; k.src.drop_salt = d->src.drop_salt;
     k.src.planar = d->src.planar; k.src.ctot = d->src.ctot;
     k.planar_out = d->planar_out; k.ctot_out = d->ctot_out;
-    if (d->src.planar && (d->dtype_in != ABC_F32 || d->src.pool || d->src.drop_p > 0.f))
-        return abc_fail(ABC_EUNSUPPORTED, "conv: planar input must be f32 without pool/dropout");
-    if (d->planar_out && (d->dtype_out != ABC_F32 || d->om != 1 || d->oy0 || d->ox0))
-        return abc_fail(ABC_EUNSUPPORTED, "conv: planar output must be f32, unit output stride");
     k.w = d->w; k.bias = d->bias; k.y = d->y; k.stats = d->stats;
     k.B = d->B; k.Hin = d->Hin; k.Win = d->Win; k.cin_off = d->cin_off; k.Cin = d->Cin; k.nchunks = abc_cdiv(d->Cin, g.CK);
     k.Hg = d->Hg; k.Wg = d->Wg; k.Hout = d->Hout; k.Wout = d->Wout; k.ldy = d->ldy; k.cout_off = d->cout_off;
@@ -628,41 +689,12 @@ extern "C" int abc_conv_fwd(const abc_conv_desc* d, abc_stream_t stream) {
     k.sB_off = g.a_bufs * g.sA_bytes; k.coef_off = g.coef_off; k.cstride = g.cstride;
     k.sB_bytes = g.sB_bytes; k.tap_off = g.tap_off; k.fast_a = g.fast_a; k.ntiles = g.grid; k.b_static = g.b_static; k.stg_off = g.stg_off;
     k.stats_rows = d->stats_rows; k.accumulate = d->accumulate; k.out_act = d->out_act; k.out_slope = d->out_slope;
-    if (d->out_act && d->planar_out) return abc_fail(ABC_EUNSUPPORTED, "conv: out_act needs an NHWC output");
-    if (d->accumulate && d->planar_out) return abc_fail(ABC_EUNSUPPORTED, "conv: accumulate needs an NHWC output");
     k.magic = 65536 / g.HW + 1;
     k.bytesA = (unsigned)((int64_t)d->B * d->src.Hx * d->src.Wx * d->src.ldx * (d->dtype_in == ABC_BF16 ? 2 : 4));
     k.bytesW = (unsigned)((int64_t)d->ntaps * k.nchunks * d->Cout_pad * g.CK * (d->dtype_c == ABC_BF16 ? 2 : 4));
     for (int t = 0; t < d->ntaps; ++t) {
         k.ty[t] = (int8_t)(d->tap_dy[t] - g.dy_min);
         k.tx[t] = (int8_t)(d->tap_dx[t] - g.dx_min);
-    }
-    // the kernel's grid must address only in-range output pixels
-    if ((d->Hg - 1) * d->om + d->oy0 >= d->Hout || (d->Wg - 1) * d->om + d->ox0 >= d->Wout)
-        return abc_fail(ABC_EINVAL, "conv: output grid exceeds output tensor");
-    if (d->heads_epi != nullptr) {
-        abc_fast_geom f;
-        if (abc_conv_fast_geom(d, &f) != ABC_OK || !f.eligible) return abc_fail(ABC_EUNSUPPORTED, "conv: heads_epi is served by the 3x3 weights-direct tile only");
-        return abc_conv_fast_launch(d, f, stream);
-    }
-    if (d->actbwd_y != nullptr) {
-        const int srv = actbwd_server(d);
-        abc_fast_geom f;
-        if (srv == 5) return abc_conv_narrow_launch(d, stream);
-        if (srv != 1 || abc_conv_fast_geom(d, &f) != ABC_OK || !f.eligible)
-            return abc_fail(ABC_EUNSUPPORTED, "conv: actbwd_y is not served for this descriptor (ask abc_conv_actbwd_ok first)");
-        return abc_conv_fast_launch(d, f, stream);
-    }
-    if (d->stem_x != nullptr && !abc_conv_narrow_ok(d)) return abc_fail(ABC_EUNSUPPORTED, "conv: the fused first convolution (stem_x) is served by the narrow-level kernel only");
-    if (d->pool_y != nullptr && !abc_conv_narrow_ok(d)) return abc_fail(ABC_EUNSUPPORTED, "conv: pool_y is served by the narrow-level kernel only (abc_conv_variant == 5)");
-    if (d->head_aux != nullptr && !abc_head_fwd_ok(d)) return abc_fail(ABC_EUNSUPPORTED, "conv: head_aux is served by the heads' 1x1 kernel only (abc_conv_variant == 3)");
-    if (abc_conv_stem_ok(d, nullptr)) return abc_conv_stem_launch(d, stream);
-    if (abc_head_fwd_ok(d)) return abc_head_fwd_launch(d, stream);
-    if (abc_head_dgrad_ok(d)) return abc_head_dgrad_launch(d, stream);
-    if (abc_conv_narrow_ok(d)) return abc_conv_narrow_launch(d, stream);
-    {
-        abc_fast_geom f;
-        if (abc_conv_fast_geom(d, &f) == ABC_OK && f.eligible) return abc_conv_fast_launch(d, f, stream);
     }
     hipStream_t st = (hipStream_t)stream;
     const int di = d->dtype_in, dc = d->dtype_c, dout = d->dtype_out;

@@ -421,24 +421,23 @@ class Engine:
             d.actbwd_y, d.actbwd_ld, d.actbwd_coff = p.y.data_ptr(), p.ld, p.coff
             d.actbwd_scale, d.actbwd_shift, d.actbwd_slope = p.scale.data_ptr(), p.shift.data_ptr(), p.slopes.data_ptr()
             d.actbwd_mean, d.actbwd_invstd = p.mean.data_ptr(), p.invstd.data_ptr()
-            d.stats = y.data_ptr()      # (placeholder for the query: the rows are allocated below)
             stats = True
-            if not self.lib.abc_conv_actbwd_ok(C.byref(d)):
-                return None
-        if only_variant is not None and self.lib.abc_conv_variant(C.byref(d)) != only_variant:
+        if stats:
+            d.stats = y.data_ptr()      # (placeholder: the library's answers read whether it is NULL; the rows are allocated below)
+        info = (L.i32 * 7)()
+        rc = self.lib.abc_conv_route_info(C.byref(d), info)
+        variant, layout, nblk, bn, mt, ck, actbwd_ok = info
+        if (actbwd is not None and not actbwd_ok) or (only_variant is not None and variant != only_variant):
             return None
-        nblk = self.lib.abc_conv_stat_blocks(C.byref(d))
+        L.check(rc, "conv_route_info")
+        self._w_layout[d.w] = layout
         st = None
         if stats:
             st = self.new((nblk, stats_rows, Cout), torch.float32)
             d.stats = st.data_ptr()
-        self._w_layout[d.w] = self.lib.abc_conv_weight_layout(C.byref(d))
-        bn_, mt_, ck_ = L.i32(), L.i32(), L.i32()
-        L.check(self.lib.abc_conv_tile(C.byref(d), C.byref(bn_), C.byref(mt_), C.byref(ck_)), "conv_tile")
-        bn, mt, ck = bn_.value, mt_.value, ck_.value
         npx = self.B * gh * gw
         in_px = self.B * lh * lw * (4 if src.pool else 1)
-        kname = ("conv_igemm", "conv_fast", "stem_conv", "head_fwd", "head_dgrad", "conv_narrow")[self.lib.abc_conv_variant(C.byref(d))]
+        kname = ("conv_igemm", "conv_fast", "stem_conv", "head_fwd", "head_dgrad", "conv_narrow")[variant]
         if actbwd is not None:
             kname += "+act_bwd"
         meta = {"kernel": "%s<%s,%s,%s,CK%d,BN%d,S%d,MT%d>" % (kname, self._dn(src.dt), self._dn(cdt), self._dn(y_dt), ck, bn, stride, mt),

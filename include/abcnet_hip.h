@@ -189,6 +189,10 @@ int abc_conv_variant(const abc_conv_desc* d);
 int abc_conv_fwd(const abc_conv_desc* d, abc_stream_t stream);
 /* tile the launcher picks for this descriptor: BN output channels x (2*mt x 16) pixels per workgroup, K-chunk ck */
 int abc_conv_tile(const abc_conv_desc* d, int32_t* bn, int32_t* mt, int32_t* ck);
+/* the five queries in one, for a plan that needs them all: info[7] = {abc_conv_variant, abc_conv_weight_layout, abc_conv_stat_blocks,
+ * bn, mt, ck, abc_conv_actbwd_ok}; returns what abc_conv_tile returns (and like it leaves bn, mt, ck alone where that is not 0).  Fill
+ * everything first, `stats` included (a placeholder will do: the answers read whether it is NULL).  Host only */
+int abc_conv_route_info(const abc_conv_desc* d, int32_t* info);
 
 /* channels per K-chunk used by the packed weight layout for (compute dtype, Cin) */
 int abc_conv_chunk(int dtype_c, int Cin);

@@ -1,6 +1,6 @@
 """Fingerprint of the launch plans the engine builds, without a GPU.
 
-    python profiles/tools/plan_fingerprint.py [--repo TREE] [--only SUBSTRING] [--dump DIR] [--routes FILE]
+    python profiles/tools/plan_fingerprint.py [--repo TREE] [--only SUBSTRING] [--dump DIR] [--routes FILE] [--conv-routes FILE]
 
 Builds every plan of CONFIGS with Engine(..., device="cpu") and replays pack_ops, fwd_ops and bwd_ops against a proxy of the library that
 forwards the plan-time queries and, for a launch (any call whose last argument is the replay's stream), records the function name and
@@ -14,7 +14,13 @@ on both (--repo names the tree whose package is imported; it needs its libabcnet
 --routes FILE collects every distinct abc_wgrad_desc the plans hand to the library, query or launch, and writes them as JSON with the
 answers of that tree's library to abc_wgrad_rowsum_ok / _fuses_apply / _pads / _tile / _blocks: the fixture tests/golden/wgrad_routes.json
 (tests/test_cabi_and_host.py rebuilds the descriptors from it), a table of numbers with one row per descriptor.  Pointers are kept as
-null / non-null only; the distinct abc_wgrad_reduce_desc are counted (no query takes one)."""
+null / non-null only; the distinct abc_wgrad_reduce_desc are counted (no query takes one).
+
+--conv-routes FILE does the same for abc_conv_desc: every distinct one handed to a query or a launch, the arrays given to
+abc_conv_batch_ok, abc_conv_fwd_batch and abc_heads_batch included, with that library's answers to abc_conv_variant / _weight_layout /
+_stat_blocks / _tile / _actbwd_ok, and a second table of the distinct arrays as row indices with abc_conv_batch_ok's answer: the fixture
+tests/golden/conv_routes.json.  A descriptor is recorded as it is when it is handed over, so one that the engine asks about before and
+after it sets `stats` is two rows.  The tool checks that the rebuilt descriptor gets the answers the engine's own one got."""
 import json
 import argparse
 import ctypes as C
@@ -28,6 +34,7 @@ ap.add_argument("--repo", default=os.path.dirname(os.path.dirname(os.path.dirnam
 ap.add_argument("--only", default="")
 ap.add_argument("--dump", default=None)
 ap.add_argument("--routes", default=None)
+ap.add_argument("--conv-routes", default=None)
 args = ap.parse_args()
 sys.path.insert(0, args.repo)
 sys.path.insert(0, os.path.join(args.repo, "tests"))
@@ -49,6 +56,7 @@ class Proxy:
     def __init__(self, real):
         self.real, self.rec = real, None
         self.wgrads, self.reduces = {}, set()      # (--routes) distinct descriptors seen, in order of first appearance
+        self.convs, self.batches = {}, {}          # (--conv-routes) the same, and the distinct arrays as tuples of descriptor keys
 
     def note(self, v):
         v = getattr(v, "_obj", v)      # byref(x)
@@ -60,15 +68,23 @@ class Proxy:
             self.wgrads.setdefault(json.dumps(f, sort_keys=True), f)
         elif isinstance(v, L.WgradReduceDesc):
             self.reduces.add(json.dumps(desc_fields(v), sort_keys=True))
+        elif isinstance(v, L.ConvDesc) and args.conv_routes:
+            f = desc_fields(v)
+            key, ans = json.dumps(f, sort_keys=True), conv_answers(self.real, v)
+            if self.convs.setdefault(key, (f, ans))[1] != ans:
+                raise RuntimeError("a query reads more of a descriptor than null / non-null pointers: %s" % key)
+            return key
 
     def __getattr__(self, name):
         fn = getattr(self.real, name)
         types = L.SYMBOLS[name][1] if name in L.SYMBOLS else None
 
         def call(*a):
-            if args.routes:
+            if args.routes or args.conv_routes:
                 for v in a:
                     self.note(v)
+            if args.conv_routes and name in ("abc_conv_batch_ok", "abc_conv_fwd_batch", "abc_heads_batch"):
+                self.batches.setdefault(tuple(self.note(a[0][i]) for i in range(a[1])), self.real.abc_conv_batch_ok(a[0], a[1]))
             if self.rec is not None and a and a[-1] == STREAM and isinstance(a[-1], int):
                 self.rec.call(name, a[:-1], types)
                 return 0
@@ -93,9 +109,9 @@ def desc_fields(v, prefix=""):
     return out
 
 
-def desc_build(f):
+def desc_build(f, cls=L.WgradDesc):
     """the inverse: a non-null pointer is a dummy address (the queries read through none of them)"""
-    v = L.WgradDesc()
+    v = cls()
     for name, x in f.items():
         o, n = v, name
         if "." in name:
@@ -120,22 +136,42 @@ def answers(lib, d):
             lib.abc_wgrad_blocks(C.byref(d))]
 
 
-def routes_table(lib, descs):
-    """the fixture: one row of numbers per descriptor -- its own fields in `columns` order, where "p", "q" and "taps" are indices into the
-    tables of distinct operands (fields in `operand` order) and tap lists -- then ANSWERS"""
+CONV_ANSWERS = ("variant", "layout", "stat_blocks", "tile_rc", "bn", "mt", "ck", "actbwd_ok")
+
+
+def conv_answers(lib, d):
+    bn, mt, ck = C.c_int32(-7), C.c_int32(-7), C.c_int32(-7)
+    rt = lib.abc_conv_tile(C.byref(d), C.byref(bn), C.byref(mt), C.byref(ck))
+    return [lib.abc_conv_variant(C.byref(d)), lib.abc_conv_weight_layout(C.byref(d)), lib.abc_conv_stat_blocks(C.byref(d)), rt, bn.value,
+            mt.value, ck.value, lib.abc_conv_actbwd_ok(C.byref(d))]
+
+
+def routes_table(lib, descs, cls=L.WgradDesc, operands="pq", answers=answers, names_of_answers=ANSWERS):
+    """the fixture: one row of numbers per descriptor -- its own fields in `columns` order, where the operands ("p", "q"; "src") and
+    "taps" are indices into the tables of distinct operands (fields in `operand` order) and tap lists -- then the answers"""
     names = [n for n in descs[0] if n not in ("tap_dy", "tap_dx") and any(f[n] for f in descs)]      # (zero everywhere: left out)
-    opnd = sorted({n[2:] for n in names if "." in n}, key=[n for n, _t in L.ActSrc._fields_].index)
+    opnd = sorted({n.split(".")[1] for n in names if "." in n}, key=[n for n, _t in L.ActSrc._fields_].index)
     cols = [n for n in names if "." not in n]
-    tabs, rows = {"p": [], "q": [], "taps": []}, []
+    tabs, rows = dict({o: [] for o in operands}, taps=[]), []
 
     def index(tab, x):
         if x not in tab:
             tab.append(x)
         return tab.index(x)
     for f in descs:
-        rows.append([index(tabs[o], [f[o + "." + n] for n in opnd]) for o in "pq"] + [f[n] for n in cols] +
-                    [index(tabs["taps"], [f["tap_dy"], f["tap_dx"]])] + answers(lib, desc_build(f)))
-    return dict(tabs, columns=["p", "q"] + cols + ["taps"] + list(ANSWERS), operand=opnd, rows=rows)
+        rows.append([index(tabs[o], [f[o + "." + n] for n in opnd]) for o in operands] + [f[n] for n in cols] +
+                    [index(tabs["taps"], [f["tap_dy"], f["tap_dx"]])] + answers(lib, desc_build(f, cls)))
+    return dict(tabs, columns=list(operands) + cols + ["taps"] + list(names_of_answers), operand=opnd, rows=rows)
+
+
+def write_table(path, tab, keys):
+    """`keys` one per line, then the rows, eight to a line"""
+    rows = tab.pop("rows")
+    enc = lambda x: json.dumps(x, separators=(",", ":"))      # noqa: E731
+    with open(path, "w") as f:
+        f.write("{" + "".join('"%s":%s,\n' % (k, enc(tab[k])) for k in keys) + '"rows":[\n')
+        f.write(",\n".join(",".join(enc(r) for r in rows[i:i + 8]) for i in range(0, len(rows), 8)) + "\n]}\n")
+    return len(rows)
 
 
 def tensors_of(x, depth=0):
@@ -299,13 +335,21 @@ def main():
         del eng, m
         gc.collect()
     if args.routes:
-        tab = routes_table(proxy.real, list(proxy.wgrads.values()))
-        rows = tab.pop("rows")
-        enc = lambda x: json.dumps(x, separators=(",", ":"))      # noqa: E731
-        with open(args.routes, "w") as f:
-            f.write("{" + "".join('"%s":%s,\n' % (k, enc(tab[k])) for k in ("columns", "operand", "p", "q", "taps")) + '"rows":[\n')
-            f.write(",\n".join(",".join(enc(r) for r in rows[i:i + 8]) for i in range(0, len(rows), 8)) + "\n]}\n")
-        print("%d distinct abc_wgrad_desc, %d distinct abc_wgrad_reduce_desc" % (len(rows), len(proxy.reduces)), file=sys.stderr)
-
+        n = write_table(args.routes, routes_table(proxy.real, list(proxy.wgrads.values())), ("columns", "operand", "p", "q", "taps"))
+        print("%d distinct abc_wgrad_desc, %d distinct abc_wgrad_reduce_desc" % (n, len(proxy.reduces)), file=sys.stderr)
+    if args.conv_routes:
+        keys = list(proxy.convs)
+        tab = routes_table(proxy.real, [f for f, _a in proxy.convs.values()], L.ConvDesc, ("src",), conv_answers, CONV_ANSWERS)
+        if [r[-len(CONV_ANSWERS):] for r in tab["rows"]] != [a for _f, a in proxy.convs.values()]:
+            raise RuntimeError("a rebuilt abc_conv_desc is answered differently from the engine's own")
+        tab["batches"] = []
+        for batch, ok in proxy.batches.items():
+            idx = [keys.index(k) for k in batch]
+            arr = (L.ConvDesc * len(idx))(*[desc_build(proxy.convs[k][0], L.ConvDesc) for k in batch])
+            if proxy.real.abc_conv_batch_ok(arr, len(idx)) != ok:
+                raise RuntimeError("a rebuilt batch is answered differently from the engine's own")
+            tab["batches"].append([idx, ok])
+        n = write_table(args.conv_routes, tab, ("columns", "operand", "src", "taps", "batches"))
+        print("%d distinct abc_conv_desc, %d distinct batches" % (n, len(tab["batches"])), file=sys.stderr)
 
 main()

@@ -642,3 +642,54 @@ def test_wgrad_routes_match_the_recorded_answers(golden_dir):
         tiles.add((at.value, bt.value))
     # the fixture reaches every family: head, one-channel, 16-channel, 5x5 32-channel, and each tile shape of the general kernel
     assert tiles >= {(0, 0), (0, 1), (0, 2), (0, 3), (1, 1), (2, 1), (2, 2), (1, 4), (4, 2)}
+
+
+def test_conv_routes_match_the_recorded_answers(golden_dir):
+    """every distinct abc_conv_desc the 44 plans of profiles/tools/plan_fingerprint.py hand to the library, query or launch, gets the
+    recorded answers from the five routing queries -- abc_conv_variant, _weight_layout, _stat_blocks, _tile, _actbwd_ok -- and the same
+    numbers from abc_conv_route_info.  tests/golden/conv_routes.json (written by that tool's --conv-routes before the queries became
+    reads of one route) is a table in the form of wgrad_routes.json: a row holds a descriptor's fields in `columns` order (pointers as
+    0 / 1; fields that are zero in every row left out), where "src" and "taps" are indices into the tables of distinct operands (fields
+    in `operand` order) and tap lists, and then the eight answers.  A descriptor is recorded as it stood when it was handed over: one
+    the engine asked about before and after it set `stats` is two rows.  `batches` lists the arrays handed to abc_conv_batch_ok,
+    abc_conv_fwd_batch and abc_heads_batch as row indices, each with abc_conv_batch_ok's answer"""
+    import ctypes as C
+    import json
+    with open(os.path.join(golden_dir, "conv_routes.json")) as f:
+        tab = json.load(f)
+    cols, lib = tab["columns"], L.load()
+    nf = cols.index("taps")
+    assert cols[0] == "src" and cols[nf + 1:] == ["variant", "layout", "stat_blocks", "tile_rc", "bn", "mt", "ck", "actbwd_ok"]
+    assert len(tab["rows"]) >= 1000
+    descs, pairs, servers, refused = [], set(), set(), 0
+    for row in tab["rows"]:
+        d = L.ConvDesc()
+        fields = [(d, n, x) for n, x in zip(cols[1:nf], row[1:])] + [(d.src, n, x) for n, x in zip(tab["operand"], tab["src"][row[0]])]
+        for o, n, x in fields:
+            if dict(o._fields_)[n] is C.c_void_p:
+                x = 0x1000 if x else None      # (non-null: the queries read through no pointer)
+            setattr(o, n, x)
+        for i, (dy, dx) in enumerate(zip(*tab["taps"][row[nf]])):
+            d.tap_dy[i], d.tap_dx[i] = dy, dx
+        descs.append(d)
+        variant, layout, blocks, tile_rc, bn, mt, ck, actbwd_ok = row[nf + 1:]
+        got = [L.i32(-7), L.i32(-7), L.i32(-7)]
+        rt = lib.abc_conv_tile(C.byref(d), *map(C.byref, got))
+        assert [lib.abc_conv_variant(C.byref(d)), lib.abc_conv_weight_layout(C.byref(d)), lib.abc_conv_stat_blocks(C.byref(d)), rt] + \
+            [g.value for g in got] + [lib.abc_conv_actbwd_ok(C.byref(d))] == row[nf + 1:], dict(zip(cols, row))
+        info = (L.i32 * 7)(*([-7] * 7))
+        assert lib.abc_conv_route_info(C.byref(d), info) == tile_rc, dict(zip(cols, row))
+        assert list(info) == [variant, layout, blocks, bn, mt, ck, actbwd_ok], dict(zip(cols, row))
+        pairs.add((variant, layout))
+        if d.actbwd_y:
+            servers.add(variant if actbwd_ok else None)
+            refused += not actbwd_ok
+    # every (kernel family, weight layout) there is; act_bwd in the epilogue served by the lean and by the narrow-level kernel, and refused
+    assert pairs == {(0, 0), (1, 0), (1, 1), (2, 0), (3, 0), (4, 0), (5, 0)}
+    assert servers == {1, 5, None} and refused >= 1
+    answers = set()
+    for rows, ok in tab["batches"]:
+        arr = (L.ConvDesc * len(rows))(*[descs[i] for i in rows])
+        assert lib.abc_conv_batch_ok(arr, len(rows)) == ok, rows
+        answers.add(ok)
+    assert answers == {0, 1}

@@ -186,6 +186,9 @@ def test_case_tables_reach_every_route():
             d = T.conv_desc_host(c, dt)
             v, lay = lib.abc_conv_variant(C.byref(d)), lib.abc_conv_weight_layout(C.byref(d))
             assert (v, lay) == (c["variant"][i], c["layout"][i]), (c["id"], dt, v, lay)
+            info = (C.c_int32 * 7)(*([-7] * 7))
+            assert lib.abc_conv_route_info(C.byref(d), info) == 0, (c["id"], dt)
+            assert tuple(info[:2]) == (c["variant"][i], c["layout"][i]), (c["id"], dt, tuple(info))
             seen.add((v, lay))
     assert seen == {(0, 0), (1, 0), (1, 1), (2, 0), (5, 0)}
     for a in T.CONVT_FUSED_CASES:
