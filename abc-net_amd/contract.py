@@ -166,7 +166,7 @@ class CandidateLists:
 
 
 class MoleculeRows:
-    """GraphAssembler's output, read in place by MolBlockWriter, GraphScore and GraphSimilarity: int32 tensors of SHAPES; a row of
+    """GraphAssembler's output, read in place by MolBlockWriter, SmilesWriter, GraphScore and GraphSimilarity: int32 tensors of SHAPES; a row of
     mol_counts is (atoms, bonds, implicit-H entries, L.MOL_* status bits); mol_implh is read by the text alone"""
     NAMES = ("mol_counts", "mol_atoms", "mol_bonds", "mol_implh")
     SHAPES = staticmethod(lambda B, cap_atoms, cap_mol_bonds: [(B, 4), (B, cap_atoms, ATOM_W), (B, cap_mol_bonds, MOL_BOND_W), (B, cap_atoms)])
@@ -176,15 +176,18 @@ class MoleculeRows:
         self.B, self.cap_atoms, self.cap_mol_bonds, self.device = mol_atoms.shape[0], mol_atoms.shape[1], mol_bonds.shape[1], mol_atoms.device
 
     @classmethod
-    def checked(cls, who, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, max_cap_atoms=None, need_implh=False, n_valid=None):
+    def checked(cls, who, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, max_cap_atoms=None, need_implh=False, n_valid=None,
+                max_cap_mol_bonds=None):
         """a MoleculeRows or the separate tensors (hand-made rows): type, shape, range, n_valid's form (ValueError), then device (AbcNetHipError)"""
         if isinstance(mol_counts, cls):
             mol_counts, mol_atoms, mol_bonds, mol_implh = mol_counts.tensors
         read = (mol_counts, mol_atoms, mol_bonds) + ((mol_implh,) if need_implh else ())
         B, cap_atoms, cap_mol_bonds = _require_layout(who, cls.NAMES, read, cls.SHAPES)
-        if B < 1 or cap_atoms < 1 or cap_mol_bonds < 1 or (max_cap_atoms is not None and cap_atoms > max_cap_atoms):
-            raise ValueError("%s: B >= 1, cap_atoms %s and cap_mol_bonds >= 1, got %d, %d, %d"
-                             % (who, ">= 1" if max_cap_atoms is None else "1..%d" % max_cap_atoms, B, cap_atoms, cap_mol_bonds))
+        if (B < 1 or cap_atoms < 1 or cap_mol_bonds < 1 or (max_cap_atoms is not None and cap_atoms > max_cap_atoms)
+                or (max_cap_mol_bonds is not None and cap_mol_bonds > max_cap_mol_bonds)):
+            raise ValueError("%s: B >= 1, cap_atoms %s and cap_mol_bonds %s, got %d, %d, %d"
+                             % (who, ">= 1" if max_cap_atoms is None else "1..%d" % max_cap_atoms,
+                                ">= 1" if max_cap_mol_bonds is None else "1..%d" % max_cap_mol_bonds, B, cap_atoms, cap_mol_bonds))
         if n_valid is not None and not (isinstance(n_valid, torch.Tensor) and n_valid.numel() == 1):
             raise ValueError("%s: n_valid must be a one-element int32 device tensor" % who)
         for t in read + (() if n_valid is None else (n_valid,)):

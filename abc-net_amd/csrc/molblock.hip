@@ -14,8 +14,8 @@
 //
 //   molblock_size_kernel   one workgroup per image: every thread adds up the lengths of its items, one workgroup sum -> lens[b]
 //                          (-1: a row the writer refuses)
-//   molblock_write_kernel  one workgroup per image: the running totals of lens[0 .. b] by a 64-bit workgroup scan (the prefix rule
-//                          needs the largest total that still fits), then per item class every thread takes a CONTIGUOUS range of
+//   molblock_write_kernel  one workgroup per image: the running totals of lens[0 .. b] by a 64-bit workgroup scan (the prefix rule of
+//                          text_pack.hpp needs the largest total that still fits), then per item class every thread takes a CONTIGUOUS range of
 //                          rows, a workgroup scan of the ranges' lengths gives its first byte, and it writes its rows one after
 //                          the other
 // Both kernels compute lengths with the same functions the writer advances by (every put_* returns the position after it), and
@@ -25,6 +25,7 @@
 #include "capi_util.hpp"
 #include "block_scan.hpp"
 #include "mol_rows.hpp"
+#include "text_pack.hpp"
 
 namespace {
 
@@ -198,11 +199,7 @@ __device__ inline Counts read_counts(const abc_molblock_desc& d, int b) {
 }
 
 // rows [lo, hi) of thread tid when n rows are dealt out in contiguous ranges
-__device__ inline void my_range(int n, int tid, int& lo, int& hi) {
-    const int per = (n + MT - 1) / MT;
-    lo = min(tid * per, n);
-    hi = min(lo + per, n);
-}
+__device__ inline void my_range(int n, int tid, int& lo, int& hi) { text_pack::my_range<MT>(n, tid, lo, hi); }
 
 __global__ __launch_bounds__(MT) void molblock_size_kernel(const abc_molblock_desc d) {
     __shared__ unsigned wt[MT / 64 + 1];
@@ -239,79 +236,33 @@ __global__ __launch_bounds__(MT) void molblock_size_kernel(const abc_molblock_de
     }
 }
 
-// exclusive prefix sum of a 64-bit value over the workgroup (the 32-bit block_excl_scan of block_scan.hpp, widened: the unclipped
-// running total of a batch may pass 2^32); wt = LDS scratch [MT / 64 + 1]
-__device__ inline u64 block_excl_scan64(u64 v, u64* wt, u64* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) wt[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 s = 0;
-#pragma unroll
-        for (int i = 0; i < MT / 64; ++i) {
-            const u64 x = wt[i];
-            wt[i] = s;
-            s += x;
-        }
-        wt[MT / 64] = s;
-    }
-    __syncthreads();
-    *total = wt[MT / 64];
-    return wt[wave] + inc - v;
-}
-
 __global__ __launch_bounds__(MT) void molblock_write_kernel(const abc_molblock_desc d) {
     __shared__ unsigned wt[MT / 64 + 1];
-    __shared__ u64 wt64[MT / 64 + 1];
-    __shared__ u64 through[2];           // the running total in front of image b, and through it
-    __shared__ u64 fits;                 // the largest running total through an image 0 .. b that is <= cap_text
     __shared__ int charged_all;
     const int b = blockIdx.x, tid = threadIdx.x;
     int* offsets = d.index;
     int* status_out = d.index + d.B + 1;
     const Counts c = read_counts(d, b);
 
-    // ---- the prefix rule: images 0 .. b in contiguous ranges, one scan of the ranges' sums, every thread walks its range
-    if (tid == 0) fits = 0, charged_all = 0;
+    // ---- the prefix rule (text_pack.hpp): the running total in front of image b and through it, and the largest that still fits
+    if (tid == 0) charged_all = 0;       // (published by the rule's barriers)
+    const text_pack::Span span = text_pack::prefix_rule<MT>(d.work, b, d.cap_text);
     int lo, hi;
-    my_range(b + 1, tid, lo, hi);
-    u64 mine = 0;
-    for (int i = lo; i < hi; ++i) mine += (u64)max(d.work[i], 0);
-    u64 all;
-    u64 run = block_excl_scan64(mine, wt64, &all);
-    {
-        u64 best = 0;
-        for (int i = lo; i < hi; ++i) {
-            if (i == b) through[0] = run;
-            run += (u64)max(d.work[i], 0);
-            if (run <= (u64)d.cap_text) best = run;      // (the totals never decrease: the last one that fits is the largest)
-        }
-        if (lo < hi && hi == b + 1) through[1] = run;
-        if (best) atomicMax(&fits, best);
-    }
-    __syncthreads();
     const int my_len = d.work[b];
-    const bool overflow = through[1] > (u64)d.cap_text;
+    const bool overflow = span.through > (u64)d.cap_text;
     const bool bad = my_len < 0;
     const bool written = !overflow && my_len > 0;
     if (tid == 0) {
         if (b == 0) offsets[0] = 0;
-        offsets[b + 1] = (int)fits;      // (fits <= cap_text <= INT32_MAX; == through[1] unless this image overflows)
+        offsets[b + 1] = (int)span.fits;      // (fits <= cap_text <= INT32_MAX; == through unless this image overflows)
         status_out[b] = c.status | (bad ? ABC_TEXT_BAD_ROW : 0) | (overflow ? ABC_TEXT_OVERFLOW : 0);
     }
     if (!written) return;                // (uniform over the workgroup)
 
     Out o;
     o.text = d.text;
-    o.end = (int64_t)through[1];
-    int64_t pos = (int64_t)through[0];
+    o.end = (int64_t)span.through;
+    int64_t pos = (int64_t)span.before;
     const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
     const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
     const int* ph = d.mol_implh + (size_t)b * d.cap_atoms;

@@ -1,0 +1,430 @@
+// A SMILES string for every assembled molecule, written on the device from the rows of abc_assemble_graphs, read in place
+// (decode.Molecule.smiles() is the host form and the oracle).  The contract -- text rule, statuses, prefix rule -- is in
+// include/abcnet_hip.h and DESIGN.md section 7.  Integers only.
+//
+//   smiles_compose_kernel  one workgroup per image.  The walk is done ONCE, here, and what is kept of it is the text itself: the
+//                          image's bytes go to its own slice of `work`, its length to work[b] (-1: a refused row, -2: the ring limit)
+//     1  validate every row; count degrees by LDS atomics, scan them, fill a CSR adjacency of (neighbour << 3 | order class)
+//     2  order every atom's list by neighbour index (a rank sort, one slot per thread at a time: position = how many of the list
+//        are smaller); equal neighbours side by side are a pair listed twice
+//     3  per atom: aromatic flag and hydrogen count
+//     4  ONE lane walks the graph (depth first, the parent pointers are the stack: no restart of a cursor, 2 m + n steps): preorder
+//        rank, parent, the class of the bond to the parent, which atoms open a branch and how many ")" follow each position
+//     5  order every list again, by the RANK of the neighbour: a neighbour that is neither the parent nor a child is the other end of
+//        a ring bond, the lower ranks (closings) now come first and both kinds in the order the rule writes them; every slot
+//        finds its twin in the neighbour's list (binary search)
+//     6  ONE lane hands out the ring numbers in preorder (the free numbers are two 64-bit masks), O(n + m)
+//     7  all threads: the byte length of every preorder position, a workgroup scan, and every thread writes its positions
+//   smiles_pack_kernel     one workgroup per image: the prefix rule over work[0 .. b] (text_pack.hpp), then a copy of the image's bytes
+// Lengths and bytes come from ONE emitter run over two sinks, so they cannot disagree; every store of either kernel is checked
+// against the end of the image's own bytes.
+#include "common.hpp"
+#include "../../include/abcnet_hip.h"
+#include "capi_util.hpp"
+#include "block_scan.hpp"
+#include "mol_rows.hpp"
+#include "graph_ids.hpp"
+#include "text_pack.hpp"
+
+namespace {
+
+constexpr int ST = 256;                              // threads per workgroup
+constexpr int MAX_ATOMS = ABC_MAX_SMILES_ATOMS;      // LDS arrays per atom
+constexpr int MAX_BONDS = 4096, MAX_SLOTS = 2 * MAX_BONDS;
+constexpr int MAX_NUMBER = 99;
+constexpr int LEN_BAD_ROW = -1, LEN_RING_LIMIT = -2;
+static_assert(MAX_ATOMS == 2 * ST, "the degree scan gives every thread two atoms");
+static_assert(MAX_ATOMS <= 1 << 13 && MAX_SLOTS <= 1 << 16, "a slot holds neighbour << 3 | class in 16 bits, an index of a slot too");
+
+// decode.ATOM_SYMBOLS, two columns each
+__device__ const char SYMBOL2[N_SYMBOLS * 2 + 1] = "C C N O P F ClS BrB SeI H Si";
+constexpr unsigned BARE_SET = 0x3FFFu & ~(1u << 10 | 1u << 12 | 1u << 13);                                  // all but Se, H, Si
+constexpr unsigned AROMATIC_SET = 1u << 0 | 1u << 1 | 1u << 2 | 1u << 3 | 1u << 4 | 1u << 7 | 1u << 9 | 1u << 10;      // B C N O P S Se
+// the valence lists by vocabulary index and charge -1 | 0 | +1: up to three values, four bits each, lowest first, 0 = no more
+#define V1(a) (a)
+#define V2(a, b) ((a) | (b) << 4)
+#define V3(a, b, c) ((a) | (b) << 4 | (c) << 8)
+__device__ const unsigned short VALENCES[N_SYMBOLS][3] = {
+    {V1(3), V1(4), V1(3)}, {V1(3), V1(4), V1(3)},                     // C, C
+    {V1(2), V1(3), V1(4)}, {V1(1), V1(2), V1(3)},                     // N, O
+    {V3(2, 4, 6), V2(3, 5), V1(4)}, {0, V1(1), V1(2)},                // P, F
+    {0, V1(1), V3(2, 4, 6)}, {V1(1), V3(2, 4, 6), V2(3, 5)},          // Cl, S
+    {0, V1(1), V3(2, 4, 6)}, {V1(4), V1(3), V1(2)},                   // Br, B
+    {V1(1), V3(2, 4, 6), V2(3, 5)}, {0, V1(1), V3(2, 4, 6)},          // Se, I
+    {0, 0, 0}, {V2(3, 5), V1(4), V1(3)}};                             // H, Si
+
+// h of an unlisted atom: s2 = the sum over its bonds of 3 for class 4 and 2 * class otherwise
+__device__ inline int hydrogens(int sym, int charge, int s2) {
+    if (sym == 12 || charge < -1 || charge > 1) return 0;
+    const int v = s2 >> 1;
+    for (unsigned list = VALENCES[sym][charge + 1]; list != 0; list >>= 4) {
+        const int t = (int)(list & 15u);
+        if (t >= v) return t - v;
+    }
+    return 0;
+}
+
+// two sinks for one emitter: Count adds up, Write stores below `end`
+struct Count {
+    int n;
+    __device__ inline void put(int) { ++n; }
+};
+struct Write {
+    uint8_t* at;
+    const uint8_t* end;
+    __device__ inline void put(int c) {
+        if (at < end) *at = (uint8_t)c;
+        ++at;
+    }
+};
+
+template <class Sink>
+__device__ inline void put_number(Sink& o, int k) {
+    if (k >= 10) o.put('%'), o.put('0' + k / 10);
+    o.put('0' + (k >= 10 ? k % 10 : k));
+}
+// class 1: nothing, but '-' between two aromatic atoms; 2 '='; 3 '#'; 4: nothing between two aromatic atoms, else ':'
+template <class Sink>
+__device__ inline void put_bond(Sink& o, int cls, bool both_aromatic) {
+    if (cls == 1) { if (both_aromatic) o.put('-'); }
+    else if (cls == 2) o.put('=');
+    else if (cls == 3) o.put('#');
+    else if (!both_aromatic) o.put(':');
+}
+template <class Sink>
+__device__ inline void put_token(Sink& o, int sym, int charge, int h, bool aromatic, bool listed) {
+    const int lower = aromatic ? 0x20 : 0;
+    const bool bare = charge == 0 && !listed && (BARE_SET >> sym & 1u);
+    if (!bare) o.put('[');
+    o.put(SYMBOL2[sym * 2] | lower);
+    if (SYMBOL2[sym * 2 + 1] != ' ') o.put(SYMBOL2[sym * 2 + 1]);
+    if (bare) return;
+    if (h >= 1) o.put('H');
+    if (h >= 2) o.put('0' + h);            // (h <= 6: the largest valence)
+    if (charge != 0) {
+        o.put(charge > 0 ? '+' : '-');
+        const int m = charge > 0 ? charge : -charge;      // (1 .. 15)
+        if (m >= 10) o.put('1');
+        if (m >= 2) o.put('0' + m % 10);
+    }
+    o.put(']');
+}
+
+// everything the emitter reads, in LDS
+struct Walk {
+    unsigned short adj[2][MAX_SLOTS];      // [0]: the lists as filled, then ordered by rank; [1]: ordered by index, then the twins
+    unsigned char number[MAX_SLOTS];       // the ring number of a ring bond's slot, at both ends
+    int deg[MAX_ATOMS];                    // degree, then the fill cursor
+    unsigned short start[MAX_ATOMS + 1];
+    short rank[MAX_ATOMS], parent[MAX_ATOMS], last_child[MAX_ATOMS];
+    unsigned short order[MAX_ATOMS], cursor[MAX_ATOMS], closes[MAX_ATOMS];
+    unsigned char sym[MAX_ATOMS], hcount[MAX_ATOMS], aromatic[MAX_ATOMS], listed[MAX_ATOMS], opens[MAX_ATOMS], parent_cls[MAX_ATOMS];
+    signed char charge[MAX_ATOMS];
+};
+
+// the atom whose list holds slot s: start[a] <= s < start[a + 1]
+__device__ inline int owner_of(const Walk& w, int na, int s) {
+    int lo = 0, hi = na - 1;
+    while (lo < hi) {                      // (at most 10 rounds)
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int)w.start[mid] <= s) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// Order every atom's list: slot s of `src` goes to the position that counts the slots of its list with a smaller key (ties by
+// slot: a permutation whatever the keys).  by_rank: the key is the neighbour's preorder rank, else the slot's own 16 bits.
+template <bool by_rank>
+__device__ inline void order_lists(Walk& w, int na, int slots, int src, int tid) {
+    for (int s = tid; s < slots; s += ST) {
+        const int a = owner_of(w, na, s), lo = w.start[a], hi = w.start[a + 1];
+        const int e = w.adj[src][s];
+        const int key = by_rank ? (int)w.rank[e >> 3] : e;
+        int pos = 0;
+        for (int t = lo; t < hi; ++t) {
+            const int f = w.adj[src][t];
+            const int other = by_rank ? (int)w.rank[f >> 3] : f;
+            pos += other < key || (other == key && t < s);
+        }
+        w.adj[src ^ 1][lo + pos] = (unsigned short)e;
+    }
+}
+
+// position p of the preorder: what stands in front of the atom, its token, its ring digits, the brackets behind it
+template <class Sink>
+__device__ inline void put_position(Sink& o, const Walk& w, int p) {
+    const int a = w.order[p], par = w.parent[a];
+    const bool arom = w.aromatic[a] != 0;
+    if (par < 0) {
+        if (p > 0) o.put('.');
+    } else {
+        if (w.opens[a]) o.put('(');
+        put_bond(o, w.parent_cls[a], arom && w.aromatic[par]);
+    }
+    put_token(o, w.sym[a], w.charge[a], w.hcount[a], arom, w.listed[a] != 0);
+    for (int s = w.start[a], hi = w.start[a + 1]; s < hi; ++s) {
+        const int e = w.adj[0][s], y = e >> 3;
+        if (y == par || w.parent[y] == a) continue;
+        if (w.rank[y] < p) put_bond(o, e & 7, arom && w.aromatic[y]);      // a closing: the symbol, then the number
+        put_number(o, w.number[s]);
+    }
+    for (int i = w.closes[p]; i > 0; --i) o.put(')');
+}
+
+struct Counts { int na, nb, nh, status; };
+__device__ inline Counts read_counts(const abc_smiles_desc& d, int b) {
+    const int* mc = d.mol_counts + (size_t)b * 4;
+    Counts c;
+    c.na = clampi(mc[0], 0, d.cap_atoms);
+    c.nb = clampi(mc[1], 0, d.cap_mol_bonds);
+    c.nh = clampi(mc[2], 0, d.cap_atoms);
+    c.status = mc[3] & (ABC_MOL_EMPTY | ABC_MOL_TRUNCATED);
+    return c;
+}
+
+// bytes one image may take at these capacities (abc_smiles_text_bytes): also the stride of the slices of `work`
+__host__ __device__ inline int64_t image_bytes(int64_t cap_atoms, int64_t cap_mol_bonds) { return 12 * cap_atoms + 7 * cap_mol_bonds; }
+__device__ inline uint8_t* slice_of(const abc_smiles_desc& d, int b) {
+    return (uint8_t*)(d.work + d.B) + (size_t)b * (size_t)image_bytes(d.cap_atoms, d.cap_mol_bonds);
+}
+
+__global__ __launch_bounds__(ST) void smiles_compose_kernel(const abc_smiles_desc d) {
+    __shared__ Walk w;
+    __shared__ unsigned wt[ST / 64 + 1];
+    __shared__ int refused;                // 0, LEN_BAD_ROW or LEN_RING_LIMIT
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const Counts c = read_counts(d, b);
+    const int na = c.na, nb = c.nb, slots = 2 * nb;
+    if ((c.status & ABC_MOL_EMPTY) || na == 0) {      // (uniform.  Bonds without an atom cannot be: their ends are outside 1..0)
+        if (tid == 0) d.work[b] = (c.status & ABC_MOL_EMPTY) || nb == 0 ? 0 : LEN_BAD_ROW;
+        return;
+    }
+    const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
+    const int* pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
+    const int* ph = d.mol_implh + (size_t)b * d.cap_atoms;
+
+    // ---- 1: rows
+    if (tid == 0) refused = 0;
+    for (int i = tid; i < na; i += ST) {
+        w.deg[i] = 0;
+        w.rank[i] = w.parent[i] = w.last_child[i] = -1;
+        w.closes[i] = 0;
+        w.listed[i] = w.opens[i] = w.parent_cls[i] = 0;
+    }
+    __syncthreads();
+    bool bad = false;
+    for (int i = tid; i < na; i += ST) {
+        const int t = pa[i * ATOM_W + 2], q = pa[i * ATOM_W + 3];
+        bad |= t < 0 || t >= N_SYMBOLS || q < -15 || q > 15;
+        w.sym[i] = (unsigned char)clampi(t, 0, N_SYMBOLS - 1);
+        w.charge[i] = (signed char)clampi(q, -15, 15);
+    }
+    for (int q = tid; q < nb; q += ST) {
+        int e1, e2;
+        if (mol_ends(pb, q, na, e1, e2) && bond_class(pb[q * MOL_BOND_W + 2]) != 0) {
+            atomicAdd(&w.deg[e1], 1);
+            atomicAdd(&w.deg[e2], 1);
+        } else {
+            bad = true;
+        }
+    }
+    for (int k = tid; k < c.nh; k += ST) {
+        const int a = ph[k];
+        if (a >= 1 && a <= na) w.listed[a - 1] = 1;      // (several entries may name one atom: they store the same byte)
+    }
+    if (bad) atomicOr(&refused, LEN_BAD_ROW);
+    __syncthreads();
+    if (refused) {                         // (uniform: read behind the barrier)
+        if (tid == 0) d.work[b] = LEN_BAD_ROW;
+        return;
+    }
+    {   // every thread takes atoms 2 tid and 2 tid + 1
+        const int i0 = 2 * tid, d0 = i0 < na ? w.deg[i0] : 0, d1 = i0 + 1 < na ? w.deg[i0 + 1] : 0;
+        unsigned total;
+        const unsigned first = block_excl_scan<ST>((unsigned)(d0 + d1), wt, &total);      // (total == slots)
+        if (i0 < na) w.start[i0] = (unsigned short)first, w.deg[i0] = 0;
+        if (i0 + 1 < na) w.start[i0 + 1] = (unsigned short)(first + d0), w.deg[i0 + 1] = 0;
+        if (tid == 0) w.start[na] = (unsigned short)total;
+    }
+    __syncthreads();
+    for (int q = tid; q < nb; q += ST) {
+        int e1, e2;
+        mol_ends(pb, q, na, e1, e2);       // (true for every row: checked above)
+        const int cls = bond_class(pb[q * MOL_BOND_W + 2]);
+        w.adj[0][w.start[e1] + atomicAdd(&w.deg[e1], 1)] = (unsigned short)(e2 << 3 | cls);
+        w.adj[0][w.start[e2] + atomicAdd(&w.deg[e2], 1)] = (unsigned short)(e1 << 3 | cls);
+    }
+    __syncthreads();
+
+    // ---- 2: by neighbour index (into adj[1]); a pair listed twice
+    order_lists<false>(w, na, slots, 0, tid);
+    __syncthreads();
+    bad = false;
+    for (int i = tid; i < na; i += ST)
+        for (int s = w.start[i] + 1, hi = w.start[i + 1]; s < hi; ++s) bad |= w.adj[1][s] >> 3 == w.adj[1][s - 1] >> 3;
+    if (bad) atomicOr(&refused, LEN_BAD_ROW);
+
+    // ---- 3: classes
+    for (int i = tid; i < na; i += ST) {
+        int s2 = 0, any4 = 0;
+        for (int s = w.start[i], hi = w.start[i + 1]; s < hi; ++s) {
+            const int cls = w.adj[1][s] & 7;
+            s2 += cls == 4 ? 3 : 2 * cls;
+            any4 |= cls == 4;
+        }
+        w.aromatic[i] = (unsigned char)(any4 && (AROMATIC_SET >> w.sym[i] & 1u));
+        w.hcount[i] = (unsigned char)(w.listed[i] ? 1 : hydrogens(w.sym[i], w.charge[i], s2));
+        w.cursor[i] = w.start[i];
+    }
+    __syncthreads();
+    if (refused) {
+        if (tid == 0) d.work[b] = LEN_BAD_ROW;
+        return;
+    }
+
+    // ---- 4: the walk
+    if (tid == 0) {
+        int next = 0, steps = slots + 2 * na;      // (every slot is passed once, every atom is left once)
+        for (int root = 0; root < na; ++root) {
+            if (w.rank[root] >= 0) continue;
+            w.rank[root] = (short)next;
+            w.order[next++] = (unsigned short)root;
+            int cur = root;
+            while (cur >= 0 && steps-- > 0) {
+                const int at = w.cursor[cur];
+                if (at == w.start[cur + 1]) {
+                    cur = w.parent[cur];
+                    continue;
+                }
+                w.cursor[cur] = (unsigned short)(at + 1);
+                const int e = w.adj[1][at], y = e >> 3;
+                if (w.rank[y] >= 0) continue;      // the parent, or the other end of a ring bond
+                const int before = w.last_child[cur];
+                if (before >= 0) {                 // that child was not the last: it stands in a branch, which ends behind the
+                    w.opens[before] = 1;           // atom visited last
+                    w.closes[next - 1] += 1;
+                }
+                w.last_child[cur] = (short)y;
+                w.parent[y] = (short)cur;
+                w.parent_cls[y] = (unsigned char)(e & 7);
+                w.rank[y] = (short)next;
+                w.order[next++] = (unsigned short)y;
+                cur = y;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- 5: by rank (back into adj[0]), then the twin of every slot (over adj[1])
+    order_lists<true>(w, na, slots, 1, tid);
+    __syncthreads();
+    for (int s = tid; s < slots; s += ST) {
+        const int a = owner_of(w, na, s), y = w.adj[0][s] >> 3, want = w.rank[a];
+        int lo = w.start[y], hi = w.start[y + 1] - 1;
+        while (lo < hi) {                  // (the list of y holds a, once, and is ascending in rank)
+            const int mid = (lo + hi) >> 1;
+            if ((int)w.rank[w.adj[0][mid] >> 3] < want) lo = mid + 1;
+            else hi = mid;
+        }
+        w.adj[1][s] = (unsigned short)lo;
+    }
+    __syncthreads();
+
+    // ---- 6: ring numbers
+    if (tid == 0) {
+        typedef unsigned long long u64;
+        u64 free_lo = ~1ull, free_hi = (1ull << (MAX_NUMBER - 63)) - 1;      // bit k of lo: number k (1 .. 63); bit j of hi: 64 + j
+        bool limit = false;
+        for (int p = 0; p < na && !limit; ++p) {
+            const int a = w.order[p], par = w.parent[a];
+            u64 closed_lo = 0, closed_hi = 0;
+            for (int s = w.start[a], hi = w.start[a + 1]; s < hi; ++s) {
+                const int y = w.adj[0][s] >> 3;
+                if (y == par || w.parent[y] == a) continue;
+                if (w.rank[y] < p) {
+                    const int k = w.number[s];
+                    if (k < 64) closed_lo |= 1ull << k;
+                    else closed_hi |= 1ull << (k - 64);
+                    continue;
+                }
+                int k;
+                if (free_lo) k = __ffsll((long long)free_lo) - 1, free_lo &= free_lo - 1;
+                else if (free_hi) k = 64 + __ffsll((long long)free_hi) - 1, free_hi &= free_hi - 1;
+                else {
+                    limit = true;
+                    break;
+                }
+                w.number[s] = (unsigned char)k;
+                w.number[w.adj[1][s]] = (unsigned char)k;
+            }
+            free_lo |= closed_lo, free_hi |= closed_hi;
+        }
+        if (limit) refused = LEN_RING_LIMIT;
+    }
+    __syncthreads();
+    if (refused) {
+        if (tid == 0) d.work[b] = LEN_RING_LIMIT;
+        return;
+    }
+
+    // ---- 7: the bytes
+    int lo, hi;
+    text_pack::my_range<ST>(na, tid, lo, hi);
+    Count n = {0};
+    for (int p = lo; p < hi; ++p) put_position(n, w, p);
+    unsigned total;
+    const unsigned first = block_excl_scan<ST>((unsigned)n.n, wt, &total);
+    uint8_t* slice = slice_of(d, b);
+    Write o = {slice + first, slice + image_bytes(d.cap_atoms, d.cap_mol_bonds)};
+    for (int p = lo; p < hi; ++p) put_position(o, w, p);
+    if (tid == 0) d.work[b] = (int)total;
+}
+
+__global__ __launch_bounds__(ST) void smiles_pack_kernel(const abc_smiles_desc d) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int* offsets = d.index;
+    int* status_out = d.index + d.B + 1;
+    const text_pack::Span span = text_pack::prefix_rule<ST>(d.work, b, d.cap_text);
+    const int len = d.work[b];
+    const bool overflow = span.through > (unsigned long long)d.cap_text;
+    if (tid == 0) {
+        if (b == 0) offsets[0] = 0;
+        offsets[b + 1] = (int)span.fits;      // (fits <= cap_text <= INT32_MAX; == through unless this image overflows)
+        status_out[b] = read_counts(d, b).status | (len == LEN_BAD_ROW ? ABC_TEXT_BAD_ROW : 0) | (len == LEN_RING_LIMIT ? ABC_TEXT_RING_LIMIT : 0)
+                        | (overflow ? ABC_TEXT_OVERFLOW : 0);
+    }
+    if (overflow || len <= 0) return;
+    // (through - before == len, and through <= cap_text: every store is inside the image's own bytes; the slice holds len of them)
+    const uint8_t* slice = slice_of(d, b);
+    const int n = (int)min((long long)len, (long long)image_bytes(d.cap_atoms, d.cap_mol_bonds));
+    for (int i = tid; i < n; i += ST) d.text[span.before + i] = slice[i];
+}
+
+}  // namespace
+
+extern "C" int abc_smiles_desc_size(void) { return (int)sizeof(abc_smiles_desc); }
+
+extern "C" int64_t abc_smiles_text_bytes(const abc_smiles_desc* d) {
+    if (!d || d->cap_atoms < 1 || d->cap_mol_bonds < 1) return 0;
+    return image_bytes(d->cap_atoms, d->cap_mol_bonds);
+}
+
+extern "C" int64_t abc_smiles_work_ints(const abc_smiles_desc* d) {
+    if (!d || d->B < 1 || d->cap_atoms < 1 || d->cap_mol_bonds < 1) return 0;
+    return d->B + (d->B * image_bytes(d->cap_atoms, d->cap_mol_bonds) + 3) / 4;
+}
+
+extern "C" int abc_write_smiles(const abc_smiles_desc* d, abc_stream_t stream) {
+    if (!d) return abc_fail(ABC_EINVAL, "write_smiles: null descriptor");
+    if (d->B < 1) return abc_fail(ABC_EINVAL, "write_smiles: empty");
+    if (d->cap_atoms < 1 || d->cap_mol_bonds < 1) return abc_fail(ABC_EINVAL, "write_smiles: cap_atoms and cap_mol_bonds must be >= 1");
+    if (d->cap_atoms > MAX_ATOMS) return abc_fail(ABC_EUNSUPPORTED, "write_smiles: cap_atoms must be <= 512 (ABC_MAX_SMILES_ATOMS)");
+    if (d->cap_mol_bonds > MAX_BONDS) return abc_fail(ABC_EUNSUPPORTED, "write_smiles: cap_mol_bonds must be <= 4096");
+    if (d->cap_text < 1 || d->cap_text > INT32_MAX) return abc_fail(ABC_EINVAL, "write_smiles: cap_text must be 1..2^31-1");
+    if (!d->mol_counts || !d->mol_atoms || !d->mol_bonds || !d->mol_implh) return abc_fail(ABC_EINVAL, "write_smiles: null molecule buffer");
+    if (!d->text || !d->index || !d->work) return abc_fail(ABC_EINVAL, "write_smiles: null output");
+    hipLaunchKernelGGL(smiles_compose_kernel, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
+    hipLaunchKernelGGL(smiles_pack_kernel, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
+    return abc_check_launch("write_smiles");
+}

@@ -1,6 +1,7 @@
 """The assembled molecule of one image (img2smiles2.py:193-311, computed on the device by csrc/assemble.hip) and the mol block
 the reference writes from it (generate_smiles.py:18-105).  Pure host string work: RDKit is not a dependency; the caller hands
-`Molecule.molblock()` to `Chem.MolFromMolBlock` exactly as generate_smiles.py:115 does.
+`Molecule.molblock()` to `Chem.MolFromMolBlock` exactly as generate_smiles.py:115 does.  `Molecule.smiles()` writes a SMILES without
+RDKit, by this project's own text rule: not RDKit's canonical string.
 """
 from __future__ import annotations
 
@@ -88,3 +89,113 @@ class Molecule:
                 out.append("M  SED   %d IMPL_H1\n" % (k + 1))
         out.append("M  END\n$$$$")
         return "".join(out)
+
+    def smiles(self):
+        """a deterministic, valid SMILES of this graph by the text rule of DESIGN.md section 7 (the host form and the oracle of
+        csrc/smiles.hip, integers only): NOT the canonical string RDKit prints; wedges are single bonds, stereo is not written,
+        hs and the positions are not read.  ValueError for a row the rule refuses and for more than 99 ring bonds open at once."""
+        n = len(self.symbols)
+        for i, (s, c) in enumerate(zip(self.symbols, self.charges)):
+            if s not in ATOM_SYMBOLS:
+                raise ValueError("Molecule.smiles: atom %d has symbol %r, which the vocabulary does not hold" % (i + 1, s))
+            if not -15 <= c <= 15:
+                raise ValueError("Molecule.smiles: atom %d has charge %d, outside -15..15" % (i + 1, c))
+        adj, pairs = [[] for _ in range(n)], set()
+        for k, ((e1, e2), order) in enumerate(zip(self.bonds, self.orders)):
+            if not 1 <= order <= 6:
+                raise ValueError("Molecule.smiles: bond row %d has order %d, outside 1..6" % (k, order))
+            if not (1 <= e1 <= n and 1 <= e2 <= n):
+                raise ValueError("Molecule.smiles: bond row %d has an end outside 1..%d: (%d, %d)" % (k, n, e1, e2))
+            if e1 == e2:
+                raise ValueError("Molecule.smiles: bond row %d has both ends on atom %d" % (k, e1))
+            if (min(e1, e2), max(e1, e2)) in pairs:
+                raise ValueError("Molecule.smiles: bond row %d is a second row for the atom pair (%d, %d)" % (k, e1, e2))
+            pairs.add((min(e1, e2), max(e1, e2)))
+            cls = 1 if order >= 5 else order
+            adj[e1 - 1].append((e2 - 1, cls))
+            adj[e2 - 1].append((e1 - 1, cls))
+        for row in adj:
+            row.sort()
+        listed = [False] * n
+        for a in self.implicit_hs:
+            if 1 <= a <= n:
+                listed[a - 1] = True
+        aromatic = [s in _SMILES_AROMATIC and any(cls == 4 for _, cls in row) for s, row in zip(self.symbols, adj)]
+
+        def bond_symbol(u, v, cls):
+            both = aromatic[u] and aromatic[v]
+            return (("-" if both else ""), "=", "#", ("" if both else ":"))[cls - 1]
+
+        def token(a):
+            s, c = self.symbols[a], self.charges[a]
+            sym = s.lower() if aromatic[a] else s
+            if c == 0 and not listed[a] and s in _SMILES_BARE:
+                return sym
+            if listed[a]:
+                h = 1
+            elif s == "H" or abs(c) > 1:
+                h = 0
+            else:
+                v = sum(3 if cls == 4 else 2 * cls for _, cls in adj[a]) // 2
+                h = next((t - v for t in _SMILES_VALENCES[s][c + 1] if t >= v), 0)
+            hydrogens = "" if h == 0 else ("H" if h == 1 else "H%d" % h)
+            charge = "" if c == 0 else ("+" if c > 0 else "-") + ("" if abs(c) == 1 else "%d" % abs(c))
+            return "[" + sym + hydrogens + charge + "]"
+
+        # the walk, with the tree's parent pointers as its stack: the rank, the parent and the brackets of every atom
+        rank, parent, order, cursor = [-1] * n, [-1] * n, [], [0] * n
+        last_child, opens_branch, closes = [-1] * n, [False] * n, [0] * n
+        for root in range(n):
+            if rank[root] >= 0:
+                continue
+            rank[root] = len(order)
+            order.append(root)
+            cur = root
+            while cur >= 0:
+                if cursor[cur] == len(adj[cur]):
+                    cur = parent[cur]
+                    continue
+                y = adj[cur][cursor[cur]][0]
+                cursor[cur] += 1
+                if rank[y] < 0:
+                    if last_child[cur] >= 0:      # the child before this one was not the last: it stands in a branch, which
+                        opens_branch[last_child[cur]] = True      # ends behind the atom visited last
+                        closes[len(order) - 1] += 1
+                    last_child[cur], parent[y], rank[y] = y, cur, len(order)
+                    order.append(y)
+                    cur = y
+        # a neighbour that is neither the parent nor a child is the other end of a ring bond: the lower rank opened it
+        free, number, out = [True] * 100, {}, []
+        for p, a in enumerate(order):
+            ring = sorted((rank[y], y, cls) for y, cls in adj[a] if y != parent[a] and parent[y] != a)
+            digits, closed = [], []
+            for r, y, cls in ring:
+                if r < p:
+                    k = number.pop((y, a))
+                    closed.append(k)
+                    digits.append(bond_symbol(y, a, cls))
+                else:
+                    k = next((i for i in range(1, 100) if free[i]), 0)
+                    if k == 0:
+                        raise ValueError("Molecule.smiles: more than 99 ring bonds are open at atom %d (the ring limit)" % (a + 1))
+                    free[k] = False
+                    number[(a, y)] = k
+                digits.append("%d" % k if k < 10 else "%%%d" % k)
+            for k in closed:
+                free[k] = True
+            if parent[a] < 0:
+                lead = "." if p > 0 else ""
+            else:
+                lead = ("(" if opens_branch[a] else "") + bond_symbol(parent[a], a, next(cls for y, cls in adj[a] if y == parent[a]))
+            out.append(lead + token(a) + "".join(digits) + ")" * closes[p])
+        return "".join(out)
+
+
+# the text rule's classes (DESIGN.md section 7): the symbols written without brackets, the ones that may be aromatic, and OUR valence
+# lists by charge -1 | 0 | +1 (an isoelectronic shift; no agreement with RDKit's valence model is claimed)
+_SMILES_BARE = frozenset(("B", "C", "N", "O", "P", "S", "F", "Cl", "Br", "I"))
+_SMILES_AROMATIC = frozenset(("B", "C", "N", "O", "P", "S", "Se"))
+_HALOGEN = ((), (1,), (2, 4, 6))
+_SMILES_VALENCES = {"B": ((4,), (3,), (2,)), "C": ((3,), (4,), (3,)), "N": ((2,), (3,), (4,)), "O": ((1,), (2,), (3,)),
+                    "F": ((), (1,), (2,)), "Si": ((3, 5), (4,), (3,)), "P": ((2, 4, 6), (3, 5), (4,)), "S": ((1,), (2, 4, 6), (3, 5)),
+                    "Se": ((1,), (2, 4, 6), (3, 5)), "Cl": _HALOGEN, "Br": _HALOGEN, "I": _HALOGEN, "H": ((), (), ())}

@@ -8,8 +8,8 @@ time, activations in the convolutions' epilogues, no dropout) + the peak-NMS ker
 steps, so re-packing them and deriving the eval-mode BatchNorm coefficients happens in `refresh()`, not in the step;
 call it again after `load_state_dict`.  The step ends with the four mask / |rho| maps the decoder reads; opt-in, the candidate
 lists (extract=True, img2smiles2.py:113-191), the assembled molecules (assemble=True, :193-311) and their mol block text
-(molblocks=True, generate_smiles.py:18-105) in the same graph.  RDKit
-(generate_smiles.py:115-119) is out of scope.
+(molblocks=True, generate_smiles.py:18-105) in the same graph, and a SMILES string of each by this project's own text rule
+(smiles=True).  RDKit (generate_smiles.py:115-119) and its canonical SMILES are out of scope.
 
 evaluate=True makes the step the loop body of the reference's src/test_accuracy.py:94-269 as well: the targets of the batch sit in
 static device buffers and one more launch sequence after the NMS (ops.EvalTables) adds the batch to the per-class tables and the 17
@@ -29,7 +29,7 @@ from .contract import HEADS, GraphRecords, alloc_targets, check_sparse_rasterize
 
 
 # the optional stages behind the NMS in launch order, each under the constructor flag that builds it
-STAGES = {"extractor": "extract", "assembler": "assemble", "texter": "molblocks", "scorer": "score_graphs",
+STAGES = {"extractor": "extract", "assembler": "assemble", "texter": "molblocks", "smiler": "smiles", "scorer": "score_graphs",
           "similarity": "score_similarity", "identity": "score_identity", "evaluator": "evaluate"}
 
 
@@ -37,7 +37,7 @@ class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
                  assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
-                 score_similarity=False, molblocks=False, score_identity=False):
+                 score_similarity=False, molblocks=False, score_identity=False, smiles=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -75,10 +75,13 @@ class InferenceRunner:
         molblocks (needs assemble=True): the mol block text of the assembled molecules (ops.MolBlockWriter), written in the same
         captured graph right after the assembler; molblocks() returns the strings that go into Chem.MolFromMolBlock -- two small
         copies per batch instead of molecules() and Molecule.molblock() per image on the host
+        smiles (needs assemble=True): a SMILES string of every assembled molecule (ops.SmilesWriter), written in the same captured
+        graph after the assembler (and after the mol block text, if both are on); smiles() returns the strings.  The text rule is
+        this project's: deterministic, its graph is the assembled graph, NOT RDKit's canonical SMILES
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
-        from .ops import OMEGA_RULES, GraphAssembler, GraphIdentity, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, check_nms_heads
+        from .ops import OMEGA_RULES, GraphAssembler, GraphIdentity, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, SmilesWriter, check_nms_heads
         if omega_rule not in OMEGA_RULES:
             raise ValueError("InferenceRunner: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
         self.omega_rule = omega_rule
@@ -86,9 +89,10 @@ class InferenceRunner:
             if on and not (assemble and evaluate):
                 raise ValueError("InferenceRunner(%s=True) scores the assembled molecules of an evaluating step: it needs "
                                  "assemble=True and evaluate=True" % flag)
-        if molblocks and not assemble:
-            raise ValueError("InferenceRunner(molblocks=True) writes the text of the assembled molecules of the step: it needs "
-                             "assemble=True")
+        for flag, on in (("molblocks", molblocks), ("smiles", smiles)):
+            if on and not assemble:
+                raise ValueError("InferenceRunner(%s=True) writes the text of the assembled molecules of the step: it needs "
+                                 "assemble=True" % flag)
         extract = bool(extract) or bool(assemble)
         check_nms_heads(model.heads, "InferenceRunner")
         if extract and tuple(model.heads) != HEADS:
@@ -129,7 +133,7 @@ class InferenceRunner:
         d.rho_abs, d.omega_mask = self.rho_abs.data_ptr(), self.omega_mask.data_ptr()
         self._nms = d
         # img2smiles2.py:113-191: compact candidate lists for the CPU graph-assembly stage, inside the same graph
-        self.extractor = self.assembler = self.texter = self.evaluator = self._rasterizer = None
+        self.extractor = self.assembler = self.texter = self.smiler = self.evaluator = self._rasterizer = None
         with torch.cuda.device(dev):
             if extract:
                 self.extractor = PeakExtractor(lg, self.atom_mask, self.bond_mask, cap_atoms=cap_atoms, cap_bonds=cap_bonds,
@@ -139,6 +143,8 @@ class InferenceRunner:
                 self.assembler = GraphAssembler.from_extractor(self.extractor, cap_mol_bonds=cap_mol_bonds)
             if molblocks:
                 self.texter = MolBlockWriter.from_assembler(self.assembler)
+            if smiles:
+                self.smiler = SmilesWriter.from_assembler(self.assembler)
         if evaluate:
             if tuple(model.heads) != HEADS:
                 raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (list(HEADS), list(model.heads)))
@@ -288,6 +294,13 @@ class InferenceRunner:
         texter = self._need("texter")
         with torch.cuda.device(self.dev):
             return texter.molblocks()
+
+    def smiles(self):
+        """a SMILES string of every image of the last step, written on the device: what `m.smiles()` gives for the m of
+        molecules(), None where that is None (host sync; needs smiles=True)"""
+        smiler = self._need("smiler")
+        with torch.cuda.device(self.dev):
+            return smiler.smiles()
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""

@@ -1,7 +1,7 @@
 """Thin host wrappers over single C-ABI kernels used outside the engine's static plan:
 fused loss (train.py:95-137), inference NMS (img2smiles2.py:61-79), candidate extraction and graph assembly
-(img2smiles2.py:113-311), the mol block text of the assembled molecules (generate_smiles.py:18-105), their score against their
-annotations, fused Adam (train.py:55,141)."""
+(img2smiles2.py:113-311), the mol block text of the assembled molecules (generate_smiles.py:18-105) and a SMILES string of each, their
+score against their annotations, fused Adam (train.py:55,141)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -467,7 +467,32 @@ class GraphAssembler:
         return out
 
 
-class MolBlockWriter:
+class PackedText:
+    """what the device text writers (MolBlockWriter, SmilesWriter) share: .text, the batch's texts back to back, and .index,
+    offsets [B + 1] then status words [B], read back through the pinned .h_index"""
+
+    def _index(self):
+        """(offsets [B + 1], status [B]) of the last run as host lists: one D2H into the pinned buffer (host sync)"""
+        self.h_index.copy_(self.index, non_blocking=True)
+        torch.cuda.current_stream(self.index.device).synchronize()
+        v = self.h_index.tolist()
+        return v[:self.B + 1], v[self.B + 1:]
+
+    def status(self):
+        """the B status words of the last run: abc_mol_status | abc_text_status bits (host sync)"""
+        return self._index()[1]
+
+    def _texts(self):
+        off, status = self._index()
+        for b, s in enumerate(status):
+            for bit, name in self.STATUS_NAMES:
+                if s & bit:
+                    raise L.AbcNetHipError("%s: image %d has status %s" % (type(self).__name__, b, name))
+        raw = self.text[:off[self.B]].cpu().numpy().tobytes()
+        return [None if s & L.MOL_EMPTY else raw[off[b]:off[b + 1]].decode("ascii") for b, s in enumerate(status)]
+
+
+class MolBlockWriter(PackedText):
     """the mol block text of the assembled molecules, written on the device (csrc/molblock.hip, abc_write_molblocks): the bytes of
     `Molecule.from_device_rows(...).molblock()` for every image of a GraphAssembler's rows, read in place, packed back to back
     into one static buffer.  Two launches, static buffers, graph-capture safe; `molblocks()` is the only host sync (two small D2H
@@ -507,28 +532,63 @@ class MolBlockWriter:
     def run(self, stream=None):
         L.check(self.lib.abc_write_molblocks(C.byref(self.d), stream_or_current(stream)), "write_molblocks")
 
-    def _index(self):
-        """(offsets [B + 1], status [B]) of the last run as host lists: one D2H into the pinned buffer (host sync)"""
-        self.h_index.copy_(self.index, non_blocking=True)
-        torch.cuda.current_stream(self.index.device).synchronize()
-        v = self.h_index.tolist()
-        return v[:self.B + 1], v[self.B + 1:]
-
-    def status(self):
-        """the B status words of the last run: abc_mol_status | abc_text_status bits (host sync)"""
-        return self._index()[1]
-
     def molblocks(self):
         """per image: the mol block as a str (the argument of Chem.MolFromMolBlock), or None for an image without an atom peak
         or without a bond peak.  Raises AbcNetHipError when an image was refused (BAD_ROW) or did not fit (OVERFLOW).  Host sync:
         the index, then the text that was written."""
-        off, status = self._index()
-        for b, s in enumerate(status):
-            for bit, name in self.STATUS_NAMES:
-                if s & bit:
-                    raise L.AbcNetHipError("MolBlockWriter: image %d has status %s" % (b, name))
-        raw = self.text[:off[self.B]].cpu().numpy().tobytes()
-        return [None if s & L.MOL_EMPTY else raw[off[b]:off[b + 1]].decode("ascii") for b, s in enumerate(status)]
+        return self._texts()
+
+
+class SmilesWriter(PackedText):
+    """a SMILES string for every assembled molecule, written on the device (csrc/smiles.hip, abc_write_smiles): the bytes of
+    `Molecule.from_device_rows(...).smiles()` for every image of a GraphAssembler's rows, read in place, packed back to back into
+    one static buffer.  Two launches, static buffers, graph-capture safe; `smiles()` is the only host sync (two small D2H copies
+    per batch).  The text is deterministic and its graph is the rows' graph; it is NOT RDKit's canonical SMILES (DESIGN.md
+    section 7: the rule, and what it leaves out)."""
+
+    STATUS_NAMES = ((L.TEXT_BAD_ROW, "ABC_TEXT_BAD_ROW (a vocabulary index outside 0..13, a charge outside -15..15, a bond order "
+                                     "outside 1..6, a bond end outside 1..n or on one atom twice, or an atom pair listed twice)"),
+                    (L.TEXT_RING_LIMIT, "ABC_TEXT_RING_LIMIT (more than 99 ring bonds are open at once)"),
+                    (L.TEXT_OVERFLOW, "ABC_TEXT_OVERFLOW (the batch's text does not fit cap_text)"))
+
+    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, cap_text=None):
+        """a contract.MoleculeRows (GraphAssembler.rows), or its four device tensors (hand-made rows); cap_atoms at most
+        L.MAX_SMILES_ATOMS, cap_mol_bonds at most L.MAX_SMILES_BONDS.  cap_text: bytes of the text buffer; default
+        B * abc_smiles_text_bytes, the bound of one image with every token at its widest -- 20 480 bytes per image at the
+        runner's default capacities (512 atoms, 2048 bonds); at most 2^31 - 1"""
+        rows = MoleculeRows.checked("SmilesWriter", mol_counts, mol_atoms, mol_bonds, mol_implh, max_cap_atoms=L.MAX_SMILES_ATOMS,
+                                    max_cap_mol_bonds=L.MAX_SMILES_BONDS, need_implh=True)
+        B, cap_atoms, cap_mol_bonds = rows.B, rows.cap_atoms, rows.cap_mol_bonds
+        self.lib = L.load()
+        dev = rows.device
+        d = L.SmilesDesc()
+        rows.fill(d)
+        d.mol_implh = rows.tensors[3].data_ptr()
+        self.image_bytes = int(self.lib.abc_smiles_text_bytes(C.byref(d)))
+        cap_text = B * self.image_bytes if cap_text is None else int(cap_text)
+        if not (1 <= cap_text <= 2 ** 31 - 1):
+            raise ValueError("SmilesWriter: cap_text must be 1..2^31-1 bytes, got %d (B = %d images of at most %d bytes)"
+                             % (cap_text, B, self.image_bytes))
+        self.B, self.cap_atoms, self.cap_mol_bonds, self.cap_text = B, cap_atoms, cap_mol_bonds, cap_text
+        self.text = torch.zeros(cap_text, dtype=torch.uint8, device=dev)
+        self.index = torch.zeros(2 * B + 1, dtype=torch.int32, device=dev)
+        self.work = torch.zeros(int(self.lib.abc_smiles_work_ints(C.byref(d))), dtype=torch.int32, device=dev)
+        self.h_index = torch.zeros(2 * B + 1, dtype=torch.int32, pin_memory=True)
+        d.text, d.index, d.work, d.cap_text = self.text.data_ptr(), self.index.data_ptr(), self.work.data_ptr(), cap_text
+        self.d, self.keep = d, rows.tensors
+
+    @classmethod
+    def from_assembler(cls, asm, cap_text=None):
+        return cls(asm.rows, cap_text=cap_text)
+
+    def run(self, stream=None):
+        L.check(self.lib.abc_write_smiles(C.byref(self.d), stream_or_current(stream)), "write_smiles")
+
+    def smiles(self):
+        """per image: the SMILES as a str, or None for an image without an atom peak or without a bond peak.  Raises
+        AbcNetHipError when an image was refused (BAD_ROW, RING_LIMIT) or did not fit (OVERFLOW).  Host sync: the index, then the
+        text that was written."""
+        return self._texts()
 
 
 def stroke_max_iter(thin, what="StrokeNormalizer"):

@@ -757,7 +757,9 @@ int abc_stroke_desc_size(void);
 /* The capacities of the SMILES decoder's stages below, the sizes of their kernels' LDS arrays (a launch with more is ABC_EINVAL):
  * cap_atoms of extract, assemble and graph score; bond peaks per image abc_extract_peaks expands; max_atoms and max_bonds of the
  * graph score; cap_atoms and max_atoms of the graph similarity and of the graph identity. */
-enum abc_decoder_limit { ABC_MAX_CAP_ATOMS = 2048, ABC_MAX_BOND_PEAKS = 4096, ABC_MAX_SCORE_RECORD = 1024, ABC_MAX_SIM_ATOMS = 512 };
+enum abc_decoder_limit { ABC_MAX_CAP_ATOMS = 2048, ABC_MAX_BOND_PEAKS = 4096, ABC_MAX_SCORE_RECORD = 1024, ABC_MAX_SIM_ATOMS = 512,
+                         /* cap_atoms of abc_write_smiles: the per-atom LDS arrays of its walk, as many as the similarity's */
+                         ABC_MAX_SMILES_ATOMS = ABC_MAX_SIM_ATOMS };
 
 /* Candidate extraction for the SMILES decoder (img2smiles2.py:113-191; replaces its per-pixel .cpu().item() loops):
  * from the NMS masks of abc_nms_peaks and the raw head maps (all NCHW f32) to compact ordered lists per image.
@@ -809,8 +811,9 @@ int abc_extract_peaks(const abc_extract_desc* d, abc_stream_t stream);
  * reference's results.append(None)); ABC_MOL_TRUNCATED: the extractor truncated a list or cap_mol_bonds was hit (the stored
  * molecule is then built from the truncated lists).  Bond peaks without a surviving candidate give zero atoms and zero bonds. */
 enum abc_mol_status { ABC_MOL_EMPTY = 1, ABC_MOL_TRUNCATED = 2 };
-/* the bits abc_write_molblocks adds to the two above in its own status words (never in mol_counts) */
-enum abc_text_status { ABC_TEXT_BAD_ROW = 4, ABC_TEXT_OVERFLOW = 8 };
+/* the bits abc_write_molblocks and abc_write_smiles add to the two above in their own status words (never in mol_counts);
+ * RING_LIMIT is the SMILES writer's alone */
+enum abc_text_status { ABC_TEXT_BAD_ROW = 4, ABC_TEXT_OVERFLOW = 8, ABC_TEXT_RING_LIMIT = 16 };
 typedef struct abc_assemble_desc {
     const int32_t* counts;    /* [B][4]            as abc_extract_desc.counts */
     const int32_t* atoms;     /* [B][cap_atoms][5] */
@@ -1059,6 +1062,70 @@ int64_t abc_molblock_text_bytes(const abc_molblock_desc* d);
 int abc_write_molblocks(const abc_molblock_desc* d, abc_stream_t stream);
 /* sizeof(abc_molblock_desc), for a binding's mirror struct (as abc_graph_similarity_desc_size) */
 int abc_molblock_desc_size(void);
+
+/* A SMILES string for every assembled molecule, written on the device from the rows of abc_assemble_graphs, read in place
+ * (csrc/smiles.hip; decode.Molecule.smiles() is the host form and the oracle; the rule with its examples: DESIGN.md section 7).
+ * NOT the canonical SMILES RDKit prints: a deterministic, valid SMILES whose graph is the graph of the rows.  Wedge bonds are
+ * single bonds and stereo is not written; x, y, hs and the bond's source are not read.  Two launches on the stream, integers only,
+ * one workgroup per image, no atomics on global memory, no allocation, no sync; deterministic.
+ *   input    image b's rows, atom and bond counts clamped to their capacities: atoms (x, y, vocabulary index, charge VALUE, hs),
+ *            bonds (end 1, end 2 (1-based), order 1..6, source), mol_implh k 1-based atom indices (one outside 1..n is ignored);
+ *   classes  symbol: the 14-entry table of decode.ATOM_SYMBOLS (index 0 is carbon).  Order class: 5 and 6 -> 1, else the order.
+ *            An atom is AROMATIC iff its symbol is one of B C N O P S Se and one of its bonds has class 4; LISTED iff mol_implh
+ *            names it;
+ *   token    bare ("C", "Cl", "n") iff the charge is 0, the atom is not listed and the symbol is one of B C N O P S F Cl Br I;
+ *            else "[" symbol, "H" if h = 1 or "H<h>" if h >= 2, the charge ("+", "-", "+<n>", "-<n>"), "]".  An aromatic atom's
+ *            symbol is in lower case ("se").  h: 1 for a listed atom (what MRV_IMPLICIT_H sets in the mol block); 0 for symbol H
+ *            or |charge| > 1; else with v = floor(s2 / 2), s2 = the sum over the atom's bonds of 3 for class 4 and 2 * class
+ *            otherwise, h = t - v for the smallest t >= v of the atom's valence list, 0 without such a t.  The lists, as
+ *            (charge -1 | 0 | +1): B 4|3|2, C 3|4|3, N 2|3|4, O 1|2|3, F -|1|2, Si 3,5|4|3, P 2,4,6|3,5|4, S and Se 1|2,4,6|3,5,
+ *            Cl, Br and I -|1|2,4,6.  The table is this library's; no agreement with RDKit's valence model is claimed;
+ *   bond     between u and v: class 1 nothing, but "-" if both are aromatic; 2 "="; 3 "#"; 4 nothing if both are aromatic, else ":";
+ *   walk     components in order of their lowest atom index, which is the root, joined by ".".  Depth first: visiting a gives it
+ *            the next preorder rank; its neighbours are scanned in ascending atom index by a cursor that is never restarted: the
+ *            tree parent and a neighbour whose edge to a already is a ring bond are skipped, a visited neighbour x makes (x, a) a
+ *            ring bond OPENED at x and CLOSED at a, an unvisited one becomes the next child of a and is walked at once;
+ *   digits   atoms in preorder; at each, first its closings in ascending rank of the opener, each as the bond symbol and the
+ *            number, then its openings in ascending rank of the closer, each taking the lowest free number of 1..99 and written as
+ *            the number alone; only then are the numbers of the closings free again.  1..9 are one digit, 10..99 "%nn";
+ *   text(a)  the token of a, its digits, then "(" bond text(child) ")" for every child but the last in scan order, then bond
+ *            text(last child);
+ *   text     the strings of the batch back to back in image order, image b is text[offsets[b] .. offsets[b+1]) (ASCII);
+ *   index    offsets[0 .. B], then status[0 .. B-1];
+ *   status   ABC_MOL_EMPTY / ABC_MOL_TRUNCATED copied from mol_counts (EMPTY: length 0; zero atoms without EMPTY: the empty string,
+ *            status 0); ABC_TEXT_BAD_ROW, length 0: a vocabulary index outside 0..13, a charge outside -15..15, a bond order
+ *            outside 1..6, a bond end outside 1..n, both ends of a bond on one atom, a second row for an atom pair (in either
+ *            orientation) -- the assembler writes none of these; ABC_TEXT_RING_LIMIT, length 0: an opening finds no free number
+ *            (more than 99 ring bonds open at once); ABC_TEXT_OVERFLOW: an image is written only if the UNCLIPPED running total of
+ *            the lengths through it is <= cap_text -- the first image that does not fit and every image after it have length 0 and
+ *            this bit, so what is written is a prefix of the batch;
+ *   work     scratch, abc_smiles_work_ints() int32: the length of every image (negative: refused), then one slice of
+ *            abc_smiles_text_bytes() bytes per image -- the walk is done once, by the first launch, which leaves the image's
+ *            bytes there; the second applies the prefix rule and copies. */
+typedef struct abc_smiles_desc {
+    const int32_t* mol_counts;   /* [B][4]                 as abc_assemble_desc.mol_counts */
+    const int32_t* mol_atoms;    /* [B][cap_atoms][5] */
+    const int32_t* mol_bonds;    /* [B][cap_mol_bonds][4] */
+    const int32_t* mol_implh;    /* [B][cap_atoms] */
+    int32_t B, cap_atoms, cap_mol_bonds;   /* B >= 1, cap_atoms 1..ABC_MAX_SMILES_ATOMS, cap_mol_bonds 1..4096 */
+    uint8_t* text;               /* [cap_text] */
+    int32_t* index;              /* [2 B + 1] */
+    int32_t* work;               /* [abc_smiles_work_ints()] */
+    int64_t cap_text;            /* 1 .. 2^31 - 1 */
+} abc_smiles_desc;
+/* Host arithmetic only (of the descriptor only cap_atoms and cap_mol_bonds are read): an upper bound of ONE image's text at these
+ * capacities, 0 for capacities below 1.  Derived token by token with everything at its widest: every atom may stand behind a "."
+ * or a "(" and a bond symbol (2), be "[" a two-letter symbol "H" and a digit, a sign and two digits "]" (9) and be followed by one
+ * ")" (there are fewer brackets than atoms): 12 per atom; every bond row may be a ring bond with "%nn" at its opening and a bond
+ * symbol and "%nn" at its closing: 7 per bond.  12 cap_atoms + 7 cap_mol_bonds: 20 480 bytes at 512 atoms and 2048 bonds. */
+int64_t abc_smiles_text_bytes(const abc_smiles_desc* d);
+/* Host arithmetic only: the int32 words of `work` (B, cap_atoms, cap_mol_bonds are read), 0 for a B or a capacity below 1 */
+int64_t abc_smiles_work_ints(const abc_smiles_desc* d);
+/* refuses null pointers, B < 1, capacities < 1 and cap_text outside 1 .. 2^31 - 1 (ABC_EINVAL), cap_atoms above
+ * ABC_MAX_SMILES_ATOMS and cap_mol_bonds above 4096 (ABC_EUNSUPPORTED); nothing is launched then */
+int abc_write_smiles(const abc_smiles_desc* d, abc_stream_t stream);
+/* sizeof(abc_smiles_desc), for a binding's mirror struct (as abc_molblock_desc_size) */
+int abc_smiles_desc_size(void);
 
 /* ---- unet2: CBAM attention + residual (unet2.py:6-74).  See csrc/cbam.hip for the pass structure. ---- */
 typedef struct abc_cbam_channel_desc { /* ChannelAttentionModule (unet2.py:6-22), one MLP evaluation per image */

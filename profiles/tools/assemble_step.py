@@ -25,13 +25,18 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            repetitions), abc_write_molblocks alone (its two launches, as `launch`), the bytes molblocks() copies, and step() with
            assemble=True against the same with molblocks=True (as `step`, with the spread of the block medians)
 
+  smiles   a SMILES string written on the device (csrc/smiles.hip, InferenceRunner(smiles=True)): molecules() plus
+           Molecule.smiles() of every image on the host against smiles() (as `text`), abc_write_smiles alone beside
+           abc_write_molblocks (two launches each, as `launch`), the bytes smiles() copies, and step() with assemble=True against the
+           same with molblocks=True and with smiles=True (as `text`'s step)
+
   --omega-rule {raw,peaks}: the extractor's candidate rule of every runner built here (InferenceRunner(omega_rule=...): "raw" is
            img2smiles2.py:139, "peaks" img2smiles.py:139 / img2smiles3.py:140); `graphs` and `score` then also report the candidates
            per image and abc_extract_peaks alone (as `launch`).  profiles/r09_omega_rule.md is one run per rule.
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text] [--omega-rule raw]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw]
 """
 import argparse
 import json
@@ -170,6 +175,33 @@ def part_host(r, reps=20):
           "note": "wall time of one call per batch of %d: D2H copies + host list building, one host thread" % B})
 
 
+def step_blocks(rs, steps, warmup, part):
+    """the step of every runner of rs in eight alternated blocks: one line per form with the median of its block medians and their
+    spread; returns {form: that median}"""
+    for q in rs.values():
+        for _ in range(warmup):
+            q.step()
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in rs}
+    for blk in range(8):
+        for name, q in (rs.items() if blk % 2 == 0 else reversed(list(rs.items()))):
+            ev = []
+            for _ in range(max(steps // 8, 1)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                q.step()
+                e1.record()
+                ev.append((e0, e1))
+            torch.cuda.synchronize()
+            blocks[name].append(statistics.median(a.elapsed_time(b) for a, b in ev))
+    med = {k: statistics.median(v) for k, v in blocks.items()}
+    for k, v in blocks.items():
+        emit({"part": part, "what": "step", "form": k, "batch": B, "size": S, "blocks": len(v), "ms_per_step_median": round(med[k], 4),
+              "block_medians_min_max": [round(min(v), 4), round(max(v), 4)],
+              "block_spread_percent": round(100 * (max(v) - min(v)) / med[k], 3)})
+    return med
+
+
 def part_text(m, x, steps, warmup, reps=30, iters=200):
     rs = {}
     for name, kw in (("assemble=True", dict(assemble=True)), ("assemble+molblocks", dict(assemble=True, molblocks=True))):
@@ -202,28 +234,54 @@ def part_text(m, x, steps, warmup, reps=30, iters=200):
           "assemble_us_per_launch": round(launch_us(r.assembler.run, iters), 2),
           "method": "device events around %d back-to-back calls of two launches each (launch gaps included)" % iters})
     # the step: block medians of each form as well, for the block-to-block spread
-    for q in rs.values():
-        for _ in range(warmup):
-            q.step()
-    torch.cuda.synchronize()
-    blocks = {k: [] for k in rs}
-    for blk in range(8):
-        for name, q in (rs.items() if blk % 2 == 0 else reversed(list(rs.items()))):
-            ev = []
-            for _ in range(max(steps // 8, 1)):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                q.step()
-                e1.record()
-                ev.append((e0, e1))
-            torch.cuda.synchronize()
-            blocks[name].append(statistics.median(a.elapsed_time(b) for a, b in ev))
-    med = {k: statistics.median(v) for k, v in blocks.items()}
-    for k, v in blocks.items():
-        emit({"part": "text", "what": "step", "form": k, "batch": B, "size": S, "blocks": len(v), "ms_per_step_median": round(med[k], 4),
-              "block_medians_min_max": [round(min(v), 4), round(max(v), 4)],
-              "block_spread_percent": round(100 * (max(v) - min(v)) / med[k], 3)})
+    med = step_blocks(rs, steps, warmup, "text")
     emit({"part": "text", "molblocks_minus_assemble_ms": round(med["assemble+molblocks"] - med["assemble=True"], 4)})
+
+
+def part_smiles(m, x, steps, warmup, reps=30, iters=200):
+    rs = {}
+    for name, kw in (("assemble=True", dict(assemble=True)), ("assemble+molblocks", dict(assemble=True, molblocks=True)),
+                     ("assemble+smiles", dict(assemble=True, smiles=True))):
+        r = InferenceRunner(m, B, S, S, use_graph=True, omega_rule=RULE, **kw)
+        r.load_batch(x.to("cuda"))
+        for _ in range(2):
+            r.step()
+        rs[name] = r
+    torch.cuda.synchronize()
+    r = rs["assemble+smiles"]
+
+    def host():
+        return [mol.smiles() if mol is not None else None for mol in r.molecules()]
+    status = r.smiler.status()
+    refused = sum(bool(s & ~3) for s in status)      # (BAD_ROW, OVERFLOW, RING_LIMIT: smiles() would raise)
+    wall = {"host": [], "device": []}
+    if not refused:
+        want, got = host(), r.smiles()
+        for _ in range(reps):
+            for name, f in (("host", host), ("device", r.smiles)):
+                t0 = time.perf_counter()
+                f()
+                wall[name].append((time.perf_counter() - t0) * 1000)
+        off = r.smiler.index.cpu().tolist()[:B + 1]
+        mc = r.assembler.mol_counts.cpu()
+        med = {k: statistics.median(v) for k, v in wall.items()}
+        emit({"part": "smiles", "what": "host", "batch": B, "molecules_plus_smiles_ms": round(med["host"], 4),
+              "molecules_plus_smiles_ms_min": round(min(wall["host"]), 4), "smiles_ms": round(med["device"], 4),
+              "smiles_ms_min": round(min(wall["device"]), 4), "ratio": round(med["host"] / med["device"], 2), "equal": got == want,
+              "molecules": sum(t is not None for t in got), "text_bytes": off[B], "index_bytes": 4 * (2 * B + 1),
+              "longest_text": max(len(t) for t in got if t is not None), "cap_text": r.smiler.cap_text,
+              "molecule_atoms_mean_max": [round(float(mc[:, 0].float().mean()), 1), int(mc[:, 0].max())],
+              "molecule_bonds_mean_max": [round(float(mc[:, 1].float().mean()), 1), int(mc[:, 1].max())],
+              "note": "wall time of one call per batch of %d, %d alternated repetitions, one host thread" % (B, reps)})
+    else:
+        emit({"part": "smiles", "what": "host", "refused_images": refused, "status": status})
+    us = [(launch_us(r.smiler.run, iters), launch_us(rs["assemble+molblocks"].texter.run, iters)) for _ in range(3)]
+    emit({"part": "smiles", "what": "launch", "batch": B, "us_per_call": [round(a, 2) for a, _ in us],
+          "molblocks_us_per_call": [round(b, 2) for _, b in us], "assemble_us_per_launch": round(launch_us(r.assembler.run, iters), 2),
+          "method": "device events around %d back-to-back calls of two launches each (launch gaps included)" % iters})
+    med = step_blocks(rs, steps, warmup, "smiles")
+    emit({"part": "smiles", "smiles_minus_assemble_ms": round(med["assemble+smiles"] - med["assemble=True"], 4),
+          "molblocks_minus_assemble_ms": round(med["assemble+molblocks"] - med["assemble=True"], 4)})
 
 
 def annotated_graph(atoms_s, bonds_s):
@@ -318,27 +376,7 @@ def part_identity(rs, steps, warmup, iters=200):
     emit(out)
     r.reset_evaluation()
     pair = {k: rs[k] for k in (without, with_id)}
-    for q in pair.values():
-        for _ in range(warmup):
-            q.step()
-    torch.cuda.synchronize()
-    blocks = {k: [] for k in pair}
-    for blk in range(8):
-        for name, q in (pair.items() if blk % 2 == 0 else reversed(list(pair.items()))):
-            ev = []
-            for _ in range(max(steps // 8, 1)):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                q.step()
-                e1.record()
-                ev.append((e0, e1))
-            torch.cuda.synchronize()
-            blocks[name].append(statistics.median(a.elapsed_time(b) for a, b in ev))
-    med = {k: statistics.median(v) for k, v in blocks.items()}
-    for k, v in blocks.items():
-        emit({"part": "identity", "what": "step", "form": k, "batch": B, "size": S, "blocks": len(v), "ms_per_step_median": round(med[k], 4),
-              "block_medians_min_max": [round(min(v), 4), round(max(v), 4)],
-              "block_spread_percent": round(100 * (max(v) - min(v)) / med[k], 3)})
+    med = step_blocks(pair, steps, warmup, "identity")
     emit({"part": "identity", "identity_minus_similarity_ms": round(med[with_id] - med[without], 4)})
 
 
@@ -410,6 +448,8 @@ def main():
         part_identity(ss, a.steps, a.warmup)
     if "text" in parts:
         part_text(m, x, a.steps, a.warmup)
+    if "smiles" in parts:
+        part_smiles(m, x, a.steps, a.warmup)
 
 
 if __name__ == "__main__":
