@@ -229,6 +229,10 @@ class SmilesDesc(C.Structure):
                 ("cap_mol_bonds", i32), ("text", vp), ("index", vp), ("work", vp), ("cap_text", i64)]
 
 
+class SmilesStereoDesc(C.Structure):
+    _fields_ = SmilesDesc._fields_ + [("stereo_stats", vp), ("stereo_out", vp)]
+
+
 class ScanDesc(C.Structure):
     _fields_ = [("out", vp), ("src", vp), ("src_stride", i64), ("src_pitch", i32), ("src_max_h", i32), ("params", vp),
                 ("params_host", vp), ("B", i32), ("S", i32), ("margin", i32), ("cover_q8", i32), ("polarity", i32), ("hist", vp),
@@ -279,6 +283,9 @@ MAX_CAP_ATOMS, MAX_BOND_PEAKS, MAX_SCORE_RECORD, MAX_SIM_ATOMS = 2048, 4096, 102
 TEXT_BAD_ROW, TEXT_OVERFLOW = 4, 8  # abc_text_status (the status words of abc_write_molblocks)
 TEXT_RING_LIMIT = 16                # abc_text_status, abc_write_smiles alone
 MAX_SMILES_ATOMS, MAX_SMILES_BONDS = MAX_SIM_ATOMS, 4096    # ABC_MAX_SMILES_ATOMS; cap_mol_bonds of abc_write_smiles
+# the columns of abc_smiles_stereo_desc.stereo_stats; the codes of .stereo_out beside +1 / -1
+SMILES_STEREO_COLUMNS = ("marked", "flat", "unqualified", "wedge_rows")
+STEREO_NONE, STEREO_FLAT, STEREO_UNQUALIFIED = 0, 2, 3
 
 
 _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnApplyDesc, WgradDesc, WgradReduceDesc,
@@ -291,7 +298,8 @@ SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_scor
               (ScanDesc, "abc_scan_desc_size")]
 # (that list is pinned, name by name, by tests/test_decoder_contract_host.py) the self-sized descriptors since: checked the same way
 SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "abc_graph_identity_desc_size"),
-                    (ScanCleanDesc, "abc_scan_clean_desc_size"), (SmilesDesc, "abc_smiles_desc_size")]
+                    (ScanCleanDesc, "abc_scan_clean_desc_size"), (SmilesDesc, "abc_smiles_desc_size"),
+                    (SmilesStereoDesc, "abc_smiles_stereo_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -387,6 +395,10 @@ SYMBOLS = {
     "abc_smiles_work_ints": (i64, [P(SmilesDesc)]),
     "abc_write_smiles": (C.c_int, [P(SmilesDesc), vp]),
     "abc_smiles_desc_size": (C.c_int, []),
+    "abc_smiles_stereo_text_bytes": (i64, [P(SmilesStereoDesc)]),
+    "abc_smiles_stereo_work_ints": (i64, [P(SmilesStereoDesc)]),
+    "abc_write_smiles_stereo": (C.c_int, [P(SmilesStereoDesc), vp]),
+    "abc_smiles_stereo_desc_size": (C.c_int, []),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "abc_plane_sum_work": (C.c_int, [i32]),
     "abc_cbam_channel_fwd": (C.c_int, [P(CbamChannelDesc), vp]),

@@ -7,17 +7,21 @@
 //     1  validate every row; count degrees by LDS atomics, scan them, fill a CSR adjacency of (neighbour << 3 | order class)
 //     2  order every atom's list by neighbour index (a rank sort, one slot per thread at a time: position = how many of the list
 //        are smaller); equal neighbours side by side are a pair listed twice
-//     3  per atom: aromatic flag and hydrogen count
+//     3  per atom: aromatic flag and hydrogen count; <stereo> the centre's code from its wedge slots, its neighbours' positions and
+//        an int64 determinant (one byte per atom), after which a wedge slot is a class-1 slot like any other
 //     4  ONE lane walks the graph (depth first, the parent pointers are the stack: no restart of a cursor, 2 m + n steps): preorder
 //        rank, parent, the class of the bond to the parent, which atoms open a branch and how many ")" follow each position
 //     5  order every list again, by the RANK of the neighbour: a neighbour that is neither the parent nor a child is the other end of
 //        a ring bond, the lower ranks (closings) now come first and both kinds in the order the rule writes them; every slot
 //        finds its twin in the neighbour's list (binary search)
 //     6  ONE lane hands out the ring numbers in preorder (the free numbers are two 64-bit masks), O(n + m)
-//     7  all threads: the byte length of every preorder position, a workgroup scan, and every thread writes its positions
+//     7  all threads: the byte length of every preorder position, a workgroup scan, and every thread writes its positions;
+//        <stereo> a centre's mark is its code times the sign of the permutation from index order to the order the text names
 //   smiles_pack_kernel     one workgroup per image: the prefix rule over work[0 .. b] (text_pack.hpp), then a copy of the image's bytes
 // Lengths and bytes come from ONE emitter run over two sinks, so they cannot disagree; every store of either kernel is checked
 // against the end of the image's own bytes.
+// Both kernels are templates over a stereo flag (abc_write_smiles_stereo, the tetrahedral rule of DESIGN.md section 7); without it
+// every stereo line is compiled out.
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
@@ -91,14 +95,17 @@ __device__ inline void put_bond(Sink& o, int cls, bool both_aromatic) {
     else if (cls == 3) o.put('#');
     else if (!both_aromatic) o.put(':');
 }
+// marks: 0 none, 1 "@", 2 "@@" (a marked atom is never bare)
 template <class Sink>
-__device__ inline void put_token(Sink& o, int sym, int charge, int h, bool aromatic, bool listed) {
+__device__ inline void put_token(Sink& o, int sym, int charge, int h, bool aromatic, bool listed, int marks = 0) {
     const int lower = aromatic ? 0x20 : 0;
-    const bool bare = charge == 0 && !listed && (BARE_SET >> sym & 1u);
+    const bool bare = charge == 0 && !listed && (BARE_SET >> sym & 1u) && marks == 0;
     if (!bare) o.put('[');
     o.put(SYMBOL2[sym * 2] | lower);
     if (SYMBOL2[sym * 2 + 1] != ' ') o.put(SYMBOL2[sym * 2 + 1]);
     if (bare) return;
+    if (marks >= 1) o.put('@');
+    if (marks >= 2) o.put('@');
     if (h >= 1) o.put('H');
     if (h >= 2) o.put('0' + h);            // (h <= 6: the largest valence)
     if (charge != 0) {
@@ -151,9 +158,60 @@ __device__ inline void order_lists(Walk& w, int na, int slots, int src, int tid)
     }
 }
 
+// stereo: the code of an atom (abc_smiles_stereo_desc.stereo_out), one byte of LDS each
+constexpr int ST_NONE = 0, ST_FLAT = 2, ST_UNQUALIFIED = 3;      // (+1 / -1: the local parity of a marked centre)
+constexpr int MAX_POSITION = 199999;                             // the mol block's range: every product below stays under 2^40
+
+// The code of atom i, a candidate (end 1 of a wedge row), by the rule: deg slots from lo in ascending neighbour index, zbits two
+// bits per slot (1: order 5, 2: order 6, from this end), single = every bond has class 1, h the text rule's hydrogen count.
+__device__ inline int stereo_code(const Walk& w, const int* pa, int i, int lo, int deg, unsigned zbits, bool single, int h) {
+    if (w.sym[i] == 12 || !single || !((deg == 4 && h == 0) || (deg == 3 && h == 1))) return ST_UNQUALIFIED;
+    const int xa = pa[i * ATOM_W], ya = pa[i * ATOM_W + 1];
+    bool flat = xa < 0 || xa > MAX_POSITION || ya < 0 || ya > MAX_POSITION;
+    long long px[4], py[4], pz[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        px[k] = py[k] = pz[k] = 0;         // (the hydrogen of deg == 3 stands on the centre)
+        if (k < deg) {
+            const int j = w.adj[1][lo + k] >> 3;      // (< na: the row's ends were checked in step 1)
+            const int x = pa[j * ATOM_W], y = pa[j * ATOM_W + 1];
+            flat |= x < 0 || x > MAX_POSITION || y < 0 || y > MAX_POSITION || (x == xa && y == ya);
+            const unsigned z = zbits >> (2 * k) & 3u;
+            px[k] = (long long)x - xa, py[k] = (long long)y - ya, pz[k] = z == 1 ? 1 : (z == 2 ? -1 : 0);
+        }
+    }
+    if (flat) return ST_FLAT;
+    const long long a1 = px[0] - px[3], a2 = py[0] - py[3], a3 = pz[0] - pz[3];
+    const long long b1 = px[1] - px[3], b2 = py[1] - py[3], b3 = pz[1] - pz[3];
+    const long long c1 = px[2] - px[3], c2 = py[2] - py[3], c3 = pz[2] - pz[3];
+    const long long t = a1 * (b2 * c3 - b3 * c2) - a2 * (b1 * c3 - b3 * c1) + a3 * (b1 * c2 - b2 * c1);
+    return t == 0 ? ST_FLAT : (t > 0 ? 1 : -1);
+}
+
+// The mark of a centre at preorder position p: 1 "@", 2 "@@".  The text names its four neighbours as parent, hydrogen, closings,
+// openings, children (the lists are in rank order: each kind stands in the order it is written); the local order is ascending
+// index with the hydrogen last, so the permutation's sign is the parity of the pairs out of order.
+__device__ inline int stereo_marks(const Walk& w, int a, int p, int code) {
+    const int par = w.parent[a], lo = w.start[a], hi = w.start[a + 1];
+    unsigned long long named = 0;          // 16 bits per neighbour, the first in the highest place used
+    if (par >= 0) named = (unsigned)par;
+    if (hi - lo == 3) named = named << 16 | 0xFFFFu;
+    for (int s = lo; s < hi; ++s) {        // closings, then openings
+        const int y = w.adj[0][s] >> 3;
+        if (y != par && w.parent[y] != a) named = named << 16 | (unsigned)y;
+    }
+    for (int s = lo; s < hi; ++s) {
+        const int y = w.adj[0][s] >> 3;
+        if (y != par && w.parent[y] == a) named = named << 16 | (unsigned)y;
+    }
+    const int k0 = (int)(named >> 48 & 0xFFFFu), k1 = (int)(named >> 32 & 0xFFFFu), k2 = (int)(named >> 16 & 0xFFFFu), k3 = (int)(named & 0xFFFFu);
+    const int swaps = (k0 > k1) + (k0 > k2) + (k0 > k3) + (k1 > k2) + (k1 > k3) + (k2 > k3);
+    return ((swaps & 1) ? -code : code) > 0 ? 1 : 2;
+}
+
 // position p of the preorder: what stands in front of the atom, its token, its ring digits, the brackets behind it
-template <class Sink>
-__device__ inline void put_position(Sink& o, const Walk& w, int p) {
+template <bool STEREO, class Sink>
+__device__ inline void put_position(Sink& o, const Walk& w, const signed char* centre, int p) {
     const int a = w.order[p], par = w.parent[a];
     const bool arom = w.aromatic[a] != 0;
     if (par < 0) {
@@ -162,7 +220,12 @@ __device__ inline void put_position(Sink& o, const Walk& w, int p) {
         if (w.opens[a]) o.put('(');
         put_bond(o, w.parent_cls[a], arom && w.aromatic[par]);
     }
-    put_token(o, w.sym[a], w.charge[a], w.hcount[a], arom, w.listed[a] != 0);
+    int marks = 0;
+    if (STEREO) {
+        const int code = centre[a];
+        if (code == 1 || code == -1) marks = stereo_marks(w, a, p, code);
+    }
+    put_token(o, w.sym[a], w.charge[a], w.hcount[a], arom, w.listed[a] != 0, marks);
     for (int s = w.start[a], hi = w.start[a + 1]; s < hi; ++s) {
         const int e = w.adj[0][s], y = e >> 3;
         if (y == par || w.parent[y] == a) continue;
@@ -172,8 +235,12 @@ __device__ inline void put_position(Sink& o, const Walk& w, int p) {
     for (int i = w.closes[p]; i > 0; --i) o.put(')');
 }
 
+template <bool STEREO> struct DescOf { typedef abc_smiles_desc type; };
+template <> struct DescOf<true> { typedef abc_smiles_stereo_desc type; };
+
 struct Counts { int na, nb, nh, status; };
-__device__ inline Counts read_counts(const abc_smiles_desc& d, int b) {
+template <class Desc>
+__device__ inline Counts read_counts(const Desc& d, int b) {
     const int* mc = d.mol_counts + (size_t)b * 4;
     Counts c;
     c.na = clampi(mc[0], 0, d.cap_atoms);
@@ -183,21 +250,35 @@ __device__ inline Counts read_counts(const abc_smiles_desc& d, int b) {
     return c;
 }
 
-// bytes one image may take at these capacities (abc_smiles_text_bytes): also the stride of the slices of `work`
-__host__ __device__ inline int64_t image_bytes(int64_t cap_atoms, int64_t cap_mol_bonds) { return 12 * cap_atoms + 7 * cap_mol_bonds; }
-__device__ inline uint8_t* slice_of(const abc_smiles_desc& d, int b) {
-    return (uint8_t*)(d.work + d.B) + (size_t)b * (size_t)image_bytes(d.cap_atoms, d.cap_mol_bonds);
+// bytes one image may take at these capacities (abc_smiles_text_bytes, abc_smiles_stereo_text_bytes: a marked token is two bytes
+// longer and never bare): also the stride of the slices of `work`
+template <bool STEREO>
+__host__ __device__ inline int64_t image_bytes(int64_t cap_atoms, int64_t cap_mol_bonds) { return (STEREO ? 14 : 12) * cap_atoms + 7 * cap_mol_bonds; }
+template <bool STEREO>
+__device__ inline uint8_t* slice_of(const typename DescOf<STEREO>::type& d, int b) {
+    return (uint8_t*)(d.work + d.B) + (size_t)b * (size_t)image_bytes<STEREO>(d.cap_atoms, d.cap_mol_bonds);
 }
 
-__global__ __launch_bounds__(ST) void smiles_compose_kernel(const abc_smiles_desc d) {
+// stereo, an image without text (EMPTY, refused): a row of zeros, and every word of its slice of stereo_out
+__device__ inline void no_centres(const abc_smiles_stereo_desc& d, int b, int tid) {
+    if (tid < 4) d.stereo_stats[(size_t)b * 4 + tid] = 0;
+    if (d.stereo_out != nullptr)
+        for (int i = tid; i < d.cap_atoms; i += ST) d.stereo_out[(size_t)b * d.cap_atoms + i] = 0;
+}
+
+template <bool STEREO>
+__global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescOf<STEREO>::type d) {
     __shared__ Walk w;
     __shared__ unsigned wt[ST / 64 + 1];
     __shared__ int refused;                // 0, LEN_BAD_ROW or LEN_RING_LIMIT
+    __shared__ signed char centre[STEREO ? MAX_ATOMS : 1];      // <stereo> the code of every atom
+    __shared__ int tally[4];                                    // <stereo> marked, flat, unqualified, wedge rows
     const int b = blockIdx.x, tid = threadIdx.x;
     const Counts c = read_counts(d, b);
     const int na = c.na, nb = c.nb, slots = 2 * nb;
     if ((c.status & ABC_MOL_EMPTY) || na == 0) {      // (uniform.  Bonds without an atom cannot be: their ends are outside 1..0)
         if (tid == 0) d.work[b] = (c.status & ABC_MOL_EMPTY) || nb == 0 ? 0 : LEN_BAD_ROW;
+        if constexpr (STEREO) no_centres(d, b, tid);
         return;
     }
     const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
@@ -206,6 +287,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const abc_smiles_des
 
     // ---- 1: rows
     if (tid == 0) refused = 0;
+    if (STEREO && tid < 4) tally[tid] = 0;
     for (int i = tid; i < na; i += ST) {
         w.deg[i] = 0;
         w.rank[i] = w.parent[i] = w.last_child[i] = -1;
@@ -237,6 +319,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const abc_smiles_des
     __syncthreads();
     if (refused) {                         // (uniform: read behind the barrier)
         if (tid == 0) d.work[b] = LEN_BAD_ROW;
+        if constexpr (STEREO) no_centres(d, b, tid);
         return;
     }
     {   // every thread takes atoms 2 tid and 2 tid + 1
@@ -251,9 +334,12 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const abc_smiles_des
     for (int q = tid; q < nb; q += ST) {
         int e1, e2;
         mol_ends(pb, q, na, e1, e2);       // (true for every row: checked above)
-        const int cls = bond_class(pb[q * MOL_BOND_W + 2]);
-        w.adj[0][w.start[e1] + atomicAdd(&w.deg[e1], 1)] = (unsigned short)(e2 << 3 | cls);
+        const int order = pb[q * MOL_BOND_W + 2], cls = bond_class(order);
+        // <stereo> a wedge speaks for its end 1 alone: that end's slot keeps the order, 5 or 6, in the three class bits until step 3
+        const bool wedge = STEREO && order >= 5;
+        w.adj[0][w.start[e1] + atomicAdd(&w.deg[e1], 1)] = (unsigned short)(e2 << 3 | (wedge ? order : cls));
         w.adj[0][w.start[e2] + atomicAdd(&w.deg[e2], 1)] = (unsigned short)(e1 << 3 | cls);
+        if (wedge) atomicAdd(&tally[3], 1);
     }
     __syncthreads();
 
@@ -268,18 +354,35 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const abc_smiles_des
     // ---- 3: classes
     for (int i = tid; i < na; i += ST) {
         int s2 = 0, any4 = 0;
-        for (int s = w.start[i], hi = w.start[i + 1]; s < hi; ++s) {
-            const int cls = w.adj[1][s] & 7;
+        unsigned zbits = 0;
+        const int lo = w.start[i], deg = w.start[i + 1] - lo;
+        for (int s = lo, hi = lo + deg; s < hi; ++s) {
+            int cls = w.adj[1][s] & 7;
+            if (STEREO && cls >= 5) {      // this atom's own wedge: from here on a class-1 slot (no other thread reads this list now)
+                if (s - lo < 4) zbits |= (unsigned)(cls - 4) << (2 * (s - lo));
+                zbits |= 1u << 8;
+                cls = 1;
+                w.adj[1][s] = (unsigned short)((w.adj[1][s] & ~7) | 1);
+            }
             s2 += cls == 4 ? 3 : 2 * cls;
             any4 |= cls == 4;
         }
         w.aromatic[i] = (unsigned char)(any4 && (AROMATIC_SET >> w.sym[i] & 1u));
         w.hcount[i] = (unsigned char)(w.listed[i] ? 1 : hydrogens(w.sym[i], w.charge[i], s2));
         w.cursor[i] = w.start[i];
+        if constexpr (STEREO) {
+            int code = ST_NONE;
+            if (zbits) {
+                code = stereo_code(w, pa, i, lo, deg, zbits & 0xFFu, s2 == 2 * deg, w.hcount[i]);
+                atomicAdd(&tally[code == ST_FLAT ? 1 : (code == ST_UNQUALIFIED ? 2 : 0)], 1);
+            }
+            centre[i] = (signed char)code;
+        }
     }
     __syncthreads();
     if (refused) {
         if (tid == 0) d.work[b] = LEN_BAD_ROW;
+        if constexpr (STEREO) no_centres(d, b, tid);
         return;
     }
 
@@ -365,6 +468,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const abc_smiles_des
     __syncthreads();
     if (refused) {
         if (tid == 0) d.work[b] = LEN_RING_LIMIT;
+        if constexpr (STEREO) no_centres(d, b, tid);
         return;
     }
 
@@ -372,16 +476,22 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const abc_smiles_des
     int lo, hi;
     text_pack::my_range<ST>(na, tid, lo, hi);
     Count n = {0};
-    for (int p = lo; p < hi; ++p) put_position(n, w, p);
+    for (int p = lo; p < hi; ++p) put_position<STEREO>(n, w, centre, p);
     unsigned total;
     const unsigned first = block_excl_scan<ST>((unsigned)n.n, wt, &total);
-    uint8_t* slice = slice_of(d, b);
-    Write o = {slice + first, slice + image_bytes(d.cap_atoms, d.cap_mol_bonds)};
-    for (int p = lo; p < hi; ++p) put_position(o, w, p);
+    uint8_t* slice = slice_of<STEREO>(d, b);
+    Write o = {slice + first, slice + image_bytes<STEREO>(d.cap_atoms, d.cap_mol_bonds)};
+    for (int p = lo; p < hi; ++p) put_position<STEREO>(o, w, centre, p);
     if (tid == 0) d.work[b] = (int)total;
+    if constexpr (STEREO) {
+        if (tid < 4) d.stereo_stats[(size_t)b * 4 + tid] = tally[tid];
+        if (d.stereo_out != nullptr)
+            for (int i = tid; i < d.cap_atoms; i += ST) d.stereo_out[(size_t)b * d.cap_atoms + i] = i < na ? (int)centre[i] : 0;
+    }
 }
 
-__global__ __launch_bounds__(ST) void smiles_pack_kernel(const abc_smiles_desc d) {
+template <bool STEREO>
+__global__ __launch_bounds__(ST) void smiles_pack_kernel(const typename DescOf<STEREO>::type d) {
     const int b = blockIdx.x, tid = threadIdx.x;
     int* offsets = d.index;
     int* status_out = d.index + d.B + 1;
@@ -396,9 +506,30 @@ __global__ __launch_bounds__(ST) void smiles_pack_kernel(const abc_smiles_desc d
     }
     if (overflow || len <= 0) return;
     // (through - before == len, and through <= cap_text: every store is inside the image's own bytes; the slice holds len of them)
-    const uint8_t* slice = slice_of(d, b);
-    const int n = (int)min((long long)len, (long long)image_bytes(d.cap_atoms, d.cap_mol_bonds));
+    const uint8_t* slice = slice_of<STEREO>(d, b);
+    const int n = (int)min((long long)len, (long long)image_bytes<STEREO>(d.cap_atoms, d.cap_mol_bonds));
     for (int i = tid; i < n; i += ST) d.text[span.before + i] = slice[i];
+}
+
+// the guards of both entry points, and the two launches
+template <bool STEREO>
+int write_smiles(const typename DescOf<STEREO>::type* d, abc_stream_t stream, const char* what) {
+    char msg[160];
+#define REFUSE(code, text) return (snprintf(msg, sizeof msg, "%s: %s", what, text), abc_fail(code, msg))
+    if (!d) REFUSE(ABC_EINVAL, "null descriptor");
+    if (d->B < 1) REFUSE(ABC_EINVAL, "empty");
+    if (d->cap_atoms < 1 || d->cap_mol_bonds < 1) REFUSE(ABC_EINVAL, "cap_atoms and cap_mol_bonds must be >= 1");
+    if (d->cap_atoms > MAX_ATOMS) REFUSE(ABC_EUNSUPPORTED, "cap_atoms must be <= 512 (ABC_MAX_SMILES_ATOMS)");
+    if (d->cap_mol_bonds > MAX_BONDS) REFUSE(ABC_EUNSUPPORTED, "cap_mol_bonds must be <= 4096");
+    if (d->cap_text < 1 || d->cap_text > INT32_MAX) REFUSE(ABC_EINVAL, "cap_text must be 1..2^31-1");
+    if (!d->mol_counts || !d->mol_atoms || !d->mol_bonds || !d->mol_implh) REFUSE(ABC_EINVAL, "null molecule buffer");
+    if (!d->text || !d->index || !d->work) REFUSE(ABC_EINVAL, "null output");
+    if constexpr (STEREO)
+        if (!d->stereo_stats) REFUSE(ABC_EINVAL, "null stereo_stats");
+#undef REFUSE
+    hipLaunchKernelGGL(smiles_compose_kernel<STEREO>, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
+    hipLaunchKernelGGL(smiles_pack_kernel<STEREO>, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
+    return abc_check_launch(what);
 }
 
 }  // namespace
@@ -407,24 +538,28 @@ extern "C" int abc_smiles_desc_size(void) { return (int)sizeof(abc_smiles_desc);
 
 extern "C" int64_t abc_smiles_text_bytes(const abc_smiles_desc* d) {
     if (!d || d->cap_atoms < 1 || d->cap_mol_bonds < 1) return 0;
-    return image_bytes(d->cap_atoms, d->cap_mol_bonds);
+    return image_bytes<false>(d->cap_atoms, d->cap_mol_bonds);
 }
 
 extern "C" int64_t abc_smiles_work_ints(const abc_smiles_desc* d) {
     if (!d || d->B < 1 || d->cap_atoms < 1 || d->cap_mol_bonds < 1) return 0;
-    return d->B + (d->B * image_bytes(d->cap_atoms, d->cap_mol_bonds) + 3) / 4;
+    return d->B + (d->B * image_bytes<false>(d->cap_atoms, d->cap_mol_bonds) + 3) / 4;
 }
 
-extern "C" int abc_write_smiles(const abc_smiles_desc* d, abc_stream_t stream) {
-    if (!d) return abc_fail(ABC_EINVAL, "write_smiles: null descriptor");
-    if (d->B < 1) return abc_fail(ABC_EINVAL, "write_smiles: empty");
-    if (d->cap_atoms < 1 || d->cap_mol_bonds < 1) return abc_fail(ABC_EINVAL, "write_smiles: cap_atoms and cap_mol_bonds must be >= 1");
-    if (d->cap_atoms > MAX_ATOMS) return abc_fail(ABC_EUNSUPPORTED, "write_smiles: cap_atoms must be <= 512 (ABC_MAX_SMILES_ATOMS)");
-    if (d->cap_mol_bonds > MAX_BONDS) return abc_fail(ABC_EUNSUPPORTED, "write_smiles: cap_mol_bonds must be <= 4096");
-    if (d->cap_text < 1 || d->cap_text > INT32_MAX) return abc_fail(ABC_EINVAL, "write_smiles: cap_text must be 1..2^31-1");
-    if (!d->mol_counts || !d->mol_atoms || !d->mol_bonds || !d->mol_implh) return abc_fail(ABC_EINVAL, "write_smiles: null molecule buffer");
-    if (!d->text || !d->index || !d->work) return abc_fail(ABC_EINVAL, "write_smiles: null output");
-    hipLaunchKernelGGL(smiles_compose_kernel, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
-    hipLaunchKernelGGL(smiles_pack_kernel, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
-    return abc_check_launch("write_smiles");
+extern "C" int abc_write_smiles(const abc_smiles_desc* d, abc_stream_t stream) { return write_smiles<false>(d, stream, "write_smiles"); }
+
+extern "C" int abc_smiles_stereo_desc_size(void) { return (int)sizeof(abc_smiles_stereo_desc); }
+
+extern "C" int64_t abc_smiles_stereo_text_bytes(const abc_smiles_stereo_desc* d) {
+    if (!d || d->cap_atoms < 1 || d->cap_mol_bonds < 1) return 0;
+    return image_bytes<true>(d->cap_atoms, d->cap_mol_bonds);
+}
+
+extern "C" int64_t abc_smiles_stereo_work_ints(const abc_smiles_stereo_desc* d) {
+    if (!d || d->B < 1 || d->cap_atoms < 1 || d->cap_mol_bonds < 1) return 0;
+    return d->B + (d->B * image_bytes<true>(d->cap_atoms, d->cap_mol_bonds) + 3) / 4;
+}
+
+extern "C" int abc_write_smiles_stereo(const abc_smiles_stereo_desc* d, abc_stream_t stream) {
+    return write_smiles<true>(d, stream, "write_smiles_stereo");
 }

@@ -90,10 +90,20 @@ class Molecule:
         out.append("M  END\n$$$$")
         return "".join(out)
 
-    def smiles(self):
+    def smiles(self, stereo=False):
         """a deterministic, valid SMILES of this graph by the text rule of DESIGN.md section 7 (the host form and the oracle of
-        csrc/smiles.hip, integers only): NOT the canonical string RDKit prints; wedges are single bonds, stereo is not written,
-        hs and the positions are not read.  ValueError for a row the rule refuses and for more than 99 ring bonds open at once."""
+        csrc/smiles.hip, integers only): NOT the canonical string RDKit prints; hs is not read.  stereo=False: wedges are single
+        bonds, no mark is written and the positions are not read.  stereo=True: the tetrahedral centres the wedge rows and the
+        positions decide (stereo_centres) are written as `@` / `@@` in a bracket token; nothing else of the text changes.
+        ValueError for a row the rule refuses and for more than 99 ring bonds open at once."""
+        return self._smiles(bool(stereo))[0]
+
+    def stereo_centres(self):
+        """one code per atom by the stereo rule of DESIGN.md section 7: 0 no candidate, +1 / -1 the local parity s(a) of a marked
+        centre, 2 flat, 3 unqualified (abc_smiles_stereo_desc.stereo_out).  ValueError as smiles()."""
+        return self._smiles(True)[1]
+
+    def _smiles(self, stereo):
         n = len(self.symbols)
         for i, (s, c) in enumerate(zip(self.symbols, self.charges)):
             if s not in ATOM_SYMBOLS:
@@ -126,21 +136,47 @@ class Molecule:
             both = aromatic[u] and aromatic[v]
             return (("-" if both else ""), "=", "#", ("" if both else ":"))[cls - 1]
 
-        def token(a):
+        def hydrogens(a):
+            s, c = self.symbols[a], self.charges[a]
+            if listed[a]:
+                return 1
+            if s == "H" or abs(c) > 1:
+                return 0
+            v = sum(3 if cls == 4 else 2 * cls for _, cls in adj[a]) // 2
+            return next((t - v for t in _SMILES_VALENCES[s][c + 1] if t >= v), 0)
+
+        def token(a, mark=""):
             s, c = self.symbols[a], self.charges[a]
             sym = s.lower() if aromatic[a] else s
-            if c == 0 and not listed[a] and s in _SMILES_BARE:
+            if c == 0 and not listed[a] and s in _SMILES_BARE and not mark:
                 return sym
-            if listed[a]:
-                h = 1
-            elif s == "H" or abs(c) > 1:
-                h = 0
-            else:
-                v = sum(3 if cls == 4 else 2 * cls for _, cls in adj[a]) // 2
-                h = next((t - v for t in _SMILES_VALENCES[s][c + 1] if t >= v), 0)
-            hydrogens = "" if h == 0 else ("H" if h == 1 else "H%d" % h)
+            h = hydrogens(a)
             charge = "" if c == 0 else ("+" if c > 0 else "-") + ("" if abs(c) == 1 else "%d" % abs(c))
-            return "[" + sym + hydrogens + charge + "]"
+            return "[" + sym + mark + ("" if h == 0 else ("H" if h == 1 else "H%d" % h)) + charge + "]"
+
+        # stereo: the code of every atom (0 none, +1 / -1 the local parity, 2 flat, 3 unqualified)
+        centre = [0] * n
+        if stereo:
+            up = {}      # (end 1, end 2) of a wedge row, 0-based -> the elevation of end 2 seen from end 1
+            for (e1, e2), order in zip(self.bonds, self.orders):
+                if order >= 5:
+                    up[(e1 - 1, e2 - 1)] = 1 if order == 5 else -1
+            for a in sorted({e1 for e1, _ in up}):
+                d, h = len(adj[a]), hydrogens(a)
+                if self.symbols[a] == "H" or any(cls != 1 for _, cls in adj[a]) or (d, h) not in ((4, 0), (3, 1)):
+                    centre[a] = 3
+                    continue
+                xa, ya = self.positions[a]
+                rows = [(self.positions[j][0] - xa, self.positions[j][1] - ya, up.get((a, j), 0)) for j, _ in adj[a]]
+                in_range = all(0 <= v <= 199999 for j in [a] + [j for j, _ in adj[a]] for v in self.positions[j])
+                if not in_range or any(r[0] == 0 and r[1] == 0 for r in rows):
+                    centre[a] = 2
+                    continue
+                if d == 3:
+                    rows.append((0, 0, 0))
+                (a1, a2, a3), (b1, b2, b3), (c1, c2, c3) = ([u - v for u, v in zip(r, rows[3])] for r in rows[:3])
+                t = a1 * (b2 * c3 - b3 * c2) - a2 * (b1 * c3 - b3 * c1) + a3 * (b1 * c2 - b2 * c1)
+                centre[a] = 2 if t == 0 else (1 if t > 0 else -1)
 
         # the walk, with the tree's parent pointers as its stack: the rank, the parent and the brackets of every atom
         rank, parent, order, cursor = [-1] * n, [-1] * n, [], [0] * n
@@ -187,8 +223,16 @@ class Molecule:
                 lead = "." if p > 0 else ""
             else:
                 lead = ("(" if opens_branch[a] else "") + bond_symbol(parent[a], a, next(cls for y, cls in adj[a] if y == parent[a]))
-            out.append(lead + token(a) + "".join(digits) + ")" * closes[p])
-        return "".join(out)
+            mark = ""
+            if centre[a] in (1, -1):
+                # the neighbours as the text names them: parent, hydrogen, ring numbers as written, children in scan order; the
+                # hydrogen is the last of the local order (n stands for it)
+                named = ([parent[a]] if parent[a] >= 0 else []) + ([n] if len(adj[a]) == 3 else []) + [y for _, y, _ in ring] \
+                    + [y for y, _ in adj[a] if parent[y] == a]
+                swaps = sum(named[i] > named[j] for i in range(4) for j in range(i + 1, 4))
+                mark = "@" if centre[a] * (-1 if swaps & 1 else 1) > 0 else "@@"
+            out.append(lead + token(a, mark) + "".join(digits) + ")" * closes[p])
+        return "".join(out), centre
 
 
 # the text rule's classes: the symbols written without brackets, the ones that may be aromatic, and OUR valence

@@ -37,7 +37,7 @@ class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
                  assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
-                 score_similarity=False, molblocks=False, score_identity=False, smiles=False):
+                 score_similarity=False, molblocks=False, score_identity=False, smiles=False, smiles_stereo=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -78,6 +78,9 @@ class InferenceRunner:
         smiles (needs assemble=True): a SMILES string of every assembled molecule (ops.SmilesWriter), written in the same captured
         graph after the assembler (and after the mol block text, if both are on); smiles() returns the strings.  The text rule is
         this project's: deterministic, its graph is the assembled graph, NOT RDKit's canonical SMILES
+        smiles_stereo (needs smiles=True): the same stage writes the tetrahedral centres that the predicted wedge bonds and the atom
+        positions decide as `@` / `@@` (SmilesWriter(stereo=True)): smiles() is then `m.smiles(stereo=True)`, stereo_stats() says
+        how many wedge rows there were and how many centres were marked, flat or unqualified.  The same two launches in the same place
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
@@ -93,6 +96,8 @@ class InferenceRunner:
             if on and not assemble:
                 raise ValueError("InferenceRunner(%s=True) writes the text of the assembled molecules of the step: it needs "
                                  "assemble=True" % flag)
+        if smiles_stereo and not smiles:
+            raise ValueError("InferenceRunner(smiles_stereo=True) is a form of the SMILES stage: it needs smiles=True")
         extract = bool(extract) or bool(assemble)
         check_nms_heads(model.heads, "InferenceRunner")
         if extract and tuple(model.heads) != HEADS:
@@ -144,7 +149,7 @@ class InferenceRunner:
             if molblocks:
                 self.texter = MolBlockWriter.from_assembler(self.assembler)
             if smiles:
-                self.smiler = SmilesWriter.from_assembler(self.assembler)
+                self.smiler = SmilesWriter.from_assembler(self.assembler, stereo=bool(smiles_stereo))
         if evaluate:
             if tuple(model.heads) != HEADS:
                 raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (list(HEADS), list(model.heads)))
@@ -297,10 +302,17 @@ class InferenceRunner:
 
     def smiles(self):
         """a SMILES string of every image of the last step, written on the device: what `m.smiles()` gives for the m of
-        molecules(), None where that is None (host sync; needs smiles=True)"""
+        molecules(), None where that is None (host sync; needs smiles=True); with smiles_stereo=True it is `m.smiles(stereo=True)`"""
         smiler = self._need("smiler")
         with torch.cuda.device(self.dev):
             return smiler.smiles()
+
+    def stereo_stats(self):
+        """what became of the wedge rows of the last step (SmilesWriter.stereo_stats: marked, flat, unqualified, wedge_rows and the
+        per-image rows; host sync; needs smiles=True and smiles_stereo=True)"""
+        smiler = self._need("smiler")
+        with torch.cuda.device(self.dev):
+            return smiler.stereo_stats()
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""

@@ -544,27 +544,32 @@ class SmilesWriter(PackedText):
     `Molecule.from_device_rows(...).smiles()` for every image of a GraphAssembler's rows, read in place, packed back to back into
     one static buffer.  Two launches, static buffers, graph-capture safe; `smiles()` is the only host sync (two small D2H copies
     per batch).  The text is deterministic and its graph is the rows' graph; it is NOT RDKit's canonical SMILES (DESIGN.md
-    section 7: the rule, and what it leaves out)."""
+    section 7: the rule, and what it leaves out).  stereo=True (abc_write_smiles_stereo): the bytes of `.smiles(stereo=True)`, the
+    tetrahedral centres of the wedge rows written as `@` / `@@`; stereo_stats() and parities() say what became of every candidate."""
 
     STATUS_NAMES = ((L.TEXT_BAD_ROW, "ABC_TEXT_BAD_ROW (a vocabulary index outside 0..13, a charge outside -15..15, a bond order "
                                      "outside 1..6, a bond end outside 1..n or on one atom twice, or an atom pair listed twice)"),
                     (L.TEXT_RING_LIMIT, "ABC_TEXT_RING_LIMIT (more than 99 ring bonds are open at once)"),
                     (L.TEXT_OVERFLOW, "ABC_TEXT_OVERFLOW (the batch's text does not fit cap_text)"))
 
-    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, cap_text=None):
+    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, cap_text=None, stereo=False):
         """a contract.MoleculeRows (GraphAssembler.rows), or its four device tensors (hand-made rows); cap_atoms at most
         L.MAX_SMILES_ATOMS, cap_mol_bonds at most L.MAX_SMILES_BONDS.  cap_text: bytes of the text buffer; default
         B * abc_smiles_text_bytes, the bound of one image with every token at its widest -- 20 480 bytes per image at the
-        runner's default capacities (512 atoms, 2048 bonds); at most 2^31 - 1"""
+        runner's default capacities (512 atoms, 2048 bonds), 21 504 with stereo (abc_smiles_stereo_text_bytes); at most 2^31 - 1"""
         rows = MoleculeRows.checked("SmilesWriter", mol_counts, mol_atoms, mol_bonds, mol_implh, max_cap_atoms=L.MAX_SMILES_ATOMS,
                                     max_cap_mol_bonds=L.MAX_SMILES_BONDS, need_implh=True)
         B, cap_atoms, cap_mol_bonds = rows.B, rows.cap_atoms, rows.cap_mol_bonds
         self.lib = L.load()
         dev = rows.device
-        d = L.SmilesDesc()
+        self.stereo = bool(stereo)
+        d = L.SmilesStereoDesc() if self.stereo else L.SmilesDesc()
+        text_bytes, work_ints, self._write, self._what = (
+            (self.lib.abc_smiles_stereo_text_bytes, self.lib.abc_smiles_stereo_work_ints, self.lib.abc_write_smiles_stereo, "write_smiles_stereo")
+            if self.stereo else (self.lib.abc_smiles_text_bytes, self.lib.abc_smiles_work_ints, self.lib.abc_write_smiles, "write_smiles"))
         rows.fill(d)
         d.mol_implh = rows.tensors[3].data_ptr()
-        self.image_bytes = int(self.lib.abc_smiles_text_bytes(C.byref(d)))
+        self.image_bytes = int(text_bytes(C.byref(d)))
         cap_text = B * self.image_bytes if cap_text is None else int(cap_text)
         if not (1 <= cap_text <= 2 ** 31 - 1):
             raise ValueError("SmilesWriter: cap_text must be 1..2^31-1 bytes, got %d (B = %d images of at most %d bytes)"
@@ -572,17 +577,41 @@ class SmilesWriter(PackedText):
         self.B, self.cap_atoms, self.cap_mol_bonds, self.cap_text = B, cap_atoms, cap_mol_bonds, cap_text
         self.text = torch.zeros(cap_text, dtype=torch.uint8, device=dev)
         self.index = torch.zeros(2 * B + 1, dtype=torch.int32, device=dev)
-        self.work = torch.zeros(int(self.lib.abc_smiles_work_ints(C.byref(d))), dtype=torch.int32, device=dev)
+        self.work = torch.zeros(int(work_ints(C.byref(d))), dtype=torch.int32, device=dev)
         self.h_index = torch.zeros(2 * B + 1, dtype=torch.int32, pin_memory=True)
         d.text, d.index, d.work, d.cap_text = self.text.data_ptr(), self.index.data_ptr(), self.work.data_ptr(), cap_text
+        self.stats = self.codes = None
+        if self.stereo:
+            self.stats = torch.zeros((B, len(L.SMILES_STEREO_COLUMNS)), dtype=torch.int32, device=dev)
+            self.codes = torch.zeros((B, cap_atoms), dtype=torch.int32, device=dev)
+            d.stereo_stats, d.stereo_out = self.stats.data_ptr(), self.codes.data_ptr()
         self.d, self.keep = d, rows.tensors
 
     @classmethod
-    def from_assembler(cls, asm, cap_text=None):
-        return cls(asm.rows, cap_text=cap_text)
+    def from_assembler(cls, asm, cap_text=None, stereo=False):
+        return cls(asm.rows, cap_text=cap_text, stereo=stereo)
 
     def run(self, stream=None):
-        L.check(self.lib.abc_write_smiles(C.byref(self.d), stream_or_current(stream)), "write_smiles")
+        L.check(self._write(C.byref(self.d), stream_or_current(stream)), self._what)
+
+    def _need_stereo(self, what):
+        if not self.stereo:
+            raise L.AbcNetHipError("SmilesWriter.%s: the writer was built without stereo=True" % what)
+
+    def stereo_stats(self):
+        """stereo=True: what became of the wedge rows of the last run -- {"marked", "flat", "unqualified", "wedge_rows"} summed
+        over the batch, and "rows", the four counts of every image (zeros for an image without text).  Host sync."""
+        self._need_stereo("stereo_stats")
+        rows = self.stats.cpu().tolist()
+        out = {name: sum(r[i] for r in rows) for i, name in enumerate(L.SMILES_STEREO_COLUMNS)}
+        out["rows"] = rows
+        return out
+
+    def parities(self):
+        """stereo=True: int32 [B, cap_atoms] on the host, the code of every atom row of the last run: 0 no candidate, +1 / -1 the
+        local parity s(a) of a marked centre, L.STEREO_FLAT, L.STEREO_UNQUALIFIED; 0 past an image's atoms.  Host sync."""
+        self._need_stereo("parities")
+        return self.codes.cpu()
 
     def smiles(self):
         """per image: the SMILES as a str, or None for an image without an atom peak or without a bond peak.  Raises

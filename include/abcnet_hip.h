@@ -1066,7 +1066,7 @@ int abc_molblock_desc_size(void);
 /* A SMILES string for every assembled molecule, written on the device from the rows of abc_assemble_graphs, read in place
  * (csrc/smiles.hip; decode.Molecule.smiles() is the host form and the oracle; the rule with its examples: DESIGN.md section 7).
  * NOT the canonical SMILES RDKit prints: a deterministic, valid SMILES whose graph is the graph of the rows.  Wedge bonds are
- * single bonds and stereo is not written; x, y, hs and the bond's source are not read.  Two launches on the stream, integers only,
+ * single bonds and stereo is not written (abc_write_smiles_stereo, below, writes it); x, y, hs and the bond's source are not read.  Two launches on the stream, integers only,
  * one workgroup per image, no atomics on global memory, no allocation, no sync; deterministic.
  *   input    image b's rows, atom and bond counts clamped to their capacities: atoms (x, y, vocabulary index, charge VALUE, hs),
  *            bonds (end 1, end 2 (1-based), order 1..6, source), mol_implh k 1-based atom indices (one outside 1..n is ignored);
@@ -1126,6 +1126,60 @@ int64_t abc_smiles_work_ints(const abc_smiles_desc* d);
 int abc_write_smiles(const abc_smiles_desc* d, abc_stream_t stream);
 /* sizeof(abc_smiles_desc), for a binding's mirror struct (as abc_molblock_desc_size) */
 int abc_smiles_desc_size(void);
+
+/* The same text with tetrahedral stereo: the centres that the wedge rows (orders 5 and 6) and the positions decide are written as
+ * "@" / "@@".  Opt-in and apart: abc_write_smiles keeps its bytes.  The same two launches (the other instantiation of the same
+ * kernels), integers only, no atomics on global memory, no sync.  Everything of abc_smiles_desc holds, and the rule joins its text
+ * rule (decode.Molecule.smiles(stereo=True) is the host form):
+ *   frame       an atom row's (x, y) is (row, column); with z toward the viewer (row down, column right, z) is right-handed;
+ *   wedge       a bond row of order 5 or 6 speaks for its END 1 alone, the narrow end, as in a mol file: seen from atom a, neighbour
+ *               j has the elevation z = +1 if a row (a, j, 5) exists, -1 for (a, j, 6), 0 otherwise (also for a row (j, a, 5 | 6));
+ *   candidate   an atom that is end 1 of at least one wedge row;
+ *   qualified   a candidate whose symbol is not H, all of whose bonds have class 1, and whose degree d and hydrogen count h (the
+ *               text rule's, for a listed atom too) are d = 4, h = 0 or d = 3, h = 1; any other candidate is UNQUALIFIED: no mark;
+ *   vectors     p_j = (x_j - x_a, y_j - y_a, z_j) for every neighbour j; for d = 3 the hydrogen is a fourth neighbour at (0, 0, 0).
+ *               A qualified atom is FLAT, no mark, if its own or a neighbour's x or y is outside 0..199999 (the mol block's range;
+ *               every product below stays under 2^40), if a neighbour stands on the atom's own (x, y), or if T = 0;
+ *   parity      T = det[p1 - p4; p2 - p4; p3 - p4] in int64 for four neighbours in some order: T > 0 says that seen from n1 the
+ *               atoms n2, n3, n4 run counter-clockwise, "@"; T < 0 "@@".  The local parity s(a) is the sign of T with the
+ *               neighbours in ascending atom index and the hydrogen last;
+ *   mark        the text names a centre's neighbours as: the tree parent if any, the hydrogen if any, the ring numbers as written
+ *               on the atom (closings, then openings), the children in scan order.  "@" iff s(a) times the sign of the permutation
+ *               from the local order to that order is positive, else "@@";
+ *   token       a marked atom is always bracketed: "[" symbol mark "H"? charge "]" -- "[C@@H]", "[C@]", "[N@+]" (never aromatic:
+ *               all its bonds have class 1).  Nothing else of the text changes; a batch without a marked atom has the bytes of
+ *               abc_write_smiles;
+ *   example     atoms 1 C (20, 20), 2 N (10, 20), 3 C (25, 29), 4 O (25, 11), rows (1, 2, 5), (1, 3, 1), (1, 4, 1): d = 3, h = 1,
+ *               T = det[(-10, 0, 1); (5, 9, 0); (5, -9, 0)] = -90, the text order (H, 2, 3, 4) is an odd permutation of
+ *               (2, 3, 4, H): "[C@H](N)(C)O"; with order 6 "[C@@H](N)(C)O"; with the row (2, 1, 5) instead "C(N)(C)O";
+ *   stereo_stats  per image (marked, flat, unqualified, wedge rows -- every row of order 5 or 6); all zeros for an image that is
+ *               EMPTY or refused (BAD_ROW, RING_LIMIT).  OVERFLOW does not change it;
+ *   stereo_out  optional, per atom row: 0 no candidate, +1 / -1 s(a) of a marked atom, 2 flat, 3 unqualified; every word of the
+ *               image's cap_atoms is written by every launch (0 past the atom count and for an image without text).
+ * Not covered: double-bond marks ("/", "\"), centres with a multiple bond (sulfoxides, phosphates), three-neighbour centres without
+ * a hydrogen, RDKit's special cases for T-shaped drawings, stereo in the identity / similarity scores. */
+typedef struct abc_smiles_stereo_desc {
+    const int32_t* mol_counts;   /* the fields of abc_smiles_desc, in its order */
+    const int32_t* mol_atoms;
+    const int32_t* mol_bonds;
+    const int32_t* mol_implh;
+    int32_t B, cap_atoms, cap_mol_bonds;
+    uint8_t* text;
+    int32_t* index;
+    int32_t* work;               /* [abc_smiles_stereo_work_ints()] */
+    int64_t cap_text;
+    int32_t* stereo_stats;       /* [B][4] */
+    int32_t* stereo_out;         /* optional: [B][cap_atoms] */
+} abc_smiles_stereo_desc;
+/* as abc_smiles_text_bytes with a marked token at its widest: "[" two letters "@@" "H" a digit, a sign and two digits "]" (11)
+ * makes 14 per atom; 14 cap_atoms + 7 cap_mol_bonds */
+int64_t abc_smiles_stereo_text_bytes(const abc_smiles_stereo_desc* d);
+/* as abc_smiles_work_ints, with slices of abc_smiles_stereo_text_bytes() */
+int64_t abc_smiles_stereo_work_ints(const abc_smiles_stereo_desc* d);
+/* the guards of abc_write_smiles, and a null stereo_stats is ABC_EINVAL; nothing is launched on a refusal */
+int abc_write_smiles_stereo(const abc_smiles_stereo_desc* d, abc_stream_t stream);
+/* sizeof(abc_smiles_stereo_desc), for a binding's mirror struct */
+int abc_smiles_stereo_desc_size(void);
 
 /* ---- unet2: CBAM attention + residual (unet2.py:6-74).  See csrc/cbam.hip for the pass structure. ---- */
 typedef struct abc_cbam_channel_desc { /* ChannelAttentionModule (unet2.py:6-22), one MLP evaluation per image */

@@ -29,6 +29,10 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            Molecule.smiles() of every image on the host against smiles() (as `text`), abc_write_smiles alone beside
            abc_write_molblocks (two launches each, as `launch`), the bytes smiles() copies, and step() with assemble=True against the
            same with molblocks=True and with smiles=True (as `text`'s step)
+           --stereo: a fourth runner with smiles_stereo=True beside the plain one -- abc_write_smiles_stereo alone beside
+           abc_write_smiles, its step against the plain stage's in the same alternated blocks, smiles() against
+           Molecule.smiles(stereo=True), and what became of the fixture's wedge rows (stereo_stats: wedge rows, marked, flat,
+           unqualified)
 
   --omega-rule {raw,peaks}: the extractor's candidate rule of every runner built here (InferenceRunner(omega_rule=...): "raw" is
            img2smiles2.py:139, "peaks" img2smiles.py:139 / img2smiles3.py:140); `graphs` and `score` then also report the candidates
@@ -36,7 +40,7 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo]
 """
 import argparse
 import json
@@ -238,10 +242,13 @@ def part_text(m, x, steps, warmup, reps=30, iters=200):
     emit({"part": "text", "molblocks_minus_assemble_ms": round(med["assemble+molblocks"] - med["assemble=True"], 4)})
 
 
-def part_smiles(m, x, steps, warmup, reps=30, iters=200):
+def part_smiles(m, x, steps, warmup, reps=30, iters=200, stereo=False):
     rs = {}
-    for name, kw in (("assemble=True", dict(assemble=True)), ("assemble+molblocks", dict(assemble=True, molblocks=True)),
-                     ("assemble+smiles", dict(assemble=True, smiles=True))):
+    forms = [("assemble=True", dict(assemble=True)), ("assemble+molblocks", dict(assemble=True, molblocks=True)),
+             ("assemble+smiles", dict(assemble=True, smiles=True))]
+    if stereo:
+        forms.append(("assemble+smiles+stereo", dict(assemble=True, smiles=True, smiles_stereo=True)))
+    for name, kw in forms:
         r = InferenceRunner(m, B, S, S, use_graph=True, omega_rule=RULE, **kw)
         r.load_batch(x.to("cuda"))
         for _ in range(2):
@@ -279,9 +286,43 @@ def part_smiles(m, x, steps, warmup, reps=30, iters=200):
     emit({"part": "smiles", "what": "launch", "batch": B, "us_per_call": [round(a, 2) for a, _ in us],
           "molblocks_us_per_call": [round(b, 2) for _, b in us], "assemble_us_per_launch": round(launch_us(r.assembler.run, iters), 2),
           "method": "device events around %d back-to-back calls of two launches each (launch gaps included)" % iters})
+    if stereo:
+        part_smiles_stereo(rs["assemble+smiles+stereo"], r, reps, iters)
     med = step_blocks(rs, steps, warmup, "smiles")
-    emit({"part": "smiles", "smiles_minus_assemble_ms": round(med["assemble+smiles"] - med["assemble=True"], 4),
-          "molblocks_minus_assemble_ms": round(med["assemble+molblocks"] - med["assemble=True"], 4)})
+    out = {"part": "smiles", "smiles_minus_assemble_ms": round(med["assemble+smiles"] - med["assemble=True"], 4),
+           "molblocks_minus_assemble_ms": round(med["assemble+molblocks"] - med["assemble=True"], 4)}
+    if stereo:
+        out["stereo_minus_smiles_ms"] = round(med["assemble+smiles+stereo"] - med["assemble+smiles"], 4)
+    emit(out)
+
+
+def part_smiles_stereo(r, plain, reps, iters):
+    """the stereo form beside the plain one: the fixture's wedge rows and what became of them, smiles() against the host form,
+    the two launches of each alternated"""
+    status = r.smiler.status()
+    refused = sum(bool(s & ~3) for s in status)
+    st = r.stereo_stats()
+    mols = r.molecules()
+    out = {"part": "smiles", "what": "stereo fixture", "batch": B, "refused_images": refused,
+           "images_with_a_wedge_row": sum(row[3] > 0 for row in st["rows"]), "images_with_a_mark": sum(row[0] > 0 for row in st["rows"]),
+           "wedge_rows_per_image_max": max(row[3] for row in st["rows"])}
+    out.update({k: st[k] for k in ("wedge_rows", "marked", "flat", "unqualified")})
+    if not refused:
+        def host():
+            return [mol.smiles(stereo=True) if mol is not None else None for mol in mols]
+        want, got = host(), r.smiles()
+        wall = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r.smiles()
+            wall.append((time.perf_counter() - t0) * 1000)
+        out.update({"equal": got == want, "texts_that_differ_from_plain": sum(a != b for a, b in zip(got, plain.smiles())),
+                    "smiles_ms": round(statistics.median(wall), 4), "text_bytes": r.smiler.index.cpu().tolist()[B]})
+    emit(out)
+    us = [(launch_us(r.smiler.run, iters), launch_us(plain.smiler.run, iters)) for _ in range(3)]
+    emit({"part": "smiles", "what": "stereo launch", "batch": B, "stereo_us_per_call": [round(a, 2) for a, _ in us],
+          "plain_us_per_call": [round(b, 2) for _, b in us],
+          "method": "device events around %d back-to-back calls of two launches each (launch gaps included), alternated" % iters})
 
 
 def annotated_graph(atoms_s, bonds_s):
@@ -417,6 +458,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--parts", default="step,launch,host,graphs")
     ap.add_argument("--omega-rule", choices=("raw", "peaks"), default="raw")
+    ap.add_argument("--stereo", action="store_true", help="the smiles part: the stereo form beside the plain one")
     a = ap.parse_args()
     global RULE
     RULE = a.omega_rule
@@ -449,7 +491,7 @@ def main():
     if "text" in parts:
         part_text(m, x, a.steps, a.warmup)
     if "smiles" in parts:
-        part_smiles(m, x, a.steps, a.warmup)
+        part_smiles(m, x, a.steps, a.warmup, stereo=a.stereo)
 
 
 if __name__ == "__main__":
