@@ -156,6 +156,121 @@ __global__ __launch_bounds__(256) void act_bwd_plain_kernel(const abc_act_bwd_de
     }
 }
 
+// eight per-channel coefficients of a thread's channel group (c a multiple of 8): two 16-byte loads where the array allows it
+// (uniform across the launch), eight 4-byte loads otherwise -- in pool_act these loads outnumbered the tensor's own six to one
+__device__ inline void ldc8(const float* p, float* v) {
+    if ((((uintptr_t)p) & 15) == 0) {
+        const f32x4 lo = *(const f32x4*)p, hi = *(const f32x4*)(p + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = p[j];
+    }
+}
+
+// One 2x2 window of the pooled form in bf16: route the pooled gradient to the first maximum (torch max_pool2d), add the
+// full-resolution source, apply act' and add the four pixels to the thread's sums in the order q = 0..3, channel by channel (every
+// channel's sums are a chain of their own, so the order of the channels is free).  The 16-byte vectors stay as loaded -- 4 registers,
+// not 8 -- and are converted element by element where they are used.
+// The roundings are spelled out, with contraction off, as act_bwd_kernel<bf16> is compiled: there the compiler contracts
+// sum(g * xhat) into one fused multiply-add per pixel, adds g itself for the first three pixels of a window and folds the fourth
+// pixel's product up * act' into the sum of g.  The partial rows feed a fixed-order reduction and are held to the bit
+// (tests/test_gpu_hbm_passes.py), so this form states that arithmetic instead of leaving it to the optimiser.
+template <bool SAME>
+__device__ inline void pool_window_bwd(const bf16x8 (&x)[4], const bf16x8& dpool, const bf16x8 (&da)[4], const float* sc, const float* sh,
+                                       const float* sl, const float* mu, const float* is, float* a1, float* a2, bf16x8 (&out)[4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float xv[4], yv[4];
+        float best = 0.f;
+        int arg = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            xv[q] = (float)x[q][j];
+            const float y = __builtin_fmaf(xv[q], sc[j], sh[j]);
+            yv[q] = y;
+            const float av = fmaxf(y, sl[j] * y);
+            if (q == 0 || av > best) { best = av; arg = q; }  // first maximum wins (torch max_pool2d)
+        }
+        const float dpv = (float)dpool[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float up = (arg == q) ? dpv : 0.f;
+            if (SAME) up = (float)da[q][j] + up;
+            const float dact = yv[q] > 0.f ? 1.f : sl[j];
+            const float gg = up * dact;
+            out[q][j] = (bf16)gg;
+            a1[j] = q < 3 ? a1[j] + gg : __builtin_fmaf(up, dact, a1[j]);
+            a2[j] = __builtin_fmaf(gg, (xv[q] - mu[j]) * is[j], a2[j]);
+        }
+        // (the channel's sums are complete HERE: left alone, the scheduler defers the additions of all eight channels to the end
+        //  and keeps their operands live -- 250 registers, one wave per SIMD)
+        asm volatile("" : "+v"(a1[j]), "+v"(a2[j]));
+    }
+}
+
+// The pooled form's common case in bf16 -- even H and W, no dropout (the pooled form has none), element offsets below 2^31:
+// all 5 or 9 16-byte loads of a window issued before the first use (act_bwd_kernel waits for each of the second source's four loads
+// on its own), WAVES waves per SIMD instead of two, one multiply-high for the only division left (pooled pixel -> pooled row: with
+// even H the window's first pixel is 4 * row * Ww + 2 * wx, no image index needed; `magic` = ceil(2^32 / Ww) is exact while
+// pixels * Ww < 2^32, checked on the host).  Items, their order per thread, the block partition and the block reduction are
+// act_bwd_kernel's: the partial rows and g are bit-identical to it.
+template <bool SAME, int WAVES>
+__global__ __launch_bounds__(256, WAVES) void act_bwd_pool_kernel(const abc_act_bwd_desc d, const unsigned magic) {
+    constexpr int N = 8;
+    __shared__ float red[256][2 * N + 1];
+    const int ncv = d.C / N;
+    const unsigned Ww = (unsigned)d.W / 2u;
+    const unsigned nitems = (unsigned)d.B * ((unsigned)d.H / 2u) * Ww * (unsigned)ncv;
+    const unsigned stride = gridDim.x * 256u;
+    const int tid = threadIdx.x;
+    const int cv = (int)((blockIdx.x * 256 + tid) % ncv);
+    const int c = cv * N;
+    const int lg = 31 - __builtin_clz((unsigned)ncv);
+    float sc[N], sh[N], sl[N], mu[N], is[N];
+    // (4-byte loads: as 16-byte loads through ldc8 the <false, 4> instantiation no longer fits 128 registers and spills)
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        sc[j] = d.scale[c + j]; sh[j] = d.shift[c + j]; sl[j] = d.slope[c + j]; mu[j] = d.mean[c + j]; is[j] = d.invstd[c + j];
+    }
+    float a1[N], a2[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) { a1[j] = 0.f; a2[j] = 0.f; }
+    const bf16* yr = (const bf16*)d.y_raw + d.cy_off + c;
+    const bf16* ds = SAME ? (const bf16*)d.dA_same + d.csame_off + c : nullptr;
+    const bf16* dp = (const bf16*)d.dA_pool + d.cpool_off + c;
+    bf16* g = (bf16*)d.g + c;
+    const unsigned W = (unsigned)d.W;
+    for (unsigned it = blockIdx.x * 256u + tid; it < nitems; it += stride) {
+        const unsigned pix = it >> lg;
+        const unsigned row = __umulhi(pix, magic);      // = pix / Ww = b * (H / 2) + wy
+        const unsigned p0 = 4u * row * Ww + 2u * (pix - row * Ww);      // full-resolution index of the window's first pixel
+        bf16x8 x[4], dpool, da[4], out[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x[q] = *(const bf16x8*)(yr + (p0 + (q >> 1) * W + (q & 1)) * (unsigned)d.ld_y);
+        dpool = *(const bf16x8*)(dp + pix * (unsigned)d.ld_pool);
+        if (SAME) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) da[q] = *(const bf16x8*)(ds + (p0 + (q >> 1) * W + (q & 1)) * (unsigned)d.ld_same);
+        }
+        pool_window_bwd<SAME>(x, dpool, da, sc, sh, sl, mu, is, a1, a2, out);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *(bf16x8*)(g + (p0 + (q >> 1) * W + (q & 1)) * (unsigned)d.ld_g) = out[q];
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) { red[tid][j] = a1[j]; red[tid][N + j] = a2[j]; }
+    __syncthreads();
+    for (int cc = tid; cc < d.C; cc += 256) {
+        const int v = cc / N, j = cc % N;
+        float s1 = 0.f, s2 = 0.f;
+        for (int t = v; t < 256; t += ncv) { s1 += red[t][j]; s2 += red[t][N + j]; }
+        d.partial[((size_t)blockIdx.x * 2 + 0) * d.C + cc] = s1;
+        d.partial[((size_t)blockIdx.x * 2 + 1) * d.C + cc] = s2;
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void act_bwd_kernel(const abc_act_bwd_desc d) {
     constexpr int N = VecOf<T>::N;
@@ -563,6 +678,17 @@ extern "C" int abc_act_bwd_blocks(const abc_act_bwd_desc* d) {
     return ew_blocks(n);
 }
 
+// act_bwd_pool_kernel's preconditions: whole windows only, and every element offset and the multiply-high division in 32 bits
+static bool act_bwd_pool_fast(const abc_act_bwd_desc* d) {
+    // (bf16 only: the kernel restates the roundings of act_bwd_kernel<bf16>; the f32 instantiation contracts differently)
+    if (d->dtype != ABC_BF16 || d->dA_pool == nullptr || d->drop_p > 0.f || ((d->H | d->W) & 1) || d->W < 4) return false;
+    const int64_t npix = (int64_t)d->B * d->H * d->W, npool = npix / 4;
+    int ld = d->ld_y > d->ld_g ? d->ld_y : d->ld_g;
+    if (d->dA_same != nullptr && d->ld_same > ld) ld = d->ld_same;
+    if (ld < 1 || d->ld_pool < 1 || npix * ld >= (int64_t(1) << 31) || npool * d->ld_pool >= (int64_t(1) << 31)) return false;
+    return npool * (d->W / 2) < (int64_t(1) << 32);
+}
+
 extern "C" int abc_act_bwd(const abc_act_bwd_desc* d, abc_stream_t stream) {
     int rc = act_bwd_check(d);
     if (rc) return rc;
@@ -570,6 +696,16 @@ extern "C" int abc_act_bwd(const abc_act_bwd_desc* d, abc_stream_t stream) {
     if (d->dA_pool == nullptr && d->drop_p <= 0.f) {
         if (d->dtype == ABC_BF16) hipLaunchKernelGGL(act_bwd_plain_kernel<bf16>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *d);
         else hipLaunchKernelGGL(act_bwd_plain_kernel<float>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *d);
+        return abc_check_launch("act_bwd");
+    }
+    if (act_bwd_pool_fast(d)) {
+        const unsigned magic = (unsigned)(((uint64_t(1) << 32) + (uint64_t)(d->W / 2) - 1) / (uint64_t)(d->W / 2));
+        const bool same = d->dA_same != nullptr;
+        hipStream_t st = (hipStream_t)stream;
+        // (one window in flight at four / three waves per SIMD: two windows in flight took 206 registers, two waves, and ran
+        //  43.2 against 32.4 us on the 384 x 384 level at b16; profiles/r20_hbm_passes.md)
+        if (same) hipLaunchKernelGGL((act_bwd_pool_kernel<true, 3>), dim3(nb), dim3(256), 0, st, *d, magic);
+        else hipLaunchKernelGGL((act_bwd_pool_kernel<false, 4>), dim3(nb), dim3(256), 0, st, *d, magic);
         return abc_check_launch("act_bwd");
     }
     if (d->dtype == ABC_BF16) hipLaunchKernelGGL(act_bwd_kernel<bf16>, dim3(nb), dim3(256), 0, (hipStream_t)stream, *d);
@@ -640,17 +776,30 @@ __global__ __launch_bounds__(256) void pool_act_kernel(const InT* x, const float
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nseg) return;
     const int segs = C / 8;
-    const int sg = (int)(i % segs);
-    int64_t pix = i / segs;
     const int Wo = Wx / 2, Ho = Hx / 2;
-    const int xo = (int)(pix % Wo); pix /= Wo;
-    const int yo = (int)(pix % Ho);
-    const int b = (int)(pix / Ho);
+    int sg, xo, yo, b;
+    if (nseg < (int64_t(1) << 31)) {      // (every real tensor: 32-bit divisions, a fraction of the 64-bit ones' instructions)
+        unsigned u = (unsigned)i;
+        sg = (int)(u % (unsigned)segs); u /= (unsigned)segs;
+        xo = (int)(u % (unsigned)Wo); u /= (unsigned)Wo;
+        yo = (int)(u % (unsigned)Ho);
+        b = (int)(u / (unsigned)Ho);
+    } else {
+        sg = (int)(i % segs);
+        int64_t pix = i / segs;
+        xo = (int)(pix % Wo); pix /= Wo;
+        yo = (int)(pix % Ho);
+        b = (int)(pix / Ho);
+    }
     const int c = c_off + sg * 8;
     float a[8], s_[8], t_[8];
     const bool tr = sc != nullptr;
+    if (tr) {
+        ldc8(sc + c, a); ldc8(sh + c, s_); ldc8(sl + c, t_);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { a[j] = tr ? sc[c + j] : 1.f; s_[j] = tr ? sh[c + j] : 0.f; t_[j] = tr ? sl[c + j] : 1.f; }
+        for (int j = 0; j < 8; ++j) { a[j] = 1.f; s_[j] = 0.f; t_[j] = 1.f; }
+    }
     float m[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {

@@ -121,38 +121,83 @@ __device__ inline void pack_one(const PackItem& it, unsigned r) {
     if (it.dtype == ABC_BF16) ((bf16*)d.dst)[o] = (bf16)v; else if (it.dtype == ABC_FP8) ((f8*)d.dst)[o] = f8(v); else ((float*)d.dst)[o] = v;
 }
 
-// A block owns 2048 consecutive destination elements of the concatenated items.  The item lookup (binary search over
-// ~100 entries) is done once per block by thread 0; blocks inside one item -- nearly all -- then run with the item
-// in scalar registers and 32-bit index arithmetic; the rare block that straddles items searches per element.
-constexpr int PACK_CHUNK = 2048;
-__device__ inline int pack_find(const PackItem* items, int nitems, int64_t i) {
-    int lo = 0, hi = nitems - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (items[mid].first <= i) lo = mid; else hi = mid - 1;
+// Eight consecutive destination elements r .. r + 7 (r a multiple of 8) of a bf16 item: eight consecutive reduction channels of one
+// (tap, chunk, row), contiguous in both layouts -> the index is taken apart once for the eight (the chunk width is a power of two),
+// the eight gathers are issued together and the store is 16 bytes.  Per element the same loads, scale and rounding as pack_one.
+__device__ inline void pack_eight_bf16(const PackItem& it, unsigned r) {
+    const abc_pack_desc& d = it.d;
+    const unsigned CK = it.CK, ntaps = it.ntaps, nchunks = it.nchunks, rows = d.rows_pad;
+    const unsigned lgck = 31 - __builtin_clz(CK);
+    const unsigned k0 = r & (CK - 1); r >>= lgck;
+    const unsigned n = r % rows; r /= rows;
+    const unsigned c = r % nchunks;
+    const unsigned t = r / nchunks;
+    const unsigned rc0 = c * CK + k0;
+    unsigned base, step, rowlim, redlim;
+    if (d.mode == 0) {
+        base = (n * d.Cin + rc0) * ntaps + t; step = ntaps; rowlim = d.Cout; redlim = d.Cin;
+    } else if (d.mode == 1) {
+        base = (rc0 * d.Cin + n) * ntaps + t; step = d.Cin * ntaps; rowlim = d.Cin; redlim = d.Cout;
+    } else if (d.mode == 2) {
+        const unsigned nx = d.px ? 2 : 1;
+        const unsigned iy = t / nx, ix = t % nx;
+        const unsigned ky = d.py ? (iy == 0 ? 0 : 2) : 1;
+        const unsigned kx = d.px ? (ix == 0 ? 0 : 2) : 1;
+        base = ((rc0 * d.Cout + n) * 3 + ky) * 3 + kx; step = d.Cout * 9; rowlim = d.Cout; redlim = d.Cin;
+    } else {
+        base = (n * d.Cout + rc0) * 9 + t; step = 9; rowlim = d.Cin; redlim = d.Cout;
     }
-    return lo;
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (n < rowlim && rc0 + i < redlim) ? d.w[base + i * step] : 0.f;
+    if (d.row_scale != nullptr && (d.mode == 0 || d.mode == 2) && n < (unsigned)d.Cout) {
+        const float rs = d.row_scale[n];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] *= rs;
+    }
+    const unsigned nch_total = (d.red_total + CK - 1) >> lgck, ch_off = (unsigned)d.red_off >> lgck;
+    const unsigned rtot = d.rows_total > 0 ? (unsigned)d.rows_total : rows;
+    const size_t o = abc_pack_offset((size_t)t * nch_total + ch_off + c, (int)rtot, (int)((unsigned)d.rows_off + n), (int)CK, (int)k0, d.layout);
+    bf16x8 ov;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ov[i] = (bf16)v[i];
+    *(bf16x8*)((bf16*)d.dst + o) = ov;
 }
+
+// A block owns 2048 consecutive destination elements of the concatenated items.  The item lookup is done once per block;
+// blocks inside one item -- nearly all -- then run with the item in scalar registers and 32-bit index arithmetic; the rare
+// block that straddles items walks them in turn.
+constexpr int PACK_CHUNK = 2048;
 __global__ __launch_bounds__(256) void pack_batch_kernel(const PackItem* items, int nitems, int64_t total) {
     __shared__ int s_lo, s_hi;
     const int64_t i0 = (int64_t)blockIdx.x * PACK_CHUNK;
     const int64_t i1 = (i0 + PACK_CHUNK < total) ? i0 + PACK_CHUNK : total;
-    if (threadIdx.x == 0) { s_lo = pack_find(items, nitems, i0); s_hi = pack_find(items, nitems, i1 - 1); }
+    // the items that hold the block's first and last element: every thread looks at its own entries of the table at once -- one trip
+    // to memory, where a binary search by one thread made fourteen dependent ones before any of the 256 threads could start.
+    // (An item that takes no range -- pack_tiles_kernel's -- holds no element; exactly one item holds any element below `total`.)
+    for (int j = threadIdx.x; j < nitems; j += 256) {
+        const int64_t f = items[j].first, e = j + 1 < nitems ? items[j + 1].first : total;
+        if (f <= i0 && i0 < e) s_lo = j;
+        if (f < i1 && i1 <= e) s_hi = j;
+    }
     __syncthreads();
     // (made provably wave-uniform, and the item copied BY VALUE: since the e4m3 packing the kernel contains a one-byte store, which
     //  may alias anything -- through a reference the item's fields were re-read with vector loads after every store, and the
     //  step's packing went 75 -> 139 us)
     const int lo = __builtin_amdgcn_readfirstlane(s_lo), hi = __builtin_amdgcn_readfirstlane(s_hi);
-    if (lo == hi) {
-        const PackItem it = items[lo];
-        if (it.ntiles > 0) return;      // (pack_tiles_kernel's)
-        const unsigned base = (unsigned)(i0 - it.first);
-        for (unsigned e = threadIdx.x; e < (unsigned)(i1 - i0); e += 256) pack_one(it, base + e);
-    } else {
-        for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-            const int j = pack_find(items, nitems, i);
-            if (items[j].ntiles > 0) continue;
-            pack_one(items[j], (unsigned)(i - items[j].first));
+    // every item the block touches, over the block's share of it (nearly always one item and the whole block; a block that straddles
+    // items walks them instead of searching the table per element: those few blocks were the launch's critical path)
+    for (int j = lo; j <= hi; ++j) {
+        const PackItem it = items[j];
+        const int64_t end = j + 1 < nitems ? items[j + 1].first : total;
+        const int64_t a = it.first > i0 ? it.first : i0, b = end < i1 ? end : i1;
+        if (it.ntiles > 0 || a >= b) continue;      // (pack_tiles_kernel's: no range here)
+        const unsigned base = (unsigned)(a - it.first), cnt = (unsigned)(b - a);
+        if (it.dtype == ABC_BF16 && ((base | cnt | (unsigned)it.CK) & 7u) == 0 && (((uintptr_t)it.d.dst) & 15) == 0) {
+            // (a thread owns eight consecutive elements: PACK_CHUNK = 256 threads x 8)
+            for (unsigned e = threadIdx.x * 8u; e < cnt; e += 2048u) pack_eight_bf16(it, base + e);
+        } else {
+            for (unsigned e = threadIdx.x; e < cnt; e += 256) pack_one(it, base + e);
         }
     }
 }
