@@ -219,6 +219,13 @@ class GraphIdentityDesc(C.Structure):
                 ("max_tries", i32), ("max_rounds", i32), ("rows", vp), ("totals", vp), ("map_out", vp)]
 
 
+class CanonDesc(C.Structure):
+    _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp), ("rec_atoms", vp), ("rec_bonds", vp),
+                ("rec_counts", vp), ("B", i32), ("cap_atoms", i32), ("cap_mol_bonds", i32), ("max_atoms", i32), ("max_bonds", i32),
+                ("max_tries", i32), ("max_rounds", i32), ("order", vp), ("stats", vp), ("key", vp), ("cert_out", vp), ("out_counts", vp),
+                ("out_atoms", vp), ("out_bonds", vp), ("out_implh", vp)]
+
+
 class MolBlockDesc(C.Structure):
     _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp), ("B", i32), ("cap_atoms", i32),
                 ("cap_mol_bonds", i32), ("text", vp), ("index", vp), ("work", vp), ("cap_text", i64)]
@@ -261,6 +268,10 @@ GRAPH_SIM_IDS = 2048    # ABC_SIM_IDS: ids_out is uint64 [B][2][GRAPH_SIM_IDS]
 GRAPH_IDENT_COLUMNS = ("counted", "none", "truncated", "size_equal", "same", "different", "undecided", "levels", "tries",
                        "backtracks", "rounds")
 IDENT_DEFAULT_TRIES, IDENT_DEFAULT_ROUNDS = 4096, 16384     # ABC_IDENT_DEFAULT_TRIES, ABC_IDENT_DEFAULT_ROUNDS
+# the ABC_CANON_* columns of abc_canon_desc.stats; the bits of its status column; the defaults of its budgets
+CANON_COLUMNS = ("status", "leaves", "tries", "rounds", "levels_max", "pruned_trace", "pruned_orbit", "automorphisms", "improved")
+CANON_EMPTY, CANON_TRUNCATED, CANON_UNDECIDED, CANON_COLLISION = 1, 2, 4, 8      # abc_canon_status
+CANON_DEFAULT_TRIES, CANON_DEFAULT_ROUNDS, CANON_ORBIT_LEVELS = 4096, 16384, 8     # ABC_CANON_DEFAULT_TRIES, _ROUNDS, ABC_CANON_ORBIT_LEVELS
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
 SCAN_NPARAM = 2     # abc_scan_param: src_h, src_w
@@ -299,7 +310,7 @@ SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_scor
 # (that list is pinned, name by name, by tests/test_decoder_contract_host.py) the self-sized descriptors since: checked the same way
 SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "abc_graph_identity_desc_size"),
                     (ScanCleanDesc, "abc_scan_clean_desc_size"), (SmilesDesc, "abc_smiles_desc_size"),
-                    (SmilesStereoDesc, "abc_smiles_stereo_desc_size")]
+                    (SmilesStereoDesc, "abc_smiles_stereo_desc_size"), (CanonDesc, "abc_canon_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -388,6 +399,8 @@ SYMBOLS = {
     "abc_graph_similarity_desc_size": (C.c_int, []),
     "abc_graph_identity_update": (C.c_int, [P(GraphIdentityDesc), vp]),
     "abc_graph_identity_desc_size": (C.c_int, []),
+    "abc_canonical_order": (C.c_int, [P(CanonDesc), vp]),
+    "abc_canon_desc_size": (C.c_int, []),
     "abc_molblock_text_bytes": (i64, [P(MolBlockDesc)]),
     "abc_write_molblocks": (C.c_int, [P(MolBlockDesc), vp]),
     "abc_molblock_desc_size": (C.c_int, []),

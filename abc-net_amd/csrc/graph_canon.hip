@@ -1,0 +1,558 @@
+// A canonical atom order per image: the least leaf of an individualise-and-refine search over EVERY branch (graph_ident.hip walks one
+// path of one side and matches the other against it; this visits the whole tree of one side and keeps the least leaf).  With it the
+// text rules of smiles.hip and molblock.hip -- pure functions of atom order, graph and implicit-H list -- write equal strings if and
+// only if the graphs are equal.  The contract is in include/abcnet_hip.h (abc_canon_desc) and DESIGN.md section 7, its host form
+// decode.canonical_labelling, its oracle tests/graphcanon_oracle.py.
+//
+// One workgroup per image; integers only (uint64, wrapping).  The graph is ONE side of the identity's, built the same way (mol_rows.hpp,
+// graph_ids.hpp), id_0, the round, the class count and indiv are graph_refine.hpp's.
+//
+//   (a) a node is the sequence choice[0 .. level); REFINE runs the level's rounds (r counts on) until one no longer raises the class
+//       count, records the trace (rounds, classes, sum of mix(id)) and compares it with the best leaf's while the path has equalled it:
+//       greater drops the branch, less makes the path strictly better (less_from)
+//   (b) a discrete colouring is a leaf: rank = the number of smaller ids, h = the hash of the relabelled graph.  The first leaf, a leaf
+//       of a strictly better path and a leaf with a smaller h become the best (ids, ranks, traces, choices kept in LDS).  An equal key:
+//       atoms are mapped onto the best's by equal id through the class table and the map is VERIFIED (class, charge, tag, the multiset
+//       of mapped rows by counting) -- an automorphism, merged into the orbit tables of the levels whose prefix it fixes, and the search
+//       returns to the level where the path left the best's; not verified: colliding sums, the search stops (COLLISION)
+//   (c) CHILD takes the next atom of the node's cell (the non-singleton class of the least id value) at or past nxt[level] that is the
+//       least of its orbit (levels <= ABC_CANON_ORBIT_LEVELS; the tables are kept flat, the root is the least atom) and individualises it
+//   (d) BACK goes to the nearest level at or above its target that still has an atom of its cell to try (nxt <= cell_max) and rebuilds
+//       its ids by replaying the recorded rounds and the choices from id_0 (no id snapshots)
+//   (e) max_rounds is checked before every round (replays included), max_tries before every individualisation: UNDECIDED, the order
+//       of the best leaf so far, or the identity order.  Every loop is bounded by n, a budget or a capacity
+//   (f) every branch depends on values all threads hold alike (reductions read from LDS after a barrier, or descriptor fields)
+//
+// Bond rows are never held in LDS (row `tid` stays in registers); the sorts of the certificate and of the canonical rows count, for
+// every row, the rows before it (quadratic in the rows of ONE image, no scratch).  Every index read from a row is range-checked before
+// it addresses anything: hand-made rows may hold any int32.
+#include "common.hpp"
+#include "../../include/abcnet_hip.h"
+#include "capi_util.hpp"
+#include "block_scan.hpp"
+#include "mol_rows.hpp"
+#include "graph_ids.hpp"
+#include "graph_refine.hpp"
+
+namespace {
+
+constexpr int GT = REFINE_GT;
+constexpr int MAX_ATOMS = ABC_MAX_SIM_ATOMS;
+constexpr int MAX_ROW_BONDS = 4096;  // cap_mol_bonds when the canonical rows are requested
+constexpr int NCOL = ABC_CANON_NCOL;
+constexpr int NW = REFINE_NW;
+constexpr int SLOTS = 2 * MAX_ATOMS;
+constexpr int ORBITS = ABC_CANON_ORBIT_LEVELS + 1;      // the levels 0 .. ABC_CANON_ORBIT_LEVELS have an orbit table
+constexpr int NONE = 1 << 30;        // less_from: the path has equalled the best so far
+constexpr u64 TAG_K = 0xD6E8FEB86659FD93ull, BOND_K = 0xC2B2AE3D27D4EB4Full;
+static_assert(MAX_ATOMS == 2 * GT, "two atoms per thread: the record scan");
+typedef unsigned short u16;
+
+// 71 KB of LDS: the ids (current, best, id_0), the round's sums, the class table with the atom of every slot, the traces of the current
+// path and of the best leaf, the stack, 9 orbit tables
+__global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d) {
+    __shared__ u64 cur[MAX_ATOMS], acc[MAX_ATOMS], init[MAX_ATOMS], best_ids[MAX_ATOMS];
+    __shared__ u64 table[SLOTS];
+    __shared__ u64 cur_sum[MAX_ATOMS], best_sum[MAX_ATOMS], cell[MAX_ATOMS];       // per level: the trace's sum; the id of the cell
+    __shared__ u16 cur_k[MAX_ATOMS], cur_c[MAX_ATOMS], best_k[MAX_ATOMS], best_c[MAX_ATOMS];      // per level: rounds, classes
+    __shared__ u16 choice[MAX_ATOMS], best_choice[MAX_ATOMS], nxt[MAX_ATOMS], cell_max[MAX_ATOMS];    // the stack
+    __shared__ u16 tidx[SLOTS];          // the best leaf's atom of every table slot
+    __shared__ int remap[MAX_ATOMS];     // record atom -> its number in T, -1 outside T
+    __shared__ u16 orig[MAX_ATOMS];      // atom of the graph -> its row
+    __shared__ u16 rk[MAX_ATOMS], brank[MAX_ATOMS], gam[MAX_ATOMS];      // ranks of the leaf, of the best leaf; the map onto the best
+    __shared__ unsigned char tag[MAX_ATOMS];
+    __shared__ int orbit[ORBITS][MAX_ATOMS];
+    __shared__ unsigned wt[NW + 1];
+    __shared__ int wi[NW];
+    __shared__ u64 wu[NW];
+    __shared__ int cnt[1], zero_at;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const bool mol = d.mol_counts != nullptr;
+    const int cap = mol ? d.cap_atoms : d.max_atoms, cap_bonds = mol ? d.cap_mol_bonds : d.max_bonds;
+    int* const order = d.order + (size_t)b * cap;
+    int* const cert = d.cert_out != nullptr ? d.cert_out + (size_t)b * (2 + cap + 3 * (size_t)cap_bonds) : nullptr;
+    const bool want_rows = mol && d.out_counts != nullptr;
+    const int max_tries = d.max_tries > 0 ? d.max_tries : ABC_CANON_DEFAULT_TRIES;
+    const int max_rounds = d.max_rounds > 0 ? d.max_rounds : ABC_CANON_DEFAULT_ROUNDS;
+
+    // ---- the image: counts clamped to their capacities, no rows when EMPTY
+    int status = 0, na = 0, nrows = 0, nt = 0, nlisted = 0;      // na: molecule atoms; nt: record atoms; nrows: bond rows of the side
+    const int *pa = nullptr, *pb = nullptr, *ph = nullptr, *ra = nullptr, *rb = nullptr;
+    if (mol) {
+        const int* mc = d.mol_counts + (size_t)b * 4;
+        status = mc[3] & (ABC_MOL_EMPTY | ABC_MOL_TRUNCATED);
+        const bool empty = (status & ABC_MOL_EMPTY) != 0;
+        na = empty ? 0 : clampi(mc[0], 0, d.cap_atoms), nrows = empty ? 0 : clampi(mc[1], 0, d.cap_mol_bonds);
+        nlisted = empty || d.mol_implh == nullptr ? 0 : clampi(mc[2], 0, d.cap_atoms);
+        pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
+        pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
+        ph = d.mol_implh != nullptr ? d.mol_implh + (size_t)b * d.cap_atoms : nullptr;
+    } else {
+        nt = clampi(d.rec_counts[b], 0, d.max_atoms), nrows = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
+        ra = d.rec_atoms + (size_t)b * d.max_atoms * REC_ATOM_W;
+        rb = d.rec_bonds + (size_t)b * d.max_bonds * REC_BOND_W;
+    }
+    const bool empty = (status & ABC_CANON_EMPTY) != 0;
+    static_assert((int)ABC_CANON_EMPTY == (int)ABC_MOL_EMPTY && (int)ABC_CANON_TRUNCATED == (int)ABC_MOL_TRUNCATED, "the two bits are copied");
+
+    // row `tid`, kept through every round (a record row's ends become numbers in T below)
+    int pi = 0, pj = 0;
+    const bool pv = tid < nrows && (mol ? mol_ends(pb, tid, na, pi, pj) : rec_ends(rb, tid, nt, pi, pj));
+    const u64 po = pv ? (u64)bond_class(mol ? pb[tid * MOL_BOND_W + 2] : rb[tid * REC_BOND_W + 2]) : 0;
+
+    // ---- degrees (in acc), the atoms of the graph, tags, id_0
+    if (tid == 0) cnt[0] = 0, zero_at = -1;
+    for (int a = tid; a < MAX_ATOMS; a += GT) acc[a] = 0, tag[a] = 0, remap[a] = -1;
+    __syncthreads();
+    {
+        int valid = pv, i, j;
+        if (pv) {
+            atomicAdd(&acc[pi], 1ull);
+            atomicAdd(&acc[pj], 1ull);
+        }
+        for (int q = tid + GT; q < nrows; q += GT) {
+            if (!(mol ? mol_ends(pb, q, na, i, j) : rec_ends(rb, q, nt, i, j))) continue;
+            ++valid;
+            atomicAdd(&acc[i], 1ull);
+            atomicAdd(&acc[j], 1ull);
+        }
+        if (valid) atomicAdd(cnt, valid);
+        for (int k = tid; k < nlisted; k += GT) {
+            const int e = ph[k];
+            if (e >= 1 && e <= na) tag[e - 1] = 1;
+        }
+    }
+    __syncthreads();
+    const int nvalid = cnt[0];
+    int n = na;
+    if (mol) {
+        for (int a = tid; a < na; a += GT) {
+            const u64 e = id0(atom_class(pa[a * ATOM_W + 2]), pa[a * ATOM_W + 3], acc[a]);
+            init[a] = tag[a] ? mix(e + TAG_K) : e;
+            orig[a] = (u16)a;
+        }
+    } else {
+        const int a0 = 2 * tid, a1 = 2 * tid + 1;
+        const u64 deg0 = a0 < nt ? acc[a0] : 0, deg1 = a1 < nt ? acc[a1] : 0;
+        const unsigned f0 = deg0 != 0, f1 = deg1 != 0;
+        unsigned total;
+        const unsigned r0 = block_excl_scan<GT>(f0 + f1, wt, &total), r1 = r0 + f0;
+        n = (int)total;
+        if (f0) remap[a0] = (int)r0, orig[r0] = (u16)a0, init[r0] = id0(atom_class(ra[a0 * REC_ATOM_W + 2]), ra[a0 * REC_ATOM_W + 3], deg0);
+        if (f1) remap[a1] = (int)r1, orig[r1] = (u16)a1, init[r1] = id0(atom_class(ra[a1 * REC_ATOM_W + 2]), ra[a1 * REC_ATOM_W + 3], deg1);
+    }
+    __syncthreads();                     // (every degree was read: acc becomes the round's sums)
+    for (int a = tid; a < MAX_ATOMS; a += GT) acc[a] = 0;
+    if (!mol && pv) pi = remap[pi], pj = remap[pj];      // (both in T: this row is one of those that put them there)
+    for (int a = tid; a < n; a += GT) cur[a] = init[a];
+    __syncthreads();
+
+    // class, charge of an atom of the graph; a bond row as (atom, atom, order class) of the graph, false for a row that names no pair
+    auto cls_of = [&](int a) __attribute__((always_inline)) { return atom_class(mol ? pa[a * ATOM_W + 2] : ra[orig[a] * REC_ATOM_W + 2]); };
+    auto chg_of = [&](int a) __attribute__((always_inline)) { return mol ? pa[a * ATOM_W + 3] : ra[orig[a] * REC_ATOM_W + 3]; };
+    auto row = [&](int q, int& i, int& j, int& o) __attribute__((always_inline)) {
+        if (mol) {
+            if (!mol_ends(pb, q, na, i, j)) return false;
+            o = bond_class(pb[q * MOL_BOND_W + 2]);
+        } else {
+            if (!rec_ends(rb, q, nt, i, j)) return false;
+            i = remap[i], j = remap[j];
+            o = bond_class(rb[q * REC_BOND_W + 2]);
+        }
+        return true;
+    };
+    auto round = [&](u64 r) __attribute__((always_inline)) {
+        if (mol) refine_round_mol(tid, cur, acc, pb, nrows, na, n, r, pv, pi, pj, po);
+        else refine_round_rec(tid, cur, acc, rb, nrows, nt, remap, n, r, pv, pi, pj, po);
+    };
+    u64 shared = ~0ull;
+    int zeros = 0;
+    auto classes = [&]() __attribute__((always_inline)) { return refine_classes<SLOTS>(tid, cur, n, table, wi, shared, zeros); };
+    auto sum_int = [&](int v) __attribute__((always_inline)) { return block_reduce(v, wi, [](int u, int w) { return u + w; }); };
+    auto min_int = [&](int v) __attribute__((always_inline)) { return block_reduce(v, wi, [](int u, int w) { return min(u, w); }); };
+    // h of the relabelled graph under the ranks `rank` (uniform)
+    auto leaf_hash = [&](const u16* rank) __attribute__((always_inline)) {
+        u64 h = 0;
+        int i, j, o;
+        for (int a = tid; a < n; a += GT)
+            h += mix(mix(mix(mix((u64)rank[a] + 1) + (u64)(cls_of(a) + 1)) + (u64)(long long)chg_of(a)) + (u64)tag[a]);
+        for (int q = tid; q < nrows; q += GT) {
+            if (!row(q, i, j, o)) continue;
+            const u64 lo = min((int)rank[i], (int)rank[j]), hi = max((int)rank[i], (int)rank[j]);
+            h += mix(mix(((lo << 32) | hi) + BOND_K) + (u64)o);
+        }
+        return block_reduce(h, wu, [](u64 u, u64 v) { return u + v; });
+    };
+
+    int leaves = 0, tries = 0, rounds = 0, levels_max = 0, pruned_trace = 0, pruned_orbit = 0, autos = 0, improved = 0;
+    bool have_best = false;
+    int best_levels = 0;
+    if (!empty && n > 0) {
+        enum { REFINE, CHILD, BACK };
+        int mode = REFINE, target = -1, level = 0, less_from = NONE;
+        u64 r = 0, best_h = 0;
+        int prev = classes();
+        while (true) {
+            if (mode == REFINE) {
+                int k = 0, c = 0;
+                bool out = false;
+                while (true) {
+                    if (rounds >= max_rounds) { out = true; break; }
+                    ++rounds, ++r, ++k;
+                    round(r);
+                    c = classes();
+                    if (c <= prev || k >= n) break;
+                    prev = c;
+                }
+                if (out) { status |= ABC_CANON_UNDECIDED; break; }
+                const u64 s = refine_multiset_sum(tid, cur, n, wu);
+                if (tid == 0) cur_k[level] = (u16)k, cur_c[level] = (u16)c, cur_sum[level] = s;
+                levels_max = max(levels_max, level);
+                mode = BACK, target = level - 1;
+                if (have_best && less_from == NONE) {
+                    const int bk = best_k[level], bc = best_c[level];
+                    const u64 bs = best_sum[level];
+                    const int cmp = k != bk ? (k < bk ? -1 : 1) : (c != bc ? (c < bc ? -1 : 1) : (s != bs ? (s < bs ? -1 : 1) : 0));
+                    if (cmp > 0) {
+                        ++pruned_trace;
+                        continue;
+                    }
+                    if (cmp < 0) less_from = level;
+                }
+                if (c == n) {
+                    // ---- (b) the leaf
+                    ++leaves;
+                    for (int a = tid; a < n; a += GT) {
+                        const u64 e = cur[a];
+                        int below = 0;
+                        for (int x = 0; x < n; ++x) below += cur[x] < e;
+                        rk[a] = (u16)below;
+                    }
+                    __syncthreads();     // (the ranks and tid 0's trace of this level are written)
+                    const u64 h = leaf_hash(rk);
+                    if (!have_best || less_from != NONE || h < best_h) {
+                        improved += have_best;
+                        for (int a = tid; a < n; a += GT) best_ids[a] = cur[a], brank[a] = rk[a];
+                        for (int l = tid; l <= level; l += GT) {
+                            best_k[l] = cur_k[l], best_c[l] = cur_c[l], best_sum[l] = cur_sum[l];
+                            if (l < level) best_choice[l] = choice[l];
+                        }
+                        have_best = true, best_levels = level, best_h = h, less_from = NONE;
+                        __syncthreads();
+                    } else if (h == best_h) {
+                        // the map onto the best leaf by equal id, through the table
+                        for (int k2 = tid; k2 < SLOTS; k2 += GT) table[k2] = 0;
+                        if (tid == 0) zero_at = -1;
+                        __syncthreads();
+                        for (int a = tid; a < n; a += GT) {
+                            const u64 e = best_ids[a];
+                            if (e == 0) {
+                                zero_at = a;
+                                continue;
+                            }
+                            unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
+                            for (int probe = 0; probe < SLOTS; ++probe) {
+                                const u64 old = atomicCAS(&table[slot], 0ull, e);
+                                if (old == 0) {
+                                    tidx[slot] = (u16)a;
+                                    break;
+                                }
+                                if (old == e) break;
+                                slot = (slot + 1) & (SLOTS - 1);
+                            }
+                        }
+                        __syncthreads();
+                        int bad = 0;
+                        for (int a = tid; a < n; a += GT) {
+                            const u64 e = cur[a];
+                            int t = -1;
+                            if (e == 0) {
+                                t = zero_at;
+                            } else {
+                                unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
+                                for (int probe = 0; probe < SLOTS; ++probe) {
+                                    const u64 at = table[slot];
+                                    if (at == e) t = tidx[slot];
+                                    if (at == e || at == 0) break;
+                                    slot = (slot + 1) & (SLOTS - 1);
+                                }
+                            }
+                            const int y = t < 0 || t >= n ? a : t;
+                            gam[a] = (u16)y;
+                            bad += t < 0 || t >= n || cls_of(a) != cls_of(y) || chg_of(a) != chg_of(y) || tag[a] != tag[y];
+                        }
+                        bool ok = sum_int(bad) == 0;      // (gam is written: the reduction synchronises)
+                        if (ok) {
+                            // the multiset of the mapped rows is the multiset of the rows, by counting
+                            int common = 0, i, j, o, i2, j2, o2;
+                            for (int q = tid; q < nrows; q += GT) {
+                                if (!row(q, i, j, o)) continue;
+                                const int gi = gam[i], gj = gam[j], lo = min(gi, gj), hi = max(gi, gj);
+                                int before = 0, there = 0;
+                                for (int q2 = 0; q2 < nrows; ++q2) {
+                                    if (!row(q2, i2, j2, o2) || o2 != o) continue;
+                                    const int gi2 = gam[i2], gj2 = gam[j2];
+                                    before += q2 < q && min(gi2, gj2) == lo && max(gi2, gj2) == hi;
+                                    there += min(i2, j2) == lo && max(i2, j2) == hi;
+                                }
+                                common += before < there;
+                            }
+                            ok = sum_int(common) == nvalid;
+                        }
+                        if (!ok) { status |= ABC_CANON_COLLISION; break; }
+                        ++autos;
+                        int first = NONE;
+                        for (int l = tid; l < level; l += GT)
+                            if (choice[l] != best_choice[l]) first = min(first, l);
+                        target = min(min_int(first), level - 1);      // the level where the path left the best's
+                        // x ~ gamma(x) in the orbit tables of the levels whose prefix gamma fixes: the greater root is hung under the less
+                        const int upto = min(target, ORBITS - 1);
+                        for (int l = 0; l <= upto; ++l) {
+                            int* p = orbit[l];
+                            for (int a = tid; a < n; a += GT) {
+                                int x = a, y = gam[a];
+                                for (int it = 0; it < n; ++it) {
+                                    for (int w = 0; w < n; ++w) {
+                                        const int up = __hip_atomic_load(&p[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                        if (up == x) break;
+                                        x = up;
+                                    }
+                                    for (int w = 0; w < n; ++w) {
+                                        const int up = __hip_atomic_load(&p[y], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                        if (up == y) break;
+                                        y = up;
+                                    }
+                                    if (x == y) break;
+                                    if (x < y) { const int t = x; x = y; y = t; }
+                                    if (atomicCAS(&p[x], x, y) == x) break;
+                                }
+                            }
+                        }
+                        __syncthreads();
+                        for (int l = 0; l <= upto; ++l) {     // flat again: every atom under its root, the least of its orbit
+                            int* p = orbit[l];
+                            int root[MAX_ATOMS / GT];
+#pragma unroll
+                            for (int u = 0; u < MAX_ATOMS / GT; ++u) {
+                                int x = min(tid + u * GT, MAX_ATOMS - 1);
+                                for (int w = 0; w < n; ++w) {
+                                    const int up = p[x];
+                                    if (up == x) break;
+                                    x = up;
+                                }
+                                root[u] = x;
+                            }
+                            __syncthreads();
+#pragma unroll
+                            for (int u = 0; u < MAX_ATOMS / GT; ++u)
+                                if (tid + u * GT < n) p[tid + u * GT] = root[u];
+                        }
+                        __syncthreads();
+                    }
+                    continue;
+                }
+                if (level + 1 >= n) { status |= ABC_CANON_COLLISION; break; }      // (only colliding hashes get here)
+                // the cell: the least id that two atoms share; its last atom
+                const u64 least = block_reduce(shared, wu, [](u64 u, u64 v) { return min(u, v); });
+                const u64 cellv = zeros > 1 ? 0 : least;
+                int last = -1;
+                for (int a = tid; a < n; a += GT)
+                    if (cur[a] == cellv) last = max(last, a);
+                last = block_reduce(last, wi, [](int u, int w) { return max(u, w); });
+                if (last < 0) { status |= ABC_CANON_COLLISION; break; }
+                if (tid == 0) cell[level] = cellv, cell_max[level] = (u16)last, nxt[level] = 0;
+                if (level < ORBITS)
+                    for (int a = tid; a < MAX_ATOMS; a += GT) orbit[level][a] = a;
+                __syncthreads();
+                mode = CHILD;
+            }
+            if (mode == CHILD) {
+                // ---- (c) the next atom of the cell that is the least of its orbit
+                const u64 cellv = cell[level];
+                const int from = nxt[level];
+                const bool orbits = level < ORBITS;
+                int first = MAX_ATOMS;
+                for (int a = tid; a < n; a += GT)
+                    if (a >= from && cur[a] == cellv && (!orbits || orbit[level][a] == a)) first = min(first, a);
+                const int v = min_int(first);
+                if (orbits) {
+                    int skipped = 0;
+                    for (int a = tid; a < n; a += GT) skipped += a >= from && a < v && cur[a] == cellv;
+                    pruned_orbit += sum_int(skipped);
+                }
+                if (v >= n) {
+                    mode = BACK, target = level - 1;
+                    continue;
+                }
+                if (tries >= max_tries) { status |= ABC_CANON_UNDECIDED; break; }
+                ++tries;
+                prev = cur_c[level] + 1;
+                if (tid == 0) choice[level] = (u16)v, nxt[level] = (u16)(v + 1), cur[v] = indiv(cur[v], level);
+                __syncthreads();
+                ++level;
+                mode = REFINE;
+                continue;
+            }
+            // ---- (d) back
+            __syncthreads();
+            for (int it = 0; it < n && target >= 0 && nxt[target] > cell_max[target]; ++it) --target;
+            if (target < 0) break;
+            level = target;
+            if (less_from != NONE && less_from > level) less_from = NONE;
+            for (int a = tid; a < n; a += GT) cur[a] = init[a];
+            __syncthreads();
+            r = 0;
+            bool out = false;
+            for (int k = 0; k <= level && !out; ++k) {
+                const int todo = cur_k[k];
+                for (int i = 0; i < todo; ++i) {
+                    if (rounds >= max_rounds) { out = true; break; }
+                    ++rounds, ++r;
+                    round(r);
+                }
+                if (!out && k < level) {
+                    if (tid == 0) cur[choice[k]] = indiv(cur[choice[k]], k);
+                    __syncthreads();
+                }
+            }
+            if (out) { status |= ABC_CANON_UNDECIDED; break; }
+            mode = CHILD;
+        }
+    }
+    __syncthreads();
+
+    // ---- the outputs: every word of every buffer
+    if (!have_best)
+        for (int a = tid; a < n; a += GT) brank[a] = (u16)a;
+    __syncthreads();
+    const bool none = empty || n == 0;
+    for (int k = tid; k < cap; k += GT)
+        if (k >= n) order[k] = -1;
+    for (int a = tid; a < n; a += GT) order[brank[a]] = orig[a];
+    const u64 key0 = none ? 0 : leaf_hash(brank);
+    u64 t = 0;
+    if (have_best)
+        for (int l = tid; l <= best_levels; l += GT) t += mix(mix(mix(mix((u64)l + 1) + (u64)best_k[l]) + (u64)best_c[l]) + best_sum[l]);
+    t = block_reduce(t, wu, [](u64 u, u64 v) { return u + v; });
+    if (tid == 0) {
+        int* st = d.stats + (size_t)b * NCOL;
+        st[ABC_CANON_STATUS] = status;
+        st[ABC_CANON_LEAVES] = leaves, st[ABC_CANON_TRIES] = tries, st[ABC_CANON_ROUNDS] = rounds, st[ABC_CANON_LEVELS_MAX] = levels_max;
+        st[ABC_CANON_PRUNED_TRACE] = pruned_trace, st[ABC_CANON_PRUNED_ORBIT] = pruned_orbit;
+        st[ABC_CANON_AUTOMORPHISMS] = autos, st[ABC_CANON_IMPROVED] = improved;
+        d.key[(size_t)b * 2] = (long long)key0;
+        d.key[(size_t)b * 2 + 1] = empty ? 0 : (long long)mix(mix(mix((u64)n) + (u64)nvalid) + t);
+    }
+    if (cert == nullptr && !want_rows) return;
+
+    int* const oc = want_rows ? d.out_counts + (size_t)b * 4 : nullptr;
+    int* const oa = want_rows ? d.out_atoms + (size_t)b * d.cap_atoms * ATOM_W : nullptr;
+    int* const ob = want_rows ? d.out_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W : nullptr;
+    int* const oh = want_rows ? d.out_implh + (size_t)b * d.cap_atoms : nullptr;
+    if (cert != nullptr) {
+        const int used = 2 + n + 3 * nvalid;
+        for (int k = tid; k < 2 + cap + 3 * cap_bonds; k += GT)
+            if (k >= used) cert[k] = -1;
+        if (tid == 0) cert[0] = n, cert[1] = nvalid;
+        for (int a = tid; a < n; a += GT)
+            cert[2 + brank[a]] = (int)(((unsigned)chg_of(a) << 5) | ((unsigned)tag[a] << 4) | (unsigned)cls_of(a));
+    }
+    if (want_rows) {
+        if (tid < 4) oc[tid] = d.mol_counts[(size_t)b * 4 + tid];
+        for (int k = tid; k < (d.cap_atoms - n) * ATOM_W; k += GT) oa[n * ATOM_W + k] = 0;
+        for (int k = tid; k < n * ATOM_W; k += GT) oa[brank[k / ATOM_W] * ATOM_W + k % ATOM_W] = pa[k];
+        for (int k = tid; k < (d.cap_mol_bonds - nrows) * MOL_BOND_W; k += GT) ob[nrows * MOL_BOND_W + k] = 0;
+        // the implicit-H list: the entries in 1..n renumbered and ascending, the others after them verbatim
+        for (int k = tid; k < d.cap_atoms; k += GT) {
+            if (k >= nlisted) {
+                oh[k] = 0;
+                continue;
+            }
+            const int e = ph[k];
+            const bool in = e >= 1 && e <= n;
+            const int val = in ? brank[e - 1] + 1 : 0;
+            int less = 0, in_all = 0, out_before = 0;
+            for (int k2 = 0; k2 < nlisted; ++k2) {
+                const int e2 = ph[k2];
+                const bool in2 = e2 >= 1 && e2 <= n;
+                in_all += in2;
+                out_before += !in2 && k2 < k;
+                if (in && in2) {
+                    const int val2 = brank[e2 - 1] + 1;
+                    less += val2 < val || (val2 == val && k2 < k);
+                }
+            }
+            oh[in ? less : in_all + out_before] = in ? val : e;
+        }
+    }
+    // the bond rows, by counting: the place of a row among the certificate's triples and among the canonical rows
+    int i, j, o, i2, j2, o2;
+    for (int q = tid; q < nrows; q += GT) {
+        const bool valid = row(q, i, j, o);
+        const int bi = valid ? brank[i] : 0, bj = valid ? brank[j] : 0, lo = min(bi, bj), hi = max(bi, bj);
+        const int pair = lo * MAX_ATOMS + hi;
+        int at_cert = 0, at_rows = 0, valid_before = 0;
+        for (int q2 = 0; q2 < nrows; ++q2) {
+            if (!row(q2, i2, j2, o2)) continue;
+            valid_before += q2 < q;
+            const int bi2 = brank[i2], bj2 = brank[j2], pair2 = min(bi2, bj2) * MAX_ATOMS + max(bi2, bj2);
+            at_rows += pair2 < pair || (pair2 == pair && q2 < q);
+            at_cert += pair2 < pair || (pair2 == pair && (o2 < o || (o2 == o && q2 < q)));
+        }
+        if (cert != nullptr && valid) {
+            int* tr = cert + 2 + n + 3 * at_cert;
+            tr[0] = lo, tr[1] = hi, tr[2] = o;
+        }
+        if (want_rows) {
+            const int* src = pb + q * MOL_BOND_W;
+            int* dst = ob + (valid ? at_rows : nvalid + q - valid_before) * MOL_BOND_W;
+            dst[0] = valid ? bi + 1 : src[0], dst[1] = valid ? bj + 1 : src[1], dst[2] = src[2], dst[3] = src[3];
+        }
+    }
+}
+
+bool overlap(const void* p, size_t np, const void* q, size_t nq) {
+    const char *a = (const char*)p, *c = (const char*)q;
+    return p != nullptr && q != nullptr && a < c + nq && c < a + np;
+}
+
+}  // namespace
+
+extern "C" int abc_canon_desc_size(void) { return (int)sizeof(abc_canon_desc); }
+
+extern "C" int abc_canonical_order(const abc_canon_desc* d, abc_stream_t stream) {
+    const bool mol = d->mol_counts != nullptr, rec = d->rec_counts != nullptr;
+    if (d->B < 1) return abc_fail(ABC_EINVAL, "canonical_order: empty");
+    if (mol == rec) return abc_fail(ABC_EINVAL, "canonical_order: give the molecule rows or the graph records, one side");
+    if (d->max_tries < 0) return abc_fail(ABC_EINVAL, "canonical_order: max_tries must be >= 0 (0: the default)");
+    if (d->max_rounds < 0) return abc_fail(ABC_EINVAL, "canonical_order: max_rounds must be >= 0 (0: the default)");
+    if (!d->order || !d->stats || !d->key) return abc_fail(ABC_EINVAL, "canonical_order: null output (order, stats, key)");
+    const int rows_given = (d->out_counts != nullptr) + (d->out_atoms != nullptr) + (d->out_bonds != nullptr) + (d->out_implh != nullptr);
+    if (rows_given != 0 && rows_given != 4) return abc_fail(ABC_EINVAL, "canonical_order: the canonical rows are four buffers, or none");
+    if (mol) {
+        if (!d->mol_atoms || !d->mol_bonds) return abc_fail(ABC_EINVAL, "canonical_order: null molecule buffer");
+        if (d->cap_atoms < 1 || d->cap_mol_bonds < 1) return abc_fail(ABC_EINVAL, "canonical_order: cap_atoms and cap_mol_bonds must be >= 1");
+        if (d->cap_atoms > MAX_ATOMS) return abc_fail(ABC_EUNSUPPORTED, "canonical_order: cap_atoms must be <= 512");
+        if (rows_given && d->cap_mol_bonds > MAX_ROW_BONDS)
+            return abc_fail(ABC_EUNSUPPORTED, "canonical_order: cap_mol_bonds must be <= 4096 when the canonical rows are requested");
+    } else {
+        if (!d->rec_atoms || !d->rec_bonds) return abc_fail(ABC_EINVAL, "canonical_order: null record buffer");
+        if (d->max_atoms < 1 || d->max_bonds < 1) return abc_fail(ABC_EINVAL, "canonical_order: max_atoms and max_bonds must be >= 1");
+        if (d->max_atoms > MAX_ATOMS) return abc_fail(ABC_EUNSUPPORTED, "canonical_order: max_atoms must be <= 512");
+        if (rows_given) return abc_fail(ABC_EINVAL, "canonical_order: the canonical rows are the molecule side's");
+    }
+    const size_t B = (size_t)d->B, cap = (size_t)(mol ? d->cap_atoms : d->max_atoms), cb = (size_t)(mol ? d->cap_mol_bonds : d->max_bonds);
+    // (pointer, bytes) of every input and of every output: no output may overlap an input or another output
+    const void* in[7] = {d->mol_counts, d->mol_atoms, d->mol_bonds, d->mol_implh, d->rec_atoms, d->rec_bonds, d->rec_counts};
+    const size_t nin[7] = {B * 16, B * cap * ATOM_W * 4, B * cb * MOL_BOND_W * 4, B * cap * 4, B * cap * REC_ATOM_W * 4, B * cb * REC_BOND_W * 4, B * 8};
+    const void* out[8] = {d->order, d->stats, d->key, d->cert_out, d->out_counts, d->out_atoms, d->out_bonds, d->out_implh};
+    const size_t nout[8] = {B * cap * 4, B * NCOL * 4, B * 16, B * (2 + cap + 3 * cb) * 4, B * 16, B * cap * ATOM_W * 4, B * cb * MOL_BOND_W * 4, B * cap * 4};
+    for (int o = 0; o < 8; ++o) {
+        for (int i = 0; i < 7; ++i)
+            if (overlap(out[o], nout[o], in[i], nin[i])) return abc_fail(ABC_EINVAL, "canonical_order: an output overlaps an input");
+        for (int o2 = 0; o2 < o; ++o2)
+            if (overlap(out[o], nout[o], out[o2], nout[o2])) return abc_fail(ABC_EINVAL, "canonical_order: two outputs overlap");
+    }
+    hipLaunchKernelGGL(graph_canon_kernel, dim3(d->B), dim3(GT), 0, (hipStream_t)stream, *d);
+    return abc_check_launch("canonical_order");
+}

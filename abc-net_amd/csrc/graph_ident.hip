@@ -31,31 +31,17 @@
 #include "block_scan.hpp"
 #include "mol_rows.hpp"
 #include "graph_ids.hpp"
+#include "graph_refine.hpp"
 
 namespace {
 
-constexpr int GT = 256;              // threads per workgroup
+constexpr int GT = REFINE_GT;         // threads per workgroup (graph_refine.hpp)
 constexpr int MAX_ATOMS = ABC_MAX_SIM_ATOMS;      // ids of both sides, one sum, id_0 of the record, the level records, the class table: 46 KB of LDS
 constexpr int NCOL = ABC_IDENT_NCOL;
 constexpr int NW = GT / 64;
 constexpr int SLOTS = 2 * MAX_ATOMS;  // of the class count's table: a power of two, at most half full
 static_assert(MAX_ATOMS == 2 * GT, "two atoms per thread: the record scan, the class count");
 enum { SAME = 1, DIFFERENT = 2, UNDECIDED = 3 };
-
-// the id of the atom individualised at `level`
-__device__ inline u64 indiv(u64 id, int level) { return mix(mix(id) + 0x9E3779B97F4A7C15ull * (u64)(level + 1)); }
-
-// f over the workgroup's values; wt = LDS scratch [NW].  Every thread must call it (it synchronises, before and after)
-template <class T, class F>
-__device__ inline T block_reduce(T v, T* wt, F f) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = f(v, (T)__shfl_xor(v, o));
-    __syncthreads();                 // wt may still be read from the previous call; what the callers wrote before is visible after
-    if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return f(f(wt[0], wt[1]), f(wt[2], wt[3]));
-}
-static_assert(NW == 4, "block_reduce folds four waves");
 
 __global__ __launch_bounds__(GT) void graph_ident_kernel(const abc_graph_identity_desc d) {
     __shared__ u64 cur[2][MAX_ATOMS];    // the ids of every atom
@@ -140,81 +126,24 @@ __global__ __launch_bounds__(GT) void graph_ident_kernel(const abc_graph_identit
     const bool size_equal = !empty && na == n_t && valid_p == valid_t;
     const int n = na;
 
-    // one round of side `s` (uniform); acc is zero on entry and on exit
+    // one round of side `s` (uniform); acc is zero on entry and on exit.  (The bodies of these three are graph_refine.hpp's, expanded
+    // here: see there)
     auto round = [&](int s, u64 r) __attribute__((always_inline)) {
         u64* id = cur[s];
         int i, j;
         if (s == 0) {
-            if (pv) {
-                atomicAdd(&acc[pi], mix(mix(id[pj]) + po));
-                atomicAdd(&acc[pj], mix(mix(id[pi]) + po));
-            }
-            for (int q = tid + GT; q < nb; q += GT) {
-                if (!mol_ends(pb, q, na, i, j)) continue;
-                const u64 o = (u64)bond_class(pb[q * MOL_BOND_W + 2]);
-                atomicAdd(&acc[i], mix(mix(id[j]) + o));
-                atomicAdd(&acc[j], mix(mix(id[i]) + o));
-            }
+            REFINE_ROUND_MOL(id, acc, pb, nb, na, tid, pv, pi, pj, po, i, j)
         } else {
-            if (tv) {
-                atomicAdd(&acc[ti], mix(mix(id[tj]) + to));
-                atomicAdd(&acc[tj], mix(mix(id[ti]) + to));
-            }
-            for (int k = tid + GT; k < m; k += GT) {
-                if (!rec_ends(rb, k, nt, i, j)) continue;
-                const u64 o = (u64)bond_class(rb[k * REC_BOND_W + 2]);
-                i = remap[i], j = remap[j];
-                atomicAdd(&acc[i], mix(mix(id[j]) + o));
-                atomicAdd(&acc[j], mix(mix(id[i]) + o));
-            }
+            REFINE_ROUND_REC(id, acc, rb, m, nt, remap, tid, tv, ti, tj, to, i, j)
         }
-        __syncthreads();
-        for (int a = tid; a < n; a += GT) {
-            id[a] = mix(mix(id[a] + r) + acc[a]);
-            acc[a] = 0;
-        }
-        __syncthreads();
+        REFINE_ROUND_END(id, acc, n, r, tid)
     };
-    // The number of distinct ids, exactly: every id goes into an open-addressed table of 2 n slots (64-bit LDS compare-and-swap; 0
-    // marks a free slot, so the ids that ARE 0 are counted apart), and the ids that found a free slot are counted -- as many as there
-    // are distinct values, in any order of the threads.  An id that finds itself there is shared by two atoms: `shared` keeps this
-    // thread's least such id, `zeros` (uniform) the number of ids that are 0, for the cell of the level.
+    // the number of distinct ids, exactly; `shared` keeps this thread's least id two atoms share, `zeros` (uniform) the number of
+    // ids that are 0, for the cell of the level
     u64 shared = ~0ull;
     int zeros = 0;
-    auto classes = [&](const u64* id) __attribute__((always_inline)) {
-        for (int k = tid; k < SLOTS; k += GT) table[k] = 0;
-        __syncthreads();
-        int fresh = 0, zero = 0;
-        shared = ~0ull;
-        for (int a = tid; a < n; a += GT) {
-            const u64 e = id[a];
-            if (e == 0) {
-                ++zero;
-                continue;
-            }
-            unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
-            for (int probe = 0; probe < SLOTS; ++probe) {             // (n <= SLOTS / 2 ids: a free slot is always found)
-                const u64 old = atomicCAS(&table[slot], 0ull, e);
-                if (old == 0) {
-                    ++fresh;
-                    break;
-                }
-                if (old == e) {
-                    shared = min(shared, e);
-                    break;
-                }
-                slot = (slot + 1) & (SLOTS - 1);
-            }
-        }
-        const int both = block_reduce(fresh + (zero << 16), wi, [](int u, int v) { return u + v; });
-        zeros = both >> 16;
-        return (both & 0xFFFF) + (zeros > 0);
-    };
-    auto multiset_sum = [&](const u64* id) __attribute__((always_inline)) {
-        u64 s = 0;
-        for (int a = tid; a < n; a += GT) s += mix(id[a]);
-        return block_reduce(s, wu, [](u64 u, u64 v) { return u + v; });
-    };
+    auto classes = [&](const u64* id) __attribute__((always_inline)) { REFINE_CLASSES(id, n, table, SLOTS, wi, tid, shared, zeros) };
+    auto multiset_sum = [&](const u64* id) __attribute__((always_inline)) { REFINE_MULTISET_SUM(id, n, wu, tid) };
 
     int result = 0, levels = 0, tries = 0, backtracks = 0, rounds = 0;
     if (empty) {

@@ -90,13 +90,67 @@ class Molecule:
         out.append("M  END\n$$$$")
         return "".join(out)
 
-    def smiles(self, stereo=False):
+    def smiles(self, stereo=False, canonical=False):
         """a deterministic, valid SMILES of this graph by the text rule of DESIGN.md section 7 (the host form and the oracle of
         csrc/smiles.hip, integers only): NOT the canonical string RDKit prints; hs is not read.  stereo=False: wedges are single
         bonds, no mark is written and the positions are not read.  stereo=True: the tetrahedral centres the wedge rows and the
         positions decide (stereo_centres) are written as `@` / `@@` in a bracket token; nothing else of the text changes.
+        canonical=True: canonical().smiles() -- the same rule on the canonical atom order, so equal graphs give equal strings (not
+        RDKit's canonical string either; refused with stereo=True: wedge ownership and the drawn geometry are not in the invariant).
         ValueError for a row the rule refuses and for more than 99 ring bonds open at once."""
+        if canonical:
+            if stereo:
+                raise ValueError("Molecule.smiles: canonical=True with stereo=True is not covered (the canonical order does not read "
+                                 "wedge ownership or positions)")
+            return self.canonical()._smiles(False)[0]
         return self._smiles(bool(stereo))[0]
+
+    def canon_graph(self):
+        """(classes, charges, bonds [(i, j, order class)] 0-based, tags) as csrc/graph_canon.hip reads the rows: every atom takes
+        part, a row with an end outside 1..n or both ends on one atom is skipped, a wedge is a single bond, a pair listed twice
+        counts twice; tag 1 for an atom implicit_hs lists"""
+        n = len(self.symbols)
+        classes = [canon_atom_class(ATOM_SYMBOLS.index(s)) if s in ATOM_SYMBOLS else 0 for s in self.symbols]
+        bonds = [(e1 - 1, e2 - 1, canon_bond_class(o)) for (e1, e2), o in zip(self.bonds, self.orders)
+                 if 1 <= e1 <= n and 1 <= e2 <= n and e1 != e2]
+        tags = [0] * n
+        for a in self.implicit_hs:
+            if 1 <= a <= n:
+                tags[a - 1] = 1
+        return classes, list(self.charges), bonds, tags
+
+    def canonical_order(self, max_tries=None, max_rounds=None):
+        """(rank, stats, key): rank[a] the canonical position of atom a, the CANON_COLUMNS of the search as a dict, the two hash
+        words of abc_canon_desc.key -- canonical_labelling on canon_graph()"""
+        g = self.canon_graph()
+        rank, st, traces = canonical_labelling(g, CANON_DEFAULT_TRIES if max_tries is None else max_tries,
+                                               CANON_DEFAULT_ROUNDS if max_rounds is None else max_rounds)
+        if self.truncated:
+            st["status"] |= CANON_TRUNCATED
+        return rank, st, canon_key(g, rank, traces)
+
+    def canonical(self, max_tries=None, max_rounds=None):
+        """this molecule on its canonical atom order (the host form of abc_canonical_order's canonical rows): atom rows moved to
+        their rank; both ends of every bond renumbered in place (end 1 stays end 1); the valid rows first, ascending by (lower end,
+        higher end, original row), the rows the graph skips after them verbatim; implicit_hs renumbered, the entries in 1..n ascending,
+        the others after them verbatim.  Two molecules with the same graph (classes, charges, order classes, listed atoms) give the
+        same symbols, charges, bonds and implicit_hs, whatever their rows' order -- unless a budget ran out (canonical_order's
+        status)."""
+        rank = self.canonical_order(max_tries, max_rounds)[0]
+        n = len(rank)
+        at = sorted(range(n), key=lambda a: rank[a])
+        valid, rest = [], []
+        for q, (e1, e2) in enumerate(self.bonds):
+            if 1 <= e1 <= n and 1 <= e2 <= n and e1 != e2:
+                f1, f2 = rank[e1 - 1] + 1, rank[e2 - 1] + 1
+                valid.append((min(f1, f2), max(f1, f2), q, [f1, f2]))
+            else:
+                rest.append((q, [e1, e2]))
+        rows = [(q, ends) for _, _, q, ends in sorted(valid)] + rest
+        listed = sorted(rank[a - 1] + 1 for a in self.implicit_hs if 1 <= a <= n) + [a for a in self.implicit_hs if not 1 <= a <= n]
+        return Molecule([self.symbols[a] for a in at], [self.charges[a] for a in at], [self.hs[a] for a in at],
+                        [self.positions[a] for a in at], [ends for _, ends in rows], [self.orders[q] for q, _ in rows], listed,
+                        None if self.sources is None else [self.sources[q] for q, _ in rows], self.truncated)
 
     def stereo_centres(self):
         """one code per atom by the stereo rule of DESIGN.md section 7: 0 no candidate, +1 / -1 the local parity s(a) of a marked
@@ -233,6 +287,250 @@ class Molecule:
                 mark = "@" if centre[a] * (-1 if swaps & 1 else 1) > 0 else "@@"
             out.append(lead + token(a, mark) + "".join(digits) + ")" * closes[p])
         return "".join(out), centre
+
+
+# ------------------------------------------------------------------------------------------------- the canonical atom order
+# The host form of csrc/graph_canon.hip (the contract: include/abcnet_hip.h, abc_canon_desc): an
+# individualise-and-refine search over EVERY branch that keeps the least leaf, with the device's budgets and counters, so that order,
+# stats, key and certificate are comparable with the kernel word for word.  Integers only (uint64, wrapping).
+CANON_COLUMNS = ("status", "leaves", "tries", "rounds", "levels_max", "pruned_trace", "pruned_orbit", "automorphisms", "improved")
+CANON_EMPTY, CANON_TRUNCATED, CANON_UNDECIDED, CANON_COLLISION = 1, 2, 4, 8
+CANON_DEFAULT_TRIES, CANON_DEFAULT_ROUNDS, CANON_ORBIT_LEVELS = 4096, 16384, 8
+_M64 = (1 << 64) - 1
+_GOLD, _CANON_TAG, _CANON_BOND = 0x9E3779B97F4A7C15, 0xD6E8FEB86659FD93, 0xC2B2AE3D27D4EB4F
+_U = np.uint64
+
+
+def _mix(x):
+    """the splitmix64 finaliser (csrc/graph_ids.hpp)"""
+    x &= _M64
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & _M64
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _mixv(x):
+    x = x ^ (x >> _U(30))
+    x = x * _U(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> _U(27))
+    x = x * _U(0x94D049BB133111EB)
+    return x ^ (x >> _U(31))
+
+
+def canon_atom_class(t):
+    """the class of a vocabulary index (csrc/mol_rows.hpp, atom_class): outside 0..13 -> 0, index 0 -> carbon"""
+    t = int(t)
+    return 0 if t < 0 or t > 13 else (1 if t == 0 else t)
+
+
+def canon_bond_class(c):
+    """the order class of a bond code (csrc/graph_ids.hpp, bond_class): a wedge is a single bond"""
+    c = int(c)
+    return 1 if c in (5, 6) else (c if 1 <= c <= 4 else 0)
+
+
+def canon_leaf_hash(graph, rank):
+    """h of a leaf: the wrapping sum, over the atoms, of mix(mix(mix(mix(rank + 1) + class + 1) + charge) + tag) and, over the valid
+    rows, of mix(mix((lower rank << 32 | higher rank) + 0xC2B2AE3D27D4EB4F) + order class)"""
+    classes, charges, bonds, tags = graph
+    h = 0
+    for a in range(len(classes)):
+        h += _mix(_mix(_mix(_mix(rank[a] + 1) + classes[a] + 1) + (charges[a] & _M64)) + tags[a])
+    for i, j, o in bonds:
+        lo, hi = min(rank[i], rank[j]), max(rank[i], rank[j])
+        h += _mix(_mix(((lo << 32) | hi) + _CANON_BOND) + o)
+    return h & _M64
+
+
+def canon_key(graph, rank, traces):
+    """(h, mix(mix(mix(n) + m) + sum over the levels l of mix(mix(mix(mix(l + 1) + rounds) + classes) + sum))): a HASH of the
+    relabelled graph, equal for equal graphs"""
+    t = sum(_mix(_mix(_mix(_mix(l + 1) + k) + c) + s) for l, (k, c, s) in enumerate(traces)) & _M64
+    return canon_leaf_hash(graph, rank), _mix(_mix(_mix(len(graph[0])) + len(graph[2])) + t)
+
+
+def canon_certificate(graph, rank):
+    """the relabelled graph itself: n, m, the packed word (charge << 5 | tag << 4 | class, as int32) of the atom at every rank, then
+    the (lower rank, higher rank, order class) triples in ascending order"""
+    classes, charges, bonds, tags = graph
+    n = len(classes)
+    at = [0] * n
+    for a in range(n):
+        w = ((charges[a] << 5) | (tags[a] << 4) | classes[a]) & 0xFFFFFFFF
+        at[rank[a]] = w - (1 << 32) if w >> 31 else w
+    tri = sorted((min(rank[i], rank[j]), max(rank[i], rank[j]), o) for i, j, o in bonds)
+    return [n, len(bonds)] + at + [v for t in tri for v in t]
+
+
+class _CanonStop(Exception):
+    def __init__(self, bit):
+        self.bit = bit
+
+
+def canonical_labelling(graph, max_tries=CANON_DEFAULT_TRIES, max_rounds=CANON_DEFAULT_ROUNDS):
+    """graph = (classes [n], charges [n], bonds [(i, j, order class)] 0-based, tags [n]) -> (rank [n], stats dict over CANON_COLUMNS,
+    traces [(rounds, classes, sum)] of the chosen leaf).  rank[a] is the canonical position of atom a: the ranks of the least leaf
+    under (trace_0, trace_1, .., h) of the search tree, certain unless the status says UNDECIDED (a budget ran out: the best leaf so
+    far, or the identity order before any leaf) or COLLISION (two 64-bit sums collided; the best leaf so far)."""
+    classes, charges, bonds, tags = graph
+    n = len(classes)
+    st = dict.fromkeys(CANON_COLUMNS, 0)
+    if n == 0:
+        return [], st, []
+    bi = np.array([q[0] for q in bonds], dtype=np.int64)
+    bj = np.array([q[1] for q in bonds], dtype=np.int64)
+    bo = np.array([q[2] for q in bonds], dtype=_U)
+    deg = [0] * n
+    for i, j, _ in bonds:
+        deg[i] += 1
+        deg[j] += 1
+    init = []
+    for a in range(n):
+        e = _mix(_mix(_mix(classes[a] + 1) + (charges[a] & _M64)) + deg[a])
+        init.append(_mix(e + _CANON_TAG * tags[a]) if tags[a] else e)
+    init = np.array(init, dtype=_U)
+
+    def one_round(ids, r):
+        if st["rounds"] >= max_rounds:
+            raise _CanonStop(CANON_UNDECIDED)
+        st["rounds"] += 1
+        acc = np.zeros(n, dtype=_U)
+        with np.errstate(over="ignore"):
+            np.add.at(acc, bi, _mixv(_mixv(ids[bj]) + bo))
+            np.add.at(acc, bj, _mixv(_mixv(ids[bi]) + bo))
+            return _mixv(_mixv(ids + _U(r)) + acc)
+
+    def individualise(ids, v, level):
+        ids[v] = _U(_mix(_mix(int(ids[v])) + _GOLD * (level + 1)))
+
+    def automorphism(ids, best_ids):
+        """the map by equal id, or None unless it keeps every label and the multiset of the bonds"""
+        where = {e: y for y, e in enumerate(best_ids.tolist())}
+        gamma = [where.get(e, -1) for e in ids.tolist()]
+        if any(y < 0 or (classes[x], charges[x], tags[x]) != (classes[y], charges[y], tags[y]) for x, y in enumerate(gamma)):
+            return None
+        key = lambda i, j, o: (min(i, j), max(i, j), o)
+        if sorted(key(gamma[i], gamma[j], o) for i, j, o in bonds) != sorted(key(i, j, o) for i, j, o in bonds):
+            return None
+        return gamma
+
+    def merge(parent, gamma):
+        """x ~ gamma(x): a union-find whose root is the least atom of the orbit, left flat"""
+        def find(x):
+            while parent[x] != x:
+                x = parent[x]
+            return x
+        for x, y in enumerate(gamma):
+            x, y = find(x), find(y)
+            if x != y:
+                parent[max(x, y)] = min(x, y)
+        for x in range(n):
+            parent[x] = find(x)
+
+    cur = [(0, 0, 0)] * n                               # the trace of every level of the current path
+    cell, cell_max, choice, nxt = [0] * n, [0] * n, [0] * n, [0] * n
+    orbit = [list(range(n)) for _ in range(CANON_ORBIT_LEVELS + 1)]
+    best = None                                         # (traces, choices, ids, h, rank) of the least leaf so far
+    less_from = None                                    # the level at which the path became less than the best; None: equal so far
+    try:
+        ids, r, level = init.copy(), 0, 0
+        prev = len(np.unique(ids))
+        mode, target = "refine", -1
+        while True:
+            if mode == "refine":
+                k = 0
+                while True:
+                    r += 1
+                    k += 1
+                    ids = one_round(ids, r)
+                    c = len(np.unique(ids))
+                    if c <= prev or k >= n:
+                        break
+                    prev = c
+                with np.errstate(over="ignore"):
+                    trace = (k, c, int(np.sum(_mixv(ids), dtype=_U)))
+                cur[level] = trace
+                st["levels_max"] = max(st["levels_max"], level)
+                mode, target = "back", level - 1
+                if best is not None and less_from is None:
+                    if trace > best[0][level]:
+                        st["pruned_trace"] += 1
+                        continue
+                    if trace < best[0][level]:
+                        less_from = level
+                if c == n:
+                    st["leaves"] += 1
+                    order = np.argsort(ids, kind="stable")
+                    rank = [0] * n
+                    for k2, a in enumerate(order.tolist()):
+                        rank[a] = k2
+                    h = canon_leaf_hash(graph, rank)
+                    if best is None or less_from is not None or h < best[3]:
+                        st["improved"] += best is not None
+                        best, less_from = (cur[:level + 1], choice[:level], ids.copy(), h, rank), None
+                    elif h == best[3]:
+                        gamma = automorphism(ids, best[2])
+                        if gamma is None:
+                            raise _CanonStop(CANON_COLLISION)
+                        st["automorphisms"] += 1
+                        target = next(l for l in range(level) if choice[l] != best[1][l])
+                        for l in range(min(target, CANON_ORBIT_LEVELS) + 1):
+                            merge(orbit[l], gamma)
+                    continue
+                if level + 1 >= n:                       # (only colliding hashes can get here)
+                    raise _CanonStop(CANON_COLLISION)
+                vals, counts = np.unique(ids, return_counts=True)
+                cell[level] = vals[counts > 1][0]
+                cell_max[level] = int(np.flatnonzero(ids == cell[level])[-1])
+                nxt[level] = 0
+                if level <= CANON_ORBIT_LEVELS:
+                    orbit[level] = list(range(n))
+                mode = "child"
+            if mode == "child":
+                v = None
+                for a in np.flatnonzero(ids == cell[level]).tolist():
+                    if a < nxt[level]:
+                        continue
+                    if level <= CANON_ORBIT_LEVELS and orbit[level][a] != a:
+                        st["pruned_orbit"] += 1
+                        continue
+                    v = a
+                    break
+                if v is None:
+                    mode, target = "back", level - 1
+                    continue
+                if st["tries"] >= max_tries:
+                    raise _CanonStop(CANON_UNDECIDED)
+                st["tries"] += 1
+                choice[level], nxt[level] = v, v + 1
+                individualise(ids, v, level)
+                prev = cur[level][1] + 1
+                level += 1
+                mode = "refine"
+                continue
+            # back: to the nearest level at or above `target` that still has an atom of its cell to try, its ids rebuilt by replay
+            while target >= 0 and nxt[target] > cell_max[target]:
+                target -= 1
+            if target < 0:
+                break
+            level = target
+            if less_from is not None and less_from > level:
+                less_from = None
+            ids, r = init.copy(), 0
+            for k in range(level + 1):
+                for _ in range(cur[k][0]):
+                    r += 1
+                    ids = one_round(ids, r)
+                if k < level:
+                    individualise(ids, choice[k], k)
+            mode = "child"
+    except _CanonStop as stop:
+        st["status"] |= stop.bit
+    if best is None:
+        return list(range(n)), st, []
+    return best[4], st, best[0]
 
 
 # the text rule's classes (DESIGN.md section 7): the symbols written without brackets, the ones that may be aromatic, and OUR valence

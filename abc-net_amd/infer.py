@@ -29,7 +29,7 @@ from .contract import HEADS, GraphRecords, alloc_targets, check_sparse_rasterize
 
 
 # the optional stages behind the NMS in launch order, each under the constructor flag that builds it
-STAGES = {"extractor": "extract", "assembler": "assemble", "texter": "molblocks", "smiler": "smiles", "scorer": "score_graphs",
+STAGES = {"extractor": "extract", "assembler": "assemble", "canonicalizer": "smiles_canonical", "texter": "molblocks", "smiler": "smiles", "scorer": "score_graphs",
           "similarity": "score_similarity", "identity": "score_identity", "evaluator": "evaluate"}
 
 
@@ -37,7 +37,8 @@ class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
                  assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
-                 score_similarity=False, molblocks=False, score_identity=False, smiles=False, smiles_stereo=False):
+                 score_similarity=False, molblocks=False, score_identity=False, smiles=False, smiles_stereo=False,
+                 smiles_canonical=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -81,10 +82,16 @@ class InferenceRunner:
         smiles_stereo (needs smiles=True): the same stage writes the tetrahedral centres that the predicted wedge bonds and the atom
         positions decide as `@` / `@@` (SmilesWriter(stereo=True)): smiles() is then `m.smiles(stereo=True)`, stereo_stats() says
         how many wedge rows there were and how many centres were marked, flat or unqualified.  The same two launches in the same place
+        smiles_canonical (needs smiles=True, refused with smiles_stereo=True): the canonical atom order of every assembled molecule
+        (ops.GraphCanonicalizer) in the same captured chain right after the assembler; the SMILES stage then reads the CANONICAL rows, so
+        smiles() is `m.smiles(canonical=True)`: equal strings if and only if equal graphs (this project's rule on a canonical order, not
+        RDKit's canonical SMILES).  molblocks=True keeps reading the assembler's rows: the mol block stays the reference's bytes.
+        canonical_stats() returns the search's rows (an UNDECIDED image is reported there), canonical_keys() the hash keys.  Stereo is
+        refused: wedge ownership and the drawn geometry are not in the invariant
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
-        from .ops import OMEGA_RULES, GraphAssembler, GraphIdentity, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, SmilesWriter, check_nms_heads
+        from .ops import OMEGA_RULES, GraphAssembler, GraphCanonicalizer, GraphIdentity, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, SmilesWriter, check_nms_heads
         if omega_rule not in OMEGA_RULES:
             raise ValueError("InferenceRunner: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
         self.omega_rule = omega_rule
@@ -98,6 +105,11 @@ class InferenceRunner:
                                  "assemble=True" % flag)
         if smiles_stereo and not smiles:
             raise ValueError("InferenceRunner(smiles_stereo=True) is a form of the SMILES stage: it needs smiles=True")
+        if smiles_canonical and not smiles:
+            raise ValueError("InferenceRunner(smiles_canonical=True) is a form of the SMILES stage: it needs smiles=True")
+        if smiles_canonical and smiles_stereo:
+            raise ValueError("InferenceRunner(smiles_canonical=True, smiles_stereo=True): a stereo text on the canonical order would not "
+                             "be canonical (wedge ownership and the drawn geometry are not in the invariant)")
         extract = bool(extract) or bool(assemble)
         check_nms_heads(model.heads, "InferenceRunner")
         if extract and tuple(model.heads) != HEADS:
@@ -138,7 +150,7 @@ class InferenceRunner:
         d.rho_abs, d.omega_mask = self.rho_abs.data_ptr(), self.omega_mask.data_ptr()
         self._nms = d
         # img2smiles2.py:113-191: compact candidate lists for the CPU graph-assembly stage, inside the same graph
-        self.extractor = self.assembler = self.texter = self.smiler = self.evaluator = self._rasterizer = None
+        self.extractor = self.assembler = self.canonicalizer = self.texter = self.smiler = self.evaluator = self._rasterizer = None
         with torch.cuda.device(dev):
             if extract:
                 self.extractor = PeakExtractor(lg, self.atom_mask, self.bond_mask, cap_atoms=cap_atoms, cap_bonds=cap_bonds,
@@ -148,7 +160,10 @@ class InferenceRunner:
                 self.assembler = GraphAssembler.from_extractor(self.extractor, cap_mol_bonds=cap_mol_bonds)
             if molblocks:
                 self.texter = MolBlockWriter.from_assembler(self.assembler)
-            if smiles:
+            if smiles_canonical:
+                self.canonicalizer = GraphCanonicalizer.from_assembler(self.assembler)
+                self.smiler = SmilesWriter(self.canonicalizer.rows())
+            elif smiles:
                 self.smiler = SmilesWriter.from_assembler(self.assembler, stereo=bool(smiles_stereo))
         if evaluate:
             if tuple(model.heads) != HEADS:
@@ -302,10 +317,24 @@ class InferenceRunner:
 
     def smiles(self):
         """a SMILES string of every image of the last step, written on the device: what `m.smiles()` gives for the m of
-        molecules(), None where that is None (host sync; needs smiles=True); with smiles_stereo=True it is `m.smiles(stereo=True)`"""
+        molecules(), None where that is None (host sync; needs smiles=True); with smiles_stereo=True it is `m.smiles(stereo=True)`,
+        with smiles_canonical=True `m.smiles(canonical=True)`"""
         smiler = self._need("smiler")
         with torch.cuda.device(self.dev):
             return smiler.smiles()
+
+    def canonical_stats(self):
+        """the canonical search of every image of the last step (GraphCanonicalizer.stats: the L.CANON_COLUMNS, `status` with the
+        L.CANON_UNDECIDED / L.CANON_COLLISION bits; host sync; needs smiles_canonical=True)"""
+        op = self._need("canonicalizer")
+        with torch.cuda.device(self.dev):
+            return op.stats()
+
+    def canonical_keys(self):
+        """the two hash words of every image's canonical graph (GraphCanonicalizer.keys; host sync; needs smiles_canonical=True)"""
+        op = self._need("canonicalizer")
+        with torch.cuda.device(self.dev):
+            return op.keys()
 
     def stereo_stats(self):
         """what became of the wedge rows of the last step (SmilesWriter.stereo_stats: marked, flat, unqualified, wedge_rows and the

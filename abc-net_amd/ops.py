@@ -854,6 +854,110 @@ class GraphIdentity(_RecordScorer):
         return out
 
 
+class GraphCanonicalizer:
+    """a canonical atom order for every image (csrc/graph_canon.hip, abc_canonical_order; the algorithm: include/abcnet_hip.h,
+    DESIGN.md section 7): the least leaf of an individualise-and-refine search over every branch of the graph GraphIdentity defines,
+    plus a tag on the atoms mol_implh lists.  The molecule side -- a GraphAssembler's rows, read in place -- also gets the CANONICAL
+    ROWS, the same molecule renumbered, which SmilesWriter and MolBlockWriter take like the assembler's: their text is then equal
+    if and only if the graphs are equal (this project's text rule on a canonical order, NOT RDKit's canonical SMILES).  The records
+    side orders the atoms of contract.GraphRecords.  Certain whenever the status says so: UNDECIDED (a budget ran out) and COLLISION
+    are reported per image, never hidden.  One launch, static buffers, graph-capture safe; orders(), stats(), keys() and
+    certificates() are the host syncs.  No CPU fallback (the host form is decode.Molecule.canonical())."""
+
+    def __init__(self, mol_counts=None, mol_atoms=None, mol_bonds=None, mol_implh=None, records=None, max_tries=None, max_rounds=None,
+                 cert=False, rows=True):
+        """a contract.MoleculeRows (GraphAssembler.rows) or its device tensors (mol_implh optional: no tags without it), OR
+        records=contract.GraphRecords.  max_tries: individualisations per image, max_rounds: refinement rounds per image, replays
+        included -- None: L.CANON_DEFAULT_TRIES / L.CANON_DEFAULT_ROUNDS.  cert: keep the relabelled graph of every image in .cert
+        (int32 [B, 2 + cap + 3 cap_bonds]).  rows (molecule side): write the canonical rows (cap_mol_bonds <= 4096)."""
+        who = "GraphCanonicalizer"
+        budgets = []
+        for name, v, default in (("max_tries", max_tries, L.CANON_DEFAULT_TRIES), ("max_rounds", max_rounds, L.CANON_DEFAULT_ROUNDS)):
+            v = default if v is None else int(v)
+            if not (1 <= v < 1 << 31):
+                raise ValueError("%s: %s must be 1..2^31-1, got %d" % (who, name, v))
+            budgets.append(v)
+        self.max_tries, self.max_rounds = budgets
+        if (mol_counts is None) == (records is None):
+            raise ValueError("%s: give the molecule rows or records=GraphRecords, one side" % who)
+        d = L.CanonDesc()
+        d.max_tries, d.max_rounds = budgets
+        self.records = self.out = None
+        if records is not None:
+            records = records.records if isinstance(records, _RecordScorer) else records
+            if not isinstance(records, GraphRecords):
+                raise ValueError("%s: records must be a GraphRecords, got %s" % (who, type(records).__name__))
+            if not 1 <= records.max_atoms <= L.MAX_SIM_ATOMS or records.max_bonds < 1:
+                raise ValueError("%s: max_atoms must be 1..%d and max_bonds >= 1, got %d, %d"
+                                 % (who, L.MAX_SIM_ATOMS, records.max_atoms, records.max_bonds))
+            records.fill(d)
+            d.B = records.B
+            self.records, self.keep = records, ()
+            self.B, self.cap, self.cap_bonds, dev = records.B, records.max_atoms, records.max_bonds, records.staging.device
+        else:
+            given = mol_counts.tensors[3] if isinstance(mol_counts, MoleculeRows) else mol_implh
+            want_rows = bool(rows)
+            mr = MoleculeRows.checked(who, mol_counts, mol_atoms, mol_bonds, mol_implh, max_cap_atoms=L.MAX_SIM_ATOMS,
+                                      need_implh=given is not None, max_cap_mol_bonds=L.MAX_SMILES_BONDS if want_rows else None)
+            mr.fill(d)
+            d.mol_implh = L.ptr(mr.tensors[3])
+            self.keep = mr.tensors
+            self.B, self.cap, self.cap_bonds, dev = mr.B, mr.cap_atoms, mr.cap_mol_bonds, mr.device
+            if want_rows:
+                out = tuple(torch.zeros(s, dtype=torch.int32, device=dev) for s in MoleculeRows.SHAPES(mr.B, mr.cap_atoms, mr.cap_mol_bonds))
+                self.out = MoleculeRows(*out)
+                d.out_counts, d.out_atoms, d.out_bonds, d.out_implh = (t.data_ptr() for t in out)
+        self.lib = L.load()
+        self.order = torch.full((self.B, self.cap), -1, dtype=torch.int32, device=dev)
+        self.stat = torch.zeros((self.B, len(L.CANON_COLUMNS)), dtype=torch.int32, device=dev)
+        self.key = torch.zeros((self.B, 2), dtype=torch.int64, device=dev)
+        self.cert = torch.full((self.B, 2 + self.cap + 3 * self.cap_bonds), -1, dtype=torch.int32, device=dev) if cert else None
+        d.order, d.stats, d.key, d.cert_out = self.order.data_ptr(), self.stat.data_ptr(), self.key.data_ptr(), L.ptr(self.cert)
+        self.d = d
+
+    @classmethod
+    def from_assembler(cls, asm, **kw):
+        return cls(asm.rows, **kw)
+
+    @classmethod
+    def from_records(cls, records, **kw):
+        return cls(records=records, **kw)
+
+    def run(self, stream=None):
+        """one launch (graph-capturable): order, stats, key, and cert / the canonical rows when they were asked for"""
+        L.check(self.lib.abc_canonical_order(C.byref(self.d), stream_or_current(stream)), "canonical_order")
+
+    def rows(self):
+        """the canonical rows of the last run as a contract.MoleculeRows on the device: what SmilesWriter(...) and
+        MolBlockWriter(...) take in place of GraphAssembler.rows"""
+        if self.out is None:
+            raise L.AbcNetHipError("GraphCanonicalizer.rows: built on graph records or with rows=False, there are no canonical rows")
+        return self.out
+
+    def orders(self):
+        """int32 [B, cap] on the host: orders()[b][k] is the 0-based row (for a record: the original record index) of the atom at
+        canonical position k, -1 beyond the image's atoms.  Host sync."""
+        return self.order.cpu()
+
+    def stats(self):
+        """the stats rows of the last run as a structured numpy array [B] with the int32 fields L.CANON_COLUMNS; `status` holds the
+        L.CANON_* bits.  Host sync."""
+        rows = np.ascontiguousarray(self.stat.cpu().numpy())
+        return rows.view(np.dtype([(c, np.int32) for c in L.CANON_COLUMNS])).reshape(self.B)
+
+    def keys(self):
+        """int64 [B, 2] on the host: two HASH words of the relabelled graph (equal for equal graphs; equal keys prove nothing --
+        certificates() does).  Host sync."""
+        return self.key.cpu()
+
+    def certificates(self):
+        """cert=True: int32 [B, 2 + cap + 3 cap_bonds] on the host, the relabelled graph of every image -- equal rows ARE equal
+        graphs.  Host sync."""
+        if self.cert is None:
+            raise L.AbcNetHipError("GraphCanonicalizer.certificates: the op was built without cert=True")
+        return self.cert.cpu()
+
+
 def timed(stream, marks, label, flops, nbytes, fn, operand_bytes=None):
     """profile(): fn() between a HIP event pair recorded on `stream` (a torch stream, the one fn launches on); the pair and the
     launch's accounting go to `marks`.  Returns what fn returned."""

@@ -1021,6 +1021,91 @@ int abc_graph_identity_update(const abc_graph_identity_desc* d, abc_stream_t str
 /* sizeof(abc_graph_identity_desc), for a binding's mirror struct (as abc_graph_similarity_desc_size) */
 int abc_graph_identity_desc_size(void);
 
+/* A CANONICAL ATOM ORDER per image: the order of the least leaf of an individualise-and-refine search that visits every branch
+ * (csrc/graph_canon.hip; its host form is decode.canonical_labelling, its test oracle tests/graphcanon_oracle.py; DESIGN.md section
+ * 7).  With it the text rules of abc_write_smiles and abc_write_molblocks, pure functions of atom order, graph and implicit-H list,
+ * write equal strings if and only if the graphs are equal.  NOT RDKit's canonical order.  One workgroup of 256 threads per image,
+ * uint64 wrapping arithmetic only, no global atomics, no allocation, no sync; every branch depends on values all threads hold alike,
+ * every index read from a row is range-checked, every loop is bounded by n, a budget or a capacity.
+ *   graph     ONE side of abc_graph_identity_update's graphs, built the same way (atom classes, order classes with wedges folded
+ *             to 1, a pair listed twice counts twice, mix, id_0, the round, indiv): the molecule rows when mol_counts is given
+ *             (every atom; EMPTY and TRUNCATED are copied into the status), else the graph records (only the atoms some valid bond
+ *             row names, in index order).  Giving both sides, or neither, is ABC_EINVAL;
+ *   tag       1 for a molecule atom that mol_implh lists (an entry in 1..n among the first mol_counts[2], clamped to cap_atoms), 0
+ *             otherwise, for records and when mol_implh is NULL.  id_0 = mix(id_0 + 0xD6E8FEB86659FD93 * tag) for tag != 0; with all
+ *             tags 0 the ids are the identity's, bit for bit;
+ *   tree      a node is a sequence of individualised atoms v_1 .. v_k; its colouring starts at id_0; for level 0 .. k: rounds (r
+ *             counts on through the levels) until one no longer raises the class count -- that round is counted, a level has at most
+ *             n -- then the level's TRACE (rounds, classes, wrapping sum of mix(id)), then id[v_(l+1)] = indiv(id, l).  The target
+ *             cell of a colouring that is not discrete is the non-singleton class of the least id VALUE; the children are its atoms
+ *             in index order; a leaf is a discrete colouring;
+ *   leaf      rank(a) = the number of atoms with a smaller id;
+ *             h = sum over the atoms of mix(mix(mix(mix(rank + 1) + class + 1) + charge) + tag)
+ *               + sum over the valid rows of mix(mix((lower rank << 32 | higher rank) + 0xC2B2AE3D27D4EB4F) + order class), wrapping;
+ *             trace and h are functions of the relabelled graph alone.  The canonical leaf is the LEAST under lexicographic
+ *             comparison of (trace_0, trace_1, .., h), a trace compared as its tuple, numbers ascending; the order is its ranks;
+ *   search    depth first, backtracking by replaying the choices from id_0, with two prunings that cannot change the result:
+ *             TRACE -- while the path has equalled the best leaf's traces, a level whose trace is greater drops the branch, one that
+ *             is less makes the path strictly better (no further comparison; its leaf replaces the best).  AUTOMORPHISM -- a leaf
+ *             whose whole key equals the best's is mapped onto it by equal id (through the LDS table) and the map VERIFIED as the
+ *             identity's leaf is: class, charge and tag of every atom, the multiset of (mapped end, mapped end, order class) by
+ *             counting.  Verified: gamma is an automorphism, certain whatever the hashes did; it fixes the stack's prefix through
+ *             the level p where the path left the best's; for every level l <= min(p, ABC_CANON_ORBIT_LEVELS) x ~ gamma(x) is merged
+ *             into that level's orbit table (a union-find over atoms in LDS, reset when the level is entered anew), and the search
+ *             returns at once to level p (the subtree left is the image of one already searched).  A child w of a node at a level
+ *             <= ABC_CANON_ORBIT_LEVELS is skipped when a lower-indexed atom of its cell is in w's orbit there; deeper levels prune
+ *             by trace only.  Not verified: two 64-bit sums collided -- the search stops with ABC_CANON_COLLISION;
+ *   budgets   max_rounds is checked before every round (replays included), max_tries before every individualisation; 0 selects the
+ *             defaults.  Running out sets ABC_CANON_UNDECIDED: the order is then that of the best leaf reached so far, a valid
+ *             permutation, or the identity order if no leaf was reached.  Chosen with the oracle at capacity: a 512-carbon ring takes
+ *             5 to 9 tries and 1483 to 2471 rounds (by numbering), a 512-carbon chain 2 tries and 1008 rounds; 170 disjoint C-C-C
+ *             and 64 disjoint benzenes need a descent per sibling below the orbit levels and END UNDECIDED at these defaults;
+ *   limits    cap_atoms (molecule side) or max_atoms (records) 1..512, else ABC_EUNSUPPORTED with nothing launched; bond rows stay
+ *             out of LDS; cap_mol_bonds <= 4096 when the canonical rows are requested (ABC_EUNSUPPORTED);
+ *   outputs   every word is written by every launch (cap = cap_atoms | max_atoms, cap_bonds = cap_mol_bonds | max_bonds):
+ *             order [B][cap]: order[b][k] = the 0-based row (for a record: the original record index) of the atom at canonical
+ *               position k, -1 beyond n;
+ *             stats [B][ABC_CANON_NCOL]: the status bits, then the counters leaves, tries, rounds, levels_max, pruned_trace,
+ *               pruned_orbit, automorphisms, improved (leaves that replaced a best one); an EMPTY image has only its status word;
+ *             key [B][2]: h of the chosen order, then mix(mix(mix(n) + m) + sum over the chosen leaf's levels l of
+ *               mix(mix(mix(mix(l + 1) + rounds_l) + classes_l) + sum_l)) -- a HASH: equal keys are necessary for equal graphs, not
+ *               sufficient;
+ *             cert_out (optional) [B][2 + cap + 3 cap_bonds]: n, m, the n atom words (charge << 5 | tag << 4 | class, wrapping: exact
+ *               for |charge| < 2^26) in rank order, the m triples (lower rank, higher rank, order class) ascending, then -1.  This is
+ *               the relabelled graph itself: equal cert_out IS equal graphs (0, 0, then -1 for an EMPTY image);
+ *             out_counts, out_atoms, out_bonds, out_implh (molecule side, optional, all four or none; they must not overlap the
+ *               inputs: ABC_EINVAL): the CANONICAL ROWS in the layouts of abc_assemble_desc -- mol_counts copied;
+ *               out_atoms[k] = mol_atoms[order[k]]; in the bond rows both ends are renumbered (1-based) in place, end 1 stays end 1 so
+ *               a wedge keeps its owner, order and source unchanged; the valid rows first, ascending by (lower end, higher end,
+ *               original row), the rows the graph skipped after them verbatim; mol_implh renumbered, the entries in 1..n ascending,
+ *               the others after them verbatim; zero past the (clamped) counts and for an EMPTY image.  */
+enum { ABC_CANON_DEFAULT_TRIES = 4096, ABC_CANON_DEFAULT_ROUNDS = 16384, ABC_CANON_ORBIT_LEVELS = 8 };
+enum abc_canon_status { ABC_CANON_EMPTY = 1, ABC_CANON_TRUNCATED = 2, ABC_CANON_UNDECIDED = 4, ABC_CANON_COLLISION = 8 };
+enum { ABC_CANON_STATUS = 0, ABC_CANON_LEAVES, ABC_CANON_TRIES, ABC_CANON_ROUNDS, ABC_CANON_LEVELS_MAX, ABC_CANON_PRUNED_TRACE,
+       ABC_CANON_PRUNED_ORBIT, ABC_CANON_AUTOMORPHISMS, ABC_CANON_IMPROVED, ABC_CANON_NCOL = 9 };
+typedef struct abc_canon_desc {
+    const int32_t* mol_counts;   /* [B][4]                 the molecule side (as abc_assemble_desc), or NULL */
+    const int32_t* mol_atoms;    /* [B][cap_atoms][5] */
+    const int32_t* mol_bonds;    /* [B][cap_mol_bonds][4] */
+    const int32_t* mol_implh;    /* optional: [B][cap_atoms], the tags */
+    const int32_t* rec_atoms;    /* [B][max_atoms][4]      the records side (as abc_graph_score_desc), or NULL */
+    const int32_t* rec_bonds;    /* [B][max_bonds][3] */
+    const int32_t* rec_counts;   /* [2][B] */
+    int32_t B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds;   /* the capacities of the side that is given */
+    int32_t max_tries, max_rounds;   /* >= 1, or 0: ABC_CANON_DEFAULT_TRIES / ABC_CANON_DEFAULT_ROUNDS; negative: ABC_EINVAL */
+    int32_t* order;              /* [B][cap] */
+    int32_t* stats;              /* [B][ABC_CANON_NCOL] */
+    int64_t* key;                /* [B][2] */
+    int32_t* cert_out;           /* optional: [B][2 + cap + 3 cap_bonds] */
+    int32_t* out_counts;         /* optional, molecule side: the canonical rows, [B][4] */
+    int32_t* out_atoms;          /* [B][cap_atoms][5] */
+    int32_t* out_bonds;          /* [B][cap_mol_bonds][4] */
+    int32_t* out_implh;          /* [B][cap_atoms] */
+} abc_canon_desc;
+int abc_canonical_order(const abc_canon_desc* d, abc_stream_t stream);
+/* sizeof(abc_canon_desc), for a binding's mirror struct (as abc_graph_identity_desc_size) */
+int abc_canon_desc_size(void);
+
 /* The mol block text of the assembled molecules (generate_smiles.py:18-105), written on the device from the rows of
  * abc_assemble_graphs, read in place: the bytes that go into Chem.MolFromMolBlock, one copy per batch (csrc/molblock.hip; the
  * contract in full: DESIGN.md section 7).  Two launches on the stream, integers only, no atomics on global memory, no allocation,

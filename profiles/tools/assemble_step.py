@@ -33,6 +33,12 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            abc_write_smiles, its step against the plain stage's in the same alternated blocks, smiles() against
            Molecule.smiles(stereo=True), and what became of the fixture's wedge rows (stereo_stats: wedge rows, marked, flat,
            unqualified)
+           --canonical: the canonical atom order (csrc/graph_canon.hip, InferenceRunner(smiles=True, smiles_canonical=True)) under
+           BOTH omega rules in this one process -- abc_canonical_order alone beside abc_write_smiles, the step with the stage
+           against the same step without it (alternated blocks), the images left UNDECIDED, the largest work of an image, smiles()
+           against Molecule.smiles(canonical=True), and how many of the 64 strings equal the canonical string of their annotation
+           (the identity's `same` of profiles/r15_identity.md, position-free: 0 under raw, 7 under peaks).  Writes what it measured
+           to profiles/r21_canonical.md
 
   --omega-rule {raw,peaks}: the extractor's candidate rule of every runner built here (InferenceRunner(omega_rule=...): "raw" is
            img2smiles2.py:139, "peaks" img2smiles.py:139 / img2smiles3.py:140); `graphs` and `score` then also report the candidates
@@ -40,7 +46,7 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--canonical]
 """
 import argparse
 import json
@@ -325,6 +331,87 @@ def part_smiles_stereo(r, plain, reps, iters):
           "method": "device events around %d back-to-back calls of two launches each (launch gaps included), alternated" % iters})
 
 
+def part_smiles_canonical(m, x, notes, steps, warmup, reps=30, iters=200):
+    """--canonical: both omega rules in this process; the lines are printed and written to profiles/r21_canonical.md"""
+    import numpy as np
+    from abcnet_amd import _lib as L
+    from abcnet_amd.decode import ATOM_SYMBOLS, Molecule
+    from abcnet_amd.raster import parse_graph
+    global RULE
+    lines, keep = [], RULE
+
+    def note(d):
+        lines.append(dict(d, omega_rule=RULE))
+        emit(d)
+    # the canonical string of every annotation: its graph record as a molecule (only bonded atoms, no listed atom)
+    want = []
+    for atoms_s, bonds_s in notes:
+        a, q = parse_graph(atoms_s, bonds_s, h=S // 4)
+        T = sorted({int(e) for row in q for e in row[:2]})
+        num = {t: k + 1 for k, t in enumerate(T)}
+        mol = Molecule([ATOM_SYMBOLS[int(a[t][2])] if 0 <= int(a[t][2]) < 14 else "?" for t in T], [int(a[t][3]) for t in T], [0] * len(T),
+                       [[int(a[t][0]), int(a[t][1])] for t in T], [[num[int(i)], num[int(j)]] for i, j, _ in q], [int(o) for _, _, o in q], [])
+        try:
+            want.append(mol.smiles(canonical=True))
+        except ValueError:
+            want.append(None)
+    for RULE in ("raw", "peaks"):
+        rs = {}
+        for name, kw in (("assemble+smiles", dict(smiles=True)), ("assemble+smiles+canonical", dict(smiles=True, smiles_canonical=True))):
+            r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, omega_rule=RULE, **kw)
+            r.load_batch(x.to("cuda"))
+            for _ in range(2):
+                r.step()
+            rs[name] = r
+        torch.cuda.synchronize()
+        r, plain = rs["assemble+smiles+canonical"], rs["assemble+smiles"]
+        st = r.canonical_stats()
+        refused = sum(bool(s & ~3) for s in r.smiler.status())
+        mols = r.molecules()
+        out = {"part": "smiles", "what": "canonical fixture", "batch": B, "refused_images": refused,
+               "undecided_images": int(((st["status"] & L.CANON_UNDECIDED) != 0).sum()), "collision_images": int(((st["status"] & L.CANON_COLLISION) != 0).sum()),
+               "molecules": sum(mol is not None for mol in mols), "molecules_with_a_listed_atom": sum(mol is not None and bool(mol.implicit_hs) for mol in mols)}
+        out.update({c + "_max": int(st[c].max()) for c in ("leaves", "tries", "rounds", "levels_max", "automorphisms")})
+        if not refused:
+            got = r.smiles()
+            host = [mol.smiles(canonical=True) if mol is not None else None for mol in mols]
+            wall = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                r.smiles()
+                wall.append((time.perf_counter() - t0) * 1000)
+            out.update({"equal_to_host_form": got == host, "texts_that_differ_from_plain": sum(a != b for a, b in zip(got, plain.smiles())),
+                        "distinct_strings": len({t for t in got if t is not None}),
+                        "strings_equal_to_their_annotation": sum(t is not None and t == w for t, w in zip(got, want)),
+                        # (the identity does not read the implicit-H list; the canonical order does: the same count without it)
+                        "equal_to_their_annotation_without_listed_atoms": sum(
+                            mol is not None and Molecule(mol.symbols, mol.charges, mol.hs, mol.positions, mol.bonds, mol.orders, []).smiles(canonical=True) == w
+                            for mol, w in zip(mols, want)),
+                        "smiles_ms": round(statistics.median(wall), 4)})
+        note(out)
+        us = [(launch_us(r.canonicalizer.run, iters), launch_us(r.smiler.run, iters), launch_us(plain.smiler.run, iters)) for _ in range(3)]
+        note({"part": "smiles", "what": "canonical launch", "batch": B, "canonical_order_us_per_launch": [round(a, 2) for a, _, _ in us],
+              "smiles_on_canonical_rows_us_per_call": [round(b, 2) for _, b, _ in us], "plain_smiles_us_per_call": [round(c, 2) for _, _, c in us],
+              "method": "device events around %d back-to-back calls (launch gaps included), alternated" % iters})
+        med = step_blocks(rs, steps, warmup, "smiles")
+        note({"part": "smiles", "what": "canonical step", "ms_per_step": {k: round(v, 4) for k, v in med.items()},
+              "canonical_minus_smiles_ms": round(med["assemble+smiles+canonical"] - med["assemble+smiles"], 4)})
+        del rs, r, plain
+    RULE = keep
+    path = os.path.join(ROOT, "profiles", "r21_canonical.md")
+    with open(path, "w") as f:
+        f.write("# The canonical atom order on the trained fixture (b%d @ %d x %d, drawn_molecules(seed 777))\n\n" % (B, S, S))
+        f.write("`python profiles/tools/assemble_step.py --parts smiles --canonical`, one process, both omega rules; the step with the stage "
+                "against the same commit's step without it, the launch beside the plain SMILES stage's two launches.  "
+                "`strings_equal_to_their_annotation` is position-free; a listed implicit hydrogen is part of this graph and not of the identity's, "
+                "so it is `equal_to_their_annotation_without_listed_atoms` that is the identity's `same` of r15_identity.md (0 under raw, 7 under "
+                "peaks).\n\n```\n")
+        for d in lines:
+            f.write(json.dumps(d) + "\n")
+        f.write("```\n")
+    print("wrote", path, flush=True)
+
+
 def annotated_graph(atoms_s, bonds_s):
     atoms = {}
     for a in atoms_s.strip(";").split(";"):
@@ -459,6 +546,7 @@ def main():
     ap.add_argument("--parts", default="step,launch,host,graphs")
     ap.add_argument("--omega-rule", choices=("raw", "peaks"), default="raw")
     ap.add_argument("--stereo", action="store_true", help="the smiles part: the stereo form beside the plain one")
+    ap.add_argument("--canonical", action="store_true", help="the smiles part: the canonical atom order, under both omega rules")
     a = ap.parse_args()
     global RULE
     RULE = a.omega_rule
@@ -492,6 +580,8 @@ def main():
         part_text(m, x, a.steps, a.warmup)
     if "smiles" in parts:
         part_smiles(m, x, a.steps, a.warmup, stereo=a.stereo)
+        if a.canonical:
+            part_smiles_canonical(m, x, notes, a.steps, a.warmup)
 
 
 if __name__ == "__main__":
