@@ -4,8 +4,8 @@
 // only if the graphs are equal.  The contract is in include/abcnet_hip.h (abc_canon_desc) and DESIGN.md section 7, its host form
 // decode.canonical_labelling, its oracle tests/graphcanon_oracle.py.
 //
-// One workgroup per image; integers only (uint64, wrapping).  The graph is ONE side of the identity's, built the same way (mol_rows.hpp,
-// graph_ids.hpp), id_0, the round, the class count and indiv are graph_refine.hpp's.
+// One workgroup per image; integers only (uint64, wrapping).  The graph is ONE side of the identity's, built by the same code: the bond
+// rows, stage (A) with id_0, the round, the class count and indiv are graph_refine.hpp's.
 //
 //   (a) a node is the sequence choice[0 .. level); REFINE runs the level's rounds (r counts on) until one no longer raises the class
 //       count, records the trace (rounds, classes, sum of mix(id)) and compares it with the best leaf's while the path has equalled it:
@@ -96,26 +96,15 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
     static_assert((int)ABC_CANON_EMPTY == (int)ABC_MOL_EMPTY && (int)ABC_CANON_TRUNCATED == (int)ABC_MOL_TRUNCATED, "the two bits are copied");
 
     // row `tid`, kept through every round (a record row's ends become numbers in T below)
-    int pi = 0, pj = 0;
-    const bool pv = tid < nrows && (mol ? mol_ends(pb, tid, na, pi, pj) : rec_ends(rb, tid, nt, pi, pj));
-    const u64 po = pv ? (u64)bond_class(mol ? pb[tid * MOL_BOND_W + 2] : rb[tid * REC_BOND_W + 2]) : 0;
+    BondRow own = {false, 0, 0, 0};
+    if (tid < nrows) own = mol ? mol_row(pb, tid, na) : rec_row(rb, tid, nt);
 
-    // ---- degrees (in acc), the atoms of the graph, tags, id_0
+    // ---- (A) degrees (in acc), the atoms of the graph, tags, id_0 (graph_refine.hpp, for the side that was given)
     if (tid == 0) cnt[0] = 0, zero_at = -1;
-    for (int a = tid; a < MAX_ATOMS; a += GT) acc[a] = 0, tag[a] = 0, remap[a] = -1;
+    for (int a = tid; a < MAX_ATOMS; a += GT) acc[a] = 0, tag[a] = 0;
     __syncthreads();
     {
-        int valid = pv, i, j;
-        if (pv) {
-            atomicAdd(&acc[pi], 1ull);
-            atomicAdd(&acc[pj], 1ull);
-        }
-        for (int q = tid + GT; q < nrows; q += GT) {
-            if (!(mol ? mol_ends(pb, q, na, i, j) : rec_ends(rb, q, nt, i, j))) continue;
-            ++valid;
-            atomicAdd(&acc[i], 1ull);
-            atomicAdd(&acc[j], 1ull);
-        }
+        const int valid = mol ? refine_degrees_mol(tid, pb, nrows, na, own, acc) : refine_degrees_rec(tid, rb, nrows, nt, own, acc);
         if (valid) atomicAdd(cnt, valid);
         for (int k = tid; k < nlisted; k += GT) {
             const int e = ph[k];
@@ -126,44 +115,30 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
     const int nvalid = cnt[0];
     int n = na;
     if (mol) {
-        for (int a = tid; a < na; a += GT) {
-            const u64 e = id0(atom_class(pa[a * ATOM_W + 2]), pa[a * ATOM_W + 3], acc[a]);
-            init[a] = tag[a] ? mix(e + TAG_K) : e;
+        refine_id0_mol(tid, pa, na, acc, init);
+        for (int a = tid; a < na; a += GT) {      // (by the thread that wrote id_0 and read the degree: acc becomes the round's sums)
+            if (tag[a]) init[a] = mix(init[a] + TAG_K);
             orig[a] = (u16)a;
+            acc[a] = 0;
         }
     } else {
-        const int a0 = 2 * tid, a1 = 2 * tid + 1;
-        const u64 deg0 = a0 < nt ? acc[a0] : 0, deg1 = a1 < nt ? acc[a1] : 0;
-        const unsigned f0 = deg0 != 0, f1 = deg1 != 0;
-        unsigned total;
-        const unsigned r0 = block_excl_scan<GT>(f0 + f1, wt, &total), r1 = r0 + f0;
-        n = (int)total;
-        if (f0) remap[a0] = (int)r0, orig[r0] = (u16)a0, init[r0] = id0(atom_class(ra[a0 * REC_ATOM_W + 2]), ra[a0 * REC_ATOM_W + 3], deg0);
-        if (f1) remap[a1] = (int)r1, orig[r1] = (u16)a1, init[r1] = id0(atom_class(ra[a1 * REC_ATOM_W + 2]), ra[a1 * REC_ATOM_W + 3], deg1);
+        n = refine_number_rec(tid, ra, nt, acc, wt, remap, orig, init);
     }
-    __syncthreads();                     // (every degree was read: acc becomes the round's sums)
-    for (int a = tid; a < MAX_ATOMS; a += GT) acc[a] = 0;
-    if (!mol && pv) pi = remap[pi], pj = remap[pj];      // (both in T: this row is one of those that put them there)
+    __syncthreads();                     // (remap, orig and id_0 are written)
+    if (!mol) renumber(own, remap);
     for (int a = tid; a < n; a += GT) cur[a] = init[a];
     __syncthreads();
 
-    // class, charge of an atom of the graph; a bond row as (atom, atom, order class) of the graph, false for a row that names no pair
+    // class, charge of an atom of the graph; a bond row of the graph
     auto cls_of = [&](int a) __attribute__((always_inline)) { return atom_class(mol ? pa[a * ATOM_W + 2] : ra[orig[a] * REC_ATOM_W + 2]); };
     auto chg_of = [&](int a) __attribute__((always_inline)) { return mol ? pa[a * ATOM_W + 3] : ra[orig[a] * REC_ATOM_W + 3]; };
-    auto row = [&](int q, int& i, int& j, int& o) __attribute__((always_inline)) {
-        if (mol) {
-            if (!mol_ends(pb, q, na, i, j)) return false;
-            o = bond_class(pb[q * MOL_BOND_W + 2]);
-        } else {
-            if (!rec_ends(rb, q, nt, i, j)) return false;
-            i = remap[i], j = remap[j];
-            o = bond_class(rb[q * REC_BOND_W + 2]);
-        }
-        return true;
-    };
+    auto row = [&](int q) __attribute__((always_inline)) { return mol ? mol_row(pb, q, na) : rec_row(rb, q, nt, remap); };
     auto round = [&](u64 r) __attribute__((always_inline)) {
-        if (mol) refine_round_mol(tid, cur, acc, pb, nrows, na, n, r, pv, pi, pj, po);
-        else refine_round_rec(tid, cur, acc, rb, nrows, nt, remap, n, r, pv, pi, pj, po);
+        if (mol) refine_add_mol(tid, cur, acc, pb, nrows, na, own);
+        else refine_add_rec(tid, cur, acc, rb, nrows, nt, remap, own);
+        __syncthreads();
+        refine_finish(tid, cur, acc, n, r);
+        __syncthreads();
     };
     u64 shared = ~0ull;
     int zeros = 0;
@@ -173,13 +148,13 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
     // h of the relabelled graph under the ranks `rank` (uniform)
     auto leaf_hash = [&](const u16* rank) __attribute__((always_inline)) {
         u64 h = 0;
-        int i, j, o;
         for (int a = tid; a < n; a += GT)
             h += mix(mix(mix(mix((u64)rank[a] + 1) + (u64)(cls_of(a) + 1)) + (u64)(long long)chg_of(a)) + (u64)tag[a]);
         for (int q = tid; q < nrows; q += GT) {
-            if (!row(q, i, j, o)) continue;
-            const u64 lo = min((int)rank[i], (int)rank[j]), hi = max((int)rank[i], (int)rank[j]);
-            h += mix(mix(((lo << 32) | hi) + BOND_K) + (u64)o);
+            const BondRow e = row(q);
+            if (!e.v) continue;
+            const u64 lo = min((int)rank[e.i], (int)rank[e.j]), hi = max((int)rank[e.i], (int)rank[e.j]);
+            h += mix(mix(((lo << 32) | hi) + BOND_K) + (u64)e.o);
         }
         return block_reduce(h, wu, [](u64 u, u64 v) { return u + v; });
     };
@@ -284,16 +259,18 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
                         bool ok = sum_int(bad) == 0;      // (gam is written: the reduction synchronises)
                         if (ok) {
                             // the multiset of the mapped rows is the multiset of the rows, by counting
-                            int common = 0, i, j, o, i2, j2, o2;
+                            int common = 0;
                             for (int q = tid; q < nrows; q += GT) {
-                                if (!row(q, i, j, o)) continue;
-                                const int gi = gam[i], gj = gam[j], lo = min(gi, gj), hi = max(gi, gj);
+                                const BondRow e = row(q);
+                                if (!e.v) continue;
+                                const int gi = gam[e.i], gj = gam[e.j], lo = min(gi, gj), hi = max(gi, gj);
                                 int before = 0, there = 0;
                                 for (int q2 = 0; q2 < nrows; ++q2) {
-                                    if (!row(q2, i2, j2, o2) || o2 != o) continue;
-                                    const int gi2 = gam[i2], gj2 = gam[j2];
+                                    const BondRow e2 = row(q2);
+                                    if (!e2.v || e2.o != e.o) continue;
+                                    const int gi2 = gam[e2.i], gj2 = gam[e2.j];
                                     before += q2 < q && min(gi2, gj2) == lo && max(gi2, gj2) == hi;
-                                    there += min(i2, j2) == lo && max(i2, j2) == hi;
+                                    there += min(e2.i, e2.j) == lo && max(e2.i, e2.j) == hi;
                                 }
                                 common += before < there;
                             }
@@ -486,22 +463,23 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
         }
     }
     // the bond rows, by counting: the place of a row among the certificate's triples and among the canonical rows
-    int i, j, o, i2, j2, o2;
     for (int q = tid; q < nrows; q += GT) {
-        const bool valid = row(q, i, j, o);
-        const int bi = valid ? brank[i] : 0, bj = valid ? brank[j] : 0, lo = min(bi, bj), hi = max(bi, bj);
+        const BondRow e = row(q);
+        const bool valid = e.v;
+        const int bi = valid ? brank[e.i] : 0, bj = valid ? brank[e.j] : 0, lo = min(bi, bj), hi = max(bi, bj);
         const int pair = lo * MAX_ATOMS + hi;
         int at_cert = 0, at_rows = 0, valid_before = 0;
         for (int q2 = 0; q2 < nrows; ++q2) {
-            if (!row(q2, i2, j2, o2)) continue;
+            const BondRow e2 = row(q2);
+            if (!e2.v) continue;
             valid_before += q2 < q;
-            const int bi2 = brank[i2], bj2 = brank[j2], pair2 = min(bi2, bj2) * MAX_ATOMS + max(bi2, bj2);
+            const int bi2 = brank[e2.i], bj2 = brank[e2.j], pair2 = min(bi2, bj2) * MAX_ATOMS + max(bi2, bj2);
             at_rows += pair2 < pair || (pair2 == pair && q2 < q);
-            at_cert += pair2 < pair || (pair2 == pair && (o2 < o || (o2 == o && q2 < q)));
+            at_cert += pair2 < pair || (pair2 == pair && (e2.o < e.o || (e2.o == e.o && q2 < q)));
         }
         if (cert != nullptr && valid) {
             int* tr = cert + 2 + n + 3 * at_cert;
-            tr[0] = lo, tr[1] = hi, tr[2] = o;
+            tr[0] = lo, tr[1] = hi, tr[2] = e.o;
         }
         if (want_rows) {
             const int* src = pb + q * MOL_BOND_W;

@@ -73,77 +73,44 @@ __global__ __launch_bounds__(GT) void graph_ident_kernel(const abc_graph_identit
     const int max_rounds = d.max_rounds > 0 ? d.max_rounds : ABC_IDENT_DEFAULT_ROUNDS;
 
     // row `tid` of each side, kept through every round
-    int pi = 0, pj = 0, ti = 0, tj = 0;
-    const bool pv = tid < nb && mol_ends(pb, tid, na, pi, pj), tv = tid < m && rec_ends(rb, tid, nt, ti, tj);
-    const u64 po = pv ? (u64)bond_class(pb[tid * MOL_BOND_W + 2]) : 0, to = tv ? (u64)bond_class(rb[tid * REC_BOND_W + 2]) : 0;
+    const BondRow none = {false, 0, 0, 0};
+    const BondRow prow = tid < nb ? mol_row(pb, tid, na) : none;
+    BondRow trow = tid < m ? rec_row(rb, tid, nt) : none;
 
-    // ---- (A) degrees, T, id_0 (as graph_sim.hip; the molecule's degrees in cur[1], the record's in acc)
+    // ---- (A) degrees, T, id_0 (graph_refine.hpp; the molecule's degrees in cur[1] to save LDS, the record's in acc)
     if (tid < 2) cnt[tid] = 0;
     for (int a = tid; a < MAX_ATOMS; a += GT) cur[1][a] = acc[a] = 0;
     __syncthreads();
     {
-        int valid_p = pv, valid_t = tv, i, j;
-        if (pv) {
-            atomicAdd(&cur[1][pi], 1ull);
-            atomicAdd(&cur[1][pj], 1ull);
-        }
-        if (tv) {
-            atomicAdd(&acc[ti], 1ull);
-            atomicAdd(&acc[tj], 1ull);
-        }
-        for (int q = tid + GT; q < nb; q += GT) {
-            if (!mol_ends(pb, q, na, i, j)) continue;
-            ++valid_p;
-            atomicAdd(&cur[1][i], 1ull);
-            atomicAdd(&cur[1][j], 1ull);
-        }
-        for (int k = tid + GT; k < m; k += GT) {
-            if (!rec_ends(rb, k, nt, i, j)) continue;
-            ++valid_t;
-            atomicAdd(&acc[i], 1ull);
-            atomicAdd(&acc[j], 1ull);
-        }
+        const int valid_p = refine_degrees_mol(tid, pb, nb, na, prow, cur[1]), valid_t = refine_degrees_rec(tid, rb, m, nt, trow, acc);
         if (valid_p) atomicAdd(cnt + 0, valid_p);
         if (valid_t) atomicAdd(cnt + 1, valid_t);
     }
     __syncthreads();
-    const int a0 = 2 * tid, a1 = 2 * tid + 1;
-    const u64 deg0 = a0 < nt ? acc[a0] : 0, deg1 = a1 < nt ? acc[a1] : 0;
-    const unsigned f0 = deg0 != 0, f1 = deg1 != 0;
-    unsigned total;
-    const unsigned r0 = block_excl_scan<GT>(f0 + f1, wt, &total), r1 = r0 + f0;
-    const int n_t = (int)total;          // |T|
-    for (int a = tid; a < na; a += GT) cur[0][a] = id0(atom_class(pa[a * ATOM_W + 2]), pa[a * ATOM_W + 3], cur[1][a]);
-    __syncthreads();                     // (the molecule's degrees are read: cur[1] becomes the record's ids)
-    remap[a0] = f0 ? (int)r0 : -1;
-    remap[a1] = f1 ? (int)r1 : -1;
-    if (f0) orig[r0] = a0, cur[1][r0] = init[r0] = id0(atom_class(ra[a0 * REC_ATOM_W + 2]), ra[a0 * REC_ATOM_W + 3], deg0);
-    if (f1) orig[r1] = a1, cur[1][r1] = init[r1] = id0(atom_class(ra[a1 * REC_ATOM_W + 2]), ra[a1 * REC_ATOM_W + 3], deg1);
-    acc[a0] = acc[a1] = 0;               // (every degree was read before the scan's barriers)
+    refine_id0_mol(tid, pa, na, cur[1], cur[0]);
+    // (id_0 of the record goes into init alone: cur[1], the molecule's degrees until here, becomes the record's ids when the search
+    // begins, by replay(0))
+    const int n_t = refine_number_rec(tid, ra, nt, acc, wt, remap, orig, init);      // |T|
     __syncthreads();
-    if (tv) ti = remap[ti], tj = remap[tj];      // (both in T: this row is one of those that put them there)
+    renumber(trow, remap);
     const int valid_p = cnt[0], valid_t = cnt[1];
     const bool size_equal = !empty && na == n_t && valid_p == valid_t;
     const int n = na;
 
-    // one round of side `s` (uniform); acc is zero on entry and on exit.  (The bodies of these three are graph_refine.hpp's, expanded
-    // here: see there)
+    // one round of side `s` (uniform); acc is zero on entry and on exit
     auto round = [&](int s, u64 r) __attribute__((always_inline)) {
-        u64* id = cur[s];
-        int i, j;
-        if (s == 0) {
-            REFINE_ROUND_MOL(id, acc, pb, nb, na, tid, pv, pi, pj, po, i, j)
-        } else {
-            REFINE_ROUND_REC(id, acc, rb, m, nt, remap, tid, tv, ti, tj, to, i, j)
-        }
-        REFINE_ROUND_END(id, acc, n, r, tid)
+        if (s == 0) refine_add_mol(tid, cur[0], acc, pb, nb, na, prow);
+        else refine_add_rec(tid, cur[1], acc, rb, m, nt, remap, trow);
+        __syncthreads();
+        refine_finish(tid, cur[s], acc, n, r);
+        __syncthreads();
     };
     // the number of distinct ids, exactly; `shared` keeps this thread's least id two atoms share, `zeros` (uniform) the number of
     // ids that are 0, for the cell of the level
     u64 shared = ~0ull;
     int zeros = 0;
-    auto classes = [&](const u64* id) __attribute__((always_inline)) { REFINE_CLASSES(id, n, table, SLOTS, wi, tid, shared, zeros) };
-    auto multiset_sum = [&](const u64* id) __attribute__((always_inline)) { REFINE_MULTISET_SUM(id, n, wu, tid) };
+    auto classes = [&](const u64* id) __attribute__((always_inline)) { return refine_classes<SLOTS>(tid, id, n, table, wi, shared, zeros); };
+    auto multiset_sum = [&](const u64* id) __attribute__((always_inline)) { return refine_multiset_sum(tid, id, n, wu); };
 
     int result = 0, levels = 0, tries = 0, backtracks = 0, rounds = 0;
     if (empty) {
@@ -229,19 +196,21 @@ __global__ __launch_bounds__(GT) void graph_ident_kernel(const abc_graph_identit
                        pa[a * ATOM_W + 3] != ra[o * REC_ATOM_W + 3];
             }
             if (block_reduce(bad, wi, [](int u, int v) { return u + v; })) return false;
-            int common = 0, i, j;
+            int common = 0;
             for (int q = tid; q < nb; q += GT) {
-                if (!mol_ends(pb, q, na, i, j)) continue;
-                const int lo = min(mapv[i], mapv[j]), hi = max(mapv[i], mapv[j]), o = bond_class(pb[q * MOL_BOND_W + 2]);
+                const BondRow e = mol_row(pb, q, na);
+                if (!e.v) continue;
+                const int lo = min(mapv[e.i], mapv[e.j]), hi = max(mapv[e.i], mapv[e.j]);
                 int before = 0, there = 0;
                 for (int q2 = 0; q2 < q; ++q2) {
-                    if (!mol_ends(pb, q2, na, i, j)) continue;
-                    before += min(mapv[i], mapv[j]) == lo && max(mapv[i], mapv[j]) == hi && bond_class(pb[q2 * MOL_BOND_W + 2]) == o;
+                    const BondRow e2 = mol_row(pb, q2, na);
+                    if (!e2.v) continue;
+                    before += min(mapv[e2.i], mapv[e2.j]) == lo && max(mapv[e2.i], mapv[e2.j]) == hi && e2.o == e.o;
                 }
                 for (int k = 0; k < m; ++k) {
-                    if (!rec_ends(rb, k, nt, i, j)) continue;
-                    i = remap[i], j = remap[j];
-                    there += min(i, j) == lo && max(i, j) == hi && bond_class(rb[k * REC_BOND_W + 2]) == o;
+                    const BondRow t = rec_row(rb, k, nt, remap);
+                    if (!t.v) continue;
+                    there += min(t.i, t.j) == lo && max(t.i, t.j) == hi && t.o == e.o;
                 }
                 common += before < there;
             }

@@ -1,5 +1,6 @@
-// The atom ids of the position-free graph scores (graph_sim.hip, graph_ident.hip): one definition of the hash, of the order class of
-// a bond code and of id_0, so that the two kernels cannot drift apart (the contract: include/abcnet_hip.h, abc_graph_similarity_desc).
+// The atom ids of the position-free graph kernels (graph_sim.hip, graph_ident.hip, graph_canon.hip): one definition of the hash, of the
+// order class of a bond code and of id_0, so that the three kernels cannot drift apart (the contract: include/abcnet_hip.h,
+// abc_graph_similarity_desc).
 #pragma once
 #include <hip/hip_runtime.h>
 

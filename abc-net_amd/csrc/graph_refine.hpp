@@ -1,11 +1,12 @@
-// Individualise-and-refine on the graphs of graph_ids.hpp, for one workgroup of 256 threads per image: what the identity test
-// (graph_ident.hip) and the canonical order (graph_canon.hip) share, so that the two cannot drift apart -- the id of an individualised
-// atom, the workgroup reduction, one round over the rows of either side, and the exact class count through an LDS table.
+// Individualise-and-refine on the graphs of graph_ids.hpp, for one workgroup of 256 threads per image: what the environment similarity
+// (graph_sim.hip), the identity test (graph_ident.hip) and the canonical order (graph_canon.hip) share, so that the three cannot drift
+// apart -- a bond row as a thread holds it, stage (A) (degrees, the numbering of a record's bonded atoms, id_0), the round in its two
+// halves, the id of an individualised atom, the workgroup reduction, and the exact class count through an LDS table.
 //
-// The round and the class count are stated once as statement macros, REFINE_*, and wrapped in functions below.  graph_ident.hip expands
-// the macros inside the lambdas it always had: through the functions its kernel computes the same but is laid out differently, and that
-// kernel is held to the instructions it had.  New code calls the functions.
+// Every piece is a function that works on the caller's LDS arrays.  None but block_reduce, refine_number_rec (its scan), refine_classes
+// and refine_multiset_sum (their reductions) synchronises: the callers place the barriers, and say why there.
 #pragma once
+#include "block_scan.hpp"
 #include "mol_rows.hpp"
 #include "graph_ids.hpp"
 
@@ -27,97 +28,169 @@ __device__ inline T block_reduce(T v, T* wt, F f) {
 }
 static_assert(REFINE_NW == 4, "block_reduce folds four waves");
 
-// The sums of one round over molecule rows into acc (zero on entry).  Row `tid` is held by the caller (pv: it is valid, its ends pi and
-// pj, its order class po); the rows past the workgroup are read again.  i, j: two int lvalues of the caller
-#define REFINE_ROUND_MOL(id, acc, pb, nb, na, tid, pv, pi, pj, po, i, j)              \
-    if (pv) {                                                                         \
-        atomicAdd(&acc[pi], mix(mix(id[pj]) + po));                                   \
-        atomicAdd(&acc[pj], mix(mix(id[pi]) + po));                                   \
-    }                                                                                 \
-    for (int q = tid + REFINE_GT; q < nb; q += REFINE_GT) {                           \
-        if (!mol_ends(pb, q, na, i, j)) continue;                                     \
-        const u64 o = (u64)bond_class(pb[q * MOL_BOND_W + 2]);                        \
-        atomicAdd(&acc[i], mix(mix(id[j]) + o));                                      \
-        atomicAdd(&acc[j], mix(mix(id[i]) + o));                                      \
-    }
-// The same over record rows: ti and tj are already numbers in T, the rows past the workgroup go through remap (record atom -> its
-// number in T; both ends of a valid row are in T)
-#define REFINE_ROUND_REC(id, acc, rb, m, nt, remap, tid, tv, ti, tj, to, i, j)        \
-    if (tv) {                                                                         \
-        atomicAdd(&acc[ti], mix(mix(id[tj]) + to));                                   \
-        atomicAdd(&acc[tj], mix(mix(id[ti]) + to));                                   \
-    }                                                                                 \
-    for (int k = tid + REFINE_GT; k < m; k += REFINE_GT) {                            \
-        if (!rec_ends(rb, k, nt, i, j)) continue;                                     \
-        const u64 o = (u64)bond_class(rb[k * REC_BOND_W + 2]);                        \
-        i = remap[i], j = remap[j];                                                   \
-        atomicAdd(&acc[i], mix(mix(id[j]) + o));                                      \
-        atomicAdd(&acc[j], mix(mix(id[i]) + o));                                      \
-    }
-// the end of a round: id[a] = mix(mix(id[a] + r) + acc[a]), acc zeroed again
-#define REFINE_ROUND_END(id, acc, n, r, tid)                                          \
-    __syncthreads();                                                                  \
-    for (int a = tid; a < n; a += REFINE_GT) {                                        \
-        id[a] = mix(mix(id[a] + r) + acc[a]);                                         \
-        acc[a] = 0;                                                                   \
-    }                                                                                 \
-    __syncthreads();
-// The number of distinct ids, exactly (the body of a function that returns it): every id goes into an open-addressed table of SLOTS >=
-// 2 n slots (64-bit LDS compare-and-swap; 0 marks a free slot, so the ids that ARE 0 are counted apart), and the ids that found a free
-// slot are counted -- as many as there are distinct values, in any order of the threads.  An id that finds itself there is shared by
-// two atoms: `shared` keeps this thread's least such id, `zeros` (uniform) the number of ids that are 0, for the cell of the level.
-// wi = LDS scratch [REFINE_NW]
-#define REFINE_CLASSES(id, n, table, SLOTS, wi, tid, shared, zeros)                                   \
-    for (int k = tid; k < SLOTS; k += REFINE_GT) table[k] = 0;                                        \
-    __syncthreads();                                                                                  \
-    int fresh = 0, zero = 0;                                                                          \
-    shared = ~0ull;                                                                                   \
-    for (int a = tid; a < n; a += REFINE_GT) {                                                        \
-        const u64 e = id[a];                                                                          \
-        if (e == 0) {                                                                                 \
-            ++zero;                                                                                   \
-            continue;                                                                                 \
-        }                                                                                             \
-        unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);                                            \
-        for (int probe = 0; probe < SLOTS; ++probe) { /* (n <= SLOTS / 2 ids: a free slot is always found) */ \
-            const u64 old = atomicCAS(&table[slot], 0ull, e);                                         \
-            if (old == 0) {                                                                           \
-                ++fresh;                                                                              \
-                break;                                                                                \
-            }                                                                                         \
-            if (old == e) {                                                                           \
-                shared = min(shared, e);                                                              \
-                break;                                                                                \
-            }                                                                                         \
-            slot = (slot + 1) & (SLOTS - 1);                                                          \
-        }                                                                                             \
-    }                                                                                                 \
-    const int both = block_reduce(fresh + (zero << 16), wi, [](int u, int v) { return u + v; });      \
-    zeros = both >> 16;                                                                               \
-    return (both & 0xFFFF) + (zeros > 0);
-// the wrapping sum of mix(id) over the atoms (the body of a function that returns it); wu = LDS scratch [REFINE_NW]
-#define REFINE_MULTISET_SUM(id, n, wu, tid)                                           \
-    u64 s = 0;                                                                        \
-    for (int a = tid; a < n; a += REFINE_GT) s += mix(id[a]);                         \
-    return block_reduce(s, wu, [](u64 u, u64 v) { return u + v; });
+// ---- a bond row: v, it names a pair of atoms of its side; its ends i and j as atom numbers; its order class.  A thread keeps row `tid`
+// of a side in registers through every round (tens of bonds per drawing: most launches read no bond row twice); the rows past the
+// workgroup's 256 threads are read from global memory again, by the same readers.  The bond code is read with the ends, whatever
+// they hold (the row is there): one load per row, not a second one that waits for the first
+struct BondRow {
+    bool v;
+    int i, j, o;
+};
+__device__ inline BondRow mol_row(const int* pb, int q, int na) {
+    BondRow e = {false, 0, 0, bond_class(pb[q * MOL_BOND_W + 2])};
+    e.v = mol_ends(pb, q, na, e.i, e.j);
+    return e;
+}
+// (ends in the record's own numbering: what the degrees are counted in)
+__device__ inline BondRow rec_row(const int* rb, int k, int nt) {
+    BondRow e = {false, 0, 0, bond_class(rb[k * REC_BOND_W + 2])};
+    e.v = rec_ends(rb, k, nt, e.i, e.j);
+    return e;
+}
+// the ends of a record row as numbers in T (remap: record atom -> its number in T; both ends of a valid row are in T: the row is one
+// of those that put them there)
+__device__ inline void renumber(BondRow& e, const int* remap) {
+    if (e.v) e.i = remap[e.i], e.j = remap[e.j];
+}
+__device__ inline BondRow rec_row(const int* rb, int k, int nt, const int* remap) {
+    BondRow e = rec_row(rb, k, nt);
+    renumber(e, remap);
+    return e;
+}
 
-// ---- the same as functions (uniform; acc is zero on entry and on exit of a round)
-__device__ __forceinline__ void refine_round_mol(int tid, u64* id, u64* acc, const int* pb, int nb, int na, int n, u64 r, bool pv, int pi, int pj,
-                                                 u64 po) {
-    int i, j;
-    REFINE_ROUND_MOL(id, acc, pb, nb, na, tid, pv, pi, pj, po, i, j)
-    REFINE_ROUND_END(id, acc, n, r, tid)
+// ---- stage (A), in the steps between the callers' barriers.  First the degrees of one side into deg (zero on entry) by 64-bit LDS
+// adds, one per valid end; `own` is the caller's row `tid`.  Returns the number of valid rows this thread met
+__device__ inline void count_ends(u64* deg, const BondRow& e) {
+    atomicAdd(&deg[e.i], 1ull);
+    atomicAdd(&deg[e.j], 1ull);
 }
-__device__ __forceinline__ void refine_round_rec(int tid, u64* id, u64* acc, const int* rb, int m, int nt, const int* remap, int n, u64 r, bool tv,
-                                                 int ti, int tj, u64 to) {
-    int i, j;
-    REFINE_ROUND_REC(id, acc, rb, m, nt, remap, tid, tv, ti, tj, to, i, j)
-    REFINE_ROUND_END(id, acc, n, r, tid)
+__device__ __forceinline__ int refine_degrees_mol(int tid, const int* pb, int nb, int na, const BondRow& own, u64* deg) {
+    int valid = own.v;
+    if (own.v) count_ends(deg, own);
+    for (int q = tid + REFINE_GT; q < nb; q += REFINE_GT) {
+        const BondRow e = mol_row(pb, q, na);
+        if (!e.v) continue;
+        ++valid;
+        count_ends(deg, e);
+    }
+    return valid;
 }
+__device__ __forceinline__ int refine_degrees_rec(int tid, const int* rb, int m, int nt, const BondRow& own, u64* deg) {
+    int valid = own.v;
+    if (own.v) count_ends(deg, own);
+    for (int k = tid + REFINE_GT; k < m; k += REFINE_GT) {
+        const BondRow e = rec_row(rb, k, nt);
+        if (!e.v) continue;
+        ++valid;
+        count_ends(deg, e);
+    }
+    return valid;
+}
+// Then, the degrees complete (a barrier of the caller): id_0 of every molecule atom into id and, where given, into layer as well.
+// deg is read only
+__device__ __forceinline__ void refine_id0_mol(int tid, const int* pa, int na, const u64* deg, u64* id, u64* layer = nullptr) {
+    for (int a = tid; a < na; a += REFINE_GT) {
+        const u64 e = id0(atom_class(pa[a * ATOM_W + 2]), pa[a * ATOM_W + 3], deg[a]);
+        id[a] = e;
+        if (layer != nullptr) layer[a] = e;
+    }
+}
+// The record side: its atoms with a bond (the set T) are numbered in index order by a workgroup scan, two atoms per thread, their
+// degrees in registers across it.  Writes remap (all of it: -1 outside T), orig (number in T -> record atom; may be null) and id_0 in
+// T numbering into id (and into layer, where given), and leaves deg zero again: each degree is read, before the scan's barriers, and
+// cleared by the one thread that numbers its atom.  Returns |T|; the caller's next barrier makes remap, orig and id visible (then
+// renumber() the kept row).  wt = LDS scratch [REFINE_NW + 1]
+template <class O>
+__device__ __forceinline__ int refine_number_rec(int tid, const int* ra, int nt, u64* deg, unsigned* wt, int* remap, O* orig, u64* id,
+                                                 u64* layer = nullptr) {
+    const int a0 = 2 * tid, a1 = 2 * tid + 1;
+    const u64 deg0 = a0 < nt ? deg[a0] : 0, deg1 = a1 < nt ? deg[a1] : 0;
+    const unsigned f0 = deg0 != 0, f1 = deg1 != 0;
+    unsigned total;
+    const unsigned r0 = block_excl_scan<REFINE_GT>(f0 + f1, wt, &total), r1 = r0 + f0;
+    remap[a0] = f0 ? (int)r0 : -1;
+    remap[a1] = f1 ? (int)r1 : -1;
+    auto number = [&](int a, unsigned t, u64 degree) __attribute__((always_inline)) {
+        const u64 e = id0(atom_class(ra[a * REC_ATOM_W + 2]), ra[a * REC_ATOM_W + 3], degree);
+        id[t] = e;
+        if (layer != nullptr) layer[t] = e;
+        if (orig != nullptr) orig[t] = (O)a;
+    };
+    if (f0) number(a0, r0, deg0);
+    if (f1) number(a1, r1, deg1);
+    deg[a0] = deg[a1] = 0;
+    return (int)total;
+}
+
+// ---- one round, id_r[a] = mix(mix(id[a] + r) + sum over the rows at a of mix(mix(id[other end]) + order class)), in two halves with
+// a barrier of the caller between them.  First the sums of one side's rows into acc (zero on entry): commutative, so no order of rows
+// or atoms can change an id.  `own` is the caller's row `tid` (a record's: renumbered)
+__device__ inline void add_terms(u64* acc, const u64* id, const BondRow& e) {
+    const u64 at_i = id[e.i], at_j = id[e.j];      // (both read before either add: the two hash chains overlap)
+    atomicAdd(&acc[e.i], mix(mix(at_j) + (u64)e.o));
+    atomicAdd(&acc[e.j], mix(mix(at_i) + (u64)e.o));
+}
+__device__ __forceinline__ void refine_add_mol(int tid, const u64* id, u64* acc, const int* pb, int nb, int na, const BondRow& own) {
+    if (own.v) add_terms(acc, id, own);
+    for (int q = tid + REFINE_GT; q < nb; q += REFINE_GT) {
+        const BondRow e = mol_row(pb, q, na);
+        if (e.v) add_terms(acc, id, e);
+    }
+}
+__device__ __forceinline__ void refine_add_rec(int tid, const u64* id, u64* acc, const int* rb, int m, int nt, const int* remap, const BondRow& own) {
+    if (own.v) add_terms(acc, id, own);
+    for (int k = tid + REFINE_GT; k < m; k += REFINE_GT) {
+        const BondRow e = rec_row(rb, k, nt, remap);
+        if (e.v) add_terms(acc, id, e);
+    }
+}
+// Then the new ids of the side's n atoms, acc zero again; layer (may be null): the new ids are stored there as well
+__device__ __forceinline__ void refine_finish(int tid, u64* id, u64* acc, int n, u64 r, u64* layer = nullptr) {
+    for (int a = tid; a < n; a += REFINE_GT) {
+        const u64 e = mix(mix(id[a] + r) + acc[a]);
+        id[a] = e;
+        acc[a] = 0;
+        if (layer != nullptr) layer[a] = e;
+    }
+}
+
+// ---- The number of distinct ids, exactly: every id goes into an open-addressed table of SLOTS >= 2 n slots (64-bit LDS
+// compare-and-swap; 0 marks a free slot, so the ids that ARE 0 are counted apart), and the ids that found a free slot are counted -- as
+// many as there are distinct values, in any order of the threads.  An id that finds itself there is shared by two atoms: `shared` keeps
+// this thread's least such id, `zeros` (uniform) the number of ids that are 0, for the cell of the level.  wi = LDS scratch [REFINE_NW]
 template <int SLOTS>
 __device__ __forceinline__ int refine_classes(int tid, const u64* id, int n, u64* table, int* wi, u64& shared, int& zeros) {
-    REFINE_CLASSES(id, n, table, SLOTS, wi, tid, shared, zeros)
+    for (int k = tid; k < SLOTS; k += REFINE_GT) table[k] = 0;
+    __syncthreads();
+    int fresh = 0, zero = 0;
+    shared = ~0ull;
+    for (int a = tid; a < n; a += REFINE_GT) {
+        const u64 e = id[a];
+        if (e == 0) {
+            ++zero;
+            continue;
+        }
+        unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
+        for (int probe = 0; probe < SLOTS; ++probe) {      // (n <= SLOTS / 2 ids: a free slot is always found)
+            const u64 old = atomicCAS(&table[slot], 0ull, e);
+            if (old == 0) {
+                ++fresh;
+                break;
+            }
+            if (old == e) {
+                shared = min(shared, e);
+                break;
+            }
+            slot = (slot + 1) & (SLOTS - 1);
+        }
+    }
+    const int both = block_reduce(fresh + (zero << 16), wi, [](int u, int v) { return u + v; });
+    zeros = both >> 16;
+    return (both & 0xFFFF) + (zeros > 0);
 }
+// the wrapping sum of mix(id) over the atoms; wu = LDS scratch [REFINE_NW]
 __device__ __forceinline__ u64 refine_multiset_sum(int tid, const u64* id, int n, u64* wu) {
-    REFINE_MULTISET_SUM(id, n, wu, tid)
+    u64 s = 0;
+    for (int a = tid; a < n; a += REFINE_GT) s += mix(id[a]);
+    return block_reduce(s, wu, [](u64 u, u64 v) { return u + v; });
 }

@@ -25,10 +25,11 @@
 #include "block_scan.hpp"
 #include "mol_rows.hpp"
 #include "graph_ids.hpp"
+#include "graph_refine.hpp"
 
 namespace {
 
-constexpr int GT = 256;            // threads per workgroup
+constexpr int GT = REFINE_GT;       // threads per workgroup (graph_refine.hpp)
 constexpr int MAX_ATOMS = ABC_MAX_SIM_ATOMS;      // ids, sums and four fingerprint layers of both sides in 48 KB of LDS
 constexpr int RADIUS = 3;            // fingerprint layers 0 .. 3
 constexpr int MAX_ROUNDS = 64;       // refinement rounds of refine_equal
@@ -55,109 +56,47 @@ __global__ __launch_bounds__(GT) void graph_sim_kernel(const abc_graph_similarit
     __shared__ u64 acc[2][MAX_ATOMS];    // degree, then the neighbour sum of the round
     __shared__ u64 fp[2][FP];            // layer-major, atom-minor: id_r[a] at r * n + a
     __shared__ int remap[MAX_ATOMS];     // record atom -> its number in T, -1 outside T
-    __shared__ unsigned wt[GT / 64 + 1];
+    __shared__ unsigned wt[REFINE_NW + 1];
     __shared__ int cnt[4];               // valid molecule bonds, valid record bonds, envs_common, common id_T
     const int b = blockIdx.x, tid = threadIdx.x;
     ScoredImage im;
     if (!scored_image<NCOL>(d, b, tid, im)) return;
     const auto [nt, m, status, na, nb, empty, pa, pb, ra, rb] = im;
 
-    // row `tid` of each side, kept through every round (tens of bonds per drawing: most launches read no bond row twice)
-    int pi = 0, pj = 0, ti = 0, tj = 0;
-    const bool pv = tid < nb && mol_ends(pb, tid, na, pi, pj), tv = tid < m && rec_ends(rb, tid, nt, ti, tj);
-    const u64 po = pv ? (u64)bond_class(pb[tid * MOL_BOND_W + 2]) : 0, to = tv ? (u64)bond_class(rb[tid * REC_BOND_W + 2]) : 0;
+    // row `tid` of each side, kept through every round
+    const BondRow none = {false, 0, 0, 0};
+    const BondRow prow = tid < nb ? mol_row(pb, tid, na) : none;
+    BondRow trow = tid < m ? rec_row(rb, tid, nt) : none;
 
-    // ---- (A) degrees, T, id_0
+    // ---- (A) degrees (in acc), T, id_0
     if (tid < 4) cnt[tid] = 0;
     for (int a = tid; a < MAX_ATOMS; a += GT) acc[0][a] = acc[1][a] = 0;
     __syncthreads();
     {
-        int valid_p = pv, valid_t = tv, i, j;
-        if (pv) {
-            atomicAdd(&acc[0][pi], 1ull);
-            atomicAdd(&acc[0][pj], 1ull);
-        }
-        if (tv) {
-            atomicAdd(&acc[1][ti], 1ull);
-            atomicAdd(&acc[1][tj], 1ull);
-        }
-        for (int q = tid + GT; q < nb; q += GT) {
-            if (!mol_ends(pb, q, na, i, j)) continue;
-            ++valid_p;
-            atomicAdd(&acc[0][i], 1ull);
-            atomicAdd(&acc[0][j], 1ull);
-        }
-        for (int k = tid + GT; k < m; k += GT) {
-            if (!rec_ends(rb, k, nt, i, j)) continue;
-            ++valid_t;
-            atomicAdd(&acc[1][i], 1ull);
-            atomicAdd(&acc[1][j], 1ull);
-        }
+        const int valid_p = refine_degrees_mol(tid, pb, nb, na, prow, acc[0]), valid_t = refine_degrees_rec(tid, rb, m, nt, trow, acc[1]);
         if (valid_p) atomicAdd(cnt + 0, valid_p);
         if (valid_t) atomicAdd(cnt + 1, valid_t);
     }
     __syncthreads();
-    // (record atoms 2 tid and 2 tid + 1: their degrees stay in registers across the scan)
-    const int a0 = 2 * tid, a1 = 2 * tid + 1;
-    const u64 deg0 = a0 < nt ? acc[1][a0] : 0, deg1 = a1 < nt ? acc[1][a1] : 0;
-    const unsigned f0 = deg0 != 0, f1 = deg1 != 0;
-    unsigned total;
-    const unsigned r0 = block_excl_scan<GT>(f0 + f1, wt, &total), r1 = r0 + f0;
-    const int n_t = (int)total;          // |T|
-    for (int a = tid; a < na; a += GT) {
-        const u64 id = id0(atom_class(pa[a * ATOM_W + 2]), pa[a * ATOM_W + 3], acc[0][a]);
-        cur[0][a] = fp[0][a] = id;
-        acc[0][a] = 0;
-    }
-    remap[a0] = f0 ? (int)r0 : -1;
-    remap[a1] = f1 ? (int)r1 : -1;
-    if (f0) cur[1][r0] = fp[1][r0] = id0(atom_class(ra[a0 * REC_ATOM_W + 2]), ra[a0 * REC_ATOM_W + 3], deg0);
-    if (f1) cur[1][r1] = fp[1][r1] = id0(atom_class(ra[a1 * REC_ATOM_W + 2]), ra[a1 * REC_ATOM_W + 3], deg1);
-    acc[1][a0] = acc[1][a1] = 0;         // (every degree was read before the scan's barriers)
+    refine_id0_mol(tid, pa, na, acc[0], cur[0], fp[0]);      // (id_0 is layer 0 of the fingerprint)
+    for (int a = tid; a < na; a += GT) acc[0][a] = 0;        // (by the thread that read the degree)
+    const int n_t = refine_number_rec(tid, ra, nt, acc[1], wt, remap, (int*)nullptr, cur[1], fp[1]);      // |T|
     __syncthreads();
-    if (tv) ti = remap[ti], tj = remap[tj];      // (both in T: this row is one of those that put them there)
+    renumber(trow, remap);
     const int valid_p = cnt[0], valid_t = cnt[1];
     const bool size_equal = !empty && na == n_t && valid_p == valid_t;
     const int rounds_t = min(na, MAX_ROUNDS);
     const int rounds = size_equal ? max(rounds_t, RADIUS) : RADIUS;
 
-    // ---- (B) and (D): the rounds; (C) after the third
+    // ---- (B) and (D): the rounds, both sides between one pair of barriers; (C) after the third
+    u64 *layer_p = fp[0], *layer_t = fp[1];      // layer r of the fingerprints while r <= RADIUS, then null
     for (int r = 1; r <= rounds; ++r) {
-        int i, j;
-        if (pv) {
-            atomicAdd(&acc[0][pi], mix(mix(cur[0][pj]) + po));
-            atomicAdd(&acc[0][pj], mix(mix(cur[0][pi]) + po));
-        }
-        if (tv) {
-            atomicAdd(&acc[1][ti], mix(mix(cur[1][tj]) + to));
-            atomicAdd(&acc[1][tj], mix(mix(cur[1][ti]) + to));
-        }
-        for (int q = tid + GT; q < nb; q += GT) {
-            if (!mol_ends(pb, q, na, i, j)) continue;
-            const u64 o = (u64)bond_class(pb[q * MOL_BOND_W + 2]);
-            atomicAdd(&acc[0][i], mix(mix(cur[0][j]) + o));
-            atomicAdd(&acc[0][j], mix(mix(cur[0][i]) + o));
-        }
-        for (int k = tid + GT; k < m; k += GT) {
-            if (!rec_ends(rb, k, nt, i, j)) continue;
-            const u64 o = (u64)bond_class(rb[k * REC_BOND_W + 2]);
-            i = remap[i], j = remap[j];
-            atomicAdd(&acc[1][i], mix(mix(cur[1][j]) + o));
-            atomicAdd(&acc[1][j], mix(mix(cur[1][i]) + o));
-        }
+        layer_p = r <= RADIUS ? layer_p + na : nullptr, layer_t = r <= RADIUS ? layer_t + n_t : nullptr;
+        refine_add_mol(tid, cur[0], acc[0], pb, nb, na, prow);
+        refine_add_rec(tid, cur[1], acc[1], rb, m, nt, remap, trow);
         __syncthreads();
-        for (int a = tid; a < na; a += GT) {
-            const u64 id = mix(mix(cur[0][a] + (u64)r) + acc[0][a]);
-            cur[0][a] = id;
-            acc[0][a] = 0;
-            if (r <= RADIUS) fp[0][r * na + a] = id;
-        }
-        for (int a = tid; a < n_t; a += GT) {
-            const u64 id = mix(mix(cur[1][a] + (u64)r) + acc[1][a]);
-            cur[1][a] = id;
-            acc[1][a] = 0;
-            if (r <= RADIUS) fp[1][r * n_t + a] = id;
-        }
+        refine_finish(tid, cur[0], acc[0], na, (u64)r, layer_p);
+        refine_finish(tid, cur[1], acc[1], n_t, (u64)r, layer_t);
         __syncthreads();
         if (r == RADIUS) {
             const int c = common_share(fp[0], (RADIUS + 1) * na, fp[1], (RADIUS + 1) * n_t, tid);

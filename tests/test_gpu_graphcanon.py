@@ -187,6 +187,16 @@ def test_the_worst_cases_at_capacity(name, rec):
     assert (rows[0]["status"] == 0) == (name != "propanes") and rows[0]["rounds"] >= 900
 
 
+def test_more_molecule_rows_than_threads():
+    """a ring of 257 carbons on the MOLECULE side: 257 bond rows, the smallest number at which the round's loop over the molecule rows
+    past the workgroup's 256 threads runs (the other molecule-side cases stay below it, the 512-atom cases are records)"""
+    mol = so.as_mol(_norm(so.permuted(np.random.RandomState(5), io.carbon_ring(257))))
+    op = _mol_op([mol], 512, 512)
+    rows = _check(op, [co.molecule_image(mol)], [mol])
+    assert rows[0]["status"] == 0 and rows[0]["leaves"] == 3 and rows[0]["tries"] == 5 and rows[0]["rounds"] == 700
+    assert op.rows().tensors[0].cpu().tolist() == [[257, 257, 0, 0]]
+
+
 # --------------------------------------------------------------------------------------------------------- renumbered uploads
 def _renumbered(rng, rec):
     """the same graph with its atoms renumbered and its bond rows in another order; every row keeps its orientation"""
