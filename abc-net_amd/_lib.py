@@ -226,6 +226,13 @@ class CanonDesc(C.Structure):
                 ("out_atoms", vp), ("out_bonds", vp), ("out_implh", vp)]
 
 
+class AromaticDesc(C.Structure):
+    _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp), ("rec_atoms", vp), ("rec_bonds", vp),
+                ("rec_counts", vp), ("B", i32), ("cap_atoms", i32), ("cap_mol_bonds", i32), ("max_atoms", i32), ("max_bonds", i32),
+                ("pad_", i32), ("stats", vp), ("code_out", vp), ("out_counts", vp), ("out_atoms", vp), ("out_bonds", vp),
+                ("out_implh", vp), ("out_rec_bonds", vp)]
+
+
 class MolBlockDesc(C.Structure):
     _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp), ("B", i32), ("cap_atoms", i32),
                 ("cap_mol_bonds", i32), ("text", vp), ("index", vp), ("work", vp), ("cap_text", i64)]
@@ -272,6 +279,9 @@ IDENT_DEFAULT_TRIES, IDENT_DEFAULT_ROUNDS = 4096, 16384     # ABC_IDENT_DEFAULT_
 CANON_COLUMNS = ("status", "leaves", "tries", "rounds", "levels_max", "pruned_trace", "pruned_orbit", "automorphisms", "improved")
 CANON_EMPTY, CANON_TRUNCATED, CANON_UNDECIDED, CANON_COLLISION = 1, 2, 4, 8      # abc_canon_status
 CANON_DEFAULT_TRIES, CANON_DEFAULT_ROUNDS, CANON_ORBIT_LEVELS = 4096, 16384, 8     # ABC_CANON_DEFAULT_TRIES, _ROUNDS, ABC_CANON_ORBIT_LEVELS
+# the ABC_AROM_* columns of abc_aromatic_desc.stats; the codes of its code_out beside the electron counts
+AROMATIC_COLUMNS = ("status", "candidates", "cycles", "aromatic", "rows_changed", "listed")
+AROM_NOT_CANDIDATE, AROM_NONE = -2, -1
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
 SCAN_NPARAM = 2     # abc_scan_param: src_h, src_w
@@ -310,7 +320,8 @@ SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_scor
 # (that list is pinned, name by name, by tests/test_decoder_contract_host.py) the self-sized descriptors since: checked the same way
 SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "abc_graph_identity_desc_size"),
                     (ScanCleanDesc, "abc_scan_clean_desc_size"), (SmilesDesc, "abc_smiles_desc_size"),
-                    (SmilesStereoDesc, "abc_smiles_stereo_desc_size"), (CanonDesc, "abc_canon_desc_size")]
+                    (SmilesStereoDesc, "abc_smiles_stereo_desc_size"), (CanonDesc, "abc_canon_desc_size"),
+                    (AromaticDesc, "abc_aromatic_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -401,6 +412,8 @@ SYMBOLS = {
     "abc_graph_identity_desc_size": (C.c_int, []),
     "abc_canonical_order": (C.c_int, [P(CanonDesc), vp]),
     "abc_canon_desc_size": (C.c_int, []),
+    "abc_perceive_aromatic": (C.c_int, [P(AromaticDesc), vp]),
+    "abc_aromatic_desc_size": (C.c_int, []),
     "abc_molblock_text_bytes": (i64, [P(MolBlockDesc)]),
     "abc_write_molblocks": (C.c_int, [P(MolBlockDesc), vp]),
     "abc_molblock_desc_size": (C.c_int, []),

@@ -248,3 +248,29 @@ class GraphRecords:
         """the rec_* and max_* fields of GraphScoreDesc and GraphSimilarityDesc"""
         d.rec_atoms, d.rec_bonds, d.rec_counts = (t.data_ptr() for t in self.staging.dev.values())
         d.max_atoms, d.max_bonds = self.max_atoms, self.max_bonds
+
+
+class _DeviceTwins:
+    """the `.dev` / `.device` half of a PinnedStaging, for tensors a device stage writes"""
+
+    def __init__(self, device, dev):
+        self.device, self.dev = torch.device(device), dict(dev)
+
+
+class DerivedGraphRecords(GraphRecords):
+    """The records of `source` as a device stage rewrote them (ops.AromaticityPerceiver.records()): a GraphRecords for every reader,
+    whose device twins are that stage's outputs (and the source's own tensors where the stage copies nothing).  It is loaded when its
+    source is, and only there: `load` is refused."""
+
+    def __init__(self, source, atoms, bonds, cnt, owner):
+        self.B, self.max_atoms, self.max_bonds = source.B, source.max_atoms, source.max_bonds
+        self.source, self.owner = source, owner
+        self.staging = _DeviceTwins(source.staging.device, {"atoms": atoms, "bonds": bonds, "cnt": cnt})
+
+    @property
+    def loaded(self):
+        return self.source.loaded
+
+    def load(self, graphs):
+        raise ValueError("these records are written on the device by %s: load its source (GraphRecords.load, InferenceRunner.load_graphs) "
+                         "and run it" % self.owner)

@@ -29,6 +29,7 @@
 #include "mol_rows.hpp"
 #include "graph_ids.hpp"
 #include "text_pack.hpp"
+#include "text_hydrogens.hpp"
 
 namespace {
 
@@ -43,30 +44,7 @@ static_assert(MAX_ATOMS <= 1 << 13 && MAX_SLOTS <= 1 << 16, "a slot holds neighb
 // decode.ATOM_SYMBOLS, two columns each
 __device__ const char SYMBOL2[N_SYMBOLS * 2 + 1] = "C C N O P F ClS BrB SeI H Si";
 constexpr unsigned BARE_SET = 0x3FFFu & ~(1u << 10 | 1u << 12 | 1u << 13);                                  // all but Se, H, Si
-constexpr unsigned AROMATIC_SET = 1u << 0 | 1u << 1 | 1u << 2 | 1u << 3 | 1u << 4 | 1u << 7 | 1u << 9 | 1u << 10;      // B C N O P S Se
-// the valence lists by vocabulary index and charge -1 | 0 | +1: up to three values, four bits each, lowest first, 0 = no more
-#define V1(a) (a)
-#define V2(a, b) ((a) | (b) << 4)
-#define V3(a, b, c) ((a) | (b) << 4 | (c) << 8)
-__device__ const unsigned short VALENCES[N_SYMBOLS][3] = {
-    {V1(3), V1(4), V1(3)}, {V1(3), V1(4), V1(3)},                     // C, C
-    {V1(2), V1(3), V1(4)}, {V1(1), V1(2), V1(3)},                     // N, O
-    {V3(2, 4, 6), V2(3, 5), V1(4)}, {0, V1(1), V1(2)},                // P, F
-    {0, V1(1), V3(2, 4, 6)}, {V1(1), V3(2, 4, 6), V2(3, 5)},          // Cl, S
-    {0, V1(1), V3(2, 4, 6)}, {V1(4), V1(3), V1(2)},                   // Br, B
-    {V1(1), V3(2, 4, 6), V2(3, 5)}, {0, V1(1), V3(2, 4, 6)},          // Se, I
-    {0, 0, 0}, {V2(3, 5), V1(4), V1(3)}};                             // H, Si
-
-// h of an unlisted atom: s2 = the sum over its bonds of 3 for class 4 and 2 * class otherwise
-__device__ inline int hydrogens(int sym, int charge, int s2) {
-    if (sym == 12 || charge < -1 || charge > 1) return 0;
-    const int v = s2 >> 1;
-    for (unsigned list = VALENCES[sym][charge + 1]; list != 0; list >>= 4) {
-        const int t = (int)(list & 15u);
-        if (t >= v) return t - v;
-    }
-    return 0;
-}
+// (AROMATIC_SET, the valence lists and hydrogens(): text_hydrogens.hpp, shared with aromatic.hip)
 
 // two sinks for one emitter: Count adds up, Write stores below `end`
 struct Count {
@@ -364,7 +342,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
                 cls = 1;
                 w.adj[1][s] = (unsigned short)((w.adj[1][s] & ~7) | 1);
             }
-            s2 += cls == 4 ? 3 : 2 * cls;
+            s2 += bond_s2(cls);
             any4 |= cls == 4;
         }
         w.aromatic[i] = (unsigned char)(any4 && (AROMATIC_SET >> w.sym[i] & 1u));

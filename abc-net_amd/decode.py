@@ -90,14 +90,17 @@ class Molecule:
         out.append("M  END\n$$$$")
         return "".join(out)
 
-    def smiles(self, stereo=False, canonical=False):
-        """a deterministic, valid SMILES of this graph by the text rule of DESIGN.md section 7 (the host form and the oracle of
+    def smiles(self, stereo=False, canonical=False, aromatize=False):
+        """aromatize=True: aromatized().smiles(stereo, canonical) -- the aromatic rings are perceived first (perceive_aromatic).
+        A deterministic, valid SMILES of this graph by the text rule of DESIGN.md section 7 (the host form and the oracle of
         csrc/smiles.hip, integers only): NOT the canonical string RDKit prints; hs is not read.  stereo=False: wedges are single
         bonds, no mark is written and the positions are not read.  stereo=True: the tetrahedral centres the wedge rows and the
         positions decide (stereo_centres) are written as `@` / `@@` in a bracket token; nothing else of the text changes.
         canonical=True: canonical().smiles() -- the same rule on the canonical atom order, so equal graphs give equal strings (not
         RDKit's canonical string either; refused with stereo=True: wedge ownership and the drawn geometry are not in the invariant).
         ValueError for a row the rule refuses and for more than 99 ring bonds open at once."""
+        if aromatize:
+            return self.aromatized().smiles(stereo=stereo, canonical=canonical)
         if canonical:
             if stereo:
                 raise ValueError("Molecule.smiles: canonical=True with stereo=True is not covered (the canonical order does not read "
@@ -152,6 +155,35 @@ class Molecule:
                         [self.positions[a] for a in at], [ends for _, ends in rows], [self.orders[q] for q, _ in rows], listed,
                         None if self.sources is None else [self.sources[q] for q, _ in rows], self.truncated)
 
+    def aromatic_perception(self):
+        """(molecule, stats, codes): this molecule with the bonds of every aromatic cycle set to order 4 (perceive_aromatic on the
+        rows as csrc/aromatic.hip reads them: the host form of abc_perceive_aromatic's molecule side), the AROMATIC_COLUMNS of the
+        pass as a dict, and the code of every atom (AROM_NOT_CANDIDATE, AROM_NONE or its electrons).  Only orders and implicit_hs
+        change: an atom implicit_hs does not list whose hydrogen count by the text rule (text_hydrogens) is 1 on these rows and 0 on
+        the perceived ones is appended, the new entries ascending -- pyrrole stays [nH]1cccc1."""
+        n = len(self.symbols)
+        rows = [(e1 - 1, e2 - 1, o) for (e1, e2), o in zip(self.bonds, self.orders)]
+        orders, codes, st = perceive_aromatic((self.symbols, self.charges, rows))
+        before, after = [[] for _ in range(n)], [[] for _ in range(n)]
+        for (i, j, o), o2 in zip(rows, orders):
+            if 0 <= i < n and 0 <= j < n and i != j:
+                for a in (i, j):
+                    before[a].append(canon_bond_class(o))
+                    after[a].append(canon_bond_class(o2))
+        listed = {a - 1 for a in self.implicit_hs}
+        new = [a + 1 for a in range(n) if a not in listed and before[a] != after[a]
+               and text_hydrogens(self.symbols[a], self.charges[a], before[a]) == 1
+               and text_hydrogens(self.symbols[a], self.charges[a], after[a]) == 0]
+        st["listed"] = len(new)
+        if self.truncated:
+            st["status"] |= 2
+        m = Molecule(self.symbols, self.charges, self.hs, self.positions, self.bonds, orders, self.implicit_hs + new, self.sources, self.truncated)
+        return m, st, codes
+
+    def aromatized(self):
+        """aromatic_perception()[0]: what every stage downstream takes in place of this molecule"""
+        return self.aromatic_perception()[0]
+
     def stereo_centres(self):
         """one code per atom by the stereo rule of DESIGN.md section 7: 0 no candidate, +1 / -1 the local parity s(a) of a marked
         centre, 2 flat, 3 unqualified (abc_smiles_stereo_desc.stereo_out).  ValueError as smiles()."""
@@ -194,10 +226,7 @@ class Molecule:
             s, c = self.symbols[a], self.charges[a]
             if listed[a]:
                 return 1
-            if s == "H" or abs(c) > 1:
-                return 0
-            v = sum(3 if cls == 4 else 2 * cls for _, cls in adj[a]) // 2
-            return next((t - v for t in _SMILES_VALENCES[s][c + 1] if t >= v), 0)
+            return text_hydrogens(s, c, [cls for _, cls in adj[a]])
 
         def token(a, mark=""):
             s, c = self.symbols[a], self.charges[a]
@@ -541,3 +570,95 @@ _HALOGEN = ((), (1,), (2, 4, 6))
 _SMILES_VALENCES = {"B": ((4,), (3,), (2,)), "C": ((3,), (4,), (3,)), "N": ((2,), (3,), (4,)), "O": ((1,), (2,), (3,)),
                     "F": ((), (1,), (2,)), "Si": ((3, 5), (4,), (3,)), "P": ((2, 4, 6), (3, 5), (4,)), "S": ((1,), (2, 4, 6), (3, 5)),
                     "Se": ((1,), (2, 4, 6), (3, 5)), "Cl": _HALOGEN, "Br": _HALOGEN, "I": _HALOGEN, "H": ((), (), ())}
+
+
+def text_hydrogens(symbol, charge, classes):
+    """the hydrogen count h of an UNLISTED atom by the text rule (csrc/text_hydrogens.hpp): classes = the order
+    classes of its bonds; v = (3 per class-4 bond + 2 * class per other bond) // 2; h = t - v for the first t >= v of the valence list
+    of the symbol at this charge, else 0; 0 for H and for a charge outside -1..1"""
+    if symbol == "H" or abs(charge) > 1 or symbol not in _SMILES_VALENCES:
+        return 0
+    v = sum(3 if cls == 4 else 2 * cls for cls in classes) // 2
+    return next((t - v for t in _SMILES_VALENCES[symbol][charge + 1] if t >= v), 0)
+
+
+# ------------------------------------------------------------------------------------------------- aromaticity perception
+# The host form of csrc/aromatic.hip (the contract: include/abcnet_hip.h, abc_aromatic_desc; DESIGN.md section 7): the rule is this
+# project's own, a function of the graph alone, integers only; codes and stats are comparable with the kernel word for word.
+AROMATIC_COLUMNS = ("status", "candidates", "cycles", "aromatic", "rows_changed", "listed")
+AROM_NOT_CANDIDATE, AROM_NONE = -2, -1
+_AROM_LONE_PAIR = frozenset(("O", "S", "Se"))
+
+
+def perceive_aromatic(graph):
+    """graph = (symbols [n] (None or a string outside the vocabulary: no symbol), charges [n], rows [(i, j, order code)] with 0-based
+    ends as they are listed, any integers) -> (orders [m], codes [n], stats dict over AROMATIC_COLUMNS; `status` and `listed` are
+    the caller's).  A row is valid when both ends are in 0..n-1 and differ; orders[q] is 4 for a row on an aromatic cycle and the
+    row's own code otherwise; codes[a] is AROM_NOT_CANDIDATE, AROM_NONE or the electrons e(a)."""
+    symbols, charges, rows = graph
+    n = len(symbols)
+    at = [[] for _ in range(n)]          # per atom: (neighbour, order class, row)
+    for q, (i, j, o) in enumerate(rows):
+        if 0 <= i < n and 0 <= j < n and i != j:
+            cls = canon_bond_class(o)
+            at[i].append((j, cls, q))
+            at[j].append((i, cls, q))
+
+    def candidate(a):
+        cls = [c for _, c, _ in at[a]]
+        return (symbols[a] in _SMILES_AROMATIC and -1 <= charges[a] <= 1 and len(at[a]) in (2, 3) and 0 not in cls and 3 not in cls
+                and cls.count(2) <= 1 and len({y for y, _, _ in at[a]}) == len(at[a]))
+
+    cand = [candidate(a) for a in range(n)]
+
+    def cycles():
+        """every candidate cycle once, as its atoms: from its least atom, the second atom below the last"""
+        for s in range(n):
+            if not cand[s]:
+                continue
+            stack = [(s, iter(at[s]))]
+            path = [s]
+            while stack:
+                step = next(stack[-1][1], None)
+                if step is None:
+                    stack.pop()
+                    path.pop()
+                    continue
+                v = step[0]
+                if v == s:
+                    if len(path) >= 5 and path[1] < path[-1]:
+                        yield list(path)
+                    continue
+                if v < s or not cand[v] or v in path or len(path) == 7:
+                    continue
+                path.append(v)
+                stack.append((v, iter(at[v])))
+
+    def rows_of(cycle):
+        return [next(q for y, _, q in at[u] if y == v) for u, v in zip(cycle, cycle[1:] + cycle[:1])]
+
+    found = list(cycles())
+    ring = {q for c in found for q in rows_of(c)}
+
+    def electrons(a):
+        s, c, d = symbols[a], charges[a], len(at[a])
+        double = [(y, q) for y, cls, q in at[a] if cls == 2]
+        if double:
+            y, q = double[0]
+            return 1 if q in ring else (0 if symbols[y] in ("N",) or symbols[y] in _AROM_LONE_PAIR else AROM_NONE)
+        has4 = any(cls == 4 for _, cls, _ in at[a])
+        if s == "C":
+            return (2, (1 if has4 else AROM_NONE), 0)[c + 1]
+        if s == "B":
+            return 0 if c == 0 else AROM_NONE
+        if s in ("N", "P"):
+            return (2, ((2 if d == 3 else 1) if has4 else 2), (1 if has4 else AROM_NONE))[c + 1]
+        return 2 if c == 0 else AROM_NONE
+
+    codes = [electrons(a) if cand[a] else AROM_NOT_CANDIDATE for a in range(n)]
+    aromatic = [c for c in found if all(codes[a] >= 0 for a in c) and sum(codes[a] for a in c) == 6]
+    marked = {q for c in aromatic for q in rows_of(c)}
+    orders = [4 if q in marked else o for q, (_, _, o) in enumerate(rows)]
+    st = dict.fromkeys(AROMATIC_COLUMNS, 0)
+    st.update(candidates=sum(cand), cycles=len(found), aromatic=len(aromatic), rows_changed=sum(o != o2 for (_, _, o), o2 in zip(rows, orders)))
+    return orders, codes, st

@@ -30,7 +30,19 @@ from .contract import HEADS, GraphRecords, alloc_targets, check_sparse_rasterize
 
 # the optional stages behind the NMS in launch order, each under the constructor flag that builds it
 STAGES = {"extractor": "extract", "assembler": "assemble", "canonicalizer": "smiles_canonical", "texter": "molblocks", "smiler": "smiles", "scorer": "score_graphs",
-          "similarity": "score_similarity", "identity": "score_identity", "evaluator": "evaluate"}
+          "similarity": "score_similarity", "identity": "score_identity", "evaluator": "evaluate",
+          "aromatizer": "aromatize", "record_aromatizer": "aromatize"}
+# ... but for the aromaticity perception, which is launched right behind the assembler (the molecule rows, then the staged graph
+# records): every stage after it but the mol block text reads what it wrote
+LAUNCH_AFTER = {"aromatizer": "assembler", "record_aromatizer": "aromatizer"}
+
+
+def launch_order():
+    """the attributes of STAGES in the order their stages are launched"""
+    order = [attr for attr in STAGES if attr not in LAUNCH_AFTER]
+    for attr, before in LAUNCH_AFTER.items():
+        order.insert(order.index(before) + 1, attr)
+    return order
 
 
 class InferenceRunner:
@@ -38,7 +50,7 @@ class InferenceRunner:
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
                  assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
                  score_similarity=False, molblocks=False, score_identity=False, smiles=False, smiles_stereo=False,
-                 smiles_canonical=False):
+                 smiles_canonical=False, aromatize=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -88,10 +100,17 @@ class InferenceRunner:
         RDKit's canonical SMILES).  molblocks=True keeps reading the assembler's rows: the mol block stays the reference's bytes.
         canonical_stats() returns the search's rows (an UNDECIDED image is reported there), canonical_keys() the hash keys.  Stereo is
         refused: wedge ownership and the drawn geometry are not in the invariant
+        aromatize (needs assemble=True): the aromatic rings of every assembled molecule are perceived (ops.AromaticityPerceiver, one
+        launch right after the assembler in the same captured chain) and, when graph records are staged, those of every record (a
+        second launch); the canonical order, the SMILES text and the three scores then read the PERCEIVED rows and records, so a ring
+        drawn with alternating orders 1 / 2 and the same ring drawn with order 4 are one molecule.  smiles() is then
+        `m.aromatized().smiles(...)` (smiles_stereo is allowed); molblocks=True keeps reading the assembler's rows: the mol block
+        stays the reference's bytes.  aromatic_stats() returns the pass's rows.  The rule is this project's,
+        not RDKit's.  Off (the default): no launch is added and no byte changes
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
-        from .ops import OMEGA_RULES, GraphAssembler, GraphCanonicalizer, GraphIdentity, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, SmilesWriter, check_nms_heads
+        from .ops import OMEGA_RULES, AromaticityPerceiver, GraphAssembler, GraphCanonicalizer, GraphIdentity, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, SmilesWriter, check_nms_heads
         if omega_rule not in OMEGA_RULES:
             raise ValueError("InferenceRunner: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
         self.omega_rule = omega_rule
@@ -103,6 +122,9 @@ class InferenceRunner:
             if on and not assemble:
                 raise ValueError("InferenceRunner(%s=True) writes the text of the assembled molecules of the step: it needs "
                                  "assemble=True" % flag)
+        if aromatize and not assemble:
+            raise ValueError("InferenceRunner(aromatize=True) perceives the aromatic rings of the assembled molecules of the step: it "
+                             "needs assemble=True")
         if smiles_stereo and not smiles:
             raise ValueError("InferenceRunner(smiles_stereo=True) is a form of the SMILES stage: it needs smiles=True")
         if smiles_canonical and not smiles:
@@ -151,6 +173,8 @@ class InferenceRunner:
         self._nms = d
         # img2smiles2.py:113-191: compact candidate lists for the CPU graph-assembly stage, inside the same graph
         self.extractor = self.assembler = self.canonicalizer = self.texter = self.smiler = self.evaluator = self._rasterizer = None
+        self.aromatizer = self.record_aromatizer = None
+        rows = None                      # what the stages behind the assembler read: its rows, or the perceived ones
         with torch.cuda.device(dev):
             if extract:
                 self.extractor = PeakExtractor(lg, self.atom_mask, self.bond_mask, cap_atoms=cap_atoms, cap_bonds=cap_bonds,
@@ -158,13 +182,17 @@ class InferenceRunner:
                                                omega_rule=omega_rule)
             if assemble:
                 self.assembler = GraphAssembler.from_extractor(self.extractor, cap_mol_bonds=cap_mol_bonds)
+                rows = self.assembler.rows
+            if aromatize:
+                self.aromatizer = AromaticityPerceiver.from_assembler(self.assembler)
+                rows = self.aromatizer.rows()
             if molblocks:
                 self.texter = MolBlockWriter.from_assembler(self.assembler)
             if smiles_canonical:
-                self.canonicalizer = GraphCanonicalizer.from_assembler(self.assembler)
+                self.canonicalizer = GraphCanonicalizer(rows)
                 self.smiler = SmilesWriter(self.canonicalizer.rows())
             elif smiles:
-                self.smiler = SmilesWriter.from_assembler(self.assembler, stereo=bool(smiles_stereo))
+                self.smiler = SmilesWriter(rows, stereo=bool(smiles_stereo))
         if evaluate:
             if tuple(model.heads) != HEADS:
                 raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (list(HEADS), list(model.heads)))
@@ -177,14 +205,17 @@ class InferenceRunner:
         self.wants_graph_records = bool(score_graphs or score_similarity or score_identity)
         if self.wants_graph_records:
             with torch.cuda.device(dev):
-                self.records = GraphRecords(eng.B, 256, 256, dev)
+                self.records = records = GraphRecords(eng.B, 256, 256, dev)      # (.records: the STAGED ones, what load_graphs fills)
+                if aromatize:
+                    self.record_aromatizer = AromaticityPerceiver.from_records(self.records)
+                    records = self.record_aromatizer.records()
                 if score_graphs:
-                    self.scorer = GraphScore.from_assembler(self.assembler, radius=score_radius, n_valid=self.n_valid, records=self.records)
+                    self.scorer = GraphScore(rows, radius=score_radius, n_valid=self.n_valid, records=records)
                 if score_similarity:
-                    self.similarity = GraphSimilarity.from_assembler(self.assembler, n_valid=self.n_valid, records=self.records)
+                    self.similarity = GraphSimilarity(rows, n_valid=self.n_valid, records=records)
                 if score_identity:
-                    self.identity = GraphIdentity.from_assembler(self.assembler, n_valid=self.n_valid, records=self.records)
-        self._stages = [attr for attr in STAGES if getattr(self, attr) is not None]
+                    self.identity = GraphIdentity(rows, n_valid=self.n_valid, records=records)
+        self._stages = [attr for attr in launch_order() if getattr(self, attr) is not None]
         self.use_graph = use_graph
         self._graph = None
         self.steps = 0
@@ -335,6 +366,14 @@ class InferenceRunner:
         op = self._need("canonicalizer")
         with torch.cuda.device(self.dev):
             return op.keys()
+
+    def aromatic_stats(self):
+        """the aromaticity perception of every image of the last step (AromaticityPerceiver.stats: the L.AROMATIC_COLUMNS -- status,
+        candidates, cycles, aromatic, rows_changed, listed; host sync; needs aromatize=True); with staged graph records a pair:
+        the molecules' rows, then the records'"""
+        op = self._need("aromatizer")
+        with torch.cuda.device(self.dev):
+            return op.stats() if self.record_aromatizer is None else (op.stats(), self.record_aromatizer.stats())
 
     def stereo_stats(self):
         """what became of the wedge rows of the last step (SmilesWriter.stereo_stats: marked, flat, unqualified, wedge_rows and the

@@ -10,8 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .contract import (HEAD_NAMES, HEADS, CandidateLists, GraphRecords, MoleculeRows, check_head_maps, check_targets, current_stream,
-                       require_device_tensor, set_target_ptrs, stream_or_current)
+from .contract import (HEAD_NAMES, HEADS, REC_BOND_W, CandidateLists, DerivedGraphRecords, GraphRecords, MoleculeRows, check_head_maps,
+                       check_targets, current_stream, require_device_tensor, set_target_ptrs, stream_or_current)
 
 EXTRACT_HEADS = HEADS      # the head widths extract.hip reads (train.py:47)
 
@@ -956,6 +956,93 @@ class GraphCanonicalizer:
         if self.cert is None:
             raise L.AbcNetHipError("GraphCanonicalizer.certificates: the op was built without cert=True")
         return self.cert.cpu()
+
+
+class AromaticityPerceiver:
+    """the aromatic rings of every image, perceived on the device (csrc/aromatic.hip, abc_perceive_aromatic; the rule:
+    include/abcnet_hip.h): the rows of a GraphAssembler -- or the bond rows of contract.GraphRecords -- copied with
+    the bonds of every aromatic cycle set to order 4, so that a Kekule drawing and an order-4 drawing of one ring are one graph.
+    rows() / records() are what GraphCanonicalizer, SmilesWriter, MolBlockWriter, GraphScore, GraphSimilarity and GraphIdentity take in
+    place of the input.  The rule is this project's own (a function of the graph, integers only), NOT RDKit's.  One launch, static
+    buffers, graph-capture safe; stats() and codes() are the host syncs.  No CPU fallback (the host form is
+    decode.Molecule.aromatized())."""
+
+    def __init__(self, mol_counts=None, mol_atoms=None, mol_bonds=None, mol_implh=None, records=None, codes=False):
+        """a contract.MoleculeRows (GraphAssembler.rows) or its device tensors (mol_implh optional: no atom counts as listed without
+        it), OR records=contract.GraphRecords (or a scorer, whose records are taken).  codes: keep the code of every atom in .code
+        (int32 [B, cap]: L.AROM_NOT_CANDIDATE, L.AROM_NONE or its electrons)."""
+        who = "AromaticityPerceiver"
+        if (mol_counts is None) == (records is None):
+            raise ValueError("%s: give the molecule rows or records=GraphRecords, one side" % who)
+        d = L.AromaticDesc()
+        self.source = self.out = self._records = None
+        if records is not None:
+            records = records.records if isinstance(records, _RecordScorer) else records
+            if not isinstance(records, GraphRecords):
+                raise ValueError("%s: records must be a GraphRecords, got %s" % (who, type(records).__name__))
+            if not 1 <= records.max_atoms <= L.MAX_SIM_ATOMS or records.max_bonds < 1:
+                raise ValueError("%s: max_atoms must be 1..%d and max_bonds >= 1, got %d, %d"
+                                 % (who, L.MAX_SIM_ATOMS, records.max_atoms, records.max_bonds))
+            records.fill(d)
+            d.B = records.B
+            self.source, self.keep = records, ()
+            self.B, self.cap, self.cap_bonds, dev = records.B, records.max_atoms, records.max_bonds, records.staging.device
+            self.out_bonds = torch.zeros((self.B, self.cap_bonds, REC_BOND_W), dtype=torch.int32, device=dev)
+            d.out_rec_bonds = self.out_bonds.data_ptr()
+            atoms, _, cnt = records.staging.dev.values()
+            self._records = DerivedGraphRecords(records, atoms, self.out_bonds, cnt, who)
+        else:
+            given = mol_counts.tensors[3] if isinstance(mol_counts, MoleculeRows) else mol_implh
+            mr = MoleculeRows.checked(who, mol_counts, mol_atoms, mol_bonds, mol_implh, max_cap_atoms=L.MAX_SIM_ATOMS, need_implh=given is not None)
+            mr.fill(d)
+            d.mol_implh = L.ptr(mr.tensors[3])
+            self.keep = mr.tensors
+            self.B, self.cap, self.cap_bonds, dev = mr.B, mr.cap_atoms, mr.cap_mol_bonds, mr.device
+            out = tuple(torch.zeros(s, dtype=torch.int32, device=dev) for s in MoleculeRows.SHAPES(mr.B, mr.cap_atoms, mr.cap_mol_bonds))
+            self.out = MoleculeRows(*out)
+            d.out_counts, d.out_atoms, d.out_bonds, d.out_implh = (t.data_ptr() for t in out)
+        self.lib = L.load()
+        self.stat = torch.zeros((self.B, len(L.AROMATIC_COLUMNS)), dtype=torch.int32, device=dev)
+        self.code = torch.full((self.B, self.cap), L.AROM_NOT_CANDIDATE, dtype=torch.int32, device=dev) if codes else None
+        d.stats, d.code_out = self.stat.data_ptr(), L.ptr(self.code)
+        self.d = d
+
+    @classmethod
+    def from_assembler(cls, asm, **kw):
+        return cls(asm.rows, **kw)
+
+    @classmethod
+    def from_records(cls, records, **kw):
+        return cls(records=records, **kw)
+
+    def run(self, stream=None):
+        """one launch (graph-capturable): the perceived rows (or record bonds), stats, and the codes when they were asked for"""
+        L.check(self.lib.abc_perceive_aromatic(C.byref(self.d), stream_or_current(stream)), "perceive_aromatic")
+
+    def rows(self):
+        """the perceived rows of the last run as a contract.MoleculeRows on the device: what the canonicaliser, the writers and the
+        scorers take in place of GraphAssembler.rows"""
+        if self.out is None:
+            raise L.AbcNetHipError("AromaticityPerceiver.rows: built on graph records, which have no molecule rows (records())")
+        return self.out
+
+    def records(self):
+        """the perceived records of the last run as a contract.GraphRecords on the device: the source's atoms and counts, this op's
+        bond rows; what the scorers and GraphCanonicalizer take as records=; its `load` is refused (load the source)"""
+        if self._records is None:
+            raise L.AbcNetHipError("AromaticityPerceiver.records: built on molecule rows, there are no records (rows())")
+        return self._records
+
+    def stats(self):
+        """the stats rows of the last run as a structured numpy array [B] with the int32 fields L.AROMATIC_COLUMNS.  Host sync."""
+        rows = np.ascontiguousarray(self.stat.cpu().numpy())
+        return rows.view(np.dtype([(c, np.int32) for c in L.AROMATIC_COLUMNS])).reshape(self.B)
+
+    def codes(self):
+        """codes=True: int32 [B, cap] on the host, per atom L.AROM_NOT_CANDIDATE, L.AROM_NONE or its electrons.  Host sync."""
+        if self.code is None:
+            raise L.AbcNetHipError("AromaticityPerceiver.codes: the op was built without codes=True")
+        return self.code.cpu()
 
 
 def timed(stream, marks, label, flops, nbytes, fn, operand_bytes=None):

@@ -1106,6 +1106,63 @@ int abc_canonical_order(const abc_canon_desc* d, abc_stream_t stream);
 /* sizeof(abc_canon_desc), for a binding's mirror struct (as abc_graph_identity_desc_size) */
 int abc_canon_desc_size(void);
 
+/* Aromaticity perception: the rows of one side copied with the bonds of every aromatic cycle set to order 4, so that a ring drawn with
+ * alternating orders 1 / 2 and the same ring drawn with order 4 are one graph for abc_canonical_order, abc_write_smiles and the three
+ * graph scores, which take the output in place of the input (csrc/aromatic.hip; host form decode.perceive_aromatic; DESIGN.md section
+ * 7).  The rule is this project's own, a function of the graph alone, integers only; RDKit is not consulted and differs on azulene,
+ * on 10-electron and larger systems and on a degree-2 `n` of an order-4 ring that carries a hydrogen.  One launch on the stream, one
+ * workgroup of 256 threads per image, no atomics on global memory, no allocation, no sync, graph-capturable.
+ *   graph     one side per call, as abc_canon_desc: the atoms of the side; the valid bond rows (molecule: both ends in 1..n and
+ *             distinct; record: both in 0..n-1 and distinct); the order class of a code: 1, 2, 3, 4 themselves, 5 and 6 (wedges) class
+ *             1, anything else class 0; degree = the number of valid rows at an atom; symbols by vocabulary index (0 and 1 are both
+ *             carbon), an index outside 0..13 (a record's -1) is no symbol;
+ *   candidate an atom whose symbol is one of B C N O P S Se, whose charge is in -1..1, whose degree is 2 or 3, none of whose rows has
+ *             class 0 or 3, at most one of whose rows has class 2, and no two of whose rows name the same neighbour;
+ *   cycle     a candidate cycle is a simple cycle of 5, 6 or 7 candidates along valid rows -- every one, the envelopes of fused rings
+ *             included (degree <= 3 bounds the walk: there is no budget); a ring bond is a valid row on at least one of them;
+ *   e(a)      the electrons of a candidate, from the INPUT classes, one value per atom; the first case that applies:
+ *             (1) a has a class-2 row: 1 if that row is a ring bond; else 0 if its other end is one of N O S Se; else NONE;
+ *             (2) with has4 = a has a class-4 row --  C: charge 0: 1 if has4 else NONE; -1: 2; +1: 0.   B: charge 0: 0; else NONE.
+ *                 N, P: charge -1: 2; +1: 1 if has4 else NONE; 0 with has4: 2 at degree 3, 1 at degree 2; 0 without has4: 2.
+ *                 O, S, Se: charge 0: 2; else NONE;
+ *   aromatic  a candidate cycle without NONE whose e sum to exactly 6;
+ *   output    every row on an aromatic cycle with order 4 (a wedge code 5 / 6 there becomes 4), every other row verbatim, invalid
+ *             rows and class-0 rows included; atoms, counts and status bits copied.  One pass: nothing reads an order this pass wrote,
+ *             so the result does not depend on numbering, row order or thread order;
+ *   hydrogen  (molecule side) with h the hydrogen count of abc_write_smiles' text rule: an atom mol_implh does not list whose h is 1
+ *             on the input rows and 0 on the output rows is appended to the list -- out_implh is the input's entries in their order,
+ *             then the new ones ascending, out_counts[2] their number (new entries past cap_atoms, which only a list naming an atom
+ *             twice can cause, are dropped); this keeps pyrrole [nH]1cccc1.  Records have no list: their side writes bonds only;
+ *   limits    cap_atoms (molecule side) or max_atoms (records) 1..512, else ABC_EUNSUPPORTED with nothing launched; bond rows stay
+ *             out of LDS: their capacity is free.  No output may overlap an input or another output (ABC_EINVAL);
+ *   outputs   every word is written by every launch, zero past the (clamped) counts and for an EMPTY image:
+ *             stats [B][ABC_AROM_NCOL]: the status bits (ABC_MOL_EMPTY, ABC_MOL_TRUNCATED, copied; 0 for a record), candidates,
+ *               candidate cycles, aromatic cycles (each cycle once), rows whose order changed, atoms appended to the list;
+ *             code_out (optional) [B][cap]: per atom ABC_AROM_NOT_CANDIDATE, ABC_AROM_NONE or e (NOT_CANDIDATE past n). */
+enum { ABC_AROM_STATUS = 0, ABC_AROM_CANDIDATES, ABC_AROM_CYCLES, ABC_AROM_AROMATIC, ABC_AROM_ROWS_CHANGED, ABC_AROM_LISTED, ABC_AROM_NCOL = 6 };
+enum { ABC_AROM_NOT_CANDIDATE = -2, ABC_AROM_NONE = -1 };
+typedef struct abc_aromatic_desc {
+    const int32_t* mol_counts;   /* [B][4]                 the molecule side (as abc_assemble_desc), or NULL */
+    const int32_t* mol_atoms;    /* [B][cap_atoms][5] */
+    const int32_t* mol_bonds;    /* [B][cap_mol_bonds][4] */
+    const int32_t* mol_implh;    /* optional: [B][cap_atoms]; without it no atom counts as listed */
+    const int32_t* rec_atoms;    /* [B][max_atoms][4]      the records side (as abc_graph_score_desc), or NULL */
+    const int32_t* rec_bonds;    /* [B][max_bonds][3] */
+    const int32_t* rec_counts;   /* [2][B] */
+    int32_t B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds;   /* the capacities of the side that is given */
+    int32_t pad_;
+    int32_t* stats;              /* [B][ABC_AROM_NCOL] */
+    int32_t* code_out;           /* optional: [B][cap] */
+    int32_t* out_counts;         /* molecule side, all four: the perceived rows, [B][4] */
+    int32_t* out_atoms;          /* [B][cap_atoms][5] */
+    int32_t* out_bonds;          /* [B][cap_mol_bonds][4] */
+    int32_t* out_implh;          /* [B][cap_atoms] */
+    int32_t* out_rec_bonds;      /* records side: [B][max_bonds][3] */
+} abc_aromatic_desc;
+int abc_perceive_aromatic(const abc_aromatic_desc* d, abc_stream_t stream);
+/* sizeof(abc_aromatic_desc), for a binding's mirror struct (as abc_canon_desc_size) */
+int abc_aromatic_desc_size(void);
+
 /* The mol block text of the assembled molecules (generate_smiles.py:18-105), written on the device from the rows of
  * abc_assemble_graphs, read in place: the bytes that go into Chem.MolFromMolBlock, one copy per batch (csrc/molblock.hip; the
  * contract in full: DESIGN.md section 7).  Two launches on the stream, integers only, no atomics on global memory, no allocation,

@@ -40,13 +40,19 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            (the identity's `same` of profiles/r15_identity.md, position-free: 0 under raw, 7 under peaks).  Writes what it measured
            to profiles/r21_canonical.md
 
+  aromatize (or --aromatize beside other parts): the aromaticity perception (csrc/aromatic.hip, InferenceRunner(aromatize=True)) under
+           BOTH omega rules in this one process -- abc_perceive_aromatic alone, on the molecule rows and on the graph records, beside
+           abc_canonical_order; the evaluating step with every graph stage with and without it (alternated blocks); the pass's stats;
+           the identity's exact / same / refine_equal and the count of canonical strings equal to their annotation's, with and
+           without it.  Writes what it measured to profiles/r22_aromatic.md
+
   --omega-rule {raw,peaks}: the extractor's candidate rule of every runner built here (InferenceRunner(omega_rule=...): "raw" is
            img2smiles2.py:139, "peaks" img2smiles.py:139 / img2smiles3.py:140); `graphs` and `score` then also report the candidates
            per image and abc_extract_peaks alone (as `launch`).  profiles/r09_omega_rule.md is one run per rule.
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--canonical]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--canonical] [--aromatize]
 """
 import argparse
 import json
@@ -412,6 +418,102 @@ def part_smiles_canonical(m, x, notes, steps, warmup, reps=30, iters=200):
     print("wrote", path, flush=True)
 
 
+def part_aromatize(m, x, notes, steps, warmup, iters=200):
+    """--aromatize: both omega rules in this process -- abc_perceive_aromatic alone (molecule rows, then graph records) beside
+    abc_canonical_order, the evaluating step with every graph stage without and with aromatize=True (alternated blocks), the stats
+    of the pass, GraphIdentity's exact / same / refine_equal without and with it, and how many canonical strings equal their
+    annotation's.  The lines are printed and written to profiles/r22_aromatic.md"""
+    from abcnet_amd import _lib as L
+    from abcnet_amd.decode import ATOM_SYMBOLS, Molecule
+    from abcnet_amd.raster import TargetRasterizer, parse_graph, parse_record
+    global RULE
+    lines, keep = [], RULE
+
+    def note(d):
+        lines.append(dict(d, omega_rule=RULE))
+        emit(d)
+    recs = [parse_record(a, b, h=S // 4) for a, b in notes]
+    graphs = [parse_graph(a, b, h=S // 4) for a, b in notes]
+    # the annotation of every image as a molecule (only bonded atoms, no listed atom), as --canonical builds it
+    annotated = []
+    for a, q in graphs:
+        T = sorted({int(e) for row in q for e in row[:2]})
+        num = {t: k + 1 for k, t in enumerate(T)}
+        annotated.append(Molecule([ATOM_SYMBOLS[int(a[t][2])] if 0 <= int(a[t][2]) < 14 else "?" for t in T], [int(a[t][3]) for t in T], [0] * len(T),
+                                  [[int(a[t][0]), int(a[t][1])] for t in T], [[num[int(i)], num[int(j)]] for i, j, _ in q], [int(o) for _, _, o in q], []))
+
+    def text(mol, aromatize):
+        try:
+            return None if mol is None else mol.smiles(canonical=True, aromatize=aromatize)
+        except ValueError:
+            return None
+    for RULE in ("raw", "peaks"):
+        rs = {}
+        for name, kw in (("graph stages", {}), ("graph stages+aromatize", dict(aromatize=True))):
+            r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, evaluate=True, smiles=True, smiles_canonical=True, score_graphs=True,
+                                score_radius=0, score_similarity=True, score_identity=True, omega_rule=RULE, **kw)
+            rz = TargetRasterizer(B, S // 4, targets=r.targets, sparse=True)
+            r.use_sparse_targets(rz)
+            rz.load(recs)
+            rz.run()
+            r.load_batch(x.to("cuda"))
+            r.load_graphs(graphs)
+            for _ in range(2):
+                r.step()
+            rs[name] = r
+        torch.cuda.synchronize()
+        r, plain = rs["graph stages+aromatize"], rs["graph stages"]
+        st_mol, st_rec = r.aromatic_stats()
+        out = {"part": "aromatize", "what": "fixture", "batch": B}
+        for side, st in (("molecules", st_mol), ("records", st_rec)):
+            out[side] = {c: int(st[c].sum()) for c in L.AROMATIC_COLUMNS[1:]}
+            out[side]["images_with_an_aromatic_cycle"] = int((st["aromatic"] > 0).sum())
+            out[side]["cycles_max"] = int(st["cycles"].max())
+        for name, q in (("without", plain), ("with", r)):
+            q.reset_evaluation()
+            q.step()
+            ev = q.evaluation()
+            mols = q.molecules()
+            got = q.smiles()
+            out[name] = {"exact": ev["molecules"]["exact"], "same": ev["identity"]["same"], "undecided": ev["identity"]["undecided"],
+                         "refine_equal": ev["similarity"]["refine_equal"], "similarity": round(ev["similarity"]["similarity"], 4),
+                         "equal_to_host_form": got == [text(mol, name == "with") for mol in mols],
+                         "strings_equal_to_their_annotation": sum(t is not None and t == text(w, name == "with") for t, w in zip(got, annotated))}
+            q.reset_evaluation()
+        note(out)
+        us = [(launch_us(r.aromatizer.run, iters), launch_us(r.record_aromatizer.run, iters), launch_us(r.canonicalizer.run, iters),
+               launch_us(plain.canonicalizer.run, iters)) for _ in range(3)]
+        note({"part": "aromatize", "what": "launch", "batch": B, "perceive_molecules_us_per_launch": [round(u[0], 2) for u in us],
+              "perceive_records_us_per_launch": [round(u[1], 2) for u in us], "canonical_order_on_perceived_rows_us_per_launch": [round(u[2], 2) for u in us],
+              "canonical_order_us_per_launch": [round(u[3], 2) for u in us],
+              "method": "device events around %d back-to-back calls (launch gaps included), alternated" % iters})
+        for q in rs.values():
+            q.reset_evaluation()
+        med = step_blocks(rs, steps, warmup, "aromatize")
+        note({"part": "aromatize", "what": "step", "ms_per_step": {k: round(v, 4) for k, v in med.items()},
+              "aromatize_minus_plain_ms": round(med["graph stages+aromatize"] - med["graph stages"], 4)})
+        del rs, r, plain
+    RULE = keep
+    path = os.path.join(ROOT, "profiles", "r22_aromatic.md")
+    with open(path, "w") as f:
+        f.write("# Aromaticity perception on the trained fixture (b%d @ %d x %d, drawn_molecules(seed 777))\n\n" % (B, S, S))
+        f.write("`python profiles/tools/assemble_step.py --parts aromatize --aromatize`, one process, both omega rules.  The step is the "
+                "evaluating step with every graph stage (canonical SMILES, score, similarity, identity), with the two perception launches "
+                "against the same commit's step without them in alternated blocks; the launches stand beside abc_canonical_order's "
+                "(56 / 62 us in r21_canonical.md).  `without` / `with` are the scores and the canonical strings of the same batch "
+                "without and with `aromatize`; the stats are sums over the batch.\n\n```\n")
+        for d in lines:
+            f.write(json.dumps(d) + "\n")
+        f.write("```\n\n")
+        fixtures = [d for d in lines if d["what"] == "fixture"]
+        f.write("Images with an aromatic cycle (%s): molecules %s, records %s of %d.  The scores and strings %s.\n"
+                % (" / ".join(d["omega_rule"] for d in fixtures), " / ".join(str(d["molecules"]["images_with_an_aromatic_cycle"]) for d in fixtures),
+                   " / ".join(str(d["records"]["images_with_an_aromatic_cycle"]) for d in fixtures), B,
+                   "are the same with and without the stage: this fixture has no molecule the perception decides"
+                   if all(d["with"] == d["without"] for d in fixtures) else "differ with the stage"))
+    print("wrote", path, flush=True)
+
+
 def annotated_graph(atoms_s, bonds_s):
     atoms = {}
     for a in atoms_s.strip(";").split(";"):
@@ -547,6 +649,7 @@ def main():
     ap.add_argument("--omega-rule", choices=("raw", "peaks"), default="raw")
     ap.add_argument("--stereo", action="store_true", help="the smiles part: the stereo form beside the plain one")
     ap.add_argument("--canonical", action="store_true", help="the smiles part: the canonical atom order, under both omega rules")
+    ap.add_argument("--aromatize", action="store_true", help="the aromatize part: the aromaticity perception, under both omega rules")
     a = ap.parse_args()
     global RULE
     RULE = a.omega_rule
@@ -582,6 +685,8 @@ def main():
         part_smiles(m, x, a.steps, a.warmup, stereo=a.stereo)
         if a.canonical:
             part_smiles_canonical(m, x, notes, a.steps, a.warmup)
+    if a.aromatize or "aromatize" in parts:
+        part_aromatize(m, x, notes, a.steps, a.warmup)
 
 
 if __name__ == "__main__":
