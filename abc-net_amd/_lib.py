@@ -247,6 +247,10 @@ class SmilesStereoDesc(C.Structure):
     _fields_ = SmilesDesc._fields_ + [("stereo_stats", vp), ("stereo_out", vp)]
 
 
+class SmilesEzDesc(C.Structure):
+    _fields_ = SmilesStereoDesc._fields_ + [("tetrahedral", i32), ("ez_stats", vp), ("ez_out", vp)]
+
+
 class ScanDesc(C.Structure):
     _fields_ = [("out", vp), ("src", vp), ("src_stride", i64), ("src_pitch", i32), ("src_max_h", i32), ("params", vp),
                 ("params_host", vp), ("B", i32), ("S", i32), ("margin", i32), ("cover_q8", i32), ("polarity", i32), ("hist", vp),
@@ -307,6 +311,9 @@ MAX_SMILES_ATOMS, MAX_SMILES_BONDS = MAX_SIM_ATOMS, 4096    # ABC_MAX_SMILES_ATO
 # the columns of abc_smiles_stereo_desc.stereo_stats; the codes of .stereo_out beside +1 / -1
 SMILES_STEREO_COLUMNS = ("marked", "flat", "unqualified", "wedge_rows")
 STEREO_NONE, STEREO_FLAT, STEREO_UNQUALIFIED = 0, 2, 3
+# the columns of abc_smiles_ez_desc.ez_stats; the codes of .ez_out beside +1 (together) / -1 (opposite)
+SMILES_EZ_COLUMNS = ("marked", "flat", "ring", "twin")
+EZ_NONE, EZ_FLAT, EZ_RING, EZ_TWIN = 0, 2, 3, 4
 
 
 _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnApplyDesc, WgradDesc, WgradReduceDesc,
@@ -321,7 +328,7 @@ SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_scor
 SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "abc_graph_identity_desc_size"),
                     (ScanCleanDesc, "abc_scan_clean_desc_size"), (SmilesDesc, "abc_smiles_desc_size"),
                     (SmilesStereoDesc, "abc_smiles_stereo_desc_size"), (CanonDesc, "abc_canon_desc_size"),
-                    (AromaticDesc, "abc_aromatic_desc_size")]
+                    (AromaticDesc, "abc_aromatic_desc_size"), (SmilesEzDesc, "abc_smiles_ez_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -425,6 +432,10 @@ SYMBOLS = {
     "abc_smiles_stereo_work_ints": (i64, [P(SmilesStereoDesc)]),
     "abc_write_smiles_stereo": (C.c_int, [P(SmilesStereoDesc), vp]),
     "abc_smiles_stereo_desc_size": (C.c_int, []),
+    "abc_smiles_ez_text_bytes": (i64, [P(SmilesEzDesc)]),
+    "abc_smiles_ez_work_ints": (i64, [P(SmilesEzDesc)]),
+    "abc_write_smiles_ez": (C.c_int, [P(SmilesEzDesc), vp]),
+    "abc_smiles_ez_desc_size": (C.c_int, []),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "abc_plane_sum_work": (C.c_int, [i32]),
     "abc_cbam_channel_fwd": (C.c_int, [P(CbamChannelDesc), vp]),

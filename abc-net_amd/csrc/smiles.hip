@@ -20,8 +20,17 @@
 //   smiles_pack_kernel     one workgroup per image: the prefix rule over work[0 .. b] (text_pack.hpp), then a copy of the image's bytes
 // Lengths and bytes come from ONE emitter run over two sinks, so they cannot disagree; every store of either kernel is checked
 // against the end of the image's own bytes.
-// Both kernels are templates over a stereo flag (abc_write_smiles_stereo, the tetrahedral rule of DESIGN.md section 7); without it
-// every stereo line is compiled out.
+// Both kernels are templates over a mode of two bits: <stereo> the tetrahedral rule (abc_write_smiles_stereo), <ez> the double-bond
+// rule (abc_write_smiles_ez), both of DESIGN.md section 7; a line of a rule the mode does not hold is compiled out.  <ez> adds:
+//     3  per atom: is it a possible end (C or N, degree 2 or 3, one class-2 bond, class 1 besides); then one thread per candidate
+//        (two such ends naming each other): twin, the sides of its substituents from the positions (int64), its code
+//     4  the walk keeps a lowpoint per atom (of the atom it stands on: in a register); behind it a tree bond to c is a bridge iff
+//        low[c] == rank[c]: any other candidate is RING
+//     5  the rank sort stores a class-1 slot at a marked end as class 5, a parallel pass does the same for the tree bonds: from here
+//        on a bond that bears a symbol is told from bits that are loaded anyway
+//     6  the same lane, in the same pass over the preorder, fixes the orientation of every group at the first symbol it meets (a
+//        stack over the group's double bonds, which form a tree: every one is pushed once)
+//     7  the symbol of a class-5 bond comes from the marked end's side bits and orientation
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
@@ -38,6 +47,7 @@ constexpr int MAX_ATOMS = ABC_MAX_SMILES_ATOMS;      // LDS arrays per atom
 constexpr int MAX_BONDS = 4096, MAX_SLOTS = 2 * MAX_BONDS;
 constexpr int MAX_NUMBER = 99;
 constexpr int LEN_BAD_ROW = -1, LEN_RING_LIMIT = -2;
+constexpr int CLS_DIRECTED = 5;      // <ez> behind the walk: a class-1 bond that bears "/" or "\\" (1 | 4: the wedge orders are gone by then)
 static_assert(MAX_ATOMS == 2 * ST, "the degree scan gives every thread two atoms");
 static_assert(MAX_ATOMS <= 1 << 13 && MAX_SLOTS <= 1 << 16, "a slot holds neighbour << 3 | class in 16 bits, an index of a slot too");
 
@@ -120,8 +130,9 @@ __device__ inline int owner_of(const Walk& w, int na, int s) {
 
 // Order every atom's list: slot s of `src` goes to the position that counts the slots of its list with a smaller key (ties by
 // slot: a permutation whatever the keys).  by_rank: the key is the neighbour's preorder rank, else the slot's own 16 bits.
-template <bool by_rank>
-__device__ inline void order_lists(Walk& w, int na, int slots, int src, int tid) {
+// <ez> code: the code byte of every atom; a class-1 slot at a marked end (code +1 / -1) is stored as class 5, a slot with a direction
+template <bool by_rank, bool TAG = false>
+__device__ inline void order_lists(Walk& w, int na, int slots, int src, int tid, const signed char* code = nullptr) {
     for (int s = tid; s < slots; s += ST) {
         const int a = owner_of(w, na, s), lo = w.start[a], hi = w.start[a + 1];
         const int e = w.adj[src][s];
@@ -132,7 +143,13 @@ __device__ inline void order_lists(Walk& w, int na, int slots, int src, int tid)
             const int other = by_rank ? (int)w.rank[f >> 3] : f;
             pos += other < key || (other == key && t < s);
         }
-        w.adj[src ^ 1][lo + pos] = (unsigned short)e;
+        if constexpr (TAG) {
+            const int ca = code[a], cy = code[e >> 3];
+            const bool directed = (e & 7) == 1 && (ca == 1 || ca == -1 || cy == 1 || cy == -1);
+            w.adj[src ^ 1][lo + pos] = (unsigned short)(directed ? e | CLS_DIRECTED : e);
+        } else {
+            w.adj[src ^ 1][lo + pos] = (unsigned short)e;
+        }
     }
 }
 
@@ -187,16 +204,118 @@ __device__ inline int stereo_marks(const Walk& w, int a, int p, int code) {
     return ((swaps & 1) ? -code : code) > 0 ? 1 : 2;
 }
 
+// ez: what is kept per atom of the double bond it is an end of (an atom is an end of at most one candidate)
+constexpr int EZ_NONE = 0, EZ_FLAT = 2, EZ_RING = 3, EZ_TWIN = 4;      // (+1 / -1: a marked double bond, together / opposite)
+constexpr unsigned EZ_SIDE0 = 1, EZ_SIDE1 = 2, EZ_UP = 4, EZ_FIXED = 8;
+template <bool EZ>
+struct Ends {
+    short partner[EZ ? MAX_ATOMS : 1];          // after step 3: the other end of this atom's one class-2 bond if the atom may be an end, else -1
+    short sub0[EZ ? MAX_ATOMS : 1];             // the lower of its substituents
+    short low[EZ ? MAX_ATOMS : 1];              // the least rank its subtree reaches by one ring bond
+    signed char code[EZ ? MAX_ATOMS : 1];       // the code of its candidate, 0 without one
+    unsigned char bits[EZ ? MAX_ATOMS : 1];     // side > 0 of sub0 and of the other substituent, the orientation u > 0, u is fixed
+};
+template <bool EZ> struct WalkRegs { int low, parent; };      // the lowpoint and the parent of the atom the walk stands on
+template <> struct WalkRegs<false> {};
+template <bool EZ>
+__device__ inline bool ez_marked(const Ends<EZ>& z, int e) { return z.code[e] == 1 || z.code[e] == -1; }
+template <bool EZ>
+__device__ inline int ez_side(const Ends<EZ>& z, int e, int s) { return (z.bits[e] & (s == z.sub0[e] ? EZ_SIDE0 : EZ_SIDE1)) ? 1 : -1; }
+template <bool EZ>
+__device__ inline int ez_u(const Ends<EZ>& z, int e) { return (z.bits[e] & EZ_UP) ? 1 : -1; }
+
+// The code of the candidate between a < b (both possible ends naming each other), a bridge supposed; lists by index in adj[1].
+__device__ inline void ez_classify(const Walk& w, Ends<true>& z, const int* pa, int a, int b) {
+    int sub[2][2], cnt[2] = {0, 0};
+    bool twin = false;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int e = k ? b : a, other = k ? a : b;
+        sub[k][0] = sub[k][1] = e;
+        for (int s = w.start[e], hi = w.start[e + 1]; s < hi; ++s) {      // (degree 2 or 3: one or two besides the partner)
+            const int y = w.adj[1][s] >> 3;
+            if (y != other && cnt[k] < 2) sub[k][cnt[k]++] = y;
+        }
+        if (cnt[k] == 1) sub[k][1] = sub[k][0];
+        const int s0 = sub[k][0], s1 = sub[k][1];
+        twin |= cnt[k] == 2 && w.start[s0 + 1] - w.start[s0] == 1 && w.start[s1 + 1] - w.start[s1] == 1
+                && atom_class(w.sym[s0]) == atom_class(w.sym[s1]) && w.charge[s0] == w.charge[s1] && w.listed[s0] == w.listed[s1];
+    }
+    int code = EZ_TWIN;
+    unsigned bits[2] = {0, 0};
+    if (!twin) {
+        const long long ax = pa[a * ATOM_W], ay = pa[a * ATOM_W + 1], bx = pa[b * ATOM_W], by = pa[b * ATOM_W + 1];
+        const long long dx = bx - ax, dy = by - ay;
+        bool flat = ax < 0 || ax > MAX_POSITION || ay < 0 || ay > MAX_POSITION || bx < 0 || bx > MAX_POSITION || by < 0 || by > MAX_POSITION;
+        int side[2][2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const long long ex = k ? bx : ax, ey = k ? by : ay;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const long long x = pa[sub[k][t] * ATOM_W], y = pa[sub[k][t] * ATOM_W + 1];
+                flat |= x < 0 || x > MAX_POSITION || y < 0 || y > MAX_POSITION;
+                const long long c = dx * (y - ey) - dy * (x - ex);      // (in range: below 2^40)
+                side[k][t] = (c > 0) - (c < 0);
+                flat |= c == 0;
+            }
+            flat |= cnt[k] == 2 && side[k][0] == side[k][1];
+            bits[k] = (side[k][0] > 0 ? EZ_SIDE0 : 0) | (side[k][1] > 0 ? EZ_SIDE1 : 0);
+        }
+        code = flat ? EZ_FLAT : (side[0][0] == side[1][0] ? 1 : -1);
+    }
+    z.code[a] = z.code[b] = (signed char)code;
+    z.sub0[a] = (short)sub[0][0], z.sub0[b] = (short)sub[1][0];
+    z.bits[a] = (unsigned char)bits[0], z.bits[b] = (unsigned char)bits[1];
+}
+
+// One lane, in text order: the directed bond read first -> second (an end of it is marked).  The first symbol met of a group fixes
+// the group: it is "/".  `stack` holds one end of every double bond whose neighbours are still to be tied (each once).
+__device__ inline void ez_fix(const Walk& w, Ends<true>& z, unsigned short* stack, int first, int second) {
+    int e, s, sign;
+    if (ez_marked(z, first)) e = first, s = second, sign = 1;
+    else e = second, s = first, sign = -1;
+    if (z.bits[e] & EZ_FIXED) return;
+    const unsigned up = sign * ez_side(z, e, s) > 0 ? EZ_UP : 0;
+    z.bits[e] |= EZ_FIXED | up, z.bits[z.partner[e]] |= EZ_FIXED | up;
+    int top = 0;
+    stack[top++] = (unsigned short)e;
+    while (top > 0) {
+        const int x0 = stack[--top];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int x = k ? (int)z.partner[x0] : x0;
+            for (int q = w.start[x], hi = w.start[x + 1]; q < hi; ++q) {
+                const int t = w.adj[0][q] >> 3;
+                if (t == z.partner[x] || !ez_marked(z, t) || (z.bits[t] & EZ_FIXED)) continue;
+                // the bond x -> t read from both ends: u(x) side(x, t) = -u(t) side(t, x)
+                const unsigned ut = -ez_u(z, x) * ez_side(z, x, t) * ez_side(z, t, x) > 0 ? EZ_UP : 0;
+                z.bits[t] |= EZ_FIXED | ut, z.bits[z.partner[t]] |= EZ_FIXED | ut;
+                if (top < MAX_ATOMS) stack[top++] = (unsigned short)t;      // (at most one entry per double bond: never full)
+            }
+        }
+    }
+}
+
+// the symbol of the directed bond read first -> second
+template <bool EZ>
+__device__ inline int ez_symbol(const Ends<EZ>& z, int first, int second) {
+    if (ez_marked(z, first)) return ez_u(z, first) * ez_side(z, first, second) > 0 ? '/' : '\\';
+    return ez_u(z, second) * ez_side(z, second, first) < 0 ? '/' : '\\';
+}
+
 // position p of the preorder: what stands in front of the atom, its token, its ring digits, the brackets behind it
-template <bool STEREO, class Sink>
-__device__ inline void put_position(Sink& o, const Walk& w, const signed char* centre, int p) {
+template <int MODE, class Sink>
+__device__ inline void put_position(Sink& o, const Walk& w, const signed char* centre, const Ends<(MODE & 2) != 0>& z, int p) {
+    constexpr bool STEREO = (MODE & 1) != 0, EZ = (MODE & 2) != 0;
     const int a = w.order[p], par = w.parent[a];
     const bool arom = w.aromatic[a] != 0;
     if (par < 0) {
         if (p > 0) o.put('.');
     } else {
         if (w.opens[a]) o.put('(');
-        put_bond(o, w.parent_cls[a], arom && w.aromatic[par]);
+        if (EZ && w.parent_cls[a] == CLS_DIRECTED) o.put(ez_symbol(z, par, a));
+        else put_bond(o, w.parent_cls[a], arom && w.aromatic[par]);
     }
     int marks = 0;
     if (STEREO) {
@@ -207,14 +326,19 @@ __device__ inline void put_position(Sink& o, const Walk& w, const signed char* c
     for (int s = w.start[a], hi = w.start[a + 1]; s < hi; ++s) {
         const int e = w.adj[0][s], y = e >> 3;
         if (y == par || w.parent[y] == a) continue;
-        if (w.rank[y] < p) put_bond(o, e & 7, arom && w.aromatic[y]);      // a closing: the symbol, then the number
+        if (w.rank[y] < p) {                                               // a closing: the symbol, then the number
+            if (EZ && (e & 7) == CLS_DIRECTED) o.put(ez_symbol(z, a, y));
+            else put_bond(o, e & 7, arom && w.aromatic[y]);
+        }
         put_number(o, w.number[s]);
     }
     for (int i = w.closes[p]; i > 0; --i) o.put(')');
 }
 
-template <bool STEREO> struct DescOf { typedef abc_smiles_desc type; };
-template <> struct DescOf<true> { typedef abc_smiles_stereo_desc type; };
+// the modes: bit 0 tetrahedral, bit 1 double bonds
+template <int MODE> struct DescOf { typedef abc_smiles_ez_desc type; };
+template <> struct DescOf<0> { typedef abc_smiles_desc type; };
+template <> struct DescOf<1> { typedef abc_smiles_stereo_desc type; };
 
 struct Counts { int na, nb, nh, status; };
 template <class Desc>
@@ -232,21 +356,32 @@ __device__ inline Counts read_counts(const Desc& d, int b) {
 // longer and never bare): also the stride of the slices of `work`
 template <bool STEREO>
 __host__ __device__ inline int64_t image_bytes(int64_t cap_atoms, int64_t cap_mol_bonds) { return (STEREO ? 14 : 12) * cap_atoms + 7 * cap_mol_bonds; }
-template <bool STEREO>
-__device__ inline uint8_t* slice_of(const typename DescOf<STEREO>::type& d, int b) {
-    return (uint8_t*)(d.work + d.B) + (size_t)b * (size_t)image_bytes<STEREO>(d.cap_atoms, d.cap_mol_bonds);
+template <int MODE>
+__device__ inline uint8_t* slice_of(const typename DescOf<MODE>::type& d, int b) {
+    return (uint8_t*)(d.work + d.B) + (size_t)b * (size_t)image_bytes<(MODE & 1) != 0>(d.cap_atoms, d.cap_mol_bonds);
 }
 
-// stereo, an image without text (EMPTY, refused): a row of zeros, and every word of its slice of stereo_out
-__device__ inline void no_centres(const abc_smiles_stereo_desc& d, int b, int tid) {
-    if (tid < 4) d.stereo_stats[(size_t)b * 4 + tid] = 0;
-    if (d.stereo_out != nullptr)
-        for (int i = tid; i < d.cap_atoms; i += ST) d.stereo_out[(size_t)b * d.cap_atoms + i] = 0;
+// stereo / ez, an image without text (EMPTY, refused): a row of zeros, and every word of its slice of stereo_out / ez_out
+template <int MODE>
+__device__ inline void no_centres(const typename DescOf<MODE>::type& d, int b, int tid) {
+    if constexpr ((MODE & 1) != 0) {
+        if (tid < 4) d.stereo_stats[(size_t)b * 4 + tid] = 0;
+        if (d.stereo_out != nullptr)
+            for (int i = tid; i < d.cap_atoms; i += ST) d.stereo_out[(size_t)b * d.cap_atoms + i] = 0;
+    }
+    if constexpr ((MODE & 2) != 0) {
+        if (tid < 4) d.ez_stats[(size_t)b * 4 + tid] = 0;
+        if (d.ez_out != nullptr)
+            for (int q = tid; q < d.cap_mol_bonds; q += ST) d.ez_out[(size_t)b * d.cap_mol_bonds + q] = 0;
+    }
 }
 
-template <bool STEREO>
-__global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescOf<STEREO>::type d) {
+template <int MODE>
+__global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescOf<MODE>::type d) {
+    constexpr bool STEREO = (MODE & 1) != 0, EZ = (MODE & 2) != 0;
     __shared__ Walk w;
+    __shared__ Ends<EZ> z;                                      // <ez>
+    __shared__ int ez_tally[4];                                 // <ez> marked, flat, ring, twin
     __shared__ unsigned wt[ST / 64 + 1];
     __shared__ int refused;                // 0, LEN_BAD_ROW or LEN_RING_LIMIT
     __shared__ signed char centre[STEREO ? MAX_ATOMS : 1];      // <stereo> the code of every atom
@@ -256,7 +391,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     const int na = c.na, nb = c.nb, slots = 2 * nb;
     if ((c.status & ABC_MOL_EMPTY) || na == 0) {      // (uniform.  Bonds without an atom cannot be: their ends are outside 1..0)
         if (tid == 0) d.work[b] = (c.status & ABC_MOL_EMPTY) || nb == 0 ? 0 : LEN_BAD_ROW;
-        if constexpr (STEREO) no_centres(d, b, tid);
+        if constexpr (MODE != 0) no_centres<MODE>(d, b, tid);
         return;
     }
     const int* pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
@@ -266,6 +401,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     // ---- 1: rows
     if (tid == 0) refused = 0;
     if (STEREO && tid < 4) tally[tid] = 0;
+    if (EZ && tid < 4) ez_tally[tid] = 0;
     for (int i = tid; i < na; i += ST) {
         w.deg[i] = 0;
         w.rank[i] = w.parent[i] = w.last_child[i] = -1;
@@ -297,7 +433,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     __syncthreads();
     if (refused) {                         // (uniform: read behind the barrier)
         if (tid == 0) d.work[b] = LEN_BAD_ROW;
-        if constexpr (STEREO) no_centres(d, b, tid);
+        if constexpr (MODE != 0) no_centres<MODE>(d, b, tid);
         return;
     }
     {   // every thread takes atoms 2 tid and 2 tid + 1
@@ -333,6 +469,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     for (int i = tid; i < na; i += ST) {
         int s2 = 0, any4 = 0;
         unsigned zbits = 0;
+        int doubles = 0, others = 0, partner = -1;      // <ez>
         const int lo = w.start[i], deg = w.start[i + 1] - lo;
         for (int s = lo, hi = lo + deg; s < hi; ++s) {
             int cls = w.adj[1][s] & 7;
@@ -344,6 +481,15 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
             }
             s2 += bond_s2(cls);
             any4 |= cls == 4;
+            if constexpr (EZ) {
+                if (cls == 2) ++doubles, partner = w.adj[1][s] >> 3;
+                else others |= cls != 1;
+            }
+        }
+        if constexpr (EZ) {
+            z.partner[i] = (short)(doubles == 1 && !others && (deg == 2 || deg == 3) && w.sym[i] <= 2 ? partner : -1);      // (0, 1: C; 2: N)
+            z.code[i] = EZ_NONE;
+            z.bits[i] = 0;
         }
         w.aromatic[i] = (unsigned char)(any4 && (AROMATIC_SET >> w.sym[i] & 1u));
         w.hcount[i] = (unsigned char)(w.listed[i] ? 1 : hydrogens(w.sym[i], w.charge[i], s2));
@@ -360,8 +506,14 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     __syncthreads();
     if (refused) {
         if (tid == 0) d.work[b] = LEN_BAD_ROW;
-        if constexpr (STEREO) no_centres(d, b, tid);
+        if constexpr (MODE != 0) no_centres<MODE>(d, b, tid);
         return;
+    }
+    if constexpr (EZ) {                    // one thread per candidate, the one of its lower end (it alone writes both ends)
+        for (int i = tid; i < na; i += ST) {
+            const int j = z.partner[i];
+            if (j > i && z.partner[j] == i) ez_classify(w, z, pa, i, j);
+        }
     }
 
     // ---- 4: the walk
@@ -372,15 +524,27 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
             w.rank[root] = (short)next;
             w.order[next++] = (unsigned short)root;
             int cur = root;
+            WalkRegs<EZ> reg;                  // <ez> of the atom the walk stands on, in registers: a slot passed costs no LDS access
+            if constexpr (EZ) reg.low = next - 1, reg.parent = -1;
             while (cur >= 0 && steps-- > 0) {
                 const int at = w.cursor[cur];
                 if (at == w.start[cur + 1]) {
-                    cur = w.parent[cur];
+                    if constexpr (EZ) {            // the atom's lowpoint is final; the parent's, kept when the walk went down, takes it in
+                        z.low[cur] = (short)reg.low;
+                        cur = reg.parent;
+                        if (cur >= 0) reg.low = min((int)z.low[cur], reg.low), reg.parent = w.parent[cur];
+                    } else {
+                        cur = w.parent[cur];
+                    }
                     continue;
                 }
                 w.cursor[cur] = (unsigned short)(at + 1);
                 const int e = w.adj[1][at], y = e >> 3;
-                if (w.rank[y] >= 0) continue;      // the parent, or the other end of a ring bond
+                if (w.rank[y] >= 0) {              // the parent, or the other end of a ring bond
+                    if constexpr (EZ)
+                        if (y != reg.parent) reg.low = min(reg.low, (int)w.rank[y]);
+                    continue;
+                }
                 const int before = w.last_child[cur];
                 if (before >= 0) {                 // that child was not the last: it stands in a branch, which ends behind the
                     w.opens[before] = 1;           // atom visited last
@@ -390,6 +554,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
                 w.parent[y] = (short)cur;
                 w.parent_cls[y] = (unsigned char)(e & 7);
                 w.rank[y] = (short)next;
+                if constexpr (EZ) z.low[cur] = (short)reg.low, reg.parent = cur, reg.low = next;
                 w.order[next++] = (unsigned short)y;
                 cur = y;
             }
@@ -397,8 +562,24 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     }
     __syncthreads();
 
+    if constexpr (EZ) {                    // a candidate that is no bridge is RING, whatever else it is; the counters
+        for (int i = tid; i < na; i += ST) {
+            const int j = z.partner[i];
+            if (j <= i || z.code[i] == EZ_NONE) continue;      // (a code: the two ends name each other)
+            const int child = w.parent[j] == i ? j : (w.parent[i] == j ? i : -1);
+            int code = z.code[i];
+            if (child < 0 || z.low[child] != w.rank[child]) z.code[i] = z.code[j] = (signed char)(code = EZ_RING);
+            atomicAdd(&ez_tally[code == EZ_FLAT ? 1 : (code == EZ_RING ? 2 : (code == EZ_TWIN ? 3 : 0))], 1);
+        }
+        __syncthreads();                   // (the codes are final: step 5 tags the slots, and here the tree bonds, that bear a symbol)
+        for (int i = tid; i < na; i += ST) {
+            const int par = w.parent[i];
+            if (par >= 0 && w.parent_cls[i] == 1 && (ez_marked(z, i) || ez_marked(z, par))) w.parent_cls[i] = CLS_DIRECTED;
+        }
+    }
+
     // ---- 5: by rank (back into adj[0]), then the twin of every slot (over adj[1])
-    order_lists<true>(w, na, slots, 1, tid);
+    order_lists<true, EZ>(w, na, slots, 1, tid, z.code);
     __syncthreads();
     for (int s = tid; s < slots; s += ST) {
         const int a = owner_of(w, na, s), y = w.adj[0][s] >> 3, want = w.rank[a];
@@ -420,10 +601,14 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
         for (int p = 0; p < na && !limit; ++p) {
             const int a = w.order[p], par = w.parent[a];
             u64 closed_lo = 0, closed_hi = 0;
+            if constexpr (EZ)                  // (w.cursor is free behind the walk: the stack)
+                if (par >= 0 && w.parent_cls[a] == CLS_DIRECTED) ez_fix(w, z, w.cursor, par, a);
             for (int s = w.start[a], hi = w.start[a + 1]; s < hi; ++s) {
                 const int y = w.adj[0][s] >> 3;
                 if (y == par || w.parent[y] == a) continue;
                 if (w.rank[y] < p) {
+                    if constexpr (EZ)
+                        if ((w.adj[0][s] & 7) == CLS_DIRECTED) ez_fix(w, z, w.cursor, a, y);
                     const int k = w.number[s];
                     if (k < 64) closed_lo |= 1ull << k;
                     else closed_hi |= 1ull << (k - 64);
@@ -446,7 +631,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     __syncthreads();
     if (refused) {
         if (tid == 0) d.work[b] = LEN_RING_LIMIT;
-        if constexpr (STEREO) no_centres(d, b, tid);
+        if constexpr (MODE != 0) no_centres<MODE>(d, b, tid);
         return;
     }
 
@@ -454,22 +639,34 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     int lo, hi;
     text_pack::my_range<ST>(na, tid, lo, hi);
     Count n = {0};
-    for (int p = lo; p < hi; ++p) put_position<STEREO>(n, w, centre, p);
+    for (int p = lo; p < hi; ++p) put_position<MODE>(n, w, centre, z, p);
     unsigned total;
     const unsigned first = block_excl_scan<ST>((unsigned)n.n, wt, &total);
-    uint8_t* slice = slice_of<STEREO>(d, b);
+    uint8_t* slice = slice_of<MODE>(d, b);
     Write o = {slice + first, slice + image_bytes<STEREO>(d.cap_atoms, d.cap_mol_bonds)};
-    for (int p = lo; p < hi; ++p) put_position<STEREO>(o, w, centre, p);
+    for (int p = lo; p < hi; ++p) put_position<MODE>(o, w, centre, z, p);
     if (tid == 0) d.work[b] = (int)total;
     if constexpr (STEREO) {
         if (tid < 4) d.stereo_stats[(size_t)b * 4 + tid] = tally[tid];
         if (d.stereo_out != nullptr)
             for (int i = tid; i < d.cap_atoms; i += ST) d.stereo_out[(size_t)b * d.cap_atoms + i] = i < na ? (int)centre[i] : 0;
     }
+    if constexpr (EZ) {
+        if (tid < 4) d.ez_stats[(size_t)b * 4 + tid] = ez_tally[tid];
+        if (d.ez_out != nullptr)
+            for (int q = tid; q < d.cap_mol_bonds; q += ST) {      // the code of a candidate's row stands on both its ends
+                int code = 0, e1, e2;
+                if (q < nb && mol_ends(pb, q, na, e1, e2) && bond_class(pb[q * MOL_BOND_W + 2]) == 2 && z.partner[e1] == e2
+                    && z.partner[e2] == e1)
+                    code = z.code[e1];
+                d.ez_out[(size_t)b * d.cap_mol_bonds + q] = code;
+            }
+    }
 }
 
-template <bool STEREO>
-__global__ __launch_bounds__(ST) void smiles_pack_kernel(const typename DescOf<STEREO>::type d) {
+template <int MODE>
+__global__ __launch_bounds__(ST) void smiles_pack_kernel(const typename DescOf<MODE>::type d) {
+    constexpr bool STEREO = (MODE & 1) != 0;
     const int b = blockIdx.x, tid = threadIdx.x;
     int* offsets = d.index;
     int* status_out = d.index + d.B + 1;
@@ -484,14 +681,14 @@ __global__ __launch_bounds__(ST) void smiles_pack_kernel(const typename DescOf<S
     }
     if (overflow || len <= 0) return;
     // (through - before == len, and through <= cap_text: every store is inside the image's own bytes; the slice holds len of them)
-    const uint8_t* slice = slice_of<STEREO>(d, b);
+    const uint8_t* slice = slice_of<MODE>(d, b);
     const int n = (int)min((long long)len, (long long)image_bytes<STEREO>(d.cap_atoms, d.cap_mol_bonds));
     for (int i = tid; i < n; i += ST) d.text[span.before + i] = slice[i];
 }
 
 // the guards of both entry points, and the two launches
-template <bool STEREO>
-int write_smiles(const typename DescOf<STEREO>::type* d, abc_stream_t stream, const char* what) {
+template <int MODE>
+int write_smiles(const typename DescOf<MODE>::type* d, abc_stream_t stream, const char* what) {
     char msg[160];
 #define REFUSE(code, text) return (snprintf(msg, sizeof msg, "%s: %s", what, text), abc_fail(code, msg))
     if (!d) REFUSE(ABC_EINVAL, "null descriptor");
@@ -502,11 +699,13 @@ int write_smiles(const typename DescOf<STEREO>::type* d, abc_stream_t stream, co
     if (d->cap_text < 1 || d->cap_text > INT32_MAX) REFUSE(ABC_EINVAL, "cap_text must be 1..2^31-1");
     if (!d->mol_counts || !d->mol_atoms || !d->mol_bonds || !d->mol_implh) REFUSE(ABC_EINVAL, "null molecule buffer");
     if (!d->text || !d->index || !d->work) REFUSE(ABC_EINVAL, "null output");
-    if constexpr (STEREO)
+    if constexpr ((MODE & 1) != 0)
         if (!d->stereo_stats) REFUSE(ABC_EINVAL, "null stereo_stats");
+    if constexpr ((MODE & 2) != 0)
+        if (!d->ez_stats) REFUSE(ABC_EINVAL, "null ez_stats");
 #undef REFUSE
-    hipLaunchKernelGGL(smiles_compose_kernel<STEREO>, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
-    hipLaunchKernelGGL(smiles_pack_kernel<STEREO>, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
+    hipLaunchKernelGGL(smiles_compose_kernel<MODE>, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
+    hipLaunchKernelGGL(smiles_pack_kernel<MODE>, dim3(d->B), dim3(ST), 0, (hipStream_t)stream, *d);
     return abc_check_launch(what);
 }
 
@@ -524,7 +723,7 @@ extern "C" int64_t abc_smiles_work_ints(const abc_smiles_desc* d) {
     return d->B + (d->B * image_bytes<false>(d->cap_atoms, d->cap_mol_bonds) + 3) / 4;
 }
 
-extern "C" int abc_write_smiles(const abc_smiles_desc* d, abc_stream_t stream) { return write_smiles<false>(d, stream, "write_smiles"); }
+extern "C" int abc_write_smiles(const abc_smiles_desc* d, abc_stream_t stream) { return write_smiles<0>(d, stream, "write_smiles"); }
 
 extern "C" int abc_smiles_stereo_desc_size(void) { return (int)sizeof(abc_smiles_stereo_desc); }
 
@@ -539,5 +738,22 @@ extern "C" int64_t abc_smiles_stereo_work_ints(const abc_smiles_stereo_desc* d) 
 }
 
 extern "C" int abc_write_smiles_stereo(const abc_smiles_stereo_desc* d, abc_stream_t stream) {
-    return write_smiles<true>(d, stream, "write_smiles_stereo");
+    return write_smiles<1>(d, stream, "write_smiles_stereo");
+}
+
+extern "C" int abc_smiles_ez_desc_size(void) { return (int)sizeof(abc_smiles_ez_desc); }
+
+extern "C" int64_t abc_smiles_ez_text_bytes(const abc_smiles_ez_desc* d) {
+    if (!d || d->cap_atoms < 1 || d->cap_mol_bonds < 1) return 0;
+    return d->tetrahedral ? image_bytes<true>(d->cap_atoms, d->cap_mol_bonds) : image_bytes<false>(d->cap_atoms, d->cap_mol_bonds);
+}
+
+extern "C" int64_t abc_smiles_ez_work_ints(const abc_smiles_ez_desc* d) {
+    if (!d || d->B < 1 || d->cap_atoms < 1 || d->cap_mol_bonds < 1) return 0;
+    return d->B + (d->B * abc_smiles_ez_text_bytes(d) + 3) / 4;
+}
+
+extern "C" int abc_write_smiles_ez(const abc_smiles_ez_desc* d, abc_stream_t stream) {
+    if (d && d->tetrahedral) return write_smiles<3>(d, stream, "write_smiles_ez");
+    return write_smiles<2>(d, stream, "write_smiles_ez");
 }

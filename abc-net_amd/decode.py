@@ -90,23 +90,27 @@ class Molecule:
         out.append("M  END\n$$$$")
         return "".join(out)
 
-    def smiles(self, stereo=False, canonical=False, aromatize=False):
-        """aromatize=True: aromatized().smiles(stereo, canonical) -- the aromatic rings are perceived first (perceive_aromatic).
+    def smiles(self, stereo=False, canonical=False, aromatize=False, double_bonds=False):
+        """aromatize=True: aromatized().smiles(stereo, canonical, double_bonds=...) -- the aromatic rings are perceived first
+        (perceive_aromatic).
         A deterministic, valid SMILES of this graph by the text rule of DESIGN.md section 7 (the host form and the oracle of
         csrc/smiles.hip, integers only): NOT the canonical string RDKit prints; hs is not read.  stereo=False: wedges are single
         bonds, no mark is written and the positions are not read.  stereo=True: the tetrahedral centres the wedge rows and the
         positions decide (stereo_centres) are written as `@` / `@@` in a bracket token; nothing else of the text changes.
+        double_bonds=True: the single bonds at every double bond the positions decide (double_bond_codes: +1 / -1) are written as
+        `/` or `\\` in place of their empty symbol; nothing else of the text changes, and the two marks are independent.
         canonical=True: canonical().smiles() -- the same rule on the canonical atom order, so equal graphs give equal strings (not
-        RDKit's canonical string either; refused with stereo=True: wedge ownership and the drawn geometry are not in the invariant).
+        RDKit's canonical string either; refused with stereo=True or double_bonds=True: wedge ownership and the drawn geometry are
+        not in the invariant).
         ValueError for a row the rule refuses and for more than 99 ring bonds open at once."""
         if aromatize:
-            return self.aromatized().smiles(stereo=stereo, canonical=canonical)
+            return self.aromatized().smiles(stereo=stereo, canonical=canonical, double_bonds=double_bonds)
         if canonical:
-            if stereo:
-                raise ValueError("Molecule.smiles: canonical=True with stereo=True is not covered (the canonical order does not read "
-                                 "wedge ownership or positions)")
+            if stereo or double_bonds:
+                raise ValueError("Molecule.smiles: canonical=True with stereo=True or double_bonds=True is not covered (the canonical "
+                                 "order does not read wedge ownership or positions)")
             return self.canonical()._smiles(False)[0]
-        return self._smiles(bool(stereo))[0]
+        return self._smiles(bool(stereo), bool(double_bonds))[0]
 
     def canon_graph(self):
         """(classes, charges, bonds [(i, j, order class)] 0-based, tags) as csrc/graph_canon.hip reads the rows: every atom takes
@@ -189,7 +193,13 @@ class Molecule:
         centre, 2 flat, 3 unqualified (abc_smiles_stereo_desc.stereo_out).  ValueError as smiles()."""
         return self._smiles(True)[1]
 
-    def _smiles(self, stereo):
+    def double_bond_codes(self):
+        """one code per bond row by the double-bond rule of DESIGN.md section 7: 0 not a candidate, +1 / -1 a marked double bond
+        (the lowest-index substituents of its two ends on one side / on opposite sides), 2 flat, 3 on a cycle, 4 an end with twin
+        leaves (abc_smiles_ez_desc.ez_out).  ValueError as smiles()."""
+        return self._smiles(False, True)[2]
+
+    def _smiles(self, stereo, double_bonds=False):
         n = len(self.symbols)
         for i, (s, c) in enumerate(zip(self.symbols, self.charges)):
             if s not in ATOM_SYMBOLS:
@@ -264,35 +274,101 @@ class Molecule:
         # the walk, with the tree's parent pointers as its stack: the rank, the parent and the brackets of every atom
         rank, parent, order, cursor = [-1] * n, [-1] * n, [], [0] * n
         last_child, opens_branch, closes = [-1] * n, [False] * n, [0] * n
+        low = [0] * n      # double bonds: the least rank a subtree reaches by one ring bond (a tree bond to c is a bridge iff low[c] == rank[c])
         for root in range(n):
             if rank[root] >= 0:
                 continue
-            rank[root] = len(order)
+            rank[root] = low[root] = len(order)
             order.append(root)
             cur = root
             while cur >= 0:
                 if cursor[cur] == len(adj[cur]):
+                    if parent[cur] >= 0:
+                        low[parent[cur]] = min(low[parent[cur]], low[cur])
                     cur = parent[cur]
                     continue
                 y = adj[cur][cursor[cur]][0]
                 cursor[cur] += 1
+                if rank[y] >= 0 and y != parent[cur]:
+                    low[cur] = min(low[cur], rank[y])
                 if rank[y] < 0:
                     if last_child[cur] >= 0:      # the child before this one was not the last: it stands in a branch, which
                         opens_branch[last_child[cur]] = True      # ends behind the atom visited last
                         closes[len(order) - 1] += 1
                     last_child[cur], parent[y], rank[y] = y, cur, len(order)
+                    low[y] = len(order)
                     order.append(y)
                     cur = y
+
+        # double bonds: the code of every bond row (0 none, +1 / -1 marked, 2 flat, 3 ring, 4 twin); of a marked one both ends are kept:
+        # end atom -> [partner, {substituent: side}, u (0: not fixed yet)]
+        ez_codes, end = [0] * len(self.bonds), {}
+        if double_bonds:
+            def leaf(s):
+                return len(adj[s]) == 1, self.symbols[s], self.charges[s], listed[s]
+
+            for k, ((e1, e2), o) in enumerate(zip(self.bonds, self.orders)):
+                if o != 2:
+                    continue
+                a, b = min(e1, e2) - 1, max(e1, e2) - 1
+                subs = {e: [s for s, _ in adj[e] if s != p] for e, p in ((a, b), (b, a))}
+                if not all(self.symbols[e] in ("C", "N") and len(adj[e]) in (2, 3) and all(cls == 1 for s, cls in adj[e] if s != p)
+                           for e, p in ((a, b), (b, a))):
+                    continue
+                child = b if parent[b] == a else (a if parent[a] == b else -1)
+                if child < 0 or low[child] != rank[child]:
+                    ez_codes[k] = 3
+                    continue
+                if any(len(subs[e]) == 2 and leaf(subs[e][0])[0] and leaf(subs[e][0]) == leaf(subs[e][1]) for e in (a, b)):
+                    ez_codes[k] = 4
+                    continue
+                pos = self.positions
+                dx, dy = pos[b][0] - pos[a][0], pos[b][1] - pos[a][1]
+                side = {e: [dx * (pos[s][1] - pos[e][1]) - dy * (pos[s][0] - pos[e][0]) for s in subs[e]] for e in (a, b)}
+                side = {e: [(t > 0) - (t < 0) for t in ts] for e, ts in side.items()}
+                if (any(not 0 <= v <= 199999 for j in [a, b] + subs[a] + subs[b] for v in pos[j])
+                        or any(t == 0 for e in (a, b) for t in side[e]) or any(len(side[e]) == 2 and side[e][0] == side[e][1] for e in (a, b))):
+                    ez_codes[k] = 2
+                    continue
+                ez_codes[k] = 1 if side[a][0] == side[b][0] else -1
+                end[a], end[b] = [b, dict(zip(subs[a], side[a])), 0], [a, dict(zip(subs[b], side[b])), 0]
+
+        def direction(first, second):
+            """the symbol of a class-1 bond read first -> second, None where no marked double bond claims it.  The first symbol met
+            of a group of double bonds joined by shared single bonds fixes the group's orientation: it is "/"."""
+            claims = [(e, s, sign) for e, s, sign in ((first, second, 1), (second, first, -1)) if e in end]
+            if not claims:
+                return None
+            e, s, sign = claims[0]
+            if end[e][2] == 0:
+                end[e][2] = end[end[e][0]][2] = sign * end[e][1][s]
+                todo = [e]
+                while todo:
+                    x = todo.pop()
+                    for x in (x, end[x][0]):
+                        for t, side_t in end[x][1].items():
+                            if t in end and end[t][2] == 0:
+                                end[t][2] = end[end[t][0]][2] = -end[x][2] * side_t * end[t][1][x]
+                                todo.append(t)
+            ups = {sign * end[e][2] * end[e][1][s] for e, s, sign in claims}
+            assert len(ups) == 1, "the two readings of the bond (%d, %d) disagree" % (first + 1, second + 1)
+            return "/" if ups == {1} else "\\"
+
         # a neighbour that is neither the parent nor a child is the other end of a ring bond: the lower rank opened it
         free, number, out = [True] * 100, {}, []
         for p, a in enumerate(order):
+            if parent[a] < 0:
+                lead = "." if p > 0 else ""
+            else:
+                cls = next(cls for y, cls in adj[a] if y == parent[a])
+                lead = ("(" if opens_branch[a] else "") + ((cls == 1 and direction(parent[a], a)) or bond_symbol(parent[a], a, cls))
             ring = sorted((rank[y], y, cls) for y, cls in adj[a] if y != parent[a] and parent[y] != a)
             digits, closed = [], []
             for r, y, cls in ring:
                 if r < p:
                     k = number.pop((y, a))
                     closed.append(k)
-                    digits.append(bond_symbol(y, a, cls))
+                    digits.append((cls == 1 and direction(a, y)) or bond_symbol(y, a, cls))      # (the closer bears the symbol)
                 else:
                     k = next((i for i in range(1, 100) if free[i]), 0)
                     if k == 0:
@@ -302,10 +378,6 @@ class Molecule:
                 digits.append("%d" % k if k < 10 else "%%%d" % k)
             for k in closed:
                 free[k] = True
-            if parent[a] < 0:
-                lead = "." if p > 0 else ""
-            else:
-                lead = ("(" if opens_branch[a] else "") + bond_symbol(parent[a], a, next(cls for y, cls in adj[a] if y == parent[a]))
             mark = ""
             if centre[a] in (1, -1):
                 # the neighbours as the text names them: parent, hydrogen, ring numbers as written, children in scan order; the
@@ -315,7 +387,7 @@ class Molecule:
                 swaps = sum(named[i] > named[j] for i in range(4) for j in range(i + 1, 4))
                 mark = "@" if centre[a] * (-1 if swaps & 1 else 1) > 0 else "@@"
             out.append(lead + token(a, mark) + "".join(digits) + ")" * closes[p])
-        return "".join(out), centre
+        return "".join(out), centre, ez_codes
 
 
 # ------------------------------------------------------------------------------------------------- the canonical atom order

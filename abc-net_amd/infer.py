@@ -50,7 +50,7 @@ class InferenceRunner:
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
                  assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
                  score_similarity=False, molblocks=False, score_identity=False, smiles=False, smiles_stereo=False,
-                 smiles_canonical=False, aromatize=False):
+                 smiles_canonical=False, aromatize=False, smiles_double_bonds=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -94,6 +94,11 @@ class InferenceRunner:
         smiles_stereo (needs smiles=True): the same stage writes the tetrahedral centres that the predicted wedge bonds and the atom
         positions decide as `@` / `@@` (SmilesWriter(stereo=True)): smiles() is then `m.smiles(stereo=True)`, stereo_stats() says
         how many wedge rows there were and how many centres were marked, flat or unqualified.  The same two launches in the same place
+        smiles_double_bonds (needs smiles=True, refused with smiles_canonical=True; smiles_stereo is allowed): the same stage writes
+        the single bonds at every double bond whose geometry the atom positions decide as `/` or `\\`
+        (SmilesWriter(double_bonds=True)): smiles() is then `m.smiles(double_bonds=True, ...)`, double_bond_stats() says how many
+        double bonds were marked, flat, on a cycle or had twin leaves, double_bond_codes() gives the code of every bond row.  The
+        same two launches in the same place; off (the default): no launch and no byte changes
         smiles_canonical (needs smiles=True, refused with smiles_stereo=True): the canonical atom order of every assembled molecule
         (ops.GraphCanonicalizer) in the same captured chain right after the assembler; the SMILES stage then reads the CANONICAL rows, so
         smiles() is `m.smiles(canonical=True)`: equal strings if and only if equal graphs (this project's rule on a canonical order, not
@@ -127,6 +132,11 @@ class InferenceRunner:
                              "needs assemble=True")
         if smiles_stereo and not smiles:
             raise ValueError("InferenceRunner(smiles_stereo=True) is a form of the SMILES stage: it needs smiles=True")
+        if smiles_double_bonds and not smiles:
+            raise ValueError("InferenceRunner(smiles_double_bonds=True) is a form of the SMILES stage: it needs smiles=True")
+        if smiles_canonical and smiles_double_bonds:
+            raise ValueError("InferenceRunner(smiles_canonical=True, smiles_double_bonds=True): a text with double-bond marks on the "
+                             "canonical order would not be canonical (the drawn geometry is not in the invariant)")
         if smiles_canonical and not smiles:
             raise ValueError("InferenceRunner(smiles_canonical=True) is a form of the SMILES stage: it needs smiles=True")
         if smiles_canonical and smiles_stereo:
@@ -192,7 +202,7 @@ class InferenceRunner:
                 self.canonicalizer = GraphCanonicalizer(rows)
                 self.smiler = SmilesWriter(self.canonicalizer.rows())
             elif smiles:
-                self.smiler = SmilesWriter(rows, stereo=bool(smiles_stereo))
+                self.smiler = SmilesWriter(rows, stereo=bool(smiles_stereo), double_bonds=bool(smiles_double_bonds))
         if evaluate:
             if tuple(model.heads) != HEADS:
                 raise ValueError("InferenceRunner(evaluate=True): the evaluation tables read heads %s, got heads %s" % (list(HEADS), list(model.heads)))
@@ -349,7 +359,7 @@ class InferenceRunner:
     def smiles(self):
         """a SMILES string of every image of the last step, written on the device: what `m.smiles()` gives for the m of
         molecules(), None where that is None (host sync; needs smiles=True); with smiles_stereo=True it is `m.smiles(stereo=True)`,
-        with smiles_canonical=True `m.smiles(canonical=True)`"""
+        with smiles_canonical=True `m.smiles(canonical=True)`, with smiles_double_bonds=True `m.smiles(double_bonds=True, ...)`"""
         smiler = self._need("smiler")
         with torch.cuda.device(self.dev):
             return smiler.smiles()
@@ -381,6 +391,20 @@ class InferenceRunner:
         smiler = self._need("smiler")
         with torch.cuda.device(self.dev):
             return smiler.stereo_stats()
+
+    def double_bond_stats(self):
+        """what became of the candidate double bonds of the last step (SmilesWriter.double_bond_stats: marked, flat, ring, twin and
+        the per-image rows; host sync; needs smiles=True and smiles_double_bonds=True)"""
+        smiler = self._need("smiler")
+        with torch.cuda.device(self.dev):
+            return smiler.double_bond_stats()
+
+    def double_bond_codes(self):
+        """the code of every bond row of the last step (SmilesWriter.double_bond_codes: int32 [B, cap_mol_bonds] on the host; host
+        sync; needs smiles=True and smiles_double_bonds=True)"""
+        smiler = self._need("smiler")
+        with torch.cuda.device(self.dev):
+            return smiler.double_bond_codes()
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""

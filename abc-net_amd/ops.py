@@ -545,14 +545,17 @@ class SmilesWriter(PackedText):
     one static buffer.  Two launches, static buffers, graph-capture safe; `smiles()` is the only host sync (two small D2H copies
     per batch).  The text is deterministic and its graph is the rows' graph; it is NOT RDKit's canonical SMILES (DESIGN.md
     section 7: the rule, and what it leaves out).  stereo=True (abc_write_smiles_stereo): the bytes of `.smiles(stereo=True)`, the
-    tetrahedral centres of the wedge rows written as `@` / `@@`; stereo_stats() and parities() say what became of every candidate."""
+    tetrahedral centres of the wedge rows written as `@` / `@@`; stereo_stats() and parities() say what became of every candidate.
+    double_bonds=True (abc_write_smiles_ez, with or without stereo): the bytes of `.smiles(double_bonds=True)`, the single bonds at
+    every double bond the positions decide written as `/` or `\\`; double_bond_stats() and double_bond_codes() say what became of
+    every class-2 row."""
 
     STATUS_NAMES = ((L.TEXT_BAD_ROW, "ABC_TEXT_BAD_ROW (a vocabulary index outside 0..13, a charge outside -15..15, a bond order "
                                      "outside 1..6, a bond end outside 1..n or on one atom twice, or an atom pair listed twice)"),
                     (L.TEXT_RING_LIMIT, "ABC_TEXT_RING_LIMIT (more than 99 ring bonds are open at once)"),
                     (L.TEXT_OVERFLOW, "ABC_TEXT_OVERFLOW (the batch's text does not fit cap_text)"))
 
-    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, cap_text=None, stereo=False):
+    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, cap_text=None, stereo=False, double_bonds=False):
         """a contract.MoleculeRows (GraphAssembler.rows), or its four device tensors (hand-made rows); cap_atoms at most
         L.MAX_SMILES_ATOMS, cap_mol_bonds at most L.MAX_SMILES_BONDS.  cap_text: bytes of the text buffer; default
         B * abc_smiles_text_bytes, the bound of one image with every token at its widest -- 20 480 bytes per image at the
@@ -562,13 +565,16 @@ class SmilesWriter(PackedText):
         B, cap_atoms, cap_mol_bonds = rows.B, rows.cap_atoms, rows.cap_mol_bonds
         self.lib = L.load()
         dev = rows.device
-        self.stereo = bool(stereo)
-        d = L.SmilesStereoDesc() if self.stereo else L.SmilesDesc()
+        self.stereo, self.double_bonds = bool(stereo), bool(double_bonds)
+        d = L.SmilesEzDesc() if self.double_bonds else (L.SmilesStereoDesc() if self.stereo else L.SmilesDesc())
         text_bytes, work_ints, self._write, self._what = (
-            (self.lib.abc_smiles_stereo_text_bytes, self.lib.abc_smiles_stereo_work_ints, self.lib.abc_write_smiles_stereo, "write_smiles_stereo")
+            (self.lib.abc_smiles_ez_text_bytes, self.lib.abc_smiles_ez_work_ints, self.lib.abc_write_smiles_ez, "write_smiles_ez")
+            if self.double_bonds else (self.lib.abc_smiles_stereo_text_bytes, self.lib.abc_smiles_stereo_work_ints, self.lib.abc_write_smiles_stereo, "write_smiles_stereo")
             if self.stereo else (self.lib.abc_smiles_text_bytes, self.lib.abc_smiles_work_ints, self.lib.abc_write_smiles, "write_smiles"))
         rows.fill(d)
         d.mol_implh = rows.tensors[3].data_ptr()
+        if self.double_bonds:
+            d.tetrahedral = int(self.stereo)
         self.image_bytes = int(text_bytes(C.byref(d)))
         cap_text = B * self.image_bytes if cap_text is None else int(cap_text)
         if not (1 <= cap_text <= 2 ** 31 - 1):
@@ -585,11 +591,16 @@ class SmilesWriter(PackedText):
             self.stats = torch.zeros((B, len(L.SMILES_STEREO_COLUMNS)), dtype=torch.int32, device=dev)
             self.codes = torch.zeros((B, cap_atoms), dtype=torch.int32, device=dev)
             d.stereo_stats, d.stereo_out = self.stats.data_ptr(), self.codes.data_ptr()
+        self.ez_stats = self.ez_codes = None
+        if self.double_bonds:
+            self.ez_stats = torch.zeros((B, len(L.SMILES_EZ_COLUMNS)), dtype=torch.int32, device=dev)
+            self.ez_codes = torch.zeros((B, cap_mol_bonds), dtype=torch.int32, device=dev)
+            d.ez_stats, d.ez_out = self.ez_stats.data_ptr(), self.ez_codes.data_ptr()
         self.d, self.keep = d, rows.tensors
 
     @classmethod
-    def from_assembler(cls, asm, cap_text=None, stereo=False):
-        return cls(asm.rows, cap_text=cap_text, stereo=stereo)
+    def from_assembler(cls, asm, cap_text=None, stereo=False, double_bonds=False):
+        return cls(asm.rows, cap_text=cap_text, stereo=stereo, double_bonds=double_bonds)
 
     def run(self, stream=None):
         L.check(self._write(C.byref(self.d), stream_or_current(stream)), self._what)
@@ -612,6 +623,25 @@ class SmilesWriter(PackedText):
         local parity s(a) of a marked centre, L.STEREO_FLAT, L.STEREO_UNQUALIFIED; 0 past an image's atoms.  Host sync."""
         self._need_stereo("parities")
         return self.codes.cpu()
+
+    def _need_double_bonds(self, what):
+        if not self.double_bonds:
+            raise L.AbcNetHipError("SmilesWriter.%s: the writer was built without double_bonds=True" % what)
+
+    def double_bond_stats(self):
+        """double_bonds=True: what became of the candidate double bonds of the last run -- {"marked", "flat", "ring", "twin"}
+        summed over the batch, and "rows", the four counts of every image (zeros for an image without text).  Host sync."""
+        self._need_double_bonds("double_bond_stats")
+        rows = self.ez_stats.cpu().tolist()
+        out = {name: sum(r[i] for r in rows) for i, name in enumerate(L.SMILES_EZ_COLUMNS)}
+        out["rows"] = rows
+        return out
+
+    def double_bond_codes(self):
+        """double_bonds=True: int32 [B, cap_mol_bonds] on the host, the code of every bond row of the last run: 0 not a candidate,
+        +1 / -1 a marked double bond (together / opposite), L.EZ_FLAT, L.EZ_RING, L.EZ_TWIN; 0 past an image's bonds.  Host sync."""
+        self._need_double_bonds("double_bond_codes")
+        return self.ez_codes.cpu()
 
     def smiles(self):
         """per image: the SMILES as a str, or None for an image without an atom peak or without a bond peak.  Raises

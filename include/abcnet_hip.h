@@ -1298,8 +1298,8 @@ int abc_smiles_desc_size(void);
  *               EMPTY or refused (BAD_ROW, RING_LIMIT).  OVERFLOW does not change it;
  *   stereo_out  optional, per atom row: 0 no candidate, +1 / -1 s(a) of a marked atom, 2 flat, 3 unqualified; every word of the
  *               image's cap_atoms is written by every launch (0 past the atom count and for an image without text).
- * Not covered: double-bond marks ("/", "\"), centres with a multiple bond (sulfoxides, phosphates), three-neighbour centres without
- * a hydrogen, RDKit's special cases for T-shaped drawings, stereo in the identity / similarity scores. */
+ * Not covered: centres with a multiple bond (sulfoxides, phosphates), three-neighbour centres without a hydrogen, RDKit's special
+ * cases for T-shaped drawings, stereo in the identity / similarity scores.  Double-bond marks ("/", "\"): abc_write_smiles_ez, below. */
 typedef struct abc_smiles_stereo_desc {
     const int32_t* mol_counts;   /* the fields of abc_smiles_desc, in its order */
     const int32_t* mol_atoms;
@@ -1322,6 +1322,64 @@ int64_t abc_smiles_stereo_work_ints(const abc_smiles_stereo_desc* d);
 int abc_write_smiles_stereo(const abc_smiles_stereo_desc* d, abc_stream_t stream);
 /* sizeof(abc_smiles_stereo_desc), for a binding's mirror struct */
 int abc_smiles_stereo_desc_size(void);
+
+/* The same text with double-bond stereo: the single bonds at every double bond whose geometry the positions decide are written as
+ * "/" or "\" in place of their (empty) symbol.  Opt-in and apart: abc_write_smiles and abc_write_smiles_stereo keep their bytes.
+ * The same two launches (two more instantiations of the same kernels), integers only, no atomics on global memory, no sync.
+ * Everything of abc_smiles_desc holds; with `tetrahedral` non-zero everything of abc_smiles_stereo_desc too (the two marks are
+ * independent: a centre has only class-1 bonds, so it is never an end).  The rule (DESIGN.md section 7;
+ * decode.Molecule.smiles(double_bonds=True) is the host form):
+ *   graph       the writer's: valid rows, unique pairs, order classes (a wedge row is a class-1 bond); (x, y) is (row, column); only
+ *               signs of cross products are compared, so mirror, rotation and shift change nothing;
+ *   candidate   a bond row of class 2 between a and b (a the lower atom index), both C or N, each of degree 2 or 3 (one or two
+ *               SUBSTITUENTS besides the partner), every substituent bond of class 1.  An atom is an end of at most one candidate;
+ *   code        per bond row, the first that applies: 0 not a candidate; 3 RING: the bond lies on a cycle of ANY size (it is not a
+ *               bridge); 4 TWIN: an end has two substituents of degree 1 with equal symbol, charge and listed-ness in mol_implh;
+ *               2 FLAT: with d = pos(b) - pos(a) and side(e, s) = sign(d.x (pos(s).y - pos(e).y) - d.y (pos(s).x - pos(e).x)) in
+ *               int64, one of the up to six atoms has x or y outside 0..199999, or some side is 0, or the two substituents of one end
+ *               have the same side; else +1 (together) / -1 (opposite): the lowest-index substituents of a and of b have equal /
+ *               unequal side, and the bond is MARKED;
+ *   mark        every substituent bond of a marked double bond D gets a symbol where the text rule writes that bond's symbol, read
+ *               as first atom, symbol, second atom: parent, child for a tree bond; closer (which bears it at its closing digit), opener
+ *               for a ring bond.  "/": the second atom is above the first.  With an orientation u(D) = +1 / -1 and above(e, s) =
+ *               u(D) side(e, s): "/" iff above(first, second) = +1 where the first atom is the end, iff above(second, first) = -1 where
+ *               the second is.  A single bond between ends of two marked double bonds bears one symbol for both, which ties their
+ *               orientations; marked double bonds are bridges, so such groups are trees and have exactly two solutions;
+ *   normal form in every group the symbol written first in the text is "/" (by preorder position of the atom it is written on; at one
+ *               atom the tree bond's before the closings', those in written order);
+ *   example     C (10, 10), C (20, 20), C (20, 30), C (30, 40), rows (1, 2, 1), (2, 3, 2), (3, 4, 1): code -1, "C/C=C/C"; with atom 4
+ *               at (10, 40) code +1, "C/C=C\C".  Stripping "/" and "\" gives the bytes written without the option;
+ *   ez_stats    per image (marked, flat, ring, twin); all zeros for an image that is EMPTY or refused.  OVERFLOW does not change it;
+ *   ez_out      optional, the code of every bond row; every word of the image's cap_mol_bonds is written by every launch (0 past the
+ *               bond count and for an image without text).
+ * The byte bound does not grow (a symbol byte per tree bond and closing is already counted).
+ * Not covered: double bonds on any cycle (macrocyclic E/Z too), equivalence of an end's substituents beyond twin leaves, ends other
+ * than C and N, RDKit's choice of which bonds to mark (all substituent bonds are marked), the canonical order, stereo in the scores. */
+typedef struct abc_smiles_ez_desc {
+    const int32_t* mol_counts;   /* the fields of abc_smiles_stereo_desc, in its order */
+    const int32_t* mol_atoms;
+    const int32_t* mol_bonds;
+    const int32_t* mol_implh;
+    int32_t B, cap_atoms, cap_mol_bonds;
+    uint8_t* text;
+    int32_t* index;
+    int32_t* work;               /* [abc_smiles_ez_work_ints()] */
+    int64_t cap_text;
+    int32_t* stereo_stats;       /* [B][4]: required iff tetrahedral != 0 */
+    int32_t* stereo_out;         /* optional: [B][cap_atoms] (tetrahedral != 0) */
+    int32_t tetrahedral;         /* non-zero: the tetrahedral marks of abc_write_smiles_stereo as well */
+    int32_t* ez_stats;           /* [B][4]: marked, flat, ring, twin */
+    int32_t* ez_out;             /* optional: [B][cap_mol_bonds] */
+} abc_smiles_ez_desc;
+/* abc_smiles_text_bytes, or abc_smiles_stereo_text_bytes with tetrahedral != 0 */
+int64_t abc_smiles_ez_text_bytes(const abc_smiles_ez_desc* d);
+/* as abc_smiles_work_ints, with slices of abc_smiles_ez_text_bytes() */
+int64_t abc_smiles_ez_work_ints(const abc_smiles_ez_desc* d);
+/* the guards of abc_write_smiles_stereo (stereo_stats only with tetrahedral != 0), and a null ez_stats is ABC_EINVAL; nothing is
+ * launched on a refusal */
+int abc_write_smiles_ez(const abc_smiles_ez_desc* d, abc_stream_t stream);
+/* sizeof(abc_smiles_ez_desc), for a binding's mirror struct */
+int abc_smiles_ez_desc_size(void);
 
 /* ---- unet2: CBAM attention + residual (unet2.py:6-74).  See csrc/cbam.hip for the pass structure. ---- */
 typedef struct abc_cbam_channel_desc { /* ChannelAttentionModule (unet2.py:6-22), one MLP evaluation per image */

@@ -33,6 +33,11 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            abc_write_smiles, its step against the plain stage's in the same alternated blocks, smiles() against
            Molecule.smiles(stereo=True), and what became of the fixture's wedge rows (stereo_stats: wedge rows, marked, flat,
            unqualified)
+           --double-bonds: the double-bond marks (abc_write_smiles_ez, InferenceRunner(smiles=True, smiles_double_bonds=True)) under
+           BOTH omega rules in this one process -- the two launches of the four instantiations (plain, tetrahedral, double bonds,
+           both) alone and alternated, the step of the four forms in the same alternated blocks, smiles() against
+           Molecule.smiles(double_bonds=True, ...), and what became of the fixture's class-2 rows (double_bond_stats: marked, flat,
+           ring, twin, and the rows that are no candidate).  profiles/r23_smiles_double_bonds.md is one run
            --canonical: the canonical atom order (csrc/graph_canon.hip, InferenceRunner(smiles=True, smiles_canonical=True)) under
            BOTH omega rules in this one process -- abc_canonical_order alone beside abc_write_smiles, the step with the stage
            against the same step without it (alternated blocks), the images left UNDECIDED, the largest work of an image, smiles()
@@ -52,7 +57,7 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--canonical] [--aromatize]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--double-bonds] [--canonical] [--aromatize]
 """
 import argparse
 import json
@@ -335,6 +340,49 @@ def part_smiles_stereo(r, plain, reps, iters):
     emit({"part": "smiles", "what": "stereo launch", "batch": B, "stereo_us_per_call": [round(a, 2) for a, _ in us],
           "plain_us_per_call": [round(b, 2) for _, b in us],
           "method": "device events around %d back-to-back calls of two launches each (launch gaps included), alternated" % iters})
+
+
+def part_smiles_double_bonds(m, x, steps, warmup, iters=200):
+    """--double-bonds: both omega rules in this process; the four instantiations of the writer side by side"""
+    global RULE
+    kept = RULE
+    forms = [("plain", {}), ("tetrahedral", dict(smiles_stereo=True)), ("double_bonds", dict(smiles_double_bonds=True)),
+             ("both", dict(smiles_stereo=True, smiles_double_bonds=True))]
+    for RULE in ("raw", "peaks"):
+        rs = {}
+        for name, kw in forms:
+            r = InferenceRunner(m, B, S, S, use_graph=True, omega_rule=RULE, assemble=True, smiles=True, **kw)
+            r.load_batch(x.to("cuda"))
+            for _ in range(2):
+                r.step()
+            rs[name] = r
+        torch.cuda.synchronize()
+        mols = rs["plain"].molecules()
+        refused = sum(bool(s & ~3) for s in rs["both"].smiler.status())
+        st = rs["double_bonds"].double_bond_stats()
+        out = {"part": "smiles", "what": "double-bond fixture", "batch": B, "refused_images": refused,
+               "class_2_rows": sum(sum(o == 2 for o in mol.orders) for mol in mols if mol is not None),
+               "images_with_a_class_2_row": sum(any(o == 2 for o in mol.orders) for mol in mols if mol is not None),
+               "images_with_a_mark": sum(row[0] > 0 for row in st["rows"]), "stats_of_both": {k: rs["both"].double_bond_stats()[k] for k in st if k != "rows"}}
+        out.update({k: st[k] for k in ("marked", "flat", "ring", "twin")})
+        out["not_a_candidate"] = out["class_2_rows"] - sum(st[k] for k in ("marked", "flat", "ring", "twin"))
+        if not refused:
+            got = {k: r.smiles() for k, r in rs.items()}
+            want = {k: [None if mol is None else mol.smiles(stereo="smiles_stereo" in kw, double_bonds="smiles_double_bonds" in kw) for mol in mols]
+                    for k, kw in forms}
+            out.update({"equal": got == want, "texts_that_differ_from_plain": sum(a != b for a, b in zip(got["double_bonds"], got["plain"])),
+                        "symbols": sum(t.count("/") + t.count("\\") for t in got["double_bonds"] if t is not None),
+                        "text_bytes": {k: r.smiler.index.cpu().tolist()[B] for k, r in rs.items()}})
+        emit(out)
+        us = [{k: round(launch_us(r.smiler.run, iters), 2) for k, r in rs.items()} for _ in range(3)]
+        emit({"part": "smiles", "what": "double-bond launch", "batch": B, "us_per_call": {k: [u[k] for u in us] for k in rs},
+              "method": "device events around %d back-to-back calls of two launches each (launch gaps included), the four alternated" % iters})
+        med = step_blocks({"assemble+smiles " + k: r for k, r in rs.items()}, steps, warmup, "smiles")
+        emit({"part": "smiles", "what": "double-bond step",
+              "double_bonds_minus_plain_ms": round(med["assemble+smiles double_bonds"] - med["assemble+smiles plain"], 4),
+              "both_minus_tetrahedral_ms": round(med["assemble+smiles both"] - med["assemble+smiles tetrahedral"], 4)})
+        del rs
+    RULE = kept
 
 
 def part_smiles_canonical(m, x, notes, steps, warmup, reps=30, iters=200):
@@ -648,6 +696,7 @@ def main():
     ap.add_argument("--parts", default="step,launch,host,graphs")
     ap.add_argument("--omega-rule", choices=("raw", "peaks"), default="raw")
     ap.add_argument("--stereo", action="store_true", help="the smiles part: the stereo form beside the plain one")
+    ap.add_argument("--double-bonds", action="store_true", help="the smiles part: the double-bond marks, the four instantiations under both omega rules")
     ap.add_argument("--canonical", action="store_true", help="the smiles part: the canonical atom order, under both omega rules")
     ap.add_argument("--aromatize", action="store_true", help="the aromatize part: the aromaticity perception, under both omega rules")
     a = ap.parse_args()
@@ -683,6 +732,8 @@ def main():
         part_text(m, x, a.steps, a.warmup)
     if "smiles" in parts:
         part_smiles(m, x, a.steps, a.warmup, stereo=a.stereo)
+        if a.double_bonds:
+            part_smiles_double_bonds(m, x, a.steps, a.warmup)
         if a.canonical:
             part_smiles_canonical(m, x, notes, a.steps, a.warmup)
     if a.aromatize or "aromatize" in parts:
