@@ -279,13 +279,10 @@ GRAPH_SIM_IDS = 2048    # ABC_SIM_IDS: ids_out is uint64 [B][2][GRAPH_SIM_IDS]
 GRAPH_IDENT_COLUMNS = ("counted", "none", "truncated", "size_equal", "same", "different", "undecided", "levels", "tries",
                        "backtracks", "rounds")
 IDENT_DEFAULT_TRIES, IDENT_DEFAULT_ROUNDS = 4096, 16384     # ABC_IDENT_DEFAULT_TRIES, ABC_IDENT_DEFAULT_ROUNDS
-# the ABC_CANON_* columns of abc_canon_desc.stats; the bits of its status column; the defaults of its budgets
-CANON_COLUMNS = ("status", "leaves", "tries", "rounds", "levels_max", "pruned_trace", "pruned_orbit", "automorphisms", "improved")
-CANON_EMPTY, CANON_TRUNCATED, CANON_UNDECIDED, CANON_COLLISION = 1, 2, 4, 8      # abc_canon_status
-CANON_DEFAULT_TRIES, CANON_DEFAULT_ROUNDS, CANON_ORBIT_LEVELS = 4096, 16384, 8     # ABC_CANON_DEFAULT_TRIES, _ROUNDS, ABC_CANON_ORBIT_LEVELS
-# the ABC_AROM_* columns of abc_aromatic_desc.stats; the codes of its code_out beside the electron counts
-AROMATIC_COLUMNS = ("status", "candidates", "cycles", "aromatic", "rows_changed", "listed")
-AROM_NOT_CANDIDATE, AROM_NONE = -2, -1
+# the ABC_CANON_* columns of abc_canon_desc.stats, the bits of its status column, the defaults of its budgets; the ABC_AROM_* columns of
+# abc_aromatic_desc.stats and the codes of its code_out: defined beside their host forms, which need neither torch nor the library
+from .decode import (AROM_NONE, AROM_NOT_CANDIDATE, AROMATIC_COLUMNS, CANON_COLLISION, CANON_COLUMNS, CANON_DEFAULT_ROUNDS,  # noqa: E402,F401
+                     CANON_DEFAULT_TRIES, CANON_EMPTY, CANON_ORBIT_LEVELS, CANON_TRUNCATED, CANON_UNDECIDED)
 IMG_TRAIN, IMG_TEST = 0, 1
 IMG_NPARAM = 10     # abc_image_param: src_h, src_w, rows, cols, ddx, ddy, salt_thr, pepper_thr, key_lo, key_hi
 SCAN_NPARAM = 2     # abc_scan_param: src_h, src_w

@@ -196,8 +196,11 @@ class MoleculeRows:
         return cls(mol_counts, mol_atoms, mol_bonds, mol_implh if need_implh else None)
 
     def fill(self, d):
-        """the mol_*, B and cap_* fields MolBlockDesc, GraphScoreDesc and GraphSimilarityDesc have in common"""
+        """the mol_*, B and cap_* fields every descriptor that reads the rows has; mol_implh (null when these rows have none) where the
+        descriptor has the field"""
         d.mol_counts, d.mol_atoms, d.mol_bonds = (t.data_ptr() for t in self.tensors[:3])
+        if hasattr(d, "mol_implh"):
+            d.mol_implh = L.ptr(self.tensors[3])
         d.B, d.cap_atoms, d.cap_mol_bonds = self.B, self.cap_atoms, self.cap_mol_bonds
 
 

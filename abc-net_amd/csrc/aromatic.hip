@@ -128,22 +128,15 @@ __global__ __launch_bounds__(GT) void aromatic_kernel(const abc_aromatic_desc d)
     const bool mol = d.mol_counts != nullptr;
     const int cap = mol ? d.cap_atoms : d.max_atoms, cap_bonds = mol ? d.cap_mol_bonds : d.max_bonds;
 
-    // ---- the image: counts clamped to their capacities, no rows when EMPTY (as graph_canon.hip)
+    // ---- the image (mol_rows.hpp), of the side that was given
     int status = 0, n = 0, nrows = 0, nlisted = 0;
     const int *pa = nullptr, *pb = nullptr, *ph = nullptr, *ra = nullptr, *rb = nullptr;
     if (mol) {
-        const int* mc = d.mol_counts + (size_t)b * 4;
-        status = mc[3] & (ABC_MOL_EMPTY | ABC_MOL_TRUNCATED);
-        const bool empty = (status & ABC_MOL_EMPTY) != 0;
-        n = empty ? 0 : clampi(mc[0], 0, d.cap_atoms), nrows = empty ? 0 : clampi(mc[1], 0, d.cap_mol_bonds);
-        nlisted = empty || d.mol_implh == nullptr ? 0 : clampi(mc[2], 0, d.cap_atoms);
-        pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
-        pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
-        ph = d.mol_implh != nullptr ? d.mol_implh + (size_t)b * d.cap_atoms : nullptr;
+        const MolImage im = mol_image(d, b);
+        status = im.status, n = im.na, nrows = im.nb, nlisted = im.nh, pa = im.pa, pb = im.pb, ph = im.ph;
     } else {
-        n = clampi(d.rec_counts[b], 0, d.max_atoms), nrows = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
-        ra = d.rec_atoms + (size_t)b * d.max_atoms * REC_ATOM_W;
-        rb = d.rec_bonds + (size_t)b * d.max_bonds * REC_BOND_W;
+        const RecImage im = rec_image(d, b);
+        n = im.nt, nrows = im.m, ra = im.ra, rb = im.rb;
     }
     auto row = [&](int q) __attribute__((always_inline)) { return mol ? mol_row(pb, q, n) : rec_row(rb, q, n); };
     auto sym_of = [&](int a) __attribute__((always_inline)) { return (int)g.sym[a]; };
@@ -319,45 +312,25 @@ __global__ __launch_bounds__(GT) void aromatic_kernel(const abc_aromatic_desc d)
     }
 }
 
-bool overlap(const void* p, size_t np, const void* q, size_t nq) {
-    const char *a = (const char*)p, *c = (const char*)q;
-    return p != nullptr && q != nullptr && a < c + nq && c < a + np;
-}
-
 }  // namespace
 
 extern "C" int abc_aromatic_desc_size(void) { return (int)sizeof(abc_aromatic_desc); }
 
 extern "C" int abc_perceive_aromatic(const abc_aromatic_desc* d, abc_stream_t stream) {
-    if (!d) return abc_fail(ABC_EINVAL, "perceive_aromatic: null descriptor");
-    const bool mol = d->mol_counts != nullptr, rec = d->rec_counts != nullptr;
-    if (d->B < 1) return abc_fail(ABC_EINVAL, "perceive_aromatic: empty");
-    if (mol == rec) return abc_fail(ABC_EINVAL, "perceive_aromatic: give the molecule rows or the graph records, one side");
+    const char* const entry = "perceive_aromatic";
+    bool mol;
+    if (const int rc = abc_one_side(entry, d, mol)) return rc;
     if (!d->stats) return abc_fail(ABC_EINVAL, "perceive_aromatic: null output (stats)");
     const int rows_given = (d->out_counts != nullptr) + (d->out_atoms != nullptr) + (d->out_bonds != nullptr) + (d->out_implh != nullptr);
-    if (mol) {
-        if (!d->mol_atoms || !d->mol_bonds) return abc_fail(ABC_EINVAL, "perceive_aromatic: null molecule buffer");
-        if (rows_given != 4 || d->out_rec_bonds) return abc_fail(ABC_EINVAL, "perceive_aromatic: the molecule side writes out_counts, out_atoms, out_bonds and out_implh, all four");
-        if (d->cap_atoms < 1 || d->cap_mol_bonds < 1) return abc_fail(ABC_EINVAL, "perceive_aromatic: cap_atoms and cap_mol_bonds must be >= 1");
-        if (d->cap_atoms > MAX_ATOMS) return abc_fail(ABC_EUNSUPPORTED, "perceive_aromatic: cap_atoms must be <= 512");
-    } else {
-        if (!d->rec_atoms || !d->rec_bonds) return abc_fail(ABC_EINVAL, "perceive_aromatic: null record buffer");
-        if (rows_given != 0 || !d->out_rec_bonds) return abc_fail(ABC_EINVAL, "perceive_aromatic: the records side writes out_rec_bonds alone");
-        if (d->max_atoms < 1 || d->max_bonds < 1) return abc_fail(ABC_EINVAL, "perceive_aromatic: max_atoms and max_bonds must be >= 1");
-        if (d->max_atoms > MAX_ATOMS) return abc_fail(ABC_EUNSUPPORTED, "perceive_aromatic: max_atoms must be <= 512");
-    }
+    if (const int rc = abc_one_side_buffers(entry, d, mol)) return rc;
+    if (mol && (rows_given != 4 || d->out_rec_bonds))
+        return abc_fail(ABC_EINVAL, "perceive_aromatic: the molecule side writes out_counts, out_atoms, out_bonds and out_implh, all four");
+    if (!mol && (rows_given != 0 || !d->out_rec_bonds)) return abc_fail(ABC_EINVAL, "perceive_aromatic: the records side writes out_rec_bonds alone");
+    if (const int rc = abc_one_side_capacities(entry, d, mol)) return rc;
     const size_t B = (size_t)d->B, cap = (size_t)(mol ? d->cap_atoms : d->max_atoms), cb = (size_t)(mol ? d->cap_mol_bonds : d->max_bonds);
-    // (pointer, bytes) of every input and of every output: no output may overlap an input or another output
-    const void* in[7] = {d->mol_counts, d->mol_atoms, d->mol_bonds, d->mol_implh, d->rec_atoms, d->rec_bonds, d->rec_counts};
-    const size_t nin[7] = {B * 16, B * cap * ATOM_W * 4, B * cb * MOL_BOND_W * 4, B * cap * 4, B * cap * REC_ATOM_W * 4, B * cb * REC_BOND_W * 4, B * 8};
-    const void* out[7] = {d->stats, d->code_out, d->out_counts, d->out_atoms, d->out_bonds, d->out_implh, d->out_rec_bonds};
-    const size_t nout[7] = {B * NCOL * 4, B * cap * 4, B * 16, B * cap * ATOM_W * 4, B * cb * MOL_BOND_W * 4, B * cap * 4, B * cb * REC_BOND_W * 4};
-    for (int o = 0; o < 7; ++o) {
-        for (int i = 0; i < 7; ++i)
-            if (overlap(out[o], nout[o], in[i], nin[i])) return abc_fail(ABC_EINVAL, "perceive_aromatic: an output overlaps an input");
-        for (int o2 = 0; o2 < o; ++o2)
-            if (overlap(out[o], nout[o], out[o2], nout[o2])) return abc_fail(ABC_EINVAL, "perceive_aromatic: two outputs overlap");
-    }
+    const abc_extent out[7] = {{d->stats, B * NCOL * 4}, {d->code_out, B * cap * 4}, {d->out_counts, B * 16}, {d->out_atoms, B * cap * ATOM_W * 4},
+                               {d->out_bonds, B * cb * MOL_BOND_W * 4}, {d->out_implh, B * cap * 4}, {d->out_rec_bonds, B * cb * REC_BOND_W * 4}};
+    if (const int rc = abc_one_side_overlap(entry, d, mol, out)) return rc;
     hipLaunchKernelGGL(aromatic_kernel, dim3(d->B), dim3(GT), 0, (hipStream_t)stream, *d);
-    return abc_check_launch("perceive_aromatic");
+    return abc_check_launch(entry);
 }

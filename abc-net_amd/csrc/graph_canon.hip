@@ -75,22 +75,15 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
     const int max_tries = d.max_tries > 0 ? d.max_tries : ABC_CANON_DEFAULT_TRIES;
     const int max_rounds = d.max_rounds > 0 ? d.max_rounds : ABC_CANON_DEFAULT_ROUNDS;
 
-    // ---- the image: counts clamped to their capacities, no rows when EMPTY
+    // ---- the image (mol_rows.hpp), of the side that was given
     int status = 0, na = 0, nrows = 0, nt = 0, nlisted = 0;      // na: molecule atoms; nt: record atoms; nrows: bond rows of the side
     const int *pa = nullptr, *pb = nullptr, *ph = nullptr, *ra = nullptr, *rb = nullptr;
     if (mol) {
-        const int* mc = d.mol_counts + (size_t)b * 4;
-        status = mc[3] & (ABC_MOL_EMPTY | ABC_MOL_TRUNCATED);
-        const bool empty = (status & ABC_MOL_EMPTY) != 0;
-        na = empty ? 0 : clampi(mc[0], 0, d.cap_atoms), nrows = empty ? 0 : clampi(mc[1], 0, d.cap_mol_bonds);
-        nlisted = empty || d.mol_implh == nullptr ? 0 : clampi(mc[2], 0, d.cap_atoms);
-        pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
-        pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
-        ph = d.mol_implh != nullptr ? d.mol_implh + (size_t)b * d.cap_atoms : nullptr;
+        const MolImage im = mol_image(d, b);
+        status = im.status, na = im.na, nrows = im.nb, nlisted = im.nh, pa = im.pa, pb = im.pb, ph = im.ph;
     } else {
-        nt = clampi(d.rec_counts[b], 0, d.max_atoms), nrows = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
-        ra = d.rec_atoms + (size_t)b * d.max_atoms * REC_ATOM_W;
-        rb = d.rec_bonds + (size_t)b * d.max_bonds * REC_BOND_W;
+        const RecImage im = rec_image(d, b);
+        nt = im.nt, nrows = im.m, ra = im.ra, rb = im.rb;
     }
     const bool empty = (status & ABC_CANON_EMPTY) != 0;
     static_assert((int)ABC_CANON_EMPTY == (int)ABC_MOL_EMPTY && (int)ABC_CANON_TRUNCATED == (int)ABC_MOL_TRUNCATED, "the two bits are copied");
@@ -489,48 +482,28 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
     }
 }
 
-bool overlap(const void* p, size_t np, const void* q, size_t nq) {
-    const char *a = (const char*)p, *c = (const char*)q;
-    return p != nullptr && q != nullptr && a < c + nq && c < a + np;
-}
-
 }  // namespace
 
 extern "C" int abc_canon_desc_size(void) { return (int)sizeof(abc_canon_desc); }
 
 extern "C" int abc_canonical_order(const abc_canon_desc* d, abc_stream_t stream) {
-    const bool mol = d->mol_counts != nullptr, rec = d->rec_counts != nullptr;
-    if (d->B < 1) return abc_fail(ABC_EINVAL, "canonical_order: empty");
-    if (mol == rec) return abc_fail(ABC_EINVAL, "canonical_order: give the molecule rows or the graph records, one side");
+    const char* const entry = "canonical_order";
+    bool mol;
+    if (const int rc = abc_one_side(entry, d, mol)) return rc;
     if (d->max_tries < 0) return abc_fail(ABC_EINVAL, "canonical_order: max_tries must be >= 0 (0: the default)");
     if (d->max_rounds < 0) return abc_fail(ABC_EINVAL, "canonical_order: max_rounds must be >= 0 (0: the default)");
     if (!d->order || !d->stats || !d->key) return abc_fail(ABC_EINVAL, "canonical_order: null output (order, stats, key)");
     const int rows_given = (d->out_counts != nullptr) + (d->out_atoms != nullptr) + (d->out_bonds != nullptr) + (d->out_implh != nullptr);
     if (rows_given != 0 && rows_given != 4) return abc_fail(ABC_EINVAL, "canonical_order: the canonical rows are four buffers, or none");
-    if (mol) {
-        if (!d->mol_atoms || !d->mol_bonds) return abc_fail(ABC_EINVAL, "canonical_order: null molecule buffer");
-        if (d->cap_atoms < 1 || d->cap_mol_bonds < 1) return abc_fail(ABC_EINVAL, "canonical_order: cap_atoms and cap_mol_bonds must be >= 1");
-        if (d->cap_atoms > MAX_ATOMS) return abc_fail(ABC_EUNSUPPORTED, "canonical_order: cap_atoms must be <= 512");
-        if (rows_given && d->cap_mol_bonds > MAX_ROW_BONDS)
-            return abc_fail(ABC_EUNSUPPORTED, "canonical_order: cap_mol_bonds must be <= 4096 when the canonical rows are requested");
-    } else {
-        if (!d->rec_atoms || !d->rec_bonds) return abc_fail(ABC_EINVAL, "canonical_order: null record buffer");
-        if (d->max_atoms < 1 || d->max_bonds < 1) return abc_fail(ABC_EINVAL, "canonical_order: max_atoms and max_bonds must be >= 1");
-        if (d->max_atoms > MAX_ATOMS) return abc_fail(ABC_EUNSUPPORTED, "canonical_order: max_atoms must be <= 512");
-        if (rows_given) return abc_fail(ABC_EINVAL, "canonical_order: the canonical rows are the molecule side's");
-    }
+    if (const int rc = abc_one_side_buffers(entry, d, mol)) return rc;
+    if (const int rc = abc_one_side_capacities(entry, d, mol)) return rc;
+    if (mol && rows_given && d->cap_mol_bonds > MAX_ROW_BONDS)
+        return abc_fail(ABC_EUNSUPPORTED, "canonical_order: cap_mol_bonds must be <= 4096 when the canonical rows are requested");
+    if (!mol && rows_given) return abc_fail(ABC_EINVAL, "canonical_order: the canonical rows are the molecule side's");
     const size_t B = (size_t)d->B, cap = (size_t)(mol ? d->cap_atoms : d->max_atoms), cb = (size_t)(mol ? d->cap_mol_bonds : d->max_bonds);
-    // (pointer, bytes) of every input and of every output: no output may overlap an input or another output
-    const void* in[7] = {d->mol_counts, d->mol_atoms, d->mol_bonds, d->mol_implh, d->rec_atoms, d->rec_bonds, d->rec_counts};
-    const size_t nin[7] = {B * 16, B * cap * ATOM_W * 4, B * cb * MOL_BOND_W * 4, B * cap * 4, B * cap * REC_ATOM_W * 4, B * cb * REC_BOND_W * 4, B * 8};
-    const void* out[8] = {d->order, d->stats, d->key, d->cert_out, d->out_counts, d->out_atoms, d->out_bonds, d->out_implh};
-    const size_t nout[8] = {B * cap * 4, B * NCOL * 4, B * 16, B * (2 + cap + 3 * cb) * 4, B * 16, B * cap * ATOM_W * 4, B * cb * MOL_BOND_W * 4, B * cap * 4};
-    for (int o = 0; o < 8; ++o) {
-        for (int i = 0; i < 7; ++i)
-            if (overlap(out[o], nout[o], in[i], nin[i])) return abc_fail(ABC_EINVAL, "canonical_order: an output overlaps an input");
-        for (int o2 = 0; o2 < o; ++o2)
-            if (overlap(out[o], nout[o], out[o2], nout[o2])) return abc_fail(ABC_EINVAL, "canonical_order: two outputs overlap");
-    }
+    const abc_extent out[8] = {{d->order, B * cap * 4}, {d->stats, B * NCOL * 4}, {d->key, B * 16}, {d->cert_out, B * (2 + cap + 3 * cb) * 4},
+                               {d->out_counts, B * 16}, {d->out_atoms, B * cap * ATOM_W * 4}, {d->out_bonds, B * cb * MOL_BOND_W * 4}, {d->out_implh, B * cap * 4}};
+    if (const int rc = abc_one_side_overlap(entry, d, mol, out)) return rc;
     hipLaunchKernelGGL(graph_canon_kernel, dim3(d->B), dim3(GT), 0, (hipStream_t)stream, *d);
-    return abc_check_launch("canonical_order");
+    return abc_check_launch(entry);
 }

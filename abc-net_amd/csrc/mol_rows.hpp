@@ -27,11 +27,65 @@ __device__ inline bool rec_ends(const int* rb, int k, int nt, int& i, int& j) {
     return i >= 0 && j >= 0 && i < nt && j < nt && i != j;
 }
 
-// image b of a scoring kernel (both descriptors name these fields alike): counts clamped to their capacities, no rows when EMPTY
-struct ScoredImage {
-    int nt, m, status, na, nb;         // record atoms and bonds, abc_mol_status bits, molecule atoms and bonds
+// ---- the one reader of an image per side: counts clamped to their capacities, no rows when EMPTY (MolCounts below: the text kernels')
+// the molecule side of image b (every descriptor names these fields alike).  status: the two bits the assembler set; nh = 0 and ph null
+// for a descriptor whose mol_implh is null or that has no such field
+struct MolImage {
+    int status, na, nb, nh;            // EMPTY | TRUNCATED of abc_mol_status, atoms, bonds, implicit-H entries
     bool empty;
-    const int *pa, *pb, *ra, *rb;      // mol_atoms, mol_bonds, rec_atoms, rec_bonds of the image
+    const int *pa, *pb, *ph;           // mol_atoms, mol_bonds, mol_implh of the image
+};
+// the counts row of image b alone, clamped to the capacities but NOT zeroed when EMPTY, and the two status bits: what mol_image starts
+// from, and the whole reader of the text kernels (molblock.hip, smiles.hip), which test EMPTY first, always have mol_implh and measured
+// slower through mol_image (profiles/r24_image_reader.md).  The four words are read before anything is decided: one load of the row
+struct MolCounts { int na, nb, nh, status; };
+template <class Desc>
+__device__ inline MolCounts mol_counts_row(const Desc& d, int b) {
+    const int* mc = d.mol_counts + (size_t)b * 4;
+    MolCounts c;
+    c.na = clampi(mc[0], 0, d.cap_atoms);
+    c.nb = clampi(mc[1], 0, d.cap_mol_bonds);
+    c.nh = clampi(mc[2], 0, d.cap_atoms);
+    c.status = mc[3] & (ABC_MOL_EMPTY | ABC_MOL_TRUNCATED);
+    return c;
+}
+// d.mol_implh, or null for a descriptor without the field (the scoring descriptors: scored_image goes through mol_image too).  The
+// int / long parameter only ranks the overloads: the first is taken wherever it compiles
+template <class Desc> __device__ inline auto implh_of(const Desc& d, int) -> decltype(d.mol_implh) { return d.mol_implh; }
+template <class Desc> __device__ inline const int* implh_of(const Desc&, long) { return nullptr; }
+template <class Desc>
+__device__ inline MolImage mol_image(const Desc& d, int b) {
+    const MolCounts c = mol_counts_row(d, b);
+    const int* implh = implh_of(d, 0);
+    MolImage s;
+    s.status = c.status;
+    s.empty = (s.status & ABC_MOL_EMPTY) != 0;
+    s.na = s.empty ? 0 : c.na, s.nb = s.empty ? 0 : c.nb;
+    s.nh = s.empty || implh == nullptr ? 0 : c.nh;
+    s.pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
+    s.pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
+    s.ph = implh != nullptr ? implh + (size_t)b * d.cap_atoms : nullptr;
+    return s;
+}
+// the record side of image b
+struct RecImage {
+    int nt, m;                         // record atoms and bonds
+    const int *ra, *rb;                // rec_atoms, rec_bonds of the image
+};
+template <class Desc>
+__device__ inline RecImage rec_image(const Desc& d, int b) {
+    RecImage s;
+    s.nt = clampi(d.rec_counts[b], 0, d.max_atoms), s.m = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
+    s.ra = d.rec_atoms + (size_t)b * d.max_atoms * REC_ATOM_W;
+    s.rb = d.rec_bonds + (size_t)b * d.max_bonds * REC_BOND_W;
+    return s;
+}
+
+// image b of a scoring kernel: both sides (the scoring kernels read no status bit beyond MolImage's two)
+struct ScoredImage {
+    int nt, m, status, na, nb;
+    bool empty;
+    const int *pa, *pb, *ra, *rb;
 };
 // false for an image at or past n_valid: its row is zeroed and the workgroup has nothing more to do (uniform)
 template <int NCOL, class Desc>
@@ -41,15 +95,9 @@ __device__ inline bool scored_image(const Desc& d, int b, int tid, ScoredImage& 
         if (tid < NCOL) d.rows[(size_t)b * NCOL + tid] = 0;
         return false;
     }
-    s.nt = clampi(d.rec_counts[b], 0, d.max_atoms), s.m = clampi(d.rec_counts[d.B + b], 0, d.max_bonds);
-    const int* mc = d.mol_counts + (size_t)b * 4;
-    s.status = mc[3];
-    s.empty = (s.status & ABC_MOL_EMPTY) != 0;
-    s.na = s.empty ? 0 : clampi(mc[0], 0, d.cap_atoms), s.nb = s.empty ? 0 : clampi(mc[1], 0, d.cap_mol_bonds);
-    s.pa = d.mol_atoms + (size_t)b * d.cap_atoms * ATOM_W;
-    s.pb = d.mol_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W;
-    s.ra = d.rec_atoms + (size_t)b * d.max_atoms * REC_ATOM_W;
-    s.rb = d.rec_bonds + (size_t)b * d.max_bonds * REC_BOND_W;
+    const RecImage r = rec_image(d, b);
+    const MolImage m = mol_image(d, b);
+    s = {r.nt, r.m, m.status, m.na, m.nb, m.empty, m.pa, m.pb, r.ra, r.rb};
     return true;
 }
 

@@ -186,18 +186,6 @@ __device__ inline int slb_len(int n) { return LIT_LEN(SLB_HEAD) + ndig((unsigned
 
 __device__ inline int head_len(int na, int nb) { return LIT_LEN(HEAD_TEXT) + int_len(na, 3) + int_len(nb, 3) + LIT_LEN(COUNTS_TAIL); }
 
-// the counts of image b, clamped to the capacities, and the two status bits the assembler set
-struct Counts { int na, nb, nh, status; };
-__device__ inline Counts read_counts(const abc_molblock_desc& d, int b) {
-    const int* mc = d.mol_counts + (size_t)b * 4;
-    Counts c;
-    c.na = clampi(mc[0], 0, d.cap_atoms);
-    c.nb = clampi(mc[1], 0, d.cap_mol_bonds);
-    c.nh = clampi(mc[2], 0, d.cap_atoms);
-    c.status = mc[3] & (ABC_MOL_EMPTY | ABC_MOL_TRUNCATED);
-    return c;
-}
-
 // rows [lo, hi) of thread tid when n rows are dealt out in contiguous ranges
 __device__ inline void my_range(int n, int tid, int& lo, int& hi) { text_pack::my_range<MT>(n, tid, lo, hi); }
 
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(MT) void molblock_size_kernel(const abc_molblock_de
     __shared__ unsigned wt[MT / 64 + 1];
     __shared__ int flags[2];             // charged atoms, a refused row
     const int b = blockIdx.x, tid = threadIdx.x;
-    const Counts c = read_counts(d, b);
+    const MolCounts c = mol_counts_row(d, b);
     if (c.status & ABC_MOL_EMPTY) {
         if (tid == 0) d.work[b] = 0;
         return;
@@ -242,7 +230,7 @@ __global__ __launch_bounds__(MT) void molblock_write_kernel(const abc_molblock_d
     const int b = blockIdx.x, tid = threadIdx.x;
     int* offsets = d.index;
     int* status_out = d.index + d.B + 1;
-    const Counts c = read_counts(d, b);
+    const MolCounts c = mol_counts_row(d, b);
 
     // ---- the prefix rule (text_pack.hpp): the running total in front of image b and through it, and the largest that still fits
     if (tid == 0) charged_all = 0;       // (published by the rule's barriers)

@@ -340,18 +340,6 @@ template <int MODE> struct DescOf { typedef abc_smiles_ez_desc type; };
 template <> struct DescOf<0> { typedef abc_smiles_desc type; };
 template <> struct DescOf<1> { typedef abc_smiles_stereo_desc type; };
 
-struct Counts { int na, nb, nh, status; };
-template <class Desc>
-__device__ inline Counts read_counts(const Desc& d, int b) {
-    const int* mc = d.mol_counts + (size_t)b * 4;
-    Counts c;
-    c.na = clampi(mc[0], 0, d.cap_atoms);
-    c.nb = clampi(mc[1], 0, d.cap_mol_bonds);
-    c.nh = clampi(mc[2], 0, d.cap_atoms);
-    c.status = mc[3] & (ABC_MOL_EMPTY | ABC_MOL_TRUNCATED);
-    return c;
-}
-
 // bytes one image may take at these capacities (abc_smiles_text_bytes, abc_smiles_stereo_text_bytes: a marked token is two bytes
 // longer and never bare): also the stride of the slices of `work`
 template <bool STEREO>
@@ -387,7 +375,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     __shared__ signed char centre[STEREO ? MAX_ATOMS : 1];      // <stereo> the code of every atom
     __shared__ int tally[4];                                    // <stereo> marked, flat, unqualified, wedge rows
     const int b = blockIdx.x, tid = threadIdx.x;
-    const Counts c = read_counts(d, b);
+    const MolCounts c = mol_counts_row(d, b);
     const int na = c.na, nb = c.nb, slots = 2 * nb;
     if ((c.status & ABC_MOL_EMPTY) || na == 0) {      // (uniform.  Bonds without an atom cannot be: their ends are outside 1..0)
         if (tid == 0) d.work[b] = (c.status & ABC_MOL_EMPTY) || nb == 0 ? 0 : LEN_BAD_ROW;
@@ -676,7 +664,7 @@ __global__ __launch_bounds__(ST) void smiles_pack_kernel(const typename DescOf<M
     if (tid == 0) {
         if (b == 0) offsets[0] = 0;
         offsets[b + 1] = (int)span.fits;      // (fits <= cap_text <= INT32_MAX; == through unless this image overflows)
-        status_out[b] = read_counts(d, b).status | (len == LEN_BAD_ROW ? ABC_TEXT_BAD_ROW : 0) | (len == LEN_RING_LIMIT ? ABC_TEXT_RING_LIMIT : 0)
+        status_out[b] = mol_counts_row(d, b).status | (len == LEN_BAD_ROW ? ABC_TEXT_BAD_ROW : 0) | (len == LEN_RING_LIMIT ? ABC_TEXT_RING_LIMIT : 0)
                         | (overflow ? ABC_TEXT_OVERFLOW : 0);
     }
     if (overflow || len <= 0) return;

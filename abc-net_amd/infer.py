@@ -45,6 +45,29 @@ def launch_order():
     return order
 
 
+# flags, the flags each of them needs, what the refusal says the flag does -- checked in this order, then FLAG_REFUSED in its order
+FLAG_NEEDS = ((("score_graphs", "score_similarity", "score_identity"), ("assemble", "evaluate"), "scores the assembled molecules of an evaluating step"),
+              (("molblocks", "smiles"), ("assemble",), "writes the text of the assembled molecules of the step"),
+              (("aromatize",), ("assemble",), "perceives the aromatic rings of the assembled molecules of the step"),
+              (("smiles_stereo", "smiles_double_bonds", "smiles_canonical"), ("smiles",), "is a form of the SMILES stage"))
+# a flag, the flag it is refused with, why
+FLAG_REFUSED = (("smiles_canonical", "smiles_double_bonds", "a text with double-bond marks on the canonical order would not be canonical "
+                 "(the drawn geometry is not in the invariant)"),
+                ("smiles_canonical", "smiles_stereo", "a stereo text on the canonical order would not be canonical (wedge ownership and the "
+                 "drawn geometry are not in the invariant)"))
+
+
+def check_flags(flags):
+    """ValueError for the first rule of FLAG_NEEDS, then of FLAG_REFUSED, that the constructor flags {name: value} break"""
+    for group, needs, does in FLAG_NEEDS:
+        for flag in group:
+            if flags[flag] and not all(flags[n] for n in needs):
+                raise ValueError("InferenceRunner(%s=True) %s: it needs %s" % (flag, does, " and ".join(n + "=True" for n in needs)))
+    for flag, other, why in FLAG_REFUSED:
+        if flags[flag] and flags[other]:
+            raise ValueError("InferenceRunner(%s=True, %s=True): %s" % (flag, other, why))
+
+
 class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
@@ -119,29 +142,9 @@ class InferenceRunner:
         if omega_rule not in OMEGA_RULES:
             raise ValueError("InferenceRunner: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
         self.omega_rule = omega_rule
-        for flag, on in (("score_graphs", score_graphs), ("score_similarity", score_similarity), ("score_identity", score_identity)):
-            if on and not (assemble and evaluate):
-                raise ValueError("InferenceRunner(%s=True) scores the assembled molecules of an evaluating step: it needs "
-                                 "assemble=True and evaluate=True" % flag)
-        for flag, on in (("molblocks", molblocks), ("smiles", smiles)):
-            if on and not assemble:
-                raise ValueError("InferenceRunner(%s=True) writes the text of the assembled molecules of the step: it needs "
-                                 "assemble=True" % flag)
-        if aromatize and not assemble:
-            raise ValueError("InferenceRunner(aromatize=True) perceives the aromatic rings of the assembled molecules of the step: it "
-                             "needs assemble=True")
-        if smiles_stereo and not smiles:
-            raise ValueError("InferenceRunner(smiles_stereo=True) is a form of the SMILES stage: it needs smiles=True")
-        if smiles_double_bonds and not smiles:
-            raise ValueError("InferenceRunner(smiles_double_bonds=True) is a form of the SMILES stage: it needs smiles=True")
-        if smiles_canonical and smiles_double_bonds:
-            raise ValueError("InferenceRunner(smiles_canonical=True, smiles_double_bonds=True): a text with double-bond marks on the "
-                             "canonical order would not be canonical (the drawn geometry is not in the invariant)")
-        if smiles_canonical and not smiles:
-            raise ValueError("InferenceRunner(smiles_canonical=True) is a form of the SMILES stage: it needs smiles=True")
-        if smiles_canonical and smiles_stereo:
-            raise ValueError("InferenceRunner(smiles_canonical=True, smiles_stereo=True): a stereo text on the canonical order would not "
-                             "be canonical (wedge ownership and the drawn geometry are not in the invariant)")
+        check_flags(dict(assemble=assemble, evaluate=evaluate, score_graphs=score_graphs, score_similarity=score_similarity,
+                         score_identity=score_identity, molblocks=molblocks, smiles=smiles, aromatize=aromatize, smiles_stereo=smiles_stereo,
+                         smiles_double_bonds=smiles_double_bonds, smiles_canonical=smiles_canonical))
         extract = bool(extract) or bool(assemble)
         check_nms_heads(model.heads, "InferenceRunner")
         if extract and tuple(model.heads) != HEADS:
@@ -242,6 +245,12 @@ class InferenceRunner:
         if op is None:
             raise L.AbcNetHipError("InferenceRunner was built without %s=True" % STAGES[attr])
         return op
+
+    def _read(self, attr, method):
+        """a host read-back of the stage `attr` (built, or AbcNetHipError) with the runner's device current"""
+        op = self._need(attr)
+        with torch.cuda.device(self.dev):
+            return getattr(op, method)()
 
     def _build_evaluator(self, target_flags):
         from .ops import EvalTables
@@ -352,59 +361,44 @@ class InferenceRunner:
     def molblocks(self):
         """the mol block (str) of every image of the last step, written on the device: what `m.molblock()` gives for the m of
         molecules(), None where that is None (host sync; needs molblocks=True)"""
-        texter = self._need("texter")
-        with torch.cuda.device(self.dev):
-            return texter.molblocks()
+        return self._read("texter", "molblocks")
 
     def smiles(self):
         """a SMILES string of every image of the last step, written on the device: what `m.smiles()` gives for the m of
         molecules(), None where that is None (host sync; needs smiles=True); with smiles_stereo=True it is `m.smiles(stereo=True)`,
         with smiles_canonical=True `m.smiles(canonical=True)`, with smiles_double_bonds=True `m.smiles(double_bonds=True, ...)`"""
-        smiler = self._need("smiler")
-        with torch.cuda.device(self.dev):
-            return smiler.smiles()
+        return self._read("smiler", "smiles")
 
     def canonical_stats(self):
         """the canonical search of every image of the last step (GraphCanonicalizer.stats: the L.CANON_COLUMNS, `status` with the
         L.CANON_UNDECIDED / L.CANON_COLLISION bits; host sync; needs smiles_canonical=True)"""
-        op = self._need("canonicalizer")
-        with torch.cuda.device(self.dev):
-            return op.stats()
+        return self._read("canonicalizer", "stats")
 
     def canonical_keys(self):
         """the two hash words of every image's canonical graph (GraphCanonicalizer.keys; host sync; needs smiles_canonical=True)"""
-        op = self._need("canonicalizer")
-        with torch.cuda.device(self.dev):
-            return op.keys()
+        return self._read("canonicalizer", "keys")
 
     def aromatic_stats(self):
         """the aromaticity perception of every image of the last step (AromaticityPerceiver.stats: the L.AROMATIC_COLUMNS -- status,
         candidates, cycles, aromatic, rows_changed, listed; host sync; needs aromatize=True); with staged graph records a pair:
         the molecules' rows, then the records'"""
-        op = self._need("aromatizer")
-        with torch.cuda.device(self.dev):
-            return op.stats() if self.record_aromatizer is None else (op.stats(), self.record_aromatizer.stats())
+        stats = self._read("aromatizer", "stats")
+        return stats if self.record_aromatizer is None else (stats, self._read("record_aromatizer", "stats"))
 
     def stereo_stats(self):
         """what became of the wedge rows of the last step (SmilesWriter.stereo_stats: marked, flat, unqualified, wedge_rows and the
         per-image rows; host sync; needs smiles=True and smiles_stereo=True)"""
-        smiler = self._need("smiler")
-        with torch.cuda.device(self.dev):
-            return smiler.stereo_stats()
+        return self._read("smiler", "stereo_stats")
 
     def double_bond_stats(self):
         """what became of the candidate double bonds of the last step (SmilesWriter.double_bond_stats: marked, flat, ring, twin and
         the per-image rows; host sync; needs smiles=True and smiles_double_bonds=True)"""
-        smiler = self._need("smiler")
-        with torch.cuda.device(self.dev):
-            return smiler.double_bond_stats()
+        return self._read("smiler", "double_bond_stats")
 
     def double_bond_codes(self):
         """the code of every bond row of the last step (SmilesWriter.double_bond_codes: int32 [B, cap_mol_bonds] on the host; host
         sync; needs smiles=True and smiles_double_bonds=True)"""
-        smiler = self._need("smiler")
-        with torch.cuda.device(self.dev):
-            return smiler.double_bond_codes()
+        return self._read("smiler", "double_bond_codes")
 
     def step(self):
         """forward + NMS on the batch in the static image buffer; results in .logits / .atom_mask / ..."""

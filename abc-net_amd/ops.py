@@ -467,6 +467,20 @@ class GraphAssembler:
         return out
 
 
+def _column_sums(stat, columns):
+    """an int32 [B, len(columns)] device table as {column: its sum over the batch} and "rows", the table as lists (host sync)"""
+    rows = stat.cpu().tolist()
+    out = {name: sum(r[i] for r in rows) for i, name in enumerate(columns)}
+    out["rows"] = rows
+    return out
+
+
+def _structured_rows(stat, columns):
+    """an int32 [B, len(columns)] device table as a structured numpy array [B] with the int32 fields `columns` (host sync)"""
+    rows = np.ascontiguousarray(stat.cpu().numpy())
+    return rows.view(np.dtype([(c, np.int32) for c in columns])).reshape(len(rows))
+
+
 class PackedText:
     """what the device text writers (MolBlockWriter, SmilesWriter) share: .text, the batch's texts back to back, and .index,
     offsets [B + 1] then status words [B], read back through the pinned .h_index"""
@@ -491,6 +505,23 @@ class PackedText:
         raw = self.text[:off[self.B]].cpu().numpy().tobytes()
         return [None if s & L.MOL_EMPTY else raw[off[b]:off[b + 1]].decode("ascii") for b, s in enumerate(status)]
 
+    def _bind_text(self, d, rows, cap_text, text_bytes, work_ints=None):
+        """the half of a writer's constructor behind `rows.fill(d)`: cap_text (default B * text_bytes(d), the bound of one image)
+        checked, the four buffers, the descriptor's text / index / work / cap_text.  work_ints(d): the int32 words of .work, default B"""
+        B, dev = rows.B, rows.device
+        self.image_bytes = int(text_bytes(C.byref(d)))
+        cap_text = B * self.image_bytes if cap_text is None else int(cap_text)
+        if not (1 <= cap_text <= 2 ** 31 - 1):
+            raise ValueError("%s: cap_text must be 1..2^31-1 bytes, got %d (B = %d images of at most %d bytes)"
+                             % (type(self).__name__, cap_text, B, self.image_bytes))
+        self.B, self.cap_atoms, self.cap_mol_bonds, self.cap_text = B, rows.cap_atoms, rows.cap_mol_bonds, cap_text
+        self.text = torch.zeros(cap_text, dtype=torch.uint8, device=dev)
+        self.index = torch.zeros(2 * B + 1, dtype=torch.int32, device=dev)
+        self.work = torch.zeros(B if work_ints is None else int(work_ints(C.byref(d))), dtype=torch.int32, device=dev)
+        self.h_index = torch.zeros(2 * B + 1, dtype=torch.int32, pin_memory=True)
+        d.text, d.index, d.work, d.cap_text = self.text.data_ptr(), self.index.data_ptr(), self.work.data_ptr(), cap_text
+        self.d, self.keep = d, rows.tensors
+
 
 class MolBlockWriter(PackedText):
     """the mol block text of the assembled molecules, written on the device (csrc/molblock.hip, abc_write_molblocks): the bytes of
@@ -506,24 +537,10 @@ class MolBlockWriter(PackedText):
         buffer; default B * abc_molblock_text_bytes, the bound of one image with every number at its widest -- 224 867 bytes per
         image at the runner's default capacities (512 atoms, 2048 bonds), 14.4 MB for a batch of 64; at most 2^31 - 1"""
         rows = MoleculeRows.checked("MolBlockWriter", mol_counts, mol_atoms, mol_bonds, mol_implh, need_implh=True)
-        B, cap_atoms, cap_mol_bonds = rows.B, rows.cap_atoms, rows.cap_mol_bonds
         self.lib = L.load()
-        dev = rows.device
         d = L.MolBlockDesc()
         rows.fill(d)
-        d.mol_implh = rows.tensors[3].data_ptr()
-        self.image_bytes = int(self.lib.abc_molblock_text_bytes(C.byref(d)))
-        cap_text = B * self.image_bytes if cap_text is None else int(cap_text)
-        if not (1 <= cap_text <= 2 ** 31 - 1):
-            raise ValueError("MolBlockWriter: cap_text must be 1..2^31-1 bytes, got %d (B = %d images of at most %d bytes)"
-                             % (cap_text, B, self.image_bytes))
-        self.B, self.cap_atoms, self.cap_mol_bonds, self.cap_text = B, cap_atoms, cap_mol_bonds, cap_text
-        self.text = torch.zeros(cap_text, dtype=torch.uint8, device=dev)
-        self.index = torch.zeros(2 * B + 1, dtype=torch.int32, device=dev)
-        self.work = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.h_index = torch.zeros(2 * B + 1, dtype=torch.int32, pin_memory=True)
-        d.text, d.index, d.work, d.cap_text = self.text.data_ptr(), self.index.data_ptr(), self.work.data_ptr(), cap_text
-        self.d, self.keep = d, rows.tensors
+        self._bind_text(d, rows, cap_text, self.lib.abc_molblock_text_bytes)
 
     @classmethod
     def from_assembler(cls, asm, cap_text=None):
@@ -554,6 +571,10 @@ class SmilesWriter(PackedText):
                                      "outside 1..6, a bond end outside 1..n or on one atom twice, or an atom pair listed twice)"),
                     (L.TEXT_RING_LIMIT, "ABC_TEXT_RING_LIMIT (more than 99 ring bonds are open at once)"),
                     (L.TEXT_OVERFLOW, "ABC_TEXT_OVERFLOW (the batch's text does not fit cap_text)"))
+    # (double_bonds, stereo) -> the descriptor and the stem of abc_write_<stem>, abc_<stem>_text_bytes, abc_<stem>_work_ints (the ez entry
+    # writes the tetrahedral marks too, under its descriptor's `tetrahedral`)
+    VARIANTS = {(False, False): (L.SmilesDesc, "smiles"), (False, True): (L.SmilesStereoDesc, "smiles_stereo"),
+                (True, False): (L.SmilesEzDesc, "smiles_ez"), (True, True): (L.SmilesEzDesc, "smiles_ez")}
 
     def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None, cap_text=None, stereo=False, double_bonds=False):
         """a contract.MoleculeRows (GraphAssembler.rows), or its four device tensors (hand-made rows); cap_atoms at most
@@ -562,30 +583,16 @@ class SmilesWriter(PackedText):
         runner's default capacities (512 atoms, 2048 bonds), 21 504 with stereo (abc_smiles_stereo_text_bytes); at most 2^31 - 1"""
         rows = MoleculeRows.checked("SmilesWriter", mol_counts, mol_atoms, mol_bonds, mol_implh, max_cap_atoms=L.MAX_SMILES_ATOMS,
                                     max_cap_mol_bonds=L.MAX_SMILES_BONDS, need_implh=True)
-        B, cap_atoms, cap_mol_bonds = rows.B, rows.cap_atoms, rows.cap_mol_bonds
+        B, cap_atoms, cap_mol_bonds, dev = rows.B, rows.cap_atoms, rows.cap_mol_bonds, rows.device
         self.lib = L.load()
-        dev = rows.device
         self.stereo, self.double_bonds = bool(stereo), bool(double_bonds)
-        d = L.SmilesEzDesc() if self.double_bonds else (L.SmilesStereoDesc() if self.stereo else L.SmilesDesc())
-        text_bytes, work_ints, self._write, self._what = (
-            (self.lib.abc_smiles_ez_text_bytes, self.lib.abc_smiles_ez_work_ints, self.lib.abc_write_smiles_ez, "write_smiles_ez")
-            if self.double_bonds else (self.lib.abc_smiles_stereo_text_bytes, self.lib.abc_smiles_stereo_work_ints, self.lib.abc_write_smiles_stereo, "write_smiles_stereo")
-            if self.stereo else (self.lib.abc_smiles_text_bytes, self.lib.abc_smiles_work_ints, self.lib.abc_write_smiles, "write_smiles"))
+        desc, entry = self.VARIANTS[self.double_bonds, self.stereo]
+        d = desc()
+        self._write, self._what = getattr(self.lib, "abc_write_" + entry), "write_" + entry
         rows.fill(d)
-        d.mol_implh = rows.tensors[3].data_ptr()
         if self.double_bonds:
             d.tetrahedral = int(self.stereo)
-        self.image_bytes = int(text_bytes(C.byref(d)))
-        cap_text = B * self.image_bytes if cap_text is None else int(cap_text)
-        if not (1 <= cap_text <= 2 ** 31 - 1):
-            raise ValueError("SmilesWriter: cap_text must be 1..2^31-1 bytes, got %d (B = %d images of at most %d bytes)"
-                             % (cap_text, B, self.image_bytes))
-        self.B, self.cap_atoms, self.cap_mol_bonds, self.cap_text = B, cap_atoms, cap_mol_bonds, cap_text
-        self.text = torch.zeros(cap_text, dtype=torch.uint8, device=dev)
-        self.index = torch.zeros(2 * B + 1, dtype=torch.int32, device=dev)
-        self.work = torch.zeros(int(work_ints(C.byref(d))), dtype=torch.int32, device=dev)
-        self.h_index = torch.zeros(2 * B + 1, dtype=torch.int32, pin_memory=True)
-        d.text, d.index, d.work, d.cap_text = self.text.data_ptr(), self.index.data_ptr(), self.work.data_ptr(), cap_text
+        self._bind_text(d, rows, cap_text, getattr(self.lib, "abc_%s_text_bytes" % entry), getattr(self.lib, "abc_%s_work_ints" % entry))
         self.stats = self.codes = None
         if self.stereo:
             self.stats = torch.zeros((B, len(L.SMILES_STEREO_COLUMNS)), dtype=torch.int32, device=dev)
@@ -596,7 +603,6 @@ class SmilesWriter(PackedText):
             self.ez_stats = torch.zeros((B, len(L.SMILES_EZ_COLUMNS)), dtype=torch.int32, device=dev)
             self.ez_codes = torch.zeros((B, cap_mol_bonds), dtype=torch.int32, device=dev)
             d.ez_stats, d.ez_out = self.ez_stats.data_ptr(), self.ez_codes.data_ptr()
-        self.d, self.keep = d, rows.tensors
 
     @classmethod
     def from_assembler(cls, asm, cap_text=None, stereo=False, double_bonds=False):
@@ -613,10 +619,7 @@ class SmilesWriter(PackedText):
         """stereo=True: what became of the wedge rows of the last run -- {"marked", "flat", "unqualified", "wedge_rows"} summed
         over the batch, and "rows", the four counts of every image (zeros for an image without text).  Host sync."""
         self._need_stereo("stereo_stats")
-        rows = self.stats.cpu().tolist()
-        out = {name: sum(r[i] for r in rows) for i, name in enumerate(L.SMILES_STEREO_COLUMNS)}
-        out["rows"] = rows
-        return out
+        return _column_sums(self.stats, L.SMILES_STEREO_COLUMNS)
 
     def parities(self):
         """stereo=True: int32 [B, cap_atoms] on the host, the code of every atom row of the last run: 0 no candidate, +1 / -1 the
@@ -632,10 +635,7 @@ class SmilesWriter(PackedText):
         """double_bonds=True: what became of the candidate double bonds of the last run -- {"marked", "flat", "ring", "twin"}
         summed over the batch, and "rows", the four counts of every image (zeros for an image without text).  Host sync."""
         self._need_double_bonds("double_bond_stats")
-        rows = self.ez_stats.cpu().tolist()
-        out = {name: sum(r[i] for r in rows) for i, name in enumerate(L.SMILES_EZ_COLUMNS)}
-        out["rows"] = rows
-        return out
+        return _column_sums(self.ez_stats, L.SMILES_EZ_COLUMNS)
 
     def double_bond_codes(self):
         """double_bonds=True: int32 [B, cap_mol_bonds] on the host, the code of every bond row of the last run: 0 not a candidate,
@@ -715,8 +715,7 @@ class StrokeNormalizer:
     def stats(self):
         """the stats rows of the last run() as a structured numpy array [B] with the int32 fields L.STROKE_STAT_COLUMNS
         (iterations, converged, ink_in, ink_out, skipped).  The only call here that synchronises."""
-        rows = np.ascontiguousarray(self.stat.cpu().numpy())
-        return rows.view(np.dtype([(c, np.int32) for c in L.STROKE_STAT_COLUMNS])).reshape(self.B)
+        return _structured_rows(self.stat, L.STROKE_STAT_COLUMNS)
 
 
 class _RecordScorer:
@@ -861,15 +860,9 @@ class GraphIdentity(_RecordScorer):
         GraphSimilarity, whose records are taken).  max_tries: record-side individualisations per image, max_rounds: refinement rounds
         per image, both sides -- None: L.IDENT_DEFAULT_TRIES / L.IDENT_DEFAULT_ROUNDS.  witness: keep the bijection of every `same`
         image in .map (int32 [B, cap_atoms]: the ORIGINAL record atom index of every molecule atom, -1 everywhere else)"""
-        budgets = []
-        for name, v, default in (("max_tries", max_tries, L.IDENT_DEFAULT_TRIES), ("max_rounds", max_rounds, L.IDENT_DEFAULT_ROUNDS)):
-            v = default if v is None else int(v)
-            if not (1 <= v < 1 << 31):
-                raise ValueError("GraphIdentity: %s must be 1..2^31-1, got %d" % (name, v))
-            budgets.append(v)
-        self.max_tries, self.max_rounds = budgets
         d = L.GraphIdentityDesc()
-        d.max_tries, d.max_rounds = budgets
+        d.max_tries, d.max_rounds = self.max_tries, self.max_rounds = _budgets(
+            "GraphIdentity", max_tries, max_rounds, (L.IDENT_DEFAULT_TRIES, L.IDENT_DEFAULT_ROUNDS))
         records = records.records if isinstance(records, _RecordScorer) else records
         self._bind(d, (mol_counts, mol_atoms, mol_bonds), n_valid, records, max_atoms, max_bonds)
         self.map = torch.full((self.B, self.cap_atoms), -1, dtype=torch.int32, device=self.rows.device) if witness else None
@@ -884,7 +877,63 @@ class GraphIdentity(_RecordScorer):
         return out
 
 
-class GraphCanonicalizer:
+def _budgets(who, max_tries, max_rounds, defaults):
+    """[max_tries, max_rounds] of a search op, None replaced by its default, each 1..2^31-1 (ValueError)"""
+    budgets = []
+    for name, v, default in zip(("max_tries", "max_rounds"), (max_tries, max_rounds), defaults):
+        v = default if v is None else int(v)
+        if not (1 <= v < 1 << 31):
+            raise ValueError("%s: %s must be 1..2^31-1, got %d" % (who, name, v))
+        budgets.append(v)
+    return budgets
+
+
+class _OneSideOp:
+    """What GraphCanonicalizer and AromaticityPerceiver share: ONE side, the molecule rows or the graph records, bound to a descriptor with
+    the mol_* / rec_* fields of abc_canon_desc; .B, .cap, .cap_bonds of that side; .out, the op's own MoleculeRows when it writes rows."""
+
+    def _bind(self, d, mol, records, want_rows, max_cap_mol_bonds=None):
+        """check the side that was given and fill its descriptor fields (out_counts .. out_implh too, with want_rows on the molecule
+        side).  mol: (mol_counts, mol_atoms, mol_bonds, mol_implh); records: a GraphRecords, or a scorer, whose records are taken.
+        Returns (the records or None, the device)."""
+        who = type(self).__name__
+        if (mol[0] is None) == (records is None):
+            raise ValueError("%s: give the molecule rows or records=GraphRecords, one side" % who)
+        self.out = None
+        if records is not None:
+            records = records.records if isinstance(records, _RecordScorer) else records
+            if not isinstance(records, GraphRecords):
+                raise ValueError("%s: records must be a GraphRecords, got %s" % (who, type(records).__name__))
+            if not 1 <= records.max_atoms <= L.MAX_SIM_ATOMS or records.max_bonds < 1:
+                raise ValueError("%s: max_atoms must be 1..%d and max_bonds >= 1, got %d, %d"
+                                 % (who, L.MAX_SIM_ATOMS, records.max_atoms, records.max_bonds))
+            records.fill(d)
+            d.B = records.B
+            self.keep = ()
+            self.B, self.cap, self.cap_bonds, dev = records.B, records.max_atoms, records.max_bonds, records.staging.device
+        else:
+            given = mol[0].tensors[3] if isinstance(mol[0], MoleculeRows) else mol[3]
+            mr = MoleculeRows.checked(who, *mol, max_cap_atoms=L.MAX_SIM_ATOMS, need_implh=given is not None, max_cap_mol_bonds=max_cap_mol_bonds)
+            mr.fill(d)
+            self.keep = mr.tensors
+            self.B, self.cap, self.cap_bonds, dev = mr.B, mr.cap_atoms, mr.cap_mol_bonds, mr.device
+            if want_rows:
+                out = tuple(torch.zeros(s, dtype=torch.int32, device=dev) for s in MoleculeRows.SHAPES(mr.B, mr.cap_atoms, mr.cap_mol_bonds))
+                self.out = MoleculeRows(*out)
+                d.out_counts, d.out_atoms, d.out_bonds, d.out_implh = (t.data_ptr() for t in out)
+        self.lib = L.load()
+        return records, dev
+
+    @classmethod
+    def from_assembler(cls, asm, **kw):
+        return cls(asm.rows, **kw)
+
+    @classmethod
+    def from_records(cls, records, **kw):
+        return cls(records=records, **kw)
+
+
+class GraphCanonicalizer(_OneSideOp):
     """a canonical atom order for every image (csrc/graph_canon.hip, abc_canonical_order; the algorithm: include/abcnet_hip.h,
     DESIGN.md section 7): the least leaf of an individualise-and-refine search over every branch of the graph GraphIdentity defines,
     plus a tag on the atoms mol_implh lists.  The molecule side -- a GraphAssembler's rows, read in place -- also gets the CANONICAL
@@ -900,58 +949,17 @@ class GraphCanonicalizer:
         records=contract.GraphRecords.  max_tries: individualisations per image, max_rounds: refinement rounds per image, replays
         included -- None: L.CANON_DEFAULT_TRIES / L.CANON_DEFAULT_ROUNDS.  cert: keep the relabelled graph of every image in .cert
         (int32 [B, 2 + cap + 3 cap_bonds]).  rows (molecule side): write the canonical rows (cap_mol_bonds <= 4096)."""
-        who = "GraphCanonicalizer"
-        budgets = []
-        for name, v, default in (("max_tries", max_tries, L.CANON_DEFAULT_TRIES), ("max_rounds", max_rounds, L.CANON_DEFAULT_ROUNDS)):
-            v = default if v is None else int(v)
-            if not (1 <= v < 1 << 31):
-                raise ValueError("%s: %s must be 1..2^31-1, got %d" % (who, name, v))
-            budgets.append(v)
-        self.max_tries, self.max_rounds = budgets
-        if (mol_counts is None) == (records is None):
-            raise ValueError("%s: give the molecule rows or records=GraphRecords, one side" % who)
         d = L.CanonDesc()
-        d.max_tries, d.max_rounds = budgets
-        self.records = self.out = None
-        if records is not None:
-            records = records.records if isinstance(records, _RecordScorer) else records
-            if not isinstance(records, GraphRecords):
-                raise ValueError("%s: records must be a GraphRecords, got %s" % (who, type(records).__name__))
-            if not 1 <= records.max_atoms <= L.MAX_SIM_ATOMS or records.max_bonds < 1:
-                raise ValueError("%s: max_atoms must be 1..%d and max_bonds >= 1, got %d, %d"
-                                 % (who, L.MAX_SIM_ATOMS, records.max_atoms, records.max_bonds))
-            records.fill(d)
-            d.B = records.B
-            self.records, self.keep = records, ()
-            self.B, self.cap, self.cap_bonds, dev = records.B, records.max_atoms, records.max_bonds, records.staging.device
-        else:
-            given = mol_counts.tensors[3] if isinstance(mol_counts, MoleculeRows) else mol_implh
-            want_rows = bool(rows)
-            mr = MoleculeRows.checked(who, mol_counts, mol_atoms, mol_bonds, mol_implh, max_cap_atoms=L.MAX_SIM_ATOMS,
-                                      need_implh=given is not None, max_cap_mol_bonds=L.MAX_SMILES_BONDS if want_rows else None)
-            mr.fill(d)
-            d.mol_implh = L.ptr(mr.tensors[3])
-            self.keep = mr.tensors
-            self.B, self.cap, self.cap_bonds, dev = mr.B, mr.cap_atoms, mr.cap_mol_bonds, mr.device
-            if want_rows:
-                out = tuple(torch.zeros(s, dtype=torch.int32, device=dev) for s in MoleculeRows.SHAPES(mr.B, mr.cap_atoms, mr.cap_mol_bonds))
-                self.out = MoleculeRows(*out)
-                d.out_counts, d.out_atoms, d.out_bonds, d.out_implh = (t.data_ptr() for t in out)
-        self.lib = L.load()
+        d.max_tries, d.max_rounds = self.max_tries, self.max_rounds = _budgets(
+            "GraphCanonicalizer", max_tries, max_rounds, (L.CANON_DEFAULT_TRIES, L.CANON_DEFAULT_ROUNDS))
+        self.records, dev = self._bind(d, (mol_counts, mol_atoms, mol_bonds, mol_implh), records, bool(rows),
+                                       L.MAX_SMILES_BONDS if rows else None)
         self.order = torch.full((self.B, self.cap), -1, dtype=torch.int32, device=dev)
         self.stat = torch.zeros((self.B, len(L.CANON_COLUMNS)), dtype=torch.int32, device=dev)
         self.key = torch.zeros((self.B, 2), dtype=torch.int64, device=dev)
         self.cert = torch.full((self.B, 2 + self.cap + 3 * self.cap_bonds), -1, dtype=torch.int32, device=dev) if cert else None
         d.order, d.stats, d.key, d.cert_out = self.order.data_ptr(), self.stat.data_ptr(), self.key.data_ptr(), L.ptr(self.cert)
         self.d = d
-
-    @classmethod
-    def from_assembler(cls, asm, **kw):
-        return cls(asm.rows, **kw)
-
-    @classmethod
-    def from_records(cls, records, **kw):
-        return cls(records=records, **kw)
 
     def run(self, stream=None):
         """one launch (graph-capturable): order, stats, key, and cert / the canonical rows when they were asked for"""
@@ -972,8 +980,7 @@ class GraphCanonicalizer:
     def stats(self):
         """the stats rows of the last run as a structured numpy array [B] with the int32 fields L.CANON_COLUMNS; `status` holds the
         L.CANON_* bits.  Host sync."""
-        rows = np.ascontiguousarray(self.stat.cpu().numpy())
-        return rows.view(np.dtype([(c, np.int32) for c in L.CANON_COLUMNS])).reshape(self.B)
+        return _structured_rows(self.stat, L.CANON_COLUMNS)
 
     def keys(self):
         """int64 [B, 2] on the host: two HASH words of the relabelled graph (equal for equal graphs; equal keys prove nothing --
@@ -988,7 +995,7 @@ class GraphCanonicalizer:
         return self.cert.cpu()
 
 
-class AromaticityPerceiver:
+class AromaticityPerceiver(_OneSideOp):
     """the aromatic rings of every image, perceived on the device (csrc/aromatic.hip, abc_perceive_aromatic; the rule:
     include/abcnet_hip.h): the rows of a GraphAssembler -- or the bond rows of contract.GraphRecords -- copied with
     the bonds of every aromatic cycle set to order 4, so that a Kekule drawing and an order-4 drawing of one ring are one graph.
@@ -1001,49 +1008,18 @@ class AromaticityPerceiver:
         """a contract.MoleculeRows (GraphAssembler.rows) or its device tensors (mol_implh optional: no atom counts as listed without
         it), OR records=contract.GraphRecords (or a scorer, whose records are taken).  codes: keep the code of every atom in .code
         (int32 [B, cap]: L.AROM_NOT_CANDIDATE, L.AROM_NONE or its electrons)."""
-        who = "AromaticityPerceiver"
-        if (mol_counts is None) == (records is None):
-            raise ValueError("%s: give the molecule rows or records=GraphRecords, one side" % who)
         d = L.AromaticDesc()
-        self.source = self.out = self._records = None
-        if records is not None:
-            records = records.records if isinstance(records, _RecordScorer) else records
-            if not isinstance(records, GraphRecords):
-                raise ValueError("%s: records must be a GraphRecords, got %s" % (who, type(records).__name__))
-            if not 1 <= records.max_atoms <= L.MAX_SIM_ATOMS or records.max_bonds < 1:
-                raise ValueError("%s: max_atoms must be 1..%d and max_bonds >= 1, got %d, %d"
-                                 % (who, L.MAX_SIM_ATOMS, records.max_atoms, records.max_bonds))
-            records.fill(d)
-            d.B = records.B
-            self.source, self.keep = records, ()
-            self.B, self.cap, self.cap_bonds, dev = records.B, records.max_atoms, records.max_bonds, records.staging.device
+        self._records = None
+        self.source, dev = self._bind(d, (mol_counts, mol_atoms, mol_bonds, mol_implh), records, True)
+        if self.source is not None:
             self.out_bonds = torch.zeros((self.B, self.cap_bonds, REC_BOND_W), dtype=torch.int32, device=dev)
             d.out_rec_bonds = self.out_bonds.data_ptr()
-            atoms, _, cnt = records.staging.dev.values()
-            self._records = DerivedGraphRecords(records, atoms, self.out_bonds, cnt, who)
-        else:
-            given = mol_counts.tensors[3] if isinstance(mol_counts, MoleculeRows) else mol_implh
-            mr = MoleculeRows.checked(who, mol_counts, mol_atoms, mol_bonds, mol_implh, max_cap_atoms=L.MAX_SIM_ATOMS, need_implh=given is not None)
-            mr.fill(d)
-            d.mol_implh = L.ptr(mr.tensors[3])
-            self.keep = mr.tensors
-            self.B, self.cap, self.cap_bonds, dev = mr.B, mr.cap_atoms, mr.cap_mol_bonds, mr.device
-            out = tuple(torch.zeros(s, dtype=torch.int32, device=dev) for s in MoleculeRows.SHAPES(mr.B, mr.cap_atoms, mr.cap_mol_bonds))
-            self.out = MoleculeRows(*out)
-            d.out_counts, d.out_atoms, d.out_bonds, d.out_implh = (t.data_ptr() for t in out)
-        self.lib = L.load()
+            atoms, _, cnt = self.source.staging.dev.values()
+            self._records = DerivedGraphRecords(self.source, atoms, self.out_bonds, cnt, "AromaticityPerceiver")
         self.stat = torch.zeros((self.B, len(L.AROMATIC_COLUMNS)), dtype=torch.int32, device=dev)
         self.code = torch.full((self.B, self.cap), L.AROM_NOT_CANDIDATE, dtype=torch.int32, device=dev) if codes else None
         d.stats, d.code_out = self.stat.data_ptr(), L.ptr(self.code)
         self.d = d
-
-    @classmethod
-    def from_assembler(cls, asm, **kw):
-        return cls(asm.rows, **kw)
-
-    @classmethod
-    def from_records(cls, records, **kw):
-        return cls(records=records, **kw)
 
     def run(self, stream=None):
         """one launch (graph-capturable): the perceived rows (or record bonds), stats, and the codes when they were asked for"""
@@ -1065,8 +1041,7 @@ class AromaticityPerceiver:
 
     def stats(self):
         """the stats rows of the last run as a structured numpy array [B] with the int32 fields L.AROMATIC_COLUMNS.  Host sync."""
-        rows = np.ascontiguousarray(self.stat.cpu().numpy())
-        return rows.view(np.dtype([(c, np.int32) for c in L.AROMATIC_COLUMNS])).reshape(self.B)
+        return _structured_rows(self.stat, L.AROMATIC_COLUMNS)
 
     def codes(self):
         """codes=True: int32 [B, cap] on the host, per atom L.AROM_NOT_CANDIDATE, L.AROM_NONE or its electrons.  Host sync."""

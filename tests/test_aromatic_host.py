@@ -223,6 +223,7 @@ def test_launcher_refuses_before_it_touches_a_device():
                                (-1, dict(rec, out_counts=8 << 20), "out_rec_bonds")):
         assert lib.abc_perceive_aromatic(C.byref(desc(**fields)), None) == code, fields
         assert text in lib.abc_last_error().decode(), (fields, lib.abc_last_error())
+    assert lib.abc_perceive_aromatic(None, None) == -1 and lib.abc_last_error().decode() == "perceive_aromatic: null descriptor"
 
 
 def test_runner_and_ops_refuse_on_the_host():

@@ -129,3 +129,59 @@ def test_self_sized_table_names_the_five_descriptors():
     for st, size_fn in L.SELF_SIZED:
         assert st not in L._STRUCTS and L.SYMBOLS[size_fn] == (C.c_int, [])
         assert getattr(lib, size_fn)() == C.sizeof(st)
+
+
+# ------------------------------------------------------------------------------------------- the runner's constructor flags
+RUNNER_FLAGS = ("assemble", "evaluate", "score_graphs", "score_similarity", "score_identity", "molblocks", "smiles", "aromatize",
+                "smiles_stereo", "smiles_double_bonds", "smiles_canonical")
+
+
+def _first_refusal(f):
+    """the refusals of InferenceRunner.__init__ as they stood before the two tables (FLAG_NEEDS, FLAG_REFUSED), in their order"""
+    for flag in ("score_graphs", "score_similarity", "score_identity"):
+        if f[flag] and not (f["assemble"] and f["evaluate"]):
+            return ("InferenceRunner(%s=True) scores the assembled molecules of an evaluating step: it needs "
+                    "assemble=True and evaluate=True" % flag)
+    for flag in ("molblocks", "smiles"):
+        if f[flag] and not f["assemble"]:
+            return ("InferenceRunner(%s=True) writes the text of the assembled molecules of the step: it needs "
+                    "assemble=True" % flag)
+    if f["aromatize"] and not f["assemble"]:
+        return ("InferenceRunner(aromatize=True) perceives the aromatic rings of the assembled molecules of the step: it "
+                "needs assemble=True")
+    if f["smiles_stereo"] and not f["smiles"]:
+        return "InferenceRunner(smiles_stereo=True) is a form of the SMILES stage: it needs smiles=True"
+    if f["smiles_double_bonds"] and not f["smiles"]:
+        return "InferenceRunner(smiles_double_bonds=True) is a form of the SMILES stage: it needs smiles=True"
+    if f["smiles_canonical"] and f["smiles_double_bonds"]:
+        return ("InferenceRunner(smiles_canonical=True, smiles_double_bonds=True): a text with double-bond marks on the "
+                "canonical order would not be canonical (the drawn geometry is not in the invariant)")
+    if f["smiles_canonical"] and not f["smiles"]:
+        return "InferenceRunner(smiles_canonical=True) is a form of the SMILES stage: it needs smiles=True"
+    if f["smiles_canonical"] and f["smiles_stereo"]:
+        return ("InferenceRunner(smiles_canonical=True, smiles_stereo=True): a stereo text on the canonical order would not "
+                "be canonical (wedge ownership and the drawn geometry are not in the invariant)")
+    return None
+
+
+def test_runner_flag_tables_refuse_every_combination_with_the_same_first_message():
+    from abcnet_amd.infer import FLAG_NEEDS, FLAG_REFUSED, InferenceRunner, check_flags
+    from molrows import Heads
+    assert {f for group, needs, _ in FLAG_NEEDS for f in group + needs} | {f for a, b, _ in FLAG_REFUSED for f in (a, b)} == set(RUNNER_FLAGS)
+    refused = seen = 0
+    for bits in range(1 << len(RUNNER_FLAGS)):
+        flags = {name: bool(bits >> i & 1) for i, name in enumerate(RUNNER_FLAGS)}
+        want = _first_refusal(flags)
+        if want is None:
+            check_flags(flags)
+            continue
+        with pytest.raises(ValueError) as e:
+            check_flags(flags)
+        assert str(e.value) == want, flags
+        refused += 1
+        if bits % 7 == 0:                # (through the constructor too: the refusals come before it reads the model or a device)
+            with pytest.raises(ValueError) as e:
+                InferenceRunner(Heads(), 2, 64, 64, **flags)
+            assert str(e.value) == want, flags
+            seen += 1
+    assert refused > 1500 and seen > 200

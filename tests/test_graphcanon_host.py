@@ -225,6 +225,7 @@ def test_launcher_refuses_before_it_touches_a_device():
                                (-1, dict(rows, mol_counts=None, rec_counts=1 << 20, rec_atoms=2 << 20, rec_bonds=3 << 20, max_atoms=8, max_bonds=8), "molecule side")):
         assert lib.abc_canonical_order(C.byref(desc(**fields)), None) == code, fields
         assert text in lib.abc_last_error().decode(), (fields, lib.abc_last_error())
+    assert lib.abc_canonical_order(None, None) == -1 and lib.abc_last_error().decode() == "canonical_order: null descriptor"
 
 
 def test_runner_refuses_the_flag_without_smiles_and_with_stereo():
