@@ -93,11 +93,15 @@ template <int NV> __device__ inline void abc_fma2_n(float* v, const float* w, co
 // Counter-based dropout keep-decision (K7).  idx = element index in the tensor the
 // mask applies to.  Mirrored bit-for-bit by abcnet_amd.dropout.keep_mask (torch int ops)
 // so that the oracle can be driven with the identical mask.
-__host__ __device__ inline uint32_t abc_drop_hash24(uint32_t idx, uint32_t seed) {
-    uint32_t h = idx * 0x9E3779B1u ^ seed;
+// (the first multiply is linear in the index: a kernel that hashes idx0 + k for many constant k forms idx0 * ABC_DROP_MUL once and
+//  calls abc_drop_hash24_mul(idx0 * ABC_DROP_MUL + k * ABC_DROP_MUL, seed) -- the same 32-bit product, the same draw)
+constexpr uint32_t ABC_DROP_MUL = 0x9E3779B1u;
+__host__ __device__ inline uint32_t abc_drop_hash24_mul(uint32_t idx_mul, uint32_t seed) {
+    uint32_t h = idx_mul ^ seed;
     h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
     return h >> 8;
 }
+__host__ __device__ inline uint32_t abc_drop_hash24(uint32_t idx, uint32_t seed) { return abc_drop_hash24_mul(idx * ABC_DROP_MUL, seed); }
 __host__ __device__ inline bool abc_drop_keep(uint32_t idx, uint32_t seed, float p) {
     return (float)abc_drop_hash24(idx, seed) * (1.0f / 16777216.0f) >= p;
 }
