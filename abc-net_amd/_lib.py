@@ -226,6 +226,15 @@ class CanonDesc(C.Structure):
                 ("out_atoms", vp), ("out_bonds", vp), ("out_implh", vp)]
 
 
+class CanonStereoDesc(C.Structure):
+    _fields_ = CanonDesc._fields_ + [("elements", vp), ("stereo_search", vp)]
+
+
+class StereoDesc(C.Structure):
+    _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp), ("B", i32), ("cap_atoms", i32),
+                ("cap_mol_bonds", i32), ("elements", vp), ("stats", vp)]
+
+
 class AromaticDesc(C.Structure):
     _fields_ = [("mol_counts", vp), ("mol_atoms", vp), ("mol_bonds", vp), ("mol_implh", vp), ("rec_atoms", vp), ("rec_bonds", vp),
                 ("rec_counts", vp), ("B", i32), ("cap_atoms", i32), ("cap_mol_bonds", i32), ("max_atoms", i32), ("max_bonds", i32),
@@ -311,6 +320,8 @@ STEREO_NONE, STEREO_FLAT, STEREO_UNQUALIFIED = 0, 2, 3
 # the columns of abc_smiles_ez_desc.ez_stats; the codes of .ez_out beside +1 (together) / -1 (opposite)
 SMILES_EZ_COLUMNS = ("marked", "flat", "ring", "twin")
 EZ_NONE, EZ_FLAT, EZ_RING, EZ_TWIN = 0, 2, 3, 4
+# ABC_STEREO_W, the columns of abc_stereo_desc.stats and of abc_canon_stereo_desc.stereo_search: defined beside their host forms
+from .decode import STEREO_NONE_ROW, STEREO_SEARCH_COLUMNS, STEREO_STATS_COLUMNS, STEREO_W  # noqa: E402,F401
 
 
 _STRUCTS = [ActSrc, ConvDesc, PackDesc, BnFwdDesc, ActBwdDesc, BnBwdDesc, BnApplyDesc, WgradDesc, WgradReduceDesc,
@@ -325,7 +336,8 @@ SELF_SIZED = [(EvalDesc, "abc_eval_desc_size"), (GraphScoreDesc, "abc_graph_scor
 SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "abc_graph_identity_desc_size"),
                     (ScanCleanDesc, "abc_scan_clean_desc_size"), (SmilesDesc, "abc_smiles_desc_size"),
                     (SmilesStereoDesc, "abc_smiles_stereo_desc_size"), (CanonDesc, "abc_canon_desc_size"),
-                    (AromaticDesc, "abc_aromatic_desc_size"), (SmilesEzDesc, "abc_smiles_ez_desc_size")]
+                    (AromaticDesc, "abc_aromatic_desc_size"), (SmilesEzDesc, "abc_smiles_ez_desc_size"),
+                    (StereoDesc, "abc_stereo_desc_size"), (CanonStereoDesc, "abc_canon_stereo_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -416,6 +428,10 @@ SYMBOLS = {
     "abc_graph_identity_desc_size": (C.c_int, []),
     "abc_canonical_order": (C.c_int, [P(CanonDesc), vp]),
     "abc_canon_desc_size": (C.c_int, []),
+    "abc_perceive_stereo": (C.c_int, [P(StereoDesc), vp]),
+    "abc_stereo_desc_size": (C.c_int, []),
+    "abc_canonical_order_stereo": (C.c_int, [P(CanonStereoDesc), vp]),
+    "abc_canon_stereo_desc_size": (C.c_int, []),
     "abc_perceive_aromatic": (C.c_int, [P(AromaticDesc), vp]),
     "abc_aromatic_desc_size": (C.c_int, []),
     "abc_molblock_text_bytes": (i64, [P(MolBlockDesc)]),

@@ -131,6 +131,11 @@ def refuse_dense_targets(rasterizer):
 
 # ---------- the decoder: rows and records its stages hand to each other; words per row as csrc/mol_rows.hpp, DESIGN.md section 7
 ATOM_W, CAND_W, MOL_BOND_W, REC_ATOM_W, REC_BOND_W = 5, 4, 4, 4, 3
+# the element table of StereoPerceiver, int32 [B, cap_atoms, STEREO_W] (csrc/mol_rows.hpp; decode.stereo_elements is its host form): the
+# name of every word; "none" (decode.STEREO_NONE_ROW) is 0 in `centre` and `bond_code`, -1 elsewhere
+from .decode import STEREO_W  # noqa: E402
+STEREO_ELEMENT = ("centre", "nb0", "nb1", "nb2", "nb3", "bond_code", "bond_row", "partner", "sub0", "sub1", "partner_sub0", "partner_sub1")
+assert len(STEREO_ELEMENT) == STEREO_W
 
 
 def _require_layout(who, names, tensors, shapes):

@@ -22,6 +22,11 @@
 //   (e) max_rounds is checked before every round (replays included), max_tries before every individualisation: UNDECIDED, the order
 //       of the best leaf so far, or the identity order.  Every loop is bounded by n, a budget or a capacity
 //   (f) every branch depends on values all threads hold alike (reductions read from LDS after a barrier, or descriptor fields)
+//   (g) <STEREO>, the second instantiation (abc_canonical_order_stereo, the molecule side alone): at a leaf every thread computes the
+//       stereo word of its atoms from the element table of stereo.hip and the ranks, one byte per canonical position; the leaves are
+//       ordered by (traces, h, word), the word compared exactly.  At an equal h the map is verified as in (b); words equal: an
+//       automorphism of the STEREO graph, merged and jumped as in (b); word smaller: the leaf becomes the best, nothing is merged;
+//       greater: a normal backtrack.  Orbit pruning so uses only automorphisms that keep the stereo
 //
 // Bond rows are never held in LDS (row `tid` stays in registers); the sorts of the certificate and of the canonical rows count, for
 // every row, the rows before it (quadratic in the rows of ONE image, no scratch).  Every index read from a row is range-checked before
@@ -48,9 +53,19 @@ constexpr u64 TAG_K = 0xD6E8FEB86659FD93ull, BOND_K = 0xC2B2AE3D27D4EB4Full;
 static_assert(MAX_ATOMS == 2 * GT, "two atoms per thread: the record scan");
 typedef unsigned short u16;
 
+// <STEREO> abc_canonical_order_stereo: the stereo word of abc_canon_stereo_desc as a third key of the leaves (every line of it is
+// compiled out of the plain instantiation, which keeps its instructions)
+template <bool STEREO> struct CanonDescOf { typedef abc_canon_desc type; };
+template <> struct CanonDescOf<true> { typedef abc_canon_stereo_desc type; };
+
 // 71 KB of LDS: the ids (current, best, id_0), the round's sums, the class table with the atom of every slot, the traces of the current
-// path and of the best leaf, the stack, 9 orbit tables
-__global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d) {
+// path and of the best leaf, the stack, 9 orbit tables; <STEREO> 2.5 KB more: the word of the leaf and of the best leaf, by position, and
+// per atom its checked centre code and the lower-index end of the marked double bond it is an end of
+template <bool STEREO>
+__global__ __launch_bounds__(GT) void graph_canon_kernel(const typename CanonDescOf<STEREO>::type d) {
+    __shared__ unsigned char sword[STEREO ? MAX_ATOMS : 1], bword[STEREO ? MAX_ATOMS : 1];
+    __shared__ signed char scode[STEREO ? MAX_ATOMS : 1];
+    __shared__ short dsrc[STEREO ? MAX_ATOMS : 1];
     __shared__ u64 cur[MAX_ATOMS], acc[MAX_ATOMS], init[MAX_ATOMS], best_ids[MAX_ATOMS];
     __shared__ u64 table[SLOTS];
     __shared__ u64 cur_sum[MAX_ATOMS], best_sum[MAX_ATOMS], cell[MAX_ATOMS];       // per level: the trace's sum; the id of the cell
@@ -67,7 +82,7 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
     __shared__ u64 wu[NW];
     __shared__ int cnt[1], zero_at;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const bool mol = d.mol_counts != nullptr;
+    const bool mol = STEREO || d.mol_counts != nullptr;      // (the launcher refuses the records side with <STEREO>)
     const int cap = mol ? d.cap_atoms : d.max_atoms, cap_bonds = mol ? d.cap_mol_bonds : d.max_bonds;
     int* const order = d.order + (size_t)b * cap;
     int* const cert = d.cert_out != nullptr ? d.cert_out + (size_t)b * (2 + cap + 3 * (size_t)cap_bonds) : nullptr;
@@ -152,6 +167,54 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
         return block_reduce(h, wu, [](u64 u, u64 v) { return u + v; });
     };
 
+    // <STEREO> the elements of the image, checked once: an index that is no atom of the image makes its element none
+    const int* elements = nullptr;
+    int s_unequal = 0, s_improved = 0, s_autos = 0;
+    if constexpr (STEREO) {
+        elements = d.elements + (size_t)b * d.cap_atoms * STEREO_W;
+        auto atom = [&](int v, int least) __attribute__((always_inline)) { return v >= least && v < n; };
+        for (int a = tid; a < n; a += GT) {
+            const int* el = elements + a * STEREO_W;
+            const int c = el[0];
+            scode[a] = (signed char)((c == 1 || c == -1) && atom(el[1], 0) && atom(el[2], 0) && atom(el[3], 0) && atom(el[4], -1) ? c : 0);
+            dsrc[a] = -1;
+        }
+        __syncthreads();
+        for (int a = tid; a < n; a += GT) {
+            const int* el = elements + a * STEREO_W;
+            const int c = el[5], other = el[7];
+            if ((c == 1 || c == -1) && atom(other, 0) && other != a && atom(el[8], 0) && atom(el[9], -1) && atom(el[10], 0) && atom(el[11], -1))
+                dsrc[a] = dsrc[other] = (short)a;
+        }
+        __syncthreads();
+    }
+    // the stereo word of the leaf whose ranks are in rk, by position (every position is written: the ranks are a permutation)
+    auto leaf_word = [&]() __attribute__((always_inline)) {
+        for (int a = tid; a < n; a += GT) {
+            int byte = 0;
+            const int sc = scode[a], a0 = dsrc[a];
+            if (sc != 0) {
+                const int* el = elements + a * STEREO_W;
+                const int last = el[4];
+                const int r0 = rk[el[1]], r1 = rk[el[2]], r2 = rk[el[3]], r3 = last >= 0 ? (int)rk[last] : MAX_ATOMS;      // (the hydrogen stays last)
+                const int swaps = (r0 > r1) + (r0 > r2) + (r0 > r3) + (r1 > r2) + (r1 > r3) + (r2 > r3);
+                byte = ((swaps & 1) ? -sc : sc) > 0 ? 1 : 2;
+            }
+            if (a0 >= 0) {
+                const int* el = elements + a0 * STEREO_W;
+                const int other = a == a0 ? el[7] : a0;
+                if (rk[a] < rk[other]) {      // the lower-rank end bears the bond's part
+                    int v = el[5];
+                    if (el[9] >= 0 && rk[el[8]] > rk[el[9]]) v = -v;
+                    if (el[11] >= 0 && rk[el[10]] > rk[el[11]]) v = -v;
+                    byte |= (v > 0 ? 1 : 2) << 2;
+                }
+            }
+            sword[rk[a]] = (unsigned char)byte;
+        }
+        __syncthreads();
+    };
+
     int leaves = 0, tries = 0, rounds = 0, levels_max = 0, pruned_trace = 0, pruned_orbit = 0, autos = 0, improved = 0;
     bool have_best = false;
     int best_levels = 0;
@@ -198,9 +261,12 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
                     }
                     __syncthreads();     // (the ranks and tid 0's trace of this level are written)
                     const u64 h = leaf_hash(rk);
+                    if constexpr (STEREO) leaf_word();
                     if (!have_best || less_from != NONE || h < best_h) {
                         improved += have_best;
                         for (int a = tid; a < n; a += GT) best_ids[a] = cur[a], brank[a] = rk[a];
+                        if constexpr (STEREO)
+                            for (int a = tid; a < n; a += GT) bword[a] = sword[a];
                         for (int l = tid; l <= level; l += GT) {
                             best_k[l] = cur_k[l], best_c[l] = cur_c[l], best_sum[l] = cur_sum[l];
                             if (l < level) best_choice[l] = choice[l];
@@ -270,6 +336,26 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
                             ok = sum_int(common) == nvalid;
                         }
                         if (!ok) { status |= ABC_CANON_COLLISION; break; }
+                        if constexpr (STEREO) {
+                            // the third key, compared exactly: the first position at which the words differ
+                            int differs = NONE;
+                            for (int k2 = tid; k2 < n; k2 += GT)
+                                if (sword[k2] != bword[k2]) differs = min(differs, k2);
+                            differs = min_int(differs);
+                            if (differs != NONE) {      // a map that does not keep the stereo: no orbit merge, no jump
+                                ++s_unequal;
+                                const bool less = sword[differs] < bword[differs];
+                                __syncthreads();         // (read before the best leaf's word is replaced)
+                                if (less) {
+                                    ++s_improved, ++improved;
+                                    for (int a = tid; a < n; a += GT) best_ids[a] = cur[a], brank[a] = rk[a], bword[a] = sword[a];
+                                    for (int l = tid; l < level; l += GT) best_choice[l] = choice[l];      // (the traces are equal)
+                                    __syncthreads();
+                                }
+                                continue;
+                            }
+                            ++s_autos;
+                        }
                         ++autos;
                         int first = NONE;
                         for (int l = tid; l < level; l += GT)
@@ -412,6 +498,10 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
         st[ABC_CANON_AUTOMORPHISMS] = autos, st[ABC_CANON_IMPROVED] = improved;
         d.key[(size_t)b * 2] = (long long)key0;
         d.key[(size_t)b * 2 + 1] = empty ? 0 : (long long)mix(mix(mix((u64)n) + (u64)nvalid) + t);
+        if constexpr (STEREO) {
+            int* ss = d.stereo_search + (size_t)b * 4;
+            ss[0] = s_unequal, ss[1] = s_improved, ss[2] = s_autos, ss[3] = 0;
+        }
     }
     if (cert == nullptr && !want_rows) return;
 
@@ -482,28 +572,47 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const abc_canon_desc d)
     }
 }
 
+// the guards of both entry points, and the launch
+template <bool STEREO>
+int canonical_order(const typename CanonDescOf<STEREO>::type* d, abc_stream_t stream, const char* entry) {
+    bool mol;
+    if (const int rc = abc_one_side(entry, d, mol)) return rc;
+    if constexpr (STEREO) {
+        if (!mol) return abc_fail_in(ABC_EINVAL, entry, "the stereo elements are the molecule side's: records are refused");
+        if (!d->elements || !d->stereo_search) return abc_fail_in(ABC_EINVAL, entry, "null elements or stereo_search");
+    }
+    if (d->max_tries < 0) return abc_fail_in(ABC_EINVAL, entry, "max_tries must be >= 0 (0: the default)");
+    if (d->max_rounds < 0) return abc_fail_in(ABC_EINVAL, entry, "max_rounds must be >= 0 (0: the default)");
+    if (!d->order || !d->stats || !d->key) return abc_fail_in(ABC_EINVAL, entry, "null output (order, stats, key)");
+    const int rows_given = (d->out_counts != nullptr) + (d->out_atoms != nullptr) + (d->out_bonds != nullptr) + (d->out_implh != nullptr);
+    if (rows_given != 0 && rows_given != 4) return abc_fail_in(ABC_EINVAL, entry, "the canonical rows are four buffers, or none");
+    if (const int rc = abc_one_side_buffers(entry, d, mol)) return rc;
+    if (const int rc = abc_one_side_capacities(entry, d, mol)) return rc;
+    if (mol && rows_given && d->cap_mol_bonds > MAX_ROW_BONDS)
+        return abc_fail_in(ABC_EUNSUPPORTED, entry, "cap_mol_bonds must be <= 4096 when the canonical rows are requested");
+    if (!mol && rows_given) return abc_fail_in(ABC_EINVAL, entry, "the canonical rows are the molecule side's");
+    const size_t B = (size_t)d->B, cap = (size_t)(mol ? d->cap_atoms : d->max_atoms), cb = (size_t)(mol ? d->cap_mol_bonds : d->max_bonds);
+    abc_extent out[9] = {{d->order, B * cap * 4}, {d->stats, B * NCOL * 4}, {d->key, B * 16}, {d->cert_out, B * (2 + cap + 3 * cb) * 4},
+                         {d->out_counts, B * 16}, {d->out_atoms, B * cap * ATOM_W * 4}, {d->out_bonds, B * cb * MOL_BOND_W * 4}, {d->out_implh, B * cap * 4},
+                         {nullptr, 0}};
+    if constexpr (STEREO) {
+        out[8] = {d->stereo_search, B * 16};
+        for (const abc_extent& o : out)
+            if (overlap(o.p, o.bytes, d->elements, B * cap * STEREO_W * 4)) return abc_fail_in(ABC_EINVAL, entry, "an output overlaps an input");
+    }
+    if (const int rc = abc_one_side_overlap(entry, d, mol, out)) return rc;
+    hipLaunchKernelGGL(graph_canon_kernel<STEREO>, dim3(d->B), dim3(GT), 0, (hipStream_t)stream, *d);
+    return abc_check_launch(entry);
+}
+
 }  // namespace
 
 extern "C" int abc_canon_desc_size(void) { return (int)sizeof(abc_canon_desc); }
 
-extern "C" int abc_canonical_order(const abc_canon_desc* d, abc_stream_t stream) {
-    const char* const entry = "canonical_order";
-    bool mol;
-    if (const int rc = abc_one_side(entry, d, mol)) return rc;
-    if (d->max_tries < 0) return abc_fail(ABC_EINVAL, "canonical_order: max_tries must be >= 0 (0: the default)");
-    if (d->max_rounds < 0) return abc_fail(ABC_EINVAL, "canonical_order: max_rounds must be >= 0 (0: the default)");
-    if (!d->order || !d->stats || !d->key) return abc_fail(ABC_EINVAL, "canonical_order: null output (order, stats, key)");
-    const int rows_given = (d->out_counts != nullptr) + (d->out_atoms != nullptr) + (d->out_bonds != nullptr) + (d->out_implh != nullptr);
-    if (rows_given != 0 && rows_given != 4) return abc_fail(ABC_EINVAL, "canonical_order: the canonical rows are four buffers, or none");
-    if (const int rc = abc_one_side_buffers(entry, d, mol)) return rc;
-    if (const int rc = abc_one_side_capacities(entry, d, mol)) return rc;
-    if (mol && rows_given && d->cap_mol_bonds > MAX_ROW_BONDS)
-        return abc_fail(ABC_EUNSUPPORTED, "canonical_order: cap_mol_bonds must be <= 4096 when the canonical rows are requested");
-    if (!mol && rows_given) return abc_fail(ABC_EINVAL, "canonical_order: the canonical rows are the molecule side's");
-    const size_t B = (size_t)d->B, cap = (size_t)(mol ? d->cap_atoms : d->max_atoms), cb = (size_t)(mol ? d->cap_mol_bonds : d->max_bonds);
-    const abc_extent out[8] = {{d->order, B * cap * 4}, {d->stats, B * NCOL * 4}, {d->key, B * 16}, {d->cert_out, B * (2 + cap + 3 * cb) * 4},
-                               {d->out_counts, B * 16}, {d->out_atoms, B * cap * ATOM_W * 4}, {d->out_bonds, B * cb * MOL_BOND_W * 4}, {d->out_implh, B * cap * 4}};
-    if (const int rc = abc_one_side_overlap(entry, d, mol, out)) return rc;
-    hipLaunchKernelGGL(graph_canon_kernel, dim3(d->B), dim3(GT), 0, (hipStream_t)stream, *d);
-    return abc_check_launch(entry);
+extern "C" int abc_canonical_order(const abc_canon_desc* d, abc_stream_t stream) { return canonical_order<false>(d, stream, "canonical_order"); }
+
+extern "C" int abc_canon_stereo_desc_size(void) { return (int)sizeof(abc_canon_stereo_desc); }
+
+extern "C" int abc_canonical_order_stereo(const abc_canon_stereo_desc* d, abc_stream_t stream) {
+    return canonical_order<true>(d, stream, "canonical_order_stereo");
 }

@@ -6,6 +6,10 @@
 
 // int32 words per row: atoms of both layouts, bond candidates, molecule bonds, record atoms, record bonds
 constexpr int ATOM_W = 5, CAND_W = 4, MOL_BOND_W = 4, REC_ATOM_W = 4, REC_BOND_W = 3;
+// the element table of stereo.hip, int32 [B][cap_atoms][STEREO_W] (include/abcnet_hip.h, abc_stereo_desc): [0] centre code; [1..4] a
+// marked centre's neighbours ascending, the hydrogen -1 last; [5] at the lower-index end of a candidate double bond its code; [6..11] of
+// a marked one the bond row, the partner, this end's substituents ascending, the partner's; "none" is 0 in [0] and [5], -1 elsewhere
+constexpr int STEREO_W = ABC_STEREO_W;
 constexpr int N_SYMBOLS = 14;        // the atom vocabulary of utils.py:12-13: indices 0 .. 13
 
 __device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }

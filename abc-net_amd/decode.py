@@ -90,8 +90,12 @@ class Molecule:
         out.append("M  END\n$$$$")
         return "".join(out)
 
-    def smiles(self, stereo=False, canonical=False, aromatize=False, double_bonds=False):
-        """aromatize=True: aromatized().smiles(stereo, canonical, double_bonds=...) -- the aromatic rings are perceived first
+    def smiles(self, stereo=False, canonical=False, aromatize=False, double_bonds=False, isomeric=False):
+        """isomeric=True: canonical(isomeric=True) written with both marks -- the canonical ISOMERIC form: equal strings if and only
+        if the stereo graphs are equal ("The isomeric order"), unless canonical_order(isomeric=True)'s status
+        says UNDECIDED or COLLISION.  A complete form of its own: stereo=, double_bonds= and canonical= are each refused with it;
+        aromatize=True is allowed (the stereo elements are perceived on the perceived rows).
+        aromatize=True: aromatized().smiles(stereo, canonical, double_bonds=...) -- the aromatic rings are perceived first
         (perceive_aromatic).
         A deterministic, valid SMILES of this graph by the text rule of DESIGN.md section 7 (the host form and the oracle of
         csrc/smiles.hip, integers only): NOT the canonical string RDKit prints; hs is not read.  stereo=False: wedges are single
@@ -103,6 +107,11 @@ class Molecule:
         RDKit's canonical string either; refused with stereo=True or double_bonds=True: wedge ownership and the drawn geometry are
         not in the invariant).
         ValueError for a row the rule refuses and for more than 99 ring bonds open at once."""
+        if isomeric:
+            if stereo or double_bonds or canonical:
+                raise ValueError("Molecule.smiles: isomeric=True already is canonical=True, stereo=True and double_bonds=True in one "
+                                 "(the canonical order that reads the stereo elements); give it alone, or with aromatize=True")
+            return (self.aromatized() if aromatize else self).canonical(isomeric=True)._smiles(True, True)[0]
         if aromatize:
             return self.aromatized().smiles(stereo=stereo, canonical=canonical, double_bonds=double_bonds)
         if canonical:
@@ -126,24 +135,32 @@ class Molecule:
                 tags[a - 1] = 1
         return classes, list(self.charges), bonds, tags
 
-    def canonical_order(self, max_tries=None, max_rounds=None):
+    def canonical_order(self, max_tries=None, max_rounds=None, isomeric=False):
         """(rank, stats, key): rank[a] the canonical position of atom a, the CANON_COLUMNS of the search as a dict, the two hash
-        words of abc_canon_desc.key -- canonical_labelling on canon_graph()"""
+        words of abc_canon_desc.key -- canonical_labelling on canon_graph().  isomeric=True: the search reads stereo_elements(self)
+        as its third key (the host form of abc_canonical_order_stereo) and a fourth value is returned, the STEREO_SEARCH_COLUMNS
+        as a list (abc_canon_stereo_desc.stereo_search)."""
         g = self.canon_graph()
-        rank, st, traces = canonical_labelling(g, CANON_DEFAULT_TRIES if max_tries is None else max_tries,
-                                               CANON_DEFAULT_ROUNDS if max_rounds is None else max_rounds)
+        tries = CANON_DEFAULT_TRIES if max_tries is None else max_tries
+        rounds = CANON_DEFAULT_ROUNDS if max_rounds is None else max_rounds
+        if isomeric:
+            rank, st, traces, search = canonical_labelling(g, tries, rounds, stereo=stereo_elements(self)[0])
+        else:
+            rank, st, traces = canonical_labelling(g, tries, rounds)
         if self.truncated:
             st["status"] |= CANON_TRUNCATED
-        return rank, st, canon_key(g, rank, traces)
+        key = canon_key(g, rank, traces)
+        return (rank, st, key, search) if isomeric else (rank, st, key)
 
-    def canonical(self, max_tries=None, max_rounds=None):
+    def canonical(self, max_tries=None, max_rounds=None, isomeric=False):
         """this molecule on its canonical atom order (the host form of abc_canonical_order's canonical rows): atom rows moved to
         their rank; both ends of every bond renumbered in place (end 1 stays end 1); the valid rows first, ascending by (lower end,
         higher end, original row), the rows the graph skips after them verbatim; implicit_hs renumbered, the entries in 1..n ascending,
         the others after them verbatim.  Two molecules with the same graph (classes, charges, order classes, listed atoms) give the
         same symbols, charges, bonds and implicit_hs, whatever their rows' order -- unless a budget ran out (canonical_order's
-        status)."""
-        rank = self.canonical_order(max_tries, max_rounds)[0]
+        status).  isomeric=True: on canonical_order(isomeric=True); two molecules with the same STEREO graph then give the same
+        stereo_centres() and double_bond_codes() too, which are the stereo word of the chosen leaf by construction."""
+        rank = self.canonical_order(max_tries, max_rounds, isomeric)[0]
         n = len(rank)
         at = sorted(range(n), key=lambda a: rank[a])
         valid, rest = [], []
@@ -470,16 +487,42 @@ class _CanonStop(Exception):
         self.bit = bit
 
 
-def canonical_labelling(graph, max_tries=CANON_DEFAULT_TRIES, max_rounds=CANON_DEFAULT_ROUNDS):
+def stereo_word(stereo, rank):
+    """the STEREO WORD of a leaf: one byte per canonical position, centre part | double-bond part << 2, each 0 none, 1 for +1, 2 for
+    -1.  Centre part of the atom at the position: s(a) times the sign of the permutation that sorts its neighbours by rank (the
+    hydrogen stays last).  Double-bond part, at the lower-RANK end: the bond's code times f(a) f(b), f(e) = -1 iff end e has two
+    substituents and the lower-ranked one is not the lower-indexed one -- "lowest-rank substituents together / opposite".
+    stereo: the element table of stereo_elements."""
+    word = [0] * len(rank)
+    for a, row in enumerate(stereo):
+        if row[0] in (1, -1):
+            nb = [rank[j] for j in row[1:5] if j >= 0]
+            swaps = sum(nb[i] > nb[j] for i in range(len(nb)) for j in range(i + 1, len(nb)))
+            word[rank[a]] |= 1 if row[0] * (-1 if swaps & 1 else 1) > 0 else 2
+        if row[5] in (1, -1):
+            v = row[5]
+            for lo, hi in ((row[8], row[9]), (row[10], row[11])):
+                if hi >= 0 and rank[lo] > rank[hi]:
+                    v = -v
+            word[min(rank[a], rank[row[7]])] |= (1 if v > 0 else 2) << 2
+    return word
+
+
+def canonical_labelling(graph, max_tries=CANON_DEFAULT_TRIES, max_rounds=CANON_DEFAULT_ROUNDS, stereo=None):
     """graph = (classes [n], charges [n], bonds [(i, j, order class)] 0-based, tags [n]) -> (rank [n], stats dict over CANON_COLUMNS,
     traces [(rounds, classes, sum)] of the chosen leaf).  rank[a] is the canonical position of atom a: the ranks of the least leaf
     under (trace_0, trace_1, .., h) of the search tree, certain unless the status says UNDECIDED (a budget ran out: the best leaf so
-    far, or the identity order before any leaf) or COLLISION (two 64-bit sums collided; the best leaf so far)."""
+    far, or the identity order before any leaf) or COLLISION (two 64-bit sums collided; the best leaf so far).
+    stereo (None: the plain search, as ever): the element table of stereo_elements.  The order of the leaves becomes (traces, h,
+    stereo_word), the word compared exactly, position by position; a leaf of equal h is mapped onto the best and verified as ever,
+    then: words equal -- an automorphism of the STEREO graph, merged and jumped as ever; word smaller -- the leaf becomes the best,
+    nothing is merged; greater -- a normal backtrack.  Only automorphisms that keep the stereo prune.  A fourth value is then
+    returned: [leaves of equal h and unequal word, stereo improvements, stereo automorphisms, 0] (STEREO_SEARCH_COLUMNS)."""
     classes, charges, bonds, tags = graph
     n = len(classes)
     st = dict.fromkeys(CANON_COLUMNS, 0)
     if n == 0:
-        return [], st, []
+        return ([], st, []) if stereo is None else ([], st, [], [0, 0, 0, 0])
     bi = np.array([q[0] for q in bonds], dtype=np.int64)
     bj = np.array([q[1] for q in bonds], dtype=np.int64)
     bo = np.array([q[2] for q in bonds], dtype=_U)
@@ -533,7 +576,8 @@ def canonical_labelling(graph, max_tries=CANON_DEFAULT_TRIES, max_rounds=CANON_D
     cur = [(0, 0, 0)] * n                               # the trace of every level of the current path
     cell, cell_max, choice, nxt = [0] * n, [0] * n, [0] * n, [0] * n
     orbit = [list(range(n)) for _ in range(CANON_ORBIT_LEVELS + 1)]
-    best = None                                         # (traces, choices, ids, h, rank) of the least leaf so far
+    best = None                                         # (traces, choices, ids, h, rank[, word]) of the least leaf so far
+    search = [0, 0, 0, 0]                               # stereo: STEREO_SEARCH_COLUMNS
     less_from = None                                    # the level at which the path became less than the best; None: equal so far
     try:
         ids, r, level = init.copy(), 0, 0
@@ -568,13 +612,22 @@ def canonical_labelling(graph, max_tries=CANON_DEFAULT_TRIES, max_rounds=CANON_D
                     for k2, a in enumerate(order.tolist()):
                         rank[a] = k2
                     h = canon_leaf_hash(graph, rank)
+                    word = None if stereo is None else stereo_word(stereo, rank)
                     if best is None or less_from is not None or h < best[3]:
                         st["improved"] += best is not None
-                        best, less_from = (cur[:level + 1], choice[:level], ids.copy(), h, rank), None
+                        best, less_from = (cur[:level + 1], choice[:level], ids.copy(), h, rank, word), None
                     elif h == best[3]:
                         gamma = automorphism(ids, best[2])
                         if gamma is None:
                             raise _CanonStop(CANON_COLLISION)
+                        if word != best[5]:
+                            search[0] += 1
+                            if word < best[5]:
+                                search[1] += 1
+                                st["improved"] += 1
+                                best = (cur[:level + 1], choice[:level], ids.copy(), h, rank, word)
+                            continue
+                        search[2] += stereo is not None
                         st["automorphisms"] += 1
                         target = next(l for l in range(level) if choice[l] != best[1][l])
                         for l in range(min(target, CANON_ORBIT_LEVELS) + 1):
@@ -629,9 +682,53 @@ def canonical_labelling(graph, max_tries=CANON_DEFAULT_TRIES, max_rounds=CANON_D
             mode = "child"
     except _CanonStop as stop:
         st["status"] |= stop.bit
-    if best is None:
-        return list(range(n)), st, []
-    return best[4], st, best[0]
+    out = (list(range(n)), st, []) if best is None else (best[4], st, best[0])
+    return out if stereo is None else out + (search,)
+
+
+# ------------------------------------------------------------------------------------------------- the stereo elements
+# The host form of csrc/stereo.hip (the contract: include/abcnet_hip.h, abc_stereo_desc; the layout: contract.STEREO_ELEMENT):
+# what the two stereo rules decide, as a table the canonical search can read.
+STEREO_W = 12
+STEREO_NONE_ROW = (0, -1, -1, -1, -1, 0, -1, -1, -1, -1, -1, -1)
+STEREO_STATS_COLUMNS = ("centres", "double_bonds", "flat", "status")
+STEREO_SEARCH_COLUMNS = ("unequal", "improved", "automorphisms", "reserved")
+STEREO_BAD_ROW = 4      # ABC_TEXT_BAD_ROW
+
+
+def stereo_elements(mol):
+    """(table [n][STEREO_W], stats [4]) of a Molecule, from its stereo_centres() and double_bond_codes().  Per atom row: [0] the
+    centre code (0, +1 / -1, 2 flat, 3 unqualified); [1..4] for a +1 / -1 centre its neighbours' 0-based rows ascending, the
+    hydrogen of a three-neighbour centre as -1 in the last place, else -1; [5] for the lower-index end of a candidate double bond the
+    code of that bond row (+1 / -1, 2, 3, 4), else 0; [6..11] for a +1 / -1 bond: the bond row, the partner, this end's one or two
+    substituents ascending (-1 for none), the partner's likewise, else -1.  stats: marked centres, marked double bonds, flat (both
+    kinds), status (1 EMPTY is the device's alone; 2 truncated; STEREO_BAD_ROW a row the writer refuses: the table is then all
+    STEREO_NONE_ROW).  (The writer's ring limit, which the perception does not have, is a refusal here too.)"""
+    n = len(mol.symbols)
+    status = 2 if mol.truncated else 0
+    try:
+        _, centre, ez = mol._smiles(True, True)
+    except ValueError:
+        return [list(STEREO_NONE_ROW) for _ in range(n)], [0, 0, 0, status | STEREO_BAD_ROW]
+    adj = [[] for _ in range(n)]
+    for e1, e2 in mol.bonds:
+        adj[e1 - 1].append(e2 - 1)
+        adj[e2 - 1].append(e1 - 1)
+    table = [list(STEREO_NONE_ROW) for _ in range(n)]
+    for a, c in enumerate(centre):
+        table[a][0] = c
+        if c in (1, -1):
+            table[a][1:5] = (sorted(adj[a]) + [-1])[:4]
+    for k, c in enumerate(ez):
+        if c == 0:
+            continue
+        a, b = min(mol.bonds[k]) - 1, max(mol.bonds[k]) - 1
+        table[a][5] = c
+        if c in (1, -1):
+            subs = [(sorted(s for s in adj[e] if s != p) + [-1])[:2] for e, p in ((a, b), (b, a))]
+            table[a][6:12] = [k, b] + subs[0] + subs[1]
+    flat = sum(c == 2 for c in centre) + sum(c == 2 for c in ez)
+    return table, [sum(c in (1, -1) for c in centre), sum(c in (1, -1) for c in ez), flat, status]
 
 
 # the text rule's classes (DESIGN.md section 7): the symbols written without brackets, the ones that may be aromatic, and OUR valence

@@ -68,12 +68,25 @@ def check_flags(flags):
             raise ValueError("InferenceRunner(%s=True, %s=True): %s" % (flag, other, why))
 
 
+def check_isomeric(smiles_isomeric, flags):
+    """the rule of smiles_isomeric, a flag of its own beside FLAG_NEEDS / FLAG_REFUSED (checked after check_flags): ValueError unless
+    smiles=True, and with each of the three forms it already is"""
+    if not smiles_isomeric:
+        return
+    if not flags["smiles"]:
+        raise ValueError("InferenceRunner(smiles_isomeric=True) is a form of the SMILES stage: it needs smiles=True")
+    for other in ("smiles_canonical", "smiles_stereo", "smiles_double_bonds"):
+        if flags[other]:
+            raise ValueError("InferenceRunner(smiles_isomeric=True, %s=True): smiles_isomeric already is smiles_canonical, smiles_stereo "
+                             "and smiles_double_bonds in one -- the canonical order that reads the stereo elements; give it alone" % other)
+
+
 class InferenceRunner:
     def __init__(self, model, batch, height, width, use_graph=True, device=None, extract=False, cap_atoms=512, cap_bonds=16384,
                  fold_bn=None, fp8=False, fp8_margin=1.0, guards=False, heads_epilogue=False, nms_in_heads=True, decode=False,
                  assemble=False, cap_mol_bonds=None, evaluate=False, score_graphs=False, score_radius=0, omega_rule="raw",
                  score_similarity=False, molblocks=False, score_identity=False, smiles=False, smiles_stereo=False,
-                 smiles_canonical=False, aromatize=False, smiles_double_bonds=False):
+                 smiles_canonical=False, aromatize=False, smiles_double_bonds=False, smiles_isomeric=False):
         """fp8: the e4m3 form of the BatchNorm-folded graph (unet.py, bf16 model): the 128-channel 3x3 convolutions at the output
         resolution on the block-scaled MFMA over e4m3 activations and weights (Engine(fp8=True)); the per-tensor activation scales
         are calibrated on the FIRST batch loaded (calibrate(); again on demand) by running the bf16 folded graph on it.
@@ -128,6 +141,13 @@ class InferenceRunner:
         RDKit's canonical SMILES).  molblocks=True keeps reading the assembler's rows: the mol block stays the reference's bytes.
         canonical_stats() returns the search's rows (an UNDECIDED image is reported there), canonical_keys() the hash keys.  Stereo is
         refused: wedge ownership and the drawn geometry are not in the invariant
+        smiles_isomeric (needs smiles=True; refused with each of smiles_canonical, smiles_stereo and smiles_double_bonds, because it
+        already is all three): the canonical ISOMERIC form.  .canonicalizer is GraphCanonicalizer(rows, stereo=True) -- the stereo
+        elements are perceived (ops.StereoPerceiver, a launch inside the canonicaliser op) and the search reads them as a third key
+        -- and the SMILES stage writes both marks on its canonical rows: smiles() is `m.smiles(isomeric=True)`, equal strings if and
+        only if equal STEREO graphs (unless canonical_stats() says UNDECIDED or COLLISION).  canonical_stats(), canonical_keys(),
+        stereo_stats(), double_bond_stats() work; stereo_search() is the read-back of the third key.  The old combination
+        smiles_canonical + smiles_stereo stays refused: the plain canonical order does not see the stereo, this one does
         aromatize (needs assemble=True): the aromatic rings of every assembled molecule are perceived (ops.AromaticityPerceiver, one
         launch right after the assembler in the same captured chain) and, when graph records are staged, those of every record (a
         second launch); the canonical order, the SMILES text and the three scores then read the PERCEIVED rows and records, so a ring
@@ -138,13 +158,15 @@ class InferenceRunner:
         omega_rule: the extractor's candidate rule (ops.PeakExtractor): "raw" (img2smiles2.py:139, the default) or "peaks"
         (img2smiles.py:139 / img2smiles3.py:140).  Everything after the extractor reads lists, not rules, so assemble, score_graphs,
         decode and fp8 work with either; .omega_rule names the one chosen"""
+        flags = dict(assemble=assemble, evaluate=evaluate, score_graphs=score_graphs, score_similarity=score_similarity,
+                     score_identity=score_identity, molblocks=molblocks, smiles=smiles, aromatize=aromatize, smiles_stereo=smiles_stereo,
+                     smiles_double_bonds=smiles_double_bonds, smiles_canonical=smiles_canonical)
         from .ops import OMEGA_RULES, AromaticityPerceiver, GraphAssembler, GraphCanonicalizer, GraphIdentity, GraphScore, GraphSimilarity, MolBlockWriter, PeakExtractor, SmilesWriter, check_nms_heads
         if omega_rule not in OMEGA_RULES:
             raise ValueError("InferenceRunner: omega_rule must be one of %s, got %r" % (sorted(OMEGA_RULES), omega_rule))
         self.omega_rule = omega_rule
-        check_flags(dict(assemble=assemble, evaluate=evaluate, score_graphs=score_graphs, score_similarity=score_similarity,
-                         score_identity=score_identity, molblocks=molblocks, smiles=smiles, aromatize=aromatize, smiles_stereo=smiles_stereo,
-                         smiles_double_bonds=smiles_double_bonds, smiles_canonical=smiles_canonical))
+        check_flags(flags)
+        check_isomeric(smiles_isomeric, flags)
         extract = bool(extract) or bool(assemble)
         check_nms_heads(model.heads, "InferenceRunner")
         if extract and tuple(model.heads) != HEADS:
@@ -201,7 +223,10 @@ class InferenceRunner:
                 rows = self.aromatizer.rows()
             if molblocks:
                 self.texter = MolBlockWriter.from_assembler(self.assembler)
-            if smiles_canonical:
+            if smiles_isomeric:
+                self.canonicalizer = GraphCanonicalizer(rows, stereo=True)
+                self.smiler = SmilesWriter(self.canonicalizer.rows(), stereo=True, double_bonds=True)
+            elif smiles_canonical:
                 self.canonicalizer = GraphCanonicalizer(rows)
                 self.smiler = SmilesWriter(self.canonicalizer.rows())
             elif smiles:
@@ -366,7 +391,8 @@ class InferenceRunner:
     def smiles(self):
         """a SMILES string of every image of the last step, written on the device: what `m.smiles()` gives for the m of
         molecules(), None where that is None (host sync; needs smiles=True); with smiles_stereo=True it is `m.smiles(stereo=True)`,
-        with smiles_canonical=True `m.smiles(canonical=True)`, with smiles_double_bonds=True `m.smiles(double_bonds=True, ...)`"""
+        with smiles_canonical=True `m.smiles(canonical=True)`, with smiles_double_bonds=True `m.smiles(double_bonds=True, ...)`, with
+        smiles_isomeric=True `m.smiles(isomeric=True)` (aromatize=True beside it where that flag is on)"""
         return self._read("smiler", "smiles")
 
     def canonical_stats(self):
@@ -377,6 +403,13 @@ class InferenceRunner:
     def canonical_keys(self):
         """the two hash words of every image's canonical graph (GraphCanonicalizer.keys; host sync; needs smiles_canonical=True)"""
         return self._read("canonicalizer", "keys")
+
+    def stereo_search(self):
+        """the third key of the canonical search of every image of the last step (GraphCanonicalizer.stereo_search: the
+        L.STEREO_SEARCH_COLUMNS; host sync; needs smiles_isomeric=True)"""
+        if self.canonicalizer is None or not self.canonicalizer.stereo:
+            raise L.AbcNetHipError("InferenceRunner was built without smiles_isomeric=True")
+        return self._read("canonicalizer", "stereo_search")
 
     def aromatic_stats(self):
         """the aromaticity perception of every image of the last step (AromaticityPerceiver.stats: the L.AROMATIC_COLUMNS -- status,

@@ -933,6 +933,47 @@ class _OneSideOp:
         return cls(records=records, **kw)
 
 
+class StereoPerceiver:
+    """the stereo elements of every assembled molecule, perceived on the device (csrc/stereo.hip, abc_perceive_stereo; the contract:
+    include/abcnet_hip.h): what SmilesWriter(stereo=True, double_bonds=True) decides about every centre and
+    every double bond of the same rows, as the element table GraphCanonicalizer(stereo=True) reads.  The molecule side only.  One
+    launch, static buffers, graph-capture safe; elements() and stats() are the host syncs.  No CPU fallback (the host form is
+    decode.stereo_elements)."""
+
+    def __init__(self, mol_counts, mol_atoms=None, mol_bonds=None, mol_implh=None):
+        """a contract.MoleculeRows (GraphAssembler.rows), or its four device tensors (hand-made rows); cap_atoms at most
+        L.MAX_SMILES_ATOMS, cap_mol_bonds at most L.MAX_SMILES_BONDS"""
+        rows = MoleculeRows.checked("StereoPerceiver", mol_counts, mol_atoms, mol_bonds, mol_implh, max_cap_atoms=L.MAX_SMILES_ATOMS,
+                                    max_cap_mol_bonds=L.MAX_SMILES_BONDS, need_implh=True)
+        self.lib = L.load()
+        self.keep = rows.tensors
+        self.B, self.cap = rows.B, rows.cap_atoms
+        self.table = torch.zeros((rows.B, rows.cap_atoms, L.STEREO_W), dtype=torch.int32, device=rows.device)
+        self.stat = torch.zeros((rows.B, len(L.STEREO_STATS_COLUMNS)), dtype=torch.int32, device=rows.device)
+        d = L.StereoDesc()
+        rows.fill(d)
+        d.elements, d.stats = self.table.data_ptr(), self.stat.data_ptr()
+        self.d = d
+
+    @classmethod
+    def from_assembler(cls, asm):
+        return cls(asm.rows)
+
+    def run(self, stream=None):
+        """one launch (graph-capturable): every word of the table and of the stats"""
+        L.check(self.lib.abc_perceive_stereo(C.byref(self.d), stream_or_current(stream)), "perceive_stereo")
+
+    def elements(self):
+        """int32 [B, cap_atoms, L.STEREO_W] on the host: the element table of the last run (contract.STEREO_ELEMENT names the
+        words; decode.STEREO_NONE_ROW past an image's atoms and for an image that is EMPTY or refused).  Host sync."""
+        return self.table.cpu()
+
+    def stats(self):
+        """the stats rows of the last run as a structured numpy array [B] with the int32 fields L.STEREO_STATS_COLUMNS (marked
+        centres, marked double bonds, flat of both kinds, status: L.MOL_EMPTY | L.MOL_TRUNCATED | L.TEXT_BAD_ROW).  Host sync."""
+        return _structured_rows(self.stat, L.STEREO_STATS_COLUMNS)
+
+
 class GraphCanonicalizer(_OneSideOp):
     """a canonical atom order for every image (csrc/graph_canon.hip, abc_canonical_order; the algorithm: include/abcnet_hip.h,
     DESIGN.md section 7): the least leaf of an individualise-and-refine search over every branch of the graph GraphIdentity defines,
@@ -941,15 +982,23 @@ class GraphCanonicalizer(_OneSideOp):
     if and only if the graphs are equal (this project's text rule on a canonical order, NOT RDKit's canonical SMILES).  The records
     side orders the atoms of contract.GraphRecords.  Certain whenever the status says so: UNDECIDED (a budget ran out) and COLLISION
     are reported per image, never hidden.  One launch, static buffers, graph-capture safe; orders(), stats(), keys() and
-    certificates() are the host syncs.  No CPU fallback (the host form is decode.Molecule.canonical())."""
+    certificates() are the host syncs.  No CPU fallback (the host form is decode.Molecule.canonical()).
+    stereo=True (abc_canonical_order_stereo, the molecule side only): the canonical ISOMERIC order -- the op owns a StereoPerceiver
+    of the same rows and its run() is two launches, perceive then order; the search reads the stereo elements as a third key, so
+    SmilesWriter(rows(), stereo=True, double_bonds=True) writes equal strings if and only if the STEREO graphs are equal (the host
+    form is decode.Molecule.smiles(isomeric=True)).  stereo_search() and stereo_elements() are its read-backs."""
 
     def __init__(self, mol_counts=None, mol_atoms=None, mol_bonds=None, mol_implh=None, records=None, max_tries=None, max_rounds=None,
-                 cert=False, rows=True):
+                 cert=False, rows=True, stereo=False):
         """a contract.MoleculeRows (GraphAssembler.rows) or its device tensors (mol_implh optional: no tags without it), OR
         records=contract.GraphRecords.  max_tries: individualisations per image, max_rounds: refinement rounds per image, replays
         included -- None: L.CANON_DEFAULT_TRIES / L.CANON_DEFAULT_ROUNDS.  cert: keep the relabelled graph of every image in .cert
         (int32 [B, 2 + cap + 3 cap_bonds]).  rows (molecule side): write the canonical rows (cap_mol_bonds <= 4096)."""
-        d = L.CanonDesc()
+        self.stereo = bool(stereo)
+        if self.stereo and records is not None:
+            raise ValueError("GraphCanonicalizer: stereo=True is the molecule side's (graph records carry no implicit-H list, so the "
+                             "stereo rules are not defined on them)")
+        d = L.CanonStereoDesc() if self.stereo else L.CanonDesc()
         d.max_tries, d.max_rounds = self.max_tries, self.max_rounds = _budgets(
             "GraphCanonicalizer", max_tries, max_rounds, (L.CANON_DEFAULT_TRIES, L.CANON_DEFAULT_ROUNDS))
         self.records, dev = self._bind(d, (mol_counts, mol_atoms, mol_bonds, mol_implh), records, bool(rows),
@@ -959,11 +1008,36 @@ class GraphCanonicalizer(_OneSideOp):
         self.key = torch.zeros((self.B, 2), dtype=torch.int64, device=dev)
         self.cert = torch.full((self.B, 2 + self.cap + 3 * self.cap_bonds), -1, dtype=torch.int32, device=dev) if cert else None
         d.order, d.stats, d.key, d.cert_out = self.order.data_ptr(), self.stat.data_ptr(), self.key.data_ptr(), L.ptr(self.cert)
+        self.perceiver = self.search = None
+        if self.stereo:
+            self.perceiver = StereoPerceiver(mol_counts, mol_atoms, mol_bonds, mol_implh)
+            self.search = torch.zeros((self.B, len(L.STEREO_SEARCH_COLUMNS)), dtype=torch.int32, device=dev)
+            d.elements, d.stereo_search = self.perceiver.table.data_ptr(), self.search.data_ptr()
         self.d = d
 
     def run(self, stream=None):
-        """one launch (graph-capturable): order, stats, key, and cert / the canonical rows when they were asked for"""
+        """one launch (graph-capturable): order, stats, key, and cert / the canonical rows when they were asked for; stereo=True:
+        two launches on the one stream, the perception first"""
+        if self.stereo:
+            self.perceiver.run(stream)
+            L.check(self.lib.abc_canonical_order_stereo(C.byref(self.d), stream_or_current(stream)), "canonical_order_stereo")
+            return
         L.check(self.lib.abc_canonical_order(C.byref(self.d), stream_or_current(stream)), "canonical_order")
+
+    def _need_stereo(self, what):
+        if not self.stereo:
+            raise L.AbcNetHipError("GraphCanonicalizer.%s: the op was built without stereo=True" % what)
+
+    def stereo_search(self):
+        """stereo=True: the stereo_search rows of the last run as a structured numpy array [B] with the int32 fields
+        L.STEREO_SEARCH_COLUMNS (leaves of equal h and unequal word, stereo improvements, stereo automorphisms, 0).  Host sync."""
+        self._need_stereo("stereo_search")
+        return _structured_rows(self.search, L.STEREO_SEARCH_COLUMNS)
+
+    def stereo_elements(self):
+        """stereo=True: StereoPerceiver.elements() of the op's own perceiver.  Host sync."""
+        self._need_stereo("stereo_elements")
+        return self.perceiver.elements()
 
     def rows(self):
         """the canonical rows of the last run as a contract.MoleculeRows on the device: what SmilesWriter(...) and

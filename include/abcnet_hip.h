@@ -1106,6 +1106,87 @@ int abc_canonical_order(const abc_canon_desc* d, abc_stream_t stream);
 /* sizeof(abc_canon_desc), for a binding's mirror struct (as abc_graph_identity_desc_size) */
 int abc_canon_desc_size(void);
 
+/* The STEREO ELEMENTS of every assembled molecule, perceived as a stage of its own (csrc/stereo.hip; the host form is
+ * decode.stereo_elements): what the tetrahedral rule of abc_write_smiles_stereo and the double-bond rule of
+ * abc_write_smiles_ez decide, word for word -- the writer's validation of rows (the duplicate-pair test too), its hydrogen count, its
+ * qualification, its int64 determinant and cross products, the position range 0..199999, the twin test, RING = not a bridge -- written
+ * as a table that abc_canonical_order_stereo reads.  One workgroup of 256 threads per image, the molecule side only, integers only,
+ * no global atomics, no allocation, no sync; the rows are read in place and every index read from a row is range-checked.
+ *   elements  [B][cap_atoms][ABC_STEREO_W], every word written by every launch; per atom row:
+ *               [0]      the centre code as abc_smiles_stereo_desc.stereo_out defines it: 0, +1 / -1, 2 flat, 3 unqualified;
+ *               [1..4]   for a +1 / -1 centre its neighbours' 0-based rows ascending, the hydrogen of a three-neighbour centre as -1
+ *                        in the last place; -1 otherwise;
+ *               [5]      for the atom that is the lower-index end of a candidate double bond, that bond row's code as
+ *                        abc_smiles_ez_desc.ez_out defines it (+1 / -1, 2, 3, 4); 0 otherwise;
+ *               [6..11]  for a +1 / -1 bond: the bond row, the partner, this end's one or two substituents ascending (-1 for none),
+ *                        the partner's likewise; -1 otherwise;
+ *             the NONE row (0, -1 x 4, 0, -1 x 6) past the atom count and for an image that is EMPTY or refused;
+ *   stats     [B][4]: marked centres, marked double bonds, flat (both kinds), status -- the EMPTY / TRUNCATED bits of mol_counts and
+ *             ABC_TEXT_BAD_ROW for rows abc_write_smiles refuses (the writer's ring limit is a limit of its text, not of the rows: it
+ *             is not read here);
+ *   limits    cap_atoms 1..ABC_MAX_SMILES_ATOMS, cap_mol_bonds 1..4096, else ABC_EUNSUPPORTED with nothing launched; a null buffer
+ *             (mol_implh too) is ABC_EINVAL.
+ * Not covered: what the two rules list as not covered; the records side (records carry no implicit-H list, so the hydrogen count,
+ * and with it qualification, is not defined there). */
+enum { ABC_STEREO_W = 12 };
+typedef struct abc_stereo_desc {
+    const int32_t* mol_counts;   /* [B][4] */
+    const int32_t* mol_atoms;    /* [B][cap_atoms][5] */
+    const int32_t* mol_bonds;    /* [B][cap_mol_bonds][4] */
+    const int32_t* mol_implh;    /* [B][cap_atoms] */
+    int32_t B, cap_atoms, cap_mol_bonds;
+    int32_t* elements;           /* [B][cap_atoms][ABC_STEREO_W] */
+    int32_t* stats;              /* [B][4] */
+} abc_stereo_desc;
+int abc_perceive_stereo(const abc_stereo_desc* d, abc_stream_t stream);
+/* sizeof(abc_stereo_desc), for a binding's mirror struct */
+int abc_stereo_desc_size(void);
+
+/* The canonical ISOMERIC order: abc_canonical_order with the stereo elements as a third key (a second instantiation of the same
+ * kernel; abc_canonical_order keeps its instructions).  Everything of abc_canon_desc holds -- tree, traces, trace pruning, budgets,
+ * replay, h, key, cert_out, the stats columns, the canonical rows -- and:
+ *   word      at a leaf, one byte per canonical position, centre part | double-bond part << 2, each 0 none, 1 for +1, 2 for -1.
+ *             Centre part, for the atom a at the position: s(a) (elements[a][0]) times the sign of the permutation that sorts its up
+ *             to four neighbours by rank, the hydrogen staying last.  Double-bond part, at the lower-RANK end of a marked double bond:
+ *             its code times f(a) f(b), f(e) = -1 iff end e has two substituents and the lower-ranked one is not the lower-indexed
+ *             one (the two lie on opposite sides: this is "lowest-rank substituents together / opposite").  An element whose indices
+ *             are not atoms of the image is read as none;
+ *   order     leaves are ordered by (traces, h, word), the word compared EXACTLY, position by position;
+ *   equal h   the map onto the best leaf is verified as ever (failure: ABC_CANON_COLLISION).  Words equal: the map is an
+ *             automorphism of the STEREO graph, merged into the orbit tables, and the search returns to the level where the paths
+ *             parted.  Word smaller: the leaf becomes the best (counted in `improved`), nothing is merged, no jump.  Greater: a normal
+ *             backtrack.  Orbit pruning so uses only automorphisms that keep the stereo; `automorphisms` counts those;
+ *   rows      the canonical rows are written as ever (positions move with their atoms, end 1 stays end 1): s and the double-bond codes
+ *             of abc_write_smiles_ez (tetrahedral != 0) on them ARE the word of the chosen leaf, so its text is equal if and only if
+ *             the stereo graphs are equal (unless UNDECIDED or COLLISION).  All leaves of equal h relabel to one graph: cert_out, key
+ *             and the plain text equal those of abc_canonical_order;
+ *   stereo_search [B][4]: leaves with equal h and unequal word, stereo improvements, stereo automorphisms, 0.
+ * The molecule side only: records with `elements` are ABC_EINVAL, as are a null elements or stereo_search. */
+typedef struct abc_canon_stereo_desc {
+    const int32_t* mol_counts;   /* the fields of abc_canon_desc, in its order */
+    const int32_t* mol_atoms;
+    const int32_t* mol_bonds;
+    const int32_t* mol_implh;
+    const int32_t* rec_atoms;    /* the records side: refused */
+    const int32_t* rec_bonds;
+    const int32_t* rec_counts;
+    int32_t B, cap_atoms, cap_mol_bonds, max_atoms, max_bonds;
+    int32_t max_tries, max_rounds;
+    int32_t* order;
+    int32_t* stats;
+    int64_t* key;
+    int32_t* cert_out;
+    int32_t* out_counts;
+    int32_t* out_atoms;
+    int32_t* out_bonds;
+    int32_t* out_implh;
+    const int32_t* elements;     /* [B][cap_atoms][ABC_STEREO_W]: abc_perceive_stereo's table of the same rows */
+    int32_t* stereo_search;      /* [B][4] */
+} abc_canon_stereo_desc;
+int abc_canonical_order_stereo(const abc_canon_stereo_desc* d, abc_stream_t stream);
+/* sizeof(abc_canon_stereo_desc), for a binding's mirror struct */
+int abc_canon_stereo_desc_size(void);
+
 /* Aromaticity perception: the rows of one side copied with the bonds of every aromatic cycle set to order 4, so that a ring drawn with
  * alternating orders 1 / 2 and the same ring drawn with order 4 are one graph for abc_canonical_order, abc_write_smiles and the three
  * graph scores, which take the output in place of the input (csrc/aromatic.hip; host form decode.perceive_aromatic; DESIGN.md section
@@ -1354,7 +1435,8 @@ int abc_smiles_stereo_desc_size(void);
  *               bond count and for an image without text).
  * The byte bound does not grow (a symbol byte per tree bond and closing is already counted).
  * Not covered: double bonds on any cycle (macrocyclic E/Z too), equivalence of an end's substituents beyond twin leaves, ends other
- * than C and N, RDKit's choice of which bonds to mark (all substituent bonds are marked), the canonical order, stereo in the scores. */
+ * than C and N, RDKit's choice of which bonds to mark (all substituent bonds are marked), the plain canonical order
+ * (abc_canonical_order_stereo is the order that reads these codes), stereo in the scores. */
 typedef struct abc_smiles_ez_desc {
     const int32_t* mol_counts;   /* the fields of abc_smiles_stereo_desc, in its order */
     const int32_t* mol_atoms;

@@ -44,6 +44,11 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            against Molecule.smiles(canonical=True), and how many of the 64 strings equal the canonical string of their annotation
            (the identity's `same` of profiles/r15_identity.md, position-free: 0 under raw, 7 under peaks).  Writes what it measured
            to profiles/r21_canonical.md
+           --isomeric: the canonical ISOMERIC form (csrc/stereo.hip and the stereo instantiation of csrc/graph_canon.hip,
+           InferenceRunner(smiles=True, smiles_isomeric=True)) under BOTH omega rules in this one process -- abc_perceive_stereo
+           alone, abc_canonical_order_stereo beside abc_canonical_order (with --parent-lib also the parent commit's build of it, on
+           the same descriptor), the step with and without, the fixture's stereo elements and third-key counters, smiles() against
+           Molecule.smiles(isomeric=True).  Writes what it measured to profiles/r24_isomeric.md
 
   aromatize (or --aromatize beside other parts): the aromaticity perception (csrc/aromatic.hip, InferenceRunner(aromatize=True)) under
            BOTH omega rules in this one process -- abc_perceive_aromatic alone, on the molecule rows and on the graph records, beside
@@ -57,7 +62,7 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--double-bonds] [--canonical] [--aromatize]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--double-bonds] [--canonical] [--aromatize] [--isomeric [--parent-lib PATH]]
 """
 import argparse
 import json
@@ -466,6 +471,90 @@ def part_smiles_canonical(m, x, notes, steps, warmup, reps=30, iters=200):
     print("wrote", path, flush=True)
 
 
+def part_smiles_isomeric(m, x, steps, warmup, parent_lib=None, iters=200):
+    """--isomeric: the canonical ISOMERIC form (InferenceRunner(smiles=True, smiles_isomeric=True)) under both omega rules in this one
+    process -- the perception launch alone, the stereo search launch beside the plain one (of this build and, with --parent-lib, of
+    the parent commit's library on the same descriptor, alternated), the step with the form against the plain canonical step and
+    the step without either; the stereo elements of the fixture, the third key's counters and how many strings equal their host
+    form.  The lines are printed and written to profiles/r24_isomeric.md (whose section on instruction counts is kept)."""
+    import ctypes as C
+    from abcnet_amd import _lib as L
+    from abcnet_amd.contract import current_stream
+    global RULE
+    lines, keep = [], RULE
+    parent = None
+    if parent_lib:
+        parent = C.CDLL(parent_lib)
+        parent.abc_canonical_order.restype, parent.abc_canonical_order.argtypes = C.c_int, [C.POINTER(L.CanonDesc), C.c_void_p]
+
+    def note(d):
+        lines.append(dict(d, omega_rule=RULE))
+        emit(d)
+    for RULE in ("raw", "peaks"):
+        rs = {}
+        for name, kw in (("assemble+smiles", dict(smiles=True)), ("assemble+smiles+canonical", dict(smiles=True, smiles_canonical=True)),
+                         ("assemble+smiles+isomeric", dict(smiles=True, smiles_isomeric=True))):
+            r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, omega_rule=RULE, **kw)
+            r.load_batch(x.to("cuda"))
+            for _ in range(2):
+                r.step()
+            rs[name] = r
+        torch.cuda.synchronize()
+        r, plain = rs["assemble+smiles+isomeric"], rs["assemble+smiles+canonical"]
+        st, search, el = r.canonical_stats(), r.stereo_search(), r.canonicalizer.perceiver.stats()
+        refused = sum(bool(s & ~3) for s in r.smiler.status())
+        mols = r.molecules()
+        out = {"part": "smiles", "what": "isomeric fixture", "batch": B, "refused_images": refused, "molecules": sum(mol is not None for mol in mols),
+               "marked_centres": int(el["centres"].sum()), "marked_double_bonds": int(el["double_bonds"].sum()), "flat": int(el["flat"].sum()),
+               "images_with_a_marked_element": int(((el["centres"] + el["double_bonds"]) > 0).sum()),
+               "images_with_unequal_words": int((search["unequal"] > 0).sum()), "stereo_improvements": int(search["improved"].sum()),
+               "stereo_automorphisms": int(search["automorphisms"].sum()),
+               "undecided_images": int(((st["status"] & L.CANON_UNDECIDED) != 0).sum()), "collision_images": int(((st["status"] & L.CANON_COLLISION) != 0).sum()),
+               "keys_equal_the_plain_search": bool((r.canonical_keys() == plain.canonical_keys()).all())}
+        out.update({c + "_max": int(st[c].max()) for c in ("leaves", "tries", "rounds")})
+        if not refused:
+            got = r.smiles()
+            host = [mol.smiles(isomeric=True) if mol is not None else None for mol in mols]
+            out.update({"strings_equal_to_host_form": sum(a == b for a, b in zip(got, host)), "strings": len(got),
+                        "texts_that_differ_from_plain_canonical": sum(a != b for a, b in zip(got, plain.smiles()))})
+        note(out)
+        cz = r.canonicalizer
+
+        def order_only():
+            L.check(cz.lib.abc_canonical_order_stereo(C.byref(cz.d), current_stream()), "canonical_order_stereo")
+
+        def parent_order():
+            L.check(parent.abc_canonical_order(C.byref(plain.canonicalizer.d), current_stream()), "parent canonical_order")
+        us = [(launch_us(cz.perceiver.run, iters), launch_us(order_only, iters), launch_us(plain.canonicalizer.run, iters),
+               launch_us(parent_order, iters) if parent else None, launch_us(r.smiler.run, iters), launch_us(plain.smiler.run, iters)) for _ in range(3)]
+        note({"part": "smiles", "what": "isomeric launch", "batch": B, "perceive_stereo_us_per_launch": [round(u[0], 2) for u in us],
+              "canonical_order_stereo_us_per_launch": [round(u[1], 2) for u in us], "canonical_order_us_per_launch": [round(u[2], 2) for u in us],
+              "parent_build_canonical_order_us_per_launch": [round(u[3], 2) for u in us] if parent else None,
+              "smiles_both_marks_us_per_call": [round(u[4], 2) for u in us], "plain_smiles_on_canonical_rows_us_per_call": [round(u[5], 2) for u in us],
+              "method": "device events around %d back-to-back calls (launch gaps included), alternated" % iters})
+        med = step_blocks(rs, steps, warmup, "smiles")
+        note({"part": "smiles", "what": "isomeric step", "ms_per_step": {k: round(v, 4) for k, v in med.items()},
+              "isomeric_minus_canonical_ms": round(med["assemble+smiles+isomeric"] - med["assemble+smiles+canonical"], 4),
+              "isomeric_minus_smiles_ms": round(med["assemble+smiles+isomeric"] - med["assemble+smiles"], 4)})
+        del rs, r, plain, cz
+    RULE = keep
+    path = os.path.join(ROOT, "profiles", "r24_isomeric.md")
+    marker, tail = "## Instruction counts", ""
+    if os.path.exists(path):
+        old = open(path).read()
+        tail = old[old.index(marker):] if marker in old else ""
+    with open(path, "w") as f:
+        f.write("# The canonical isomeric form on the trained fixture (b%d @ %d x %d, drawn_molecules(seed 777))\n\n" % (B, S, S))
+        f.write("`python profiles/tools/assemble_step.py --parts smiles --isomeric [--parent-lib <the parent commit's library>]`, one process, both "
+                "omega rules.  The perception launch alone; the stereo search launch beside the plain one of this build and of the parent "
+                "commit's build on the same descriptor (56 / 62 us in r21_canonical.md); the step with the form against the plain canonical "
+                "step and the step without either, in alternated blocks.\n\n```\n")
+        for d in lines:
+            f.write(json.dumps(d) + "\n")
+        f.write("```\n\n" + tail)
+    print("wrote", path, flush=True)
+
+
 def part_aromatize(m, x, notes, steps, warmup, iters=200):
     """--aromatize: both omega rules in this process -- abc_perceive_aromatic alone (molecule rows, then graph records) beside
     abc_canonical_order, the evaluating step with every graph stage without and with aromatize=True (alternated blocks), the stats
@@ -699,6 +788,8 @@ def main():
     ap.add_argument("--double-bonds", action="store_true", help="the smiles part: the double-bond marks, the four instantiations under both omega rules")
     ap.add_argument("--canonical", action="store_true", help="the smiles part: the canonical atom order, under both omega rules")
     ap.add_argument("--aromatize", action="store_true", help="the aromatize part: the aromaticity perception, under both omega rules")
+    ap.add_argument("--isomeric", action="store_true", help="the smiles part: the canonical isomeric form, under both omega rules")
+    ap.add_argument("--parent-lib", default=None, help="--isomeric: a libabcnet_hip.so of the parent commit, whose abc_canonical_order is timed beside")
     a = ap.parse_args()
     global RULE
     RULE = a.omega_rule
@@ -736,6 +827,8 @@ def main():
             part_smiles_double_bonds(m, x, a.steps, a.warmup)
         if a.canonical:
             part_smiles_canonical(m, x, notes, a.steps, a.warmup)
+        if a.isomeric:
+            part_smiles_isomeric(m, x, a.steps, a.warmup, parent_lib=a.parent_lib)
     if a.aromatize or "aromatize" in parts:
         part_aromatize(m, x, notes, a.steps, a.warmup)
 
