@@ -260,6 +260,11 @@ class SmilesEzDesc(C.Structure):
     _fields_ = SmilesStereoDesc._fields_ + [("tetrahedral", i32), ("ez_stats", vp), ("ez_out", vp)]
 
 
+class SmilesReadDesc(C.Structure):
+    _fields_ = [("text", vp), ("offsets", vp), ("rec_atoms", vp), ("rec_bonds", vp), ("rec_counts", vp), ("B", i32), ("max_atoms", i32),
+                ("max_bonds", i32), ("cap_text", i32), ("status", vp), ("stats", vp)]
+
+
 class ScanDesc(C.Structure):
     _fields_ = [("out", vp), ("src", vp), ("src_stride", i64), ("src_pitch", i32), ("src_max_h", i32), ("params", vp),
                 ("params_host", vp), ("B", i32), ("S", i32), ("margin", i32), ("cover_q8", i32), ("polarity", i32), ("hist", vp),
@@ -320,6 +325,10 @@ STEREO_NONE, STEREO_FLAT, STEREO_UNQUALIFIED = 0, 2, 3
 # the columns of abc_smiles_ez_desc.ez_stats; the codes of .ez_out beside +1 (together) / -1 (opposite)
 SMILES_EZ_COLUMNS = ("marked", "flat", "ring", "twin")
 EZ_NONE, EZ_FLAT, EZ_RING, EZ_TWIN = 0, 2, 3, 4
+# enum abc_smiles_read_status (one value per string, in order of priority), ABC_MAX_SMILES_READ_BYTES and the columns of
+# abc_smiles_read_desc.stats: defined beside the host form, decode.parse_smiles
+from .decode import (MAX_SMILES_READ_BYTES, READ_DUPLICATE, READ_EMPTY, READ_OK, READ_STATS_COLUMNS, READ_STATUS_NAMES,  # noqa: E402,F401
+                     READ_SYNTAX, READ_TOO_LONG, READ_TRUNCATED)
 # ABC_STEREO_W, the columns of abc_stereo_desc.stats and of abc_canon_stereo_desc.stereo_search: defined beside their host forms
 from .decode import STEREO_NONE_ROW, STEREO_SEARCH_COLUMNS, STEREO_STATS_COLUMNS, STEREO_W  # noqa: E402,F401
 
@@ -337,7 +346,8 @@ SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "a
                     (ScanCleanDesc, "abc_scan_clean_desc_size"), (SmilesDesc, "abc_smiles_desc_size"),
                     (SmilesStereoDesc, "abc_smiles_stereo_desc_size"), (CanonDesc, "abc_canon_desc_size"),
                     (AromaticDesc, "abc_aromatic_desc_size"), (SmilesEzDesc, "abc_smiles_ez_desc_size"),
-                    (StereoDesc, "abc_stereo_desc_size"), (CanonStereoDesc, "abc_canon_stereo_desc_size")]
+                    (StereoDesc, "abc_stereo_desc_size"), (CanonStereoDesc, "abc_canon_stereo_desc_size"),
+                    (SmilesReadDesc, "abc_smiles_read_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -449,6 +459,8 @@ SYMBOLS = {
     "abc_smiles_ez_work_ints": (i64, [P(SmilesEzDesc)]),
     "abc_write_smiles_ez": (C.c_int, [P(SmilesEzDesc), vp]),
     "abc_smiles_ez_desc_size": (C.c_int, []),
+    "abc_read_smiles": (C.c_int, [P(SmilesReadDesc), vp]),
+    "abc_smiles_read_desc_size": (C.c_int, []),
     "abc_plane_sum": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "abc_plane_sum_work": (C.c_int, [i32]),
     "abc_cbam_channel_fwd": (C.c_int, [P(CbamChannelDesc), vp]),

@@ -831,3 +831,163 @@ def perceive_aromatic(graph):
     st = dict.fromkeys(AROMATIC_COLUMNS, 0)
     st.update(candidates=sum(cand), cycles=len(found), aromatic=len(aromatic), rows_changed=sum(o != o2 for (_, _, o), o2 in zip(rows, orders)))
     return orders, codes, st
+
+
+# ---------------------------------------------------------------------------------------------------------- the SMILES reader
+# enum abc_smiles_read_status: the status word of abc_read_smiles, exactly one value per string, in order of priority
+READ_OK, READ_EMPTY, READ_TOO_LONG, READ_SYNTAX, READ_TRUNCATED, READ_DUPLICATE = 0, 1, 2, 3, 4, 5
+READ_STATUS_NAMES = ("OK", "EMPTY", "TOO_LONG", "SYNTAX", "TRUNCATED", "DUPLICATE")
+MAX_SMILES_READ_BYTES = 4096     # ABC_MAX_SMILES_READ_BYTES
+READ_STATS_COLUMNS = ("bytes", "atoms", "bonds", "ring_bonds")
+_READ_BARE = {b"B": 9, b"C": 1, b"N": 2, b"O": 3, b"P": 4, b"S": 7, b"F": 5, b"I": 11}
+_READ_ORDER = {b"-": 1, b"/": 1, b"\\": 1, b"=": 2, b"#": 3, b":": 4}
+_EMPTY_RECORD = (np.zeros((0, 4), dtype=np.int32), np.zeros((0, 3), dtype=np.int32))
+
+
+def smiles_bytes(text):
+    """the bytes of one string as the reader takes them: bytes as they are, a str in ASCII with `?` (a syntax error) for every
+    character outside it"""
+    if isinstance(text, (bytes, bytearray)):
+        return bytes(text)
+    if not isinstance(text, str):
+        raise ValueError("a SMILES string must be a str (or its bytes), got %s" % type(text).__name__)
+    return text.encode("ascii", "replace")
+
+
+def _read_class(symbol):
+    """the record's atom class of a symbol with its first letter in upper case: the raster.ATOM_VOCAB index, -1 outside it"""
+    return ATOM_SYMBOLS.index(symbol, 1) if symbol in ATOM_SYMBOLS[1:] else -1
+
+
+def _read_bracket(s, i):
+    """the bracket atom whose `[` stands at s[i] -> (end, class, charge, aromatic), or None"""
+    def digits(k):
+        while s[k:k + 1].isdigit():
+            k += 1
+        return k
+
+    def upper(k):
+        return b"A" <= s[k:k + 1] <= b"Z"
+
+    k = digits(i + 1)                                    # isotope
+    if s[k:k + 1] == b"*":
+        symbol, aromatic, k = "*", False, k + 1
+    elif upper(k):
+        n = 2 if b"a" <= s[k + 1:k + 2] <= b"z" else 1
+        symbol, aromatic, k = s[k:k + n].decode(), False, k + n
+    elif s[k:k + 2] in (b"se", b"as", b"te"):
+        symbol, aromatic, k = s[k:k + 2].decode().capitalize(), True, k + 2
+    elif s[k:k + 1] in (b"b", b"c", b"n", b"o", b"p", b"s") and k < len(s):
+        symbol, aromatic, k = s[k:k + 1].decode().upper(), True, k + 1
+    else:
+        return None
+    if s[k:k + 1] == b"@":                               # chirality: @ or @@, then a class such as TH1
+        k += 2 if s[k + 1:k + 2] == b"@" else 1
+        if upper(k) and upper(k + 1) and s[k + 2:k + 3].isdigit():
+            k = digits(k + 2)
+    if s[k:k + 1] == b"H":                               # hydrogens
+        k += 2 if s[k + 1:k + 2].isdigit() else 1
+    charge = 0
+    if s[k:k + 1] in (b"+", b"-"):
+        sign = s[k:k + 1]
+        unit = 1 if sign == b"+" else -1
+        k += 1
+        if s[k:k + 1].isdigit():
+            e = k + 2 if s[k + 1:k + 2].isdigit() else k + 1
+            charge, k = unit * int(s[k:e]), e
+        else:
+            n = 1
+            while n < 3 and s[k:k + 1] == sign:
+                n, k = n + 1, k + 1
+            charge = unit * n
+        if not -15 <= charge <= 15:
+            return None
+    if s[k:k + 1] == b":":                               # atom class
+        if not s[k + 1:k + 2].isdigit():
+            return None
+        k = digits(k + 1)
+    if s[k:k + 1] != b"]":
+        return None
+    return k + 1, _read_class(symbol), charge, aromatic
+
+
+def parse_smiles(text, max_atoms=None, max_bonds=None):
+    """One SMILES string read into a graph record by the reading rule of DESIGN.md section 7 (the host form and the reference of
+    csrc/smiles_read.hip; a stated subset of OpenSMILES, no claim about what RDKit accepts): -> (status, atoms int32 [n, 4]
+    (0, 0, class, charge), bonds int32 [m, 3] (i < j, order)), status one of READ_*; every status but READ_OK comes with an empty
+    record.  Sequential: one pass with the previous atom, the pending bond symbol, the branch stack and the open ring numbers."""
+    s = smiles_bytes(text)
+    if len(s) == 0:
+        return (READ_EMPTY,) + _EMPTY_RECORD
+    if len(s) > MAX_SMILES_READ_BYTES:
+        return (READ_TOO_LONG,) + _EMPTY_RECORD
+    syntax = (READ_SYNTAX,) + _EMPTY_RECORD
+    atoms, aromatic, bonds = [], [], []
+    prev, pending, stack, rings = None, 0, [], {}
+    need_atom, after_close = True, False          # after the start, `(` and `.`; between `)` and the next atom
+    i = 0
+    while i < len(s):
+        c = s[i:i + 1]
+        atom = None                               # (end, class, charge, aromatic)
+        if c == b"[":
+            atom = _read_bracket(s, i)
+            if atom is None:
+                return syntax
+        elif s[i:i + 2] in (b"Cl", b"Br"):
+            atom = (i + 2, 6 if c == b"C" else 8, 0, False)
+        elif c in _READ_BARE:
+            atom = (i + 1, _READ_BARE[c], 0, False)
+        elif c in (b"b", b"c", b"n", b"o", b"p", b"s"):
+            atom = (i + 1, _READ_BARE[c.upper()], 0, True)
+        elif c == b"*":
+            atom = (i + 1, -1, 0, False)
+        if atom is not None:
+            a = len(atoms)
+            atoms.append((0, 0, atom[1], atom[2]))
+            aromatic.append(atom[3])
+            if prev is not None:
+                bonds.append((prev, a, pending or (4 if aromatic[prev] and atom[3] else 1)))
+            prev, pending, need_atom, after_close, i = a, 0, False, False, atom[0]
+        elif c in _READ_ORDER:
+            if prev is None or pending:
+                return syntax
+            pending, i = _READ_ORDER[c], i + 1
+        elif c.isdigit() or c == b"%":
+            if c == b"%":
+                if not (s[i + 1:i + 2].isdigit() and s[i + 2:i + 3].isdigit()):
+                    return syntax
+                number, i = int(s[i + 1:i + 3]), i + 3
+            else:
+                number, i = int(c), i + 1
+            if prev is None or need_atom or after_close:      # a number is attached to the atom token before it
+                return syntax
+            if number in rings:
+                first, symbol = rings.pop(number)
+                if first == prev or (symbol and pending and symbol != pending):
+                    return syntax
+                bonds.append((first, prev, symbol or pending or (4 if aromatic[first] and aromatic[prev] else 1)))
+            else:
+                rings[number] = (prev, pending)
+            pending = 0
+        elif c == b"(":
+            if prev is None or pending or need_atom:
+                return syntax
+            stack.append(prev)
+            need_atom, i = True, i + 1
+        elif c == b")":
+            if not stack or pending or need_atom:
+                return syntax
+            prev, after_close, i = stack.pop(), True, i + 1
+        elif c == b".":
+            if stack or pending or need_atom:
+                return syntax
+            prev, need_atom, i = None, True, i + 1
+        else:
+            return syntax
+    if stack or pending or need_atom or rings:
+        return syntax
+    if (max_atoms is not None and len(atoms) > max_atoms) or (max_bonds is not None and len(bonds) > max_bonds):
+        return (READ_TRUNCATED,) + _EMPTY_RECORD
+    if len({(i, j) for i, j, _ in bonds}) != len(bonds):
+        return (READ_DUPLICATE,) + _EMPTY_RECORD
+    return READ_OK, np.array(atoms, dtype=np.int32).reshape(-1, 4), np.array(bonds, dtype=np.int32).reshape(-1, 3)

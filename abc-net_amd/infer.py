@@ -239,6 +239,7 @@ class InferenceRunner:
                 self.n_valid = torch.full((1,), eng.B, dtype=torch.int32, device=dev)
             self._build_evaluator(None)
         self.records = self.scorer = self.similarity = self.identity = None
+        self.smiles_reader = None      # (load_smiles builds it on first use)
         # (one set, staged once per batch, whichever score reads it)
         self.wants_graph_records = bool(score_graphs or score_similarity or score_identity)
         if self.wants_graph_records:
@@ -373,6 +374,30 @@ class InferenceRunner:
             self._need("scorer")
         with torch.cuda.device(self.dev):
             self.records.load(records)
+
+    def load_smiles(self, strings):
+        """score_similarity=True or score_identity=True: the batch's truth as SMILES strings, n <= batch of them -- a dataset's
+        SMILES column in place of annotation records (cal_acc.py's `df['Smiles']`).  An ops.SmilesReader, built on first use, reads
+        them on the device into the same .records load_graphs fills, on the same stream; a string the reading rule (DESIGN.md
+        section 7) refuses leaves an empty record, a miss for the scores (record_status() says which).  Refused with
+        score_graphs=True: that score reads positions and a SMILES has none."""
+        if self.records is None:
+            self._need("similarity")
+        if self.scorer is not None:
+            raise ValueError("InferenceRunner.load_smiles: score_graphs=True compares positions, and a SMILES string has none; "
+                             "load annotation records (load_graphs), or build the runner without score_graphs")
+        with torch.cuda.device(self.dev):
+            if self.smiles_reader is None:
+                from .ops import SmilesReader
+                self.smiles_reader = SmilesReader(self.records)
+            self.smiles_reader.load(strings)
+
+    def record_status(self):
+        """one L.READ_* value per string of the last load_smiles (host sync)"""
+        if self.smiles_reader is None:
+            raise L.AbcNetHipError("InferenceRunner.record_status: load_smiles was never called")
+        with torch.cuda.device(self.dev):
+            return self.smiles_reader.status()
 
     def candidates(self):
         """the per-image atom / bond candidate lists of the last step (host sync; needs extract=True)"""

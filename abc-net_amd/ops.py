@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .contract import (HEAD_NAMES, HEADS, REC_BOND_W, CandidateLists, DerivedGraphRecords, GraphRecords, MoleculeRows, check_head_maps,
+from .contract import (HEAD_NAMES, HEADS, REC_BOND_W, CandidateLists, DerivedGraphRecords, GraphRecords, MoleculeRows, PinnedStaging, check_head_maps,
                        check_targets, current_stream, require_device_tensor, set_target_ptrs, stream_or_current)
 
 EXTRACT_HEADS = HEADS      # the head widths extract.hip reads (train.py:47)
@@ -648,6 +648,72 @@ class SmilesWriter(PackedText):
         AbcNetHipError when an image was refused (BAD_ROW, RING_LIMIT) or did not fit (OVERFLOW).  Host sync: the index, then the
         text that was written."""
         return self._texts()
+
+
+class SmilesReader:
+    """graph records read from a batch of SMILES strings on the device (csrc/smiles_read.hip, abc_read_smiles): what
+    `decode.parse_smiles` gives for every string, written into the device twins of an existing contract.GraphRecords, so that every
+    reader of those records -- the three scores, AromaticityPerceiver.from_records, GraphCanonicalizer.from_records -- needs nothing
+    new.  The reading rule is this project's ("Reading a SMILES"): a stated subset of OpenSMILES; a string it
+    refuses leaves an empty record, which the scores count as a miss.  One launch per load; `status()` and `stats()` are the host
+    syncs."""
+
+    def __init__(self, records, cap_text=None):
+        """records: the contract.GraphRecords to fill (not a derived one); cap_text: bytes of the batch's text, default
+        B * L.MAX_SMILES_READ_BYTES (every string at the limit)"""
+        if not isinstance(records, GraphRecords) or isinstance(records, DerivedGraphRecords):
+            raise ValueError("SmilesReader: records must be a contract.GraphRecords that is loaded from the host, got %s" % type(records).__name__)
+        B = records.B
+        cap_text = B * L.MAX_SMILES_READ_BYTES if cap_text is None else int(cap_text)
+        if not (1 <= cap_text <= 2 ** 31 - 1):
+            raise ValueError("SmilesReader: cap_text must be 1..2^31-1 bytes, got %d" % cap_text)
+        self.lib = L.load()
+        self.records, self.B, self.cap_text = records, B, cap_text
+        dev = records.staging.device
+        with torch.cuda.device(dev):
+            self.staging = PinnedStaging(dev, {"text": ((cap_text,), torch.uint8), "offsets": ((B + 1,), torch.int32)})
+            self.status_words = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.stat = torch.zeros((B, len(L.READ_STATS_COLUMNS)), dtype=torch.int32, device=dev)
+        d = L.SmilesReadDesc()
+        d.text, d.offsets = (t.data_ptr() for t in self.staging.dev.values())
+        d.rec_atoms, d.rec_bonds, d.rec_counts = (t.data_ptr() for t in records.staging.dev.values())
+        d.B, d.max_atoms, d.max_bonds, d.cap_text = B, records.max_atoms, records.max_bonds, cap_text
+        d.status, d.stats = self.status_words.data_ptr(), self.stat.data_ptr()
+        self.d = d
+
+    def load(self, strings):
+        """n <= B str, one SMILES each (stripping a CSV field is the caller's job: every byte counts); the rows past n are empty
+        strings.  Asynchronous H2D of the bytes and offsets, then the launch, on the current stream; the records count as loaded."""
+        strings = list(strings)
+        if len(strings) > self.B:
+            raise ValueError("SmilesReader.load: expected at most %d strings, got %d" % (self.B, len(strings)))
+        for k, s in enumerate(strings):
+            if not isinstance(s, str):
+                raise ValueError("SmilesReader.load: string %d is a %s, not a str" % (k, type(s).__name__))
+        raw = [s.encode("ascii", "replace") for s in strings]      # (decode.smiles_bytes: `?`, a syntax error, for a character outside ASCII)
+        ends = np.cumsum([len(r) for r in raw], dtype=np.int64) if raw else np.zeros(0, dtype=np.int64)
+        total = int(ends[-1]) if len(ends) else 0
+        if total > self.cap_text:
+            raise ValueError("SmilesReader.load: %d bytes of text, cap_text is %d" % (total, self.cap_text))
+        h_text, h_off = self.staging.host.values()
+        self.staging.wait()
+        if total:
+            h_text[:total] = torch.from_numpy(np.frombuffer(b"".join(raw), dtype=np.uint8).copy())
+        h_off[0] = 0
+        h_off[1:len(raw) + 1] = torch.from_numpy(ends.astype(np.int32))
+        h_off[len(raw) + 1:] = total
+        with torch.cuda.device(self.staging.device):
+            self.staging.commit()
+            L.check(self.lib.abc_read_smiles(C.byref(self.d), current_stream()), "read_smiles")
+        self.records.loaded = True
+
+    def status(self):
+        """the B status words of the last load: one L.READ_* value per string (host sync)"""
+        return self.status_words.cpu().tolist()
+
+    def stats(self):
+        """{"bytes", "atoms", "bonds", "ring_bonds"} of the last load summed over the batch, and "rows", the four per string (host sync)"""
+        return _column_sums(self.stat, L.READ_STATS_COLUMNS)
 
 
 def stroke_max_iter(thin, what="StrokeNormalizer"):

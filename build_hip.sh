@@ -23,7 +23,7 @@ stale() {
 
 OBJS=""
 pids=""
-for f in conv_igemm conv_fast convt_fused conv_narrow stem heads heads_fused wgrad wgrad_heads wgrad_c1 wgrad_narrow bn_act loss misc optim cbam metrics eval_tables extract raster augment scan stroke assemble graph_score graph_sim graph_ident graph_canon stereo aromatic molblock smiles exchange; do
+for f in conv_igemm conv_fast convt_fused conv_narrow stem heads heads_fused wgrad wgrad_heads wgrad_c1 wgrad_narrow bn_act loss misc optim cbam metrics eval_tables extract raster augment scan stroke assemble graph_score graph_sim graph_ident graph_canon stereo aromatic molblock smiles smiles_read exchange; do
   if stale $f; then
     hipcc $FLAGS -MD -MF $f.d -c $f.hip -o $f.o &
     pids="$pids $!"

@@ -1463,6 +1463,42 @@ int abc_write_smiles_ez(const abc_smiles_ez_desc* d, abc_stream_t stream);
 /* sizeof(abc_smiles_ez_desc), for a binding's mirror struct */
 int abc_smiles_ez_desc_size(void);
 
+/* Read a batch of SMILES strings into graph records on the device: the writer's inverse (csrc/smiles_read.hip; decode.parse_smiles is
+ * the host form and the reference; the reading rule -- a stated subset of OpenSMILES, no claim about what RDKit accepts -- is in
+ * DESIGN.md section 7, "Reading a SMILES", and its token grammar in csrc/smiles_tokens.hpp).  The records are the ones
+ * raster.parse_graph fills from annotation strings, so the three scores, abc_perceive_aromatic and abc_canonical_order read them
+ * unchanged: rec_atoms (0, 0, class, charge) in order of appearance, rec_bonds (i < j 0-based, order 1..4) in the order of the byte
+ * that completes the bond.  Stereo marks, isotopes, hydrogen counts and atom classes are read and dropped.  One launch, one workgroup
+ * of 256 threads per string with the bytes in LDS, integers only, no atomics on global memory, no sync, no allocation: capturable.
+ *   text     the strings back to back; string b is the bytes text[offsets[b] .. offsets[b + 1]), every byte counts
+ *   offsets  [B + 1]; a pair that is not 0 <= offsets[b] <= offsets[b + 1] <= cap_text is ABC_READ_SYNTAX for that string
+ *   status   [B], exactly one abc_smiles_read_status per string, the first that holds in the enum's order; every launch writes it
+ *            and rec_counts for all B strings, and every status but ABC_READ_OK leaves 0 atoms and 0 bonds (rows past the counts
+ *            are unspecified)
+ *   stats    optional [B][4]: bytes, atoms, bonds, ring bonds of a string that was read (bytes alone otherwise)
+ *   limits   a string of more than ABC_MAX_SMILES_READ_BYTES bytes is ABC_READ_TOO_LONG: the bytes and one word or less per token
+ *            live in LDS (60 KB at 4096; 8192 would pass the 64 KB a kernel gets without asking).  max_atoms and max_bonds have no
+ *            upper limit: a string has fewer atoms and bonds than bytes */
+#define ABC_MAX_SMILES_READ_BYTES 4096   /* a power of two: the kernel packs an atom index into 12 bits */
+enum abc_smiles_read_status { ABC_READ_OK = 0, ABC_READ_EMPTY = 1, ABC_READ_TOO_LONG = 2, ABC_READ_SYNTAX = 3, ABC_READ_TRUNCATED = 4,
+                              ABC_READ_DUPLICATE = 5 };
+typedef struct abc_smiles_read_desc {
+    const uint8_t* text;         /* [cap_text] */
+    const int32_t* offsets;      /* [B + 1] */
+    int32_t* rec_atoms;          /* [B][max_atoms][4] */
+    int32_t* rec_bonds;          /* [B][max_bonds][3] */
+    int32_t* rec_counts;         /* [2][B]: atoms, then bonds */
+    int32_t B, max_atoms, max_bonds;   /* all >= 1 */
+    int32_t cap_text;            /* >= 1 */
+    int32_t* status;             /* [B] */
+    int32_t* stats;              /* [B][4] or null */
+} abc_smiles_read_desc;
+/* a null descriptor, a null pointer but stats, B < 1, max_atoms < 1, max_bonds < 1 or cap_text < 1 is ABC_EINVAL; nothing is
+ * launched then */
+int abc_read_smiles(const abc_smiles_read_desc* d, abc_stream_t stream);
+/* sizeof(abc_smiles_read_desc), for a binding's mirror struct */
+int abc_smiles_read_desc_size(void);
+
 /* ---- unet2: CBAM attention + residual (unet2.py:6-74).  See csrc/cbam.hip for the pass structure. ---- */
 typedef struct abc_cbam_channel_desc { /* ChannelAttentionModule (unet2.py:6-22), one MLP evaluation per image */
     const float* partial;  /* fwd: conv stats [B*tiles_per_img][4][C] (sum,sumsq,max,min of y2); bwd: [B*tiles_per_img][C] */

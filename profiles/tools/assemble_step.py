@@ -56,13 +56,18 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            the identity's exact / same / refine_equal and the count of canonical strings equal to their annotation's, with and
            without it.  Writes what it measured to profiles/r22_aromatic.md
 
+  --records-from-smiles (beside any parts, or with --parts none): the SMILES reader (csrc/smiles_read.hip, InferenceRunner.load_smiles) --
+           every annotation record of the fixture written as a string by the host writer and loaded as a string: abc_read_smiles
+           alone, decode.parse_smiles + GraphRecords.load on the host for the same strings, load + step with load_smiles against the
+           same with load_graphs, the identity and similarity totals both ways (they must be equal).  profiles/r26_smiles_reader.md
+
   --omega-rule {raw,peaks}: the extractor's candidate rule of every runner built here (InferenceRunner(omega_rule=...): "raw" is
            img2smiles2.py:139, "peaks" img2smiles.py:139 / img2smiles3.py:140); `graphs` and `score` then also report the candidates
            per image and abc_extract_peaks alone (as `launch`).  profiles/r09_omega_rule.md is one run per rule.
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--double-bonds] [--canonical] [--aromatize] [--isomeric [--parent-lib PATH]]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--double-bonds] [--canonical] [--aromatize] [--isomeric [--parent-lib PATH]] [--records-from-smiles]
 """
 import argparse
 import json
@@ -778,6 +783,90 @@ def part_graphs(r, notes):
           "share": round(same / len(mols), 4)})
 
 
+def part_records_from_smiles(m, x, notes, steps, warmup, iters=200, reps=20):
+    """--records-from-smiles: every annotation record of the fixture written as a string (the host writer on the record's graph) and
+    loaded as a string -- abc_read_smiles alone, decode.parse_smiles + GraphRecords.load for the same strings, the evaluating step
+    fed by load_smiles against the same step fed by load_graphs, and the identity and similarity totals both ways (equal, or it raises)"""
+    import ctypes as C
+    from abcnet_amd.decode import ATOM_SYMBOLS, Molecule, parse_smiles
+    from abcnet_amd.raster import parse_graph
+    strings = []
+    for a, q in (parse_graph(a, b, h=S // 4) for a, b in notes):
+        mol = Molecule([ATOM_SYMBOLS[max(int(t), 0)] for t in a[:, 2]], a[:, 3].tolist(), [0] * len(a), a[:, :2].tolist(),
+                       [[int(i) + 1, int(j) + 1] for i, j, _ in q], q[:, 2].tolist(), [])
+        strings.append(mol.smiles())
+    rs = {}
+    for name in ("load_graphs", "load_smiles"):
+        r = InferenceRunner(m, B, S, S, use_graph=True, assemble=True, evaluate=True, score_similarity=True, score_identity=True, omega_rule=RULE)
+        r.load_batch(x.to("cuda"))
+        rs[name] = r
+    parsed = lambda: [parse_smiles(t, 256, 256)[1:] for t in strings]
+    loads = {"load_graphs": lambda: rs["load_graphs"].load_graphs(parsed()), "load_smiles": lambda: rs["load_smiles"].load_smiles(strings)}
+    totals = {}
+    for name, r in rs.items():
+        loads[name]()
+        for _ in range(2):
+            r.step()
+        r.reset_evaluation()
+        r.step()
+        ev = r.evaluation()
+        totals[name] = {key: {k: (v.tolist() if k == "rows" else v) for k, v in ev[key].items() if k == "rows" or v == v} for key in ("identity", "similarity")}
+    if totals["load_graphs"] != totals["load_smiles"]:
+        raise SystemExit("the scores differ between load_graphs and load_smiles")
+    reader = rs["load_smiles"].smiles_reader
+    status = reader.status()
+    emit({"part": "records_from_smiles", "what": "fixture", "strings": len(strings), "bytes": sum(len(t) for t in strings),
+          "bytes_max": max(len(t) for t in strings), "read": status.count(0), "stats": {k: v for k, v in reader.stats().items() if k != "rows"},
+          "identity": {k: v for k, v in totals["load_smiles"]["identity"].items() if k != "rows"},
+          "similarity": {k: v for k, v in totals["load_smiles"]["similarity"].items() if k != "rows"}, "equal_both_ways": True})
+    lib, st = reader.lib, torch.cuda.current_stream().cuda_stream
+    us = [launch_us(lambda: lib.abc_read_smiles(C.byref(reader.d), st), iters) for _ in range(3)]
+
+    def wall(f):
+        out = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return round(statistics.median(out), 4)
+
+    emit({"part": "records_from_smiles", "what": "load", "batch": B, "read_smiles_us_per_launch": [round(u, 2) for u in us],
+          "host_parse_smiles_ms": wall(parsed), "host_parse_smiles_plus_records_load_ms": wall(loads["load_graphs"]),
+          "load_smiles_ms": wall(loads["load_smiles"]),
+          "method": "device events around %d back-to-back launches; wall clock between device syncs, median of %d" % (iters, reps)})
+    for r in rs.values():
+        for _ in range(warmup):
+            r.step()
+    times = {k: [] for k in rs}
+    for blk in range(4):
+        for name in (list(rs) if blk % 2 == 0 else list(rs)[::-1]):
+            for _ in range(steps // 4):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                loads[name]()
+                rs[name].step()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    for k, v in times.items():
+        emit({"part": "records_from_smiles", "what": "load + step", "form": k, "batch": B, "size": S, "steps": len(v),
+              "ms_median": round(med[k], 4), "ms_min": round(min(v), 4)})
+    emit({"part": "records_from_smiles", "load_smiles_minus_load_graphs_ms": round(med["load_smiles"] - med["load_graphs"], 4)})
+    # the launch at the limit: 64 copies of one 4096-byte string, four shapes (the bracket walk and the ring lanes are the one-lane phases)
+    from abcnet_amd.contract import GraphRecords
+    from abcnet_amd.ops import SmilesReader
+    long_reader = SmilesReader(GraphRecords(B, 4096, 4096, "cuda"))
+    shapes = {"chain": "C" * 4096, "nested 1365 deep": "C(" * 1365 + "C" + ")" * 1365, "1023 branches": "C(C)" * 1023 + "CCCC",
+              "819 rings": "C1CC1" * 819 + "C", "longest fixture string": max(strings, key=len)}
+    for name, text in shapes.items():
+        long_reader.load([text] * B)
+        us = [launch_us(lambda: lib.abc_read_smiles(C.byref(long_reader.d), st), iters) for _ in range(3)]
+        emit({"part": "records_from_smiles", "what": "launch at the limit", "shape": name, "bytes": len(text), "batch": B,
+              "read": long_reader.status().count(0), "read_smiles_us_per_launch": [round(u, 2) for u in us]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
@@ -790,6 +879,8 @@ def main():
     ap.add_argument("--aromatize", action="store_true", help="the aromatize part: the aromaticity perception, under both omega rules")
     ap.add_argument("--isomeric", action="store_true", help="the smiles part: the canonical isomeric form, under both omega rules")
     ap.add_argument("--parent-lib", default=None, help="--isomeric: a libabcnet_hip.so of the parent commit, whose abc_canonical_order is timed beside")
+    ap.add_argument("--records-from-smiles", action="store_true",
+                    help="the annotation records as SMILES strings: abc_read_smiles and load_smiles against parse_smiles + load_graphs")
     a = ap.parse_args()
     global RULE
     RULE = a.omega_rule
@@ -831,6 +922,8 @@ def main():
             part_smiles_isomeric(m, x, a.steps, a.warmup, parent_lib=a.parent_lib)
     if a.aromatize or "aromatize" in parts:
         part_aromatize(m, x, notes, a.steps, a.warmup)
+    if a.records_from_smiles:
+        part_records_from_smiles(m, x, notes, a.steps, a.warmup)
 
 
 if __name__ == "__main__":
