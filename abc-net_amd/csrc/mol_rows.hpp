@@ -11,6 +11,9 @@ constexpr int ATOM_W = 5, CAND_W = 4, MOL_BOND_W = 4, REC_ATOM_W = 4, REC_BOND_W
 // a marked one the bond row, the partner, this end's substituents ascending, the partner's; "none" is 0 in [0] and [5], -1 elsewhere
 constexpr int STEREO_W = ABC_STEREO_W;
 constexpr int N_SYMBOLS = 14;        // the atom vocabulary of utils.py:12-13: indices 0 .. 13
+// x and y of an atom row, 0 .. 199999: what the mol block can print (|px - 60| * 500 * 2 + 3 stays far inside int32), and the range of
+// the stereo rules (stereo_rules.hpp), where every product of two differences stays under 2^40
+constexpr int MAX_POSITION = 199999;
 
 __device__ inline int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 

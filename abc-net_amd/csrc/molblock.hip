@@ -32,7 +32,6 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int MT = 256;                  // threads per workgroup
-constexpr int MAX_POS = 199999;          // positions 0 .. 199999: |px - 60| * 500 * 2 + 3 stays far inside int32
 
 // utils.py:12-13 inverted, index 0 decoded as carbon (decode.ATOM_SYMBOLS), each padded to the 4 columns of the atom line
 __device__ const char SYMBOLS[N_SYMBOLS * 4 + 1] = "C   C   N   O   P   F   Cl  S   Br  B   Se  I   H   Si  ";
@@ -123,7 +122,7 @@ __device__ inline int64_t put_coord(const Out& o, int64_t pos, int px) {
 }
 
 __device__ inline bool atom_ok(const int* a) {
-    return a[0] >= 0 && a[0] <= MAX_POS && a[1] >= 0 && a[1] <= MAX_POS && a[2] >= 0 && a[2] < N_SYMBOLS;
+    return a[0] >= 0 && a[0] <= MAX_POSITION && a[1] >= 0 && a[1] <= MAX_POSITION && a[2] >= 0 && a[2] < N_SYMBOLS;
 }
 __device__ inline int atom_len(const int* a) { return coord_len(a[0]) + coord_len(a[1]) + LIT_LEN(ATOM_Z) + 4 + LIT_LEN(ATOM_TAIL); }
 __device__ inline int64_t put_atom(const Out& o, int64_t pos, const int* a) {

@@ -39,17 +39,12 @@
 #include "graph_ids.hpp"
 #include "text_pack.hpp"
 #include "text_hydrogens.hpp"
+#include "stereo_rules.hpp"      // ST, MAX_ATOMS, MAX_BONDS, the codes, the rank sort and both stereo rules: shared with stereo.hip
 
 namespace {
 
-constexpr int ST = 256;                              // threads per workgroup
-constexpr int MAX_ATOMS = ABC_MAX_SMILES_ATOMS;      // LDS arrays per atom
-constexpr int MAX_BONDS = 4096, MAX_SLOTS = 2 * MAX_BONDS;
 constexpr int MAX_NUMBER = 99;
 constexpr int LEN_BAD_ROW = -1, LEN_RING_LIMIT = -2;
-constexpr int CLS_DIRECTED = 5;      // <ez> behind the walk: a class-1 bond that bears "/" or "\\" (1 | 4: the wedge orders are gone by then)
-static_assert(MAX_ATOMS == 2 * ST, "the degree scan gives every thread two atoms");
-static_assert(MAX_ATOMS <= 1 << 13 && MAX_SLOTS <= 1 << 16, "a slot holds neighbour << 3 | class in 16 bits, an index of a slot too");
 
 // decode.ATOM_SYMBOLS, two columns each
 __device__ const char SYMBOL2[N_SYMBOLS * 2 + 1] = "C C N O P F ClS BrB SeI H Si";
@@ -117,72 +112,6 @@ struct Walk {
     signed char charge[MAX_ATOMS];
 };
 
-// the atom whose list holds slot s: start[a] <= s < start[a + 1]
-__device__ inline int owner_of(const Walk& w, int na, int s) {
-    int lo = 0, hi = na - 1;
-    while (lo < hi) {                      // (at most 10 rounds)
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int)w.start[mid] <= s) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// Order every atom's list: slot s of `src` goes to the position that counts the slots of its list with a smaller key (ties by
-// slot: a permutation whatever the keys).  by_rank: the key is the neighbour's preorder rank, else the slot's own 16 bits.
-// <ez> code: the code byte of every atom; a class-1 slot at a marked end (code +1 / -1) is stored as class 5, a slot with a direction
-template <bool by_rank, bool TAG = false>
-__device__ inline void order_lists(Walk& w, int na, int slots, int src, int tid, const signed char* code = nullptr) {
-    for (int s = tid; s < slots; s += ST) {
-        const int a = owner_of(w, na, s), lo = w.start[a], hi = w.start[a + 1];
-        const int e = w.adj[src][s];
-        const int key = by_rank ? (int)w.rank[e >> 3] : e;
-        int pos = 0;
-        for (int t = lo; t < hi; ++t) {
-            const int f = w.adj[src][t];
-            const int other = by_rank ? (int)w.rank[f >> 3] : f;
-            pos += other < key || (other == key && t < s);
-        }
-        if constexpr (TAG) {
-            const int ca = code[a], cy = code[e >> 3];
-            const bool directed = (e & 7) == 1 && (ca == 1 || ca == -1 || cy == 1 || cy == -1);
-            w.adj[src ^ 1][lo + pos] = (unsigned short)(directed ? e | CLS_DIRECTED : e);
-        } else {
-            w.adj[src ^ 1][lo + pos] = (unsigned short)e;
-        }
-    }
-}
-
-// stereo: the code of an atom (abc_smiles_stereo_desc.stereo_out), one byte of LDS each
-constexpr int ST_NONE = 0, ST_FLAT = 2, ST_UNQUALIFIED = 3;      // (+1 / -1: the local parity of a marked centre)
-constexpr int MAX_POSITION = 199999;                             // the mol block's range: every product below stays under 2^40
-
-// The code of atom i, a candidate (end 1 of a wedge row), by the rule: deg slots from lo in ascending neighbour index, zbits two
-// bits per slot (1: order 5, 2: order 6, from this end), single = every bond has class 1, h the text rule's hydrogen count.
-__device__ inline int stereo_code(const Walk& w, const int* pa, int i, int lo, int deg, unsigned zbits, bool single, int h) {
-    if (w.sym[i] == 12 || !single || !((deg == 4 && h == 0) || (deg == 3 && h == 1))) return ST_UNQUALIFIED;
-    const int xa = pa[i * ATOM_W], ya = pa[i * ATOM_W + 1];
-    bool flat = xa < 0 || xa > MAX_POSITION || ya < 0 || ya > MAX_POSITION;
-    long long px[4], py[4], pz[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        px[k] = py[k] = pz[k] = 0;         // (the hydrogen of deg == 3 stands on the centre)
-        if (k < deg) {
-            const int j = w.adj[1][lo + k] >> 3;      // (< na: the row's ends were checked in step 1)
-            const int x = pa[j * ATOM_W], y = pa[j * ATOM_W + 1];
-            flat |= x < 0 || x > MAX_POSITION || y < 0 || y > MAX_POSITION || (x == xa && y == ya);
-            const unsigned z = zbits >> (2 * k) & 3u;
-            px[k] = (long long)x - xa, py[k] = (long long)y - ya, pz[k] = z == 1 ? 1 : (z == 2 ? -1 : 0);
-        }
-    }
-    if (flat) return ST_FLAT;
-    const long long a1 = px[0] - px[3], a2 = py[0] - py[3], a3 = pz[0] - pz[3];
-    const long long b1 = px[1] - px[3], b2 = py[1] - py[3], b3 = pz[1] - pz[3];
-    const long long c1 = px[2] - px[3], c2 = py[2] - py[3], c3 = pz[2] - pz[3];
-    const long long t = a1 * (b2 * c3 - b3 * c2) - a2 * (b1 * c3 - b3 * c1) + a3 * (b1 * c2 - b2 * c1);
-    return t == 0 ? ST_FLAT : (t > 0 ? 1 : -1);
-}
-
 // The mark of a centre at preorder position p: 1 "@", 2 "@@".  The text names its four neighbours as parent, hydrogen, closings,
 // openings, children (the lists are in rank order: each kind stands in the order it is written); the local order is ascending
 // index with the hydrogen last, so the permutation's sign is the parity of the pairs out of order.
@@ -205,8 +134,7 @@ __device__ inline int stereo_marks(const Walk& w, int a, int p, int code) {
 }
 
 // ez: what is kept per atom of the double bond it is an end of (an atom is an end of at most one candidate)
-constexpr int EZ_NONE = 0, EZ_FLAT = 2, EZ_RING = 3, EZ_TWIN = 4;      // (+1 / -1: a marked double bond, together / opposite)
-constexpr unsigned EZ_SIDE0 = 1, EZ_SIDE1 = 2, EZ_UP = 4, EZ_FIXED = 8;
+constexpr unsigned EZ_UP = 4, EZ_FIXED = 8;      // (beside EZ_SIDE0, EZ_SIDE1 of the rule)
 template <bool EZ>
 struct Ends {
     short partner[EZ ? MAX_ATOMS : 1];          // after step 3: the other end of this atom's one class-2 bond if the atom may be an end, else -1
@@ -223,51 +151,6 @@ template <bool EZ>
 __device__ inline int ez_side(const Ends<EZ>& z, int e, int s) { return (z.bits[e] & (s == z.sub0[e] ? EZ_SIDE0 : EZ_SIDE1)) ? 1 : -1; }
 template <bool EZ>
 __device__ inline int ez_u(const Ends<EZ>& z, int e) { return (z.bits[e] & EZ_UP) ? 1 : -1; }
-
-// The code of the candidate between a < b (both possible ends naming each other), a bridge supposed; lists by index in adj[1].
-__device__ inline void ez_classify(const Walk& w, Ends<true>& z, const int* pa, int a, int b) {
-    int sub[2][2], cnt[2] = {0, 0};
-    bool twin = false;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int e = k ? b : a, other = k ? a : b;
-        sub[k][0] = sub[k][1] = e;
-        for (int s = w.start[e], hi = w.start[e + 1]; s < hi; ++s) {      // (degree 2 or 3: one or two besides the partner)
-            const int y = w.adj[1][s] >> 3;
-            if (y != other && cnt[k] < 2) sub[k][cnt[k]++] = y;
-        }
-        if (cnt[k] == 1) sub[k][1] = sub[k][0];
-        const int s0 = sub[k][0], s1 = sub[k][1];
-        twin |= cnt[k] == 2 && w.start[s0 + 1] - w.start[s0] == 1 && w.start[s1 + 1] - w.start[s1] == 1
-                && atom_class(w.sym[s0]) == atom_class(w.sym[s1]) && w.charge[s0] == w.charge[s1] && w.listed[s0] == w.listed[s1];
-    }
-    int code = EZ_TWIN;
-    unsigned bits[2] = {0, 0};
-    if (!twin) {
-        const long long ax = pa[a * ATOM_W], ay = pa[a * ATOM_W + 1], bx = pa[b * ATOM_W], by = pa[b * ATOM_W + 1];
-        const long long dx = bx - ax, dy = by - ay;
-        bool flat = ax < 0 || ax > MAX_POSITION || ay < 0 || ay > MAX_POSITION || bx < 0 || bx > MAX_POSITION || by < 0 || by > MAX_POSITION;
-        int side[2][2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const long long ex = k ? bx : ax, ey = k ? by : ay;
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const long long x = pa[sub[k][t] * ATOM_W], y = pa[sub[k][t] * ATOM_W + 1];
-                flat |= x < 0 || x > MAX_POSITION || y < 0 || y > MAX_POSITION;
-                const long long c = dx * (y - ey) - dy * (x - ex);      // (in range: below 2^40)
-                side[k][t] = (c > 0) - (c < 0);
-                flat |= c == 0;
-            }
-            flat |= cnt[k] == 2 && side[k][0] == side[k][1];
-            bits[k] = (side[k][0] > 0 ? EZ_SIDE0 : 0) | (side[k][1] > 0 ? EZ_SIDE1 : 0);
-        }
-        code = flat ? EZ_FLAT : (side[0][0] == side[1][0] ? 1 : -1);
-    }
-    z.code[a] = z.code[b] = (signed char)code;
-    z.sub0[a] = (short)sub[0][0], z.sub0[b] = (short)sub[1][0];
-    z.bits[a] = (unsigned char)bits[0], z.bits[b] = (unsigned char)bits[1];
-}
 
 // One lane, in text order: the directed bond read first -> second (an end of it is marked).  The first symbol met of a group fixes
 // the group: it is "/".  `stack` holds one end of every double bond whose neighbours are still to be tied (each once).
@@ -475,7 +358,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
             }
         }
         if constexpr (EZ) {
-            z.partner[i] = (short)(doubles == 1 && !others && (deg == 2 || deg == 3) && w.sym[i] <= 2 ? partner : -1);      // (0, 1: C; 2: N)
+            z.partner[i] = (short)possible_end(w, i, deg, doubles, others, partner);
             z.code[i] = EZ_NONE;
             z.bits[i] = 0;
         }
@@ -500,7 +383,7 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
     if constexpr (EZ) {                    // one thread per candidate, the one of its lower end (it alone writes both ends)
         for (int i = tid; i < na; i += ST) {
             const int j = z.partner[i];
-            if (j > i && z.partner[j] == i) ez_classify(w, z, pa, i, j);
+            if (j > i && z.partner[j] == i) ez_classify<true>(w, z, pa, i, j);
         }
     }
 
@@ -554,9 +437,9 @@ __global__ __launch_bounds__(ST) void smiles_compose_kernel(const typename DescO
         for (int i = tid; i < na; i += ST) {
             const int j = z.partner[i];
             if (j <= i || z.code[i] == EZ_NONE) continue;      // (a code: the two ends name each other)
-            const int child = w.parent[j] == i ? j : (w.parent[i] == j ? i : -1);
+            const bool bridge = is_bridge(w, z.low, i, j);      // (ahead of the code's load: the order that moves this kernel least, r27_stereo_rules.md)
             int code = z.code[i];
-            if (child < 0 || z.low[child] != w.rank[child]) z.code[i] = z.code[j] = (signed char)(code = EZ_RING);
+            if (!bridge) z.code[i] = z.code[j] = (signed char)(code = EZ_RING);
             atomicAdd(&ez_tally[code == EZ_FLAT ? 1 : (code == EZ_RING ? 2 : (code == EZ_TWIN ? 3 : 0))], 1);
         }
         __syncthreads();                   // (the codes are final: step 5 tags the slots, and here the tree bonds, that bear a symbol)

@@ -11,9 +11,12 @@
 //   4  ONE lane walks every component depth first with a lowpoint per atom: a candidate whose bond is no bridge is RING.  (A bridge is
 //      a property of the graph: the walk need not be the writer's.)
 //   5  the table, every word of the image's cap_atoms rows
-// The rules are written a second time here, word for word as in smiles.hip, whose instantiations must not move: tests/
-// test_gpu_stereo_perceive.py holds the two copies together on every case of both rules.  Every index read from a row is range-checked
-// before it addresses anything.
+// Both rules are the writer's, from the one header both files include (stereo_rules.hpp: the codes, the rank sort, stereo_code,
+// possible_end, ez_classify, is_bridge), so a rule changes in one place.  Written here again, as that header explains, are the row
+// checks and the fill of step 1, the duplicate test of step 2 and the slot loop of step 3; its own are the LDS struct, the walk of
+// step 4, the tally (three columns, FLAT of both kinds in one), the exits without elements and the table.  tests/
+// test_gpu_stereo_perceive.py holds the two kernels to one answer on every case of both rules.  Every index read from a row is
+// range-checked before it addresses anything.
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
@@ -21,18 +24,11 @@
 #include "mol_rows.hpp"
 #include "graph_ids.hpp"
 #include "text_hydrogens.hpp"
+#include "stereo_rules.hpp"      // ST, MAX_ATOMS, MAX_BONDS, the codes, the rank sort and both stereo rules: shared with smiles.hip
 
 namespace {
 
-constexpr int ST = 256;
-constexpr int MAX_ATOMS = ABC_MAX_SMILES_ATOMS;
-constexpr int MAX_BONDS = 4096, MAX_SLOTS = 2 * MAX_BONDS;
 constexpr int W = ABC_STEREO_W;
-constexpr int ST_NONE = 0, ST_FLAT = 2, ST_UNQUALIFIED = 3;
-constexpr int EZ_NONE = 0, EZ_FLAT = 2, EZ_RING = 3, EZ_TWIN = 4;
-constexpr int MAX_POSITION = 199999;      // the mol block's range: every product below stays under 2^40
-static_assert(MAX_ATOMS == 2 * ST, "the degree scan gives every thread two atoms");
-static_assert(MAX_ATOMS <= 1 << 13 && MAX_SLOTS <= 1 << 16, "a slot holds neighbour << 3 | class in 16 bits");
 static_assert(W == 12, "the layout of mol_rows.hpp");
 
 struct Lists {
@@ -46,88 +42,6 @@ struct Lists {
     unsigned char sym[MAX_ATOMS], listed[MAX_ATOMS];
     signed char charge[MAX_ATOMS], centre[MAX_ATOMS], code[MAX_ATOMS];
 };
-
-// the atom whose list holds slot s: start[a] <= s < start[a + 1]
-__device__ inline int owner_of(const Lists& w, int na, int s) {
-    int lo = 0, hi = na - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int)w.start[mid] <= s) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// the tetrahedral rule (smiles.hip, stereo_code): the code of atom i, end 1 of a wedge row
-__device__ inline int stereo_code(const Lists& w, const int* pa, int i, int lo, int deg, unsigned zbits, bool single, int h) {
-    if (w.sym[i] == 12 || !single || !((deg == 4 && h == 0) || (deg == 3 && h == 1))) return ST_UNQUALIFIED;
-    const int xa = pa[i * ATOM_W], ya = pa[i * ATOM_W + 1];
-    bool flat = xa < 0 || xa > MAX_POSITION || ya < 0 || ya > MAX_POSITION;
-    long long px[4], py[4], pz[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        px[k] = py[k] = pz[k] = 0;         // (the hydrogen of deg == 3 stands on the centre)
-        if (k < deg) {
-            const int j = w.adj[1][lo + k] >> 3;      // (< na: the row's ends were checked in step 1)
-            const int x = pa[j * ATOM_W], y = pa[j * ATOM_W + 1];
-            flat |= x < 0 || x > MAX_POSITION || y < 0 || y > MAX_POSITION || (x == xa && y == ya);
-            const unsigned z = zbits >> (2 * k) & 3u;
-            px[k] = (long long)x - xa, py[k] = (long long)y - ya, pz[k] = z == 1 ? 1 : (z == 2 ? -1 : 0);
-        }
-    }
-    if (flat) return ST_FLAT;
-    const long long a1 = px[0] - px[3], a2 = py[0] - py[3], a3 = pz[0] - pz[3];
-    const long long b1 = px[1] - px[3], b2 = py[1] - py[3], b3 = pz[1] - pz[3];
-    const long long c1 = px[2] - px[3], c2 = py[2] - py[3], c3 = pz[2] - pz[3];
-    const long long t = a1 * (b2 * c3 - b3 * c2) - a2 * (b1 * c3 - b3 * c1) + a3 * (b1 * c2 - b2 * c1);
-    return t == 0 ? ST_FLAT : (t > 0 ? 1 : -1);
-}
-
-// the one or two substituents of end e besides `other`, ascending; sub[1] = -1 for none (the lists are in index order)
-__device__ inline int substituents(const Lists& w, int e, int other, int (&sub)[2]) {
-    int cnt = 0;
-    sub[0] = sub[1] = -1;
-    for (int s = w.start[e], hi = w.start[e + 1]; s < hi; ++s) {      // (degree 2 or 3)
-        const int y = w.adj[1][s] >> 3;
-        if (y != other && cnt < 2) sub[cnt++] = y;
-    }
-    return cnt;
-}
-
-// the double-bond rule (smiles.hip, ez_classify): the code of the candidate between a < b, a bridge supposed
-__device__ inline int ez_classify(const Lists& w, const int* pa, int a, int b) {
-    int sub[2][2], cnt[2];
-    bool twin = false;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int e = k ? b : a, other = k ? a : b;
-        cnt[k] = substituents(w, e, other, sub[k]);
-        if (cnt[k] == 0) sub[k][0] = e;
-        if (cnt[k] <= 1) sub[k][1] = sub[k][0];
-        const int s0 = sub[k][0], s1 = sub[k][1];
-        twin |= cnt[k] == 2 && w.start[s0 + 1] - w.start[s0] == 1 && w.start[s1 + 1] - w.start[s1] == 1
-                && atom_class(w.sym[s0]) == atom_class(w.sym[s1]) && w.charge[s0] == w.charge[s1] && w.listed[s0] == w.listed[s1];
-    }
-    if (twin) return EZ_TWIN;
-    const long long ax = pa[a * ATOM_W], ay = pa[a * ATOM_W + 1], bx = pa[b * ATOM_W], by = pa[b * ATOM_W + 1];
-    const long long dx = bx - ax, dy = by - ay;
-    bool flat = ax < 0 || ax > MAX_POSITION || ay < 0 || ay > MAX_POSITION || bx < 0 || bx > MAX_POSITION || by < 0 || by > MAX_POSITION;
-    int side[2][2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const long long ex = k ? bx : ax, ey = k ? by : ay;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const long long x = pa[sub[k][t] * ATOM_W], y = pa[sub[k][t] * ATOM_W + 1];
-            flat |= x < 0 || x > MAX_POSITION || y < 0 || y > MAX_POSITION;
-            const long long c = dx * (y - ey) - dy * (x - ex);      // (in range: below 2^40)
-            side[k][t] = (c > 0) - (c < 0);
-            flat |= c == 0;
-        }
-        flat |= cnt[k] == 2 && side[k][0] == side[k][1];
-    }
-    return flat ? EZ_FLAT : (side[0][0] == side[1][0] ? 1 : -1);
-}
 
 // an image without elements (EMPTY, refused): every row of the table is "none"
 __device__ inline void none_row(int* el) {
@@ -210,17 +124,8 @@ __global__ __launch_bounds__(ST) void stereo_perceive_kernel(const abc_stereo_de
     }
     __syncthreads();
 
-    // ---- 2: by neighbour index (into adj[1]: a rank sort, position = how many of the list are smaller); a pair listed twice
-    for (int s = tid; s < slots; s += ST) {
-        const int a = owner_of(w, na, s), lo = w.start[a], hi = w.start[a + 1];
-        const int e = w.adj[0][s];
-        int pos = 0;
-        for (int t = lo; t < hi; ++t) {
-            const int f = w.adj[0][t];
-            pos += f < e || (f == e && t < s);
-        }
-        w.adj[1][lo + pos] = (unsigned short)e;
-    }
+    // ---- 2: by neighbour index (into adj[1]); a pair listed twice
+    order_lists<false>(w, na, slots, 0, tid);
     __syncthreads();
     bad = false;
     for (int i = tid; i < na; i += ST)
@@ -244,7 +149,7 @@ __global__ __launch_bounds__(ST) void stereo_perceive_kernel(const abc_stereo_de
             if (cls == 2) ++doubles, partner = w.adj[1][s] >> 3;
             else others |= cls != 1;
         }
-        w.partner[i] = (short)(doubles == 1 && !others && (deg == 2 || deg == 3) && w.sym[i] <= 2 ? partner : -1);      // (0, 1: C; 2: N)
+        w.partner[i] = (short)possible_end(w, i, deg, doubles, others, partner);
         w.code[i] = EZ_NONE;
         w.cursor[i] = w.start[i];
         int code = ST_NONE;
@@ -262,7 +167,7 @@ __global__ __launch_bounds__(ST) void stereo_perceive_kernel(const abc_stereo_de
     }
     for (int i = tid; i < na; i += ST) {   // one thread per candidate, the one of its lower end (it alone writes both ends)
         const int j = w.partner[i];
-        if (j > i && w.partner[j] == i) w.code[i] = w.code[j] = (signed char)ez_classify(w, pa, i, j);
+        if (j > i && w.partner[j] == i) ez_classify<false>(w, w, pa, i, j);      // (the code alone, at both ends)
     }
 
     // ---- 4: the bridges
@@ -295,9 +200,8 @@ __global__ __launch_bounds__(ST) void stereo_perceive_kernel(const abc_stereo_de
     for (int i = tid; i < na; i += ST) {   // a candidate that is no bridge is RING, whatever else it is; the counters
         const int j = w.partner[i];
         if (j <= i || w.code[i] == EZ_NONE) continue;      // (a code: the two ends name each other)
-        const int child = w.parent[j] == i ? j : (w.parent[i] == j ? i : -1);
         int code = w.code[i];
-        if (child < 0 || w.low[child] != w.rank[child]) w.code[i] = w.code[j] = (signed char)(code = EZ_RING);
+        if (!is_bridge(w, w.low, i, j)) w.code[i] = w.code[j] = (signed char)(code = EZ_RING);
         if (code == 1 || code == -1) atomicAdd(&tally[1], 1);
         if (code == EZ_FLAT) atomicAdd(&tally[2], 1);
     }
@@ -323,9 +227,9 @@ __global__ __launch_bounds__(ST) void stereo_perceive_kernel(const abc_stereo_de
         const int code = w.code[i];
         r[5] = code;
         if (code != 1 && code != -1) continue;
-        int sa[2], sb[2];
-        substituents(w, i, j, sa);
-        substituents(w, j, i, sb);
+        int sa[2], sb[2], ca = 0, cb = 0;      // (the counts are not needed: -1 stands where there is none)
+        substituents(w, i, j, -1, sa, ca);
+        substituents(w, j, i, -1, sb, cb);
         r[6] = q, r[7] = j, r[8] = sa[0], r[9] = sa[1], r[10] = sb[0], r[11] = sb[1];
     }
     if (tid < 4) d.stats[(size_t)b * 4 + tid] = tid == 3 ? c.status : tally[tid];

@@ -1108,9 +1108,10 @@ int abc_canon_desc_size(void);
 
 /* The STEREO ELEMENTS of every assembled molecule, perceived as a stage of its own (csrc/stereo.hip; the host form is
  * decode.stereo_elements): what the tetrahedral rule of abc_write_smiles_stereo and the double-bond rule of
- * abc_write_smiles_ez decide, word for word -- the writer's validation of rows (the duplicate-pair test too), its hydrogen count, its
- * qualification, its int64 determinant and cross products, the position range 0..199999, the twin test, RING = not a bridge -- written
- * as a table that abc_canonical_order_stereo reads.  One workgroup of 256 threads per image, the molecule side only, integers only,
+ * abc_write_smiles_ez decide, by the same code -- qualification, the int64 determinant and cross products, the position range
+ * 0..199999, the twin test and RING = not a bridge are stated once, in csrc/stereo_rules.hpp, for the writer and for this stage, which
+ * also validates rows (the duplicate-pair test too) and counts hydrogens as the writer does -- written as a table that
+ * abc_canonical_order_stereo reads.  One workgroup of 256 threads per image, the molecule side only, integers only,
  * no global atomics, no allocation, no sync; the rows are read in place and every index read from a row is range-checked.
  *   elements  [B][cap_atoms][ABC_STEREO_W], every word written by every launch; per atom row:
  *               [0]      the centre code as abc_smiles_stereo_desc.stereo_out defines it: 0, +1 / -1, 2 flat, 3 unqualified;

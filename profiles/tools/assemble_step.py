@@ -46,7 +46,8 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            to profiles/r21_canonical.md
            --isomeric: the canonical ISOMERIC form (csrc/stereo.hip and the stereo instantiation of csrc/graph_canon.hip,
            InferenceRunner(smiles=True, smiles_isomeric=True)) under BOTH omega rules in this one process -- abc_perceive_stereo
-           alone, abc_canonical_order_stereo beside abc_canonical_order (with --parent-lib also the parent commit's build of it, on
+           alone, abc_canonical_order_stereo beside abc_canonical_order, the writer with both marks and with the double-bond marks
+           alone (with --parent-lib also the parent commit's build of the plain search, the perception and both writers, each on
            the same descriptor), the step with and without, the fixture's stereo elements and third-key counters, smiles() against
            Molecule.smiles(isomeric=True).  Writes what it measured to profiles/r24_isomeric.md
 
@@ -478,19 +479,22 @@ def part_smiles_canonical(m, x, notes, steps, warmup, reps=30, iters=200):
 
 def part_smiles_isomeric(m, x, steps, warmup, parent_lib=None, iters=200):
     """--isomeric: the canonical ISOMERIC form (InferenceRunner(smiles=True, smiles_isomeric=True)) under both omega rules in this one
-    process -- the perception launch alone, the stereo search launch beside the plain one (of this build and, with --parent-lib, of
-    the parent commit's library on the same descriptor, alternated), the step with the form against the plain canonical step and
+    process -- the perception launch alone, the stereo search launch beside the plain one, the writer with both marks and with the
+    double-bond marks alone (with --parent-lib each also of the parent commit's library on the same descriptor, alternated), the step with the form against the plain canonical step and
     the step without either; the stereo elements of the fixture, the third key's counters and how many strings equal their host
     form.  The lines are printed and written to profiles/r24_isomeric.md (whose section on instruction counts is kept)."""
     import ctypes as C
     from abcnet_amd import _lib as L
     from abcnet_amd.contract import current_stream
+    from abcnet_amd.ops import SmilesWriter
     global RULE
     lines, keep = [], RULE
     parent = None
     if parent_lib:
         parent = C.CDLL(parent_lib)
         parent.abc_canonical_order.restype, parent.abc_canonical_order.argtypes = C.c_int, [C.POINTER(L.CanonDesc), C.c_void_p]
+        parent.abc_perceive_stereo.restype, parent.abc_perceive_stereo.argtypes = C.c_int, [C.POINTER(L.StereoDesc), C.c_void_p]
+        parent.abc_write_smiles_ez.restype, parent.abc_write_smiles_ez.argtypes = C.c_int, [C.POINTER(L.SmilesEzDesc), C.c_void_p]
 
     def note(d):
         lines.append(dict(d, omega_rule=RULE))
@@ -530,18 +534,29 @@ def part_smiles_isomeric(m, x, steps, warmup, parent_lib=None, iters=200):
 
         def parent_order():
             L.check(parent.abc_canonical_order(C.byref(plain.canonicalizer.d), current_stream()), "parent canonical_order")
+        # the writer with the double-bond marks alone, on the same canonical rows (the runner's own writes both marks); of the parent
+        # commit's build the perception and both of these writers, each on this build's descriptor
+        ez = SmilesWriter(cz.rows(), double_bonds=True)
+
+        def of_parent(entry, d):
+            return (lambda: L.check(getattr(parent, entry)(C.byref(d), current_stream()), "parent " + entry)) if parent else None
+        beside = {"perceive_stereo": of_parent("abc_perceive_stereo", cz.perceiver.d), "smiles_both_marks": of_parent("abc_write_smiles_ez", r.smiler.d),
+                  "smiles_double_bonds": of_parent("abc_write_smiles_ez", ez.d)}
         us = [(launch_us(cz.perceiver.run, iters), launch_us(order_only, iters), launch_us(plain.canonicalizer.run, iters),
-               launch_us(parent_order, iters) if parent else None, launch_us(r.smiler.run, iters), launch_us(plain.smiler.run, iters)) for _ in range(3)]
+               launch_us(parent_order, iters) if parent else None, launch_us(r.smiler.run, iters), launch_us(plain.smiler.run, iters),
+               launch_us(ez.run, iters), {k: launch_us(f, iters) for k, f in beside.items() if f}) for _ in range(3)]
         note({"part": "smiles", "what": "isomeric launch", "batch": B, "perceive_stereo_us_per_launch": [round(u[0], 2) for u in us],
               "canonical_order_stereo_us_per_launch": [round(u[1], 2) for u in us], "canonical_order_us_per_launch": [round(u[2], 2) for u in us],
               "parent_build_canonical_order_us_per_launch": [round(u[3], 2) for u in us] if parent else None,
               "smiles_both_marks_us_per_call": [round(u[4], 2) for u in us], "plain_smiles_on_canonical_rows_us_per_call": [round(u[5], 2) for u in us],
+              "smiles_double_bonds_us_per_call": [round(u[6], 2) for u in us],
+              "parent_build_us": {k: [round(u[7][k], 2) for u in us] for k in us[0][7]} if parent else None,
               "method": "device events around %d back-to-back calls (launch gaps included), alternated" % iters})
         med = step_blocks(rs, steps, warmup, "smiles")
         note({"part": "smiles", "what": "isomeric step", "ms_per_step": {k: round(v, 4) for k, v in med.items()},
               "isomeric_minus_canonical_ms": round(med["assemble+smiles+isomeric"] - med["assemble+smiles+canonical"], 4),
               "isomeric_minus_smiles_ms": round(med["assemble+smiles+isomeric"] - med["assemble+smiles"], 4)})
-        del rs, r, plain, cz
+        del rs, r, plain, cz, ez
     RULE = keep
     path = os.path.join(ROOT, "profiles", "r24_isomeric.md")
     marker, tail = "## Instruction counts", ""

@@ -81,6 +81,12 @@ WIDE_4 = rows(["C", "F", "Cl", "Br", "I"], [(100000, 100000), (0, 0), (0, 199999
               [(1, 2, 5), (1, 3, 1), (1, 4, 5), (1, 5, 1)])
 
 
+def wedged_chain():
+    """512 atoms, the capacity: a chain of 511 carbons with a methyl (atom 512) on atom 500, the wedge from atom 500 to it"""
+    places = [(2 * i + (i % 3), 40 + (i * i) % 7) for i in range(511)] + [(2 * 499 + 9, 80)]
+    return rows(["C"] * 512, places, [(i, i + 1, 1) for i in range(1, 511)] + [(500, 512, 6)])
+
+
 def random_rows(rng):
     """one molecule of the seeded recipe, built so that centres exist: a tree of 4..24 atoms of degree <= 4 (now and then 5) with a
     few ring bonds, mostly carbon, mostly single bonds, places on a 20..W-20 grid; then wedges from atoms of degree 3 and 4 (and a

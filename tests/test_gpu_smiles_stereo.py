@@ -22,7 +22,7 @@ import smiles_stereo_oracle as S  # noqa: E402
 from molrows import assemble_golden, filled_unet  # noqa: E402
 from smiles_cases import chain, complete  # noqa: E402
 from smiles_cases import random_rows as plain_random_rows  # noqa: E402
-from smiles_stereo_cases import CASES, REFUSALS, WIDE, WIDE_4, random_images, rows  # noqa: E402
+from smiles_stereo_cases import CASES, REFUSALS, WIDE, WIDE_4, random_images, wedged_chain  # noqa: E402
 
 DEV = "cuda"
 EINVAL, EUNSUPPORTED = -1, -2
@@ -142,8 +142,7 @@ def test_device_text_read_back_agrees_with_the_geometry(device_texts):
 
 def test_wide_indices():
     """cap_atoms 512: a chain of 511 carbons with a methyl on atom 500, the wedge from atom 500 to it"""
-    places = [(2 * i + (i % 3), 40 + (i * i) % 7) for i in range(511)] + [(2 * 499 + 9, 80)]
-    image = rows(["C"] * 512, places, [(i, i + 1, 1) for i in range(1, 511)] + [(500, 512, 6)]) + (0,)
+    image = wedged_chain() + (0,)
     w = _run([image, chain(512) + (0,)], 512, 512)
     texts = _check(w, [image, chain(512) + (0,)])
     codes = w.parities()

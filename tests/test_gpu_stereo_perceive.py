@@ -1,6 +1,7 @@
 """The stereo perception stage on the device (csrc/stereo.hip, abc_perceive_stereo, ops.StereoPerceiver) against the SMILES writer's
-own codes on the same rows (the rules are written twice: this holds the two copies together) and against the host form
-decode.stereo_elements.  Integers: exact, no tolerance anywhere."""
+own codes on the same rows (the two kernels take both rules from csrc/stereo_rules.hpp, but each fills its own lists, does its own walk
+and writes its own outputs: this holds them to one answer) and against the host form decode.stereo_elements.  Integers: exact, no
+tolerance anywhere."""
 import ctypes as C
 import os
 import sys
@@ -173,6 +174,14 @@ def test_a_long_chain_past_one_atom_per_thread():
     assert st[0].tolist() == [1, 1, 0, 0]
     assert el[0, 280, 0] in (1, -1) and el[0, 280, 1:5].tolist() == [279, 281, 299, -1]
     assert el[0, 270, 5] in (1, -1) and el[0, 270, 6:].tolist() == [270, 271, 269, -1, 272, -1]
+
+
+def test_at_the_capacity_of_512_atoms():
+    """MAX_ATOMS == 2 * ST, the last thread's second atom: the 512-carbon zigzag polyene (255 marked double bonds; the last candidate
+    has its lower end at index 509 and the last atom, 511, for a substituent) and the 512-atom chain with the wedge from atom 500"""
+    images = [with_status(EZ.zigzag_polyene(512)), with_status(ST.wedged_chain()), with_status(ONE_ATOM)]
+    el, st = check(images, cap_atoms=512, cap_bonds=512)
+    assert st[0, 1] == 255 and st[1, 0] == 1
 
 
 def test_a_second_run_overwrites_every_word_and_is_capturable():
