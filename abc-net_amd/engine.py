@@ -10,17 +10,21 @@ never materialised by a copy: the encoder conv and the transposed conv write the
 channel halves of one buffer in place (unet.py:51-59).
 
 PyTorch is used here only to own device memory and the stream.
+
+This module holds the core (memory, emitters, the trunk and its backward, unet2, execution); the output heads' plans are
+engine_heads.HeadsPlan, which Engine inherits, and Op / Src / Rec are engine_types'.
 """
 from __future__ import annotations
 
 import ctypes as C
 import weakref
-from typing import NamedTuple
 
 import torch
 
 from . import _lib as L
 from . import arch
+from .engine_heads import HeadsPlan
+from .engine_types import Op, Rec, Src, taps_mirror, taps_square
 
 BN_EPS = 1e-5
 BN_MOM = 0.1
@@ -32,15 +36,6 @@ def head_offsets(heads):
         offs.append(o)
         o += h
     return offs
-
-
-def taps_square(k):
-    p = (k - 1) // 2
-    return [(ky - p, kx - p) for ky in range(k) for kx in range(k)]
-
-
-def taps_mirror(taps):
-    return [(-dy, -dx) for dy, dx in taps]
 
 
 def convT_phase_taps(py, px, crop_y=True, crop_x=True):
@@ -73,50 +68,6 @@ def convT_dgrad_taps(crop_y=True, crop_x=True):
 TAPS_CONVT_DGRAD = convT_dgrad_taps()
 
 
-class Op(NamedTuple):
-    """one launch of a plan: fn(*args, stream).  args keeps what it points to alive (byref objects hold their structure); it is a list
-    because a workspace pointer may be patched in once the plan knows its size (_finish_build)"""
-    fn: object
-    args: list
-    what: str
-    writes: tuple   # names of parameters whose GRADIENT is final once this op has run (bucketed all-reduce)
-    meta: dict      # {kernel, flops, bytes}: algorithmic work of this launch (for the roofline report)
-
-
-class Src:
-    """an activation as a consumer sees it: raw tensor + on-load transform"""
-
-    def __init__(self, t, dt, H, W, ld, coff, C, coef=None, pool=False, drop_p=0.0, drop_seed=0, producer=None, planar=False):
-        self.t, self.dt, self.H, self.W, self.ld, self.coff, self.C = t, dt, H, W, ld, coff, C
-        self.coef, self.pool, self.drop_p, self.drop_seed, self.producer = coef, pool, drop_p, drop_seed, producer
-        self.drop_salt = None  # device uint32 scalar added to drop_seed (the engine's per-step counter)
-        self.planar = planar  # NCHW f32 [B][C][H][W] (head maps / their gradients)
-        self.q = None         # fp8 tensors: (amax, s, 1 / s) device scalars of the per-tensor scale
-
-    def lh(self):  # logical dims
-        return (self.H // 2, self.W // 2) if self.pool else (self.H, self.W)
-
-    def fill(self, a: L.ActSrc):
-        a.x = self.t.data_ptr()
-        a.planar, a.ctot = (1, self.C) if self.planar else (0, 0)
-        if self.coef is not None:
-            a.scale, a.shift, a.slope = (c.data_ptr() for c in self.coef)
-        else:
-            a.scale = a.shift = a.slope = None
-        a.Hx, a.Wx, a.ldx, a.pool = self.H, self.W, self.ld, 1 if self.pool else 0
-        a.drop_p, a.drop_seed = self.drop_p, self.drop_seed
-        a.drop_salt = self.drop_salt.data_ptr() if (self.drop_salt is not None and self.drop_p > 0) else None
-
-
-class Rec:
-    """one conv (+BN) layer: what forward produced and what backward needs"""
-
-    def __init__(self, **kw):
-        self.grad_same = None  # (tensor, ld, coff): grad wrt the activated output, full resolution
-        self.grad_pool = None  # (tensor, ld, coff): grad wrt the pooled activated output
-        self.__dict__.update(kw)
-
-
 def set_reserved_cus(n):
     """abc_set_reserved_cus for Python callers: leave n of the 256 CUs out of the persistent convolution grids (PROCESS-wide).  The plans
     of this process bake the value into grid sizes and BatchNorm partial-row buffers, so it can only change while no plan is alive:
@@ -134,7 +85,7 @@ def set_reserved_cus(n):
     return n
 
 
-class Engine:
+class Engine(HeadsPlan):
     # every plan alive in this process (weak references): the reserved-CU count is a PROCESS-wide setting of the library that plans bake
     # into their grids and buffer sizes, so it may only change while no plan exists (set_reserved_cus below)
     _live = weakref.WeakSet()
@@ -462,18 +413,6 @@ class Engine:
             return
         self._emit(ops, self.lib.abc_conv_fwd_batch, (arr, n), what, meta=meta)
 
-    def emit_heads_batch(self, ops, items, which, what):
-        """the heads' 1x1 convolutions collected by emit_conv(collect=...) as ONE launch (abc_heads_batch) when every one of
-        them is served by the dedicated heads kernel (which = 0 forward / 1 data gradient), else one launch each"""
-        want = 3 if which == 0 else 4
-        ok = 1 <= len(items) <= 8 and all(self.lib.abc_conv_variant(C.byref(d)) == want for d, _w, _m in items) and self.batched_heads
-        if not ok:
-            for d, w, m in items:
-                self._emit(ops, self.lib.abc_conv_fwd, (d,), w, meta=m)
-            return
-        arr, meta = self._batch([d for d, _w, _m in items], [m for _d, _w, m in items], "heads_%s_batch" % ("fwd" if which == 0 else "dgrad"))
-        self._emit(ops, self.lib.abc_heads_batch, (arr, len(items), which), what, meta=meta)
-
     def _wgrad_desc(self, p: Src, q: Src, Ca, Cb, taps, stride, cp_off=None, cq_off=None, dual=None):
         """the descriptor of a weight gradient and the library's geometry for it: (desc, (ca_pad, cb_pad), (a-tile, b-tile), default
         K-split, meta without its bytes); None when `dual` (emit_wgrad) is asked for and the library does not serve the descriptor so"""
@@ -571,30 +510,6 @@ class Engine:
                 else:
                     self._emit(ops, self.lib.abc_wgrad_reduce, (rd,), w, writes=wr, meta=m)
         return "rowsum" if fused_rowsum else True
-
-    def emit_wgrad_heads_batch(self, ops, items, what):
-        """the heads' 1x1 weight gradients collected by emit_wgrad(collect=...) as ONE launch (abc_wgrad_heads_batch) when the
-        heads kernel serves every one of them ((0, 0) tile), else one launch each; their slab reductions follow"""
-        def tile(d):
-            at_, bt_ = L.i32(), L.i32()
-            L.check(self.lib.abc_wgrad_tile(C.byref(d), C.byref(at_), C.byref(bt_)), "wgrad_tile")
-            return at_.value, bt_.value
-        ok = 1 <= len(items) <= 8 and all(tile(d) == (0, 0) for d, _w, _m, _p in items) and self.batched_heads
-        if ok:
-            arr, meta = self._batch([d for d, _w, _m, _p in items], [m for _d, _w, m, _p in items], "heads_wgrad_batch")
-            self._emit(ops, self.lib.abc_wgrad_heads_batch, (arr, len(items)), what, meta=meta)
-        else:
-            for d, w, m, _p in items:
-                self._emit(ops, self.lib.abc_wgrad, (d,), w, meta=m)
-        posts = [p for _d, _w, _m, post in items for p in post]
-        if ok and len(posts) <= 16:
-            # the 8 weight-gradient and 8 bias row-sum reductions as one launch too
-            rarr, meta = self._batch([rd for rd, _w, _wr, _m in posts], [m for _rd, _w, _wr, m in posts], "wgrad_reduce_batch")
-            self._emit(ops, self.lib.abc_wgrad_reduce_batch, (rarr, len(posts)), what + " reduce",
-                       tuple(w for _rd, _w, wr, _m in posts for w in wr), meta)
-        else:
-            for rd, w, wr, m in posts:
-                self._emit(ops, self.lib.abc_wgrad_reduce, (rd,), w, writes=wr, meta=m)
 
     def emit_colsum(self, ops, t, dt, npix, ld, c_off, Cn, chan_scale, bname, what):
         nb = self.lib.abc_colsum_blocks(npix)
@@ -732,14 +647,7 @@ class Engine:
             L.check(lib.abc_fill_f32(amax.data_ptr(), 0.0, 1, stream), "fill")
             L.check(lib.abc_absmax(t.y.data_ptr(), L.BF16, t.y.numel(), amax.data_ptr(), stream), "absmax")
             L.check(lib.abc_fp8_act_scale(amax.data_ptr(), margin, s.data_ptr(), inv_s.data_ptr(), stream), "fp8_act_scale")
-        if self.hfeat_q is not None:      # the eight heads' features: 128 columns each of one tensor, each head its own scale
-            amax, s, inv_s = self.hfeat_q
-            nh = amax.numel()
-            npx = ref.hfeat.numel() // (128 * nh)
-            L.check(lib.abc_fill_f32(amax.data_ptr(), 0.0, nh, stream), "fill")
-            for i in range(nh):
-                L.check(lib.abc_absmax_cols(ref.hfeat.data_ptr(), L.BF16, npx, 128 * nh, 128 * i, 128, amax.data_ptr() + 4 * i, stream), "absmax_cols")
-                L.check(lib.abc_fp8_act_scale(amax.data_ptr() + 4 * i, margin, s.data_ptr() + 4 * i, inv_s.data_ptr() + 4 * i, stream), "fp8_act_scale")
+        self._calibrate_fp8_heads(ref, stream, margin)
         self.fp8_calibrated = True
 
     def double_conv(self, prefix, src, cout, k, dst_b=None):
@@ -937,201 +845,6 @@ class Engine:
         for a in self._colsum_users:
             a[7] = self.cs_ws.data_ptr()
 
-    def _build_heads(self, trunk: Src):
-        h, w = trunk.H, trunk.W
-        nh = len(self.heads)
-        self.h, self.w = h, w
-        # (fp8 graph: the heads' features are e4m3 too when the merged conv1 and the heads' own 1x1 kernel serve them)
-        f8_feat = self.fp8 and trunk.dt == L.FP8 and trunk.C == 128 and nh <= 8 and self.batched_heads and (h * w) % 64 == 0
-        # folded graph: the heads' 1x1 convolutions in the epilogue of the merged conv1 (abc_conv_desc.heads_epi): no feature tensor
-        self.hepi = None
-        if self.fold and self.heads_epilogue and self.batched_heads and self.dt == L.BF16 and trunk.C == 128 and nh <= 8 and \
-                (trunk.dt == L.BF16 or f8_feat):
-            self.hepi = torch.zeros(nh * C.sizeof(L.HeadsEpi), dtype=torch.uint8, device=self.dev)
-            self.keep.append(self.hepi)
-        if self.hepi is not None:
-            # (a placeholder: with heads_epi the convolution does not write its y)
-            self.hfeat = self.new((1, 1, 1, 128 * nh), self._tdt(L.FP8) if f8_feat else None)
-            self.hcoef = None
-        else:
-            self.hfeat, self.hcoef = self.act_buf(h, w, 128 * nh, L.FP8 if f8_feat else None)
-        if f8_feat:
-            self.hfeat_q = (self.new((nh,), torch.float32, 0.0), self.new((nh,), torch.float32, 1.0), self.new((nh,), torch.float32, 1.0))
-        epi_items = []
-        # the list forward() returns: one contiguous NCHW f32 map per head (unet.py:119), written directly
-        self.logits = [self.new((self.B, hc, h, w), torch.float32) for hc in self.heads]
-        self.head_recs, self.head2 = [], []
-        head_convs, head_fins = [], []
-        # batch statistics of the eight heads' BatchNorms side by side (one act_bwd pass over all 8 x 128 channels)
-        self.hmean, self.hinvstd = self.new((128 * nh,), torch.float32), self.new((128 * nh,), torch.float32, 1.0)
-        batch_fin = nh <= 8 and self.batched_heads
-        # the eight conv1's (unet.py:66,116-118: the same 128-channel trunk into 8 x 128 channels) as ONE 128 -> 8 x 128
-        # convolution: the input halo tile is shared by the 8 n-blocks of a pixel tile (same XCD, its L2), and 8 x 768 tiles
-        # fill the 512 workgroup slots 12.0 times instead of 8 x 1.5
-        shared = None
-        if batch_fin and self.dt == L.BF16 and trunk.C == 128:
-            shared = self._heads_conv1_merged(trunk, h, w)
-        fused = self.want_fused_heads and shared is not None and (h * w) % 128 == 0 \
-            and self.B * h * w * 128 * nh < (1 << 30)
-        for i, hc in enumerate(self.heads):
-            p = "out_modules.%d" % i
-            rec, f = self.conv_bn(p + ".conv1", p + ".bn", trunk, 128, 3, (self.hfeat, self.hcoef, h, w, 128 * nh, 128 * i), 0.01,
-                                  stat_out=(self.hmean[128 * i:128 * (i + 1)], self.hinvstd[128 * i:128 * (i + 1)]),
-                                  collect_fin=head_fins if batch_fin else None, shared=shared)
-            rec.is_head = True
-            self.head_recs.append(rec)
-            f.drop_p, f.drop_seed, f.drop_salt = self.drop_p, self.drop_seed, self.drop_salt
-            if not fused:
-                rows_pad = -(-hc // 32) * 32
-                if self.hfeat_q is not None:
-                    f.dt, f.q = L.FP8, tuple(t[i:i + 1] for t in self.hfeat_q)
-                    qmul, deq = self._fp8_weight_scales(p + ".conv2.weight", hc, 128, None, f.q[1], self.new((hc,), torch.float32, 1.0),
-                                                        self.new((hc,), torch.float32, 1.0))
-                    w2 = self.packed(1, 128, rows_pad, cdt=L.FP8)
-                    self.emit_pack(p + ".conv2.weight", w2, 0, hc, 128, 1, rows_pad, 128, row_scale=qmul.data_ptr(), cdt=L.FP8)
-                    if self.hepi is not None:
-                        epi_items.append((w2, self.P(p + ".conv2.bias"), deq, self.logits[i], hc, rows_pad))
-                    else:
-                        self.emit_conv(self.fwd_ops, f, w2, self.P(p + ".conv2.bias"), self.logits[i], L.F32, h, w, hc, 0, hc,
-                                       [(0, 0)], what="fwd %s.conv2" % p, planar_out=True, collect=head_convs, cdt=L.FP8, out_scale=deq)
-                    self.head2.append(Rec(kind="head2", cname=p + ".conv2", src=f, cout=hc, idx=i))
-                    continue
-                w2 = self._pack_weights(p + ".conv2.weight", 0, hc, 128, 1)
-                if self.hepi is not None:
-                    epi_items.append((w2, self.P(p + ".conv2.bias"), None, self.logits[i], hc, rows_pad))
-                else:
-                    self.emit_conv(self.fwd_ops, f, w2, self.P(p + ".conv2.bias"), self.logits[i], L.F32, h, w, hc, 0, hc,
-                                   [(0, 0)], what="fwd %s.conv2" % p, planar_out=True, collect=head_convs)
-            self.head2.append(Rec(kind="head2", cname=p + ".conv2", src=f, cout=hc, idx=i))
-        if head_fins:
-            arr = (L.BnFwdDesc * len(head_fins))(*head_fins)
-            self._emit(self.fwd_ops, self.lib.abc_bn_finalize_fwd_batch, (arr, len(head_fins), 128 * nh if shared is not None else 0),
-                       "bn out_modules.*.bn", meta={"kernel": "bn", "flops": 0, "bytes": 0})
-        if fused:
-            self._heads_fused_setup()
-            return
-        if self.hepi is not None:
-            # the table the merged conv1 reads in its epilogue: static pointers, written once
-            host = (L.HeadsEpi * nh)()
-            for i, (w2, bias_ptr, deq, lg, hc, rows_pad) in enumerate(epi_items):
-                host[i].w2, host[i].bias, host[i].oscale = w2.data_ptr(), bias_ptr, (None if deq is None else deq.data_ptr())
-                host[i].y, host[i].Cout, host[i].Cout_pad = lg.data_ptr(), hc, rows_pad
-            self.hepi.copy_(torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8))
-            self.keep.append(epi_items)
-            return
-        # (the eight conv1 launches above write the eight slices of hfeat; the eight 1x1 convolutions go as one launch)
-        if self.nms_heads and self.heads == arch.TRAIN_HEADS and len(head_convs) == 8:
-            d6, d7 = head_convs[6][0], head_convs[7][0]
-            rho, om = self.new((self.B, 60, h, w), torch.float32), self.new((self.B, 60, h, w), torch.float32)
-            d6.head_aux, d6.head_aux_mode = rho.data_ptr(), 1
-            d7.head_aux, d7.head_aux_mode = om.data_ptr(), 2
-            if self.lib.abc_conv_variant(C.byref(d6)) == 3 and self.lib.abc_conv_variant(C.byref(d7)) == 3:
-                self.nms_rho, self.nms_omega = rho, om
-                head_convs[7][2]["bytes"] += float(self.B * 60 * h * w * 4)
-                head_convs[6][2]["bytes"] += float(self.B * 60 * h * w * 4)
-                if self.decode:
-                    d5 = head_convs[5][0]
-                    idx = self.new((self.B, 60, h, w), torch.uint8)
-                    y5, y6 = d5.y, d6.y
-                    d5.head_aux, d5.head_aux_mode, d5.y, d6.y = idx.data_ptr(), 3, None, None
-                    if self.lib.abc_conv_variant(C.byref(d5)) == 3 and self.lib.abc_conv_variant(C.byref(d6)) == 3:
-                        self.btype_idx = idx
-                        head_convs[5][2]["bytes"] -= float(self.B * 360 * h * w * 4 - self.B * 60 * h * w)
-                        head_convs[6][2]["bytes"] -= float(self.B * 60 * h * w * 4)
-                        # (the bond-type and rho maps are neither written nor read in decode mode: release them -- 1.7 GB at b64 @ 512 x 512)
-                        for dead in (self.logits[5], self.logits[6]):
-                            self.keep[:] = [t for t in self.keep if t is not dead]
-                        self.logits[5] = self.logits[6] = None
-                    else:
-                        d5.head_aux, d5.head_aux_mode, d5.y, d6.y = None, 0, y5, y6
-                        self.decode = False
-            else:
-                d6.head_aux = d7.head_aux = None
-                d6.head_aux_mode = d7.head_aux_mode = 0
-        self.emit_heads_batch(self.fwd_ops, head_convs, 0, "fwd out_modules.*.conv2")
-
-    def _heads_fused_setup(self):
-        """descriptor + buffers of the fused heads pass (abc_heads_fused_*): the conv2 forward leaves the forward plan -- the
-        Trainer runs abc_heads_fused_fwd_bwd + abc_loss_finalize between forward and backward (ops.FusedHeadsLoss, which also
-        binds the targets) -- and the backward plan starts from its outputs (_heads_backward)"""
-        lib, nh, B, h, w = self.lib, len(self.heads), self.B, self.h, self.w
-        Ct = 128 * nh
-        d = L.HeadsFusedDesc()
-        sc, sh, sl = self.hcoef
-        d.feat, d.ld = self.hfeat.data_ptr(), Ct
-        d.scale, d.shift, d.slope = sc.data_ptr(), sh.data_ptr(), sl.data_ptr()
-        d.mean, d.invstd = self.hmean.data_ptr(), self.hinvstd.data_ptr()
-        d.drop_p, d.drop_seed = self.drop_p, self.drop_seed
-        d.drop_salt = self.drop_salt.data_ptr() if self.drop_p > 0 else None
-        d.B, d.h, d.w = B, h, w
-        nchunk = lib.abc_heads_fused_chunks(C.byref(d))
-        self.hf_pack = self.new((lib.abc_heads_fused_pack_bytes() // 4 + 4,), torch.float32)
-        self.hf_dl = self.new((lib.abc_heads_fused_dl_elems(C.byref(d)),), torch.bfloat16)
-        self.hf_g = self.new((B, h, w, Ct))
-        self.hf_bnpart = self.new((nchunk, 2, Ct), torch.float32)
-        self.hf_lossblocks = lib.abc_heads_fused_loss_blocks(C.byref(d))
-        self.hf_losspart = torch.zeros((self.hf_lossblocks, 16), dtype=torch.float64, device=self.dev)
-        self.chan_scale = self.new((sum(self.heads),), torch.float32, 0.0)
-        self.hf_work = self.new((lib.abc_heads_fused_wgrad_floats(C.byref(d)),), torch.float32)
-        d.w2_pack, d.dl, d.g = self.hf_pack.data_ptr(), self.hf_dl.data_ptr(), self.hf_g.data_ptr()
-        d.bn_partial, d.loss_partial = self.hf_bnpart.data_ptr(), self.hf_losspart.data_ptr()
-        d.chan_scale, d.wgrad_work = self.chan_scale.data_ptr(), self.hf_work.data_ptr()
-        if self.drop_p > 0:
-            # the dropout keep bits of the three wide heads' features, from the fused pass to its conv2 weight gradient
-            self.hf_keep = self.new((3 * B * h * w * 16,), torch.uint8, 0)
-            d.keep_mask = self.hf_keep.data_ptr()
-        # which bond-type row tiles carried a target (abc_heads_fused_desc.dl_tiles): the fused pass writes d(logits) only there and
-        # its conv2 weight gradient reads only those; one word per 128-pixel chunk, rewritten by every step
-        self.hf_tiles = self.new((nchunk,), torch.int64, 0)
-        d.dl_tiles = self.hf_tiles.data_ptr()
-        d.no_zero_skip = 0 if self.zero_skip else 1
-        for i in range(nh):
-            p = "out_modules.%d.conv2" % i
-            d.w2[i], d.b2[i], d.logits[i] = self.P(p + ".weight"), self.P(p + ".bias"), self.logits[i].data_ptr()
-            d.dw2[i], d.db2[i], d.chan_off[i] = self.G(p + ".weight"), self.G(p + ".bias"), self.head_off[i]
-        self.hf, self.hf_chunks = d, nchunk
-        self._emit(self.pack_ops, lib.abc_heads_fused_pack, (d,), "pack out_modules.*.conv2", meta={"kernel": "heads_fused_pack", "flops": 0, "bytes": 0})
-
-    def _heads_conv1_merged(self, trunk: Src, h, w):
-        """pack the eight conv1 weights one below the other ([tap][chunk][8 x 128][CK]), gather their biases, emit the one
-        convolution into hfeat; returns (stats partials [nblk][2][8 x 128] or None, nblk)"""
-        nh = len(self.heads)
-        Ct = 128 * nh
-        taps = taps_square(3)
-        wf = self.packed(len(taps), 128, Ct)
-        bias_all = self.new((Ct,), torch.float32)
-        if self.fold:
-            scale_all = self.new((Ct,), torch.float32, 1.0)
-            f8 = trunk.dt == L.FP8      # fp8 graph: e4m3 trunk and weights, bf16 features for the heads' 1x1 convolutions
-            if f8:
-                wf = self.packed(len(taps), 128, Ct, cdt=L.FP8)
-                qmul_all, deq_all = self.new((Ct,), torch.float32, 1.0), self.new((Ct,), torch.float32, 1.0)
-            for i in range(nh):
-                p = "out_modules.%d" % i
-                sl = slice(128 * i, 128 * (i + 1))
-                self._fold_coeffs(p + ".conv1", p + ".bn", 128, scale_all[sl], bias_all[sl])
-                if f8:
-                    self._fp8_weight_scales(p + ".conv1.weight", 128, 128 * 9, scale_all[sl], trunk.q[1], qmul_all[sl], deq_all[sl])
-                    self.emit_pack(p + ".conv1.weight", wf, 0, 128, 128, 3, 128, 128, rows_total=Ct, rows_off=128 * i,
-                                   row_scale=qmul_all[sl].data_ptr(), cdt=L.FP8)
-                else:
-                    self.emit_pack(p + ".conv1.weight", wf, 0, 128, 128, 3, 128, 128, rows_total=Ct, rows_off=128 * i,
-                                   row_scale=scale_all[sl].data_ptr())
-            self.emit_conv(self.fwd_ops, trunk, wf, bias_all.data_ptr(), self.hfeat, L.FP8 if self.hfeat_q is not None else self.dt, h, w, Ct, 0, Ct, taps,
-                           what="fwd out_modules.*.conv1", out_slope=0.01, cdt=L.FP8 if f8 else None, out_scale=deq_all if f8 else None,
-                           out_quant=None if self.hfeat_q is None else self.hfeat_q[2], out_quant_stride=0 if self.hfeat_q is None else 1,
-                           heads_epi=self.hepi)
-            return None, 0
-        for i in range(nh):
-            self.emit_pack("out_modules.%d.conv1.weight" % i, wf, 0, 128, 128, 3, 128, 128, rows_total=Ct, rows_off=128 * i)
-        srcs = (C.c_void_p * nh)(*[self.P("out_modules.%d.conv1.bias" % i) for i in range(nh)])
-        counts = (C.c_int32 * nh)(*([128] * nh))
-        bp = bias_all.data_ptr()
-        self._emit(self.pack_ops, self.lib.abc_concat_f32, (srcs, counts, nh, bp), "gather out_modules.*.conv1.bias",
-                   meta={"kernel": "concat", "flops": 0, "bytes": 0})
-        return self.emit_conv(self.fwd_ops, trunk, wf, bp, self.hfeat, self.dt, h, w, Ct, 0, Ct, taps, stats=self.train,
-                              what="fwd out_modules.*.conv1")
-
     # ------------------------------------------------------------------ backward plan
     def _act_bwd(self, ops, rec, same, pool, g_ptr, ld_g, drop=None):
         """emit the activation backward of rec: g = d(BatchNorm output) at g_ptr (pixel stride ld_g) from the gradients wrt the activated
@@ -1315,175 +1028,6 @@ class Engine:
             else:
                 self._convT_backward(ops, rec)
 
-    def _heads_backward(self, ops):
-        B, h, w = self.B, self.h, self.w
-        nh = len(self.heads)
-        if self.hf is not None:
-            return self._heads_backward_fused(ops)
-        self.dlogits = [self.new((B, hc, h, w), torch.float32) for hc in self.heads]
-        nchan = sum(self.heads)
-        self.chan_scale = self.new((nchan,), torch.float32, 0.0)
-        one = self.new((max(self.heads),), torch.float32, 1.0)
-        zero = self.new((max(self.heads),), torch.float32, 0.0)
-        dfeat = self.new((B, h, w, 128 * nh))
-        # ---- heads' 1x1 convs (weight gradients one by one, the eight data gradients as one launch)
-        head_dgrads, head_wgrads = [], []
-        # K-splits of the heads' batched 1x1 weight gradient: ONE round of ~256 workgroups over all heads, instead of 256 splits
-        # per head = 8 rounds of workgroups that each lived for 4 chunks and wrote a 64 KB slab.  Shared out by the measured
-        # cost of a 128-pixel chunk: ~4 us for the feature tile alone, ~9 us with 128 rows of dL beside it (the rows of the
-        # channel-planar dL are 36 KB apart: 128 concurrent 512-byte streams per workgroup, poor DRAM page locality)
-        units = [-(-(-(-hc // 32)) // 4) for hc in self.heads]
-        cost = [4.0 + 5.2 * (hc / u) / 128.0 for hc, u in zip(self.heads, units)]
-        tot = sum(u * c for u, c in zip(units, cost))
-        head_splits = [max(1, int(256 * c / tot)) for c in cost] if self.batched_heads else [None] * nh
-        for r2 in self.head2:
-            i, hc = r2.idx, r2.cout
-            cs = self.chan_scale[self.head_off[i]:self.head_off[i] + hc]
-            dl = Src(self.dlogits[i], L.F32, h, w, 0, 0, hc, coef=(cs, zero, one), planar=True)
-            got = self.emit_wgrad(ops, dl, r2.src, hc, 128, [(0, 0)], 1, r2.cname + ".weight", "wgrad " + r2.cname,
-                                  rowsum_to=r2.cname + ".bias", collect=head_wgrads, nsplit=head_splits[i])
-            if got != "rowsum":
-                psw = self.new((self.lib.abc_plane_sum_work(hc),), torch.float32)
-                a = (self.dlogits[i].data_ptr(), B, hc, h * w, cs.data_ptr(), psw.data_ptr(), self.G(r2.cname + ".bias"))
-                self._emit(ops, self.lib.abc_plane_sum, a, "dbias " + r2.cname, (r2.cname + ".bias",),
-                           {"kernel": "plane_sum", "flops": 0, "bytes": float(B * hc * h * w * 4)})
-            wd = self._pack_weights(r2.cname + ".weight", 1, hc, 128, 1)
-            self.emit_conv(ops, dl, wd, None, dfeat, self.dt, h, w, 128 * nh, 128 * i, 128, [(0, 0)], what="dgrad " + r2.cname,
-                           collect=head_dgrads)
-        self.emit_wgrad_heads_batch(ops, head_wgrads, "wgrad out_modules.*.conv2")
-        self.emit_heads_batch(ops, head_dgrads, 1, "dgrad out_modules.*.conv2")
-        # ---- heads' BN + conv1: per-head BN backward, ONE data-gradient conv over the 8x128 concatenated channels
-        taps = taps_square(3)
-        dyh = self.new((B, h, w, 128 * nh))
-        merged = None
-        drop = (self.drop_p, self.drop_seed) if self.drop_p > 0 else None
-        # (the one act_bwd pass over 128 x nh channels takes 16 nh bf16 vectors per pixel, which must divide its 256 threads: 1, 2, 4
-        #  or 8 heads; unet.py's default six heads and other counts take the per-head passes below)
-        if self.dt == L.BF16 and self.batched_heads and nh in (1, 2, 4, 8):
-            # BN -> LeakyReLU -> Dropout backward of ALL heads as one pass over the 8 x 128 channels of hfeat / dfeat (their
-            # coefficient and statistics arrays sit side by side), one batched finalisation
-            g = self.new((B, h, w, 128 * nh))
-            sc, sh, sl = self.hcoef
-            wide = Rec(bname="out_modules.*.bn", y=self.hfeat, ld=128 * nh, coff=0, cout=128 * nh, H=h, W=w, scale=sc, shift=sh, slopes=sl,
-                       mean=self.hmean, invstd=self.hinvstd)
-            part, nblk = self._act_bwd(ops, wide, (dfeat, 128 * nh, 0), None, g.data_ptr(), 128 * nh, drop)
-            merged = self._heads_bn_bwd_batch(ops, g, part, nblk)
-        one_wgrad = merged is not None and self._heads_conv1_wgrad_merged(ops, merged, dyh, taps)
-        for i, rec in enumerate(self.head_recs):
-            if one_wgrad:
-                continue
-            if self.dt == L.BF16:
-                # bf16: the weight-gradient kernel applies the BN-backward correction on load and writes dY into this
-                # head's channel slice of dyh (no separate apply pass)
-                gsrc = merged[i] if merged is not None else self._bn_backward(ops, rec, (dfeat, 128 * nh, 128 * i), drop=drop, defer=True)[0]
-                ok = self.emit_wgrad(ops, gsrc, rec.src, 128, 128, taps, 1, rec.cname + ".weight", "wgrad " + rec.cname,
-                                     dual=(rec.y, rec.ld, rec.coff, dyh.data_ptr() + 128 * i * dyh.element_size(), 128 * nh))
-                if not ok:
-                    raise RuntimeError("fused BN-backward apply was refused for " + rec.cname)
-            else:
-                dY = self._bn_backward(ops, rec, (dfeat, 128 * nh, 128 * i), drop=drop, g=(dyh, 128 * nh, 128 * i), in_place=True)
-                self.emit_wgrad(ops, dY, rec.src, 128, 128, taps, 1, rec.cname + ".weight", "wgrad " + rec.cname)
-        self._heads_conv1_dgrad(ops, dyh, taps)
-
-    def _heads_conv1_dgrad(self, ops, dyh, taps):
-        """the tail of both heads-backward plans: the eight heads' conv1 data gradients as ONE 8 x 128 -> 128 convolution over dyh, their dY
-        side by side (unet.py:66,116-118 backward); the trunk's last layer has no reader but the heads, so its act_bwd pass rides in
-        this launch's epilogue where the library serves it"""
-        h, w = self.h, self.w
-        Ct = 128 * len(self.heads)
-        wd_all = self.packed(9, Ct, 128)
-        for i, rec in enumerate(self.head_recs):
-            self.emit_pack(rec.cname + ".weight", wd_all, 1, 128, 128, 3, 128, 128, red_total=Ct, red_off=128 * i)
-        dtrunk = self.new((self.B, h, w, 128))
-        self.dyh, self.dtrunk = dyh, dtrunk      # (handles for the in-situ parity tests)
-        dy_all = Src(dyh, self.dt, h, w, Ct, 0, Ct)
-        p = self.trunk.producer
-        what = "dgrad heads.conv1"
-        p.grad_same = (dtrunk, 128, 0)
-        if (self.actbwd_epilogue and self.train and self.dt == L.BF16 and isinstance(p, Rec) and p.kind == "conv" and self.trunk.t is p.y and
-                not self.trunk.pool and self.trunk.drop_p == 0 and p.coff == 0 and p.ld == p.cout == 128 and (p.H, p.W) == (h, w) and
-                all(getattr(r, "is_head", False) for r in self.recs + list(self.head_recs)
-                    if getattr(r, "src", None) is not None and (r.src.producer is p or r.src.t is p.y))):
-            got = self.emit_conv(ops, dy_all, wd_all, None, dtrunk, self.dt, h, w, 128, 0, 128, taps_mirror(taps),
-                                 what=what + " + act_bwd " + p.bname, actbwd=p)
-            if got is not None:
-                p.fused_g = (dtrunk, got[0], got[1])
-                p.g = dtrunk
-                self.heads_dgrad_is_g = True
-                return
-        self.emit_conv(ops, dy_all, wd_all, None, dtrunk, self.dt, h, w, 128, 0, 128, taps_mirror(taps), what=what)
-
-    def _heads_bn_bwd_batch(self, ops, g, part, nblk, in_scale=None):
-        """the finalisers of all heads' BatchNorm backward as one launch, from partial sums [nblk][2][nh x 128] (in_scale: the flat
-        per-channel loss-scale array, each head's factors from its offset); returns per head the Src of its 128 channels of g with the
-        deferred-apply coefficients (as _bn_backward(defer=True))"""
-        nh = len(self.heads)
-        Ct = 128 * nh
-        # the deferred-apply coefficients are indexed by the ABSOLUTE channel of g (abc_act_src): one array of 8 x 128 per
-        # quantity, every head's finalisation writing its own slice
-        ca_all, cb_all, cc_all = (self.new((Ct,), torch.float32) for _ in range(3))
-        descs, writes, out = [], (), []
-        for i, rec in enumerate(self.head_recs):
-            sl = slice(128 * i, 128 * (i + 1))
-            f, _k, wr = self._bn_bwd_desc(rec, part.data_ptr() + 4 * 128 * i, nblk, (ca_all[sl], cb_all[sl], cc_all[sl]),
-                                          None if in_scale is None else in_scale.data_ptr() + 4 * self.head_off[i])
-            descs.append(f)
-            writes += wr
-            out.append(Src(g, self.dt, rec.H, rec.W, Ct, 128 * i, 128, coef=(ca_all, cc_all, cb_all)))
-        self._emit(ops, self.lib.abc_bn_finalize_bwd_batch, ((L.BnBwdDesc * nh)(*descs), nh, Ct), "bn_bwd out_modules.*.bn", writes,
-                   {"kernel": "bn_bwd", "flops": 0, "bytes": 0})
-        return out
-
-    def _heads_backward_fused(self, ops):
-        """backward plan behind the fused heads pass: conv2's weight / bias gradients from the blocked d(logits), the eight
-        BatchNorm finalisations from the pass's partial sums (times the head's loss factor), then conv1 as in the unfused plan"""
-        B, h, w = self.B, self.h, self.w
-        nh = len(self.heads)
-        Ct = 128 * nh
-        npx = B * h * w
-        writes = tuple(n for i in range(nh) for n in ("out_modules.%d.conv2.weight" % i, "out_modules.%d.conv2.bias" % i))
-        self._emit(ops, self.lib.abc_heads_fused_wgrad, (self.hf,), "wgrad out_modules.*.conv2", writes,
-                   {"kernel": "heads_fused_wgrad", "flops": 2.0 * npx * sum(self.heads) * 128,
-                    "bytes": float(npx * Ct * 2 + self.hf_dl.numel() * 2 + self.hf_work.numel() * 4)})
-        merged = self._heads_bn_bwd_batch(ops, self.hf_g, self.hf_bnpart, self.hf_chunks, in_scale=self.chan_scale)
-        taps = taps_square(3)
-        dyh = self.new((B, h, w, Ct))
-        if not self._heads_conv1_wgrad_merged(ops, merged, dyh, taps):
-            raise RuntimeError("fused heads: the merged conv1 weight gradient was refused")
-        self._heads_conv1_dgrad(ops, dyh, taps)
-
-    def _heads_conv1_wgrad_merged(self, ops, merged, dyh, taps):
-        """The eight heads' conv1 weight gradients (unet.py:66, 8 x [128,128,3,3]) as ONE weight gradient with 8 x 128
-        a-channels: the eight share their Q operand (the trunk activation), their P operands sit side by side in g / hfeat,
-        so one launch of 8 x 2 tiles x 16 splits reads Q once per XCD, writes an eighth of the split-K slabs (16 instead
-        of 128 slabs per head) and runs 72 instead of 9 patches per workgroup.  The slab reduction scatters the eight
-        row blocks to the eight parameters' gradients (one batched launch).  False when the library does not serve the
-        fused BatchNorm-backward load for this descriptor (the caller then emits one launch per head)."""
-        nh = len(self.heads)
-        Ct = 128 * nh
-        q = self.head_recs[0].src
-        g0 = merged[0]
-        p = Src(g0.t, self.dt, g0.H, g0.W, Ct, 0, Ct, coef=g0.coef)
-        got = self._wgrad_desc(p, q, Ct, 128, taps, 1, dual=(self.hfeat, Ct, 0, dyh.data_ptr(), Ct))
-        if got is None:
-            return False
-        d, (ca_pad, cb_pad), _tile, nsplit, meta = got      # (the default K-split: emit_wgrad's per-tile overrides are not for this launch)
-        d.nsplit = nsplit
-        need = nsplit * len(taps) * ca_pad * cb_pad
-        slabs = self.new((need,), torch.float32)
-        d.partial = slabs.data_ptr()
-        npx = self.B * g0.H * g0.W
-        # g + y_raw read, dY written, Q read once, the slabs written
-        meta["bytes"] = float(3 * npx * Ct * self._esz(self.dt) + npx * 128 * self._esz(q.dt) + need * 4)
-        self._emit(ops, self.lib.abc_wgrad, (d,), "wgrad out_modules.*.conv1", meta=meta)
-        # (this head's 128 rows of every slab)
-        reduces = [self._reduce_desc(slabs.data_ptr() + 4 * 128 * i * cb_pad, nsplit, len(taps), 128, 128, ca_pad, cb_pad, self.G(rec.cname + ".weight"))
-                   for i, rec in enumerate(self.head_recs)]
-        self._emit(ops, self.lib.abc_wgrad_reduce_batch, ((L.WgradReduceDesc * nh)(*reduces), nh), "wgrad out_modules.*.conv1 reduce",
-                   tuple(rec.cname + ".weight" for rec in self.head_recs),
-                   {"kernel": "wgrad_reduce_batch", "flops": 0, "bytes": float(need * 4 + Ct * 128 * len(taps) * 4)})
-        return True
-
     def _convT_backward(self, ops, rec):
         """ConvTranspose2d(k3,s2) backward: bias (column sums of dOut), weight (stride-2 wgrad), data (stride-2 gather)"""
         B = self.B
@@ -1664,11 +1208,10 @@ class Engine:
             rec2, rec1 = blk.rec2, blk.rec1
             # (the BN-backward apply fused into the weight gradient's load, as unet does: neutral in round 1 -- bn_apply -0.27 ms,
             #  dual weight gradients +0.33 ms -- +0.9 % since the weight-gradient kernel's prefetch got cheaper: 1231 -> 1242 img/s)
-            defer2 = True
-            dY2 = self._bn_backward(ops, rec2, defer=defer2, g=(dz, Cc, 0), partials=(part3, nb3), in_place=True)
+            dY2 = self._bn_backward(ops, rec2, defer=True, g=(dz, Cc, 0), partials=(part3, nb3), in_place=True)
             dA1 = self._conv_backward(ops, rec2, dY2)
             rec1.grad_same = (dA1, rec1.cout, 0)
-            dY1 = self._bn_backward(ops, rec1, rec1.grad_same, None, defer=defer2)
+            dY1 = self._bn_backward(ops, rec1, rec1.grad_same, None, defer=True)
             xin = blk.xin
             has_prod = xin.producer is not None
             # (identity residual, unet2.py:72: d(x) = d(conv path) + d(out) -- where the 32 -> 32 kernel serves it the data gradient is

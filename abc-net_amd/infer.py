@@ -193,7 +193,7 @@ class InferenceRunner:
         lg = eng.logits
         self.atom_mask, self.bond_mask = torch.empty_like(lg[0]), torch.empty_like(lg[4])
         self.nms_in_heads = eng.nms_rho is not None
-        self.decode = bool(getattr(eng, "decode", False)) and eng.btype_idx is not None
+        self.decode = eng.decode and eng.btype_idx is not None
         self.btype_idx = eng.btype_idx
         if self.nms_in_heads:
             self.rho_abs, self.omega_mask = eng.nms_rho, eng.nms_omega      # (written by the forward plan itself)

@@ -2,7 +2,7 @@
 
     python profiles/tools/plan_fingerprint.py [--repo TREE] [--only SUBSTRING] [--dump DIR] [--routes FILE] [--conv-routes FILE]
 
-Builds every plan of CONFIGS with Engine(..., device="cpu") and replays pack_ops, fwd_ops and bwd_ops against a proxy of the library that
+Builds every plan of configs(), then of more_configs(), with Engine(..., device="cpu") and replays pack_ops, fwd_ops and bwd_ops against a proxy of the library that
 forwards the plan-time queries and, for a launch (any call whose last argument is the replay's stream), records the function name and
 every argument instead of launching: scalars as they are, ctypes structures and arrays (through byref()._obj too) field by field.  Every
 pointer -- argument or field -- becomes (owner ordinal, byte offset): the owner is the tensor storage that holds the address, numbered in
@@ -55,6 +55,7 @@ class Proxy:
 
     def __init__(self, real):
         self.real, self.rec = real, None
+        self.collect = True                        # (--routes / --conv-routes) False while the plans of more_configs() are built
         self.wgrads, self.reduces = {}, set()      # (--routes) distinct descriptors seen, in order of first appearance
         self.convs, self.batches = {}, {}          # (--conv-routes) the same, and the distinct arrays as tuples of descriptor keys
 
@@ -80,10 +81,10 @@ class Proxy:
         types = L.SYMBOLS[name][1] if name in L.SYMBOLS else None
 
         def call(*a):
-            if args.routes or args.conv_routes:
+            if self.collect and (args.routes or args.conv_routes):
                 for v in a:
                     self.note(v)
-            if args.conv_routes and name in ("abc_conv_batch_ok", "abc_conv_fwd_batch", "abc_heads_batch"):
+            if self.collect and args.conv_routes and name in ("abc_conv_batch_ok", "abc_conv_fwd_batch", "abc_heads_batch"):
                 self.batches.setdefault(tuple(self.note(a[0][i]) for i in range(a[1])), self.real.abc_conv_batch_ok(a[0], a[1]))
             if self.rec is not None and a and a[-1] == STREAM and isinstance(a[-1], int):
                 self.rec.call(name, a[:-1], types)
@@ -310,14 +311,42 @@ def configs():
     return out
 
 
+def more_configs():
+    """the heads' forms the 44 plans of configs() leave out (profiles/r28_heads_plan.md).  Hashed and dumped after them, so the dump
+    indices of the 44 stay; kept out of --routes / --conv-routes, so the two fixtures stay the 44 plans' tables"""
+    small = (2, 64, 64)
+    six = OTHER_HEADS[0][2]
+    out = []
+    for label, kw in ((" fold_bn fp8 nms_heads", dict(fold_bn=True, fp8=True, nms_heads=True)),      # (InferenceRunner(fp8=True)'s default)
+                      (" fold_bn fp8 nms_heads decode", dict(fold_bn=True, fp8=True, nms_heads=True, decode=True)),
+                      (" fold_bn fp8 heads_epilogue", dict(fold_bn=True, fp8=True, heads_epilogue=True)),
+                      (" fold_bn batched_heads=False", dict(fold_bn=True, batched_heads=False))):
+        out.append(("unet bf16 eval 2x64x64" + label, "unet", 1, HEADS, small, "bf16", False, kw))
+    # (six heads: the NMS second outputs must not be granted)
+    out.append(("unet heads %s bf16 eval 2x64x64 fold_bn nms_heads" % six, "unet", 1, six, small, "bf16", False, dict(fold_bn=True, nms_heads=True)))
+    # (an image of 2x40x24 does not build -- five poolings need 32 x 32; ragged head maps instead: 160 x 96 gives the 40 x 24 map of
+    #  tests/test_gpu_fp8.py, ragged tiles; 72 x 88 gives 18 x 22, (h * w) % 64 != 0: the e4m3 features fall away)
+    for shape in ((2, 160, 96), (1, 72, 88)):
+        for label, kw in ((" fold_bn heads_epilogue", dict(fold_bn=True, heads_epilogue=True)), (" fold_bn fp8", dict(fold_bn=True, fp8=True)),
+                          (" fold_bn fp8 heads_epilogue", dict(fold_bn=True, fp8=True, heads_epilogue=True))):
+            out.append(("unet bf16 eval %dx%dx%d" % shape + label, "unet", 1, HEADS, shape, "bf16", False, kw))
+    # (72 x 88: (h * w) % 128 != 0 too, the fused heads pass is asked for and falls back)
+    out.append(("unet bf16 train 1x72x88 fused_heads", "unet", 1, HEADS, (1, 72, 88), "bf16", True, dict(fused_heads=True)))
+    out.append(("unet bf16 train 2x64x64 fused_heads=False", "unet", 1, HEADS, small, "bf16", True, dict(fused_heads=False)))
+    out.append(("unet bf16 train 2x64x64 fused_heads zero_skip=False", "unet", 1, HEADS, small, "bf16", True, dict(fused_heads=True, zero_skip=False)))
+    return out
+
+
 def main():
     proxy = Proxy(L.load())
     L._lib = proxy
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)
-    for i, (name, variant, cin, heads, (B, H, W), dtype, train, kw) in enumerate(configs()):
+    first = configs()
+    for i, (name, variant, cin, heads, (B, H, W), dtype, train, kw) in enumerate(first + more_configs()):
         if args.only not in name:
             continue
+        proxy.collect = i < len(first)
         torch.manual_seed(1234)
         m = (UNet if variant == "unet" else UNet2)(cin, heads, dtype=dtype)
         m._flat_grad = torch.zeros_like(m._flat.data)
