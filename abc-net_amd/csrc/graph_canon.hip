@@ -38,6 +38,7 @@
 #include "mol_rows.hpp"
 #include "graph_ids.hpp"
 #include "graph_refine.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -54,154 +55,204 @@ static_assert(MAX_ATOMS == 2 * GT, "two atoms per thread: the record scan");
 typedef unsigned short u16;
 
 // <STEREO> abc_canonical_order_stereo: the stereo word of abc_canon_stereo_desc as a third key of the leaves (every line of it is
-// compiled out of the plain instantiation, which keeps its instructions)
+// compiled out of the plain instantiation)
 template <bool STEREO> struct CanonDescOf { typedef abc_canon_desc type; };
 template <> struct CanonDescOf<true> { typedef abc_canon_stereo_desc type; };
 
+// What a thread holds of its image in registers: the side that was given (mol_rows.hpp), the graph built from it, the thread's own row
+struct Image {
+    int tid;
+    bool mol, empty;
+    int na, nt, nrows, nlisted;      // molecule atoms; record atoms; bond rows of the side; entries of the implicit-H list
+    int n, nvalid;                   // atoms of the graph, its valid rows
+    const int *pa, *pb, *ph, *ra, *rb, *elements;
+    BondRow own;                     // row `tid`, kept through every round (a record row's ends are numbers in T)
+};
+
+// The state of the search, uniform over the workgroup but `shared`: budgets, where the search stands, the best leaf's scalars, counters
+enum Mode { REFINE, CHILD, BACK, STOP };
+struct Search {
+    int max_tries, max_rounds;
+    Mode mode;
+    int level, target, less_from;    // target: the level BACK returns to; less_from: the level from which the path is strictly better
+    int prev;                        // the class count the level's first round has to beat
+    u64 r, best_h, shared;           // the round number of the path; h of the best leaf; refine_classes' least shared id of this thread
+    int zeros;
+    bool have_best;
+    int best_levels, status;
+    int leaves, tries, rounds, levels_max, pruned_trace, pruned_orbit, autos, improved;
+    int s_unequal, s_improved, s_autos;      // <STEREO> the stereo_search row
+};
+
+// The LDS of the two instantiations apart: the records side needs remap and the scan's scratch and is refused with <STEREO> (so the
+// plain kernel holds neither word nor element, the stereo kernel no remap: what the separate arrays were sized to before)
+struct RecordSide {
+    int remap[MAX_ATOMS];            // record atom -> its number in T, -1 outside T
+    unsigned wt[NW + 1];
+};
+// <STEREO> 2.5 KB: the word of the leaf and of the best leaf, by position, and per atom its checked centre code and the lower-index end
+// of the marked double bond it is an end of
+struct StereoSide {
+    unsigned char sword[MAX_ATOMS], bword[MAX_ATOMS];
+    signed char scode[MAX_ATOMS];
+    short dsrc[MAX_ATOMS];
+};
+
 // 71 KB of LDS: the ids (current, best, id_0), the round's sums, the class table with the atom of every slot, the traces of the current
-// path and of the best leaf, the stack, 9 orbit tables; <STEREO> 2.5 KB more: the word of the leaf and of the best leaf, by position, and
-// per atom its checked centre code and the lower-index end of the marked double bond it is an end of
+// path and of the best leaf, the stack, 9 orbit tables -- and the steps of the search on them.  Every step is inlined into the kernel;
+// each says which barriers it places
 template <bool STEREO>
-__global__ __launch_bounds__(GT) void graph_canon_kernel(const typename CanonDescOf<STEREO>::type d) {
-    __shared__ unsigned char sword[STEREO ? MAX_ATOMS : 1], bword[STEREO ? MAX_ATOMS : 1];
-    __shared__ signed char scode[STEREO ? MAX_ATOMS : 1];
-    __shared__ short dsrc[STEREO ? MAX_ATOMS : 1];
-    __shared__ u64 cur[MAX_ATOMS], acc[MAX_ATOMS], init[MAX_ATOMS], best_ids[MAX_ATOMS];
-    __shared__ u64 table[SLOTS];
-    __shared__ u64 cur_sum[MAX_ATOMS], best_sum[MAX_ATOMS], cell[MAX_ATOMS];       // per level: the trace's sum; the id of the cell
-    __shared__ u16 cur_k[MAX_ATOMS], cur_c[MAX_ATOMS], best_k[MAX_ATOMS], best_c[MAX_ATOMS];      // per level: rounds, classes
-    __shared__ u16 choice[MAX_ATOMS], best_choice[MAX_ATOMS], nxt[MAX_ATOMS], cell_max[MAX_ATOMS];    // the stack
-    __shared__ u16 tidx[SLOTS];          // the best leaf's atom of every table slot
-    __shared__ int remap[MAX_ATOMS];     // record atom -> its number in T, -1 outside T
-    __shared__ u16 orig[MAX_ATOMS];      // atom of the graph -> its row
-    __shared__ u16 rk[MAX_ATOMS], brank[MAX_ATOMS], gam[MAX_ATOMS];      // ranks of the leaf, of the best leaf; the map onto the best
-    __shared__ unsigned char tag[MAX_ATOMS];
-    __shared__ int orbit[ORBITS][MAX_ATOMS];
-    __shared__ unsigned wt[NW + 1];
-    __shared__ int wi[NW];
-    __shared__ u64 wu[NW];
-    __shared__ int cnt[1], zero_at;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const bool mol = STEREO || d.mol_counts != nullptr;      // (the launcher refuses the records side with <STEREO>)
-    const int cap = mol ? d.cap_atoms : d.max_atoms, cap_bonds = mol ? d.cap_mol_bonds : d.max_bonds;
-    int* const order = d.order + (size_t)b * cap;
-    int* const cert = d.cert_out != nullptr ? d.cert_out + (size_t)b * (2 + cap + 3 * (size_t)cap_bonds) : nullptr;
-    const bool want_rows = mol && d.out_counts != nullptr;
-    const int max_tries = d.max_tries > 0 ? d.max_tries : ABC_CANON_DEFAULT_TRIES;
-    const int max_rounds = d.max_rounds > 0 ? d.max_rounds : ABC_CANON_DEFAULT_ROUNDS;
+struct Canon : std::conditional_t<STEREO, StereoSide, RecordSide> {
+    u64 cur[MAX_ATOMS], acc[MAX_ATOMS], init[MAX_ATOMS], best_ids[MAX_ATOMS];
+    u64 table[SLOTS];
+    u64 cur_sum[MAX_ATOMS], best_sum[MAX_ATOMS], cell[MAX_ATOMS];       // per level: the trace's sum; the id of the cell
+    u64 wu[NW];
+    int orbit[ORBITS][MAX_ATOMS];
+    int wi[NW];
+    int cnt[1], zero_at;
+    u16 cur_k[MAX_ATOMS], cur_c[MAX_ATOMS], best_k[MAX_ATOMS], best_c[MAX_ATOMS];      // per level: rounds, classes
+    u16 choice[MAX_ATOMS], best_choice[MAX_ATOMS], nxt[MAX_ATOMS], cell_max[MAX_ATOMS];    // the stack
+    u16 tidx[SLOTS];                 // the best leaf's atom of every table slot
+    u16 orig[MAX_ATOMS];             // atom of the graph -> its row
+    u16 rk[MAX_ATOMS], brank[MAX_ATOMS], gam[MAX_ATOMS];      // ranks of the leaf, of the best leaf; the map onto the best
+    unsigned char tag[MAX_ATOMS];
 
-    // ---- the image (mol_rows.hpp), of the side that was given
-    int status = 0, na = 0, nrows = 0, nt = 0, nlisted = 0;      // na: molecule atoms; nt: record atoms; nrows: bond rows of the side
-    const int *pa = nullptr, *pb = nullptr, *ph = nullptr, *ra = nullptr, *rb = nullptr;
-    if (mol) {
-        const MolImage im = mol_image(d, b);
-        status = im.status, na = im.na, nrows = im.nb, nlisted = im.nh, pa = im.pa, pb = im.pb, ph = im.ph;
-    } else {
-        const RecImage im = rec_image(d, b);
-        nt = im.nt, nrows = im.m, ra = im.ra, rb = im.rb;
+    // ---- class, charge of an atom of the graph; a bond row of the graph; the reductions
+    __device__ __forceinline__ int cls_of(const Image& im, int a) const {
+        return atom_class(im.mol ? im.pa[a * ATOM_W + 2] : im.ra[orig[a] * REC_ATOM_W + 2]);
     }
-    const bool empty = (status & ABC_CANON_EMPTY) != 0;
-    static_assert((int)ABC_CANON_EMPTY == (int)ABC_MOL_EMPTY && (int)ABC_CANON_TRUNCATED == (int)ABC_MOL_TRUNCATED, "the two bits are copied");
-
-    // row `tid`, kept through every round (a record row's ends become numbers in T below)
-    BondRow own = {false, 0, 0, 0};
-    if (tid < nrows) own = mol ? mol_row(pb, tid, na) : rec_row(rb, tid, nt);
-
-    // ---- (A) degrees (in acc), the atoms of the graph, tags, id_0 (graph_refine.hpp, for the side that was given)
-    if (tid == 0) cnt[0] = 0, zero_at = -1;
-    for (int a = tid; a < MAX_ATOMS; a += GT) acc[a] = 0, tag[a] = 0;
-    __syncthreads();
-    {
-        const int valid = mol ? refine_degrees_mol(tid, pb, nrows, na, own, acc) : refine_degrees_rec(tid, rb, nrows, nt, own, acc);
-        if (valid) atomicAdd(cnt, valid);
-        for (int k = tid; k < nlisted; k += GT) {
-            const int e = ph[k];
-            if (e >= 1 && e <= na) tag[e - 1] = 1;
-        }
+    __device__ __forceinline__ int chg_of(const Image& im, int a) const { return im.mol ? im.pa[a * ATOM_W + 3] : im.ra[orig[a] * REC_ATOM_W + 3]; }
+    __device__ __forceinline__ BondRow row(const Image& im, int q) const {
+        if constexpr (!STEREO)
+            if (!im.mol) return rec_row(im.rb, q, im.nt, this->remap);
+        return mol_row(im.pb, q, im.na);
     }
-    __syncthreads();
-    const int nvalid = cnt[0];
-    int n = na;
-    if (mol) {
-        refine_id0_mol(tid, pa, na, acc, init);
-        for (int a = tid; a < na; a += GT) {      // (by the thread that wrote id_0 and read the degree: acc becomes the round's sums)
-            if (tag[a]) init[a] = mix(init[a] + TAG_K);
-            orig[a] = (u16)a;
-            acc[a] = 0;
-        }
-    } else {
-        n = refine_number_rec(tid, ra, nt, acc, wt, remap, orig, init);
-    }
-    __syncthreads();                     // (remap, orig and id_0 are written)
-    if (!mol) renumber(own, remap);
-    for (int a = tid; a < n; a += GT) cur[a] = init[a];
-    __syncthreads();
-
-    // class, charge of an atom of the graph; a bond row of the graph
-    auto cls_of = [&](int a) __attribute__((always_inline)) { return atom_class(mol ? pa[a * ATOM_W + 2] : ra[orig[a] * REC_ATOM_W + 2]); };
-    auto chg_of = [&](int a) __attribute__((always_inline)) { return mol ? pa[a * ATOM_W + 3] : ra[orig[a] * REC_ATOM_W + 3]; };
-    auto row = [&](int q) __attribute__((always_inline)) { return mol ? mol_row(pb, q, na) : rec_row(rb, q, nt, remap); };
-    auto round = [&](u64 r) __attribute__((always_inline)) {
-        if (mol) refine_add_mol(tid, cur, acc, pb, nrows, na, own);
-        else refine_add_rec(tid, cur, acc, rb, nrows, nt, remap, own);
+    __device__ __forceinline__ int sum_int(int v) { return block_reduce(v, wi, [](int u, int w) { return u + w; }); }
+    __device__ __forceinline__ int min_int(int v) { return block_reduce(v, wi, [](int u, int w) { return min(u, w); }); }
+    // one round on cur: the sums, a barrier, the new ids (acc zero again), a barrier
+    __device__ __forceinline__ void round(const Image& im, u64 r) {
+        if (im.mol) refine_add_mol(im.tid, cur, acc, im.pb, im.nrows, im.na, im.own);
+        else if constexpr (!STEREO) refine_add_rec(im.tid, cur, acc, im.rb, im.nrows, im.nt, this->remap, im.own);
         __syncthreads();
-        refine_finish(tid, cur, acc, n, r);
+        refine_finish(im.tid, cur, acc, im.n, r);
         __syncthreads();
-    };
-    u64 shared = ~0ull;
-    int zeros = 0;
-    auto classes = [&]() __attribute__((always_inline)) { return refine_classes<SLOTS>(tid, cur, n, table, wi, shared, zeros); };
-    auto sum_int = [&](int v) __attribute__((always_inline)) { return block_reduce(v, wi, [](int u, int w) { return u + w; }); };
-    auto min_int = [&](int v) __attribute__((always_inline)) { return block_reduce(v, wi, [](int u, int w) { return min(u, w); }); };
-    // h of the relabelled graph under the ranks `rank` (uniform)
-    auto leaf_hash = [&](const u16* rank) __attribute__((always_inline)) {
-        u64 h = 0;
-        for (int a = tid; a < n; a += GT)
-            h += mix(mix(mix(mix((u64)rank[a] + 1) + (u64)(cls_of(a) + 1)) + (u64)(long long)chg_of(a)) + (u64)tag[a]);
-        for (int q = tid; q < nrows; q += GT) {
-            const BondRow e = row(q);
-            if (!e.v) continue;
-            const u64 lo = min((int)rank[e.i], (int)rank[e.j]), hi = max((int)rank[e.i], (int)rank[e.j]);
-            h += mix(mix(((lo << 32) | hi) + BOND_K) + (u64)e.o);
-        }
-        return block_reduce(h, wu, [](u64 u, u64 v) { return u + v; });
-    };
+    }
+    __device__ __forceinline__ int classes(const Image& im, Search& q) { return refine_classes<SLOTS>(im.tid, cur, im.n, table, wi, q.shared, q.zeros); }
 
-    // <STEREO> the elements of the image, checked once: an index that is no atom of the image makes its element none
-    const int* elements = nullptr;
-    int s_unequal = 0, s_improved = 0, s_autos = 0;
-    if constexpr (STEREO) {
-        elements = d.elements + (size_t)b * d.cap_atoms * STEREO_W;
+    // ---- the image (mol_rows.hpp) of the side that was given, and stage (A): degrees (in acc), the atoms of the graph, tags, id_0
+    // (graph_refine.hpp), cur = id_0.  Returns the status bits of the image.  Barriers: behind the clearing, behind the degrees and
+    // tags, behind remap / orig / id_0, behind cur
+    template <class Desc>
+    __device__ __forceinline__ int setup(const Desc& d, int b, Image& im) {
+        const int tid = im.tid = threadIdx.x;
+        const bool mol = im.mol = STEREO || d.mol_counts != nullptr;      // (the launcher refuses the records side with <STEREO>)
+        int status = 0;
+        im.na = im.nt = im.nrows = im.nlisted = 0;
+        im.pa = im.pb = im.ph = im.ra = im.rb = im.elements = nullptr;
+        if (mol) {
+            const MolImage m = mol_image(d, b);
+            status = m.status, im.na = m.na, im.nrows = m.nb, im.nlisted = m.nh, im.pa = m.pa, im.pb = m.pb, im.ph = m.ph;
+        } else {
+            const RecImage m = rec_image(d, b);
+            im.nt = m.nt, im.nrows = m.m, im.ra = m.ra, im.rb = m.rb;
+        }
+        im.empty = (status & ABC_CANON_EMPTY) != 0;
+        static_assert((int)ABC_CANON_EMPTY == (int)ABC_MOL_EMPTY && (int)ABC_CANON_TRUNCATED == (int)ABC_MOL_TRUNCATED, "the two bits are copied");
+        im.own = {false, 0, 0, 0};
+        if (tid < im.nrows) im.own = mol ? mol_row(im.pb, tid, im.na) : rec_row(im.rb, tid, im.nt);
+
+        if (tid == 0) cnt[0] = 0, zero_at = -1;
+        for (int a = tid; a < MAX_ATOMS; a += GT) acc[a] = 0, tag[a] = 0;
+        __syncthreads();
+        {
+            const int valid = mol ? refine_degrees_mol(tid, im.pb, im.nrows, im.na, im.own, acc) : refine_degrees_rec(tid, im.rb, im.nrows, im.nt, im.own, acc);
+            if (valid) atomicAdd(cnt, valid);
+            for (int k = tid; k < im.nlisted; k += GT) {
+                const int e = im.ph[k];
+                if (e >= 1 && e <= im.na) tag[e - 1] = 1;
+            }
+        }
+        __syncthreads();
+        im.nvalid = cnt[0];
+        im.n = im.na;
+        if (mol) {
+            refine_id0_mol(tid, im.pa, im.na, acc, init);
+            for (int a = tid; a < im.na; a += GT) {      // (by the thread that wrote id_0 and read the degree: acc becomes the round's sums)
+                if (tag[a]) init[a] = mix(init[a] + TAG_K);
+                orig[a] = (u16)a;
+                acc[a] = 0;
+            }
+        } else if constexpr (!STEREO) {
+            im.n = refine_number_rec(tid, im.ra, im.nt, acc, this->wt, this->remap, orig, init);
+        }
+        __syncthreads();                     // (remap, orig and id_0 are written)
+        if constexpr (!STEREO)
+            if (!mol) renumber(im.own, this->remap);
+        for (int a = tid; a < im.n; a += GT) cur[a] = init[a];
+        __syncthreads();
+        return status;
+    }
+    // <STEREO> the elements of the image, checked once: an index that is no atom of the image makes its element none.  Barriers: behind
+    // scode and the clearing of dsrc, behind dsrc
+    template <class Desc>
+    __device__ __forceinline__ void check_elements(const Desc& d, int b, Image& im) {
+        const int tid = im.tid, n = im.n;
+        const int* elements = im.elements = d.elements + (size_t)b * d.cap_atoms * STEREO_W;
         auto atom = [&](int v, int least) __attribute__((always_inline)) { return v >= least && v < n; };
         for (int a = tid; a < n; a += GT) {
             const int* el = elements + a * STEREO_W;
             const int c = el[0];
-            scode[a] = (signed char)((c == 1 || c == -1) && atom(el[1], 0) && atom(el[2], 0) && atom(el[3], 0) && atom(el[4], -1) ? c : 0);
-            dsrc[a] = -1;
+            this->scode[a] = (signed char)((c == 1 || c == -1) && atom(el[1], 0) && atom(el[2], 0) && atom(el[3], 0) && atom(el[4], -1) ? c : 0);
+            this->dsrc[a] = -1;
         }
         __syncthreads();
         for (int a = tid; a < n; a += GT) {
             const int* el = elements + a * STEREO_W;
             const int c = el[5], other = el[7];
             if ((c == 1 || c == -1) && atom(other, 0) && other != a && atom(el[8], 0) && atom(el[9], -1) && atom(el[10], 0) && atom(el[11], -1))
-                dsrc[a] = dsrc[other] = (short)a;
+                this->dsrc[a] = this->dsrc[other] = (short)a;
         }
         __syncthreads();
     }
-    // the stereo word of the leaf whose ranks are in rk, by position (every position is written: the ranks are a permutation)
-    auto leaf_word = [&]() __attribute__((always_inline)) {
-        for (int a = tid; a < n; a += GT) {
+
+    // ---- (b) the leaf.  rank = the number of smaller ids, into rk.  Barrier: behind the ranks (and tid 0's trace of this level)
+    __device__ __forceinline__ void leaf_ranks(const Image& im) {
+        for (int a = im.tid; a < im.n; a += GT) {
+            const u64 e = cur[a];
+            int below = 0;
+            for (int x = 0; x < im.n; ++x) below += cur[x] < e;
+            rk[a] = (u16)below;
+        }
+        __syncthreads();
+    }
+    // h of the relabelled graph under the ranks `rank` (uniform).  Barriers: the reduction's two
+    __device__ __forceinline__ u64 leaf_hash(const Image& im, const u16* rank) {
+        u64 h = 0;
+        for (int a = im.tid; a < im.n; a += GT)
+            h += mix(mix(mix(mix((u64)rank[a] + 1) + (u64)(cls_of(im, a) + 1)) + (u64)(long long)chg_of(im, a)) + (u64)tag[a]);
+        for (int q = im.tid; q < im.nrows; q += GT) {
+            const BondRow e = row(im, q);
+            if (!e.v) continue;
+            const u64 lo = min((int)rank[e.i], (int)rank[e.j]), hi = max((int)rank[e.i], (int)rank[e.j]);
+            h += mix(mix(((lo << 32) | hi) + BOND_K) + (u64)e.o);
+        }
+        return block_reduce(h, wu, [](u64 u, u64 v) { return u + v; });
+    }
+    // <STEREO> the stereo word of the leaf whose ranks are in rk, by position (every position is written: the ranks are a
+    // permutation).  Barrier: behind the word
+    __device__ __forceinline__ void leaf_word(const Image& im) {
+        for (int a = im.tid; a < im.n; a += GT) {
             int byte = 0;
-            const int sc = scode[a], a0 = dsrc[a];
+            const int sc = this->scode[a], a0 = this->dsrc[a];
             if (sc != 0) {
-                const int* el = elements + a * STEREO_W;
+                const int* el = im.elements + a * STEREO_W;
                 const int last = el[4];
                 const int r0 = rk[el[1]], r1 = rk[el[2]], r2 = rk[el[3]], r3 = last >= 0 ? (int)rk[last] : MAX_ATOMS;      // (the hydrogen stays last)
                 const int swaps = (r0 > r1) + (r0 > r2) + (r0 > r3) + (r1 > r2) + (r1 > r3) + (r2 > r3);
                 byte = ((swaps & 1) ? -sc : sc) > 0 ? 1 : 2;
             }
             if (a0 >= 0) {
-                const int* el = elements + a0 * STEREO_W;
+                const int* el = im.elements + a0 * STEREO_W;
                 const int other = a == a0 ? el[7] : a0;
                 if (rk[a] < rk[other]) {      // the lower-rank end bears the bond's part
                     int v = el[5];
@@ -210,320 +261,316 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const typename CanonDes
                     byte |= (v > 0 ? 1 : 2) << 2;
                 }
             }
-            sword[rk[a]] = (unsigned char)byte;
+            this->sword[rk[a]] = (unsigned char)byte;
         }
         __syncthreads();
-    };
-
-    int leaves = 0, tries = 0, rounds = 0, levels_max = 0, pruned_trace = 0, pruned_orbit = 0, autos = 0, improved = 0;
-    bool have_best = false;
-    int best_levels = 0;
-    if (!empty && n > 0) {
-        enum { REFINE, CHILD, BACK };
-        int mode = REFINE, target = -1, level = 0, less_from = NONE;
-        u64 r = 0, best_h = 0;
-        int prev = classes();
-        while (true) {
-            if (mode == REFINE) {
-                int k = 0, c = 0;
-                bool out = false;
-                while (true) {
-                    if (rounds >= max_rounds) { out = true; break; }
-                    ++rounds, ++r, ++k;
-                    round(r);
-                    c = classes();
-                    if (c <= prev || k >= n) break;
-                    prev = c;
-                }
-                if (out) { status |= ABC_CANON_UNDECIDED; break; }
-                const u64 s = refine_multiset_sum(tid, cur, n, wu);
-                if (tid == 0) cur_k[level] = (u16)k, cur_c[level] = (u16)c, cur_sum[level] = s;
-                levels_max = max(levels_max, level);
-                mode = BACK, target = level - 1;
-                if (have_best && less_from == NONE) {
-                    const int bk = best_k[level], bc = best_c[level];
-                    const u64 bs = best_sum[level];
-                    const int cmp = k != bk ? (k < bk ? -1 : 1) : (c != bc ? (c < bc ? -1 : 1) : (s != bs ? (s < bs ? -1 : 1) : 0));
-                    if (cmp > 0) {
-                        ++pruned_trace;
-                        continue;
-                    }
-                    if (cmp < 0) less_from = level;
-                }
-                if (c == n) {
-                    // ---- (b) the leaf
-                    ++leaves;
-                    for (int a = tid; a < n; a += GT) {
-                        const u64 e = cur[a];
-                        int below = 0;
-                        for (int x = 0; x < n; ++x) below += cur[x] < e;
-                        rk[a] = (u16)below;
-                    }
-                    __syncthreads();     // (the ranks and tid 0's trace of this level are written)
-                    const u64 h = leaf_hash(rk);
-                    if constexpr (STEREO) leaf_word();
-                    if (!have_best || less_from != NONE || h < best_h) {
-                        improved += have_best;
-                        for (int a = tid; a < n; a += GT) best_ids[a] = cur[a], brank[a] = rk[a];
-                        if constexpr (STEREO)
-                            for (int a = tid; a < n; a += GT) bword[a] = sword[a];
-                        for (int l = tid; l <= level; l += GT) {
-                            best_k[l] = cur_k[l], best_c[l] = cur_c[l], best_sum[l] = cur_sum[l];
-                            if (l < level) best_choice[l] = choice[l];
-                        }
-                        have_best = true, best_levels = level, best_h = h, less_from = NONE;
-                        __syncthreads();
-                    } else if (h == best_h) {
-                        // the map onto the best leaf by equal id, through the table
-                        for (int k2 = tid; k2 < SLOTS; k2 += GT) table[k2] = 0;
-                        if (tid == 0) zero_at = -1;
-                        __syncthreads();
-                        for (int a = tid; a < n; a += GT) {
-                            const u64 e = best_ids[a];
-                            if (e == 0) {
-                                zero_at = a;
-                                continue;
-                            }
-                            unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
-                            for (int probe = 0; probe < SLOTS; ++probe) {
-                                const u64 old = atomicCAS(&table[slot], 0ull, e);
-                                if (old == 0) {
-                                    tidx[slot] = (u16)a;
-                                    break;
-                                }
-                                if (old == e) break;
-                                slot = (slot + 1) & (SLOTS - 1);
-                            }
-                        }
-                        __syncthreads();
-                        int bad = 0;
-                        for (int a = tid; a < n; a += GT) {
-                            const u64 e = cur[a];
-                            int t = -1;
-                            if (e == 0) {
-                                t = zero_at;
-                            } else {
-                                unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
-                                for (int probe = 0; probe < SLOTS; ++probe) {
-                                    const u64 at = table[slot];
-                                    if (at == e) t = tidx[slot];
-                                    if (at == e || at == 0) break;
-                                    slot = (slot + 1) & (SLOTS - 1);
-                                }
-                            }
-                            const int y = t < 0 || t >= n ? a : t;
-                            gam[a] = (u16)y;
-                            bad += t < 0 || t >= n || cls_of(a) != cls_of(y) || chg_of(a) != chg_of(y) || tag[a] != tag[y];
-                        }
-                        bool ok = sum_int(bad) == 0;      // (gam is written: the reduction synchronises)
-                        if (ok) {
-                            // the multiset of the mapped rows is the multiset of the rows, by counting
-                            int common = 0;
-                            for (int q = tid; q < nrows; q += GT) {
-                                const BondRow e = row(q);
-                                if (!e.v) continue;
-                                const int gi = gam[e.i], gj = gam[e.j], lo = min(gi, gj), hi = max(gi, gj);
-                                int before = 0, there = 0;
-                                for (int q2 = 0; q2 < nrows; ++q2) {
-                                    const BondRow e2 = row(q2);
-                                    if (!e2.v || e2.o != e.o) continue;
-                                    const int gi2 = gam[e2.i], gj2 = gam[e2.j];
-                                    before += q2 < q && min(gi2, gj2) == lo && max(gi2, gj2) == hi;
-                                    there += min(e2.i, e2.j) == lo && max(e2.i, e2.j) == hi;
-                                }
-                                common += before < there;
-                            }
-                            ok = sum_int(common) == nvalid;
-                        }
-                        if (!ok) { status |= ABC_CANON_COLLISION; break; }
-                        if constexpr (STEREO) {
-                            // the third key, compared exactly: the first position at which the words differ
-                            int differs = NONE;
-                            for (int k2 = tid; k2 < n; k2 += GT)
-                                if (sword[k2] != bword[k2]) differs = min(differs, k2);
-                            differs = min_int(differs);
-                            if (differs != NONE) {      // a map that does not keep the stereo: no orbit merge, no jump
-                                ++s_unequal;
-                                const bool less = sword[differs] < bword[differs];
-                                __syncthreads();         // (read before the best leaf's word is replaced)
-                                if (less) {
-                                    ++s_improved, ++improved;
-                                    for (int a = tid; a < n; a += GT) best_ids[a] = cur[a], brank[a] = rk[a], bword[a] = sword[a];
-                                    for (int l = tid; l < level; l += GT) best_choice[l] = choice[l];      // (the traces are equal)
-                                    __syncthreads();
-                                }
-                                continue;
-                            }
-                            ++s_autos;
-                        }
-                        ++autos;
-                        int first = NONE;
-                        for (int l = tid; l < level; l += GT)
-                            if (choice[l] != best_choice[l]) first = min(first, l);
-                        target = min(min_int(first), level - 1);      // the level where the path left the best's
-                        // x ~ gamma(x) in the orbit tables of the levels whose prefix gamma fixes: the greater root is hung under the less
-                        const int upto = min(target, ORBITS - 1);
-                        for (int l = 0; l <= upto; ++l) {
-                            int* p = orbit[l];
-                            for (int a = tid; a < n; a += GT) {
-                                int x = a, y = gam[a];
-                                for (int it = 0; it < n; ++it) {
-                                    for (int w = 0; w < n; ++w) {
-                                        const int up = __hip_atomic_load(&p[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                        if (up == x) break;
-                                        x = up;
-                                    }
-                                    for (int w = 0; w < n; ++w) {
-                                        const int up = __hip_atomic_load(&p[y], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                        if (up == y) break;
-                                        y = up;
-                                    }
-                                    if (x == y) break;
-                                    if (x < y) { const int t = x; x = y; y = t; }
-                                    if (atomicCAS(&p[x], x, y) == x) break;
-                                }
-                            }
-                        }
-                        __syncthreads();
-                        for (int l = 0; l <= upto; ++l) {     // flat again: every atom under its root, the least of its orbit
-                            int* p = orbit[l];
-                            int root[MAX_ATOMS / GT];
-#pragma unroll
-                            for (int u = 0; u < MAX_ATOMS / GT; ++u) {
-                                int x = min(tid + u * GT, MAX_ATOMS - 1);
-                                for (int w = 0; w < n; ++w) {
-                                    const int up = p[x];
-                                    if (up == x) break;
-                                    x = up;
-                                }
-                                root[u] = x;
-                            }
-                            __syncthreads();
-#pragma unroll
-                            for (int u = 0; u < MAX_ATOMS / GT; ++u)
-                                if (tid + u * GT < n) p[tid + u * GT] = root[u];
-                        }
-                        __syncthreads();
-                    }
-                    continue;
-                }
-                if (level + 1 >= n) { status |= ABC_CANON_COLLISION; break; }      // (only colliding hashes get here)
-                // the cell: the least id that two atoms share; its last atom
-                const u64 least = block_reduce(shared, wu, [](u64 u, u64 v) { return min(u, v); });
-                const u64 cellv = zeros > 1 ? 0 : least;
-                int last = -1;
-                for (int a = tid; a < n; a += GT)
-                    if (cur[a] == cellv) last = max(last, a);
-                last = block_reduce(last, wi, [](int u, int w) { return max(u, w); });
-                if (last < 0) { status |= ABC_CANON_COLLISION; break; }
-                if (tid == 0) cell[level] = cellv, cell_max[level] = (u16)last, nxt[level] = 0;
-                if (level < ORBITS)
-                    for (int a = tid; a < MAX_ATOMS; a += GT) orbit[level][a] = a;
-                __syncthreads();
-                mode = CHILD;
-            }
-            if (mode == CHILD) {
-                // ---- (c) the next atom of the cell that is the least of its orbit
-                const u64 cellv = cell[level];
-                const int from = nxt[level];
-                const bool orbits = level < ORBITS;
-                int first = MAX_ATOMS;
-                for (int a = tid; a < n; a += GT)
-                    if (a >= from && cur[a] == cellv && (!orbits || orbit[level][a] == a)) first = min(first, a);
-                const int v = min_int(first);
-                if (orbits) {
-                    int skipped = 0;
-                    for (int a = tid; a < n; a += GT) skipped += a >= from && a < v && cur[a] == cellv;
-                    pruned_orbit += sum_int(skipped);
-                }
-                if (v >= n) {
-                    mode = BACK, target = level - 1;
-                    continue;
-                }
-                if (tries >= max_tries) { status |= ABC_CANON_UNDECIDED; break; }
-                ++tries;
-                prev = cur_c[level] + 1;
-                if (tid == 0) choice[level] = (u16)v, nxt[level] = (u16)(v + 1), cur[v] = indiv(cur[v], level);
-                __syncthreads();
-                ++level;
-                mode = REFINE;
+    }
+    // the leaf becomes the best: ids, ranks, <STEREO> word, the choices of the path and, with `traces`, the traces of the levels 0 ..
+    // level (without: they equal the best's).  Barrier: behind the copies
+    __device__ __forceinline__ void keep_best(const Image& im, int level, bool traces) {
+        for (int a = im.tid; a < im.n; a += GT) {
+            best_ids[a] = cur[a], brank[a] = rk[a];
+            if constexpr (STEREO) this->bword[a] = this->sword[a];
+        }
+        for (int l = im.tid; l <= level; l += GT) {
+            if (traces) best_k[l] = cur_k[l], best_c[l] = cur_c[l], best_sum[l] = cur_sum[l];
+            if (l < level) best_choice[l] = choice[l];
+        }
+        __syncthreads();
+    }
+    // the map onto the best leaf by equal id, through the class table, into gam, VERIFIED: class, charge and tag of every atom, and the
+    // multiset of the mapped rows is the multiset of the rows.  Uniform.  Barriers: behind the clearing of the table, behind the puts,
+    // the two reductions' (the first is behind gam)
+    __device__ __forceinline__ bool map_onto_best(const Image& im) {
+        const int tid = im.tid, n = im.n;
+        for (int k = tid; k < SLOTS; k += GT) table[k] = 0;
+        if (tid == 0) zero_at = -1;
+        __syncthreads();
+        for (int a = tid; a < n; a += GT) {
+            const u64 e = best_ids[a];
+            if (e == 0) {
+                zero_at = a;
                 continue;
             }
-            // ---- (d) back
-            __syncthreads();
-            for (int it = 0; it < n && target >= 0 && nxt[target] > cell_max[target]; ++it) --target;
-            if (target < 0) break;
-            level = target;
-            if (less_from != NONE && less_from > level) less_from = NONE;
-            for (int a = tid; a < n; a += GT) cur[a] = init[a];
-            __syncthreads();
-            r = 0;
-            bool out = false;
-            for (int k = 0; k <= level && !out; ++k) {
-                const int todo = cur_k[k];
-                for (int i = 0; i < todo; ++i) {
-                    if (rounds >= max_rounds) { out = true; break; }
-                    ++rounds, ++r;
-                    round(r);
-                }
-                if (!out && k < level) {
-                    if (tid == 0) cur[choice[k]] = indiv(cur[choice[k]], k);
-                    __syncthreads();
+            const TableSlot at = id_table_put<SLOTS>(table, e);
+            if (at.slot >= 0 && at.fresh) tidx[at.slot] = (u16)a;
+        }
+        __syncthreads();
+        int bad = 0;
+        for (int a = tid; a < n; a += GT) {
+            const u64 e = cur[a];
+            int t = zero_at;
+            if (e != 0) {
+                const int slot = id_table_find<SLOTS>(table, e);
+                t = slot >= 0 ? (int)tidx[slot] : -1;
+            }
+            const int y = t < 0 || t >= n ? a : t;
+            gam[a] = (u16)y;
+            bad += t < 0 || t >= n || cls_of(im, a) != cls_of(im, y) || chg_of(im, a) != chg_of(im, y) || tag[a] != tag[y];
+        }
+        if (sum_int(bad) != 0) return false;      // (gam is written: the reduction synchronises)
+        // the multiset of the mapped rows is the multiset of the rows, by counting (one loop: the graph is mapped onto itself, so
+        // every row is read once for both counts; why this is not the identity's loop: graph_refine.hpp)
+        int common = 0;
+        for (int q = tid; q < im.nrows; q += GT) {
+            const BondRow e = row(im, q);
+            if (!e.v) continue;
+            const int gi = gam[e.i], gj = gam[e.j], lo = min(gi, gj), hi = max(gi, gj);
+            int before = 0, there = 0;
+            for (int q2 = 0; q2 < im.nrows; ++q2) {
+                const BondRow e2 = row(im, q2);
+                if (!e2.v || e2.o != e.o) continue;
+                const int gi2 = gam[e2.i], gj2 = gam[e2.j];
+                before += q2 < q && min(gi2, gj2) == lo && max(gi2, gj2) == hi;
+                there += min(e2.i, e2.j) == lo && max(e2.i, e2.j) == hi;
+            }
+            common += before < there;
+        }
+        return sum_int(common) == im.nvalid;
+    }
+    // x ~ gam(x) in the orbit tables of the levels 0 .. upto, whose prefix the map fixes: the greater root is hung under the less.
+    // Barrier: behind the unions
+    __device__ __forceinline__ void merge_orbits(const Image& im, int upto) {
+        const int n = im.n;
+        for (int l = 0; l <= upto; ++l) {
+            int* p = orbit[l];
+            for (int a = im.tid; a < n; a += GT) {
+                int x = a, y = gam[a];
+                for (int it = 0; it < n; ++it) {
+                    for (int w = 0; w < n; ++w) {
+                        const int up = __hip_atomic_load(&p[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (up == x) break;
+                        x = up;
+                    }
+                    for (int w = 0; w < n; ++w) {
+                        const int up = __hip_atomic_load(&p[y], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (up == y) break;
+                        y = up;
+                    }
+                    if (x == y) break;
+                    if (x < y) { const int t = x; x = y; y = t; }
+                    if (atomicCAS(&p[x], x, y) == x) break;
                 }
             }
-            if (out) { status |= ABC_CANON_UNDECIDED; break; }
-            mode = CHILD;
         }
+        __syncthreads();
     }
-    __syncthreads();
+    // the tables 0 .. upto flat again: every atom under its root, the least of its orbit.  Barriers: per table between the reading of
+    // the roots and the writing, and behind the last table
+    __device__ __forceinline__ void flatten_orbits(const Image& im, int upto) {
+        const int tid = im.tid, n = im.n;
+        for (int l = 0; l <= upto; ++l) {
+            int* p = orbit[l];
+            int root[MAX_ATOMS / GT];
+#pragma unroll
+            for (int u = 0; u < MAX_ATOMS / GT; ++u) {
+                int x = min(tid + u * GT, MAX_ATOMS - 1);
+                for (int w = 0; w < n; ++w) {
+                    const int up = p[x];
+                    if (up == x) break;
+                    x = up;
+                }
+                root[u] = x;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < MAX_ATOMS / GT; ++u)
+                if (tid + u * GT < n) p[tid + u * GT] = root[u];
+        }
+        __syncthreads();
+    }
+    // (b) a discrete colouring: ranks, h, <STEREO> word; the first leaf, a leaf of a strictly better path and a leaf with a smaller h
+    // become the best; an equal h is mapped onto the best and verified -- an automorphism is merged into the orbits and the search
+    // returns to the level where the path left the best's
+    __device__ __forceinline__ Mode leaf(const Image& im, Search& q) {
+        const int tid = im.tid, n = im.n, level = q.level;
+        ++q.leaves;
+        leaf_ranks(im);
+        const u64 h = leaf_hash(im, rk);
+        if constexpr (STEREO) leaf_word(im);
+        if (!q.have_best || q.less_from != NONE || h < q.best_h) {
+            q.improved += q.have_best;
+            keep_best(im, level, true);
+            q.have_best = true, q.best_levels = level, q.best_h = h, q.less_from = NONE;
+            return BACK;
+        }
+        if (h != q.best_h) return BACK;
+        if (!map_onto_best(im)) {
+            q.status |= ABC_CANON_COLLISION;
+            return STOP;
+        }
+        if constexpr (STEREO) {
+            // the third key, compared exactly: the first position at which the words differ
+            int differs = NONE;
+            for (int k = tid; k < n; k += GT)
+                if (this->sword[k] != this->bword[k]) differs = min(differs, k);
+            differs = min_int(differs);
+            if (differs != NONE) {      // a map that does not keep the stereo: no orbit merge, no jump
+                ++q.s_unequal;
+                const bool less = this->sword[differs] < this->bword[differs];
+                __syncthreads();         // (read before the best leaf's word is replaced)
+                if (less) {
+                    ++q.s_improved, ++q.improved;
+                    keep_best(im, level, false);      // (the traces are equal)
+                }
+                return BACK;
+            }
+            ++q.s_autos;
+        }
+        ++q.autos;
+        int first = NONE;
+        for (int l = tid; l < level; l += GT)
+            if (choice[l] != best_choice[l]) first = min(first, l);
+        q.target = min(min_int(first), level - 1);      // the level where the path left the best's
+        const int upto = min(q.target, ORBITS - 1);
+        merge_orbits(im, upto);
+        flatten_orbits(im, upto);
+        return BACK;
+    }
 
-    // ---- the outputs: every word of every buffer
-    if (!have_best)
-        for (int a = tid; a < n; a += GT) brank[a] = (u16)a;
-    __syncthreads();
-    const bool none = empty || n == 0;
-    for (int k = tid; k < cap; k += GT)
-        if (k >= n) order[k] = -1;
-    for (int a = tid; a < n; a += GT) order[brank[a]] = orig[a];
-    const u64 key0 = none ? 0 : leaf_hash(brank);
-    u64 t = 0;
-    if (have_best)
-        for (int l = tid; l <= best_levels; l += GT) t += mix(mix(mix(mix((u64)l + 1) + (u64)best_k[l]) + (u64)best_c[l]) + best_sum[l]);
-    t = block_reduce(t, wu, [](u64 u, u64 v) { return u + v; });
-    if (tid == 0) {
+    // ---- (a) REFINE: the level's rounds, the trace and its comparison with the best leaf's, then the leaf or the cell of the node.
+    // Barrier of its own: behind the cell, cell_max, nxt and the fresh orbit table of the level
+    __device__ __forceinline__ Mode refine(const Image& im, Search& q) {
+        const int tid = im.tid, n = im.n, level = q.level;
+        const LevelRun lv = refine_level(n, q.prev, q.rounds, q.max_rounds, q.r, [&](u64 r) __attribute__((always_inline)) { round(im, r); },
+                                         [&]() __attribute__((always_inline)) { return classes(im, q); });
+        if (lv.out) {
+            q.status |= ABC_CANON_UNDECIDED;
+            return STOP;
+        }
+        const int k = lv.rounds, c = lv.classes;
+        const u64 s = refine_multiset_sum(tid, cur, n, wu);
+        if (tid == 0) cur_k[level] = (u16)k, cur_c[level] = (u16)c, cur_sum[level] = s;
+        q.levels_max = max(q.levels_max, level);
+        q.target = level - 1;
+        if (q.have_best && q.less_from == NONE) {
+            const int bk = best_k[level], bc = best_c[level];
+            const u64 bs = best_sum[level];
+            const int cmp = k != bk ? (k < bk ? -1 : 1) : (c != bc ? (c < bc ? -1 : 1) : (s != bs ? (s < bs ? -1 : 1) : 0));
+            if (cmp > 0) {
+                ++q.pruned_trace;
+                return BACK;
+            }
+            if (cmp < 0) q.less_from = level;
+        }
+        if (c == n) return leaf(im, q);
+        if (level + 1 >= n) {            // (only colliding hashes get here)
+            q.status |= ABC_CANON_COLLISION;
+            return STOP;
+        }
+        // the cell: the least id that two atoms share; its last atom
+        const u64 cellv = refine_cell(q.shared, q.zeros, wu);
+        const int last = cell_member<true>(tid, cur, n, cellv, 0, wi);
+        if (last < 0) {
+            q.status |= ABC_CANON_COLLISION;
+            return STOP;
+        }
+        if (tid == 0) cell[level] = cellv, cell_max[level] = (u16)last, nxt[level] = 0;
+        if (level < ORBITS)
+            for (int a = tid; a < MAX_ATOMS; a += GT) orbit[level][a] = a;
+        __syncthreads();
+        return CHILD;
+    }
+    // ---- (c) CHILD: the next atom of the cell that is the least of its orbit, individualised.  Barrier of its own: behind the stack
+    // and the individualised id
+    __device__ __forceinline__ Mode next_child(const Image& im, Search& q) {
+        const int tid = im.tid, n = im.n, level = q.level;
+        const u64 cellv = cell[level];
+        const int from = nxt[level];
+        const bool orbits = level < ORBITS;
+        const int* least_of = orbit[min(level, ORBITS - 1)];
+        const int v = cell_member<false>(tid, cur, n, cellv, from, wi, [&](int a) __attribute__((always_inline)) { return !orbits || least_of[a] == a; });
+        if (orbits) {
+            int skipped = 0;
+            for (int a = tid; a < n; a += GT) skipped += a >= from && a < v && cur[a] == cellv;
+            q.pruned_orbit += sum_int(skipped);
+        }
+        if (v >= n) {
+            q.target = level - 1;
+            return BACK;
+        }
+        if (q.tries >= q.max_tries) {
+            q.status |= ABC_CANON_UNDECIDED;
+            return STOP;
+        }
+        ++q.tries;
+        q.prev = cur_c[level] + 1;
+        if (tid == 0) choice[level] = (u16)v, nxt[level] = (u16)(v + 1), cur[v] = indiv(cur[v], level);
+        __syncthreads();
+        ++q.level;
+        return REFINE;
+    }
+    // ---- (d) BACK: the nearest level at or above the target that still has an atom of its cell to try; its ids by replay.  Barrier
+    // of its own: in front (nxt and cell_max of the levels are tid 0's writes)
+    __device__ __forceinline__ Mode back(const Image& im, Search& q) {
+        __syncthreads();
+        for (int it = 0; it < im.n && q.target >= 0 && nxt[q.target] > cell_max[q.target]; ++it) --q.target;
+        if (q.target < 0) return STOP;
+        q.level = q.target;
+        if (q.less_from != NONE && q.less_from > q.level) q.less_from = NONE;
+        if (!refine_replay(im.tid, cur, init, im.n, q.level, cur_k, choice, q.rounds, q.max_rounds, q.r, [&](u64 r) __attribute__((always_inline)) { round(im, r); })) {
+            q.status |= ABC_CANON_UNDECIDED;
+            return STOP;
+        }
+        return CHILD;
+    }
+
+    // ---- the outputs: every word of every buffer.  The order of the best leaf (none: the identity order), the two keys, the stats row
+    // and <STEREO> the stereo_search row.  Barriers: in front (the search's last writes), behind the identity order, the reductions'
+    template <class Desc>
+    __device__ __forceinline__ void write_order_key_stats(const Desc& d, int b, const Image& im, const Search& q, int cap) {
+        const int tid = im.tid, n = im.n;
+        int* const order = d.order + (size_t)b * cap;
+        __syncthreads();
+        if (!q.have_best)
+            for (int a = tid; a < n; a += GT) brank[a] = (u16)a;
+        __syncthreads();
+        const bool none = im.empty || n == 0;
+        for (int k = tid; k < cap; k += GT)
+            if (k >= n) order[k] = -1;
+        for (int a = tid; a < n; a += GT) order[brank[a]] = orig[a];
+        const u64 key0 = none ? 0 : leaf_hash(im, brank);
+        u64 t = 0;
+        if (q.have_best)
+            for (int l = tid; l <= q.best_levels; l += GT) t += mix(mix(mix(mix((u64)l + 1) + (u64)best_k[l]) + (u64)best_c[l]) + best_sum[l]);
+        t = block_reduce(t, wu, [](u64 u, u64 v) { return u + v; });
+        if (tid != 0) return;
         int* st = d.stats + (size_t)b * NCOL;
-        st[ABC_CANON_STATUS] = status;
-        st[ABC_CANON_LEAVES] = leaves, st[ABC_CANON_TRIES] = tries, st[ABC_CANON_ROUNDS] = rounds, st[ABC_CANON_LEVELS_MAX] = levels_max;
-        st[ABC_CANON_PRUNED_TRACE] = pruned_trace, st[ABC_CANON_PRUNED_ORBIT] = pruned_orbit;
-        st[ABC_CANON_AUTOMORPHISMS] = autos, st[ABC_CANON_IMPROVED] = improved;
+        st[ABC_CANON_STATUS] = q.status;
+        st[ABC_CANON_LEAVES] = q.leaves, st[ABC_CANON_TRIES] = q.tries, st[ABC_CANON_ROUNDS] = q.rounds, st[ABC_CANON_LEVELS_MAX] = q.levels_max;
+        st[ABC_CANON_PRUNED_TRACE] = q.pruned_trace, st[ABC_CANON_PRUNED_ORBIT] = q.pruned_orbit;
+        st[ABC_CANON_AUTOMORPHISMS] = q.autos, st[ABC_CANON_IMPROVED] = q.improved;
         d.key[(size_t)b * 2] = (long long)key0;
-        d.key[(size_t)b * 2 + 1] = empty ? 0 : (long long)mix(mix(mix((u64)n) + (u64)nvalid) + t);
+        d.key[(size_t)b * 2 + 1] = im.empty ? 0 : (long long)mix(mix(mix((u64)n) + (u64)im.nvalid) + t);
         if constexpr (STEREO) {
             int* ss = d.stereo_search + (size_t)b * 4;
-            ss[0] = s_unequal, ss[1] = s_improved, ss[2] = s_autos, ss[3] = 0;
+            ss[0] = q.s_unequal, ss[1] = q.s_improved, ss[2] = q.s_autos, ss[3] = 0;
         }
     }
-    if (cert == nullptr && !want_rows) return;
-
-    int* const oc = want_rows ? d.out_counts + (size_t)b * 4 : nullptr;
-    int* const oa = want_rows ? d.out_atoms + (size_t)b * d.cap_atoms * ATOM_W : nullptr;
-    int* const ob = want_rows ? d.out_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W : nullptr;
-    int* const oh = want_rows ? d.out_implh + (size_t)b * d.cap_atoms : nullptr;
-    if (cert != nullptr) {
-        const int used = 2 + n + 3 * nvalid;
+    // the certificate but its triples: the padding, the two counts, a word per atom at its canonical position
+    __device__ __forceinline__ void write_certificate(int* cert, const Image& im, int cap, int cap_bonds) {
+        const int tid = im.tid, n = im.n, used = 2 + n + 3 * im.nvalid;
         for (int k = tid; k < 2 + cap + 3 * cap_bonds; k += GT)
             if (k >= used) cert[k] = -1;
-        if (tid == 0) cert[0] = n, cert[1] = nvalid;
+        if (tid == 0) cert[0] = n, cert[1] = im.nvalid;
         for (int a = tid; a < n; a += GT)
-            cert[2 + brank[a]] = (int)(((unsigned)chg_of(a) << 5) | ((unsigned)tag[a] << 4) | (unsigned)cls_of(a));
+            cert[2 + brank[a]] = (int)(((unsigned)chg_of(im, a) << 5) | ((unsigned)tag[a] << 4) | (unsigned)cls_of(im, a));
     }
-    if (want_rows) {
+    // the canonical rows but the bond rows' places: the counts, the atom rows at their positions, the padding of atoms and bonds
+    template <class Desc>
+    __device__ __forceinline__ void write_canonical_rows(const Desc& d, int b, const Image& im, int* oa, int* ob) {
+        const int tid = im.tid, n = im.n;
+        int* const oc = d.out_counts + (size_t)b * 4;
         if (tid < 4) oc[tid] = d.mol_counts[(size_t)b * 4 + tid];
         for (int k = tid; k < (d.cap_atoms - n) * ATOM_W; k += GT) oa[n * ATOM_W + k] = 0;
-        for (int k = tid; k < n * ATOM_W; k += GT) oa[brank[k / ATOM_W] * ATOM_W + k % ATOM_W] = pa[k];
-        for (int k = tid; k < (d.cap_mol_bonds - nrows) * MOL_BOND_W; k += GT) ob[nrows * MOL_BOND_W + k] = 0;
-        // the implicit-H list: the entries in 1..n renumbered and ascending, the others after them verbatim
-        for (int k = tid; k < d.cap_atoms; k += GT) {
+        for (int k = tid; k < n * ATOM_W; k += GT) oa[brank[k / ATOM_W] * ATOM_W + k % ATOM_W] = im.pa[k];
+        for (int k = tid; k < (d.cap_mol_bonds - im.nrows) * MOL_BOND_W; k += GT) ob[im.nrows * MOL_BOND_W + k] = 0;
+    }
+    // the implicit-H list: the entries in 1..n renumbered and ascending, the others after them verbatim
+    __device__ __forceinline__ void write_implicit_h(int* oh, const Image& im, int cap_atoms) {
+        const int n = im.n, nlisted = im.nlisted;
+        const int* ph = im.ph;
+        for (int k = im.tid; k < cap_atoms; k += GT) {
             if (k >= nlisted) {
                 oh[k] = 0;
                 continue;
@@ -545,31 +592,72 @@ __global__ __launch_bounds__(GT) void graph_canon_kernel(const typename CanonDes
             oh[in ? less : in_all + out_before] = in ? val : e;
         }
     }
-    // the bond rows, by counting: the place of a row among the certificate's triples and among the canonical rows
-    for (int q = tid; q < nrows; q += GT) {
-        const BondRow e = row(q);
-        const bool valid = e.v;
-        const int bi = valid ? brank[e.i] : 0, bj = valid ? brank[e.j] : 0, lo = min(bi, bj), hi = max(bi, bj);
-        const int pair = lo * MAX_ATOMS + hi;
-        int at_cert = 0, at_rows = 0, valid_before = 0;
-        for (int q2 = 0; q2 < nrows; ++q2) {
-            const BondRow e2 = row(q2);
-            if (!e2.v) continue;
-            valid_before += q2 < q;
-            const int bi2 = brank[e2.i], bj2 = brank[e2.j], pair2 = min(bi2, bj2) * MAX_ATOMS + max(bi2, bj2);
-            at_rows += pair2 < pair || (pair2 == pair && q2 < q);
-            at_cert += pair2 < pair || (pair2 == pair && (e2.o < e.o || (e2.o == e.o && q2 < q)));
-        }
-        if (cert != nullptr && valid) {
-            int* tr = cert + 2 + n + 3 * at_cert;
-            tr[0] = lo, tr[1] = hi, tr[2] = e.o;
-        }
-        if (want_rows) {
-            const int* src = pb + q * MOL_BOND_W;
-            int* dst = ob + (valid ? at_rows : nvalid + q - valid_before) * MOL_BOND_W;
-            dst[0] = valid ? bi + 1 : src[0], dst[1] = valid ? bj + 1 : src[1], dst[2] = src[2], dst[3] = src[3];
+    // the bond rows, by counting: the place of a row among the certificate's triples (cert, may be null) and among the canonical
+    // rows (ob, may be null)
+    __device__ __forceinline__ void write_bond_rows(int* cert, int* ob, const Image& im) {
+        const int n = im.n, nrows = im.nrows;
+        for (int q = im.tid; q < nrows; q += GT) {
+            const BondRow e = row(im, q);
+            const bool valid = e.v;
+            const int bi = valid ? brank[e.i] : 0, bj = valid ? brank[e.j] : 0, lo = min(bi, bj), hi = max(bi, bj);
+            const int pair = lo * MAX_ATOMS + hi;
+            int at_cert = 0, at_rows = 0, valid_before = 0;
+            for (int q2 = 0; q2 < nrows; ++q2) {
+                const BondRow e2 = row(im, q2);
+                if (!e2.v) continue;
+                valid_before += q2 < q;
+                const int bi2 = brank[e2.i], bj2 = brank[e2.j], pair2 = min(bi2, bj2) * MAX_ATOMS + max(bi2, bj2);
+                at_rows += pair2 < pair || (pair2 == pair && q2 < q);
+                at_cert += pair2 < pair || (pair2 == pair && (e2.o < e.o || (e2.o == e.o && q2 < q)));
+            }
+            if (cert != nullptr && valid) {
+                int* tr = cert + 2 + n + 3 * at_cert;
+                tr[0] = lo, tr[1] = hi, tr[2] = e.o;
+            }
+            if (ob != nullptr) {
+                const int* src = im.pb + q * MOL_BOND_W;
+                int* dst = ob + (valid ? at_rows : im.nvalid + q - valid_before) * MOL_BOND_W;
+                dst[0] = valid ? bi + 1 : src[0], dst[1] = valid ? bj + 1 : src[1], dst[2] = src[2], dst[3] = src[3];
+            }
         }
     }
+};
+
+// The search as a loop of modes: REFINE -> the leaf (then BACK) or CHILD; CHILD -> REFINE one level down, or BACK; BACK -> CHILD at a
+// level that has a candidate left, or the end.  A budget or a collision stops it where it stands.  One turn of the loop runs the modes
+// in that order, so REFINE falls through to CHILD and either to BACK
+template <bool STEREO>
+__global__ __launch_bounds__(GT) void graph_canon_kernel(const typename CanonDescOf<STEREO>::type d) {
+    __shared__ Canon<STEREO> s;
+    const int b = blockIdx.x;
+    Image im;
+    Search q = {};
+    q.status = s.setup(d, b, im);
+    if constexpr (STEREO) s.check_elements(d, b, im);
+    q.max_tries = d.max_tries > 0 ? d.max_tries : ABC_CANON_DEFAULT_TRIES;
+    q.max_rounds = d.max_rounds > 0 ? d.max_rounds : ABC_CANON_DEFAULT_ROUNDS;
+    q.mode = REFINE, q.target = -1, q.less_from = NONE, q.shared = ~0ull;
+    if (!im.empty && im.n > 0) {
+        q.prev = s.classes(im, q);
+        while (q.mode != STOP) {
+            if (q.mode == REFINE) q.mode = s.refine(im, q);
+            if (q.mode == CHILD) q.mode = s.next_child(im, q);
+            if (q.mode == BACK) q.mode = s.back(im, q);
+        }
+    }
+
+    const int cap = im.mol ? d.cap_atoms : d.max_atoms, cap_bonds = im.mol ? d.cap_mol_bonds : d.max_bonds;
+    s.write_order_key_stats(d, b, im, q, cap);
+    int* const cert = d.cert_out != nullptr ? d.cert_out + (size_t)b * (2 + cap + 3 * (size_t)cap_bonds) : nullptr;
+    const bool want_rows = im.mol && d.out_counts != nullptr;
+    if (cert == nullptr && !want_rows) return;
+    int* const ob = want_rows ? d.out_bonds + (size_t)b * d.cap_mol_bonds * MOL_BOND_W : nullptr;
+    if (cert != nullptr) s.write_certificate(cert, im, cap, cap_bonds);
+    if (want_rows) {
+        s.write_canonical_rows(d, b, im, d.out_atoms + (size_t)b * d.cap_atoms * ATOM_W, ob);
+        s.write_implicit_h(d.out_implh + (size_t)b * d.cap_atoms, im, d.cap_atoms);
+    }
+    s.write_bond_rows(cert, ob, im);
 }
 
 // the guards of both entry points, and the launch

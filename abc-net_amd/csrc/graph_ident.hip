@@ -43,242 +43,244 @@ constexpr int SLOTS = 2 * MAX_ATOMS;  // of the class count's table: a power of 
 static_assert(MAX_ATOMS == 2 * GT, "two atoms per thread: the record scan, the class count");
 enum { SAME = 1, DIFFERENT = 2, UNDECIDED = 3 };
 
-__global__ __launch_bounds__(GT) void graph_ident_kernel(const abc_graph_identity_desc d) {
-    __shared__ u64 cur[2][MAX_ATOMS];    // the ids of every atom
-    __shared__ u64 acc[MAX_ATOMS];       // the neighbour sum of the round (one side runs at a time); the record's degrees in (A)
-    __shared__ u64 init[MAX_ATOMS];      // id_0 of the record: where every replay starts
-    __shared__ u64 lv_sum[MAX_ATOMS], lv_cell[MAX_ATOMS];      // per level: sum of mix(id), the id of the cell
-    __shared__ int lv_rounds[MAX_ATOMS], lv_classes[MAX_ATOMS];
-    __shared__ int choice[MAX_ATOMS], nxt[MAX_ATOMS + 1];      // the record's stack: the atom taken, the first index not yet tried
-    __shared__ int remap[MAX_ATOMS];     // record atom -> its number in T, -1 outside T
-    __shared__ int orig[MAX_ATOMS];      // number in T -> record atom
-    __shared__ int mapv[MAX_ATOMS];      // molecule atom -> number in T, at a leaf
-    __shared__ u64 table[SLOTS];         // the ids of one side, open-addressed: the class count
-    __shared__ unsigned wt[NW + 1];
-    __shared__ int wi[NW];
-    __shared__ u64 wu[NW];
-    __shared__ int cnt[2];               // valid molecule bonds, valid record bonds
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int* const map_row = d.map_out != nullptr ? d.map_out + (size_t)b * d.cap_atoms : nullptr;
-    ScoredImage im;
-    if (!scored_image<NCOL>(d, b, tid, im)) {
-        if (map_row != nullptr)
-            for (int a = tid; a < d.cap_atoms; a += GT) map_row[a] = -1;
-        return;
-    }
-    const int nt = im.nt, m = im.m, status = im.status, na = im.na, nb = im.nb;      // (plain locals: the lambdas below capture them)
-    const bool empty = im.empty;
-    const int *const pa = im.pa, *const pb = im.pb, *const ra = im.ra, *const rb = im.rb;
-    const int max_tries = d.max_tries > 0 ? d.max_tries : ABC_IDENT_DEFAULT_TRIES;
-    const int max_rounds = d.max_rounds > 0 ? d.max_rounds : ABC_IDENT_DEFAULT_ROUNDS;
+// What a thread holds of its pair in registers: the two images (mol_rows.hpp), the sizes of the graphs, row `tid` of each side
+struct Pair {
+    int tid, n;                      // n: the atoms of either graph, once the sizes are equal
+    int na, nb, nt, m, valid_p;      // molecule atoms and rows, record atoms and rows, the molecule's valid rows
+    const int *pa, *pb, *ra, *rb;
+    BondRow prow, trow;              // kept through every round (the record row's ends are numbers in T)
+};
+// The outcome and the work counters (uniform), the budgets, and refine_classes' `shared` (this thread's) and `zeros`
+struct Outcome {
+    int max_tries, max_rounds;
+    int result, levels, tries, backtracks, rounds;
+    u64 shared;
+    int zeros;
+};
 
-    // row `tid` of each side, kept through every round
-    const BondRow none = {false, 0, 0, 0};
-    const BondRow prow = tid < nb ? mol_row(pb, tid, na) : none;
-    BondRow trow = tid < m ? rec_row(rb, tid, nt) : none;
+// 46 KB of LDS and the steps of the test on them.  Every step is inlined into the kernel; each says which barriers it places
+struct Ident {
+    u64 cur[2][MAX_ATOMS];           // the ids of every atom
+    u64 acc[MAX_ATOMS];              // the neighbour sum of the round (one side runs at a time); the record's degrees in (A)
+    u64 init[MAX_ATOMS];             // id_0 of the record: where every replay starts
+    u64 lv_sum[MAX_ATOMS], lv_cell[MAX_ATOMS];      // per level: sum of mix(id), the id of the cell
+    u64 table[SLOTS];                // the ids of one side, open-addressed: the class count
+    u64 wu[NW];
+    int lv_rounds[MAX_ATOMS], lv_classes[MAX_ATOMS];
+    int choice[MAX_ATOMS], nxt[MAX_ATOMS + 1];      // the record's stack: the atom taken, the first index not yet tried
+    int remap[MAX_ATOMS];            // record atom -> its number in T, -1 outside T
+    int orig[MAX_ATOMS];             // number in T -> record atom
+    int mapv[MAX_ATOMS];             // molecule atom -> number in T, at a leaf
+    unsigned wt[NW + 1];
+    int wi[NW];
+    int cnt[2];                      // valid molecule bonds, valid record bonds
 
-    // ---- (A) degrees, T, id_0 (graph_refine.hpp; the molecule's degrees in cur[1] to save LDS, the record's in acc)
-    if (tid < 2) cnt[tid] = 0;
-    for (int a = tid; a < MAX_ATOMS; a += GT) cur[1][a] = acc[a] = 0;
-    __syncthreads();
-    {
-        const int valid_p = refine_degrees_mol(tid, pb, nb, na, prow, cur[1]), valid_t = refine_degrees_rec(tid, rb, m, nt, trow, acc);
-        if (valid_p) atomicAdd(cnt + 0, valid_p);
-        if (valid_t) atomicAdd(cnt + 1, valid_t);
-    }
-    __syncthreads();
-    refine_id0_mol(tid, pa, na, cur[1], cur[0]);
-    // (id_0 of the record goes into init alone: cur[1], the molecule's degrees until here, becomes the record's ids when the search
-    // begins, by replay(0))
-    const int n_t = refine_number_rec(tid, ra, nt, acc, wt, remap, orig, init);      // |T|
-    __syncthreads();
-    renumber(trow, remap);
-    const int valid_p = cnt[0], valid_t = cnt[1];
-    const bool size_equal = !empty && na == n_t && valid_p == valid_t;
-    const int n = na;
-
-    // one round of side `s` (uniform); acc is zero on entry and on exit
-    auto round = [&](int s, u64 r) __attribute__((always_inline)) {
-        if (s == 0) refine_add_mol(tid, cur[0], acc, pb, nb, na, prow);
-        else refine_add_rec(tid, cur[1], acc, rb, m, nt, remap, trow);
+    // one round of side `s` (uniform); acc is zero on entry and on exit.  Barriers: between the halves, behind the new ids
+    __device__ __forceinline__ void round(const Pair& p, int s, u64 r) {
+        if (s == 0) refine_add_mol(p.tid, cur[0], acc, p.pb, p.nb, p.na, p.prow);
+        else refine_add_rec(p.tid, cur[1], acc, p.rb, p.m, p.nt, remap, p.trow);
         __syncthreads();
-        refine_finish(tid, cur[s], acc, n, r);
+        refine_finish(p.tid, cur[s], acc, p.n, r);
         __syncthreads();
-    };
-    // the number of distinct ids, exactly; `shared` keeps this thread's least id two atoms share, `zeros` (uniform) the number of
-    // ids that are 0, for the cell of the level
-    u64 shared = ~0ull;
-    int zeros = 0;
-    auto classes = [&](const u64* id) __attribute__((always_inline)) { return refine_classes<SLOTS>(tid, id, n, table, wi, shared, zeros); };
-    auto multiset_sum = [&](const u64* id) __attribute__((always_inline)) { return refine_multiset_sum(tid, id, n, wu); };
+    }
+    // the number of distinct ids of side `s`, exactly; q.shared keeps this thread's least id two atoms share, q.zeros (uniform) the
+    // number of ids that are 0, for the cell of the level
+    __device__ __forceinline__ int classes(const Pair& p, Outcome& q, int s) { return refine_classes<SLOTS>(p.tid, cur[s], p.n, table, wi, q.shared, q.zeros); }
 
-    int result = 0, levels = 0, tries = 0, backtracks = 0, rounds = 0;
-    if (empty) {
-        result = 0;
-    } else if (!size_equal) {
-        result = DIFFERENT;
-    } else {
-        // ---- (b) the molecule's path
-        int level = 0, prev = classes(cur[0]);
+    // ---- (A) degrees, T, id_0 (graph_refine.hpp; the molecule's degrees in cur[1] to save LDS, the record's in acc); (a) true when
+    // the sizes are equal.  Barriers: behind the clearing, behind the degrees, behind remap / orig / id_0
+    __device__ __forceinline__ bool setup(const ScoredImage& im, Pair& p) {
+        const int tid = p.tid = threadIdx.x;
+        p.na = im.na, p.nb = im.nb, p.nt = im.nt, p.m = im.m, p.pa = im.pa, p.pb = im.pb, p.ra = im.ra, p.rb = im.rb;
+        const BondRow none = {false, 0, 0, 0};
+        p.prow = tid < p.nb ? mol_row(p.pb, tid, p.na) : none;
+        p.trow = tid < p.m ? rec_row(p.rb, tid, p.nt) : none;
+        if (tid < 2) cnt[tid] = 0;
+        for (int a = tid; a < MAX_ATOMS; a += GT) cur[1][a] = acc[a] = 0;
+        __syncthreads();
+        {
+            const int valid_p = refine_degrees_mol(tid, p.pb, p.nb, p.na, p.prow, cur[1]), valid_t = refine_degrees_rec(tid, p.rb, p.m, p.nt, p.trow, acc);
+            if (valid_p) atomicAdd(cnt + 0, valid_p);
+            if (valid_t) atomicAdd(cnt + 1, valid_t);
+        }
+        __syncthreads();
+        refine_id0_mol(tid, p.pa, p.na, cur[1], cur[0]);
+        // (id_0 of the record goes into init alone: cur[1], the molecule's degrees until here, becomes the record's ids when the search
+        // begins, by the replay of level 0)
+        const int n_t = refine_number_rec(tid, p.ra, p.nt, acc, wt, remap, orig, init);      // |T|
+        __syncthreads();
+        renumber(p.trow, remap);
+        p.valid_p = cnt[0];
+        p.n = p.na;
+        return !im.empty && p.na == n_t && p.valid_p == cnt[1];
+    }
+
+    // ---- (b) the molecule's path: per level its rounds, the record of the level, then the cell's first atom individualised.  Sets
+    // q.levels, or q.result = UNDECIDED.  Barriers of its own: behind every individualisation, behind the level records
+    __device__ __forceinline__ void molecule_path(const Pair& p, Outcome& q) {
+        const int tid = p.tid, n = p.n;
+        int level = 0, prev = classes(p, q, 0);
         u64 r = 0;
         while (true) {
-            int k = 0, c = 0;
-            while (true) {
-                if (rounds >= max_rounds) { result = UNDECIDED; break; }
-                ++rounds, ++r, ++k;
-                round(0, r);
-                c = classes(cur[0]);
-                if (c <= prev || k >= n) break;
-                prev = c;
-            }
-            if (result) break;
-            const u64 sum = multiset_sum(cur[0]);
-            if (tid == 0) lv_rounds[level] = k, lv_sum[level] = sum, lv_classes[level] = c;
-            if (c == n) break;
+            const LevelRun lv = refine_level(n, prev, q.rounds, q.max_rounds, r, [&](u64 r_) __attribute__((always_inline)) { round(p, 0, r_); },
+                                             [&]() __attribute__((always_inline)) { return classes(p, q, 0); });
+            if (lv.out) { q.result = UNDECIDED; break; }
+            const u64 sum = refine_multiset_sum(tid, cur[0], n, wu);
+            if (tid == 0) lv_rounds[level] = lv.rounds, lv_sum[level] = sum, lv_classes[level] = lv.classes;
+            if (lv.classes == n) break;
             // the cell: the least id that two atoms share, then its first atom
-            const u64 least = block_reduce(shared, wu, [](u64 u, u64 v) { return min(u, v); });
-            const u64 cell = zeros > 1 ? 0 : least;
-            int first = MAX_ATOMS;
-            for (int a = tid; a < n; a += GT)
-                if (cur[0][a] == cell) first = min(first, a);
-            const int v = block_reduce(first, wi, [](int u, int w) { return min(u, w); });
-            if (level + 1 >= n || v >= n) { result = UNDECIDED; break; }      // (only colliding hashes get here)
+            const u64 cell = refine_cell(q.shared, q.zeros, wu);
+            const int v = cell_member<false>(tid, cur[0], n, cell, 0, wi);
+            if (level + 1 >= n || v >= n) { q.result = UNDECIDED; break; }      // (only colliding hashes get here)
             if (tid == 0) lv_cell[level] = cell, cur[0][v] = indiv(cur[0][v], level);
             __syncthreads();
             ++level;
-            prev = c + 1;
+            prev = lv.classes + 1;
         }
-        levels = result ? 0 : level;
+        q.levels = q.result ? 0 : level;
         __syncthreads();                 // (the level records are written)
+    }
 
-        // ---- (c) the record's search
-        u64 rt = 0;
-        // the recorded rounds of level k on the record's ids; false: out of rounds
-        auto refine = [&](int k) __attribute__((always_inline)) {
-            const int todo = lv_rounds[k];
-            for (int i = 0; i < todo; ++i) {
-                if (rounds >= max_rounds) return false;
-                ++rounds, ++rt;
-                round(1, rt);
+    // ---- (d) the leaf: true when mapping by equal id is an isomorphism -- every molecule atom has one record atom of its id (a scan:
+    // the leaf is met once per image, see graph_refine.hpp), of its class and charge, and the multiset of the mapped rows is the
+    // record's.  Barriers: the two reductions' (the first is behind mapv)
+    __device__ __forceinline__ bool verify(const Pair& p) {
+        const int tid = p.tid, n = p.n;
+        int bad = 0;
+        for (int a = tid; a < n; a += GT) {
+            const u64 e = cur[0][a];
+            int hits = 0, t = 0;
+            for (int i = 0; i < n; ++i)
+                if (cur[1][i] == e) ++hits, t = i;
+            mapv[a] = t;
+            const int o = orig[t];
+            bad += hits != 1 || atom_class(p.pa[a * ATOM_W + 2]) != atom_class(p.ra[o * REC_ATOM_W + 2]) || p.pa[a * ATOM_W + 3] != p.ra[o * REC_ATOM_W + 3];
+        }
+        if (block_reduce(bad, wi, [](int u, int v) { return u + v; })) return false;
+        // a molecule row is counted when fewer equal mapped rows stand before it than the record has rows equal to it (two loops:
+        // the molecule's rows before q, then the record's; why this is not the canonical order's loop: graph_refine.hpp)
+        int common = 0;
+        for (int q = tid; q < p.nb; q += GT) {
+            const BondRow e = mol_row(p.pb, q, p.na);
+            if (!e.v) continue;
+            const int lo = min(mapv[e.i], mapv[e.j]), hi = max(mapv[e.i], mapv[e.j]);
+            int before = 0, there = 0;
+            for (int q2 = 0; q2 < q; ++q2) {
+                const BondRow e2 = mol_row(p.pb, q2, p.na);
+                if (!e2.v) continue;
+                before += min(mapv[e2.i], mapv[e2.j]) == lo && max(mapv[e2.i], mapv[e2.j]) == hi && e2.o == e.o;
             }
-            return true;
-        };
+            for (int k = 0; k < p.m; ++k) {
+                const BondRow t = rec_row(p.rb, k, p.nt, remap);
+                if (!t.v) continue;
+                there += min(t.i, t.j) == lo && max(t.i, t.j) == hi && t.o == e.o;
+            }
+            common += before < there;
+        }
+        return block_reduce(common, wi, [](int u, int v) { return u + v; }) == p.valid_p;
+    }
+
+    // ---- (c) the record's search, depth first, doing what (b) recorded.  Sets q.result.  Barriers of its own: behind nxt[0], behind
+    // every individualisation with its stack entries
+    __device__ __forceinline__ void record_search(const Pair& p, Outcome& q) {
+        const int tid = p.tid, n = p.n;
+        u64 rt = 0;
+        auto round1 = [&](u64 r) __attribute__((always_inline)) { round(p, 1, r); };
+        // the class count and the sum of the record's ids are those recorded for level k: else the branch is proved wrong
         auto matches = [&](int k) __attribute__((always_inline)) {
-            const int c = classes(cur[1]);
-            const u64 s = multiset_sum(cur[1]);
+            const int c = classes(p, q, 1);
+            const u64 s = refine_multiset_sum(tid, cur[1], n, wu);
             return c == lv_classes[k] && s == lv_sum[k];
         };
-        // the ids after the rounds of level `upto` under choice[0 .. upto - 1]; false: out of rounds
         auto replay = [&](int upto) __attribute__((always_inline)) {
-            for (int a = tid; a < n; a += GT) cur[1][a] = init[a];
-            __syncthreads();
-            rt = 0;
-            for (int k = 0; k <= upto; ++k) {
-                if (!refine(k)) return false;
-                if (k < upto) {
-                    if (tid == 0) cur[1][choice[k]] = indiv(cur[1][choice[k]], k);
+            return refine_replay(tid, cur[1], init, n, upto, lv_rounds, choice, q.rounds, q.max_rounds, rt, round1);
+        };
+        int level = 0;
+        bool ok = false;
+        if (!replay(0)) q.result = UNDECIDED;
+        else ok = matches(0);
+        if (tid == 0) nxt[0] = 0;
+        __syncthreads();
+        while (!q.result) {
+            if (ok && level == q.levels) {
+                if (verify(p)) { q.result = SAME; break; }
+                ok = false;
+            }
+            if (ok) {
+                // the candidates of the level: the record atoms whose id is the recorded cell id, in index order
+                const int v = cell_member<false>(tid, cur[1], n, lv_cell[level], nxt[level], wi);
+                if (v < n) {
+                    if (q.tries >= q.max_tries) { q.result = UNDECIDED; break; }
+                    ++q.tries;
+                    if (tid == 0) choice[level] = v, nxt[level] = v + 1, nxt[level + 1] = 0, cur[1][v] = indiv(cur[1][v], level);
                     __syncthreads();
+                    ++level;
+                    if (!refine_rounds(lv_rounds[level], q.rounds, q.max_rounds, rt, round1)) { q.result = UNDECIDED; break; }
+                    ok = matches(level);
+                    continue;
                 }
             }
-            return true;
-        };
-        // (d) the leaf: true when mapping by equal id is an isomorphism
-        auto verify = [&]() __attribute__((always_inline)) {
-            int bad = 0;
-            for (int a = tid; a < n; a += GT) {
-                const u64 e = cur[0][a];
-                int hits = 0, t = 0;
-                for (int i = 0; i < n; ++i)
-                    if (cur[1][i] == e) ++hits, t = i;
-                mapv[a] = t;
-                const int o = orig[t];
-                bad += hits != 1 || atom_class(pa[a * ATOM_W + 2]) != atom_class(ra[o * REC_ATOM_W + 2]) ||
-                       pa[a * ATOM_W + 3] != ra[o * REC_ATOM_W + 3];
-            }
-            if (block_reduce(bad, wi, [](int u, int v) { return u + v; })) return false;
-            int common = 0;
-            for (int q = tid; q < nb; q += GT) {
-                const BondRow e = mol_row(pb, q, na);
-                if (!e.v) continue;
-                const int lo = min(mapv[e.i], mapv[e.j]), hi = max(mapv[e.i], mapv[e.j]);
-                int before = 0, there = 0;
-                for (int q2 = 0; q2 < q; ++q2) {
-                    const BondRow e2 = mol_row(pb, q2, na);
-                    if (!e2.v) continue;
-                    before += min(mapv[e2.i], mapv[e2.j]) == lo && max(mapv[e2.i], mapv[e2.j]) == hi && e2.o == e.o;
-                }
-                for (int k = 0; k < m; ++k) {
-                    const BondRow t = rec_row(rb, k, nt, remap);
-                    if (!t.v) continue;
-                    there += min(t.i, t.j) == lo && max(t.i, t.j) == hi && t.o == e.o;
-                }
-                common += before < there;
-            }
-            return block_reduce(common, wi, [](int u, int v) { return u + v; }) == valid_p;
-        };
-
-        if (!result) {
-            int level = 0;
-            bool ok = false;
-            if (!replay(0)) result = UNDECIDED;
-            else ok = matches(0);
-            if (tid == 0) nxt[0] = 0;
-            __syncthreads();
-            while (!result) {
-                if (ok && level == levels) {
-                    if (verify()) { result = SAME; break; }
-                    ok = false;
-                }
-                if (ok) {
-                    const u64 cell = lv_cell[level];
-                    const int from = nxt[level];
-                    int first = MAX_ATOMS;
-                    for (int a = tid; a < n; a += GT)
-                        if (a >= from && cur[1][a] == cell) first = min(first, a);
-                    const int v = block_reduce(first, wi, [](int u, int w) { return min(u, w); });
-                    if (v < n) {
-                        if (tries >= max_tries) { result = UNDECIDED; break; }
-                        ++tries;
-                        if (tid == 0) choice[level] = v, nxt[level] = v + 1, nxt[level + 1] = 0, cur[1][v] = indiv(cur[1][v], level);
-                        __syncthreads();
-                        ++level;
-                        if (!refine(level)) { result = UNDECIDED; break; }
-                        ok = matches(level);
-                        continue;
-                    }
-                }
-                if (level == 0) { result = DIFFERENT; break; }
-                ++backtracks;
-                --level;
-                if (!replay(level)) { result = UNDECIDED; break; }
-                ok = true;
-            }
+            if (level == 0) { q.result = DIFFERENT; break; }
+            ++q.backtracks;
+            --level;
+            if (!replay(level)) { q.result = UNDECIDED; break; }      // a failed branch: the ids of the level above, rebuilt
+            ok = true;
         }
     }
-    __syncthreads();
-    if (map_row != nullptr)
-        for (int a = tid; a < d.cap_atoms; a += GT) map_row[a] = result == SAME && a < n ? orig[mapv[a]] : -1;
 
-    if (tid == 0) {
+    // ---- the map of a verified pair (else -1 everywhere) and the stats row with its totals.  Barrier: in front (mapv, orig)
+    __device__ __forceinline__ void write(const abc_graph_identity_desc& d, int b, const ScoredImage& im, const Pair& p, const Outcome& q, bool size_equal) {
+        __syncthreads();
+        if (d.map_out != nullptr) {
+            int* const map_row = d.map_out + (size_t)b * d.cap_atoms;
+            for (int a = p.tid; a < d.cap_atoms; a += GT) map_row[a] = q.result == SAME && a < p.n ? orig[mapv[a]] : -1;
+        }
+        if (p.tid != 0) return;
         int r[NCOL];
 #pragma unroll
         for (int i = 0; i < NCOL; ++i) r[i] = 0;
         r[ABC_IDENT_COUNTED] = 1;
-        if (empty) {
+        if (im.empty) {
             r[ABC_IDENT_NONE] = 1;
         } else {
-            r[ABC_IDENT_TRUNCATED] = (status & ABC_MOL_TRUNCATED) ? 1 : 0;
+            r[ABC_IDENT_TRUNCATED] = (im.status & ABC_MOL_TRUNCATED) ? 1 : 0;
             r[ABC_IDENT_SIZE_EQUAL] = size_equal;
-            r[ABC_IDENT_SAME] = result == SAME;
-            r[ABC_IDENT_DIFFERENT] = result == DIFFERENT;
-            r[ABC_IDENT_UNDECIDED] = result == UNDECIDED;
-            r[ABC_IDENT_LEVELS] = levels;
-            r[ABC_IDENT_TRIES] = tries;
-            r[ABC_IDENT_BACKTRACKS] = backtracks;
-            r[ABC_IDENT_ROUNDS] = rounds;
+            r[ABC_IDENT_SAME] = q.result == SAME;
+            r[ABC_IDENT_DIFFERENT] = q.result == DIFFERENT;
+            r[ABC_IDENT_UNDECIDED] = q.result == UNDECIDED;
+            r[ABC_IDENT_LEVELS] = q.levels;
+            r[ABC_IDENT_TRIES] = q.tries;
+            r[ABC_IDENT_BACKTRACKS] = q.backtracks;
+            r[ABC_IDENT_ROUNDS] = q.rounds;
         }
         write_row_and_totals<NCOL>(d.rows + (size_t)b * NCOL, d.totals, r);
     }
+};
+
+__global__ __launch_bounds__(GT) void graph_ident_kernel(const abc_graph_identity_desc d) {
+    __shared__ Ident s;
+    const int b = blockIdx.x;
+    ScoredImage im;
+    if (!scored_image<NCOL>(d, b, threadIdx.x, im)) {
+        if (d.map_out != nullptr)
+            for (int a = threadIdx.x; a < d.cap_atoms; a += GT) d.map_out[(size_t)b * d.cap_atoms + a] = -1;
+        return;
+    }
+    Pair p;
+    Outcome q = {};
+    q.max_tries = d.max_tries > 0 ? d.max_tries : ABC_IDENT_DEFAULT_TRIES;
+    q.max_rounds = d.max_rounds > 0 ? d.max_rounds : ABC_IDENT_DEFAULT_ROUNDS;
+    q.shared = ~0ull;
+    const bool size_equal = s.setup(im, p);
+    if (im.empty) {
+        q.result = 0;
+    } else if (!size_equal) {
+        q.result = DIFFERENT;
+    } else {
+        s.molecule_path(p, q);
+        if (!q.result) s.record_search(p, q);
+    }
+    s.write(d, b, im, p, q, size_equal);
 }
 
 }  // namespace

@@ -1,10 +1,29 @@
 // Individualise-and-refine on the graphs of graph_ids.hpp, for one workgroup of 256 threads per image: what the environment similarity
 // (graph_sim.hip), the identity test (graph_ident.hip) and the canonical order (graph_canon.hip) share, so that the three cannot drift
 // apart -- a bond row as a thread holds it, stage (A) (degrees, the numbering of a record's bonded atoms, id_0), the round in its two
-// halves, the id of an individualised atom, the workgroup reduction, and the exact class count through an LDS table.
+// halves, the id of an individualised atom, the workgroup reduction, the exact class count through an LDS table, and the pieces of the
+// SEARCH that the identity and the canonical order both run: the rounds of a level, the replay of a path, the cell and its members.
 //
-// Every piece is a function that works on the caller's LDS arrays.  None but block_reduce, refine_number_rec (its scan), refine_classes
-// and refine_multiset_sum (their reductions) synchronises: the callers place the barriers, and say why there.
+// Every piece is a function that works on the caller's LDS arrays; none branches on which kernel calls it.  Stage (A) and the halves of
+// the round do not synchronise: the callers place the barriers, and say why there.  The pieces that do synchronise say so in their
+// comment: block_reduce, refine_number_rec (its scan), refine_classes and refine_multiset_sum (their reductions), and of the search
+// refine_replay, refine_cell and cell_member; refine_level and refine_rounds hold only the barriers of the `round` and `classes` they
+// are given.
+//
+// STILL WRITTEN IN BOTH SEARCH KERNELS, and why:
+//   - "the multiset of the mapped rows equals the multiset of the rows, by counting" (Ident::verify, Canon::map_onto_best).  The
+//     canonical order maps a graph onto ITSELF, so one loop reads every row once for both counts; the identity has two sides and reads
+//     the molecule's rows before q, then the record's.  One function over two row readers and a map (one loop, the second side first,
+//     the first side's row under `q2 < q`) was measured: the identity's reads stay, but the canonical order's row reader branches on
+//     its side, the two reads of a row are not merged, and the launch on the trained fixture took 55.1 us for 49.2 (plain, `raw`),
+//     63.4 for 57.9 (`peaks`), 170 propanes at capacity 31.5 ms for 29.5 (profiles/r29_graph_search.md).  The identity's two-loop form
+//     for both would read every row of the canonical order 1.5 times.  So each kernel keeps its loop; they state the same test.
+//   - the map of a leaf onto the other colouring by equal id.  The identity scans (quadratic, no table: its leaf is met once per image),
+//     the canonical order looks the ids up in the class table (one leaf per automorphism).  Two algorithms with two costs, not one
+//     piece written twice; id_table_put / id_table_find below are the table's only insert and lookup.
+//   - what a level records and what is done with it: the identity records the molecule's trace and demands it of the record, the
+//     canonical order compares the trace of the path with the best leaf's.  The order of the search (one path and a depth-first match
+//     against all the tree with orbit pruning) is what makes them two kernels.
 #pragma once
 #include "block_scan.hpp"
 #include "mol_rows.hpp"
@@ -154,10 +173,45 @@ __device__ __forceinline__ void refine_finish(int tid, u64* id, u64* acc, int n,
     }
 }
 
-// ---- The number of distinct ids, exactly: every id goes into an open-addressed table of SLOTS >= 2 n slots (64-bit LDS
-// compare-and-swap; 0 marks a free slot, so the ids that ARE 0 are counted apart), and the ids that found a free slot are counted -- as
-// many as there are distinct values, in any order of the threads.  An id that finds itself there is shared by two atoms: `shared` keeps
-// this thread's least such id, `zeros` (uniform) the number of ids that are 0, for the cell of the level.  wi = LDS scratch [REFINE_NW]
+// ---- An open-addressed table of ids in LDS: SLOTS (a power of two) 64-bit words, 0 marks a free slot, so an id that IS 0 is never
+// put (the callers count it apart).  id_table_put inserts e by compare-and-swap, in any order of the threads: slot >= 0 and fresh when
+// e took a free slot, slot >= 0 and not fresh when e was there already (two atoms share it), slot < 0 when no slot was free (a table at
+// most half full always has one).  id_table_find, after a barrier behind the puts: the slot that holds e, or -1.  Neither synchronises.
+// The probe loops are not unrolled: the first probe nearly always ends them, and unrolled (the compiler's choice for a loop that
+// returns) they add 2 KB of cold code per kernel and 1 % to a launch of the canonical order (profiles/r29_graph_search.md)
+struct TableSlot {
+    int slot;
+    bool fresh;
+};
+template <int SLOTS>
+__device__ __forceinline__ TableSlot id_table_put(u64* table, u64 e) {
+    unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
+#pragma unroll 1
+    for (int probe = 0; probe < SLOTS; ++probe) {
+        const u64 old = atomicCAS(&table[slot], 0ull, e);
+        if (old == 0 || old == e) return {(int)slot, old == 0};
+        slot = (slot + 1) & (SLOTS - 1);
+    }
+    return {-1, false};
+}
+template <int SLOTS>
+__device__ __forceinline__ int id_table_find(const u64* table, u64 e) {
+    unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
+#pragma unroll 1
+    for (int probe = 0; probe < SLOTS; ++probe) {
+        const u64 at = table[slot];
+        if (at == e) return (int)slot;
+        if (at == 0) break;
+        slot = (slot + 1) & (SLOTS - 1);
+    }
+    return -1;
+}
+
+// ---- The number of distinct ids, exactly: every id goes into the table of SLOTS >= 2 n slots (the ids that ARE 0 are counted apart),
+// and the ids that found a free slot are counted -- as many as there are distinct values, in any order of the threads.  An id that
+// finds itself there is shared by two atoms: `shared` keeps this thread's least such id, `zeros` (uniform) the number of ids that are
+// 0, for the cell of the level (refine_cell).  wi = LDS scratch [REFINE_NW].  Barriers: one behind the clearing of the table, and the
+// reduction's two (the first of them is behind every put)
 template <int SLOTS>
 __device__ __forceinline__ int refine_classes(int tid, const u64* id, int n, u64* table, int* wi, u64& shared, int& zeros) {
     for (int k = tid; k < SLOTS; k += REFINE_GT) table[k] = 0;
@@ -170,19 +224,10 @@ __device__ __forceinline__ int refine_classes(int tid, const u64* id, int n, u64
             ++zero;
             continue;
         }
-        unsigned slot = (unsigned)(e >> 32) & (SLOTS - 1);
-        for (int probe = 0; probe < SLOTS; ++probe) {      // (n <= SLOTS / 2 ids: a free slot is always found)
-            const u64 old = atomicCAS(&table[slot], 0ull, e);
-            if (old == 0) {
-                ++fresh;
-                break;
-            }
-            if (old == e) {
-                shared = min(shared, e);
-                break;
-            }
-            slot = (slot + 1) & (SLOTS - 1);
-        }
+        const TableSlot at = id_table_put<SLOTS>(table, e);      // (n <= SLOTS / 2 ids: a free slot is always found)
+        if (at.slot < 0) continue;
+        if (at.fresh) ++fresh;
+        else shared = min(shared, e);
     }
     const int both = block_reduce(fresh + (zero << 16), wi, [](int u, int v) { return u + v; });
     zeros = both >> 16;
@@ -193,4 +238,79 @@ __device__ __forceinline__ u64 refine_multiset_sum(int tid, const u64* id, int n
     u64 s = 0;
     for (int a = tid; a < n; a += REFINE_GT) s += mix(id[a]);
     return block_reduce(s, wu, [](u64 u, u64 v) { return u + v; });
+}
+
+// ---- The search of graph_ident.hip and graph_canon.hip.  `round(r)` runs round r on the caller's ids, both halves and their two
+// barriers; `classes()` is the caller's refine_classes.  rounds / max_rounds: the image's count of rounds and its budget, checked BEFORE
+// every round, replays included; r: the number of the round, which counts on through the levels of a path.
+//
+// The rounds of one level: until one no longer raises the class count (that round is counted), at most n.  prev: the class count the
+// first round has to beat.  out: the budget ran out before round `rounds + 1` of the level; classes is then the count after the last
+// round that ran (0: none ran)
+struct LevelRun {
+    int rounds, classes;
+    bool out;
+};
+template <class Round, class Classes>
+__device__ __forceinline__ LevelRun refine_level(int n, int prev, int& rounds, int max_rounds, u64& r, Round round, Classes classes) {
+    int k = 0, c = 0;
+    while (true) {
+        if (rounds >= max_rounds) return {k, c, true};
+        ++rounds, ++r, ++k;
+        round(r);
+        c = classes();
+        if (c <= prev || k >= n) break;
+        prev = c;
+    }
+    return {k, c, false};
+}
+// `todo` recorded rounds, no class count between them; false: out of rounds
+template <class Round>
+__device__ __forceinline__ bool refine_rounds(int todo, int& rounds, int max_rounds, u64& r, Round round) {
+    for (int i = 0; i < todo; ++i) {
+        if (rounds >= max_rounds) return false;
+        ++rounds, ++r;
+        round(r);
+    }
+    return true;
+}
+// Replay: the ids after the rounds of level `upto` under choice[0 .. upto) -- id from init, r from 0, then for every level its
+// recorded rounds lv_rounds[k] and, below `upto`, its choice individualised (no id snapshots in LDS).  false: out of rounds.
+// Barriers: one behind the copy of init (the first round reads every id), one behind every individualisation (tid 0 writes it, the
+// next round reads it)
+template <class K, class C, class Round>
+__device__ __forceinline__ bool refine_replay(int tid, u64* id, const u64* init, int n, int upto, const K* lv_rounds, const C* choice, int& rounds,
+                                              int max_rounds, u64& r, Round round) {
+    for (int a = tid; a < n; a += REFINE_GT) id[a] = init[a];
+    __syncthreads();
+    r = 0;
+    for (int k = 0; k <= upto; ++k) {
+        if (!refine_rounds(lv_rounds[k], rounds, max_rounds, r, round)) return false;
+        if (k < upto) {
+            if (tid == 0) id[choice[k]] = indiv(id[choice[k]], k);
+            __syncthreads();
+        }
+    }
+    return true;
+}
+
+// The cell of a level that is not discrete: the non-singleton class of the least id VALUE (invariant under renumbering) -- the least id
+// two atoms share, 0 when more than one id is 0.  shared, zeros: of the refine_classes that counted this colouring.  Uniform.
+// wu = LDS scratch [REFINE_NW].  Barriers: the reduction's two
+__device__ __forceinline__ u64 refine_cell(u64 shared, int zeros, u64* wu) {
+    const u64 least = block_reduce(shared, wu, [](u64 u, u64 v) { return min(u, v); });
+    return zeros > 1 ? 0 : least;
+}
+// The first (LAST: the last) atom at or past `from` whose id is `cell` and for which pred(atom) holds; none: n (LAST: -1).  Uniform.
+// wi = LDS scratch [REFINE_NW].  Barriers: the reduction's two, so an id written before the call is read by every thread
+template <bool LAST, class P>
+__device__ __forceinline__ int cell_member(int tid, const u64* id, int n, u64 cell, int from, int* wi, P pred) {
+    int at = LAST ? -1 : n;
+    for (int a = tid; a < n; a += REFINE_GT)
+        if (a >= from && id[a] == cell && pred(a)) at = LAST ? max(at, a) : min(at, a);
+    return block_reduce(at, wi, [](int u, int v) { return LAST ? max(u, v) : min(u, v); });
+}
+template <bool LAST>
+__device__ __forceinline__ int cell_member(int tid, const u64* id, int n, u64 cell, int from, int* wi) {
+    return cell_member<LAST>(tid, id, n, cell, from, wi, [](int) { return true; });
 }

@@ -14,7 +14,8 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            refine_equal and exact (InferenceRunner(score_graphs=True, score_similarity=True), one step, csrc/graph_sim.hip), and
            step() with score_graphs=True against the same with score_similarity=True as well (as `step`)
 
-  identity abc_graph_identity_update alone beside abc_graph_similarity_update (as `launch`); the fixture's verified `same` between
+  identity abc_graph_identity_update alone beside abc_graph_similarity_update (as `launch`; with --parent-lib also the parent commit's
+           build of the launch on the same descriptor); the fixture's verified `same` between
            `exact` and `refine_equal` with `undecided` and the largest levels / tries / rounds of an image
            (InferenceRunner(score_graphs=True, score_similarity=True, score_identity=True), one step, csrc/graph_ident.hip); and
            step() with score_graphs=True, score_similarity=True against the same with score_identity=True as well (as `text`'s
@@ -47,8 +48,8 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
            --isomeric: the canonical ISOMERIC form (csrc/stereo.hip and the stereo instantiation of csrc/graph_canon.hip,
            InferenceRunner(smiles=True, smiles_isomeric=True)) under BOTH omega rules in this one process -- abc_perceive_stereo
            alone, abc_canonical_order_stereo beside abc_canonical_order, the writer with both marks and with the double-bond marks
-           alone (with --parent-lib also the parent commit's build of the plain search, the perception and both writers, each on
-           the same descriptor), the step with and without, the fixture's stereo elements and third-key counters, smiles() against
+           alone (with --parent-lib also the parent commit's build of the plain and the stereo search, the perception and both
+           writers, each on the same descriptor), the step with and without, the fixture's stereo elements and third-key counters, smiles() against
            Molecule.smiles(isomeric=True).  Writes what it measured to profiles/r24_isomeric.md
 
   aromatize (or --aromatize beside other parts): the aromaticity perception (csrc/aromatic.hip, InferenceRunner(aromatize=True)) under
@@ -68,7 +69,7 @@ frozen trained fixture (tests/golden/trained_unet_state.npz) on drawn_molecules(
 
 One JSON line per measurement, each naming the rule.
 
-    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--double-bonds] [--canonical] [--aromatize] [--isomeric [--parent-lib PATH]] [--records-from-smiles]
+    python profiles/tools/assemble_step.py [--steps 40] [--warmup 5] [--parts step,launch,host,graphs,score,similarity,identity,text,smiles] [--omega-rule raw] [--stereo] [--double-bonds] [--canonical] [--aromatize] [--isomeric] [--parent-lib PATH] [--records-from-smiles]
 """
 import argparse
 import json
@@ -493,6 +494,7 @@ def part_smiles_isomeric(m, x, steps, warmup, parent_lib=None, iters=200):
     if parent_lib:
         parent = C.CDLL(parent_lib)
         parent.abc_canonical_order.restype, parent.abc_canonical_order.argtypes = C.c_int, [C.POINTER(L.CanonDesc), C.c_void_p]
+        parent.abc_canonical_order_stereo.restype, parent.abc_canonical_order_stereo.argtypes = C.c_int, [C.POINTER(L.CanonStereoDesc), C.c_void_p]
         parent.abc_perceive_stereo.restype, parent.abc_perceive_stereo.argtypes = C.c_int, [C.POINTER(L.StereoDesc), C.c_void_p]
         parent.abc_write_smiles_ez.restype, parent.abc_write_smiles_ez.argtypes = C.c_int, [C.POINTER(L.SmilesEzDesc), C.c_void_p]
 
@@ -540,7 +542,8 @@ def part_smiles_isomeric(m, x, steps, warmup, parent_lib=None, iters=200):
 
         def of_parent(entry, d):
             return (lambda: L.check(getattr(parent, entry)(C.byref(d), current_stream()), "parent " + entry)) if parent else None
-        beside = {"perceive_stereo": of_parent("abc_perceive_stereo", cz.perceiver.d), "smiles_both_marks": of_parent("abc_write_smiles_ez", r.smiler.d),
+        beside = {"canonical_order_stereo": of_parent("abc_canonical_order_stereo", cz.d),
+                  "perceive_stereo": of_parent("abc_perceive_stereo", cz.perceiver.d), "smiles_both_marks": of_parent("abc_write_smiles_ez", r.smiler.d),
                   "smiles_double_bonds": of_parent("abc_write_smiles_ez", ez.d)}
         us = [(launch_us(cz.perceiver.run, iters), launch_us(order_only, iters), launch_us(plain.canonicalizer.run, iters),
                launch_us(parent_order, iters) if parent else None, launch_us(r.smiler.run, iters), launch_us(plain.smiler.run, iters),
@@ -738,17 +741,29 @@ def part_similarity(rs, steps, warmup, iters=200):
               diff_name="similarity_minus_score_ms")
 
 
-def part_identity(rs, steps, warmup, iters=200):
+def part_identity(rs, steps, warmup, parent_lib=None, iters=200):
+    import ctypes as C
+    from abcnet_amd import _lib as L
     from abcnet_amd._lib import GRAPH_IDENT_COLUMNS
+    from abcnet_amd.contract import current_stream
     with_id, without = "assemble+evaluate+score+similarity+identity", "assemble+evaluate+score+similarity"
     r = rs[with_id]
     ident, sim = r.identity, r.similarity
     keep = ident.totals.clone(), sim.totals.clone()
-    us = [(launch_us(ident.run, iters), launch_us(sim.run, iters)) for _ in range(3)]      # the two launches alternated, three figures each
+    parent_run = None
+    if parent_lib:      # the parent commit's build of the launch on this build's descriptor, alternated with this build's
+        parent = C.CDLL(parent_lib)
+        parent.abc_graph_identity_update.restype, parent.abc_graph_identity_update.argtypes = C.c_int, [C.POINTER(type(ident.d)), C.c_void_p]
+
+        def parent_run():
+            L.check(parent.abc_graph_identity_update(C.byref(ident.d), current_stream()), "parent graph_identity_update")
+    us = [(launch_us(ident.run, iters), launch_us(sim.run, iters), launch_us(parent_run, iters) if parent_run else None)
+          for _ in range(3)]      # the launches alternated, three figures each
     ident.totals.copy_(keep[0])
     sim.totals.copy_(keep[1])
-    emit({"part": "identity", "what": "launch", "batch": B, "us_per_launch": [round(a, 2) for a, _ in us],
-          "graph_similarity_us_per_launch": [round(b, 2) for _, b in us],
+    emit({"part": "identity", "what": "launch", "batch": B, "us_per_launch": [round(a, 2) for a, _, _ in us],
+          "graph_similarity_us_per_launch": [round(b, 2) for _, b, _ in us],
+          "parent_build_us_per_launch": [round(c, 2) for _, _, c in us] if parent_run else None,
           "method": "device events around %d back-to-back launches (launch gaps included)" % iters})
     r.reset_evaluation()
     r.step()
@@ -893,7 +908,7 @@ def main():
     ap.add_argument("--canonical", action="store_true", help="the smiles part: the canonical atom order, under both omega rules")
     ap.add_argument("--aromatize", action="store_true", help="the aromatize part: the aromaticity perception, under both omega rules")
     ap.add_argument("--isomeric", action="store_true", help="the smiles part: the canonical isomeric form, under both omega rules")
-    ap.add_argument("--parent-lib", default=None, help="--isomeric: a libabcnet_hip.so of the parent commit, whose abc_canonical_order is timed beside")
+    ap.add_argument("--parent-lib", default=None, help="--isomeric, --parts identity: a libabcnet_hip.so of the parent commit, whose launches are timed beside this build's")
     ap.add_argument("--records-from-smiles", action="store_true",
                     help="the annotation records as SMILES strings: abc_read_smiles and load_smiles against parse_smiles + load_graphs")
     a = ap.parse_args()
@@ -924,7 +939,7 @@ def main():
     if "similarity" in parts:
         part_similarity(ss, a.steps, a.warmup)
     if "identity" in parts:
-        part_identity(ss, a.steps, a.warmup)
+        part_identity(ss, a.steps, a.warmup, parent_lib=a.parent_lib)
     if "text" in parts:
         part_text(m, x, a.steps, a.warmup)
     if "smiles" in parts:

@@ -162,13 +162,51 @@ def test_symmetric_graphs_equal_the_oracle():
     assert torch.equal(cert[:6], cert[6:])                            # a renumbered copy: the same relabelled graph
 
 
-@pytest.mark.parametrize("budgets", [dict(max_tries=1), dict(max_rounds=1)])
-def test_tiny_budgets_end_undecided(budgets):
-    """benzene beside a pair that needs one round and no try: a budget is an image's own, and the order is the oracle's"""
-    mols = [so.as_mol(co.BENZENE), so.mol([1, 2], [(1, 2, 1)])]
-    rows = _check(_mol_op(mols, **budgets), [co.molecule_image(m) for m in mols], mols, **budgets)
-    assert rows[0]["status"] == co.UNDECIDED and rows[0]["leaves"] == 0
-    assert rows[1]["status"] == 0 and rows[1]["leaves"] == 1 and rows[1]["rounds"] == 1
+def _check_stereo(mols, cap_atoms=64, cap_mol_bonds=96, **budgets):
+    """abc_canonical_order_stereo on molecules without a stereo element: the element table is all none, order, stats, key, certificate
+    and rows are those of the plain search (_check) and the stereo_search row is the host form's; returns (rows, stereo_search rows)"""
+    from abcnet_amd import decode as D
+    op = GraphCanonicalizer(*_upload(mols, cap_atoms, cap_mol_bonds), cert=True, stereo=True, **budgets)
+    op.search.fill_(77)
+    rows = _check(op, [co.molecule_image(m) for m in mols], mols, **budgets)
+    table = op.stereo_elements()
+    for b, m in enumerate(mols):
+        assert table[b, :len(m["atoms"])].tolist() == [list(D.STEREO_NONE_ROW)] * len(m["atoms"]), b
+    search = op.search.cpu().tolist()
+    tries, rounds = budgets.get("max_tries", D.CANON_DEFAULT_TRIES), budgets.get("max_rounds", D.CANON_DEFAULT_ROUNDS)
+    assert search == [D.canonical_labelling(co.of_molecule(m), tries, rounds, stereo=[D.STEREO_NONE_ROW] * len(m["atoms"]))[3] for m in mols]
+    return rows, search
+
+
+# a budget that runs out AFTER a best leaf exists, inside a replay or a later level: the order written is the best leaf so far
+LATE = [(dict(max_tries=3), 8, dict(leaves=2, tries=3, rounds=17, automorphisms=1)), (dict(max_rounds=12), 6, dict(leaves=2, rounds=12))]
+
+
+@pytest.mark.parametrize("budgets, ring, want", [(dict(max_tries=1), 0, dict(leaves=0)), (dict(max_rounds=1), 0, dict(leaves=0))] + LATE,
+                         ids=["budgets0", "budgets1", "budgets2", "budgets3"])      # (the ids the first two cases have always had)
+def test_tiny_budgets_end_undecided(budgets, ring, want):
+    """benzene (ring 0), or under a LATE budget its ring of carbons, beside a pair that needs one round and no try: a budget is an
+    image's own, and the order is the oracle's -- the identity order before any leaf, the best leaf so far after one (those on both
+    sides)"""
+    first = co.BENZENE if ring == 0 else _norm(io.carbon_ring(ring))
+    recs = [first, so.record([1, 2], [(0, 1, 1)])]
+    mols = [so.as_mol(first), so.mol([1, 2], [(1, 2, 1)])]
+    sides = [_check(_mol_op(mols, **budgets), [co.molecule_image(m) for m in mols], mols, **budgets)]
+    if ring:
+        sides.append(_check(_rec_op(recs, **budgets), [co.record_image(r) for r in recs], **budgets))
+    for rows in sides:
+        assert rows[0]["status"] == co.UNDECIDED and {k: rows[0][k] for k in want} == want
+        assert rows[1]["status"] == 0 and rows[1]["leaves"] == 1 and rows[1]["rounds"] == 1
+
+
+@pytest.mark.parametrize("budgets, ring, want", LATE)
+def test_late_budgets_end_undecided_in_the_stereo_search(budgets, ring, want):
+    """the same two rings through abc_canonical_order_stereo with an element table that is all none, each beside the image that
+    finishes: the plain search's answer, and the one automorphism is a stereo automorphism"""
+    mols = [so.as_mol(_norm(io.carbon_ring(ring))), so.mol([1, 2], [(1, 2, 1)])]
+    rows, search = _check_stereo(mols, **budgets)
+    assert rows[0]["status"] == co.UNDECIDED and {k: rows[0][k] for k in want} == want and search[0] == [0, 0, 1, 0]
+    assert rows[1]["status"] == 0 and rows[1]["leaves"] == 1 and rows[1]["rounds"] == 1 and search[1] == [0, 0, 0, 0]
 
 
 @pytest.mark.parametrize("name, rec", [("ring", io.carbon_ring(512)), ("chain", io.carbon_chain(512)), ("propanes", io.propanes(170))])
@@ -195,6 +233,10 @@ def test_more_molecule_rows_than_threads():
     rows = _check(op, [co.molecule_image(mol)], [mol])
     assert rows[0]["status"] == 0 and rows[0]["leaves"] == 3 and rows[0]["tries"] == 5 and rows[0]["rounds"] == 700
     assert op.rows().tensors[0].cpu().tolist() == [[257, 257, 0, 0]]
+    # the same rows through the stereo entry, the element table all none: the same order, key and stats
+    rows, search = _check_stereo([mol], 512, 512)
+    assert rows[0]["status"] == 0 and rows[0]["leaves"] == 3 and rows[0]["tries"] == 5 and rows[0]["rounds"] == 700
+    assert search == [[0, 0, 2, 0]]
 
 
 # --------------------------------------------------------------------------------------------------------- renumbered uploads

@@ -134,9 +134,14 @@ def test_hand_made_rows_equal_the_oracle():
 
 @pytest.mark.parametrize("budgets, want", [(dict(max_tries=1), [1, 0, 0, 1, 0, 0, 1, 5, 1, 1, 25]),
                                            (dict(max_rounds=20), [1, 0, 0, 1, 0, 0, 1, 5, 1, 0, 20]),
-                                           (dict(max_rounds=3), [1, 0, 0, 1, 0, 0, 1, 0, 0, 0, 3])])
+                                           (dict(max_rounds=3), [1, 0, 0, 1, 0, 0, 1, 0, 0, 0, 3]),
+                                           (dict(max_rounds=24), [1, 0, 0, 1, 0, 0, 1, 5, 1, 1, 24]),
+                                           (dict(max_rounds=33), [1, 0, 0, 1, 0, 0, 1, 5, 3, 2, 33])])
 def test_tiny_budgets_end_undecided(budgets, want):
-    """the backtracking fixture beside a pair that needs one round per side and no try: a budget is an image's own"""
+    """the backtracking fixture beside a pair that needs one round per side and no try: a budget is an image's own.  The last two end
+    inside the record's search after a backtrack (graphident_oracle.identify: 23 rounds are run when the first backtrack comes, the
+    third try is made by round 31, the fourth at 35): 24 one round into the replay behind the first backtrack, 33 in the rounds of a
+    level behind the second"""
     mols, recs = [so.as_mol(io.UNION_PERMUTED), so.mol([1, 2], [(1, 2, 1)])], [io.UNION, so.record([2, 1], [(0, 1, 1)])]
     rows = _check(_op(mols, recs, **budgets), mols, recs, **budgets)
     assert [rows[0][c] for c in io.COLUMNS] == want
