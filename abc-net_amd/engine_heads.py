@@ -365,6 +365,7 @@ class HeadsPlan:
         wide = Rec(bname="out_modules.*.bn", y=self.hfeat, ld=128 * nh, coff=0, cout=128 * nh, H=h, W=w, scale=sc, shift=sh, slopes=sl,
                    mean=self.hmean, invstd=self.hinvstd)
         part, nblk = self._act_bwd(ops, wide, (dfeat, 128 * nh, 0), None, g.data_ptr(), 128 * nh, self._heads_drop())
+        self.heads_dfeat, self.heads_g = dfeat, g      # (handles for the in-situ parity tests)
         return (g, part, nblk), dfeat
 
     def _heads_conv1_wgrad_per_head(self, ops, merged, dfeat, dyh, taps):
