@@ -276,6 +276,11 @@ class ScanCleanDesc(C.Structure):
                 ("keep_q8", i32)]
 
 
+class ScanSplitDesc(C.Structure):
+    _fields_ = [("scratch", vp), ("pages", vp), ("drawings", vp), ("total", vp), ("labels_out", vp), ("canvas_out", vp),
+                ("canvases", i32), ("max_per_page", i32), ("cell", i32), ("reach", i32), ("min_ink", i32), ("keep_q8", i32)]
+
+
 class StrokeDesc(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("B", i32), ("S", i32), ("drop_isolated", i32), ("max_iter", i32), ("radius", i32),
                 ("skip_stride", i32), ("skip", vp), ("stats", vp)]
@@ -309,6 +314,11 @@ SCAN_NO_COMPONENT, SCAN_CLEAN_FAILED = 4, 8     # abc_scan_clean_status: further
 SCAN_CLEAN_CELLS = (8, 16, 32, 64)              # the values of abc_scan_clean_desc.cell
 # the abc_scan_clean_stat columns of abc_scan_clean_desc.stats
 SCAN_CLEAN_COLUMNS = ("components", "kept", "ink_kept", "ink_dropped", "heaviest", "occupied_cells")
+SCAN_SPLIT_PAGE_FULL, SCAN_SPLIT_BATCH_FULL = 16, 32    # abc_scan_split_status: further bits of a page's status
+SCAN_SPLIT_MAX_PER_PAGE, SCAN_SPLIT_MAX_REACH = 64, 4   # ABC_SCAN_SPLIT_MAX_PER_PAGE, ABC_SCAN_SPLIT_MAX_REACH
+# the abc_scan_page_stat columns of abc_scan_split_desc.pages and the abc_scan_drawing columns of .drawings
+SCAN_PAGE_COLUMNS = ("status", "groups", "kept", "first", "taken", "ink_kept", "ink_dropped", "occupied_cells")
+SCAN_DRAWING_COLUMNS = ("page", "label", "weight", "rank_in_page")
 STROKE_UNTIL_STABLE = -1    # ABC_STROKE_UNTIL_STABLE: abc_stroke_desc.max_iter
 STROKE_MAX_SIZE = 1024      # ABC_STROKE_MAX_SIZE: the largest canvas abc_normalize_strokes holds in LDS
 # the abc_stroke_stat columns of abc_stroke_desc.stats
@@ -347,7 +357,7 @@ SELF_SIZED_SINCE = [(StrokeDesc, "abc_stroke_desc_size"), (GraphIdentityDesc, "a
                     (SmilesStereoDesc, "abc_smiles_stereo_desc_size"), (CanonDesc, "abc_canon_desc_size"),
                     (AromaticDesc, "abc_aromatic_desc_size"), (SmilesEzDesc, "abc_smiles_ez_desc_size"),
                     (StereoDesc, "abc_stereo_desc_size"), (CanonStereoDesc, "abc_canon_stereo_desc_size"),
-                    (SmilesReadDesc, "abc_smiles_read_desc_size")]
+                    (SmilesReadDesc, "abc_smiles_read_desc_size"), (ScanSplitDesc, "abc_scan_split_desc_size")]
 
 # every symbol include/abcnet_hip.h declares: name -> (restype, argtypes)
 P = C.POINTER
@@ -422,6 +432,9 @@ SYMBOLS = {
     "abc_build_scan_images_clean": (C.c_int, [P(ScanDesc), P(ScanCleanDesc), vp]),
     "abc_scan_clean_desc_size": (C.c_int, []),
     "abc_scan_clean_scratch_bytes": (i64, [i32, i32, i32, i32]),
+    "abc_split_scan_pages": (C.c_int, [P(ScanDesc), P(ScanSplitDesc), vp]),
+    "abc_scan_split_desc_size": (C.c_int, []),
+    "abc_scan_split_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
     "abc_normalize_strokes": (C.c_int, [P(StrokeDesc), vp]),
     "abc_stroke_desc_size": (C.c_int, []),
     "abc_metrics_blocks": (C.c_int, [P(MetricsDesc)]),

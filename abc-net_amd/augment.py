@@ -437,6 +437,191 @@ class ScanBuilder:
         return scan_record_offsets(*(int(g[c]) for c in ("y0", "x0", "bh", "bw", "rows", "cols", "ddx", "ddy")))
 
 
+def scan_page_positions(offsets, xy):
+    """the inverse of scan_record_offsets: canvas positions xy [..., 2] (x indexes rows, y columns, as everywhere here) back
+    into SOURCE coordinates, float64 -- x_src = (x - ddx') / scale_x, y_src = (y - ddy') / scale_y"""
+    scale_x, scale_y, ddx, ddy = offsets
+    xy = np.asarray(xy, dtype=np.float64)
+    if xy.shape[-1:] != (2,):
+        raise ValueError("scan_page_positions: positions are [..., 2] (x, y), got shape %s" % (xy.shape,))
+    return (xy - np.array([ddx, ddy], dtype=np.float64)) / np.array([scale_x, scale_y], dtype=np.float64)
+
+
+# the cell and the reach PageSplitter uses when none is given: the pair that merged no drawing with its caption and, among those,
+# left the most drawings whole on the composed pages of profiles/r27_page_split.md (profiles/tools/page_split_step.py)
+DEFAULT_SPLIT_CELL, DEFAULT_SPLIT_REACH = 32, 3
+
+
+class PageSplitter:
+    """page scans into their drawings, one f32 canvas [1, size, size] each, on the device (csrc/scan.hip; the contract:
+    include/abcnet_hip.h, abc_scan_split_desc, and DESIGN.md section 7).  `pages` grey pages per load, `canvases` canvases per
+    run: `out` is [canvases, 1, size, size] and may be an InferenceRunner.input_images of batch `canvases`.  Per page the
+    threshold, the polarity and the cells are ScanBuilder's; occupied cells within `reach` cells of each other (Chebyshev
+    distance) are one group, a group is kept when it has at least min_ink ink pixels and keep / 256 of the page's heaviest, a
+    page's kept groups are its drawings in the reading order of their first cells, at most max_per_page of them, and the
+    drawings of all pages fill the canvases in order without holes; each is cropped by its own box and fitted as ScanBuilder
+    fits.  Unused canvases are blank with status L.SCAN_NO_COMPONENT.  `total` is a device int32 [2] (canvases written, kept
+    groups of all pages); `n_canvases` is its first word as a [1] view, the format of InferenceRunner.n_valid:
+    runner.n_valid.copy_(splitter.n_canvases) needs no sync.  A page that held more than max_per_page groups carries
+    L.SCAN_SPLIT_PAGE_FULL in its status, a page that lost a drawing to `canvases` L.SCAN_SPLIT_BATCH_FULL.  No CPU fallback.
+
+    cell and reach default to DEFAULT_SPLIT_CELL and DEFAULT_SPLIT_REACH (32 and 3; a first guess was 32 and 2), the measured
+    choice of profiles/r27_page_split.md: pages composed on the host from synthetic drawings with white gutters and a caption
+    under each, because no real page was available.  Those drawings are sparse, and no pair tried kept all of them whole: a
+    page of known layout deserves a cell and reach of its own (reach * cell is about the gap, in pixels, that still joins).  Not covered: drawings that touch (one group), a caption within reach of its drawing (joins it), deskewing, and
+    pages whose Otsu threshold takes a ground or a frame for ink."""
+
+    def __init__(self, pages, canvases, size, out=None, max_src=(2048, 2048), max_per_page=16, cell=None, reach=None, min_ink=0,
+                 keep=0, margin=None, cover=None, polarity="dark", device="cuda", debug_cells=False):
+        if polarity not in POLARITIES:
+            raise ValueError("PageSplitter: polarity must be 'dark', 'light' or 'auto', got %r" % (polarity,))
+        cell = DEFAULT_SPLIT_CELL if cell is None else cell
+        reach = DEFAULT_SPLIT_REACH if reach is None else reach
+        if isinstance(cell, bool) or cell not in L.SCAN_CLEAN_CELLS:
+            raise ValueError("PageSplitter: cell must be one of %s, got %r" % (L.SCAN_CLEAN_CELLS, cell))
+        if isinstance(reach, bool) or int(reach) != reach or not 1 <= reach <= L.SCAN_SPLIT_MAX_REACH:
+            raise ValueError("PageSplitter: reach is a distance in cells, 1 .. %d, got %r" % (L.SCAN_SPLIT_MAX_REACH, reach))
+        if isinstance(max_per_page, bool) or int(max_per_page) != max_per_page or not 1 <= max_per_page <= L.SCAN_SPLIT_MAX_PER_PAGE:
+            raise ValueError("PageSplitter: max_per_page must be 1 .. %d, got %r" % (L.SCAN_SPLIT_MAX_PER_PAGE, max_per_page))
+        if int(min_ink) != min_ink or min_ink < 0 or min_ink >= 2 ** 31:
+            raise ValueError("PageSplitter: min_ink is a count of ink pixels, an integer >= 0, got %r" % (min_ink,))
+        if int(keep) != keep or not 0 <= keep <= 256:
+            raise ValueError("PageSplitter: keep is in 1 / 256 of the heaviest group, 0 .. 256, got %r" % (keep,))
+        S = int(size)
+        if S < 8 or S % 8 or S > 8192:
+            raise ValueError("PageSplitter: size must be a multiple of 8 (8 .. 8192), got %d" % S)
+        max_h, max_w = int(max_src[0]), int(max_src[1])
+        if not (1 <= max_h <= 4096 and 1 <= max_w <= 4096):
+            raise ValueError("PageSplitter: sources are at most 4096 x 4096, got max_src %s" % ((max_h, max_w),))
+        if not 1 <= pages <= 65535:
+            raise ValueError("PageSplitter: pages must be 1 .. 65535, got %d" % pages)
+        if not 1 <= canvases <= 65535:
+            raise ValueError("PageSplitter: canvases must be 1 .. 65535, got %d" % canvases)
+        margin = S * 20 // 512 if margin is None else int(margin)
+        cover = DEFAULT_COVER_Q8 if cover is None else int(cover)
+        if not 0 <= 2 * margin < S:
+            raise ValueError("PageSplitter: 0 <= 2 * margin < size, got margin %d at size %d" % (margin, S))
+        if not 0 <= cover <= 256:
+            raise ValueError("PageSplitter: cover is in 1 / 256, 0 .. 256, got %d" % cover)
+        if not torch.cuda.is_available():
+            raise L.AbcNetHipError("PageSplitter needs an MI355X; abcnet_amd has no CPU fallback")
+        P, D, cell = int(pages), int(canvases), int(cell)
+        shape = (D, 1, S, S)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float32, device=device)
+        if tuple(out.shape) != shape:
+            raise L.AbcNetHipError("PageSplitter: out %s does not match the contract %s (a %d-channel input is not an image of this "
+                                   "loader)" % (tuple(out.shape), shape, out.shape[1] if out.dim() == 4 else -1))
+        require_device_tensor(out, torch.float32, "PageSplitter: out")
+        self.lib = L.load()
+        self.out, self.P, self.D, self.S, self.margin, self.cover, self.polarity = out, P, D, S, margin, cover, polarity
+        self.max_h, self.max_w = max_h, max_w
+        self.pitch = -(-max_w // 16) * 16
+        self.cap_cells = (-(-max_h // cell), -(-self.pitch // cell))
+        dev = out.device
+        self.staging = PinnedStaging(dev, {"src": ((P, max_h, self.pitch), torch.uint8, 255), "par": ((P, L.SCAN_NPARAM), torch.int32)})
+        self.h_src, self.h_par = self.staging.host.values()
+        self.d_src, self.d_par = self.staging.dev.values()
+        self._np_src, self._np_par = self.h_src.numpy(), self.h_par.numpy()
+        self.hist = torch.zeros((P, 256), dtype=torch.int32, device=dev)                 # (uint32 bit patterns)
+        self.box = torch.zeros((D, L.SCAN_NBOX), dtype=torch.int32, device=dev)
+        self.geom = torch.zeros((D, len(L.SCAN_GEOM_COLUMNS)), dtype=torch.int32, device=dev)
+        self.page_rows = torch.zeros((P, len(L.SCAN_PAGE_COLUMNS)), dtype=torch.int32, device=dev)
+        self.drawing_rows = torch.zeros((D, len(L.SCAN_DRAWING_COLUMNS)), dtype=torch.int32, device=dev)
+        self.total = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.n_canvases = self.total[:1]
+        nbytes = self.lib.abc_scan_split_scratch_bytes(P, max_h, self.pitch, cell, D)
+        if nbytes < 0:
+            raise L.AbcNetHipError("scan_split_scratch_bytes: %s" % self.lib.abc_last_error().decode())
+        self.scratch = torch.zeros(nbytes // 4, dtype=torch.int32, device=dev)
+        d = L.ScanDesc()
+        d.out, d.src, d.params = out.data_ptr(), self.d_src.data_ptr(), self.d_par.data_ptr()
+        d.params_host = self.h_par.data_ptr()      # (what the last load staged: checked by every eager call)
+        d.src_stride, d.src_pitch, d.src_max_h = max_h * self.pitch, self.pitch, max_h
+        d.B, d.S, d.margin, d.cover_q8, d.polarity = P, S, margin, cover, POLARITIES[polarity]
+        d.hist, d.box, d.geom = self.hist.data_ptr(), self.box.data_ptr(), self.geom.data_ptr()
+        q = L.ScanSplitDesc()
+        q.scratch, q.pages, q.drawings, q.total = (self.scratch.data_ptr(), self.page_rows.data_ptr(), self.drawing_rows.data_ptr(),
+                                                   self.total.data_ptr())
+        q.canvases, q.max_per_page, q.cell, q.reach, q.min_ink, q.keep_q8 = D, int(max_per_page), cell, int(reach), int(min_ink), int(keep)
+        self.cell_labels = self.cell_canvas = None
+        if debug_cells:
+            self.cell_labels = torch.zeros((P,) + self.cap_cells, dtype=torch.int32, device=dev)
+            self.cell_canvas = torch.zeros((P,) + self.cap_cells, dtype=torch.int32, device=dev)
+            q.labels_out, q.canvas_out = self.cell_labels.data_ptr(), self.cell_canvas.data_ptr()
+        self.d, self.q = d, q
+
+    def load(self, images_u8):
+        """images_u8: `pages` 2-d uint8 arrays (decoded grey pages), each within max_src.  Host work: the checks and one memcpy
+        per page into pinned staging, then an asynchronous H2D copy."""
+        if len(images_u8) != self.P:
+            raise ValueError("expected %d images" % self.P)
+        imgs = []
+        for b, img in enumerate(images_u8):
+            img = np.asarray(img)
+            if img.dtype != np.uint8 or img.ndim != 2:
+                raise ValueError("image %d: a 2-d uint8 array, got %s %s" % (b, img.dtype, img.shape))
+            h, w = img.shape
+            if h < 1 or w < 1:
+                raise ValueError("image %d: an empty array (%d x %d)" % (b, h, w))
+            if h > self.max_h or w > self.max_w:
+                raise ValueError("image %d: %d x %d exceeds the staging capacity %d x %d" % (b, h, w, self.max_h, self.max_w))
+            imgs.append(img)
+        self.staging.wait()
+        for b, img in enumerate(imgs):
+            self._np_src[b, :img.shape[0], :img.shape[1]] = img
+            self._np_par[b] = img.shape
+        self.staging.commit()
+
+    def run(self, stream=None):
+        """ten launches in order on one stream (graph-capturable), the same number whatever the pages hold: the canvases into
+        self.out, their geometry rows, the page and drawing tables and `total` beside them"""
+        L.check(self.lib.abc_split_scan_pages(C.byref(self.d), C.byref(self.q), stream_or_current(stream, self.out.device)),
+                "split_scan_pages")
+        return self.out
+
+    @staticmethod
+    def _structured(t, columns):
+        rows = np.ascontiguousarray(t.cpu().numpy())
+        return rows.view(np.dtype([(c, np.int32) for c in columns])).reshape(rows.shape[0])
+
+    def geometry(self):
+        """the canvases' geometry rows of the last run() as a structured numpy array [canvases] with the int32 fields
+        L.SCAN_GEOM_COLUMNS; thr and inverted are the page's, ink the drawing's weight (synchronises)"""
+        return self._structured(self.geom, L.SCAN_GEOM_COLUMNS)
+
+    def pages(self):
+        """the page rows of the last run() as a structured numpy array [pages] with the int32 fields L.SCAN_PAGE_COLUMNS (status,
+        groups, kept, first, taken, ink_kept, ink_dropped, occupied_cells) (synchronises)"""
+        return self._structured(self.page_rows, L.SCAN_PAGE_COLUMNS)
+
+    def drawings(self):
+        """the drawing rows of the last run() as a structured numpy array [canvases] with the int32 fields L.SCAN_DRAWING_COLUMNS
+        (page, label, weight, rank_in_page); -1, -1, 0, -1 for an unused canvas (synchronises)"""
+        return self._structured(self.drawing_rows, L.SCAN_DRAWING_COLUMNS)
+
+    def cells(self):
+        """(labels int32, canvas int32), each [pages, cap_ch, cap_cw] over the capacity grid of cells, of the last run(): an
+        occupied cell's label is the smallest cy * cap_cw + cx of its group, the canvas the one its ink went to; -1 elsewhere
+        (synchronises).  Needs debug_cells=True"""
+        if self.cell_labels is None:
+            raise ValueError("PageSplitter: cells() needs debug_cells=True")
+        return self.cell_labels.cpu().numpy(), self.cell_canvas.cpu().numpy()
+
+    def record_offsets(self, j):
+        """(scale_x, scale_y, ddx', ddy') of canvas j after run(), by scan_record_offsets: the map of its PAGE's coordinates onto
+        the canvas, what raster.parse_record / parse_graph take (synchronises: geometry())"""
+        g = self.geometry()[j]
+        if g["status"]:
+            raise ValueError("canvas %d has no drawing (status %d)" % (j, int(g["status"])))
+        return scan_record_offsets(*(int(g[c]) for c in ("y0", "x0", "bh", "bw", "rows", "cols", "ddx", "ddy")))
+
+    def page_positions(self, j, xy):
+        """positions xy [..., 2] on canvas j (decoded atom positions: x indexes rows, y columns) back into the coordinates of its
+        page, drawings()[j]["page"]: the inverse of record_offsets(j) (synchronises)"""
+        return scan_page_positions(self.record_offsets(j), xy)
+
+
 class SampleBuilder:
     """a whole batch on the device: an ImageBuilder over owner.input_images and a TargetRasterizer over owner.targets, fed with
     the SAME draws (utils.py:42-228 for every image).  `owner` is a Trainer, or an InferenceRunner(evaluate=True) -- the loop of

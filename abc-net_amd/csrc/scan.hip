@@ -15,9 +15,12 @@
 //              writes its geometry row
 // abc_build_scan_images_clean (the contract: abc_scan_clean_desc) puts four launches between the threshold and the box -- cells,
 // union, flatten, decide, below -- and launches the box and fit+write kernels with a mask argument: nine launches, the same way.
+// abc_split_scan_pages (the contract: abc_scan_split_desc) runs the same front over pages and gives every kept group of cells a
+// canvas of its own: ten launches, at the end of this file.
 #include "common.hpp"
 #include "../../include/abcnet_hip.h"
 #include "capi_util.hpp"
+#include "block_scan.hpp"
 
 namespace {
 
@@ -175,6 +178,26 @@ struct scan_mask {
 };
 
 __device__ inline const scan_mask& mask_of(const scan_mask& k) { return k; }
+// the image whose source output b reads under a mask, and whether the ink in cell (cy, cx) of that image counts for b
+__device__ inline int mask_source(const scan_mask&, int b) { return b; }
+__device__ inline bool mask_keeps(const scan_mask& k, int b, int, int cy, int cx) {
+    const uint8_t* kr = k.keep + (size_t)b * k.stride + (size_t)cy * k.cap_cw;
+    return kr[cx];
+}
+
+// what the fit+write pass of abc_split_scan_pages reads beside abc_scan_desc: output b is a canvas, its source the page of its
+// drawings row (page 0 for an unused canvas, which reads no source), and a cell's ink counts when the cell's canvas is b
+struct split_mask {
+    const int32_t* canvas;         // [P][ncap]: the canvas of every cell of the capacity grid, -1 for none
+    const int32_t* drawings;       // [D][ABC_SCAN_NDRAWING]
+    int ncap, cap_cw, shift;
+};
+
+__device__ inline const split_mask& mask_of(const split_mask& k) { return k; }
+__device__ inline int mask_source(const split_mask& k, int b) { return max(k.drawings[(size_t)b * ABC_SCAN_NDRAWING + ABC_SCAN_D_PAGE], 0); }
+__device__ inline bool mask_keeps(const split_mask& k, int b, int page, int cy, int cx) {
+    return k.canvas[(size_t)page * k.ncap + (size_t)cy * k.cap_cw + cx] == b;
+}
 
 // launched with d alone this is the box pass of abc_build_scan_images as it always was (the same kernel arguments, the same code);
 // launched with d and a scan_mask it drops the ink outside kept cells
@@ -251,7 +274,7 @@ __host__ __device__ inline void scan_fit(int bh, int bw, int S, int margin, int&
 }
 
 // launched with d alone this is the fit+write pass of abc_build_scan_images as it always was; launched with d and a scan_mask it
-// counts n over the ink of kept cells only
+// counts n over the ink of kept cells only; launched with d and a split_mask it writes canvas b from its page's source
 template <class... M>
 __global__ __launch_bounds__(STHR) void scan_write_kernel(const abc_scan_desc d, const M... mk) {
     constexpr bool MASKED = sizeof...(M) != 0;
@@ -311,7 +334,9 @@ __global__ __launch_bounds__(STHR) void scan_write_kernel(const abc_scan_desc d,
             if (rem >= (uint32_t)cols) { rem -= (uint32_t)cols; ++q; }
             xb[j] = x0 + (int)q - (rem == 0u ? 1 : 0);
         }
-        const uint8_t* src = d.src + (size_t)b * d.src_stride;
+        int sb = b;
+        if constexpr (MASKED) sb = mask_source(mask_of(mk...), b);
+        const uint8_t* src = d.src + (size_t)sb * d.src_stride;
         for (int yy = ya; yy <= yb; ++yy) {
             const uint64_t* row = (const uint64_t*)(src + (size_t)yy * d.src_pitch);
             int have = -1;                                    // the aligned 8-byte word whose ink bits `bits` holds
@@ -323,9 +348,8 @@ __global__ __launch_bounds__(STHR) void scan_write_kernel(const abc_scan_desc d,
                         const uint64_t t = row[w];
                         bits = ink_bits((uint32_t)t, thr, inv) | (ink_bits((uint32_t)(t >> 32), thr, inv) << 4);
                         if constexpr (MASKED) {      // (cells are multiples of 8 wide: an aligned 8-byte word lies in one cell)
-                            const scan_mask& k = mask_of(mk...);
-                            const uint8_t* kr = k.keep + (size_t)b * k.stride + (size_t)(yy >> k.shift) * k.cap_cw;
-                            if (!kr[(8 * w) >> k.shift]) bits = 0u;
+                            const auto& k = mask_of(mk...);
+                            if (!mask_keeps(k, b, sb, yy >> k.shift, (8 * w) >> k.shift)) bits = 0u;
                         }
                         have = w;
                     }
@@ -604,6 +628,250 @@ __global__ __launch_bounds__(DTHR) void clean_decide_kernel(const abc_scan_desc 
     }
 }
 
+// ---- abc_split_scan_pages: a page into its drawings, one canvas each.  Ten launches: zero, histogram, threshold, cells and flatten
+// are the kernels above, run over the pages with the per-page box words in the scratch; between and after them
+//   union      one thread per cell: an occupied cell unions with the occupied cells in the preceding half of its window
+//   rank       one workgroup per page: H, the keep rule per root, the kept roots' ranks in label order by a scan with a running
+//              carry over the grid in cell order, every cell's rank (-1: none), the page row, the page's list of taken roots
+//   pack       one workgroup: first and taken per page by a scan over the pages, total, the drawings rows, the canvases' box
+//              words reset, every cell's rank turned into its canvas
+//   box        grid as the histogram: min / max per canvas in an LDS table of the page's slots, then one atomic per touched word
+//   fit+write  scan_write_kernel over the D canvases with a split_mask
+constexpr int SPLIT_K = ABC_SCAN_SPLIT_MAX_PER_PAGE;
+
+// the split's slices of abc_scan_split_desc.scratch and its sizes, derived on the host once
+struct split_view {
+    clean_grid G;
+    int32_t* pbox;                 // [P][ABC_SCAN_NBOX]: the box words of the pages (abc_scan_desc.box is the canvases')
+    void* cells;                   // the clean_slice of every page
+    int32_t* canvas;               // [P][ncap]: after rank a cell's rank in its page, after pack its canvas
+    int32_t* list;                 // [P][SPLIT_K][2]: label and weight of the page's taken groups in order
+    int P, D, K, reach;
+};
+
+__host__ __device__ inline int64_t split_canvas_words(int64_t P, int64_t ncap) { return (P * ncap + 3) / 4 * 4; }
+
+__global__ __launch_bounds__(CTHR) void split_union_kernel(const abc_scan_desc d, const split_view W) {
+    const clean_grid& G = W.G;
+    const int b = blockIdx.y;
+    if (d.box[(size_t)b * ABC_SCAN_NBOX + BOX_STATUS] != 0) return;
+    const int c = blockIdx.x * CTHR + threadIdx.x;
+    if (c >= G.ncap) return;
+    const clean_view V = clean_slice(W.cells, b, G.ncap);
+    if (!V.ink[c]) return;
+    const int cy = c / G.cap_cw, cx = c - cy * G.cap_cw;
+    bool ok = true;
+    // the cells before c in cell order within Chebyshev distance reach: the rows above in full, this row to the left (the other
+    // half of the window is joined by its own cells).  No occupied cell stands for another here: that holds at reach 1 alone
+    for (int y = max(cy - W.reach, 0); y <= cy; ++y) {
+        const int xe = y < cy ? min(cx + W.reach, G.cap_cw - 1) : cx - 1;
+        for (int x = max(cx - W.reach, 0); x <= xe; ++x) {
+            const int n = y * G.cap_cw + x;
+            if (V.ink[n]) clean_unite(V.parent, c, n, G.ncap, ok);
+        }
+    }
+    if (!ok) atomicOr(&V.meta[META_FAIL], 1);
+}
+
+__global__ __launch_bounds__(DTHR) void split_rank_kernel(const abc_scan_desc d, const abc_scan_split_desc q, const split_view W) {
+    __shared__ int64_t red[DTHR / 64][5];
+    __shared__ unsigned wt[DTHR / 64 + 1];
+    const clean_grid& G = W.G;
+    const int p = blockIdx.x, t = threadIdx.x;
+    const int32_t* box = d.box + (size_t)p * ABC_SCAN_NBOX;
+    int32_t* row = q.pages + (size_t)p * ABC_SCAN_NPAGE;
+    int32_t* rank = W.canvas + (size_t)p * G.ncap;
+    int32_t* lab = q.labels_out ? q.labels_out + (size_t)p * G.ncap : nullptr;
+    const clean_view V = clean_slice(W.cells, p, G.ncap);
+    const int status = box[BOX_STATUS];
+    const bool failed = status == 0 && V.meta[META_FAIL] != 0;      // (uniform; a skipped page's scratch is not read)
+    if (status != 0 || failed) {                                     // no drawings: the status and zeros
+        if (t < ABC_SCAN_NPAGE) row[t] = t == ABC_SCAN_P_STATUS ? (failed ? ABC_SCAN_CLEAN_FAILED : status) : 0;
+        for (int c = t; c < G.ncap; c += DTHR) {
+            rank[c] = -1;
+            if (lab) lab[c] = -1;
+        }
+        return;
+    }
+    // the groups, the occupied cells and the heaviest weight
+    int64_t s[4] = {0, 0, 0, 0};
+    int H = 0;
+    for (int c = t; c < G.ncap; c += DTHR) {
+        if (!V.ink[c]) continue;
+        s[0] += 1;
+        if (V.parent[c] == c) { s[1] += 1; H = max(H, (int)V.weight[c]); }
+    }
+    clean_reduce(s, H, red);
+    // the kept roots in cell order, which is label order: a root's rank is the number of kept roots before it
+    int64_t u[4] = {0, 0, 0, 0};
+    int unused = 0;
+    unsigned carry = 0u;
+    int32_t* list = W.list + (size_t)p * SPLIT_K * 2;
+    for (int c0 = 0; c0 < G.ncap; c0 += DTHR) {
+        const int c = c0 + t;
+        bool keep = false;
+        int64_t w = 0;
+        if (c < G.ncap && V.ink[c] && V.parent[c] == c) {
+            w = (int64_t)V.weight[c];
+            keep = w >= (int64_t)q.min_ink && 256 * w >= (int64_t)q.keep_q8 * (int64_t)H;
+        }
+        unsigned tot;
+        const unsigned r = carry + block_excl_scan<DTHR>(keep ? 1u : 0u, wt, &tot);
+        carry += tot;
+        const bool taken = keep && r < (unsigned)W.K;
+        if (keep) u[0] += w;
+        if (taken) { list[2 * r] = c; list[2 * r + 1] = (int32_t)w; }
+        if (c < G.ncap) rank[c] = taken ? (int)r : -1;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // every other cell takes its root's rank (roots are written above and only read here)
+    for (int c = t; c < G.ncap; c += DTHR) {
+        const int label = V.ink[c] ? V.parent[c] : -1;
+        if (label >= 0 && label != c) rank[c] = rank[label];
+        if (lab) lab[c] = label;
+    }
+    clean_reduce(u, unused, red);
+    if (t == 0) {
+        const int kept = (int)carry;
+        row[ABC_SCAN_P_STATUS] = (kept == 0 ? ABC_SCAN_NO_COMPONENT : 0) | (kept > W.K ? ABC_SCAN_SPLIT_PAGE_FULL : 0);
+        row[ABC_SCAN_P_GROUPS] = (int)s[1];
+        row[ABC_SCAN_P_KEPT] = kept;
+        row[ABC_SCAN_P_FIRST] = 0;                                  // (pack's)
+        row[ABC_SCAN_P_TAKEN] = min(kept, W.K);                     // (what the page asks for: pack cuts it at D)
+        row[ABC_SCAN_P_INK_KEPT] = (int)u[0];
+        row[ABC_SCAN_P_INK_DROPPED] = box[BOX_INK] - (int)u[0];
+        row[ABC_SCAN_P_OCCUPIED] = (int)s[0];
+    }
+}
+
+__global__ __launch_bounds__(DTHR) void split_pack_kernel(const abc_scan_desc d, const abc_scan_split_desc q, const split_view W) {
+    __shared__ unsigned wt[DTHR / 64 + 1];
+    const clean_grid& G = W.G;
+    const int t = threadIdx.x;
+    // first and taken, page by page without holes
+    unsigned carry = 0u, truth = 0u;
+    for (int p0 = 0; p0 < W.P; p0 += DTHR) {
+        const int p = p0 + t;
+        int32_t* row = q.pages + (size_t)p * ABC_SCAN_NPAGE;
+        const unsigned want = p < W.P ? (unsigned)row[ABC_SCAN_P_TAKEN] : 0u;
+        const unsigned kept = p < W.P ? (unsigned)row[ABC_SCAN_P_KEPT] : 0u;
+        unsigned tot, tot_kept;
+        const unsigned before = carry + block_excl_scan<DTHR>(want, wt, &tot);
+        block_excl_scan<DTHR>(kept, wt, &tot_kept);
+        carry += tot;
+        truth += tot_kept;
+        if (p < W.P) {
+            const unsigned first = min(before, (unsigned)W.D), taken = min(want, (unsigned)W.D - first);
+            row[ABC_SCAN_P_FIRST] = (int)first;
+            row[ABC_SCAN_P_TAKEN] = (int)taken;
+            if (taken < want) row[ABC_SCAN_P_STATUS] |= ABC_SCAN_SPLIT_BATCH_FULL;
+        }
+    }
+    const int written = (int)min(carry, (unsigned)W.D);
+    if (t == 0) { q.total[0] = written; q.total[1] = (int)truth; }
+    __threadfence_block();
+    __syncthreads();
+    // the drawings rows and the canvases' box words: the taken groups, then the unused canvases
+    for (int64_t i = t; i < (int64_t)W.P * SPLIT_K; i += DTHR) {
+        const int p = (int)(i / SPLIT_K), r = (int)(i - (int64_t)p * SPLIT_K);
+        const int32_t* row = q.pages + (size_t)p * ABC_SCAN_NPAGE;
+        if (r >= row[ABC_SCAN_P_TAKEN]) continue;
+        const int j = row[ABC_SCAN_P_FIRST] + r;                    // < D
+        const int32_t* e = W.list + ((size_t)p * SPLIT_K + r) * 2;
+        const int32_t* pb = W.pbox + (size_t)p * ABC_SCAN_NBOX;
+        int32_t* dr = q.drawings + (size_t)j * ABC_SCAN_NDRAWING;
+        dr[ABC_SCAN_D_PAGE] = p; dr[ABC_SCAN_D_LABEL] = e[0]; dr[ABC_SCAN_D_WEIGHT] = e[1]; dr[ABC_SCAN_D_RANK] = r;
+        int32_t* box = d.box + (size_t)j * ABC_SCAN_NBOX;
+        box[BOX_Y0] = 0x7FFFFFFF; box[BOX_Y1] = -1; box[BOX_X0] = 0x7FFFFFFF; box[BOX_X1] = -1;
+        box[BOX_THR] = pb[BOX_THR]; box[BOX_INV] = pb[BOX_INV]; box[BOX_STATUS] = 0; box[BOX_INK] = e[1];
+    }
+    for (int j = written + t; j < W.D; j += DTHR) {
+        int32_t* dr = q.drawings + (size_t)j * ABC_SCAN_NDRAWING;
+        dr[ABC_SCAN_D_PAGE] = -1; dr[ABC_SCAN_D_LABEL] = -1; dr[ABC_SCAN_D_WEIGHT] = 0; dr[ABC_SCAN_D_RANK] = -1;
+        int32_t* box = d.box + (size_t)j * ABC_SCAN_NBOX;
+        box[BOX_Y0] = 0x7FFFFFFF; box[BOX_Y1] = -1; box[BOX_X0] = 0x7FFFFFFF; box[BOX_X1] = -1;
+        box[BOX_THR] = -1; box[BOX_INV] = 0; box[BOX_STATUS] = ABC_SCAN_NO_COMPONENT; box[BOX_INK] = 0;
+    }
+    // every cell's rank into its canvas
+    for (int p = 0; p < W.P; ++p) {
+        const int32_t* row = q.pages + (size_t)p * ABC_SCAN_NPAGE;
+        const int first = row[ABC_SCAN_P_FIRST], taken = row[ABC_SCAN_P_TAKEN];
+        int32_t* cv = W.canvas + (size_t)p * G.ncap;
+        int32_t* co = q.canvas_out ? q.canvas_out + (size_t)p * G.ncap : nullptr;
+        for (int c = t; c < G.ncap; c += DTHR) {
+            const int r = cv[c];
+            const int j = r >= 0 && r < taken ? first + r : -1;
+            cv[c] = j;
+            if (co) co[c] = j;
+        }
+    }
+}
+
+__global__ __launch_bounds__(STHR) void split_box_kernel(const abc_scan_desc d, const abc_scan_split_desc q, const split_view W) {
+    __shared__ int tab[SPLIT_K][4];                               // BOX_Y0 .. BOX_X1 of the page's slots (4 SPLIT_K <= STHR)
+    const clean_grid& G = W.G;
+    const int p = blockIdx.y;
+    const int32_t* row = q.pages + (size_t)p * ABC_SCAN_NPAGE;
+    const int first = row[ABC_SCAN_P_FIRST], taken = row[ABC_SCAN_P_TAKEN];
+    if (taken == 0) return;                                       // (uniform: also every page without drawings)
+    const int32_t* P = d.params + (size_t)p * ABC_SCAN_NPARAM;
+    const int sh = P[ABC_SCAN_SRC_H], sw = P[ABC_SCAN_SRC_W];
+    const int r0 = blockIdx.x * SCAN_ROWS;
+    if (r0 >= sh) return;
+    if (threadIdx.x < 4 * taken) tab[threadIdx.x >> 2][threadIdx.x & 3] = (threadIdx.x & 1) ? -1 : 0x7FFFFFFF;
+    __syncthreads();
+    const int nrow = min(SCAN_ROWS, sh - r0);
+    const int vpr = (sw + 15) >> 4;
+    const int32_t* pb = W.pbox + (size_t)p * ABC_SCAN_NBOX;
+    const int thr = pb[BOX_THR], inv = pb[BOX_INV];
+    const uint8_t* src = d.src + (size_t)p * d.src_stride;
+    const int32_t* cv = W.canvas + (size_t)p * G.ncap;
+    // a thread keeps the extent of the slot it met last and adds it to the table when the slot changes
+    int slot = -1, ymin = 0x7FFFFFFF, ymax = -1, xmin = 0x7FFFFFFF, xmax = -1;
+    auto flush = [&]() {
+        if (slot < 0) return;
+        atomicMin(&tab[slot][BOX_Y0], ymin); atomicMax(&tab[slot][BOX_Y1], ymax);
+        atomicMin(&tab[slot][BOX_X0], xmin); atomicMax(&tab[slot][BOX_X1], xmax);
+    };
+    // the ink bits m (bit i: column x + i) of row y belong to canvas j
+    auto add = [&](int j, uint32_t m, int y, int x) {
+        if (!m || j < 0) return;
+        const int sl = j - first;                                 // 0 .. taken - 1: a page's canvases are consecutive
+        if (sl != slot) { flush(); slot = sl; ymin = 0x7FFFFFFF; ymax = -1; xmin = 0x7FFFFFFF; xmax = -1; }
+        ymin = min(ymin, y); ymax = max(ymax, y);
+        xmin = min(xmin, x + (__ffs((int)m) - 1)); xmax = max(xmax, x + (31 - __clz((int)m)));
+    };
+    for (int i = threadIdx.x; i < nrow * vpr; i += STHR) {
+        const int y = i / vpr, v = i - y * vpr;
+        const u32x4 w = load_vec(src, d.src_pitch, r0 + y, v);
+        uint32_t m = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m |= ink_bits(w[k], thr, inv) << (4 * k);
+        const int valid = sw - 16 * v;      // >= 1
+        if (valid < 16) m &= (1u << valid) - 1u;
+        if (!m) continue;
+        // (a 16-byte vector lies in one cell, or at cell 8 in the two cells 2 v and 2 v + 1 < cap_cw = pitch / 8)
+        const int32_t* cr = cv + (size_t)((r0 + y) >> G.shift) * G.cap_cw;
+        if (G.shift == 3) {
+            add(cr[2 * v], m & 0xFFu, r0 + y, 16 * v);
+            add(cr[2 * v + 1], m >> 8, r0 + y, 16 * v + 8);
+        } else {
+            add(cr[(16 * v) >> G.shift], m, r0 + y, 16 * v);
+        }
+    }
+    flush();
+    __syncthreads();
+    if (threadIdx.x < 4 * taken) {
+        const int sl = threadIdx.x >> 2, w = threadIdx.x & 3;
+        if (tab[sl][BOX_Y1] >= 0) {                               // a slot this workgroup's rows touched
+            int32_t* box = d.box + (size_t)(first + sl) * ABC_SCAN_NBOX;
+            if (w & 1) atomicMax(&box[w], tab[sl][w]);
+            else atomicMin(&box[w], tab[sl][w]);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int abc_scan_desc_size(void) { return (int)sizeof(abc_scan_desc); }
@@ -693,4 +961,66 @@ extern "C" int abc_build_scan_images_clean(const abc_scan_desc* d, const abc_sca
     const int64_t per_img = (int64_t)d->S * d->S / VEC;
     hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)((per_img + STHR - 1) / STHR), (unsigned)d->B), dim3(STHR), 0, s, *d, k);
     return abc_check_launch("build_scan_images_clean");
+}
+
+extern "C" int abc_scan_split_desc_size(void) { return (int)sizeof(abc_scan_split_desc); }
+
+extern "C" int64_t abc_scan_split_scratch_bytes(int32_t P, int32_t src_max_h, int32_t src_pitch, int32_t cell, int32_t D) {
+    if (P < 1 || P > 65535 || D < 1 || D > 65535 || src_max_h < 1 || src_max_h > 4096 || src_pitch < 16 || src_pitch > 4096 ||
+        src_pitch % 16 || clean_shift(cell) < 0)
+        return abc_fail(ABC_EINVAL, "scan_split_scratch_bytes: P, D, src_max_h, src_pitch or cell outside abc_split_scan_pages' limits");
+    const int64_t ncap = (int64_t)((src_max_h + cell - 1) / cell) * ((src_pitch + cell - 1) / cell);
+    // the pages' box words, their cells, every cell's canvas, the pages' lists (the canvases' own words are d->box: D sizes nothing here)
+    return ((int64_t)P * ABC_SCAN_NBOX + (int64_t)P * clean_image_words(ncap) + split_canvas_words(P, ncap) + (int64_t)P * SPLIT_K * 2) * 4;
+}
+
+extern "C" int abc_split_scan_pages(const abc_scan_desc* d, const abc_scan_split_desc* q, abc_stream_t stream) {
+    if (const int rc = scan_guards(d)) return rc;
+    if (!q) return abc_fail(ABC_EINVAL, "split_scan_pages: null splitting descriptor");
+    const int shift = clean_shift(q->cell);
+    if (shift < 0) return abc_fail(ABC_EUNSUPPORTED, "split_scan_pages: cell must be 8, 16, 32 or 64");
+    if (q->canvases < 1 || q->canvases > 65535) return abc_fail(ABC_EINVAL, "split_scan_pages: canvases must be 1 .. 65535");
+    if (q->max_per_page < 1 || q->max_per_page > SPLIT_K) return abc_fail(ABC_EINVAL, "split_scan_pages: max_per_page must be 1 .. 64");
+    if (q->reach < 1 || q->reach > ABC_SCAN_SPLIT_MAX_REACH) return abc_fail(ABC_EINVAL, "split_scan_pages: reach must be 1 .. 4");
+    if (q->min_ink < 0) return abc_fail(ABC_EINVAL, "split_scan_pages: min_ink must be >= 0");
+    if (q->keep_q8 < 0 || q->keep_q8 > 256) return abc_fail(ABC_EINVAL, "split_scan_pages: keep_q8 must be 0 .. 256");
+    if (!q->scratch || !q->pages || !q->drawings || !q->total) return abc_fail(ABC_EINVAL, "split_scan_pages: null pointer");
+    if ((uintptr_t)q->scratch % 16) return abc_fail(ABC_EINVAL, "split_scan_pages: scratch must be 16-byte aligned");
+    if (((uintptr_t)q->pages | (uintptr_t)q->drawings | (uintptr_t)q->total | (uintptr_t)q->labels_out | (uintptr_t)q->canvas_out) % 4)
+        return abc_fail(ABC_EINVAL, "split_scan_pages: pages, drawings, total, labels_out and canvas_out must be 4-byte aligned");
+    split_view W;
+    W.G.shift = shift;
+    W.G.cap_ch = (d->src_max_h + q->cell - 1) >> shift;
+    W.G.cap_cw = (d->src_pitch + q->cell - 1) >> shift;
+    W.G.ncap = W.G.cap_ch * W.G.cap_cw;                        // <= 512 * 512
+    W.P = d->B; W.D = q->canvases; W.K = q->max_per_page; W.reach = q->reach;
+    W.pbox = (int32_t*)q->scratch;
+    int32_t* cells = W.pbox + (size_t)W.P * ABC_SCAN_NBOX;
+    W.cells = cells;
+    W.canvas = cells + (size_t)W.P * clean_image_words(W.G.ncap);
+    W.list = W.canvas + split_canvas_words(W.P, W.G.ncap);
+    abc_scan_desc pg = *d;                                       // the pages as the kernels above take images: their box words
+    pg.box = W.pbox;
+    abc_scan_clean_desc qc = {};                                 // (the cells and flatten kernels read the scratch alone)
+    qc.scratch = W.cells;
+    qc.cell = q->cell;
+    split_mask k;
+    k.canvas = W.canvas;
+    k.drawings = q->drawings;
+    k.ncap = W.G.ncap; k.cap_cw = W.G.cap_cw; k.shift = shift;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 chunks((unsigned)((d->src_max_h + SCAN_ROWS - 1) / SCAN_ROWS), (unsigned)W.P);
+    const dim3 cellgrid((unsigned)((W.G.ncap + CTHR - 1) / CTHR), (unsigned)W.P);
+    hipLaunchKernelGGL(scan_zero_kernel, dim3((unsigned)W.P), dim3(256), 0, s, pg.hist);
+    hipLaunchKernelGGL(scan_hist_kernel, chunks, dim3(STHR), 0, s, pg);
+    hipLaunchKernelGGL(scan_threshold_kernel, dim3((unsigned)W.P), dim3(256), 0, s, pg);
+    hipLaunchKernelGGL(clean_cells_kernel, chunks, dim3(STHR), 0, s, pg, qc, W.G);
+    hipLaunchKernelGGL(split_union_kernel, cellgrid, dim3(CTHR), 0, s, pg, W);
+    hipLaunchKernelGGL(clean_flatten_kernel, cellgrid, dim3(CTHR), 0, s, pg, qc, W.G);
+    hipLaunchKernelGGL(split_rank_kernel, dim3((unsigned)W.P), dim3(DTHR), 0, s, pg, *q, W);
+    hipLaunchKernelGGL(split_pack_kernel, dim3(1), dim3(DTHR), 0, s, *d, *q, W);
+    hipLaunchKernelGGL(split_box_kernel, chunks, dim3(STHR), 0, s, *d, *q, W);
+    const int64_t per_img = (int64_t)d->S * d->S / VEC;
+    hipLaunchKernelGGL(scan_write_kernel, dim3((unsigned)((per_img + STHR - 1) / STHR), (unsigned)W.D), dim3(STHR), 0, s, *d, k);
+    return abc_check_launch("split_scan_pages");
 }

@@ -707,6 +707,67 @@ int abc_scan_clean_desc_size(void);
 /* the bytes of abc_scan_clean_desc.scratch for these capacities; ABC_EINVAL (negative) when one of them is outside the limits above */
 int64_t abc_scan_clean_scratch_bytes(int32_t B, int32_t src_max_h, int32_t src_pitch, int32_t cell);
 
+/* A page scan into its drawings, one canvas each (csrc/scan.hip).  d is read as abc_build_scan_images_clean
+ * reads it, with d->B the number of pages P: src, params, params_host and hist are per page; out, geom and box are per canvas, and
+ * there are D = q->canvases of them (box: [D][ABC_SCAN_NBOX]).  Integers only, everything exact.  Threshold, polarity, ink, cells,
+ * ink(cy, cx), the capacity grid, the fit and the resample are those above, per page.
+ *   groups      two occupied cells belong together when their Chebyshev distance max(|dcy|, |dcx|) is at most reach (1 .. 4);
+ *               groups are the transitive closure.  reach = 1 is the 8-connected partition above.  A group's label is the smallest
+ *               cy cap_cw + cx among its cells, its weight the sum of ink over its cells; H is the largest weight of the page.
+ *   keep rule   per page, in 64 bits: weight >= min_ink and 256 weight >= keep_q8 H.
+ *   order       a page's kept groups in ascending label (the reading order of their first cells; labels are distinct: no tie-break).
+ *               A page takes its first min(kept, max_per_page) groups; a page with more gets ABC_SCAN_SPLIT_PAGE_FULL.  Canvases are
+ *               given page by page in that order without holes: first[p] = sum of taken[p'] for p' < p, taken[p] = what of the page's
+ *               groups fits below D; every page that lost one to D gets ABC_SCAN_SPLIT_BATCH_FULL.
+ *   canvas j    of page p and group g: the box over the ink pixels of p that lie in cells of g; the fit unchanged; the resample with
+ *               n counted over the ink in cells of g only, the area a unchanged.  Its geometry row: thr and inverted of the page,
+ *               status 0, box, fit and offsets as for any builder, ink = the weight of g.  A canvas j >= total[0] is blank (0.0)
+ *               and its row is thr = -1, status ABC_SCAN_NO_COMPONENT, zeros elsewhere.
+ *   total       int32 [2]: total[0] = the canvases written (<= D), total[1] = the kept groups of all pages (the true count).
+ *   drawings    int32 [D][ABC_SCAN_NDRAWING]: page, label, weight, rank_in_page; -1, -1, 0, -1 in an unused row.
+ *   pages       int32 [P][ABC_SCAN_NPAGE] (abc_scan_page_stat order): status, groups, kept (by the keep rule, before max_per_page
+ *               and D), first, taken, ink_kept (the ink of the kept groups), ink_dropped (the page's ink less ink_kept),
+ *               occupied_cells.  status is the page's abc_scan_status (ABC_SCAN_CONSTANT, ABC_SCAN_BAD_PARAMS; ABC_SCAN_NO_COMPONENT
+ *               when min_ink > H keeps nothing; ABC_SCAN_CLEAN_FAILED when a parent walk reached its bound) or-ed with the two
+ *               overflow bits.  A CONSTANT, BAD_PARAMS or CLEAN_FAILED page has no drawings and zeros in every other column but
+ *               first; it owns no canvas (so no NaN is written) and disturbs no other page.
+ *   labels_out  optional int32 [P][cap_ch][cap_cw]: an occupied cell's label, -1 elsewhere and on pages without drawings.
+ *   canvas_out  optional int32 of the same shape: the canvas a cell's ink goes to, -1 for none.
+ * Every word of out, geom, total, drawings, pages and the optional slices is written by every call.
+ * Ten launches on the stream, in order, whatever the pages hold: zero, histogram, threshold, cells, union (every occupied cell
+ * with the occupied cells in the preceding half of its (2 reach + 1)^2 window), flatten, rank (one workgroup per page: H, the keep
+ * rule, each kept group's rank in label order, the page row), pack (one workgroup: first, taken, total, drawings, each cell's
+ * canvas, the canvases' box words), box (per canvas), fit+write (per canvas).  No parallel branch (capturable), no sync, no
+ * allocation; scratch is the caller's, abc_scan_split_scratch_bytes of it, 16-byte aligned, and the sequence resets all it uses.
+ * Every guard of abc_build_scan_images applies (B to P); ABC_EUNSUPPORTED: cell outside 8 / 16 / 32 / 64; ABC_EINVAL: canvases
+ * outside 1 .. 65535, max_per_page outside 1 .. ABC_SCAN_SPLIT_MAX_PER_PAGE, reach outside 1 .. 4, min_ink < 0, keep_q8 outside
+ * 0 .. 256, a NULL scratch, pages, drawings or total, scratch not 16-byte aligned or a table not 4-byte aligned.  With params_host
+ * set a bad page is refused at call time (ABC_EINVAL) as above.  Nothing is launched after a refusal. */
+enum abc_scan_split_status { ABC_SCAN_SPLIT_PAGE_FULL = 16, ABC_SCAN_SPLIT_BATCH_FULL = 32 };      /* further page status bits */
+enum abc_scan_page_stat { ABC_SCAN_P_STATUS = 0, ABC_SCAN_P_GROUPS, ABC_SCAN_P_KEPT, ABC_SCAN_P_FIRST, ABC_SCAN_P_TAKEN,
+                          ABC_SCAN_P_INK_KEPT, ABC_SCAN_P_INK_DROPPED, ABC_SCAN_P_OCCUPIED, ABC_SCAN_NPAGE };
+enum abc_scan_drawing { ABC_SCAN_D_PAGE = 0, ABC_SCAN_D_LABEL, ABC_SCAN_D_WEIGHT, ABC_SCAN_D_RANK, ABC_SCAN_NDRAWING };
+enum { ABC_SCAN_SPLIT_MAX_PER_PAGE = 64, ABC_SCAN_SPLIT_MAX_REACH = 4 };
+typedef struct abc_scan_split_desc {
+    void* scratch;                  /* abc_scan_split_scratch_bytes(P, src_max_h, src_pitch, cell, canvases) bytes, 16-byte aligned */
+    int32_t* pages;                 /* out [P][ABC_SCAN_NPAGE] */
+    int32_t* drawings;              /* out [canvases][ABC_SCAN_NDRAWING] */
+    int32_t* total;                 /* out [2]: canvases written, kept groups of all pages */
+    int32_t* labels_out;            /* optional out [P][cap_ch][cap_cw] (NULL: not written) */
+    int32_t* canvas_out;            /* optional out [P][cap_ch][cap_cw] (NULL: not written) */
+    int32_t canvases;               /* D, 1 .. 65535 */
+    int32_t max_per_page;           /* K, 1 .. ABC_SCAN_SPLIT_MAX_PER_PAGE */
+    int32_t cell;                   /* 8, 16, 32 or 64 */
+    int32_t reach;                  /* 1 .. ABC_SCAN_SPLIT_MAX_REACH, in cells */
+    int32_t min_ink;                /* >= 0 */
+    int32_t keep_q8;                /* 0 .. 256 */
+} abc_scan_split_desc;
+int abc_split_scan_pages(const abc_scan_desc* d, const abc_scan_split_desc* q, abc_stream_t stream);
+/* sizeof(abc_scan_split_desc), for a binding's mirror struct (as abc_scan_desc_size) */
+int abc_scan_split_desc_size(void);
+/* the bytes of abc_scan_split_desc.scratch for these capacities; ABC_EINVAL (negative) when one of them is outside the limits above */
+int64_t abc_scan_split_scratch_bytes(int32_t P, int32_t src_max_h, int32_t src_pitch, int32_t cell, int32_t D);
+
 /* Stroke width of a binary drawing, normalised (csrc/stroke.hip): peel it toward its skeleton, then grow it
  * back to a chosen width.  The augmentation the reference leaves commented out (utils.py:65-71: sm.thin, then sm.dilation with
  * sm.disk(1)) as a device stage; synthetic._line's lines of 3 pixels are a one-pixel skeleton dilated by disk(1).
